@@ -52,6 +52,55 @@ def algorithmic_bytes(N, T, nnz1, its):
     }
 
 
+DUMP_SEED = 20241016      # --dump-outputs: the sample positions depend on this seed and the array lengths only
+DUMP_VALUES = 1 << 19     # sampled entries of each length-6N vector (x, F)
+DUMP_BLOCKS = 1 << 16     # sampled 4x4 blocks of J
+
+
+def _sample(n, k):
+    """Sorted positions of a fixed, seeded sample of k of n items (all of them when n <= k)."""
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+
+
+def _gather(ptr, n, width, idx, chunk_values=1 << 23):
+    """Rows idx (sorted) of the float64 device array [n][width] at ptr, read in chunks so the whole array never sits on the host."""
+    from dedflow_amd import api
+    rows = max(1, chunk_values // width)
+    out = np.empty((len(idx), width))
+    for s in range(0, n, rows):
+        e = min(n, s + rows)
+        lo, hi = np.searchsorted(idx, [s, e])
+        if lo < hi:
+            part = api.DeviceArray((e - s) * width, np.float64, ptr=ptr + s * width * 8).numpy().reshape(-1, width)
+            out[lo:hi] = part[idx[lo:hi] - s]
+    return out
+
+
+def dump_outputs(out_dir, P, x_d, F_d, its, r0, hist):
+    """What one step hands its caller -- solution x, residual F, matrix J (4x4 blocks over the 1x1 pattern, include/dedflow.h)
+    and the GMRES statistics -- as float64 .npy files.  x, F and J are fixed seeded samples (positions in *_index, J_row,
+    J_col), about 25 MB in all at any mesh size."""
+    from dedflow_amd import api
+    os.makedirs(out_dir, exist_ok=True)
+    save = lambda name, a: np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
+    for name, d in (("x", x_d), ("F", F_d)):
+        idx = _sample(d.n, DUMP_VALUES)
+        save(name, _gather(d.ptr, d.n, 1, idx)[:, 0])
+        save(name + "_index", idx)
+    bv = api.lib().MatrixFSBlockValues(P.J)   # asked again: the placement calibration may have moved the array
+    if not bv:
+        raise RuntimeError("--dump-outputs: J holds no 4x4 block array")
+    row_ptr, col_ind = P.pattern()
+    k = _sample(P.nnz1, DUMP_BLOCKS)
+    save("J_blocks", _gather(bv, P.nnz1, 16, k))
+    save("J_row", np.searchsorted(row_ptr, k, side="right") - 1)
+    save("J_col", col_ind[k])
+    save("residual_history", hist)
+    save("solve_stats", [its, r0])
+
+
 def cpu_model():
     try:
         for line in open("/proc/cpuinfo"):
@@ -151,7 +200,13 @@ def main():
     ap.add_argument("--solve-to-rtol", type=int, default=1, help="also time one PC_ILU0 solve to rtol 1e-4 after the timed steps (0 = skip)")
     ap.add_argument("--coupled-M", type=int, default=55, help="fluid mesh of the coupled fluid + DEM step leg (0 = skip)")
     ap.add_argument("--dem-particles", type=int, default=100000, help="DEM contact sweep leg after the timed step (0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (x, F, samples "
+                                                          "of J, GMRES history) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.gpus > 1 or os.environ.get("DFL_FORCE_DIST") == "1"):
+        ap.error("--dump-outputs is only written by the single-rank run (--gpus 1)")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -248,6 +303,8 @@ def main():
     t_total = time.perf_counter() - t0
     ms_per_step = 1e3 * t_total / args.steps
     solve_ms_timed = float(np.mean(solve_ms[-args.steps:]))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, P, x_d, F_d, it, r0, hist)
     # what the Krylov work-space calibration measured and chose in the first warm-up solve ("SpMV placement":
     # the in-loop SpMV time is a property of where the value array and the basis landed; this is the record of that draw)
     placement_log = (L.DflKrylovCalibrationLog() or b"").decode(errors="replace").strip().split("\n")
