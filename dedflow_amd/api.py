@@ -242,10 +242,19 @@ class Particles:
         lib().ParticleContextDestroy(self.ctx)
 
 
-PC_DECOMPOSITION, PC_ILU0, PC_TWOLEVEL = 0x2, 0x5, 0x6   # PCType values (include/dedflow.h)
+PC_DECOMPOSITION, PC_AMGX, PC_ILU0, PC_TWOLEVEL = 0x2, 0x3, 0x5, 0x6   # PCType values (include/dedflow.h)
 ALLREDUCE_FN = C.CFUNCTYPE(None, vp, vp, C.c_int32)
 HALO_FN = C.CFUNCTYPE(None, vp, vp)
 STREAM_FN = C.CFUNCTYPE(vp, vp)
+
+
+class DflAMGXConfig(C.Structure):
+    _fields_ = [("relaxation_factor", C.c_double), ("selector_passes", C.c_int32), ("smoother", C.c_int32),
+                ("presweeps", C.c_int32), ("postsweeps", C.c_int32), ("max_levels", C.c_int32),
+                ("min_coarse_rows", C.c_int32), ("max_iters", C.c_int32), ("unknown_keys", C.c_int32)]
+
+
+AMGX_SMOOTHER_DILU, AMGX_SMOOTHER_JACOBI = 0, 1
 
 
 class DflComm(C.Structure):
@@ -298,6 +307,12 @@ def _declare(L):
     f("KrylovSetFlexible", None, [vp, i32]); f("KrylovSetMesh", None, [vp, C.POINTER(Mesh3D)]); f("KrylovSetAggregateSize", None, [vp, i32])
     f("PCTwoLevelInfo", None, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_int64)]); f("PCTwoLevelAggregates", vp, [vp])
     f("PCTwoLevelCoarseMatrix", C.POINTER(Matrix), [vp]); f("PCTwoLevelSetInner", None, [vp, i32, f64])
+    f("PCCreateAMGX", vp, [C.POINTER(Matrix), vp]); f("PCAMGXRebuild", None, [vp]); f("PCAMGXNumLevels", i32, [vp])
+    f("PCAMGXInfo", None, [vp, vp, vp, vp, C.POINTER(f64), C.POINTER(i32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)])
+    f("PCAMGXLevelAggregates", vp, [vp, i32]); f("PCAMGXLevelColors", vp, [vp, i32])
+    f("PCAMGXLevelMatrix", C.POINTER(Matrix), [vp, i32]); f("PCAMGXCoarsePivots", vp, [vp])
+    f("DflAMGXParseConfig", C.c_int, [C.c_char_p, C.POINTER(DflAMGXConfig)])
+    f("DflAMGXAggregateHost", i32, [i32, vp, vp, vp, C.c_int, vp]); f("KrylovSetAMGXConfig", None, [vp, C.c_char_p])
     f("AssembleSystemTet", None, [C.POINTER(Mesh3D), vp, vp, vp, C.POINTER(Matrix)])
     f("AssembleSystemTetFace", None, [C.POINTER(Mesh3D), vp, vp, vp, C.POINTER(Matrix)])
     f("AssembleSystem", None, [C.POINTER(Mesh3D), vp, vp, vp, C.POINTER(Matrix), vp, i32])

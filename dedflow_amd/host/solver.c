@@ -193,11 +193,6 @@ PC* PCCreateDecomposition(Matrix* mat, index_type n_sec, const index_type* offse
     return pc;
 }
 
-PC* PCCreateAMGX(Matrix* mat, void* options) {
-    UNUSED(mat);
-    UNUSED(options);
-    return NULL;
-}
 void PCApply(PC* pc, f64* x, f64* y) { pc->op->apply(pc, x, y); }
 void PCSetup(PC* pc) { pc->op->setup(pc); }
 void PCDestroy(PC* pc) {
@@ -246,6 +241,15 @@ void KrylovSetRestart(Krylov* k, index_type m) { kext(k)->restart = m; }
 void KrylovSetFlexible(Krylov* k, b32 on) {
     kext(k)->flexible = on;
     kext(k)->flexible_user = on;
+}
+void KrylovSetAMGXConfig(Krylov* k, const char* options) {
+    KrylovExt* x = kext(k);
+    free(x->amgx_cfg);
+    x->amgx_cfg = options ? strdup(options) : NULL;
+    if (x->pc_type == PC_AMGX) { /* rebuilt with the new configuration at the next KrylovSolve */
+        PCDestroy((PC*)k->pc);
+        k->pc = NULL;
+    }
 }
 void KrylovSetMesh(Krylov* k, const Mesh3D* mesh) { kext(k)->mesh = mesh; }
 void KrylovSetAggregateSize(Krylov* k, index_type nodes) { kext(k)->agg_size = nodes; }
@@ -385,6 +389,15 @@ void DflPcApplyFused(PC* pc, index_type na, f64* w, const f64* d_nrm, f64* z) {
         return;
     }
     if (d_nrm) dfl_dscal_inv_dev(na, d_nrm, w, DflStream());
+    if (pc && pc->type == PC_DECOMPOSITION) {
+        /* a tree with AMG on A11: the sections inside the active length only (phi / T lie beyond [0,4N) when b's tail is 0) */
+        PCDecomposition* d = (PCDecomposition*)pc->data;
+        if (d->n_sec == 4 && d->pc[1] && d->pc[1]->type == PC_AMGX) {
+            for (index_type i = 0; i < d->n_sec; ++i)
+                if (d->offset[i] < na) PCApply(d->pc[i], w + d->offset[i], z + d->offset[i]);
+            return;
+        }
+    }
     if (pc && pc->type == PC_ILU0) PCDILUSetActiveLength(pc, na);
     if (pc && pc->type == PC_TWOLEVEL) PCTwoLevelSetActiveLength(pc, na);
     if (pc) PCApply(pc, w, z);
@@ -1036,6 +1049,7 @@ void KrylovDestroy(Krylov* ksp) {
         HIPGUARD(hipEventDestroy(kext(ksp)->ev_h));
         HIPGUARD(hipStreamDestroy(kext(ksp)->red_stream));
     }
+    free(kext(ksp)->amgx_cfg);
     CdamFreeHost(ksp->ext, SIZE_OF(KrylovExt));
     CdamFreeHost(ksp, SIZE_OF(Krylov));
 }
@@ -1066,8 +1080,25 @@ PC* DflKrylovBuildPC(Krylov* ksp, Matrix* A) {
             DflWsVecFreeAs(kx->Z, kx->ws_pooled);
             kx->Z = NULL;
         }
+        /* PC_AMGX: the reference's tree with AMG on the pressure block (krylov.c:450), or AMG on a plain CSR matrix.  Refused
+           with a communicator (no partitioned AMG; a property of the setup, so every rank falls back alike) */
+        PC* amg = NULL;
+        const b32 fs_tree = A->type == MAT_TYPE_FS && ((MatrixFS*)A->data)->n_offset >= 4;
+        if (!two_level && kx->pc_type == PC_AMGX) {
+            if (kx->has_comm) {
+                /* no partitioned AMG */
+            } else if (fs_tree) {
+                MatrixFS* fs = (MatrixFS*)A->data;
+                amg = PCCreateAMGX(fs->mat[1 * fs->n_offset + 1], kx->amgx_cfg);
+            } else if (A->type == MAT_TYPE_CSR) amg = PCCreateAMGX(A, kx->amgx_cfg);
+            if (!amg)
+                fprintf(stderr, "KrylovSolve: PC_AMGX unavailable %s, using %s\n", kx->has_comm ? "with a communicator" : "for this matrix",
+                        fs_tree ? "the reference's Jacobi tree" : "no preconditioner");
+        }
         if (two_level) {
             /* built above */
+        } else if (amg && !fs_tree) {
+            pc = amg;
         } else if ((kx->pc_type == PC_ILU0 || kx->pc_type == PC_TWOLEVEL) && MatrixFSBlockValues(A)) {
             pc = PCCreateDILU(A);
         } else if (A->type == MAT_TYPE_FS && ((MatrixFS*)A->data)->n_offset >= 4) {
@@ -1078,7 +1109,7 @@ PC* DflKrylovBuildPC(Krylov* ksp, Matrix* A) {
             Matrix* A11 = fs->mat[1 * fs->n_offset + 1];
             pc = PCCreateDecomposition(A, 4, offset, ksp->handle);
             ((PCDecomposition*)pc->data)->pc[0] = PCCreateJacobi(A00, 3, ksp->handle);
-            ((PCDecomposition*)pc->data)->pc[1] = PCCreateJacobi(A11, 1, ksp->handle);
+            ((PCDecomposition*)pc->data)->pc[1] = amg ? amg : PCCreateJacobi(A11, 1, ksp->handle);
             ((PCDecomposition*)pc->data)->pc[2] = PCCreateNone(NULL, n);
             ((PCDecomposition*)pc->data)->pc[3] = PCCreateNone(NULL, n);
         } else {

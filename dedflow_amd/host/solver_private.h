@@ -40,6 +40,7 @@ typedef struct KrylovExt {
     hipStream_t red_stream;
     hipEvent_t ev_w, ev_h;
     b32 no_calibration; /* inner / coarse solvers of PC_TWOLEVEL: never time basis placements (DflKrylovMarkInner) */
+    char* amgx_cfg;     /* KrylovSetAMGXConfig: options of PCCreateAMGX (NULL: the reference configuration) */
 } KrylovExt;
 
 

@@ -379,7 +379,39 @@ typedef struct PCDecomposition { index_type n_sec; index_type* offset; PC** pc; 
 PC* PCCreateNone(Matrix* mat, index_type n);
 PC* PCCreateJacobi(Matrix* mat, index_type bs, void* handle);
 PC* PCCreateDecomposition(Matrix* mat, index_type n, const index_type* offset, void* handle);
-PC* PCCreateAMGX(Matrix* mat, void* options); /* returns NULL: NVIDIA-only external library (pc.c:300-304) */
+/* PC_AMGX (host/pc_amgx.c, csrc/k_amgx.hip): a native scalar AMG in place of the NVIDIA AMGX library the reference links
+ * (pc.c:160-235, 279-295): pairwise aggregation (SIZE_2/4/8), piecewise-constant P, Galerkin P^T A P, multicolour-DILU or
+ * Jacobi smoothing, dense LU on the coarsest level (zero pivots skipped: singular coarsest matrices such as the Neumann
+ * pressure block are fine), V-cycles from a zero initial guess.  `mat`: a MAT_TYPE_CSR matrix with its own values, or the
+ * A11 view fs->mat[n_offset+1] of a block-mode (u,p) MatrixFS on one GPU.  `options`: NULL (the reference configuration of
+ * krylov.c:413-437), an inline AMGX string "config_version=2, solver:preconditioner:smoother=..., ..." or the path of a file
+ * holding that string or AMGX's JSON form.  Structure is built here from the current values; PCSetup recomputes every value,
+ * PCAMGXRebuild the structure.  Returns NULL (with a message on stderr) for an unsupported matrix or option value.
+ * The V-cycle is a fixed linear operator: plain (non-flexible) GMRES. */
+PC* PCCreateAMGX(Matrix* mat, void* options);
+typedef struct DflAMGXConfig {
+    f64 relaxation_factor;
+    int32_t selector_passes; /* SIZE_2 / SIZE_4 / SIZE_8: 1 / 2 / 3 pairwise passes per level */
+    int32_t smoother;        /* DFL_AMGX_SMOOTHER_* */
+    int32_t presweeps, postsweeps, max_levels, min_coarse_rows, max_iters;
+    int32_t unknown_keys;    /* keys that were listed on stderr and ignored */
+} DflAMGXConfig;
+enum { DFL_AMGX_SMOOTHER_DILU = 0, DFL_AMGX_SMOOTHER_JACOBI = 1 };
+int DflAMGXParseConfig(const char* options, DflAMGXConfig* cfg); /* host only; 0 = accepted */
+/* host only: the aggregates PCCreateAMGX forms on a host CSR matrix (columns ascending) with `passes` pairwise passes;
+ * agg_out[n]; returns the number of aggregates */
+index_type DflAMGXAggregateHost(index_type n, const index_type* rp, const index_type* ci, const f64* val, int passes,
+                                index_type* agg_out);
+void PCAMGXRebuild(PC* pc);
+index_type PCAMGXNumLevels(PC* pc);
+/* per level (arrays of PCAMGXNumLevels entries, any may be NULL): rows, nonzeros, colours; operator complexity; the first
+ * level of the one-workgroup tail; kernel launches of the last PCApply and the last PCSetup */
+void PCAMGXInfo(PC* pc, index_type* rows, index_type* nnz, index_type* colors, f64* op_complexity, index_type* tail_level,
+                int64_t* launches_apply, int64_t* launches_setup);
+const index_type* PCAMGXLevelAggregates(PC* pc, index_type level); /* device [n_level]: row -> next-level row; NULL on the coarsest */
+const index_type* PCAMGXLevelColors(PC* pc, index_type level);     /* device [n_level] */
+Matrix* PCAMGXLevelMatrix(PC* pc, index_type level); /* MAT_TYPE_CSR over the level's values (current after PCSetup); owned by the PC */
+const index_type* PCAMGXCoarsePivots(PC* pc); /* device [2 n_coarsest]: the LU's row exchanges, then 1 for pivots taken as zero */
 /* PC_ILU0: multicolor block-DILU on the block-mode (u,p) matrix (host/pc_dilu.c, csrc/k_dilu.hip); build-defined:
  * the reference's PCType ends at PC_CUSTOM = 0x4 (pc.h:15-21); 0x5 and 0x6 are this build's additions.  KrylovSetPCType(ksp, PC_ILU0) makes KrylovSolve build it instead
  * of the reference's Jacobi tree (PC_DECOMPOSITION = the reference default). */
@@ -443,7 +475,12 @@ const KrylovStats* KrylovGetStats(const Krylov* krylov);
 /* 0: GMRES tests convergence every 20 iterations like the reference (krylov.c:281-290); k>0: every k */
 void KrylovSetCheckInterval(Krylov* krylov, index_type k);
 void KrylovSetVerbose(Krylov* krylov, b32 verbose);
-void KrylovSetPCType(Krylov* krylov, PCType type); /* PC_DECOMPOSITION (default, reference tree), PC_ILU0 or PC_TWOLEVEL */
+/* PC_DECOMPOSITION (default, reference tree), PC_ILU0, PC_TWOLEVEL or PC_AMGX.  PC_AMGX: on a (u,p) MatrixFS the reference
+ * tree with pc[1] = PCCreateAMGX(A11, cfg) (the commented line krylov.c:450), on a MAT_TYPE_CSR matrix PCCreateAMGX(A, cfg);
+ * cfg from KrylovSetAMGXConfig.  With a communicator, or when PCCreateAMGX returns NULL, the solver says so and builds what
+ * it builds without PC_AMGX. */
+void KrylovSetPCType(Krylov* krylov, PCType type);
+void KrylovSetAMGXConfig(Krylov* krylov, const char* options); /* copied; NULL = the reference configuration */
 PC* KrylovGetPC(const Krylov* krylov);
 /* off by default: the norm of the orthogonalised vector from w.w - sum h_j^2, so that a partitioned Arnoldi step needs ONE
  * all-reduce (h and w.w together) instead of two and, with the Jacobi tree on <= 500k rows, ONE launch for update + Givens

@@ -444,6 +444,47 @@ void dfl_amg_prolong_add(dfl_index N, const dfl_index* agg, dfl_index Nc, const 
 void dfl_amg_prolong_add_rows(dfl_index nrows, dfl_index N, const dfl_index* agg, dfl_index Nc, const dfl_value* xc, dfl_value* z,
                               void* stream);
 
+/* ---- PC_AMGX: scalar pairwise-aggregation AMG V-cycle (csrc/k_amgx.hip, host/pc_amgx.c).  One level of the hierarchy as
+ * the kernels see it; every pointer is device memory, the structure is built on the host (PCCreateAMGX).
+ *   rows[coff[c] .. coff[c+1])   the rows of colour c (greedy colouring in row order)
+ *   diag[i]                      position of a_ii;  trans[k] position of a_ji for a_ij = val[k] (-1: not stored)
+ *   agg[n] / aoff[nc+1], amem[n] the map to the next level (nc rows) and the members of every next-level row, ascending
+ *   goff[nnz+1], gidx            this level's nonzero k = sum of the previous level's val[gidx[goff[k] .. goff[k+1])]
+ *   einv                         1/E (DILU) or 1/a_ii (Jacobi); b, x, w: right-hand side, iterate, sweep scratch
+ *   lu[n*n], piv[n], zpiv[n]     coarsest level only: the dense LU, its row exchanges, the pivots that count as zero */
+typedef struct dfl_amgx_level {
+    dfl_index n, nnz, ncolor, nc;
+    const dfl_index *rp, *ci, *diag, *trans, *color, *rows, *coff;
+    const dfl_index *agg, *aoff, *amem, *goff, *gidx;
+    dfl_value *val, *einv, *b, *x, *w;
+    dfl_value* lu;
+    dfl_index *piv, *zpiv;
+} dfl_amgx_level;
+/* the (3,3) entry of every 4x4 block: the pressure sub-matrix A11 of the block-mode (u,p) matrix as a compact scalar array */
+void dfl_amgx_gather_a11(dfl_index nnz, const dfl_value* block_val, dfl_value* val, void* stream);
+/* setup on one grid level: Galerkin sums of level c from the values vf of the level above; DILU E^-1 of the rows of colour
+ * `color` = rows[s0 .. s0+cnt) (colours in ascending order, one launch each); Jacobi 1/a_ii */
+void dfl_amgx_galerkin(dfl_amgx_level c, const dfl_value* vf, void* stream);
+void dfl_amgx_dilu_setup_color(dfl_amgx_level L, dfl_index color, dfl_index s0, dfl_index cnt, void* stream);
+void dfl_amgx_jacobi_setup(dfl_amgx_level L, void* stream);
+/* one smoothing step x <- x + omega S^-1 (b - A x) on one grid level.  DILU: forward colour kernels (ascending) compute
+ * w = (E+L)^-1 (b - A x) with the residual in the same row walk, backward kernels (descending) w = (E+U)^-1 E w and
+ * x += omega w.  Jacobi: w = x + omega D^-1 (b - A x) in one launch (the caller swaps x and w).  x_zero: x is zero, not read */
+void dfl_amgx_dilu_forward(dfl_amgx_level L, dfl_index color, dfl_index s0, dfl_index cnt, int x_zero, void* stream);
+void dfl_amgx_dilu_backward(dfl_amgx_level L, dfl_index color, dfl_index s0, dfl_index cnt, dfl_value omega, int x_zero,
+                            void* stream);
+void dfl_amgx_jacobi_sweep(dfl_amgx_level L, dfl_value omega, int x_zero, void* stream);
+/* c.b = P^T (L.b - L.A L.x) (x_zero: P^T L.b);  L.x (+)= P c.x;  t = r - A z on level L */
+void dfl_amgx_restrict(dfl_amgx_level L, dfl_amgx_level c, int x_zero, void* stream);
+void dfl_amgx_prolong(dfl_amgx_level L, const dfl_value* xc, int x_zero, void* stream);
+void dfl_amgx_residual(dfl_amgx_level L, const dfl_value* r, const dfl_value* z, dfl_value* t, void* stream);
+/* the tail: levels [l0, nlev) of the device array `levels` in ONE launch of one 1024-thread workgroup, phases separated by
+ * __syncthreads.  tail_setup: Galerkin sums of levels max(l0,1) .. nlev-1, their smoother data, the dense LU of the coarsest.
+ * tail_cycle: the V-cycle from level l0 down and back (b0 / x0 / w0 replace level l0's b / x / w) */
+void dfl_amgx_tail_setup(const dfl_amgx_level* levels, dfl_index l0, dfl_index nlev, int jacobi, void* stream);
+void dfl_amgx_tail_cycle(const dfl_amgx_level* levels, dfl_index l0, dfl_index nlev, int jacobi, int presweeps, int postsweeps,
+                         dfl_value omega, const dfl_value* b0, dfl_value* x0, dfl_value* w0, void* stream);
+
 /* ---- DEM contact sweep (build-defined; the reference's Particle.c holds storage only)
  *  model: monodisperse spheres, linear spring-dashpot normal contact F = (kn*overlap - gamma_n*vn) n between
  *  particles and against the six walls of the unit box; uniform cell list with cell edge >= 2R:
