@@ -233,6 +233,41 @@ class Particles:
     def update(self):
         lib().ParticleContextUpdate(self.ctx)
 
+    # ---- particle-fluid coupling (build-defined; model in include/dedflow.h) --------------------------------------
+    def couple(self, problem, rho_f=1e3, mu_f=10.0 / 3.0, gravity=(0.0, 0.0, 0.0), two_way=False):
+        """ParticleContextSetFluidCoupling with problem's mesh; problem None turns the coupling off."""
+        if problem is None:
+            lib().ParticleContextSetFluidCoupling(self.ctx, None, None)
+            self.N = 0
+            return
+        cfg = DflFluidCoupling(rho_f, mu_f, (C.c_double * 3)(*gravity), 1 if two_way else 0)
+        lib().ParticleContextSetFluidCoupling(self.ctx, problem.mesh, C.byref(cfg))
+        self.N = problem.N
+
+    def locate(self):
+        lib().ParticleContextLocate(self.ctx)
+
+    def tet(self):
+        """tet of every particle (-1 outside the mesh, -2 walk cap hit)"""
+        return d2h(lib().ParticleContextTet(self.ctx), self.P, np.int32)
+
+    def barycentric(self):
+        return d2h(lib().ParticleContextBarycentric(self.ctx), 4 * self.P, np.float64).reshape(self.P, 4)
+
+    def lost_count(self):
+        return int(lib().ParticleContextLostCount(self.ctx))
+
+    def fluid_step(self, w):
+        """one coupled sub-step in the fluid state w (DeviceArray of 6N)"""
+        lib().ParticleContextFluidStep(self.ctx, w.ptr)
+
+    def reaction_load(self, out=None):
+        """ParticleContextReactionLoad into `out` (DeviceArray of 3N, allocated when None); returns the DeviceArray"""
+        if out is None:
+            out = DeviceArray(3 * self.N)
+        lib().ParticleContextReactionLoad(self.ctx, out.ptr)
+        return out
+
     def arrays(self):
         """(coord, vel, acc) copied back from the device"""
         c = self.ctx.contents
@@ -240,6 +275,10 @@ class Particles:
 
     def close(self):
         lib().ParticleContextDestroy(self.ctx)
+
+
+class DflFluidCoupling(C.Structure):
+    _fields_ = [("rho_f", C.c_double), ("mu_f", C.c_double), ("gravity", C.c_double * 3), ("two_way", C.c_int32)]
 
 
 PC_DECOMPOSITION, PC_AMGX, PC_ILU0, PC_TWOLEVEL = 0x2, 0x3, 0x5, 0x6   # PCType values (include/dedflow.h)
@@ -331,6 +370,11 @@ def _declare(L):
     f("ParticleContextUpdateDevice", None, [C.POINTER(ParticleContext)]); f("ParticleContextUpdateHost", None, [C.POINTER(ParticleContext)])
     f("ParticleContextSetContactModel", None, [C.POINTER(ParticleContext), f64, f64, f64])
     f("ParticleContextComputeForces", None, [C.POINTER(ParticleContext)]); f("ParticleContextUpdate", None, [C.POINTER(ParticleContext)])
+    f("ParticleContextSetFluidCoupling", None, [C.POINTER(ParticleContext), C.POINTER(Mesh3D), C.POINTER(DflFluidCoupling)])
+    f("ParticleContextLocate", None, [C.POINTER(ParticleContext)]); f("ParticleContextTet", vp, [C.POINTER(ParticleContext)])
+    f("ParticleContextBarycentric", vp, [C.POINTER(ParticleContext)]); f("ParticleContextLostCount", i32, [C.POINTER(ParticleContext)])
+    f("ParticleContextFluidStep", None, [C.POINTER(ParticleContext), vp]); f("ParticleContextReactionLoad", None, [C.POINTER(ParticleContext), vp])
+    f("DflMeshSetExternalLoad", None, [C.POINTER(Mesh3D), vp])
     f("SolveFlowSystem", i32, [C.POINTER(Mesh3D), vp, vp, vp, C.POINTER(Matrix), vp, vp, vp, vp, i32, i32, vp, vp])
     f("DflTimeStep", i32, [C.POINTER(Mesh3D), vp, vp, vp, C.POINTER(Matrix), vp, vp, vp, vp, i32, i32, C.POINTER(ParticleContext),
                            i32, vp, vp])
@@ -438,6 +482,11 @@ class Problem:
 
     def assemble_face(self, wg, dwg, F=None, want_J=False):
         lib().AssembleSystemTetFace(self.mesh, wg.ptr, dwg.ptr, F.ptr if F is not None else None, self.J if want_J else None)
+
+    def set_external_load(self, load):
+        """DflMeshSetExternalLoad: a DeviceArray of 3N (kept alive here while registered), or None"""
+        self._ext_load = load
+        lib().DflMeshSetExternalLoad(self.mesh, load.ptr if load is not None else None)
 
     def matvec(self, x, y):
         lib().MatrixMatVec(self.J, x.ptr, y.ptr)

@@ -47,6 +47,8 @@ void DflSetWeakBCGroup(index_type group) { g_asm.face_group = group; }
 void DflMeshSetAssemblySchedule(Mesh3D* mesh, int mode) { ((MeshExt*)mesh->ext)->cfg.sched_mode = mode; }
 void DflMeshSetWeakBCGroup(Mesh3D* mesh, index_type group) { ((MeshExt*)mesh->ext)->cfg.face_group = group; }
 void DflSetQuiet(b32 quiet) { g_quiet = quiet; }
+void DflMeshSetExternalLoad(Mesh3D* mesh, const f64* load) { ((MeshExt*)mesh->ext)->ext_load = load; }
+const f64* DflMeshExternalLoad(const Mesh3D* mesh) { return ((const MeshExt*)mesh->ext)->ext_load; }
 /* node coordinates were modified (moving mesh): drop the per-element geometry cache, rebuilt at the next assembly */
 void DflMeshGeometryChanged(Mesh3D* mesh) {
     MeshExt* x = (MeshExt*)mesh->ext;
@@ -293,6 +295,9 @@ void DflAssembleSystemPrepacked(Mesh3D* mesh, f64* wgalpha, f64* dwgalpha, f64* 
         DflAssembleSystemTetBeta(mesh, wgalpha, dwgalpha, F, J, overwrite ? 0.0 : 1.0);
         AssembleSystemTetFace(mesh, wgalpha, dwgalpha, F, J);
     }
+    /* external force on the momentum equations (particle reaction, include/dedflow.h): R = (...) - f_ext, after the tet and
+       face terms and before the Dirichlet rows */
+    if (F && x->ext_load) dfl_daxpy(3 * num_node, -1.0, x->ext_load, F, s);
     x->nodep_current = FALSE;
     if (F) HIPGUARD(hipMemsetAsync(F + 4 * (size_t)num_node, 0, (size_t)num_node * sizeof(f64) * 2, s)); /* main.c:63-66 */
     for (index_type ibc = 0; ibc < nbc; ++ibc) {

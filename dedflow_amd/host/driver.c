@@ -122,7 +122,10 @@ index_type SolveFlowSystem(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matr
     return iter;
 }
 
-/* one time step of main.c:537-565: predictor, Newton solve, corrector; optional DEM sub-steps */
+/* one time step of main.c:537-565: predictor, Newton solve, corrector; optional DEM sub-steps.  A particle context coupled
+ * to this mesh (ParticleContextSetFluidCoupling) instead takes `dem_substeps` fluid sub-steps after the corrector, in the
+ * fluid state of the new time level; with two_way, the Newton solve sees the reaction load of the previous step's
+ * sub-steps as an external load. */
 index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* J, f64* F, f64* dx, Krylov* ksp, Dirichlet** bcs,
                        index_type nbc, index_type newton_maxit, ParticleContext* pctx, index_type dem_substeps, f64* rnorm_out,
                        f64* rnorm_init_out) {
@@ -130,12 +133,26 @@ index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* 
     hipStream_t s = DflStream();
     const f64 fac_pred = (kGAMMA - 1.0) / kGAMMA;
     const f64 fac_corr[] = {kDT * (1.0 - kGAMMA), kDT * kGAMMA};
+    const b32 coupled = pctx && DflParticleCoupledMesh(pctx) == mesh;
+    if (coupled && KrylovGetComm(ksp)) {
+        fprintf(stderr, "DflTimeStep: particle-fluid coupling is single-GPU only; the solver has a communicator: step refused\n");
+        return -1;
+    }
     DflRangePush("DflTimeStep");
+    const f64* user_load = DflMeshExternalLoad(mesh);
+    const f64* reaction = coupled && DflParticleTwoWay(pctx) ? DflParticlePendingLoad(pctx) : NULL;
+    if (reaction) {
+        ASSERT(!user_load && "DflTimeStep: a two-way coupled step cannot add to an external load already registered");
+        DflMeshSetExternalLoad(mesh, reaction);
+    }
     dfl_alpha_predict(N, fac_pred, dwg, s);
     index_type it = SolveFlowSystem(mesh, wgold, dwgold, dwg, J, F, dx, ksp, bcs, nbc, newton_maxit, rnorm_out, rnorm_init_out);
-    if (pctx)
+    if (reaction) DflMeshSetExternalLoad(mesh, user_load);
+    if (pctx && !coupled)
         for (index_type k = 0; k < dem_substeps; ++k) ParticleContextUpdate(pctx); /* coupled step: contact sweep (config 4) */
     dfl_alpha_correct(N, fac_corr[0], fac_corr[1], wgold, dwgold, dwg, s);
+    if (coupled)
+        for (index_type k = 0; k < dem_substeps; ++k) ParticleContextFluidStep(pctx, wgold); /* u at t_{n+1} */
     DflRangePop();
     return it;
 }

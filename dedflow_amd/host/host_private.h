@@ -113,6 +113,7 @@ typedef struct MeshExt {
     RowPatchSched* rowpatch;       /* LHS row-owner patch schedule (mode 3), built on first use */
     PatchSched* patch;             /* LHS patch schedule (assembly schedule mode 2), built on first use */
     SlotPatchSched* slotpatch;     /* LHS slot-owner schedule (mode 4, default), built on first use */
+    const f64* ext_load;           /* device [3N] external load on the momentum rows (DflMeshSetExternalLoad), NULL: none */
 } MeshExt;
 
 void DflMeshPrepareFaces(Mesh3D* mesh, index_type group);
@@ -121,6 +122,27 @@ void DflMeshFreeFaceLists(struct MeshExt* x);
 /* AssembleSystemTet with J = beta_J * J + contributions (beta_J = 0 only takes effect in schedules 3 and 4) */
 void DflAssembleSystemTetBeta(Mesh3D* mesh, f64* wgalpha, f64* dwgalpha, f64* F, Matrix* J, f64 beta_J);
 b32 DflQuiet(void);
+
+/* workspace of a ParticleContext (ctx->ext): the contact sweep (host/particle.c) and the fluid coupling (host/couple.c) */
+typedef struct ParticleExt {
+    f64 kn, gamma_n, dt;
+    f64 cell;
+    index_type ncell;
+    /* persistent workspace of the sweep (device): nothing is allocated, freed or synchronised per sweep */
+    index_type *cell_of, *rank, *slot, *order;  /* [P] */
+    index_type *count, *cell_start, *chunk_sum; /* [ncell^3 + 1], [ncell^3 + 1], [chunks] */
+    f64* sorted;                                /* [P][6] position + velocity in (cell, id) order */
+    index_type cap_particle, cap_cell;
+    struct CoupleState* couple;                 /* particle-fluid coupling (host/couple.c), NULL when off */
+} ParticleExt;
+struct CoupleState;
+void DflCoupleFree(struct CoupleState* c);
+/* the mesh a particle context is coupled to (NULL: uncoupled), its two-way switch, and the reaction load of the sub-steps
+ * since the last ParticleContextReactionLoad into the context's own [3N] buffer (NULL when there were none) */
+Mesh3D* DflParticleCoupledMesh(const ParticleContext* ctx);
+b32 DflParticleTwoWay(const ParticleContext* ctx);
+f64* DflParticlePendingLoad(ParticleContext* ctx);
+const f64* DflMeshExternalLoad(const Mesh3D* mesh);
 
 /* profiling tags (runtime.c) */
 enum { DFL_TAG_SPMV = 0, DFL_TAG_CGS_DOTS = 1, DFL_TAG_CGS_UPDATE = 2, DFL_TAG_PC = 3, DFL_TAG_ASM_LHS = 4,

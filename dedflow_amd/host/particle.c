@@ -9,17 +9,6 @@
 #include "dedflow_kernels.h"
 #include "host_private.h"
 
-typedef struct ParticleExt {
-    f64 kn, gamma_n, dt;
-    f64 cell;
-    index_type ncell;
-    /* persistent workspace of the sweep (device): nothing is allocated, freed or synchronised per sweep */
-    index_type *cell_of, *rank, *slot, *order;  /* [P] */
-    index_type *count, *cell_start, *chunk_sum; /* [ncell^3 + 1], [ncell^3 + 1], [chunks] */
-    f64* sorted;                                /* [P][6] position + velocity in (cell, id) order */
-    index_type cap_particle, cap_cell;
-} ParticleExt;
-
 ParticleContext* ParticleContextCreate(index_type num_particle) {
     ParticleContext* ctx = (ParticleContext*)CdamMallocHost(SIZE_OF(ParticleContext));
     memset(ctx, 0, sizeof *ctx);
@@ -50,6 +39,7 @@ void ParticleContextDestroy(ParticleContext* ctx) {
     if (x) {
         CdamFreeDevice(x->cell_of, 0); CdamFreeDevice(x->rank, 0); CdamFreeDevice(x->slot, 0); CdamFreeDevice(x->order, 0); CdamFreeDevice(x->sorted, 0);
         CdamFreeDevice(x->count, 0); CdamFreeDevice(x->cell_start, 0); CdamFreeDevice(x->chunk_sum, 0);
+        DflCoupleFree(x->couple);
         CdamFreeHost(x, SIZE_OF(ParticleExt));
     }
     CdamFreeHost(ctx, SIZE_OF(ParticleContext));

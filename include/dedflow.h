@@ -704,6 +704,50 @@ void ParticleContextRemove(ParticleContext* ctx);
 void ParticleContextSetContactModel(ParticleContext* ctx, f64 kn, f64 gamma_n, f64 dt);
 void ParticleContextComputeForces(ParticleContext* ctx); /* acc <- contact forces / mass */
 
+/* ---- particle-fluid coupling (build-defined: the reference has the hooks, not the physics) -------------------------
+ * Opt-in; a context that is never coupled behaves exactly as without this section.
+ *   location   every particle is located on the tet mesh by a walk over the tet neighbour table, starting from its tet
+ *              of the previous call (or from a uniform seed grid over the mesh's bounding box when it has none).  The
+ *              result is the tet (-1: outside the mesh, -2: the walk hit its cap of DFL_COUPLE_MAX_WALK steps; such a
+ *              particle is counted by ParticleContextLostCount) and the barycentric coordinates lambda[4] (min >= -1e-12).
+ *              "Outside" means the walk stood in a tet whose only faces with lambda < -1e-12 are boundary faces: exact
+ *              for CONVEX domains; in a non-convex domain a particle may be reported outside wrongly.
+ *   drag       u_f = sum_a lambda_a u(node_a) (u = the first 3N entries of the 6N state), d = 2R,
+ *              rho_p = m / (4/3 pi R^3), Re = rho_f |u_f - v| d / mu_f, Schiller-Naumann f = 1 + 0.15 Re^0.687 (Re <= 1000)
+ *              or 0.44 Re / 24, tau = rho_p d^2 / (18 mu_f).  Implicit in v with f lagged (stable for any dt / tau):
+ *                v' = (v + dt (a_contact + (1 - rho_f/rho_p) g + f u_f / tau)) / (1 + dt f / tau),  x' = x + dt v'
+ *              acc <- (v' - v) / dt; the drag impulse m f (u_f - v') / tau dt is accumulated per particle.  A particle
+ *              outside the mesh feels gravity only (no buoyancy, no drag).
+ *   reaction   load[3a + d] = -sum_p lambda_{a,p} impulse_p[d] / (time since the last call): the force of the particles
+ *              on the fluid at node a, with the particles' latest lambda (a particle outside the mesh at that moment
+ *              contributes nothing).  Summed in a fixed order (no float atomics): bitwise reproducible; sum_a load =
+ *              -sum_p impulse_p / dt to rounding.
+ *   two-way    DflMeshSetExternalLoad registers such a force on a mesh; the assembly of F subtracts it from the momentum
+ *              rows (the residual is R = (...) - f_ext: body forces enter with a minus sign, as kRHO * fb does) after the tet
+ *              and face terms and before the Dirichlet rows, which therefore stay exact.  The coupling is explicit (not
+ *              in J).  DflTimeStep registers the reaction load of the previous step's sub-steps for its Newton solve.
+ * Defaults: rho_f = 1e3, mu_f = 10/3 (the reference's kRHO and kMU), g = 0, two_way off.  One GPU only: DflTimeStep
+ * refuses a coupled context when the solver has a communicator.  Nothing is allocated or synchronised per call except
+ * by ParticleContextLostCount (one 4-byte read). */
+typedef struct DflFluidCoupling {
+    f64 rho_f, mu_f, gravity[3];
+    b32 two_way;
+} DflFluidCoupling;
+/* couple to `mesh` (builds the neighbour table, sorted V2E lists and seed grid once per mesh; resets every particle's tet
+ * to "none", the impulses and the lost count); cfg NULL = defaults; mesh NULL = coupling off (frees its state) */
+void ParticleContextSetFluidCoupling(ParticleContext* ctx, Mesh3D* mesh, const DflFluidCoupling* cfg);
+void ParticleContextLocate(ParticleContext* ctx);
+const index_type* ParticleContextTet(const ParticleContext* ctx);        /* device [P] */
+const f64* ParticleContextBarycentric(const ParticleContext* ctx);       /* device [P][4] */
+index_type ParticleContextLostCount(const ParticleContext* ctx);        /* walks that hit the cap since coupling was set */
+/* one coupled sub-step with the fluid state w (device, 6N): contact forces, locate, drag + gravity + integration (dt of
+ * ParticleContextSetContactModel) */
+void ParticleContextFluidStep(ParticleContext* ctx, const f64* w);
+/* load (device, 3N) <- the reaction load of the sub-steps since the last call (zero when there were none); resets them */
+void ParticleContextReactionLoad(ParticleContext* ctx, f64* load);
+/* device [3N] external force on the momentum equations (NULL = none); the array must outlive its registration */
+void DflMeshSetExternalLoad(Mesh3D* mesh, const f64* load);
+
 #ifdef __cplusplus
 }
 #endif

@@ -503,6 +503,34 @@ void dfl_dem_forces(dfl_index P, const dfl_value* sorted, dfl_value radius, dfl_
                     dfl_value cell, dfl_index ncell, const dfl_index* order, const dfl_index* cell_start, dfl_value* acc,
                     void* stream);
 
+/* ---- particle-fluid coupling (build-defined, csrc/k_couple.hip; model in include/dedflow.h)
+ *    dfl_couple_sort_v2e      every V2E list ascending (one thread per node)
+ *    dfl_couple_neighbours    nbr[4t + k] = tet across the face opposite local vertex k, -1 on the boundary
+ *    dfl_couple_locate        walk of every particle from tet[i] (or the seed-grid tet when tet[i] < 0); writes tet[i]
+ *                             (-1 outside, -2 walk cap hit: *lost += 1) and lambda[i][4]; `order` (may be NULL) = the
+ *                             thread -> particle map
+ *    dfl_couple_fluid_step    drag + gravity + integration of every particle; imp[i][3] += drag impulse
+ *    dfl_couple_sort_by_tet   members[tstart[t] .. tstart[t+1]) = the particles in tet t, ascending id; tcount[T] is
+ *                             zero-initialised scratch that the call leaves zeroed again
+ *    dfl_couple_node_load     load[3a + d] = -scale * sum_{e in V2E(a)} sum_{p in e} lambda_{p,k(a,e)} imp[p][d] */
+#define DFL_COUPLE_MAX_WALK 4096
+void dfl_couple_sort_v2e(dfl_index N, const dfl_index* vrow, dfl_index* vcol, void* stream);
+void dfl_couple_neighbours(dfl_index T, const dfl_index* ien, const dfl_index* vrow, const dfl_index* vcol, dfl_index* nbr,
+                           void* stream);
+void dfl_couple_locate(dfl_index P, const dfl_index* order, const dfl_value* coord, const dfl_value* xg, const dfl_index* ien,
+                       const dfl_index* nbr, const dfl_index* seed, const dfl_value* grid_lo, const dfl_value* grid_inv_h,
+                       dfl_index grid_dim, dfl_index* tet, dfl_value* lambda, dfl_index* lost, void* stream);
+void dfl_couple_fluid_step(dfl_index P, const dfl_index* order, const dfl_index* tet, const dfl_value* lambda,
+                           const dfl_index* ien, const dfl_value* w, dfl_value mass, dfl_value radius, dfl_value rho_f,
+                           dfl_value mu_f, const dfl_value* gravity, dfl_value dt, dfl_value* coord, dfl_value* vel,
+                           dfl_value* acc, dfl_value* imp, void* stream);
+void dfl_couple_sort_by_tet(dfl_index P, dfl_index T, const dfl_index* tet, dfl_index* tcount, dfl_index* rank,
+                            dfl_index* tstart, dfl_index* slot, dfl_index* members, void* scan_temp, int64_t scan_temp_bytes,
+                            void* stream);
+void dfl_couple_node_load(dfl_index N, const dfl_index* vrow, const dfl_index* vcol, const dfl_index* ien,
+                          const dfl_index* tstart, const dfl_index* members, const dfl_value* lambda, const dfl_value* imp,
+                          dfl_value scale, dfl_value* load, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
