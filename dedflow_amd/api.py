@@ -268,6 +268,21 @@ class Particles:
         lib().ParticleContextReactionLoad(self.ctx, out.ptr)
         return out
 
+    # ---- walls from a mesh's boundary faces (build-defined; model in include/dedflow.h) ----------------------------
+    def set_walls(self, problem, groups=range(6)):
+        """ParticleContextSetWallMesh: the boundary faces of `groups` of problem's mesh become the walls (the other groups
+        are open); problem None returns to the unit box."""
+        if problem is None:
+            lib().ParticleContextSetWallMesh(self.ctx, None, 0)
+            return
+        mask = 0
+        for g in groups:
+            mask |= 1 << int(g)
+        lib().ParticleContextSetWallMesh(self.ctx, problem.mesh, mask)
+
+    def wall_dropped_count(self):
+        return int(lib().ParticleContextWallDroppedCount(self.ctx))
+
     def arrays(self):
         """(coord, vel, acc) copied back from the device"""
         c = self.ctx.contents
@@ -374,6 +389,8 @@ def _declare(L):
     f("ParticleContextLocate", None, [C.POINTER(ParticleContext)]); f("ParticleContextTet", vp, [C.POINTER(ParticleContext)])
     f("ParticleContextBarycentric", vp, [C.POINTER(ParticleContext)]); f("ParticleContextLostCount", i32, [C.POINTER(ParticleContext)])
     f("ParticleContextFluidStep", None, [C.POINTER(ParticleContext), vp]); f("ParticleContextReactionLoad", None, [C.POINTER(ParticleContext), vp])
+    f("ParticleContextSetWallMesh", None, [C.POINTER(ParticleContext), C.POINTER(Mesh3D), i32])
+    f("ParticleContextWallDroppedCount", i32, [C.POINTER(ParticleContext)])
     f("DflMeshSetExternalLoad", None, [C.POINTER(Mesh3D), vp])
     f("SolveFlowSystem", i32, [C.POINTER(Mesh3D), vp, vp, vp, C.POINTER(Matrix), vp, vp, vp, vp, i32, i32, vp, vp])
     f("DflTimeStep", i32, [C.POINTER(Mesh3D), vp, vp, vp, C.POINTER(Matrix), vp, vp, vp, vp, i32, i32, C.POINTER(ParticleContext),

@@ -197,17 +197,24 @@ extern "C" {
 I dfl_dem_num_chunks(I ncell3) { return (I)(((long long)ncell3 + 1 + SCAN_CHUNK - 1) / SCAN_CHUNK); }
 
 // count[ncell3 + 1] must be zero on entry (it is again on return); chunk_sum[dfl_dem_num_chunks] and slot[P] are scratch
+// chunk / scan / place / sort after a bin pass that left cell_of, rank and count[nbin] (the wall sweep, k_walls.hip, bins
+// with its own kernel)
+void dfl_dem_sort_binned(I P, I nbin, const T* coord, const T* vel, I* cell_of, I* rank, I* count, I* chunk_sum, I* cell_start,
+                         I* slot, I* order, T* sorted, void* stream) {
+    const I nchunk = dfl_dem_num_chunks(nbin);
+    dem_chunk_sum_kernel<<<nchunk, BLK, 0, S(stream)>>>(nbin, count, chunk_sum);
+    dem_scan_kernel<<<nchunk, BLK, 0, S(stream)>>>(nbin, count, chunk_sum, cell_start);
+    dem_place_kernel<<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, cell_of, rank, cell_start, slot);
+    dem_sort_cells_kernel<<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, cell_of, cell_start, slot, order, coord, vel, sorted);
+    DFL_LAUNCH_CHECK();
+}
+
 void dfl_dem_build_cells(I P, const T* coord, const T* vel, T cell, I ncell, I* cell_of, I* rank, I* count, I* chunk_sum,
                          I* cell_start, I* slot, I* order, T* sorted, void* stream) {
     if (P <= 0) return;
     const I ncell3 = ncell * ncell * ncell;
-    const I nchunk = dfl_dem_num_chunks(ncell3);
     dem_bin_kernel<<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, coord, 1.0 / cell, ncell, cell_of, rank, count);
-    dem_chunk_sum_kernel<<<nchunk, BLK, 0, S(stream)>>>(ncell3, count, chunk_sum);
-    dem_scan_kernel<<<nchunk, BLK, 0, S(stream)>>>(ncell3, count, chunk_sum, cell_start);
-    dem_place_kernel<<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, cell_of, rank, cell_start, slot);
-    dem_sort_cells_kernel<<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, cell_of, cell_start, slot, order, coord, vel, sorted);
-    DFL_LAUNCH_CHECK();
+    dfl_dem_sort_binned(P, ncell3, coord, vel, cell_of, rank, count, chunk_sum, cell_start, slot, order, sorted, stream);
 }
 
 void dfl_dem_forces(I P, const T* sorted, T radius, T mass, T kn, T gamma_n, T cell, I ncell, const I* order, const I* cell_start,

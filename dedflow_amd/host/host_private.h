@@ -134,9 +134,16 @@ typedef struct ParticleExt {
     f64* sorted;                                /* [P][6] position + velocity in (cell, id) order */
     index_type cap_particle, cap_cell;
     struct CoupleState* couple;                 /* particle-fluid coupling (host/couple.c), NULL when off */
+    struct WallState* walls;                    /* mesh walls (host/walls.c), NULL: the unit box */
 } ParticleExt;
+/* the sweep's device workspace for P particles over nbin cell-list bins (count / cell_start [nbin + 1]); grows only */
+void DflDemReserve(ParticleExt* x, index_type P, index_type nbin);
 struct CoupleState;
 void DflCoupleFree(struct CoupleState* c);
+struct WallState;
+void DflWallsFree(struct WallState* w);
+/* the contact sweep against the mesh walls (ParticleContextComputeForces when walls are set) */
+void DflWallsComputeForces(ParticleContext* ctx);
 /* the mesh a particle context is coupled to (NULL: uncoupled), its two-way switch, and the reaction load of the sub-steps
  * since the last ParticleContextReactionLoad into the context's own [3N] buffer (NULL when there were none) */
 Mesh3D* DflParticleCoupledMesh(const ParticleContext* ctx);

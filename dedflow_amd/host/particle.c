@@ -2,7 +2,8 @@
  * (coord / vel / acc, host + device, mass 1.0, radius 0.1 hard-coded, Particle.c:8-26) and
  * empty Add/Update/Remove hooks (:120-130).  The contact sweep is build-defined
  * (dedflow_amd/csrc/k_dem.hip): ParticleContextComputeForces = cell list + force kernel,
- * ParticleContextUpdate = forces + semi-implicit Euler step. */
+ * ParticleContextUpdate = forces + semi-implicit Euler step.  With walls from a mesh (ParticleContextSetWallMesh) the sweep
+ * runs in host/walls.c instead. */
 #include <math.h>
 #include <string.h>
 #include "dedflow.h"
@@ -40,6 +41,7 @@ void ParticleContextDestroy(ParticleContext* ctx) {
         CdamFreeDevice(x->cell_of, 0); CdamFreeDevice(x->rank, 0); CdamFreeDevice(x->slot, 0); CdamFreeDevice(x->order, 0); CdamFreeDevice(x->sorted, 0);
         CdamFreeDevice(x->count, 0); CdamFreeDevice(x->cell_start, 0); CdamFreeDevice(x->chunk_sum, 0);
         DflCoupleFree(x->couple);
+        DflWallsFree(x->walls);
         CdamFreeHost(x, SIZE_OF(ParticleExt));
     }
     CdamFreeHost(ctx, SIZE_OF(ParticleContext));
@@ -68,8 +70,31 @@ void ParticleContextSetContactModel(ParticleContext* ctx, f64 kn, f64 gamma_n, f
     x->dt = dt;
 }
 
+void DflDemReserve(ParticleExt* x, index_type P, index_type nbin) {
+    if (x->cap_particle < P) {
+        CdamFreeDevice(x->cell_of, 0); CdamFreeDevice(x->rank, 0); CdamFreeDevice(x->slot, 0); CdamFreeDevice(x->order, 0); CdamFreeDevice(x->sorted, 0);
+        x->cell_of = (index_type*)CdamMallocDevice((ptrdiff_t)P * SIZE_OF(index_type));
+        x->rank = (index_type*)CdamMallocDevice((ptrdiff_t)P * SIZE_OF(index_type));
+        x->slot = (index_type*)CdamMallocDevice((ptrdiff_t)P * SIZE_OF(index_type));
+        x->order = (index_type*)CdamMallocDevice((ptrdiff_t)P * SIZE_OF(index_type));
+        x->sorted = (f64*)CdamMallocDevice((ptrdiff_t)P * 6 * SIZE_OF(f64));
+        x->cap_particle = P;
+    }
+    if (x->cap_cell < nbin + 1) { /* zero-filled by the allocator; every sweep leaves count / chunk_sum zeroed again */
+        CdamFreeDevice(x->count, 0); CdamFreeDevice(x->cell_start, 0); CdamFreeDevice(x->chunk_sum, 0);
+        x->count = (index_type*)CdamMallocDevice(((ptrdiff_t)nbin + 1) * SIZE_OF(index_type));
+        x->cell_start = (index_type*)CdamMallocDevice(((ptrdiff_t)nbin + 1) * SIZE_OF(index_type));
+        x->chunk_sum = (index_type*)CdamMallocDevice((ptrdiff_t)dfl_dem_num_chunks(nbin) * SIZE_OF(index_type));
+        x->cap_cell = nbin + 1;
+    }
+}
+
 void ParticleContextComputeForces(ParticleContext* ctx) {
     ParticleExt* x = (ParticleExt*)ctx->ext;
+    if (x->walls) {
+        DflWallsComputeForces(ctx);
+        return;
+    }
     const index_type P = ctx->num_particle;
     const f64 R = ParticleRadius(ctx);
     hipStream_t s = DflStream();
@@ -84,22 +109,7 @@ void ParticleContextComputeForces(ParticleContext* ctx) {
     if (ncell > 256) ncell = 256; /* 2^24 cells at most (the dense cell arrays) */
     const f64 cell = 1.0 / (f64)ncell; /* >= 4R */
     const index_type ncell3 = ncell * ncell * ncell;
-    if (x->cap_particle < P) {
-        CdamFreeDevice(x->cell_of, 0); CdamFreeDevice(x->rank, 0); CdamFreeDevice(x->slot, 0); CdamFreeDevice(x->order, 0); CdamFreeDevice(x->sorted, 0);
-        x->cell_of = (index_type*)CdamMallocDevice((ptrdiff_t)P * SIZE_OF(index_type));
-        x->rank = (index_type*)CdamMallocDevice((ptrdiff_t)P * SIZE_OF(index_type));
-        x->slot = (index_type*)CdamMallocDevice((ptrdiff_t)P * SIZE_OF(index_type));
-        x->order = (index_type*)CdamMallocDevice((ptrdiff_t)P * SIZE_OF(index_type));
-        x->sorted = (f64*)CdamMallocDevice((ptrdiff_t)P * 6 * SIZE_OF(f64));
-        x->cap_particle = P;
-    }
-    if (x->cap_cell < ncell3 + 1) { /* zero-filled by the allocator; every sweep leaves count / chunk_sum zeroed again */
-        CdamFreeDevice(x->count, 0); CdamFreeDevice(x->cell_start, 0); CdamFreeDevice(x->chunk_sum, 0);
-        x->count = (index_type*)CdamMallocDevice(((ptrdiff_t)ncell3 + 1) * SIZE_OF(index_type));
-        x->cell_start = (index_type*)CdamMallocDevice(((ptrdiff_t)ncell3 + 1) * SIZE_OF(index_type));
-        x->chunk_sum = (index_type*)CdamMallocDevice((ptrdiff_t)dfl_dem_num_chunks(ncell3) * SIZE_OF(index_type));
-        x->cap_cell = ncell3 + 1;
-    }
+    DflDemReserve(x, P, ncell3);
     x->cell = cell;
     x->ncell = ncell;
     const f64* coord = ArrayData(ParticleCTXDeviceCoord(ctx));

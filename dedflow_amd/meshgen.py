@@ -195,3 +195,73 @@ def fan_mesh(num_surface: int = 40, seed: int = 5) -> TetMesh:
                    bound_elem_offset=np.array([0] + [nf] * 6, np.int32),
                    bound_ien=np.ascontiguousarray(tets[:, 1:].reshape(-1).astype(np.int32)),
                    bound_f2e=np.arange(nf, dtype=np.int32), bound_forn=np.zeros(nf, np.int32))
+
+
+def kuhn_box(M, lo, hi, keep=None) -> TetMesh:
+    """Kuhn tets (6 per cell, as kuhn_cube) on the axis-aligned box [lo, hi] with M cells per axis (an int, or one per
+    axis).  keep(i, j, k) -> bool drops whole cells (e.g. a quadrant for an L-shape); nodes no kept cell uses are removed
+    and the others renumbered in order.  Boundary groups are re-derived from the exposed tet faces by outward normal, in the
+    order x-, x+, y-, y+, z-, z+ (faces of a group by parent tet, then local face); forn / f2e as in kuhn_cube."""
+    Ms = np.broadcast_to(np.asarray(M, dtype=np.int64), (3,))
+    lo, hi = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
+    n1 = Ms + 1
+    strides = (1, int(n1[0]), int(n1[0] * n1[1]))
+    ids = np.arange(int(np.prod(n1)), dtype=np.int64)
+    ijk = np.stack([ids % n1[0], (ids // n1[0]) % n1[1], ids // (n1[0] * n1[1])], axis=1)
+    xg = lo[None, :] + (hi - lo)[None, :] * (ijk / Ms[None, :])
+
+    c = np.arange(int(np.prod(Ms)), dtype=np.int64)
+    ci, cj, ck = c % Ms[0], (c // Ms[0]) % Ms[1], c // (Ms[0] * Ms[1])
+    if keep is not None:
+        mask = np.array([bool(keep(int(a), int(b), int(d))) for a, b, d in zip(ci, cj, ck)], dtype=bool)
+        ci, cj, ck = ci[mask], cj[mask], ck[mask]
+    base = ci + strides[1] * cj + strides[2] * ck
+    ien = np.empty((base.size, 6, 4), dtype=np.int64)
+    for t, p in enumerate(_PERMS):
+        v0 = base
+        v1 = v0 + strides[p[0]]
+        v2 = v1 + strides[p[1]]
+        v3 = v2 + strides[p[2]]
+        if _perm_is_odd(p):
+            v1, v2 = v2, v1
+        ien[:, t, 0], ien[:, t, 1], ien[:, t, 2], ien[:, t, 3] = v0, v1, v2, v3
+    ien = ien.reshape(-1, 4)
+    used = np.unique(ien)
+    renum = np.full(ids.size, -1, dtype=np.int64)
+    renum[used] = np.arange(used.size)
+    ien = renum[ien]
+    xg = xg[used]
+
+    # exposed faces: (tet, local face opposite vertex k) whose sorted node triple occurs once
+    faces = np.stack([np.sort(np.delete(ien, k, axis=1), axis=1) for k in range(4)], axis=1).reshape(-1, 3)
+    _, inv, cnt = np.unique(faces, axis=0, return_inverse=True, return_counts=True)
+    exposed = np.nonzero(cnt[inv.reshape(-1)] == 1)[0]
+    tet, opp = exposed // 4, exposed % 4
+    fn = np.stack([np.delete(ien[t], k) for t, k in zip(tet, opp)]) if exposed.size else np.zeros((0, 3), np.int64)
+    x = xg[fn]
+    nrm = np.cross(x[:, 1] - x[:, 0], x[:, 2] - x[:, 0])   # axis-aligned: every exposed face lies on a cell face
+    axis = np.argmax(np.abs(nrm), axis=1)
+    away = x[:, 0] - xg[ien[tet, opp]]                      # from the opposite vertex towards the face: outward
+    side = (away[np.arange(axis.size), axis] > 0).astype(np.int64)
+    group = 2 * axis + side
+    node_off, elem_off, nodes, bien, f2e, forn = [0], [0], [], [], [], []
+    for g in range(6):
+        sel = np.nonzero(group == g)[0]
+        sel = sel[np.lexsort((opp[sel], tet[sel]))]
+        nodes.append(np.unique(fn[sel]))
+        bien.append(fn[sel].reshape(-1))
+        f2e.append(tet[sel])
+        forn.append(opp[sel])
+        node_off.append(node_off[-1] + nodes[-1].size)
+        elem_off.append(elem_off[-1] + sel.size)
+    return TetMesh(
+        M=int(Ms.max()),
+        xg=np.ascontiguousarray(xg.reshape(-1)),
+        ien=np.ascontiguousarray(ien.reshape(-1).astype(np.int32)),
+        bound_node_offset=np.asarray(node_off, dtype=np.int32),
+        bound_node=np.concatenate(nodes).astype(np.int32),
+        bound_elem_offset=np.asarray(elem_off, dtype=np.int32),
+        bound_ien=np.concatenate(bien).astype(np.int32),
+        bound_f2e=np.concatenate(f2e).astype(np.int32),
+        bound_forn=np.concatenate(forn).astype(np.int32),
+    )

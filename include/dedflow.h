@@ -748,6 +748,48 @@ void ParticleContextReactionLoad(ParticleContext* ctx, f64* load);
 /* device [3N] external force on the momentum equations (NULL = none); the array must outlive its registration */
 void DflMeshSetExternalLoad(Mesh3D* mesh, const f64* load);
 
+/* ---- particle walls from a mesh's boundary faces (build-defined; opt-in) ----------------------------------------------
+ * A context that never calls ParticleContextSetWallMesh keeps the six walls of the unit box and its contact grid over
+ * [0,1]^3, bit for bit.  With walls set, every contact sweep (ParticleContextComputeForces, hence ParticleContextUpdate,
+ * ParticleContextFluidStep and the DEM sub-steps of DflTimeStep) collides the particles with the wall triangles instead:
+ *   walls      the boundary faces of the groups whose bit is set in group_mask; the other groups are open (inlet, outlet):
+ *              particles cross them freely.  Normal n_t of a triangle t = the unit normal towards the opposite vertex of
+ *              its tet (into the fluid).
+ *   law        the linear spring-dashpot law of the particle pairs, no clamping of negative f:
+ *                f = kn delta - gamma_n (v . n),  F += f n
+ *              for centre c, triangle t (vertex a), s = (c - a) . n_t and q = the point of t closest to c:
+ *                face contact     q in the interior of t (Voronoi region of the face) and -R < s < R: delta = R - s, n = n_t
+ *                                 (a centre slightly behind the plane is still pushed out, as the box law does)
+ *                edge / vertex    q on an edge or vertex of t, s > 0 and |c - q| < R: delta = R - |c - q|,
+ *                                 n = (c - q) / |c - q|; a q at an endpoint of an edge is that vertex's contact
+ *   de-duplication (tolerance tol = 1e-12 x the diagonal of the mesh's bounding box; the candidates in ascending id):
+ *              1. face contacts with the same supporting plane (normals equal to 1e-12, offsets to tol) count once;
+ *              2. an edge or vertex contact whose q lies in the plane of a kept face contact is dropped;
+ *              3. edge contacts count once per sorted node pair, vertex contacts once per node id;
+ *              4. an edge or vertex contact is dropped unless it is a local minimum of the distance to the walls, i.e.
+ *                 when a wall triangle holding that edge (both nodes) or vertex lies nearer to c than |c - q| - tol.  This keeps
+ *                 one contact at a convex edge of the domain whether c faces the middle of a mesh edge or a mesh vertex,
+ *                 and none from the further vertices along that edge.
+ *   cap        a particle keeps at most DFL_WALL_MAX_CONTACTS distinct contacts; further ones are dropped and counted
+ *              (ParticleContextWallDroppedCount).
+ *   grids      the contact cell grid spans the mesh's bounding box padded by R (cell edge >= 4R per axis, about half a
+ *              particle per cell, at most 2^24 cells).  A particle whose centre lies outside that box gets NO contact
+ *              acceleration, from pairs or walls, and is no pair partner of the others: it has left through an open group.
+ *              Wall candidates come from a static grid over the same box; forces are bitwise reproducible.
+ *   setup      the wall records and grids are built at the call, and again only when ParticleRadius (or the particle
+ *              count) changes; a sweep allocates nothing and does not wait for the device.  The walls are a snapshot of
+ *              the mesh: a moved mesh needs another call.  Point location of the coupling stays exact for convex domains
+ *              only; walls do not change that. */
+#ifndef DFL_WALL_MAX_CONTACTS
+#define DFL_WALL_MAX_CONTACTS 8
+#endif
+/* particle walls = the boundary faces of `mesh` in the groups whose bit is set in group_mask (bit i = group i);
+ * replaces the unit-box walls and spans the contact cell grid over the mesh's bounding box padded by R;
+ * mesh NULL = back to the unit box (frees the wall state) */
+void ParticleContextSetWallMesh(ParticleContext* ctx, Mesh3D* mesh, index_type group_mask);
+/* wall contacts dropped since the walls were set because a particle had more than DFL_WALL_MAX_CONTACTS */
+index_type ParticleContextWallDroppedCount(const ParticleContext* ctx);
+
 #ifdef __cplusplus
 }
 #endif

@@ -502,6 +502,38 @@ void dfl_dem_integrate(dfl_index P, dfl_value dt, dfl_value* coord, dfl_value* v
 void dfl_dem_forces(dfl_index P, const dfl_value* sorted, dfl_value radius, dfl_value mass, dfl_value kn, dfl_value gamma_n,
                     dfl_value cell, dfl_index ncell, const dfl_index* order, const dfl_index* cell_start, dfl_value* acc,
                     void* stream);
+/* the last four launches of dfl_dem_build_cells, for a bin pass of the caller's over nbin bins */
+void dfl_dem_sort_binned(dfl_index P, dfl_index nbin, const dfl_value* coord, const dfl_value* vel, dfl_index* cell_of,
+                         dfl_index* rank, dfl_index* count, dfl_index* chunk_sum, dfl_index* cell_start, dfl_index* slot,
+                         dfl_index* order, dfl_value* sorted, void* stream);
+
+/* ---- DEM contacts with the boundary faces of a tet mesh (build-defined, csrc/k_walls.hip; model in include/dedflow.h)
+ *  dfl_grid3            a uniform grid: cell (i, j, k) = floor((x - lo) * inv) per axis, n cells per axis, x fastest
+ *  dfl_wall_tri         one wall triangle in one 128-byte cache line: vertices v[3][3], inward unit normal n, plane offset
+ *                       off = n . v0, the mesh node ids of the vertices and the triangle id
+ *    dfl_walls_build_cells  dfl_dem_build_cells on `grid`; a particle outside it goes to the extra bin nx*ny*nz (count and
+ *                           cell_start then hold nx*ny*nz + 2 entries, chunk_sum dfl_dem_num_chunks(nx*ny*nz + 1))
+ *    dfl_walls_forces       acc[i] = (sum_j F_ij + F_walls) / mass for the particles inside `grid`, 0 for the others; the
+ *                           wall candidates of a particle are wall_list[wall_start[c] .. wall_start[c+1]) of the wall_grid
+ *                           cell c holding its centre; *dropped += contacts over DFL_WALL_MAX_CONTACTS */
+#ifndef DFL_WALL_MAX_CONTACTS
+#define DFL_WALL_MAX_CONTACTS 8
+#endif
+typedef struct dfl_grid3 {
+    dfl_value lo[3], inv[3];
+    dfl_index n[3];
+} dfl_grid3;
+typedef struct dfl_wall_tri {
+    dfl_value v[9], n[3], off, pad;
+    dfl_index node[3], id;
+} dfl_wall_tri;
+void dfl_walls_build_cells(dfl_index P, const dfl_value* coord, const dfl_value* vel, dfl_grid3 grid, dfl_index* cell_of,
+                           dfl_index* rank, dfl_index* count, dfl_index* chunk_sum, dfl_index* cell_start, dfl_index* slot,
+                           dfl_index* order, dfl_value* sorted, void* stream);
+void dfl_walls_forces(dfl_index P, const dfl_value* sorted, dfl_value radius, dfl_value mass, dfl_value kn, dfl_value gamma_n,
+                      dfl_grid3 grid, const dfl_index* order, const dfl_index* cell_start, const dfl_wall_tri* tri,
+                      dfl_grid3 wall_grid, const dfl_index* wall_start, const dfl_index* wall_list, dfl_value tol,
+                      dfl_index* dropped, dfl_value* acc, void* stream);
 
 /* ---- particle-fluid coupling (build-defined, csrc/k_couple.hip; model in include/dedflow.h)
  *    dfl_couple_sort_v2e      every V2E list ascending (one thread per node)

@@ -4,9 +4,11 @@ R = 0.004.  Times, per sub-step, with device events (DflProfile tags of host/cou
   locate + drag), the reaction load (counting sort by tet + node scatter) after 10 sub-steps;
 the walk with the particles in the contact sweep's cell order against particle-id order
 (DFL_COUPLE_CELL_ORDER=0: the walk; the drag kernel always runs in id order); and DflTimeStep (two-level PC, 2 Newton
-iterations, 10 sub-steps) coupled one-way and two-way against the uncoupled contact sweep.  Prints one JSON line (and writes it to --out).
+iterations, 10 sub-steps) coupled one-way and two-way against the uncoupled contact sweep.  With --walls every particle
+context takes its walls from all six boundary groups of the mesh (ParticleContextSetWallMesh) instead of the unit box;
+"sweep" then also times the contact sweep alone.  Prints one JSON line (and writes it to --out).
 
-  python tools/probe_coupling.py [--reps 50] [--steps 3] [--out profiles/probe_coupling.json]
+  python tools/probe_coupling.py [--reps 50] [--steps 3] [--walls] [--out profiles/probe_coupling.json]
 """
 import argparse
 import ctypes as C
@@ -36,6 +38,7 @@ def main():
     ap.add_argument("--particles", type=int, default=100000)
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--walls", action="store_true")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     L = api.lib()
@@ -49,7 +52,7 @@ def main():
     P = api.Problem(m, maxit=120, atol=1e-12, rtol=1e-4)
     L.KrylovSetPCType(P.ksp, api.PC_TWOLEVEL)
     w_d = api.DeviceArray.from_numpy(wg)
-    out = {"M": a.M, "tets": m.num_tet, "particles": a.particles, "R": R}
+    out = {"M": a.M, "tets": m.num_tet, "particles": a.particles, "R": R, "walls": a.walls}
 
     def particles(order=True):
         if not order:
@@ -57,6 +60,8 @@ def main():
         try:
             pc = api.Particles(x, v, R, mass=mass, dt=1e-4)
             t0 = time.perf_counter()
+            if a.walls:
+                pc.set_walls(P)
             pc.couple(P, two_way=True)
             api.sync()
             return pc, time.perf_counter() - t0
@@ -98,7 +103,13 @@ def main():
             pc.reaction_load(load)
         react = collect(L, TAG_REACTION)
         L.DflProfileEnable(0)
-        out[key] = {"setup_s": setup_s, "locate_cold": cold, "locate_history": hist, "locate_in_substep": loc_sub, "drag": drag,
+        t = api.Timer()
+        t.start()
+        for _ in range(a.reps):
+            pc.compute_forces()
+        t.stop()
+        sweep_us = 1e3 * t.ms() / a.reps
+        out[key] = {"setup_s": setup_s, "sweep_us": sweep_us, "locate_cold": cold, "locate_history": hist, "locate_in_substep": loc_sub, "drag": drag,
                     "dem_force": force, "fluid_substep_us": 1e3 * sub_ms, "reaction_load": react,
                     "lost": pc.lost_count(), "outside": int((pc.tet() == -1).sum())}
         pc.close()
@@ -109,6 +120,8 @@ def main():
     stats = L.KrylovGetStats(P.ksp).contents
     for key in ("uncoupled", "one_way", "two_way"):
         pc = api.Particles(x, v, R, mass=mass, dt=1e-4)
+        if a.walls:
+            pc.set_walls(P)
         if key != "uncoupled":
             pc.couple(P, two_way=key == "two_way")
         st = [api.DeviceArray.from_numpy(q) for q in (wg, 0.1 * dw0, 0.1 * dw0)]
