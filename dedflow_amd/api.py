@@ -283,6 +283,44 @@ class Particles:
     def wall_dropped_count(self):
         return int(lib().ParticleContextWallDroppedCount(self.ctx))
 
+    # ---- contact friction and rotation (build-defined; model in include/dedflow.h) --------------------------------
+    def set_friction(self, mu, kt=None, gamma_t=None):
+        """ParticleContextSetFriction: Coulomb coefficient mu, tangential stiffness kt (None: 2/7 kn) and damping gamma_t
+        (None: gamma_n); mu None turns friction off.  Turning it on starts every particle at zero spin; later calls keep
+        the spin and clear the contact history."""
+        if mu is None:
+            lib().ParticleContextSetFriction(self.ctx, None)
+            return
+        cfg = DflContactFriction(float(mu), 0.0 if kt is None else float(kt), -1.0 if gamma_t is None else float(gamma_t))
+        lib().ParticleContextSetFriction(self.ctx, C.byref(cfg))
+
+    def set_gravity(self, g):
+        """body acceleration g[3] of update() (not of fluid_step, which uses the coupling's gravity)"""
+        lib().ParticleContextSetGravity(self.ctx, (C.c_double * 3)(*[float(a) for a in g]))
+
+    def _spin_ptr(self, name):
+        p = getattr(lib(), name)(self.ctx)
+        if not p:
+            raise RuntimeError("friction is off: call set_friction first")
+        return p
+
+    def omega(self):
+        """angular velocity [P][3] copied back from the device"""
+        return d2h(self._spin_ptr("ParticleContextAngularVelocity"), 3 * self.P, np.float64).reshape(self.P, 3)
+
+    def set_omega(self, w):
+        """overwrite the angular velocity with w ([P][3])"""
+        p = self._spin_ptr("ParticleContextAngularVelocity")
+        sync()
+        DeviceArray(3 * self.P, ptr=p).upload(np.asarray(w, dtype=np.float64).reshape(-1))
+
+    def alpha(self):
+        """angular acceleration (torque / I) [P][3] of the last contact sweep"""
+        return d2h(self._spin_ptr("ParticleContextAngularAcc"), 3 * self.P, np.float64).reshape(self.P, 3)
+
+    def friction_overflow_count(self):
+        return int(lib().ParticleContextFrictionOverflowCount(self.ctx))
+
     def arrays(self):
         """(coord, vel, acc) copied back from the device"""
         c = self.ctx.contents
@@ -290,6 +328,10 @@ class Particles:
 
     def close(self):
         lib().ParticleContextDestroy(self.ctx)
+
+
+class DflContactFriction(C.Structure):
+    _fields_ = [("mu", C.c_double), ("kt", C.c_double), ("gamma_t", C.c_double)]
 
 
 class DflFluidCoupling(C.Structure):
@@ -391,6 +433,10 @@ def _declare(L):
     f("ParticleContextFluidStep", None, [C.POINTER(ParticleContext), vp]); f("ParticleContextReactionLoad", None, [C.POINTER(ParticleContext), vp])
     f("ParticleContextSetWallMesh", None, [C.POINTER(ParticleContext), C.POINTER(Mesh3D), i32])
     f("ParticleContextWallDroppedCount", i32, [C.POINTER(ParticleContext)])
+    f("ParticleContextSetFriction", None, [C.POINTER(ParticleContext), C.POINTER(DflContactFriction)])
+    f("ParticleContextAngularVelocity", vp, [C.POINTER(ParticleContext)]); f("ParticleContextAngularAcc", vp, [C.POINTER(ParticleContext)])
+    f("ParticleContextFrictionOverflowCount", i32, [C.POINTER(ParticleContext)])
+    f("ParticleContextSetGravity", None, [C.POINTER(ParticleContext), C.POINTER(C.c_double)])
     f("DflMeshSetExternalLoad", None, [C.POINTER(Mesh3D), vp])
     f("SolveFlowSystem", i32, [C.POINTER(Mesh3D), vp, vp, vp, C.POINTER(Matrix), vp, vp, vp, vp, i32, i32, vp, vp])
     f("DflTimeStep", i32, [C.POINTER(Mesh3D), vp, vp, vp, C.POINTER(Matrix), vp, vp, vp, vp, i32, i32, C.POINTER(ParticleContext),

@@ -14,6 +14,7 @@
 // (counting sort + per-cell ordering => fixed summation order => bitwise reproducible forces).
 // HBM-bound: (48 read + 24 write) B per particle + 24 B per tested neighbour.
 #include "dfl_common.hpp"
+#include "dem_friction.hpp"
 
 namespace {
 
@@ -190,6 +191,109 @@ __global__ void dem_integrate_kernel(I n3, T dt, T* __restrict__ coord, T* __res
     coord[i] += dt * v;
 }
 
+// the sort with the sorted copy of omega as well (friction on): sorted_w[P][3] next to sorted[P][6]
+__global__ __launch_bounds__(BLK) void dem_sort_cells_spin_kernel(I P, const I* __restrict__ cell_of, const I* __restrict__ cell_start,
+                                                                 const I* __restrict__ slot, I* __restrict__ order,
+                                                                 const T* __restrict__ coord, const T* __restrict__ vel,
+                                                                 const T* __restrict__ omega, T* __restrict__ sorted,
+                                                                 T* __restrict__ sorted_w) {
+    const int i = blockIdx.x * BLK + threadIdx.x;
+    if (i >= P) return;
+    const int c = cell_of[i];
+    const int lo = cell_start[c], hi = cell_start[c + 1];
+    int r = 0;
+    for (int a = lo; a < hi; ++a) r += slot[a] < i;
+    const long long pos = lo + r;
+    order[pos] = i;
+    T* o = sorted + pos * 6;
+    o[0] = coord[3 * i]; o[1] = coord[3 * i + 1]; o[2] = coord[3 * i + 2];
+    o[3] = vel[3 * i]; o[4] = vel[3 * i + 1]; o[5] = vel[3 * i + 2];
+    T* w = sorted_w + pos * 3;
+    w[0] = omega[3 * i]; w[1] = omega[3 * i + 1]; w[2] = omega[3 * i + 2];
+}
+
+// dem_force_kernel with the tangential law (dem_friction.hpp): pairs in the same visit order, then the six walls of the
+// unit box (axis 0..2, side lo then hi); writes acc, alpha and the particle's new history row
+__global__ __launch_bounds__(BLK) void dem_force_friction_kernel(I P, const T* __restrict__ sorted, const T* __restrict__ sorted_w,
+                                                                T R, T mass, T kn, T gn, dfl_friction_law law, T inv_cell, I ncell,
+                                                                const I* __restrict__ order, const I* __restrict__ cell_start,
+                                                                dfl_contact_history hist, T* __restrict__ acc,
+                                                                T* __restrict__ alpha) {
+    const int s = blockIdx.x * BLK + threadIdx.x;
+    if (s >= P) return;
+    const long long i = order[s];
+    const T* me = sorted + (long long)s * 6;
+    const double p[3] = {me[0], me[1], me[2]}, v[3] = {me[3], me[4], me[5]};
+    const double w[3] = {sorted_w[3 * (long long)s], sorted_w[3 * (long long)s + 1], sorted_w[3 * (long long)s + 2]};
+    dfl_friction::Contacts c;
+    dfl_friction::begin(c, hist, i);
+    const double rng = 2.0 * R;
+    const int x0 = cell_coord(p[0] - rng, inv_cell, ncell), x1 = cell_coord(p[0] + rng, inv_cell, ncell);
+    const int y0 = cell_coord(p[1] - rng, inv_cell, ncell), y1 = cell_coord(p[1] + rng, inv_cell, ncell);
+    const int z0 = cell_coord(p[2] - rng, inv_cell, ncell), z1 = cell_coord(p[2] + rng, inv_cell, ncell);
+    const double d2max = 4.0 * R * R;
+    for (int z = z0; z <= z1; ++z) {
+        for (int y = y0; y <= y1; ++y) {
+            const int c0 = x0 + ncell * (y + ncell * z), c1 = x1 + ncell * (y + ncell * z);
+            for (int t = cell_start[c0]; t < cell_start[c1 + 1]; ++t) {
+                if (t == s) continue;
+                const T* o = sorted + (long long)t * 6;
+                const double rx = p[0] - o[0], ry = p[1] - o[1], rz = p[2] - o[2];
+                const double d2 = rx * rx + ry * ry + rz * rz;
+                if (d2 >= d2max || d2 == 0.0) continue;
+                const double dist = sqrt(d2), inv = 1.0 / dist;
+                const double n[3] = {rx * inv, ry * inv, rz * inv};
+                const double dv[3] = {v[0] - o[3], v[1] - o[4], v[2] - o[5]};
+                const double vn = dv[0] * n[0] + dv[1] * n[1] + dv[2] * n[2];
+                const double fn = kn * (2.0 * R - dist) - gn * vn;
+                const T* ow = sorted_w + (long long)t * 3;
+                const double ws[3] = {w[0] + ow[0], w[1] + ow[1], w[2] + ow[2]};
+                dfl_friction::contact(c, law, dfl_friction::KEY_PARTNER | (uint64_t)order[t], n, fn, 0.5 * dist, dv, ws);
+            }
+        }
+    }
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+#pragma unroll
+        for (int side = 0; side < 2; ++side) {
+            const double delta = side == 0 ? R - p[d] : p[d] + R - 1.0;
+            if (!(delta > 0.0)) continue;
+            double n[3] = {0.0, 0.0, 0.0};
+            n[d] = side == 0 ? 1.0 : -1.0;
+            const double fn = kn * delta - gn * (v[d] * n[d]);
+            dfl_friction::contact(c, law, dfl_friction::KEY_WALL | (uint64_t)(2 * d + side), n, fn, fmax(R - delta, 0.0), v, w);
+        }
+    }
+    dfl_friction::finish(c, hist, i, mass, law.inertia, acc, alpha);
+}
+
+// semi-implicit Euler with a body acceleration g and rotation: v += dt (a + g) ; x += dt v ; omega += dt alpha
+__global__ __launch_bounds__(BLK) void dem_integrate_spin_kernel(I P, T dt, T gx, T gy, T gz, T* __restrict__ coord,
+                                                                T* __restrict__ vel, const T* __restrict__ acc,
+                                                                T* __restrict__ omega, const T* __restrict__ alpha) {
+    const int i = blockIdx.x * BLK + threadIdx.x;
+    if (i >= P) return;
+    const double g[3] = {gx, gy, gz};
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        const long long k = 3 * (long long)i + d;
+        const double v = vel[k] + dt * (acc[k] + g[d]);
+        vel[k] = v;
+        coord[k] += dt * v;
+    }
+    if (omega) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) omega[3 * (long long)i + d] += dt * alpha[3 * (long long)i + d];
+    }
+}
+
+// omega += dt alpha (after the coupled sub-step, whose kernel integrates v and x)
+__global__ void dem_spin_kernel(I n3, T dt, T* __restrict__ omega, const T* __restrict__ alpha) {
+    const int i = blockIdx.x * BLK + threadIdx.x;
+    if (i >= n3) return;
+    omega[i] += dt * alpha[i];
+}
+
 }  // namespace
 
 extern "C" {
@@ -228,6 +332,47 @@ void dfl_dem_forces(I P, const T* sorted, T radius, T mass, T kn, T gamma_n, T c
 void dfl_dem_integrate(I P, T dt, T* coord, T* vel, const T* acc, void* stream) {
     if (P <= 0) return;
     dem_integrate_kernel<<<ceil_div((long long)P * 3, BLK), BLK, 0, S(stream)>>>(3 * P, dt, coord, vel, acc);
+    DFL_LAUNCH_CHECK();
+}
+
+void dfl_dem_sort_binned_spin(I P, I nbin, const T* coord, const T* vel, const T* omega, I* cell_of, I* rank, I* count,
+                              I* chunk_sum, I* cell_start, I* slot, I* order, T* sorted, T* sorted_w, void* stream) {
+    const I nchunk = dfl_dem_num_chunks(nbin);
+    dem_chunk_sum_kernel<<<nchunk, BLK, 0, S(stream)>>>(nbin, count, chunk_sum);
+    dem_scan_kernel<<<nchunk, BLK, 0, S(stream)>>>(nbin, count, chunk_sum, cell_start);
+    dem_place_kernel<<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, cell_of, rank, cell_start, slot);
+    dem_sort_cells_spin_kernel<<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, cell_of, cell_start, slot, order, coord, vel, omega, sorted,
+                                                                      sorted_w);
+    DFL_LAUNCH_CHECK();
+}
+
+void dfl_dem_build_cells_spin(I P, const T* coord, const T* vel, const T* omega, T cell, I ncell, I* cell_of, I* rank, I* count,
+                              I* chunk_sum, I* cell_start, I* slot, I* order, T* sorted, T* sorted_w, void* stream) {
+    if (P <= 0) return;
+    const I ncell3 = ncell * ncell * ncell;
+    dem_bin_kernel<<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, coord, 1.0 / cell, ncell, cell_of, rank, count);
+    dfl_dem_sort_binned_spin(P, ncell3, coord, vel, omega, cell_of, rank, count, chunk_sum, cell_start, slot, order, sorted, sorted_w,
+                             stream);
+}
+
+void dfl_dem_forces_friction(I P, const T* sorted, const T* sorted_w, T radius, T mass, T kn, T gamma_n, dfl_friction_law law, T cell,
+                             I ncell, const I* order, const I* cell_start, dfl_contact_history hist, T* acc, T* alpha,
+                             void* stream) {
+    if (P <= 0) return;
+    dem_force_friction_kernel<<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, sorted, sorted_w, radius, mass, kn, gamma_n, law, 1.0 / cell,
+                                                                     ncell, order, cell_start, hist, acc, alpha);
+    DFL_LAUNCH_CHECK();
+}
+
+void dfl_dem_integrate_spin(I P, T dt, const T* g, T* coord, T* vel, const T* acc, T* omega, const T* alpha, void* stream) {
+    if (P <= 0) return;
+    dem_integrate_spin_kernel<<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, dt, g[0], g[1], g[2], coord, vel, acc, omega, alpha);
+    DFL_LAUNCH_CHECK();
+}
+
+void dfl_dem_spin(I P, T dt, T* omega, const T* alpha, void* stream) {
+    if (P <= 0) return;
+    dem_spin_kernel<<<ceil_div((long long)P * 3, BLK), BLK, 0, S(stream)>>>(3 * P, dt, omega, alpha);
     DFL_LAUNCH_CHECK();
 }
 

@@ -13,6 +13,7 @@
 // one or two wall cells: the "wall cell empty" branch is wave-uniform in the interior, and the 128-byte records (one cache
 // line each) of a shared cell are read once per wave from L1 / L2.
 #include "dfl_common.hpp"
+#include "dem_friction.hpp"
 
 namespace {
 
@@ -248,6 +249,127 @@ __global__ __launch_bounds__(BLK) void wall_force_kernel(I P, const T* __restric
     acc[3 * i + 2] = f[2] * im;
 }
 
+// wall_contacts with the tangential law: the same candidates, de-duplication and cap, in the same order; a face contact is
+// keyed by the plane id of its triangle, an edge by its sorted node pair, a vertex by its node id
+__device__ void wall_contacts_friction(const double* p, const double* v, const double* w, double R, double kn, double gn,
+                                       const dfl_friction_law& law, double tol, const dfl_wall_tri* __restrict__ tri,
+                                       const I* __restrict__ plane_id, const I* __restrict__ list, int lo, int hi,
+                                       dfl_friction::Contacts& c, int& dropped) {
+    double plane[MAXC][4];
+    int key[MAXC][2];
+    int nf = 0, ne = 0;
+    for (int k = lo; k < hi; ++k) {
+        const dfl_wall_tri* t = tri + list[k];
+        const double s = plane_distance(t, p);
+        if (!(s > -R && s < R)) continue;
+        const Feature ft = feature_of(t, p);
+        if (ft.kind != 0) continue;
+        bool dup = false;
+        for (int j = 0; j < nf; ++j)
+            dup |= fabs(plane[j][0] - t->n[0]) <= 1e-12 && fabs(plane[j][1] - t->n[1]) <= 1e-12 &&
+                   fabs(plane[j][2] - t->n[2]) <= 1e-12 && fabs(plane[j][3] - t->off) <= tol;
+        if (dup) continue;
+        if (nf + ne >= MAXC) { ++dropped; continue; }
+        plane[nf][0] = t->n[0]; plane[nf][1] = t->n[1]; plane[nf][2] = t->n[2]; plane[nf][3] = t->off;
+        ++nf;
+        const double n[3] = {t->n[0], t->n[1], t->n[2]};
+        const double vn = v[0] * n[0] + v[1] * n[1] + v[2] * n[2];
+        const double delta = R - ft.s;
+        dfl_friction::contact(c, law, dfl_friction::KEY_WALL | (uint64_t)plane_id[list[k]], n, kn * delta - gn * vn,
+                              fmax(R - delta, 0.0), v, w);
+    }
+    const double R2 = R * R;
+    for (int k = lo; k < hi; ++k) {
+        const dfl_wall_tri* t = tri + list[k];
+        const double s = plane_distance(t, p);
+        if (!(s > 0.0 && s < R)) continue;
+        const Feature ft = feature_of(t, p);
+        if (ft.kind == 0 || !(ft.d2 < R2)) continue;
+        bool skip = false;
+        for (int j = 0; j < nf; ++j)
+            skip |= fabs(ft.q[0] * plane[j][0] + ft.q[1] * plane[j][1] + ft.q[2] * plane[j][2] - plane[j][3]) <= tol;
+        for (int j = 0; j < ne; ++j) skip |= key[j][0] == ft.k0 && key[j][1] == ft.k1;
+        if (skip) continue;
+        const double dist = sqrt(ft.d2);
+        for (int m = lo; m < hi && !skip; ++m) {
+            if (m == k) continue;
+            const dfl_wall_tri* u = tri + list[m];
+            if (!holds(u, ft.k0, ft.k1)) continue;
+            const Feature fu = feature_of(u, p);
+            skip = sqrt(fu.d2) < dist - tol;
+        }
+        if (skip) continue;
+        if (nf + ne >= MAXC) { ++dropped; continue; }
+        key[ne][0] = ft.k0; key[ne][1] = ft.k1;
+        ++ne;
+        const double inv = 1.0 / dist;
+        const double n[3] = {(p[0] - ft.q[0]) * inv, (p[1] - ft.q[1]) * inv, (p[2] - ft.q[2]) * inv};
+        const double vn = v[0] * n[0] + v[1] * n[1] + v[2] * n[2];
+        const double delta = R - dist;
+        const uint64_t hk = ft.k1 >= 0 ? dfl_friction::edge_key(ft.k0, ft.k1) : (dfl_friction::KEY_VERTEX | (uint64_t)ft.k0);
+        dfl_friction::contact(c, law, hk, n, kn * delta - gn * vn, fmax(R - delta, 0.0), v, w);
+    }
+}
+
+// wall_force_kernel with the tangential law: pairs (same order), then the wall contacts; writes acc, alpha and the new
+// history row (a particle outside the padded box: zero acc and alpha, an empty row)
+__global__ __launch_bounds__(BLK) void wall_force_friction_kernel(I P, const T* __restrict__ sorted, const T* __restrict__ sorted_w,
+                                                                 T R, T mass, T kn, T gn, dfl_friction_law law, dfl_grid3 g,
+                                                                 const I* __restrict__ order, const I* __restrict__ cell_start,
+                                                                 const dfl_wall_tri* __restrict__ tri,
+                                                                 const I* __restrict__ plane_id, dfl_grid3 wg,
+                                                                 const I* __restrict__ wstart, const I* __restrict__ wlist, T tol,
+                                                                 I* __restrict__ dropped, dfl_contact_history hist,
+                                                                 T* __restrict__ acc, T* __restrict__ alpha) {
+    const int s = blockIdx.x * BLK + threadIdx.x;
+    if (s >= P) return;
+    const long long i = order[s];
+    dfl_friction::Contacts c;
+    dfl_friction::begin(c, hist, i);
+    const int ncell3 = g.n[0] * g.n[1] * g.n[2];
+    if (s >= cell_start[ncell3]) {
+        dfl_friction::finish(c, hist, i, mass, law.inertia, acc, alpha);
+        return;
+    }
+    const T* me = sorted + (long long)s * 6;
+    const double p[3] = {me[0], me[1], me[2]}, v[3] = {me[3], me[4], me[5]};
+    const double w[3] = {sorted_w[3 * (long long)s], sorted_w[3 * (long long)s + 1], sorted_w[3 * (long long)s + 2]};
+    const double rng = 2.0 * R;
+    const int x0 = grid_coord(p[0] - rng, g.lo[0], g.inv[0], g.n[0]), x1 = grid_coord(p[0] + rng, g.lo[0], g.inv[0], g.n[0]);
+    const int y0 = grid_coord(p[1] - rng, g.lo[1], g.inv[1], g.n[1]), y1 = grid_coord(p[1] + rng, g.lo[1], g.inv[1], g.n[1]);
+    const int z0 = grid_coord(p[2] - rng, g.lo[2], g.inv[2], g.n[2]), z1 = grid_coord(p[2] + rng, g.lo[2], g.inv[2], g.n[2]);
+    const double d2max = 4.0 * R * R;
+    for (int z = z0; z <= z1; ++z) {
+        for (int y = y0; y <= y1; ++y) {
+            const int c0 = x0 + g.n[0] * (y + g.n[1] * z), c1 = x1 + g.n[0] * (y + g.n[1] * z);
+            for (int t = cell_start[c0]; t < cell_start[c1 + 1]; ++t) {
+                if (t == s) continue;
+                const T* o = sorted + (long long)t * 6;
+                const double rx = p[0] - o[0], ry = p[1] - o[1], rz = p[2] - o[2];
+                const double d2 = rx * rx + ry * ry + rz * rz;
+                if (d2 >= d2max || d2 == 0.0) continue;
+                const double dist = sqrt(d2), inv = 1.0 / dist;
+                const double n[3] = {rx * inv, ry * inv, rz * inv};
+                const double dv[3] = {v[0] - o[3], v[1] - o[4], v[2] - o[5]};
+                const double vn = dv[0] * n[0] + dv[1] * n[1] + dv[2] * n[2];
+                const double fn = kn * (2.0 * R - dist) - gn * vn;
+                const T* ow = sorted_w + (long long)t * 3;
+                const double ws[3] = {w[0] + ow[0], w[1] + ow[1], w[2] + ow[2]};
+                dfl_friction::contact(c, law, dfl_friction::KEY_PARTNER | (uint64_t)order[t], n, fn, 0.5 * dist, dv, ws);
+            }
+        }
+    }
+    const int wc = grid_coord(p[0], wg.lo[0], wg.inv[0], wg.n[0]) +
+                   wg.n[0] * (grid_coord(p[1], wg.lo[1], wg.inv[1], wg.n[1]) + wg.n[1] * grid_coord(p[2], wg.lo[2], wg.inv[2], wg.n[2]));
+    const int wlo = wstart[wc], whi = wstart[wc + 1];
+    if (wlo < whi) {
+        int nd = 0;
+        wall_contacts_friction(p, v, w, R, kn, gn, law, tol, tri, plane_id, wlist, wlo, whi, c, nd);
+        if (nd) atomicAdd(dropped, nd);
+    }
+    dfl_friction::finish(c, hist, i, mass, law.inertia, acc, alpha);
+}
+
 }  // namespace
 
 extern "C" {
@@ -267,6 +389,27 @@ void dfl_walls_forces(I P, const T* sorted, T radius, T mass, T kn, T gamma_n, d
     if (P <= 0) return;
     wall_force_kernel<<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, sorted, radius, mass, kn, gamma_n, grid, order, cell_start, tri,
                                                              wall_grid, wall_start, wall_list, tol, dropped, acc);
+    DFL_LAUNCH_CHECK();
+}
+
+void dfl_walls_build_cells_spin(I P, const T* coord, const T* vel, const T* omega, dfl_grid3 grid, I* cell_of, I* rank, I* count,
+                                I* chunk_sum, I* cell_start, I* slot, I* order, T* sorted, T* sorted_w, void* stream) {
+    if (P <= 0) return;
+    wall_bin_kernel<<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, coord, grid, cell_of, rank, count);
+    DFL_LAUNCH_CHECK();
+    const I nbin = grid.n[0] * grid.n[1] * grid.n[2] + 1;
+    dfl_dem_sort_binned_spin(P, nbin, coord, vel, omega, cell_of, rank, count, chunk_sum, cell_start, slot, order, sorted, sorted_w,
+                             stream);
+}
+
+void dfl_walls_forces_friction(I P, const T* sorted, const T* sorted_w, T radius, T mass, T kn, T gamma_n, dfl_friction_law law,
+                               dfl_grid3 grid, const I* order, const I* cell_start, const dfl_wall_tri* tri, const I* plane,
+                               dfl_grid3 wall_grid, const I* wall_start, const I* wall_list, T tol, I* dropped,
+                               dfl_contact_history hist, T* acc, T* alpha, void* stream) {
+    if (P <= 0) return;
+    wall_force_friction_kernel<<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, sorted, sorted_w, radius, mass, kn, gamma_n, law, grid,
+                                                                      order, cell_start, tri, plane, wall_grid, wall_start,
+                                                                      wall_list, tol, dropped, hist, acc, alpha);
     DFL_LAUNCH_CHECK();
 }
 

@@ -237,6 +237,7 @@ void ParticleContextFluidStep(ParticleContext* ctx, const f64* w) {
                           ArrayData(ParticleCTXDeviceCoord(ctx)), ArrayData(ParticleCTXDeviceVel(ctx)),
                           ArrayData(ParticleCTXDeviceAcc(ctx)), c->imp, DflStream());
     DflProfileEnd(slot);
+    if (x->omega) dfl_dem_spin(ctx->num_particle, x->dt, x->omega, x->alpha, DflStream()); /* the fluid exerts no torque */
     c->imp_time += x->dt;
     DflRangePop();
 }

@@ -2,6 +2,7 @@
 #ifndef DFL_HOST_PRIVATE_H
 #define DFL_HOST_PRIVATE_H
 #include "dedflow.h"
+#include "dedflow_kernels.h"
 
 /* Patch schedule of the LHS assembly (host/patch.c): spatial patches of <= leaf tets whose (row,col)
  * blocks fit an LDS table; patches of one color share no node. */
@@ -135,7 +136,19 @@ typedef struct ParticleExt {
     index_type cap_particle, cap_cell;
     struct CoupleState* couple;                 /* particle-fluid coupling (host/couple.c), NULL when off */
     struct WallState* walls;                    /* mesh walls (host/walls.c), NULL: the unit box */
+    /* contact friction and rotation (ParticleContextSetFriction); friction is on when omega != NULL */
+    dfl_friction_law law;                       /* mu, resolved kt / gamma_t; dt and inertia are set per sweep */
+    f64 *omega, *alpha, *sorted_w;              /* device [P][3] */
+    dfl_contact_hist* hist[2];                  /* device [P][DFL_DEM_MAX_HISTORY] rows, ping-pong */
+    index_type* hist_count[2];                  /* device [P] live entries of every row */
+    index_type* overflow;                       /* device [1] */
+    int hist_cur;                               /* the rows the next sweep reads */
+    f64 gravity[3];                             /* body acceleration of ParticleContextUpdate */
 } ParticleExt;
+/* the history of the next sweep (flips the ping-pong: call once per sweep) */
+dfl_contact_history DflFrictionHistory(ParticleExt* x);
+dfl_friction_law DflFrictionLaw(const ParticleContext* ctx);
+void DflFrictionClearHistory(ParticleContext* ctx); /* no-op when friction is off */
 /* the sweep's device workspace for P particles over nbin cell-list bins (count / cell_start [nbin + 1]); grows only */
 void DflDemReserve(ParticleExt* x, index_type P, index_type nbin);
 struct CoupleState;

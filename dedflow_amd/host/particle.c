@@ -3,7 +3,8 @@
  * empty Add/Update/Remove hooks (:120-130).  The contact sweep is build-defined
  * (dedflow_amd/csrc/k_dem.hip): ParticleContextComputeForces = cell list + force kernel,
  * ParticleContextUpdate = forces + semi-implicit Euler step.  With walls from a mesh (ParticleContextSetWallMesh) the sweep
- * runs in host/walls.c instead. */
+ * runs in host/walls.c instead.  With friction on (ParticleContextSetFriction) both sweeps run their friction kernels,
+ * which read the previous sweep's contact history and write the next one into the other of two buffers. */
 #include <math.h>
 #include <string.h>
 #include "dedflow.h"
@@ -42,6 +43,7 @@ void ParticleContextDestroy(ParticleContext* ctx) {
         CdamFreeDevice(x->count, 0); CdamFreeDevice(x->cell_start, 0); CdamFreeDevice(x->chunk_sum, 0);
         DflCoupleFree(x->couple);
         DflWallsFree(x->walls);
+        ParticleContextSetFriction(ctx, NULL);
         CdamFreeHost(x, SIZE_OF(ParticleExt));
     }
     CdamFreeHost(ctx, SIZE_OF(ParticleContext));
@@ -115,6 +117,16 @@ void ParticleContextComputeForces(ParticleContext* ctx) {
     const f64* coord = ArrayData(ParticleCTXDeviceCoord(ctx));
     const f64* vel = ArrayData(ParticleCTXDeviceVel(ctx));
     f64* acc = ArrayData(ParticleCTXDeviceAcc(ctx));
+    if (x->omega) {
+        dfl_dem_build_cells_spin(P, coord, vel, x->omega, cell, ncell, x->cell_of, x->rank, x->count, x->chunk_sum, x->cell_start,
+                                 x->slot, x->order, x->sorted, x->sorted_w, s);
+        int slot = DflProfileBegin(DFL_TAG_SMALL + 1);
+        dfl_dem_forces_friction(P, x->sorted, x->sorted_w, R, ParticleMass(ctx), x->kn, x->gamma_n, DflFrictionLaw(ctx), cell, ncell,
+                                x->order, x->cell_start, DflFrictionHistory(x), acc, x->alpha, s);
+        DflProfileEnd(slot);
+        DflRangePop();
+        return;
+    }
     dfl_dem_build_cells(P, coord, vel, cell, ncell, x->cell_of, x->rank, x->count, x->chunk_sum, x->cell_start, x->slot, x->order, x->sorted, s);
     int slot = DflProfileBegin(DFL_TAG_SMALL + 1);
     dfl_dem_forces(P, x->sorted, R, ParticleMass(ctx), x->kn, x->gamma_n, cell, ncell, x->order, x->cell_start, acc, s);
@@ -125,6 +137,103 @@ void ParticleContextComputeForces(ParticleContext* ctx) {
 void ParticleContextUpdate(ParticleContext* ctx) {
     ParticleExt* x = (ParticleExt*)ctx->ext;
     ParticleContextComputeForces(ctx);
-    dfl_dem_integrate(ctx->num_particle, x->dt, ArrayData(ParticleCTXDeviceCoord(ctx)), ArrayData(ParticleCTXDeviceVel(ctx)),
-                      ArrayData(ParticleCTXDeviceAcc(ctx)), DflStream());
+    const b32 gravity = x->gravity[0] != 0.0 || x->gravity[1] != 0.0 || x->gravity[2] != 0.0;
+    if (x->omega || gravity)
+        dfl_dem_integrate_spin(ctx->num_particle, x->dt, x->gravity, ArrayData(ParticleCTXDeviceCoord(ctx)),
+                               ArrayData(ParticleCTXDeviceVel(ctx)), ArrayData(ParticleCTXDeviceAcc(ctx)), x->omega, x->alpha,
+                               DflStream());
+    else
+        dfl_dem_integrate(ctx->num_particle, x->dt, ArrayData(ParticleCTXDeviceCoord(ctx)), ArrayData(ParticleCTXDeviceVel(ctx)),
+                          ArrayData(ParticleCTXDeviceAcc(ctx)), DflStream());
+}
+
+/* ---- contact friction and rotation (model in include/dedflow.h) ---- */
+
+static void clear_history(ParticleExt* x, index_type P) {
+    hipStream_t s = DflStream();
+    for (int k = 0; k < 2; ++k) HIPGUARD(hipMemsetAsync(x->hist_count[k], 0, (size_t)(P > 0 ? P : 1) * sizeof(index_type), s));
+    HIPGUARD(hipMemsetAsync(x->overflow, 0, sizeof(index_type), s));
+    x->hist_cur = 0;
+}
+
+void ParticleContextSetFriction(ParticleContext* ctx, const DflContactFriction* cfg) {
+    ParticleExt* x = (ParticleExt*)ctx->ext;
+    const index_type P = ctx->num_particle;
+    const ptrdiff_t n = P > 0 ? P : 1;
+    if (!cfg) {
+        if (!x->omega) return;
+        HIPGUARD(hipStreamSynchronize(DflStream()));
+        CdamFreeDevice(x->omega, 0); CdamFreeDevice(x->alpha, 0); CdamFreeDevice(x->sorted_w, 0); CdamFreeDevice(x->overflow, 0);
+        for (int k = 0; k < 2; ++k) {
+            CdamFreeDevice(x->hist[k], 0);
+            CdamFreeDevice(x->hist_count[k], 0);
+            x->hist[k] = NULL;
+            x->hist_count[k] = NULL;
+        }
+        x->omega = x->alpha = x->sorted_w = NULL;
+        x->overflow = NULL;
+        return;
+    }
+    ASSERT(cfg->mu >= 0.0 && "ParticleContextSetFriction: mu must not be negative");
+    x->law.mu = cfg->mu;
+    x->law.kt = cfg->kt > 0.0 ? cfg->kt : 2.0 / 7.0 * x->kn;
+    x->law.gamma_t = cfg->gamma_t >= 0.0 ? cfg->gamma_t : x->gamma_n;
+    if (!x->omega) {
+        hipStream_t s = DflStream();
+        x->omega = (f64*)CdamMallocDevice(n * 3 * SIZE_OF(f64));
+        x->alpha = (f64*)CdamMallocDevice(n * 3 * SIZE_OF(f64));
+        x->sorted_w = (f64*)CdamMallocDevice(n * 3 * SIZE_OF(f64));
+        x->overflow = (index_type*)CdamMallocDevice(SIZE_OF(index_type));
+        for (int k = 0; k < 2; ++k) {
+            x->hist[k] = (dfl_contact_hist*)CdamMallocDevice(n * DFL_DEM_MAX_HISTORY * SIZE_OF(dfl_contact_hist));
+            x->hist_count[k] = (index_type*)CdamMallocDevice(n * SIZE_OF(index_type));
+        }
+        HIPGUARD(hipMemsetAsync(x->omega, 0, (size_t)n * 3 * sizeof(f64), s));
+        HIPGUARD(hipMemsetAsync(x->alpha, 0, (size_t)n * 3 * sizeof(f64), s));
+    }
+    clear_history(x, P);
+}
+
+void DflFrictionClearHistory(ParticleContext* ctx) {
+    ParticleExt* x = (ParticleExt*)ctx->ext;
+    if (x->omega) clear_history(x, ctx->num_particle);
+}
+
+dfl_friction_law DflFrictionLaw(const ParticleContext* ctx) {
+    const ParticleExt* x = (const ParticleExt*)ctx->ext;
+    dfl_friction_law law = x->law;
+    const f64 R = ParticleRadius(ctx);
+    law.dt = x->dt;
+    law.inertia = 0.4 * ParticleMass(ctx) * R * R;
+    return law;
+}
+
+dfl_contact_history DflFrictionHistory(ParticleExt* x) {
+    dfl_contact_history h;
+    const int a = x->hist_cur, b = 1 - a;
+    h.old_row = x->hist[a];
+    h.old_count = x->hist_count[a];
+    h.new_row = x->hist[b];
+    h.new_count = x->hist_count[b];
+    h.overflow = x->overflow;
+    x->hist_cur = b;
+    return h;
+}
+
+f64* ParticleContextAngularVelocity(ParticleContext* ctx) { return ((ParticleExt*)ctx->ext)->omega; }
+const f64* ParticleContextAngularAcc(const ParticleContext* ctx) { return ((const ParticleExt*)ctx->ext)->alpha; }
+
+index_type ParticleContextFrictionOverflowCount(const ParticleContext* ctx) {
+    const ParticleExt* x = (const ParticleExt*)ctx->ext;
+    if (!x->overflow) return 0;
+    index_type n = 0;
+    hipStream_t s = DflStream();
+    HIPGUARD(hipMemcpyAsync(&n, x->overflow, sizeof n, D2H, s));
+    HIPGUARD(hipStreamSynchronize(s));
+    return n;
+}
+
+void ParticleContextSetGravity(ParticleContext* ctx, const f64 g[3]) {
+    ParticleExt* x = (ParticleExt*)ctx->ext;
+    for (int d = 0; d < 3; ++d) x->gravity[d] = g ? g[d] : 0.0;
 }

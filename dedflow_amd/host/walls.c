@@ -4,7 +4,8 @@
  * At ParticleContextSetWallMesh, on the host: the faces of the masked groups become packed 128-byte records (vertices in
  * ascending local index of the parent tet, normal oriented towards the tet's opposite vertex, the node ids); the record
  * id is the position in group order.  At that call and again whenever ParticleRadius changes (a host-side comparison per
- * sweep): the particle grid and the wall grid over the bounding box padded by R.  The wall grid is built on the host: it
+ * sweep): the particle grid and the wall grid over the bounding box padded by R.  Also at that call, for the contact keys of
+ * the friction sweep: the plane id of every record (sort by the rounded plane, then de-duplication rule 1 within runs).  The wall grid is built on the host: it
  * is a one-time O(faces) job, and walking the faces in id order fills every cell's list in ascending id without a sort.
  * Per sweep nothing is allocated and nothing waits for the device. */
 #include <math.h>
@@ -25,6 +26,7 @@ typedef struct WallState {
     index_type P;
     dfl_grid3 pgrid, wgrid;
     index_type *wstart, *wlist;  /* device [wcells + 1], [entries] */
+    index_type* plane;           /* device [nf]: plane id of every record (friction contact keys) */
     index_type* dropped;         /* device [1] */
 } WallState;
 
@@ -34,7 +36,7 @@ typedef struct WallState {
 void DflWallsFree(WallState* w) {
     if (!w) return;
     HIPGUARD(hipStreamSynchronize(DflStream()));
-    CdamFreeDevice(w->tri, 0); CdamFreeDevice(w->wstart, 0); CdamFreeDevice(w->wlist, 0); CdamFreeDevice(w->dropped, 0);
+    CdamFreeDevice(w->tri, 0); CdamFreeDevice(w->plane, 0); CdamFreeDevice(w->wstart, 0); CdamFreeDevice(w->wlist, 0); CdamFreeDevice(w->dropped, 0);
     free(w->h_tri);
     CdamFreeHost(w, SIZE_OF(WallState));
 }
@@ -138,10 +140,62 @@ static void build_grids(WallState* w, f64 R, index_type P) {
     w->P = P;
 }
 
+/* plane ids: the smallest record id among the records whose plane equals this one under de-duplication rule 1 (normals
+ * equal to 1e-12, offsets to tol).  The records are sorted by their plane rounded to a grid much coarser than those
+ * tolerances (2^-30 on the normal, 2^10 tol on the offset), then by id; within a run of equal rounded planes every record
+ * joins the first earlier group of the run it matches.  Rounding noise splits a plane only when it straddles a grid line */
+typedef struct PlaneKey {
+    int64_t q[4];
+    index_type id;
+} PlaneKey;
+
+static int cmp_plane_key(const void* a, const void* b) {
+    const PlaneKey* x = (const PlaneKey*)a;
+    const PlaneKey* y = (const PlaneKey*)b;
+    for (int k = 0; k < 4; ++k)
+        if (x->q[k] != y->q[k]) return x->q[k] < y->q[k] ? -1 : 1;
+    return (x->id > y->id) - (x->id < y->id);
+}
+
+static b32 same_plane(const dfl_wall_tri* a, const dfl_wall_tri* b, f64 tol) {
+    return fabs(a->n[0] - b->n[0]) <= 1e-12 && fabs(a->n[1] - b->n[1]) <= 1e-12 && fabs(a->n[2] - b->n[2]) <= 1e-12 &&
+           fabs(a->off - b->off) <= tol;
+}
+
+static void plane_ids(const dfl_wall_tri* tri, index_type nf, f64 tol, index_type* plane) {
+    PlaneKey* key = (PlaneKey*)malloc((size_t)(nf > 0 ? nf : 1) * sizeof(PlaneKey));
+    const f64 qn = 1073741824.0, qo = 1.0 / (1024.0 * (tol > 0.0 ? tol : 1e-300));
+    for (index_type t = 0; t < nf; ++t) {
+        for (int d = 0; d < 3; ++d) key[t].q[d] = (int64_t)llround(tri[t].n[d] * qn);
+        key[t].q[3] = (int64_t)llround(tri[t].off * qo);
+        key[t].id = t;
+    }
+    qsort(key, (size_t)nf, sizeof(PlaneKey), cmp_plane_key);
+    for (index_type a = 0; a < nf;) {
+        index_type b = a + 1;
+        while (b < nf && memcmp(key[b].q, key[a].q, sizeof key[a].q) == 0) ++b;
+        /* run [a, b), ascending id: a record is a group leader unless it matches an earlier leader of the run */
+        for (index_type r = a; r < b; ++r) {
+            const index_type t = key[r].id;
+            plane[t] = t;
+            for (index_type u = a; u < r; ++u) {
+                const index_type l = key[u].id;
+                if (plane[l] == l && same_plane(&tri[l], &tri[t], tol)) {
+                    plane[t] = l;
+                    break;
+                }
+            }
+        }
+        a = b;
+    }
+    free(key);
+}
+
 void ParticleContextSetWallMesh(ParticleContext* ctx, Mesh3D* mesh, index_type group_mask) {
     ParticleExt* x = (ParticleExt*)ctx->ext;
     DflWallsFree(x->walls);
     x->walls = NULL;
+    DflFrictionClearHistory(ctx); /* the keys of the wall contacts change meaning */
     if (!mesh) return;
     const index_type N = Mesh3DNumNode(mesh), T = Mesh3DNumTet(mesh);
     if (N <= 0 || T <= 0) {
@@ -228,6 +282,11 @@ void ParticleContextSetWallMesh(ParticleContext* ctx, Mesh3D* mesh, index_type g
     free(xg);
     w->tri = (dfl_wall_tri*)CdamMallocDevice((ptrdiff_t)(nf > 0 ? nf : 1) * SIZE_OF(dfl_wall_tri));
     HIPGUARD(hipMemcpy(w->tri, w->h_tri, (size_t)(nf > 0 ? nf : 1) * sizeof(dfl_wall_tri), H2D));
+    index_type* h_plane = (index_type*)malloc((size_t)(nf > 0 ? nf : 1) * sizeof(index_type));
+    plane_ids(w->h_tri, nf, 1e-12 * w->scale, h_plane);
+    w->plane = (index_type*)CdamMallocDevice((ptrdiff_t)(nf > 0 ? nf : 1) * SIZE_OF(index_type));
+    HIPGUARD(hipMemcpy(w->plane, h_plane, (size_t)(nf > 0 ? nf : 1) * sizeof(index_type), H2D));
+    free(h_plane);
     w->dropped = (index_type*)CdamMallocDevice(SIZE_OF(index_type));
     HIPGUARD(hipMemset(w->dropped, 0, sizeof(index_type)));
     build_grids(w, ParticleRadius(ctx), ctx->num_particle);
@@ -257,6 +316,17 @@ void DflWallsComputeForces(ParticleContext* ctx) {
     const f64* coord = ArrayData(ParticleCTXDeviceCoord(ctx));
     const f64* vel = ArrayData(ParticleCTXDeviceVel(ctx));
     f64* acc = ArrayData(ParticleCTXDeviceAcc(ctx));
+    if (x->omega) {
+        dfl_walls_build_cells_spin(P, coord, vel, x->omega, w->pgrid, x->cell_of, x->rank, x->count, x->chunk_sum, x->cell_start,
+                                   x->slot, x->order, x->sorted, x->sorted_w, s);
+        int slot = DflProfileBegin(DFL_TAG_SMALL + 1);
+        dfl_walls_forces_friction(P, x->sorted, x->sorted_w, R, ParticleMass(ctx), x->kn, x->gamma_n, DflFrictionLaw(ctx), w->pgrid,
+                                  x->order, x->cell_start, w->tri, w->plane, w->wgrid, w->wstart, w->wlist, 1e-12 * w->scale,
+                                  w->dropped, DflFrictionHistory(x), acc, x->alpha, s);
+        DflProfileEnd(slot);
+        DflRangePop();
+        return;
+    }
     dfl_walls_build_cells(P, coord, vel, w->pgrid, x->cell_of, x->rank, x->count, x->chunk_sum, x->cell_start, x->slot, x->order,
                           x->sorted, s);
     int slot = DflProfileBegin(DFL_TAG_SMALL + 1);

@@ -790,6 +790,65 @@ void ParticleContextSetWallMesh(ParticleContext* ctx, Mesh3D* mesh, index_type g
 /* wall contacts dropped since the walls were set because a particle had more than DFL_WALL_MAX_CONTACTS */
 index_type ParticleContextWallDroppedCount(const ParticleContext* ctx);
 
+/* ---- contact friction and particle rotation (build-defined; opt-in) ---------------------------------------------------
+ * A context that never calls ParticleContextSetFriction with a configuration runs the frictionless kernels, bit for bit.
+ * With friction on, every contact sweep (ParticleContextComputeForces, hence ParticleContextUpdate,
+ * ParticleContextFluidStep and the DEM sub-steps of DflTimeStep, coupled or not) adds the Cundall-Strack tangential law
+ * to the pair, unit-box and mesh-wall contacts:
+ *   spheres    monodisperse, radius R, mass m, moment of inertia I = 2/5 m R^2; angular velocity w, angular acceleration
+ *              alpha = tau / I.  The normal law is unchanged: f_n = kn delta - gamma_n v_n, not clamped.
+ *   contact    unit normal n towards the particle; lever ell = distance from the centre to the contact point:
+ *                pair           ell = dist / 2 (the contact point is the midpoint of the centres)
+ *                wall           ell = max(R - delta, 0) (unit box, mesh face, edge or vertex; the point is q, the closest
+ *                               point of the wall)
+ *              contact-point velocity  pair: v_rel = (v_i - v_j) - ell (w_i + w_j) x n;  wall at rest: v_rel = v - ell w x n
+ *              v_t = v_rel - (v_rel . n) n
+ *   spring     xi = the contact's tangential spring from the previous sweep (0 for a new contact); it is first rotated onto
+ *              the current tangent plane keeping its length, xi <- (xi - (xi.n) n) |xi| / |xi - (xi.n) n| (0 when the
+ *              denominator is 0), then xi <- xi + v_t dt
+ *   force      F_t = -kt xi - gamma_t v_t; when |F_t| > mu max(f_n, 0) it is scaled to that cap and
+ *              xi <- -(F_t + gamma_t v_t) / kt (the spring consistent with sliding).  Load: force f_n n + F_t, torque
+ *              (-ell n) x F_t.  A pair is evaluated so that particle j's computation is the exact negation of i's: the
+ *              tangential forces are exactly opposite and the torques exactly equal, and an isolated pair conserves
+ *              sum m x x v + I w (to rounding under the semi-implicit step).
+ *   history    EVERY sweep advances the springs by the context's dt (ParticleContextSetContactModel):
+ *              ParticleContextComputeForces is no longer a pure function of the state once friction is on.  History is
+ *              matched by a 64-bit contact key, kind in the two high bits:
+ *                0 << 62 | j                  partner particle j
+ *                1 << 62 | 2 axis + side      unit-box wall (side 0: x_axis = 0, side 1: x_axis = 1)
+ *                1 << 62 | plane id           mesh face contact: the smallest triangle id among the triangles whose plane
+ *                                             equals this one under de-duplication rule 1 of the walls block (assigned at
+ *                                             ParticleContextSetWallMesh; a sphere rolling over coplanar triangles keeps
+ *                                             one history)
+ *                2 << 62 | n0 << 31 | n1      mesh edge contact, node ids n0 < n1
+ *                3 << 62 | node               mesh vertex contact
+ *              (a context has unit-box walls or mesh walls, never both, so the two wall keys do not meet.)
+ *   capacity   at most DFL_DEM_MAX_HISTORY entries per particle, pairs and walls together, taken in the sweep's visit
+ *              order (pairs, then walls).  A contact that finds no free entry gets its normal force and the tangential
+ *              force of a new contact (xi = 0), stores nothing and is counted (ParticleContextFrictionOverflowCount).
+ *   state      turning friction on allocates w and alpha (zero) and the history; later ParticleContextSetFriction calls
+ *              keep w and clear the history and the overflow count; ParticleContextSetWallMesh clears the history.
+ *              cfg NULL turns friction off and frees the state.  Nothing is allocated per sweep.
+ *   integration ParticleContextUpdate and ParticleContextFluidStep integrate w by semi-implicit Euler with alpha after the
+ *              sweep.  The fluid exerts no torque on a particle (no rotational drag, no lift).
+ *   gravity    ParticleContextSetGravity sets a body acceleration that ParticleContextUpdate (hence the uncoupled DEM
+ *              sub-steps of DflTimeStep) adds in its integration step; default 0.  The coupled sub-step keeps using
+ *              DflFluidCoupling.gravity.  acc stays the contact acceleration.
+ *   not kept   ParticleContextCopy and ParticleContextSave / Load handle coord, vel and acc only: w and the history are
+ *              neither copied nor saved. */
+#ifndef DFL_DEM_MAX_HISTORY
+#define DFL_DEM_MAX_HISTORY 16
+#endif
+typedef struct DflContactFriction {
+    f64 mu, kt, gamma_t; /* kt <= 0: 2/7 kn; gamma_t < 0: gamma_n (of ParticleContextSetContactModel at this call) */
+} DflContactFriction;
+void ParticleContextSetFriction(ParticleContext* ctx, const DflContactFriction* cfg); /* NULL: off, frees the state */
+f64* ParticleContextAngularVelocity(ParticleContext* ctx);        /* device [P][3], writable (initial spin); NULL when off */
+const f64* ParticleContextAngularAcc(const ParticleContext* ctx); /* device [P][3], torque / I of the last sweep */
+/* contacts that found no free history entry since friction was last set */
+index_type ParticleContextFrictionOverflowCount(const ParticleContext* ctx);
+void ParticleContextSetGravity(ParticleContext* ctx, const f64 g[3]); /* body acceleration of ParticleContextUpdate */
+
 #ifdef __cplusplus
 }
 #endif

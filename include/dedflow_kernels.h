@@ -535,6 +535,63 @@ void dfl_walls_forces(dfl_index P, const dfl_value* sorted, dfl_value radius, df
                       dfl_grid3 wall_grid, const dfl_index* wall_start, const dfl_index* wall_list, dfl_value tol,
                       dfl_index* dropped, dfl_value* acc, void* stream);
 
+/* ---- DEM contact friction and rotation (build-defined, opt-in; csrc/dem_friction.hpp, model in include/dedflow.h)
+ *  dfl_contact_hist     one history entry (32 B): the contact key and the tangential spring xi
+ *  dfl_friction_law     mu, kt, gamma_t (resolved: kt > 0, gamma_t >= 0), the sweep's dt (the springs advance by it) and
+ *                       the moment of inertia I = 2/5 m R^2
+ *  dfl_contact_history  rows of DFL_DEM_MAX_HISTORY entries per particle id: the previous sweep's rows and live counts
+ *                       (read), this sweep's (written; the two alternate between sweeps), *overflow += the contacts of a
+ *                       particle that found no free entry
+ *    dfl_dem_build_cells_spin / dfl_walls_build_cells_spin   the cell sort, also writing sorted_w[P][3] = omega in the
+ *                           sorted order
+ *    dfl_dem_forces_friction / dfl_walls_forces_friction      the force kernels with the tangential law: acc and
+ *                           alpha = torque / I of every particle, the new history rows; plane[F] = the plane id of every
+ *                           wall triangle (include/dedflow.h, contact keys)
+ *    dfl_dem_integrate_spin  v += dt (a + g) ; x += dt v ; omega += dt alpha (omega NULL: no rotation)
+ *    dfl_dem_spin            omega += dt alpha */
+#ifndef DFL_DEM_MAX_HISTORY
+#define DFL_DEM_MAX_HISTORY 16
+#endif
+typedef struct dfl_contact_hist {
+    uint64_t key;
+    dfl_value xi[3];
+} dfl_contact_hist;
+typedef struct dfl_friction_law {
+    dfl_value mu, kt, gamma_t, dt, inertia;
+} dfl_friction_law;
+typedef struct dfl_contact_history {
+    const dfl_contact_hist* old_row;
+    const dfl_index* old_count;
+    dfl_contact_hist* new_row;
+    dfl_index* new_count;
+    dfl_index* overflow;
+} dfl_contact_history;
+void dfl_dem_build_cells_spin(dfl_index P, const dfl_value* coord, const dfl_value* vel, const dfl_value* omega, dfl_value cell,
+                              dfl_index ncell, dfl_index* cell_of, dfl_index* rank, dfl_index* count, dfl_index* chunk_sum,
+                              dfl_index* cell_start, dfl_index* slot, dfl_index* order, dfl_value* sorted, dfl_value* sorted_w,
+                              void* stream);
+void dfl_dem_sort_binned_spin(dfl_index P, dfl_index nbin, const dfl_value* coord, const dfl_value* vel, const dfl_value* omega,
+                              dfl_index* cell_of, dfl_index* rank, dfl_index* count, dfl_index* chunk_sum,
+                              dfl_index* cell_start, dfl_index* slot, dfl_index* order, dfl_value* sorted, dfl_value* sorted_w,
+                              void* stream);
+void dfl_walls_build_cells_spin(dfl_index P, const dfl_value* coord, const dfl_value* vel, const dfl_value* omega,
+                                dfl_grid3 grid, dfl_index* cell_of, dfl_index* rank, dfl_index* count, dfl_index* chunk_sum,
+                                dfl_index* cell_start, dfl_index* slot, dfl_index* order, dfl_value* sorted,
+                                dfl_value* sorted_w, void* stream);
+void dfl_dem_forces_friction(dfl_index P, const dfl_value* sorted, const dfl_value* sorted_w, dfl_value radius, dfl_value mass,
+                             dfl_value kn, dfl_value gamma_n, dfl_friction_law law, dfl_value cell, dfl_index ncell,
+                             const dfl_index* order, const dfl_index* cell_start, dfl_contact_history hist, dfl_value* acc,
+                             dfl_value* alpha, void* stream);
+void dfl_walls_forces_friction(dfl_index P, const dfl_value* sorted, const dfl_value* sorted_w, dfl_value radius,
+                               dfl_value mass, dfl_value kn, dfl_value gamma_n, dfl_friction_law law, dfl_grid3 grid,
+                               const dfl_index* order, const dfl_index* cell_start, const dfl_wall_tri* tri,
+                               const dfl_index* plane, dfl_grid3 wall_grid, const dfl_index* wall_start,
+                               const dfl_index* wall_list, dfl_value tol, dfl_index* dropped, dfl_contact_history hist,
+                               dfl_value* acc, dfl_value* alpha, void* stream);
+void dfl_dem_integrate_spin(dfl_index P, dfl_value dt, const dfl_value* g, dfl_value* coord, dfl_value* vel,
+                            const dfl_value* acc, dfl_value* omega, const dfl_value* alpha, void* stream);
+void dfl_dem_spin(dfl_index P, dfl_value dt, dfl_value* omega, const dfl_value* alpha, void* stream);
+
 /* ---- particle-fluid coupling (build-defined, csrc/k_couple.hip; model in include/dedflow.h)
  *    dfl_couple_sort_v2e      every V2E list ascending (one thread per node)
  *    dfl_couple_neighbours    nbr[4t + k] = tet across the face opposite local vertex k, -1 on the boundary

@@ -6,9 +6,10 @@ the walk with the particles in the contact sweep's cell order against particle-i
 (DFL_COUPLE_CELL_ORDER=0: the walk; the drag kernel always runs in id order); and DflTimeStep (two-level PC, 2 Newton
 iterations, 10 sub-steps) coupled one-way and two-way against the uncoupled contact sweep.  With --walls every particle
 context takes its walls from all six boundary groups of the mesh (ParticleContextSetWallMesh) instead of the unit box;
-"sweep" then also times the contact sweep alone.  Prints one JSON line (and writes it to --out).
+"sweep" then also times the contact sweep alone.  With --friction every particle context turns on the contact friction
+(ParticleContextSetFriction, mu = 0.5, default kt and gamma_t).  Prints one JSON line (and writes it to --out).
 
-  python tools/probe_coupling.py [--reps 50] [--steps 3] [--walls] [--out profiles/probe_coupling.json]
+  python tools/probe_coupling.py [--reps 50] [--steps 3] [--walls] [--friction] [--out profiles/probe_coupling.json]
 """
 import argparse
 import ctypes as C
@@ -39,6 +40,7 @@ def main():
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--walls", action="store_true")
+    ap.add_argument("--friction", action="store_true")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     L = api.lib()
@@ -52,7 +54,7 @@ def main():
     P = api.Problem(m, maxit=120, atol=1e-12, rtol=1e-4)
     L.KrylovSetPCType(P.ksp, api.PC_TWOLEVEL)
     w_d = api.DeviceArray.from_numpy(wg)
-    out = {"M": a.M, "tets": m.num_tet, "particles": a.particles, "R": R, "walls": a.walls}
+    out = {"M": a.M, "tets": m.num_tet, "particles": a.particles, "R": R, "walls": a.walls, "friction": a.friction}
 
     def particles(order=True):
         if not order:
@@ -62,6 +64,8 @@ def main():
             t0 = time.perf_counter()
             if a.walls:
                 pc.set_walls(P)
+            if a.friction:
+                pc.set_friction(0.5)
             pc.couple(P, two_way=True)
             api.sync()
             return pc, time.perf_counter() - t0
@@ -122,6 +126,8 @@ def main():
         pc = api.Particles(x, v, R, mass=mass, dt=1e-4)
         if a.walls:
             pc.set_walls(P)
+        if a.friction:
+            pc.set_friction(0.5)
         if key != "uncoupled":
             pc.couple(P, two_way=key == "two_way")
         st = [api.DeviceArray.from_numpy(q) for q in (wg, 0.1 * dw0, 0.1 * dw0)]
