@@ -218,7 +218,6 @@ class Particles:
         L = lib()
         L.Init(0, None)
         P = coord.size // 3
-        self.P = P
         self.ctx = L.ParticleContextCreate(P)
         c = self.ctx.contents
         c.buff[0], c.buff[1] = mass, radius
@@ -226,6 +225,11 @@ class Particles:
         C.memmove(c.h_arr[1].contents.data, np.ascontiguousarray(vel).ctypes.data, 24 * P)
         L.ParticleContextUpdateDevice(self.ctx)
         L.ParticleContextSetContactModel(self.ctx, kn, gamma_n, dt)
+
+    @property
+    def P(self):
+        """the current particle count (changes under add() / remove())"""
+        return int(self.ctx.contents.num_particle)
 
     def compute_forces(self):
         lib().ParticleContextComputeForces(self.ctx)
@@ -318,8 +322,64 @@ class Particles:
         """angular acceleration (torque / I) [P][3] of the last contact sweep"""
         return d2h(self._spin_ptr("ParticleContextAngularAcc"), 3 * self.P, np.float64).reshape(self.P, 3)
 
+    def friction_history(self):
+        """the contact history the next sweep reads: keys [P][16] uint64, springs xi [P][16][3], live counts [P]"""
+        rows, counts = vp(), C.POINTER(C.c_int32)()
+        lib().ParticleContextFrictionHistory(self.ctx, C.byref(rows), C.byref(counts))
+        if not rows.value:
+            raise RuntimeError("friction is off: call set_friction first")
+        raw = d2h(rows.value, 4 * 16 * self.P, np.float64).reshape(self.P, 16, 4)
+        keys = raw[:, :, 0].copy().view(np.uint64)
+        return keys, raw[:, :, 1:].copy(), d2h(C.cast(counts, vp).value, self.P, np.int32)
+
     def friction_overflow_count(self):
         return int(lib().ParticleContextFrictionOverflowCount(self.ctx))
+
+    # ---- particle inflow and outflow (build-defined; model in include/dedflow.h) ------------------------------------
+    def set_outflow(self, planes=(), outside_mesh=False):
+        """ParticleContextSetOutflow: remove() drops the particles with n . x > d for any (n0, n1, n2, d) in `planes` and, with
+        outside_mesh on a coupled context, those located outside the mesh; planes None turns outflow off"""
+        if planes is None:
+            lib().ParticleContextSetOutflow(self.ctx, None)
+            return
+        planes = np.asarray(planes, dtype=np.float64).reshape(-1, 4)
+        if len(planes) > DFL_OUTFLOW_MAX_PLANES:
+            raise ValueError(f"at most {DFL_OUTFLOW_MAX_PLANES} outflow planes")
+        cfg = DflParticleOutflow()
+        cfg.num_planes = len(planes)
+        for k, pl in enumerate(planes):
+            for d in range(4):
+                cfg.plane[k][d] = float(pl[d])
+        cfg.outside_mesh = 1 if outside_mesh else 0
+        lib().ParticleContextSetOutflow(self.ctx, C.byref(cfg))
+
+    def set_inflow(self, origin, edge_u, edge_v, vel=(0.0, 0.0, 0.0), per_call=1.0, jitter=0.0, seed=0, max_particles=2**31 - 1):
+        """ParticleContextSetInflow: add() inserts into the slots of the inlet rectangle origin + s edge_u + t edge_v;
+        origin None turns inflow off"""
+        if origin is None:
+            lib().ParticleContextSetInflow(self.ctx, None)
+            return
+        v3 = lambda a: (C.c_double * 3)(*[float(q) for q in a])
+        cfg = DflParticleInflow(v3(origin), v3(edge_u), v3(edge_v), v3(vel), float(per_call), float(jitter), int(seed),
+                                int(max_particles))
+        lib().ParticleContextSetInflow(self.ctx, C.byref(cfg))
+
+    def add(self):
+        lib().ParticleContextAdd(self.ctx)
+
+    def remove(self):
+        lib().ParticleContextRemove(self.ctx)
+
+    def tags(self):
+        """stable 64-bit tag of every particle (None until inflow or outflow was set)"""
+        p = lib().ParticleContextTag(self.ctx)
+        return None if not p else d2h(p, self.P, np.int64)
+
+    def flow_stats(self):
+        """dict inserted / removed / blocked since the first set_inflow / set_outflow"""
+        st = DflParticleFlowStats()
+        lib().ParticleContextFlowStats(self.ctx, C.byref(st))
+        return {"inserted": int(st.inserted), "removed": int(st.removed), "blocked": int(st.blocked)}
 
     def arrays(self):
         """(coord, vel, acc) copied back from the device"""
@@ -332,6 +392,22 @@ class Particles:
 
 class DflContactFriction(C.Structure):
     _fields_ = [("mu", C.c_double), ("kt", C.c_double), ("gamma_t", C.c_double)]
+
+
+DFL_OUTFLOW_MAX_PLANES = 8
+
+
+class DflParticleOutflow(C.Structure):
+    _fields_ = [("num_planes", C.c_int32), ("plane", (C.c_double * 4) * DFL_OUTFLOW_MAX_PLANES), ("outside_mesh", C.c_int32)]
+
+
+class DflParticleInflow(C.Structure):
+    _fields_ = [("origin", C.c_double * 3), ("edge_u", C.c_double * 3), ("edge_v", C.c_double * 3), ("vel", C.c_double * 3),
+                ("per_call", C.c_double), ("jitter", C.c_double), ("seed", C.c_uint64), ("max_particles", C.c_int32)]
+
+
+class DflParticleFlowStats(C.Structure):
+    _fields_ = [("inserted", C.c_int64), ("removed", C.c_int64), ("blocked", C.c_int64)]
 
 
 class DflFluidCoupling(C.Structure):
@@ -437,6 +513,12 @@ def _declare(L):
     f("ParticleContextAngularVelocity", vp, [C.POINTER(ParticleContext)]); f("ParticleContextAngularAcc", vp, [C.POINTER(ParticleContext)])
     f("ParticleContextFrictionOverflowCount", i32, [C.POINTER(ParticleContext)])
     f("ParticleContextSetGravity", None, [C.POINTER(ParticleContext), C.POINTER(C.c_double)])
+    f("ParticleContextSetOutflow", None, [C.POINTER(ParticleContext), C.POINTER(DflParticleOutflow)])
+    f("ParticleContextSetInflow", None, [C.POINTER(ParticleContext), C.POINTER(DflParticleInflow)])
+    f("ParticleContextAdd", None, [C.POINTER(ParticleContext)]); f("ParticleContextRemove", None, [C.POINTER(ParticleContext)])
+    f("ParticleContextFlowStats", None, [C.POINTER(ParticleContext), C.POINTER(DflParticleFlowStats)])
+    f("ParticleContextTag", vp, [C.POINTER(ParticleContext)])
+    f("ParticleContextFrictionHistory", None, [C.POINTER(ParticleContext), C.POINTER(vp), C.POINTER(C.POINTER(C.c_int32))])
     f("DflMeshSetExternalLoad", None, [C.POINTER(Mesh3D), vp])
     f("SolveFlowSystem", i32, [C.POINTER(Mesh3D), vp, vp, vp, C.POINTER(Matrix), vp, vp, vp, vp, i32, i32, vp, vp])
     f("DflTimeStep", i32, [C.POINTER(Mesh3D), vp, vp, vp, C.POINTER(Matrix), vp, vp, vp, vp, i32, i32, C.POINTER(ParticleContext),

@@ -14,25 +14,6 @@
 #include "dedflow_kernels.h"
 #include "host_private.h"
 
-typedef struct CoupleState {
-    Mesh3D* mesh;
-    index_type N, T, P;
-    DflFluidCoupling cfg;
-    b32 use_order;                   /* locate in the contact sweep's cell order (DFL_COUPLE_CELL_ORDER=0: id order) */
-    index_type *vrow, *vcol;         /* device V2E map [N+1], [4T], every list ascending */
-    index_type* nbr;                 /* device [T][4] */
-    index_type* seed;                /* device [gdim^3] */
-    index_type gdim;
-    f64 lo[3], inv_h[3];
-    index_type *tet, *lost;          /* device [P], [1] */
-    f64 *lambda, *imp;               /* device [P][4], [P][3] */
-    index_type *tcount, *tstart;     /* device [T], [T+1] */
-    index_type *rank, *slot, *members; /* device [P] */
-    void* scan_tmp;
-    int64_t scan_bytes;
-    f64* load;                       /* device [3N]: the reaction load DflTimeStep registers */
-    f64 imp_time;                    /* time the impulses were accumulated over */
-} CoupleState;
 
 static CoupleState* state(const ParticleContext* ctx) { return ((ParticleExt*)ctx->ext)->couple; }
 
@@ -43,6 +24,7 @@ void DflCoupleFree(CoupleState* c) {
     CdamFreeDevice(c->tet, 0); CdamFreeDevice(c->lost, 0); CdamFreeDevice(c->lambda, 0); CdamFreeDevice(c->imp, 0);
     CdamFreeDevice(c->tcount, 0); CdamFreeDevice(c->tstart, 0); CdamFreeDevice(c->rank, 0); CdamFreeDevice(c->slot, 0);
     CdamFreeDevice(c->members, 0); CdamFreeDevice(c->scan_tmp, 0); CdamFreeDevice(c->load, 0);
+    CdamFreeDevice(c->rem_load, 0); CdamFreeDevice(c->rem_tmp, 0);
     CdamFreeHost(c, SIZE_OF(CoupleState));
 }
 
@@ -143,6 +125,8 @@ static void build_mesh_tables(CoupleState* c, Mesh3D* mesh) {
     c->scan_bytes = dfl_scan_temp_bytes(T);
     c->scan_tmp = CdamMallocDevice((ptrdiff_t)c->scan_bytes);
     c->load = (f64*)CdamMallocDevice((ptrdiff_t)(N > 0 ? N : 1) * 3 * SIZE_OF(f64));
+    c->rem_load = (f64*)CdamMallocDevice((ptrdiff_t)(N > 0 ? N : 1) * 3 * SIZE_OF(f64));
+    c->rem_tmp = (f64*)CdamMallocDevice((ptrdiff_t)(N > 0 ? N : 1) * 3 * SIZE_OF(f64));
     HIPGUARD(hipStreamSynchronize(s));
 }
 
@@ -167,7 +151,7 @@ void ParticleContextSetFluidCoupling(ParticleContext* ctx, Mesh3D* mesh, const D
         c->T = Mesh3DNumTet(mesh);
         c->P = P;
         build_mesh_tables(c, mesh);
-        const ptrdiff_t np = P > 0 ? P : 1;
+        const ptrdiff_t np = x->cap > 0 ? x->cap : 1; /* every per-particle buffer has the context's capacity */
         c->tet = (index_type*)CdamMallocDevice(np * SIZE_OF(index_type));
         c->lost = (index_type*)CdamMallocDevice(SIZE_OF(index_type));
         c->lambda = (f64*)CdamMallocDevice(np * 4 * SIZE_OF(f64));
@@ -186,15 +170,17 @@ void ParticleContextSetFluidCoupling(ParticleContext* ctx, Mesh3D* mesh, const D
     HIPGUARD(hipMemsetAsync(c->lambda, 0, (size_t)(P > 0 ? P : 1) * 4 * sizeof(f64), s));
     HIPGUARD(hipMemsetAsync(c->imp, 0, (size_t)(P > 0 ? P : 1) * 3 * sizeof(f64), s));
     HIPGUARD(hipMemsetAsync(c->lost, 0, sizeof(index_type), s));
+    HIPGUARD(hipMemsetAsync(c->rem_load, 0, (size_t)(c->N > 0 ? c->N : 1) * 3 * sizeof(f64), s));
+    c->rem_pending = FALSE;
     c->imp_time = 0.0;
 }
 
-/* the thread -> particle map of the walk: the contact sweep's (cell, id) order when it has run (any permutation is
- * correct; neighbouring lanes then walk neighbouring tets: 10.7 / 28 us from history / cold against 11.4 / 33 us in
- * particle-id order at 1M tets and 100k particles), else particle order */
+/* the thread -> particle map of the walk: the contact sweep's (cell, id) order when it has run since the particle count
+ * last changed (any permutation is correct; neighbouring lanes then walk neighbouring tets: 10.7 / 28 us from history /
+ * cold against 11.4 / 33 us in particle-id order at 1M tets and 100k particles), else particle order */
 static const index_type* particle_order(const ParticleContext* ctx, const CoupleState* c) {
     const ParticleExt* x = (const ParticleExt*)ctx->ext;
-    return c->use_order && x->order && x->cap_particle >= ctx->num_particle ? x->order : NULL;
+    return c->use_order && x->order && x->order_valid && x->cap_particle >= ctx->num_particle ? x->order : NULL;
 }
 
 void ParticleContextLocate(ParticleContext* ctx) {
@@ -257,10 +243,27 @@ void ParticleContextReactionLoad(ParticleContext* ctx, f64* load) {
     dfl_couple_sort_by_tet(P, c->T, c->tet, c->tcount, c->rank, c->tstart, c->slot, c->members, c->scan_tmp, c->scan_bytes, s);
     dfl_couple_node_load(c->N, c->vrow, c->vcol, Mesh3DDevice(c->mesh)->ien, c->tstart, c->members, c->lambda, c->imp,
                          1.0 / c->imp_time, load, s);
+    if (c->rem_pending) { /* the impulse of the particles removed since the last call (ParticleContextRemove) */
+        dfl_daxpy(c->N * 3, 1.0 / c->imp_time, c->rem_load, load, s);
+        HIPGUARD(hipMemsetAsync(c->rem_load, 0, (size_t)c->N * 3 * sizeof(f64), s));
+        c->rem_pending = FALSE;
+    }
     HIPGUARD(hipMemsetAsync(c->imp, 0, (size_t)(P > 0 ? P : 1) * 3 * sizeof(f64), s));
     DflProfileEnd(slot);
     c->imp_time = 0.0;
     DflRangePop();
+}
+
+void DflCoupleAccumulateRemoved(ParticleContext* ctx, const index_type* rtet) {
+    CoupleState* c = state(ctx);
+    hipStream_t s = DflStream();
+    /* the pattern of the reaction load, restricted to the removed particles: rem_tmp = -sum lambda imp, then rem_load += it */
+    dfl_couple_sort_by_tet(ctx->num_particle, c->T, rtet, c->tcount, c->rank, c->tstart, c->slot, c->members, c->scan_tmp,
+                           c->scan_bytes, s);
+    dfl_couple_node_load(c->N, c->vrow, c->vcol, Mesh3DDevice(c->mesh)->ien, c->tstart, c->members, c->lambda, c->imp, 1.0,
+                         c->rem_tmp, s);
+    dfl_daxpy(c->N * 3, 1.0, c->rem_tmp, c->rem_load, s);
+    c->rem_pending = TRUE;
 }
 
 Mesh3D* DflParticleCoupledMesh(const ParticleContext* ctx) { return state(ctx) ? state(ctx)->mesh : NULL; }

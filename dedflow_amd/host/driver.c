@@ -125,7 +125,8 @@ index_type SolveFlowSystem(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matr
 /* one time step of main.c:537-565: predictor, Newton solve, corrector; optional DEM sub-steps.  A particle context coupled
  * to this mesh (ParticleContextSetFluidCoupling) instead takes `dem_substeps` fluid sub-steps after the corrector, in the
  * fluid state of the new time level; with two_way, the Newton solve sees the reaction load of the previous step's
- * sub-steps as an external load. */
+ * sub-steps as an external load.  With inflow / outflow set on the context (ParticleContextSetInflow / SetOutflow),
+ * ParticleContextAdd runs after the predictor and ParticleContextRemove after the particle sub-steps. */
 index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* J, f64* F, f64* dx, Krylov* ksp, Dirichlet** bcs,
                        index_type nbc, index_type newton_maxit, ParticleContext* pctx, index_type dem_substeps, f64* rnorm_out,
                        f64* rnorm_init_out) {
@@ -146,6 +147,7 @@ index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* 
         DflMeshSetExternalLoad(mesh, reaction);
     }
     dfl_alpha_predict(N, fac_pred, dwg, s);
+    if (pctx) ParticleContextAdd(pctx); /* main.c:547-548; a no-op unless inflow is set */
     index_type it = SolveFlowSystem(mesh, wgold, dwgold, dwg, J, F, dx, ksp, bcs, nbc, newton_maxit, rnorm_out, rnorm_init_out);
     if (reaction) DflMeshSetExternalLoad(mesh, user_load);
     if (pctx && !coupled)
@@ -153,6 +155,7 @@ index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* 
     dfl_alpha_correct(N, fac_corr[0], fac_corr[1], wgold, dwgold, dwg, s);
     if (coupled)
         for (index_type k = 0; k < dem_substeps; ++k) ParticleContextFluidStep(pctx, wgold); /* u at t_{n+1} */
+    if (pctx) ParticleContextRemove(pctx); /* main.c:568-569; a no-op unless outflow is set */
     DflRangePop();
     return it;
 }

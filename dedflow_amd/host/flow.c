@@ -1,0 +1,403 @@
+/* Particle inflow and outflow: ParticleContextAdd and ParticleContextRemove (build-defined: empty hooks in the reference,
+ * Particle.c:120-130; model in include/dedflow.h, kernels in dedflow_amd/csrc/k_flow.hip).
+ *
+ * Every per-particle buffer of a context is sized to its capacity x->cap >= num_particle.  Remove scatters the survivors
+ * into spare buffers of the same capacity and swaps the pointers (the friction history into the other ping-pong row
+ * set, which flips); Add appends in place after growing the capacity by x1.5 when it must.  Each call reads the new count
+ * back (4 bytes) and allocates nothing unless the capacity grows. */
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+#include "dedflow.h"
+#include "dedflow_kernels.h"
+#include "host_private.h"
+
+typedef struct FlowState {
+    b32 in_on, out_on;
+    DflParticleInflow in;
+    DflParticleOutflow out;
+    dfl_inlet inlet;                 /* lattice of the current radius */
+    f64 inlet_R;                     /* radius the lattice was built for */
+    index_type nslot;
+    uint64_t call;                   /* Add calls since ParticleContextSetInflow */
+    f64 credit;
+    int64_t next_tag;
+    DflParticleFlowStats stats;
+    index_type cap;                  /* capacity the buffers below (and the spares) are sized for */
+    int64_t *tag, *tag_spare;        /* device [cap] */
+    f64* spare3[6];                  /* device [cap][3]: coord, vel, acc, omega, alpha, imp */
+    index_type* tet_spare;           /* device [cap] */
+    f64* lambda_spare;               /* device [cap][4] */
+    index_type *keep, *newid, *rtet; /* device [cap], [cap + 1], [cap] */
+    void* scan_tmp;
+    int64_t scan_bytes;
+    index_type *blocked, *slot, *slot_out; /* device [nslot] */
+    uint64_t *key, *key_out;               /* device [nslot] */
+    void* sort_tmp;
+    int64_t sort_bytes;
+    index_type* count;               /* device [1] */
+} FlowState;
+
+static void free_slots(FlowState* f) {
+    CdamFreeDevice(f->blocked, 0); CdamFreeDevice(f->slot, 0); CdamFreeDevice(f->slot_out, 0);
+    CdamFreeDevice(f->key, 0); CdamFreeDevice(f->key_out, 0); CdamFreeDevice(f->sort_tmp, 0);
+    f->blocked = f->slot = f->slot_out = NULL;
+    f->key = f->key_out = NULL;
+    f->sort_tmp = NULL;
+}
+
+static void free_spares(FlowState* f) {
+    for (int k = 0; k < 6; ++k) {
+        CdamFreeDevice(f->spare3[k], 0);
+        f->spare3[k] = NULL;
+    }
+    CdamFreeDevice(f->tag_spare, 0); CdamFreeDevice(f->tet_spare, 0); CdamFreeDevice(f->lambda_spare, 0);
+    f->tag_spare = NULL;
+    f->tet_spare = NULL;
+    f->lambda_spare = NULL;
+}
+
+/* the scratch of a capacity: tags are carried, the rest is scratch */
+static void free_capacity_scratch(FlowState* f) {
+    CdamFreeDevice(f->keep, 0); CdamFreeDevice(f->newid, 0); CdamFreeDevice(f->rtet, 0); CdamFreeDevice(f->scan_tmp, 0);
+    free_spares(f);
+}
+static void alloc_capacity_scratch(FlowState* f, index_type cap) {
+    const ptrdiff_t n = cap > 0 ? cap : 1;
+    f->keep = (index_type*)CdamMallocDevice(n * SIZE_OF(index_type));
+    f->newid = (index_type*)CdamMallocDevice((n + 1) * SIZE_OF(index_type));
+    f->rtet = (index_type*)CdamMallocDevice(n * SIZE_OF(index_type));
+    f->scan_bytes = dfl_scan_temp_bytes((index_type)n);
+    f->scan_tmp = CdamMallocDevice((ptrdiff_t)f->scan_bytes);
+    f->tag_spare = (int64_t*)CdamMallocDevice(n * SIZE_OF(int64_t));
+    f->cap = cap;
+}
+
+void DflFlowFree(FlowState* f) {
+    if (!f) return;
+    HIPGUARD(hipStreamSynchronize(DflStream()));
+    free_slots(f);
+    free_capacity_scratch(f);
+    CdamFreeDevice(f->tag, 0); CdamFreeDevice(f->count, 0);
+    CdamFreeHost(f, SIZE_OF(FlowState));
+}
+
+/* the flow state of a context: created (tags 0 .. P-1) at the first Set call */
+static FlowState* flow_state(ParticleContext* ctx) {
+    ParticleExt* x = (ParticleExt*)ctx->ext;
+    if (x->flow) return x->flow;
+    const index_type P = ctx->num_particle;
+    FlowState* f = (FlowState*)CdamMallocHost(SIZE_OF(FlowState));
+    memset(f, 0, sizeof *f);
+    const ptrdiff_t n = x->cap > 0 ? x->cap : 1;
+    f->tag = (int64_t*)CdamMallocDevice(n * SIZE_OF(int64_t));
+    f->count = (index_type*)CdamMallocDevice(SIZE_OF(index_type));
+    alloc_capacity_scratch(f, x->cap);
+    int64_t* h = (int64_t*)malloc((size_t)n * sizeof(int64_t));
+    for (index_type i = 0; i < P; ++i) h[i] = i;
+    HIPGUARD(hipStreamSynchronize(DflStream()));
+    if (P > 0) HIPGUARD(hipMemcpy(f->tag, h, (size_t)P * sizeof(int64_t), H2D));
+    free(h);
+    f->next_tag = P;
+    x->flow = f;
+    return f;
+}
+
+/* a device buffer of new_bytes holding the first keep_bytes of `old` (freed); stream-ordered */
+static void* regrow(void* old, size_t keep_bytes, size_t new_bytes) {
+    void* p = CdamMallocDevice((ptrdiff_t)new_bytes);
+    if (old && keep_bytes) HIPGUARD(hipMemcpyAsync(p, old, keep_bytes, hipMemcpyDeviceToDevice, DflStream()));
+    CdamFreeDevice(old, 0);
+    return p;
+}
+#define REGROW(ptr, keep_elems, new_elems) \
+    ((ptr) = regrow((ptr), (size_t)(keep_elems) * sizeof *(ptr), (size_t)(new_elems) * sizeof *(ptr)))
+
+/* the spares the next compaction writes, for the state that is on now */
+static void ensure_spares(ParticleContext* ctx) {
+    ParticleExt* x = (ParticleExt*)ctx->ext;
+    FlowState* f = x->flow;
+    const ptrdiff_t n = x->cap > 0 ? x->cap : 1;
+    const int need3 = 3 + (x->omega ? 2 : 0) + (x->couple ? 1 : 0); /* coord, vel, acc, [w, alpha], [imp] */
+    for (int k = 0; k < need3; ++k)
+        if (!f->spare3[k]) f->spare3[k] = (f64*)CdamMallocDevice(n * 3 * SIZE_OF(f64));
+    if (x->couple && !f->tet_spare) {
+        f->tet_spare = (index_type*)CdamMallocDevice(n * SIZE_OF(index_type));
+        f->lambda_spare = (f64*)CdamMallocDevice(n * 4 * SIZE_OF(f64));
+    }
+}
+
+/* capacity >= need: every buffer sized by the particle count, the live entries carried */
+static void grow(ParticleContext* ctx, index_type need) {
+    ParticleExt* x = (ParticleExt*)ctx->ext;
+    FlowState* f = x->flow;
+    if (need <= x->cap) return;
+    const int64_t want = (int64_t)x->cap + x->cap / 2;
+    const index_type cap = want > need ? (want < INT32_MAX / DFL_DEM_MAX_HISTORY ? (index_type)want : need) : need;
+    const index_type P = ctx->num_particle;
+    HIPGUARD(hipStreamSynchronize(DflStream()));
+    for (int k = 0; k < 3; ++k) {
+        Array* d = ctx->d_arr[k];
+        REGROW(d->data, 3 * (size_t)P, 3 * (size_t)cap);
+        Array* h = ctx->h_arr[k];
+        f64* hd = (f64*)CdamMallocHost((ptrdiff_t)cap * 3 * SIZE_OF(f64));
+        memset(hd, 0, (size_t)cap * 3 * sizeof(f64));
+        if (P > 0) memcpy(hd, h->data, (size_t)P * 3 * sizeof(f64));
+        CdamFreeHost(h->data, (ptrdiff_t)x->cap * 3 * SIZE_OF(f64));
+        h->data = hd;
+    }
+    if (x->omega) {
+        REGROW(x->omega, 3 * (size_t)P, 3 * (size_t)cap);
+        REGROW(x->alpha, 3 * (size_t)P, 3 * (size_t)cap);
+        REGROW(x->sorted_w, 0, 3 * (size_t)cap);
+        for (int k = 0; k < 2; ++k) {
+            REGROW(x->hist[k], (size_t)P * DFL_DEM_MAX_HISTORY, (size_t)cap * DFL_DEM_MAX_HISTORY);
+            REGROW(x->hist_count[k], P, cap);
+        }
+    }
+    CoupleState* c = x->couple;
+    if (c) {
+        REGROW(c->tet, P, cap);
+        REGROW(c->lambda, 4 * (size_t)P, 4 * (size_t)cap);
+        REGROW(c->imp, 3 * (size_t)P, 3 * (size_t)cap);
+        REGROW(c->rank, 0, cap);
+        REGROW(c->slot, 0, cap);
+        REGROW(c->members, 0, cap);
+    }
+    REGROW(f->tag, P, cap);
+    free_capacity_scratch(f);
+    alloc_capacity_scratch(f, cap);
+    x->cap = cap;
+    if (f->out_on) ensure_spares(ctx);
+}
+
+static void set_count(ParticleContext* ctx, index_type P) {
+    ParticleExt* x = (ParticleExt*)ctx->ext;
+    ctx->num_particle = P;
+    for (int k = 0; k < 3; ++k) ctx->h_arr[k]->len = ctx->d_arr[k]->len = 3 * P;
+    if (x->couple) x->couple->P = P;
+    x->order_valid = FALSE; /* the sweep's permutation holds the old ids */
+}
+
+static index_type read_count(const index_type* d) {
+    index_type n = 0;
+    hipStream_t s = DflStream();
+    HIPGUARD(hipMemcpyAsync(&n, d, sizeof n, D2H, s));
+    HIPGUARD(hipStreamSynchronize(s));
+    return n;
+}
+
+void ParticleContextSetOutflow(ParticleContext* ctx, const DflParticleOutflow* cfg) {
+    ParticleExt* x = (ParticleExt*)ctx->ext;
+    if (!cfg) {
+        if (x->flow) x->flow->out_on = FALSE;
+        return;
+    }
+    ASSERT(cfg->num_planes >= 0 && cfg->num_planes <= DFL_OUTFLOW_MAX_PLANES && "ParticleContextSetOutflow: num_planes");
+    FlowState* f = flow_state(ctx);
+    f->out = *cfg;
+    f->out_on = TRUE;
+    ensure_spares(ctx);
+}
+
+static f64 norm3(const f64* a) { return sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]); }
+
+/* the slot lattice of include/dedflow.h for radius R (slot buffers sized to it) */
+static void build_inlet(FlowState* f, f64 R) {
+    const DflParticleInflow* in = &f->in;
+    dfl_inlet* L = &f->inlet;
+    memset(L, 0, sizeof *L);
+    const f64 lu = norm3(in->edge_u), lv = norm3(in->edge_v);
+    const f64 nuf = R > 0.0 ? floor(lu / (2.0 * R)) : 0.0, nvf = R > 0.0 ? floor(lv / (2.0 * R)) : 0.0;
+    ASSERT(nuf * nvf <= (f64)(1 << 24) && "ParticleContextSetInflow: more than 2^24 inlet slots");
+    L->nu = (index_type)nuf;
+    L->nv = (index_type)nvf;
+    const f64 jitter = in->jitter < 0.0 ? 0.0 : (in->jitter > 1.0 ? 1.0 : in->jitter);
+    if (L->nu > 0 && L->nv > 0) {
+        L->ju = jitter * (0.5 * (lu / (f64)L->nu - 2.0 * R));
+        L->jv = jitter * (0.5 * (lv / (f64)L->nv - 2.0 * R));
+        L->pitch_u = lu / (f64)L->nu;
+        L->pitch_v = lv / (f64)L->nv;
+        for (int d = 0; d < 3; ++d) {
+            L->pu[d] = in->edge_u[d] / (f64)L->nu;
+            L->pv[d] = in->edge_v[d] / (f64)L->nv;
+            L->base[d] = (in->origin[d] + 0.5 * L->pu[d]) + 0.5 * L->pv[d];
+            L->uhat[d] = in->edge_u[d] / lu;
+            L->vhat[d] = in->edge_v[d] / lv;
+            L->ou[d] = L->uhat[d] * L->ju;
+            L->ov[d] = L->vhat[d] * L->jv;
+            L->o[d] = in->origin[d];
+        }
+        const f64* a = L->uhat;
+        const f64* b = L->vhat;
+        f64 n[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
+        const f64 ln = norm3(n);
+        for (int d = 0; d < 3; ++d) L->nrm[d] = n[d] / ln;
+        const f64 om = fmax(fabs(in->origin[0]), fmax(fabs(in->origin[1]), fabs(in->origin[2])));
+        L->plane_tol = 1e-9 * (om + lu + lv + R);
+    }
+    for (int d = 0; d < 3; ++d) L->vel[d] = in->vel[d];
+    L->seed = in->seed;
+    f->inlet_R = R;
+    const index_type nslot = L->nu * L->nv;
+    if (nslot != f->nslot || !f->blocked) {
+        HIPGUARD(hipStreamSynchronize(DflStream()));
+        free_slots(f);
+        const ptrdiff_t n = nslot > 0 ? nslot : 1;
+        f->blocked = (index_type*)CdamMallocDevice(n * SIZE_OF(index_type));
+        f->slot = (index_type*)CdamMallocDevice(n * SIZE_OF(index_type));
+        f->slot_out = (index_type*)CdamMallocDevice(n * SIZE_OF(index_type));
+        f->key = (uint64_t*)CdamMallocDevice(n * SIZE_OF(uint64_t));
+        f->key_out = (uint64_t*)CdamMallocDevice(n * SIZE_OF(uint64_t));
+        f->sort_bytes = dfl_inflow_select_temp_bytes(nslot);
+        f->sort_tmp = CdamMallocDevice((ptrdiff_t)f->sort_bytes);
+        f->nslot = nslot;
+    }
+}
+
+void ParticleContextSetInflow(ParticleContext* ctx, const DflParticleInflow* cfg) {
+    ParticleExt* x = (ParticleExt*)ctx->ext;
+    if (!cfg) {
+        if (x->flow) x->flow->in_on = FALSE;
+        return;
+    }
+    const f64 uv = (cfg->edge_u[0] * cfg->edge_v[0] + cfg->edge_u[1] * cfg->edge_v[1]) + cfg->edge_u[2] * cfg->edge_v[2];
+    ASSERT(fabs(uv) <= 1e-9 * norm3(cfg->edge_u) * norm3(cfg->edge_v) && "ParticleContextSetInflow: edge_u must be perpendicular to edge_v");
+    ASSERT(cfg->per_call >= 0.0 && "ParticleContextSetInflow: per_call must not be negative");
+    FlowState* f = flow_state(ctx);
+    f->in = *cfg;
+    f->in_on = TRUE;
+    f->call = 0;
+    f->credit = 0.0;
+    build_inlet(f, ParticleRadius(ctx));
+}
+
+void ParticleContextRemove(ParticleContext* ctx) {
+    ParticleExt* x = (ParticleExt*)ctx->ext;
+    FlowState* f = x->flow;
+    if (!f || !f->out_on) return;
+    CoupleState* c = x->couple;
+    const b32 by_mesh = f->out.outside_mesh && c;
+    if (by_mesh) ParticleContextLocate(ctx); /* tet -1 also means "not located yet" */
+    const index_type P = ctx->num_particle;
+    if (P <= 0) return;
+    DflRangePush("ParticleContextRemove");
+    hipStream_t s = DflStream();
+    ensure_spares(ctx);
+    dfl_outflow_planes pl;
+    memset(&pl, 0, sizeof pl);
+    pl.num = f->out.num_planes;
+    memcpy(pl.plane, f->out.plane, sizeof pl.plane);
+    const b32 pending = c && c->imp_time > 0.0;
+    dfl_flow_flag(P, ArrayData(ParticleCTXDeviceCoord(ctx)), pl, c ? c->tet : NULL, by_mesh ? 1 : 0, f->keep,
+                  pending ? f->rtet : NULL, s);
+    dfl_exclusive_scan_i32(P, f->keep, f->newid, f->scan_tmp, f->scan_bytes, s);
+    const index_type Pn = read_count(f->newid + P);
+    if (Pn == P) {
+        DflRangePop();
+        return;
+    }
+    if (pending) DflCoupleAccumulateRemoved(ctx, f->rtet); /* before the compaction moves imp and lambda */
+    dfl_flow_fields fl;
+    memset(&fl, 0, sizeof fl);
+    f64* src3[6] = {ArrayData(ParticleCTXDeviceCoord(ctx)), ArrayData(ParticleCTXDeviceVel(ctx)), ArrayData(ParticleCTXDeviceAcc(ctx)),
+                    x->omega, x->alpha, c ? c->imp : NULL};
+    int n3 = 0;
+    for (int k = 0; k < 6; ++k) {
+        if (!src3[k]) continue;
+        fl.src3[n3] = src3[k];
+        fl.dst3[n3] = f->spare3[n3];
+        ++n3;
+    }
+    fl.n3 = n3;
+    fl.tag_src = f->tag;
+    fl.tag_dst = f->tag_spare;
+    if (c) {
+        fl.tet_src = c->tet;
+        fl.tet_dst = f->tet_spare;
+        fl.lambda_src = c->lambda;
+        fl.lambda_dst = f->lambda_spare;
+    }
+    const int cur = x->hist_cur;
+    if (x->omega) { /* the rows the next sweep reads move into the other row set, which becomes the current one */
+        fl.hrow_src = x->hist[cur];
+        fl.hcount_src = x->hist_count[cur];
+        fl.hrow_dst = x->hist[1 - cur];
+        fl.hcount_dst = x->hist_count[1 - cur];
+    }
+    dfl_flow_compact(P, f->keep, f->newid, fl, s);
+    /* swap: the compacted copies become the live buffers, the old ones the spares */
+    f64** live3[6] = {&ParticleCTXDeviceCoord(ctx)->data, &ParticleCTXDeviceVel(ctx)->data, &ParticleCTXDeviceAcc(ctx)->data,
+                      &x->omega, &x->alpha, c ? &c->imp : NULL};
+    for (int k = 0, m = 0; k < 6; ++k) {
+        if (!src3[k]) continue;
+        f64* t = *live3[k];
+        *live3[k] = f->spare3[m];
+        f->spare3[m] = t;
+        ++m;
+    }
+    int64_t* tg = f->tag;
+    f->tag = f->tag_spare;
+    f->tag_spare = tg;
+    if (c) {
+        index_type* tt = c->tet;
+        c->tet = f->tet_spare;
+        f->tet_spare = tt;
+        f64* tl = c->lambda;
+        c->lambda = f->lambda_spare;
+        f->lambda_spare = tl;
+    }
+    if (x->omega) x->hist_cur = 1 - cur;
+    f->stats.removed += P - Pn;
+    set_count(ctx, Pn);
+    DflRangePop();
+}
+
+void ParticleContextAdd(ParticleContext* ctx) {
+    ParticleExt* x = (ParticleExt*)ctx->ext;
+    FlowState* f = x->flow;
+    if (!f || !f->in_on) return;
+    const f64 R = ParticleRadius(ctx);
+    if (R != f->inlet_R) build_inlet(f, R);
+    f->inlet.call = f->call++;
+    f->credit += f->in.per_call;
+    f64 want_f = floor(f->credit);
+    f->credit -= want_f;
+    const index_type P = ctx->num_particle;
+    const f64 room = f->in.max_particles > P ? (f64)(f->in.max_particles - P) : 0.0;
+    if (want_f > room) want_f = room;
+    const index_type want = (index_type)want_f;
+    if (want <= 0) return;
+    const index_type n_try = want < f->nslot ? want : f->nslot;
+    if (n_try <= 0) {
+        f->stats.blocked += want;
+        return;
+    }
+    DflRangePush("ParticleContextAdd");
+    hipStream_t s = DflStream();
+    grow(ctx, P + n_try);
+    CoupleState* c = x->couple;
+    dfl_inflow_block(P, ArrayData(ParticleCTXDeviceCoord(ctx)), f->inlet, R, f->blocked, s);
+    dfl_inflow_select(f->inlet, f->blocked, f->key, f->key_out, f->slot, f->slot_out, f->sort_tmp, f->sort_bytes, s);
+    dfl_inflow_append(P, n_try, f->inlet, f->key_out, f->slot_out, f->next_tag, ArrayData(ParticleCTXDeviceCoord(ctx)),
+                      ArrayData(ParticleCTXDeviceVel(ctx)), ArrayData(ParticleCTXDeviceAcc(ctx)), f->tag, x->omega, x->alpha,
+                      x->omega ? x->hist_count[x->hist_cur] : NULL, c ? c->tet : NULL, c ? c->lambda : NULL, c ? c->imp : NULL,
+                      f->count, s);
+    const index_type n = read_count(f->count);
+    f->next_tag += n;
+    f->stats.inserted += n;
+    f->stats.blocked += want - n;
+    if (n > 0) set_count(ctx, P + n);
+    DflRangePop();
+}
+
+void ParticleContextFlowStats(const ParticleContext* ctx, DflParticleFlowStats* out) {
+    const FlowState* f = ((const ParticleExt*)ctx->ext)->flow;
+    if (f) *out = f->stats;
+    else memset(out, 0, sizeof *out);
+}
+
+const int64_t* ParticleContextTag(const ParticleContext* ctx) {
+    const FlowState* f = ((const ParticleExt*)ctx->ext)->flow;
+    return f ? f->tag : NULL;
+}

@@ -144,6 +144,9 @@ typedef struct ParticleExt {
     index_type* overflow;                       /* device [1] */
     int hist_cur;                               /* the rows the next sweep reads */
     f64 gravity[3];                             /* body acceleration of ParticleContextUpdate */
+    index_type cap;                             /* capacity of every per-particle buffer (>= num_particle; host/flow.c) */
+    b32 order_valid;                            /* `order` is the last sweep's, for the current particles */
+    struct FlowState* flow;                     /* particle inflow / outflow (host/flow.c), NULL when never set */
 } ParticleExt;
 /* the history of the next sweep (flips the ping-pong: call once per sweep) */
 dfl_contact_history DflFrictionHistory(ParticleExt* x);
@@ -151,8 +154,33 @@ dfl_friction_law DflFrictionLaw(const ParticleContext* ctx);
 void DflFrictionClearHistory(ParticleContext* ctx); /* no-op when friction is off */
 /* the sweep's device workspace for P particles over nbin cell-list bins (count / cell_start [nbin + 1]); grows only */
 void DflDemReserve(ParticleExt* x, index_type P, index_type nbin);
-struct CoupleState;
+/* particle-fluid coupling state (host/couple.c) */
+typedef struct CoupleState {
+    Mesh3D* mesh;
+    index_type N, T, P;
+    DflFluidCoupling cfg;
+    b32 use_order;                   /* locate in the contact sweep's cell order (DFL_COUPLE_CELL_ORDER=0: id order) */
+    index_type *vrow, *vcol;         /* device V2E map [N+1], [4T], every list ascending */
+    index_type* nbr;                 /* device [T][4] */
+    index_type* seed;                /* device [gdim^3] */
+    index_type gdim;
+    f64 lo[3], inv_h[3];
+    index_type *tet, *lost;          /* device [cap], [1] */
+    f64 *lambda, *imp;               /* device [cap][4], [cap][3] */
+    index_type *tcount, *tstart;     /* device [T], [T+1] */
+    index_type *rank, *slot, *members; /* device [cap] */
+    void* scan_tmp;
+    int64_t scan_bytes;
+    f64* load;                       /* device [3N]: the reaction load DflTimeStep registers */
+    f64 imp_time;                    /* time the impulses were accumulated over */
+    f64 *rem_load, *rem_tmp;         /* device [3N]: -(impulse of removed particles) scattered to the nodes, and scratch */
+    b32 rem_pending;                 /* rem_load holds something the next reaction load adds */
+} CoupleState;
 void DflCoupleFree(struct CoupleState* c);
+/* scatter the pending impulse of the particles with rtet[i] >= 0 (removed, located) into rem_load (host/couple.c) */
+void DflCoupleAccumulateRemoved(ParticleContext* ctx, const index_type* rtet);
+struct FlowState;
+void DflFlowFree(struct FlowState* f);
 struct WallState;
 void DflWallsFree(struct WallState* w);
 /* the contact sweep against the mesh walls (ParticleContextComputeForces when walls are set) */

@@ -27,6 +27,7 @@ ParticleContext* ParticleContextCreate(index_type num_particle) {
     x->kn = 1.0e4;
     x->gamma_n = 1.0;
     x->dt = 1.0e-4;
+    x->cap = num_particle;
     ctx->ext = x;
     return ctx;
 }
@@ -35,6 +36,7 @@ void ParticleContextDestroy(ParticleContext* ctx) {
     if (!ctx) return;
     ParticleExt* x = (ParticleExt*)ctx->ext;
     for (int k = 0; k < 3; ++k) {
+        if (x) ctx->h_arr[k]->len = ctx->d_arr[k]->len = 3 * x->cap; /* the size they were allocated with */
         ArrayDestroy(ctx->h_arr[k]);
         ArrayDestroy(ctx->d_arr[k]);
     }
@@ -44,6 +46,7 @@ void ParticleContextDestroy(ParticleContext* ctx) {
         DflCoupleFree(x->couple);
         DflWallsFree(x->walls);
         ParticleContextSetFriction(ctx, NULL);
+        DflFlowFree(x->flow);
         CdamFreeHost(x, SIZE_OF(ParticleExt));
     }
     CdamFreeHost(ctx, SIZE_OF(ParticleContext));
@@ -62,8 +65,6 @@ void ParticleContextUpdateHost(ParticleContext* ctx) {
 void ParticleContextUpdateDevice(ParticleContext* ctx) {
     for (int k = 0; k < 3; ++k) ArrayCopy(ctx->d_arr[k], ctx->h_arr[k], H2D);
 }
-void ParticleContextAdd(ParticleContext* ctx) { UNUSED(ctx); }
-void ParticleContextRemove(ParticleContext* ctx) { UNUSED(ctx); }
 
 void ParticleContextSetContactModel(ParticleContext* ctx, f64 kn, f64 gamma_n, f64 dt) {
     ParticleExt* x = (ParticleExt*)ctx->ext;
@@ -74,6 +75,7 @@ void ParticleContextSetContactModel(ParticleContext* ctx, f64 kn, f64 gamma_n, f
 
 void DflDemReserve(ParticleExt* x, index_type P, index_type nbin) {
     if (x->cap_particle < P) {
+        if (P < x->cap) P = x->cap; /* the context's capacity (grows geometrically under ParticleContextAdd) */
         CdamFreeDevice(x->cell_of, 0); CdamFreeDevice(x->rank, 0); CdamFreeDevice(x->slot, 0); CdamFreeDevice(x->order, 0); CdamFreeDevice(x->sorted, 0);
         x->cell_of = (index_type*)CdamMallocDevice((ptrdiff_t)P * SIZE_OF(index_type));
         x->rank = (index_type*)CdamMallocDevice((ptrdiff_t)P * SIZE_OF(index_type));
@@ -120,6 +122,7 @@ void ParticleContextComputeForces(ParticleContext* ctx) {
     if (x->omega) {
         dfl_dem_build_cells_spin(P, coord, vel, x->omega, cell, ncell, x->cell_of, x->rank, x->count, x->chunk_sum, x->cell_start,
                                  x->slot, x->order, x->sorted, x->sorted_w, s);
+        x->order_valid = TRUE;
         int slot = DflProfileBegin(DFL_TAG_SMALL + 1);
         dfl_dem_forces_friction(P, x->sorted, x->sorted_w, R, ParticleMass(ctx), x->kn, x->gamma_n, DflFrictionLaw(ctx), cell, ncell,
                                 x->order, x->cell_start, DflFrictionHistory(x), acc, x->alpha, s);
@@ -128,6 +131,7 @@ void ParticleContextComputeForces(ParticleContext* ctx) {
         return;
     }
     dfl_dem_build_cells(P, coord, vel, cell, ncell, x->cell_of, x->rank, x->count, x->chunk_sum, x->cell_start, x->slot, x->order, x->sorted, s);
+    x->order_valid = TRUE;
     int slot = DflProfileBegin(DFL_TAG_SMALL + 1);
     dfl_dem_forces(P, x->sorted, R, ParticleMass(ctx), x->kn, x->gamma_n, cell, ncell, x->order, x->cell_start, acc, s);
     DflProfileEnd(slot);
@@ -159,7 +163,7 @@ static void clear_history(ParticleExt* x, index_type P) {
 void ParticleContextSetFriction(ParticleContext* ctx, const DflContactFriction* cfg) {
     ParticleExt* x = (ParticleExt*)ctx->ext;
     const index_type P = ctx->num_particle;
-    const ptrdiff_t n = P > 0 ? P : 1;
+    const ptrdiff_t n = x->cap > 0 ? x->cap : 1;
     if (!cfg) {
         if (!x->omega) return;
         HIPGUARD(hipStreamSynchronize(DflStream()));
@@ -218,6 +222,12 @@ dfl_contact_history DflFrictionHistory(ParticleExt* x) {
     h.overflow = x->overflow;
     x->hist_cur = b;
     return h;
+}
+
+void ParticleContextFrictionHistory(const ParticleContext* ctx, const void** rows, const index_type** counts) {
+    const ParticleExt* x = (const ParticleExt*)ctx->ext;
+    *rows = x->omega ? (const void*)x->hist[x->hist_cur] : NULL;
+    *counts = x->omega ? x->hist_count[x->hist_cur] : NULL;
 }
 
 f64* ParticleContextAngularVelocity(ParticleContext* ctx) { return ((ParticleExt*)ctx->ext)->omega; }

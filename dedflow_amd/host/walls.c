@@ -51,15 +51,20 @@ static index_type clamp_cell(f64 v, index_type n) {
     return c < 0.0 ? 0 : (c >= (f64)n ? n - 1 : (index_type)c);
 }
 
-/* the particle grid: cell edge >= 4R per axis and about half a particle per cell, as the unit-box grid; the wall grid:
- * cubic cells of max(2R, median wall edge); both over the bounding box padded by R, with their cell counts capped */
-static void build_grids(WallState* w, f64 R, index_type P) {
-    f64 glo[3], ext[3];
+/* the bounding box padded by R: origin and extent */
+static void padded_box(const WallState* w, f64 R, f64 glo[3], f64 ext[3]) {
     for (int d = 0; d < 3; ++d) {
         glo[d] = w->lo[d] - R;
         ext[d] = (w->hi[d] - w->lo[d]) + 2.0 * R;
         if (!(ext[d] > 0.0)) ext[d] = 1.0;
     }
+}
+
+/* the particle grid: cell edge >= 4R per axis and about half a particle per cell, as the unit-box grid, over the bounding
+ * box padded by R, with its cell count capped.  Host arithmetic only: a particle count change rebuilds just this */
+static void build_particle_grid(WallState* w, f64 R, index_type P) {
+    f64 glo[3], ext[3];
+    padded_box(w, R, glo, ext);
     const f64 vol = ext[0] * ext[1] * ext[2];
     f64 h = cbrt(vol / (2.0 * (f64)(P > 0 ? P : 1)));
     if (h < 4.0 * R) h = 4.0 * R;
@@ -77,7 +82,14 @@ static void build_grids(WallState* w, f64 R, index_type P) {
         w->pgrid.lo[d] = glo[d];
         w->pgrid.inv[d] = (f64)w->pgrid.n[d] / ext[d];
     }
+    w->P = P;
+}
 
+/* the wall grid: cubic cells of max(2R, median wall edge) over the same padded box, with its cell count capped; the lists
+ * are built on the host and uploaded (synchronises) */
+static void build_wall_grid(WallState* w, f64 R) {
+    f64 glo[3], ext[3];
+    padded_box(w, R, glo, ext);
     f64 hw = w->edge > 2.0 * R ? w->edge : 2.0 * R;
     for (;;) {
         f64 cells = 1.0;
@@ -137,7 +149,11 @@ static void build_grids(WallState* w, f64 R, index_type P) {
     free(range);
     free(start);
     w->R = R;
-    w->P = P;
+}
+
+static void build_grids(WallState* w, f64 R, index_type P) {
+    build_particle_grid(w, R, P);
+    build_wall_grid(w, R);
 }
 
 /* plane ids: the smallest record id among the records whose plane equals this one under de-duplication rule 1 (normals
@@ -310,7 +326,8 @@ void DflWallsComputeForces(ParticleContext* ctx) {
     const f64 R = ParticleRadius(ctx);
     hipStream_t s = DflStream();
     DflRangePush("ParticleContextComputeForces");
-    if (R != w->R || P != w->P) build_grids(w, R, P);
+    if (R != w->R) build_grids(w, R, P);
+    else if (P != w->P) build_particle_grid(w, R, P); /* ParticleContextAdd / Remove: the walls stay */
     const index_type ncell3 = w->pgrid.n[0] * w->pgrid.n[1] * w->pgrid.n[2];
     DflDemReserve(x, P, ncell3 + 1); /* + the bin of the particles outside the grid */
     const f64* coord = ArrayData(ParticleCTXDeviceCoord(ctx));
@@ -319,6 +336,7 @@ void DflWallsComputeForces(ParticleContext* ctx) {
     if (x->omega) {
         dfl_walls_build_cells_spin(P, coord, vel, x->omega, w->pgrid, x->cell_of, x->rank, x->count, x->chunk_sum, x->cell_start,
                                    x->slot, x->order, x->sorted, x->sorted_w, s);
+        x->order_valid = TRUE;
         int slot = DflProfileBegin(DFL_TAG_SMALL + 1);
         dfl_walls_forces_friction(P, x->sorted, x->sorted_w, R, ParticleMass(ctx), x->kn, x->gamma_n, DflFrictionLaw(ctx), w->pgrid,
                                   x->order, x->cell_start, w->tri, w->plane, w->wgrid, w->wstart, w->wlist, 1e-12 * w->scale,
@@ -329,6 +347,7 @@ void DflWallsComputeForces(ParticleContext* ctx) {
     }
     dfl_walls_build_cells(P, coord, vel, w->pgrid, x->cell_of, x->rank, x->count, x->chunk_sum, x->cell_start, x->slot, x->order,
                           x->sorted, s);
+    x->order_valid = TRUE;
     int slot = DflProfileBegin(DFL_TAG_SMALL + 1);
     dfl_walls_forces(P, x->sorted, R, ParticleMass(ctx), x->kn, x->gamma_n, w->pgrid, x->order, x->cell_start, w->tri, w->wgrid,
                      w->wstart, w->wlist, 1e-12 * w->scale, w->dropped, acc, s);

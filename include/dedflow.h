@@ -697,6 +697,7 @@ void ParticleContextLoad(ParticleContext* ctx, H5FileInfo* h5f, const char* grou
 void ParticleContextSave(const ParticleContext* ctx, H5FileInfo* h5f, const char* group_name);
 void ParticleContextUpdateHost(ParticleContext* ctx);
 void ParticleContextUpdateDevice(ParticleContext* ctx);
+/* empty in the reference (Particle.c:120-130); here: inlet insertion and outflow removal once configured (below) */
 void ParticleContextAdd(ParticleContext* ctx);
 /* empty in the reference (Particle.c:120-130); here: contact-force sweep + explicit update (build-defined) */
 void ParticleContextUpdate(ParticleContext* ctx);
@@ -776,8 +777,9 @@ void DflMeshSetExternalLoad(Mesh3D* mesh, const f64* load);
  *              particle per cell, at most 2^24 cells).  A particle whose centre lies outside that box gets NO contact
  *              acceleration, from pairs or walls, and is no pair partner of the others: it has left through an open group.
  *              Wall candidates come from a static grid over the same box; forces are bitwise reproducible.
- *   setup      the wall records and grids are built at the call, and again only when ParticleRadius (or the particle
- *              count) changes; a sweep allocates nothing and does not wait for the device.  The walls are a snapshot of
+ *   setup      the wall records and grids are built at the call, and again only when ParticleRadius changes; a change of
+ *              the particle count rebuilds the particle grid only (host arithmetic); a sweep allocates nothing and does not
+ *              wait for the device.  The walls are a snapshot of
  *              the mesh: a moved mesh needs another call.  Point location of the coupling stays exact for convex domains
  *              only; walls do not change that. */
 #ifndef DFL_WALL_MAX_CONTACTS
@@ -848,6 +850,76 @@ const f64* ParticleContextAngularAcc(const ParticleContext* ctx); /* device [P][
 /* contacts that found no free history entry since friction was last set */
 index_type ParticleContextFrictionOverflowCount(const ParticleContext* ctx);
 void ParticleContextSetGravity(ParticleContext* ctx, const f64 g[3]); /* body acceleration of ParticleContextUpdate */
+/* the history the next sweep reads: device rows [P][DFL_DEM_MAX_HISTORY] of 32-byte entries (uint64 key, f64 xi[3]) and
+ * live counts [P]; both NULL when friction is off */
+void ParticleContextFrictionHistory(const ParticleContext* ctx, const void** rows, const index_type** counts);
+
+/* ---- particle inflow and outflow (build-defined; opt-in) ---------------------------------------------------------------
+ * A context that never calls ParticleContextSetInflow or ParticleContextSetOutflow with a configuration keeps its particle
+ * count for life: ParticleContextAdd and ParticleContextRemove are no-ops and DflTimeStep is unchanged, bit for bit.
+ *   tags       the first Set call gives every particle a stable 64-bit tag 0 .. P-1; inserted particles take the next tags
+ *              in insertion order.  Ids change under compaction, tags do not (ParticleContextTag).
+ *   capacity   every per-particle buffer is sized to a capacity >= num_particle that grows by x1.5 only when an Add needs
+ *              it.  The Arrays' len is always 3 num_particle (ParticleContextSave writes the live particles).  Add and
+ *              Remove swap the Arrays' data pointers with spare storage: a pointer taken from ArrayData, or from
+ *              ParticleContextTet / Barycentric / AngularVelocity / AngularAcc / Tag, is valid until the next Add or Remove.
+ *   Remove     1. with outside_mesh on a coupled context: ParticleContextLocate first (tet -1 also means "not located").
+ *              2. particle i is removed when n . x_i > d for any plane (n[3], d) = plane[k], computed as
+ *                 (n0 x0 + n1 x1) + n2 x2 without fused multiply-add, or (outside_mesh, coupled) when tet_i == -1.  A particle
+ *                 at tet -2 (walk cap hit; counted by ParticleContextLostCount) is kept.
+ *              3. stable compaction: survivors keep their relative order and carry coord, vel, acc, the tag, with friction
+ *                 w, alpha and the history rows the next sweep reads (partner keys 0 << 62 | j remapped to the partner's
+ *                 new id, entries whose partner was removed dropped, the others in their order; wall keys unchanged),
+ *                 and with coupling tet, lambda and the pending drag impulse.
+ *              4. the drag impulse of the removed particles still pending (imp_time > 0) is scattered to the nodes with
+ *                 their current lambda (fixed order, no float atomics) into a per-context accumulator that the next
+ *                 ParticleContextReactionLoad adds and clears: that load equals, to rounding, the one without the Remove.
+ *   Add        inlet rectangle o + s u + t v (s, t in [0, 1], u perpendicular to v), nu = floor(|u| / 2R), nv likewise;
+ *              slot k = i + nu j (i < nu, j < nv).  No slot when nu or nv is 0.  Host constants, IEEE double, left to right:
+ *                pu = u / nu, pv = v / nv, base = (o + 0.5 pu) + 0.5 pv,
+ *                ju = jitter (0.5 (|u| / nu - 2R)), ou = (u / |u|) ju, and jv, ov likewise (|u| = sqrt((u0 u0 + u1 u1) + u2 u2))
+ *              hash h(a) = splitmix64(a) = mix(a + 0x9E3779B97F4A7C15) with mix(z) = z ^ (z >> 30), * 0xBF58476D1CE4E5B9,
+ *                ^ (z >> 27), * 0x94D049BB133111EB, ^ (z >> 31) (wrapping 64-bit);  H(c, k, a) = h(h(h(seed) ^ c) ^ (4k + a))
+ *                with c = the index of this Add call since ParticleContextSetInflow (0, 1, ...), counted whether or not it
+ *                inserts;  r_a = 2 ((H(c, k, a) >> 11) 2^-53) - 1 in [-1, 1)
+ *              candidate centre of slot k in call c, per axis d, without fused multiply-add:
+ *                x_d = (((base_d + i pu_d) + j pv_d) + r_0 ou_d) + r_1 ov_d
+ *              so two candidates are never closer than 2R.  Slot k is blocked when an existing particle centre y has
+ *              (y0 - x0)^2 + (y1 - x1)^2 + (y2 - x2)^2 < (2R)^2 (summed left to right).  Candidates are not tested against
+ *              walls: the caller places the inlet inside the fluid domain, at least R from every wall.
+ *              credit += per_call; want = floor(credit); credit -= want; want = min(want, max(max_particles - P, 0)).  The
+ *              free slots in ascending (H(c, k, 2) >> 1, k) are the candidates; the first min(want, free) are appended at
+ *              ids P, P+1, ... with vel = cfg.vel, acc 0, spin 0, an empty history row, tet -1, lambda 0, no impulse.
+ *              want - inserted is added to `blocked` and not carried over.  Selection and positions are a pure function
+ *              of (seed, c, the blocked slots).
+ *   cost       Remove and Add each read 4 bytes back (the new count) and allocate nothing except when Add grows the
+ *              capacity; DflTimeStep calls ParticleContextAdd after the predictor (inflow set) and ParticleContextRemove
+ *              after the particle sub-steps (outflow set), as the reference's commented-out calls at main.c:548 and :569.
+ *   other      the contact sweep's cell order is invalidated by a count change (the next locate runs in id order until
+ *              the next sweep); mesh walls rebuild only their particle grid.  Set*flow(ctx, NULL) turns that direction
+ *              off; tags and the statistics stay until the context is destroyed.  One GPU only. */
+#define DFL_OUTFLOW_MAX_PLANES 8
+typedef struct DflParticleOutflow {
+    index_type num_planes;
+    f64 plane[DFL_OUTFLOW_MAX_PLANES][4]; /* removed when n . x > d, (n[3], d) = plane[k] */
+    b32 outside_mesh;                     /* coupled only: also remove the particles located outside the mesh (tet -1) */
+} DflParticleOutflow;
+typedef struct DflParticleInflow {
+    f64 origin[3], edge_u[3], edge_v[3]; /* inlet rectangle origin + s u + t v, s, t in [0, 1]; u perpendicular to v */
+    f64 vel[3];                          /* velocity of an inserted particle */
+    f64 per_call;                        /* particles wanted per ParticleContextAdd (the fraction is carried as credit) */
+    f64 jitter;                          /* in [0, 1]: share of each slot's slack used for the in-plane offset */
+    uint64_t seed;
+    index_type max_particles;            /* Add never lets num_particle exceed this */
+} DflParticleInflow;
+typedef struct DflParticleFlowStats {
+    int64_t inserted, removed, blocked;
+} DflParticleFlowStats;
+void ParticleContextSetOutflow(ParticleContext* ctx, const DflParticleOutflow* cfg); /* NULL: off */
+void ParticleContextSetInflow(ParticleContext* ctx, const DflParticleInflow* cfg);   /* NULL: off; resets call index and credit */
+/* particles inserted, removed and inlet candidates that found their slot blocked since the first Set*flow call */
+void ParticleContextFlowStats(const ParticleContext* ctx, DflParticleFlowStats* out);
+const int64_t* ParticleContextTag(const ParticleContext* ctx); /* device [P]; NULL until inflow or outflow was set */
 
 #ifdef __cplusplus
 }

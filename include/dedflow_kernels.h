@@ -620,6 +620,59 @@ void dfl_couple_node_load(dfl_index N, const dfl_index* vrow, const dfl_index* v
                           const dfl_index* tstart, const dfl_index* members, const dfl_value* lambda, const dfl_value* imp,
                           dfl_value scale, dfl_value* load, void* stream);
 
+/* ---- particle inflow and outflow (build-defined, opt-in; csrc/k_flow.hip, model in include/dedflow.h)
+ *    dfl_flow_flag          keep[i] = 0 when particle i is beyond a plane (n . x > d) or, by_tet, at tet[i] == -1; else 1.
+ *                           rtet (may be NULL; needs tet) = tet[i] of the removed particles, -1 for the kept ones
+ *    dfl_flow_compact       stable scatter of every kept particle i to newid[i] (newid = exclusive scan of keep): the
+ *                           [P][3] records of src3 / dst3, the tags, with tet_src != NULL tet and lambda, with hrow_src !=
+ *                           NULL the live history entries (partner keys remapped through newid, entries of removed partners
+ *                           dropped).  Destinations are distinct from every source
+ *    dfl_inflow_block       blocked[nu nv] <- 0, then 1 for every slot whose candidate lies closer than 2R to a particle
+ *    dfl_inflow_select      key_out / slot_out = the slots in ascending (rank key, slot): rank key H(c, k, 2) >> 1, 2^63
+ *                           for a blocked slot; temp from dfl_inflow_select_temp_bytes
+ *    dfl_inflow_append      the first `want` (<= nu nv) of the sorted slots that are free are appended at ids P, P+1, ...;
+ *                           *count <- their number.  hist_count / tet / lambda / imp / omega / alpha may be NULL */
+typedef struct dfl_outflow_planes {
+    dfl_value plane[8][4];
+    dfl_index num;
+} dfl_outflow_planes;
+typedef struct dfl_flow_fields {
+    const dfl_value* src3[6];
+    dfl_value* dst3[6];
+    int n3;
+    const int64_t* tag_src;
+    int64_t* tag_dst;
+    const dfl_index* tet_src;
+    dfl_index* tet_dst;
+    const dfl_value* lambda_src;
+    dfl_value* lambda_dst;
+    const dfl_contact_hist* hrow_src;
+    const dfl_index* hcount_src;
+    dfl_contact_hist* hrow_dst;
+    dfl_index* hcount_dst;
+} dfl_flow_fields;
+/* the inlet lattice: the host constants of include/dedflow.h (base, pu, pv, ou, ov), the plane frame (o, unit uhat, vhat,
+ * normal) and the prefilter widths of the blocking pass */
+typedef struct dfl_inlet {
+    dfl_value base[3], pu[3], pv[3], ou[3], ov[3];
+    dfl_value o[3], uhat[3], vhat[3], nrm[3];
+    dfl_value pitch_u, pitch_v, ju, jv, plane_tol;
+    dfl_value vel[3];            /* velocity of an inserted particle */
+    dfl_index nu, nv;
+    uint64_t seed, call;
+} dfl_inlet;
+void dfl_flow_flag(dfl_index P, const dfl_value* coord, dfl_outflow_planes planes, const dfl_index* tet, int by_tet,
+                   dfl_index* keep, dfl_index* rtet, void* stream);
+void dfl_flow_compact(dfl_index P, const dfl_index* keep, const dfl_index* newid, dfl_flow_fields f, void* stream);
+void dfl_inflow_block(dfl_index P, const dfl_value* coord, dfl_inlet in, dfl_value radius, dfl_index* blocked, void* stream);
+int64_t dfl_inflow_select_temp_bytes(dfl_index nslot);
+void dfl_inflow_select(dfl_inlet in, const dfl_index* blocked, uint64_t* key, uint64_t* key_out, dfl_index* slot,
+                       dfl_index* slot_out, void* temp, int64_t temp_bytes, void* stream);
+void dfl_inflow_append(dfl_index P, dfl_index want, dfl_inlet in, const uint64_t* key_sorted, const dfl_index* slot_sorted,
+                       int64_t first_tag, dfl_value* coord, dfl_value* vel, dfl_value* acc,
+                       int64_t* tag, dfl_value* omega, dfl_value* alpha, dfl_index* hist_count, dfl_index* tet,
+                       dfl_value* lambda, dfl_value* imp, dfl_index* count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

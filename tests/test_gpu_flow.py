@@ -1,0 +1,403 @@
+"""GPU tests of particle inflow and outflow (ParticleContextAdd / ParticleContextRemove; host/flow.c, csrc/k_flow.hip).
+Build-defined (the reference's hooks are empty): pinned to tests/flow_model.py bit for bit, to twin runs without the
+feature, and to conservation of the count and of the reaction load."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import flow_model as fl
+from dedflow_amd.meshgen import dem_lattice, dem_particles, kuhn_box, kuhn_cube, synthetic_fields
+
+pytestmark = pytest.mark.gpu
+KN, GN = 1.0e4, 1.0
+
+
+@pytest.fixture(scope="module")
+def api():
+    from dedflow_amd import api as A
+    A.lib()
+    return A
+
+
+def _pool(L):
+    r, u = C.c_int64(0), C.c_int64(0)
+    L.DflDevicePoolStats(C.byref(r), C.byref(u))
+    return u.value
+
+
+def _mass(R, rho_p):
+    return rho_p * 4.0 / 3.0 * np.pi * R ** 3
+
+
+def _inside(m, n, seed):
+    rng = np.random.default_rng(seed)
+    t = rng.integers(0, m.num_tet, n)
+    lam = rng.dirichlet(np.ones(4), n)
+    return np.einsum("na,nad->nd", lam, m.xg.reshape(-1, 3)[m.ien.reshape(-1, 4)[t]])
+
+
+def _state(pc, api, friction=False, coupled=False):
+    api.sync()
+    s = {"x": pc.arrays()[0].reshape(-1, 3), "v": pc.arrays()[1].reshape(-1, 3), "a": pc.arrays()[2].reshape(-1, 3)}
+    if friction:
+        s["w"], s["alpha"] = pc.omega(), pc.alpha()
+        s["hk"], s["hx"], s["hc"] = pc.friction_history()
+    if coupled:
+        s["tet"], s["lam"] = pc.tet(), pc.barycentric()
+    t = pc.tags()
+    if t is not None:
+        s["tag"] = t
+    return s
+
+
+@pytest.mark.parametrize("friction,coupled", [(False, False), (True, False), (False, True), (True, True)])
+def test_remove_by_planes_matches_the_filter(api, friction, coupled):
+    x, v, R = dem_particles(5000, 0.03)
+    m = kuhn_cube(6) if coupled else None
+    P = api.Problem(m) if coupled else None
+    pc = api.Particles(x, v, R, kn=KN, gamma_n=GN)
+    try:
+        if friction:
+            pc.set_friction(0.5)
+        if coupled:
+            pc.couple(P)
+        for _ in range(3):
+            pc.update()          # contacts build history, acc and alpha are non-trivial
+        if coupled:
+            pc.locate()
+        planes = [(1.0, 0.0, 0.0, 0.8), (0.0, -1.0, 0.0, -0.1), (0.3, 0.4, 0.5, 0.9)]
+        pc.set_outflow(planes)
+        before = _state(pc, api, friction, coupled)
+        assert np.array_equal(before["tag"], np.arange(5000))
+        keep = fl.outflow_keep(before["x"], planes)
+        assert 0 < keep.sum() < 5000
+        pc.remove()
+        after = _state(pc, api, friction, coupled)
+        assert pc.P == keep.sum() and pc.flow_stats() == {"inserted": 0, "removed": 5000 - keep.sum(), "blocked": 0}
+        for k in ("x", "v", "a", "tag") + (("w", "alpha") if friction else ()) + (("tet", "lam") if coupled else ()):
+            assert np.array_equal(after[k], before[k][keep]), k
+        if friction:
+            assert before["hc"].sum() > 1000
+            nk, nx, nc = fl.remap_history(before["hk"], before["hx"], before["hc"], keep)
+            assert np.array_equal(after["hc"], nc)
+            for j in range(len(nc)):
+                assert np.array_equal(after["hk"][j, :nc[j]], nk[j, :nc[j]])
+                assert np.array_equal(after["hx"][j, :nc[j]], nx[j, :nc[j]])
+        # the context keeps working at the new count
+        pc.update()
+        if coupled:
+            pc.locate()
+        api.sync()
+        assert np.isfinite(pc.arrays()[0]).all()
+    finally:
+        pc.close()
+        if P is not None:
+            P.close()
+
+
+def test_history_survives_removal(api):
+    """a frictional heap plus isolated particles far above it; twin runs, one removes the isolated ones: the survivors'
+    trajectories over the next 200 sweeps are bitwise those of the run without the removal"""
+    R = 0.02                                    # floor(1 / 4R) = 12 cells per axis, below the count rule at these counts
+    heap = dem_lattice((0.0, 0.0, 0.0), (0.5, 0.5, 0.25), R, spacing=1.95 * R, jitter=0.1)
+    g = np.linspace(0.6, 0.9, 4)
+    lone = np.stack(np.meshgrid(g, g, [0.85], indexing="ij"), axis=-1).reshape(-1, 3)
+    x = np.concatenate([heap, lone])
+    order = np.random.default_rng(3).permutation(len(x))     # interleave the ids
+    x = x[order]
+    runs = []
+    for remove in (False, True):
+        pc = api.Particles(x.reshape(-1), np.zeros(x.size), R, kn=KN, gamma_n=GN, dt=1e-4)
+        try:
+            pc.set_friction(0.5)
+            pc.set_gravity((0.0, 0.0, -9.81))
+            for _ in range(100):
+                pc.update()
+            if remove:
+                pc.set_outflow([(0.0, 0.0, 1.0, 0.7)])
+                pc.remove()
+                assert pc.P == len(heap)
+            for _ in range(200):
+                pc.update()
+            runs.append(_state(pc, api, friction=True))
+        finally:
+            pc.close()
+    keep = x[:, 2] < 0.7
+    full, cut = runs
+    assert full["hc"][keep].sum() > 2 * len(heap)           # the springs are live
+    for k in ("x", "v", "w"):
+        assert np.array_equal(cut[k], full[k][keep]), k
+    assert np.array_equal(cut["tag"], np.flatnonzero(keep))
+
+
+def test_reaction_load_is_conserved_across_remove(api):
+    m = kuhn_cube(6, jitter=0.2)
+    N = m.num_node
+    wg, _ = synthetic_fields(m)
+    w_d = api.DeviceArray.from_numpy(wg)
+    R, dt = 0.005, 2e-4
+    x = _inside(m, 400, 5)
+    v = np.random.default_rng(6).normal(0, 0.3, x.shape)
+    loads = []
+    for remove in (False, True):
+        pc = api.Particles(x.reshape(-1), v.reshape(-1), R, mass=_mass(R, 2000.0), dt=dt)
+        P = api.Problem(m)
+        try:
+            pc.couple(P)
+            for _ in range(5):
+                pc.fluid_step(w_d)
+            if remove:
+                pc.set_outflow([(1.0, 0.0, 0.0, 0.5)])
+                pc.remove()
+                assert 100 < pc.P < 300
+            loads.append(pc.reaction_load().numpy())
+            # the accumulator is spent: the next (empty) load is zero in both
+            assert not pc.reaction_load().numpy().any()
+        finally:
+            pc.close()
+            P.close()
+    full, cut = loads
+    assert np.abs(full).max() > 0.0
+    assert np.abs(cut - full).max() <= 1e-12 * np.abs(full).max()
+
+
+def test_outside_mesh_removes_what_left_through_an_open_group(api):
+    m = kuhn_box(4, (0, 0, 0), (1, 1, 1))
+    R, dt = 0.05, 1e-3
+    gx, gy = 0.2 + 0.15 * (np.arange(10) % 5), 0.3 + 0.3 * (np.arange(10) // 5)     # 0.15 apart: no contacts
+    up = np.column_stack([gx, gy, np.full(10, 0.9)])
+    rest = np.column_stack([gx, gy, np.full(10, 0.4)])
+    x = np.empty((20, 3))
+    x[0::2], x[1::2] = up, rest
+    v = np.zeros((20, 3))
+    v[0::2, 2] = 1.0
+    P = api.Problem(m)
+    pc = api.Particles(x.reshape(-1), v.reshape(-1), R, kn=KN, gamma_n=GN, dt=dt)
+    try:
+        pc.set_walls(P, range(5))            # z+ open
+        pc.couple(P)
+        pc.set_outflow([], outside_mesh=True)
+        pc.remove()
+        assert pc.P == 20 and pc.flow_stats()["removed"] == 0
+        for _ in range(300):
+            pc.update()
+        pc.remove()
+        api.sync()
+        assert pc.P == 10 and pc.flow_stats()["removed"] == 10 and pc.lost_count() == 0
+        assert np.array_equal(pc.tags(), np.arange(1, 20, 2))
+        assert (pc.tet() >= 0).all()
+    finally:
+        pc.close()
+        P.close()
+
+
+def _inflow_setup(R=0.03, jitter=0.6, seed=1234, per_call=25.5, max_particles=10 ** 6):
+    origin, u, v = (0.1, 0.1, 0.9), (0.8, 0.0, 0.0), (0.0, 0.8, 0.0)
+    inlet = fl.Inlet(origin, u, v, R, jitter=jitter, seed=seed)
+    model = fl.InflowModel(inlet, per_call, max_particles, vel=(0.0, 0.0, -0.5))
+    kw = dict(origin=origin, edge_u=u, edge_v=v, vel=(0.0, 0.0, -0.5), per_call=per_call, jitter=jitter, seed=seed,
+              max_particles=max_particles)
+    return inlet, model, kw
+
+
+def test_add_matches_the_model(api):
+    R = 0.03
+    inlet, model, kw = _inflow_setup(R)
+    x, v, _ = dem_particles(300, R)
+    x = x.reshape(-1, 3)
+    x[:, 2] *= 0.5
+    x[:5] = inlet.centres(0)[[3, 40, 41, 100, 168]]     # sitting on slots of the first call
+    x[5] = inlet.centres(1)[7] + [0.0, 0.0, 1.5 * R]   # in reach of a slot of the second call
+    v = v.reshape(-1, 3)
+    pc = api.Particles(x.reshape(-1), v.reshape(-1), R, kn=KN, gamma_n=GN)
+    try:
+        pc.set_inflow(**kw)
+        coord, vel, tags = x.copy(), v.copy(), np.arange(300, dtype=np.int64)
+        for call in range(6):
+            coord, vel, tags, n = model.add(coord, vel, tags, len(coord))
+            pc.add()
+            s = _state(pc, api)
+            assert pc.P == len(coord)
+            assert np.array_equal(s["x"], coord), call
+            assert np.array_equal(s["v"], vel) and np.array_equal(s["tag"], tags)
+            assert not s["a"][300:].any()
+        st = pc.flow_stats()
+        assert st["inserted"] == len(coord) - 300 and st["blocked"] == model.blocked_total and st["removed"] == 0
+        new = coord[300:]
+        d = np.linalg.norm(new[:, None] - coord[None], axis=2)
+        d[np.arange(len(new)), 300 + np.arange(len(new))] = np.inf
+        assert d.min() >= 2 * R * (1 - 1e-12)
+    finally:
+        pc.close()
+
+
+def test_one_particle_blocks_exactly_its_slot(api):
+    R = 0.03
+    inlet = fl.Inlet((0.1, 0.1, 0.9), (0.8, 0.0, 0.0), (0.0, 0.8, 0.0), R, jitter=0.0, seed=9)
+    c = inlet.centres(0)
+    x = np.array([c[57], [0.5, 0.5, 0.2]])
+    pc = api.Particles(x.reshape(-1), np.zeros(6), R, kn=KN, gamma_n=GN)
+    try:
+        pc.set_inflow((0.1, 0.1, 0.9), (0.8, 0.0, 0.0), (0.0, 0.8, 0.0), per_call=inlet.nslot, jitter=0.0, seed=9)
+        pc.add()
+        api.sync()
+        assert pc.P == 2 + inlet.nslot - 1
+        assert pc.flow_stats() == {"inserted": inlet.nslot - 1, "removed": 0, "blocked": 1}
+        new = pc.arrays()[0].reshape(-1, 3)[2:]
+        assert not (np.linalg.norm(new - c[57], axis=1) < 1e-12).any()
+        assert {tuple(p) for p in new} == {tuple(p) for p in np.delete(c, 57, axis=0)}
+    finally:
+        pc.close()
+
+
+@pytest.mark.parametrize("friction,coupled", [(False, False), (True, True)])
+def test_growth_cap_and_memory(api, friction, coupled):
+    L = api.lib()
+    R = 0.03
+    m = kuhn_cube(4)
+    P = api.Problem(m)
+    api.sync()
+    base = _pool(L)
+    x, v, _ = dem_particles(10, R)
+    x = x.reshape(-1, 3)
+    x[:, 2] *= 0.4
+    pc = api.Particles(x.reshape(-1), v, R, kn=KN, gamma_n=GN)
+    try:
+        if friction:
+            pc.set_friction(0.4)
+        if coupled:
+            pc.couple(P)
+        inlet, model, kw = _inflow_setup(R, per_call=37.0, max_particles=150)
+        pc.set_inflow(**kw)
+        pc.set_outflow([(0.0, 0.0, 1.0, 2.0)])
+        sizes = []
+        for _ in range(6):
+            pc.add()
+            sizes.append(pc.P)
+            pc.update()
+            if coupled:
+                pc.locate()
+        pc.remove()
+        api.sync()
+        assert sizes == [47, 84, 121, 150, 150, 150]
+        st = pc.flow_stats()
+        assert st["inserted"] == 140 and st["removed"] == 0 and np.array_equal(pc.tags(), np.arange(150))
+        assert np.isfinite(pc.arrays()[0]).all()
+        if friction:
+            pc.omega()
+        if coupled:
+            assert (pc.tet() >= 0).all()
+    finally:
+        pc.close()
+    api.sync()
+    assert _pool(L) == base
+    P.close()
+
+
+def test_zero_particles(api):
+    m = kuhn_cube(4)
+    wg, _ = synthetic_fields(m)
+    w_d = api.DeviceArray.from_numpy(wg)
+    R = 0.02
+    x = _inside(m, 50, 2)
+    P = api.Problem(m)
+    pc = api.Particles(x.reshape(-1), np.zeros(x.size), R, mass=_mass(R, 2000.0), dt=1e-4)
+    try:
+        pc.set_friction(0.3)
+        pc.couple(P)
+        pc.fluid_step(w_d)
+        pc.set_outflow([(0.0, 0.0, 0.0, -1.0)])           # 0 > -1: everything goes
+        pc.remove()
+        api.sync()
+        assert pc.P == 0 and pc.flow_stats()["removed"] == 50
+        load = pc.reaction_load().numpy()                  # the removed particles' impulse is still delivered
+        assert np.abs(load).max() > 0.0
+        pc.compute_forces()
+        pc.update()
+        pc.locate()
+        pc.fluid_step(w_d)
+        assert not pc.reaction_load().numpy().any()
+        pc.remove()
+        pc.set_inflow((0.2, 0.2, 0.5), (0.6, 0.0, 0.0), (0.0, 0.6, 0.0), per_call=20, seed=4)
+        pc.add()
+        api.sync()
+        assert pc.P == 20 and np.array_equal(pc.tags(), np.arange(50, 70))
+        pc.fluid_step(w_d)
+        api.sync()
+        assert np.isfinite(pc.arrays()[0]).all() and (pc.tet() >= 0).all()
+    finally:
+        pc.close()
+        P.close()
+
+
+def _channel(api, steps, configure=True):
+    """a coupled channel along x: inlet near x = 0, outlet beyond x = 0.6, gravity along +x, walls on the y and z sides"""
+    m = kuhn_box(4, (0, 0, 0), (1, 1, 1))
+    N = m.num_node
+    wg, _ = synthetic_fields(m)
+    wg[:4 * N] = 0.0
+    R, dt = 0.03, 1e-3
+    x = dem_lattice((0.3, 0.3, 0.3), (0.5, 0.7, 0.7), R, spacing=2.5 * R)
+    P = api.Problem(m, maxit=120, atol=1e-12, rtol=1e-4)
+    pc = api.Particles(x.reshape(-1), np.zeros(x.size), R, mass=_mass(R, 2000.0), kn=1e5, gamma_n=5.0, dt=dt)
+    out = {"P0": len(x), "counts": []}
+    try:
+        pc.set_walls(P, (2, 3, 4, 5))
+        pc.couple(P, gravity=(30.0, 0.0, 0.0), two_way=True)
+        if configure:
+            pc.set_inflow((0.1, 0.2, 0.2), (0.0, 0.6, 0.0), (0.0, 0.0, 0.6), vel=(1.0, 0.0, 0.0), per_call=7.5, jitter=0.5,
+                          seed=77)
+            pc.set_outflow([(1.0, 0.0, 0.0, 0.6)])
+        st = [api.DeviceArray.from_numpy(a) for a in (wg, np.zeros(6 * N), np.zeros(6 * N))]
+        F_d, dx_d = api.DeviceArray(6 * N), api.DeviceArray(6 * N)
+        for _ in range(steps):
+            P.time_step(st[0], st[1], st[2], F_d, dx_d, newton_maxit=2, particles=pc, dem_substeps=20)
+            out["counts"].append(pc.P)
+        s = _state(pc, api, coupled=True)
+        s["w"] = st[0].numpy()
+        out.update(s)
+        out["stats"] = pc.flow_stats()
+        return out
+    finally:
+        pc.close()
+        P.close()
+
+
+def test_flow_through_time_step(api):
+    a = _channel(api, 20)
+    st = a["stats"]
+    assert st["inserted"] > 50 and st["removed"] > 10, st
+    assert a["counts"][-1] == a["P0"] + st["inserted"] - st["removed"]
+    assert np.isfinite(a["x"]).all() and np.isfinite(a["v"]).all() and np.isfinite(a["w"]).all()
+    assert (a["x"][:, 0] <= 0.6 + 1e-12).all()
+    x = a["x"]
+    d = np.linalg.norm(x[:, None] - x[None], axis=2) + np.eye(len(x)) * 1e9
+    R = 0.03
+    assert d.min() > 2 * R - 0.1 * R, d.min()        # no pair deeper than 0.1 R
+    # bitwise repeatable, tags included
+    b = _channel(api, 20)
+    for k in ("x", "v", "a", "tag", "tet", "lam", "w"):
+        assert np.array_equal(a[k], b[k]), k
+    assert a["stats"] == b["stats"] and a["counts"] == b["counts"]
+
+
+def test_off_means_off(api):
+    x, v, R = dem_particles(2000, 0.02)
+    pc = api.Particles(x, v, R, kn=KN, gamma_n=GN)
+    try:
+        pc.set_friction(0.5)
+        pc.update()
+        before = _state(pc, api, friction=True)
+        pc.add()
+        pc.remove()
+        after = _state(pc, api, friction=True)
+        assert pc.P == 2000 and pc.tags() is None
+        assert pc.flow_stats() == {"inserted": 0, "removed": 0, "blocked": 0}
+        for k in before:
+            assert np.array_equal(before[k], after[k]), k
+    finally:
+        pc.close()
+    # DflTimeStep with the hooks off equals a run whose outflow never triggers (no compaction)
+    a = _channel(api, 3, configure=False)
+    assert a["counts"] == [a["P0"]] * 3 and "tag" not in a
