@@ -414,7 +414,7 @@ class DflFluidCoupling(C.Structure):
     _fields_ = [("rho_f", C.c_double), ("mu_f", C.c_double), ("gravity", C.c_double * 3), ("two_way", C.c_int32)]
 
 
-PC_DECOMPOSITION, PC_AMGX, PC_ILU0, PC_TWOLEVEL = 0x2, 0x3, 0x5, 0x6   # PCType values (include/dedflow.h)
+PC_JACOBI, PC_DECOMPOSITION, PC_AMGX, PC_ILU0, PC_TWOLEVEL = 0x1, 0x2, 0x3, 0x5, 0x6   # PCType values (include/dedflow.h)
 ALLREDUCE_FN = C.CFUNCTYPE(None, vp, vp, C.c_int32)
 HALO_FN = C.CFUNCTYPE(None, vp, vp)
 STREAM_FN = C.CFUNCTYPE(vp, vp)
@@ -427,6 +427,11 @@ class DflAMGXConfig(C.Structure):
 
 
 AMGX_SMOOTHER_DILU, AMGX_SMOOTHER_JACOBI = 0, 1
+
+
+class DflScalarTransport(C.Structure):
+    _fields_ = [("phi", C.c_int32), ("T", C.c_int32), ("dirichlet_phi", C.c_int32), ("dirichlet_T", C.c_int32),
+                ("pc", C.c_int), ("rtol", C.c_double), ("maxit", C.c_int32)]
 
 
 class DflComm(C.Structure):
@@ -526,6 +531,12 @@ def _declare(L):
     f("DflDevicePoolStats", None, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)])
     f("DflKrylovCalibrationLog", C.c_char_p, []); f("DflDeviceMemoryInUse", C.c_int64, []); f("DflWaitDeviceMemoryQuiet", C.c_double, [C.c_double])
     f("DflProfileEnable", None, [C.c_int]); f("DflProfileCollect", C.c_int, [C.c_int, C.POINTER(f64), C.POINTER(f64)])
+    f("DflMeshSetScalarTransport", None, [C.POINTER(Mesh3D), C.POINTER(DflScalarTransport)])
+    f("DflMeshScalarTransportEnabled", i32, [C.POINTER(Mesh3D)])
+    f("DflAssembleScalarJacobian", None, [C.POINTER(Mesh3D), vp, vp, C.POINTER(Matrix), C.POINTER(Matrix)])
+    f("DflMeshScalarResidual", vp, [C.POINTER(Mesh3D)])
+    f("DflScalarTransportSolve", i32, [C.POINTER(Mesh3D), vp, vp, vp, vp])
+    f("DflScalarTransportIterations", None, [C.POINTER(Mesh3D), C.POINTER(i32)])
     f("GenerateRandomColor", None, [vp, i32, i32])
     f("dfl_abi_version", C.c_int, [])
 
@@ -656,9 +667,57 @@ class Problem:
                                C.cast(rn, vp), C.cast(r0, vp))
         return int(it), np.array(rn[:]), np.array(r0[:])
 
+    # ---- phi / T transport (include/dedflow.h, "scalar transport") -----------------------------------------------------
+    def set_scalar_transport(self, phi=True, T=True, dirichlet_phi=(), dirichlet_T=(), pc="jacobi", rtol=1e-10, maxit=200):
+        """DflMeshSetScalarTransport: advance phi and / or T in SolveFlowSystem; dirichlet_*: boundary groups whose nodes hold
+        their value; pc: "jacobi" or "amgx"."""
+        pcs = {"jacobi": PC_JACOBI, "amgx": PC_AMGX}
+        if pc not in pcs:
+            raise ValueError(f"pc must be one of {sorted(pcs)}")
+        cfg = DflScalarTransport(1 if phi else 0, 1 if T else 0, sum(1 << int(g) for g in dirichlet_phi),
+                                 sum(1 << int(g) for g in dirichlet_T), pcs[pc], float(rtol), int(maxit))
+        lib().DflMeshSetScalarTransport(self.mesh, C.byref(cfg))
+
+    def clear_scalar_transport(self):
+        lib().DflMeshSetScalarTransport(self.mesh, None)
+
+    def assemble_scalar_jacobian(self, wg, dwg):
+        """DflAssembleScalarJacobian at the alpha states (wg, dwg): the values of Jphi and JT over the nodal pattern
+        (self.pattern()), as two numpy arrays."""
+        L = lib()
+        if getattr(self, "_sj", None) is None:
+            self._sj = (L.MatrixCreateTypeCSR(self.spy1x1, None), L.MatrixCreateTypeCSR(self.spy1x1, None))
+        L.DflAssembleScalarJacobian(self.mesh, wg.ptr, dwg.ptr, self._sj[0], self._sj[1])
+        sync()
+        out = []
+        for m in self._sj:
+            csr = C.cast(m.contents.data, C.POINTER(MatrixCSR)).contents
+            out.append(d2h(csr.val, self.nnz1, np.float64))
+        return out[0], out[1]
+
+    def scalar_residual(self):
+        """DflMeshScalarResidual: the phi / T rows [2N] of the last F assembly (None without a transport)."""
+        p = lib().DflMeshScalarResidual(self.mesh)
+        sync()
+        return d2h(p, 2 * self.N, np.float64) if p else None
+
+    def solve_scalar(self, wgold, dwgold, dwg):
+        """DflScalarTransportSolve: one scalar Newton update of dwg[4N:6N) at the current u; returns
+        (norms of the phi / T residual it solved against, GMRES iterations of the two solves)."""
+        rn = (C.c_double * 2)()
+        rc = lib().DflScalarTransportSolve(self.mesh, wgold.ptr, dwgold.ptr, dwg.ptr, C.cast(rn, vp))
+        if rc != 0:
+            raise RuntimeError("DflScalarTransportSolve refused (no scalar transport set)")
+        its = (C.c_int32 * 2)()
+        lib().DflScalarTransportIterations(self.mesh, its)
+        return np.array(rn[:]), (int(its[0]), int(its[1]))
+
     def close(self):
         L = lib()
         sync()
+        for m in getattr(self, "_sj", None) or ():
+            L.MatrixDestroy(m)
+        self._sj = None
         for bc in self.bcs:
             L.DirichletDestroy(bc)
         self.bcs = []

@@ -299,6 +299,7 @@ void DflAssembleSystemPrepacked(Mesh3D* mesh, f64* wgalpha, f64* dwgalpha, f64* 
        face terms and before the Dirichlet rows */
     if (F && x->ext_load) dfl_daxpy(3 * num_node, -1.0, x->ext_load, F, s);
     x->nodep_current = FALSE;
+    if (F && x->scalar) DflScalarCaptureResidual(mesh, F); /* the phi / T rows, kept for the scalar transport (host/scalar.c) */
     if (F) HIPGUARD(hipMemsetAsync(F + 4 * (size_t)num_node, 0, (size_t)num_node * sizeof(f64) * 2, s)); /* main.c:63-66 */
     for (index_type ibc = 0; ibc < nbc; ++ibc) {
         if (F) DirichletApplyVec(bcs[ibc], F);

@@ -87,14 +87,21 @@ index_type SolveFlowSystem(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matr
     index_type iter = 0;
     b32 converged = FALSE;
     if (maxit <= 0) maxit = 4;
-    FlowWork* fw = fw_get(mesh);
     const DflComm* comm = KrylovGetComm(ksp);
+    /* phi / T transport (host/scalar.c): single-GPU only, refused before anything is computed */
+    const b32 scalar = DflMeshScalarTransportEnabled(mesh);
+    if (scalar && comm) {
+        fprintf(stderr, "SolveFlowSystem: the phi / T transport is single-GPU only; the solver has a communicator: solve refused\n");
+        return -1;
+    }
+    FlowWork* fw = fw_get(mesh);
     KrylovSetMesh(ksp, mesh); /* node coordinates for aggregation-based preconditioners */
     f64 *wgalpha = fw->wgalpha, *dwgalpha = fw->dwgalpha;
     alpha_states(mesh, wgold, dwgold, dwg, wgalpha, dwgalpha);
     DflAssembleSystemPrepacked(mesh, wgalpha, dwgalpha, F, NULL, bcs, nbc, TRUE);
     zero_ghost_residual(N, F, comm);
     four_norms(fw, N, F, rnorm_init, comm);
+    if (scalar) DflScalarNorms(mesh, rnorm_init + 2); /* F[4N:6N) is zero: the phi / T rows were kept aside */
     if (!DflQuiet())
         for (int k = 0; k < 4; ++k)
             fprintf(stdout, "Newton %d) abs = %.17e rel = %6.4e (tol = %6.4e)\n", 0, rnorm_init[k], 1.0, tol);
@@ -104,12 +111,16 @@ index_type SolveFlowSystem(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matr
         DflAssembleSystemPrepacked(mesh, wgalpha, dwgalpha, NULL, J, bcs, nbc, TRUE); /* same states as the residual before */
         HIPGUARD(hipMemsetAsync(dx, 0, (size_t)N * BS * sizeof(f64), s));
         KrylovSolve(ksp, J, dx, F);
+        /* F[4N:6N) is zero, so the (u,p) solve runs on its 4N active rows and leaves dx[4N:6N) at the zero it was given;
+           the scalar increments go there, at the same alpha states (block-Jacobi Newton) */
+        if (scalar) DflScalarSolveIncrements(mesh, wgalpha, dwgalpha, dx + 4 * (size_t)N);
         if (comm) comm->halo_exchange(comm->ctx, dx); /* ghost copies of the increment from their owners */
         dfl_daxpy(N * BS, -1.0, dx, dwg, s); /* dwg -= dx, main.c:226 */
         alpha_states(mesh, wgold, dwgold, dwg, wgalpha, dwgalpha);
         DflAssembleSystemPrepacked(mesh, wgalpha, dwgalpha, F, NULL, bcs, nbc, TRUE);
         zero_ghost_residual(N, F, comm);
         four_norms(fw, N, F, rnorm, comm);
+        if (scalar) DflScalarNorms(mesh, rnorm + 2);
         if (!DflQuiet())
             for (int k = 0; k < 4; ++k)
                 fprintf(stdout, "Newton %d) abs = %.17e rel = %6.4e (tol = %6.4e)\n", iter + 1, rnorm[k], rnorm[k] / rnorm_init[k], tol);
@@ -139,6 +150,10 @@ index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* 
         fprintf(stderr, "DflTimeStep: particle-fluid coupling is single-GPU only; the solver has a communicator: step refused\n");
         return -1;
     }
+    if (DflMeshScalarTransportEnabled(mesh) && KrylovGetComm(ksp)) {
+        fprintf(stderr, "DflTimeStep: the phi / T transport is single-GPU only; the solver has a communicator: step refused\n");
+        return -1;
+    }
     DflRangePush("DflTimeStep");
     const f64* user_load = DflMeshExternalLoad(mesh);
     const f64* reaction = coupled && DflParticleTwoWay(pctx) ? DflParticlePendingLoad(pctx) : NULL;
@@ -158,4 +173,25 @@ index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* 
     if (pctx) ParticleContextRemove(pctx); /* main.c:568-569; a no-op unless outflow is set */
     DflRangePop();
     return it;
+}
+
+/* one scalar Newton update at the current u (include/dedflow.h): alpha states, residual (its phi / T rows kept by the F
+ * assembly), both Jacobians, both solves, dwg[4N:6N) -= dx */
+index_type DflScalarTransportSolve(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, f64* rnorm_out) {
+    if (!DflMeshScalarTransportEnabled(mesh)) {
+        fprintf(stderr, "DflScalarTransportSolve: no scalar transport is set on this mesh (DflMeshSetScalarTransport)\n");
+        return -1;
+    }
+    const index_type N = Mesh3DNumNode(mesh);
+    FlowWork* fw = fw_get(mesh);
+    f64 *F, *dx2;
+    DflScalarWork(mesh, &F, &dx2);
+    DflRangePush("DflScalarTransportSolve");
+    alpha_states(mesh, wgold, dwgold, dwg, fw->wgalpha, fw->dwgalpha);
+    DflAssembleSystemPrepacked(mesh, fw->wgalpha, fw->dwgalpha, F, NULL, NULL, 0, TRUE);
+    DflScalarSolveIncrements(mesh, fw->wgalpha, fw->dwgalpha, dx2);
+    dfl_daxpy(2 * N, -1.0, dx2, dwg + 4 * (size_t)N, DflStream());
+    if (rnorm_out) DflScalarNorms(mesh, rnorm_out);
+    DflRangePop();
+    return 0;
 }

@@ -115,6 +115,7 @@ typedef struct MeshExt {
     PatchSched* patch;             /* LHS patch schedule (assembly schedule mode 2), built on first use */
     SlotPatchSched* slotpatch;     /* LHS slot-owner schedule (mode 4, default), built on first use */
     const f64* ext_load;           /* device [3N] external load on the momentum rows (DflMeshSetExternalLoad), NULL: none */
+    struct ScalarState* scalar;    /* phi / T transport (host/scalar.c, DflMeshSetScalarTransport), NULL: off */
 } MeshExt;
 
 void DflMeshPrepareFaces(Mesh3D* mesh, index_type group);
@@ -214,6 +215,14 @@ int DflVectorArenaFree(void* p);
 index_type SolveFlowSystem(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* J, f64* F, f64* dx, Krylov* ksp,
                            Dirichlet** bcs, index_type nbc, index_type maxit, f64* rnorm_out, f64* rnorm_init_out);
 void DflKrylovSolvePrepared(Krylov* ksp, Matrix* A, f64* x, f64* b); /* KrylovSolve without PC (re)build and PCSetup */
+
+/* host/scalar.c: the phi / T transport of a mesh (all of them no-ops or unused while it is off) */
+struct ScalarState;
+void DflScalarFree(struct ScalarState* st);
+void DflScalarCaptureResidual(Mesh3D* mesh, const f64* F);        /* F[4N:6N) -> the mesh's [2N] residual, Dirichlet rows zeroed */
+void DflScalarSolveIncrements(Mesh3D* mesh, f64* wgalpha, f64* dwgalpha, f64* dx2); /* Jacobians + both solves -> dx2 [2N] */
+void DflScalarNorms(Mesh3D* mesh, f64* out2);                      /* ||R_phi||, ||R_T|| of that residual (synchronises) */
+void DflScalarWork(Mesh3D* mesh, f64** F, f64** dx2);              /* scratch [6N], [2N] of DflScalarTransportSolve */
 
 /* named ranges for rocprofv3 --marker-trace (DFL_ROCTX=1); no-ops otherwise */
 void DflRangePush(const char* name);

@@ -97,6 +97,7 @@ void Mesh3DDestroy(Mesh3D* m) {
         DflFreeSlotPatchSchedule(x->slotpatch);
         DflFreeRhsPatchSchedule(x->rhspatch);
         DflFreeFlowWork(x->flow);
+        DflScalarFree(x->scalar);
         CdamFreeDevice(x->egeo_b, 0);
         if (x->h_sched_elem) CdamFreeHost(x->h_sched_elem, 0);
         CdamFreeDevice(x->nodep, 0);

@@ -570,6 +570,48 @@ struct ParticleContext;
 index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* J, f64* F, f64* dx, Krylov* ksp, Dirichlet** bcs,
                        index_type nbc, index_type newton_maxit, struct ParticleContext* pctx, index_type dem_substeps,
                        f64* rnorm_out, f64* rnorm_init_out);
+/* ---- scalar transport: level set phi and temperature T (build-defined; opt-in) -------------------------------------------
+ * The residual has SUPG rows for phi (advection) and T (advection-diffusion) (src/assemble.cu:885-906), but the reference
+ * zeroes them before the solve (main.c:63-66) and its matrix has no phi / T blocks, so neither field ever moves.  With a
+ * transport configured on the mesh both become transported fields:
+ *   Jacobians  the exact derivatives of the phi / T rows with respect to the rates dphi / dT at fixed u (alpha-level chain
+ *              rule: f1 = alpha_m, f2 = dt alpha_f gamma).  Given u the rows are affine in (dphi, dT), phi and T feed neither
+ *              each other nor the (u,p) rows: two independent N x N systems, volume terms only.
+ *   residual   every F assembly of the mesh (AssembleSystem, SolveFlowSystem) keeps the phi / T rows it computed in a
+ *              mesh-owned [2N] array (DflMeshScalarResidual) before zeroing F[4N:6N) as the reference does; F itself and
+ *              the (u,p) solve are unchanged.
+ *   Dirichlet  nodes of the boundary groups in dirichlet_phi / dirichlet_T (bit g = group g) get a zero residual row and a
+ *              unit matrix row: their increment is 0, they keep their value (separate from Dirichlet / DirichletApplyVec).
+ *   Newton     SolveFlowSystem, after each (u,p) solve, assembles both Jacobians at the same alpha states, solves them
+ *              (one GMRES per field, rtol / maxit below) against the saved residual into dx[4N:5N) and dx[5N:6N), and the
+ *              one update dwg -= dx applies all increments (block-Jacobi Newton: the dependence of phi / T on u is left out,
+ *              as in the reference's block structure).  rnorm[2] / rnorm[3] are the norms of the saved residual, so the
+ *              convergence test covers them.  With a communicator SolveFlowSystem and DflTimeStep print why and return -1.
+ * A mesh that never had a transport set, or had it cleared with NULL, computes bit for bit what it computed before. */
+typedef struct DflScalarTransport {
+    b32 phi, T;                            /* fields to advance */
+    index_type dirichlet_phi, dirichlet_T; /* bit masks of boundary groups whose nodes hold their value */
+    PCType pc;                             /* PC_JACOBI (default; PC_NONE is taken as PC_JACOBI) or PC_AMGX */
+    f64 rtol;                              /* inner GMRES: relative tolerance (<= 0: 1e-10) */
+    index_type maxit;                      /* inner GMRES: iterations (<= 0: 200) */
+} DflScalarTransport;
+void DflMeshSetScalarTransport(Mesh3D* mesh, const DflScalarTransport* cfg); /* copied; NULL: off, frees everything */
+b32 DflMeshScalarTransportEnabled(const Mesh3D* mesh);
+/* both Jacobians at the alpha states (wgalpha: only u is read; dwgalpha unused, the Jacobians do not depend on it) into
+ * MAT_TYPE_CSR matrices over the nodal pattern (CSRAttrCreate; columns ascending) that own their values, overwritten; either
+ * may be NULL.  Under a configured transport the rows of its Dirichlet groups become unit rows.  One launch per pattern
+ * (csrc/k_scalar.hip), bitwise reproducible, the same under every assembly schedule. */
+void DflAssembleScalarJacobian(Mesh3D* mesh, f64* wgalpha, f64* dwgalpha, Matrix* Jphi, Matrix* JT);
+/* device [2N]: the phi / T rows of the last F assembly, scalar Dirichlet rows zeroed (a field that is not advanced: zeros);
+ * NULL without a transport */
+f64* DflMeshScalarResidual(Mesh3D* mesh);
+/* one scalar Newton update at the current u: alpha states, residual, both Jacobians, both solves, dwg[4N:6N) -= dx.  Lets a
+ * caller prescribe u and march the scalars alone.  rnorm_out[2] (may be NULL): norms of the phi / T residual it solved
+ * against.  Returns 0, or -1 (with a message) when the mesh has no transport. */
+index_type DflScalarTransportSolve(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, f64* rnorm_out);
+/* GMRES iterations of the last phi / T solves (-1: field not solved yet) */
+void DflScalarTransportIterations(const Mesh3D* mesh, index_type its[2]);
+
 /* the assembly caches J^-1-derived element geometry per mesh (the reference recomputes it every call); after writing new
  * node coordinates into Mesh3DDevice(mesh)->xg call this once so the next assembly rebuilds the cache */
 void DflMeshGeometryChanged(Mesh3D* mesh);

@@ -673,6 +673,15 @@ void dfl_inflow_append(dfl_index P, dfl_index want, dfl_inlet in, const uint64_t
                        int64_t* tag, dfl_value* omega, dfl_value* alpha, dfl_index* hist_count, dfl_index* tet,
                        dfl_value* lambda, dfl_value* imp, dfl_index* count, void* stream);
 
+/* ---- scalar transport (host/scalar.c, csrc/k_scalar.hip) ------------------------------------------------------------
+ * dfl_assemble_scalar_jacobian: the level-set and temperature Jacobians (d R_phi / d dphi, d R_T / d dT) over the nodal
+ * pattern (row_ptr / col_ind, columns ascending), one value per nonzero, overwritten (beta = 0).  vrow / vcol: the V2E map
+ * of the tets with every list ascending; wgalpha: the alpha-level state (only u = wgalpha[0, 3N) is read).  Either value
+ * array may be NULL.  One launch, no atomics: bitwise reproducible. */
+void dfl_assemble_scalar_jacobian(dfl_index N, const dfl_index* vrow, const dfl_index* vcol, const dfl_index* ien,
+                                  const dfl_value* xg, const dfl_value* wgalpha, const dfl_index* row_ptr,
+                                  const dfl_index* col_ind, dfl_value* val_phi, dfl_value* val_T, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
