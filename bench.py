@@ -101,6 +101,16 @@ def dump_outputs(out_dir, P, x_d, F_d, its, r0, hist):
     save("solve_stats", [its, r0])
 
 
+def calibration_cap_gb(N, nnz1, its):
+    """Default transient-memory cap of the explicit work-space calibration (--placement-cap-gb -1): room for what its first
+    round holds at once -- five more Krylov bases of 6N x (its + 2) doubles and six copies of the 4x4 block values -- and
+    40 % more for the spacers in front of its far blocks.  Every draw is still made and timed; the cap shortens the time spent
+    allocating and releasing spacers of up to 5/8 of the free memory (10M-tet mesh: 48 GB, calibration 12 s instead of
+    30-35 s, winning blocks as fast in the loop)."""
+    held = 5 * 6.0 * N * (its + 2) * 8 + 6 * 128.0 * nnz1
+    return 1.4 * held / 2 ** 30
+
+
 def cpu_model():
     try:
         for line in open("/proc/cpuinfo"):
@@ -190,16 +200,22 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--M", type=int, default=119, help="cells per cube edge (119 -> 10.1M tets)")
     ap.add_argument("--gmres-its", type=int, default=40)
-    ap.add_argument("--cpu-M", type=int, default=-1, help="cube size of the multi-thread CPU-baseline leg (-1 = the GPU line's M, 0 = skip)")
-    ap.add_argument("--cpu-single-M", type=int, default=64, help="cube size of the single-thread CPU leg + scipy yardstick (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything beyond the headline figure: per-kernel durations and the "
+                         "roofline (a profiled pass of their own), the SpMV back to back, whole AssembleSystem calls, the solves to "
+                         "rtol 1e-4, the CPU baseline, the DEM sweep and the coupled step.  Without it a run sets up, warms up, "
+                         "times the steps, writes --dump-outputs and prints the result line")
+    ap.add_argument("--cpu-M", type=int, default=-1, help="--full: cube size of the multi-thread CPU-baseline leg (-1 = the GPU line's M, 0 = skip)")
+    ap.add_argument("--cpu-single-M", type=int, default=64, help="--full: cube size of the single-thread CPU leg + scipy yardstick (0 = skip)")
     ap.add_argument("--placement", choices=["calibrate", "default", "off"], default="calibrate",
                     help="Krylov work-space placement: explicit heavy DflKrylovCalibratePlacement before the warm-up (calibrate), the "
                          "library's bounded default, or none")
-    ap.add_argument("--placement-cap-gb", type=float, default=0.0, help="transient device memory the explicit calibration may hold (0 = no cap)")
+    ap.add_argument("--placement-cap-gb", type=float, default=-1.0,
+                    help="transient device memory the explicit calibration may hold (-1 = room for its draws + 40 %%, 0 = no cap)")
     ap.add_argument("--jitter", type=float, default=0.2)
-    ap.add_argument("--solve-to-rtol", type=int, default=1, help="also time one PC_ILU0 solve to rtol 1e-4 after the timed steps (0 = skip)")
-    ap.add_argument("--coupled-M", type=int, default=55, help="fluid mesh of the coupled fluid + DEM step leg (0 = skip)")
-    ap.add_argument("--dem-particles", type=int, default=100000, help="DEM contact sweep leg after the timed step (0 = skip)")
+    ap.add_argument("--solve-to-rtol", type=int, default=1, help="--full: also time one PC_ILU0 solve to rtol 1e-4 after the timed steps (0 = skip)")
+    ap.add_argument("--coupled-M", type=int, default=55, help="--full: fluid mesh of the coupled fluid + DEM step leg (0 = skip)")
+    ap.add_argument("--dem-particles", type=int, default=100000, help="--full: DEM contact sweep leg after the timed step (0 = skip)")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (x, F, samples "
                                                           "of J, GMRES history) as DIR/<name>.npy")
     args = ap.parse_args()
@@ -232,15 +248,15 @@ def main():
     os.dup2(2, 1)
     if world > 1 or os.environ.get("DFL_FORCE_DIST") == "1":  # DFL_FORCE_DIST: rehearse the N>1 leg on one rank
         from dedflow_amd import dist_bench
+        if not args.full:
+            args.solve_to_rtol = 0    # its leg after the timed steps is one of --full's
+        args.placement_cap_gb = max(args.placement_cap_gb, 0.0)   # per-rank calibrations: no cap unless one is given
         return dist_bench.run(args, rank, world, local_rank)
 
     from dedflow_amd import api
     from dedflow_amd.meshgen import kuhn_cube, synthetic_fields
     L = api.lib()
     api.hip().hipSetDevice(local_rank)
-    L.DflProfileEnable.argtypes = [C.c_int]
-    L.DflProfileCollect.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    L.DflProfileCollect.restype = C.c_int
 
     t_setup = time.perf_counter()
     mesh = kuhn_cube(args.M, jitter=args.jitter)
@@ -281,13 +297,14 @@ def main():
     L.DflKrylovCalibratePlacement.argtypes = [C.c_void_p, C.POINTER(api.Matrix), C.c_int64]
     L.DflKrylovCalibratePlacement.restype = None
     t_cal = 0.0
+    cap_gb = calibration_cap_gb(N, nnz1, its) if args.placement_cap_gb < 0 else args.placement_cap_gb
     if args.placement == "off":
         os.environ["DFL_WS_CANDIDATES"] = "1"
     elif args.placement == "calibrate":
         P.assemble_system(wg_d, dwg_d, None, want_J=True)
         api.sync()
         t_cal = time.perf_counter()
-        L.DflKrylovCalibratePlacement(P.ksp, P.J, int(args.placement_cap_gb * 2 ** 30))
+        L.DflKrylovCalibratePlacement(P.ksp, P.J, int(cap_gb * 2 ** 30))
         api.sync()
         t_cal = time.perf_counter() - t_cal
     for _ in range(args.warmup):
@@ -308,6 +325,45 @@ def main():
     # what the Krylov work-space calibration measured and chose in the first warm-up solve ("SpMV placement":
     # the in-loop SpMV time is a property of where the value array and the basis landed; this is the record of that draw)
     placement_log = (L.DflKrylovCalibrationLog() or b"").decode(errors="replace").strip().split("\n")
+    ab = algorithmic_bytes(N, T, nnz1, its)
+    out = {
+        "metric": "assembled DOFs/s + Krylov-SpMV GB/s (%HBM peak), 10M-tet mesh",
+        "value": 4.0 * N / (ms_per_step * 1e-3), "unit": "DOF/s",
+        "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": f"Kuhn cube M={args.M}: {T} tets, {N} nodes, nnz1={nnz1}; step = AssembleSystem(F) + "
+                               f"AssembleSystem(J) + Jacobi-PC GMRES x{its} iterations",
+                   "colors": P.num_color, "gmres_its": its, "parallelism": "1 GPU",
+                   "placement": {"calibrate": f"explicit DflKrylovCalibratePlacement before the warm-up ({t_cal:.1f} s, cap "
+                                              f"{f'{cap_gb:.1f}' if cap_gb > 0 else 'none'} GB): basis blocks + value-array copies behind spacers",
+                                 "default": "library default: bounded pick among <= 4 basis blocks in the first solve",
+                                 "off": "none (DFL_WS_CANDIDATES=1)"}[args.placement]},
+        "spmv_placement_calibration": placement_log, "waits_for_driver_memory_wipe_s": quiet_waits,
+        # the whole Krylov solve against the HBM roofline: algorithmic bytes of its `its` matvecs (x0 = 0: r0 = b needs none),
+        # its CGS steps, its+1 preconditioner applications and the final basis combination over the un-instrumented solve time
+        "krylov_solve": (lambda b: {"ms": solve_ms_timed, "algorithmic_GB": b / 1e9, "GBps": b / (solve_ms_timed * 1e-3) / 1e9,
+                                    "frac_of_8TBps": b / (solve_ms_timed * 1e-3) / 1e9 / HBM_PEAK_GBS})(
+            its * ab["spmv"] + sum(ab["cgs"]) + (its + 1) * ab["pc_apply"] + 8.0 * 4 * N * (its + 2)),
+        "setup_s": t_setup, "gmres_residual_drop": float(hist[-1] / r0) if len(hist) else None,
+    }
+    if args.full:
+        out.update(full_legs(args, L, P, step, quiet, wg_d, dwg_d, F_d, x_d))
+    sys.stdout.flush()
+    os.write(args._stdout_fd, (json.dumps(out) + "\n").encode())
+    P.close()
+
+
+def full_legs(args, L, P, step, quiet, wg_d, dwg_d, F_d, x_d):
+    """What `--full` measures after the timed steps, on the same problem and device arrays: per-kernel durations and the
+    roofline (a separate profiled pass), the SpMV back to back, whole AssembleSystem calls, the solves to the reference's
+    tolerance, the CPU baseline, the DEM sweep and the coupled fluid + DEM step.  Returns the keys it adds to the JSON line."""
+    from dedflow_amd import api
+    from dedflow_amd.meshgen import kuhn_cube, synthetic_fields
+    N, T, nnz1, its = P.N, P.T, P.nnz1, args.gmres_its
+    L.DflProfileEnable.argtypes = [C.c_int]
+    L.DflProfileCollect.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.DflProfileCollect.restype = C.c_int
+
     # separate, untimed pass with the profiler on: per-kernel durations for the roofline figures
     L.DflProfileEnable(1)
     n_prof_steps = min(args.steps, 20)   # the profiler holds 8192 intervals (~165 per step)
@@ -497,18 +553,7 @@ def main():
 
     tJ = kernels.get("asm_lhs", {}).get("total_ms_per_step", 0.0)
     tF = kernels.get("asm_rhs", {}).get("total_ms_per_step", 0.0)
-    out = {
-        "metric": "assembled DOFs/s + Krylov-SpMV GB/s (%HBM peak), 10M-tet mesh",
-        "value": 4.0 * N / (ms_per_step * 1e-3), "unit": "DOF/s",
-        "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": f"Kuhn cube M={args.M}: {T} tets, {N} nodes, nnz1={nnz1}; step = AssembleSystem(F) + "
-                               f"AssembleSystem(J) + Jacobi-PC GMRES x{its} iterations",
-                   "colors": P.num_color, "gmres_its": its, "parallelism": "1 GPU",
-                   "placement": {"calibrate": f"explicit DflKrylovCalibratePlacement before the warm-up ({t_cal:.1f} s, cap "
-                                              f"{args.placement_cap_gb or 'none'} GB): basis blocks + value-array copies behind spacers",
-                                 "default": "library default: bounded pick among <= 4 basis blocks in the first solve",
-                                 "off": "none (DFL_WS_CANDIDATES=1)"}[args.placement]},
+    return {
         "spmv_GBps": kernels.get("spmv", {}).get("GBps"), "spmv_frac_of_hbm_peak": kernels.get("spmv", {}).get("frac_of_8TBps"),
         # whole AssembleSystem calls (pack + element kernels + faces + Dirichlet), event-timed; the element kernels alone
         # are in `kernels` (asm_lhs / asm_rhs)
@@ -518,17 +563,8 @@ def main():
         "assemble_F_kernel_dofs_per_s": (6.0 * N / (tF * 1e-3)) if tF else None,
         "solve_to_rtol": to_rtol,
         "roofline": roofline, "kernels": kernels, "cpu_baseline": cpu, "dem_sweep": dem,
-        "spmv_back_to_back_ms": spmv_grouped_ms, "spmv_placement_calibration": placement_log, "waits_for_driver_memory_wipe_s": quiet_waits, "coupled_step": coupled,
-        # the whole Krylov solve against the HBM roofline: algorithmic bytes of its `its` matvecs (x0 = 0: r0 = b needs none),
-        # its CGS steps, its+1 preconditioner applications and the final basis combination over the un-instrumented solve time
-        "krylov_solve": (lambda b: {"ms": solve_ms_timed, "algorithmic_GB": b / 1e9, "GBps": b / (solve_ms_timed * 1e-3) / 1e9,
-                                    "frac_of_8TBps": b / (solve_ms_timed * 1e-3) / 1e9 / HBM_PEAK_GBS})(
-            its * ab["spmv"] + sum(ab["cgs"]) + (its + 1) * ab["pc_apply"] + 8.0 * 4 * N * (its + 2)),
-        "setup_s": t_setup, "gmres_residual_drop": float(hist[-1] / r0) if len(hist) else None,
+        "spmv_back_to_back_ms": spmv_grouped_ms, "coupled_step": coupled,
     }
-    sys.stdout.flush()
-    os.write(args._stdout_fd, (json.dumps(out) + "\n").encode())
-    P.close()
 
 
 if __name__ == "__main__":

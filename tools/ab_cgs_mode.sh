@@ -3,7 +3,7 @@
 # plain instead of nontemporal loads, bit 2 = the update's row chunks in one contiguous slab per XCD)
 OUT=${1:-gpurun_out/cgs_mode}; mkdir -p $OUT
 for m in ${2:-0 1 2 3}; do
-  DFL_CGS_MODE=$m timeout -k 10 300 python bench.py --steps 10 --warmup 3 --cpu-M 0 --cpu-single-M 0 --solve-to-rtol 0 --coupled-M 0 --dem-particles 0 --placement default > $OUT/mode$m.json 2> $OUT/mode$m.err || exit 1
+  DFL_CGS_MODE=$m timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 --cpu-M 0 --cpu-single-M 0 --solve-to-rtol 0 --coupled-M 0 --dem-particles 0 --placement default > $OUT/mode$m.json 2> $OUT/mode$m.err || exit 1
   python - $OUT/mode$m.json $m <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

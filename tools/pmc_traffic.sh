@@ -9,7 +9,7 @@ REPO=$PWD
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --kernel-trace --pmc $c -d $REPO/$OUT/$c -o pmc --output-format csv -- python3 $REPO/bench.py --M $M --steps 1 --warmup 0 --gmres-its 6 --cpu-M 0 --dem-particles 0 --solve-to-rtol 0 --placement default > $REPO/$OUT/$c.log 2>&1 || { echo "pass $c failed"; tail -5 $REPO/$OUT/$c.log; exit 1; }
+  rocprofv3 --kernel-trace --pmc $c -d $REPO/$OUT/$c -o pmc --output-format csv -- python3 $REPO/bench.py --full --M $M --steps 1 --warmup 0 --gmres-its 6 --cpu-M 0 --dem-particles 0 --solve-to-rtol 0 --placement default > $REPO/$OUT/$c.log 2>&1 || { echo "pass $c failed"; tail -5 $REPO/$OUT/$c.log; exit 1; }
 done
 cd $REPO
 python3 - $OUT $M <<'PY'
@@ -27,7 +27,7 @@ for c in ("FETCH_SIZE", "WRITE_SIZE"):
             for g, pat in groups.items():
                 if pat in r["Kernel_Name"]:
                     acc[g][c].append(float(r["Counter_Value"]))
-res = {"_about": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE (separate passes), bench.py --M %d --steps 1 --warmup 0 "
+res = {"_about": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE (separate passes), bench.py --full --M %d --steps 1 --warmup 0 "
                  "--gmres-its 6 --cpu-M 0; counter values are KB (bytes = value*1024); gfx950 correction per MI355X_MICROARCH.md: "
                  "FETCH_SIZE reports half the bytes of 16-B-per-lane streaming reads -> doubled ('fetch_bytes_corrected'). "
                  "Per launch = mean over the launches of that kernel in the run (cgs_*: Arnoldi steps k=0..5 only)." % M}
