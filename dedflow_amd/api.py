@@ -448,12 +448,10 @@ def _declare(L):
     i32, f64 = C.c_int32, C.c_double
     f("Init", None, [C.c_int, vp]); f("Finalize", None, [])
     f("DflStream", vp, []); f("DflSetStream", None, [vp]); f("DflSetQuiet", None, [i32])
-    f("DflSetAssemblySchedule", None, [C.c_int]); f("DflSetPatchParameters", None, [i32, i32])
-    f("DflSetRowPatchParameters", None, [i32, i32]); f("dfl_tune_asm", None, [C.c_int])
+    f("DflSetAssemblySchedule", None, [C.c_int]); f("dfl_set_rhs_lane_grid_cap", None, [C.c_int])
     f("DflMeshSetAssemblySchedule", None, [C.POINTER(Mesh3D), C.c_int]); f("DflMeshSetWeakBCGroup", None, [C.POINTER(Mesh3D), i32])
     f("DflSetWeakBCGroup", None, [i32])
-    f("DflSetSlotPatchParameters", None, [i32, i32, i32]); f("DflSetRhsWaveParameters", None, [i32, i32])
-    f("DflSetRhsPatchParameters", None, [i32, i32]); f("DflMeshGeometryChanged", None, [C.POINTER(Mesh3D)])
+    f("DflSetSlotPatchParameters", None, [i32, i32, i32]); f("DflMeshGeometryChanged", None, [C.POINTER(Mesh3D)])
     f("Mesh3DCreate", C.POINTER(Mesh3D), [i32, i32, i32, i32]); f("Mesh3DDestroy", None, [C.POINTER(Mesh3D)])
     f("Mesh3DUpdateDevice", None, [C.POINTER(Mesh3D)]); f("Mesh3DGenerateColorBatch", None, [C.POINTER(Mesh3D)])
     f("Mesh3DSetBound", None, [C.POINTER(Mesh3D), i32, vp, vp, vp, vp, vp])

@@ -155,72 +155,6 @@ __global__ __launch_bounds__(LBLK) void tet_lhs_kernel(I B, const I* __restrict_
 }
 
 // ====================================================================================
-//  LHS, patch form (assembly schedule 2; host/patch.c).  One workgroup owns one spatial patch
-//  of tets: every (a,b) block contribution is summed into an LDS table indexed by the patch's
-//  local block slots (LDS f64 atomics: ds_add_f64), and each distinct block of the patch is
-//  read-modify-written in HBM once per patch instead of once per tet.  Patches of one launch
-//  share no node (patch coloring), so the global RMW needs no atomics.
-//  LDS table layout: entry-major, tab[i * NS + slot] (NS odd), so the 8 lanes that flush one
-//  block line read 8 different banks.
-// ====================================================================================
-__global__ __launch_bounds__(LBLK) void tet_lhs_patch_kernel(const I* __restrict__ p_eoff, const I* __restrict__ p_boff,
-                                                            I patch_base, const I* __restrict__ ien_p,
-                                                            const unsigned short* __restrict__ lslot,
-                                                            const I* __restrict__ blk_nz, const T* __restrict__ egeo,
-                                                            const T* __restrict__ nodep, T* __restrict__ val, int NS, int dbg) {
-    extern __shared__ double dyn_lds[];
-    __shared__ LhsStage S;
-    double* tab = dyn_lds;  // [16][NS]
-    const int t = threadIdx.x;
-    const int te = t >> 4, p = t & 15;
-    const int patch = patch_base + blockIdx.x;
-    const int e0 = p_eoff[patch], ne = p_eoff[patch + 1] - e0;
-    const int b0 = p_boff[patch], nb = p_boff[patch + 1] - b0;
-    for (int i = t; i < 16 * NS; i += LBLK) tab[i] = 0.0;
-    __syncthreads();
-    for (int base = 0; base < ((dbg & 1) ? 0 : ne); base += EPB) {
-        const int le = base + te;
-        const bool valid = le < ne;
-        const long long e = e0 + (valid ? le : 0);
-        double Bk[16];
-        WAVE_SYNC();  // the wave's staging slots are about to be overwritten
-        lhs_element_block(S, te, p, valid, ien_p + e * 4, egeo + e * 16, nodep, Bk);
-        if (valid) {
-            const int slot = lslot[e * 16 + p];
-#pragma unroll
-            for (int i = 0; i < 16; ++i) if (!(dbg & 4)) atomicAdd(&tab[i * NS + slot], Bk[i]); else if (Bk[i] == 1.2345e300) tab[i] = 1.0;
-        }
-    }
-    __syncthreads();
-    // flush: 8 lanes per block line, 32 lines per pass, 4 passes in flight
-    const int l8 = t & 7;
-    if (dbg & 2) return;
-    for (int s0 = t >> 3; s0 < nb; s0 += 32 * 4) {
-        double2 oldv[4];
-        long long addr[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int s = s0 + 32 * k;
-            addr[k] = -1;
-            if (s < nb) {
-                addr[k] = (long long)blk_nz[b0 + s] * 16 + 2 * l8;
-                oldv[k] = *reinterpret_cast<const double2*>(val + addr[k]);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int s = s0 + 32 * k;
-            if (addr[k] >= 0) {
-                double2 nv;
-                nv.x = oldv[k].x + tab[(2 * l8) * NS + s];
-                nv.y = oldv[k].y + tab[(2 * l8 + 1) * NS + s];
-                *reinterpret_cast<double2*>(val + addr[k]) = nv;
-            }
-        }
-    }
-}
-
-// ====================================================================================
 //  RHS: AssembleWeakFormKernel<..,1> (assemble.cu:761-924) + ElemRHSLocal2Global x4
 //  (:188-208, 1709-1724).  4 lanes per element: lane = node a for the gather and the
 //  scatter, lane = quadrature point q for the weak form; the 4 quadrature
@@ -259,60 +193,6 @@ __global__ __launch_bounds__(RBLK) void tet_rhs_kernel(I B, const I* __restrict_
     f1.x += mine[2]; f1.y += mine[3];
     f2.x += mine[4]; f2.y += mine[5];
     dst[0] = f0; dst[1] = f1; dst[2] = f2;
-}
-
-// ---- RHS, patch form (host/patch.c: DflBuildRhsPatchSchedule).  One workgroup = one spatial patch of <= 64 tets:
-// the patch's node records are staged in LDS once (each record is fetched once per patch instead of once per tet),
-// every tet is evaluated by 4 lanes exactly as above, the per-(tet, vertex) results are parked in LDS and summed per
-// patch node in a fixed order (adjacency lists), and ONE partial record per patch node is written.
-constexpr int RP_MAXN = 96;  // node records a patch may stage (the host caps patches at this many distinct nodes)
-constexpr int RP_MAXT = 64;   // tets per patch (the tet loop below takes 64 per trip)
-
-__global__ __launch_bounds__(RBLK) void tet_rhs_patch_kernel(const I* __restrict__ p_eoff, const I* __restrict__ p_noff,
-                                                            const I* __restrict__ pnode, const unsigned char* __restrict__ lien,
-                                                            const unsigned short* __restrict__ adj,
-                                                            const unsigned short* __restrict__ adj_start,
-                                                            const T* __restrict__ nodep, T* __restrict__ partial, I P, int xcd) {
-    __shared__ double s_rec[RP_MAXN][NV + 1];
-    __shared__ double s_out[RP_MAXT * 4][6 + 1];
-    __shared__ unsigned short s_adj[RP_MAXT * 4];
-    __shared__ unsigned short s_st[RP_MAXN + 1];
-    const int t = threadIdx.x;
-    // XCD-aware order (see tet_lhs_rowpatch_kernel): neighbouring patches share node records -> same L2
-    const int per = (P + 7) >> 3;
-    const int pid = (xcd & 1) ? (blockIdx.x & 7) * per + (blockIdx.x >> 3) : blockIdx.x;
-    if (pid >= P) return;
-    const int e0 = p_eoff[pid], ne = p_eoff[pid + 1] - e0;
-    const int n0 = p_noff[pid], nn = p_noff[pid + 1] - n0;
-    const int a = t & 3;
-    uchar4 lnv = make_uchar4(0, 0, 0, 0);
-    if ((t >> 2) < ne) lnv = *reinterpret_cast<const uchar4*>(lien + ((long long)e0 + (t >> 2)) * 4);
-    for (int k = t; k < ne * 4; k += RBLK) s_adj[k] = adj[(long long)e0 * 4 + k];
-    for (int k = t; k <= nn; k += RBLK) s_st[k] = adj_start[n0 + pid + k];
-    for (int k = t; k < nn * 7; k += RBLK) {
-        const int ln = k / 7, part = k - ln * 7;
-        const double2 v = reinterpret_cast<const double2*>(nodep + (long long)pnode[n0 + ln] * NREC)[part];
-        s_rec[ln][2 * part] = v.x;
-        s_rec[ln][2 * part + 1] = v.y;
-    }
-    __syncthreads();
-    if (xcd & 64) return;
-    for (int le = t >> 2; le < ne; le += REPB) {  // whole quads
-        if (le >= REPB) lnv = *reinterpret_cast<const uchar4*>(lien + ((long long)e0 + le) * 4);
-        const double* r[4] = {s_rec[lnv.x], s_rec[lnv.y], s_rec[lnv.z], s_rec[lnv.w]};
-        double mine[6];
-        rhs_quad(r, a, mine);
-#pragma unroll
-        for (int j = 0; j < 6; ++j) s_out[le * 4 + a][j] = mine[j];
-    }
-    __syncthreads();
-    // ordered sum per patch node: contributions in ascending local tet order (adjacency staged in LDS above)
-    for (int k = t; k < nn * 6; k += RBLK) {
-        const int ln = k / 6, j = k - ln * 6;
-        double sum = 0.0;
-        for (int q = s_st[ln]; q < s_st[ln + 1]; ++q) sum += s_out[s_adj[q]][j];
-        partial[(long long)n0 * 6 + k] = sum;
-    }
 }
 
 // F (reference layout) += sum of the node's partial records, ascending patch order (fixed => reproducible)
@@ -354,45 +234,7 @@ __global__ __launch_bounds__(256) void rhs_node_sum_kernel(I N, const I* __restr
 // gather layout: one line per node, written once per assembly call from the reference-layout vectors
 // nodexu != NULL: also the compact (x, u) records of the Jacobian kernel, 64 B per node (it reads nothing else of a node:
 // half the bytes per record fetched from HBM)
-__global__ __launch_bounds__(256) void pack_nodes_kernel(I N, const T* __restrict__ xg, const T* __restrict__ wg,
-                                                        const T* __restrict__ dwg, T* __restrict__ nodep, T* __restrict__ nodexu) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= N) return;
-    double r[NREC];
-    r[0] = xg[3 * i]; r[1] = xg[3 * i + 1]; r[2] = xg[3 * i + 2];
-    r[3] = wg[3 * i]; r[4] = wg[3 * i + 1]; r[5] = wg[3 * i + 2];
-    if (!nodep) {  // (uniform) a Jacobian-only call on the slot-owner schedule: the compact records are all that is read
-        double2* c = reinterpret_cast<double2*>(nodexu + i * 8);
-        c[0] = make_double2(r[0], r[1]);
-        c[1] = make_double2(r[2], r[3]);
-        c[2] = make_double2(r[4], r[5]);
-        c[3] = make_double2(0.0, 0.0);
-        return;
-    }
-    r[6] = wg[4LL * N + i];
-    r[7] = wg[5LL * N + i];
-    if (dwg) {
-        r[8] = dwg[3 * i]; r[9] = dwg[3 * i + 1]; r[10] = dwg[3 * i + 2];
-        r[11] = dwg[3LL * N + i];  // pressure always from the rate vector (Q9, assemble.cu:1606-1609)
-        r[12] = dwg[4LL * N + i];
-        r[13] = dwg[5LL * N + i];
-    } else {
-        r[8] = r[9] = r[10] = r[11] = r[12] = r[13] = 0.0;
-    }
-    r[14] = r[15] = 0.0;
-    double2* o = reinterpret_cast<double2*>(nodep + i * NREC);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) o[k] = make_double2(r[2 * k], r[2 * k + 1]);
-    if (nodexu) {
-        double2* c = reinterpret_cast<double2*>(nodexu + i * 8);
-        c[0] = make_double2(r[0], r[1]);
-        c[1] = make_double2(r[2], r[3]);
-        c[2] = make_double2(r[4], r[5]);
-        c[3] = make_double2(0.0, 0.0);
-    }
-}
-
-// The same records written through LDS: a thread still reads its own node (coalesced reads of the reference-layout arrays) but
+// The records are written through LDS: a thread reads its own node (coalesced reads of the reference-layout arrays) but
 // the wave writes its 64 records as 8 (full) / 4 (compact) store instructions of 1 KB of consecutive addresses each, instead
 // of 64 different lines per instruction.  LDS slice of a wave: piece k (16 B) of node n at [k * 65 + n].
 __global__ __launch_bounds__(256) void pack_nodes_lds_kernel(I N, const T* __restrict__ xg, const T* __restrict__ wg,
@@ -723,189 +565,10 @@ __global__ __launch_bounds__(256) void gather_ien_kernel(I T_, const I* __restri
     ien_b[i] = ien[(long long)batch_ind[i >> 2] * 4 + (i & 3)];
 }
 
-// ====================================================================================
-//  LHS, row-owner patch form (assembly schedule 3; host/rowpatch.c).  One workgroup owns the
-//  matrix rows of one spatial patch of NODES.  Work item = (tet e, local node a) with node a
-//  owned by the patch: its 4 lanes (lane = b = quadrature point q) evaluate the block row
-//  (a, 0..3) of the tet and add it into an LDS image of the owned CSR rows; afterwards the rows
-//  stream out once (val = beta * val + table; beta = 0 folds the MatrixZero pass into the write).
-//  All staging between the 4 lanes of an item goes through DPP quad broadcasts: no LDS staging,
-//  no barriers inside the item loop.
-// ====================================================================================
-
-// PROBE = true only under dfl_tune_asm (developer phase split): the shipped instantiation carries no probe branches
-template <bool PROBE>
-__global__ __launch_bounds__(LBLK, 5) void tet_lhs_rowpatch_kernel(I P, const I* __restrict__ p_ioff, const I* __restrict__ p_soff,
-                                                               const I* __restrict__ item_ea,
-                                                               const unsigned short* __restrict__ item_slot,
-                                                               const I* __restrict__ slot_nz, const I* __restrict__ ien,
-                                                               const T* __restrict__ egeo, const T* __restrict__ nodep,
-                                                               T* __restrict__ val, T beta, int dbg_in) {
-    const int dbg = PROBE ? dbg_in : 0;
-    extern __shared__ double dyn_lds[];
-    double* tab = dyn_lds;  // [16][nsp], entry-major
-    // XCD-aware order: workgroup w runs on XCD w % 8; give every XCD one contiguous range of the spatially
-    // ordered patches so that neighbouring patches (which share halo tets and node records) share an L2
-    const int per = (P + 7) >> 3;
-    const int pid = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-    if (pid >= P) return;
-    const int t = threadIdx.x;
-    const int b = t & 3;
-    const int i0 = p_ioff[pid], ni = p_ioff[pid + 1] - i0;
-    const int s0 = p_soff[pid], ns = p_soff[pid + 1] - s0;
-    const int nsp = ns | 1;
-    for (int i = t; i < 16 * nsp; i += LBLK) tab[i] = 0.0;
-    __syncthreads();
-    // the index chain item -> tet -> node of iteration k+1 is fetched while iteration k computes
-    const int nloop = (dbg & 1) ? 0 : ni;
-    int ea_n = 0, slot_n = 0;
-    long long node_n = 0;
-    if ((t >> 2) < nloop) {
-        ea_n = item_ea[i0 + (t >> 2)];
-        slot_n = item_slot[((long long)i0 + (t >> 2)) * 4 + b];
-        node_n = ien[(long long)(ea_n >> 2) * 4 + b];
-    }
-    for (int base = 0; base < nloop; base += LBLK / 4) {
-        const int it = base + (t >> 2);
-        const bool valid = it < ni;  // whole quads are valid or not
-        const int ea = ea_n;
-        const int slot = slot_n;
-        const long long node_b = node_n;
-        const long long e = ea >> 2;
-        const int a = ea & 3;
-        if (it + LBLK / 4 < ni) {
-            ea_n = item_ea[i0 + it + LBLK / 4];
-            slot_n = item_slot[((long long)i0 + it + LBLK / 4) * 4 + b];
-            node_n = ien[(long long)(ea_n >> 2) * 4 + b];
-        }
-        const double* nrec = nodep + node_b * 16 + 3;  // packed node record: u at [3..5]
-        double ub[3] = {nrec[0], nrec[1], nrec[2]};
-        const double* ge = egeo + e * 16;
-        const double2* grec = reinterpret_cast<const double2*>(ge);
-        const double g3 = ge[3];  // rows of J^-1 = shape gradients of nodes 1..3
-        const double2 g45 = grec[2], g67 = grec[3], g89 = grec[4], gab = grec[5], gs = grec[6];
-        const double itr = ge[14];
-        double ga[3], gb[3];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            ga[d] = ge[a * 3 + d];
-            gb[d] = ge[b * 3 + d];
-        }
-        // u at this lane's quadrature point q = b (qr_wgalpha, :1648-1655): shl(c,q) = SHB + (SHA-SHB)[c == q]
-        double uq[3];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            double sum = ub[d] + dpp_quad<0xB1>(ub[d]);
-            sum += dpp_quad<0x4E>(sum);
-            uq[d] = SHB * sum + (SHA - SHB) * ub[d];
-        }
-        // |J^-1 u|^2 and the stabilisation parameters at q (:587-603); 1/sqrt and sqrt through v_rsq_f64
-        const double c1 = g3 * uq[0] + g45.x * uq[1] + g45.y * uq[2];
-        const double c2 = g67.x * uq[0] + g67.y * uq[1] + g89.x * uq[2];
-        const double c3 = g89.y * uq[0] + gab.x * uq[1] + gab.y * uq[2];
-        const double knu = kMU / kRHO;
-        const double y = c1 * c1 + c2 * c2 + c3 * c3 + (3.0 * knu * knu) * gs.y;
-        const double tau0 = rsqrt(4.0 / (kDT * kDT) + y) * (1.0 / kRHO);
-        const double tau1 = y * rsqrt(y) * itr;
-        const double ca_own = ga[0] * uq[0] + ga[1] * uq[1] + ga[2] * uq[2];
-        // quadrature-point values of the whole quad in every lane
-        double t0[4], t1[4], ca[4], cb[4];
-#define DFL_QUAD_POINT(IQ, CTRL)                                             \
-        {                                                                    \
-            const double q0 = quad_bcast<CTRL>(uq[0]), q1 = quad_bcast<CTRL>(uq[1]), q2 = quad_bcast<CTRL>(uq[2]); \
-            ca[IQ] = ga[0] * q0 + ga[1] * q1 + ga[2] * q2; /* shconv (:574-583) */ \
-            cb[IQ] = gb[0] * q0 + gb[1] * q1 + gb[2] * q2;                   \
-            t0[IQ] = quad_bcast<CTRL>(tau0);                                 \
-            t1[IQ] = quad_bcast<CTRL>(tau1);                                 \
-        }
-        DFL_QUAD_POINT(0, 0x00)
-        DFL_QUAD_POINT(1, 0x55)
-        DFL_QUAD_POINT(2, 0xAA)
-        DFL_QUAD_POINT(3, 0xFF)
-#undef DFL_QUAD_POINT
-        // block (a, b) with b == this lane's quadrature point: the sums over q that carry shl(b, q) collapse to
-        // SHB * (plain sum) + (SHA - SHB) * (own term); same terms as lhs_block_eval, different association
-        double Bk[16];
-        {
-            const double fact1 = kALPHAM;
-            const double fact2 = kDT * kALPHAF * kGAMMA;
-            const double eK = ga[0] * gb[0] + ga[1] * gb[1] + ga[2] * gb[2];
-            double S_t0 = 0.0, S_t1 = 0.0, S_t0ca = 0.0, S_sacb = 0.0, S_t0cacb = 0.0, S_t0cb = 0.0;
-#pragma unroll
-            for (int iq = 0; iq < 4; ++iq) {
-                const double t0ca = t0[iq] * ca[iq];
-                S_t0 += t0[iq];
-                S_t1 += t1[iq];
-                S_t0ca += t0ca;
-                S_sacb += (iq == a ? SHA : SHB) * cb[iq];
-                S_t0cacb += t0ca * cb[iq];
-                S_t0cb += t0[iq] * cb[iq];
-            }
-            const double S_t0casb = SHB * S_t0ca + (SHA - SHB) * (tau0 * ca_own);
-            const double S_t0sb = SHB * S_t0 + (SHA - SHB) * tau0;
-            const double S_sasb = (a == b) ? (SHA * SHA + 3.0 * SHB * SHB) : (2.0 * SHA * SHB + 2.0 * SHB * SHB);
-            const double S_one = SHA + 3.0 * SHB;  // sum of the shape functions over the quadrature points
-            const double w = gs.x * GW;
-            const double diag = w * (fact1 * kRHO * S_sasb + fact1 * kRHO * kRHO * S_t0casb + fact2 * kRHO * S_sacb +
-                                     fact2 * kRHO * kRHO * S_t0cacb + 4.0 * fact2 * kMU * eK);
-            const double cK = 4.0 * fact2 * kMU * w, cT = fact2 * kRHO * S_t1 * w;
-            double kgb[3], tgb[3];
-#pragma unroll
-            for (int d = 0; d < 3; ++d) {
-                kgb[d] = cK * gb[d];
-                tgb[d] = cT * gb[d];
-            }
-#pragma unroll
-            for (int ii = 0; ii < 3; ++ii)
-#pragma unroll
-                for (int jj = 0; jj < 3; ++jj) Bk[ii * 4 + jj] = ga[jj] * kgb[ii] + ga[ii] * tgb[jj];
-            Bk[0] += diag;
-            Bk[5] += diag;
-            Bk[10] += diag;
-            const double cP0 = w * S_one, cP1 = w * kRHO * S_t0ca;
-            const double cU0 = w * (fact1 * kRHO * S_t0sb + fact2 * kRHO * S_t0cb), cU1 = w * fact2 * S_one;
-#pragma unroll
-            for (int ii = 0; ii < 3; ++ii) {
-                Bk[ii * 4 + 3] = cP1 * gb[ii] - cP0 * ga[ii];  // dRM/dP
-                Bk[12 + ii] = cU0 * ga[ii] + cU1 * gb[ii];     // dRC/dU
-            }
-            Bk[15] = w * S_t0 * eK;  // dRC/dP
-        }
-        if (valid) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) atomicAdd(&tab[i * nsp + slot], Bk[i]);
-        }
-    }
-    __syncthreads();
-    if (dbg & 2) return;
-    // stream the owned rows out: 8 lanes per 128-byte block line
-    const int l8 = t & 7;
-    if (beta == 0.0 || (dbg & 8)) {
-        for (int s = t >> 3; s < ns; s += LBLK / 8) {
-            const long long addr = (long long)slot_nz[s0 + s] * 16 + 2 * l8;
-            double2 nv;
-            nv.x = tab[(2 * l8) * nsp + s];
-            nv.y = tab[(2 * l8 + 1) * nsp + s];
-            *reinterpret_cast<double2*>(val + addr) = nv;
-        }
-    } else {
-        for (int s = t >> 3; s < ns; s += LBLK / 8) {
-            const long long addr = (long long)slot_nz[s0 + s] * 16 + 2 * l8;
-            double2 nv = *reinterpret_cast<const double2*>(val + addr);
-            nv.x = beta * nv.x + tab[(2 * l8) * nsp + s];
-            nv.y = beta * nv.y + tab[(2 * l8 + 1) * nsp + s];
-            *reinterpret_cast<double2*>(val + addr) = nv;
-        }
-    }
-}
-
 }  // namespace
 
 extern "C" {
 
-int g_patch_dbg = 0;
-void dfl_tune_asm(int v) { g_patch_dbg = v; }
-int dfl_tune_asm_flags(void) { return g_patch_dbg; }
 void dfl_elem_geometry(I T_, const I* ien_x, const T* xg, T* egeo, void* stream) {
     if (T_ <= 0) return;
     elem_geometry_kernel<<<ceil_div(T_, 256), 256, 0, S(stream)>>>(T_, ien_x, xg, egeo);
@@ -918,55 +581,12 @@ void dfl_assemble_tet_lhs(I B, const I* ien_b, const I* nzmap_b, const T* egeo_b
     DFL_LAUNCH_CHECK();
 }
 
-void dfl_assemble_tet_lhs_patch(I npatch, I patch_base, const I* p_eoff, const I* p_boff, const I* ien_p,
-                                const unsigned short* lslot, const I* blk_nz, const T* egeo_p, const T* nodep, T* val,
-                                I max_slots, void* stream) {
-    if (npatch <= 0) return;
-    const int NS = (int)max_slots | 1;  // odd stride: conflict-free flush reads
-    const size_t shmem = (size_t)16 * NS * sizeof(double);
-    tet_lhs_patch_kernel<<<npatch, LBLK, shmem, S(stream)>>>(p_eoff, p_boff, patch_base, ien_p, lslot, blk_nz, egeo_p, nodep, val, NS, g_patch_dbg);
-    DFL_LAUNCH_CHECK();
-}
-
-void dfl_assemble_tet_lhs_rowpatch(I npatch, const I* p_ioff, const I* p_soff, const I* item_ea, const unsigned short* item_slot,
-                                   const I* slot_nz, const I* ien, const T* egeo, const T* nodep, T* val, T beta,
-                                   I max_slots, void* stream) {
-    if (npatch <= 0) return;
-    const size_t lds = (size_t)16 * (size_t)(max_slots | 1) * sizeof(double);
-    static size_t lds_set = 0;
-    if (lds > lds_set) {
-        DFL_GUARD(hipFuncSetAttribute((const void*)tet_lhs_rowpatch_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        DFL_GUARD(hipFuncSetAttribute((const void*)tet_lhs_rowpatch_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        lds_set = lds;
-    }
-    const int grid = 8 * ((npatch + 7) / 8);
-    if (g_patch_dbg)
-        tet_lhs_rowpatch_kernel<true><<<grid, LBLK, lds, S(stream)>>>(npatch, p_ioff, p_soff, item_ea, item_slot, slot_nz, ien, egeo,
-                                                                      nodep, val, beta, g_patch_dbg);
-    else
-        tet_lhs_rowpatch_kernel<false><<<grid, LBLK, lds, S(stream)>>>(npatch, p_ioff, p_soff, item_ea, item_slot, slot_nz, ien, egeo,
-                                                                       nodep, val, beta, 0);
-    DFL_LAUNCH_CHECK();
-}
-
-void dfl_assemble_tet_rhs_patch(I npatch, const I* p_eoff, const I* p_noff, const I* pnode, const unsigned char* lien,
-                                 const unsigned short* adj, const unsigned short* adj_start, const T* nodep, T* partial,
-                                 void* stream) {
-    if (npatch <= 0) return;
-    tet_rhs_patch_kernel<<<8 * ((npatch + 7) / 8), RBLK, 0, S(stream)>>>(p_eoff, p_noff, pnode, lien, adj, adj_start, nodep,
-                                                                          partial, npatch, ((g_patch_dbg & 32) ? 0 : 1) | (g_patch_dbg & 64));
-    DFL_LAUNCH_CHECK();
-}
-
 void dfl_rhs_node_sum(I N, const I* goff, const I* gidx, const T* partial, T* F, void* stream) {
     if (N <= 0) return;
     // (three lanes per node, one 16-byte third of every partial record each: 0.147 against 0.138 ms -- not kept)
     rhs_node_sum_kernel<<<ceil_div(N, 256), 256, 0, S(stream)>>>(N, goff, gidx, partial, F);
     DFL_LAUNCH_CHECK();
 }
-
-int dfl_rhs_patch_max_nodes(void) { return RP_MAXN; }
-int dfl_rhs_patch_max_tets(void) { return RP_MAXT; }
 
 void dfl_assemble_tet_rhs(I B, const I* ien_b, const T* nodep, T* Fp, void* stream) {
     if (B <= 0) return;
@@ -976,9 +596,7 @@ void dfl_assemble_tet_rhs(I B, const I* ien_b, const T* nodep, T* Fp, void* stre
 
 void dfl_pack_nodes2(I N, const T* xg, const T* wg, const T* dwg, T* nodep, T* nodexu, void* stream) {
     if (N <= 0 || (!nodep && !nodexu)) return;
-    static const bool direct = getenv("DFL_PACK_LDS") && atoi(getenv("DFL_PACK_LDS")) == 0;  // developer A/B
-    if (direct) pack_nodes_kernel<<<ceil_div(N, 256), 256, 0, S(stream)>>>(N, xg, wg, dwg, nodep, nodexu);
-    else pack_nodes_lds_kernel<<<ceil_div(N, 256), 256, 0, S(stream)>>>(N, xg, wg, dwg, nodep, nodexu);
+    pack_nodes_lds_kernel<<<ceil_div(N, 256), 256, 0, S(stream)>>>(N, xg, wg, dwg, nodep, nodexu);
     DFL_LAUNCH_CHECK();
 }
 void dfl_pack_nodes(I N, const T* xg, const T* wg, const T* dwg, T* nodep, void* stream) {

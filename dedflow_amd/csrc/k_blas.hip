@@ -125,7 +125,6 @@ constexpr int CT = 8;
 constexpr int RPT = 4;                      // double2 slots per thread
 constexpr int ROWS_PER_BLOCK = BLK * RPT * 2;  // 2048 rows
 
-template <int MODE = 0>  // bit 1 = plain loads (developer A/B)
 __global__ __launch_bounds__(BLK) void cgs_dots_stage1(I n, I ncol, const T* __restrict__ Q, long long ldq,
                                                       const T* __restrict__ w, T* __restrict__ part, int nrb, int ct) {
     __shared__ double lds[4];
@@ -147,59 +146,13 @@ __global__ __launch_bounds__(BLK) void cgs_dots_stage1(I n, I ncol, const T* __r
 #pragma unroll
         for (int i = 0; i < RPT; ++i) {
             double2 qv;
-            if (row[i] + 1 < n) qv = (MODE & 2) ? *reinterpret_cast<const double2*>(q + row[i]) : ld_stream(q + row[i]);
+            if (row[i] + 1 < n) qv = ld_stream(q + row[i]);
             else { qv.x = (row[i] < n) ? q[row[i]] : 0.0; qv.y = 0.0; }
             acc += qv.x * wv[i].x + qv.y * wv[i].y;
         }
         double r = block_sum_256(acc, lds);
         if (threadIdx.x == 0) part[(long long)col * nrb + blockIdx.x] = r;
     }
-}
-
-// The same partial sums with ALL loads of a column tile issued before the first reduction: the kernel above runs a
-// workgroup reduction (two barriers) after every column, so only the 4 loads of one column are in flight per thread; here
-// the CT * RPT loads of the tile are, and one barrier serves the eight sums.  Same additions in the same order per column:
-// bitwise the same partial sums.
-template <int MODE = 0>
-__global__ __launch_bounds__(BLK) void cgs_dots_stage1_tile(I n, I ncol, const T* __restrict__ Q, long long ldq,
-                                                           const T* __restrict__ w, T* __restrict__ part, int nrb) {
-    __shared__ double lds8[4][CT];
-    const long long r0 = (long long)blockIdx.x * ROWS_PER_BLOCK;
-    const int c0 = blockIdx.y * CT;
-    double2 wv[RPT];
-    long long row[RPT];
-#pragma unroll
-    for (int i = 0; i < RPT; ++i) {
-        row[i] = r0 + 2LL * threadIdx.x + (long long)i * (2 * BLK);
-        if (row[i] + 1 < n) wv[i] = *reinterpret_cast<const double2*>(w + row[i]);
-        else { wv[i].x = (row[i] < n) ? w[row[i]] : 0.0; wv[i].y = 0.0; }
-    }
-    double acc[CT];
-#pragma unroll
-    for (int c = 0; c < CT; ++c) {
-        acc[c] = 0.0;
-        const int col = c0 + c;
-        if (col < ncol) {  // uniform
-            const T* q = Q + (long long)col * ldq;
-#pragma unroll
-            for (int i = 0; i < RPT; ++i) {
-                double2 qv;
-                if (row[i] + 1 < n) qv = (MODE & 2) ? *reinterpret_cast<const double2*>(q + row[i]) : ld_stream(q + row[i]);
-                else { qv.x = (row[i] < n) ? q[row[i]] : 0.0; qv.y = 0.0; }
-                acc[c] += qv.x * wv[i].x + qv.y * wv[i].y;
-            }
-        }
-    }
-    const int lane = threadIdx.x & 63, wv_id = threadIdx.x >> 6;
-#pragma unroll
-    for (int c = 0; c < CT; ++c) {
-        const double v = wave_sum(acc[c]);
-        if (lane == 0) lds8[wv_id][c] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < CT && c0 + (int)threadIdx.x < ncol)
-        part[(long long)(c0 + threadIdx.x) * nrb + blockIdx.x] =
-            (lds8[0][threadIdx.x] + lds8[1][threadIdx.x]) + (lds8[2][threadIdx.x] + lds8[3][threadIdx.x]);
 }
 
 __global__ __launch_bounds__(BLK) void cgs_dots_stage2(int nrb, const T* part, T* d_h) {
@@ -214,18 +167,14 @@ __global__ __launch_bounds__(BLK) void cgs_dots_stage2(int nrb, const T* part, T
 // w -= Q h (SUB) or y = Q c (!SUB); optional partial ||w||^2 per block
 constexpr int UPT = 2;  // double2 slots per thread (1 and 4 measured: 0.2093 against 0.2028 ms per CGS kernel)
 constexpr int UROWS = BLK * UPT * 2;
-template <bool SUB, int MODE = 0>  // MODE (developer A/B, DFL_CGS_MODE): bit 0 = columns walked last to first, bit 1 = plain loads
+template <bool SUB>
 __global__ __launch_bounds__(BLK) void cgs_update_kernel(I n, I ncol, const T* __restrict__ Q, long long ldq,
                                                         const T* __restrict__ d_h, T* __restrict__ w, T* __restrict__ part) {
     __shared__ double lds[4];
     __shared__ double sh[128];
     for (int j = threadIdx.x; j < ncol && j < 128; j += BLK) sh[j] = d_h[j];
     __syncthreads();
-    long long blk = blockIdx.x;
-    if (MODE & 4) {  // developer A/B: one contiguous slab of row chunks per XCD (workgroup b runs on XCD b % 8), as the SpMV
-        const long long per = (gridDim.x + 7) >> 3;
-        blk = (blk & 7) * per + (blk >> 3);
-    }
+    const long long blk = blockIdx.x;
     const long long r0 = blk * UROWS;
     long long row[UPT];
     double2 acc[UPT];
@@ -238,14 +187,13 @@ __global__ __launch_bounds__(BLK) void cgs_update_kernel(I n, I ncol, const T* _
         } else { acc[i].x = 0.0; acc[i].y = 0.0; }
     }
 #pragma unroll 4  // (8 columns in flight: 0.212 against 0.205 ms per CGS kernel -- slower)
-    for (int jj = 0; jj < ncol; ++jj) {
-        const int j = (MODE & 1) ? ncol - 1 - jj : jj;
+    for (int j = 0; j < ncol; ++j) {
         const double h = (j < 128) ? sh[j] : d_h[j];
         const T* q = Q + (long long)j * ldq;
 #pragma unroll
         for (int i = 0; i < UPT; ++i) {
             double2 qv;
-            if (row[i] + 1 < n) qv = (MODE & 2) ? *reinterpret_cast<const double2*>(q + row[i]) : ld_stream(q + row[i]);
+            if (row[i] + 1 < n) qv = ld_stream(q + row[i]);
             else { qv.x = (row[i] < n) ? q[row[i]] : 0.0; qv.y = 0.0; }
             if (SUB) { acc[i].x -= qv.x * h; acc[i].y -= qv.y * h; }
             else { acc[i].x += qv.x * h; acc[i].y += qv.y * h; }
@@ -260,7 +208,7 @@ __global__ __launch_bounds__(BLK) void cgs_update_kernel(I n, I ncol, const T* _
     }
     if (part) {
         double r = block_sum_256(ss, lds);
-        if (threadIdx.x == 0 && blk < gridDim.x) part[blk] = r;  // (slab order: the partial of row chunk blk, as without the remap)
+        if (threadIdx.x == 0 && blk < gridDim.x) part[blk] = r;  // (the bound always holds; kept: the kernel stays as measured)
     }
 }
 
@@ -433,103 +381,6 @@ __global__ __launch_bounds__(BLK) void cgs_update_pc_kernel(I nrows, I N, I ncol
             o[0] = make_double2(z0, z1);
             o[1] = make_double2(z2, zp);
         }
-    }
-    if (blockIdx.x == 0) {  // uniform per block: the barriers inside givens_step_block are safe
-        T* col = H + (long long)iter * ldh;
-        for (int j = threadIdx.x; j < ncol; j += BLK) col[j] = sh[j];
-        if (threadIdx.x == 0) d_nrm[0] = nrm;
-        __syncthreads();
-        givens_step_block(iter, nrm, H, ldh, gv, beta, res_hist, s_col, s_gv);
-    }
-}
-
-// The same step with TWO owned nodes per thread: nodes 2t and 2t + 1 are six consecutive velocity rows (three 16-byte
-// loads per basis column, 16-byte aligned: the column stride 4N doubles and 6t doubles are both multiples of two) and two
-// consecutive pressure rows (one 16-byte load, 8-byte aligned when N is odd) -- the node-per-thread form above streams the
-// basis with 8-byte loads (5.0 TB/s at 227k owned nodes).  REVERSE walks the basis columns from the newest to the oldest:
-// the dots pass before it read them oldest to newest, so the columns it touched last (still in the 256 MiB Infinity Cache
-// when the whole basis no longer fits) are read first.  Same arithmetic per row except for the order of the column sum.
-typedef double d2a8 __attribute__((ext_vector_type(2), aligned(8)));
-template <bool REVERSE>
-__global__ __launch_bounds__(BLK) void cgs_update_pc2_kernel(I nrows, I N, I ncol, const T* __restrict__ Q, long long ldq,
-                                                            const T* __restrict__ hraw, T* __restrict__ w,
-                                                            const T* __restrict__ dinv33, const T* __restrict__ dinv1,
-                                                            T* __restrict__ z, I iter, T* H, I ldh, T* gv, T* beta, T* res_hist,
-                                                            T* d_nrm, int* d_flag) {
-    __shared__ double sh[GIV_MAX + 2];
-    __shared__ double s_col[GIV_MAX], s_gv[2 * GIV_MAX];
-    __shared__ double s_nrm;
-    for (int j = threadIdx.x; j < ncol + 1 && j < GIV_MAX + 2; j += BLK) sh[j] = hraw[j];
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const double ww = sh[ncol];
-        double hh = 0.0;
-        for (I j = 0; j < ncol; ++j) hh += sh[j] * sh[j];
-        double r = ww - hh;
-        if (r < 1e-6 * ww) {
-            if (d_flag && blockIdx.x == 0) *d_flag = 1;
-            if (r < 0.0) r = 0.0;
-        }
-        s_nrm = sqrt(r);
-    }
-    __syncthreads();
-    const double nrm = s_nrm;
-    const long long i0 = 2 * ((long long)blockIdx.x * BLK + threadIdx.x);
-    if (i0 + 1 < nrows) {
-        const T* wu = w + 3 * i0;
-        const T* wp = w + 3LL * N + i0;
-        d2s u0 = *reinterpret_cast<const d2s*>(wu), u1 = *reinterpret_cast<const d2s*>(wu + 2), u2 = *reinterpret_cast<const d2s*>(wu + 4);
-        d2a8 pp = *reinterpret_cast<const d2a8*>(wp);
-#pragma unroll 4
-        for (int jj = 0; jj < ncol; ++jj) {
-            const int j = REVERSE ? ncol - 1 - jj : jj;
-            const double h = sh[j];
-            const T* q = Q + (long long)j * ldq;
-            const d2s q0 = __builtin_nontemporal_load(reinterpret_cast<const d2s*>(q + 3 * i0));
-            const d2s q1 = __builtin_nontemporal_load(reinterpret_cast<const d2s*>(q + 3 * i0 + 2));
-            const d2s q2 = __builtin_nontemporal_load(reinterpret_cast<const d2s*>(q + 3 * i0 + 4));
-            const d2a8 qp = __builtin_nontemporal_load(reinterpret_cast<const d2a8*>(q + 3LL * N + i0));
-            u0 -= q0 * h; u1 -= q1 * h; u2 -= q2 * h;
-            pp.x -= qp.x * h; pp.y -= qp.y * h;
-        }
-        const double s = 1.0 / nrm;
-        u0 *= s; u1 *= s; u2 *= s; pp.x *= s; pp.y *= s;
-        *reinterpret_cast<d2s*>(w + 3 * i0) = u0;
-        *reinterpret_cast<d2s*>(w + 3 * i0 + 2) = u1;
-        *reinterpret_cast<d2s*>(w + 3 * i0 + 4) = u2;
-        *reinterpret_cast<d2a8*>(w + 3LL * N + i0) = pp;
-        const T* A = dinv33 + i0 * 9;  // node 2t: (u0.x, u0.y, u1.x); node 2t + 1: (u1.y, u2.x, u2.y)
-        d2s z0, z1, z2;
-        z0.x = A[0] * u0.x + A[3] * u0.y + A[6] * u1.x;
-        z0.y = A[1] * u0.x + A[4] * u0.y + A[7] * u1.x;
-        z1.x = A[2] * u0.x + A[5] * u0.y + A[8] * u1.x;
-        z1.y = A[9] * u1.y + A[12] * u2.x + A[15] * u2.y;
-        z2.x = A[10] * u1.y + A[13] * u2.x + A[16] * u2.y;
-        z2.y = A[11] * u1.y + A[14] * u2.x + A[17] * u2.y;
-        *reinterpret_cast<d2s*>(z + 3 * i0) = z0;
-        *reinterpret_cast<d2s*>(z + 3 * i0 + 2) = z1;
-        *reinterpret_cast<d2s*>(z + 3 * i0 + 4) = z2;
-        d2a8 zp;
-        zp.x = pp.x * dinv1[i0];
-        zp.y = pp.y * dinv1[i0 + 1];
-        *reinterpret_cast<d2a8*>(z + 3LL * N + i0) = zp;
-    } else if (i0 < nrows) {  // the odd last node
-        const long long i = i0;
-        double a0 = w[3 * i], a1 = w[3 * i + 1], a2 = w[3 * i + 2], ap = w[3LL * N + i];
-        for (int jj = 0; jj < ncol; ++jj) {
-            const int j = REVERSE ? ncol - 1 - jj : jj;
-            const double h = sh[j];
-            const T* q = Q + (long long)j * ldq;
-            a0 -= q[3 * i] * h; a1 -= q[3 * i + 1] * h; a2 -= q[3 * i + 2] * h; ap -= q[3LL * N + i] * h;
-        }
-        const double s = 1.0 / nrm;
-        a0 *= s; a1 *= s; a2 *= s; ap *= s;
-        w[3 * i] = a0; w[3 * i + 1] = a1; w[3 * i + 2] = a2; w[3LL * N + i] = ap;
-        const T* A = dinv33 + i * 9;
-        z[3 * i + 0] = A[0] * a0 + A[3] * a1 + A[6] * a2;
-        z[3 * i + 1] = A[1] * a0 + A[4] * a1 + A[7] * a2;
-        z[3 * i + 2] = A[2] * a0 + A[5] * a1 + A[8] * a2;
-        z[3LL * N + i] = ap * dinv1[i];
     }
     if (blockIdx.x == 0) {  // uniform per block: the barriers inside givens_step_block are safe
         T* col = H + (long long)iter * ldh;
@@ -789,21 +640,6 @@ void dfl_dscal_inv_dev(I n, const T* d_scale, T* x, void* stream) {
     DFL_LAUNCH_CHECK();
 }
 
-static int cgs_mode() {
-    static int m = -1;
-    if (m < 0) m = getenv("DFL_CGS_MODE") ? atoi(getenv("DFL_CGS_MODE")) & 7 : 0;
-    return m;
-}
-#define CGS_UPDATE_LAUNCH(...)                                                                     \
-    do {                                                                                           \
-        switch (cgs_mode()) {                                                                      \
-            case 1: cgs_update_kernel<true, 1><<<g, BLK, 0, S(stream)>>>(__VA_ARGS__); break;      \
-            case 2: cgs_update_kernel<true, 2><<<g, BLK, 0, S(stream)>>>(__VA_ARGS__); break;      \
-            case 3: cgs_update_kernel<true, 3><<<g, BLK, 0, S(stream)>>>(__VA_ARGS__); break;      \
-            case 4: cgs_update_kernel<true, 4><<<(g + 7) / 8 * 8, BLK, 0, S(stream)>>>(__VA_ARGS__); break; \
-            default: cgs_update_kernel<true, 0><<<g, BLK, 0, S(stream)>>>(__VA_ARGS__); break;     \
-        }                                                                                          \
-    } while (0)
 int64_t dfl_cgs_work_size(I n, I ncol) {
     int64_t nrb = ceil_div(n, ROWS_PER_BLOCK);
     int64_t a = nrb * (int64_t)(ncol > 0 ? ncol : 1);
@@ -813,25 +649,16 @@ int64_t dfl_cgs_work_size(I n, I ncol) {
 void dfl_cgs_dots(I n, I ncol, const T* Q, int64_t ldq, const T* w, T* d_h, T* work, void* stream) {
     if (ncol <= 0) return;
     int nrb = ceil_div(n, ROWS_PER_BLOCK);
-    // column tile of a workgroup: w is read once per (row block, tile), so with tiles of 8 a 41-column step re-read it six
-    // times (15 % of the kernel's bytes over a 40-iteration solve); tiles of 64 read it once while the grid still has
-    // thousands of row blocks.  Below 64k rows the grid would get too small: tiles of 8 there (DFL_CGS_TILE overrides).
-    static int tile_env = -1;
-    if (tile_env < 0) tile_env = getenv("DFL_CGS_TILE") ? atoi(getenv("DFL_CGS_TILE")) : 0;
-    const int ct = tile_env > 0 ? tile_env : CT;  // (measured: 0.2013-0.2017 ms per CGS kernel with 64, 0.2021-0.2026 with 8: the re-reads of w come out of the caches; not worth a change of the default)
-    dim3 grid(nrb, ceil_div(ncol, ct));
-    // developer A/B, DFL_CGS_DOTS_TILE=1: all loads of a column tile before the reductions -- 0.2144-0.216 against 0.212-0.2138 ms:
-    // not faster (occupancy already hides the per-column barrier), so the per-column kernel stays
-    static const bool per_column = !(getenv("DFL_CGS_DOTS_TILE") && atoi(getenv("DFL_CGS_DOTS_TILE")) == 1);
-    if (cgs_mode() & 2) cgs_dots_stage1<2><<<grid, BLK, 0, S(stream)>>>(n, ncol, Q, ldq, w, work, nrb, ct);
-    else if (per_column) cgs_dots_stage1<0><<<grid, BLK, 0, S(stream)>>>(n, ncol, Q, ldq, w, work, nrb, ct);
-    else { dim3 grid8(nrb, ceil_div(ncol, CT)); cgs_dots_stage1_tile<0><<<grid8, BLK, 0, S(stream)>>>(n, ncol, Q, ldq, w, work, nrb); }
+    // column tile of a workgroup: CT columns share one read of w per row block (tiles of 64, which read w once per 41-column
+    // step, measured 0.2013-0.2017 against 0.2021-0.2026 ms per CGS kernel: the re-reads of w come out of the caches)
+    dim3 grid(nrb, ceil_div(ncol, CT));
+    cgs_dots_stage1<<<grid, BLK, 0, S(stream)>>>(n, ncol, Q, ldq, w, work, nrb, CT);
     cgs_dots_stage2<<<ncol, BLK, 0, S(stream)>>>(nrb, work, d_h);
     DFL_LAUNCH_CHECK();
 }
 void dfl_cgs_update(I n, I ncol, const T* Q, int64_t ldq, const T* d_h, T* w, T* d_nrm, int take_sqrt, T* work, void* stream) {
     int g = ceil_div(n, UROWS);
-    CGS_UPDATE_LAUNCH(n, ncol, Q, ldq, d_h, w, d_nrm ? work : nullptr);
+    cgs_update_kernel<true><<<g, BLK, 0, S(stream)>>>(n, ncol, Q, ldq, d_h, w, d_nrm ? work : nullptr);
     if (d_nrm) {
         if (take_sqrt) reduce_stage2<true><<<1, BLK, 0, S(stream)>>>(g, work, d_nrm);
         else reduce_stage2<false><<<1, BLK, 0, S(stream)>>>(g, work, d_nrm);
@@ -841,7 +668,7 @@ void dfl_cgs_update(I n, I ncol, const T* Q, int64_t ldq, const T* d_h, T* w, T*
 void dfl_cgs_update_givens(I n, I ncol, const T* Q, int64_t ldq, const T* d_h, T* w, T* d_nrm, T* work, I iter, T* d_H, I ldh,
                            T* d_gv, T* d_beta, T* d_res_hist, void* stream) {
     int g = ceil_div(n, UROWS);
-    CGS_UPDATE_LAUNCH(n, ncol, Q, ldq, d_h, w, work);
+    cgs_update_kernel<true><<<g, BLK, 0, S(stream)>>>(n, ncol, Q, ldq, d_h, w, work);
     norm_givens_kernel<<<1, BLK, 0, S(stream)>>>(g, work, d_nrm, iter, d_H, ldh, d_gv, d_beta, d_res_hist);
     DFL_LAUNCH_CHECK();
 }
@@ -878,23 +705,8 @@ void dfl_cgs_update_pc_givens_x4(I nrows, I N, I ncol, const T* Q, int64_t ldq, 
                                  const T* dinv1, T* z, T* z4, I iter, T* d_H, I ldh, T* d_gv, T* d_beta, T* d_res_hist, T* d_nrm,
                                  int* d_flag, void* stream) {
     if (ncol + 1 > GIV_MAX + 2 || nrows <= 0) abort();  // the caller falls back to the separate kernels beyond GIV_MAX columns
-    // DFL_UPDATE_PC: 0 = one node per thread (default), 1 = two nodes per thread (16-byte loads), 2 = + newest column first.
-    // Measured on rank 0 / rank 4 of the 8-way 10M-tet partition (gpurun_out/r3c, profiles/r03_rank_local_*): 7.99 / 7.39 ms
-    // per step with 0, 8.09 / 7.51 with 1, 8.11 / 7.51 with 2 -- at 227k owned nodes the two-node form leaves 1.7 waves per
-    // SIMD, and the wider loads do not make up for the lost memory-level parallelism; the column order changes nothing (the
-    // rank's basis streams from HBM either way).  The wide forms stay for A/B.
-    static int variant = -1;
-    if (variant < 0) { const char* e = getenv("DFL_UPDATE_PC"); variant = e ? atoi(e) : 0; }
-    const int grid2 = (int)ceil_div((nrows + 1) / 2, BLK);
-    if (variant == 0 || z4)
-        cgs_update_pc_kernel<<<ceil_div(nrows, BLK), BLK, 0, S(stream)>>>(nrows, N, ncol, Q, ldq, d_hraw, w, dinv33, dinv1, z, iter, d_H, ldh,
-                                                                          d_gv, d_beta, d_res_hist, d_nrm, d_flag, z4);
-    else if (variant == 1)
-        cgs_update_pc2_kernel<false><<<grid2, BLK, 0, S(stream)>>>(nrows, N, ncol, Q, ldq, d_hraw, w, dinv33, dinv1, z, iter, d_H, ldh, d_gv,
-                                                                   d_beta, d_res_hist, d_nrm, d_flag);
-    else
-        cgs_update_pc2_kernel<true><<<grid2, BLK, 0, S(stream)>>>(nrows, N, ncol, Q, ldq, d_hraw, w, dinv33, dinv1, z, iter, d_H, ldh, d_gv,
-                                                                  d_beta, d_res_hist, d_nrm, d_flag);
+    cgs_update_pc_kernel<<<ceil_div(nrows, BLK), BLK, 0, S(stream)>>>(nrows, N, ncol, Q, ldq, d_hraw, w, dinv33, dinv1, z, iter, d_H, ldh,
+                                                                      d_gv, d_beta, d_res_hist, d_nrm, d_flag, z4);
     DFL_LAUNCH_CHECK();
 }
 void dfl_gmres_givens_pythagoras(I iter, T* d_nrm, T* d_H, I ldh, T* d_gv, T* d_beta, T* d_res_hist, int* d_flag, void* stream) {

@@ -17,82 +17,10 @@ constexpr int BLK = 256;
 __device__ __forceinline__ long long xidx(int col, int c, long long N3) { return c < 3 ? 3LL * col + c : N3 + col; }
 
 typedef double d2v __attribute__((ext_vector_type(2)));
-template <bool NT>
 __device__ __forceinline__ d2v ld_val(const d2v* p) {
     // the 3.3 GB value stream is read exactly once per matvec: nontemporal keeps it from
     // evicting the gathered x (55 MB at 10M tets) out of L2 / MALL
-    return NT ? __builtin_nontemporal_load(p) : *p;
-}
-
-// PERSISTENT form of the matvec (round 3, late; developer A/B, dfl_tune(0, 12 | 13 | 14) -- NOT faster: 0.59-0.62 ms against
-// 0.571 ms back to back).  The question it answers: the counters of the default kernel show 216k waves (10M tets) living
-// 4.8 us each with only 1.8 of them resident per SIMD, and a kernel reading HALF the value bytes (the single-precision copy
-// below) takes the same time with the same number of waves -- is the launch of short-lived waves what paces it?  No: with
-// workgroups that stay, the same rows take longer.  What the two kernels share is the number of L2 requests (3.5e7), one
-// per 128-byte block line or 64-byte half line plus the gathers.  Here a workgroup stays and walks blocks of 32 rows: XCD x (= blockIdx % 8) owns a contiguous slab of
-// row blocks, its W workgroups take blocks j, j + W, ... of the slab (a moving window over val / y), and the row pointers
-// of the next block are requested before the current block's loop.
-template <bool BETA0, bool NT, int U>
-__global__ __launch_bounds__(BLK) void bcsr_spmv_persist_kernel(I row0, I nrows, I N, const I* __restrict__ rp,
-                                                               const I* __restrict__ ci, const T* __restrict__ val, T alpha,
-                                                               const T* __restrict__ x, T beta, T* __restrict__ y) {
-    const int l = threadIdx.x & 7, g = threadIdx.x >> 3;  // lane in the row group, row group in the workgroup (32 of them)
-    const long long N3 = 3LL * N;
-    const int r = l >> 1;
-    const bool hi = (l & 1);
-    const d2v* __restrict__ v2 = reinterpret_cast<const d2v*>(val) + l;
-    const long long nb = ((long long)(nrows - row0) + 31) >> 5;  // blocks of 32 rows
-    const long long per = (nb + 7) >> 3;                         // blocks per XCD slab
-    const long long W = gridDim.x >> 3;                          // workgroups per XCD
-    const long long b0 = (blockIdx.x & 7) * per, b1 = min(nb, b0 + per);
-    long long b = b0 + (blockIdx.x >> 3);
-    if (b >= b1) return;
-    int row = row0 + (int)(b << 5) + g;
-    int s = 0, e = 0;
-    if (row < nrows) { s = rp[row]; e = rp[row + 1]; }
-    for (;;) {
-        const long long bn = b + W;
-        const int rown = row0 + (int)(bn << 5) + g;
-        int sn = 0, en = 0;
-        if (bn < b1 && rown < nrows) { sn = rp[rown]; en = rp[rown + 1]; }  // next block's row pointers: in flight during this block
-        if (row < nrows) {
-            double acc[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) acc[u] = 0.0;
-            int k = s;
-            for (; k + U <= e; k += U) {
-                int c[U];
-                d2v a[U];
-                double xa[U], xb[U];
-#pragma unroll
-                for (int u = 0; u < U; ++u) c[u] = ci[k + u];
-#pragma unroll
-                for (int u = 0; u < U; ++u) a[u] = ld_val<NT>(v2 + (long long)(k + u) * 8);
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    xa[u] = x[hi ? 3LL * c[u] + 2 : 3LL * c[u]];
-                    xb[u] = x[hi ? N3 + c[u] : 3LL * c[u] + 1];
-                }
-#pragma unroll
-                for (int u = 0; u < U; ++u) acc[u] += a[u].x * xa[u] + a[u].y * xb[u];
-            }
-            for (; k < e; ++k) {
-                const int c0 = ci[k];
-                const d2v a0 = ld_val<NT>(v2 + (long long)k * 8);
-                acc[0] += a0.x * x[hi ? 3LL * c0 + 2 : 3LL * c0] + a0.y * x[hi ? N3 + c0 : 3LL * c0 + 1];
-            }
-            double tot = acc[0];
-#pragma unroll
-            for (int u = 1; u < U; ++u) tot += acc[u];
-            tot += __shfl_xor(tot, 1, WAVE);
-            if (!hi) {
-                const long long yi = xidx(row, r, N3);
-                y[yi] = BETA0 ? alpha * tot : alpha * tot + beta * y[yi];
-            }
-        }
-        if (bn >= b1) break;
-        b = bn; row = rown; s = sn; e = en;
-    }
+    return __builtin_nontemporal_load(p);
 }
 
 // Matvec reading x INTERLEAVED (x4[node][4] = u0 u1 u2 p, 32 B per node): the pair of lanes of a block row fetches its two
@@ -105,12 +33,12 @@ __global__ __launch_bounds__(BLK) void interleave4_kernel(I node0, I node1, I N,
     o[0] = make_double2(x[3 * i], x[3 * i + 1]);
     o[1] = make_double2(x[3 * i + 2], x[3LL * N + i]);
 }
-// CIDX: the U column indices of a trip come with ONE load per row group (lane l fetches ci[k + l % U]) and are passed round
-// with shuffles, instead of U broadcast loads (the product launcher uses it; dfl_tune(0, 15 | 16) is the A/B without / with)
-template <bool NT, int U, bool CIDX = false>
+// The U column indices of a trip come with ONE load per row group (lane l fetches ci[k + l % U]) and are passed round with
+// shuffles, instead of U broadcast loads
 __global__ __launch_bounds__(BLK) void bcsr_spmv_x4_kernel(I row0, I nrows, I N, const I* __restrict__ rp, const I* __restrict__ ci,
                                                           const T* __restrict__ val, T alpha, const T* __restrict__ x4,
                                                           T* __restrict__ y) {
+    constexpr int U = 4;  // nodal nonzeros per loop trip
     long long blk = blockIdx.x;
     const long long per = gridDim.x >> 3;  // grid is a multiple of 8
     blk = (blk & 7) * per + (blk >> 3);
@@ -131,16 +59,11 @@ __global__ __launch_bounds__(BLK) void bcsr_spmv_x4_kernel(I row0, I nrows, I N,
     for (; k + U <= e; k += U) {
         int c[U];
         d2v a[U], xx[U];
-        if (CIDX) {
-            const int cl = ci[k + (l & (U - 1))];
+        const int cl = ci[k + (l & (U - 1))];
 #pragma unroll
-            for (int u = 0; u < U; ++u) c[u] = __shfl(cl, u, 8);
-        } else {
+        for (int u = 0; u < U; ++u) c[u] = __shfl(cl, u, 8);
 #pragma unroll
-            for (int u = 0; u < U; ++u) c[u] = ci[k + u];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) a[u] = ld_val<NT>(v2 + (long long)(k + u) * 8);
+        for (int u = 0; u < U; ++u) a[u] = ld_val(v2 + (long long)(k + u) * 8);
 #pragma unroll
         for (int u = 0; u < U; ++u) xx[u] = xv[2LL * c[u]];
 #pragma unroll
@@ -148,7 +71,7 @@ __global__ __launch_bounds__(BLK) void bcsr_spmv_x4_kernel(I row0, I nrows, I N,
     }
     for (; k < e; ++k) {
         const int c0 = ci[k];
-        const d2v a0 = ld_val<NT>(v2 + (long long)k * 8);
+        const d2v a0 = ld_val(v2 + (long long)k * 8);
         const d2v x0 = xv[2LL * c0];
         acc[0] += a0.x * x0.x + a0.y * x0.y;
     }
@@ -231,106 +154,65 @@ __global__ __launch_bounds__(BLK) void bcsr_spmv_f32_kernel(I nrows, I N, const 
 
 // U nodal nonzeros per loop trip: all U index loads, then all U value loads, then the 2U
 // gathers are issued before the first FMA -- more bytes in flight per 8-lane row group
-// STORE: 0 = every row group stores its 4 results itself (3 x 8 B + 8 B per row: two partial 128-B lines per wave
-//            instruction), 1 = developer probe without the store, 2 = as 0 with nontemporal stores,
-//        3 = the 32 rows of a workgroup are staged in LDS and written by ONE wave instruction as whole lines
-//            (48 lanes x 16 B of the velocity part + 16 lanes x 16 B of the pressure part)
-// CHUNK > 0 (with XCD): instead of ONE slab per XCD, the XCDs take chunks of CHUNK consecutive workgroups round-robin:
-//        the eight row ranges being read and written at any moment are neighbours (one moving window over val / y)
-//        rather than eight streams a fixed 1/8 of the arrays apart
-template <bool BETA0, bool NT, int U, bool XCD = false, int STORE = 0, int CHUNK = 0>
+template <bool BETA0, bool XCD>
 __global__ __launch_bounds__(BLK) void bcsr_spmv_kernel(I row0, I nrows, I N, const I* __restrict__ rp, const I* __restrict__ ci,
                                                        const T* __restrict__ val, T alpha, const T* __restrict__ x, T beta,
                                                        T* __restrict__ y) {
+    constexpr int U = 4;
     // XCD: workgroup b runs on XCD b % 8 (one L2 each); hand every XCD one contiguous slab of rows so that the x
     // entries shared by neighbouring rows are fetched into ONE L2 instead of up to eight
     long long blk = blockIdx.x;
-    if (XCD && CHUNK > 0) {
-        const long long i = blk >> 3, xcd = blk & 7;
-        blk = ((i / CHUNK) * 8 + xcd) * CHUNK + (i % CHUNK);  // grid is a multiple of 8 * CHUNK
-    } else if (XCD) {
+    if (XCD) {
         const long long per = gridDim.x >> 3;  // grid is a multiple of 8
         blk = (blk & 7) * per + (blk >> 3);
     }
     const long long gid = blk * BLK + threadIdx.x;
     const int row = row0 + (int)(gid >> 3);
     const int l = threadIdx.x & 7;
-    const bool active = row < nrows;  // whole 8-lane groups
-    if (STORE != 3 && !active) return;
+    if (row >= nrows) return;  // whole 8-lane groups
     const long long N3 = 3LL * N;
     const int r = l >> 1;
     const bool hi = (l & 1);  // false: columns (u0,u1); true: columns (u2,p)
-    double tot = 0.0;
-    if (active) {
-        const int s = rp[row], e = rp[row + 1];
-        const d2v* __restrict__ v2 = reinterpret_cast<const d2v*>(val) + l;
-        double acc[U];
+    const int s = rp[row], e = rp[row + 1];
+    const d2v* __restrict__ v2 = reinterpret_cast<const d2v*>(val) + l;
+    double acc[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u) acc[u] = 0.0;
-        int k = s;
-        for (; k + U <= e; k += U) {
-            int c[U];
-            d2v a[U];
-            double xa[U], xb[U];
+    for (int u = 0; u < U; ++u) acc[u] = 0.0;
+    int k = s;
+    for (; k + U <= e; k += U) {
+        int c[U];
+        d2v a[U];
+        double xa[U], xb[U];
 #pragma unroll
-            for (int u = 0; u < U; ++u) c[u] = ci[k + u];
+        for (int u = 0; u < U; ++u) c[u] = ci[k + u];
 #pragma unroll
-            for (int u = 0; u < U; ++u) a[u] = ld_val<NT>(v2 + (long long)(k + u) * 8);
+        for (int u = 0; u < U; ++u) a[u] = ld_val(v2 + (long long)(k + u) * 8);
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const long long ia = hi ? 3LL * c[u] + 2 : 3LL * c[u];
-                const long long ib = hi ? N3 + c[u] : 3LL * c[u] + 1;
-                xa[u] = x[ia];
-                xb[u] = x[ib];
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) acc[u] += a[u].x * xa[u] + a[u].y * xb[u];
+        for (int u = 0; u < U; ++u) {
+            const long long ia = hi ? 3LL * c[u] + 2 : 3LL * c[u];
+            const long long ib = hi ? N3 + c[u] : 3LL * c[u] + 1;
+            xa[u] = x[ia];
+            xb[u] = x[ib];
         }
-        for (; k < e; ++k) {
-            const int c0 = ci[k];
-            const d2v a0 = ld_val<NT>(v2 + (long long)k * 8);
-            const long long ia = hi ? 3LL * c0 + 2 : 3LL * c0;
-            const long long ib = hi ? N3 + c0 : 3LL * c0 + 1;
-            acc[0] += a0.x * x[ia] + a0.y * x[ib];
-        }
-        tot = acc[0];
 #pragma unroll
-        for (int u = 1; u < U; ++u) tot += acc[u];
+        for (int u = 0; u < U; ++u) acc[u] += a[u].x * xa[u] + a[u].y * xb[u];
     }
+    for (; k < e; ++k) {
+        const int c0 = ci[k];
+        const d2v a0 = ld_val(v2 + (long long)k * 8);
+        const long long ia = hi ? 3LL * c0 + 2 : 3LL * c0;
+        const long long ib = hi ? N3 + c0 : 3LL * c0 + 1;
+        acc[0] += a0.x * x[ia] + a0.y * x[ib];
+    }
+    double tot = acc[0];
+#pragma unroll
+    for (int u = 1; u < U; ++u) tot += acc[u];
     tot += __shfl_xor(tot, 1, WAVE);
-    if (STORE == 3) {
-        __shared__ double s_y[128];  // [0,96): 32 rows x (u0,u1,u2); [96,128): p of the 32 rows
-        const int lr = threadIdx.x >> 3;
-        if (!hi) s_y[r < 3 ? lr * 3 + r : 96 + lr] = alpha * tot;
-        __syncthreads();
-        const long long R = row0 + blk * (BLK / 8);  // first row of this workgroup
-        const int t = threadIdx.x;
-        if (t < 64) {
-            const bool whole = R + BLK / 8 <= nrows && !((3 * R) & 1) && !((N3 + R) & 1) && !(reinterpret_cast<uintptr_t>(y) & 15);
-            if (whole) {  // one instruction: 8 full 128-byte lines
-                const double2 v = reinterpret_cast<const double2*>(s_y)[t];
-                double2* dst = t < 48 ? reinterpret_cast<double2*>(y + 3 * R) + t : reinterpret_cast<double2*>(y + N3 + R) + (t - 48);
-                *dst = v;
-            } else {
-                for (int i = t; i < 128; i += 64) {
-                    const long long rr = R + (i < 96 ? i / 3 : i - 96);
-                    if (rr < nrows) y[i < 96 ? 3 * R + i : N3 + R + (i - 96)] = s_y[i];
-                }
-            }
-        }
-        return;
-    }
     if (!hi) {
         const long long yi = xidx(row, r, N3);
-        const double out = BETA0 ? alpha * tot : alpha * tot + beta * y[yi];
-        if (STORE == 1) { if (out == 1.2345e300) y[yi] = out; }
-        else if (STORE == 2) __builtin_nontemporal_store(out, y + yi);
-        else y[yi] = out;
+        y[yi] = BETA0 ? alpha * tot : alpha * tot + beta * y[yi];
     }
 }
-
-int g_spmv_variant = 4;
-int g_pc_apply_mode = 0;
 
 // scalar CSR, 8 lanes per row (reference-layout sub-matrices)
 __global__ __launch_bounds__(BLK) void csr_spmv_kernel(I nrow, const I* __restrict__ rp, const I* __restrict__ ci,
@@ -395,37 +277,22 @@ __global__ __launch_bounds__(BLK) void pc_setup_kernel(I nrows, const I* rp, con
 }
 
 // PCDecompositionApply (pc.c:136-147): z_u = inv(D)^T r_u (Q7), z_p = r_p * dinv1, tail copied.
-// MODE (developer A/B, dfl_tune(1, mode)): bit 0 = XCD-aware node ranges (workgroup b writes the rows that XCD b % 8 reads in
-// the SpMV that follows), bit 1 = nontemporal store of the normalised column q, bit 2 = nontemporal store of y
-template <bool SCALED, int MODE = 0>
+template <bool SCALED>
 __global__ __launch_bounds__(BLK) void pc_apply_kernel(I nrows, I N, const T* __restrict__ dinv33, const T* __restrict__ dinv1,
                                                       const T* __restrict__ x, const T* __restrict__ d_nrm, T* __restrict__ q,
                                                       T* __restrict__ y, T* __restrict__ y4 = nullptr) {
-    long long blk = blockIdx.x;
-    if (MODE & 1) {
-        const long long per = gridDim.x >> 3;  // grid is a multiple of 8
-        blk = (blk & 7) * per + (blk >> 3);
-    }
-    const long long i = blk * BLK + threadIdx.x;
+    const long long i = (long long)blockIdx.x * BLK + threadIdx.x;
     const double s = SCALED ? 1.0 / d_nrm[0] : 1.0;
     if (i < nrows) {
         const T* A = dinv33 + i * 9;  // column-major image: A(r,c) = A[r + 3c]
         double x0 = x[3 * i], x1 = x[3 * i + 1], x2 = x[3 * i + 2], xp = x[3LL * N + i];
         if (SCALED) {
             x0 *= s; x1 *= s; x2 *= s; xp *= s;
-            if (MODE & 2) {
-                __builtin_nontemporal_store(x0, q + 3 * i); __builtin_nontemporal_store(x1, q + 3 * i + 1);
-                __builtin_nontemporal_store(x2, q + 3 * i + 2); __builtin_nontemporal_store(xp, q + 3LL * N + i);
-            } else {
-                q[3 * i] = x0; q[3 * i + 1] = x1; q[3 * i + 2] = x2; q[3LL * N + i] = xp;
-            }
+            q[3 * i] = x0; q[3 * i + 1] = x1; q[3 * i + 2] = x2; q[3LL * N + i] = xp;
         }
         const double y0 = A[0] * x0 + A[3] * x1 + A[6] * x2, y1 = A[1] * x0 + A[4] * x1 + A[7] * x2;
         const double y2 = A[2] * x0 + A[5] * x1 + A[8] * x2, yp = xp * dinv1[i];
-        if (MODE & 4) {
-            __builtin_nontemporal_store(y0, y + 3 * i); __builtin_nontemporal_store(y1, y + 3 * i + 1);
-            __builtin_nontemporal_store(y2, y + 3 * i + 2); __builtin_nontemporal_store(yp, y + 3LL * N + i);
-        } else if (y) {  // (y == NULL: the caller only wants the interleaved copy)
+        if (y) {  // (y == NULL: the caller only wants the interleaved copy)
             y[3 * i + 0] = y0; y[3 * i + 1] = y1; y[3 * i + 2] = y2; y[3LL * N + i] = yp;
         }
         if (y4) {  // the interleaved copy the matvec gathers from (dfl_bcsr_spmv_x4): 32 B per node, written here for free
@@ -753,54 +620,10 @@ void dfl_bcsr_spmv_range(I row0, I row1, I N, const I* rp, const I* ci, const T*
     if (row1 <= row0) return;
     const I nrows = row1;
     const int grid = ceil_div((long long)(row1 - row0) * 8, BLK);
-    const int grid8 = (grid + 7) & ~7;
-#define SPMV_LAUNCH(B0, NTV, UV) bcsr_spmv_kernel<B0, NTV, UV><<<grid, BLK, 0, S(stream)>>>(row0, nrows, N, rp, ci, val, alpha, x, beta, y)
-    if (beta == 0.0) {
-        switch (g_spmv_variant) {
-            case 0: SPMV_LAUNCH(true, false, 2); break;
-            case 1: SPMV_LAUNCH(true, true, 2); break;
-            case 2: SPMV_LAUNCH(true, false, 4); break;
-            case 3: SPMV_LAUNCH(true, true, 4); break;
-            case 5: bcsr_spmv_kernel<true, true, 4, true, 1><<<grid8, BLK, 0, S(stream)>>>(row0, nrows, N, rp, ci, val, alpha, x, beta, y); break;
-            case 6: bcsr_spmv_kernel<true, true, 4, true, 2><<<grid8, BLK, 0, S(stream)>>>(row0, nrows, N, rp, ci, val, alpha, x, beta, y); break;
-            case 7: bcsr_spmv_kernel<true, true, 4, true, 3><<<grid8, BLK, 0, S(stream)>>>(row0, nrows, N, rp, ci, val, alpha, x, beta, y); break;
-            case 8: bcsr_spmv_kernel<true, true, 4, true, 0, 64><<<(grid + 511) / 512 * 512, BLK, 0, S(stream)>>>(row0, nrows, N, rp, ci, val, alpha, x, beta, y); break;
-            case 9: bcsr_spmv_kernel<true, true, 4, true, 0, 512><<<(grid + 4095) / 4096 * 4096, BLK, 0, S(stream)>>>(row0, nrows, N, rp, ci, val, alpha, x, beta, y); break;
-            case 10: bcsr_spmv_kernel<true, true, 4, true, 3, 64><<<(grid + 511) / 512 * 512, BLK, 0, S(stream)>>>(row0, nrows, N, rp, ci, val, alpha, x, beta, y); break;
-            case 11: bcsr_spmv_kernel<true, true, 4, true, 0, 8><<<(grid + 63) / 64 * 64, BLK, 0, S(stream)>>>(row0, nrows, N, rp, ci, val, alpha, x, beta, y); break;
-            case 16: {  // developer A/B: case 15 with one column-index load per row group and trip
-                static const T* x_seen = nullptr;
-                static T* x4 = nullptr;
-                static I n4 = 0;
-                if (n4 < N) { if (x4) DFL_GUARD(hipFree(x4)); DFL_GUARD(hipMalloc((void**)&x4, (size_t)N * 4 * sizeof(T))); n4 = N; x_seen = nullptr; }
-                if (x_seen != x) { interleave4_kernel<<<ceil_div(N, BLK), BLK, 0, S(stream)>>>(0, N, N, x, x4); x_seen = x; }
-                bcsr_spmv_x4_kernel<true, 4, true><<<grid8, BLK, 0, S(stream)>>>(row0, nrows, N, rp, ci, val, alpha, x4, y);
-                break;
-            }
-            case 15: {  // developer A/B: x read interleaved (the copy is made here, once per x pointer: timing harness only)
-                static const T* x_seen = nullptr;
-                static T* x4 = nullptr;
-                static I n4 = 0;
-                if (n4 < N) { if (x4) DFL_GUARD(hipFree(x4)); DFL_GUARD(hipMalloc((void**)&x4, (size_t)N * 4 * sizeof(T))); n4 = N; x_seen = nullptr; }
-                if (x_seen != x) { interleave4_kernel<<<ceil_div(N, BLK), BLK, 0, S(stream)>>>(0, N, N, x, x4); x_seen = x; }
-                bcsr_spmv_x4_kernel<true, 4><<<grid8, BLK, 0, S(stream)>>>(row0, nrows, N, rp, ci, val, alpha, x4, y);
-                break;
-            }
-            case 12: case 13: case 14: {  // persistent workgroups: 8 / 16 / 4 per CU
-                static int cus = 0;
-                if (!cus) { int dev = 0; DFL_GUARD(hipGetDevice(&dev)); DFL_GUARD(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)); if (cus < 8) cus = 8; }
-                const int wg_per_cu = g_spmv_variant == 12 ? 8 : g_spmv_variant == 13 ? 16 : 4;
-                int gp = (cus * wg_per_cu) / 8 * 8;
-                if (gp > grid8) gp = grid8;
-                bcsr_spmv_persist_kernel<true, true, 4><<<gp, BLK, 0, S(stream)>>>(row0, nrows, N, rp, ci, val, alpha, x, beta, y);
-                break;
-            }
-            default: bcsr_spmv_kernel<true, true, 4, true><<<grid8, BLK, 0, S(stream)>>>(row0, nrows, N, rp, ci, val, alpha, x, beta, y); break;
-        }
-    } else {
-        SPMV_LAUNCH(false, true, 4);
-    }
-#undef SPMV_LAUNCH
+    if (beta == 0.0)
+        bcsr_spmv_kernel<true, true><<<(grid + 7) & ~7, BLK, 0, S(stream)>>>(row0, nrows, N, rp, ci, val, alpha, x, beta, y);
+    else
+        bcsr_spmv_kernel<false, false><<<grid, BLK, 0, S(stream)>>>(row0, nrows, N, rp, ci, val, alpha, x, beta, y);
     DFL_LAUNCH_CHECK();
 }
 void dfl_bcsr_spmv_rows(I nrows, I N, const I* rp, const I* ci, const T* val, T alpha, const T* x, T beta, T* y, void* stream) {
@@ -873,13 +696,6 @@ void dfl_bcsr_zero_scalar_rows(I N, const I* rp, const I* ci, T* val, I n, const
     bcsr_zero_scalar_rows_kernel<<<ceil_div((long long)n * 8, BLK), BLK, 0, S(stream)>>>(N, rp, ci, val, n, row, shift, diag);
     DFL_LAUNCH_CHECK();
 }
-/* kernel-variant selection for A/B measurements (key 0: block-CSR SpMV variant 0..4; 4 = default, XCD-aware row slabs) */
-extern int g_rhs_lane_grid_cap;
-void dfl_tune(int key, int value) {
-    if (key == 0) g_spmv_variant = value;
-    if (key == 1) g_pc_apply_mode = value;
-    if (key == 2) g_rhs_lane_grid_cap = value;  // workgroups of the persistent residual kernel (0 = as many as are resident)
-}
 void dfl_interleave4(I node0, I node1, I N, const T* x, T* x4, void* stream) {
     if (node1 <= node0) return;
     interleave4_kernel<<<ceil_div(node1 - node0, BLK), BLK, 0, S(stream)>>>(node0, node1, N, x, x4);
@@ -890,7 +706,7 @@ void dfl_bcsr_spmv_x4(I row0, I row1, I N, const I* rp, const I* ci, const T* va
     const int grid = ceil_div((long long)(row1 - row0) * 8, BLK);
     const int grid8 = (grid + 7) & ~7;
     // (column indices by one cooperative load per row group and trip: 0.4990 against 0.5027 ms back to back)
-    bcsr_spmv_x4_kernel<true, 4, true><<<grid8, BLK, 0, S(stream)>>>(row0, row1, N, rp, ci, val, alpha, x4, y);
+    bcsr_spmv_x4_kernel<<<grid8, BLK, 0, S(stream)>>>(row0, row1, N, rp, ci, val, alpha, x4, y);
     DFL_LAUNCH_CHECK();
 }
 void dfl_bcsr_values_to_f32(int64_t n, const T* val, float* valf, void* stream) {
@@ -937,15 +753,7 @@ void dfl_pc_jacobi_apply(I N, I n, const T* dinv33, const T* dinv1, const T* x, 
 void dfl_pc_jacobi_apply_scaled_rows(I nrows, I N, I n, const T* dinv33, const T* dinv1, const T* w, const T* d_nrm, T* q_out,
                                      T* y, void* stream) {
     if (nrows > 0) {
-        const int g = ceil_div(nrows, BLK), g8 = (g + 7) & ~7;
-        switch (g_pc_apply_mode) {
-            case 1: pc_apply_kernel<true, 1><<<g8, BLK, 0, S(stream)>>>(nrows, N, dinv33, dinv1, w, d_nrm, q_out, y); break;
-            case 2: pc_apply_kernel<true, 2><<<g, BLK, 0, S(stream)>>>(nrows, N, dinv33, dinv1, w, d_nrm, q_out, y); break;
-            case 3: pc_apply_kernel<true, 3><<<g8, BLK, 0, S(stream)>>>(nrows, N, dinv33, dinv1, w, d_nrm, q_out, y); break;
-            case 4: pc_apply_kernel<true, 4><<<g, BLK, 0, S(stream)>>>(nrows, N, dinv33, dinv1, w, d_nrm, q_out, y); break;
-            case 6: pc_apply_kernel<true, 6><<<g, BLK, 0, S(stream)>>>(nrows, N, dinv33, dinv1, w, d_nrm, q_out, y); break;
-            default: pc_apply_kernel<true><<<g, BLK, 0, S(stream)>>>(nrows, N, dinv33, dinv1, w, d_nrm, q_out, y); break;
-        }
+        pc_apply_kernel<true><<<ceil_div(nrows, BLK), BLK, 0, S(stream)>>>(nrows, N, dinv33, dinv1, w, d_nrm, q_out, y);
     }
     if (n > 4 * N)
         tail_copy_kernel<<<ceil_div((long long)n - 4LL * N, BLK), BLK, 0, S(stream)>>>(4LL * N, n, w, d_nrm, q_out, y);

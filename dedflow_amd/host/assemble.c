@@ -10,41 +10,26 @@
 #define BS (6)
 static b32 g_quiet = FALSE;
 /* process defaults of the per-mesh assembly configuration (copied into every mesh at Mesh3DCreate):
- *   schedule 2  tets per patch before the LDS-slot cap applies, and that cap (16 * (cap|1) * 8 B of dynamic LDS per
- *               workgroup; 448 -> 57.5 KB -> two workgroups per CU)
- *   schedule 3  nodes per patch and the cap on their summed row lengths (LDS slots)
  *   schedule 4  nodes per patch, nodal nonzeros and tets per patch (one slot offset / one tet per lane of a 256-thread
- *               workgroup: <= 255 / <= 256); residual: one wave per patch of (tets, nodes) = (16,32), (32,48) or (64,64)
+ *               workgroup: <= 255 / <= 256)
  *   face group  boundary group whose faces carry the weak-BC terms (the reference hard-codes group 4) */
-static AsmConfig g_asm = {4, 4, 96, 448, 16, 255, 7, 200, 128, 64, 64, 64, 64};
+static AsmConfig g_asm = {4, 4, 7, 200, 128};
 const AsmConfig* DflAsmDefaults(void) { return &g_asm; }
-void DflSetAssemblySchedule(int mode) { g_asm.sched_mode = mode; }
-void DflSetPatchParameters(index_type leaf, index_type slot_cap) {
-    if (leaf > 0) g_asm.patch_leaf = leaf;
-    if (slot_cap > 0 && slot_cap <= 511) g_asm.patch_cap = slot_cap;
+/* the schedule numbers that exist (include/dedflow.h); anything else is reported and replaced by the default */
+static int checked_schedule(int mode) {
+    if (mode == 0 || mode == 1 || mode == 4) return mode;
+    fprintf(stderr, "dedflow: assembly schedule %d does not exist (0, 1 or 4); using schedule 4\n", mode);
+    return 4;
 }
-void DflSetRowPatchParameters(index_type leaf_nodes, index_type slot_cap) {
-    if (leaf_nodes > 0) g_asm.rowpatch_leaf = leaf_nodes;
-    if (slot_cap > 0 && slot_cap <= 1023) g_asm.rowpatch_cap = slot_cap;
-}
+void DflSetAssemblySchedule(int mode) { g_asm.sched_mode = checked_schedule(mode); }
 void DflSetSlotPatchParameters(index_type leaf_nodes, index_type slot_cap, index_type tet_cap) {
     if (leaf_nodes > 0) g_asm.slot_leaf = leaf_nodes;
     if (slot_cap > 0) g_asm.slot_cap = slot_cap > DFL_SLOT_BLOCK - 1 ? DFL_SLOT_BLOCK - 1 : slot_cap;
     if (tet_cap > 0) g_asm.slot_tets = tet_cap > DFL_SLOT_BLOCK ? DFL_SLOT_BLOCK : tet_cap;
 }
-void DflSetRhsPatchParameters(index_type leaf_tets, index_type node_cap) {
-    if (leaf_tets > 0 && leaf_tets <= dfl_rhs_patch_max_tets()) g_asm.rhspatch_leaf = leaf_tets;
-    if (node_cap >= 4 && node_cap <= dfl_rhs_patch_max_nodes()) g_asm.rhspatch_nodes = node_cap;
-}
-void DflSetRhsWaveParameters(index_type tets, index_type nodes) {
-    if ((tets == 16 && nodes == 32) || (tets == 32 && nodes == 48) || (tets == 64 && nodes == 64)) {
-        g_asm.rhswave_tets = tets;
-        g_asm.rhswave_nodes = nodes;
-    }
-}
 void DflSetWeakBCGroup(index_type group) { g_asm.face_group = group; }
 /* the same two switches for one existing mesh (the schedule before Mesh3DGenerateColorBatch) */
-void DflMeshSetAssemblySchedule(Mesh3D* mesh, int mode) { ((MeshExt*)mesh->ext)->cfg.sched_mode = mode; }
+void DflMeshSetAssemblySchedule(Mesh3D* mesh, int mode) { ((MeshExt*)mesh->ext)->cfg.sched_mode = checked_schedule(mode); }
 void DflMeshSetWeakBCGroup(Mesh3D* mesh, index_type group) { ((MeshExt*)mesh->ext)->cfg.face_group = group; }
 void DflSetQuiet(b32 quiet) { g_quiet = quiet; }
 void DflMeshSetExternalLoad(Mesh3D* mesh, const f64* load) { ((MeshExt*)mesh->ext)->ext_load = load; }
@@ -55,10 +40,6 @@ void DflMeshGeometryChanged(Mesh3D* mesh) {
     if (!x) return;
     CdamFreeDevice(x->egeo_b, 0);
     x->egeo_b = NULL;
-    if (x->patch) { /* schedule 2 keeps its own copy in patch order */
-        CdamFreeDevice(x->patch->d_egeo, 0);
-        x->patch->d_egeo = NULL;
-    }
     /* schedule 4 and the residual kernels recompute the geometry from the node records; the face lists hold no geometry */
 }
 b32 DflQuiet(void) { return g_quiet; }
@@ -105,28 +86,16 @@ f64* DflMeshNodeRecords(Mesh3D* mesh) {
     return x->nodep;
 }
 
-/* The Jacobian schedule of this mesh for this pattern (modes 2-4), built on first use.  A builder that refuses the mesh --
+/* The Jacobian schedule of this mesh for this pattern (mode 4), built on first use.  A builder that refuses the mesh --
  * it has printed why: a node patch beyond the kernel's slot / tet limits, too many patch colors -- makes the mesh FALL BACK
  * to schedule 1 (compact colors, the reference-shaped scatter) for good instead of trapping.  Returns the mode in force. */
 static int ensure_lhs_schedule(Mesh3D* mesh, const CSRAttr* spy) {
     MeshExt* x = (MeshExt*)mesh->ext;
-    const int mode = x->cfg.sched_mode;
-    b32 failed = FALSE;
-    if (mode == 2) {
-        if (x->patch && x->patch->attr != spy) { DflFreePatchSchedule(x->patch); x->patch = NULL; }
-        if (!x->patch) x->patch = DflBuildPatchSchedule(mesh, spy, x->cfg.patch_leaf, x->cfg.patch_cap);
-        failed = x->patch == NULL;
-    } else if (mode == 3) {
-        if (x->rowpatch && x->rowpatch->attr != spy) { DflFreeRowPatchSchedule(x->rowpatch); x->rowpatch = NULL; }
-        if (!x->rowpatch) x->rowpatch = DflBuildRowPatchSchedule(mesh, spy, x->cfg.rowpatch_leaf, x->cfg.rowpatch_cap);
-        failed = x->rowpatch == NULL;
-    } else if (mode == 4) {
-        if (x->slotpatch && x->slotpatch->attr != spy) { DflFreeSlotPatchSchedule(x->slotpatch); x->slotpatch = NULL; }
-        if (!x->slotpatch) x->slotpatch = DflBuildSlotPatchSchedule(mesh, spy, x->cfg.slot_leaf, x->cfg.slot_cap, x->cfg.slot_tets);
-        failed = x->slotpatch == NULL;
-    }
-    if (failed) {
-        fprintf(stderr, "dedflow: assembly schedule %d is not available for this mesh; falling back to schedule 1 (compact colors)\n", mode);
+    if (x->cfg.sched_mode != 4) return x->cfg.sched_mode;
+    if (x->slotpatch && x->slotpatch->attr != spy) { DflFreeSlotPatchSchedule(x->slotpatch); x->slotpatch = NULL; }
+    if (!x->slotpatch) x->slotpatch = DflBuildSlotPatchSchedule(mesh, spy, x->cfg.slot_leaf, x->cfg.slot_cap, x->cfg.slot_tets);
+    if (!x->slotpatch) {
+        fprintf(stderr, "dedflow: assembly schedule 4 is not available for this mesh; falling back to schedule 1 (compact colors)\n");
         x->cfg.sched_mode = 1;
     }
     return x->cfg.sched_mode;
@@ -155,27 +124,16 @@ void DflAssembleSystemTetBeta(Mesh3D* mesh, f64* wgalpha_dptr, f64* dwgalpha_dpt
             HIPGUARD(hipMemsetAsync(val, 0, (size_t)spy->nnz * 16 * sizeof(value_type), s));
             beta_J = 1.0;
         }
-        if (x->cfg.sched_mode < 2) ensure_nzmap(mesh, spy);
+        if (x->cfg.sched_mode != 4) ensure_nzmap(mesh, spy);
     }
     /* packed gather records (one line per node) and packed residual accumulator */
     DflMeshNodeRecords(mesh);
     /* (the compact (x, u) copy only when a Jacobian follows: the residual kernels read the full records) */
-    const b32 patch_lhs = J && x->cfg.sched_mode == 2;
-    const b32 rowpatch_lhs = J && x->cfg.sched_mode == 3;
     const b32 slot_lhs = J && x->cfg.sched_mode == 4;
-    const b32 patch_rhs = F && x->cfg.sched_mode >= 2;
+    const b32 patch_rhs = F && x->cfg.sched_mode == 4;
     /* Who reads which records: the slot-owner J kernel only the compact (x, u) ones, every other element kernel the full
-       ones; a Jacobian-only call on the default schedule therefore packs only the compact records.  (DFL_RHS_DIRECT=1, a
-       measured alternative: the lane-per-tet residual kernel gathers from the caller's arrays itself and a residual-only
-       call packs nothing -- 14 8-byte gathers per node cost the kernel more, 0.38 M of 1.28 M cycles per wave, than the
-       0.10 ms pack pass it saves: 1.01 against 0.96 ms per call.) */
-    static int rhs_direct_ok = -1;
-    if (rhs_direct_ok < 0) rhs_direct_ok = getenv("DFL_RHS_DIRECT") && atoi(getenv("DFL_RHS_DIRECT")) == 1;
-    const b32 lane_rhs = patch_rhs && x->cfg.sched_mode >= 4 && x->cfg.rhswave_tets == 64 && x->cfg.rhswave_nodes == 64 &&
-                         !dfl_tune_asm_flags();
-    const b32 rhs_direct = lane_rhs && rhs_direct_ok && dwgalpha_dptr && wgalpha_dptr && !x->nodep_current &&
-                           !(getenv("DFL_RHS_WPB") && atoi(getenv("DFL_RHS_WPB")) == 4);
-    const b32 need_full = (F && !rhs_direct) || (J && !slot_lhs);
+       ones; a Jacobian-only call on the default schedule therefore packs only the compact records. */
+    const b32 need_full = F || (J && !slot_lhs);
     if (!x->nodep_current)
         dfl_pack_nodes2(N, dev->xg, wgalpha_dptr, dwgalpha_dptr, need_full ? x->nodep : NULL, slot_lhs ? x->nodexu : NULL, s);
     if (J && !slot_lhs && !x->egeo_b) { /* geometry cache in schedule order (static mesh), built once; the LHS kernels read it */
@@ -190,57 +148,21 @@ void DflAssembleSystemTetBeta(Mesh3D* mesh, f64* wgalpha_dptr, f64* dwgalpha_dpt
         if (bsz == 0) continue;
         const index_type* ien_b = x->ien_b + (size_t)off * 4;
         if (F && !patch_rhs) DFL_TIMED(DFL_TAG_ASM_RHS, dfl_assemble_tet_rhs(bsz, ien_b, x->nodep, x->Fp, s));
-        if (J && !patch_lhs && !rowpatch_lhs && !slot_lhs)
+        if (J && !slot_lhs)
             DFL_TIMED(DFL_TAG_ASM_LHS, dfl_assemble_tet_lhs(bsz, ien_b, x->nzmap_b + (size_t)off * 16, x->egeo_b + (size_t)off * 16,
                                                             x->nodep, val, s));
-    }
-    if (patch_lhs) { /* schedule 2: one launch per PATCH color, each block RMW'd once per patch (host/patch.c) */
-        if (!x->patch->d_egeo) {
-            x->patch->d_egeo = (f64*)CdamMallocDevice((ptrdiff_t)mesh->num_tet * 16 * SIZE_OF(f64));
-            dfl_elem_geometry(mesh->num_tet, x->patch->d_ien, dev->xg, x->patch->d_egeo, s);
-        }
-        const PatchSched* ps = x->patch;
-        for (index_type c = 0; c < ps->num_color; ++c) {
-            const index_type p0 = ps->color_offset[c], np = ps->color_offset[c + 1] - p0;
-            if (!np) continue;
-            DFL_TIMED(DFL_TAG_ASM_LHS, dfl_assemble_tet_lhs_patch(np, p0, ps->d_eoff, ps->d_boff, ps->d_ien, ps->d_lslot,
-                                                                  ps->d_blk_nz, ps->d_egeo, x->nodep, val, ps->max_slots, s));
-        }
-    }
-    if (rowpatch_lhs) { /* schedule 3: ONE launch, every workgroup owns the rows of its node patch (host/rowpatch.c) */
-        const RowPatchSched* rs = x->rowpatch;
-        DFL_TIMED(DFL_TAG_ASM_LHS, dfl_assemble_tet_lhs_rowpatch(rs->num_patch, rs->d_ioff, rs->d_soff, rs->d_item_ea, rs->d_item_slot,
-                                                                 rs->d_slot_nz, x->ien_b, x->egeo_b, x->nodep, val, beta_J,
-                                                                 rs->max_slots, s));
     }
     if (slot_lhs) { /* schedule 4: ONE launch, every nodal nonzero is summed in registers by its owner lanes (host/slotpatch.c) */
         const SlotPatchSched* ss = x->slotpatch;
         DFL_TIMED(DFL_TAG_ASM_LHS, dfl_assemble_tet_lhs_slot(ss->num_patch, ss->d_hdr, ss->d_ptet_lid, ss->d_pnode, ss->d_slot_nz, ss->d_ldesc,
                                                              x->nodexu, val, beta_J, ss->max_tets, s));
     }
-    if (patch_rhs) { /* schedules 2, 3, 4: patch-staged residual, two launches, fixed summation order (host/patch.c) */
-        const b32 wave = x->cfg.sched_mode >= 4; /* schedule 4: one wave per patch, padded layout */
-        if (x->rhspatch && (x->rhspatch->pad_tets > 0) != wave) {
-            DflFreeRhsPatchSchedule(x->rhspatch);
-            x->rhspatch = NULL;
-        }
-        if (!x->rhspatch)
-            x->rhspatch = wave ? DflBuildRhsPatchSchedule(mesh, x->cfg.rhswave_tets, x->cfg.rhswave_nodes, x->cfg.rhswave_tets, x->cfg.rhswave_nodes)
-                               : DflBuildRhsPatchSchedule(mesh, x->cfg.rhspatch_leaf, x->cfg.rhspatch_nodes, 0, 0);
+    if (patch_rhs) { /* schedule 4: patch-staged residual, two launches, fixed summation order (host/patch.c) */
+        if (!x->rhspatch) x->rhspatch = DflBuildRhsPatchSchedule(mesh);
         const RhsPatchSched* rp = x->rhspatch;
         int slot = DflProfileBegin(DFL_TAG_ASM_RHS);
-        if (wave && rp->d_sub4 && rhs_direct)
-            dfl_assemble_tet_rhs_lane_direct(rp->num_patch, rp->d_cnt, rp->d_pnode, rp->d_lien, rp->d_sub4, rp->d_sub_start, dev->xg,
-                                             wgalpha_dptr, dwgalpha_dptr, N, rp->d_partial, s);
-        else if (wave && rp->d_sub4 && !(dfl_tune_asm_flags() & 32))
-            dfl_assemble_tet_rhs_lane(rp->num_patch, rp->d_cnt, rp->d_pnode, rp->d_lien, rp->d_sub4, rp->d_sub_start, x->nodep,
-                                      rp->d_partial, s);
-        else if (wave)
-            dfl_assemble_tet_rhs_wave(rp->num_patch, rp->pad_tets, rp->pad_nodes, rp->d_cnt, rp->d_pnode, rp->d_lien, rp->d_adj,
-                                      rp->d_adj_start, x->nodep, rp->d_partial, s);
-        else
-            dfl_assemble_tet_rhs_patch(rp->num_patch, rp->d_eoff, rp->d_noff, rp->d_pnode, rp->d_lien, rp->d_adj, rp->d_adj_start,
-                                       x->nodep, rp->d_partial, s);
+        dfl_assemble_tet_rhs_lane(rp->num_patch, rp->d_cnt, rp->d_pnode, rp->d_lien, rp->d_sub4, rp->d_sub_start, x->nodep,
+                                  rp->d_partial, s);
         dfl_rhs_node_sum(N, rp->d_goff, rp->d_gidx, rp->d_partial, F, s);
         DflProfileEnd(slot);
     } else if (F) {
@@ -286,10 +208,10 @@ void DflAssembleSystemPrepacked(Mesh3D* mesh, f64* wgalpha, f64* dwgalpha, f64* 
     hipStream_t s = DflStream();
     DflRangePush(F && J ? "AssembleSystem(F,J)" : F ? "AssembleSystem(F)" : "AssembleSystem(J)");
     if (F) HIPGUARD(hipMemsetAsync(F, 0, (size_t)num_node * sizeof(f64) * BS, s));
-    /* schedule 3 writes every row of J exactly once: the zero pass folds into that write */
-    if (J && Mesh3DNumTet(mesh) && MatrixFSBlockValues(J) && x->cfg.sched_mode >= 2)
+    /* schedule 4 writes every row of J exactly once: the zero pass folds into that write */
+    if (J && Mesh3DNumTet(mesh) && MatrixFSBlockValues(J) && x->cfg.sched_mode == 4)
         (void)ensure_lhs_schedule(mesh, ((MatrixFS*)J->data)->spy1x1); /* may fall back to schedule 1: decides `overwrite` */
-    const b32 overwrite = J && x->cfg.sched_mode >= 3 && Mesh3DNumTet(mesh) && MatrixFSBlockValues(J);
+    const b32 overwrite = J && x->cfg.sched_mode == 4 && Mesh3DNumTet(mesh) && MatrixFSBlockValues(J);
     if (J && !overwrite) MatrixZero(J);
     if (Mesh3DNumTet(mesh)) {
         DflAssembleSystemTetBeta(mesh, wgalpha, dwgalpha, F, J, overwrite ? 0.0 : 1.0);

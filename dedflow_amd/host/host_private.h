@@ -4,57 +4,23 @@
 #include "dedflow.h"
 #include "dedflow_kernels.h"
 
-/* Patch schedule of the LHS assembly (host/patch.c): spatial patches of <= leaf tets whose (row,col)
- * blocks fit an LDS table; patches of one color share no node. */
-typedef struct PatchSched {
-    const CSRAttr* attr;       /* pattern the slot maps were built for */
-    index_type num_patch, num_color, max_slots;
-    index_type* color_offset;  /* host [num_color+1], patches sorted by color */
-    index_type* d_eoff;        /* device [num_patch+1] element offsets (patch order) */
-    index_type* d_boff;        /* device [num_patch+1] block-slot offsets */
-    index_type* d_ien;         /* device [T][4] connectivity in patch order */
-    uint16_t* d_lslot;         /* device [T][16] LDS slot of each (elem,a,b) block */
-    index_type* d_blk_nz;      /* device [sum slots] nodal nonzero of each slot */
-    f64* d_egeo;               /* device [T][16] element geometry cache in patch order */
-    int64_t total_slots;
-} PatchSched;
-PatchSched* DflBuildPatchSchedule(Mesh3D* mesh, const CSRAttr* spy, index_type leaf, index_type slot_cap);
-void DflFreePatchSchedule(PatchSched* ps);
-
-/* RHS patch schedule (host/patch.c): spatial patches of <= 64 tets / <= node_cap nodes; partial residual
- * records per (patch, node) + a node -> partials list for the ordered second pass. */
+/* RHS patch schedule (host/patch.c): spatial patches of <= 64 tets / <= 64 nodes in a fixed-stride layout (patch p at tet
+ * slot p*64, node slot p*64); partial residual records per (patch, node) + a node -> partials list for the ordered second
+ * pass. */
 typedef struct RhsPatchSched {
     index_type num_patch, total_nodes;
-    index_type* d_eoff;      /* device [P+1] tet offsets (patch order) */
-    index_type* d_noff;      /* device [P+1] patch-node offsets = partial record offsets */
-    index_type* d_pnode;     /* device [total_nodes] global node of each patch node */
-    u8* d_lien;              /* device [T][4] local (patch) node index of each tet vertex */
-    uint16_t* d_adj;         /* device [4T] per patch: (local tet)*4 + a grouped by patch node, ascending tet */
-    uint16_t* d_adj_start;   /* device [total_nodes + P] per patch nn+1 group starts */
+    index_type* d_pnode;     /* device [total_nodes] global node of each patch node, -1 = unused slot */
+    u8* d_lien;              /* device [P*64][4] local (patch) node index of each tet vertex */
     index_type* d_goff;      /* device [N+1] node -> range of gidx */
     index_type* d_gidx;      /* device [total_nodes] partial record ids of each node, ascending patch */
     f64* d_partial;          /* device [total_nodes][6] */
-    index_type pad_tets, pad_nodes; /* > 0: fixed-stride layout (patch p at tet slot p*pad_tets, node slot p*pad_nodes) */
     index_type* d_cnt;       /* device [P] num_tets | num_nodes << 16 */
-    /* 64-tet padded layout only (lane-per-tet kernel): the adjacency of a patch node cut into sub-lists of <= 4 entries */
+    /* the adjacency of a patch node (its (tet, vertex) results, ascending tet) cut into sub-lists of <= 4 entries */
     uint16_t* d_sub4;        /* device [P][128][4] result slots (local tet * 4 + a) of each sub-list, 256 = the zero slot */
-    uint16_t* d_sub_start;   /* device [P][pad_nodes + 1] first sub-list of each patch node; entry nn = number of sub-lists */
+    uint16_t* d_sub_start;   /* device [P][65] first sub-list of each patch node; entry nn = number of sub-lists */
 } RhsPatchSched;
-RhsPatchSched* DflBuildRhsPatchSchedule(Mesh3D* mesh, index_type leaf, index_type node_cap, index_type pad_tets, index_type pad_nodes);
+RhsPatchSched* DflBuildRhsPatchSchedule(Mesh3D* mesh);
 void DflFreeRhsPatchSchedule(RhsPatchSched* ps);
-
-/* Row-owner patch schedule (host/rowpatch.c): spatial patches of nodes, each owning its CSR rows. */
-typedef struct RowPatchSched {
-    const CSRAttr* attr;
-    index_type num_patch, max_slots;
-    index_type* d_ioff;      /* device [num_patch+1] item offsets */
-    index_type* d_soff;      /* device [num_patch+1] slot offsets */
-    index_type* d_item_ea;   /* device [4T] (schedule position of the tet)*4 + a */
-    uint16_t* d_item_slot;   /* device [4T][4] LDS slot of block (a, b) */
-    index_type* d_slot_nz;   /* device [nnz1] nodal nonzero of each slot */
-} RowPatchSched;
-RowPatchSched* DflBuildRowPatchSchedule(Mesh3D* mesh, const CSRAttr* spy, index_type leaf, index_type slot_cap);
-void DflFreeRowPatchSchedule(RowPatchSched* ps);
 
 /* Slot-owner patch schedule (host/slotpatch.c): node patches; every nodal nonzero is summed by one lane pair. */
 typedef struct SlotPatchSched {
@@ -75,13 +41,9 @@ void DflFreeSlotPatchSchedule(SlotPatchSched* ps);
 /* Assembly configuration of ONE mesh: a copy of the process defaults (the DflSet* setters of include/dedflow.h) taken
  * at Mesh3DCreate, so that two meshes with different schedules / face groups / patch shapes coexist in one process. */
 typedef struct AsmConfig {
-    int sched_mode;              /* 0 reference colors, 1 compact colors, 2 tet patches, 3 row-owner patches, 4 slot-owner (default) */
+    int sched_mode;              /* 0 reference colors, 1 compact colors, 4 slot-owner patches (default) */
     index_type face_group;       /* boundary group of the weak-BC faces (4 in the reference, assemble.cu:1826-1828) */
-    index_type patch_leaf, patch_cap;           /* schedule 2: tets per patch, LDS block slots */
-    index_type rowpatch_leaf, rowpatch_cap;     /* schedule 3: nodes per patch, LDS block slots */
     index_type slot_leaf, slot_cap, slot_tets;  /* schedule 4: nodes per patch, nodal nonzeros, tets touching the patch */
-    index_type rhspatch_leaf, rhspatch_nodes;   /* schedules 2, 3: residual patches */
-    index_type rhswave_tets, rhswave_nodes;     /* schedule 4: one wave per residual patch */
 } AsmConfig;
 const AsmConfig* DflAsmDefaults(void);
 struct FlowWork;
@@ -105,14 +67,11 @@ typedef struct MeshExt {
     index_type *face_nz, *face_nz_off, *face_nz_ent;       /* device: nonzero, CSR offsets, entries f*16+a*4+b */
     f64 *face_pF, *face_pJ;        /* device parking buffers [nf][16] and [nf][256] */
     index_type* h_f2e;             /* host copy of bound_f2e */
-    index_type* h_sched_elem;      /* host [T]: element id at each position of the execution schedule */
     f64* egeo_b;                   /* device [T][16] element geometry cache in schedule order (LHS kernel) */
     f64* nodep;                    /* device [N][16] packed gather records (x,u,phi,T,du,p,dphi,dT) */
     f64* nodexu;                   /* device [N][8] compact (x,u) records: all the slot-owner Jacobian kernel reads of a node */
     f64* Fp;                       /* device [N][8] packed residual accumulator, zero between calls */
-    RhsPatchSched* rhspatch;       /* RHS patch schedule (modes 2, 3), built on first use */
-    RowPatchSched* rowpatch;       /* LHS row-owner patch schedule (mode 3), built on first use */
-    PatchSched* patch;             /* LHS patch schedule (assembly schedule mode 2), built on first use */
+    RhsPatchSched* rhspatch;       /* RHS patch schedule (mode 4), built on first use */
     SlotPatchSched* slotpatch;     /* LHS slot-owner schedule (mode 4, default), built on first use */
     const f64* ext_load;           /* device [3N] external load on the momentum rows (DflMeshSetExternalLoad), NULL: none */
     struct ScalarState* scalar;    /* phi / T transport (host/scalar.c, DflMeshSetScalarTransport), NULL: off */
@@ -121,7 +80,7 @@ typedef struct MeshExt {
 void DflMeshPrepareFaces(Mesh3D* mesh, index_type group);
 void DflMeshPrepareFaceNonzeros(Mesh3D* mesh, index_type group, const CSRAttr* spy);
 void DflMeshFreeFaceLists(struct MeshExt* x);
-/* AssembleSystemTet with J = beta_J * J + contributions (beta_J = 0 only takes effect in schedules 3 and 4) */
+/* AssembleSystemTet with J = beta_J * J + contributions (beta_J = 0 only takes effect in schedule 4) */
 void DflAssembleSystemTetBeta(Mesh3D* mesh, f64* wgalpha, f64* dwgalpha, f64* F, Matrix* J, f64 beta_J);
 b32 DflQuiet(void);
 

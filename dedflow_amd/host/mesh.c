@@ -92,14 +92,11 @@ void Mesh3DDestroy(Mesh3D* m) {
     if (x) {
         CdamFreeDevice(x->ien_b, 0);
         CdamFreeDevice(x->nzmap_b, 0);
-        DflFreePatchSchedule(x->patch);
-        DflFreeRowPatchSchedule(x->rowpatch);
         DflFreeSlotPatchSchedule(x->slotpatch);
         DflFreeRhsPatchSchedule(x->rhspatch);
         DflFreeFlowWork(x->flow);
         DflScalarFree(x->scalar);
         CdamFreeDevice(x->egeo_b, 0);
-        if (x->h_sched_elem) CdamFreeHost(x->h_sched_elem, 0);
         CdamFreeDevice(x->nodep, 0);
         CdamFreeDevice(x->nodexu, 0);
         CdamFreeDevice(x->Fp, 0);
@@ -171,7 +168,7 @@ void Mesh3DColor(Mesh3D* mesh) {
  * 0: launches follow the reference's JPL color batches one to one (same summation order as
  *    the reference inside every matrix / RHS entry);
  * 1: compact schedule below.  Results differ from mode 0 by summation order only;
- * 2-4: patch schedules (patch.c, rowpatch.c, slotpatch.c), built on first use by host/assemble.c. */
+ * 4: patch schedules (slotpatch.c for J, patch.c for F), built on first use by host/assemble.c. */
 
 /* JPL colors one independent set of local maxima per round, i.e. ~140 colors of ~T/140 tets
  * for a tet mesh whose conflict graph needs ~30.  A 77k-tet launch is 4.4 waves per SIMD for
@@ -225,7 +222,7 @@ static b32 build_compact_schedule(Mesh3D* mesh, MeshExt* x) {
     dfl_gather_ien(T, mesh->device->ien, d_ind, x->ien_b, DflStream());
     HIPGUARD(hipStreamSynchronize(DflStream()));
     CdamFreeDevice(d_ind, 0);
-    x->h_sched_elem = ind; /* schedule position -> element id, kept for the row-owner schedule builder */
+    CdamFreeHost(ind, 0);
     CdamFreeHost(cls, 0);
     CdamFreeHost(node_mask, 0);
     return TRUE;
@@ -246,17 +243,13 @@ void Mesh3DGenerateColorBatch(Mesh3D* mesh) {
     dfl_color_batches(mesh->color, T, nc, mesh->batch_offset, mesh->batch_ind);
     x->ien_b = (index_type*)CdamMallocDevice((ptrdiff_t)T * 4 * SIZE_OF(index_type));
     if (x->sched_offset) CdamFreeHost(x->sched_offset, 0);
-    if (x->h_sched_elem) CdamFreeHost(x->h_sched_elem, 0);
-    x->h_sched_elem = NULL;
     if (x->cfg.sched_mode == 0 || !build_compact_schedule(mesh, x)) {
         /* execution schedule == the reference's JPL color batches (asked for, or the compact schedule refused the mesh: the
-           colored kernels of schedule 1 then run one launch per reference color; schedules 2-4 are unaffected) */
+           colored kernels of schedule 1 then run one launch per reference color; schedule 4 is unaffected) */
         x->sched_num = nc;
         x->sched_offset = (index_type*)CdamMallocHost(SIZE_OF(index_type) * (nc + 1));
         memcpy(x->sched_offset, mesh->batch_offset, sizeof(index_type) * (size_t)(nc + 1));
         dfl_gather_ien(T, mesh->device->ien, mesh->batch_ind, x->ien_b, DflStream());
-        x->h_sched_elem = (index_type*)CdamMallocHost((ptrdiff_t)T * SIZE_OF(index_type));
-        HIPGUARD(hipMemcpy(x->h_sched_elem, mesh->batch_ind, sizeof(index_type) * (size_t)T, D2H));
     }
     HIPGUARD(hipStreamSynchronize(DflStream()));
 }

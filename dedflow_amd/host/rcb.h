@@ -1,5 +1,5 @@
 /* Recursive-coordinate-bisection helpers shared by the partitioner and the patch / aggregate builders (host/partition.c,
- * patch.c, rowpatch.c, slotpatch.c, pc_twolevel.c): the total order on points along one axis (ties broken by index, so
+ * patch.c, slotpatch.c, pc_twolevel.c): the total order on points along one axis (ties broken by index, so
  * that every build of a schedule is deterministic), quickselect on an index array, the longest axis of a point set. */
 #ifndef DFL_HOST_RCB_H
 #define DFL_HOST_RCB_H

@@ -645,28 +645,19 @@ void DflSetWeakBCGroup(index_type group);
 void DflMeshSetAssemblySchedule(Mesh3D* mesh, int mode);
 void DflMeshSetWeakBCGroup(Mesh3D* mesh, index_type group);
 void DflSetQuiet(b32 quiet); /* suppress the reference's stdout chatter ("Assemble: F J", timers) */
-/* which conflict-free launches the assembly kernels execute (set BEFORE Mesh3DGenerateColorBatch):
+/* which schedule the assembly kernels execute (set BEFORE Mesh3DGenerateColorBatch):
  *   0  the reference's JPL color batches, one launch per color (reference summation order)
  *   1  compact balanced re-coloring, ~4x fewer / larger launches; mesh->color,
- *      batch_offset and batch_ind are the reference's JPL result in both modes */
+ *      batch_offset and batch_ind are the reference's JPL result in both modes
+ *   4  (default) slot-owner node patches for J (host/slotpatch.c): one launch, every workgroup owns the CSR rows of its nodes,
+ *      every nodal nonzero is summed in registers by its owner lanes and written once -- no atomics, fixed summation order
+ *      (bitwise reproducible), no geometry cache; AssembleSystem skips the zero pass.  The residual is assembled by spatial
+ *      patches of <= 64 tets / <= 64 nodes (host/patch.c), one lane per tet, summed per node in a fixed order.
+ *      A mesh whose patches exceed the kernel's limits falls back to schedule 1 (with a message on stderr).
+ * Any other value is reported on stderr and replaced by 4. */
 void DflSetAssemblySchedule(int mode);
-/*   2  as 1 for the RHS; the Jacobian is assembled patch-wise: one workgroup sums all blocks of a spatial
- *      patch of tets in LDS and read-modify-writes each distinct block once per patch (host/patch.c) --
- *      ~3x less HBM traffic than one RMW per tet; LDS atomics => values reproducible to rounding, not bitwise */
-void DflSetPatchParameters(index_type leaf, index_type slot_cap);
-/*   3  (default) as 1 for the RHS; the Jacobian is assembled by row-owner node patches: one launch, every workgroup sums the
- *      block rows of its nodes in LDS and writes them once (host/rowpatch.c); AssembleSystem skips the zero pass.
- *      Reproducible to rounding, not bitwise (LDS atomics). */
-/* schedule 3 (row-owner node patches): nodes per patch and cap on their summed nodal row lengths
- * (one 128-byte LDS line per nodal nonzero; 255 -> 32 KB per workgroup) */
-void DflSetRowPatchParameters(index_type leaf_nodes, index_type slot_cap);
-/*   4  slot-owner node patches for J (host/slotpatch.c): as 3, but every nodal nonzero is summed in registers by its owner
- *      lanes and written once -- no LDS atomics, fixed summation order (bitwise reproducible), no geometry cache */
+/* schedule 4: nodes per patch, cap on the nodal nonzeros of a patch and on the tets touching it */
 void DflSetSlotPatchParameters(index_type leaf_nodes, index_type slot_cap, index_type tet_cap);
-/* schedule 4 assembles the residual with one wave per patch of <= tets tets / <= nodes nodes: (16,32), (32,48) or (64,64) */
-void DflSetRhsWaveParameters(index_type tets, index_type nodes);
-/* schedules 2 and 3 assemble the residual by spatial tet patches (<= 64 tets, <= node_cap <= 96 distinct nodes each) */
-void DflSetRhsPatchParameters(index_type leaf_tets, index_type node_cap);
 
 /* ---- arrays / particles (Array.h, Particle.h) ------------------------------------------ */
 typedef struct Array {

@@ -321,35 +321,11 @@ void dfl_elem_geometry(dfl_index T, const dfl_index* ien_x, const dfl_value* xg,
 void dfl_assemble_tet_lhs(dfl_index batch_size, const dfl_index* ien_b, const dfl_index* nzmap_b, const dfl_value* egeo_b,
                           const dfl_value* nodep, dfl_value* val, void* stream);
 void dfl_assemble_tet_rhs(dfl_index batch_size, const dfl_index* ien_b, const dfl_value* nodep, dfl_value* Fp, void* stream);
-/* patch form of the same residual (host/patch.c: DflBuildRhsPatchSchedule): workgroup p evaluates tets
- * [p_eoff[p], p_eoff[p+1]) whose vertices are the patch nodes pnode[p_noff[p] + lien[tet*4 + a]], and writes one
- * 6-component partial record per patch node, partial[(p_noff[p] + k)*6 ..], summed in the order of the adjacency lists
- * (adj / adj_start).  dfl_rhs_node_sum then adds, for every node, its partial
- * records gidx[goff[n] .. goff[n+1]) in that order into F (reference layout).  No atomics: bitwise reproducible. */
-int dfl_rhs_patch_max_nodes(void);
-int dfl_rhs_patch_max_tets(void);
-void dfl_assemble_tet_rhs_patch(dfl_index npatch, const dfl_index* p_eoff, const dfl_index* p_noff, const dfl_index* pnode,
-                                 const unsigned char* lien, const unsigned short* adj, const unsigned short* adj_start,
-                                 const dfl_value* nodep, dfl_value* partial, void* stream);
+/* dfl_rhs_node_sum adds, for every node, the 6-component partial records of the patch form of the residual
+ * (dfl_assemble_tet_rhs_lane) gidx[goff[n] .. goff[n+1]) in that order into F (reference layout).  No atomics: bitwise
+ * reproducible. */
 void dfl_rhs_node_sum(dfl_index N, const dfl_index* goff, const dfl_index* gidx, const dfl_value* partial, dfl_value* F,
                       void* stream);
-/* patch form of the LHS assembly (assembly schedule 2): one workgroup per spatial patch of tets sums all
- * (a,b) blocks of the patch in an LDS table (ds_add_f64) and read-modify-writes each distinct block once.
- * Launch = the `npatch` patches [patch_base, patch_base+npatch) of one patch color (no shared nodes).
- * p_eoff/p_boff: per-patch element / block-slot offsets; ien_p: connectivity in patch order;
- * lslot[e*16 + a*4+b]: LDS slot of each block; blk_nz: nodal nonzero of each slot; max_slots <= 511. */
-void dfl_assemble_tet_lhs_patch(dfl_index npatch, dfl_index patch_base, const dfl_index* p_eoff, const dfl_index* p_boff,
-                                const dfl_index* ien_p, const unsigned short* lslot, const dfl_index* blk_nz,
-                                const dfl_value* egeo_p, const dfl_value* nodep, dfl_value* val, dfl_index max_slots,
-                                void* stream);
-/* row-owner patch form (assembly schedule 3, host/rowpatch.c): workgroup p owns the CSR rows of its nodes.
- * item_ea[i] = tet*4 + a for every (tet, owned node a) pair of the patch, item_slot[i*4 + b] = LDS slot of block
- * (a, b), slot_nz = nodal nonzero of every slot; `tet` indexes `ien` / `egeo` (execution-schedule order in the host layer).
- * val = beta * val + assembled rows (beta = 0 overwrites: no prior MatrixZero needed). */
-void dfl_assemble_tet_lhs_rowpatch(dfl_index npatch, const dfl_index* p_ioff, const dfl_index* p_soff, const dfl_index* item_ea,
-                                   const unsigned short* item_slot, const dfl_index* slot_nz, const dfl_index* ien,
-                                   const dfl_value* egeo, const dfl_value* nodep, dfl_value* val, dfl_value beta,
-                                   dfl_index max_slots, void* stream);
 /* slot-owner form (assembly schedule 4, default; host/slotpatch.c, csrc/k_assemble2.hip): workgroup p owns the CSR rows of
  * its node patch; hdr[p] = {tet_off, num_tet | num_node << 16, pos_off, num_pos, group_off, trips_lo, trips_hi, node_off};
  * pnode[node_off + n] = global id of the patch's n-th distinct node (ascending; every node of every tet touching the patch,
@@ -371,26 +347,17 @@ int64_t dfl_lhs_slot_lds_bytes(dfl_index max_tets);
 void dfl_assemble_tet_lhs_slot(dfl_index npatch, const int32_t* hdr, const uint32_t* ptet_lid, const dfl_index* pnode,
                                const dfl_index* slot_nz, const uint32_t* ldesc, const dfl_value* nodexu, dfl_value* val,
                                dfl_value beta, dfl_index max_tets, void* stream);
-/* wave-per-patch form of the residual (schedule 4): the padded layout of host/patch.c -- patch p holds tet slots
- * [p*pad_tets, ..) of lien / adj, node slots [p*pad_nodes, ..) of pnode / partial and adj_start[p*(pad_nodes+1) ..];
- * cnt[p] = num_tets | num_nodes << 16.  Supported shapes (pad_tets, pad_nodes): (16,32), (32,48), (64,64). */
-void dfl_assemble_tet_rhs_wave(dfl_index npatch, dfl_index pad_tets, dfl_index pad_nodes, const dfl_index* cnt,
-                               const dfl_index* pnode, const unsigned char* lien, const unsigned short* adj,
-                               const unsigned short* adj_start, const dfl_value* nodep, dfl_value* partial, void* stream);
-/* lane-per-tet form on the (64,64) shape: the adjacency as sub-lists of exactly 4 result slots (256 = zero slot),
+/* patch form of the residual (schedule 4, host/patch.c: DflBuildRhsPatchSchedule): the padded layout -- patch p holds tet
+ * slots [p*64, ..) of lien (four local node ids per tet, a byte each) and node slots [p*64, ..) of pnode / partial;
+ * cnt[p] = num_tets | num_nodes << 16.  One lane per tet; every patch node gets one 6-component partial record, summed in
+ * adjacency order.  grid cap > 0 (tests): at most that many workgroups (rounded up to a multiple of 8), so that a small mesh
+ * walks the pipelined patch loop. */
+void dfl_set_rhs_lane_grid_cap(int workgroups);
+/* the adjacency as sub-lists of exactly 4 result slots (256 = zero slot),
  * sub4[p][128][4], and sub_start[p][65] (first sub-list of each patch node; entry num_nodes.. = number of sub-lists) */
 void dfl_assemble_tet_rhs_lane(dfl_index npatch, const dfl_index* cnt, const dfl_index* pnode, const unsigned char* lien,
                                const unsigned short* sub4, const unsigned short* sub_start, const dfl_value* nodep,
                                dfl_value* partial, void* stream);
-/* the same kernel gathering the node values from the caller's arrays (xg[N][3] and the reference-layout state vectors
- * wgalpha / dwgalpha, all non-NULL) instead of packed records: a residual-only assembly call needs no pack pass */
-void dfl_assemble_tet_rhs_lane_direct(dfl_index npatch, const dfl_index* cnt, const dfl_index* pnode, const unsigned char* lien,
-                                      const unsigned short* sub4, const unsigned short* sub_start, const dfl_value* xg,
-                                      const dfl_value* wgalpha, const dfl_value* dwgalpha, dfl_index N, dfl_value* partial,
-                                      void* stream);
-/* developer probe of the patch kernel (bit 0 skip element loop, bit 1 skip flush, bit 2 skip LDS adds) */
-void dfl_tune_asm(int flags);
-int dfl_tune_asm_flags(void);
 /* weak-BC faces of one color (src/assemble.cu:1764-1964): face list entries index f2e/forn of the group */
 void dfl_assemble_face(dfl_index n_face, const dfl_index* face_list, const dfl_index* f2e, const dfl_index* forn,
                        const dfl_index* ien, dfl_index N, const dfl_value* xg, const dfl_value* wgalpha,

@@ -286,7 +286,7 @@ def test_reference_color_schedule_matches_compact_schedule(api, oracle_lib):
     wg, dwg = synthetic_fields(m)
     F, vals = S.assemble_system(wg, dwg, True, True)
     out = []
-    for mode in (0, 1, 2, 3, 4):
+    for mode in (0, 1, 4):
         P = api.Problem(m, schedule=mode)
         try:
             assert np.array_equal(P.color(), S.color) and np.array_equal(P.batch_ind(), S.batch_ind)
@@ -306,42 +306,6 @@ def test_reference_color_schedule_matches_compact_schedule(api, oracle_lib):
             assert ok, err
     # the two schedules agree to rounding, far inside the parity bar
     assert np.abs(out[0][0] - out[1][0]).max() <= 1e-13 * np.abs(F).max()
-
-
-def test_row_owner_schedule_add_and_overwrite(api):
-    """Schedule 3: AssembleSystemTet keeps the reference's additive contract (assemble twice = 2x), while
-    AssembleSystem (zero + assemble, src/main.c:44-52) overwrites whatever J held before; both across patch sizes."""
-    m = kuhn_cube(7, jitter=0.2)
-    wg, dwg = synthetic_fields(m)
-    L = api.lib()
-    ref = None
-    for leaf, cap in ((16, 255), (3, 40), (64, 1023)):
-        L.DflSetRowPatchParameters(leaf, cap)
-        P = api.Problem(m, schedule=3)
-        try:
-            wg_d, dwg_d = api.DeviceArray.from_numpy(wg), api.DeviceArray.from_numpy(dwg)
-            L.MatrixZero(P.J)
-            P.assemble_tet(wg_d, dwg_d, None, want_J=True)
-            api.sync()
-            v1 = P.block_values().numpy().copy()
-            P.assemble_tet(wg_d, dwg_d, None, want_J=True)
-            api.sync()
-            v2 = P.block_values().numpy().copy()
-            assert np.abs(v2 - 2.0 * v1).max() <= 1e-13 * np.abs(v1).max()
-            P.assemble_system(wg_d, dwg_d, None, want_J=True)   # J holds 2x: must be overwritten, then faces + BC rows
-            api.sync()
-            v3 = P.block_values().numpy().copy()
-            L.MatrixZero(P.J)
-            P.assemble_system(wg_d, dwg_d, None, want_J=True)
-            api.sync()
-            v4 = P.block_values().numpy()
-            assert np.abs(v3 - v4).max() <= 1e-13 * np.abs(v4).max()
-            if ref is None:
-                ref = v1
-            assert np.abs(v1 - ref).max() <= 1e-13 * np.abs(ref).max()
-        finally:
-            P.close()
-    L.DflSetRowPatchParameters(16, 255)
 
 
 def test_slot_owner_schedule_add_overwrite_and_bitwise_reproducible(api, oracle_lib):
@@ -382,35 +346,6 @@ def test_slot_owner_schedule_add_overwrite_and_bitwise_reproducible(api, oracle_
                 P.close()
     finally:
         L.DflSetSlotPatchParameters(16, 255, 208)
-
-
-def test_patch_residual_is_reproducible_and_patch_size_independent(api, oracle_lib):
-    """Schedules 2/3 assemble F by spatial tet patches with a fixed summation order: bitwise equal run to run,
-    equal to the oracle within the parity bar for every patch size (incl. 1-tet patches and ragged tails)."""
-    m = kuhn_cube(7, jitter=0.2)
-    S = oracle_lib.System(m)
-    wg, dwg = synthetic_fields(m)
-    F, _ = S.assemble_system(wg, dwg, True, False)
-    L = api.lib()
-    try:
-        for leaf, cap in ((64, 64), (1, 4), (7, 20), (64, 96)):
-            L.DflSetRhsPatchParameters(leaf, cap)
-            P = api.Problem(m, schedule=3)
-            try:
-                wg_d, dwg_d = api.DeviceArray.from_numpy(wg), api.DeviceArray.from_numpy(dwg)
-                runs = []
-                for rep in range(2):
-                    F_d = api.DeviceArray(6 * S.N)
-                    P.assemble_system(wg_d, dwg_d, F_d, want_J=False)
-                    api.sync()
-                    runs.append(F_d.numpy().copy())
-                assert np.array_equal(runs[0], runs[1])
-                ok, err = close(runs[0], F)
-                assert ok, (leaf, cap, err)
-            finally:
-                P.close()
-    finally:
-        L.DflSetRhsPatchParameters(64, 64)
 
 
 def test_two_problems_with_different_configurations_coexist(api, oracle_lib):
@@ -460,23 +395,20 @@ def test_two_problems_with_different_configurations_coexist(api, oracle_lib):
         Pb.close()
 
 
-def test_wave_residual_is_reproducible_and_shape_independent(api, oracle_lib):
-    """Schedule 4 assembles F with one wave per spatial patch (padded layout, no workgroup barriers): bitwise equal run to
-    run, equal to the oracle within the parity bar for every supported patch shape and kernel build -- the default
-    lane-per-tet kernel on 64-tet patches (2 waves per SIMD), its 1-wave build (dfl_tune_asm 64), the 4-lanes-per-tet wave
-    kernel on the same patches (32) and on the smaller shapes.  dfl_tune(2, 8) caps the persistent kernel at 8 workgroups so
-    that every wave walks several patches through the pipelined loop (prefetch of the next patch's records and lists)."""
-    m = kuhn_cube(12, jitter=0.2)   # 10368 tets = 162 full patches of 64 on 32 persistent waves
+def test_lane_residual_is_reproducible_with_and_without_grid_cap(api, oracle_lib):
+    """Schedule 4 assembles F with one lane per tet on spatial patches of 64 tets / 64 nodes (padded layout, persistent
+    waves): bitwise equal run to run and equal to the oracle within the parity bar, with the grid the device keeps resident
+    and with dfl_set_rhs_lane_grid_cap(8), which caps the persistent kernel at 8 workgroups so that every wave walks several
+    patches through the pipelined loop (prefetch of the next patch's records and lists, patches claimed from the
+    workgroup's counter)."""
+    m = kuhn_cube(12, jitter=0.2)   # 10368 tets = 162 full patches of 64 on 64 persistent waves under the cap
     S = oracle_lib.System(m)
     wg, dwg = synthetic_fields(m)
     F, _ = S.assemble_system(wg, dwg, True, False)
     L = api.lib()
-    L.dfl_tune.argtypes = [C.c_int, C.c_int]
     try:
-        for tets, nodes, bits, cap in ((64, 64, 0, 8), (64, 64, 0, 0), (64, 64, 64, 8), (64, 64, 32, 0), (32, 48, 0, 0), (16, 32, 0, 0)):
-            L.DflSetRhsWaveParameters(tets, nodes)
-            L.dfl_tune_asm(bits)
-            L.dfl_tune(2, cap)
+        for cap in (8, 0):
+            L.dfl_set_rhs_lane_grid_cap(cap)
             P = api.Problem(m, schedule=4)
             try:
                 wg_d, dwg_d = api.DeviceArray.from_numpy(wg), api.DeviceArray.from_numpy(dwg)
@@ -488,13 +420,36 @@ def test_wave_residual_is_reproducible_and_shape_independent(api, oracle_lib):
                     runs.append(F_d.numpy().copy())
                 assert np.array_equal(runs[0], runs[1])
                 ok, err = close(runs[0], F)
-                assert ok, (tets, nodes, bits, cap, err)
+                assert ok, (cap, err)
             finally:
                 P.close()
     finally:
-        L.DflSetRhsWaveParameters(64, 64)
-        L.dfl_tune_asm(0)
-        L.dfl_tune(2, 0)
+        L.dfl_set_rhs_lane_grid_cap(0)
+
+
+def test_removed_schedule_number_is_refused_and_runs_schedule_4(api, capfd):
+    """Schedules 2 and 3 no longer exist: asking for them (or for any number but 0, 1, 4) prints one line on stderr and
+    the problem assembles with schedule 4 -- F and J bitwise equal to those of a schedule-4 problem on the same mesh."""
+    m = kuhn_cube(6, jitter=0.2)
+    wg, dwg = synthetic_fields(m)
+    out = {}
+    for sched in (4, 2, 3, 5):
+        capfd.readouterr()
+        P = api.Problem(m, schedule=sched)
+        err = capfd.readouterr().err
+        try:
+            if sched != 4:
+                assert f"assembly schedule {sched} does not exist" in err, err
+            wg_d, dwg_d = api.DeviceArray.from_numpy(wg), api.DeviceArray.from_numpy(dwg)
+            F_d = api.DeviceArray(6 * P.N)
+            P.assemble_system(wg_d, dwg_d, F_d, want_J=True)
+            api.sync()
+            out[sched] = (F_d.numpy().copy(), P.block_values().numpy().copy())
+        finally:
+            P.close()
+    for sched in (2, 3, 5):
+        assert np.array_equal(out[sched][0], out[4][0]), sched
+        assert np.array_equal(out[sched][1], out[4][1]), sched
 
 
 def test_geometry_cache_follows_moved_nodes(api, oracle_lib):
