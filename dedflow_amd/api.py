@@ -381,6 +381,43 @@ class Particles:
         lib().ParticleContextFlowStats(self.ctx, C.byref(st))
         return {"inserted": int(st.inserted), "removed": int(st.removed), "blocked": int(st.blocked)}
 
+    # ---- polydisperse particles (build-defined; model in include/dedflow.h) ------------------------------------------
+    def set_sizes(self, radius, mass=None):
+        """ParticleContextSetSizes: per-particle radius [P] and mass [P] (None: the reference particle's density,
+        m = mass (r / radius)^3); radius None returns to monodisperse.  Raises ValueError on a non-positive or non-finite
+        value (the context is left unchanged)"""
+        if radius is None:
+            lib().ParticleContextSetSizes(self.ctx, None, None)
+            return
+        r = np.ascontiguousarray(radius, dtype=np.float64).reshape(-1)
+        m = None if mass is None else np.ascontiguousarray(mass, dtype=np.float64).reshape(-1)
+        if r.size != self.P or (m is not None and m.size != self.P):
+            raise ValueError(f"set_sizes: need {self.P} radii (and masses)")
+        if not (np.all(np.isfinite(r)) and np.all(r > 0) and (m is None or (np.all(np.isfinite(m)) and np.all(m > 0)))):
+            raise ValueError("set_sizes: radii and masses must be positive and finite")
+        lib().ParticleContextSetSizes(self.ctx, r.ctypes.data, None if m is None else m.ctypes.data)
+
+    def radii(self):
+        """radius of every particle [P] (None when monodisperse)"""
+        p = lib().ParticleContextRadii(self.ctx)
+        return None if not p else d2h(p, self.P, np.float64)
+
+    def masses(self):
+        """mass of every particle [P] (None when monodisperse)"""
+        p = lib().ParticleContextMasses(self.ctx)
+        return None if not p else d2h(p, self.P, np.float64)
+
+    @property
+    def max_radius(self):
+        """Rmax: the bound on every radius the grids are built for (the radius when monodisperse)"""
+        return float(lib().ParticleContextMaxRadius(self.ctx))
+
+    def set_inflow_sizes(self, r_lo, r_hi):
+        """ParticleContextSetInflowSizes: add() inserts radii in [r_lo, r_hi) (makes the context polydisperse)"""
+        if not (0.0 < float(r_lo) <= float(r_hi) and np.isfinite(r_hi)):
+            raise ValueError("set_inflow_sizes: need 0 < r_lo <= r_hi")
+        lib().ParticleContextSetInflowSizes(self.ctx, float(r_lo), float(r_hi))
+
     def arrays(self):
         """(coord, vel, acc) copied back from the device"""
         c = self.ctx.contents
@@ -521,6 +558,11 @@ def _declare(L):
     f("ParticleContextAdd", None, [C.POINTER(ParticleContext)]); f("ParticleContextRemove", None, [C.POINTER(ParticleContext)])
     f("ParticleContextFlowStats", None, [C.POINTER(ParticleContext), C.POINTER(DflParticleFlowStats)])
     f("ParticleContextTag", vp, [C.POINTER(ParticleContext)])
+    f("ParticleContextSetSizes", None, [C.POINTER(ParticleContext), vp, vp])
+    f("ParticleContextRadii", vp, [C.POINTER(ParticleContext)]); f("ParticleContextMasses", vp, [C.POINTER(ParticleContext)])
+    f("ParticleContextMaxRadius", f64, [C.POINTER(ParticleContext)])
+    f("ParticleContextSetInflowSizes", None, [C.POINTER(ParticleContext), f64, f64])
+    f("ParticleContextCopy", None, [C.POINTER(ParticleContext), C.POINTER(ParticleContext)])
     f("ParticleContextFrictionHistory", None, [C.POINTER(ParticleContext), C.POINTER(vp), C.POINTER(C.POINTER(C.c_int32))])
     f("DflMeshSetExternalLoad", None, [C.POINTER(Mesh3D), vp])
     f("SolveFlowSystem", i32, [C.POINTER(Mesh3D), vp, vp, vp, C.POINTER(Matrix), vp, vp, vp, vp, i32, i32, vp, vp])

@@ -38,13 +38,21 @@ __device__ __forceinline__ void begin(Contacts& c, const dfl_contact_history& h,
 }
 
 // one contact: unit normal n towards the particle, normal force fn (unclamped), lever ell; v and w are the particle's
-// velocity and angular velocity relative to the partner (pair: v_i - v_j and w_i + w_j; wall at rest: v and w)
+// velocity and angular velocity relative to the partner (pair: v_i - v_j and w_i + w_j; wall at rest: v and w).
+// LEVER (a pair of unequal radii): w is the lever velocity ell_a w_a x n + ell_b w_b x n itself, already evaluated in the
+// pair's id order (lever_velocity), and ell is particle i's own lever, used for the torque only
+template <bool LEVER = false>
 __device__ __forceinline__ void contact(Contacts& c, const dfl_friction_law& L, uint64_t key, const double* n, double fn,
                                         double ell, const double* v, const double* w) {
     // contact-point velocity v - ell w x n and its tangential part
-    const double vr0 = v[0] - ell * (w[1] * n[2] - w[2] * n[1]);
-    const double vr1 = v[1] - ell * (w[2] * n[0] - w[0] * n[2]);
-    const double vr2 = v[2] - ell * (w[0] * n[1] - w[1] * n[0]);
+    double vr0, vr1, vr2;
+    if (LEVER) {
+        vr0 = v[0] - w[0]; vr1 = v[1] - w[1]; vr2 = v[2] - w[2];
+    } else {
+        vr0 = v[0] - ell * (w[1] * n[2] - w[2] * n[1]);
+        vr1 = v[1] - ell * (w[2] * n[0] - w[0] * n[2]);
+        vr2 = v[2] - ell * (w[0] * n[1] - w[1] * n[0]);
+    }
     const double vrn = vr0 * n[0] + vr1 * n[1] + vr2 * n[2];
     const double vt0 = vr0 - vrn * n[0], vt1 = vr1 - vrn * n[1], vt2 = vr2 - vrn * n[2];
     double x0 = 0.0, x1 = 0.0, x2 = 0.0;
@@ -97,6 +105,15 @@ __device__ __forceinline__ void contact(Contacts& c, const dfl_friction_law& L, 
     c.tau[0] += a1 * F2 - a2 * F1;
     c.tau[1] += a2 * F0 - a0 * F2;
     c.tau[2] += a0 * F1 - a1 * F0;
+}
+
+// lever velocity of a pair of unequal radii: ell_a (w_a x n) + ell_b (w_b x n), a the smaller particle id.  Both particles
+// of the pair evaluate the same expression with n (and so every term) negated: the results are exact negations
+__device__ __forceinline__ void lever_velocity(double ell_a, const double* wa, double ell_b, const double* wb, const double* n,
+                                               double* lw) {
+    lw[0] = ell_a * (wa[1] * n[2] - wa[2] * n[1]) + ell_b * (wb[1] * n[2] - wb[2] * n[1]);
+    lw[1] = ell_a * (wa[2] * n[0] - wa[0] * n[2]) + ell_b * (wb[2] * n[0] - wb[0] * n[2]);
+    lw[2] = ell_a * (wa[0] * n[1] - wa[1] * n[0]) + ell_b * (wb[0] * n[1] - wb[1] * n[0]);
 }
 
 // acc, alpha and the live count of particle i; one atomic per particle that overflowed

@@ -156,12 +156,14 @@ __global__ __launch_bounds__(BLK) void couple_locate_kernel(I P, const I* __rest
 
 // fluid sub-step of one particle: u_f = sum_a lambda_a u(node_a); Schiller-Naumann drag integrated implicitly in v
 // (f lagged), gravity reduced by buoyancy; outside the fluid (tet < 0) gravity only.  acc <- the applied acceleration,
-// imp += the drag impulse of the step (for the reaction load)
+// imp += the drag impulse of the step (for the reaction load).  POLY: mass and radius of particle i are m[i] and r[i]
+template <bool POLY>
 __global__ __launch_bounds__(BLK) void couple_fluid_kernel(I P, const I* __restrict__ order, const I* __restrict__ tet,
                                                           const T* __restrict__ lambda, const I* __restrict__ ien,
-                                                          const T* __restrict__ w, T mass, T radius, T rho_f, T mu_f, T g0,
+                                                          const T* __restrict__ w, T mass_, T radius_, T rho_f, T mu_f, T g0,
                                                           T g1, T g2, T dt, T* __restrict__ coord, T* __restrict__ vel,
-                                                          T* __restrict__ acc, T* __restrict__ imp) {
+                                                          T* __restrict__ acc, T* __restrict__ imp, const T* __restrict__ m,
+                                                          const T* __restrict__ r) {
     const int s = blockIdx.x * BLK + threadIdx.x;
     if (s >= P) return;
     const long long i = order ? order[s] : s;
@@ -174,6 +176,7 @@ __global__ __launch_bounds__(BLK) void couple_fluid_kernel(I P, const I* __restr
     }
     const int t = tet[i];
     if (t >= 0) {
+        const double mass = POLY ? m[i] : mass_, radius = POLY ? r[i] : radius_;
         double uf[3] = {0.0, 0.0, 0.0};
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
@@ -299,8 +302,19 @@ void dfl_couple_locate(I P, const I* order, const T* coord, const T* xg, const I
 void dfl_couple_fluid_step(I P, const I* order, const I* tet, const T* lambda, const I* ien, const T* w, T mass, T radius,
                            T rho_f, T mu_f, const T* gravity, T dt, T* coord, T* vel, T* acc, T* imp, void* stream) {
     if (P <= 0) return;
-    couple_fluid_kernel<<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, order, tet, lambda, ien, w, mass, radius, rho_f, mu_f,
-                                                               gravity[0], gravity[1], gravity[2], dt, coord, vel, acc, imp);
+    couple_fluid_kernel<false><<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, order, tet, lambda, ien, w, mass, radius, rho_f, mu_f,
+                                                                      gravity[0], gravity[1], gravity[2], dt, coord, vel, acc, imp,
+                                                                      nullptr, nullptr);
+    DFL_LAUNCH_CHECK();
+}
+
+void dfl_couple_fluid_step_sizes(I P, const I* order, const I* tet, const T* lambda, const I* ien, const T* w, const T* mass,
+                                 const T* radius, T rho_f, T mu_f, const T* gravity, T dt, T* coord, T* vel, T* acc, T* imp,
+                                 void* stream) {
+    if (P <= 0) return;
+    couple_fluid_kernel<true><<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, order, tet, lambda, ien, w, 0.0, 0.0, rho_f, mu_f,
+                                                                     gravity[0], gravity[1], gravity[2], dt, coord, vel, acc, imp,
+                                                                     mass, radius);
     DFL_LAUNCH_CHECK();
 }
 

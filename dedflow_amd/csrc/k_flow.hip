@@ -68,6 +68,7 @@ __global__ __launch_bounds__(BLK) void flow_compact_kernel(I P, const I* __restr
     if (i >= P || !keep[i]) return;
     const size_t j = (size_t)newid[i];
     for (int a = 0; a < f.n3; ++a) copy3(f.src3[a], f.dst3[a], (size_t)i, j);
+    for (int a = 0; a < f.n1; ++a) f.dst1[a][j] = f.src1[a][i];
     f.tag_dst[j] = f.tag_src[i];
     if (f.tet_src) {
         f.tet_dst[j] = f.tet_src[i];
@@ -96,13 +97,22 @@ __global__ __launch_bounds__(BLK) void flow_compact_kernel(I P, const I* __restr
     }
 }
 
+// radius of slot k in call c (polydisperse inflow): r_lo + (r_hi - r_lo) u, u = (H(c, k, 3) >> 11) 2^-53
+__device__ __forceinline__ double slot_radius(const dfl_inlet& in, int k, double r_lo, double r_hi) {
+    return r_lo + (r_hi - r_lo) * ((double)(slot_hash(in, k, 3) >> 11) * 0x1p-53);
+}
+
+// POLY: particle p has radius rad[p], the slots radii in [r_lo, r_hi]: the prefilter widths use r_p + r_hi in place of 2R
+// and slot k is blocked when dist^2 < (r_p + r_k)^2
+template <bool POLY>
 __global__ __launch_bounds__(BLK) void inflow_block_kernel(I P, const T* __restrict__ coord, dfl_inlet in, T radius,
-                                                          I* __restrict__ blocked) {
+                                                          I* __restrict__ blocked, const T* __restrict__ rad, T r_lo, T r_hi) {
     const int p = blockIdx.x * BLK + threadIdx.x;
     if (p >= P) return;
     const double y[3] = {coord[3 * (size_t)p], coord[3 * (size_t)p + 1], coord[3 * (size_t)p + 2]};
     const double rel[3] = {y[0] - in.o[0], y[1] - in.o[1], y[2] - in.o[2]};
-    const double two_r = 2.0 * radius;
+    const double ry = POLY ? rad[p] : 0.0;
+    const double two_r = POLY ? ry + r_hi : 2.0 * radius;
     const double dn = (rel[0] * in.nrm[0] + rel[1] * in.nrm[1]) + rel[2] * in.nrm[2];
     if (!(fabs(dn) < two_r + in.plane_tol)) return;  // (a NaN centre blocks nothing)
     // conservative slot ranges along u and v (one extra slot per side against rounding); the exact test decides
@@ -121,7 +131,12 @@ __global__ __launch_bounds__(BLK) void inflow_block_kernel(I P, const T* __restr
             double c[3];
             slot_centre(in, k, c);
             const double d0 = y[0] - c[0], d1 = y[1] - c[1], d2 = y[2] - c[2];
-            if ((d0 * d0 + d1 * d1) + d2 * d2 < lim) atomicOr(&blocked[k], 1);
+            double l = lim;
+            if (POLY) {
+                const double rr = ry + slot_radius(in, k, r_lo, r_hi);
+                l = rr * rr;
+            }
+            if ((d0 * d0 + d1 * d1) + d2 * d2 < l) atomicOr(&blocked[k], 1);
         }
 }
 
@@ -133,12 +148,15 @@ __global__ __launch_bounds__(BLK) void inflow_key_kernel(dfl_inlet in, I nslot, 
     slot[k] = k;
 }
 
+// POLY: also radius[i] = r_k and mass[i] = m0 ((q q) q), q = r_k / r0
+template <bool POLY>
 __global__ __launch_bounds__(BLK) void inflow_append_kernel(I P, I want, dfl_inlet in, const uint64_t* __restrict__ key,
                                                            const I* __restrict__ slot, int64_t first_tag, T* __restrict__ coord,
                                                            T* __restrict__ vel, T* __restrict__ acc, int64_t* __restrict__ tag,
                                                            T* __restrict__ omega, T* __restrict__ alpha, I* __restrict__ hist_count,
                                                            I* __restrict__ tet, T* __restrict__ lambda, T* __restrict__ imp,
-                                                           I* __restrict__ count) {
+                                                           I* __restrict__ count, T* __restrict__ radius, T* __restrict__ mass,
+                                                           T r_lo, T r_hi, T r0, T m0) {
     const int k = blockIdx.x * BLK + threadIdx.x;
     if (k >= want) return;
     // the free slots sort first: the inserted ones are the prefix [0, n) of the first `want`
@@ -159,6 +177,11 @@ __global__ __launch_bounds__(BLK) void inflow_append_kernel(I P, I want, dfl_inl
         if (imp) imp[3 * i + d] = 0.0;
     }
     tag[i] = first_tag + k;
+    if (POLY) {
+        const double r = slot_radius(in, slot[k], r_lo, r_hi), q = r / r0;
+        radius[i] = r;
+        mass[i] = m0 * ((q * q) * q);
+    }
     if (hist_count) hist_count[i] = 0;
     if (tet) {
         tet[i] = -1;
@@ -187,7 +210,16 @@ void dfl_inflow_block(I P, const T* coord, dfl_inlet in, T radius, I* blocked, v
     if (nslot <= 0) return;
     DFL_GUARD(hipMemsetAsync(blocked, 0, (size_t)nslot * sizeof(I), S(stream)));
     if (P <= 0) return;
-    inflow_block_kernel<<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, coord, in, radius, blocked);
+    inflow_block_kernel<false><<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, coord, in, radius, blocked, nullptr, 0.0, 0.0);
+    DFL_LAUNCH_CHECK();
+}
+
+void dfl_inflow_block_sizes(I P, const T* coord, dfl_inlet in, const T* radius, T r_lo, T r_hi, I* blocked, void* stream) {
+    const long long nslot = (long long)in.nu * in.nv;
+    if (nslot <= 0) return;
+    DFL_GUARD(hipMemsetAsync(blocked, 0, (size_t)nslot * sizeof(I), S(stream)));
+    if (P <= 0) return;
+    inflow_block_kernel<true><<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, coord, in, 0.0, blocked, radius, r_lo, r_hi);
     DFL_LAUNCH_CHECK();
 }
 
@@ -217,9 +249,24 @@ void dfl_inflow_append(I P, I want, dfl_inlet in, const uint64_t* key_sorted, co
         DFL_GUARD(hipMemsetAsync(count, 0, sizeof(I), S(stream)));
         return;
     }
-    inflow_append_kernel<<<ceil_div(want, BLK), BLK, 0, S(stream)>>>(P, want, in, key_sorted, slot_sorted, first_tag, coord,
-                                                                    vel, acc, tag, omega, alpha, hist_count, tet, lambda, imp,
-                                                                    count);
+    inflow_append_kernel<false><<<ceil_div(want, BLK), BLK, 0, S(stream)>>>(P, want, in, key_sorted, slot_sorted, first_tag, coord,
+                                                                           vel, acc, tag, omega, alpha, hist_count, tet, lambda,
+                                                                           imp, count, nullptr, nullptr, 0.0, 0.0, 1.0, 1.0);
+    DFL_LAUNCH_CHECK();
+}
+
+void dfl_inflow_append_sizes(I P, I want, dfl_inlet in, const uint64_t* key_sorted, const I* slot_sorted, int64_t first_tag,
+                             T* coord, T* vel, T* acc, int64_t* tag, T* omega, T* alpha, I* hist_count, I* tet, T* lambda, T* imp,
+                             T* radius, T* mass, T r_lo, T r_hi, T r0, T m0, I* count, void* stream) {
+    const I nslot = in.nu * in.nv;
+    if (want > nslot) want = nslot;
+    if (want <= 0) {
+        DFL_GUARD(hipMemsetAsync(count, 0, sizeof(I), S(stream)));
+        return;
+    }
+    inflow_append_kernel<true><<<ceil_div(want, BLK), BLK, 0, S(stream)>>>(P, want, in, key_sorted, slot_sorted, first_tag, coord,
+                                                                          vel, acc, tag, omega, alpha, hist_count, tet, lambda,
+                                                                          imp, count, radius, mass, r_lo, r_hi, r0, m0);
     DFL_LAUNCH_CHECK();
 }
 

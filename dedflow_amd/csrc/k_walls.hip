@@ -198,11 +198,13 @@ __device__ int wall_contacts(const double* p, const double* v, double R, double 
     return dropped;
 }
 
+// POLY: radius sz.sorted_r[s] and mass sz.mass[i] per particle, search range r_i + sz.rmax (k_dem.hip, dem_force_kernel)
+template <bool POLY>
 __global__ __launch_bounds__(BLK) void wall_force_kernel(I P, const T* __restrict__ sorted, T R, T mass, T kn, T gn, dfl_grid3 g,
                                                         const I* __restrict__ order, const I* __restrict__ cell_start,
                                                         const dfl_wall_tri* __restrict__ tri, dfl_grid3 wg,
                                                         const I* __restrict__ wstart, const I* __restrict__ wlist, T tol,
-                                                        I* __restrict__ dropped, T* __restrict__ acc) {
+                                                        I* __restrict__ dropped, T* __restrict__ acc, dfl_sizes sz) {
     const int s = blockIdx.x * BLK + threadIdx.x;
     if (s >= P) return;
     const long long i = order[s];
@@ -213,7 +215,8 @@ __global__ __launch_bounds__(BLK) void wall_force_kernel(I P, const T* __restric
     }
     const T* me = sorted + (long long)s * 6;
     const double p[3] = {me[0], me[1], me[2]}, v[3] = {me[3], me[4], me[5]};
-    const double rng = 2.0 * R;
+    const double ri = POLY ? sz.sorted_r[s] : R;
+    const double rng = POLY ? ri + sz.rmax : 2.0 * R;
     const int x0 = grid_coord(p[0] - rng, g.lo[0], g.inv[0], g.n[0]), x1 = grid_coord(p[0] + rng, g.lo[0], g.inv[0], g.n[0]);
     const int y0 = grid_coord(p[1] - rng, g.lo[1], g.inv[1], g.n[1]), y1 = grid_coord(p[1] + rng, g.lo[1], g.inv[1], g.n[1]);
     const int z0 = grid_coord(p[2] - rng, g.lo[2], g.inv[2], g.n[2]), z1 = grid_coord(p[2] + rng, g.lo[2], g.inv[2], g.n[2]);
@@ -227,11 +230,12 @@ __global__ __launch_bounds__(BLK) void wall_force_kernel(I P, const T* __restric
                 const T* o = sorted + (long long)t * 6;
                 const double rx = p[0] - o[0], ry = p[1] - o[1], rz = p[2] - o[2];
                 const double d2 = rx * rx + ry * ry + rz * rz;
-                if (d2 >= d2max || d2 == 0.0) continue;
+                const double rs = POLY ? ri + sz.sorted_r[t] : 0.0;
+                if (d2 >= (POLY ? rs * rs : d2max) || d2 == 0.0) continue;
                 const double dist = sqrt(d2), inv = 1.0 / dist;
                 const double nx = rx * inv, ny = ry * inv, nz = rz * inv;
                 const double vn = (v[0] - o[3]) * nx + (v[1] - o[4]) * ny + (v[2] - o[5]) * nz;
-                const double fm = kn * (2.0 * R - dist) - gn * vn;
+                const double fm = kn * ((POLY ? rs : 2.0 * R) - dist) - gn * vn;
                 f[0] += fm * nx; f[1] += fm * ny; f[2] += fm * nz;
             }
         }
@@ -240,10 +244,11 @@ __global__ __launch_bounds__(BLK) void wall_force_kernel(I P, const T* __restric
                    wg.n[0] * (grid_coord(p[1], wg.lo[1], wg.inv[1], wg.n[1]) + wg.n[1] * grid_coord(p[2], wg.lo[2], wg.inv[2], wg.n[2]));
     const int wlo = wstart[wc], whi = wstart[wc + 1];
     if (wlo < whi) {
-        const int nd = wall_contacts(p, v, R, kn, gn, tol, tri, wlist, wlo, whi, f);
+        const int nd = wall_contacts(p, v, ri, kn, gn, tol, tri, wlist, wlo, whi, f);
         if (nd) atomicAdd(dropped, nd);
     }
-    const double im = 1.0 / mass;
+    double im = 1.0 / mass;
+    if (POLY) im = 1.0 / sz.mass[i];
     acc[3 * i] = f[0] * im;
     acc[3 * i + 1] = f[1] * im;
     acc[3 * i + 2] = f[2] * im;
@@ -312,7 +317,8 @@ __device__ void wall_contacts_friction(const double* p, const double* v, const d
 }
 
 // wall_force_kernel with the tangential law: pairs (same order), then the wall contacts; writes acc, alpha and the new
-// history row (a particle outside the padded box: zero acc and alpha, an empty row)
+// history row (a particle outside the padded box: zero acc and alpha, an empty row).  POLY as in k_dem.hip
+template <bool POLY>
 __global__ __launch_bounds__(BLK) void wall_force_friction_kernel(I P, const T* __restrict__ sorted, const T* __restrict__ sorted_w,
                                                                  T R, T mass, T kn, T gn, dfl_friction_law law, dfl_grid3 g,
                                                                  const I* __restrict__ order, const I* __restrict__ cell_start,
@@ -320,7 +326,7 @@ __global__ __launch_bounds__(BLK) void wall_force_friction_kernel(I P, const T* 
                                                                  const I* __restrict__ plane_id, dfl_grid3 wg,
                                                                  const I* __restrict__ wstart, const I* __restrict__ wlist, T tol,
                                                                  I* __restrict__ dropped, dfl_contact_history hist,
-                                                                 T* __restrict__ acc, T* __restrict__ alpha) {
+                                                                 T* __restrict__ acc, T* __restrict__ alpha, dfl_sizes sz) {
     const int s = blockIdx.x * BLK + threadIdx.x;
     if (s >= P) return;
     const long long i = order[s];
@@ -328,13 +334,19 @@ __global__ __launch_bounds__(BLK) void wall_force_friction_kernel(I P, const T* 
     dfl_friction::begin(c, hist, i);
     const int ncell3 = g.n[0] * g.n[1] * g.n[2];
     if (s >= cell_start[ncell3]) {
-        dfl_friction::finish(c, hist, i, mass, law.inertia, acc, alpha);
+        if (POLY) {
+            const double mi = sz.mass[i], ri = sz.sorted_r[s];
+            dfl_friction::finish(c, hist, i, mi, 0.4 * mi * ri * ri, acc, alpha);
+        } else {
+            dfl_friction::finish(c, hist, i, mass, law.inertia, acc, alpha);
+        }
         return;
     }
     const T* me = sorted + (long long)s * 6;
     const double p[3] = {me[0], me[1], me[2]}, v[3] = {me[3], me[4], me[5]};
     const double w[3] = {sorted_w[3 * (long long)s], sorted_w[3 * (long long)s + 1], sorted_w[3 * (long long)s + 2]};
-    const double rng = 2.0 * R;
+    const double ri = POLY ? sz.sorted_r[s] : R;
+    const double rng = POLY ? ri + sz.rmax : 2.0 * R;
     const int x0 = grid_coord(p[0] - rng, g.lo[0], g.inv[0], g.n[0]), x1 = grid_coord(p[0] + rng, g.lo[0], g.inv[0], g.n[0]);
     const int y0 = grid_coord(p[1] - rng, g.lo[1], g.inv[1], g.n[1]), y1 = grid_coord(p[1] + rng, g.lo[1], g.inv[1], g.n[1]);
     const int z0 = grid_coord(p[2] - rng, g.lo[2], g.inv[2], g.n[2]), z1 = grid_coord(p[2] + rng, g.lo[2], g.inv[2], g.n[2]);
@@ -347,13 +359,27 @@ __global__ __launch_bounds__(BLK) void wall_force_friction_kernel(I P, const T* 
                 const T* o = sorted + (long long)t * 6;
                 const double rx = p[0] - o[0], ry = p[1] - o[1], rz = p[2] - o[2];
                 const double d2 = rx * rx + ry * ry + rz * rz;
-                if (d2 >= d2max || d2 == 0.0) continue;
+                const double rj = POLY ? sz.sorted_r[t] : 0.0;
+                const double rs = POLY ? ri + rj : 0.0;
+                if (d2 >= (POLY ? rs * rs : d2max) || d2 == 0.0) continue;
                 const double dist = sqrt(d2), inv = 1.0 / dist;
                 const double n[3] = {rx * inv, ry * inv, rz * inv};
                 const double dv[3] = {v[0] - o[3], v[1] - o[4], v[2] - o[5]};
                 const double vn = dv[0] * n[0] + dv[1] * n[1] + dv[2] * n[2];
-                const double fn = kn * (2.0 * R - dist) - gn * vn;
+                const double fn = kn * ((POLY ? rs : 2.0 * R) - dist) - gn * vn;
                 const T* ow = sorted_w + (long long)t * 3;
+                if (POLY && ri != rj) {
+                    const long long j = order[t];
+                    const double ell_i = 0.5 * (dist + (ri - rj)), ell_j = 0.5 * (dist + (rj - ri));
+                    // operands picked first, then ONE evaluation: both particles run the same instructions on them
+                    const bool a_is_i = i < j;
+                    const double wa[3] = {a_is_i ? w[0] : ow[0], a_is_i ? w[1] : ow[1], a_is_i ? w[2] : ow[2]};
+                    const double wb[3] = {a_is_i ? ow[0] : w[0], a_is_i ? ow[1] : w[1], a_is_i ? ow[2] : w[2]};
+                    double lw[3];
+                    dfl_friction::lever_velocity(a_is_i ? ell_i : ell_j, wa, a_is_i ? ell_j : ell_i, wb, n, lw);
+                    dfl_friction::contact<true>(c, law, dfl_friction::KEY_PARTNER | (uint64_t)j, n, fn, ell_i, dv, lw);
+                    continue;
+                }
                 const double ws[3] = {w[0] + ow[0], w[1] + ow[1], w[2] + ow[2]};
                 dfl_friction::contact(c, law, dfl_friction::KEY_PARTNER | (uint64_t)order[t], n, fn, 0.5 * dist, dv, ws);
             }
@@ -364,10 +390,15 @@ __global__ __launch_bounds__(BLK) void wall_force_friction_kernel(I P, const T* 
     const int wlo = wstart[wc], whi = wstart[wc + 1];
     if (wlo < whi) {
         int nd = 0;
-        wall_contacts_friction(p, v, w, R, kn, gn, law, tol, tri, plane_id, wlist, wlo, whi, c, nd);
+        wall_contacts_friction(p, v, w, ri, kn, gn, law, tol, tri, plane_id, wlist, wlo, whi, c, nd);
         if (nd) atomicAdd(dropped, nd);
     }
-    dfl_friction::finish(c, hist, i, mass, law.inertia, acc, alpha);
+    if (POLY) {
+        const double mi = sz.mass[i];
+        dfl_friction::finish(c, hist, i, mi, 0.4 * mi * ri * ri, acc, alpha);
+    } else {
+        dfl_friction::finish(c, hist, i, mass, law.inertia, acc, alpha);
+    }
 }
 
 }  // namespace
@@ -387,8 +418,9 @@ void dfl_walls_forces(I P, const T* sorted, T radius, T mass, T kn, T gamma_n, d
                       const dfl_wall_tri* tri, dfl_grid3 wall_grid, const I* wall_start, const I* wall_list, T tol, I* dropped,
                       T* acc, void* stream) {
     if (P <= 0) return;
-    wall_force_kernel<<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, sorted, radius, mass, kn, gamma_n, grid, order, cell_start, tri,
-                                                             wall_grid, wall_start, wall_list, tol, dropped, acc);
+    wall_force_kernel<false><<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, sorted, radius, mass, kn, gamma_n, grid, order, cell_start,
+                                                                    tri, wall_grid, wall_start, wall_list, tol, dropped, acc,
+                                                                    dfl_sizes{});
     DFL_LAUNCH_CHECK();
 }
 
@@ -407,9 +439,41 @@ void dfl_walls_forces_friction(I P, const T* sorted, const T* sorted_w, T radius
                                dfl_grid3 wall_grid, const I* wall_start, const I* wall_list, T tol, I* dropped,
                                dfl_contact_history hist, T* acc, T* alpha, void* stream) {
     if (P <= 0) return;
-    wall_force_friction_kernel<<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, sorted, sorted_w, radius, mass, kn, gamma_n, law, grid,
-                                                                      order, cell_start, tri, plane, wall_grid, wall_start,
-                                                                      wall_list, tol, dropped, hist, acc, alpha);
+    wall_force_friction_kernel<false><<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, sorted, sorted_w, radius, mass, kn, gamma_n, law,
+                                                                             grid, order, cell_start, tri, plane, wall_grid,
+                                                                             wall_start, wall_list, tol, dropped, hist, acc, alpha,
+                                                                             dfl_sizes{});
+    DFL_LAUNCH_CHECK();
+}
+
+void dfl_walls_build_cells_sizes(I P, const T* coord, const T* vel, const T* omega, const T* radius, dfl_grid3 grid, I* cell_of,
+                                 I* rank, I* count, I* chunk_sum, I* cell_start, I* slot, I* order, T* sorted, T* sorted_w,
+                                 T* sorted_r, void* stream) {
+    if (P <= 0) return;
+    wall_bin_kernel<<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, coord, grid, cell_of, rank, count);
+    DFL_LAUNCH_CHECK();
+    const I nbin = grid.n[0] * grid.n[1] * grid.n[2] + 1;
+    dfl_dem_sort_binned_sizes(P, nbin, coord, vel, omega, radius, cell_of, rank, count, chunk_sum, cell_start, slot, order, sorted,
+                              sorted_w, sorted_r, stream);
+}
+
+void dfl_walls_forces_sizes(I P, const T* sorted, dfl_sizes sz, T kn, T gamma_n, dfl_grid3 grid, const I* order, const I* cell_start,
+                            const dfl_wall_tri* tri, dfl_grid3 wall_grid, const I* wall_start, const I* wall_list, T tol,
+                            I* dropped, T* acc, void* stream) {
+    if (P <= 0) return;
+    wall_force_kernel<true><<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, sorted, 0.0, 0.0, kn, gamma_n, grid, order, cell_start, tri,
+                                                                   wall_grid, wall_start, wall_list, tol, dropped, acc, sz);
+    DFL_LAUNCH_CHECK();
+}
+
+void dfl_walls_forces_friction_sizes(I P, const T* sorted, const T* sorted_w, dfl_sizes sz, T kn, T gamma_n, dfl_friction_law law,
+                                     dfl_grid3 grid, const I* order, const I* cell_start, const dfl_wall_tri* tri, const I* plane,
+                                     dfl_grid3 wall_grid, const I* wall_start, const I* wall_list, T tol, I* dropped,
+                                     dfl_contact_history hist, T* acc, T* alpha, void* stream) {
+    if (P <= 0) return;
+    wall_force_friction_kernel<true><<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, sorted, sorted_w, 0.0, 0.0, kn, gamma_n, law, grid,
+                                                                            order, cell_start, tri, plane, wall_grid, wall_start,
+                                                                            wall_list, tol, dropped, hist, acc, alpha, sz);
     DFL_LAUNCH_CHECK();
 }
 

@@ -33,6 +33,8 @@ def lib():
         L.Mesh3DCreateH5.argtypes = [vp, C.c_char_p]
         L.DflSolutionWriteH5.argtypes = [C.c_char_p, C.c_int32, vp, vp]
         L.DflSolutionReadH5.argtypes = [C.c_char_p, C.c_int32, vp, vp]
+        L.ParticleContextSave.argtypes = [C.POINTER(api.ParticleContext), vp, C.c_char_p]
+        L.ParticleContextLoad.argtypes = [C.POINTER(api.ParticleContext), vp, C.c_char_p]
         _LIB = L
     return _LIB
 
@@ -56,3 +58,21 @@ def read_dataset(path, name, dtype):
         (L.H5ReadDatasetf64 if np.dtype(dtype) == np.float64 else L.H5ReadDatasetInd)(f, name.encode(), out.ctypes.data)
     L.H5CloseFile(f)
     return out
+
+
+def save_particles(path, particles, group="particles"):
+    """ParticleContextSave of an api.Particles into a new file: <group>/{coord,vel,acc} and, when polydisperse,
+    <group>/{radius,mass}"""
+    L = lib()
+    api.lib().ParticleContextUpdateHost(particles.ctx)
+    f = L.H5OpenFile(path.encode(), b"w")
+    L.ParticleContextSave(particles.ctx, f, group.encode())
+    L.H5CloseFile(f)
+
+
+def load_particles(path, particles, group="particles"):
+    """ParticleContextLoad into an api.Particles of the same particle count (radius and mass when the file has both)"""
+    L = lib()
+    f = L.H5OpenFile(path.encode(), b"r")
+    L.ParticleContextLoad(particles.ctx, f, group.encode())
+    L.H5CloseFile(f)

@@ -8,6 +8,7 @@
  *   <grp>/bound/{node_offset[nb+1], node, elem_offset[nb+1], ien(3/face), f2e, forn}.
  * Solution files sol.<k>.h5 (src/main.c:521-532, 571-590): u[3N], p, phi, T, du[3N], dphi, dT. */
 #include <hdf5.h>
+#include <stdlib.h>
 #include <string.h>
 #include "dedflow.h"
 
@@ -171,6 +172,23 @@ void ParticleContextLoad(ParticleContext* ctx, H5FileInfo* f, const char* group)
         ArrayLoad(ctx->h_arr[k], f, path);
         ArrayCopy(ctx->d_arr[k], ctx->h_arr[k], H2D);
     }
+    /* polydisperse sizes: both datasets, or neither (the context stays as it is) */
+    char pr[256], pm[256];
+    snprintf(pr, sizeof pr, "%s/radius", group);
+    snprintf(pm, sizeof pm, "%s/mass", group);
+    if (!H5DatasetExist(f, pr) || !H5DatasetExist(f, pm)) return;
+    const index_type P = ctx->num_particle;
+    index_type lr = 0, lm = 0;
+    H5GetDatasetSize(f, pr, &lr);
+    H5GetDatasetSize(f, pm, &lm);
+    ASSERT(lr == P && lm == P && "ParticleContextLoad: radius / mass length mismatch");
+    f64* h = (f64*)malloc((size_t)(P > 0 ? 2 * P : 1) * sizeof(f64));
+    if (P > 0) {
+        H5ReadDatasetf64(f, pr, h);
+        H5ReadDatasetf64(f, pm, h + P);
+    }
+    ParticleContextSetSizes(ctx, h, h + P);
+    free(h);
 }
 void ParticleContextSave(const ParticleContext* ctx, H5FileInfo* f, const char* group) {
     char path[256];
@@ -180,6 +198,21 @@ void ParticleContextSave(const ParticleContext* ctx, H5FileInfo* f, const char* 
         snprintf(path, sizeof path, "%s/%s", group, part[k]);
         ArraySave(ctx->h_arr[k], f, path);
     }
+    const f64* r = ParticleContextRadii(ctx);
+    if (!r) return;
+    const index_type P = ctx->num_particle;
+    f64* h = (f64*)malloc((size_t)(P > 0 ? 2 * P : 1) * sizeof(f64));
+    hipStream_t s = DflStream();
+    HIPGUARD(hipStreamSynchronize(s));
+    if (P > 0) {
+        HIPGUARD(hipMemcpy(h, r, (size_t)P * sizeof(f64), hipMemcpyDeviceToHost));
+        HIPGUARD(hipMemcpy(h + P, ParticleContextMasses(ctx), (size_t)P * sizeof(f64), hipMemcpyDeviceToHost));
+    }
+    snprintf(path, sizeof path, "%s/radius", group);
+    H5WriteDatasetf64(f, path, P, h);
+    snprintf(path, sizeof path, "%s/mass", group);
+    H5WriteDatasetf64(f, path, P, h + P);
+    free(h);
 }
 
 Mesh3D* Mesh3DCreateH5(H5FileInfo* f, const char* group) {

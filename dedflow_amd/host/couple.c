@@ -218,10 +218,15 @@ void ParticleContextFluidStep(ParticleContext* ctx, const f64* w) {
     int slot = DflProfileBegin(DFL_TAG_SMALL + 3);
     /* particle-id order: the kernel's contiguous per-particle reads and writes outweigh the gather locality of the cell
        order (1M tets, 100k particles: 14.2 us in id order, 23.4 us in cell order; tools/probe_coupling.py) */
-    dfl_couple_fluid_step(ctx->num_particle, NULL, c->tet, c->lambda, Mesh3DDevice(c->mesh)->ien, w,
-                          ParticleMass(ctx), ParticleRadius(ctx), c->cfg.rho_f, c->cfg.mu_f, c->cfg.gravity, x->dt,
-                          ArrayData(ParticleCTXDeviceCoord(ctx)), ArrayData(ParticleCTXDeviceVel(ctx)),
-                          ArrayData(ParticleCTXDeviceAcc(ctx)), c->imp, DflStream());
+    if (x->radius)
+        dfl_couple_fluid_step_sizes(ctx->num_particle, NULL, c->tet, c->lambda, Mesh3DDevice(c->mesh)->ien, w, x->mass, x->radius,
+                                    c->cfg.rho_f, c->cfg.mu_f, c->cfg.gravity, x->dt, ArrayData(ParticleCTXDeviceCoord(ctx)),
+                                    ArrayData(ParticleCTXDeviceVel(ctx)), ArrayData(ParticleCTXDeviceAcc(ctx)), c->imp, DflStream());
+    else
+        dfl_couple_fluid_step(ctx->num_particle, NULL, c->tet, c->lambda, Mesh3DDevice(c->mesh)->ien, w,
+                              ParticleMass(ctx), ParticleRadius(ctx), c->cfg.rho_f, c->cfg.mu_f, c->cfg.gravity, x->dt,
+                              ArrayData(ParticleCTXDeviceCoord(ctx)), ArrayData(ParticleCTXDeviceVel(ctx)),
+                              ArrayData(ParticleCTXDeviceAcc(ctx)), c->imp, DflStream());
     DflProfileEnd(slot);
     if (x->omega) dfl_dem_spin(ctx->num_particle, x->dt, x->omega, x->alpha, DflStream()); /* the fluid exerts no torque */
     c->imp_time += x->dt;

@@ -26,6 +26,7 @@ typedef struct FlowState {
     index_type cap;                  /* capacity the buffers below (and the spares) are sized for */
     int64_t *tag, *tag_spare;        /* device [cap] */
     f64* spare3[6];                  /* device [cap][3]: coord, vel, acc, omega, alpha, imp */
+    f64* spare1[2];                  /* device [cap]: radius, mass (polydisperse) */
     index_type* tet_spare;           /* device [cap] */
     f64* lambda_spare;               /* device [cap][4] */
     index_type *keep, *newid, *rtet; /* device [cap], [cap + 1], [cap] */
@@ -50,6 +51,10 @@ static void free_spares(FlowState* f) {
     for (int k = 0; k < 6; ++k) {
         CdamFreeDevice(f->spare3[k], 0);
         f->spare3[k] = NULL;
+    }
+    for (int k = 0; k < 2; ++k) {
+        CdamFreeDevice(f->spare1[k], 0);
+        f->spare1[k] = NULL;
     }
     CdamFreeDevice(f->tag_spare, 0); CdamFreeDevice(f->tet_spare, 0); CdamFreeDevice(f->lambda_spare, 0);
     f->tag_spare = NULL;
@@ -121,6 +126,9 @@ static void ensure_spares(ParticleContext* ctx) {
     const int need3 = 3 + (x->omega ? 2 : 0) + (x->couple ? 1 : 0); /* coord, vel, acc, [w, alpha], [imp] */
     for (int k = 0; k < need3; ++k)
         if (!f->spare3[k]) f->spare3[k] = (f64*)CdamMallocDevice(n * 3 * SIZE_OF(f64));
+    if (x->radius)
+        for (int k = 0; k < 2; ++k)
+            if (!f->spare1[k]) f->spare1[k] = (f64*)CdamMallocDevice(n * SIZE_OF(f64));
     if (x->couple && !f->tet_spare) {
         f->tet_spare = (index_type*)CdamMallocDevice(n * SIZE_OF(index_type));
         f->lambda_spare = (f64*)CdamMallocDevice(n * 4 * SIZE_OF(f64));
@@ -154,6 +162,11 @@ static void grow(ParticleContext* ctx, index_type need) {
             REGROW(x->hist[k], (size_t)P * DFL_DEM_MAX_HISTORY, (size_t)cap * DFL_DEM_MAX_HISTORY);
             REGROW(x->hist_count[k], P, cap);
         }
+    }
+    if (x->radius) {
+        REGROW(x->radius, P, cap);
+        REGROW(x->mass, P, cap);
+        REGROW(x->sorted_r, 0, cap);
     }
     CoupleState* c = x->couple;
     if (c) {
@@ -269,7 +282,9 @@ void ParticleContextSetInflow(ParticleContext* ctx, const DflParticleInflow* cfg
     f->in_on = TRUE;
     f->call = 0;
     f->credit = 0.0;
-    build_inlet(f, ParticleRadius(ctx));
+    f64 r_lo, r_hi;
+    DflInflowRadii(ctx, &r_lo, &r_hi);
+    build_inlet(f, x->radius ? r_hi : ParticleRadius(ctx));
 }
 
 void ParticleContextRemove(ParticleContext* ctx) {
@@ -310,6 +325,11 @@ void ParticleContextRemove(ParticleContext* ctx) {
         ++n3;
     }
     fl.n3 = n3;
+    if (x->radius) {
+        fl.src1[0] = x->radius; fl.dst1[0] = f->spare1[0];
+        fl.src1[1] = x->mass; fl.dst1[1] = f->spare1[1];
+        fl.n1 = 2;
+    }
     fl.tag_src = f->tag;
     fl.tag_dst = f->tag_spare;
     if (c) {
@@ -347,6 +367,10 @@ void ParticleContextRemove(ParticleContext* ctx) {
         c->lambda = f->lambda_spare;
         f->lambda_spare = tl;
     }
+    if (x->radius) {
+        f64* t = x->radius; x->radius = f->spare1[0]; f->spare1[0] = t;
+        t = x->mass; x->mass = f->spare1[1]; f->spare1[1] = t;
+    }
     if (x->omega) x->hist_cur = 1 - cur;
     f->stats.removed += P - Pn;
     set_count(ctx, Pn);
@@ -357,7 +381,10 @@ void ParticleContextAdd(ParticleContext* ctx) {
     ParticleExt* x = (ParticleExt*)ctx->ext;
     FlowState* f = x->flow;
     if (!f || !f->in_on) return;
-    const f64 R = ParticleRadius(ctx);
+    f64 r_lo, r_hi; /* polydisperse: the lattice is built for r_hi */
+    DflInflowRadii(ctx, &r_lo, &r_hi);
+    const f64 R = x->radius ? r_hi : ParticleRadius(ctx);
+    if (x->radius && r_hi > x->rmax) x->rmax = r_hi; /* inserted at ParticleRadius without SetInflowSizes */
     if (R != f->inlet_R) build_inlet(f, R);
     f->inlet.call = f->call++;
     f->credit += f->in.per_call;
@@ -377,12 +404,22 @@ void ParticleContextAdd(ParticleContext* ctx) {
     hipStream_t s = DflStream();
     grow(ctx, P + n_try);
     CoupleState* c = x->couple;
-    dfl_inflow_block(P, ArrayData(ParticleCTXDeviceCoord(ctx)), f->inlet, R, f->blocked, s);
-    dfl_inflow_select(f->inlet, f->blocked, f->key, f->key_out, f->slot, f->slot_out, f->sort_tmp, f->sort_bytes, s);
-    dfl_inflow_append(P, n_try, f->inlet, f->key_out, f->slot_out, f->next_tag, ArrayData(ParticleCTXDeviceCoord(ctx)),
-                      ArrayData(ParticleCTXDeviceVel(ctx)), ArrayData(ParticleCTXDeviceAcc(ctx)), f->tag, x->omega, x->alpha,
-                      x->omega ? x->hist_count[x->hist_cur] : NULL, c ? c->tet : NULL, c ? c->lambda : NULL, c ? c->imp : NULL,
-                      f->count, s);
+    if (x->radius) {
+        dfl_inflow_block_sizes(P, ArrayData(ParticleCTXDeviceCoord(ctx)), f->inlet, x->radius, r_lo, r_hi, f->blocked, s);
+        dfl_inflow_select(f->inlet, f->blocked, f->key, f->key_out, f->slot, f->slot_out, f->sort_tmp, f->sort_bytes, s);
+        dfl_inflow_append_sizes(P, n_try, f->inlet, f->key_out, f->slot_out, f->next_tag, ArrayData(ParticleCTXDeviceCoord(ctx)),
+                                ArrayData(ParticleCTXDeviceVel(ctx)), ArrayData(ParticleCTXDeviceAcc(ctx)), f->tag, x->omega,
+                                x->alpha, x->omega ? x->hist_count[x->hist_cur] : NULL, c ? c->tet : NULL, c ? c->lambda : NULL,
+                                c ? c->imp : NULL, x->radius, x->mass, r_lo, r_hi, ParticleRadius(ctx), ParticleMass(ctx), f->count,
+                                s);
+    } else {
+        dfl_inflow_block(P, ArrayData(ParticleCTXDeviceCoord(ctx)), f->inlet, R, f->blocked, s);
+        dfl_inflow_select(f->inlet, f->blocked, f->key, f->key_out, f->slot, f->slot_out, f->sort_tmp, f->sort_bytes, s);
+        dfl_inflow_append(P, n_try, f->inlet, f->key_out, f->slot_out, f->next_tag, ArrayData(ParticleCTXDeviceCoord(ctx)),
+                          ArrayData(ParticleCTXDeviceVel(ctx)), ArrayData(ParticleCTXDeviceAcc(ctx)), f->tag, x->omega, x->alpha,
+                          x->omega ? x->hist_count[x->hist_cur] : NULL, c ? c->tet : NULL, c ? c->lambda : NULL, c ? c->imp : NULL,
+                          f->count, s);
+    }
     const index_type n = read_count(f->count);
     f->next_tag += n;
     f->stats.inserted += n;

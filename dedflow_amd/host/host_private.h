@@ -107,7 +107,17 @@ typedef struct ParticleExt {
     index_type cap;                             /* capacity of every per-particle buffer (>= num_particle; host/flow.c) */
     b32 order_valid;                            /* `order` is the last sweep's, for the current particles */
     struct FlowState* flow;                     /* particle inflow / outflow (host/flow.c), NULL when never set */
+    /* polydisperse particles (ParticleContextSetSizes); monodisperse when radius == NULL */
+    f64 *radius, *mass;                         /* device [cap], by particle id */
+    f64* sorted_r;                              /* device [cap] radii in the sweep's cell order */
+    f64 rmax;                                   /* upper bound on every radius (host only, never lowered by Remove) */
+    b32 in_sizes;                               /* ParticleContextSetInflowSizes was called: inserted radii in [in_r_lo, in_r_hi) */
+    f64 in_r_lo, in_r_hi;
 } ParticleExt;
+/* the per-particle sizes of the kernels (valid while x->radius != NULL) */
+dfl_sizes DflSizes(const ParticleExt* x);
+/* the radius range of the particles the next ParticleContextAdd inserts: (r_lo, r_hi) of SetInflowSizes, else (R, R) */
+void DflInflowRadii(const ParticleContext* ctx, f64* r_lo, f64* r_hi);
 /* the history of the next sweep (flips the ping-pong: call once per sweep) */
 dfl_contact_history DflFrictionHistory(ParticleExt* x);
 dfl_friction_law DflFrictionLaw(const ParticleContext* ctx);

@@ -6,6 +6,8 @@
  * runs in host/walls.c instead.  With friction on (ParticleContextSetFriction) both sweeps run their friction kernels,
  * which read the previous sweep's contact history and write the next one into the other of two buffers. */
 #include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include "dedflow.h"
 #include "dedflow_kernels.h"
@@ -47,6 +49,7 @@ void ParticleContextDestroy(ParticleContext* ctx) {
         DflWallsFree(x->walls);
         ParticleContextSetFriction(ctx, NULL);
         DflFlowFree(x->flow);
+        ParticleContextSetSizes(ctx, NULL, NULL);
         CdamFreeHost(x, SIZE_OF(ParticleExt));
     }
     CdamFreeHost(ctx, SIZE_OF(ParticleContext));
@@ -58,6 +61,23 @@ void ParticleContextCopy(ParticleContext* dst, const ParticleContext* src) {
         ArrayCopy(dst->h_arr[k], src->h_arr[k], H2H);
         ArrayCopy(dst->d_arr[k], src->d_arr[k], D2D);
     }
+    /* the sizes travel with the particles (the inflow radius range is configuration and stays) */
+    const ParticleExt* xs = (const ParticleExt*)src->ext;
+    ParticleExt* xd = (ParticleExt*)dst->ext;
+    if (!xs->radius) {
+        if (xd->radius) ParticleContextSetSizes(dst, NULL, NULL);
+        return;
+    }
+    const index_type P = src->num_particle;
+    f64* h = (f64*)malloc((size_t)(P > 0 ? 2 * P : 1) * sizeof(f64));
+    HIPGUARD(hipStreamSynchronize(DflStream()));
+    if (P > 0) {
+        HIPGUARD(hipMemcpy(h, xs->radius, (size_t)P * sizeof(f64), D2H));
+        HIPGUARD(hipMemcpy(h + P, xs->mass, (size_t)P * sizeof(f64), D2H));
+    }
+    ParticleContextSetSizes(dst, h, h + P);
+    if (xd->radius && xs->rmax > xd->rmax) xd->rmax = xs->rmax;
+    free(h);
 }
 void ParticleContextUpdateHost(ParticleContext* ctx) {
     for (int k = 0; k < 3; ++k) ArrayCopy(ctx->h_arr[k], ctx->d_arr[k], D2H);
@@ -100,7 +120,7 @@ void ParticleContextComputeForces(ParticleContext* ctx) {
         return;
     }
     const index_type P = ctx->num_particle;
-    const f64 R = ParticleRadius(ctx);
+    const f64 R = x->radius ? x->rmax : ParticleRadius(ctx); /* polydisperse: the grid is built for Rmax */
     hipStream_t s = DflStream();
     DflRangePush("ParticleContextComputeForces");
     /* cell edge >= 4R: the interaction range of a particle covers at most two cells per axis; and not (much) finer than a few
@@ -119,6 +139,20 @@ void ParticleContextComputeForces(ParticleContext* ctx) {
     const f64* coord = ArrayData(ParticleCTXDeviceCoord(ctx));
     const f64* vel = ArrayData(ParticleCTXDeviceVel(ctx));
     f64* acc = ArrayData(ParticleCTXDeviceAcc(ctx));
+    if (x->radius) {
+        dfl_dem_build_cells_sizes(P, coord, vel, x->omega, x->radius, cell, ncell, x->cell_of, x->rank, x->count, x->chunk_sum,
+                                  x->cell_start, x->slot, x->order, x->sorted, x->sorted_w, x->sorted_r, s);
+        x->order_valid = TRUE;
+        int slot = DflProfileBegin(DFL_TAG_SMALL + 1);
+        if (x->omega)
+            dfl_dem_forces_friction_sizes(P, x->sorted, x->sorted_w, DflSizes(x), x->kn, x->gamma_n, DflFrictionLaw(ctx), cell, ncell,
+                                          x->order, x->cell_start, DflFrictionHistory(x), acc, x->alpha, s);
+        else
+            dfl_dem_forces_sizes(P, x->sorted, DflSizes(x), x->kn, x->gamma_n, cell, ncell, x->order, x->cell_start, acc, s);
+        DflProfileEnd(slot);
+        DflRangePop();
+        return;
+    }
     if (x->omega) {
         dfl_dem_build_cells_spin(P, coord, vel, x->omega, cell, ncell, x->cell_of, x->rank, x->count, x->chunk_sum, x->cell_start,
                                  x->slot, x->order, x->sorted, x->sorted_w, s);
@@ -246,4 +280,106 @@ index_type ParticleContextFrictionOverflowCount(const ParticleContext* ctx) {
 void ParticleContextSetGravity(ParticleContext* ctx, const f64 g[3]) {
     ParticleExt* x = (ParticleExt*)ctx->ext;
     for (int d = 0; d < 3; ++d) x->gravity[d] = g ? g[d] : 0.0;
+}
+
+/* ---- polydisperse particles (model in include/dedflow.h) ---- */
+
+dfl_sizes DflSizes(const ParticleExt* x) {
+    dfl_sizes sz;
+    sz.radius = x->radius;
+    sz.mass = x->mass;
+    sz.sorted_r = x->sorted_r;
+    sz.rmax = x->rmax;
+    return sz;
+}
+
+void DflInflowRadii(const ParticleContext* ctx, f64* r_lo, f64* r_hi) {
+    const ParticleExt* x = (const ParticleExt*)ctx->ext;
+    *r_lo = x->in_sizes ? x->in_r_lo : ParticleRadius(ctx);
+    *r_hi = x->in_sizes ? x->in_r_hi : ParticleRadius(ctx);
+}
+
+static void free_sizes(ParticleExt* x) {
+    if (!x->radius) return;
+    HIPGUARD(hipStreamSynchronize(DflStream()));
+    CdamFreeDevice(x->radius, 0); CdamFreeDevice(x->mass, 0); CdamFreeDevice(x->sorted_r, 0);
+    x->radius = x->mass = x->sorted_r = NULL;
+    x->in_sizes = FALSE;
+    x->rmax = 0.0;
+}
+
+void ParticleContextSetSizes(ParticleContext* ctx, const f64* radius, const f64* mass) {
+    ParticleExt* x = (ParticleExt*)ctx->ext;
+    if (!radius) {
+        free_sizes(x);
+        return;
+    }
+    const index_type P = ctx->num_particle;
+    const f64 R = ParticleRadius(ctx), M = ParticleMass(ctx);
+    f64 rmax = 0.0;
+    for (index_type i = 0; i < P; ++i) {
+        if (!(radius[i] > 0.0 && isfinite(radius[i])) || (mass && !(mass[i] > 0.0 && isfinite(mass[i])))) {
+            fprintf(stderr, "ParticleContextSetSizes: particle %d has radius %g, mass %g; the sizes stay as they were\n", (int)i,
+                    radius[i], mass ? mass[i] : 0.0);
+            return;
+        }
+        if (radius[i] > rmax) rmax = radius[i];
+    }
+    if (!mass && !(R > 0.0 && M > 0.0)) {
+        fprintf(stderr, "ParticleContextSetSizes: no masses and no positive reference particle; the sizes stay as they were\n");
+        return;
+    }
+    const ptrdiff_t n = x->cap > 0 ? x->cap : 1;
+    f64* m = (f64*)malloc((size_t)(P > 0 ? P : 1) * sizeof(f64));
+    for (index_type i = 0; i < P; ++i) {
+        if (mass) {
+            m[i] = mass[i];
+        } else {
+            const f64 q = radius[i] / R; /* the reference particle's density; q = 1 gives M exactly */
+            m[i] = M * ((q * q) * q);
+        }
+    }
+    if (!x->radius) {
+        x->radius = (f64*)CdamMallocDevice(n * SIZE_OF(f64));
+        x->mass = (f64*)CdamMallocDevice(n * SIZE_OF(f64));
+        x->sorted_r = (f64*)CdamMallocDevice(n * SIZE_OF(f64));
+    }
+    HIPGUARD(hipStreamSynchronize(DflStream()));
+    if (P > 0) {
+        HIPGUARD(hipMemcpy(x->radius, radius, (size_t)P * sizeof(f64), H2D));
+        HIPGUARD(hipMemcpy(x->mass, m, (size_t)P * sizeof(f64), H2D));
+    }
+    free(m);
+    if (x->in_sizes && x->in_r_hi > rmax) rmax = x->in_r_hi;
+    if (P == 0 && rmax == 0.0) rmax = R;
+    x->rmax = rmax;
+}
+
+void ParticleContextSetInflowSizes(ParticleContext* ctx, f64 r_lo, f64 r_hi) {
+    ParticleExt* x = (ParticleExt*)ctx->ext;
+    if (!(r_lo > 0.0 && r_lo <= r_hi && isfinite(r_hi))) {
+        fprintf(stderr, "ParticleContextSetInflowSizes: need 0 < r_lo <= r_hi, got %g, %g; unchanged\n", r_lo, r_hi);
+        return;
+    }
+    if (!x->radius) { /* a monodisperse context becomes polydisperse: every particle keeps R and M */
+        const index_type P = ctx->num_particle;
+        f64* r = (f64*)calloc((size_t)(P > 0 ? P : 1), sizeof(f64));
+        for (index_type i = 0; i < P; ++i) r[i] = ParticleRadius(ctx);
+        ParticleContextSetSizes(ctx, r, NULL);
+        free(r);
+        if (!x->radius) return;
+        if (P == 0) x->rmax = ParticleRadius(ctx);
+    }
+    x->in_sizes = TRUE;
+    x->in_r_lo = r_lo;
+    x->in_r_hi = r_hi;
+    if (r_hi > x->rmax) x->rmax = r_hi;
+}
+
+const f64* ParticleContextRadii(const ParticleContext* ctx) { return ((const ParticleExt*)ctx->ext)->radius; }
+const f64* ParticleContextMasses(const ParticleContext* ctx) { return ((const ParticleExt*)ctx->ext)->mass; }
+
+f64 ParticleContextMaxRadius(const ParticleContext* ctx) {
+    const ParticleExt* x = (const ParticleExt*)ctx->ext;
+    return x->radius ? x->rmax : ParticleRadius(ctx);
 }

@@ -3,7 +3,7 @@
  *
  * At ParticleContextSetWallMesh, on the host: the faces of the masked groups become packed 128-byte records (vertices in
  * ascending local index of the parent tet, normal oriented towards the tet's opposite vertex, the node ids); the record
- * id is the position in group order.  At that call and again whenever ParticleRadius changes (a host-side comparison per
+ * id is the position in group order.  At that call and again whenever ParticleRadius (Rmax when polydisperse) changes (a host-side comparison per
  * sweep): the particle grid and the wall grid over the bounding box padded by R.  Also at that call, for the contact keys of
  * the friction sweep: the plane id of every record (sort by the rounded plane, then de-duplication rule 1 within runs).  The wall grid is built on the host: it
  * is a one-time O(faces) job, and walking the faces in id order fills every cell's list in ascending id without a sort.
@@ -305,7 +305,7 @@ void ParticleContextSetWallMesh(ParticleContext* ctx, Mesh3D* mesh, index_type g
     free(h_plane);
     w->dropped = (index_type*)CdamMallocDevice(SIZE_OF(index_type));
     HIPGUARD(hipMemset(w->dropped, 0, sizeof(index_type)));
-    build_grids(w, ParticleRadius(ctx), ctx->num_particle);
+    build_grids(w, ParticleContextMaxRadius(ctx), ctx->num_particle);
     x->walls = w;
 }
 
@@ -323,7 +323,7 @@ void DflWallsComputeForces(ParticleContext* ctx) {
     ParticleExt* x = (ParticleExt*)ctx->ext;
     WallState* w = x->walls;
     const index_type P = ctx->num_particle;
-    const f64 R = ParticleRadius(ctx);
+    const f64 R = ParticleContextMaxRadius(ctx); /* Rmax of a polydisperse context */
     hipStream_t s = DflStream();
     DflRangePush("ParticleContextComputeForces");
     if (R != w->R) build_grids(w, R, P);
@@ -333,6 +333,22 @@ void DflWallsComputeForces(ParticleContext* ctx) {
     const f64* coord = ArrayData(ParticleCTXDeviceCoord(ctx));
     const f64* vel = ArrayData(ParticleCTXDeviceVel(ctx));
     f64* acc = ArrayData(ParticleCTXDeviceAcc(ctx));
+    if (x->radius) {
+        dfl_walls_build_cells_sizes(P, coord, vel, x->omega, x->radius, w->pgrid, x->cell_of, x->rank, x->count, x->chunk_sum,
+                                    x->cell_start, x->slot, x->order, x->sorted, x->sorted_w, x->sorted_r, s);
+        x->order_valid = TRUE;
+        int slot = DflProfileBegin(DFL_TAG_SMALL + 1);
+        if (x->omega)
+            dfl_walls_forces_friction_sizes(P, x->sorted, x->sorted_w, DflSizes(x), x->kn, x->gamma_n, DflFrictionLaw(ctx), w->pgrid,
+                                            x->order, x->cell_start, w->tri, w->plane, w->wgrid, w->wstart, w->wlist,
+                                            1e-12 * w->scale, w->dropped, DflFrictionHistory(x), acc, x->alpha, s);
+        else
+            dfl_walls_forces_sizes(P, x->sorted, DflSizes(x), x->kn, x->gamma_n, w->pgrid, x->order, x->cell_start, w->tri, w->wgrid,
+                                   w->wstart, w->wlist, 1e-12 * w->scale, w->dropped, acc, s);
+        DflProfileEnd(slot);
+        DflRangePop();
+        return;
+    }
     if (x->omega) {
         dfl_walls_build_cells_spin(P, coord, vel, x->omega, w->pgrid, x->cell_of, x->rank, x->count, x->chunk_sum, x->cell_start,
                                    x->slot, x->order, x->sorted, x->sorted_w, s);

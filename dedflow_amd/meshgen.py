@@ -169,6 +169,44 @@ def dem_particles(P: int, radius: float, seed_x: int = 11, seed_v: int = 12):
     return np.ascontiguousarray(x.reshape(-1)), np.ascontiguousarray(v.reshape(-1)), radius
 
 
+def dem_particles_poly(P: int, r_lo: float, r_hi: float, seed: int = 14):
+    """P non-overlapping spheres in the unit box: radii uniform in [r_lo, r_hi], centres by random sequential addition
+    (uniform in [r, 1 - r]^3, a candidate that overlaps an accepted sphere is drawn again).  Returns (x (P, 3), r (P,));
+    raises ValueError when the box is too full to place them."""
+    rng = np.random.default_rng(seed)
+    r = rng.uniform(r_lo, r_hi, size=P)
+    h = 2.0 * r_hi  # grid cell: the neighbours of a candidate lie in the 27 cells around it
+    n = max(1, int(1.0 / h))
+    grid = {}
+    x = np.empty((P, 3))
+    for i in range(P):
+        for _ in range(1000):
+            c = rng.uniform(r[i], 1.0 - r[i], size=3)
+            k = np.minimum((c * n).astype(int), n - 1)
+            ok = True
+            for dz in (-1, 0, 1):
+                for dy in (-1, 0, 1):
+                    for dx in (-1, 0, 1):
+                        for j in grid.get((k[0] + dx, k[1] + dy, k[2] + dz), ()):
+                            d = c - x[j]
+                            if d @ d < (r[i] + r[j]) ** 2:
+                                ok = False
+                                break
+                        if not ok:
+                            break
+                    if not ok:
+                        break
+                if not ok:
+                    break
+            if ok:
+                x[i] = c
+                grid.setdefault((k[0], k[1], k[2]), []).append(i)
+                break
+        else:
+            raise ValueError(f"dem_particles_poly: no room for particle {i} of {P}")
+    return np.ascontiguousarray(x), r
+
+
 def dem_lattice(lo, hi, radius: float, spacing: float | None = None, kind: str = "sc", jitter: float = 0.0, seed: int = 13,
                 max_particles: int | None = None):
     """DEM centres on a simple-cubic ("sc") or face-centred cubic ("fcc") lattice filling the box [lo + R, hi - R], in

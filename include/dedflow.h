@@ -830,7 +830,7 @@ index_type ParticleContextWallDroppedCount(const ParticleContext* ctx);
  * With friction on, every contact sweep (ParticleContextComputeForces, hence ParticleContextUpdate,
  * ParticleContextFluidStep and the DEM sub-steps of DflTimeStep, coupled or not) adds the Cundall-Strack tangential law
  * to the pair, unit-box and mesh-wall contacts:
- *   spheres    monodisperse, radius R, mass m, moment of inertia I = 2/5 m R^2; angular velocity w, angular acceleration
+ *   spheres    radius R, mass m, moment of inertia I = 2/5 m R^2 (per particle: polydisperse block); angular velocity w, angular acceleration
  *              alpha = tau / I.  The normal law is unchanged: f_n = kn delta - gamma_n v_n, not clamped.
  *   contact    unit normal n towards the particle; lever ell = distance from the centre to the contact point:
  *                pair           ell = dist / 2 (the contact point is the midpoint of the centres)
@@ -953,6 +953,52 @@ void ParticleContextSetInflow(ParticleContext* ctx, const DflParticleInflow* cfg
 /* particles inserted, removed and inlet candidates that found their slot blocked since the first Set*flow call */
 void ParticleContextFlowStats(const ParticleContext* ctx, DflParticleFlowStats* out);
 const int64_t* ParticleContextTag(const ParticleContext* ctx); /* device [P]; NULL until inflow or outflow was set */
+
+/* ---- polydisperse particles (build-defined; opt-in) ---------------------------------------------------------------------
+ * A context that never calls ParticleContextSetSizes or ParticleContextSetInflowSizes is monodisperse: every kernel reads
+ * ParticleRadius / ParticleMass and runs as without this section, bit for bit.  Once sizes are set:
+ *   spheres    particle i has radius r_i > 0 and mass m_i > 0, I_i = 2/5 m_i r_i^2.  ParticleRadius and ParticleMass are
+ *              only the reference particle of the default masses and of inflow without SetInflowSizes; no kernel reads
+ *              them.  Rmax (ParticleContextMaxRadius) bounds every radius: the max of the radii passed to SetSizes and of
+ *              r_hi of SetInflowSizes (and R when inflow inserts at R); Remove never lowers it; it is host state only.
+ *   laws       the laws above with per-particle values, written so that with every radius R and every mass M the floating
+ *              point operations are exactly the monodisperse ones:
+ *                pairs   contact when d2 < (r_i + r_j)^2, delta = (r_i + r_j) - dist, f = kn delta - gamma_n v_n,
+ *                        acc_i = F_i (1 / m_i)   ((R + R) == 2R and (R + R)^2 == 4 R R exactly)
+ *                walls   r_i wherever R appears: the unit box, the face test -r_i < s < r_i, edge and vertex contacts
+ *                        |c - q| < r_i, the wall lever max(r_i - delta, 0)
+ *                friction  contact point = the middle of the overlap: levers ell_i = 0.5 (dist + (r_i - r_j)) and
+ *                        ell_j = 0.5 (dist + (r_j - r_i)); v_rel = (v_i - v_j) - (ell_i w_i + ell_j w_j) x n; torque on i
+ *                        (-ell_i n) x F_t.  The lever term is ell (w_i + w_j) x n with ell = 0.5 dist when r_i == r_j (as
+ *                        above), else ell_a (w_a x n) + ell_b (w_b x n) with a the smaller particle id: j's evaluation stays
+ *                        the exact negation of i's (xi_j == -xi_i), and sum m x x v + I w is conserved to rounding
+ *                coupling  d_i = 2 r_i, rho_p,i = m_i / (4/3 pi r_i^3), the impulse with m_i; location and the reaction
+ *                        load are unchanged
+ *   search     particle i searches the cells within r_i + Rmax; cell edge >= 4 Rmax (unit-box grid, padded mesh-wall grid
+ *              and the wall grid's R-expansion, rebuilt when Rmax changes).  Radius ratios above about 3 stay correct but
+ *              slow: many small particles share one big cell (no multi-level grid).
+ *   history    a big particle among small ones can exceed DFL_DEM_MAX_HISTORY contacts; the excess is counted by
+ *              ParticleContextFrictionOverflowCount as before.
+ *   masses     SetSizes without masses: m_i = ParticleMass ((q q) q), q = r_i / ParticleRadius (the reference particle's
+ *              density; q = 1 gives ParticleMass exactly).
+ *   inflow     SetInflowSizes(r_lo, r_hi), 0 < r_lo <= r_hi (a monodisperse context becomes polydisperse, every particle at
+ *              ParticleRadius / ParticleMass): the slot lattice and jitter of the inflow block with R replaced by r_hi;
+ *              slot k of call c gets r = r_lo + (r_hi - r_lo) u, u = (H(c, k, 3) >> 11) 2^-53 (no fused multiply-add) and
+ *              the default mass; a slot is blocked when dist^2 < (r_y + r_k)^2 against an existing particle y.  Without
+ *              SetInflowSizes a polydisperse context inserts at ParticleRadius.
+ *   outflow    compaction carries r and m; capacity growth and the spare-buffer swaps cover them.
+ *   kept       ParticleContextCopy carries the sizes (dst becomes what src is); ParticleContextSave writes <group>/radius and
+ *              <group>/mass when polydisperse; ParticleContextLoad reads them when both are present (the context becomes
+ *              polydisperse); files without them behave as before.
+ *   cost       the sort writes a sorted copy of the radii ([P], next to the 48-byte records); the force kernels read 8 more
+ *              bytes per tested neighbour and the own mass.  Nothing new allocates per sweep or reads back to the host. */
+/* radius, mass: host [P]; mass NULL = the default masses; radius NULL = monodisperse again (frees the arrays).  A non-positive
+ * or non-finite value is reported on stderr and leaves the context unchanged */
+void ParticleContextSetSizes(ParticleContext* ctx, const f64* radius, const f64* mass);
+const f64* ParticleContextRadii(const ParticleContext* ctx);  /* device [P]; NULL when monodisperse; valid until Add / Remove */
+const f64* ParticleContextMasses(const ParticleContext* ctx); /* device [P]; NULL when monodisperse; valid until Add / Remove */
+f64 ParticleContextMaxRadius(const ParticleContext* ctx);     /* Rmax; ParticleRadius when monodisperse */
+void ParticleContextSetInflowSizes(ParticleContext* ctx, f64 r_lo, f64 r_hi);
 
 #ifdef __cplusplus
 }

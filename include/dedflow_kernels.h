@@ -617,6 +617,9 @@ typedef struct dfl_flow_fields {
     const dfl_index* hcount_src;
     dfl_contact_hist* hrow_dst;
     dfl_index* hcount_dst;
+    const dfl_value* src1[2];    /* [P] per-particle scalars (radius, mass of a polydisperse context) */
+    dfl_value* dst1[2];
+    int n1;
 } dfl_flow_fields;
 /* the inlet lattice: the host constants of include/dedflow.h (base, pu, pv, ou, ov), the plane frame (o, unit uhat, vhat,
  * normal) and the prefilter widths of the blocking pass */
@@ -639,6 +642,62 @@ void dfl_inflow_append(dfl_index P, dfl_index want, dfl_inlet in, const uint64_t
                        int64_t first_tag, dfl_value* coord, dfl_value* vel, dfl_value* acc,
                        int64_t* tag, dfl_value* omega, dfl_value* alpha, dfl_index* hist_count, dfl_index* tet,
                        dfl_value* lambda, dfl_value* imp, dfl_index* count, void* stream);
+
+/* ---- polydisperse particles (build-defined, opt-in; model in include/dedflow.h, "polydisperse particles")
+ *  dfl_sizes            per-particle radius and mass (device [P], by particle id), the radii in the sweep's cell order
+ *                       (sorted_r [P], written by the sizes sort) and rmax >= every radius (the search range and the grids)
+ *    dfl_dem_sort_binned_sizes / dfl_dem_build_cells_sizes / dfl_walls_build_cells_sizes   the cell sort, also writing
+ *                       sorted_r[pos] = radius[i] and, with omega != NULL, sorted_w
+ *    dfl_dem_forces_sizes / dfl_dem_forces_friction_sizes / dfl_walls_forces_sizes / dfl_walls_forces_friction_sizes
+ *                       the POLY instantiations of the force kernels (radius and mass arguments replaced by sz)
+ *    dfl_couple_fluid_step_sizes   the coupled sub-step with d = 2 r_i, rho_p = m_i / (4/3 pi r_i^3)
+ *    dfl_inflow_block_sizes        blocked when dist^2 < (r_y + r_k)^2, r_k = r_lo + (r_hi - r_lo) u_k (include/dedflow.h)
+ *    dfl_inflow_append_sizes       dfl_inflow_append that also writes radius[i] = r_k and mass[i] = m0 ((q q) q), q = r_k / r0 */
+typedef struct dfl_sizes {
+    const dfl_value* radius;
+    const dfl_value* mass;
+    const dfl_value* sorted_r;
+    dfl_value rmax;
+} dfl_sizes;
+void dfl_dem_sort_binned_sizes(dfl_index P, dfl_index nbin, const dfl_value* coord, const dfl_value* vel, const dfl_value* omega,
+                               const dfl_value* radius, dfl_index* cell_of, dfl_index* rank, dfl_index* count,
+                               dfl_index* chunk_sum, dfl_index* cell_start, dfl_index* slot, dfl_index* order, dfl_value* sorted,
+                               dfl_value* sorted_w, dfl_value* sorted_r, void* stream);
+void dfl_dem_build_cells_sizes(dfl_index P, const dfl_value* coord, const dfl_value* vel, const dfl_value* omega,
+                               const dfl_value* radius, dfl_value cell, dfl_index ncell, dfl_index* cell_of, dfl_index* rank,
+                               dfl_index* count, dfl_index* chunk_sum, dfl_index* cell_start, dfl_index* slot, dfl_index* order,
+                               dfl_value* sorted, dfl_value* sorted_w, dfl_value* sorted_r, void* stream);
+void dfl_walls_build_cells_sizes(dfl_index P, const dfl_value* coord, const dfl_value* vel, const dfl_value* omega,
+                                 const dfl_value* radius, dfl_grid3 grid, dfl_index* cell_of, dfl_index* rank, dfl_index* count,
+                                 dfl_index* chunk_sum, dfl_index* cell_start, dfl_index* slot, dfl_index* order,
+                                 dfl_value* sorted, dfl_value* sorted_w, dfl_value* sorted_r, void* stream);
+void dfl_dem_forces_sizes(dfl_index P, const dfl_value* sorted, dfl_sizes sz, dfl_value kn, dfl_value gamma_n, dfl_value cell,
+                          dfl_index ncell, const dfl_index* order, const dfl_index* cell_start, dfl_value* acc, void* stream);
+void dfl_dem_forces_friction_sizes(dfl_index P, const dfl_value* sorted, const dfl_value* sorted_w, dfl_sizes sz, dfl_value kn,
+                                   dfl_value gamma_n, dfl_friction_law law, dfl_value cell, dfl_index ncell,
+                                   const dfl_index* order, const dfl_index* cell_start, dfl_contact_history hist,
+                                   dfl_value* acc, dfl_value* alpha, void* stream);
+void dfl_walls_forces_sizes(dfl_index P, const dfl_value* sorted, dfl_sizes sz, dfl_value kn, dfl_value gamma_n, dfl_grid3 grid,
+                            const dfl_index* order, const dfl_index* cell_start, const dfl_wall_tri* tri, dfl_grid3 wall_grid,
+                            const dfl_index* wall_start, const dfl_index* wall_list, dfl_value tol, dfl_index* dropped,
+                            dfl_value* acc, void* stream);
+void dfl_walls_forces_friction_sizes(dfl_index P, const dfl_value* sorted, const dfl_value* sorted_w, dfl_sizes sz,
+                                     dfl_value kn, dfl_value gamma_n, dfl_friction_law law, dfl_grid3 grid,
+                                     const dfl_index* order, const dfl_index* cell_start, const dfl_wall_tri* tri,
+                                     const dfl_index* plane, dfl_grid3 wall_grid, const dfl_index* wall_start,
+                                     const dfl_index* wall_list, dfl_value tol, dfl_index* dropped, dfl_contact_history hist,
+                                     dfl_value* acc, dfl_value* alpha, void* stream);
+void dfl_couple_fluid_step_sizes(dfl_index P, const dfl_index* order, const dfl_index* tet, const dfl_value* lambda,
+                                 const dfl_index* ien, const dfl_value* w, const dfl_value* mass, const dfl_value* radius,
+                                 dfl_value rho_f, dfl_value mu_f, const dfl_value* gravity, dfl_value dt, dfl_value* coord,
+                                 dfl_value* vel, dfl_value* acc, dfl_value* imp, void* stream);
+void dfl_inflow_block_sizes(dfl_index P, const dfl_value* coord, dfl_inlet in, const dfl_value* radius, dfl_value r_lo,
+                            dfl_value r_hi, dfl_index* blocked, void* stream);
+void dfl_inflow_append_sizes(dfl_index P, dfl_index want, dfl_inlet in, const uint64_t* key_sorted,
+                             const dfl_index* slot_sorted, int64_t first_tag, dfl_value* coord, dfl_value* vel, dfl_value* acc,
+                             int64_t* tag, dfl_value* omega, dfl_value* alpha, dfl_index* hist_count, dfl_index* tet,
+                             dfl_value* lambda, dfl_value* imp, dfl_value* radius, dfl_value* mass, dfl_value r_lo,
+                             dfl_value r_hi, dfl_value r0, dfl_value m0, dfl_index* count, void* stream);
 
 /* ---- scalar transport (host/scalar.c, csrc/k_scalar.hip) ------------------------------------------------------------
  * dfl_assemble_scalar_jacobian: the level-set and temperature Jacobians (d R_phi / d dphi, d R_T / d dT) over the nodal
