@@ -9,21 +9,19 @@
 //                  every wall triangle whose R-expanded bounding box overlaps it.  A particle reads the one cell that holds
 //                  its centre: fixed order => bitwise reproducible forces
 // The bin kernel is the only new launch of the cell sort (chunk / scan / place / sort are k_dem.hip's); the force kernel
-// adds the wall contacts to the particle pairs.  Threads run in the sorted (cell, id) order, so the lanes of a wave share
+// runs the shared pair loop (dem_sweep.hpp) and then the wall contacts, with the same POLY and FRICTION variants as the
+// unit box.  Threads run in the sorted (cell, id) order, so the lanes of a wave share
 // one or two wall cells: the "wall cell empty" branch is wave-uniform in the interior, and the 128-byte records (one cache
 // line each) of a shared cell are read once per wave from L1 / L2.
 #include "dfl_common.hpp"
-#include "dem_friction.hpp"
+#include "dem_sweep.hpp"
 
 namespace {
 
 constexpr int BLK = 256;
 constexpr int MAXC = DFL_WALL_MAX_CONTACTS;
 
-__device__ __forceinline__ int grid_coord(double x, double lo, double inv, int n) {
-    int c = (int)floor((x - lo) * inv);
-    return c < 0 ? 0 : (c >= n ? n - 1 : c);
-}
+using dfl_dem::grid_coord;
 
 __device__ __forceinline__ bool in_grid(double x, double lo, double inv, int n) {
     const double c = floor((x - lo) * inv);
@@ -138,10 +136,17 @@ __device__ __forceinline__ bool holds(const dfl_wall_tri* __restrict__ t, int k0
     return h0 && (t->node[0] == k1 || t->node[1] == k1 || t->node[2] == k1);
 }
 
-// wall contacts of one particle over the candidate triangles list[lo, hi) (ascending id); adds kn delta - gn v.n along n
-// into f[3]; returns the number of distinct contacts dropped by the cap
-__device__ int wall_contacts(const double* p, const double* v, double R, double kn, double gn, double tol,
-                             const dfl_wall_tri* __restrict__ tri, const I* __restrict__ list, int lo, int hi, double* f) {
+// wall contacts of particle a over the candidate triangles list[lo, hi) (ascending id), each kept contact handed to the
+// sink with its normal, overlap delta and normal force kn delta - gn v.n; returns the number of distinct contacts dropped
+// by the cap.  History keys (FRICTION only): a face by the plane id of its triangle, an edge by its sorted node pair, a
+// vertex by its node id
+template <bool FRICTION, class SinkT>
+__device__ __forceinline__ int wall_contacts(const dfl_dem::Particle& a, double kn, double gn, double tol,
+                                             const dfl_wall_tri* __restrict__ tri, const I* __restrict__ plane_id,
+                                             const I* __restrict__ list, int lo, int hi, SinkT& sink) {
+    const double* p = a.p;
+    const double* v = a.v;
+    const double R = a.r;
     double plane[MAXC][4];   // kept face contacts: normal, offset
     int key[MAXC][2];        // kept edge / vertex contacts: node ids
     int nf = 0, ne = 0, dropped = 0;
@@ -160,129 +165,13 @@ __device__ int wall_contacts(const double* p, const double* v, double R, double 
         if (nf + ne >= MAXC) { ++dropped; continue; }
         plane[nf][0] = t->n[0]; plane[nf][1] = t->n[1]; plane[nf][2] = t->n[2]; plane[nf][3] = t->off;
         ++nf;
-        const double vn = v[0] * t->n[0] + v[1] * t->n[1] + v[2] * t->n[2];
-        const double fm = kn * (R - ft.s) - gn * vn;
-        f[0] += fm * t->n[0]; f[1] += fm * t->n[1]; f[2] += fm * t->n[2];
-    }
-    // pass 2: edge and vertex contacts that are local minima of the distance to the wall and off every kept face plane
-    const double R2 = R * R;
-    for (int k = lo; k < hi; ++k) {
-        const dfl_wall_tri* t = tri + list[k];
-        const double s = plane_distance(t, p);
-        if (!(s > 0.0 && s < R)) continue;
-        const Feature ft = feature_of(t, p);
-        if (ft.kind == 0 || !(ft.d2 < R2)) continue;
-        bool skip = false;
-        for (int j = 0; j < nf; ++j)
-            skip |= fabs(ft.q[0] * plane[j][0] + ft.q[1] * plane[j][1] + ft.q[2] * plane[j][2] - plane[j][3]) <= tol;
-        for (int j = 0; j < ne; ++j) skip |= key[j][0] == ft.k0 && key[j][1] == ft.k1;
-        if (skip) continue;
-        const double dist = sqrt(ft.d2);
-        for (int m = lo; m < hi && !skip; ++m) {
-            if (m == k) continue;
-            const dfl_wall_tri* u = tri + list[m];
-            if (!holds(u, ft.k0, ft.k1)) continue;
-            const Feature fu = feature_of(u, p);
-            skip = sqrt(fu.d2) < dist - tol;
-        }
-        if (skip) continue;
-        if (nf + ne >= MAXC) { ++dropped; continue; }
-        key[ne][0] = ft.k0; key[ne][1] = ft.k1;
-        ++ne;
-        const double inv = 1.0 / dist;
-        const double nx = (p[0] - ft.q[0]) * inv, ny = (p[1] - ft.q[1]) * inv, nz = (p[2] - ft.q[2]) * inv;
-        const double vn = v[0] * nx + v[1] * ny + v[2] * nz;
-        const double fm = kn * (R - dist) - gn * vn;
-        f[0] += fm * nx; f[1] += fm * ny; f[2] += fm * nz;
-    }
-    return dropped;
-}
-
-// POLY: radius sz.sorted_r[s] and mass sz.mass[i] per particle, search range r_i + sz.rmax (k_dem.hip, dem_force_kernel)
-template <bool POLY>
-__global__ __launch_bounds__(BLK) void wall_force_kernel(I P, const T* __restrict__ sorted, T R, T mass, T kn, T gn, dfl_grid3 g,
-                                                        const I* __restrict__ order, const I* __restrict__ cell_start,
-                                                        const dfl_wall_tri* __restrict__ tri, dfl_grid3 wg,
-                                                        const I* __restrict__ wstart, const I* __restrict__ wlist, T tol,
-                                                        I* __restrict__ dropped, T* __restrict__ acc, dfl_sizes sz) {
-    const int s = blockIdx.x * BLK + threadIdx.x;
-    if (s >= P) return;
-    const long long i = order[s];
-    const int ncell3 = g.n[0] * g.n[1] * g.n[2];
-    if (s >= cell_start[ncell3]) {  // the extra bin: centre outside the padded box, no contact acceleration
-        acc[3 * i] = 0.0; acc[3 * i + 1] = 0.0; acc[3 * i + 2] = 0.0;
-        return;
-    }
-    const T* me = sorted + (long long)s * 6;
-    const double p[3] = {me[0], me[1], me[2]}, v[3] = {me[3], me[4], me[5]};
-    const double ri = POLY ? sz.sorted_r[s] : R;
-    const double rng = POLY ? ri + sz.rmax : 2.0 * R;
-    const int x0 = grid_coord(p[0] - rng, g.lo[0], g.inv[0], g.n[0]), x1 = grid_coord(p[0] + rng, g.lo[0], g.inv[0], g.n[0]);
-    const int y0 = grid_coord(p[1] - rng, g.lo[1], g.inv[1], g.n[1]), y1 = grid_coord(p[1] + rng, g.lo[1], g.inv[1], g.n[1]);
-    const int z0 = grid_coord(p[2] - rng, g.lo[2], g.inv[2], g.n[2]), z1 = grid_coord(p[2] + rng, g.lo[2], g.inv[2], g.n[2]);
-    double f[3] = {0.0, 0.0, 0.0};
-    const double d2max = 4.0 * R * R;
-    for (int z = z0; z <= z1; ++z) {
-        for (int y = y0; y <= y1; ++y) {
-            const int c0 = x0 + g.n[0] * (y + g.n[1] * z), c1 = x1 + g.n[0] * (y + g.n[1] * z);
-            for (int t = cell_start[c0]; t < cell_start[c1 + 1]; ++t) {
-                if (t == s) continue;
-                const T* o = sorted + (long long)t * 6;
-                const double rx = p[0] - o[0], ry = p[1] - o[1], rz = p[2] - o[2];
-                const double d2 = rx * rx + ry * ry + rz * rz;
-                const double rs = POLY ? ri + sz.sorted_r[t] : 0.0;
-                if (d2 >= (POLY ? rs * rs : d2max) || d2 == 0.0) continue;
-                const double dist = sqrt(d2), inv = 1.0 / dist;
-                const double nx = rx * inv, ny = ry * inv, nz = rz * inv;
-                const double vn = (v[0] - o[3]) * nx + (v[1] - o[4]) * ny + (v[2] - o[5]) * nz;
-                const double fm = kn * ((POLY ? rs : 2.0 * R) - dist) - gn * vn;
-                f[0] += fm * nx; f[1] += fm * ny; f[2] += fm * nz;
-            }
-        }
-    }
-    const int wc = grid_coord(p[0], wg.lo[0], wg.inv[0], wg.n[0]) +
-                   wg.n[0] * (grid_coord(p[1], wg.lo[1], wg.inv[1], wg.n[1]) + wg.n[1] * grid_coord(p[2], wg.lo[2], wg.inv[2], wg.n[2]));
-    const int wlo = wstart[wc], whi = wstart[wc + 1];
-    if (wlo < whi) {
-        const int nd = wall_contacts(p, v, ri, kn, gn, tol, tri, wlist, wlo, whi, f);
-        if (nd) atomicAdd(dropped, nd);
-    }
-    double im = 1.0 / mass;
-    if (POLY) im = 1.0 / sz.mass[i];
-    acc[3 * i] = f[0] * im;
-    acc[3 * i + 1] = f[1] * im;
-    acc[3 * i + 2] = f[2] * im;
-}
-
-// wall_contacts with the tangential law: the same candidates, de-duplication and cap, in the same order; a face contact is
-// keyed by the plane id of its triangle, an edge by its sorted node pair, a vertex by its node id
-__device__ void wall_contacts_friction(const double* p, const double* v, const double* w, double R, double kn, double gn,
-                                       const dfl_friction_law& law, double tol, const dfl_wall_tri* __restrict__ tri,
-                                       const I* __restrict__ plane_id, const I* __restrict__ list, int lo, int hi,
-                                       dfl_friction::Contacts& c, int& dropped) {
-    double plane[MAXC][4];
-    int key[MAXC][2];
-    int nf = 0, ne = 0;
-    for (int k = lo; k < hi; ++k) {
-        const dfl_wall_tri* t = tri + list[k];
-        const double s = plane_distance(t, p);
-        if (!(s > -R && s < R)) continue;
-        const Feature ft = feature_of(t, p);
-        if (ft.kind != 0) continue;
-        bool dup = false;
-        for (int j = 0; j < nf; ++j)
-            dup |= fabs(plane[j][0] - t->n[0]) <= 1e-12 && fabs(plane[j][1] - t->n[1]) <= 1e-12 &&
-                   fabs(plane[j][2] - t->n[2]) <= 1e-12 && fabs(plane[j][3] - t->off) <= tol;
-        if (dup) continue;
-        if (nf + ne >= MAXC) { ++dropped; continue; }
-        plane[nf][0] = t->n[0]; plane[nf][1] = t->n[1]; plane[nf][2] = t->n[2]; plane[nf][3] = t->off;
-        ++nf;
         const double n[3] = {t->n[0], t->n[1], t->n[2]};
         const double vn = v[0] * n[0] + v[1] * n[1] + v[2] * n[2];
         const double delta = R - ft.s;
-        dfl_friction::contact(c, law, dfl_friction::KEY_WALL | (uint64_t)plane_id[list[k]], n, kn * delta - gn * vn,
-                              fmax(R - delta, 0.0), v, w);
+        const uint64_t hk = FRICTION ? dfl_friction::KEY_WALL | (uint64_t)plane_id[list[k]] : 0;
+        sink.wall(a, hk, n, delta, kn * delta - gn * vn);
     }
+    // pass 2: edge and vertex contacts that are local minima of the distance to the wall and off every kept face plane
     const double R2 = R * R;
     for (int k = lo; k < hi; ++k) {
         const dfl_wall_tri* t = tri + list[k];
@@ -312,168 +201,68 @@ __device__ void wall_contacts_friction(const double* p, const double* v, const d
         const double vn = v[0] * n[0] + v[1] * n[1] + v[2] * n[2];
         const double delta = R - dist;
         const uint64_t hk = ft.k1 >= 0 ? dfl_friction::edge_key(ft.k0, ft.k1) : (dfl_friction::KEY_VERTEX | (uint64_t)ft.k0);
-        dfl_friction::contact(c, law, hk, n, kn * delta - gn * vn, fmax(R - delta, 0.0), v, w);
+        sink.wall(a, hk, n, delta, kn * delta - gn * vn);
     }
+    return dropped;
 }
 
-// wall_force_kernel with the tangential law: pairs (same order), then the wall contacts; writes acc, alpha and the new
-// history row (a particle outside the padded box: zero acc and alpha, an empty row).  POLY as in k_dem.hip
-template <bool POLY>
-__global__ __launch_bounds__(BLK) void wall_force_friction_kernel(I P, const T* __restrict__ sorted, const T* __restrict__ sorted_w,
-                                                                 T R, T mass, T kn, T gn, dfl_friction_law law, dfl_grid3 g,
-                                                                 const I* __restrict__ order, const I* __restrict__ cell_start,
-                                                                 const dfl_wall_tri* __restrict__ tri,
-                                                                 const I* __restrict__ plane_id, dfl_grid3 wg,
-                                                                 const I* __restrict__ wstart, const I* __restrict__ wlist, T tol,
-                                                                 I* __restrict__ dropped, dfl_contact_history hist,
-                                                                 T* __restrict__ acc, T* __restrict__ alpha, dfl_sizes sz) {
-    const int s = blockIdx.x * BLK + threadIdx.x;
-    if (s >= P) return;
-    const long long i = order[s];
-    dfl_friction::Contacts c;
-    dfl_friction::begin(c, hist, i);
-    const int ncell3 = g.n[0] * g.n[1] * g.n[2];
-    if (s >= cell_start[ncell3]) {
-        if (POLY) {
-            const double mi = sz.mass[i], ri = sz.sorted_r[s];
-            dfl_friction::finish(c, hist, i, mi, 0.4 * mi * ri * ri, acc, alpha);
-        } else {
-            dfl_friction::finish(c, hist, i, mass, law.inertia, acc, alpha);
-        }
+// The force kernel over a mesh: pairs (the order of the unit box), then the wall contacts of the wall-grid cell that holds
+// the centre: faces, then edges and vertices.  A particle outside the padded box (the extra bin) gets zero acc and, with
+// FRICTION, zero alpha and an empty history row.  Arguments as dem_force_kernel (k_dem.hip)
+template <bool POLY, bool FRICTION>
+__global__ __launch_bounds__(BLK) void wall_force_kernel(I P, const T* __restrict__ sorted, const T* __restrict__ sorted_w, T R,
+                                                        T mass, dfl_sizes sz, T kn, T gn, dfl_friction_law law, dfl_grid3 g,
+                                                        const I* __restrict__ order, const I* __restrict__ cell_start,
+                                                        const dfl_wall_tri* __restrict__ tri, const I* __restrict__ plane_id,
+                                                        dfl_grid3 wg, const I* __restrict__ wstart, const I* __restrict__ wlist,
+                                                        T tol, I* __restrict__ dropped, dfl_contact_history hist,
+                                                        T* __restrict__ acc, T* __restrict__ alpha) {
+    dfl_dem::Particle a;
+    a.s = blockIdx.x * BLK + threadIdx.x;
+    if (a.s >= P) return;
+    a.i = order[a.s];
+    a.r = POLY ? sz.sorted_r[a.s] : R;
+    dfl_dem::Sink<POLY, FRICTION> sink(a, law, hist, sorted_w, order);
+    if (a.s >= cell_start[g.n[0] * g.n[1] * g.n[2]]) {
+        sink.finish(a, mass, sz, acc, alpha);  // no contact: 0 / m
         return;
     }
-    const T* me = sorted + (long long)s * 6;
-    const double p[3] = {me[0], me[1], me[2]}, v[3] = {me[3], me[4], me[5]};
-    const double w[3] = {sorted_w[3 * (long long)s], sorted_w[3 * (long long)s + 1], sorted_w[3 * (long long)s + 2]};
-    const double ri = POLY ? sz.sorted_r[s] : R;
-    const double rng = POLY ? ri + sz.rmax : 2.0 * R;
-    const int x0 = grid_coord(p[0] - rng, g.lo[0], g.inv[0], g.n[0]), x1 = grid_coord(p[0] + rng, g.lo[0], g.inv[0], g.n[0]);
-    const int y0 = grid_coord(p[1] - rng, g.lo[1], g.inv[1], g.n[1]), y1 = grid_coord(p[1] + rng, g.lo[1], g.inv[1], g.n[1]);
-    const int z0 = grid_coord(p[2] - rng, g.lo[2], g.inv[2], g.n[2]), z1 = grid_coord(p[2] + rng, g.lo[2], g.inv[2], g.n[2]);
-    const double d2max = 4.0 * R * R;
-    for (int z = z0; z <= z1; ++z) {
-        for (int y = y0; y <= y1; ++y) {
-            const int c0 = x0 + g.n[0] * (y + g.n[1] * z), c1 = x1 + g.n[0] * (y + g.n[1] * z);
-            for (int t = cell_start[c0]; t < cell_start[c1 + 1]; ++t) {
-                if (t == s) continue;
-                const T* o = sorted + (long long)t * 6;
-                const double rx = p[0] - o[0], ry = p[1] - o[1], rz = p[2] - o[2];
-                const double d2 = rx * rx + ry * ry + rz * rz;
-                const double rj = POLY ? sz.sorted_r[t] : 0.0;
-                const double rs = POLY ? ri + rj : 0.0;
-                if (d2 >= (POLY ? rs * rs : d2max) || d2 == 0.0) continue;
-                const double dist = sqrt(d2), inv = 1.0 / dist;
-                const double n[3] = {rx * inv, ry * inv, rz * inv};
-                const double dv[3] = {v[0] - o[3], v[1] - o[4], v[2] - o[5]};
-                const double vn = dv[0] * n[0] + dv[1] * n[1] + dv[2] * n[2];
-                const double fn = kn * ((POLY ? rs : 2.0 * R) - dist) - gn * vn;
-                const T* ow = sorted_w + (long long)t * 3;
-                if (POLY && ri != rj) {
-                    const long long j = order[t];
-                    const double ell_i = 0.5 * (dist + (ri - rj)), ell_j = 0.5 * (dist + (rj - ri));
-                    // operands picked first, then ONE evaluation: both particles run the same instructions on them
-                    const bool a_is_i = i < j;
-                    const double wa[3] = {a_is_i ? w[0] : ow[0], a_is_i ? w[1] : ow[1], a_is_i ? w[2] : ow[2]};
-                    const double wb[3] = {a_is_i ? ow[0] : w[0], a_is_i ? ow[1] : w[1], a_is_i ? ow[2] : w[2]};
-                    double lw[3];
-                    dfl_friction::lever_velocity(a_is_i ? ell_i : ell_j, wa, a_is_i ? ell_j : ell_i, wb, n, lw);
-                    dfl_friction::contact<true>(c, law, dfl_friction::KEY_PARTNER | (uint64_t)j, n, fn, ell_i, dv, lw);
-                    continue;
-                }
-                const double ws[3] = {w[0] + ow[0], w[1] + ow[1], w[2] + ow[2]};
-                dfl_friction::contact(c, law, dfl_friction::KEY_PARTNER | (uint64_t)order[t], n, fn, 0.5 * dist, dv, ws);
-            }
-        }
-    }
-    const int wc = grid_coord(p[0], wg.lo[0], wg.inv[0], wg.n[0]) +
-                   wg.n[0] * (grid_coord(p[1], wg.lo[1], wg.inv[1], wg.n[1]) + wg.n[1] * grid_coord(p[2], wg.lo[2], wg.inv[2], wg.n[2]));
+    dfl_dem::load_state<FRICTION>(a, sorted, sorted_w);
+    dfl_dem::pair_contacts<POLY>(a, dfl_dem::MeshGrid{g}, sorted, cell_start, kn, gn, sz, sink);
+    const int wc = grid_coord(a.p[0], wg.lo[0], wg.inv[0], wg.n[0]) +
+                   wg.n[0] * (grid_coord(a.p[1], wg.lo[1], wg.inv[1], wg.n[1]) + wg.n[1] * grid_coord(a.p[2], wg.lo[2], wg.inv[2], wg.n[2]));
     const int wlo = wstart[wc], whi = wstart[wc + 1];
     if (wlo < whi) {
-        int nd = 0;
-        wall_contacts_friction(p, v, w, ri, kn, gn, law, tol, tri, plane_id, wlist, wlo, whi, c, nd);
+        const int nd = wall_contacts<FRICTION>(a, kn, gn, tol, tri, plane_id, wlist, wlo, whi, sink);
         if (nd) atomicAdd(dropped, nd);
     }
-    if (POLY) {
-        const double mi = sz.mass[i];
-        dfl_friction::finish(c, hist, i, mi, 0.4 * mi * ri * ri, acc, alpha);
-    } else {
-        dfl_friction::finish(c, hist, i, mass, law.inertia, acc, alpha);
-    }
+    sink.finish(a, mass, sz, acc, alpha);
 }
 
 }  // namespace
 
 extern "C" {
 
-void dfl_walls_build_cells(I P, const T* coord, const T* vel, dfl_grid3 grid, I* cell_of, I* rank, I* count, I* chunk_sum,
-                           I* cell_start, I* slot, I* order, T* sorted, void* stream) {
+void dfl_walls_build_cells(I P, const T* coord, const T* vel, const T* omega, const T* radius, dfl_grid3 grid, I* cell_of, I* rank,
+                           I* count, I* chunk_sum, I* cell_start, I* slot, I* order, T* sorted, T* sorted_w, T* sorted_r,
+                           void* stream) {
     if (P <= 0) return;
     wall_bin_kernel<<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, coord, grid, cell_of, rank, count);
     DFL_LAUNCH_CHECK();
     const I nbin = grid.n[0] * grid.n[1] * grid.n[2] + 1;
-    dfl_dem_sort_binned(P, nbin, coord, vel, cell_of, rank, count, chunk_sum, cell_start, slot, order, sorted, stream);
+    dfl_dem_sort_binned(P, nbin, coord, vel, omega, radius, cell_of, rank, count, chunk_sum, cell_start, slot, order, sorted,
+                        sorted_w, sorted_r, stream);
 }
 
-void dfl_walls_forces(I P, const T* sorted, T radius, T mass, T kn, T gamma_n, dfl_grid3 grid, const I* order, const I* cell_start,
-                      const dfl_wall_tri* tri, dfl_grid3 wall_grid, const I* wall_start, const I* wall_list, T tol, I* dropped,
-                      T* acc, void* stream) {
+void dfl_walls_forces(I P, const T* sorted, const T* sorted_w, T radius, T mass, dfl_sizes sz, T kn, T gamma_n, dfl_friction_law law,
+                      dfl_grid3 grid, const I* order, const I* cell_start, const dfl_wall_tri* tri, const I* plane,
+                      dfl_grid3 wall_grid, const I* wall_start, const I* wall_list, T tol, I* dropped, dfl_contact_history hist,
+                      T* acc, T* alpha, void* stream) {
     if (P <= 0) return;
-    wall_force_kernel<false><<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, sorted, radius, mass, kn, gamma_n, grid, order, cell_start,
-                                                                    tri, wall_grid, wall_start, wall_list, tol, dropped, acc,
-                                                                    dfl_sizes{});
-    DFL_LAUNCH_CHECK();
-}
-
-void dfl_walls_build_cells_spin(I P, const T* coord, const T* vel, const T* omega, dfl_grid3 grid, I* cell_of, I* rank, I* count,
-                                I* chunk_sum, I* cell_start, I* slot, I* order, T* sorted, T* sorted_w, void* stream) {
-    if (P <= 0) return;
-    wall_bin_kernel<<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, coord, grid, cell_of, rank, count);
-    DFL_LAUNCH_CHECK();
-    const I nbin = grid.n[0] * grid.n[1] * grid.n[2] + 1;
-    dfl_dem_sort_binned_spin(P, nbin, coord, vel, omega, cell_of, rank, count, chunk_sum, cell_start, slot, order, sorted, sorted_w,
-                             stream);
-}
-
-void dfl_walls_forces_friction(I P, const T* sorted, const T* sorted_w, T radius, T mass, T kn, T gamma_n, dfl_friction_law law,
-                               dfl_grid3 grid, const I* order, const I* cell_start, const dfl_wall_tri* tri, const I* plane,
-                               dfl_grid3 wall_grid, const I* wall_start, const I* wall_list, T tol, I* dropped,
-                               dfl_contact_history hist, T* acc, T* alpha, void* stream) {
-    if (P <= 0) return;
-    wall_force_friction_kernel<false><<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, sorted, sorted_w, radius, mass, kn, gamma_n, law,
-                                                                             grid, order, cell_start, tri, plane, wall_grid,
-                                                                             wall_start, wall_list, tol, dropped, hist, acc, alpha,
-                                                                             dfl_sizes{});
-    DFL_LAUNCH_CHECK();
-}
-
-void dfl_walls_build_cells_sizes(I P, const T* coord, const T* vel, const T* omega, const T* radius, dfl_grid3 grid, I* cell_of,
-                                 I* rank, I* count, I* chunk_sum, I* cell_start, I* slot, I* order, T* sorted, T* sorted_w,
-                                 T* sorted_r, void* stream) {
-    if (P <= 0) return;
-    wall_bin_kernel<<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, coord, grid, cell_of, rank, count);
-    DFL_LAUNCH_CHECK();
-    const I nbin = grid.n[0] * grid.n[1] * grid.n[2] + 1;
-    dfl_dem_sort_binned_sizes(P, nbin, coord, vel, omega, radius, cell_of, rank, count, chunk_sum, cell_start, slot, order, sorted,
-                              sorted_w, sorted_r, stream);
-}
-
-void dfl_walls_forces_sizes(I P, const T* sorted, dfl_sizes sz, T kn, T gamma_n, dfl_grid3 grid, const I* order, const I* cell_start,
-                            const dfl_wall_tri* tri, dfl_grid3 wall_grid, const I* wall_start, const I* wall_list, T tol,
-                            I* dropped, T* acc, void* stream) {
-    if (P <= 0) return;
-    wall_force_kernel<true><<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, sorted, 0.0, 0.0, kn, gamma_n, grid, order, cell_start, tri,
-                                                                   wall_grid, wall_start, wall_list, tol, dropped, acc, sz);
-    DFL_LAUNCH_CHECK();
-}
-
-void dfl_walls_forces_friction_sizes(I P, const T* sorted, const T* sorted_w, dfl_sizes sz, T kn, T gamma_n, dfl_friction_law law,
-                                     dfl_grid3 grid, const I* order, const I* cell_start, const dfl_wall_tri* tri, const I* plane,
-                                     dfl_grid3 wall_grid, const I* wall_start, const I* wall_list, T tol, I* dropped,
-                                     dfl_contact_history hist, T* acc, T* alpha, void* stream) {
-    if (P <= 0) return;
-    wall_force_friction_kernel<true><<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, sorted, sorted_w, 0.0, 0.0, kn, gamma_n, law, grid,
-                                                                            order, cell_start, tri, plane, wall_grid, wall_start,
-                                                                            wall_list, tol, dropped, hist, acc, alpha, sz);
+    const auto kernel = sz.sorted_r ? (sorted_w ? wall_force_kernel<true, true> : wall_force_kernel<true, false>)
+                                    : (sorted_w ? wall_force_kernel<false, true> : wall_force_kernel<false, false>);
+    kernel<<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, sorted, sorted_w, radius, mass, sz, kn, gamma_n, law, grid, order, cell_start,
+                                                  tri, plane, wall_grid, wall_start, wall_list, tol, dropped, hist, acc, alpha);
     DFL_LAUNCH_CHECK();
 }
 

@@ -114,11 +114,11 @@ typedef struct ParticleExt {
     b32 in_sizes;                               /* ParticleContextSetInflowSizes was called: inserted radii in [in_r_lo, in_r_hi) */
     f64 in_r_lo, in_r_hi;
 } ParticleExt;
-/* the per-particle sizes of the kernels (valid while x->radius != NULL) */
+/* the per-particle sizes of the kernels (all NULL, rmax 0 while x->radius == NULL: one size) */
 dfl_sizes DflSizes(const ParticleExt* x);
 /* the radius range of the particles the next ParticleContextAdd inserts: (r_lo, r_hi) of SetInflowSizes, else (R, R) */
 void DflInflowRadii(const ParticleContext* ctx, f64* r_lo, f64* r_hi);
-/* the history of the next sweep (flips the ping-pong: call once per sweep) */
+/* the history of the next sweep (flips the ping-pong: call once per sweep); friction off: all NULL */
 dfl_contact_history DflFrictionHistory(ParticleExt* x);
 dfl_friction_law DflFrictionLaw(const ParticleContext* ctx);
 void DflFrictionClearHistory(ParticleContext* ctx); /* no-op when friction is off */

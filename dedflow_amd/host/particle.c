@@ -139,35 +139,12 @@ void ParticleContextComputeForces(ParticleContext* ctx) {
     const f64* coord = ArrayData(ParticleCTXDeviceCoord(ctx));
     const f64* vel = ArrayData(ParticleCTXDeviceVel(ctx));
     f64* acc = ArrayData(ParticleCTXDeviceAcc(ctx));
-    if (x->radius) {
-        dfl_dem_build_cells_sizes(P, coord, vel, x->omega, x->radius, cell, ncell, x->cell_of, x->rank, x->count, x->chunk_sum,
-                                  x->cell_start, x->slot, x->order, x->sorted, x->sorted_w, x->sorted_r, s);
-        x->order_valid = TRUE;
-        int slot = DflProfileBegin(DFL_TAG_SMALL + 1);
-        if (x->omega)
-            dfl_dem_forces_friction_sizes(P, x->sorted, x->sorted_w, DflSizes(x), x->kn, x->gamma_n, DflFrictionLaw(ctx), cell, ncell,
-                                          x->order, x->cell_start, DflFrictionHistory(x), acc, x->alpha, s);
-        else
-            dfl_dem_forces_sizes(P, x->sorted, DflSizes(x), x->kn, x->gamma_n, cell, ncell, x->order, x->cell_start, acc, s);
-        DflProfileEnd(slot);
-        DflRangePop();
-        return;
-    }
-    if (x->omega) {
-        dfl_dem_build_cells_spin(P, coord, vel, x->omega, cell, ncell, x->cell_of, x->rank, x->count, x->chunk_sum, x->cell_start,
-                                 x->slot, x->order, x->sorted, x->sorted_w, s);
-        x->order_valid = TRUE;
-        int slot = DflProfileBegin(DFL_TAG_SMALL + 1);
-        dfl_dem_forces_friction(P, x->sorted, x->sorted_w, R, ParticleMass(ctx), x->kn, x->gamma_n, DflFrictionLaw(ctx), cell, ncell,
-                                x->order, x->cell_start, DflFrictionHistory(x), acc, x->alpha, s);
-        DflProfileEnd(slot);
-        DflRangePop();
-        return;
-    }
-    dfl_dem_build_cells(P, coord, vel, cell, ncell, x->cell_of, x->rank, x->count, x->chunk_sum, x->cell_start, x->slot, x->order, x->sorted, s);
+    dfl_dem_build_cells(P, coord, vel, x->omega, x->radius, cell, ncell, x->cell_of, x->rank, x->count, x->chunk_sum, x->cell_start,
+                        x->slot, x->order, x->sorted, x->sorted_w, x->sorted_r, s);
     x->order_valid = TRUE;
     int slot = DflProfileBegin(DFL_TAG_SMALL + 1);
-    dfl_dem_forces(P, x->sorted, R, ParticleMass(ctx), x->kn, x->gamma_n, cell, ncell, x->order, x->cell_start, acc, s);
+    dfl_dem_forces(P, x->sorted, x->sorted_w, R, ParticleMass(ctx), DflSizes(x), x->kn, x->gamma_n, DflFrictionLaw(ctx), cell, ncell,
+                   x->order, x->cell_start, DflFrictionHistory(x), acc, x->alpha, s);
     DflProfileEnd(slot);
     DflRangePop();
 }
@@ -247,7 +224,8 @@ dfl_friction_law DflFrictionLaw(const ParticleContext* ctx) {
 }
 
 dfl_contact_history DflFrictionHistory(ParticleExt* x) {
-    dfl_contact_history h;
+    dfl_contact_history h = {NULL, NULL, NULL, NULL, NULL};
+    if (!x->omega) return h;
     const int a = x->hist_cur, b = 1 - a;
     h.old_row = x->hist[a];
     h.old_count = x->hist_count[a];

@@ -333,40 +333,13 @@ void DflWallsComputeForces(ParticleContext* ctx) {
     const f64* coord = ArrayData(ParticleCTXDeviceCoord(ctx));
     const f64* vel = ArrayData(ParticleCTXDeviceVel(ctx));
     f64* acc = ArrayData(ParticleCTXDeviceAcc(ctx));
-    if (x->radius) {
-        dfl_walls_build_cells_sizes(P, coord, vel, x->omega, x->radius, w->pgrid, x->cell_of, x->rank, x->count, x->chunk_sum,
-                                    x->cell_start, x->slot, x->order, x->sorted, x->sorted_w, x->sorted_r, s);
-        x->order_valid = TRUE;
-        int slot = DflProfileBegin(DFL_TAG_SMALL + 1);
-        if (x->omega)
-            dfl_walls_forces_friction_sizes(P, x->sorted, x->sorted_w, DflSizes(x), x->kn, x->gamma_n, DflFrictionLaw(ctx), w->pgrid,
-                                            x->order, x->cell_start, w->tri, w->plane, w->wgrid, w->wstart, w->wlist,
-                                            1e-12 * w->scale, w->dropped, DflFrictionHistory(x), acc, x->alpha, s);
-        else
-            dfl_walls_forces_sizes(P, x->sorted, DflSizes(x), x->kn, x->gamma_n, w->pgrid, x->order, x->cell_start, w->tri, w->wgrid,
-                                   w->wstart, w->wlist, 1e-12 * w->scale, w->dropped, acc, s);
-        DflProfileEnd(slot);
-        DflRangePop();
-        return;
-    }
-    if (x->omega) {
-        dfl_walls_build_cells_spin(P, coord, vel, x->omega, w->pgrid, x->cell_of, x->rank, x->count, x->chunk_sum, x->cell_start,
-                                   x->slot, x->order, x->sorted, x->sorted_w, s);
-        x->order_valid = TRUE;
-        int slot = DflProfileBegin(DFL_TAG_SMALL + 1);
-        dfl_walls_forces_friction(P, x->sorted, x->sorted_w, R, ParticleMass(ctx), x->kn, x->gamma_n, DflFrictionLaw(ctx), w->pgrid,
-                                  x->order, x->cell_start, w->tri, w->plane, w->wgrid, w->wstart, w->wlist, 1e-12 * w->scale,
-                                  w->dropped, DflFrictionHistory(x), acc, x->alpha, s);
-        DflProfileEnd(slot);
-        DflRangePop();
-        return;
-    }
-    dfl_walls_build_cells(P, coord, vel, w->pgrid, x->cell_of, x->rank, x->count, x->chunk_sum, x->cell_start, x->slot, x->order,
-                          x->sorted, s);
+    dfl_walls_build_cells(P, coord, vel, x->omega, x->radius, w->pgrid, x->cell_of, x->rank, x->count, x->chunk_sum, x->cell_start,
+                          x->slot, x->order, x->sorted, x->sorted_w, x->sorted_r, s);
     x->order_valid = TRUE;
     int slot = DflProfileBegin(DFL_TAG_SMALL + 1);
-    dfl_walls_forces(P, x->sorted, R, ParticleMass(ctx), x->kn, x->gamma_n, w->pgrid, x->order, x->cell_start, w->tri, w->wgrid,
-                     w->wstart, w->wlist, 1e-12 * w->scale, w->dropped, acc, s);
+    dfl_walls_forces(P, x->sorted, x->sorted_w, R, ParticleMass(ctx), DflSizes(x), x->kn, x->gamma_n, DflFrictionLaw(ctx), w->pgrid,
+                     x->order, x->cell_start, w->tri, w->plane, w->wgrid, w->wstart, w->wlist, 1e-12 * w->scale, w->dropped,
+                     DflFrictionHistory(x), acc, x->alpha, s);
     DflProfileEnd(slot);
     DflRangePop();
 }

@@ -453,36 +453,20 @@ void dfl_amgx_tail_cycle(const dfl_amgx_level* levels, dfl_index l0, dfl_index n
                          dfl_value omega, const dfl_value* b0, dfl_value* x0, dfl_value* w0, void* stream);
 
 /* ---- DEM contact sweep (build-defined; the reference's Particle.c holds storage only)
- *  model: monodisperse spheres, linear spring-dashpot normal contact F = (kn*overlap - gamma_n*vn) n between
- *  particles and against the six walls of the unit box; uniform cell list with cell edge >= 2R:
- *    dfl_dem_build_cells  counting sort of the particles by cell (4 launches, no allocation, no synchronisation):
- *                         cell_start[ncell^3 + 1], order[P] = particle ids by (cell, id), sorted[P][6] = position and
- *                         velocity in that order; count[ncell^3 + 1] and chunk_sum[dfl_dem_num_chunks(ncell^3)] are
- *                         zero-initialised scratch that the call leaves zeroed again
- *    dfl_dem_forces       acc[i] = (sum_j F_ij + F_walls) / mass, neighbours from the 27 surrounding cells
+ *  model: spheres, linear spring-dashpot normal contact F = (kn*overlap - gamma_n*vn) n between particles and against
+ *  the six walls of the unit box or the boundary faces of a tet mesh; uniform cell list with cell edge >= 4R.  Opt-in:
+ *  contact friction with rotation, per-particle radius and mass (the blocks below).  The launchers of the sweep
+ *  (dfl_dem_build_cells ... dfl_walls_forces) follow the types they take: "DEM contact sweep: launchers" below.
+ *    dfl_dem_num_chunks   length of the chunk_sum scratch for a cell list of ncell3 bins
  *    dfl_dem_integrate    v += dt*a ; x += dt*v */
 dfl_index dfl_dem_num_chunks(dfl_index ncell3);
-void dfl_dem_build_cells(dfl_index P, const dfl_value* coord, const dfl_value* vel, dfl_value cell, dfl_index ncell,
-                         dfl_index* cell_of, dfl_index* rank, dfl_index* count, dfl_index* chunk_sum, dfl_index* cell_start,
-                         dfl_index* slot, dfl_index* order, dfl_value* sorted, void* stream);
 void dfl_dem_integrate(dfl_index P, dfl_value dt, dfl_value* coord, dfl_value* vel, const dfl_value* acc, void* stream);
-void dfl_dem_forces(dfl_index P, const dfl_value* sorted, dfl_value radius, dfl_value mass, dfl_value kn, dfl_value gamma_n,
-                    dfl_value cell, dfl_index ncell, const dfl_index* order, const dfl_index* cell_start, dfl_value* acc,
-                    void* stream);
-/* the last four launches of dfl_dem_build_cells, for a bin pass of the caller's over nbin bins */
-void dfl_dem_sort_binned(dfl_index P, dfl_index nbin, const dfl_value* coord, const dfl_value* vel, dfl_index* cell_of,
-                         dfl_index* rank, dfl_index* count, dfl_index* chunk_sum, dfl_index* cell_start, dfl_index* slot,
-                         dfl_index* order, dfl_value* sorted, void* stream);
 
 /* ---- DEM contacts with the boundary faces of a tet mesh (build-defined, csrc/k_walls.hip; model in include/dedflow.h)
  *  dfl_grid3            a uniform grid: cell (i, j, k) = floor((x - lo) * inv) per axis, n cells per axis, x fastest
  *  dfl_wall_tri         one wall triangle in one 128-byte cache line: vertices v[3][3], inward unit normal n, plane offset
  *                       off = n . v0, the mesh node ids of the vertices and the triangle id
- *    dfl_walls_build_cells  dfl_dem_build_cells on `grid`; a particle outside it goes to the extra bin nx*ny*nz (count and
- *                           cell_start then hold nx*ny*nz + 2 entries, chunk_sum dfl_dem_num_chunks(nx*ny*nz + 1))
- *    dfl_walls_forces       acc[i] = (sum_j F_ij + F_walls) / mass for the particles inside `grid`, 0 for the others; the
- *                           wall candidates of a particle are wall_list[wall_start[c] .. wall_start[c+1]) of the wall_grid
- *                           cell c holding its centre; *dropped += contacts over DFL_WALL_MAX_CONTACTS */
+ *  DFL_WALL_MAX_CONTACTS distinct wall contacts of one particle at most; the sweep counts the ones beyond */
 #ifndef DFL_WALL_MAX_CONTACTS
 #define DFL_WALL_MAX_CONTACTS 8
 #endif
@@ -494,13 +478,6 @@ typedef struct dfl_wall_tri {
     dfl_value v[9], n[3], off, pad;
     dfl_index node[3], id;
 } dfl_wall_tri;
-void dfl_walls_build_cells(dfl_index P, const dfl_value* coord, const dfl_value* vel, dfl_grid3 grid, dfl_index* cell_of,
-                           dfl_index* rank, dfl_index* count, dfl_index* chunk_sum, dfl_index* cell_start, dfl_index* slot,
-                           dfl_index* order, dfl_value* sorted, void* stream);
-void dfl_walls_forces(dfl_index P, const dfl_value* sorted, dfl_value radius, dfl_value mass, dfl_value kn, dfl_value gamma_n,
-                      dfl_grid3 grid, const dfl_index* order, const dfl_index* cell_start, const dfl_wall_tri* tri,
-                      dfl_grid3 wall_grid, const dfl_index* wall_start, const dfl_index* wall_list, dfl_value tol,
-                      dfl_index* dropped, dfl_value* acc, void* stream);
 
 /* ---- DEM contact friction and rotation (build-defined, opt-in; csrc/dem_friction.hpp, model in include/dedflow.h)
  *  dfl_contact_hist     one history entry (32 B): the contact key and the tangential spring xi
@@ -509,11 +486,6 @@ void dfl_walls_forces(dfl_index P, const dfl_value* sorted, dfl_value radius, df
  *  dfl_contact_history  rows of DFL_DEM_MAX_HISTORY entries per particle id: the previous sweep's rows and live counts
  *                       (read), this sweep's (written; the two alternate between sweeps), *overflow += the contacts of a
  *                       particle that found no free entry
- *    dfl_dem_build_cells_spin / dfl_walls_build_cells_spin   the cell sort, also writing sorted_w[P][3] = omega in the
- *                           sorted order
- *    dfl_dem_forces_friction / dfl_walls_forces_friction      the force kernels with the tangential law: acc and
- *                           alpha = torque / I of every particle, the new history rows; plane[F] = the plane id of every
- *                           wall triangle (include/dedflow.h, contact keys)
  *    dfl_dem_integrate_spin  v += dt (a + g) ; x += dt v ; omega += dt alpha (omega NULL: no rotation)
  *    dfl_dem_spin            omega += dt alpha */
 #ifndef DFL_DEM_MAX_HISTORY
@@ -533,28 +505,6 @@ typedef struct dfl_contact_history {
     dfl_index* new_count;
     dfl_index* overflow;
 } dfl_contact_history;
-void dfl_dem_build_cells_spin(dfl_index P, const dfl_value* coord, const dfl_value* vel, const dfl_value* omega, dfl_value cell,
-                              dfl_index ncell, dfl_index* cell_of, dfl_index* rank, dfl_index* count, dfl_index* chunk_sum,
-                              dfl_index* cell_start, dfl_index* slot, dfl_index* order, dfl_value* sorted, dfl_value* sorted_w,
-                              void* stream);
-void dfl_dem_sort_binned_spin(dfl_index P, dfl_index nbin, const dfl_value* coord, const dfl_value* vel, const dfl_value* omega,
-                              dfl_index* cell_of, dfl_index* rank, dfl_index* count, dfl_index* chunk_sum,
-                              dfl_index* cell_start, dfl_index* slot, dfl_index* order, dfl_value* sorted, dfl_value* sorted_w,
-                              void* stream);
-void dfl_walls_build_cells_spin(dfl_index P, const dfl_value* coord, const dfl_value* vel, const dfl_value* omega,
-                                dfl_grid3 grid, dfl_index* cell_of, dfl_index* rank, dfl_index* count, dfl_index* chunk_sum,
-                                dfl_index* cell_start, dfl_index* slot, dfl_index* order, dfl_value* sorted,
-                                dfl_value* sorted_w, void* stream);
-void dfl_dem_forces_friction(dfl_index P, const dfl_value* sorted, const dfl_value* sorted_w, dfl_value radius, dfl_value mass,
-                             dfl_value kn, dfl_value gamma_n, dfl_friction_law law, dfl_value cell, dfl_index ncell,
-                             const dfl_index* order, const dfl_index* cell_start, dfl_contact_history hist, dfl_value* acc,
-                             dfl_value* alpha, void* stream);
-void dfl_walls_forces_friction(dfl_index P, const dfl_value* sorted, const dfl_value* sorted_w, dfl_value radius,
-                               dfl_value mass, dfl_value kn, dfl_value gamma_n, dfl_friction_law law, dfl_grid3 grid,
-                               const dfl_index* order, const dfl_index* cell_start, const dfl_wall_tri* tri,
-                               const dfl_index* plane, dfl_grid3 wall_grid, const dfl_index* wall_start,
-                               const dfl_index* wall_list, dfl_value tol, dfl_index* dropped, dfl_contact_history hist,
-                               dfl_value* acc, dfl_value* alpha, void* stream);
 void dfl_dem_integrate_spin(dfl_index P, dfl_value dt, const dfl_value* g, dfl_value* coord, dfl_value* vel,
                             const dfl_value* acc, dfl_value* omega, const dfl_value* alpha, void* stream);
 void dfl_dem_spin(dfl_index P, dfl_value dt, dfl_value* omega, const dfl_value* alpha, void* stream);
@@ -645,11 +595,7 @@ void dfl_inflow_append(dfl_index P, dfl_index want, dfl_inlet in, const uint64_t
 
 /* ---- polydisperse particles (build-defined, opt-in; model in include/dedflow.h, "polydisperse particles")
  *  dfl_sizes            per-particle radius and mass (device [P], by particle id), the radii in the sweep's cell order
- *                       (sorted_r [P], written by the sizes sort) and rmax >= every radius (the search range and the grids)
- *    dfl_dem_sort_binned_sizes / dfl_dem_build_cells_sizes / dfl_walls_build_cells_sizes   the cell sort, also writing
- *                       sorted_r[pos] = radius[i] and, with omega != NULL, sorted_w
- *    dfl_dem_forces_sizes / dfl_dem_forces_friction_sizes / dfl_walls_forces_sizes / dfl_walls_forces_friction_sizes
- *                       the POLY instantiations of the force kernels (radius and mass arguments replaced by sz)
+ *                       (sorted_r [P], written by the cell sort) and rmax >= every radius (the search range and the grids)
  *    dfl_couple_fluid_step_sizes   the coupled sub-step with d = 2 r_i, rho_p = m_i / (4/3 pi r_i^3)
  *    dfl_inflow_block_sizes        blocked when dist^2 < (r_y + r_k)^2, r_k = r_lo + (r_hi - r_lo) u_k (include/dedflow.h)
  *    dfl_inflow_append_sizes       dfl_inflow_append that also writes radius[i] = r_k and mass[i] = m0 ((q q) q), q = r_k / r0 */
@@ -659,34 +605,6 @@ typedef struct dfl_sizes {
     const dfl_value* sorted_r;
     dfl_value rmax;
 } dfl_sizes;
-void dfl_dem_sort_binned_sizes(dfl_index P, dfl_index nbin, const dfl_value* coord, const dfl_value* vel, const dfl_value* omega,
-                               const dfl_value* radius, dfl_index* cell_of, dfl_index* rank, dfl_index* count,
-                               dfl_index* chunk_sum, dfl_index* cell_start, dfl_index* slot, dfl_index* order, dfl_value* sorted,
-                               dfl_value* sorted_w, dfl_value* sorted_r, void* stream);
-void dfl_dem_build_cells_sizes(dfl_index P, const dfl_value* coord, const dfl_value* vel, const dfl_value* omega,
-                               const dfl_value* radius, dfl_value cell, dfl_index ncell, dfl_index* cell_of, dfl_index* rank,
-                               dfl_index* count, dfl_index* chunk_sum, dfl_index* cell_start, dfl_index* slot, dfl_index* order,
-                               dfl_value* sorted, dfl_value* sorted_w, dfl_value* sorted_r, void* stream);
-void dfl_walls_build_cells_sizes(dfl_index P, const dfl_value* coord, const dfl_value* vel, const dfl_value* omega,
-                                 const dfl_value* radius, dfl_grid3 grid, dfl_index* cell_of, dfl_index* rank, dfl_index* count,
-                                 dfl_index* chunk_sum, dfl_index* cell_start, dfl_index* slot, dfl_index* order,
-                                 dfl_value* sorted, dfl_value* sorted_w, dfl_value* sorted_r, void* stream);
-void dfl_dem_forces_sizes(dfl_index P, const dfl_value* sorted, dfl_sizes sz, dfl_value kn, dfl_value gamma_n, dfl_value cell,
-                          dfl_index ncell, const dfl_index* order, const dfl_index* cell_start, dfl_value* acc, void* stream);
-void dfl_dem_forces_friction_sizes(dfl_index P, const dfl_value* sorted, const dfl_value* sorted_w, dfl_sizes sz, dfl_value kn,
-                                   dfl_value gamma_n, dfl_friction_law law, dfl_value cell, dfl_index ncell,
-                                   const dfl_index* order, const dfl_index* cell_start, dfl_contact_history hist,
-                                   dfl_value* acc, dfl_value* alpha, void* stream);
-void dfl_walls_forces_sizes(dfl_index P, const dfl_value* sorted, dfl_sizes sz, dfl_value kn, dfl_value gamma_n, dfl_grid3 grid,
-                            const dfl_index* order, const dfl_index* cell_start, const dfl_wall_tri* tri, dfl_grid3 wall_grid,
-                            const dfl_index* wall_start, const dfl_index* wall_list, dfl_value tol, dfl_index* dropped,
-                            dfl_value* acc, void* stream);
-void dfl_walls_forces_friction_sizes(dfl_index P, const dfl_value* sorted, const dfl_value* sorted_w, dfl_sizes sz,
-                                     dfl_value kn, dfl_value gamma_n, dfl_friction_law law, dfl_grid3 grid,
-                                     const dfl_index* order, const dfl_index* cell_start, const dfl_wall_tri* tri,
-                                     const dfl_index* plane, dfl_grid3 wall_grid, const dfl_index* wall_start,
-                                     const dfl_index* wall_list, dfl_value tol, dfl_index* dropped, dfl_contact_history hist,
-                                     dfl_value* acc, dfl_value* alpha, void* stream);
 void dfl_couple_fluid_step_sizes(dfl_index P, const dfl_index* order, const dfl_index* tet, const dfl_value* lambda,
                                  const dfl_index* ien, const dfl_value* w, const dfl_value* mass, const dfl_value* radius,
                                  dfl_value rho_f, dfl_value mu_f, const dfl_value* gravity, dfl_value dt, dfl_value* coord,
@@ -698,6 +616,48 @@ void dfl_inflow_append_sizes(dfl_index P, dfl_index want, dfl_inlet in, const ui
                              int64_t* tag, dfl_value* omega, dfl_value* alpha, dfl_index* hist_count, dfl_index* tet,
                              dfl_value* lambda, dfl_value* imp, dfl_value* radius, dfl_value* mass, dfl_value r_lo,
                              dfl_value r_hi, dfl_value r0, dfl_value m0, dfl_index* count, void* stream);
+
+/* ---- DEM contact sweep: launchers (csrc/k_dem.hip, csrc/k_walls.hip, csrc/dem_sweep.hpp)
+ * One sweep is a cell sort and one force kernel, on the unit box (dfl_dem_*) or on a mesh's grid (dfl_walls_*), all on
+ * `stream`, with no allocation and no synchronisation.  Optional arguments select the variant:
+ *    friction   on when omega (cell sort) / sorted_w (forces) is not NULL; off: sorted_w, law, hist and alpha are not read
+ *    sizes      per-particle when radius (cell sort) / sz.sorted_r (forces) is not NULL, and then the scalars radius and
+ *               mass are not read; one size: sz is not read (a zeroed dfl_sizes) and every particle has radius, mass
+ *    dfl_dem_build_cells    counting sort of the particles by cell (5 launches): cell_start[ncell^3 + 1], order[P] =
+ *                           particle ids by (cell, id), and the copies in that order: sorted[P][6] = position and
+ *                           velocity, sorted_w[P][3] = omega (friction), sorted_r[P] = radius (sizes).  count[ncell^3 + 1]
+ *                           and chunk_sum[dfl_dem_num_chunks(ncell^3)] are zero-initialised scratch that the call leaves
+ *                           zeroed again; cell_of, rank and slot [P] are scratch
+ *    dfl_dem_sort_binned    the last four launches of dfl_dem_build_cells, for a bin pass of the caller's over nbin bins
+ *    dfl_dem_forces         acc[i] = (sum_j F_ij + F_walls) / m_i, neighbours from the cells within the interaction range;
+ *                           with friction also alpha[i] = torque / I_i and the new history rows
+ *    dfl_walls_build_cells  dfl_dem_build_cells on `grid`; a particle outside it goes to the extra bin nx*ny*nz (count and
+ *                           cell_start then hold nx*ny*nz + 2 entries, chunk_sum dfl_dem_num_chunks(nx*ny*nz + 1))
+ *    dfl_walls_forces       dfl_dem_forces for the particles inside `grid` with the mesh's walls, 0 for the others; the
+ *                           wall candidates of a particle are wall_list[wall_start[c] .. wall_start[c+1]) of the wall_grid
+ *                           cell c holding its centre; *dropped += contacts over DFL_WALL_MAX_CONTACTS; plane[F] = the
+ *                           plane id of every wall triangle (include/dedflow.h, contact keys), read with friction only */
+void dfl_dem_sort_binned(dfl_index P, dfl_index nbin, const dfl_value* coord, const dfl_value* vel, const dfl_value* omega,
+                         const dfl_value* radius, dfl_index* cell_of, dfl_index* rank, dfl_index* count, dfl_index* chunk_sum,
+                         dfl_index* cell_start, dfl_index* slot, dfl_index* order, dfl_value* sorted, dfl_value* sorted_w,
+                         dfl_value* sorted_r, void* stream);
+void dfl_dem_build_cells(dfl_index P, const dfl_value* coord, const dfl_value* vel, const dfl_value* omega,
+                         const dfl_value* radius, dfl_value cell, dfl_index ncell, dfl_index* cell_of, dfl_index* rank,
+                         dfl_index* count, dfl_index* chunk_sum, dfl_index* cell_start, dfl_index* slot, dfl_index* order,
+                         dfl_value* sorted, dfl_value* sorted_w, dfl_value* sorted_r, void* stream);
+void dfl_dem_forces(dfl_index P, const dfl_value* sorted, const dfl_value* sorted_w, dfl_value radius, dfl_value mass,
+                    dfl_sizes sz, dfl_value kn, dfl_value gamma_n, dfl_friction_law law, dfl_value cell, dfl_index ncell,
+                    const dfl_index* order, const dfl_index* cell_start, dfl_contact_history hist, dfl_value* acc,
+                    dfl_value* alpha, void* stream);
+void dfl_walls_build_cells(dfl_index P, const dfl_value* coord, const dfl_value* vel, const dfl_value* omega,
+                           const dfl_value* radius, dfl_grid3 grid, dfl_index* cell_of, dfl_index* rank, dfl_index* count,
+                           dfl_index* chunk_sum, dfl_index* cell_start, dfl_index* slot, dfl_index* order, dfl_value* sorted,
+                           dfl_value* sorted_w, dfl_value* sorted_r, void* stream);
+void dfl_walls_forces(dfl_index P, const dfl_value* sorted, const dfl_value* sorted_w, dfl_value radius, dfl_value mass,
+                      dfl_sizes sz, dfl_value kn, dfl_value gamma_n, dfl_friction_law law, dfl_grid3 grid,
+                      const dfl_index* order, const dfl_index* cell_start, const dfl_wall_tri* tri, const dfl_index* plane,
+                      dfl_grid3 wall_grid, const dfl_index* wall_start, const dfl_index* wall_list, dfl_value tol,
+                      dfl_index* dropped, dfl_contact_history hist, dfl_value* acc, dfl_value* alpha, void* stream);
 
 /* ---- scalar transport (host/scalar.c, csrc/k_scalar.hip) ------------------------------------------------------------
  * dfl_assemble_scalar_jacobian: the level-set and temperature Jacobians (d R_phi / d dphi, d R_T / d dT) over the nodal

@@ -122,7 +122,7 @@ def test_library_exports_the_friction_entry_points():
     out = subprocess.check_output(["nm", "-D", "--defined-only", os.path.join(ROOT, "dedflow_amd", "libdedflow.so")], text=True)
     names = {line.split()[-1] for line in out.splitlines() if line.strip()}
     for name in ("ParticleContextSetFriction", "ParticleContextAngularVelocity", "ParticleContextAngularAcc",
-                 "ParticleContextFrictionOverflowCount", "ParticleContextSetGravity", "dfl_dem_build_cells_spin",
-                 "dfl_walls_build_cells_spin", "dfl_dem_forces_friction", "dfl_walls_forces_friction",
+                 "ParticleContextFrictionOverflowCount", "ParticleContextSetGravity", "dfl_dem_build_cells",
+                 "dfl_walls_build_cells", "dfl_dem_forces", "dfl_walls_forces",
                  "dfl_dem_integrate_spin", "dfl_dem_spin"):
         assert name in names, name
