@@ -533,6 +533,18 @@ def _declare(L):
     f("dfl_cgs_work_size", C.c_int64, [i32, i32]); f("dfl_reduce_work_size", i32, [])
     f("dfl_cgs_dots", None, [i32, i32, vp, C.c_int64, vp, vp, vp, vp])
     f("dfl_cgs_update", None, [i32, i32, vp, C.c_int64, vp, vp, vp, C.c_int, vp, vp])
+    f("dfl_cgs_update_givens", None, [i32, i32, vp, C.c_int64, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp])
+    f("dfl_gemv_n", None, [i32, i32, vp, C.c_int64, vp, vp, vp])
+    f("dfl_gmres_givens", None, [i32, vp, vp, i32, vp, vp, vp, vp]); f("dfl_gmres_givens_sq", None, [i32, vp, vp, i32, vp, vp, vp, vp])
+    f("dfl_gmres_givens_pythagoras", None, [i32, vp, vp, i32, vp, vp, vp, vp, vp])
+    f("dfl_cgs_update_pc_givens", None, [i32, i32, i32, vp, C.c_int64, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp])
+    f("dfl_cgs_update_pc_givens_x4", None, [i32, i32, i32, vp, C.c_int64, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp])
+    f("dfl_gmres_trsv", None, [i32, vp, i32, vp, vp])
+    f("dfl_dscal_inv_dev", None, [i32, vp, vp, vp]); f("dfl_dsqrt_dev", None, [vp, vp])
+    f("dfl_norms4", None, [i32, vp, vp, C.c_int, vp, vp])
+    f("dfl_alpha_states", None, [i32, vp, vp, vp, f64, f64, f64, f64, vp, vp, vp, vp, vp])
+    f("dfl_alpha_states2", None, [i32, vp, vp, vp, f64, f64, f64, f64, vp, vp, vp, vp, vp, vp])
+    f("dfl_alpha_predict", None, [i32, f64, vp, vp]); f("dfl_alpha_correct", None, [i32, f64, f64, vp, vp, vp, vp])
     f("dfl_ddot", None, [i32, vp, vp, vp, vp, vp]); f("dfl_dnrm2", None, [i32, vp, vp, vp, vp])
     f("dfl_daxpy", None, [i32, f64, vp, vp, vp]); f("dfl_dscal", None, [i32, f64, vp, vp])
     f("dfl_pc_jacobi_setup", None, [i32, vp, vp, vp, vp, vp, vp]); f("dfl_pc_jacobi_apply", None, [i32, i32, vp, vp, vp, vp, vp])
