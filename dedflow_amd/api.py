@@ -418,6 +418,62 @@ class Particles:
             raise ValueError("set_inflow_sizes: need 0 < r_lo <= r_hi")
         lib().ParticleContextSetInflowSizes(self.ctx, float(r_lo), float(r_hi))
 
+    # ---- particle heat transfer (build-defined; model in include/dedflow.h) -----------------------------------------
+    def set_heat(self, cp_p, k_p=0.0, cp_f=0.0, k_f=0.0, T_init=0.0, two_way=False):
+        """ParticleContextSetHeat: particle specific heat cp_p (> 0), conductivity k_p (<= 0: no contact conduction), fluid
+        cp_f / k_f (<= 0: the reference's constants), the temperature T_init of every particle now and of inserted ones;
+        cp_p None turns heat off."""
+        if cp_p is None:
+            lib().ParticleContextSetHeat(self.ctx, None)
+            return
+        if not (float(cp_p) > 0.0 and np.isfinite(cp_p) and np.isfinite(T_init)):
+            raise ValueError("set_heat: need cp_p > 0 and a finite T_init")
+        cfg = DflParticleHeat(float(cp_p), float(k_p), float(cp_f), float(k_f), float(T_init), 1 if two_way else 0)
+        lib().ParticleContextSetHeat(self.ctx, C.byref(cfg))
+
+    def _heat_ptr(self, name):
+        p = getattr(lib(), name)(self.ctx)
+        if not p:
+            raise RuntimeError("heat is off: call set_heat first")
+        return p
+
+    def temperature(self):
+        """temperature of every particle [P] copied back from the device"""
+        return d2h(self._heat_ptr("ParticleContextTemperature"), self.P, np.float64)
+
+    def set_temperature(self, T):
+        """overwrite the particle temperatures with T ([P])"""
+        p = self._heat_ptr("ParticleContextTemperature")
+        sync()
+        DeviceArray(self.P, ptr=p).upload(np.asarray(T, dtype=np.float64).reshape(-1))
+
+    def heat_rate(self):
+        """heat flowing into every particle [P] in the last heat step"""
+        return d2h(self._heat_ptr("ParticleContextHeatRate"), self.P, np.float64)
+
+    def _pending_energy(self):
+        """energy the fluid gave every particle [P] since the last heat_source (library-private accessor, for tests)"""
+        return d2h(self._heat_ptr("DflParticlePendingEnergy"), self.P, np.float64)
+
+    def _conduction_rate(self):
+        """q_i [P] of the last heat step with k_p > 0 (library-private accessor, for tests)"""
+        return d2h(self._heat_ptr("DflParticleConductionRate"), self.P, np.float64)
+
+    def heat_step(self, w=None):
+        """ParticleContextHeatStep: one thermal sub-step in the fluid state w (DeviceArray of 6N; None: conduction only)"""
+        self._heat_ptr("ParticleContextTemperature")
+        lib().ParticleContextHeatStep(self.ctx, w.ptr if w is not None else None)
+
+    def heat_source(self, out=None):
+        """ParticleContextHeatSource into `out` (DeviceArray of N, allocated when None); returns the DeviceArray"""
+        self._heat_ptr("ParticleContextTemperature")
+        if not getattr(self, "N", 0):
+            raise RuntimeError("heat_source needs a coupled context: call couple first")
+        if out is None:
+            out = DeviceArray(self.N)
+        lib().ParticleContextHeatSource(self.ctx, out.ptr)
+        return out
+
     def arrays(self):
         """(coord, vel, acc) copied back from the device"""
         c = self.ctx.contents
@@ -445,6 +501,11 @@ class DflParticleInflow(C.Structure):
 
 class DflParticleFlowStats(C.Structure):
     _fields_ = [("inserted", C.c_int64), ("removed", C.c_int64), ("blocked", C.c_int64)]
+
+
+class DflParticleHeat(C.Structure):
+    _fields_ = [("cp_p", C.c_double), ("k_p", C.c_double), ("cp_f", C.c_double), ("k_f", C.c_double), ("T_init", C.c_double),
+                ("two_way", C.c_int32)]
 
 
 class DflFluidCoupling(C.Structure):
@@ -577,6 +638,11 @@ def _declare(L):
     f("ParticleContextCopy", None, [C.POINTER(ParticleContext), C.POINTER(ParticleContext)])
     f("ParticleContextFrictionHistory", None, [C.POINTER(ParticleContext), C.POINTER(vp), C.POINTER(C.POINTER(C.c_int32))])
     f("DflMeshSetExternalLoad", None, [C.POINTER(Mesh3D), vp])
+    f("ParticleContextSetHeat", None, [C.POINTER(ParticleContext), C.POINTER(DflParticleHeat)])
+    f("ParticleContextTemperature", vp, [C.POINTER(ParticleContext)]); f("ParticleContextHeatRate", vp, [C.POINTER(ParticleContext)])
+    f("ParticleContextHeatStep", None, [C.POINTER(ParticleContext), vp]); f("ParticleContextHeatSource", None, [C.POINTER(ParticleContext), vp])
+    f("DflMeshSetHeatSource", None, [C.POINTER(Mesh3D), vp])
+    f("DflParticlePendingEnergy", vp, [C.POINTER(ParticleContext)]); f("DflParticleConductionRate", vp, [C.POINTER(ParticleContext)])
     f("SolveFlowSystem", i32, [C.POINTER(Mesh3D), vp, vp, vp, C.POINTER(Matrix), vp, vp, vp, vp, i32, i32, vp, vp])
     f("DflTimeStep", i32, [C.POINTER(Mesh3D), vp, vp, vp, C.POINTER(Matrix), vp, vp, vp, vp, i32, i32, C.POINTER(ParticleContext),
                            i32, vp, vp])
@@ -695,6 +761,12 @@ class Problem:
         """DflMeshSetExternalLoad: a DeviceArray of 3N (kept alive here while registered), or None"""
         self._ext_load = load
         lib().DflMeshSetExternalLoad(self.mesh, load.ptr if load is not None else None)
+
+    def set_heat_source(self, q):
+        """DflMeshSetHeatSource: a DeviceArray of N subtracted from the T rows of every F (kept alive here while registered),
+        or None"""
+        self._heat_source = q
+        lib().DflMeshSetHeatSource(self.mesh, q.ptr if q is not None else None)
 
     def matvec(self, x, y):
         lib().MatrixMatVec(self.J, x.ptr, y.ptr)

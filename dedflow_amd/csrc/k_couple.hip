@@ -244,15 +244,19 @@ __global__ __launch_bounds__(BLK) void couple_stable_kernel(I P, const I* __rest
     members[lo + r] = i;
 }
 
-// load[3a + d] = -scale * sum over the tets e of node a (ascending) and the particles p of e (ascending id) of
-// lambda_{p, k(a, e)} imp[p][d]
+// load[C a + d] = -scale * sum over the tets e of node a (ascending) and the particles p of e (ascending id) of
+// lambda_{p, k(a, e)} imp[p][d], d < C.  C = 3: the reaction load of the drag impulses; C = 1: the heat source of the
+// particles' pending energy (k_heat.hip)
+template <int C>
 __global__ __launch_bounds__(BLK) void couple_node_kernel(I N, const I* __restrict__ vrow, const I* __restrict__ vcol,
                                                          const I* __restrict__ ien, const I* __restrict__ tstart,
                                                          const I* __restrict__ members, const T* __restrict__ lambda,
                                                          const T* __restrict__ imp, T scale, T* __restrict__ load) {
     const int a = blockIdx.x * BLK + threadIdx.x;
     if (a >= N) return;
-    double sx = 0.0, sy = 0.0, sz = 0.0;
+    double s[C];
+#pragma unroll
+    for (int d = 0; d < C; ++d) s[d] = 0.0;
     for (int q = vrow[a]; q < vrow[a + 1]; ++q) {
         const int e = vcol[q];
         const int lo = tstart[e], hi = tstart[e + 1];
@@ -264,14 +268,12 @@ __global__ __launch_bounds__(BLK) void couple_node_kernel(I N, const I* __restri
         for (int m = lo; m < hi; ++m) {
             const long long p = members[m];
             const double l = lambda[4 * p + k];
-            sx += l * imp[3 * p];
-            sy += l * imp[3 * p + 1];
-            sz += l * imp[3 * p + 2];
+#pragma unroll
+            for (int d = 0; d < C; ++d) s[d] += l * imp[C * p + d];
         }
     }
-    load[3LL * a] = -scale * sx;
-    load[3LL * a + 1] = -scale * sy;
-    load[3LL * a + 2] = -scale * sz;
+#pragma unroll
+    for (int d = 0; d < C; ++d) load[(long long)C * a + d] = -scale * s[d];
 }
 
 }  // namespace
@@ -332,7 +334,14 @@ void dfl_couple_sort_by_tet(I P, I T_, const I* tet, I* tcount, I* rank, I* tsta
 void dfl_couple_node_load(I N, const I* vrow, const I* vcol, const I* ien, const I* tstart, const I* members, const T* lambda,
                           const T* imp, T scale, T* load, void* stream) {
     if (N <= 0) return;
-    couple_node_kernel<<<ceil_div(N, BLK), BLK, 0, S(stream)>>>(N, vrow, vcol, ien, tstart, members, lambda, imp, scale, load);
+    couple_node_kernel<3><<<ceil_div(N, BLK), BLK, 0, S(stream)>>>(N, vrow, vcol, ien, tstart, members, lambda, imp, scale, load);
+    DFL_LAUNCH_CHECK();
+}
+
+void dfl_couple_node_scalar(I N, const I* vrow, const I* vcol, const I* ien, const I* tstart, const I* members, const T* lambda,
+                            const T* e, T scale, T* out, void* stream) {
+    if (N <= 0) return;
+    couple_node_kernel<1><<<ceil_div(N, BLK), BLK, 0, S(stream)>>>(N, vrow, vcol, ien, tstart, members, lambda, e, scale, out);
     DFL_LAUNCH_CHECK();
 }
 

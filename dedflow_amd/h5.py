@@ -62,7 +62,7 @@ def read_dataset(path, name, dtype):
 
 def save_particles(path, particles, group="particles"):
     """ParticleContextSave of an api.Particles into a new file: <group>/{coord,vel,acc} and, when polydisperse,
-    <group>/{radius,mass}"""
+    <group>/{radius,mass} and, with particle heat on, <group>/temp"""
     L = lib()
     api.lib().ParticleContextUpdateHost(particles.ctx)
     f = L.H5OpenFile(path.encode(), b"w")
@@ -71,7 +71,8 @@ def save_particles(path, particles, group="particles"):
 
 
 def load_particles(path, particles, group="particles"):
-    """ParticleContextLoad into an api.Particles of the same particle count (radius and mass when the file has both)"""
+    """ParticleContextLoad into an api.Particles of the same particle count (radius and mass when the file has both; temp when
+    the file has it and heat is on)"""
     L = lib()
     f = L.H5OpenFile(path.encode(), b"r")
     L.ParticleContextLoad(particles.ctx, f, group.encode())

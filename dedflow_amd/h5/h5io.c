@@ -172,6 +172,24 @@ void ParticleContextLoad(ParticleContext* ctx, H5FileInfo* f, const char* group)
         ArrayLoad(ctx->h_arr[k], f, path);
         ArrayCopy(ctx->d_arr[k], ctx->h_arr[k], H2D);
     }
+    /* particle temperatures: read when the file has them and heat is on (the file holds no heat configuration) */
+    f64* temp = ParticleContextTemperature(ctx);
+    snprintf(path, sizeof path, "%s/temp", group);
+    if (!temp && H5DatasetExist(f, path))
+        fprintf(stderr, "ParticleContextLoad: %s is in the file but particle heat is off (ParticleContextSetHeat): not read\n", path);
+    if (temp && H5DatasetExist(f, path)) {
+        const index_type P = ctx->num_particle;
+        index_type lt = 0;
+        H5GetDatasetSize(f, path, &lt);
+        ASSERT(lt == P && "ParticleContextLoad: temp length mismatch");
+        f64* h = (f64*)malloc((size_t)(P > 0 ? P : 1) * sizeof(f64));
+        if (P > 0) {
+            H5ReadDatasetf64(f, path, h);
+            HIPGUARD(hipStreamSynchronize(DflStream()));
+            HIPGUARD(hipMemcpy(temp, h, (size_t)P * sizeof(f64), hipMemcpyHostToDevice));
+        }
+        free(h);
+    }
     /* polydisperse sizes: both datasets, or neither (the context stays as it is) */
     char pr[256], pm[256];
     snprintf(pr, sizeof pr, "%s/radius", group);
@@ -198,9 +216,18 @@ void ParticleContextSave(const ParticleContext* ctx, H5FileInfo* f, const char* 
         snprintf(path, sizeof path, "%s/%s", group, part[k]);
         ArraySave(ctx->h_arr[k], f, path);
     }
+    const index_type P = ctx->num_particle;
+    const f64* temp = ParticleContextTemperature((ParticleContext*)ctx);
+    if (temp) { /* <group>/temp when heat is on */
+        f64* ht = (f64*)malloc((size_t)(P > 0 ? P : 1) * sizeof(f64));
+        HIPGUARD(hipStreamSynchronize(DflStream()));
+        if (P > 0) HIPGUARD(hipMemcpy(ht, temp, (size_t)P * sizeof(f64), hipMemcpyDeviceToHost));
+        snprintf(path, sizeof path, "%s/temp", group);
+        H5WriteDatasetf64(f, path, P, ht);
+        free(ht);
+    }
     const f64* r = ParticleContextRadii(ctx);
     if (!r) return;
-    const index_type P = ctx->num_particle;
     f64* h = (f64*)malloc((size_t)(P > 0 ? 2 * P : 1) * sizeof(f64));
     hipStream_t s = DflStream();
     HIPGUARD(hipStreamSynchronize(s));

@@ -34,6 +34,8 @@ void DflMeshSetWeakBCGroup(Mesh3D* mesh, index_type group) { ((MeshExt*)mesh->ex
 void DflSetQuiet(b32 quiet) { g_quiet = quiet; }
 void DflMeshSetExternalLoad(Mesh3D* mesh, const f64* load) { ((MeshExt*)mesh->ext)->ext_load = load; }
 const f64* DflMeshExternalLoad(const Mesh3D* mesh) { return ((const MeshExt*)mesh->ext)->ext_load; }
+void DflMeshSetHeatSource(Mesh3D* mesh, const f64* q) { ((MeshExt*)mesh->ext)->heat_source = q; }
+const f64* DflMeshHeatSource(const Mesh3D* mesh) { return ((const MeshExt*)mesh->ext)->heat_source; }
 /* node coordinates were modified (moving mesh): drop the per-element geometry cache, rebuilt at the next assembly */
 void DflMeshGeometryChanged(Mesh3D* mesh) {
     MeshExt* x = (MeshExt*)mesh->ext;
@@ -220,6 +222,8 @@ void DflAssembleSystemPrepacked(Mesh3D* mesh, f64* wgalpha, f64* dwgalpha, f64* 
     /* external force on the momentum equations (particle reaction, include/dedflow.h): R = (...) - f_ext, after the tet and
        face terms and before the Dirichlet rows */
     if (F && x->ext_load) dfl_daxpy(3 * num_node, -1.0, x->ext_load, F, s);
+    /* heat source on the T rows (particle heat, include/dedflow.h): R_T = (...) - q, before the rows are captured */
+    if (F && x->heat_source) dfl_daxpy(num_node, -1.0, x->heat_source, F + 5 * (size_t)num_node, s);
     x->nodep_current = FALSE;
     if (F && x->scalar) DflScalarCaptureResidual(mesh, F); /* the phi / T rows, kept for the scalar transport (host/scalar.c) */
     if (F) HIPGUARD(hipMemsetAsync(F + 4 * (size_t)num_node, 0, (size_t)num_node * sizeof(f64) * 2, s)); /* main.c:63-66 */

@@ -138,7 +138,10 @@ void ParticleContextSetFluidCoupling(ParticleContext* ctx, Mesh3D* mesh, const D
         DflCoupleFree(c);
         c = x->couple = NULL;
     }
-    if (!mesh) return;
+    if (!mesh) {
+        DflHeatCouplingChanged(ctx);
+        return;
+    }
     if (Mesh3DNumTet(mesh) <= 0) {
         fprintf(stderr, "ParticleContextSetFluidCoupling: the mesh has no tets; coupling stays off\n");
         return;
@@ -173,6 +176,7 @@ void ParticleContextSetFluidCoupling(ParticleContext* ctx, Mesh3D* mesh, const D
     HIPGUARD(hipMemsetAsync(c->rem_load, 0, (size_t)(c->N > 0 ? c->N : 1) * 3 * sizeof(f64), s));
     c->rem_pending = FALSE;
     c->imp_time = 0.0;
+    DflHeatCouplingChanged(ctx);
 }
 
 /* the thread -> particle map of the walk: the contact sweep's (cell, id) order when it has run since the particle count
@@ -230,6 +234,7 @@ void ParticleContextFluidStep(ParticleContext* ctx, const f64* w) {
     DflProfileEnd(slot);
     if (x->omega) dfl_dem_spin(ctx->num_particle, x->dt, x->omega, x->alpha, DflStream()); /* the fluid exerts no torque */
     c->imp_time += x->dt;
+    if (x->heat) DflHeatStep(ctx, w); /* conduction over this sweep's contacts, convection at the new velocity */
     DflRangePop();
 }
 

@@ -136,7 +136,8 @@ index_type SolveFlowSystem(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matr
 /* one time step of main.c:537-565: predictor, Newton solve, corrector; optional DEM sub-steps.  A particle context coupled
  * to this mesh (ParticleContextSetFluidCoupling) instead takes `dem_substeps` fluid sub-steps after the corrector, in the
  * fluid state of the new time level; with two_way, the Newton solve sees the reaction load of the previous step's
- * sub-steps as an external load.  With inflow / outflow set on the context (ParticleContextSetInflow / SetOutflow),
+ * sub-steps as an external load, and with two-way particle heat (ParticleContextSetHeat) the heat they gave the fluid as a
+ * source of the T rows.  With inflow / outflow set on the context (ParticleContextSetInflow / SetOutflow),
  * ParticleContextAdd runs after the predictor and ParticleContextRemove after the particle sub-steps. */
 index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* J, f64* F, f64* dx, Krylov* ksp, Dirichlet** bcs,
                        index_type nbc, index_type newton_maxit, ParticleContext* pctx, index_type dem_substeps, f64* rnorm_out,
@@ -161,10 +162,18 @@ index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* 
         ASSERT(!user_load && "DflTimeStep: a two-way coupled step cannot add to an external load already registered");
         DflMeshSetExternalLoad(mesh, reaction);
     }
+    /* the heat the particles gave the fluid in the previous step's sub-steps: a source of the T rows, treated as the load */
+    const f64* user_heat = DflMeshHeatSource(mesh);
+    const f64* heat = coupled && DflParticleHeatTwoWay(pctx) ? DflParticlePendingHeatSource(pctx) : NULL;
+    if (heat) {
+        ASSERT(!user_heat && "DflTimeStep: a two-way heat step cannot add to a heat source already registered");
+        DflMeshSetHeatSource(mesh, heat);
+    }
     dfl_alpha_predict(N, fac_pred, dwg, s);
     if (pctx) ParticleContextAdd(pctx); /* main.c:547-548; a no-op unless inflow is set */
     index_type it = SolveFlowSystem(mesh, wgold, dwgold, dwg, J, F, dx, ksp, bcs, nbc, newton_maxit, rnorm_out, rnorm_init_out);
     if (reaction) DflMeshSetExternalLoad(mesh, user_load);
+    if (heat) DflMeshSetHeatSource(mesh, user_heat);
     if (pctx && !coupled)
         for (index_type k = 0; k < dem_substeps; ++k) ParticleContextUpdate(pctx); /* coupled step: contact sweep (config 4) */
     dfl_alpha_correct(N, fac_corr[0], fac_corr[1], wgold, dwgold, dwg, s);

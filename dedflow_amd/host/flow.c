@@ -26,7 +26,7 @@ typedef struct FlowState {
     index_type cap;                  /* capacity the buffers below (and the spares) are sized for */
     int64_t *tag, *tag_spare;        /* device [cap] */
     f64* spare3[6];                  /* device [cap][3]: coord, vel, acc, omega, alpha, imp */
-    f64* spare1[2];                  /* device [cap]: radius, mass (polydisperse) */
+    f64* spare1[5];                  /* device [cap]: radius, mass (polydisperse), temperature, energy, heat rate (heat) */
     index_type* tet_spare;           /* device [cap] */
     f64* lambda_spare;               /* device [cap][4] */
     index_type *keep, *newid, *rtet; /* device [cap], [cap + 1], [cap] */
@@ -52,7 +52,7 @@ static void free_spares(FlowState* f) {
         CdamFreeDevice(f->spare3[k], 0);
         f->spare3[k] = NULL;
     }
-    for (int k = 0; k < 2; ++k) {
+    for (int k = 0; k < 5; ++k) {
         CdamFreeDevice(f->spare1[k], 0);
         f->spare1[k] = NULL;
     }
@@ -126,9 +126,9 @@ static void ensure_spares(ParticleContext* ctx) {
     const int need3 = 3 + (x->omega ? 2 : 0) + (x->couple ? 1 : 0); /* coord, vel, acc, [w, alpha], [imp] */
     for (int k = 0; k < need3; ++k)
         if (!f->spare3[k]) f->spare3[k] = (f64*)CdamMallocDevice(n * 3 * SIZE_OF(f64));
-    if (x->radius)
-        for (int k = 0; k < 2; ++k)
-            if (!f->spare1[k]) f->spare1[k] = (f64*)CdamMallocDevice(n * SIZE_OF(f64));
+    const int need1 = (x->radius ? 2 : 0) + (x->heat ? 3 : 0); /* [radius, mass], [temp, e, rate] */
+    for (int k = 0; k < need1; ++k)
+        if (!f->spare1[k]) f->spare1[k] = (f64*)CdamMallocDevice(n * SIZE_OF(f64));
     if (x->couple && !f->tet_spare) {
         f->tet_spare = (index_type*)CdamMallocDevice(n * SIZE_OF(index_type));
         f->lambda_spare = (f64*)CdamMallocDevice(n * 4 * SIZE_OF(f64));
@@ -168,6 +168,14 @@ static void grow(ParticleContext* ctx, index_type need) {
         REGROW(x->mass, P, cap);
         REGROW(x->sorted_r, 0, cap);
     }
+    HeatState* h = x->heat;
+    if (h) {
+        REGROW(h->temp, P, cap);
+        REGROW(h->e, P, cap);
+        REGROW(h->rate, P, cap);
+        REGROW(h->q, 0, cap);
+        REGROW(h->sorted_t, 0, cap);
+    }
     CoupleState* c = x->couple;
     if (c) {
         REGROW(c->tet, P, cap);
@@ -189,7 +197,7 @@ static void set_count(ParticleContext* ctx, index_type P) {
     ctx->num_particle = P;
     for (int k = 0; k < 3; ++k) ctx->h_arr[k]->len = ctx->d_arr[k]->len = 3 * P;
     if (x->couple) x->couple->P = P;
-    x->order_valid = FALSE; /* the sweep's permutation holds the old ids */
+    x->order_valid = x->sort_valid = FALSE; /* the sweep's permutation holds the old ids */
 }
 
 static index_type read_count(const index_type* d) {
@@ -304,8 +312,9 @@ void ParticleContextRemove(ParticleContext* ctx) {
     pl.num = f->out.num_planes;
     memcpy(pl.plane, f->out.plane, sizeof pl.plane);
     const b32 pending = c && c->imp_time > 0.0;
+    const b32 heat_pending = DflHeatPending(ctx);
     dfl_flow_flag(P, ArrayData(ParticleCTXDeviceCoord(ctx)), pl, c ? c->tet : NULL, by_mesh ? 1 : 0, f->keep,
-                  pending ? f->rtet : NULL, s);
+                  pending || heat_pending ? f->rtet : NULL, s);
     dfl_exclusive_scan_i32(P, f->keep, f->newid, f->scan_tmp, f->scan_bytes, s);
     const index_type Pn = read_count(f->newid + P);
     if (Pn == P) {
@@ -313,6 +322,7 @@ void ParticleContextRemove(ParticleContext* ctx) {
         return;
     }
     if (pending) DflCoupleAccumulateRemoved(ctx, f->rtet); /* before the compaction moves imp and lambda */
+    if (heat_pending) DflHeatAccumulateRemoved(ctx, f->rtet);
     dfl_flow_fields fl;
     memset(&fl, 0, sizeof fl);
     f64* src3[6] = {ArrayData(ParticleCTXDeviceCoord(ctx)), ArrayData(ParticleCTXDeviceVel(ctx)), ArrayData(ParticleCTXDeviceAcc(ctx)),
@@ -325,11 +335,17 @@ void ParticleContextRemove(ParticleContext* ctx) {
         ++n3;
     }
     fl.n3 = n3;
-    if (x->radius) {
-        fl.src1[0] = x->radius; fl.dst1[0] = f->spare1[0];
-        fl.src1[1] = x->mass; fl.dst1[1] = f->spare1[1];
-        fl.n1 = 2;
+    HeatState* h = x->heat;
+    f64** live1[5] = {x->radius ? &x->radius : NULL, x->radius ? &x->mass : NULL, h ? &h->temp : NULL, h ? &h->e : NULL,
+                      h ? &h->rate : NULL};
+    int n1 = 0;
+    for (int k = 0; k < 5; ++k) {
+        if (!live1[k]) continue;
+        fl.src1[n1] = *live1[k];
+        fl.dst1[n1] = f->spare1[n1];
+        ++n1;
     }
+    fl.n1 = n1;
     fl.tag_src = f->tag;
     fl.tag_dst = f->tag_spare;
     if (c) {
@@ -367,9 +383,12 @@ void ParticleContextRemove(ParticleContext* ctx) {
         c->lambda = f->lambda_spare;
         f->lambda_spare = tl;
     }
-    if (x->radius) {
-        f64* t = x->radius; x->radius = f->spare1[0]; f->spare1[0] = t;
-        t = x->mass; x->mass = f->spare1[1]; f->spare1[1] = t;
+    for (int k = 0, m = 0; k < 5; ++k) {
+        if (!live1[k]) continue;
+        f64* t = *live1[k];
+        *live1[k] = f->spare1[m];
+        f->spare1[m] = t;
+        ++m;
     }
     if (x->omega) x->hist_cur = 1 - cur;
     f->stats.removed += P - Pn;
@@ -384,7 +403,10 @@ void ParticleContextAdd(ParticleContext* ctx) {
     f64 r_lo, r_hi; /* polydisperse: the lattice is built for r_hi */
     DflInflowRadii(ctx, &r_lo, &r_hi);
     const f64 R = x->radius ? r_hi : ParticleRadius(ctx);
-    if (x->radius && r_hi > x->rmax) x->rmax = r_hi; /* inserted at ParticleRadius without SetInflowSizes */
+    if (x->radius && r_hi > x->rmax) { /* inserted at ParticleRadius without SetInflowSizes */
+        x->rmax = r_hi;
+        x->sort_valid = FALSE;
+    }
     if (R != f->inlet_R) build_inlet(f, R);
     f->inlet.call = f->call++;
     f->credit += f->in.per_call;
@@ -424,6 +446,8 @@ void ParticleContextAdd(ParticleContext* ctx) {
     f->next_tag += n;
     f->stats.inserted += n;
     f->stats.blocked += want - n;
+    if (n > 0 && x->heat) /* inserted particles start at T_init with nothing pending */
+        dfl_heat_fill(P, n, x->heat->cfg.T_init, x->heat->temp, x->heat->rate, x->heat->e, s);
     if (n > 0) set_count(ctx, P + n);
     DflRangePop();
 }

@@ -75,6 +75,7 @@ typedef struct MeshExt {
     SlotPatchSched* slotpatch;     /* LHS slot-owner schedule (mode 4, default), built on first use */
     const f64* ext_load;           /* device [3N] external load on the momentum rows (DflMeshSetExternalLoad), NULL: none */
     struct ScalarState* scalar;    /* phi / T transport (host/scalar.c, DflMeshSetScalarTransport), NULL: off */
+    const f64* heat_source;        /* device [N] heat source of the T rows (DflMeshSetHeatSource), NULL: none */
 } MeshExt;
 
 void DflMeshPrepareFaces(Mesh3D* mesh, index_type group);
@@ -106,6 +107,9 @@ typedef struct ParticleExt {
     f64 gravity[3];                             /* body acceleration of ParticleContextUpdate */
     index_type cap;                             /* capacity of every per-particle buffer (>= num_particle; host/flow.c) */
     b32 order_valid;                            /* `order` is the last sweep's, for the current particles */
+    b32 sort_valid;                             /* ... and its cell list and sorted copies are those of the current grid and
+                                                   sizes (cleared by SetSizes / SetInflowSizes / SetWallMesh too): what a
+                                                   bare heat step needs before it reuses the sweep */
     struct FlowState* flow;                     /* particle inflow / outflow (host/flow.c), NULL when never set */
     /* polydisperse particles (ParticleContextSetSizes); monodisperse when radius == NULL */
     f64 *radius, *mass;                         /* device [cap], by particle id */
@@ -113,6 +117,7 @@ typedef struct ParticleExt {
     f64 rmax;                                   /* upper bound on every radius (host only, never lowered by Remove) */
     b32 in_sizes;                               /* ParticleContextSetInflowSizes was called: inserted radii in [in_r_lo, in_r_hi) */
     f64 in_r_lo, in_r_hi;
+    struct HeatState* heat;                     /* particle heat transfer (host/heat.c), NULL when off */
 } ParticleExt;
 /* the per-particle sizes of the kernels (all NULL, rmax 0 while x->radius == NULL: one size) */
 dfl_sizes DflSizes(const ParticleExt* x);
@@ -124,6 +129,8 @@ dfl_friction_law DflFrictionLaw(const ParticleContext* ctx);
 void DflFrictionClearHistory(ParticleContext* ctx); /* no-op when friction is off */
 /* the sweep's device workspace for P particles over nbin cell-list bins (count / cell_start [nbin + 1]); grows only */
 void DflDemReserve(ParticleExt* x, index_type P, index_type nbin);
+/* the cell sort of the contact sweep alone (unit box or mesh-wall grid): order / cell_start / sorted copies, order_valid */
+void DflDemBuildCells(ParticleContext* ctx);
 /* particle-fluid coupling state (host/couple.c) */
 typedef struct CoupleState {
     Mesh3D* mesh;
@@ -149,12 +156,38 @@ typedef struct CoupleState {
 void DflCoupleFree(struct CoupleState* c);
 /* scatter the pending impulse of the particles with rtet[i] >= 0 (removed, located) into rem_load (host/couple.c) */
 void DflCoupleAccumulateRemoved(ParticleContext* ctx, const index_type* rtet);
+/* particle heat transfer (host/heat.c): every per-particle buffer has the context's capacity */
+typedef struct HeatState {
+    DflParticleHeat cfg;
+    f64 cp_f, k_f;                   /* resolved fluid constants */
+    f64 *temp, *e, *rate;            /* device [cap] by particle id: temperature, pending energy from the fluid, last heat rate */
+    f64 *q, *sorted_t;               /* device [cap]: conduction rate by id, temperatures in the sweep's cell order */
+    f64 time;                        /* time the pending energy was accumulated over */
+    index_type N;                    /* nodes the two buffers below are sized for (0: none yet) */
+    f64 *source, *rem_q;             /* device [N]: the source DflTimeStep registers; -(energy of removed particles) per node */
+    b32 rem_pending;
+} HeatState;
+void DflHeatFree(struct HeatState* h);
+/* one thermal sub-step after the integration of ParticleContextUpdate (w NULL) / ParticleContextFluidStep */
+void DflHeatStep(ParticleContext* ctx, const f64* w);
+void DflHeatCopy(ParticleContext* dst, const ParticleContext* src);
+void DflHeatCouplingChanged(ParticleContext* ctx); /* SetFluidCoupling: pending energy and time start from zero */
+/* scatter the pending energy of the particles with rtet[i] >= 0 (removed, located) into rem_q, as the impulse above */
+void DflHeatAccumulateRemoved(ParticleContext* ctx, const index_type* rtet);
+b32 DflHeatPending(const ParticleContext* ctx);    /* heat on, coupled, and a coupled heat step ran since the last source */
+const f64* DflParticlePendingEnergy(const ParticleContext* ctx); /* device [P]: e_i since the last source (tests, probes) */
+const f64* DflParticleConductionRate(const ParticleContext* ctx); /* device [P]: q_i of the last heat step with k_p > 0 (tests) */
+b32 DflParticleHeatTwoWay(const ParticleContext* ctx);
+f64* DflParticlePendingHeatSource(ParticleContext* ctx); /* the pending source in the context's own [N] buffer, or NULL */
+const f64* DflMeshHeatSource(const Mesh3D* mesh);
 struct FlowState;
 void DflFlowFree(struct FlowState* f);
 struct WallState;
 void DflWallsFree(struct WallState* w);
 /* the contact sweep against the mesh walls (ParticleContextComputeForces when walls are set) */
 void DflWallsComputeForces(ParticleContext* ctx);
+void DflWallsBuildCells(ParticleContext* ctx);                   /* its cell sort alone */
+const dfl_grid3* DflWallsParticleGrid(const ParticleContext* ctx); /* the particle grid of that sort */
 /* the mesh a particle context is coupled to (NULL: uncoupled), its two-way switch, and the reaction load of the sub-steps
  * since the last ParticleContextReactionLoad into the context's own [3N] buffer (NULL when there were none) */
 Mesh3D* DflParticleCoupledMesh(const ParticleContext* ctx);

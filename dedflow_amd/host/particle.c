@@ -50,6 +50,7 @@ void ParticleContextDestroy(ParticleContext* ctx) {
         ParticleContextSetFriction(ctx, NULL);
         DflFlowFree(x->flow);
         ParticleContextSetSizes(ctx, NULL, NULL);
+        DflHeatFree(x->heat);
         CdamFreeHost(x, SIZE_OF(ParticleExt));
     }
     CdamFreeHost(ctx, SIZE_OF(ParticleContext));
@@ -61,6 +62,7 @@ void ParticleContextCopy(ParticleContext* dst, const ParticleContext* src) {
         ArrayCopy(dst->h_arr[k], src->h_arr[k], H2H);
         ArrayCopy(dst->d_arr[k], src->d_arr[k], D2D);
     }
+    DflHeatCopy(dst, src); /* the thermal state travels too */
     /* the sizes travel with the particles (the inflow radius range is configuration and stays) */
     const ParticleExt* xs = (const ParticleExt*)src->ext;
     ParticleExt* xd = (ParticleExt*)dst->ext;
@@ -113,16 +115,11 @@ void DflDemReserve(ParticleExt* x, index_type P, index_type nbin) {
     }
 }
 
-void ParticleContextComputeForces(ParticleContext* ctx) {
+/* the cell sort of the unit-box sweep */
+static void box_build_cells(ParticleContext* ctx) {
     ParticleExt* x = (ParticleExt*)ctx->ext;
-    if (x->walls) {
-        DflWallsComputeForces(ctx);
-        return;
-    }
     const index_type P = ctx->num_particle;
     const f64 R = x->radius ? x->rmax : ParticleRadius(ctx); /* polydisperse: the grid is built for Rmax */
-    hipStream_t s = DflStream();
-    DflRangePush("ParticleContextComputeForces");
     /* cell edge >= 4R: the interaction range of a particle covers at most two cells per axis; and not (much) finer than a few
        particles per cell -- the scan over the cells is what an over-fine grid pays for (125^3 cells for 100k particles cost
        14 us of scan; 58^3 cells 4 us, and the force kernel still tests only ~1.5 neighbours per particle) */
@@ -136,15 +133,32 @@ void ParticleContextComputeForces(ParticleContext* ctx) {
     DflDemReserve(x, P, ncell3);
     x->cell = cell;
     x->ncell = ncell;
-    const f64* coord = ArrayData(ParticleCTXDeviceCoord(ctx));
-    const f64* vel = ArrayData(ParticleCTXDeviceVel(ctx));
+    dfl_dem_build_cells(P, ArrayData(ParticleCTXDeviceCoord(ctx)), ArrayData(ParticleCTXDeviceVel(ctx)), x->omega, x->radius, cell,
+                        ncell, x->cell_of, x->rank, x->count, x->chunk_sum, x->cell_start, x->slot, x->order, x->sorted, x->sorted_w,
+                        x->sorted_r, DflStream());
+    x->order_valid = x->sort_valid = TRUE;
+}
+
+void DflDemBuildCells(ParticleContext* ctx) {
+    if (((ParticleExt*)ctx->ext)->walls) DflWallsBuildCells(ctx);
+    else box_build_cells(ctx);
+}
+
+void ParticleContextComputeForces(ParticleContext* ctx) {
+    ParticleExt* x = (ParticleExt*)ctx->ext;
+    if (x->walls) {
+        DflWallsComputeForces(ctx);
+        return;
+    }
+    const index_type P = ctx->num_particle;
+    const f64 R = x->radius ? x->rmax : ParticleRadius(ctx);
+    hipStream_t s = DflStream();
+    DflRangePush("ParticleContextComputeForces");
+    box_build_cells(ctx);
     f64* acc = ArrayData(ParticleCTXDeviceAcc(ctx));
-    dfl_dem_build_cells(P, coord, vel, x->omega, x->radius, cell, ncell, x->cell_of, x->rank, x->count, x->chunk_sum, x->cell_start,
-                        x->slot, x->order, x->sorted, x->sorted_w, x->sorted_r, s);
-    x->order_valid = TRUE;
     int slot = DflProfileBegin(DFL_TAG_SMALL + 1);
-    dfl_dem_forces(P, x->sorted, x->sorted_w, R, ParticleMass(ctx), DflSizes(x), x->kn, x->gamma_n, DflFrictionLaw(ctx), cell, ncell,
-                   x->order, x->cell_start, DflFrictionHistory(x), acc, x->alpha, s);
+    dfl_dem_forces(P, x->sorted, x->sorted_w, R, ParticleMass(ctx), DflSizes(x), x->kn, x->gamma_n, DflFrictionLaw(ctx), x->cell,
+                   x->ncell, x->order, x->cell_start, DflFrictionHistory(x), acc, x->alpha, s);
     DflProfileEnd(slot);
     DflRangePop();
 }
@@ -160,6 +174,7 @@ void ParticleContextUpdate(ParticleContext* ctx) {
     else
         dfl_dem_integrate(ctx->num_particle, x->dt, ArrayData(ParticleCTXDeviceCoord(ctx)), ArrayData(ParticleCTXDeviceVel(ctx)),
                           ArrayData(ParticleCTXDeviceAcc(ctx)), DflStream());
+    if (x->heat) DflHeatStep(ctx, NULL); /* conduction over this sweep's contacts */
 }
 
 /* ---- contact friction and rotation (model in include/dedflow.h) ---- */
@@ -283,6 +298,7 @@ static void free_sizes(ParticleExt* x) {
     CdamFreeDevice(x->radius, 0); CdamFreeDevice(x->mass, 0); CdamFreeDevice(x->sorted_r, 0);
     x->radius = x->mass = x->sorted_r = NULL;
     x->in_sizes = FALSE;
+    x->sort_valid = FALSE; /* the sorted copies and the grid were those of the per-particle sizes */
     x->rmax = 0.0;
 }
 
@@ -331,6 +347,7 @@ void ParticleContextSetSizes(ParticleContext* ctx, const f64* radius, const f64*
     if (x->in_sizes && x->in_r_hi > rmax) rmax = x->in_r_hi;
     if (P == 0 && rmax == 0.0) rmax = R;
     x->rmax = rmax;
+    x->sort_valid = FALSE; /* sorted_r and the grid of the last sweep are not these sizes' */
 }
 
 void ParticleContextSetInflowSizes(ParticleContext* ctx, f64 r_lo, f64 r_hi) {
@@ -351,7 +368,10 @@ void ParticleContextSetInflowSizes(ParticleContext* ctx, f64 r_lo, f64 r_hi) {
     x->in_sizes = TRUE;
     x->in_r_lo = r_lo;
     x->in_r_hi = r_hi;
-    if (r_hi > x->rmax) x->rmax = r_hi;
+    if (r_hi > x->rmax) {
+        x->rmax = r_hi;
+        x->sort_valid = FALSE; /* the grid is built for Rmax */
+    }
 }
 
 const f64* ParticleContextRadii(const ParticleContext* ctx) { return ((const ParticleExt*)ctx->ext)->radius; }

@@ -211,6 +211,7 @@ void ParticleContextSetWallMesh(ParticleContext* ctx, Mesh3D* mesh, index_type g
     ParticleExt* x = (ParticleExt*)ctx->ext;
     DflWallsFree(x->walls);
     x->walls = NULL;
+    x->sort_valid = FALSE;        /* the last cell sort was on the other grid */
     DflFrictionClearHistory(ctx); /* the keys of the wall contacts change meaning */
     if (!mesh) return;
     const index_type N = Mesh3DNumNode(mesh), T = Mesh3DNumTet(mesh);
@@ -319,23 +320,32 @@ index_type ParticleContextWallDroppedCount(const ParticleContext* ctx) {
     return n;
 }
 
-void DflWallsComputeForces(ParticleContext* ctx) {
+void DflWallsBuildCells(ParticleContext* ctx) {
     ParticleExt* x = (ParticleExt*)ctx->ext;
     WallState* w = x->walls;
     const index_type P = ctx->num_particle;
     const f64 R = ParticleContextMaxRadius(ctx); /* Rmax of a polydisperse context */
-    hipStream_t s = DflStream();
-    DflRangePush("ParticleContextComputeForces");
     if (R != w->R) build_grids(w, R, P);
     else if (P != w->P) build_particle_grid(w, R, P); /* ParticleContextAdd / Remove: the walls stay */
     const index_type ncell3 = w->pgrid.n[0] * w->pgrid.n[1] * w->pgrid.n[2];
     DflDemReserve(x, P, ncell3 + 1); /* + the bin of the particles outside the grid */
-    const f64* coord = ArrayData(ParticleCTXDeviceCoord(ctx));
-    const f64* vel = ArrayData(ParticleCTXDeviceVel(ctx));
+    dfl_walls_build_cells(P, ArrayData(ParticleCTXDeviceCoord(ctx)), ArrayData(ParticleCTXDeviceVel(ctx)), x->omega, x->radius,
+                          w->pgrid, x->cell_of, x->rank, x->count, x->chunk_sum, x->cell_start, x->slot, x->order, x->sorted,
+                          x->sorted_w, x->sorted_r, DflStream());
+    x->order_valid = x->sort_valid = TRUE;
+}
+
+const dfl_grid3* DflWallsParticleGrid(const ParticleContext* ctx) { return &((const ParticleExt*)ctx->ext)->walls->pgrid; }
+
+void DflWallsComputeForces(ParticleContext* ctx) {
+    ParticleExt* x = (ParticleExt*)ctx->ext;
+    WallState* w = x->walls;
+    const index_type P = ctx->num_particle;
+    const f64 R = ParticleContextMaxRadius(ctx);
+    hipStream_t s = DflStream();
+    DflRangePush("ParticleContextComputeForces");
+    DflWallsBuildCells(ctx);
     f64* acc = ArrayData(ParticleCTXDeviceAcc(ctx));
-    dfl_walls_build_cells(P, coord, vel, x->omega, x->radius, w->pgrid, x->cell_of, x->rank, x->count, x->chunk_sum, x->cell_start,
-                          x->slot, x->order, x->sorted, x->sorted_w, x->sorted_r, s);
-    x->order_valid = TRUE;
     int slot = DflProfileBegin(DFL_TAG_SMALL + 1);
     dfl_walls_forces(P, x->sorted, x->sorted_w, R, ParticleMass(ctx), DflSizes(x), x->kn, x->gamma_n, DflFrictionLaw(ctx), w->pgrid,
                      x->order, x->cell_start, w->tri, w->plane, w->wgrid, w->wstart, w->wlist, 1e-12 * w->scale, w->dropped,

@@ -1000,6 +1000,75 @@ const f64* ParticleContextMasses(const ParticleContext* ctx); /* device [P]; NUL
 f64 ParticleContextMaxRadius(const ParticleContext* ctx);     /* Rmax; ParticleRadius when monodisperse */
 void ParticleContextSetInflowSizes(ParticleContext* ctx, f64 r_lo, f64 r_hi);
 
+/* ---- particle heat transfer (build-defined; opt-in) ---------------------------------------------------------------------
+ * The reference has no physics here (empty particle hooks, no source in its T equation).  A context that never calls
+ * ParticleContextSetHeat with a configuration, and a mesh that never gets a heat source, compute bit for bit what they
+ * compute without this section, through the same launches.  One GPU only (DflTimeStep refuses a coupled context under a
+ * communicator).  With r_i, m_i the particle's radius and mass (ParticleRadius / ParticleMass when monodisperse),
+ * d = 2 r_i, C_i = m_i cp_p:
+ *   conduction  (k_p > 0) for every particle pair in contact in the sub-step's contact sweep -- the sorted copies, the cell
+ *               list and the overlap test of the force kernel, through the same pair loop, so no pair is a contact for the
+ *               force and not for the heat -- with overlap delta = (r_i + r_j) - dist: contact radius a = sqrt(r* delta),
+ *               r* = r_i r_j / (r_i + r_j), conductance H = 2 k_p a (Batchelor-O'Brien, equal conductivities),
+ *               q_i += H (T_j - T_i) with the temperatures at the START of the sub-step (explicit).  H is evaluated with
+ *               commutative operations on (r_i, r_j): both partners get exactly opposite heat.  Visit order = the pair
+ *               loop's: bitwise reproducible for a given contact grid; two grids that bin the particles differently (the
+ *               unit box and a wall mesh's, or another Rmax) visit a particle's partners in another order and agree to
+ *               the rounding of the sum.  Walls are adiabatic (box walls and mesh walls alike).  A particle outside
+ *               the contact grid of a wall mesh has no partner, as for forces.  Explicit conduction is stable for
+ *               dt sum_j H_ij / C_i < 1: the caller's condition, not enforced.
+ *   convection  (coupled context, fluid state given, particle located in a tet) T_f = sum_a lambda_a T(node_a) with
+ *               T = w[5N + node], u_f as the drag does, Re = rho_f |u_f - v| d / mu_f with the velocity v the particle has
+ *               when the heat step runs, Pr = cp_f mu_f / k_f, Ranz-Marshall Nu = 2 + 0.6 Re^(1/2) Pr^(1/3),
+ *               tau_T = C_i / (Nu k_f pi d); rho_f and mu_f are the coupling's.  A particle outside the mesh (tet < 0)
+ *               exchanges nothing with the fluid.
+ *   update      implicit in T_i for the convective part (stable for any dt / tau_T, the thermal twin of the drag update):
+ *                 T_i' = (T_i + dt (q_i / C_i + T_f / tau_T)) / (1 + dt / tau_T);   without convection T_i' = T_i + dt q_i / C_i
+ *               heat_rate_i = C_i (T_i' - T_i) / dt (0 for dt = 0).  The energy the fluid gave the particle, e_i = dt C_i (T_f - T_i') / tau_T,
+ *               is accumulated per particle like the drag impulse.
+ *   source      q[a] = -sum_p lambda_{a,p} e_p / (time since the last call), summed in the fixed order of the reaction load
+ *               (no float atomics, bitwise reproducible), with the latest lambda; a particle outside the mesh at that
+ *               moment contributes nothing.  The energy pending on particles that ParticleContextRemove takes out is kept
+ *               and added to the next source.  sum_a q[a] = -sum_p e_p / time to rounding.
+ *   T rows      with a source registered (DflMeshSetHeatSource) every F assembly subtracts it from F[5N:6N): the residual is
+ *               R_T = (...) - q, after the tet and face terms and before the phi / T rows are captured for the scalar
+ *               transport, whose Dirichlet rows stay exactly zero and whose Newton solve sees it.  Explicit: not in J_T.
+ *   time step   ParticleContextUpdate (uncoupled: conduction only) and ParticleContextFluidStep (coupled) run the heat step
+ *               after their integration when heat is on; it never changes coord / vel / acc / omega.  Conduction thus sees
+ *               the geometry of the sub-step's force sweep (positions before the integration), convection the tets and
+ *               weights of that sub-step's location and the velocity after it.  With two_way, DflTimeStep registers the
+ *               pending source for its Newton solve and restores the caller's registration afterwards, as it treats the
+ *               reaction load; a user source already registered is an ASSERT.  A bare ParticleContextHeatStep runs the cell
+ *               sort itself when no sweep is valid for the current particles (it never computes forces) and, coupled with
+ *               a fluid state, locates the particles first.  A sweep stops being valid when the particle count, the sizes
+ *               or the wall mesh change; particles that merely MOVED since the last sweep (its own integration, or
+ *               coordinates the caller rewrote) do not invalidate it: conduction then sees that sweep's geometry, as in the
+ *               sub-steps.  Call ParticleContextComputeForces first to conduct over rewritten coordinates.
+ *   travel      temperature and pending energy follow the particle through ParticleContextRemove; particles inserted by
+ *               ParticleContextAdd get T_init; ParticleContextCopy carries the heat state (dst becomes what src is);
+ *               ParticleContextSave writes <group>/temp when heat is on, ParticleContextLoad reads it when the file has it
+ *               and heat is on (the file holds no heat configuration; with heat off the dataset is skipped with a line
+ *               on stderr).
+ * A heat step is three small launches (one when k_p <= 0); nothing is allocated or synchronised per call: the per-node
+ * buffers are sized when heat is set on a coupled context or the coupling is set on a context with heat. */
+typedef struct DflParticleHeat {
+    f64 cp_p;        /* particle specific heat            (> 0, required)                              */
+    f64 k_p;         /* particle conductivity for contact conduction; <= 0: no contact conduction      */
+    f64 cp_f, k_f;   /* fluid specific heat / conductivity; <= 0: the reference's kCP = 1, kKAPPA = 0.66 */
+    f64 T_init;      /* temperature of every particle at the call, and of particles inserted later      */
+    b32 two_way;     /* DflTimeStep feeds the particles' heat back into the T rows                      */
+} DflParticleHeat;
+/* cfg NULL: off, frees the state.  A call with a configuration sets every temperature to T_init and clears what is pending;
+ * cp_p <= 0 is reported on stderr and leaves the context unchanged */
+void ParticleContextSetHeat(ParticleContext* ctx, const DflParticleHeat* cfg);
+f64* ParticleContextTemperature(ParticleContext* ctx);           /* device [P], writable; NULL when off; valid until Add / Remove */
+const f64* ParticleContextHeatRate(const ParticleContext* ctx);  /* device [P]: W into each particle, last step; NULL when off */
+void ParticleContextHeatStep(ParticleContext* ctx, const f64* w);/* one thermal sub-step; w NULL or uncoupled: conduction only */
+/* q (device [N]) <- the heat given to the fluid per node and unit time since the last call (zero when no coupled sub-step
+ * ran); resets it.  Needs heat on and a coupled context */
+void ParticleContextHeatSource(ParticleContext* ctx, f64* q);
+void DflMeshSetHeatSource(Mesh3D* mesh, const f64* q);           /* device [N], NULL = none; must outlive registration */
+
 #ifdef __cplusplus
 }
 #endif

@@ -518,7 +518,8 @@ void dfl_dem_spin(dfl_index P, dfl_value dt, dfl_value* omega, const dfl_value* 
  *    dfl_couple_fluid_step    drag + gravity + integration of every particle; imp[i][3] += drag impulse
  *    dfl_couple_sort_by_tet   members[tstart[t] .. tstart[t+1]) = the particles in tet t, ascending id; tcount[T] is
  *                             zero-initialised scratch that the call leaves zeroed again
- *    dfl_couple_node_load     load[3a + d] = -scale * sum_{e in V2E(a)} sum_{p in e} lambda_{p,k(a,e)} imp[p][d] */
+ *    dfl_couple_node_load     load[3a + d] = -scale * sum_{e in V2E(a)} sum_{p in e} lambda_{p,k(a,e)} imp[p][d]
+ *    dfl_couple_node_scalar   the same sum of one value per particle: out[a] = -scale * sum lambda_{p,k(a,e)} e[p] */
 #define DFL_COUPLE_MAX_WALK 4096
 void dfl_couple_sort_v2e(dfl_index N, const dfl_index* vrow, dfl_index* vcol, void* stream);
 void dfl_couple_neighbours(dfl_index T, const dfl_index* ien, const dfl_index* vrow, const dfl_index* vcol, dfl_index* nbr,
@@ -536,6 +537,9 @@ void dfl_couple_sort_by_tet(dfl_index P, dfl_index T, const dfl_index* tet, dfl_
 void dfl_couple_node_load(dfl_index N, const dfl_index* vrow, const dfl_index* vcol, const dfl_index* ien,
                           const dfl_index* tstart, const dfl_index* members, const dfl_value* lambda, const dfl_value* imp,
                           dfl_value scale, dfl_value* load, void* stream);
+void dfl_couple_node_scalar(dfl_index N, const dfl_index* vrow, const dfl_index* vcol, const dfl_index* ien,
+                            const dfl_index* tstart, const dfl_index* members, const dfl_value* lambda, const dfl_value* e,
+                            dfl_value scale, dfl_value* out, void* stream);
 
 /* ---- particle inflow and outflow (build-defined, opt-in; csrc/k_flow.hip, model in include/dedflow.h)
  *    dfl_flow_flag          keep[i] = 0 when particle i is beyond a plane (n . x > d) or, by_tet, at tet[i] == -1; else 1.
@@ -567,8 +571,9 @@ typedef struct dfl_flow_fields {
     const dfl_index* hcount_src;
     dfl_contact_hist* hrow_dst;
     dfl_index* hcount_dst;
-    const dfl_value* src1[2];    /* [P] per-particle scalars (radius, mass of a polydisperse context) */
-    dfl_value* dst1[2];
+    const dfl_value* src1[5];    /* [P] per-particle scalars (radius, mass of a polydisperse context; temperature, pending
+                                    energy and heat rate with particle heat on) */
+    dfl_value* dst1[5];
     int n1;
 } dfl_flow_fields;
 /* the inlet lattice: the host constants of include/dedflow.h (base, pu, pv, ou, ov), the plane frame (o, unit uhat, vhat,
@@ -658,6 +663,32 @@ void dfl_walls_forces(dfl_index P, const dfl_value* sorted, const dfl_value* sor
                       const dfl_index* order, const dfl_index* cell_start, const dfl_wall_tri* tri, const dfl_index* plane,
                       dfl_grid3 wall_grid, const dfl_index* wall_start, const dfl_index* wall_list, dfl_value tol,
                       dfl_index* dropped, dfl_contact_history hist, dfl_value* acc, dfl_value* alpha, void* stream);
+
+/* ---- particle heat transfer (build-defined, opt-in; csrc/k_heat.hip, model in include/dedflow.h)
+ * One thermal sub-step = gather, conduction (when k_p > 0), update; all on `stream`, nothing allocated or synchronised.
+ *    dfl_heat_gather           sorted_t[s] = temp[order[s]]: the temperatures in the contact sweep's cell order
+ *    dfl_heat_conduction       q[i] = sum_j 2 k_p sqrt(r* delta) (T_j - T_i) over the contacts of the unit-box sweep whose
+ *                              cell sort left sorted / order / cell_start (and sz.sorted_r when per-particle sizes)
+ *    dfl_heat_conduction_grid  the same over the sweep on a mesh's grid (dfl_walls_build_cells); 0 for a particle outside it
+ *    dfl_heat_update           the temperature update of every particle, in id order: convection with the fluid state w
+ *                              ([6N], T = w[5N + node]) for a particle with tet[i] >= 0, conduction rate q (may be NULL);
+ *                              w or tet NULL: conduction only.  m, r: per-particle mass and radius, or NULL for the scalars.
+ *                              pr13 = Pr^(1/3).  Writes temp, rate = C (T' - T) / dt (0 when dt == 0), e += the energy the
+ *                              fluid gave
+ *    dfl_heat_fill             temp = t_init, rate = e = 0 for the particles [first, first + count) */
+void dfl_heat_gather(dfl_index P, const dfl_index* order, const dfl_value* temp, dfl_value* sorted_t, void* stream);
+void dfl_heat_conduction(dfl_index P, const dfl_value* sorted, dfl_value radius, dfl_sizes sz, dfl_value cell, dfl_index ncell,
+                         const dfl_index* order, const dfl_index* cell_start, const dfl_value* sorted_t, dfl_value k_p,
+                         dfl_value* q, void* stream);
+void dfl_heat_conduction_grid(dfl_index P, const dfl_value* sorted, dfl_value radius, dfl_sizes sz, dfl_grid3 grid,
+                              const dfl_index* order, const dfl_index* cell_start, const dfl_value* sorted_t, dfl_value k_p,
+                              dfl_value* q, void* stream);
+void dfl_heat_update(dfl_index P, const dfl_index* tet, const dfl_value* lambda, const dfl_index* ien, const dfl_value* w,
+                     dfl_index N, dfl_value mass, dfl_value radius, const dfl_value* m, const dfl_value* r, const dfl_value* vel,
+                     dfl_value cp_p, dfl_value k_f, dfl_value rho_f, dfl_value mu_f, dfl_value pr13, dfl_value dt,
+                     const dfl_value* q, dfl_value* temp, dfl_value* rate, dfl_value* e, void* stream);
+void dfl_heat_fill(dfl_index first, dfl_index count, dfl_value t_init, dfl_value* temp, dfl_value* rate, dfl_value* e,
+                   void* stream);
 
 /* ---- scalar transport (host/scalar.c, csrc/k_scalar.hip) ------------------------------------------------------------
  * dfl_assemble_scalar_jacobian: the level-set and temperature Jacobians (d R_phi / d dphi, d R_T / d dT) over the nodal
