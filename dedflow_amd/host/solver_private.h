@@ -1,4 +1,4 @@
-/* Krylov solver internals shared by host/solver.c and host/ws_placement.c. */
+/* Krylov solver internals shared by host/solver.c, host/gmres.c and host/ws_placement.c. */
 #ifndef DFL_SOLVER_PRIVATE_H
 #define DFL_SOLVER_PRIVATE_H
 #include "dedflow.h"
@@ -43,17 +43,58 @@ typedef struct KrylovExt {
     char* amgx_cfg;     /* KrylovSetAMGXConfig: options of PCCreateAMGX (NULL: the reference configuration) */
 } KrylovExt;
 
+static inline KrylovExt* kext(const Krylov* k) { return (KrylovExt*)k->ext; }
+
+/* Everything about one GMRES solve that does not change while it runs; filled once per solve by DflGmresPlanFill. */
+typedef enum { GMRES_X4_NONE, GMRES_X4_SINGLE, GMRES_X4_PARTITIONED } GmresX4; /* matvec gathers from the interleaved copy */
+typedef enum {
+    GMRES_STEP_REFERENCE,      /* one GPU: dots, then update + norm + Givens in one launch (dfl_cgs_update_givens) */
+    GMRES_STEP_TWO_REDUCTIONS, /* partitioned: all-reduce of h, update, all-reduce of the norm, dfl_givens_sq */
+    GMRES_STEP_FUSED_NORM,     /* KrylovSetFusedNorm: ||w - Qh|| from w.w - sum h^2, one reduction (dfl_gmres_givens_pythagoras) */
+    GMRES_STEP_FUSED_UPDATE_PC /* ... with update, Givens and the next M^-1 in one launch (dfl_cgs_update_pc_givens_x4) */
+} GmresStep;
+typedef struct GmresPlan {
+    index_type n, na, m, ldh, maxit; /* rows, active length, basis columns per cycle, leading dimension of H, iteration cap */
+    b32 dist, split_rows;            /* communicator; interior rows run while the halo is in flight */
+    index_type n_interior, owned_rows;
+    hipStream_t side;          /* split rows: the exchange's stream, which the boundary rows run on; NULL: the library stream */
+    GmresX4 x4;                /* x4_N: nodes of the block matrix; x4_owned: nodes whose entries the producer of z interleaves */
+    index_type x4_N, x4_owned;
+    b32 x4_skip_z;             /* one GPU: nothing reads z in the reference layout, the PC kernel does not store it */
+    f64* z4;                   /* the interleaved copy: the spare column of the basis block; NULL without x4 */
+    GmresStep step;
+    const f64 *d33, *d1;       /* Jacobi tree (DflPcJacobiTreeData: d33, d1, N, rows) for the fused step */
+    index_type N, rows;
+    f64* Zb;                   /* FGMRES: the basis of preconditioned vectors; NULL otherwise */
+    b32 lazy;                  /* host reads ride behind the next iteration instead of idling the device */
+} GmresPlan;
+
+#define DFL_INTERNAL __attribute__((visibility("hidden"))) /* shared between the host sources, not exported */
 
 /* host/solver.c */
+PC* DflKrylovBuildPC(Krylov* ksp, Matrix* A);            /* the (re)build step of KrylovSolve */
+void DflKrylovMarkInner(Krylov* ksp);
+/* the reference's tree (krylov.c:439-453) in its fused form: the two inverse-diagonal arrays, node count, owned rows */
+DFL_INTERNAL b32 DflPcJacobiTreeData(PC* pc, const f64** d33, const f64** d1, index_type* N, index_type* nrows);
+
+/* host/gmres.c */
 int DflWsInPool(void);
 void DflWsVecFreeAs(f64* p, int pooled);
 void DflPcApplyFused(PC* pc, index_type na, f64* w, const f64* d_nrm, f64* z);
 b32 DflPcApplyFusedX4(PC* pc, index_type na, f64* w, const f64* d_nrm, f64* z, f64* z4); /* TRUE: z4 written too */
-PC* DflKrylovBuildPC(Krylov* ksp, Matrix* A);            /* the (re)build step of KrylovSolve */
 b32 DflKrylovEnsureWorkspace(Krylov* ksp, Matrix* A, index_type* n, index_type* m, index_type* ldh);
-void DflKrylovMarkInner(Krylov* ksp);
+DFL_INTERNAL void GMRESSolvePrivate(Matrix* A, f64* x, f64* b, void* ctx);
+DFL_INTERNAL void DflWsEnsure(KrylovExt* x, index_type n, index_type maxit, index_type ldh, index_type hist);
+DFL_INTERNAL void DflWsFree(KrylovExt* x);
+DFL_INTERNAL void DflGmresSizes(const KrylovExt* ex, index_type max_iter, index_type* m, index_type* ldh);
+DFL_INTERNAL index_type DflKrylovTailBegin(Matrix* A);
+DFL_INTERNAL void DflProbeOperands(const f64* b, index_type begin, index_type n, const f64* x, f64* scratch, b32* tail_zero, b32* x_zero);
+DFL_INTERNAL void DflZeroGhostRows(const KrylovExt* ex, Matrix* A, f64* v, index_type na);
+DFL_INTERNAL void DflGmresPlanFill(GmresPlan* p, const KrylovExt* ex, index_type max_iter, Matrix* A, PC* pc, index_type na, b32 pipelined);
+DFL_INTERNAL b32 DflKrylovConverged(const Krylov* ksp, f64 rnrm, f64 rnrm_init);
+DFL_INTERNAL void DflKrylovPrintProgress(const Krylov* ksp, index_type it, f64 rnrm, f64 rnrm_init, index_type restart_cycle);
 
 /* host/ws_placement.c: where the Krylov basis (and, in the explicit heavy form, the value array) is placed */
-f64* DflWsPickBasis(KrylovExt* ex, Matrix* A, PC* pc, f64* first, ptrdiff_t count, index_type na, index_type m, index_type ldh);
+f64* DflWsPickBasis(KrylovExt* ex, Matrix* A, PC* pc, f64* first, index_type max_iter, index_type na);
 
 #endif

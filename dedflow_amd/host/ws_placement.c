@@ -12,9 +12,9 @@
  *     milliseconds of loop pieces).  Skipped for inner / coarse solvers, small systems, pooled or arena work spaces.
  *
  *   DflKrylovCalibratePlacement (explicit opt-in; bench.py calls it before its timed legs and says so in `config`): the heavy
- *     lottery of round 2 -- six basis blocks, two of them behind spacers, up to six heap copies of the value array behind
+ *     lottery -- six basis blocks, two of them behind spacers, up to six heap copies of the value array behind
  *     spacers of 1/8 ... 5/8 of the free memory, a second round of three more far blocks, waits for the driver's wipe around
- *     the timings -- now capped by `max_extra_bytes` of transient device memory.  It MAY move the block value array
+ *     the timings -- capped by `max_extra_bytes` of transient device memory.  It MAY move the block value array
  *     (DFL_VAL_RELOCATE=0 forbids): a host that cached MatrixFSBlockValues(A) must ask again afterwards.
  *
  * Both time the same thing: a short piece of the real Arnoldi loop (CGS over 6 columns, preconditioner, SpMV into the next
@@ -52,27 +52,23 @@ typedef struct Loop {
     KrylovExt* ex;
     Matrix* A;
     PC* pc;
-    index_type na, m, ldh;
-    index_type n;  /* column stride of the basis block */
+    index_type na, m; /* active length = column stride of the basis block; basis columns per cycle */
     index_type x4; /* > 0: the solver's matvec gathers from the interleaved copy (nodes of the unpartitioned block matrix) */
     hipEvent_t a, b;
 } Loop;
 
-static void loop_open(Loop* L, KrylovExt* ex, Matrix* A, PC* pc, index_type na, index_type m, index_type ldh) {
-    L->ex = ex; L->A = A; L->pc = pc; L->na = na; L->m = m; L->ldh = ldh;
-    L->n = na;
-    {   /* the conditions of gmres_run's x4_path (one GPU, block values, not switched off) */
-        const index_type N = MatrixFSBlockValues(A) ? ((MatrixFS*)A->data)->spy1x1->num_row : 0;
-        const b32 off = getenv("DFL_SPMV_X4") && atoi(getenv("DFL_SPMV_X4")) == 0;
-        /* (partitioned solvers gather from the interleaved copy too -- owned rows, ghost columns filled behind the unpack; the
-           timing loop fills the ghost part from tmp, whatever it holds: placement, not values, is what is measured) */
-        L->x4 = (!off && N >= 4096 && na >= 4 * N && (ex->has_comm || (!ex->fused_norm && MatrixFSOwnedRows(A) == N))) ? N : 0;
-    }
+static void loop_open(Loop* L, KrylovExt* ex, Matrix* A, PC* pc, index_type max_iter, index_type na) {
+    GmresPlan plan; /* what the solver itself will do with this matrix, preconditioner and active length */
+    DflGmresPlanFill(&plan, ex, max_iter, A, pc, na, FALSE);
+    L->ex = ex; L->A = A; L->pc = pc; L->na = na; L->m = plan.m;
+    /* (partitioned solvers gather from the interleaved copy too -- owned rows, ghost columns filled behind the unpack; the
+       timing loop fills the ghost part from tmp, whatever it holds: placement, not values, is what is measured) */
+    L->x4 = plan.x4 != GMRES_X4_NONE ? plan.x4_N : 0;
     HIPGUARD(hipEventCreate(&L->a));
     HIPGUARD(hipEventCreate(&L->b));
     const f64 one = 1.0;
     HIPGUARD(hipMemcpyAsync(ex->nrm, &one, sizeof one, H2D, DflStream()));
-    HIPGUARD(hipMemsetAsync(ex->H, 0, (size_t)ldh * sizeof(f64), DflStream()));
+    HIPGUARD(hipMemsetAsync(ex->H, 0, (size_t)plan.ldh * sizeof(f64), DflStream()));
 }
 static void loop_close(Loop* L) {
     HIPGUARD(hipEventDestroy(L->a));
@@ -93,20 +89,15 @@ static float time_block(const Loop* L, f64* Qk) {
         f64* y = Qk + (size_t)col * (size_t)na;
         dfl_cgs_dots(na, 6, Qk, na, w, ex->H, ex->work, s);
         dfl_cgs_update(na, 6, Qk, na, ex->H, w, ex->nrm + 1, 1, ex->work, s);
-        if (L->x4) { /* as the solver does it: the interleaved copy in the spare column of THIS block, written by the PC kernel */
-            f64* z4 = Qk + (size_t)(m + 1) * (size_t)na;
-            const index_type owned = MatrixFSOwnedRows(L->A);
-            if (!DflPcApplyFusedX4(L->pc, na, w, ex->nrm, ex->tmp, z4)) dfl_interleave4(0, owned, L->x4, ex->tmp, z4, s);
-            if (owned < L->x4) dfl_interleave4(owned, L->x4, L->x4, ex->tmp, z4, s);
-            HIPGUARD(hipEventRecord(L->a, s));
-            DflMatrixFSMatVecX4Range(L->A, z4, y, 0, owned);
-            HIPGUARD(hipEventRecord(L->b, s));
-        } else {
-            DflPcApplyFused(L->pc, na, w, ex->nrm, ex->tmp);
-            HIPGUARD(hipEventRecord(L->a, s));
-            MatrixMatVec(L->A, ex->tmp, y);
-            HIPGUARD(hipEventRecord(L->b, s));
-        }
+        /* as the solver does it: the interleaved copy in the spare column of THIS block, written by the PC kernel */
+        f64* const z4 = L->x4 ? Qk + (size_t)(m + 1) * (size_t)na : NULL;
+        const index_type owned = MatrixFSOwnedRows(L->A);
+        if (!DflPcApplyFusedX4(L->pc, na, w, ex->nrm, ex->tmp, z4) && z4) dfl_interleave4(0, owned, L->x4, ex->tmp, z4, s);
+        if (z4 && owned < L->x4) dfl_interleave4(owned, L->x4, L->x4, ex->tmp, z4, s);
+        HIPGUARD(hipEventRecord(L->a, s));
+        if (z4) DflMatrixFSMatVecX4Range(L->A, z4, y, 0, owned);
+        else MatrixMatVec(L->A, ex->tmp, y);
+        HIPGUARD(hipEventRecord(L->b, s));
         HIPGUARD(hipEventSynchronize(L->b));
         HIPGUARD(hipEventElapsedTime(&ms, L->a, L->b));
         if (rep > 0) sum_ms += ms;
@@ -126,7 +117,9 @@ static void* try_malloc(size_t bytes) {
 }
 
 /* ---- default: bounded, no side effects beyond the choice of the basis block ------------------------------------------ */
-f64* DflWsPickBasis(KrylovExt* ex, Matrix* A, PC* pc, f64* first, ptrdiff_t count, index_type na, index_type m, index_type ldh) {
+f64* DflWsPickBasis(KrylovExt* ex, Matrix* A, PC* pc, f64* first, index_type max_iter, index_type na) {
+    index_type m, ldh;
+    DflGmresSizes(ex, max_iter, &m, &ldh);
     int ncand = 4;
     const char* e = getenv("DFL_WS_CANDIDATES");
     if (e) ncand = atoi(e);
@@ -134,7 +127,7 @@ f64* DflWsPickBasis(KrylovExt* ex, Matrix* A, PC* pc, f64* first, ptrdiff_t coun
     if (ncand < 2 || !eligible(ex, A, na, m)) return first;
     const double t_begin = omp_get_wtime();
     hipStream_t s = DflStream();
-    const size_t bytes = (size_t)count * sizeof(f64);
+    const size_t bytes = (size_t)MatrixNumRow(A) * (size_t)(m + 2) * sizeof(f64); /* the basis block as DflWsEnsure sizes it */
     size_t budget = (size_t)16 << 30;
     if (getenv("DFL_WS_MAX_EXTRA_GB")) budget = (size_t)(atof(getenv("DFL_WS_MAX_EXTRA_GB")) * 1073741824.0);
     {
@@ -162,7 +155,7 @@ f64* DflWsPickBasis(KrylovExt* ex, Matrix* A, PC* pc, f64* first, ptrdiff_t coun
     }
     if (n == 1) return first;
     Loop L;
-    loop_open(&L, ex, A, pc, na, m, ldh);
+    loop_open(&L, ex, A, pc, max_iter, na);
     int best = 0;
     for (int k = 0; k < n; ++k) {
         ms[k] = time_block(&L, cand[k]);
@@ -243,12 +236,11 @@ void DflKrylovCalibratePlacement(Krylov* ksp, Matrix* A, int64_t max_extra_bytes
     if (!DflKrylovEnsureWorkspace(ksp, A, &n, &m, &ldh)) return; /* not a GMRES solver */
     PC* pc = DflKrylovBuildPC(ksp, A);
     PCSetup(pc);
-    const index_type N = ((MatrixFS*)A->data)->spy1x1->num_row;
-    const index_type na = n == 6 * N ? 4 * N : n; /* the driver path: the phi / T tail of b is zero (Q5) */
+    const index_type na = DflKrylovTailBegin(A); /* the driver path: the phi / T tail of b is zero (Q5) */
     ex->ws_fresh = FALSE;                          /* the first solve does not calibrate again */
     if (ex->flexible || !eligible(ex, A, na, m)) return;
     hipStream_t s = DflStream();
-    const ptrdiff_t count = (ptrdiff_t)n * (m + 2); /* (+ the spare column of the interleaved matvec input, as ws_ensure) */
+    const ptrdiff_t count = (ptrdiff_t)n * (m + 2); /* (+ the spare column of the interleaved matvec input, as DflWsEnsure) */
     const size_t bytes = (size_t)count * sizeof(f64);
     Budget bud = {max_extra_bytes > 0 ? (size_t)max_extra_bytes : ~(size_t)0, 0};
     double settle_cap = 10.0;
@@ -285,7 +277,7 @@ void DflKrylovCalibratePlacement(Krylov* ksp, Matrix* A, int64_t max_extra_bytes
             if (hv[v]) HIPGUARD(hipMemcpyAsync(hv[v], old_val, vbytes, D2D, s));
         }
     Loop L;
-    loop_open(&L, ex, A, pc, na, m, ldh);
+    loop_open(&L, ex, A, pc, ksp->max_iter, na);
     /* 3. quiet, then the candidate matrix */
     float settled_ms[2] = {0.f, 0.f};
     double settled_s[2] = {0.0, 0.0};

@@ -79,7 +79,7 @@ def run_cpu(rank, world, M, its):
     yg = Sg.matvec(valsg, xr)
     assert np.abs(yl[own4] - yg[gidx4]).max() <= 1e-10 * np.abs(yg).max()
 
-    # distributed right-preconditioned GMRES (mirror of dedflow_amd/host/solver.c)
+    # distributed right-preconditioned GMRES (mirror of dedflow_amd/host/gmres.c)
     d33, d1 = S.pc_setup(vals)
 
     def pc(v):
