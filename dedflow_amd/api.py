@@ -474,6 +474,57 @@ class Particles:
         lib().ParticleContextHeatSource(self.ctx, out.ptr)
         return out
 
+    # ---- laser energy deposition (build-defined; model in include/dedflow.h) ----------------------------------------
+    def set_laser(self, origin, direction=(0.0, 0.0, -1.0), power=0.0, w=1.0, h=1.0, r_cut=1.0, eta_p=1.0, eta_s=1.0,
+                  scan_vel=(0.0, 0.0, 0.0), substrate_groups=()):
+        """ParticleContextSetLaser: a collimated Gaussian beam through `origin` along `direction`, power (W), 1/e^2 radius w,
+        column edge h and cut-off radius r_cut of the column grid, absorptivities of powder and substrate, the axis'
+        velocity, and the boundary groups of the coupled mesh that receive the transmitted beam; origin None turns the
+        laser off.  Needs set_heat.  A configuration the library refuses (reported on stderr) leaves the context as it was:
+        laser_on tells."""
+        if origin is None:
+            lib().ParticleContextSetLaser(self.ctx, None)
+            return
+        mask = 0
+        for g in substrate_groups:
+            mask |= 1 << int(g)
+        v3 = lambda a: (C.c_double * 3)(*[float(q) for q in a])
+        cfg = DflLaser(v3(origin), v3(direction), v3(scan_vel), float(power), float(w), float(h), float(r_cut), float(eta_p),
+                       float(eta_s), mask)
+        lib().ParticleContextSetLaser(self.ctx, C.byref(cfg))
+
+    @property
+    def laser_on(self):
+        return bool(lib().ParticleContextLaserRate(self.ctx))
+
+    def _laser_ptr(self):
+        p = lib().ParticleContextLaserRate(self.ctx)
+        if not p:
+            raise RuntimeError("the laser is off: call set_laser first")
+        return p
+
+    def laser_step(self, dt):
+        """ParticleContextLaserStep: bin, attenuation, deposit and tally with the beam advanced by dt; no temperature update"""
+        self._laser_ptr()
+        lib().ParticleContextLaserStep(self.ctx, float(dt))
+
+    def laser_rate(self):
+        """W absorbed by every particle [P] in the last laser step"""
+        return d2h(self._laser_ptr(), self.P, np.float64)
+
+    def laser_tally(self):
+        """dict outside / absorbed_particles / scattered / substrate / reflected / missed of the last laser step (W)"""
+        t = DflLaserTally()
+        lib().ParticleContextLaserTally(self.ctx, C.byref(t))
+        return {k: float(getattr(t, k)) for k, _ in DflLaserTally._fields_}
+
+    def laser_columns(self):
+        """(transmitted power [n n], hit face record id [n n], -1: none) of the last laser step"""
+        self._laser_ptr()
+        tp, fp = vp(), vp()
+        n = int(lib().ParticleContextLaserColumns(self.ctx, C.byref(tp), C.byref(fp)))
+        return d2h(tp.value, n, np.float64), d2h(fp.value, n, np.int32)
+
     def arrays(self):
         """(coord, vel, acc) copied back from the device"""
         c = self.ctx.contents
@@ -506,6 +557,17 @@ class DflParticleFlowStats(C.Structure):
 class DflParticleHeat(C.Structure):
     _fields_ = [("cp_p", C.c_double), ("k_p", C.c_double), ("cp_f", C.c_double), ("k_f", C.c_double), ("T_init", C.c_double),
                 ("two_way", C.c_int32)]
+
+
+class DflLaser(C.Structure):
+    _fields_ = [("origin", C.c_double * 3), ("dir", C.c_double * 3), ("scan_vel", C.c_double * 3), ("power", C.c_double),
+                ("w", C.c_double), ("h", C.c_double), ("r_cut", C.c_double), ("eta_p", C.c_double), ("eta_s", C.c_double),
+                ("substrate_groups", C.c_int32)]
+
+
+class DflLaserTally(C.Structure):
+    _fields_ = [("outside", C.c_double), ("absorbed_particles", C.c_double), ("scattered", C.c_double),
+                ("substrate", C.c_double), ("reflected", C.c_double), ("missed", C.c_double)]
 
 
 class DflFluidCoupling(C.Structure):
@@ -642,6 +704,11 @@ def _declare(L):
     f("ParticleContextTemperature", vp, [C.POINTER(ParticleContext)]); f("ParticleContextHeatRate", vp, [C.POINTER(ParticleContext)])
     f("ParticleContextHeatStep", None, [C.POINTER(ParticleContext), vp]); f("ParticleContextHeatSource", None, [C.POINTER(ParticleContext), vp])
     f("DflMeshSetHeatSource", None, [C.POINTER(Mesh3D), vp])
+    f("ParticleContextSetLaser", None, [C.POINTER(ParticleContext), C.POINTER(DflLaser)])
+    f("ParticleContextLaserStep", None, [C.POINTER(ParticleContext), C.c_double])
+    f("ParticleContextLaserRate", vp, [C.POINTER(ParticleContext)])
+    f("ParticleContextLaserTally", None, [C.POINTER(ParticleContext), C.POINTER(DflLaserTally)])
+    f("ParticleContextLaserColumns", C.c_int32, [C.POINTER(ParticleContext), C.POINTER(vp), C.POINTER(vp)])
     f("DflParticlePendingEnergy", vp, [C.POINTER(ParticleContext)]); f("DflParticleConductionRate", vp, [C.POINTER(ParticleContext)])
     f("SolveFlowSystem", i32, [C.POINTER(Mesh3D), vp, vp, vp, C.POINTER(Matrix), vp, vp, vp, vp, i32, i32, vp, vp])
     f("DflTimeStep", i32, [C.POINTER(Mesh3D), vp, vp, vp, C.POINTER(Matrix), vp, vp, vp, vp, i32, i32, C.POINTER(ParticleContext),

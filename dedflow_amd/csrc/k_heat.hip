@@ -70,20 +70,23 @@ __global__ __launch_bounds__(BLK) void heat_conduction_kernel(I P, const T* __re
 }
 
 // The thermal update of particle i (include/dedflow.h): with a fluid state and a tet, convection implicit in T_i;
-// else conduction only.  q may be NULL (no contact conduction); w NULL or tet NULL: uncoupled.  POLY: m[i], r[i]
-template <bool POLY>
+// else conduction only.  q may be NULL (no contact conduction); w NULL or tet NULL: uncoupled.  POLY: m[i], r[i].  LASER:
+// the absorbed laser power p[i] joins q[i] (k_laser.hip); without it the arithmetic is that of a context with no laser
+template <bool POLY, bool LASER>
 __global__ __launch_bounds__(BLK) void heat_update_kernel(I P, const I* __restrict__ tet, const T* __restrict__ lambda,
                                                          const I* __restrict__ ien, const T* __restrict__ w, I N, T mass_,
                                                          T radius_, const T* __restrict__ m, const T* __restrict__ r,
                                                          const T* __restrict__ vel, T cp_p, T k_f, T rho_f, T mu_f, T pr13, T dt,
-                                                         const T* __restrict__ q, T* __restrict__ temp, T* __restrict__ rate,
-                                                         T* __restrict__ e) {
+                                                         const T* __restrict__ q, const T* __restrict__ p,
+                                                         T* __restrict__ temp, T* __restrict__ rate, T* __restrict__ e) {
     const long long i = (long long)blockIdx.x * BLK + threadIdx.x;
     if (i >= P) return;
     const double mass = POLY ? m[i] : mass_, radius = POLY ? r[i] : radius_;
     const double cap = mass * cp_p;
     const double ti = temp[i];
-    const double qc = q ? q[i] / cap : 0.0;
+    double qc;
+    if constexpr (LASER) qc = ((q ? q[i] : 0.0) + p[i]) / cap;
+    else qc = q ? q[i] / cap : 0.0;
     const int t = (w && tet) ? tet[i] : -1;
     double tn;
     if (t >= 0) {
@@ -151,11 +154,13 @@ void dfl_heat_conduction_grid(I P, const T* sorted, T radius, dfl_sizes sz, dfl_
 }
 
 void dfl_heat_update(I P, const I* tet, const T* lambda, const I* ien, const T* w, I N, T mass, T radius, const T* m, const T* r,
-                     const T* vel, T cp_p, T k_f, T rho_f, T mu_f, T pr13, T dt, const T* q, T* temp, T* rate, T* e, void* stream) {
+                     const T* vel, T cp_p, T k_f, T rho_f, T mu_f, T pr13, T dt, const T* q, const T* laser, T* temp, T* rate, T* e,
+                     void* stream) {
     if (P <= 0) return;
-    const auto kernel = m ? heat_update_kernel<true> : heat_update_kernel<false>;
+    const auto kernel = laser ? (m ? heat_update_kernel<true, true> : heat_update_kernel<false, true>)
+                              : (m ? heat_update_kernel<true, false> : heat_update_kernel<false, false>);
     kernel<<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, tet, lambda, ien, w, N, mass, radius, m, r, vel, cp_p, k_f, rho_f, mu_f, pr13,
-                                                  dt, q, temp, rate, e);
+                                                  dt, q, laser, temp, rate, e);
     DFL_LAUNCH_CHECK();
 }
 

@@ -189,6 +189,7 @@ static void grow(ParticleContext* ctx, index_type need) {
     free_capacity_scratch(f);
     alloc_capacity_scratch(f, cap);
     x->cap = cap;
+    DflLaserCapacityChanged(ctx); /* scratch and the per-step rate only: nothing to carry */
     if (f->out_on) ensure_spares(ctx);
 }
 
@@ -312,7 +313,7 @@ void ParticleContextRemove(ParticleContext* ctx) {
     pl.num = f->out.num_planes;
     memcpy(pl.plane, f->out.plane, sizeof pl.plane);
     const b32 pending = c && c->imp_time > 0.0;
-    const b32 heat_pending = DflHeatPending(ctx);
+    const b32 heat_pending = DflHeatPending(ctx) && x->heat->time > 0.0; /* the laser's substrate energy is per node */
     dfl_flow_flag(P, ArrayData(ParticleCTXDeviceCoord(ctx)), pl, c ? c->tet : NULL, by_mesh ? 1 : 0, f->keep,
                   pending || heat_pending ? f->rtet : NULL, s);
     dfl_exclusive_scan_i32(P, f->keep, f->newid, f->scan_tmp, f->scan_bytes, s);

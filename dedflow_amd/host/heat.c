@@ -38,6 +38,7 @@ static void clear_pending(HeatState* h, index_type P) {
 void ParticleContextSetHeat(ParticleContext* ctx, const DflParticleHeat* cfg) {
     ParticleExt* x = (ParticleExt*)ctx->ext;
     if (!cfg) {
+        DflLaserFree(ctx); /* the laser heats through the heat update: it goes with it */
         DflHeatFree(x->heat);
         x->heat = NULL;
         return;
@@ -91,6 +92,7 @@ void DflHeatCouplingChanged(ParticleContext* ctx) {
     const CoupleState* c = ((ParticleExt*)ctx->ext)->couple;
     if (c) node_buffers(h, c->N);
     clear_pending(h, ctx->num_particle);
+    DflLaserCouplingChanged(ctx); /* the substrate of the new mesh; a no-op without a laser */
 }
 
 void DflHeatStep(ParticleContext* ctx, const f64* w) {
@@ -98,6 +100,7 @@ void DflHeatStep(ParticleContext* ctx, const f64* w) {
     HeatState* h = x->heat;
     const index_type P = ctx->num_particle;
     hipStream_t s = DflStream();
+    if (x->laser) DflLaserStep(ctx, x->dt); /* the absorbed power of this sub-step, before the update that spends it */
     DflRangePush("ParticleContextHeatStep");
     int slot = DflProfileBegin(DFL_TAG_SMALL + 5);
     const b32 conduct = h->cfg.k_p > 0.0 && P > 0;
@@ -116,7 +119,7 @@ void DflHeatStep(ParticleContext* ctx, const f64* w) {
     const f64 pr13 = cbrt(h->cp_f * mu_f / h->k_f);
     dfl_heat_update(P, c ? c->tet : NULL, c ? c->lambda : NULL, c ? Mesh3DDevice(c->mesh)->ien : NULL, c ? w : NULL, c ? c->N : 0,
                     ParticleMass(ctx), ParticleRadius(ctx), x->mass, x->radius, ArrayData(ParticleCTXDeviceVel(ctx)), h->cfg.cp_p,
-                    h->k_f, rho_f, mu_f, pr13, x->dt, conduct ? h->q : NULL, h->temp, h->rate, h->e, s);
+                    h->k_f, rho_f, mu_f, pr13, x->dt, conduct ? h->q : NULL, ParticleContextLaserRate(ctx), h->temp, h->rate, h->e, s);
     if (c) h->time += x->dt;
     DflProfileEnd(slot);
     DflRangePop();
@@ -135,7 +138,7 @@ void ParticleContextHeatStep(ParticleContext* ctx, const f64* w) {
 
 b32 DflHeatPending(const ParticleContext* ctx) {
     const HeatState* h = heat(ctx);
-    return h && ((ParticleExt*)ctx->ext)->couple && h->time > 0.0;
+    return h && ((ParticleExt*)ctx->ext)->couple && (h->time > 0.0 || DflLaserPending(ctx));
 }
 
 void ParticleContextHeatSource(ParticleContext* ctx, f64* q) {
@@ -147,6 +150,7 @@ void ParticleContextHeatSource(ParticleContext* ctx, f64* q) {
     hipStream_t s = DflStream();
     if (h->time <= 0.0) {
         HIPGUARD(hipMemsetAsync(q, 0, (size_t)c->N * sizeof(f64), s));
+        DflLaserAddSource(ctx, q); /* the laser's substrate power of bare laser steps or uncoupled sub-steps */
         return;
     }
     DflRangePush("ParticleContextHeatSource");
@@ -161,6 +165,7 @@ void ParticleContextHeatSource(ParticleContext* ctx, f64* q) {
     }
     HIPGUARD(hipMemsetAsync(h->e, 0, (size_t)(P > 0 ? P : 1) * sizeof(f64), s));
     h->time = 0.0;
+    DflLaserAddSource(ctx, q); /* + the substrate's laser energy / its time; a no-op without a laser */
     DflRangePop();
 }
 

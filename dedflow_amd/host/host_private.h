@@ -118,6 +118,7 @@ typedef struct ParticleExt {
     b32 in_sizes;                               /* ParticleContextSetInflowSizes was called: inserted radii in [in_r_lo, in_r_hi) */
     f64 in_r_lo, in_r_hi;
     struct HeatState* heat;                     /* particle heat transfer (host/heat.c), NULL when off */
+    struct LaserState* laser;                   /* laser energy deposition (host/laser.c), NULL when off; needs heat */
 } ParticleExt;
 /* the per-particle sizes of the kernels (all NULL, rmax 0 while x->radius == NULL: one size) */
 dfl_sizes DflSizes(const ParticleExt* x);
@@ -180,6 +181,17 @@ const f64* DflParticleConductionRate(const ParticleContext* ctx); /* device [P]:
 b32 DflParticleHeatTwoWay(const ParticleContext* ctx);
 f64* DflParticlePendingHeatSource(ParticleContext* ctx); /* the pending source in the context's own [N] buffer, or NULL */
 const f64* DflMeshHeatSource(const Mesh3D* mesh);
+/* laser energy deposition (host/laser.c); every call below is a no-op on a context without a laser */
+struct LaserState;
+void DflLaserFree(ParticleContext* ctx);            /* off: frees the state */
+void DflLaserStep(ParticleContext* ctx, f64 dt);    /* one laser step (the laser must be on) */
+void DflLaserCouplingChanged(ParticleContext* ctx); /* SetFluidCoupling: the substrate list of the new mesh, nothing pending */
+void DflLaserCapacityChanged(ParticleContext* ctx); /* the per-particle buffers for the context's new capacity */
+void DflLaserCopy(ParticleContext* dst, const ParticleContext* src);
+b32 DflLaserPending(const ParticleContext* ctx);    /* substrate energy accumulated since the last heat source */
+void DflLaserAddSource(ParticleContext* ctx, f64* q); /* q[N] += that energy / its time; clears it */
+/* the boundary faces of the masked groups as wall records in group order (host/walls.c; synchronises; free() both) */
+dfl_wall_tri* DflMeshBoundaryTris(Mesh3D* mesh, index_type group_mask, index_type* nf_out, f64 lo[3], f64 hi[3], f64** edges_out);
 struct FlowState;
 void DflFlowFree(struct FlowState* f);
 struct WallState;

@@ -50,6 +50,7 @@ void ParticleContextDestroy(ParticleContext* ctx) {
         ParticleContextSetFriction(ctx, NULL);
         DflFlowFree(x->flow);
         ParticleContextSetSizes(ctx, NULL, NULL);
+        DflLaserFree(ctx);
         DflHeatFree(x->heat);
         CdamFreeHost(x, SIZE_OF(ParticleExt));
     }
@@ -68,6 +69,7 @@ void ParticleContextCopy(ParticleContext* dst, const ParticleContext* src) {
     ParticleExt* xd = (ParticleExt*)dst->ext;
     if (!xs->radius) {
         if (xd->radius) ParticleContextSetSizes(dst, NULL, NULL);
+        DflLaserCopy(dst, src);
         return;
     }
     const index_type P = src->num_particle;
@@ -80,6 +82,7 @@ void ParticleContextCopy(ParticleContext* dst, const ParticleContext* src) {
     ParticleContextSetSizes(dst, h, h + P);
     if (xd->radius && xs->rmax > xd->rmax) xd->rmax = xs->rmax;
     free(h);
+    DflLaserCopy(dst, src); /* the configuration and the elapsed scan time (after the sizes: h >= 2 Rmax) */
 }
 void ParticleContextUpdateHost(ParticleContext* ctx) {
     for (int k = 0; k < 3; ++k) ArrayCopy(ctx->h_arr[k], ctx->d_arr[k], D2H);

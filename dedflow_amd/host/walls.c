@@ -207,18 +207,11 @@ static void plane_ids(const dfl_wall_tri* tri, index_type nf, f64 tol, index_typ
     free(key);
 }
 
-void ParticleContextSetWallMesh(ParticleContext* ctx, Mesh3D* mesh, index_type group_mask) {
-    ParticleExt* x = (ParticleExt*)ctx->ext;
-    DflWallsFree(x->walls);
-    x->walls = NULL;
-    x->sort_valid = FALSE;        /* the last cell sort was on the other grid */
-    DflFrictionClearHistory(ctx); /* the keys of the wall contacts change meaning */
-    if (!mesh) return;
+/* the boundary faces of the masked groups as packed records, in group order (the record id), from host copies of what the
+ * device holds (synchronises); also the bounding box of the mesh nodes and, when asked for, the 3 nf edge lengths.  The
+ * caller frees both with free().  Shared with the laser's substrate list (host/laser.c) */
+dfl_wall_tri* DflMeshBoundaryTris(Mesh3D* mesh, index_type group_mask, index_type* nf_out, f64 lo[3], f64 hi[3], f64** edges_out) {
     const index_type N = Mesh3DNumNode(mesh), T = Mesh3DNumTet(mesh);
-    if (N <= 0 || T <= 0) {
-        fprintf(stderr, "ParticleContextSetWallMesh: the mesh has no tets; the walls stay the unit box\n");
-        return;
-    }
     const index_type nb = mesh->num_bound;
     const index_type nfall = nb > 0 ? mesh->bound_elem_offset[nb] : 0;
     /* host copies of what the device holds */
@@ -234,31 +227,26 @@ void ParticleContextSetWallMesh(ParticleContext* ctx, Mesh3D* mesh, index_type g
         HIPGUARD(hipMemcpy(f2e, mesh->bound_f2e, (size_t)nfall * sizeof(index_type), D2H));
         HIPGUARD(hipMemcpy(forn, mesh->bound_forn, (size_t)nfall * sizeof(index_type), D2H));
     }
-    WallState* w = (WallState*)CdamMallocHost(SIZE_OF(WallState));
-    memset(w, 0, sizeof *w);
     for (int d = 0; d < 3; ++d) {
-        w->lo[d] = HUGE_VAL;
-        w->hi[d] = -HUGE_VAL;
+        lo[d] = HUGE_VAL;
+        hi[d] = -HUGE_VAL;
     }
     for (index_type a = 0; a < N; ++a)
         for (int d = 0; d < 3; ++d) {
             const f64 c = xg[3 * (size_t)a + d];
-            if (c < w->lo[d]) w->lo[d] = c;
-            if (c > w->hi[d]) w->hi[d] = c;
+            if (c < lo[d]) lo[d] = c;
+            if (c > hi[d]) hi[d] = c;
         }
-    w->scale = sqrt((w->hi[0] - w->lo[0]) * (w->hi[0] - w->lo[0]) + (w->hi[1] - w->lo[1]) * (w->hi[1] - w->lo[1]) +
-                    (w->hi[2] - w->lo[2]) * (w->hi[2] - w->lo[2]));
     index_type nf = 0;
     for (index_type g = 0; g < nb && g < 31; ++g)
         if (group_mask >> g & 1) nf += mesh->bound_elem_offset[g + 1] - mesh->bound_elem_offset[g];
-    w->nf = nf;
-    w->h_tri = (dfl_wall_tri*)calloc((size_t)(nf > 0 ? nf : 1), sizeof(dfl_wall_tri));
+    dfl_wall_tri* tri = (dfl_wall_tri*)calloc((size_t)(nf > 0 ? nf : 1), sizeof(dfl_wall_tri));
     f64* edges = (f64*)malloc((size_t)(nf > 0 ? 3 * nf : 1) * sizeof(f64));
     index_type id = 0;
     for (index_type g = 0; g < nb && g < 31; ++g) {
         if (!(group_mask >> g & 1)) continue;
         for (index_type e = mesh->bound_elem_offset[g]; e < mesh->bound_elem_offset[g + 1]; ++e, ++id) {
-            dfl_wall_tri* r = &w->h_tri[id];
+            dfl_wall_tri* r = &tri[id];
             const index_type* tv = ien + 4 * (size_t)f2e[e];
             const index_type opp = tv[forn[e]];
             for (int k = 0, j = 0; k < 4; ++k) {
@@ -286,6 +274,36 @@ void ParticleContextSetWallMesh(ParticleContext* ctx, Mesh3D* mesh, index_type g
             }
         }
     }
+    free(forn);
+    free(f2e);
+    free(ien);
+    free(xg);
+    if (edges_out) *edges_out = edges;
+    else free(edges);
+    *nf_out = nf;
+    return tri;
+}
+
+void ParticleContextSetWallMesh(ParticleContext* ctx, Mesh3D* mesh, index_type group_mask) {
+    ParticleExt* x = (ParticleExt*)ctx->ext;
+    DflWallsFree(x->walls);
+    x->walls = NULL;
+    x->sort_valid = FALSE;        /* the last cell sort was on the other grid */
+    DflFrictionClearHistory(ctx); /* the keys of the wall contacts change meaning */
+    if (!mesh) return;
+    const index_type N = Mesh3DNumNode(mesh), T = Mesh3DNumTet(mesh);
+    if (N <= 0 || T <= 0) {
+        fprintf(stderr, "ParticleContextSetWallMesh: the mesh has no tets; the walls stay the unit box\n");
+        return;
+    }
+    WallState* w = (WallState*)CdamMallocHost(SIZE_OF(WallState));
+    memset(w, 0, sizeof *w);
+    f64* edges = NULL;
+    index_type nf = 0;
+    w->h_tri = DflMeshBoundaryTris(mesh, group_mask, &nf, w->lo, w->hi, &edges);
+    w->nf = nf;
+    w->scale = sqrt((w->hi[0] - w->lo[0]) * (w->hi[0] - w->lo[0]) + (w->hi[1] - w->lo[1]) * (w->hi[1] - w->lo[1]) +
+                    (w->hi[2] - w->lo[2]) * (w->hi[2] - w->lo[2]));
     if (nf > 0) {
         qsort(edges, 3 * (size_t)nf, sizeof(f64), cmp_f64);
         w->edge = edges[3 * (size_t)nf / 2];
@@ -293,10 +311,6 @@ void ParticleContextSetWallMesh(ParticleContext* ctx, Mesh3D* mesh, index_type g
         w->edge = w->scale;
     }
     free(edges);
-    free(forn);
-    free(f2e);
-    free(ien);
-    free(xg);
     w->tri = (dfl_wall_tri*)CdamMallocDevice((ptrdiff_t)(nf > 0 ? nf : 1) * SIZE_OF(dfl_wall_tri));
     HIPGUARD(hipMemcpy(w->tri, w->h_tri, (size_t)(nf > 0 ? nf : 1) * sizeof(dfl_wall_tri), H2D));
     index_type* h_plane = (index_type*)malloc((size_t)(nf > 0 ? nf : 1) * sizeof(index_type));

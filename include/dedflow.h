@@ -1069,6 +1069,77 @@ void ParticleContextHeatStep(ParticleContext* ctx, const f64* w);/* one thermal 
 void ParticleContextHeatSource(ParticleContext* ctx, f64* q);
 void DflMeshSetHeatSource(Mesh3D* mesh, const f64* q);           /* device [N], NULL = none; must outlive registration */
 
+/* ---- laser energy deposition (build-defined; opt-in) -------------------------------------------------------------------
+ * The reference has no source term in its T equation.  A context that never calls ParticleContextSetLaser with a
+ * configuration computes bit for bit what it computes without this section, through the same launches.  The laser needs
+ * particle heat on (ParticleContextSetHeat).  One GPU only.
+ *   beam       collimated and Gaussian: a point `origin` on the axis, the direction `dir` (normalised by the library:
+ *              dir / sqrt((d0 d0 + d1 d1) + d2 d2)), power P, 1/e^2 radius w: I(rho) = 2P / (pi w^2) exp(-2 rho^2 / w^2)
+ *              at distance rho from the axis.  The axis translates with scan_vel: every laser step first advances the
+ *              elapsed time, t += dt (t = 0 at the call that set the laser), and then uses o = origin + scan_vel t, the
+ *              axis at the END of the sub-step, where the sub-step's integration has put the particles.
+ *   frame      k = the coordinate axis least aligned with dir (smallest |dir_k|, the lowest k on a tie);
+ *              e1 = (a_k - dir_k dir) / |a_k - dir_k dir|, e2 = dir x e1.  A point x has transverse coordinates
+ *              u = (x - o) . e1, v = (x - o) . e2 and depth s = (x - o) . dir, every dot product evaluated as
+ *              (d0 a0 + d1 a1) + d2 a2 in IEEE double without fused multiply-add.
+ *   columns    n x n square columns of edge h centred on the axis, n = 2 ceil(r_cut / h) <= 256, h >= 2 Rmax; column
+ *              (i, j), id i + n j, holds floor(u / h) = i - n/2 and floor(v / h) = j - n/2.  Its power is
+ *              P_c = ((P / 4) gx[i]) gy[j], gx[i] = erf(sqrt2 x_{i+1} / w) - erf(sqrt2 x_i / w), x_i = (i - n/2) h, gy = gx,
+ *              computed on the host with the C library's erf.  P - sum_c P_c falls outside the grid.
+ *   shadowing  Beer-Lambert per column.  A particle belongs to the column holding the projection of its centre; outside
+ *              the grid it is unlit.  Within a column the particles are ordered by depth s ascending, ties by ascending
+ *              id.  With A_i = pi r_i^2, a = h^2: p_in = P_c exp(-sum_{j before i} A_j / a); particle i intercepts
+ *              p_in (1 - exp(-A_i / a)), evaluated as -expm1(-A_i / a), and absorbs the fraction eta_p of it
+ *              (laser_rate_i, W); the rest of what it intercepts is scattered and leaves the beam.  A particle deeper
+ *              than its column's substrate hit (s > s_hit) is unlit and shadows nothing.
+ *   substrate  on a coupled context with substrate_groups != 0: the candidate faces are the boundary faces of the coupled
+ *              mesh in those groups (bit g = group g, the records of ParticleContextSetWallMesh) whose inward normal
+ *              opposes the beam, n . dir < 0.  Each column's centre ray ((i - n/2 + 1/2) h, (j - n/2 + 1/2) h) is
+ *              deposited on the first candidate face whose projection holds it (edges included): the smallest depth
+ *              of the hit point, depths compared on a grid of 2^-40 of the candidates' depth range, ties by the lowest
+ *              face id -- so a ray through a shared edge or vertex has exactly one owner.  The column's transmitted power
+ *              T_c = P_c exp(-sum A_j / a) splits into eta_s T_c absorbed and (1 - eta_s) T_c reflected; the absorbed part
+ *              goes to the face's three nodes by the barycentric weights of the hit point (nodal power in W, the unit of
+ *              DflMeshSetHeatSource).  A column without a hit (uncoupled context, mask 0, a ray that leaves through an
+ *              open group) books T_c as missed.  The face list is a snapshot of the mesh, built once per (coupled mesh,
+ *              mask, direction); at most 2^24 candidate faces.
+ *   tally      DflLaserTally holds the power of the last laser step in W; its six entries sum to P up to rounding.
+ *   time step  a laser step runs inside every thermal sub-step (ParticleContextUpdate, ParticleContextFluidStep, the DEM
+ *              sub-steps of DflTimeStep, ParticleContextHeatStep) with the context's dt, before the heat update, which sees
+ *              q_i + laser_rate_i where it sees q_i without a laser.  The substrate's nodal energy accumulates over the
+ *              steps (+= dt power); ParticleContextHeatSource adds energy / (time of those steps) to the q it returns
+ *              and clears it, so the two-way path of DflTimeStep puts the laser on the T rows.  ParticleContextLaserStep
+ *              is the bare step (bin, attenuation, deposit, tally; no temperature update), also with zero particles.
+ *   travel     ParticleContextCopy carries the configuration and the elapsed scan time (dst becomes what src is; substrate
+ *              energy still pending on src is not copied: dst starts with none); laser_rate is recomputed by every step
+ *              and is not carried by Remove / Add.  ParticleContextSetFluidCoupling rebuilds the substrate list for the
+ *              new mesh (none when uncoupled: every column then books its power as missed) and drops pending energy.
+ *   limits     h >= 2 Rmax is checked at ParticleContextSetLaser only: sizes set later (ParticleContextSetSizes,
+ *              SetInflowSizes) are the caller's to keep below h / 2; a larger particle is still binned by its centre
+ *              and its A / a may exceed 1.  Non-finite particle coordinates are not supported (the depth order of that
+ *              particle's column is then undefined; nothing is written out of bounds).
+ * Column runs longer than the column kernel's LDS cap (512 particles) take a slower path with the same result.  A step
+ * allocates nothing and does not wait for the device; the state is sized at ParticleContextSetLaser and again when the
+ * coupling or the particle capacity changes; only ParticleContextLaserTally copies to the host. */
+typedef struct DflLaser {
+    f64 origin[3], dir[3], scan_vel[3];
+    f64 power, w, h, r_cut;        /* P (W), 1/e^2 radius, column edge, cut-off radius of the column grid */
+    f64 eta_p, eta_s;              /* absorptivity of the powder / of the substrate, in [0, 1] */
+    index_type substrate_groups;   /* boundary groups of the coupled mesh that receive the transmitted beam; 0: none */
+} DflLaser;
+typedef struct DflLaserTally {
+    f64 outside, absorbed_particles, scattered, substrate, reflected, missed;
+} DflLaserTally;
+/* the configuration is copied; NULL: off, frees the state.  Reported on stderr, context unchanged: heat off, a zero dir,
+ * non-finite or non-positive w, h, r_cut, a negative power, an eta outside [0, 1], n > 256, h < 2 Rmax */
+void ParticleContextSetLaser(ParticleContext* ctx, const DflLaser* cfg);
+void ParticleContextLaserStep(ParticleContext* ctx, f64 dt);
+const f64* ParticleContextLaserRate(const ParticleContext* ctx); /* device [P] by id: W absorbed in the last step; NULL when off */
+void ParticleContextLaserTally(ParticleContext* ctx, DflLaserTally* out); /* the last step's (synchronises); zeros when off */
+/* device [n n], read-only: every column's transmitted power and the record id of the face it hit (-1: none); returns n n
+ * (0 and NULL pointers when off) */
+index_type ParticleContextLaserColumns(const ParticleContext* ctx, const f64** transmitted, const index_type** face);
+
 #ifdef __cplusplus
 }
 #endif

@@ -674,7 +674,8 @@ void dfl_walls_forces(dfl_index P, const dfl_value* sorted, const dfl_value* sor
  *                              ([6N], T = w[5N + node]) for a particle with tet[i] >= 0, conduction rate q (may be NULL);
  *                              w or tet NULL: conduction only.  m, r: per-particle mass and radius, or NULL for the scalars.
  *                              pr13 = Pr^(1/3).  Writes temp, rate = C (T' - T) / dt (0 when dt == 0), e += the energy the
- *                              fluid gave
+ *                              fluid gave.  laser (may be NULL): W absorbed by every particle, added to q; NULL runs the
+ *                              kernel without it, the arithmetic of a context that has no laser
  *    dfl_heat_fill             temp = t_init, rate = e = 0 for the particles [first, first + count) */
 void dfl_heat_gather(dfl_index P, const dfl_index* order, const dfl_value* temp, dfl_value* sorted_t, void* stream);
 void dfl_heat_conduction(dfl_index P, const dfl_value* sorted, dfl_value radius, dfl_sizes sz, dfl_value cell, dfl_index ncell,
@@ -686,9 +687,52 @@ void dfl_heat_conduction_grid(dfl_index P, const dfl_value* sorted, dfl_value ra
 void dfl_heat_update(dfl_index P, const dfl_index* tet, const dfl_value* lambda, const dfl_index* ien, const dfl_value* w,
                      dfl_index N, dfl_value mass, dfl_value radius, const dfl_value* m, const dfl_value* r, const dfl_value* vel,
                      dfl_value cp_p, dfl_value k_f, dfl_value rho_f, dfl_value mu_f, dfl_value pr13, dfl_value dt,
-                     const dfl_value* q, dfl_value* temp, dfl_value* rate, dfl_value* e, void* stream);
+                     const dfl_value* q, const dfl_value* laser, dfl_value* temp, dfl_value* rate, dfl_value* e, void* stream);
 void dfl_heat_fill(dfl_index first, dfl_index count, dfl_value t_init, dfl_value* temp, dfl_value* rate, dfl_value* e,
                    void* stream);
+
+/* ---- laser energy deposition (build-defined, opt-in; csrc/k_laser.hip, model in include/dedflow.h)
+ * One laser step = hit (substrate only), bin + dfl_dem_sort_binned on the laser's own scratch, columns, deposit, tally; all
+ * on `stream`, nothing allocated or synchronised, no floating-point atomics, every output written once.
+ *  dfl_laser_beam        the beam of one step: origin o, frame (e1, e2, dir), column edge h, a = h h, n columns per side
+ *    dfl_laser_column_cap   entries of a column run the column kernel sorts in LDS; longer runs take its fallback
+ *    dfl_laser_bin          cell_of[i] = column of particle i, or n n + (i >> DFL_LASER_OUTSIDE_SHIFT) outside the grid (and
+ *                           then rate[i] = 0): n n + ((P - 1) >> DFL_LASER_OUTSIDE_SHIFT) + 1 bins; rank, count as the bin
+ *                           pass of dfl_walls_build_cells
+ *    dfl_laser_hit          colkey[n n] <- all ones, then per column the minimum over the candidate faces tri[0, nf) whose
+ *                           projection holds the column centre of floor((depth - s_lo) scale) << 24 | face (nf <= 2^24,
+ *                           (depth - s_lo) scale in [0, 2^40))
+ *    dfl_laser_columns      per column the run cell_start[c] .. cell_start[c+1] of order / sorted / sorted_r (NULL: every
+ *                           particle has `radius`) by (depth, id): rate[id], col_T[c] = transmitted power, col_face[c] = id
+ *                           of the hit face's record (-1: none), part[6][n n] = column power, absorbed, scattered,
+ *                           substrate, reflected, missed.  gw[2n] = the column weights gx, gy.  k_tau / k_id [P]: scratch
+ *                           of runs longer than the cap.  P <= 0: no particles, cell_start is not read
+ *    dfl_laser_deposit      per substrate node a in [0, ns) with faces sface[soff[a] .. soff[a+1]) = 4 face + local
+ *                           vertex: power[a] = sum over the columns its faces won of eta_s col_T w_vertex;
+ *                           energy[a] += dt power[a]
+ *    dfl_laser_tally        tally[6] = power - sum column power, and the sums of the other five partials (fixed tree)
+ *    dfl_laser_source_add   q[snode[a]] += energy[a] inv_time; energy[a] = 0 */
+#define DFL_LASER_OUTSIDE_SHIFT 3
+typedef struct dfl_laser_beam {
+    dfl_value o[3], e1[3], e2[3], dir[3];
+    dfl_value h, area;
+    dfl_index n;
+} dfl_laser_beam;
+dfl_index dfl_laser_column_cap(void);
+void dfl_laser_bin(dfl_index P, const dfl_value* coord, dfl_laser_beam b, dfl_index* cell_of, dfl_index* rank, dfl_index* count,
+                   dfl_value* rate, void* stream);
+void dfl_laser_hit(dfl_index nf, const dfl_wall_tri* tri, dfl_laser_beam b, dfl_value s_lo, dfl_value scale, uint64_t* colkey,
+                   void* stream);
+void dfl_laser_columns(dfl_index P, dfl_laser_beam b, dfl_value power, dfl_value eta_p, dfl_value eta_s, const dfl_value* gw,
+                       const dfl_index* cell_start, const dfl_index* order, const dfl_value* sorted, const dfl_value* sorted_r,
+                       dfl_value radius, const dfl_wall_tri* tri, const uint64_t* colkey, dfl_value* k_tau, dfl_index* k_id,
+                       dfl_value* rate, dfl_value* col_T, dfl_index* col_face, dfl_value* part, void* stream);
+void dfl_laser_deposit(dfl_index ns, const dfl_index* soff, const dfl_index* sface, const dfl_wall_tri* tri, dfl_laser_beam b,
+                       dfl_value eta_s, dfl_value dt, const uint64_t* colkey, const dfl_value* col_T, dfl_value* power,
+                       dfl_value* energy, void* stream);
+void dfl_laser_tally(dfl_index ncol, dfl_value power, const dfl_value* part, dfl_value* tally, void* stream);
+void dfl_laser_source_add(dfl_index ns, const dfl_index* snode, dfl_value inv_time, dfl_value* energy, dfl_value* q,
+                          void* stream);
 
 /* ---- scalar transport (host/scalar.c, csrc/k_scalar.hip) ------------------------------------------------------------
  * dfl_assemble_scalar_jacobian: the level-set and temperature Jacobians (d R_phi / d dphi, d R_T / d dT) over the nodal
