@@ -302,21 +302,17 @@ void dfl_couple_locate(I P, const I* order, const T* coord, const T* xg, const I
 }
 
 void dfl_couple_fluid_step(I P, const I* order, const I* tet, const T* lambda, const I* ien, const T* w, T mass, T radius,
-                           T rho_f, T mu_f, const T* gravity, T dt, T* coord, T* vel, T* acc, T* imp, void* stream) {
+                           const T* mass_i, const T* radius_i, T rho_f, T mu_f, const T* gravity, T dt, T* coord, T* vel, T* acc,
+                           T* imp, void* stream) {
     if (P <= 0) return;
-    couple_fluid_kernel<false><<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, order, tet, lambda, ien, w, mass, radius, rho_f, mu_f,
-                                                                      gravity[0], gravity[1], gravity[2], dt, coord, vel, acc, imp,
-                                                                      nullptr, nullptr);
-    DFL_LAUNCH_CHECK();
-}
-
-void dfl_couple_fluid_step_sizes(I P, const I* order, const I* tet, const T* lambda, const I* ien, const T* w, const T* mass,
-                                 const T* radius, T rho_f, T mu_f, const T* gravity, T dt, T* coord, T* vel, T* acc, T* imp,
-                                 void* stream) {
-    if (P <= 0) return;
-    couple_fluid_kernel<true><<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, order, tet, lambda, ien, w, 0.0, 0.0, rho_f, mu_f,
-                                                                     gravity[0], gravity[1], gravity[2], dt, coord, vel, acc, imp,
-                                                                     mass, radius);
+    if (radius_i)
+        couple_fluid_kernel<true><<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, order, tet, lambda, ien, w, 0.0, 0.0, rho_f, mu_f,
+                                                                         gravity[0], gravity[1], gravity[2], dt, coord, vel, acc,
+                                                                         imp, mass_i, radius_i);
+    else
+        couple_fluid_kernel<false><<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, order, tet, lambda, ien, w, mass, radius, rho_f, mu_f,
+                                                                          gravity[0], gravity[1], gravity[2], dt, coord, vel, acc,
+                                                                          imp, nullptr, nullptr);
     DFL_LAUNCH_CHECK();
 }
 

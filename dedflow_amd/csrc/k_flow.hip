@@ -67,13 +67,13 @@ __global__ __launch_bounds__(BLK) void flow_compact_kernel(I P, const I* __restr
     const int i = blockIdx.x * BLK + threadIdx.x;
     if (i >= P || !keep[i]) return;
     const size_t j = (size_t)newid[i];
-    for (int a = 0; a < f.n3; ++a) copy3(f.src3[a], f.dst3[a], (size_t)i, j);
-    for (int a = 0; a < f.n1; ++a) f.dst1[a][j] = f.src1[a][i];
-    f.tag_dst[j] = f.tag_src[i];
-    if (f.tet_src) {
-        f.tet_dst[j] = f.tet_src[i];
-        const double4 l = reinterpret_cast<const double4*>(f.lambda_src)[i];
-        reinterpret_cast<double4*>(f.lambda_dst)[j] = l;
+    int a = f.first[0];
+    for (; a < f.first[1]; ++a) static_cast<I*>(f.pair[a].dst)[j] = static_cast<const I*>(f.pair[a].src)[i];
+    for (; a < f.first[2]; ++a) static_cast<uint64_t*>(f.pair[a].dst)[j] = static_cast<const uint64_t*>(f.pair[a].src)[i];
+    for (; a < f.first[3]; ++a) copy3(static_cast<const T*>(f.pair[a].src), static_cast<T*>(f.pair[a].dst), (size_t)i, j);
+    for (; a < f.first[4]; ++a) {
+        const double4 l = static_cast<const double4*>(f.pair[a].src)[i];
+        static_cast<double4*>(f.pair[a].dst)[j] = l;
     }
     if (f.hrow_src) {
         const int n = f.hcount_src[i];
@@ -205,21 +205,15 @@ void dfl_flow_compact(I P, const I* keep, const I* newid, dfl_flow_fields f, voi
     DFL_LAUNCH_CHECK();
 }
 
-void dfl_inflow_block(I P, const T* coord, dfl_inlet in, T radius, I* blocked, void* stream) {
+void dfl_inflow_block(I P, const T* coord, dfl_inlet in, T radius, const T* radius_i, T r_lo, T r_hi, I* blocked, void* stream) {
     const long long nslot = (long long)in.nu * in.nv;
     if (nslot <= 0) return;
     DFL_GUARD(hipMemsetAsync(blocked, 0, (size_t)nslot * sizeof(I), S(stream)));
     if (P <= 0) return;
-    inflow_block_kernel<false><<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, coord, in, radius, blocked, nullptr, 0.0, 0.0);
-    DFL_LAUNCH_CHECK();
-}
-
-void dfl_inflow_block_sizes(I P, const T* coord, dfl_inlet in, const T* radius, T r_lo, T r_hi, I* blocked, void* stream) {
-    const long long nslot = (long long)in.nu * in.nv;
-    if (nslot <= 0) return;
-    DFL_GUARD(hipMemsetAsync(blocked, 0, (size_t)nslot * sizeof(I), S(stream)));
-    if (P <= 0) return;
-    inflow_block_kernel<true><<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, coord, in, 0.0, blocked, radius, r_lo, r_hi);
+    if (radius_i)
+        inflow_block_kernel<true><<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, coord, in, 0.0, blocked, radius_i, r_lo, r_hi);
+    else
+        inflow_block_kernel<false><<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, coord, in, radius, blocked, nullptr, 0.0, 0.0);
     DFL_LAUNCH_CHECK();
 }
 
@@ -241,32 +235,24 @@ void dfl_inflow_select(dfl_inlet in, const I* blocked, uint64_t* key, uint64_t* 
 }
 
 void dfl_inflow_append(I P, I want, dfl_inlet in, const uint64_t* key_sorted, const I* slot_sorted, int64_t first_tag, T* coord,
-                       T* vel, T* acc, int64_t* tag, T* omega, T* alpha, I* hist_count, I* tet, T* lambda, T* imp, I* count,
-                       void* stream) {
+                       T* vel, T* acc, int64_t* tag, T* omega, T* alpha, I* hist_count, I* tet, T* lambda, T* imp, T* radius_i,
+                       T* mass_i, T r_lo, T r_hi, T r0, T m0, I* count, void* stream) {
     const I nslot = in.nu * in.nv;
     if (want > nslot) want = nslot;
     if (want <= 0) {
         DFL_GUARD(hipMemsetAsync(count, 0, sizeof(I), S(stream)));
         return;
     }
-    inflow_append_kernel<false><<<ceil_div(want, BLK), BLK, 0, S(stream)>>>(P, want, in, key_sorted, slot_sorted, first_tag, coord,
-                                                                           vel, acc, tag, omega, alpha, hist_count, tet, lambda,
-                                                                           imp, count, nullptr, nullptr, 0.0, 0.0, 1.0, 1.0);
-    DFL_LAUNCH_CHECK();
-}
-
-void dfl_inflow_append_sizes(I P, I want, dfl_inlet in, const uint64_t* key_sorted, const I* slot_sorted, int64_t first_tag,
-                             T* coord, T* vel, T* acc, int64_t* tag, T* omega, T* alpha, I* hist_count, I* tet, T* lambda, T* imp,
-                             T* radius, T* mass, T r_lo, T r_hi, T r0, T m0, I* count, void* stream) {
-    const I nslot = in.nu * in.nv;
-    if (want > nslot) want = nslot;
-    if (want <= 0) {
-        DFL_GUARD(hipMemsetAsync(count, 0, sizeof(I), S(stream)));
-        return;
-    }
-    inflow_append_kernel<true><<<ceil_div(want, BLK), BLK, 0, S(stream)>>>(P, want, in, key_sorted, slot_sorted, first_tag, coord,
-                                                                          vel, acc, tag, omega, alpha, hist_count, tet, lambda,
-                                                                          imp, count, radius, mass, r_lo, r_hi, r0, m0);
+    if (radius_i)
+        inflow_append_kernel<true><<<ceil_div(want, BLK), BLK, 0, S(stream)>>>(P, want, in, key_sorted, slot_sorted, first_tag,
+                                                                              coord, vel, acc, tag, omega, alpha, hist_count, tet,
+                                                                              lambda, imp, count, radius_i, mass_i, r_lo, r_hi, r0,
+                                                                              m0);
+    else
+        inflow_append_kernel<false><<<ceil_div(want, BLK), BLK, 0, S(stream)>>>(P, want, in, key_sorted, slot_sorted, first_tag,
+                                                                               coord, vel, acc, tag, omega, alpha, hist_count, tet,
+                                                                               lambda, imp, count, nullptr, nullptr, 0.0, 0.0, 1.0,
+                                                                               1.0);
     DFL_LAUNCH_CHECK();
 }
 

@@ -17,15 +17,16 @@
 
 static CoupleState* state(const ParticleContext* ctx) { return ((ParticleExt*)ctx->ext)->couple; }
 
-void DflCoupleFree(CoupleState* c) {
+void DflCoupleFree(ParticleContext* ctx) {
+    CoupleState* c = state(ctx);
     if (!c) return;
     HIPGUARD(hipStreamSynchronize(DflStream()));
+    DflParticleFieldsFree(ctx, DFL_PF_COUPLE);
     CdamFreeDevice(c->vrow, 0); CdamFreeDevice(c->vcol, 0); CdamFreeDevice(c->nbr, 0); CdamFreeDevice(c->seed, 0);
-    CdamFreeDevice(c->tet, 0); CdamFreeDevice(c->lost, 0); CdamFreeDevice(c->lambda, 0); CdamFreeDevice(c->imp, 0);
-    CdamFreeDevice(c->tcount, 0); CdamFreeDevice(c->tstart, 0); CdamFreeDevice(c->rank, 0); CdamFreeDevice(c->slot, 0);
-    CdamFreeDevice(c->members, 0); CdamFreeDevice(c->scan_tmp, 0); CdamFreeDevice(c->load, 0);
-    CdamFreeDevice(c->rem_load, 0); CdamFreeDevice(c->rem_tmp, 0);
+    CdamFreeDevice(c->lost, 0); CdamFreeDevice(c->tcount, 0); CdamFreeDevice(c->tstart, 0); CdamFreeDevice(c->scan_tmp, 0);
+    CdamFreeDevice(c->load, 0); CdamFreeDevice(c->rem_load, 0); CdamFreeDevice(c->rem_tmp, 0);
     CdamFreeHost(c, SIZE_OF(CoupleState));
+    ((ParticleExt*)ctx->ext)->couple = NULL;
 }
 
 /* seed grid: gdim^3 cells over the bounding box (about 8 tets per cell), each holding the tet whose centroid lies nearest
@@ -135,8 +136,8 @@ void ParticleContextSetFluidCoupling(ParticleContext* ctx, Mesh3D* mesh, const D
     const index_type P = ctx->num_particle;
     CoupleState* c = x->couple;
     if (c && (!mesh || c->mesh != mesh || c->N != Mesh3DNumNode(mesh) || c->T != Mesh3DNumTet(mesh) || c->P != P)) {
-        DflCoupleFree(c);
-        c = x->couple = NULL;
+        DflCoupleFree(ctx);
+        c = NULL;
     }
     if (!mesh) {
         DflHeatCouplingChanged(ctx);
@@ -154,17 +155,11 @@ void ParticleContextSetFluidCoupling(ParticleContext* ctx, Mesh3D* mesh, const D
         c->T = Mesh3DNumTet(mesh);
         c->P = P;
         build_mesh_tables(c, mesh);
-        const ptrdiff_t np = x->cap > 0 ? x->cap : 1; /* every per-particle buffer has the context's capacity */
-        c->tet = (index_type*)CdamMallocDevice(np * SIZE_OF(index_type));
         c->lost = (index_type*)CdamMallocDevice(SIZE_OF(index_type));
-        c->lambda = (f64*)CdamMallocDevice(np * 4 * SIZE_OF(f64));
-        c->imp = (f64*)CdamMallocDevice(np * 3 * SIZE_OF(f64));
-        c->rank = (index_type*)CdamMallocDevice(np * SIZE_OF(index_type));
-        c->slot = (index_type*)CdamMallocDevice(np * SIZE_OF(index_type));
-        c->members = (index_type*)CdamMallocDevice(np * SIZE_OF(index_type));
         const char* e = getenv("DFL_COUPLE_CELL_ORDER");
         c->use_order = !(e && e[0] == '0');
         x->couple = c;
+        DflParticleFieldsAlloc(ctx, DFL_PF_COUPLE);
     }
     DflFluidCoupling def = {1.0e3, 10.0 / 3.0, {0.0, 0.0, 0.0}, FALSE}; /* kRHO, kMU of assemble.cu:35,40 */
     c->cfg = cfg ? *cfg : def;
@@ -203,12 +198,7 @@ const f64* ParticleContextBarycentric(const ParticleContext* ctx) { return state
 
 index_type ParticleContextLostCount(const ParticleContext* ctx) {
     const CoupleState* c = state(ctx);
-    if (!c) return 0;
-    index_type n = 0;
-    hipStream_t s = DflStream();
-    HIPGUARD(hipMemcpyAsync(&n, c->lost, sizeof n, D2H, s));
-    HIPGUARD(hipStreamSynchronize(s));
-    return n;
+    return c ? DflReadDeviceIndex(c->lost) : 0;
 }
 
 void ParticleContextFluidStep(ParticleContext* ctx, const f64* w) {
@@ -222,20 +212,25 @@ void ParticleContextFluidStep(ParticleContext* ctx, const f64* w) {
     int slot = DflProfileBegin(DFL_TAG_SMALL + 3);
     /* particle-id order: the kernel's contiguous per-particle reads and writes outweigh the gather locality of the cell
        order (1M tets, 100k particles: 14.2 us in id order, 23.4 us in cell order; tools/probe_coupling.py) */
-    if (x->radius)
-        dfl_couple_fluid_step_sizes(ctx->num_particle, NULL, c->tet, c->lambda, Mesh3DDevice(c->mesh)->ien, w, x->mass, x->radius,
-                                    c->cfg.rho_f, c->cfg.mu_f, c->cfg.gravity, x->dt, ArrayData(ParticleCTXDeviceCoord(ctx)),
-                                    ArrayData(ParticleCTXDeviceVel(ctx)), ArrayData(ParticleCTXDeviceAcc(ctx)), c->imp, DflStream());
-    else
-        dfl_couple_fluid_step(ctx->num_particle, NULL, c->tet, c->lambda, Mesh3DDevice(c->mesh)->ien, w,
-                              ParticleMass(ctx), ParticleRadius(ctx), c->cfg.rho_f, c->cfg.mu_f, c->cfg.gravity, x->dt,
-                              ArrayData(ParticleCTXDeviceCoord(ctx)), ArrayData(ParticleCTXDeviceVel(ctx)),
-                              ArrayData(ParticleCTXDeviceAcc(ctx)), c->imp, DflStream());
+    dfl_couple_fluid_step(ctx->num_particle, NULL, c->tet, c->lambda, Mesh3DDevice(c->mesh)->ien, w, ParticleMass(ctx),
+                          ParticleRadius(ctx), x->mass, x->radius, c->cfg.rho_f, c->cfg.mu_f, c->cfg.gravity, x->dt,
+                          ArrayData(ParticleCTXDeviceCoord(ctx)), ArrayData(ParticleCTXDeviceVel(ctx)),
+                          ArrayData(ParticleCTXDeviceAcc(ctx)), c->imp, DflStream());
     DflProfileEnd(slot);
     if (x->omega) dfl_dem_spin(ctx->num_particle, x->dt, x->omega, x->alpha, DflStream()); /* the fluid exerts no torque */
     c->imp_time += x->dt;
     if (x->heat) DflHeatStep(ctx, w); /* conduction over this sweep's contacts, convection at the new velocity */
     DflRangePop();
+}
+
+void DflCoupleNodeScatter(ParticleContext* ctx, const index_type* tet, const f64* val, int ncomp, f64 scale, f64* out) {
+    CoupleState* c = state(ctx);
+    hipStream_t s = DflStream();
+    const index_type* ien = Mesh3DDevice(c->mesh)->ien;
+    dfl_couple_sort_by_tet(ctx->num_particle, c->T, tet, c->tcount, c->rank, c->tstart, c->slot, c->members, c->scan_tmp,
+                           c->scan_bytes, s);
+    if (ncomp == 3) dfl_couple_node_load(c->N, c->vrow, c->vcol, ien, c->tstart, c->members, c->lambda, val, scale, out, s);
+    else dfl_couple_node_scalar(c->N, c->vrow, c->vcol, ien, c->tstart, c->members, c->lambda, val, scale, out, s);
 }
 
 void ParticleContextReactionLoad(ParticleContext* ctx, f64* load) {
@@ -250,9 +245,7 @@ void ParticleContextReactionLoad(ParticleContext* ctx, f64* load) {
     DflRangePush("ParticleContextReactionLoad");
     int slot = DflProfileBegin(DFL_TAG_SMALL + 4);
     const index_type P = ctx->num_particle;
-    dfl_couple_sort_by_tet(P, c->T, c->tet, c->tcount, c->rank, c->tstart, c->slot, c->members, c->scan_tmp, c->scan_bytes, s);
-    dfl_couple_node_load(c->N, c->vrow, c->vcol, Mesh3DDevice(c->mesh)->ien, c->tstart, c->members, c->lambda, c->imp,
-                         1.0 / c->imp_time, load, s);
+    DflCoupleNodeScatter(ctx, c->tet, c->imp, 3, 1.0 / c->imp_time, load);
     if (c->rem_pending) { /* the impulse of the particles removed since the last call (ParticleContextRemove) */
         dfl_daxpy(c->N * 3, 1.0 / c->imp_time, c->rem_load, load, s);
         HIPGUARD(hipMemsetAsync(c->rem_load, 0, (size_t)c->N * 3 * sizeof(f64), s));
@@ -268,10 +261,7 @@ void DflCoupleAccumulateRemoved(ParticleContext* ctx, const index_type* rtet) {
     CoupleState* c = state(ctx);
     hipStream_t s = DflStream();
     /* the pattern of the reaction load, restricted to the removed particles: rem_tmp = -sum lambda imp, then rem_load += it */
-    dfl_couple_sort_by_tet(ctx->num_particle, c->T, rtet, c->tcount, c->rank, c->tstart, c->slot, c->members, c->scan_tmp,
-                           c->scan_bytes, s);
-    dfl_couple_node_load(c->N, c->vrow, c->vcol, Mesh3DDevice(c->mesh)->ien, c->tstart, c->members, c->lambda, c->imp, 1.0,
-                         c->rem_tmp, s);
+    DflCoupleNodeScatter(ctx, rtet, c->imp, 3, 1.0, c->rem_tmp);
     dfl_daxpy(c->N * 3, 1.0, c->rem_tmp, c->rem_load, s);
     c->rem_pending = TRUE;
 }

@@ -1,8 +1,9 @@
 /* Particle inflow and outflow: ParticleContextAdd and ParticleContextRemove (build-defined: empty hooks in the reference,
  * Particle.c:120-130; model in include/dedflow.h, kernels in dedflow_amd/csrc/k_flow.hip).
  *
- * Every per-particle buffer of a context is sized to its capacity x->cap >= num_particle.  Remove scatters the survivors
- * into spare buffers of the same capacity and swaps the pointers (the friction history into the other ping-pong row
+ * Every per-particle buffer of a context is sized to its capacity x->cap >= num_particle; which buffers there are is the
+ * table of host/pfields.c, and nothing here names a field of another feature.  Remove scatters the survivors of every
+ * carried field into spare buffers of the same capacity and swaps the pointers (the friction history into the other ping-pong row
  * set, which flips); Add appends in place after growing the capacity by x1.5 when it must.  Each call reads the new count
  * back (4 bytes) and allocates nothing unless the capacity grows. */
 #include <math.h>
@@ -11,33 +12,6 @@
 #include "dedflow.h"
 #include "dedflow_kernels.h"
 #include "host_private.h"
-
-typedef struct FlowState {
-    b32 in_on, out_on;
-    DflParticleInflow in;
-    DflParticleOutflow out;
-    dfl_inlet inlet;                 /* lattice of the current radius */
-    f64 inlet_R;                     /* radius the lattice was built for */
-    index_type nslot;
-    uint64_t call;                   /* Add calls since ParticleContextSetInflow */
-    f64 credit;
-    int64_t next_tag;
-    DflParticleFlowStats stats;
-    index_type cap;                  /* capacity the buffers below (and the spares) are sized for */
-    int64_t *tag, *tag_spare;        /* device [cap] */
-    f64* spare3[6];                  /* device [cap][3]: coord, vel, acc, omega, alpha, imp */
-    f64* spare1[5];                  /* device [cap]: radius, mass (polydisperse), temperature, energy, heat rate (heat) */
-    index_type* tet_spare;           /* device [cap] */
-    f64* lambda_spare;               /* device [cap][4] */
-    index_type *keep, *newid, *rtet; /* device [cap], [cap + 1], [cap] */
-    void* scan_tmp;
-    int64_t scan_bytes;
-    index_type *blocked, *slot, *slot_out; /* device [nslot] */
-    uint64_t *key, *key_out;               /* device [nslot] */
-    void* sort_tmp;
-    int64_t sort_bytes;
-    index_type* count;               /* device [1] */
-} FlowState;
 
 static void free_slots(FlowState* f) {
     CdamFreeDevice(f->blocked, 0); CdamFreeDevice(f->slot, 0); CdamFreeDevice(f->slot_out, 0);
@@ -48,43 +22,55 @@ static void free_slots(FlowState* f) {
 }
 
 static void free_spares(FlowState* f) {
-    for (int k = 0; k < 6; ++k) {
-        CdamFreeDevice(f->spare3[k], 0);
-        f->spare3[k] = NULL;
+    for (int e = 0; e < DFL_FLOW_MAX_FIELDS; ++e) {
+        CdamFreeDevice(f->spare[e], 0);
+        f->spare[e] = NULL;
     }
-    for (int k = 0; k < 5; ++k) {
-        CdamFreeDevice(f->spare1[k], 0);
-        f->spare1[k] = NULL;
-    }
-    CdamFreeDevice(f->tag_spare, 0); CdamFreeDevice(f->tet_spare, 0); CdamFreeDevice(f->lambda_spare, 0);
-    f->tag_spare = NULL;
-    f->tet_spare = NULL;
-    f->lambda_spare = NULL;
 }
 
-/* the scratch of a capacity: tags are carried, the rest is scratch */
-static void free_capacity_scratch(FlowState* f) {
-    CdamFreeDevice(f->keep, 0); CdamFreeDevice(f->newid, 0); CdamFreeDevice(f->rtet, 0); CdamFreeDevice(f->scan_tmp, 0);
-    free_spares(f);
+/* the spare a compaction writes `row` into: one of the row's element size that no earlier row of this walk took (bit e of
+ * *taken: spare e is taken), allocated at the context's capacity when there is none */
+static void** spare_of(FlowState* f, const DflPField* row, index_type cap, unsigned* taken) {
+    int e = 0, empty = -1;
+    for (; e < DFL_FLOW_MAX_FIELDS; ++e) {
+        if (f->spare[e] && f->spare_bytes[e] == row->bytes && !(*taken >> e & 1)) break;
+        if (!f->spare[e] && empty < 0) empty = e;
+    }
+    if (e == DFL_FLOW_MAX_FIELDS) {
+        ASSERT(empty >= 0 && "more carried per-particle fields than DFL_FLOW_MAX_FIELDS");
+        e = empty;
+        f->spare[e] = DflParticleFieldAlloc(row, cap);
+        f->spare_bytes[e] = row->bytes;
+    }
+    *taken |= 1u << e;
+    return &f->spare[e];
 }
-static void alloc_capacity_scratch(FlowState* f, index_type cap) {
-    const ptrdiff_t n = cap > 0 ? cap : 1;
-    f->keep = (index_type*)CdamMallocDevice(n * SIZE_OF(index_type));
-    f->newid = (index_type*)CdamMallocDevice((n + 1) * SIZE_OF(index_type));
-    f->rtet = (index_type*)CdamMallocDevice(n * SIZE_OF(index_type));
-    f->scan_bytes = dfl_scan_temp_bytes((index_type)n);
+
+/* the spares the next compaction writes, for the state that is on now */
+static void ensure_spares(ParticleContext* ctx) {
+    ParticleExt* x = (ParticleExt*)ctx->ext;
+    DflPField rows[DFL_PF_MAX_ROWS];
+    const int nrow = DflParticleFields(ctx, DflParticleLiveFeatures(ctx), rows);
+    unsigned taken = 0;
+    for (int r = 0; r < nrow; ++r)
+        if (rows[r].kind == DFL_PF_CARRIED) spare_of(x->flow, &rows[r], x->cap, &taken);
+}
+
+static void alloc_scan(FlowState* f, index_type cap) {
+    f->scan_bytes = dfl_scan_temp_bytes(cap > 0 ? cap : 1);
     f->scan_tmp = CdamMallocDevice((ptrdiff_t)f->scan_bytes);
-    f->tag_spare = (int64_t*)CdamMallocDevice(n * SIZE_OF(int64_t));
-    f->cap = cap;
 }
 
-void DflFlowFree(FlowState* f) {
+void DflFlowFree(ParticleContext* ctx) {
+    FlowState* f = ((ParticleExt*)ctx->ext)->flow;
     if (!f) return;
     HIPGUARD(hipStreamSynchronize(DflStream()));
     free_slots(f);
-    free_capacity_scratch(f);
-    CdamFreeDevice(f->tag, 0); CdamFreeDevice(f->count, 0);
+    free_spares(f);
+    DflParticleFieldsFree(ctx, DFL_PF_FLOW);
+    CdamFreeDevice(f->scan_tmp, 0); CdamFreeDevice(f->count, 0);
     CdamFreeHost(f, SIZE_OF(FlowState));
+    ((ParticleExt*)ctx->ext)->flow = NULL;
 }
 
 /* the flow state of a context: created (tags 0 .. P-1) at the first Set call */
@@ -94,45 +80,17 @@ static FlowState* flow_state(ParticleContext* ctx) {
     const index_type P = ctx->num_particle;
     FlowState* f = (FlowState*)CdamMallocHost(SIZE_OF(FlowState));
     memset(f, 0, sizeof *f);
-    const ptrdiff_t n = x->cap > 0 ? x->cap : 1;
-    f->tag = (int64_t*)CdamMallocDevice(n * SIZE_OF(int64_t));
+    x->flow = f;
+    DflParticleFieldsAlloc(ctx, DFL_PF_FLOW);
     f->count = (index_type*)CdamMallocDevice(SIZE_OF(index_type));
-    alloc_capacity_scratch(f, x->cap);
-    int64_t* h = (int64_t*)malloc((size_t)n * sizeof(int64_t));
+    alloc_scan(f, x->cap);
+    int64_t* h = (int64_t*)malloc((size_t)(P > 0 ? P : 1) * sizeof(int64_t));
     for (index_type i = 0; i < P; ++i) h[i] = i;
     HIPGUARD(hipStreamSynchronize(DflStream()));
     if (P > 0) HIPGUARD(hipMemcpy(f->tag, h, (size_t)P * sizeof(int64_t), H2D));
     free(h);
     f->next_tag = P;
-    x->flow = f;
     return f;
-}
-
-/* a device buffer of new_bytes holding the first keep_bytes of `old` (freed); stream-ordered */
-static void* regrow(void* old, size_t keep_bytes, size_t new_bytes) {
-    void* p = CdamMallocDevice((ptrdiff_t)new_bytes);
-    if (old && keep_bytes) HIPGUARD(hipMemcpyAsync(p, old, keep_bytes, hipMemcpyDeviceToDevice, DflStream()));
-    CdamFreeDevice(old, 0);
-    return p;
-}
-#define REGROW(ptr, keep_elems, new_elems) \
-    ((ptr) = regrow((ptr), (size_t)(keep_elems) * sizeof *(ptr), (size_t)(new_elems) * sizeof *(ptr)))
-
-/* the spares the next compaction writes, for the state that is on now */
-static void ensure_spares(ParticleContext* ctx) {
-    ParticleExt* x = (ParticleExt*)ctx->ext;
-    FlowState* f = x->flow;
-    const ptrdiff_t n = x->cap > 0 ? x->cap : 1;
-    const int need3 = 3 + (x->omega ? 2 : 0) + (x->couple ? 1 : 0); /* coord, vel, acc, [w, alpha], [imp] */
-    for (int k = 0; k < need3; ++k)
-        if (!f->spare3[k]) f->spare3[k] = (f64*)CdamMallocDevice(n * 3 * SIZE_OF(f64));
-    const int need1 = (x->radius ? 2 : 0) + (x->heat ? 3 : 0); /* [radius, mass], [temp, e, rate] */
-    for (int k = 0; k < need1; ++k)
-        if (!f->spare1[k]) f->spare1[k] = (f64*)CdamMallocDevice(n * SIZE_OF(f64));
-    if (x->couple && !f->tet_spare) {
-        f->tet_spare = (index_type*)CdamMallocDevice(n * SIZE_OF(index_type));
-        f->lambda_spare = (f64*)CdamMallocDevice(n * 4 * SIZE_OF(f64));
-    }
 }
 
 /* capacity >= need: every buffer sized by the particle count, the live entries carried */
@@ -143,10 +101,18 @@ static void grow(ParticleContext* ctx, index_type need) {
     const int64_t want = (int64_t)x->cap + x->cap / 2;
     const index_type cap = want > need ? (want < INT32_MAX / DFL_DEM_MAX_HISTORY ? (index_type)want : need) : need;
     const index_type P = ctx->num_particle;
-    HIPGUARD(hipStreamSynchronize(DflStream()));
+    hipStream_t s = DflStream();
+    HIPGUARD(hipStreamSynchronize(s));
+    DflPField rows[DFL_PF_MAX_ROWS];
+    const int nrow = DflParticleFields(ctx, DflParticleLiveFeatures(ctx), rows);
+    for (int r = 0; r < nrow; ++r) { /* stream-ordered: the copy, then the old buffer goes */
+        void* old = *rows[r].ptr;
+        *rows[r].ptr = DflParticleFieldAlloc(&rows[r], cap);
+        if (rows[r].kind != DFL_PF_SCRATCH && P > 0)
+            HIPGUARD(hipMemcpyAsync(*rows[r].ptr, old, (size_t)P * rows[r].bytes, hipMemcpyDeviceToDevice, s));
+        CdamFreeDevice(old, 0);
+    }
     for (int k = 0; k < 3; ++k) {
-        Array* d = ctx->d_arr[k];
-        REGROW(d->data, 3 * (size_t)P, 3 * (size_t)cap);
         Array* h = ctx->h_arr[k];
         f64* hd = (f64*)CdamMallocHost((ptrdiff_t)cap * 3 * SIZE_OF(f64));
         memset(hd, 0, (size_t)cap * 3 * sizeof(f64));
@@ -154,42 +120,11 @@ static void grow(ParticleContext* ctx, index_type need) {
         CdamFreeHost(h->data, (ptrdiff_t)x->cap * 3 * SIZE_OF(f64));
         h->data = hd;
     }
-    if (x->omega) {
-        REGROW(x->omega, 3 * (size_t)P, 3 * (size_t)cap);
-        REGROW(x->alpha, 3 * (size_t)P, 3 * (size_t)cap);
-        REGROW(x->sorted_w, 0, 3 * (size_t)cap);
-        for (int k = 0; k < 2; ++k) {
-            REGROW(x->hist[k], (size_t)P * DFL_DEM_MAX_HISTORY, (size_t)cap * DFL_DEM_MAX_HISTORY);
-            REGROW(x->hist_count[k], P, cap);
-        }
-    }
-    if (x->radius) {
-        REGROW(x->radius, P, cap);
-        REGROW(x->mass, P, cap);
-        REGROW(x->sorted_r, 0, cap);
-    }
-    HeatState* h = x->heat;
-    if (h) {
-        REGROW(h->temp, P, cap);
-        REGROW(h->e, P, cap);
-        REGROW(h->rate, P, cap);
-        REGROW(h->q, 0, cap);
-        REGROW(h->sorted_t, 0, cap);
-    }
-    CoupleState* c = x->couple;
-    if (c) {
-        REGROW(c->tet, P, cap);
-        REGROW(c->lambda, 4 * (size_t)P, 4 * (size_t)cap);
-        REGROW(c->imp, 3 * (size_t)P, 3 * (size_t)cap);
-        REGROW(c->rank, 0, cap);
-        REGROW(c->slot, 0, cap);
-        REGROW(c->members, 0, cap);
-    }
-    REGROW(f->tag, P, cap);
-    free_capacity_scratch(f);
-    alloc_capacity_scratch(f, cap);
+    CdamFreeDevice(f->scan_tmp, 0);
+    alloc_scan(f, cap);
+    free_spares(f);
     x->cap = cap;
-    DflLaserCapacityChanged(ctx); /* scratch and the per-step rate only: nothing to carry */
+    DflLaserCapacityChanged(ctx); /* its bins are sized with the capacity too */
     if (f->out_on) ensure_spares(ctx);
 }
 
@@ -199,14 +134,6 @@ static void set_count(ParticleContext* ctx, index_type P) {
     for (int k = 0; k < 3; ++k) ctx->h_arr[k]->len = ctx->d_arr[k]->len = 3 * P;
     if (x->couple) x->couple->P = P;
     x->order_valid = x->sort_valid = FALSE; /* the sweep's permutation holds the old ids */
-}
-
-static index_type read_count(const index_type* d) {
-    index_type n = 0;
-    hipStream_t s = DflStream();
-    HIPGUARD(hipMemcpyAsync(&n, d, sizeof n, D2H, s));
-    HIPGUARD(hipStreamSynchronize(s));
-    return n;
 }
 
 void ParticleContextSetOutflow(ParticleContext* ctx, const DflParticleOutflow* cfg) {
@@ -317,44 +244,37 @@ void ParticleContextRemove(ParticleContext* ctx) {
     dfl_flow_flag(P, ArrayData(ParticleCTXDeviceCoord(ctx)), pl, c ? c->tet : NULL, by_mesh ? 1 : 0, f->keep,
                   pending || heat_pending ? f->rtet : NULL, s);
     dfl_exclusive_scan_i32(P, f->keep, f->newid, f->scan_tmp, f->scan_bytes, s);
-    const index_type Pn = read_count(f->newid + P);
+    const index_type Pn = DflReadDeviceIndex(f->newid + P);
     if (Pn == P) {
         DflRangePop();
         return;
     }
     if (pending) DflCoupleAccumulateRemoved(ctx, f->rtet); /* before the compaction moves imp and lambda */
     if (heat_pending) DflHeatAccumulateRemoved(ctx, f->rtet);
+    /* every carried field into a spare, grouped by element size; the swap in the same walk: the compacted copy becomes the
+       live buffer, the old one the spare */
+    static const int group_bytes[4] = {4, 8, 24, 32};
+    DflPField rows[DFL_PF_MAX_ROWS];
+    const int nrow = DflParticleFields(ctx, DflParticleLiveFeatures(ctx), rows);
     dfl_flow_fields fl;
     memset(&fl, 0, sizeof fl);
-    f64* src3[6] = {ArrayData(ParticleCTXDeviceCoord(ctx)), ArrayData(ParticleCTXDeviceVel(ctx)), ArrayData(ParticleCTXDeviceAcc(ctx)),
-                    x->omega, x->alpha, c ? c->imp : NULL};
-    int n3 = 0;
-    for (int k = 0; k < 6; ++k) {
-        if (!src3[k]) continue;
-        fl.src3[n3] = src3[k];
-        fl.dst3[n3] = f->spare3[n3];
-        ++n3;
+    unsigned taken = 0;
+    int n = 0, carried = 0;
+    for (int g = 0; g < 4; ++g) {
+        fl.first[g] = n;
+        for (int r = 0; r < nrow; ++r) {
+            if (rows[r].kind != DFL_PF_CARRIED || rows[r].bytes != group_bytes[g]) continue;
+            void** spare = spare_of(f, &rows[r], x->cap, &taken);
+            fl.pair[n].src = *rows[r].ptr;
+            fl.pair[n].dst = *spare;
+            *spare = *rows[r].ptr;
+            *rows[r].ptr = fl.pair[n].dst;
+            ++n;
+        }
     }
-    fl.n3 = n3;
-    HeatState* h = x->heat;
-    f64** live1[5] = {x->radius ? &x->radius : NULL, x->radius ? &x->mass : NULL, h ? &h->temp : NULL, h ? &h->e : NULL,
-                      h ? &h->rate : NULL};
-    int n1 = 0;
-    for (int k = 0; k < 5; ++k) {
-        if (!live1[k]) continue;
-        fl.src1[n1] = *live1[k];
-        fl.dst1[n1] = f->spare1[n1];
-        ++n1;
-    }
-    fl.n1 = n1;
-    fl.tag_src = f->tag;
-    fl.tag_dst = f->tag_spare;
-    if (c) {
-        fl.tet_src = c->tet;
-        fl.tet_dst = f->tet_spare;
-        fl.lambda_src = c->lambda;
-        fl.lambda_dst = f->lambda_spare;
-    }
+    fl.first[4] = n;
+    for (int r = 0; r < nrow; ++r) carried += rows[r].kind == DFL_PF_CARRIED;
+    ASSERT(n == carried && "a carried per-particle field whose element size the compaction kernel has no copy path for");
     const int cur = x->hist_cur;
     if (x->omega) { /* the rows the next sweep reads move into the other row set, which becomes the current one */
         fl.hrow_src = x->hist[cur];
@@ -363,34 +283,6 @@ void ParticleContextRemove(ParticleContext* ctx) {
         fl.hcount_dst = x->hist_count[1 - cur];
     }
     dfl_flow_compact(P, f->keep, f->newid, fl, s);
-    /* swap: the compacted copies become the live buffers, the old ones the spares */
-    f64** live3[6] = {&ParticleCTXDeviceCoord(ctx)->data, &ParticleCTXDeviceVel(ctx)->data, &ParticleCTXDeviceAcc(ctx)->data,
-                      &x->omega, &x->alpha, c ? &c->imp : NULL};
-    for (int k = 0, m = 0; k < 6; ++k) {
-        if (!src3[k]) continue;
-        f64* t = *live3[k];
-        *live3[k] = f->spare3[m];
-        f->spare3[m] = t;
-        ++m;
-    }
-    int64_t* tg = f->tag;
-    f->tag = f->tag_spare;
-    f->tag_spare = tg;
-    if (c) {
-        index_type* tt = c->tet;
-        c->tet = f->tet_spare;
-        f->tet_spare = tt;
-        f64* tl = c->lambda;
-        c->lambda = f->lambda_spare;
-        f->lambda_spare = tl;
-    }
-    for (int k = 0, m = 0; k < 5; ++k) {
-        if (!live1[k]) continue;
-        f64* t = *live1[k];
-        *live1[k] = f->spare1[m];
-        f->spare1[m] = t;
-        ++m;
-    }
     if (x->omega) x->hist_cur = 1 - cur;
     f->stats.removed += P - Pn;
     set_count(ctx, Pn);
@@ -427,23 +319,13 @@ void ParticleContextAdd(ParticleContext* ctx) {
     hipStream_t s = DflStream();
     grow(ctx, P + n_try);
     CoupleState* c = x->couple;
-    if (x->radius) {
-        dfl_inflow_block_sizes(P, ArrayData(ParticleCTXDeviceCoord(ctx)), f->inlet, x->radius, r_lo, r_hi, f->blocked, s);
-        dfl_inflow_select(f->inlet, f->blocked, f->key, f->key_out, f->slot, f->slot_out, f->sort_tmp, f->sort_bytes, s);
-        dfl_inflow_append_sizes(P, n_try, f->inlet, f->key_out, f->slot_out, f->next_tag, ArrayData(ParticleCTXDeviceCoord(ctx)),
-                                ArrayData(ParticleCTXDeviceVel(ctx)), ArrayData(ParticleCTXDeviceAcc(ctx)), f->tag, x->omega,
-                                x->alpha, x->omega ? x->hist_count[x->hist_cur] : NULL, c ? c->tet : NULL, c ? c->lambda : NULL,
-                                c ? c->imp : NULL, x->radius, x->mass, r_lo, r_hi, ParticleRadius(ctx), ParticleMass(ctx), f->count,
-                                s);
-    } else {
-        dfl_inflow_block(P, ArrayData(ParticleCTXDeviceCoord(ctx)), f->inlet, R, f->blocked, s);
-        dfl_inflow_select(f->inlet, f->blocked, f->key, f->key_out, f->slot, f->slot_out, f->sort_tmp, f->sort_bytes, s);
-        dfl_inflow_append(P, n_try, f->inlet, f->key_out, f->slot_out, f->next_tag, ArrayData(ParticleCTXDeviceCoord(ctx)),
-                          ArrayData(ParticleCTXDeviceVel(ctx)), ArrayData(ParticleCTXDeviceAcc(ctx)), f->tag, x->omega, x->alpha,
-                          x->omega ? x->hist_count[x->hist_cur] : NULL, c ? c->tet : NULL, c ? c->lambda : NULL, c ? c->imp : NULL,
-                          f->count, s);
-    }
-    const index_type n = read_count(f->count);
+    dfl_inflow_block(P, ArrayData(ParticleCTXDeviceCoord(ctx)), f->inlet, R, x->radius, r_lo, r_hi, f->blocked, s);
+    dfl_inflow_select(f->inlet, f->blocked, f->key, f->key_out, f->slot, f->slot_out, f->sort_tmp, f->sort_bytes, s);
+    dfl_inflow_append(P, n_try, f->inlet, f->key_out, f->slot_out, f->next_tag, ArrayData(ParticleCTXDeviceCoord(ctx)),
+                      ArrayData(ParticleCTXDeviceVel(ctx)), ArrayData(ParticleCTXDeviceAcc(ctx)), f->tag, x->omega, x->alpha,
+                      x->omega ? x->hist_count[x->hist_cur] : NULL, c ? c->tet : NULL, c ? c->lambda : NULL, c ? c->imp : NULL,
+                      x->radius, x->mass, r_lo, r_hi, ParticleRadius(ctx), ParticleMass(ctx), f->count, s);
+    const index_type n = DflReadDeviceIndex(f->count);
     f->next_tag += n;
     f->stats.inserted += n;
     f->stats.blocked += want - n;

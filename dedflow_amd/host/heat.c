@@ -16,12 +16,14 @@
 
 static HeatState* heat(const ParticleContext* ctx) { return ((ParticleExt*)ctx->ext)->heat; }
 
-void DflHeatFree(HeatState* h) {
+void DflHeatFree(ParticleContext* ctx) {
+    HeatState* h = heat(ctx);
     if (!h) return;
     HIPGUARD(hipStreamSynchronize(DflStream()));
-    CdamFreeDevice(h->temp, 0); CdamFreeDevice(h->e, 0); CdamFreeDevice(h->rate, 0); CdamFreeDevice(h->q, 0);
-    CdamFreeDevice(h->sorted_t, 0); CdamFreeDevice(h->source, 0); CdamFreeDevice(h->rem_q, 0);
+    DflParticleFieldsFree(ctx, DFL_PF_HEAT);
+    CdamFreeDevice(h->source, 0); CdamFreeDevice(h->rem_q, 0);
     CdamFreeHost(h, SIZE_OF(HeatState));
+    ((ParticleExt*)ctx->ext)->heat = NULL;
 }
 
 static void node_buffers(HeatState* h, index_type N);
@@ -39,8 +41,7 @@ void ParticleContextSetHeat(ParticleContext* ctx, const DflParticleHeat* cfg) {
     ParticleExt* x = (ParticleExt*)ctx->ext;
     if (!cfg) {
         DflLaserFree(ctx); /* the laser heats through the heat update: it goes with it */
-        DflHeatFree(x->heat);
-        x->heat = NULL;
+        DflHeatFree(ctx);
         return;
     }
     if (!(cfg->cp_p > 0.0 && isfinite(cfg->cp_p) && isfinite(cfg->T_init))) {
@@ -50,15 +51,10 @@ void ParticleContextSetHeat(ParticleContext* ctx, const DflParticleHeat* cfg) {
     HeatState* h = x->heat;
     const index_type P = ctx->num_particle;
     if (!h) {
-        const ptrdiff_t n = x->cap > 0 ? x->cap : 1;
         h = (HeatState*)CdamMallocHost(SIZE_OF(HeatState));
         memset(h, 0, sizeof *h);
-        h->temp = (f64*)CdamMallocDevice(n * SIZE_OF(f64));
-        h->e = (f64*)CdamMallocDevice(n * SIZE_OF(f64));
-        h->rate = (f64*)CdamMallocDevice(n * SIZE_OF(f64));
-        h->q = (f64*)CdamMallocDevice(n * SIZE_OF(f64));
-        h->sorted_t = (f64*)CdamMallocDevice(n * SIZE_OF(f64));
         x->heat = h;
+        DflParticleFieldsAlloc(ctx, DFL_PF_HEAT);
     }
     h->cfg = *cfg;
     h->cp_f = cfg->cp_f > 0.0 ? cfg->cp_f : 1.0;  /* kCP, assemble.cu:36 */
@@ -155,9 +151,7 @@ void ParticleContextHeatSource(ParticleContext* ctx, f64* q) {
     }
     DflRangePush("ParticleContextHeatSource");
     const index_type P = ctx->num_particle;
-    dfl_couple_sort_by_tet(P, c->T, c->tet, c->tcount, c->rank, c->tstart, c->slot, c->members, c->scan_tmp, c->scan_bytes, s);
-    dfl_couple_node_scalar(c->N, c->vrow, c->vcol, Mesh3DDevice(c->mesh)->ien, c->tstart, c->members, c->lambda, h->e, 1.0 / h->time,
-                           q, s);
+    DflCoupleNodeScatter(ctx, c->tet, h->e, 1, 1.0 / h->time, q);
     if (h->rem_pending) { /* the energy of the particles removed since the last call */
         dfl_daxpy(c->N, 1.0 / h->time, h->rem_q, q, s);
         HIPGUARD(hipMemsetAsync(h->rem_q, 0, (size_t)c->N * sizeof(f64), s));
@@ -175,10 +169,7 @@ void DflHeatAccumulateRemoved(ParticleContext* ctx, const index_type* rtet) {
     CoupleState* c = x->couple;
     hipStream_t s = DflStream();
     /* the pattern of the source, restricted to the removed particles: rem_tmp = -sum lambda e, then rem_q += it */
-    dfl_couple_sort_by_tet(ctx->num_particle, c->T, rtet, c->tcount, c->rank, c->tstart, c->slot, c->members, c->scan_tmp,
-                           c->scan_bytes, s);
-    dfl_couple_node_scalar(c->N, c->vrow, c->vcol, Mesh3DDevice(c->mesh)->ien, c->tstart, c->members, c->lambda, h->e, 1.0,
-                           c->rem_tmp, s);
+    DflCoupleNodeScatter(ctx, rtet, h->e, 1, 1.0, c->rem_tmp);
     dfl_daxpy(c->N, 1.0, c->rem_tmp, h->rem_q, s);
     h->rem_pending = TRUE;
 }

@@ -132,6 +132,24 @@ void DflFrictionClearHistory(ParticleContext* ctx); /* no-op when friction is of
 void DflDemReserve(ParticleExt* x, index_type P, index_type nbin);
 /* the cell sort of the contact sweep alone (unit box or mesh-wall grid): order / cell_start / sorted copies, order_valid */
 void DflDemBuildCells(ParticleContext* ctx);
+/* the per-particle device arrays of a context, one table for all features (host/pfields.c).  A row: the owning pointer,
+ * the bytes of one particle and a kind -- carried (the first num_particle entries follow the particle), scratch (sized by
+ * the capacity, contents never carried) or the friction history (carried by grow; a compaction remaps its keys itself).
+ * `extra`: entries beyond the capacity. */
+enum { DFL_PF_CARRIED, DFL_PF_SCRATCH, DFL_PF_HISTORY };
+enum { DFL_PF_BASE = 1, DFL_PF_FRICTION = 2, DFL_PF_SIZES = 4, DFL_PF_HEAT = 8, DFL_PF_COUPLE = 16, DFL_PF_LASER = 32, DFL_PF_FLOW = 64 };
+#define DFL_PF_MAX_ROWS 48
+typedef struct DflPField {
+    void** ptr;
+    int bytes, kind, extra;
+} DflPField;
+unsigned DflParticleLiveFeatures(const ParticleContext* ctx);     /* coord / vel / acc and every feature that is on */
+int DflParticleFields(ParticleContext* ctx, unsigned features, DflPField* rows); /* rows [DFL_PF_MAX_ROWS]; returns their number */
+void* DflParticleFieldAlloc(const DflPField* row, index_type cap);  /* a buffer of the row for capacity cap */
+/* every array of one feature at the context's capacity x->cap (its state struct is attached), and freed and NULLed again */
+void DflParticleFieldsAlloc(ParticleContext* ctx, unsigned feature);
+void DflParticleFieldsFree(ParticleContext* ctx, unsigned feature);
+index_type DflReadDeviceIndex(const index_type* d);               /* one device counter copied back (synchronises) */
 /* particle-fluid coupling state (host/couple.c) */
 typedef struct CoupleState {
     Mesh3D* mesh;
@@ -154,7 +172,11 @@ typedef struct CoupleState {
     f64 *rem_load, *rem_tmp;         /* device [3N]: -(impulse of removed particles) scattered to the nodes, and scratch */
     b32 rem_pending;                 /* rem_load holds something the next reaction load adds */
 } CoupleState;
-void DflCoupleFree(struct CoupleState* c);
+void DflCoupleFree(ParticleContext* ctx);
+/* the node scatter of the coupled mesh: out[ncomp a + d] = -scale * sum over the particles p of the tets e around node a of
+ * lambda_{p,k(a,e)} val[ncomp p + d], `tet` (c->tet, or the removed particles' rtet) saying which tet holds p; ncomp 1 or 3.
+ * The sort by tet, then the node pass */
+void DflCoupleNodeScatter(ParticleContext* ctx, const index_type* tet, const f64* val, int ncomp, f64 scale, f64* out);
 /* scatter the pending impulse of the particles with rtet[i] >= 0 (removed, located) into rem_load (host/couple.c) */
 void DflCoupleAccumulateRemoved(ParticleContext* ctx, const index_type* rtet);
 /* particle heat transfer (host/heat.c): every per-particle buffer has the context's capacity */
@@ -168,7 +190,7 @@ typedef struct HeatState {
     f64 *source, *rem_q;             /* device [N]: the source DflTimeStep registers; -(energy of removed particles) per node */
     b32 rem_pending;
 } HeatState;
-void DflHeatFree(struct HeatState* h);
+void DflHeatFree(ParticleContext* ctx);
 /* one thermal sub-step after the integration of ParticleContextUpdate (w NULL) / ParticleContextFluidStep */
 void DflHeatStep(ParticleContext* ctx, const f64* w);
 void DflHeatCopy(ParticleContext* dst, const ParticleContext* src);
@@ -182,18 +204,63 @@ b32 DflParticleHeatTwoWay(const ParticleContext* ctx);
 f64* DflParticlePendingHeatSource(ParticleContext* ctx); /* the pending source in the context's own [N] buffer, or NULL */
 const f64* DflMeshHeatSource(const Mesh3D* mesh);
 /* laser energy deposition (host/laser.c); every call below is a no-op on a context without a laser */
-struct LaserState;
+typedef struct LaserState {
+    DflLaser cfg;                    /* as the caller gave it */
+    f64 dir[3], e1[3], e2[3];        /* the frame of include/dedflow.h */
+    f64 t;                           /* elapsed scan time */
+    index_type n, ncol;
+    f64* gw;                         /* device [2n]: gx, gy */
+    index_type nbin;                 /* bins of the column sort: the columns + one per 8 particle ids for those outside */
+    index_type *count, *cell_start, *chunk_sum; /* device [nbin + 1], [nbin + 1], [chunks], sized with the capacity */
+    uint64_t* colkey;                /* device [ncol] */
+    f64 *col_T, *part, *tally;       /* device [ncol], [6][ncol], [6] */
+    index_type* col_face;            /* device [ncol] */
+    f64 *rate, *sorted, *sorted_r, *k_tau;         /* device [cap], [cap][6], [cap], [cap] */
+    index_type *cell_of, *rank, *slot, *order, *k_id; /* device [cap] */
+    /* substrate */
+    index_type nf, ns;               /* candidate faces, their distinct nodes */
+    dfl_wall_tri* tri;               /* device [nf], ascending record id */
+    index_type *snode, *soff, *sface; /* device [ns], [ns + 1], [3 nf]: node id, its faces as 4 face + local vertex */
+    f64 *power, *energy;             /* device [ns] */
+    f64 vdmin, vdmax;                /* range of v . dir over the candidates' vertices */
+    f64 time;                        /* time the energy was accumulated over */
+} LaserState;
 void DflLaserFree(ParticleContext* ctx);            /* off: frees the state */
 void DflLaserStep(ParticleContext* ctx, f64 dt);    /* one laser step (the laser must be on) */
 void DflLaserCouplingChanged(ParticleContext* ctx); /* SetFluidCoupling: the substrate list of the new mesh, nothing pending */
-void DflLaserCapacityChanged(ParticleContext* ctx); /* the per-particle buffers for the context's new capacity */
+void DflLaserCapacityChanged(ParticleContext* ctx); /* after the table's buffers grew: the bins of the new capacity, rate zero */
 void DflLaserCopy(ParticleContext* dst, const ParticleContext* src);
 b32 DflLaserPending(const ParticleContext* ctx);    /* substrate energy accumulated since the last heat source */
 void DflLaserAddSource(ParticleContext* ctx, f64* q); /* q[N] += that energy / its time; clears it */
 /* the boundary faces of the masked groups as wall records in group order (host/walls.c; synchronises; free() both) */
 dfl_wall_tri* DflMeshBoundaryTris(Mesh3D* mesh, index_type group_mask, index_type* nf_out, f64 lo[3], f64 hi[3], f64** edges_out);
-struct FlowState;
-void DflFlowFree(struct FlowState* f);
+/* particle inflow / outflow (host/flow.c) */
+typedef struct FlowState {
+    b32 in_on, out_on;
+    DflParticleInflow in;
+    DflParticleOutflow out;
+    dfl_inlet inlet;                 /* lattice of the current radius */
+    f64 inlet_R;                     /* radius the lattice was built for */
+    index_type nslot;
+    uint64_t call;                   /* Add calls since ParticleContextSetInflow */
+    f64 credit;
+    int64_t next_tag;
+    DflParticleFlowStats stats;
+    int64_t* tag;                    /* device [cap] */
+    index_type *keep, *newid, *rtet; /* device [cap], [cap + 1], [cap] */
+    /* what a compaction writes: buffers of the capacity, one per carried field of the features that are on; after it they
+       hold the fields' old buffers.  spare_bytes: bytes per particle of each, which is all that tells them apart */
+    void* spare[DFL_FLOW_MAX_FIELDS];
+    int spare_bytes[DFL_FLOW_MAX_FIELDS];
+    void* scan_tmp;
+    int64_t scan_bytes;
+    index_type *blocked, *slot, *slot_out; /* device [nslot] */
+    uint64_t *key, *key_out;               /* device [nslot] */
+    void* sort_tmp;
+    int64_t sort_bytes;
+    index_type* count;               /* device [1] */
+} FlowState;
+void DflFlowFree(ParticleContext* ctx);
 struct WallState;
 void DflWallsFree(struct WallState* w);
 /* the contact sweep against the mesh walls (ParticleContextComputeForces when walls are set) */

@@ -21,39 +21,7 @@
 #define LASER_MAX_COLUMNS 256
 #define LASER_MAX_FACES (1 << 24)
 
-typedef struct LaserState {
-    DflLaser cfg;                    /* as the caller gave it */
-    f64 dir[3], e1[3], e2[3];        /* the frame of include/dedflow.h */
-    f64 t;                           /* elapsed scan time */
-    index_type n, ncol;
-    f64* gw;                         /* device [2n]: gx, gy */
-    index_type nbin;                 /* bins of the column sort: the columns + one per 8 particle ids for those outside */
-    index_type *count, *cell_start, *chunk_sum; /* device [nbin + 1], [nbin + 1], [chunks], sized with the capacity */
-    uint64_t* colkey;                /* device [ncol] */
-    f64 *col_T, *part, *tally;       /* device [ncol], [6][ncol], [6] */
-    index_type* col_face;            /* device [ncol] */
-    index_type cap;                  /* capacity the per-particle buffers below are sized for */
-    f64 *rate, *sorted, *sorted_r, *k_tau;         /* device [cap], [cap][6], [cap], [cap] */
-    index_type *cell_of, *rank, *slot, *order, *k_id; /* device [cap] */
-    /* substrate */
-    index_type nf, ns;               /* candidate faces, their distinct nodes */
-    dfl_wall_tri* tri;               /* device [nf], ascending record id */
-    index_type *snode, *soff, *sface; /* device [ns], [ns + 1], [3 nf]: node id, its faces as 4 face + local vertex */
-    f64 *power, *energy;             /* device [ns] */
-    f64 vdmin, vdmax;                /* range of v . dir over the candidates' vertices */
-    f64 time;                        /* time the energy was accumulated over */
-} LaserState;
-
 static LaserState* laser(const ParticleContext* ctx) { return ((ParticleExt*)ctx->ext)->laser; }
-
-static void free_particle_buffers(LaserState* l) {
-    CdamFreeDevice(l->rate, 0); CdamFreeDevice(l->sorted, 0); CdamFreeDevice(l->sorted_r, 0); CdamFreeDevice(l->k_tau, 0);
-    CdamFreeDevice(l->cell_of, 0); CdamFreeDevice(l->rank, 0); CdamFreeDevice(l->slot, 0); CdamFreeDevice(l->order, 0);
-    CdamFreeDevice(l->k_id, 0); CdamFreeDevice(l->count, 0); CdamFreeDevice(l->cell_start, 0); CdamFreeDevice(l->chunk_sum, 0);
-    l->rate = l->sorted = l->sorted_r = l->k_tau = NULL;
-    l->cell_of = l->rank = l->slot = l->order = l->k_id = NULL;
-    l->count = l->cell_start = l->chunk_sum = NULL;
-}
 
 static void free_substrate(LaserState* l) {
     CdamFreeDevice(l->tri, 0); CdamFreeDevice(l->snode, 0); CdamFreeDevice(l->soff, 0); CdamFreeDevice(l->sface, 0);
@@ -70,7 +38,8 @@ void DflLaserFree(ParticleContext* ctx) {
     LaserState* l = x->laser;
     if (!l) return;
     HIPGUARD(hipStreamSynchronize(DflStream()));
-    free_particle_buffers(l);
+    DflParticleFieldsFree(ctx, DFL_PF_LASER);
+    CdamFreeDevice(l->count, 0); CdamFreeDevice(l->cell_start, 0); CdamFreeDevice(l->chunk_sum, 0);
     free_substrate(l);
     CdamFreeDevice(l->gw, 0);
     CdamFreeDevice(l->colkey, 0); CdamFreeDevice(l->col_T, 0); CdamFreeDevice(l->part, 0); CdamFreeDevice(l->tally, 0);
@@ -79,18 +48,10 @@ void DflLaserFree(ParticleContext* ctx) {
     x->laser = NULL;
 }
 
-static void particle_buffers(LaserState* l, index_type cap) {
+/* what the capacity sizes beside the table's per-particle buffers: the bins of the column sort; and a zero rate */
+static void bin_buffers(LaserState* l, index_type cap) {
     const ptrdiff_t n = cap > 0 ? cap : 1;
-    free_particle_buffers(l);
-    l->rate = (f64*)CdamMallocDevice(n * SIZE_OF(f64));
-    l->sorted = (f64*)CdamMallocDevice(n * 6 * SIZE_OF(f64));
-    l->sorted_r = (f64*)CdamMallocDevice(n * SIZE_OF(f64));
-    l->k_tau = (f64*)CdamMallocDevice(n * SIZE_OF(f64));
-    l->cell_of = (index_type*)CdamMallocDevice(n * SIZE_OF(index_type));
-    l->rank = (index_type*)CdamMallocDevice(n * SIZE_OF(index_type));
-    l->slot = (index_type*)CdamMallocDevice(n * SIZE_OF(index_type));
-    l->order = (index_type*)CdamMallocDevice(n * SIZE_OF(index_type));
-    l->k_id = (index_type*)CdamMallocDevice(n * SIZE_OF(index_type));
+    CdamFreeDevice(l->count, 0); CdamFreeDevice(l->cell_start, 0); CdamFreeDevice(l->chunk_sum, 0);
     hipStream_t s = DflStream();
     HIPGUARD(hipMemsetAsync(l->rate, 0, (size_t)n * sizeof(f64), s));
     /* the bins: every column, then one per 2^DFL_LASER_OUTSIDE_SHIFT particle ids for the particles outside the grid */
@@ -103,7 +64,6 @@ static void particle_buffers(LaserState* l, index_type cap) {
     HIPGUARD(hipMemsetAsync(l->cell_start, 0, ((size_t)nbin + 1) * sizeof(index_type), s));
     HIPGUARD(hipMemsetAsync(l->chunk_sum, 0, (size_t)nchunk * sizeof(index_type), s));
     l->nbin = nbin;
-    l->cap = cap;
 }
 
 /* the weights and per-column outputs of an n x n grid */
@@ -264,8 +224,9 @@ void ParticleContextSetLaser(ParticleContext* ctx, const DflLaser* cfg) {
     l->n = (index_type)nside;
     l->ncol = l->n * l->n;
     column_buffers(l);
-    particle_buffers(l, x->cap);
     x->laser = l;
+    DflParticleFieldsAlloc(ctx, DFL_PF_LASER);
+    bin_buffers(l, x->cap);
     build_substrate(ctx, l);
 }
 
@@ -276,7 +237,7 @@ void DflLaserCouplingChanged(ParticleContext* ctx) {
 
 void DflLaserCapacityChanged(ParticleContext* ctx) {
     LaserState* l = laser(ctx);
-    if (l && l->cap != ((ParticleExt*)ctx->ext)->cap) particle_buffers(l, ((ParticleExt*)ctx->ext)->cap);
+    if (l) bin_buffers(l, ((ParticleExt*)ctx->ext)->cap);
 }
 
 void DflLaserCopy(ParticleContext* dst, const ParticleContext* src) {

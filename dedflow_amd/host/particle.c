@@ -45,13 +45,13 @@ void ParticleContextDestroy(ParticleContext* ctx) {
     if (x) {
         CdamFreeDevice(x->cell_of, 0); CdamFreeDevice(x->rank, 0); CdamFreeDevice(x->slot, 0); CdamFreeDevice(x->order, 0); CdamFreeDevice(x->sorted, 0);
         CdamFreeDevice(x->count, 0); CdamFreeDevice(x->cell_start, 0); CdamFreeDevice(x->chunk_sum, 0);
-        DflCoupleFree(x->couple);
+        DflCoupleFree(ctx);
         DflWallsFree(x->walls);
         ParticleContextSetFriction(ctx, NULL);
-        DflFlowFree(x->flow);
+        DflFlowFree(ctx);
         ParticleContextSetSizes(ctx, NULL, NULL);
         DflLaserFree(ctx);
-        DflHeatFree(x->heat);
+        DflHeatFree(ctx);
         CdamFreeHost(x, SIZE_OF(ParticleExt));
     }
     CdamFreeHost(ctx, SIZE_OF(ParticleContext));
@@ -192,18 +192,11 @@ static void clear_history(ParticleExt* x, index_type P) {
 void ParticleContextSetFriction(ParticleContext* ctx, const DflContactFriction* cfg) {
     ParticleExt* x = (ParticleExt*)ctx->ext;
     const index_type P = ctx->num_particle;
-    const ptrdiff_t n = x->cap > 0 ? x->cap : 1;
     if (!cfg) {
         if (!x->omega) return;
         HIPGUARD(hipStreamSynchronize(DflStream()));
-        CdamFreeDevice(x->omega, 0); CdamFreeDevice(x->alpha, 0); CdamFreeDevice(x->sorted_w, 0); CdamFreeDevice(x->overflow, 0);
-        for (int k = 0; k < 2; ++k) {
-            CdamFreeDevice(x->hist[k], 0);
-            CdamFreeDevice(x->hist_count[k], 0);
-            x->hist[k] = NULL;
-            x->hist_count[k] = NULL;
-        }
-        x->omega = x->alpha = x->sorted_w = NULL;
+        DflParticleFieldsFree(ctx, DFL_PF_FRICTION);
+        CdamFreeDevice(x->overflow, 0);
         x->overflow = NULL;
         return;
     }
@@ -213,16 +206,11 @@ void ParticleContextSetFriction(ParticleContext* ctx, const DflContactFriction* 
     x->law.gamma_t = cfg->gamma_t >= 0.0 ? cfg->gamma_t : x->gamma_n;
     if (!x->omega) {
         hipStream_t s = DflStream();
-        x->omega = (f64*)CdamMallocDevice(n * 3 * SIZE_OF(f64));
-        x->alpha = (f64*)CdamMallocDevice(n * 3 * SIZE_OF(f64));
-        x->sorted_w = (f64*)CdamMallocDevice(n * 3 * SIZE_OF(f64));
+        const size_t n = (size_t)(x->cap > 0 ? x->cap : 1);
+        DflParticleFieldsAlloc(ctx, DFL_PF_FRICTION);
         x->overflow = (index_type*)CdamMallocDevice(SIZE_OF(index_type));
-        for (int k = 0; k < 2; ++k) {
-            x->hist[k] = (dfl_contact_hist*)CdamMallocDevice(n * DFL_DEM_MAX_HISTORY * SIZE_OF(dfl_contact_hist));
-            x->hist_count[k] = (index_type*)CdamMallocDevice(n * SIZE_OF(index_type));
-        }
-        HIPGUARD(hipMemsetAsync(x->omega, 0, (size_t)n * 3 * sizeof(f64), s));
-        HIPGUARD(hipMemsetAsync(x->alpha, 0, (size_t)n * 3 * sizeof(f64), s));
+        HIPGUARD(hipMemsetAsync(x->omega, 0, n * 3 * sizeof(f64), s));
+        HIPGUARD(hipMemsetAsync(x->alpha, 0, n * 3 * sizeof(f64), s));
     }
     clear_history(x, P);
 }
@@ -265,12 +253,7 @@ const f64* ParticleContextAngularAcc(const ParticleContext* ctx) { return ((cons
 
 index_type ParticleContextFrictionOverflowCount(const ParticleContext* ctx) {
     const ParticleExt* x = (const ParticleExt*)ctx->ext;
-    if (!x->overflow) return 0;
-    index_type n = 0;
-    hipStream_t s = DflStream();
-    HIPGUARD(hipMemcpyAsync(&n, x->overflow, sizeof n, D2H, s));
-    HIPGUARD(hipStreamSynchronize(s));
-    return n;
+    return x->overflow ? DflReadDeviceIndex(x->overflow) : 0;
 }
 
 void ParticleContextSetGravity(ParticleContext* ctx, const f64 g[3]) {
@@ -295,11 +278,11 @@ void DflInflowRadii(const ParticleContext* ctx, f64* r_lo, f64* r_hi) {
     *r_hi = x->in_sizes ? x->in_r_hi : ParticleRadius(ctx);
 }
 
-static void free_sizes(ParticleExt* x) {
+static void free_sizes(ParticleContext* ctx) {
+    ParticleExt* x = (ParticleExt*)ctx->ext;
     if (!x->radius) return;
     HIPGUARD(hipStreamSynchronize(DflStream()));
-    CdamFreeDevice(x->radius, 0); CdamFreeDevice(x->mass, 0); CdamFreeDevice(x->sorted_r, 0);
-    x->radius = x->mass = x->sorted_r = NULL;
+    DflParticleFieldsFree(ctx, DFL_PF_SIZES);
     x->in_sizes = FALSE;
     x->sort_valid = FALSE; /* the sorted copies and the grid were those of the per-particle sizes */
     x->rmax = 0.0;
@@ -308,7 +291,7 @@ static void free_sizes(ParticleExt* x) {
 void ParticleContextSetSizes(ParticleContext* ctx, const f64* radius, const f64* mass) {
     ParticleExt* x = (ParticleExt*)ctx->ext;
     if (!radius) {
-        free_sizes(x);
+        free_sizes(ctx);
         return;
     }
     const index_type P = ctx->num_particle;
@@ -326,7 +309,6 @@ void ParticleContextSetSizes(ParticleContext* ctx, const f64* radius, const f64*
         fprintf(stderr, "ParticleContextSetSizes: no masses and no positive reference particle; the sizes stay as they were\n");
         return;
     }
-    const ptrdiff_t n = x->cap > 0 ? x->cap : 1;
     f64* m = (f64*)malloc((size_t)(P > 0 ? P : 1) * sizeof(f64));
     for (index_type i = 0; i < P; ++i) {
         if (mass) {
@@ -336,11 +318,7 @@ void ParticleContextSetSizes(ParticleContext* ctx, const f64* radius, const f64*
             m[i] = M * ((q * q) * q);
         }
     }
-    if (!x->radius) {
-        x->radius = (f64*)CdamMallocDevice(n * SIZE_OF(f64));
-        x->mass = (f64*)CdamMallocDevice(n * SIZE_OF(f64));
-        x->sorted_r = (f64*)CdamMallocDevice(n * SIZE_OF(f64));
-    }
+    if (!x->radius) DflParticleFieldsAlloc(ctx, DFL_PF_SIZES);
     HIPGUARD(hipStreamSynchronize(DflStream()));
     if (P > 0) {
         HIPGUARD(hipMemcpy(x->radius, radius, (size_t)P * sizeof(f64), H2D));

@@ -515,7 +515,9 @@ void dfl_dem_spin(dfl_index P, dfl_value dt, dfl_value* omega, const dfl_value* 
  *    dfl_couple_locate        walk of every particle from tet[i] (or the seed-grid tet when tet[i] < 0); writes tet[i]
  *                             (-1 outside, -2 walk cap hit: *lost += 1) and lambda[i][4]; `order` (may be NULL) = the
  *                             thread -> particle map
- *    dfl_couple_fluid_step    drag + gravity + integration of every particle; imp[i][3] += drag impulse
+ *    dfl_couple_fluid_step    drag + gravity + integration of every particle; imp[i][3] += drag impulse.  With
+ *                             radius_i != NULL (per-particle sizes) d = 2 r_i, rho_p = m_i / (4/3 pi r_i^3) from mass_i /
+ *                             radius_i, and the scalars mass and radius are not read
  *    dfl_couple_sort_by_tet   members[tstart[t] .. tstart[t+1]) = the particles in tet t, ascending id; tcount[T] is
  *                             zero-initialised scratch that the call leaves zeroed again
  *    dfl_couple_node_load     load[3a + d] = -scale * sum_{e in V2E(a)} sum_{p in e} lambda_{p,k(a,e)} imp[p][d]
@@ -528,9 +530,9 @@ void dfl_couple_locate(dfl_index P, const dfl_index* order, const dfl_value* coo
                        const dfl_index* nbr, const dfl_index* seed, const dfl_value* grid_lo, const dfl_value* grid_inv_h,
                        dfl_index grid_dim, dfl_index* tet, dfl_value* lambda, dfl_index* lost, void* stream);
 void dfl_couple_fluid_step(dfl_index P, const dfl_index* order, const dfl_index* tet, const dfl_value* lambda,
-                           const dfl_index* ien, const dfl_value* w, dfl_value mass, dfl_value radius, dfl_value rho_f,
-                           dfl_value mu_f, const dfl_value* gravity, dfl_value dt, dfl_value* coord, dfl_value* vel,
-                           dfl_value* acc, dfl_value* imp, void* stream);
+                           const dfl_index* ien, const dfl_value* w, dfl_value mass, dfl_value radius, const dfl_value* mass_i,
+                           const dfl_value* radius_i, dfl_value rho_f, dfl_value mu_f, const dfl_value* gravity, dfl_value dt,
+                           dfl_value* coord, dfl_value* vel, dfl_value* acc, dfl_value* imp, void* stream);
 void dfl_couple_sort_by_tet(dfl_index P, dfl_index T, const dfl_index* tet, dfl_index* tcount, dfl_index* rank,
                             dfl_index* tstart, dfl_index* slot, dfl_index* members, void* scan_temp, int64_t scan_temp_bytes,
                             void* stream);
@@ -544,37 +546,35 @@ void dfl_couple_node_scalar(dfl_index N, const dfl_index* vrow, const dfl_index*
 /* ---- particle inflow and outflow (build-defined, opt-in; csrc/k_flow.hip, model in include/dedflow.h)
  *    dfl_flow_flag          keep[i] = 0 when particle i is beyond a plane (n . x > d) or, by_tet, at tet[i] == -1; else 1.
  *                           rtet (may be NULL; needs tet) = tet[i] of the removed particles, -1 for the kept ones
- *    dfl_flow_compact       stable scatter of every kept particle i to newid[i] (newid = exclusive scan of keep): the
- *                           [P][3] records of src3 / dst3, the tags, with tet_src != NULL tet and lambda, with hrow_src !=
- *                           NULL the live history entries (partner keys remapped through newid, entries of removed partners
- *                           dropped).  Destinations are distinct from every source
- *    dfl_inflow_block       blocked[nu nv] <- 0, then 1 for every slot whose candidate lies closer than 2R to a particle
+ *    dfl_flow_compact       stable scatter of every kept particle i to newid[i] (newid = exclusive scan of keep): every
+ *                           (src, dst) pair of dfl_flow_fields and, with hrow_src != NULL, the live history entries (partner
+ *                           keys remapped through newid, entries of removed partners dropped).  Destinations are distinct
+ *                           from every source
+ *    dfl_inflow_block       blocked[nu nv] <- 0, then 1 for every slot whose candidate lies closer than 2R to a particle;
+ *                           with radius_i != NULL (per-particle sizes) closer than r_y + r_k, r_k = r_lo + (r_hi - r_lo) u_k
+ *                           (include/dedflow.h), and the scalar radius is not read
  *    dfl_inflow_select      key_out / slot_out = the slots in ascending (rank key, slot): rank key H(c, k, 2) >> 1, 2^63
  *                           for a blocked slot; temp from dfl_inflow_select_temp_bytes
  *    dfl_inflow_append      the first `want` (<= nu nv) of the sorted slots that are free are appended at ids P, P+1, ...;
- *                           *count <- their number.  hist_count / tet / lambda / imp / omega / alpha may be NULL */
+ *                           *count <- their number.  hist_count / tet / lambda / imp / omega / alpha may be NULL; with
+ *                           radius_i != NULL also radius_i[i] = r_k and mass_i[i] = m0 ((q q) q), q = r_k / r0 */
 typedef struct dfl_outflow_planes {
     dfl_value plane[8][4];
     dfl_index num;
 } dfl_outflow_planes;
+/* what a compaction moves: (src, dst) pairs of per-particle arrays grouped by the bytes of one particle, 4 / 8 / 24 / 32:
+ * the pairs of group g are pair[first[g]] .. pair[first[g + 1] - 1]; and the friction history (hrow_src NULL: none) */
+#define DFL_FLOW_MAX_FIELDS 16
 typedef struct dfl_flow_fields {
-    const dfl_value* src3[6];
-    dfl_value* dst3[6];
-    int n3;
-    const int64_t* tag_src;
-    int64_t* tag_dst;
-    const dfl_index* tet_src;
-    dfl_index* tet_dst;
-    const dfl_value* lambda_src;
-    dfl_value* lambda_dst;
+    struct {
+        const void* src;
+        void* dst;
+    } pair[DFL_FLOW_MAX_FIELDS];
+    int first[5];
     const dfl_contact_hist* hrow_src;
     const dfl_index* hcount_src;
     dfl_contact_hist* hrow_dst;
     dfl_index* hcount_dst;
-    const dfl_value* src1[5];    /* [P] per-particle scalars (radius, mass of a polydisperse context; temperature, pending
-                                    energy and heat rate with particle heat on) */
-    dfl_value* dst1[5];
-    int n1;
 } dfl_flow_fields;
 /* the inlet lattice: the host constants of include/dedflow.h (base, pu, pv, ou, ov), the plane frame (o, unit uhat, vhat,
  * normal) and the prefilter widths of the blocking pass */
@@ -589,38 +589,27 @@ typedef struct dfl_inlet {
 void dfl_flow_flag(dfl_index P, const dfl_value* coord, dfl_outflow_planes planes, const dfl_index* tet, int by_tet,
                    dfl_index* keep, dfl_index* rtet, void* stream);
 void dfl_flow_compact(dfl_index P, const dfl_index* keep, const dfl_index* newid, dfl_flow_fields f, void* stream);
-void dfl_inflow_block(dfl_index P, const dfl_value* coord, dfl_inlet in, dfl_value radius, dfl_index* blocked, void* stream);
+void dfl_inflow_block(dfl_index P, const dfl_value* coord, dfl_inlet in, dfl_value radius, const dfl_value* radius_i,
+                      dfl_value r_lo, dfl_value r_hi, dfl_index* blocked, void* stream);
 int64_t dfl_inflow_select_temp_bytes(dfl_index nslot);
 void dfl_inflow_select(dfl_inlet in, const dfl_index* blocked, uint64_t* key, uint64_t* key_out, dfl_index* slot,
                        dfl_index* slot_out, void* temp, int64_t temp_bytes, void* stream);
 void dfl_inflow_append(dfl_index P, dfl_index want, dfl_inlet in, const uint64_t* key_sorted, const dfl_index* slot_sorted,
                        int64_t first_tag, dfl_value* coord, dfl_value* vel, dfl_value* acc,
                        int64_t* tag, dfl_value* omega, dfl_value* alpha, dfl_index* hist_count, dfl_index* tet,
-                       dfl_value* lambda, dfl_value* imp, dfl_index* count, void* stream);
+                       dfl_value* lambda, dfl_value* imp, dfl_value* radius_i, dfl_value* mass_i, dfl_value r_lo,
+                       dfl_value r_hi, dfl_value r0, dfl_value m0, dfl_index* count, void* stream);
 
 /* ---- polydisperse particles (build-defined, opt-in; model in include/dedflow.h, "polydisperse particles")
  *  dfl_sizes            per-particle radius and mass (device [P], by particle id), the radii in the sweep's cell order
- *                       (sorted_r [P], written by the cell sort) and rmax >= every radius (the search range and the grids)
- *    dfl_couple_fluid_step_sizes   the coupled sub-step with d = 2 r_i, rho_p = m_i / (4/3 pi r_i^3)
- *    dfl_inflow_block_sizes        blocked when dist^2 < (r_y + r_k)^2, r_k = r_lo + (r_hi - r_lo) u_k (include/dedflow.h)
- *    dfl_inflow_append_sizes       dfl_inflow_append that also writes radius[i] = r_k and mass[i] = m0 ((q q) q), q = r_k / r0 */
+ *                       (sorted_r [P], written by the cell sort) and rmax >= every radius (the search range and the grids).
+ *  A launcher takes the per-particle arrays as optional arguments: not NULL selects its per-particle-size variant */
 typedef struct dfl_sizes {
     const dfl_value* radius;
     const dfl_value* mass;
     const dfl_value* sorted_r;
     dfl_value rmax;
 } dfl_sizes;
-void dfl_couple_fluid_step_sizes(dfl_index P, const dfl_index* order, const dfl_index* tet, const dfl_value* lambda,
-                                 const dfl_index* ien, const dfl_value* w, const dfl_value* mass, const dfl_value* radius,
-                                 dfl_value rho_f, dfl_value mu_f, const dfl_value* gravity, dfl_value dt, dfl_value* coord,
-                                 dfl_value* vel, dfl_value* acc, dfl_value* imp, void* stream);
-void dfl_inflow_block_sizes(dfl_index P, const dfl_value* coord, dfl_inlet in, const dfl_value* radius, dfl_value r_lo,
-                            dfl_value r_hi, dfl_index* blocked, void* stream);
-void dfl_inflow_append_sizes(dfl_index P, dfl_index want, dfl_inlet in, const uint64_t* key_sorted,
-                             const dfl_index* slot_sorted, int64_t first_tag, dfl_value* coord, dfl_value* vel, dfl_value* acc,
-                             int64_t* tag, dfl_value* omega, dfl_value* alpha, dfl_index* hist_count, dfl_index* tet,
-                             dfl_value* lambda, dfl_value* imp, dfl_value* radius, dfl_value* mass, dfl_value r_lo,
-                             dfl_value r_hi, dfl_value r0, dfl_value m0, dfl_index* count, void* stream);
 
 /* ---- DEM contact sweep: launchers (csrc/k_dem.hip, csrc/k_walls.hip, csrc/dem_sweep.hpp)
  * One sweep is a cell sort and one force kernel, on the unit box (dfl_dem_*) or on a mesh's grid (dfl_walls_*), all on

@@ -192,6 +192,110 @@ def test_outside_mesh_removes_what_left_through_an_open_group(api):
         P.close()
 
 
+def _all_fields(pc, api):
+    """every carried per-particle field the API exposes, the history and the tags, copied to the host"""
+    s = _state(pc, api, friction=True, coupled=True)
+    s.update(r=pc.radii(), m=pc.masses(), T=pc.temperature(), e=pc._pending_energy(), rate=pc.heat_rate())
+    return s
+
+
+CARRIED = ("x", "v", "a", "w", "alpha", "r", "m", "T", "e", "rate", "tet", "lam", "tag")
+
+
+def _assert_history_rows(after, nk, nx, nc):
+    assert np.array_equal(after["hc"][:len(nc)], nc)
+    for j in range(len(nc)):
+        assert np.array_equal(after["hk"][j, :nc[j]], nk[j, :nc[j]]), j
+        assert np.array_equal(after["hx"][j, :nc[j]], nx[j, :nc[j]]), j
+
+
+def _assert_gathered(after, before, keep):
+    """after == before[keep] for every carried field, bit for bit; the history rows remapped as flow_model.remap_history"""
+    for k in CARRIED:
+        assert after[k].dtype == before[k].dtype and np.array_equal(after[k], before[k][keep]), k
+    _assert_history_rows(after, *fl.remap_history(before["hk"], before["hx"], before["hc"], keep))
+
+
+def test_every_field_follows_its_tag_with_everything_on(api):
+    """friction, sizes, heat, coupling and a laser on one context whose count changes: remove, add with growth, remove.
+    Every carried field must follow its particle; the expected values are the host copies indexed by the survivors"""
+    m = kuhn_cube(4)
+    wg, _ = synthetic_fields(m)
+    w_d = api.DeviceArray.from_numpy(wg)
+    rng = np.random.default_rng(11)
+    r_lo, r_hi, T_init, N0 = 0.003, 0.005, 300.0, 400
+    # 200 points and, 1.5 r_lo from each, a partner: 200 overlapping pairs, so that the history is live
+    base = 0.1 + 0.8 * _inside(m, N0 // 2, 12)
+    d = rng.normal(size=base.shape)
+    x = np.concatenate([base, base + 1.5 * r_lo * d / np.linalg.norm(d, axis=1, keepdims=True)])
+    x = x[rng.permutation(N0)]
+    v = rng.normal(0, 0.3, x.shape)
+    r = rng.uniform(r_lo, r_hi, N0)
+    P = api.Problem(m)
+    pc = api.Particles(x.reshape(-1), v.reshape(-1), r_hi, mass=_mass(r_hi, 7800.0), dt=1e-4)
+    try:
+        pc.set_friction(0.5)
+        pc.set_sizes(r, _mass(r, 7800.0) * rng.uniform(0.9, 1.1, N0))
+        pc.set_inflow_sizes(r_lo, r_hi)
+        pc.set_heat(cp_p=500.0, k_p=20.0, T_init=T_init)
+        pc.set_temperature(rng.uniform(300.0, 400.0, N0))
+        pc.couple(P)
+        pc.set_laser((0.5037, 0.4961, 1.5), (0.0, 0.0, -1.0), power=400.0, w=0.06, h=0.0113, r_cut=0.12, eta_p=0.35, eta_s=0.45)
+        assert pc.laser_on
+        pc.set_outflow([(1.0, 0.0, 0.0, 0.62)])
+        for _ in range(4):
+            pc.fluid_step(w_d)
+        s0 = _all_fields(pc, api)
+        assert np.array_equal(s0["tag"], np.arange(N0)) and s0["hc"].sum() >= 100 and (s0["tet"] >= 0).sum() > N0 // 2
+        for k in ("a", "w", "alpha", "e", "rate", "lam"):
+            assert np.count_nonzero(s0[k]) > 0, k
+        assert np.count_nonzero(pc.laser_rate()) > 0
+
+        # 1. remove about a third
+        keep = fl.outflow_keep(s0["x"], [(1.0, 0.0, 0.0, 0.62)])
+        P0 = int(keep.sum())
+        assert N0 // 2 < P0 < 3 * N0 // 4
+        pc.remove()
+        s1 = _all_fields(pc, api)
+        assert pc.P == P0
+        _assert_gathered(s1, s0, keep)
+
+        # 2. add more than half of P0: the capacity (400) must grow
+        vel_in = (0.0, 0.0, -0.5)
+        pc.set_inflow((0.1, 0.1, 0.95), (0.8, 0.0, 0.0), (0.0, 0.8, 0.0), vel=vel_in, per_call=P0 // 2 + 60, seed=5)
+        pc.add()
+        s2 = _all_fields(pc, api)
+        n = pc.P - P0
+        assert n > P0 // 2 and pc.P > N0 and pc.flow_stats()["inserted"] == n
+        for k in CARRIED:
+            assert np.array_equal(s2[k][:P0], s1[k]), k
+        _assert_history_rows(s2, s1["hk"], s1["hx"], s1["hc"])
+        new = slice(P0, P0 + n)
+        assert (s2["T"][new] == T_init).all() and not s2["e"][new].any() and not s2["rate"][new].any()
+        assert not s2["w"][new].any() and not s2["alpha"][new].any() and not s2["a"][new].any() and not s2["hc"][new].any()
+        assert (s2["tet"][new] == -1).all() and not s2["lam"][new].any()
+        assert (s2["r"][new] >= r_lo).all() and (s2["r"][new] <= r_hi).all() and len(np.unique(s2["r"][new])) > n // 2
+        q = s2["r"][new] / r_hi
+        assert np.array_equal(s2["m"][new], _mass(r_hi, 7800.0) * ((q * q) * q))
+        assert np.array_equal(s2["v"][new], np.tile(vel_in, (n, 1))) and np.array_equal(s2["tag"][new], N0 + np.arange(n))
+
+        # 3. remove again, by another plane
+        planes = [(0.0, 1.0, 0.0, 0.55)]
+        pc.set_outflow(planes)
+        keep = fl.outflow_keep(s2["x"], planes)
+        assert 0 < keep[:P0].sum() < P0 and 0 < keep[P0:].sum() < n
+        pc.remove()
+        s3 = _all_fields(pc, api)
+        assert pc.P == keep.sum()
+        _assert_gathered(s3, s2, keep)
+        pc.fluid_step(w_d)
+        api.sync()
+        assert np.isfinite(pc.arrays()[2]).all() and np.isfinite(pc.temperature()).all()
+    finally:
+        pc.close()
+        P.close()
+
+
 def _inflow_setup(R=0.03, jitter=0.6, seed=1234, per_call=25.5, max_particles=10 ** 6):
     origin, u, v = (0.1, 0.1, 0.9), (0.8, 0.0, 0.0), (0.0, 0.8, 0.0)
     inlet = fl.Inlet(origin, u, v, R, jitter=jitter, seed=seed)
