@@ -23,11 +23,10 @@ __global__ __launch_bounds__(BLK) void galerkin_kernel(I nnzc, const I* __restri
     if (g == 0) vc[w * 16 + e] = acc;
 }
 
-// rc[I] = sum of r over the nodes of aggregate I (node lists: anode[aoff[I] .. aoff[I+1])), 4 components.
+// rc[I] = sum of r - sub over the nodes of aggregate I (node lists: anode[aoff[I] .. aoff[I+1])), 4 components.
 // One wave per aggregate: 16 nodes x 4 components per trip.
-// DIFF: the restricted vector is r - s (the residual r - A z with s = A z left by a plain matvec: the general
-// y = b y + a A x form of the matvec is 0.70 ms at 10M tets against 0.59 ms, and the copy of r goes as well)
-template <bool DIFF>
+// The restricted vector is the residual r - A z with sub = A z left by a plain matvec: the general y = b y + a A x form of
+// the matvec is 0.70 ms at 10M tets against 0.59 ms, and the copy of r goes as well.
 __global__ __launch_bounds__(BLK) void restrict_kernel(I Nc, const I* __restrict__ aoff, const I* __restrict__ anode, I N,
                                                       const T* __restrict__ r, const T* __restrict__ sub, T* __restrict__ rc) {
     const long long w = ((long long)blockIdx.x * BLK + threadIdx.x) >> 6;
@@ -38,7 +37,7 @@ __global__ __launch_bounds__(BLK) void restrict_kernel(I Nc, const I* __restrict
     for (int k = lo + g; k < hi; k += 16) {
         const long long n = anode[k];
         const long long i = c < 3 ? 3 * n + c : 3LL * N + n;
-        acc += DIFF ? r[i] - sub[i] : r[i];
+        acc += r[i] - sub[i];
     }
 #pragma unroll
     for (int s = 4; s < 64; s <<= 1) acc += __shfl_xor(acc, s, WAVE);
@@ -66,23 +65,15 @@ void dfl_amg_galerkin(I nnzc, const I* off, const I* idx, const T* val_fine, T* 
     galerkin_kernel<<<ceil_div((long long)nnzc * 64, BLK), BLK, 0, S(stream)>>>(nnzc, off, idx, val_fine, val_coarse);
     DFL_LAUNCH_CHECK();
 }
-void dfl_amg_restrict(I Nc, const I* aoff, const I* anode, I N, const T* r, T* rc, void* stream) {
-    if (Nc <= 0) return;
-    restrict_kernel<false><<<ceil_div((long long)Nc * 64, BLK), BLK, 0, S(stream)>>>(Nc, aoff, anode, N, r, nullptr, rc);
-    DFL_LAUNCH_CHECK();
-}
 void dfl_amg_restrict_diff(I Nc, const I* aoff, const I* anode, I N, const T* r, const T* sub, T* rc, void* stream) {
     if (Nc <= 0) return;
-    restrict_kernel<true><<<ceil_div((long long)Nc * 64, BLK), BLK, 0, S(stream)>>>(Nc, aoff, anode, N, r, sub, rc);
+    restrict_kernel<<<ceil_div((long long)Nc * 64, BLK), BLK, 0, S(stream)>>>(Nc, aoff, anode, N, r, sub, rc);
     DFL_LAUNCH_CHECK();
 }
 void dfl_amg_prolong_add_rows(I nrows, I N, const I* agg, I Nc, const T* xc, T* z, void* stream) {
     if (nrows <= 0) return;
     prolong_add_kernel<<<ceil_div(nrows, BLK), BLK, 0, S(stream)>>>(nrows, N, agg, Nc, xc, z);
     DFL_LAUNCH_CHECK();
-}
-void dfl_amg_prolong_add(I N, const I* agg, I Nc, const T* xc, T* z, void* stream) {
-    dfl_amg_prolong_add_rows(N, N, agg, Nc, xc, z, stream);
 }
 
 }  // extern "C"

@@ -1,322 +1,25 @@
 /* PC_AMGX: a native scalar algebraic multigrid behind the reference's PCCreateAMGX (pc.c:160-235, 279-295), with the
  * configuration the reference sketches at krylov.c:413-437 (AGGREGATION, SIZE_2, MULTICOLOR_DILU, V(0,3), omega 0.75,
- * DENSE_LU_SOLVER on >= 32 rows).  Kernels: csrc/k_amgx.hip.  Algorithm, and why the coarsest solve tolerates a singular
- * matrix: DESIGN.md "PC_AMGX".
+ * DENSE_LU_SOLVER on >= 32 rows).  Kernels: csrc/k_amgx.hip.  Options: amgx_config.c.  Algorithm, and why the coarsest solve
+ * tolerates a singular matrix: DESIGN.md "PC_AMGX".
  *
  * Structure (aggregates, Galerkin patterns and lists, colourings) is built on the host ONCE, in PCCreateAMGX, from the
  * values the matrix holds then -- as AMGX_solver_setup does in the reference's create -- and again only by PCAMGXRebuild.
+ * amgx_build goes one level at a time: amgx_host_level (no HIP) completes the level's host structure from its matrix,
+ * amgx_upload_level puts it on the device, amgx_galerkin_host forms the next level's matrix, and the level's host arrays
+ * are freed.  The bucket lists (aggregate members, colour rows, Galerkin lists) come from csr_lists.h.
  * PCSetup recomputes every value on the device from the current fine values: Galerkin sums in list order, the smoother's
  * diagonal, the dense LU of the coarsest level.  Levels with more than `tail_rows` rows run one launch per colour and
- * triangular pass; all smaller levels and the coarse solve run in one launch of one workgroup (setup and cycle alike).
- *
- * Options: NULL (the reference configuration), an inline AMGX string "config_version=2, key=value, ..." or the path of a
- * file holding that string or AMGX's JSON form.  The AMG parameters come from the preconditioner scope
- * (solver:preconditioner:*, JSON "preconditioner") when there is one, else from the top-level solver scope; outer-solver
- * keys (solver=FGMRES, tolerance, gmres_n_restart, ...) are ignored -- the Krylov object governs those. */
-#include <ctype.h>
+ * triangular pass; all smaller levels and the coarse solve run in one launch of one workgroup (setup and cycle alike). */
 #include <math.h>
-#include <stdarg.h>
+#include <stddef.h>
 #include <string.h>
 #include "dedflow.h"
 #include "dedflow_kernels.h"
 #include "host_private.h"
-
-/* ============================== options ================================================ */
-#define AMGX_MAX_PAIRS 512
-#define AMGX_STR 160
-typedef struct AmgxPair {
-    char path[AMGX_STR]; /* scope components and key, ':'-separated, "(name)" annotations removed */
-    char val[AMGX_STR];
-} AmgxPair;
-typedef struct AmgxPairs {
-    int n;
-    AmgxPair p[AMGX_MAX_PAIRS];
-    char pre_name[AMGX_STR]; /* "solver:preconditioner(amg)=AMG" names the preconditioner scope "amg" */
-} AmgxPairs;
-
-static void amgx_trim(char* s) {
-    size_t n = strlen(s), a = 0;
-    while (a < n && isspace((unsigned char)s[a])) ++a;
-    while (n > a && isspace((unsigned char)s[n - 1])) --n;
-    memmove(s, s + a, n - a);
-    s[n - a] = '\0';
-}
-static void amgx_strip_quotes(char* s) {
-    size_t n = strlen(s);
-    if (n >= 2 && ((s[0] == '"' && s[n - 1] == '"') || (s[0] == '\'' && s[n - 1] == '\''))) {
-        memmove(s, s + 1, n - 2);
-        s[n - 2] = '\0';
-    }
-}
-static int amgx_add(AmgxPairs* P, const char* path, const char* val) {
-    if (P->n >= AMGX_MAX_PAIRS || strlen(path) >= AMGX_STR || strlen(val) >= AMGX_STR) return -1;
-    /* "(name)" annotations: "preconditioner(amg)" names the preconditioner scope */
-    char clean[AMGX_STR];
-    size_t o = 0;
-    for (const char* c = path; *c;) {
-        if (*c == '(') {
-            const char* e = strchr(c, ')');
-            if (!e) return -1;
-            if (o >= strlen("preconditioner") && strncmp(clean + o - strlen("preconditioner"), "preconditioner", 14) == 0 &&
-                (size_t)(e - c - 1) < AMGX_STR) {
-                memcpy(P->pre_name, c + 1, (size_t)(e - c - 1));
-                P->pre_name[e - c - 1] = '\0';
-            }
-            c = e + 1;
-            continue;
-        }
-        clean[o++] = *c++;
-    }
-    clean[o] = '\0';
-    strcpy(P->p[P->n].path, clean);
-    strcpy(P->p[P->n].val, val);
-    amgx_trim(P->p[P->n].path);
-    amgx_trim(P->p[P->n].val);
-    amgx_strip_quotes(P->p[P->n].val);
-    P->n++;
-    return 0;
-}
-
-/* "key=value, key=value, ..." */
-static int amgx_parse_inline(const char* text, AmgxPairs* P) {
-    const char* s = text;
-    while (*s) {
-        const char* e = strchr(s, ',');
-        size_t len = e ? (size_t)(e - s) : strlen(s);
-        char tok[2 * AMGX_STR];
-        if (len >= sizeof tok) return -1;
-        memcpy(tok, s, len);
-        tok[len] = '\0';
-        amgx_trim(tok);
-        if (tok[0]) {
-            char* eq = strchr(tok, '=');
-            if (!eq) return -1;
-            *eq = '\0';
-            if (amgx_add(P, tok, eq + 1)) return -1;
-        }
-        if (!e) break;
-        s = e + 1;
-    }
-    return 0;
-}
-
-/* minimal JSON: objects, strings, numbers (and true / false / null as words); nested objects become path components */
-typedef struct { const char* s; } JsonCur;
-static void js_ws(JsonCur* c) { while (*c->s && isspace((unsigned char)*c->s)) c->s++; }
-static int js_string(JsonCur* c, char* out, size_t cap) {
-    if (*c->s != '"') return -1;
-    c->s++;
-    size_t o = 0;
-    while (*c->s && *c->s != '"') {
-        char ch = *c->s++;
-        if (ch == '\\' && *c->s) ch = *c->s++;
-        if (o + 1 >= cap) return -1;
-        out[o++] = ch;
-    }
-    if (*c->s != '"') return -1;
-    c->s++;
-    out[o] = '\0';
-    return 0;
-}
-static int js_object(JsonCur* c, const char* prefix, AmgxPairs* P, int depth) {
-    if (depth > 16) return -1;
-    js_ws(c);
-    if (*c->s != '{') return -1;
-    c->s++;
-    js_ws(c);
-    if (*c->s == '}') { c->s++; return 0; }
-    for (;;) {
-        char key[AMGX_STR], path[AMGX_STR];
-        js_ws(c);
-        if (js_string(c, key, sizeof key)) return -1;
-        js_ws(c);
-        if (*c->s != ':') return -1;
-        c->s++;
-        js_ws(c);
-        if (snprintf(path, sizeof path, "%s%s%s", prefix, prefix[0] ? ":" : "", key) >= (int)sizeof path) return -1;
-        if (*c->s == '{') {
-            if (js_object(c, path, P, depth + 1)) return -1;
-        } else {
-            char val[AMGX_STR];
-            if (*c->s == '"') {
-                if (js_string(c, val, sizeof val)) return -1;
-            } else {
-                size_t o = 0;
-                while (*c->s && *c->s != ',' && *c->s != '}' && !isspace((unsigned char)*c->s)) {
-                    if (o + 1 >= sizeof val) return -1;
-                    val[o++] = *c->s++;
-                }
-                val[o] = '\0';
-                if (!o) return -1;
-            }
-            if (amgx_add(P, path, val)) return -1;
-        }
-        js_ws(c);
-        if (*c->s == ',') { c->s++; continue; }
-        if (*c->s == '}') { c->s++; return 0; }
-        return -1;
-    }
-}
-
-static int amgx_in(const char* name, const char* const* list) {
-    for (int i = 0; list[i]; ++i)
-        if (strcmp(name, list[i]) == 0) return 1;
-    return 0;
-}
-static int amgx_err(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    fprintf(stderr, "PCCreateAMGX: ");
-    vfprintf(stderr, fmt, ap);
-    fprintf(stderr, "\n");
-    va_end(ap);
-    return -1;
-}
-static int amgx_int(const char* key, const char* v, int lo, int32_t* out) {
-    char* end;
-    long x = strtol(v, &end, 10);
-    if (end == v || *end || x < lo || x > 1000000) return amgx_err("%s=%s: expected an integer >= %d", key, v, lo);
-    *out = (int32_t)x;
-    return 0;
-}
-
-static void amgx_defaults(DflAMGXConfig* c) { /* krylov.c:413-437 */
-    memset(c, 0, sizeof *c);
-    c->relaxation_factor = 0.75;
-    c->selector_passes = 1;
-    c->smoother = DFL_AMGX_SMOOTHER_DILU;
-    c->presweeps = 0;
-    c->postsweeps = 3;
-    c->max_levels = 100;
-    c->min_coarse_rows = 32;
-    c->max_iters = 1;
-}
-
-int DflAMGXParseConfig(const char* options, DflAMGXConfig* cfg) {
-    amgx_defaults(cfg);
-    if (!options) return 0;
-    /* a readable file holds the configuration; anything else is the configuration itself */
-    char* text = NULL;
-    FILE* f = fopen(options, "rb");
-    if (f) {
-        fseek(f, 0, SEEK_END);
-        long len = ftell(f);
-        fseek(f, 0, SEEK_SET);
-        if (len < 0 || len > (1 << 20)) { fclose(f); return amgx_err("%s: unreadable or too large", options); }
-        text = (char*)malloc((size_t)len + 1);
-        size_t got = fread(text, 1, (size_t)len, f);
-        text[got] = '\0';
-        fclose(f);
-    } else {
-        text = strdup(options);
-    }
-    AmgxPairs* P = (AmgxPairs*)calloc(1, sizeof(AmgxPairs));
-    const char* t = text;
-    while (*t && isspace((unsigned char)*t)) ++t;
-    int rc;
-    if (*t == '{') {
-        JsonCur c = {t};
-        rc = js_object(&c, "", P, 0);
-        js_ws(&c);
-        if (!rc && *c.s) rc = -1;
-    } else {
-        /* a file may spread the inline form over lines */
-        for (char* q = text; *q; ++q)
-            if (*q == '\n' || *q == '\r') *q = ' ';
-        rc = amgx_parse_inline(t, P);
-    }
-    free(text);
-    if (rc) {
-        free(P);
-        return amgx_err("cannot parse the configuration");
-    }
-    /* scope of every pair: preconditioner (a "preconditioner" component, or the named preconditioner scope) or top */
-    static const char* const amg_keys[] = {"algorithm", "selector", "smoother", "presweeps", "postsweeps", "relaxation_factor",
-                                           "max_levels", "min_coarse_rows", "coarse_solver", "cycle", "max_iters", "solver", NULL};
-    static const char* const ignored[] = {"config_version", "scope", "monitor_residual", "convergence", "tolerance", "norm",
-                                          "print_solve_stats", "print_grid_stats", "obtain_timings", "use_scalar_norm",
-                                          "gmres_n_restart", "error_scaling", "max_uncolored_percentage",
-                                          "matrix_coloring_scheme", "store_res_history", "print_config", "determinism_flag",
-                                          "exception_handling", "print_vis_data", "preconditioner", NULL};
-    int scope[AMGX_MAX_PAIRS];
-    int has_pre = 0;
-    for (int i = 0; i < P->n; ++i) {
-        char tmp[AMGX_STR];
-        strcpy(tmp, P->p[i].path);
-        char* last = strrchr(tmp, ':');
-        scope[i] = 0;
-        if (last) {
-            *last = '\0';
-            for (char* tok = strtok(tmp, ":"); tok; tok = strtok(NULL, ":")) {
-                amgx_trim(tok);
-                if (strcmp(tok, "preconditioner") == 0 || (P->pre_name[0] && strcmp(tok, P->pre_name) == 0)) scope[i] = 1;
-            }
-        }
-        has_pre |= scope[i];
-    }
-    char unknown[1024] = "";
-    rc = 0;
-    for (int i = 0; i < P->n && !rc; ++i) {
-        const char* key = strrchr(P->p[i].path, ':');
-        key = key ? key + 1 : P->p[i].path;
-        const char* v = P->p[i].val;
-        const int amg_scope = has_pre ? scope[i] == 1 : 1;
-        if (amgx_in(key, ignored)) continue;
-        if (!amgx_in(key, amg_keys)) {
-            cfg->unknown_keys++;
-            if (strlen(unknown) + strlen(P->p[i].path) + 3 < sizeof unknown) {
-                if (unknown[0]) strcat(unknown, ", ");
-                strcat(unknown, P->p[i].path);
-            }
-            continue;
-        }
-        if (!amg_scope) continue; /* the outer solver's keys: the Krylov object governs those */
-        if (strcmp(key, "solver") == 0) {
-            if (has_pre && strcmp(v, "AMG") != 0) rc = amgx_err("solver=%s: only AMG is supported as the preconditioner", v);
-        } else if (strcmp(key, "algorithm") == 0) {
-            if (strcmp(v, "AGGREGATION") != 0) rc = amgx_err("algorithm=%s: only AGGREGATION is supported", v);
-        } else if (strcmp(key, "selector") == 0) {
-            if (strcmp(v, "SIZE_2") == 0) cfg->selector_passes = 1;
-            else if (strcmp(v, "SIZE_4") == 0) cfg->selector_passes = 2;
-            else if (strcmp(v, "SIZE_8") == 0) cfg->selector_passes = 3;
-            else rc = amgx_err("selector=%s: supported are SIZE_2, SIZE_4, SIZE_8", v);
-        } else if (strcmp(key, "smoother") == 0) {
-            if (strcmp(v, "MULTICOLOR_DILU") == 0) cfg->smoother = DFL_AMGX_SMOOTHER_DILU;
-            else if (strcmp(v, "BLOCK_JACOBI") == 0) cfg->smoother = DFL_AMGX_SMOOTHER_JACOBI;
-            else rc = amgx_err("smoother=%s: supported are MULTICOLOR_DILU, BLOCK_JACOBI", v);
-        } else if (strcmp(key, "coarse_solver") == 0) {
-            if (strcmp(v, "DENSE_LU_SOLVER") != 0) rc = amgx_err("coarse_solver=%s: only DENSE_LU_SOLVER is supported", v);
-        } else if (strcmp(key, "cycle") == 0) {
-            if (strcmp(v, "V") != 0) rc = amgx_err("cycle=%s: only V is supported", v);
-        } else if (strcmp(key, "relaxation_factor") == 0) {
-            char* end;
-            double x = strtod(v, &end);
-            if (end == v || *end || !(x > 0.0) || !isfinite(x)) rc = amgx_err("relaxation_factor=%s: expected a positive number", v);
-            else cfg->relaxation_factor = x;
-        } else if (strcmp(key, "presweeps") == 0) rc = amgx_int(key, v, 0, &cfg->presweeps);
-        else if (strcmp(key, "postsweeps") == 0) rc = amgx_int(key, v, 0, &cfg->postsweeps);
-        else if (strcmp(key, "max_levels") == 0) rc = amgx_int(key, v, 1, &cfg->max_levels);
-        else if (strcmp(key, "min_coarse_rows") == 0) rc = amgx_int(key, v, 1, &cfg->min_coarse_rows);
-        else if (strcmp(key, "max_iters") == 0) rc = amgx_int(key, v, 1, &cfg->max_iters);
-    }
-    if (unknown[0]) fprintf(stderr, "PCCreateAMGX: ignoring unknown option keys: %s\n", unknown);
-    free(P);
-    return rc;
-}
+#include "csr_lists.h"
 
 /* ============================== hierarchy (host) ======================================= */
-/* position of column j in row i (columns ascending), -1 if not stored */
-static index_type amgx_find(const index_type* rp, const index_type* ci, index_type i, index_type j) {
-    index_type lo = rp[i], hi = rp[i + 1] - 1;
-    while (lo <= hi) {
-        const index_type mid = lo + (hi - lo) / 2;
-        if (ci[mid] == j) return mid;
-        if (ci[mid] < j) lo = mid + 1;
-        else hi = mid - 1;
-    }
-    return -1;
-}
-
 /* one pairwise pass.  Strength w_ij = (|a_ij|/|a_ii| + |a_ji|/|a_jj|) / 2 (a_ji = 0 if not stored; a ratio with a zero
  * diagonal counts 0); only neighbours with w_ij > 0 count.  Four handshake rounds: every unaggregated row picks its
  * strongest unaggregated neighbour (ties: the smaller column), mutual picks become pairs.  A row left over joins the
@@ -329,14 +32,14 @@ static index_type amgx_pairwise(index_type n, const index_type* rp, const index_
     index_type* label = (index_type*)malloc(sizeof(index_type) * (size_t)(n > 0 ? n : 1));
     index_type* pick = (index_type*)malloc(sizeof(index_type) * (size_t)(n > 0 ? n : 1));
     for (index_type i = 0; i < n; ++i) {
-        const index_type d = amgx_find(rp, ci, i, i);
+        const index_type d = csr_find(rp, ci, i, i);
         dg[i] = d >= 0 ? fabs(val[d]) : 0.0;
     }
     for (index_type i = 0; i < n; ++i)
         for (index_type k = rp[i]; k < rp[i + 1]; ++k) {
             const index_type j = ci[k];
             if (j == i) { w[k] = 0.0; continue; }
-            const index_type t = amgx_find(rp, ci, j, i);
+            const index_type t = csr_find(rp, ci, j, i);
             const f64 aij = dg[i] > 0.0 ? fabs(val[k]) / dg[i] : 0.0;
             const f64 aji = (t >= 0 && dg[j] > 0.0) ? fabs(val[t]) / dg[j] : 0.0;
             w[k] = 0.5 * (aij + aji);
@@ -392,114 +95,115 @@ static index_type amgx_pairwise(index_type n, const index_type* rp, const index_
     return nc;
 }
 
-/* Galerkin structure of P^T A P for the map agg (nc aggregates): coarse pattern (columns ascending), per coarse nonzero the
- * ascending list of fine nonzeros summed into it, and (if val) the coarse values in that order */
-typedef struct AmgxGal {
-    index_type nc, nnz;
-    index_type *rp, *ci, *goff, *gidx;
+/* One level on the host.  All arrays are owned here (amgx_host_free).  The matrix (and, below level 0, the Galerkin lists
+ * that produced it) comes first; amgx_host_level completes the rest from it. */
+typedef struct AmgxHost {
+    index_type n, nnz;
+    index_type *rp, *ci;
     f64* val;
-} AmgxGal;
+    index_type *goff, *gidx;             /* NULL on level 0 */
+    index_type *diag, *trans;            /* position of a_ii; of a_ji for every a_ij (-1: not stored) */
+    index_type ncolor, *color, *coff, *rows;
+    index_type nc, *agg, *aoff, *amem;   /* nc == 0: the coarsest level, no map */
+} AmgxHost;
+
+/* everything but the matrix and the map with its members (what the Galerkin product of the next level reads) */
+static void amgx_host_free_structure(AmgxHost* H) {
+    free(H->goff);
+    free(H->gidx);
+    free(H->diag);
+    free(H->trans);
+    free(H->color);
+    free(H->coff);
+    free(H->rows);
+    H->goff = H->gidx = H->diag = H->trans = H->color = H->coff = H->rows = NULL;
+}
+static void amgx_host_free(AmgxHost* H) {
+    amgx_host_free_structure(H);
+    free(H->rp);
+    free(H->ci);
+    free(H->val);
+    free(H->agg);
+    free(H->aoff);
+    free(H->amem);
+    memset(H, 0, sizeof *H);
+}
+
+/* The next level C = P^T A P for the map agg (nc aggregates, members amem[aoff[c] .. aoff[c+1]) ascending): pattern (columns
+ * ascending), per coarse nonzero the ascending list of fine nonzeros summed into it, and the values in that order */
 static void amgx_galerkin_host(index_type n, const index_type* rp, const index_type* ci, const f64* val, const index_type* agg,
-                               index_type nc, AmgxGal* G) {
-    index_type* aoff = (index_type*)calloc((size_t)nc + 1, sizeof(index_type));
-    index_type* amem = (index_type*)malloc(sizeof(index_type) * (size_t)(n > 0 ? n : 1));
-    for (index_type i = 0; i < n; ++i) aoff[agg[i] + 1]++;
-    for (index_type c = 0; c < nc; ++c) aoff[c + 1] += aoff[c];
-    index_type* cur = (index_type*)malloc(sizeof(index_type) * (size_t)(nc + 1));
-    memcpy(cur, aoff, sizeof(index_type) * (size_t)nc);
-    for (index_type i = 0; i < n; ++i) amem[cur[agg[i]]++] = i;
+                               index_type nc, const index_type* aoff, const index_type* amem, AmgxHost* C) {
+    memset(C, 0, sizeof *C);
     index_type* mark = (index_type*)malloc(sizeof(index_type) * (size_t)(nc > 0 ? nc : 1));
     for (index_type c = 0; c < nc; ++c) mark[c] = -1;
-    G->nc = nc;
-    G->rp = (index_type*)calloc((size_t)nc + 1, sizeof(index_type));
+    C->n = nc;
+    C->rp = (index_type*)calloc((size_t)nc + 1, sizeof(index_type));
     size_t cap = (size_t)rp[n] + 1, used = 0;
-    G->ci = (index_type*)malloc(sizeof(index_type) * cap);
+    C->ci = (index_type*)malloc(sizeof(index_type) * cap);
     for (index_type c = 0; c < nc; ++c) {
         const size_t start = used;
         for (index_type t = aoff[c]; t < aoff[c + 1]; ++t) {
             const index_type i = amem[t];
             for (index_type k = rp[i]; k < rp[i + 1]; ++k) {
                 const index_type J = agg[ci[k]];
-                if (mark[J] != c) { mark[J] = c; G->ci[used++] = J; }
+                if (mark[J] != c) { mark[J] = c; C->ci[used++] = J; }
             }
         }
         /* insertion sort of the row (short rows) */
         for (size_t a = start + 1; a < used; ++a) {
-            const index_type v = G->ci[a];
+            const index_type v = C->ci[a];
             size_t b = a;
-            while (b > start && G->ci[b - 1] > v) { G->ci[b] = G->ci[b - 1]; --b; }
-            G->ci[b] = v;
+            while (b > start && C->ci[b - 1] > v) { C->ci[b] = C->ci[b - 1]; --b; }
+            C->ci[b] = v;
         }
-        G->rp[c + 1] = (index_type)used;
+        C->rp[c + 1] = (index_type)used;
     }
-    G->nnz = (index_type)used;
+    free(mark);
+    C->nnz = (index_type)used;
     const index_type nnzf = rp[n];
     index_type* pos = (index_type*)malloc(sizeof(index_type) * (size_t)(nnzf > 0 ? nnzf : 1));
-    G->goff = (index_type*)calloc((size_t)G->nnz + 1, sizeof(index_type));
     for (index_type i = 0; i < n; ++i)
-        for (index_type k = rp[i]; k < rp[i + 1]; ++k) {
-            pos[k] = amgx_find(G->rp, G->ci, agg[i], agg[ci[k]]);
-            G->goff[pos[k] + 1]++;
-        }
-    for (index_type k = 0; k < G->nnz; ++k) G->goff[k + 1] += G->goff[k];
-    G->gidx = (index_type*)malloc(sizeof(index_type) * (size_t)(nnzf > 0 ? nnzf : 1));
-    index_type* fill = (index_type*)malloc(sizeof(index_type) * (size_t)(G->nnz > 0 ? G->nnz : 1));
-    memcpy(fill, G->goff, sizeof(index_type) * (size_t)G->nnz);
-    for (index_type k = 0; k < nnzf; ++k) G->gidx[fill[pos[k]]++] = k;
-    G->val = NULL;
-    if (val) {
-        G->val = (f64*)malloc(sizeof(f64) * (size_t)(G->nnz > 0 ? G->nnz : 1));
-        for (index_type k = 0; k < G->nnz; ++k) {
-            f64 s = 0.0;
-            for (index_type t = G->goff[k]; t < G->goff[k + 1]; ++t) s += val[G->gidx[t]];
-            G->val[k] = s;
-        }
-    }
-    free(fill);
+        for (index_type k = rp[i]; k < rp[i + 1]; ++k) pos[k] = csr_find(C->rp, C->ci, agg[i], agg[ci[k]]);
+    csr_bucket_fill(nnzf, pos, C->nnz, &C->goff, &C->gidx);
     free(pos);
-    free(mark);
-    free(cur);
-    free(aoff);
-    free(amem);
-}
-static void amgx_gal_free(AmgxGal* G) {
-    free(G->rp);
-    free(G->ci);
-    free(G->goff);
-    free(G->gidx);
-    free(G->val);
-    memset(G, 0, sizeof *G);
+    C->val = (f64*)malloc(sizeof(f64) * (size_t)(C->nnz > 0 ? C->nnz : 1));
+    for (index_type k = 0; k < C->nnz; ++k) {
+        f64 s = 0.0;
+        for (index_type t = C->goff[k]; t < C->goff[k + 1]; ++t) s += val[C->gidx[t]];
+        C->val[k] = s;
+    }
 }
 
-/* `passes` pairwise passes composed (SIZE_2 / 4 / 8), each later one on the Galerkin graph of the previous */
+/* `passes` pairwise passes composed (SIZE_2 / 4 / 8).  Loop state: the current graph (the caller's matrix, then the
+ * Galerkin graph G of the map so far) and agg, the map from the caller's rows to the current graph's aggregates; every
+ * pass pairs the rows of the current graph (step) and is composed into agg. */
 static index_type amgx_aggregate(index_type n, const index_type* rp, const index_type* ci, const f64* val, int passes,
                                  index_type* agg) {
-    index_type nc = amgx_pairwise(n, rp, ci, val, agg);
-    AmgxGal G = {0};
-    const index_type *crp = rp, *cci = ci;
-    const f64* cval = val;
-    index_type cn = n;
-    index_type* a2 = NULL;
-    for (int p = 1; p < passes && nc > 1; ++p) {
-        AmgxGal H = {0};
-        amgx_galerkin_host(cn, crp, cci, cval, p == 1 ? agg : a2, nc, &H);
-        if (p > 1) amgx_gal_free(&G);
-        G = H;
-        /* the map of this pass applies to the previous coarse rows; compose (a2 keeps it for the next Galerkin graph) */
-        if (p == 1) a2 = (index_type*)malloc(sizeof(index_type) * (size_t)(nc > 0 ? nc : 1));
-        index_type* step = (index_type*)malloc(sizeof(index_type) * (size_t)(nc > 0 ? nc : 1));
-        const index_type nc2 = amgx_pairwise(nc, G.rp, G.ci, G.val, step);
+    index_type* step = (index_type*)malloc(sizeof(index_type) * (size_t)(n > 0 ? n : 1));
+    AmgxHost G = {0};
+    index_type cn = n, nc = n;
+    for (index_type i = 0; i < n; ++i) agg[i] = i;
+    for (int p = 0; p < passes; ++p) {
+        if (p > 0) {
+            if (nc <= 1) break;
+            index_type *aoff, *amem;
+            AmgxHost H;
+            csr_bucket_fill(cn, step, nc, &aoff, &amem);
+            amgx_galerkin_host(cn, rp, ci, val, step, nc, aoff, amem, &H);
+            free(aoff);
+            free(amem);
+            amgx_host_free(&G);
+            G = H;
+            cn = nc;
+            rp = G.rp;
+            ci = G.ci;
+            val = G.val;
+        }
+        nc = amgx_pairwise(cn, rp, ci, val, step);
         for (index_type i = 0; i < n; ++i) agg[i] = step[agg[i]];
-        memcpy(a2, step, sizeof(index_type) * (size_t)nc);
-        free(step);
-        cn = nc;
-        crp = G.rp;
-        cci = G.ci;
-        cval = G.val;
-        nc = nc2;
     }
-    if (passes > 1) amgx_gal_free(&G);
-    free(a2);
+    amgx_host_free(&G);
+    free(step);
     return nc;
 }
 
@@ -528,6 +232,33 @@ static index_type amgx_color(index_type n, const index_type* rp, const index_typ
     return nc;
 }
 
+/* the structure of level number `depth` (from 1) from its matrix; no HIP in here.  The map comes first: the passes of
+ * amgx_aggregate hold the most memory, so nothing else of the level is alive then. */
+static void amgx_host_level(AmgxHost* H, const DflAMGXConfig* cfg, index_type depth) {
+    const index_type n = H->n;
+    /* stop rules: small enough, level budget, a pass that keeps more than 90 % of the rows */
+    H->nc = 0;
+    if (n > cfg->min_coarse_rows && depth < cfg->max_levels) {
+        H->agg = (index_type*)malloc(sizeof(index_type) * (size_t)(n > 0 ? n : 1));
+        H->nc = amgx_aggregate(n, H->rp, H->ci, H->val, cfg->selector_passes, H->agg);
+        if ((f64)H->nc > 0.9 * (f64)n) {
+            free(H->agg);
+            H->agg = NULL;
+            H->nc = 0;
+        } else {
+            csr_bucket_fill(n, H->agg, H->nc, &H->aoff, &H->amem);
+        }
+    }
+    H->diag = (index_type*)malloc(sizeof(index_type) * (size_t)(n > 0 ? n : 1));
+    H->trans = (index_type*)malloc(sizeof(index_type) * (size_t)(H->nnz > 0 ? H->nnz : 1));
+    for (index_type i = 0; i < n; ++i) {
+        H->diag[i] = csr_find(H->rp, H->ci, i, i);
+        for (index_type k = H->rp[i]; k < H->rp[i + 1]; ++k) H->trans[k] = csr_find(H->rp, H->ci, H->ci[k], i);
+    }
+    H->color = (index_type*)malloc(sizeof(index_type) * (size_t)(n > 0 ? n : 1));
+    H->ncolor = amgx_color(n, H->rp, H->ci, H->color);
+    csr_bucket_fill(n, H->color, H->ncolor, &H->coff, &H->rows);
+}
 /* ============================== the preconditioner ===================================== */
 #define AMGX_MAX_COARSE 2048 /* rows of the coarsest level: the dense LU runs in one workgroup */
 
@@ -560,22 +291,28 @@ static void* amgx_up(const void* h, size_t bytes) {
     return d;
 }
 
+/* the device arrays a level owns, as members of dfl_amgx_level.  val is not among them (level 0 may hold the caller's:
+ * own_val), nor zpiv (the second half of piv) */
+#define LV(m) offsetof(dfl_amgx_level, m)
+static const size_t amgx_level_owned[] = {LV(rp),   LV(ci),   LV(diag), LV(trans), LV(color), LV(rows), LV(coff), LV(agg), LV(aoff),
+                                          LV(amem), LV(goff), LV(gidx), LV(einv),  LV(b),     LV(x),    LV(w),    LV(lu),  LV(piv)};
+#undef LV
+
 static void amgx_free_levels(PCAmgx* p) {
     if (!p->lev) return;
     HIPGUARD(hipStreamSynchronize(DflStream()));
     for (index_type l = 0; l < p->nlev; ++l) {
         AmgxLevel* L = &p->lev[l];
-        dfl_amgx_level* d = &L->d;
         if (L->mat) {
             ((MatrixCSR*)L->mat->data)->val = NULL; /* the values belong to this object or to the caller */
             MatrixDestroy(L->mat);
         }
-        void* ptrs[] = {(void*)d->rp, (void*)d->ci, (void*)d->diag, (void*)d->trans, (void*)d->color, (void*)d->rows,
-                        (void*)d->coff, (void*)d->agg, (void*)d->aoff, (void*)d->amem, (void*)d->goff, (void*)d->gidx,
-                        d->einv, d->b, d->x, d->w, d->lu, d->piv};
-        for (size_t k = 0; k < sizeof ptrs / sizeof ptrs[0]; ++k)
-            if (ptrs[k]) CdamFreeDevice(ptrs[k], 0);
-        if (L->own_val) CdamFreeDevice(d->val, 0);
+        for (size_t k = 0; k < sizeof amgx_level_owned / sizeof amgx_level_owned[0]; ++k) {
+            void* q;
+            memcpy(&q, (char*)&L->d + amgx_level_owned[k], sizeof q);
+            if (q) CdamFreeDevice(q, 0);
+        }
+        if (L->own_val) CdamFreeDevice(L->d.val, 0);
         free(L->coff);
     }
     free(p->lev);
@@ -621,6 +358,48 @@ static void amgx_level_matrix(AmgxLevel* L) {
     ((MatrixCSR*)L->mat->data)->val = L->d.val;
 }
 
+/* level L on the device from its host structure H.  val0: the device values of level 0 (the caller's array, or the
+ * gathered A11 this level then owns); every other level uploads its own.  The coarsest level that fits gets the dense LU. */
+static void amgx_upload_level(AmgxLevel* L, const AmgxHost* H, value_type* val0, b32 own_val0) {
+    dfl_amgx_level* d = &L->d;
+    const size_t n = (size_t)H->n, nnz = (size_t)H->nnz, I = sizeof(index_type);
+    d->n = H->n;
+    d->nnz = H->nnz;
+    d->ncolor = H->ncolor;
+    d->nc = H->nc;
+    d->rp = (index_type*)amgx_up(H->rp, I * (n + 1));
+    d->ci = (index_type*)amgx_up(H->ci, I * nnz);
+    if (H->goff) {
+        d->val = (value_type*)amgx_up(H->val, sizeof(f64) * nnz);
+        L->own_val = TRUE;
+        d->goff = (index_type*)amgx_up(H->goff, I * (nnz + 1));
+        d->gidx = (index_type*)amgx_up(H->gidx, I * (size_t)H->goff[nnz]);
+    } else {
+        d->val = val0;
+        L->own_val = own_val0;
+    }
+    d->trans = (index_type*)amgx_up(H->trans, I * nnz);
+    d->diag = (index_type*)amgx_up(H->diag, I * n);
+    d->rows = (index_type*)amgx_up(H->rows, I * n);
+    d->color = (index_type*)amgx_up(H->color, I * n);
+    d->coff = (index_type*)amgx_up(H->coff, I * ((size_t)H->ncolor + 1));
+    L->coff = (index_type*)malloc(I * ((size_t)H->ncolor + 1));
+    memcpy(L->coff, H->coff, I * ((size_t)H->ncolor + 1));
+    d->einv = (value_type*)amgx_dev(sizeof(f64) * n);
+    d->b = (value_type*)amgx_dev(sizeof(f64) * n);
+    d->x = (value_type*)amgx_dev(sizeof(f64) * n);
+    d->w = (value_type*)amgx_dev(sizeof(f64) * n);
+    if (H->nc) {
+        d->agg = (index_type*)amgx_up(H->agg, I * n);
+        d->aoff = (index_type*)amgx_up(H->aoff, I * ((size_t)H->nc + 1));
+        d->amem = (index_type*)amgx_up(H->amem, I * n);
+    } else if (H->n <= AMGX_MAX_COARSE) {
+        d->lu = (value_type*)amgx_dev(sizeof(f64) * n * n);
+        d->piv = (index_type*)amgx_dev(I * 2 * n);
+        d->zpiv = d->piv + n;
+    }
+}
+
 /* structure of every level; returns FALSE (with a message) if the hierarchy cannot be built */
 static b32 amgx_build(PCAmgx* p) {
     index_type n;
@@ -633,40 +412,35 @@ static b32 amgx_build(PCAmgx* p) {
     }
     hipStream_t s = DflStream();
     HIPGUARD(hipStreamSynchronize(s));
-    index_type* rp = (index_type*)malloc(sizeof(index_type) * ((size_t)n + 1));
-    HIPGUARD(hipMemcpy(rp, at->row_ptr, sizeof(index_type) * ((size_t)n + 1), D2H));
-    const index_type nnz = rp[n];
-    index_type* ci = (index_type*)malloc(sizeof(index_type) * (size_t)(nnz > 0 ? nnz : 1));
-    f64* val = (f64*)malloc(sizeof(f64) * (size_t)(nnz > 0 ? nnz : 1));
-    HIPGUARD(hipMemcpy(ci, at->col_ind, sizeof(index_type) * (size_t)nnz, D2H));
+    AmgxHost H = {0}; /* the current level, coarsened until a stop rule holds */
+    H.n = n;
+    H.rp = (index_type*)malloc(sizeof(index_type) * ((size_t)n + 1));
+    HIPGUARD(hipMemcpy(H.rp, at->row_ptr, sizeof(index_type) * ((size_t)n + 1), D2H));
+    const index_type nnz = H.nnz = H.rp[n];
+    H.ci = (index_type*)malloc(sizeof(index_type) * (size_t)(nnz > 0 ? nnz : 1));
+    H.val = (f64*)malloc(sizeof(f64) * (size_t)(nnz > 0 ? nnz : 1));
+    HIPGUARD(hipMemcpy(H.ci, at->col_ind, sizeof(index_type) * (size_t)nnz, D2H));
     value_type* v0 = dval;
     if (p->block_val) {
         v0 = (value_type*)amgx_dev(sizeof(f64) * (size_t)nnz);
         dfl_amgx_gather_a11(nnz, p->block_val, v0, s);
     }
-    HIPGUARD(hipMemcpy(val, v0, sizeof(f64) * (size_t)nnz, D2H));
+    HIPGUARD(hipMemcpy(H.val, v0, sizeof(f64) * (size_t)nnz, D2H));
     b32 ok = TRUE;
     for (index_type i = 0; i < n && ok; ++i) {
-        for (index_type k = rp[i] + 1; k < rp[i + 1]; ++k)
-            if (ci[k] <= ci[k - 1]) ok = FALSE;
-        if (amgx_find(rp, ci, i, i) < 0) ok = FALSE;
+        for (index_type k = H.rp[i] + 1; k < H.rp[i + 1]; ++k)
+            if (H.ci[k] <= H.ci[k - 1]) ok = FALSE;
+        if (csr_find(H.rp, H.ci, i, i) < 0) ok = FALSE;
     }
     if (!ok) {
         fprintf(stderr, "PCCreateAMGX: every row needs its diagonal and ascending column indices\n");
         if (p->block_val) CdamFreeDevice(v0, 0);
-        free(rp);
-        free(ci);
-        free(val);
+        amgx_host_free(&H);
         return FALSE;
     }
-    /* levels: host arrays of the current level, coarsened until a stop rule holds */
     int cap = 8;
     p->lev = (AmgxLevel*)calloc((size_t)cap, sizeof(AmgxLevel));
     p->nlev = 0;
-    index_type *crp = rp, *cci = ci, cn = n;
-    f64* cval = val;
-    index_type* goff = NULL;
-    index_type* gidx = NULL;
     f64 nnz_total = 0.0;
     for (;;) {
         if (p->nlev == cap) {
@@ -674,110 +448,21 @@ static b32 amgx_build(PCAmgx* p) {
             p->lev = (AmgxLevel*)realloc(p->lev, sizeof(AmgxLevel) * (size_t)cap);
             memset(p->lev + cap / 2, 0, sizeof(AmgxLevel) * (size_t)(cap / 2));
         }
-        AmgxLevel* L = &p->lev[p->nlev++];
-        dfl_amgx_level* d = &L->d;
-        const index_type cnnz = crp[cn];
-        nnz_total += cnnz;
-        d->n = cn;
-        d->nnz = cnnz;
-        d->rp = (index_type*)amgx_up(crp, sizeof(index_type) * ((size_t)cn + 1));
-        d->ci = (index_type*)amgx_up(cci, sizeof(index_type) * (size_t)cnnz);
-        if (p->nlev == 1) {
-            d->val = v0;
-            L->own_val = p->block_val != NULL;
-        } else {
-            d->val = (value_type*)amgx_up(cval, sizeof(f64) * (size_t)cnnz);
-            L->own_val = TRUE;
-            d->goff = (index_type*)amgx_up(goff, sizeof(index_type) * ((size_t)cnnz + 1));
-            d->gidx = (index_type*)amgx_up(gidx, sizeof(index_type) * (size_t)p->lev[p->nlev - 2].d.nnz);
-            free(goff);
-            free(gidx);
-            goff = gidx = NULL;
-        }
-        {
-            index_type* h = (index_type*)malloc(sizeof(index_type) * (size_t)(cnnz > 0 ? cnnz : 1));
-            index_type* dg = (index_type*)malloc(sizeof(index_type) * (size_t)(cn > 0 ? cn : 1));
-            for (index_type i = 0; i < cn; ++i) {
-                dg[i] = amgx_find(crp, cci, i, i);
-                for (index_type k = crp[i]; k < crp[i + 1]; ++k) h[k] = amgx_find(crp, cci, cci[k], i);
-            }
-            d->trans = (index_type*)amgx_up(h, sizeof(index_type) * (size_t)cnnz);
-            d->diag = (index_type*)amgx_up(dg, sizeof(index_type) * (size_t)cn);
-            /* colouring, rows grouped by colour */
-            index_type* color = h;
-            if (cnnz < cn) color = (index_type*)realloc(h, sizeof(index_type) * (size_t)cn), h = color;
-            d->ncolor = amgx_color(cn, crp, cci, color);
-            L->coff = (index_type*)calloc((size_t)d->ncolor + 1, sizeof(index_type));
-            for (index_type i = 0; i < cn; ++i) L->coff[color[i] + 1]++;
-            for (index_type c = 0; c < d->ncolor; ++c) L->coff[c + 1] += L->coff[c];
-            index_type* cur = (index_type*)malloc(sizeof(index_type) * (size_t)(d->ncolor + 1));
-            memcpy(cur, L->coff, sizeof(index_type) * (size_t)d->ncolor);
-            for (index_type i = 0; i < cn; ++i) dg[cur[color[i]]++] = i;
-            d->rows = (index_type*)amgx_up(dg, sizeof(index_type) * (size_t)cn);
-            d->color = (index_type*)amgx_up(color, sizeof(index_type) * (size_t)cn);
-            d->coff = (index_type*)amgx_up(L->coff, sizeof(index_type) * ((size_t)d->ncolor + 1));
-            free(cur);
-            free(h);
-            free(dg);
-        }
-        d->einv = (value_type*)amgx_dev(sizeof(f64) * (size_t)cn);
-        d->b = (value_type*)amgx_dev(sizeof(f64) * (size_t)cn);
-        d->x = (value_type*)amgx_dev(sizeof(f64) * (size_t)cn);
-        d->w = (value_type*)amgx_dev(sizeof(f64) * (size_t)cn);
-        /* stop rules: small enough, level budget, a pass that keeps more than 90 % of the rows */
-        b32 last = cn <= p->cfg.min_coarse_rows || p->nlev >= p->cfg.max_levels;
-        index_type* agg = NULL;
-        index_type nc = 0;
-        if (!last) {
-            agg = (index_type*)malloc(sizeof(index_type) * (size_t)(cn > 0 ? cn : 1));
-            nc = amgx_aggregate(cn, crp, cci, cval, p->cfg.selector_passes, agg);
-            if ((f64)nc > 0.9 * (f64)cn) last = TRUE;
-        }
-        if (last) {
-            free(agg);
-            if (cn > AMGX_MAX_COARSE) {
-                fprintf(stderr, "PCCreateAMGX: the coarsest level keeps %d rows (more than %d): no hierarchy\n", cn, AMGX_MAX_COARSE);
-                ok = FALSE;
-            } else {
-                d->lu = (value_type*)amgx_dev(sizeof(f64) * (size_t)cn * (size_t)cn);
-                d->piv = (index_type*)amgx_dev(sizeof(index_type) * 2 * (size_t)cn);
-                d->zpiv = d->piv + cn;
-            }
-            break;
-        }
-        AmgxGal G = {0};
-        amgx_galerkin_host(cn, crp, cci, cval, agg, nc, &G);
-        {
-            index_type* aoff = (index_type*)calloc((size_t)nc + 1, sizeof(index_type));
-            index_type* amem = (index_type*)malloc(sizeof(index_type) * (size_t)(cn > 0 ? cn : 1));
-            for (index_type i = 0; i < cn; ++i) aoff[agg[i] + 1]++;
-            for (index_type c = 0; c < nc; ++c) aoff[c + 1] += aoff[c];
-            index_type* cur = (index_type*)malloc(sizeof(index_type) * (size_t)(nc + 1));
-            memcpy(cur, aoff, sizeof(index_type) * (size_t)nc);
-            for (index_type i = 0; i < cn; ++i) amem[cur[agg[i]]++] = i;
-            d->nc = nc;
-            d->agg = (index_type*)amgx_up(agg, sizeof(index_type) * (size_t)cn);
-            d->aoff = (index_type*)amgx_up(aoff, sizeof(index_type) * ((size_t)nc + 1));
-            d->amem = (index_type*)amgx_up(amem, sizeof(index_type) * (size_t)cn);
-            free(aoff);
-            free(amem);
-            free(cur);
-        }
-        free(agg);
-        if (crp != rp) { free(crp); free(cci); free(cval); }
-        crp = G.rp;
-        cci = G.ci;
-        cval = G.val;
-        goff = G.goff;
-        gidx = G.gidx;
-        cn = nc;
+        nnz_total += H.nnz;
+        amgx_host_level(&H, &p->cfg, p->nlev + 1);
+        amgx_upload_level(&p->lev[p->nlev++], &H, v0, p->block_val != NULL);
+        amgx_host_free_structure(&H);
+        if (!H.nc) break;
+        AmgxHost C;
+        amgx_galerkin_host(H.n, H.rp, H.ci, H.val, H.agg, H.nc, H.aoff, H.amem, &C);
+        amgx_host_free(&H);
+        H = C;
     }
-    if (crp != rp) { free(crp); free(cci); free(cval); }
-    free(goff);
-    free(gidx);
-    free(rp);
-    free(ci);
-    free(val);
+    if (H.n > AMGX_MAX_COARSE) {
+        fprintf(stderr, "PCCreateAMGX: the coarsest level keeps %d rows (more than %d): no hierarchy\n", H.n, AMGX_MAX_COARSE);
+        ok = FALSE;
+    }
+    amgx_host_free(&H);
     if (!ok) {
         amgx_free_levels(p);
         return FALSE;

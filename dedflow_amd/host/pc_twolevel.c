@@ -42,6 +42,7 @@
 #include "host_private.h"
 #include "solver_private.h"
 #include "rcb.h"
+#include "csr_lists.h"
 
 typedef struct PCTwoLevel {
     Matrix* A;
@@ -287,30 +288,12 @@ static void tl_build(PCTwoLevel* d) {
     }
     /* 3. Galerkin lists: coarse nonzero -> fine nonzeros of the OWNED fine rows (they come first), ascending fine index */
     const index_type fnz = rp[no];
-    index_type* goff = (index_type*)calloc((size_t)nnzc + 1, sizeof(index_type));
     index_type* fz2cz = (index_type*)malloc(sizeof(index_type) * (size_t)(fnz > 0 ? fnz : 1));
 #pragma omp parallel for schedule(static) num_threads(nt)
-    for (index_type i = 0; i < no; ++i) {
-        const index_type I = agg[i];
-        for (index_type z = rp[i]; z < rp[i + 1]; ++z) {
-            const index_type J = agg[ci[z]];
-            index_type lo = crp[I], hi = crp[I + 1] - 1;
-            while (lo < hi) {
-                index_type mid = (lo + hi) >> 1;
-                if (cci[mid] < J) lo = mid + 1; else hi = mid;
-            }
-            fz2cz[z] = lo;
-        }
-    }
-    for (index_type z = 0; z < fnz; ++z) goff[fz2cz[z] + 1]++;
-    for (index_type c = 0; c < nnzc; ++c) goff[c + 1] += goff[c];
-    index_type* gidx = (index_type*)malloc(sizeof(index_type) * (size_t)(fnz > 0 ? fnz : 1));
-    {
-        index_type* cur = (index_type*)malloc(sizeof(index_type) * (size_t)(nnzc > 0 ? nnzc : 1));
-        memcpy(cur, goff, sizeof(index_type) * (size_t)nnzc);
-        for (index_type z = 0; z < fnz; ++z) gidx[cur[fz2cz[z]]++] = z;
-        free(cur);
-    }
+    for (index_type i = 0; i < no; ++i)
+        for (index_type z = rp[i]; z < rp[i + 1]; ++z) fz2cz[z] = csr_find(crp, cci, agg[i], agg[ci[z]]);
+    index_type *goff, *gidx;
+    csr_bucket_fill(fnz, fz2cz, nnzc, &goff, &gidx);
     /* 4. upload; coarse matrix objects in the reference's own shapes */
 #define UP(dst, src, cnt)                                                                             \
     dst = (index_type*)CdamMallocDevice((ptrdiff_t)((cnt) > 0 ? (cnt) : 1) * SIZE_OF(index_type));    \

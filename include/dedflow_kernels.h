@@ -376,11 +376,10 @@ void dfl_face_sum_J(dfl_index num_nz_entries, const dfl_index* fnz, const dfl_in
 
 /* ---- two-level preconditioner (csrc/k_amg.hip, host/pc_twolevel.c; build-defined): piecewise-constant aggregation.
  *  galerkin   : coarse 4x4 blocks val_coarse[cz] = sum of val_fine[idx[off[cz] .. off[cz+1])] (list order)
- *  restrict   : rc[I] = sum of r over the nodes anode[aoff[I] .. aoff[I+1]) of aggregate I, layouts [u: 3N | p: N]
- *  prolong_add: z[i] += xc[agg[i]] */
+ *  restrict_diff   : rc[I] = sum of r - sub over the nodes anode[aoff[I] .. aoff[I+1]) of aggregate I, layouts
+ *                    [u: 3N | p: N] (the residual r - A z with sub = A z from a plain matvec)
+ *  prolong_add_rows: z[i] += xc[agg[i]] for rows [0, nrows) of N (partitioned runs: the owned nodes come first) */
 void dfl_amg_galerkin(dfl_index nnzc, const dfl_index* off, const dfl_index* idx, const dfl_value* val_fine, dfl_value* val_coarse,
-                      void* stream);
-void dfl_amg_restrict(dfl_index Nc, const dfl_index* aoff, const dfl_index* anode, dfl_index N, const dfl_value* r, dfl_value* rc,
                       void* stream);
 /* The matvec with x gathered from an INTERLEAVED copy x4[node][4] = (u0 u1 u2 p): the two lanes of a block row fetch their x
  * entries with one 16-byte load each instead of two 8-byte loads from the u part and the p part of the reference layout --
@@ -403,11 +402,8 @@ void dfl_bcsr_spmv_f32(dfl_index nrows, dfl_index N, const dfl_index* row_ptr, c
 void dfl_dilu_sweep_color_f32(int forward, dfl_index slot0, dfl_index nrows_c, const dfl_index* rows, dfl_index N,
                               const dfl_index* eptr, const dfl_index* enz, const dfl_index* ecol, const float* valf,
                               const dfl_value* Einv, const dfl_value* r, dfl_value* z, void* stream);
-/* the same of r - sub (the residual r - A z with sub = A z from a plain matvec) */
 void dfl_amg_restrict_diff(dfl_index Nc, const dfl_index* aoff, const dfl_index* anode, dfl_index N, const dfl_value* r,
                            const dfl_value* sub, dfl_value* rc, void* stream);
-void dfl_amg_prolong_add(dfl_index N, const dfl_index* agg, dfl_index Nc, const dfl_value* xc, dfl_value* z, void* stream);
-/* the same for rows [0, nrows) of N (partitioned runs: the owned nodes come first) */
 void dfl_amg_prolong_add_rows(dfl_index nrows, dfl_index N, const dfl_index* agg, dfl_index Nc, const dfl_value* xc, dfl_value* z,
                               void* stream);
 

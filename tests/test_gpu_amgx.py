@@ -62,7 +62,7 @@ def _hierarchy(api, pc):
     return mats, aggs, cols
 
 
-def _check_structure(mats, aggs, cols):
+def _check_structure(mats, aggs, cols, passes=1):
     for l in range(len(mats)):
         A = mats[l]
         assert np.array_equal(cols[l], am.greedy_colors(A.indptr, A.indices)), l
@@ -70,7 +70,7 @@ def _check_structure(mats, aggs, cols):
         off = rows != A.indices
         assert np.all(cols[l][rows[off]] != cols[l][A.indices[off]]), l     # a valid colouring
         if l + 1 < len(mats):
-            agg, nc = am.pairwise(A.indptr, A.indices, A.data)
+            agg, nc = am.aggregate(A, passes)                                   # one pass: am.pairwise
             assert nc == mats[l + 1].shape[0] and np.array_equal(aggs[l], agg), l
             Ac = am.galerkin(A, aggs[l], nc)
             D = (mats[l + 1] - Ac).tocsr()
@@ -332,6 +332,86 @@ def test_options_forms_and_pool(api, tmp_path):
             pc = L.PCCreateAMGX(M, None)
             L.PCSetup(pc)
             L.PCDestroy(pc)
+        api.sync()
+        res1, use1 = C.c_int64(0), C.c_int64(0)
+        L.DflDevicePoolStats(C.byref(res1), C.byref(use1))
+        assert use1.value == use0.value
+        L.MatrixDestroy(M)
+    finally:
+        P.close()
+
+
+# SIZE_4: every level's map is two pairwise passes composed, the second on the Galerkin graph of the first
+@pytest.mark.parametrize("tail_rows", [8192, 0])
+@pytest.mark.parametrize("smoother", ["MULTICOLOR_DILU", "BLOCK_JACOBI"])
+def test_multipass_selector_hierarchy_and_apply(api, monkeypatch, smoother, tail_rows):
+    m, A = _dirichlet_poisson(8)
+    P = api.Problem(m)
+    L = api.lib()
+    try:
+        M, vals = _csr_on_pattern(api, P, A)
+        monkeypatch.setenv("DFL_AMGX_TAIL_ROWS", str(tail_rows))
+        pc = L.PCCreateAMGX(M, f"config_version=2, solver:preconditioner:selector=SIZE_4, "
+                               f"solver:preconditioner:smoother={smoother}".encode())
+        monkeypatch.delenv("DFL_AMGX_TAIL_ROWS")
+        assert pc
+        L.PCSetup(pc)
+        api.sync()
+        mats, aggs, cols = _hierarchy(api, pc)
+        assert len(mats) >= 3                                                  # two coarse levels at least
+        assert np.array_equal(mats[0].toarray(), A.toarray())
+        _check_structure(mats, aggs, cols, passes=2)
+        model = am.Model(mats, aggs, cols, smoother="JACOBI" if smoother == "BLOCK_JACOBI" else "DILU")
+        r = np.random.default_rng(13).normal(size=A.shape[0])
+        z, zm = _apply(api, pc, r), model.apply(r)
+        assert np.all(np.isfinite(z)) and np.abs(z - zm).max() <= 1e-12 * np.abs(zm).max()
+        assert np.array_equal(z, _apply(api, pc, r))                           # bitwise reproducible
+        L.PCDestroy(pc)
+        L.MatrixDestroy(M)
+    finally:
+        P.close()
+
+
+def test_rebuild_equals_a_fresh_preconditioner(api):
+    m, A = _dirichlet_poisson(8)
+    P = api.Problem(m)
+    L = api.lib()
+    try:
+        M, vals = _csr_on_pattern(api, P, A)
+        api.sync()
+        res0, use0 = C.c_int64(0), C.c_int64(0)
+        L.DflDevicePoolStats(C.byref(res0), C.byref(use0))
+
+        def state(pc, r):
+            L.PCSetup(pc)
+            api.sync()
+            mats, aggs, cols = _hierarchy(api, pc)
+            piv = api.d2h(L.PCAMGXCoarsePivots(pc), 2 * mats[-1].shape[0], np.int32)
+            arrays = [a for A_l in mats for a in (A_l.indptr, A_l.indices, A_l.data)] + aggs + cols + [piv, _apply(api, pc, r)]
+            return aggs, arrays
+
+        rng = np.random.default_rng(17)
+        r = rng.normal(size=A.shape[0])
+        pc = L.PCCreateAMGX(M, None)
+        assert pc
+        aggs0, _ = state(pc, r)
+        # new values with other strengths: rows and columns scaled by different vectors.  (Scaling rows alone would not do:
+        # the strength |a_ij| / |a_ii| does not see it.)
+        rows = np.repeat(np.arange(A.shape[0]), np.diff(A.indptr))
+        A2 = A.copy()
+        A2.data = A.data * (1.0 + rng.random(A.shape[0]))[rows] * (1.0 + rng.random(A.shape[0]))[A.indices]
+        vals.upload(A2.data)
+        L.PCAMGXRebuild(pc)
+        aggs1, rebuilt = state(pc, r)
+        assert len(aggs1) != len(aggs0) or any(not np.array_equal(a, b) for a, b in zip(aggs0, aggs1))
+        fresh_pc = L.PCCreateAMGX(M, None)
+        assert fresh_pc
+        _, fresh = state(fresh_pc, r)
+        assert len(rebuilt) == len(fresh)
+        for a, b in zip(rebuilt, fresh):
+            assert a.dtype == b.dtype and np.array_equal(a, b)
+        L.PCDestroy(pc)
+        L.PCDestroy(fresh_pc)
         api.sync()
         res1, use1 = C.c_int64(0), C.c_int64(0)
         L.DflDevicePoolStats(C.byref(res1), C.byref(use1))
