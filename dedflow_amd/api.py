@@ -525,6 +525,43 @@ class Particles:
         n = int(lib().ParticleContextLaserColumns(self.ctx, C.byref(tp), C.byref(fp)))
         return d2h(tp.value, n, np.float64), d2h(fp.value, n, np.int32)
 
+    # ---- melt-pool capture (build-defined; model in include/dedflow.h) ----------------------------------------------
+    def set_capture(self, level=0.0, side=1, reach=0.0, T_melt=-np.inf, two_way=False):
+        """ParticleContextSetCapture: capture() takes out the particles that reach the metal surface phi = level (side +1:
+        metal where phi > level, -1: where phi < level; reach in particle radii) where the fluid has T_f >= T_melt, and
+        deposits their mass, excess momentum and excess heat on the nodes; level None turns capture off.  Needs couple.  A
+        configuration the library refuses (reported on stderr) leaves the context as it was: capture_on tells."""
+        if level is None:
+            lib().ParticleContextSetCapture(self.ctx, None)
+            return
+        cfg = DflParticleCapture(float(level), int(side), float(reach), float(T_melt), 1 if two_way else 0)
+        lib().ParticleContextSetCapture(self.ctx, C.byref(cfg))
+
+    @property
+    def capture_on(self):
+        return bool(lib().DflParticleCaptureOn(self.ctx))
+
+    def capture(self, w):
+        """ParticleContextCapture in the fluid state w (DeviceArray of 6N); returns the number of particles captured"""
+        return int(lib().ParticleContextCapture(self.ctx, w.ptr))
+
+    def capture_source(self, time):
+        """ParticleContextCaptureSource over the window `time` (> 0): (q_vol [N], load [3N], q_heat [N]) as DeviceArrays; clears
+        what was pending"""
+        if not self.capture_on:
+            raise RuntimeError("capture is off: call set_capture first")
+        if not float(time) > 0.0:
+            raise ValueError("capture_source: the time window must be positive")
+        out = DeviceArray(self.N), DeviceArray(3 * self.N), DeviceArray(self.N)
+        lib().ParticleContextCaptureSource(self.ctx, float(time), out[0].ptr, out[1].ptr, out[2].ptr)
+        return out
+
+    def capture_stats(self):
+        """dict captured (since capture was set) / last (by the last capture call)"""
+        st = DflParticleCaptureStats()
+        lib().ParticleContextCaptureStats(self.ctx, C.byref(st))
+        return {"captured": int(st.captured), "last": int(st.last)}
+
     def arrays(self):
         """(coord, vel, acc) copied back from the device"""
         c = self.ctx.contents
@@ -557,6 +594,14 @@ class DflParticleFlowStats(C.Structure):
 class DflParticleHeat(C.Structure):
     _fields_ = [("cp_p", C.c_double), ("k_p", C.c_double), ("cp_f", C.c_double), ("k_f", C.c_double), ("T_init", C.c_double),
                 ("two_way", C.c_int32)]
+
+
+class DflParticleCapture(C.Structure):
+    _fields_ = [("level", C.c_double), ("side", C.c_int32), ("reach", C.c_double), ("T_melt", C.c_double), ("two_way", C.c_int32)]
+
+
+class DflParticleCaptureStats(C.Structure):
+    _fields_ = [("captured", C.c_int64), ("last", C.c_int32)]
 
 
 class DflLaser(C.Structure):
@@ -709,6 +754,12 @@ def _declare(L):
     f("ParticleContextLaserRate", vp, [C.POINTER(ParticleContext)])
     f("ParticleContextLaserTally", None, [C.POINTER(ParticleContext), C.POINTER(DflLaserTally)])
     f("ParticleContextLaserColumns", C.c_int32, [C.POINTER(ParticleContext), C.POINTER(vp), C.POINTER(vp)])
+    f("ParticleContextSetCapture", None, [C.POINTER(ParticleContext), C.POINTER(DflParticleCapture)])
+    f("ParticleContextCapture", i32, [C.POINTER(ParticleContext), vp])
+    f("ParticleContextCaptureSource", None, [C.POINTER(ParticleContext), f64, vp, vp, vp])
+    f("ParticleContextCaptureStats", None, [C.POINTER(ParticleContext), C.POINTER(DflParticleCaptureStats)])
+    f("DflParticleCaptureOn", i32, [C.POINTER(ParticleContext)])
+    f("DflMeshSetVolumeSource", None, [C.POINTER(Mesh3D), vp]); f("DflMeshVolumeSource", vp, [C.POINTER(Mesh3D)])
     f("DflParticlePendingEnergy", vp, [C.POINTER(ParticleContext)]); f("DflParticleConductionRate", vp, [C.POINTER(ParticleContext)])
     f("SolveFlowSystem", i32, [C.POINTER(Mesh3D), vp, vp, vp, C.POINTER(Matrix), vp, vp, vp, vp, i32, i32, vp, vp])
     f("DflTimeStep", i32, [C.POINTER(Mesh3D), vp, vp, vp, C.POINTER(Matrix), vp, vp, vp, vp, i32, i32, C.POINTER(ParticleContext),
@@ -834,6 +885,17 @@ class Problem:
         or None"""
         self._heat_source = q
         lib().DflMeshSetHeatSource(self.mesh, q.ptr if q is not None else None)
+
+    def set_volume_source(self, q):
+        """DflMeshSetVolumeSource: a DeviceArray of N (m^3/s per node) subtracted from the p rows of every F (kept alive here
+        while registered), or None"""
+        self._vol_source = q
+        lib().DflMeshSetVolumeSource(self.mesh, q.ptr if q is not None else None)
+
+    def volume_source(self):
+        """the registered volume source [N] copied back from the device (None: none registered)"""
+        p = lib().DflMeshVolumeSource(self.mesh)
+        return d2h(p, self.N, np.float64) if p else None
 
     def matvec(self, x, y):
         lib().MatrixMatVec(self.J, x.ptr, y.ptr)

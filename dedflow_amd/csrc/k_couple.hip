@@ -246,7 +246,7 @@ __global__ __launch_bounds__(BLK) void couple_stable_kernel(I P, const I* __rest
 
 // load[C a + d] = -scale * sum over the tets e of node a (ascending) and the particles p of e (ascending id) of
 // lambda_{p, k(a, e)} imp[p][d], d < C.  C = 3: the reaction load of the drag impulses; C = 1: the heat source of the
-// particles' pending energy (k_heat.hip)
+// particles' pending energy (k_heat.hip); C = 5: the deposits of captured particles (k_capture.hip)
 template <int C>
 __global__ __launch_bounds__(BLK) void couple_node_kernel(I N, const I* __restrict__ vrow, const I* __restrict__ vcol,
                                                          const I* __restrict__ ien, const I* __restrict__ tstart,
@@ -338,6 +338,13 @@ void dfl_couple_node_scalar(I N, const I* vrow, const I* vcol, const I* ien, con
                             const T* e, T scale, T* out, void* stream) {
     if (N <= 0) return;
     couple_node_kernel<1><<<ceil_div(N, BLK), BLK, 0, S(stream)>>>(N, vrow, vcol, ien, tstart, members, lambda, e, scale, out);
+    DFL_LAUNCH_CHECK();
+}
+
+void dfl_couple_node_deposit(I N, const I* vrow, const I* vcol, const I* ien, const I* tstart, const I* members, const T* lambda,
+                             const T* dep, T scale, T* out, void* stream) {
+    if (N <= 0) return;
+    couple_node_kernel<5><<<ceil_div(N, BLK), BLK, 0, S(stream)>>>(N, vrow, vcol, ien, tstart, members, lambda, dep, scale, out);
     DFL_LAUNCH_CHECK();
 }
 

@@ -36,6 +36,8 @@ void DflMeshSetExternalLoad(Mesh3D* mesh, const f64* load) { ((MeshExt*)mesh->ex
 const f64* DflMeshExternalLoad(const Mesh3D* mesh) { return ((const MeshExt*)mesh->ext)->ext_load; }
 void DflMeshSetHeatSource(Mesh3D* mesh, const f64* q) { ((MeshExt*)mesh->ext)->heat_source = q; }
 const f64* DflMeshHeatSource(const Mesh3D* mesh) { return ((const MeshExt*)mesh->ext)->heat_source; }
+void DflMeshSetVolumeSource(Mesh3D* mesh, const f64* q_vol) { ((MeshExt*)mesh->ext)->vol_source = q_vol; }
+const f64* DflMeshVolumeSource(const Mesh3D* mesh) { return ((const MeshExt*)mesh->ext)->vol_source; }
 /* node coordinates were modified (moving mesh): drop the per-element geometry cache, rebuilt at the next assembly */
 void DflMeshGeometryChanged(Mesh3D* mesh) {
     MeshExt* x = (MeshExt*)mesh->ext;
@@ -222,6 +224,8 @@ void DflAssembleSystemPrepacked(Mesh3D* mesh, f64* wgalpha, f64* dwgalpha, f64* 
     /* external force on the momentum equations (particle reaction, include/dedflow.h): R = (...) - f_ext, after the tet and
        face terms and before the Dirichlet rows */
     if (F && x->ext_load) dfl_daxpy(3 * num_node, -1.0, x->ext_load, F, s);
+    /* volume source on the continuity rows (melt-pool capture, include/dedflow.h): R_p = (...) - q_V, explicit as the load */
+    if (F && x->vol_source) dfl_daxpy(num_node, -1.0, x->vol_source, F + 3 * (size_t)num_node, s);
     /* heat source on the T rows (particle heat, include/dedflow.h): R_T = (...) - q, before the rows are captured */
     if (F && x->heat_source) dfl_daxpy(num_node, -1.0, x->heat_source, F + 5 * (size_t)num_node, s);
     x->nodep_current = FALSE;

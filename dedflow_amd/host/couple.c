@@ -141,6 +141,7 @@ void ParticleContextSetFluidCoupling(ParticleContext* ctx, Mesh3D* mesh, const D
     }
     if (!mesh) {
         DflHeatCouplingChanged(ctx);
+        DflCaptureCouplingChanged(ctx);
         return;
     }
     if (Mesh3DNumTet(mesh) <= 0) {
@@ -172,6 +173,7 @@ void ParticleContextSetFluidCoupling(ParticleContext* ctx, Mesh3D* mesh, const D
     c->rem_pending = FALSE;
     c->imp_time = 0.0;
     DflHeatCouplingChanged(ctx);
+    DflCaptureCouplingChanged(ctx);
 }
 
 /* the thread -> particle map of the walk: the contact sweep's (cell, id) order when it has run since the particle count

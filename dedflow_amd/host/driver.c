@@ -138,7 +138,9 @@ index_type SolveFlowSystem(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matr
  * fluid state of the new time level; with two_way, the Newton solve sees the reaction load of the previous step's
  * sub-steps as an external load, and with two-way particle heat (ParticleContextSetHeat) the heat they gave the fluid as a
  * source of the T rows.  With inflow / outflow set on the context (ParticleContextSetInflow / SetOutflow),
- * ParticleContextAdd runs after the predictor and ParticleContextRemove after the particle sub-steps. */
+ * ParticleContextAdd runs after the predictor and ParticleContextRemove after the particle sub-steps; with capture set
+ * (ParticleContextSetCapture) ParticleContextCapture runs just before that Remove, and with its two_way the deposits of
+ * the previous step enter the p, momentum and T rows of this step's Newton solve. */
 index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* J, f64* F, f64* dx, Krylov* ksp, Dirichlet** bcs,
                        index_type nbc, index_type newton_maxit, ParticleContext* pctx, index_type dem_substeps, f64* rnorm_out,
                        f64* rnorm_init_out) {
@@ -169,16 +171,34 @@ index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* 
         ASSERT(!user_heat && "DflTimeStep: a two-way heat step cannot add to a heat source already registered");
         DflMeshSetHeatSource(mesh, heat);
     }
+    /* what the melt pool captured since the last step (two-way capture): the volume rate on the p rows, the momentum and
+       heat rates on top of the load and the heat source, in the capture's own buffers */
+    const f64* user_vol = DflMeshVolumeSource(mesh);
+    f64 *cap_vol = NULL, *cap_load = NULL, *cap_heat = NULL;
+    if (coupled && DflCaptureTakePending(pctx, kDT, &cap_vol, &cap_load, &cap_heat)) {
+        ASSERT(!user_vol && "DflTimeStep: a two-way capture step cannot add to a volume source already registered");
+        DflMeshSetVolumeSource(mesh, cap_vol);
+        if (reaction) dfl_daxpy(3 * N, 1.0, reaction, cap_load, s);
+        else ASSERT(!user_load && "DflTimeStep: a two-way capture step cannot add to an external load already registered");
+        DflMeshSetExternalLoad(mesh, reaction = cap_load);
+        if (cap_heat) {
+            if (heat) dfl_daxpy(N, 1.0, heat, cap_heat, s);
+            else ASSERT(!user_heat && "DflTimeStep: a two-way capture step cannot add to a heat source already registered");
+            DflMeshSetHeatSource(mesh, heat = cap_heat);
+        }
+    }
     dfl_alpha_predict(N, fac_pred, dwg, s);
     if (pctx) ParticleContextAdd(pctx); /* main.c:547-548; a no-op unless inflow is set */
     index_type it = SolveFlowSystem(mesh, wgold, dwgold, dwg, J, F, dx, ksp, bcs, nbc, newton_maxit, rnorm_out, rnorm_init_out);
     if (reaction) DflMeshSetExternalLoad(mesh, user_load);
     if (heat) DflMeshSetHeatSource(mesh, user_heat);
+    if (cap_vol) DflMeshSetVolumeSource(mesh, user_vol);
     if (pctx && !coupled)
         for (index_type k = 0; k < dem_substeps; ++k) ParticleContextUpdate(pctx); /* coupled step: contact sweep (config 4) */
     dfl_alpha_correct(N, fac_corr[0], fac_corr[1], wgold, dwgold, dwg, s);
     if (coupled)
         for (index_type k = 0; k < dem_substeps; ++k) ParticleContextFluidStep(pctx, wgold); /* u at t_{n+1} */
+    if (coupled) ParticleContextCapture(pctx, wgold); /* a no-op unless capture is set; before the outflow */
     if (pctx) ParticleContextRemove(pctx); /* main.c:568-569; a no-op unless outflow is set */
     DflRangePop();
     return it;

@@ -47,7 +47,7 @@ static void** spare_of(FlowState* f, const DflPField* row, index_type cap, unsig
 }
 
 /* the spares the next compaction writes, for the state that is on now */
-static void ensure_spares(ParticleContext* ctx) {
+void DflFlowEnsureSpares(ParticleContext* ctx) {
     ParticleExt* x = (ParticleExt*)ctx->ext;
     DflPField rows[DFL_PF_MAX_ROWS];
     const int nrow = DflParticleFields(ctx, DflParticleLiveFeatures(ctx), rows);
@@ -74,7 +74,7 @@ void DflFlowFree(ParticleContext* ctx) {
 }
 
 /* the flow state of a context: created (tags 0 .. P-1) at the first Set call */
-static FlowState* flow_state(ParticleContext* ctx) {
+FlowState* DflFlowState(ParticleContext* ctx) {
     ParticleExt* x = (ParticleExt*)ctx->ext;
     if (x->flow) return x->flow;
     const index_type P = ctx->num_particle;
@@ -125,7 +125,7 @@ static void grow(ParticleContext* ctx, index_type need) {
     free_spares(f);
     x->cap = cap;
     DflLaserCapacityChanged(ctx); /* its bins are sized with the capacity too */
-    if (f->out_on) ensure_spares(ctx);
+    if (f->out_on || x->capture) DflFlowEnsureSpares(ctx);
 }
 
 static void set_count(ParticleContext* ctx, index_type P) {
@@ -143,10 +143,10 @@ void ParticleContextSetOutflow(ParticleContext* ctx, const DflParticleOutflow* c
         return;
     }
     ASSERT(cfg->num_planes >= 0 && cfg->num_planes <= DFL_OUTFLOW_MAX_PLANES && "ParticleContextSetOutflow: num_planes");
-    FlowState* f = flow_state(ctx);
+    FlowState* f = DflFlowState(ctx);
     f->out = *cfg;
     f->out_on = TRUE;
-    ensure_spares(ctx);
+    DflFlowEnsureSpares(ctx);
 }
 
 static f64 norm3(const f64* a) { return sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]); }
@@ -213,7 +213,7 @@ void ParticleContextSetInflow(ParticleContext* ctx, const DflParticleInflow* cfg
     const f64 uv = (cfg->edge_u[0] * cfg->edge_v[0] + cfg->edge_u[1] * cfg->edge_v[1]) + cfg->edge_u[2] * cfg->edge_v[2];
     ASSERT(fabs(uv) <= 1e-9 * norm3(cfg->edge_u) * norm3(cfg->edge_v) && "ParticleContextSetInflow: edge_u must be perpendicular to edge_v");
     ASSERT(cfg->per_call >= 0.0 && "ParticleContextSetInflow: per_call must not be negative");
-    FlowState* f = flow_state(ctx);
+    FlowState* f = DflFlowState(ctx);
     f->in = *cfg;
     f->in_on = TRUE;
     f->call = 0;
@@ -234,7 +234,7 @@ void ParticleContextRemove(ParticleContext* ctx) {
     if (P <= 0) return;
     DflRangePush("ParticleContextRemove");
     hipStream_t s = DflStream();
-    ensure_spares(ctx);
+    DflFlowEnsureSpares(ctx);
     dfl_outflow_planes pl;
     memset(&pl, 0, sizeof pl);
     pl.num = f->out.num_planes;
@@ -251,6 +251,16 @@ void ParticleContextRemove(ParticleContext* ctx) {
     }
     if (pending) DflCoupleAccumulateRemoved(ctx, f->rtet); /* before the compaction moves imp and lambda */
     if (heat_pending) DflHeatAccumulateRemoved(ctx, f->rtet);
+    DflFlowCompact(ctx, Pn);
+    f->stats.removed += P - Pn;
+    DflRangePop();
+}
+
+void DflFlowCompact(ParticleContext* ctx, index_type Pn) {
+    ParticleExt* x = (ParticleExt*)ctx->ext;
+    FlowState* f = x->flow;
+    const index_type P = ctx->num_particle;
+    hipStream_t s = DflStream();
     /* every carried field into a spare, grouped by element size; the swap in the same walk: the compacted copy becomes the
        live buffer, the old one the spare */
     static const int group_bytes[4] = {4, 8, 24, 32};
@@ -284,9 +294,7 @@ void ParticleContextRemove(ParticleContext* ctx) {
     }
     dfl_flow_compact(P, f->keep, f->newid, fl, s);
     if (x->omega) x->hist_cur = 1 - cur;
-    f->stats.removed += P - Pn;
     set_count(ctx, Pn);
-    DflRangePop();
 }
 
 void ParticleContextAdd(ParticleContext* ctx) {

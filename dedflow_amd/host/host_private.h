@@ -76,6 +76,7 @@ typedef struct MeshExt {
     const f64* ext_load;           /* device [3N] external load on the momentum rows (DflMeshSetExternalLoad), NULL: none */
     struct ScalarState* scalar;    /* phi / T transport (host/scalar.c, DflMeshSetScalarTransport), NULL: off */
     const f64* heat_source;        /* device [N] heat source of the T rows (DflMeshSetHeatSource), NULL: none */
+    const f64* vol_source;         /* device [N] volume source of the p rows (DflMeshSetVolumeSource), NULL: none */
 } MeshExt;
 
 void DflMeshPrepareFaces(Mesh3D* mesh, index_type group);
@@ -119,6 +120,7 @@ typedef struct ParticleExt {
     f64 in_r_lo, in_r_hi;
     struct HeatState* heat;                     /* particle heat transfer (host/heat.c), NULL when off */
     struct LaserState* laser;                   /* laser energy deposition (host/laser.c), NULL when off; needs heat */
+    struct CaptureState* capture;               /* melt-pool capture (host/capture.c), NULL when off; needs the coupling */
 } ParticleExt;
 /* the per-particle sizes of the kernels (all NULL, rmax 0 while x->radius == NULL: one size) */
 dfl_sizes DflSizes(const ParticleExt* x);
@@ -137,7 +139,8 @@ void DflDemBuildCells(ParticleContext* ctx);
  * the capacity, contents never carried) or the friction history (carried by grow; a compaction remaps its keys itself).
  * `extra`: entries beyond the capacity. */
 enum { DFL_PF_CARRIED, DFL_PF_SCRATCH, DFL_PF_HISTORY };
-enum { DFL_PF_BASE = 1, DFL_PF_FRICTION = 2, DFL_PF_SIZES = 4, DFL_PF_HEAT = 8, DFL_PF_COUPLE = 16, DFL_PF_LASER = 32, DFL_PF_FLOW = 64 };
+enum { DFL_PF_BASE = 1, DFL_PF_FRICTION = 2, DFL_PF_SIZES = 4, DFL_PF_HEAT = 8, DFL_PF_COUPLE = 16, DFL_PF_LASER = 32, DFL_PF_FLOW = 64,
+       DFL_PF_CAPTURE = 128 };
 #define DFL_PF_MAX_ROWS 48
 typedef struct DflPField {
     void** ptr;
@@ -261,6 +264,30 @@ typedef struct FlowState {
     index_type* count;               /* device [1] */
 } FlowState;
 void DflFlowFree(ParticleContext* ctx);
+/* what ParticleContextRemove and ParticleContextCapture share (host/flow.c): the flow state of a context, created with the
+ * tags 0 .. P-1 at the first call; the spares the next compaction writes, for the features that are on now; and the
+ * compaction itself: with keep [P] and its exclusive scan newid [P + 1] in the flow state and new_count = newid[P] <
+ * num_particle, every carried field and the friction history move to the survivors' new ids and the count is set */
+FlowState* DflFlowState(ParticleContext* ctx);
+void DflFlowEnsureSpares(ParticleContext* ctx);
+void DflFlowCompact(ParticleContext* ctx, index_type new_count);
+/* melt-pool capture (host/capture.c) */
+typedef struct CaptureState {
+    DflParticleCapture cfg;
+    DflParticleCaptureStats stats;
+    f64* dep;                        /* device [cap][5]: the deposits of the last capture call, by particle id (scratch) */
+    index_type N;                    /* nodes the buffers below are sized for */
+    f64 *A, *A_tmp;                  /* device [N][5]: the accumulator, and one call's node sums */
+    f64 *q_vol, *load, *q_heat;      /* device [N], [3N], [N]: what DflTimeStep registers */
+    b32 pending, heat_pending;       /* A holds something; ... that was captured with heat on */
+} CaptureState;
+void DflCaptureFree(ParticleContext* ctx);
+void DflCaptureCopy(ParticleContext* dst, const ParticleContext* src);
+void DflCaptureCouplingChanged(ParticleContext* ctx); /* SetFluidCoupling: A sized for the new mesh, nothing pending */
+b32 DflParticleCaptureOn(const ParticleContext* ctx);
+/* two_way and something pending: the source over `time` into the context's own buffers (heat NULL when nothing was captured
+ * with heat on); FALSE and nothing done otherwise */
+b32 DflCaptureTakePending(ParticleContext* ctx, f64 time, f64** q_vol, f64** load, f64** q_heat);
 struct WallState;
 void DflWallsFree(struct WallState* w);
 /* the contact sweep against the mesh walls (ParticleContextComputeForces when walls are set) */

@@ -48,6 +48,7 @@ void ParticleContextDestroy(ParticleContext* ctx) {
         DflCoupleFree(ctx);
         DflWallsFree(x->walls);
         ParticleContextSetFriction(ctx, NULL);
+        DflCaptureFree(ctx);
         DflFlowFree(ctx);
         ParticleContextSetSizes(ctx, NULL, NULL);
         DflLaserFree(ctx);
@@ -64,6 +65,7 @@ void ParticleContextCopy(ParticleContext* dst, const ParticleContext* src) {
         ArrayCopy(dst->d_arr[k], src->d_arr[k], D2D);
     }
     DflHeatCopy(dst, src); /* the thermal state travels too */
+    DflCaptureCopy(dst, src); /* the capture configuration (nothing pending) */
     /* the sizes travel with the particles (the inflow radius range is configuration and stays) */
     const ParticleExt* xs = (const ParticleExt*)src->ext;
     ParticleExt* xd = (ParticleExt*)dst->ext;

@@ -10,7 +10,8 @@
 unsigned DflParticleLiveFeatures(const ParticleContext* ctx) {
     const ParticleExt* x = (const ParticleExt*)ctx->ext;
     return DFL_PF_BASE | (x->omega ? DFL_PF_FRICTION : 0) | (x->radius ? DFL_PF_SIZES : 0) | (x->heat ? DFL_PF_HEAT : 0) |
-           (x->couple ? DFL_PF_COUPLE : 0) | (x->laser ? DFL_PF_LASER : 0) | (x->flow ? DFL_PF_FLOW : 0);
+           (x->couple ? DFL_PF_COUPLE : 0) | (x->laser ? DFL_PF_LASER : 0) | (x->flow ? DFL_PF_FLOW : 0) |
+           (x->capture ? DFL_PF_CAPTURE : 0);
 }
 
 int DflParticleFields(ParticleContext* ctx, unsigned features, DflPField* rows) {
@@ -72,6 +73,7 @@ int DflParticleFields(ParticleContext* ctx, unsigned features, DflPField* rows) 
         ROW(DFL_PF_SCRATCH, f->newid, sizeof(index_type), 1); /* the exclusive scan of keep and its total */
         SCRATCH(f->rtet, sizeof(index_type));
     }
+    if (features & DFL_PF_CAPTURE) SCRATCH(x->capture->dep, 5 * sizeof(f64)); /* rewritten by every capture call */
 #undef SCRATCH
 #undef CARRIED
 #undef ROW

@@ -1140,6 +1140,77 @@ void ParticleContextLaserTally(ParticleContext* ctx, DflLaserTally* out); /* the
  * (0 and NULL pointers when off) */
 index_type ParticleContextLaserColumns(const ParticleContext* ctx, const f64** transmitted, const index_type** face);
 
+/* ---- melt-pool capture (build-defined; opt-in) ---------------------------------------------------------------------------
+ * The reference's particle hooks are empty and its continuity equation has no source.  A context that never calls
+ * ParticleContextSetCapture with a configuration, and a mesh that never gets a volume source, compute bit for bit what they
+ * compute without this section, through the same launches.  The context must be coupled to a mesh
+ * (ParticleContextSetFluidCoupling).  One GPU only.  A particle that reaches the metal surface phi = level where the fluid
+ * is molten leaves the particle set and joins the fluid as mass, momentum and heat.
+ *   decision    ParticleContextCapture first runs ParticleContextLocate.  For particle i in tet t = tet_i >= 0 with nodes
+ *               n_a = ien[4t + a] and weights lambda_a, I(f) = ((lambda_0 f_0 + lambda_1 f_1) + lambda_2 f_2) + lambda_3 f_3
+ *               without fused multiply-add; phi_p = I(w[4N + n_a]), T_f = I(w[5N + n_a]), u_f as the drag computes it.
+ *               g = sum_a phi_a grad N_a, the tet's constant gradient, from the node coordinates x_a in closed form: with
+ *               e_k = x_k - x_0, c23 = e_2 x e_3, c31 = e_3 x e_1, c12 = e_1 x e_2 and det = (e_1 . c23),
+ *                 g_d = (((phi_1 - phi_0) c23_d + (phi_2 - phi_0) c31_d) + (phi_3 - phi_0) c12_d) / det,
+ *               |g| = sqrt((g0 g0 + g1 g1) + g2 g2).  c_i = side (phi_p - level) + (reach r_i) |g|: for a distance-like phi
+ *               (|g| = 1) reach = 0 asks the centre to cross the surface and reach = 1 the sphere to touch it.  Captured
+ *               iff t >= 0, c_i >= 0 and T_f >= T_melt; a NaN anywhere captures nothing; particles at tet -1 or -2 are
+ *               kept (removing those is the outflow's job).
+ *   deposits    of a captured particle, with m_i, r_i the particle's mass and radius (ParticleMass / ParticleRadius when
+ *               monodisperse): volume V_i = m_i / rho_f (rho_f of the coupling: mass is conserved in the single-density
+ *               fluid), excess momentum dP_i = m_i (v_i - u_f), excess heat E_i = (m_i cp_p)(T_i - T_f) with heat on, else
+ *               0.  Latent heat is not modelled.
+ *   nodes       one accumulator A[N][5] = (vol, mom0, mom1, mom2, heat), A[n_a] += lambda_a (V_i, dP_i, E_i), summed in
+ *               the fixed order of the reaction load (particles sorted by tet, stable by id; nodes walk their sorted V2E
+ *               lists) by one sort and one node pass for all five components: no float atomics, bitwise reproducible;
+ *               sum_a A[a] = the sum over the captured particles to rounding.  The drag impulse and the convective energy
+ *               still pending on a captured particle go where ParticleContextRemove sends them.
+ *   compaction  the stable compaction of ParticleContextRemove: survivors keep their order and every carried field, friction
+ *               history partners are remapped, entries whose partner was captured are dropped.  ParticleContextSetCapture
+ *               creates the tags as the first Set*flow call does.  A call reads 4 bytes back (the new count), allocates
+ *               nothing and does nothing further when no particle was captured.
+ *   source      ParticleContextCaptureSource(ctx, time, q_vol, load, q_heat) writes A / time into q_vol [N] (m^3/s),
+ *               load [3N] (N) and q_heat [N] (W) -- any of them may be NULL, which drops that part -- and clears A.  The
+ *               caller gives the time window: a deposit applied as a rate over a fluid step of that length delivers
+ *               exactly the deposited amount.  time <= 0 is an ASSERT.
+ *   p rows      with a volume source registered (DflMeshSetVolumeSource) every F assembly subtracts it from F[3N:4N): the
+ *               residual is R_p = (...) - q_V, after the tet and face terms and before the Dirichlet rows, so the converged
+ *               field has int N_a div u = q_V[a]: the velocity diverges where metal arrives, the level set moves out with
+ *               u, and the liquid volume grows by the deposited volume.  Explicit: not in J.
+ *   time step   with two_way and something pending, DflTimeStep takes the source with time = kDT, registers q_vol as the
+ *               volume source (one already registered is an ASSERT, as for the load), adds the momentum rate to the load
+ *               and the heat rate to the heat source it registers (in the capture's own buffers, together with the reaction
+ *               load / particle heat source when those are pending too) and restores the caller's registrations after the
+ *               solve.  After the particle sub-steps it calls ParticleContextCapture(pctx, wgold), then
+ *               ParticleContextRemove.  That call locates the particles at their positions after the sub-steps whether or
+ *               not it captures anything, as ParticleContextRemove with outside_mesh does: with capture set, a two-way
+ *               reaction load or heat source taken afterwards is spread with the weights of those positions, not with
+ *               those of the last sub-step's locate, so a two-way coupled run with capture set that never fires agrees
+ *               with the run without capture to the change of those weights, not bit for bit.  One-way runs are
+ *               bit-identical.
+ *   travel      ParticleContextCopy carries the configuration (to a coupled dst), not the pending A;
+ *               ParticleContextSetFluidCoupling on another mesh resizes A and drops what was pending; Save / Load are
+ *               untouched: capture has no per-particle state. */
+typedef struct DflParticleCapture {
+    f64 level;        /* phi value of the metal surface */
+    index_type side;  /* +1: metal where phi > level, -1: metal where phi < level (anything else: refused on stderr) */
+    f64 reach;        /* >= 0, in particle radii: 0 = the centre must cross, 1 = the sphere touches the surface */
+    f64 T_melt;       /* captured only where the fluid has T_f >= T_melt; -HUGE_VAL: anywhere */
+    b32 two_way;      /* DflTimeStep puts the deposits on the p, momentum and T rows */
+} DflParticleCapture;
+typedef struct DflParticleCaptureStats {
+    int64_t captured; /* since capture was first set on the context */
+    index_type last;  /* by the last ParticleContextCapture */
+} DflParticleCaptureStats;
+/* the configuration is copied; NULL: off, frees the state.  Reported on stderr, context unchanged: side not +-1, reach < 0
+ * or not finite, an uncoupled context */
+void ParticleContextSetCapture(ParticleContext* ctx, const DflParticleCapture* cfg);
+index_type ParticleContextCapture(ParticleContext* ctx, const f64* w); /* w: device 6N fluid state; returns the number captured */
+void ParticleContextCaptureSource(ParticleContext* ctx, f64 time, f64* q_vol, f64* load, f64* q_heat);
+void ParticleContextCaptureStats(const ParticleContext* ctx, DflParticleCaptureStats* out); /* zeros when off */
+void DflMeshSetVolumeSource(Mesh3D* mesh, const f64* q_vol);     /* device [N], m^3/s; NULL = none; must outlive registration */
+const f64* DflMeshVolumeSource(const Mesh3D* mesh);
+
 #ifdef __cplusplus
 }
 #endif

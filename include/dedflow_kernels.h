@@ -538,6 +538,10 @@ void dfl_couple_node_load(dfl_index N, const dfl_index* vrow, const dfl_index* v
 void dfl_couple_node_scalar(dfl_index N, const dfl_index* vrow, const dfl_index* vcol, const dfl_index* ien,
                             const dfl_index* tstart, const dfl_index* members, const dfl_value* lambda, const dfl_value* e,
                             dfl_value scale, dfl_value* out, void* stream);
+/* the same sum of five values per particle (the deposits of the melt-pool capture): out[5a + d] = -scale * sum ... dep[p][d] */
+void dfl_couple_node_deposit(dfl_index N, const dfl_index* vrow, const dfl_index* vcol, const dfl_index* ien,
+                             const dfl_index* tstart, const dfl_index* members, const dfl_value* lambda, const dfl_value* dep,
+                             dfl_value scale, dfl_value* out, void* stream);
 
 /* ---- particle inflow and outflow (build-defined, opt-in; csrc/k_flow.hip, model in include/dedflow.h)
  *    dfl_flow_flag          keep[i] = 0 when particle i is beyond a plane (n . x > d) or, by_tet, at tet[i] == -1; else 1.
@@ -718,6 +722,22 @@ void dfl_laser_deposit(dfl_index ns, const dfl_index* soff, const dfl_index* sfa
 void dfl_laser_tally(dfl_index ncol, dfl_value power, const dfl_value* part, dfl_value* tally, void* stream);
 void dfl_laser_source_add(dfl_index ns, const dfl_index* snode, dfl_value inv_time, dfl_value* energy, dfl_value* q,
                           void* stream);
+
+/* ---- melt-pool capture (build-defined, opt-in; csrc/k_capture.hip, model in include/dedflow.h)
+ *    dfl_capture_flag       one thread per particle: the decision of include/dedflow.h from tet / lambda (of a locate just
+ *                           run), the node coordinates xg and the fluid state w [6N].  keep[i] = 0 when captured, else 1;
+ *                           rtet[i] = the tet of a captured particle, else -1; dep[5i ..] = (V, dP0, dP1, dP2, E) of a
+ *                           captured particle, zeros otherwise.  mass_i / radius_i NULL: the scalars.  temp NULL (heat
+ *                           off): E = 0.  No LDS, no atomics
+ *    dfl_capture_source     q_vol[a] = A[5a] / time, load[3a + d] = A[5a + 1 + d] / time, q_heat[a] = A[5a + 4] / time; any
+ *                           of the three may be NULL */
+void dfl_capture_flag(dfl_index P, const dfl_index* tet, const dfl_value* lambda, const dfl_index* ien, const dfl_value* xg,
+                      const dfl_value* w, dfl_index N, const dfl_value* vel, const dfl_value* temp, dfl_value mass,
+                      dfl_value radius, const dfl_value* mass_i, const dfl_value* radius_i, dfl_value rho_f, dfl_value cp_p,
+                      dfl_value level, dfl_value side, dfl_value reach, dfl_value T_melt, dfl_index* keep, dfl_index* rtet,
+                      dfl_value* dep, void* stream);
+void dfl_capture_source(dfl_index N, const dfl_value* A, dfl_value time, dfl_value* q_vol, dfl_value* load, dfl_value* q_heat,
+                        void* stream);
 
 /* ---- scalar transport (host/scalar.c, csrc/k_scalar.hip) ------------------------------------------------------------
  * dfl_assemble_scalar_jacobian: the level-set and temperature Jacobians (d R_phi / d dphi, d R_T / d dT) over the nodal
