@@ -776,24 +776,29 @@ void dfl_pc_jacobi_apply_scaled(I N, I n, const T* dinv33, const T* dinv1, const
 }
 
 void dfl_block3_invert(I N, T* diag33, void* stream) {
+    if (N <= 0) return;
     block3_invert_kernel<<<ceil_div(N, BLK), BLK, 0, S(stream)>>>(N, diag33);
     DFL_LAUNCH_CHECK();
 }
 void dfl_block3_apply(I N, const T* dinv33, const T* x, T* y, void* stream) {
+    if (N <= 0) return;
     block3_apply_kernel<<<ceil_div(N, BLK), BLK, 0, S(stream)>>>(N, dinv33, x, y);
     DFL_LAUNCH_CHECK();
 }
 
 void dfl_bcsr_get_diag(I N, const I* rp, const I* ci, const T* val, T* d33, T* dp, T* du, void* stream) {
+    if (N <= 0) return;
     get_diag_kernel<<<ceil_div(N, BLK), BLK, 0, S(stream)>>>(N, rp, ci, val, d33, dp, du);
     DFL_LAUNCH_CHECK();
 }
 
 void dfl_block_export_fs(I N, const I* rp, const T* val, T* A00, T* A01, T* A10, T* A11, void* stream) {
+    if (N <= 0) return;
     convert_kernel<true><<<N, BLK, 0, S(stream)>>>(N, rp, const_cast<T*>(val), A00, A01, A10, A11);
     DFL_LAUNCH_CHECK();
 }
 void dfl_block_import_fs(I N, const I* rp, T* val, const T* A00, const T* A01, const T* A10, const T* A11, void* stream) {
+    if (N <= 0) return;
     convert_kernel<false><<<N, BLK, 0, S(stream)>>>(N, rp, val, const_cast<T*>(A00), const_cast<T*>(A01), const_cast<T*>(A10),
                                                    const_cast<T*>(A11));
     DFL_LAUNCH_CHECK();
@@ -819,11 +824,13 @@ void MatrixCSRZeroRowGPU(T* matval, I num_row, I num_col, const I* rp, const I* 
     DFL_LAUNCH_CHECK();
 }
 void MatrixCSRGetDiagGPU(const T* val, const I* rp, const I* ci, T* diag, I num_row) {
+    if (num_row <= 0) return;
     ref_get_diag_kernel<<<ceil_div(num_row, BLK), BLK>>>(val, rp, ci, diag, num_row);
     DFL_LAUNCH_CHECK();
 }
 void MatrixGetDiagBlockGPU(const T* matval, I bs, I num_row, I num_col, const I* rp, const I* ci, T* out, int lda, int stride) {
     (void)num_col;
+    if (num_row <= 0) return;
     ref_get_diag_block_kernel<<<ceil_div(num_row, BLK), BLK>>>(matval, bs, num_row, rp, ci, out, lda, stride);
     DFL_LAUNCH_CHECK();
 }

@@ -18,22 +18,18 @@ Not here, on purpose: no case aims at a fault.  No null or out-of-range pointers
 (dfl_cgs_update_pc_givens_x4 aborts above 1025 columns), and no n <= 0 for the launchers that do not guard it
 (dfl_cgs_update, dfl_gemv_n, dfl_ddot, dfl_dnrm2 would ask for an empty grid).
 """
-import json
-import os
-
 import numpy as np
 import pytest
 
 import krylov_model as M
+from guarded_buffers import ALL, SENT, Pool, Recorder, assert_bits, bits, sent
 
 pytestmark = pytest.mark.gpu
 
 U = M.U
 F64, LD, I64 = np.float64, np.longdouble, np.int64
-SENT = np.array([0x7FF8DEADBEEF0BAD], np.uint64).view(F64)[0]
-GUARD = 64
 needs_extended = pytest.mark.skipif(not M.HAVE_EXTENDED, reason=M.EXTENDED_REASON)
-_RECORDS = []
+record = Recorder()
 
 
 @pytest.fixture(scope="module")
@@ -46,83 +42,7 @@ def api():
 @pytest.fixture(scope="module", autouse=True)
 def _parity_records():
     yield
-    out = os.environ.get("DFL_PARITY_OUT")
-    if out and _RECORDS:
-        with open(out, "w") as fh:
-            for r in _RECORDS:
-                fh.write(json.dumps(r) + "\n")
-
-
-def record(kernel, case, ratio):
-    _RECORDS.append({"kernel": kernel, "case": case, "max_err_over_bound": float(ratio)})
-
-
-def bits(a):
-    return np.ascontiguousarray(a, F64).view(np.uint64)
-
-
-def sent(n):
-    return np.full(int(n), SENT)
-
-
-def assert_bits(got, want, what):
-    g, w = bits(got), bits(np.asarray(want).astype(F64))
-    assert g.shape == w.shape, what
-    bad = np.flatnonzero(g != w)
-    assert bad.size == 0, "%s: %d of %d entries differ, first at %d: got %r, want %r" % (
-        what, bad.size, g.size, bad[0], np.asarray(got).ravel()[bad[0]], np.asarray(want).ravel()[bad[0]])
-
-
-class Pool:
-    """the guarded device buffers of one test; freed when the test ends"""
-
-    def __init__(self, api):
-        self.api, self.slots = api, []
-
-    def slot(self, data, off=0, dtype=F64):
-        s = Slot(self.api, data, off, dtype)
-        self.slots.append(s)
-        return s
-
-    def free(self):
-        for s in self.slots:
-            s.dev.free()
-        self.slots = []
-
-
-class Slot:
-    """a host array inside a larger device buffer: [guard | off | data | guard]"""
-
-    def __init__(self, api, data, off, dtype):
-        data = np.ascontiguousarray(data, dtype)
-        self.n, self.lo, self.dtype = data.size, GUARD + off, np.dtype(dtype)
-        fill = SENT if dtype == F64 else 0x5A5A5A5A
-        self.image = np.full(self.lo + self.n + GUARD + 1, fill, dtype)
-        self.image[self.lo: self.lo + self.n] = data
-        self.dev = api.DeviceArray(self.image.size, dtype)
-        self.dev.upload(self.image)
-        self.ptr = self.dev.ptr + self.lo * self.dtype.itemsize
-        assert (self.ptr & 15) == (8 * off if dtype == F64 else 0)
-
-    def reset(self, data=None):
-        if data is not None:
-            self.image[self.lo: self.lo + self.n] = data
-        self.dev.upload(self.image)
-
-    def get(self):
-        return self.dev.numpy()[self.lo: self.lo + self.n]
-
-    def check(self, what, written=None):
-        """bands, and every entry outside the boolean mask `written`, hold what was uploaded; returns the data"""
-        now = self.dev.numpy()
-        raw = lambda a: a.view(np.uint64) if self.dtype == F64 else a
-        keep = np.ones(now.size, bool)
-        if written is not None:
-            keep[self.lo: self.lo + self.n] = ~np.broadcast_to(written, (self.n,))
-        bad = np.flatnonzero(keep & (raw(now) != raw(self.image)))
-        assert bad.size == 0, "%s: %d entries outside the output changed, first at offset %d" % (
-            what, bad.size, bad[0] - self.lo)
-        return now[self.lo: self.lo + self.n]
+    record.write()
 
 
 @pytest.fixture
@@ -130,9 +50,6 @@ def pool(api):
     p = Pool(api)
     yield p
     p.free()
-
-
-ALL = True  # written-mask: the whole array is output
 
 
 def with_gaps(Q, n, ncol, ldq):
