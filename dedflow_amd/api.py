@@ -639,6 +639,13 @@ class DflScalarTransport(C.Structure):
                 ("pc", C.c_int), ("rtol", C.c_double), ("maxit", C.c_int32)]
 
 
+class DflSurfaceForces(C.Structure):
+    _fields_ = [("level", C.c_double), ("side", C.c_int32), ("eps", C.c_double), ("sigma0", C.c_double),
+                ("dsigma_dT", C.c_double), ("T_ref", C.c_double), ("recoil_p0", C.c_double), ("recoil_a", C.c_double),
+                ("T_boil", C.c_double), ("h_conv", C.c_double), ("emissivity", C.c_double), ("T_amb", C.c_double),
+                ("evap_q0", C.c_double), ("in_time_step", C.c_int32)]
+
+
 class DflComm(C.Structure):
     _fields_ = [("allreduce_sum", ALLREDUCE_FN), ("halo_exchange", HALO_FN), ("ctx", vp), ("num_owned_node", C.c_int32),
                 ("halo_begin", HALO_FN), ("halo_end", HALO_FN), ("num_interior_node", C.c_int32),
@@ -773,6 +780,10 @@ def _declare(L):
     f("DflMeshScalarResidual", vp, [C.POINTER(Mesh3D)])
     f("DflScalarTransportSolve", i32, [C.POINTER(Mesh3D), vp, vp, vp, vp])
     f("DflScalarTransportIterations", None, [C.POINTER(Mesh3D), C.POINTER(i32)])
+    f("DflMeshSetSurfaceForces", None, [C.POINTER(Mesh3D), C.POINTER(DflSurfaceForces)])
+    f("DflMeshSurfaceForcesEnabled", i32, [C.POINTER(Mesh3D)])
+    f("DflMeshSurfaceLoad", None, [C.POINTER(Mesh3D), vp, vp, vp, vp])
+    f("DflSurfaceForcesCheck", C.c_int, [C.POINTER(DflSurfaceForces), C.c_char_p, C.c_size_t])
     f("GenerateRandomColor", None, [vp, i32, i32])
     f("dfl_abi_version", C.c_int, [])
 
@@ -964,6 +975,38 @@ class Problem:
         its = (C.c_int32 * 2)()
         lib().DflScalarTransportIterations(self.mesh, its)
         return np.array(rn[:]), (int(its[0]), int(its[1]))
+
+    # ---- free-surface forces (include/dedflow.h, "free-surface forces") ----------------------------------------------------
+    def set_surface_forces(self, level=0.0, side=1, eps=None, sigma0=0.0, dsigma_dT=0.0, T_ref=0.0, recoil_p0=0.0,
+                           recoil_a=0.0, T_boil=0.0, h_conv=0.0, emissivity=0.0, T_amb=0.0, evap_q0=0.0, in_time_step=False):
+        """DflMeshSetSurfaceForces: surface tension / Marangoni (sigma0, dsigma_dT, T_ref), recoil (recoil_p0, recoil_a,
+        T_boil) and heat loss (h_conv, emissivity, T_amb, evap_q0) of the surface phi = level smeared over the half-width eps,
+        metal where side (phi - level) > 0; in_time_step: time_step applies them itself.  eps None turns the feature off.  A
+        configuration the library refuses (reported on stderr) leaves the mesh as it was: surface_forces_on tells."""
+        if eps is None:
+            lib().DflMeshSetSurfaceForces(self.mesh, None)
+            return
+        cfg = DflSurfaceForces(float(level), int(side), float(eps), float(sigma0), float(dsigma_dT), float(T_ref),
+                               float(recoil_p0), float(recoil_a), float(T_boil), float(h_conv), float(emissivity), float(T_amb),
+                               float(evap_q0), 1 if in_time_step else 0)
+        lib().DflMeshSetSurfaceForces(self.mesh, C.byref(cfg))
+
+    @property
+    def surface_forces_on(self):
+        return bool(lib().DflMeshSurfaceForcesEnabled(self.mesh))
+
+    def surface_load(self, w, want=("load", "heat", "area")):
+        """DflMeshSurfaceLoad at the state w (DeviceArray of 6N): a dict of the wanted outputs as DeviceArrays, load [3N],
+        heat [N], area [N]; the others are passed as NULL"""
+        bad = set(want) - {"load", "heat", "area"}
+        if bad:
+            raise ValueError(f"surface_load: unknown outputs {sorted(bad)}")
+        if not self.surface_forces_on:
+            raise RuntimeError("no free-surface forces are set: call set_surface_forces first")
+        out = {k: DeviceArray(n * self.N) for k, n in (("load", 3), ("heat", 1), ("area", 1)) if k in want}
+        ptr = [out[k].ptr if k in out else None for k in ("load", "heat", "area")]
+        lib().DflMeshSurfaceLoad(self.mesh, w.ptr, ptr[0], ptr[1], ptr[2])
+        return out
 
     def close(self):
         L = lib()

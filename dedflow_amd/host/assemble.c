@@ -44,7 +44,8 @@ void DflMeshGeometryChanged(Mesh3D* mesh) {
     if (!x) return;
     CdamFreeDevice(x->egeo_b, 0);
     x->egeo_b = NULL;
-    /* schedule 4 and the residual kernels recompute the geometry from the node records; the face lists hold no geometry */
+    /* schedule 4 and the residual kernels recompute the geometry from the node records; the face lists hold no geometry,
+       and the free-surface state (host/surface.c) holds connectivity only: its kernels read xg at every call */
 }
 b32 DflQuiet(void) { return g_quiet; }
 

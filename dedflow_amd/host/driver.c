@@ -140,7 +140,8 @@ index_type SolveFlowSystem(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matr
  * source of the T rows.  With inflow / outflow set on the context (ParticleContextSetInflow / SetOutflow),
  * ParticleContextAdd runs after the predictor and ParticleContextRemove after the particle sub-steps; with capture set
  * (ParticleContextSetCapture) ParticleContextCapture runs just before that Remove, and with its two_way the deposits of
- * the previous step enter the p, momentum and T rows of this step's Newton solve. */
+ * the previous step enter the p, momentum and T rows of this step's Newton solve.  With free-surface forces set on the mesh
+ * with in_time_step (DflMeshSetSurfaceForces), their load and heat loss at wgold enter the momentum and T rows as well. */
 index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* J, f64* F, f64* dx, Krylov* ksp, Dirichlet** bcs,
                        index_type nbc, index_type newton_maxit, ParticleContext* pctx, index_type dem_substeps, f64* rnorm_out,
                        f64* rnorm_init_out) {
@@ -155,6 +156,10 @@ index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* 
     }
     if (DflMeshScalarTransportEnabled(mesh) && KrylovGetComm(ksp)) {
         fprintf(stderr, "DflTimeStep: the phi / T transport is single-GPU only; the solver has a communicator: step refused\n");
+        return -1;
+    }
+    if (DflSurfaceInTimeStep(mesh) && KrylovGetComm(ksp)) {
+        fprintf(stderr, "DflTimeStep: the free-surface forces are single-GPU only; the solver has a communicator: step refused\n");
         return -1;
     }
     DflRangePush("DflTimeStep");
@@ -186,6 +191,17 @@ index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* 
             else ASSERT(!user_heat && "DflTimeStep: a two-way capture step cannot add to a heat source already registered");
             DflMeshSetHeatSource(mesh, heat = cap_heat);
         }
+    }
+    /* the free-surface forces at wgold (in_time_step): surface tension, Marangoni and recoil on top of the load, the surface
+       heat loss on top of the heat source, in the mesh's own buffers */
+    f64 *surf_load = NULL, *surf_heat = NULL;
+    if (DflSurfaceTakeLoad(mesh, wgold, &surf_load, &surf_heat)) {
+        if (reaction) dfl_daxpy(3 * N, 1.0, reaction, surf_load, s);
+        else ASSERT(!user_load && "DflTimeStep: a free-surface step cannot add to an external load already registered");
+        DflMeshSetExternalLoad(mesh, reaction = surf_load);
+        if (heat) dfl_daxpy(N, 1.0, heat, surf_heat, s);
+        else ASSERT(!user_heat && "DflTimeStep: a free-surface step cannot add to a heat source already registered");
+        DflMeshSetHeatSource(mesh, heat = surf_heat);
     }
     dfl_alpha_predict(N, fac_pred, dwg, s);
     if (pctx) ParticleContextAdd(pctx); /* main.c:547-548; a no-op unless inflow is set */

@@ -77,6 +77,7 @@ typedef struct MeshExt {
     struct ScalarState* scalar;    /* phi / T transport (host/scalar.c, DflMeshSetScalarTransport), NULL: off */
     const f64* heat_source;        /* device [N] heat source of the T rows (DflMeshSetHeatSource), NULL: none */
     const f64* vol_source;         /* device [N] volume source of the p rows (DflMeshSetVolumeSource), NULL: none */
+    struct SurfaceState* surface;  /* free-surface forces (host/surface.c, DflMeshSetSurfaceForces), NULL: off */
 } MeshExt;
 
 void DflMeshPrepareFaces(Mesh3D* mesh, index_type group);
@@ -331,6 +332,17 @@ void DflScalarCaptureResidual(Mesh3D* mesh, const f64* F);        /* F[4N:6N) ->
 void DflScalarSolveIncrements(Mesh3D* mesh, f64* wgalpha, f64* dwgalpha, f64* dx2); /* Jacobians + both solves -> dx2 [2N] */
 void DflScalarNorms(Mesh3D* mesh, f64* out2);                      /* ||R_phi||, ||R_T|| of that residual (synchronises) */
 void DflScalarWork(Mesh3D* mesh, f64** F, f64** dx2);              /* scratch [6N], [2N] of DflScalarTransportSolve */
+/* the V2E map of a mesh's tets with every list ascending, device [N + 1] and [4T] (allocates and synchronises) */
+void DflMeshBuildSortedV2E(const Mesh3D* mesh, index_type** vrow_out, index_type** vcol_out);
+
+/* host/surface.c: the free-surface forces of a mesh */
+struct SurfaceState;
+void DflSurfaceFree(struct SurfaceState* st);
+/* 0 when DflMeshSetSurfaceForces accepts the configuration, else why not in `why` */
+int DflSurfaceForcesCheck(const DflSurfaceForces* cfg, char* why, size_t why_len);
+b32 DflSurfaceInTimeStep(const Mesh3D* mesh); /* a configuration with in_time_step is set */
+/* in_time_step is set: load [3N] and q_heat [N] at the state w into the mesh's own buffers; FALSE and nothing done otherwise */
+b32 DflSurfaceTakeLoad(Mesh3D* mesh, const f64* w, f64** load, f64** q_heat);
 
 /* named ranges for rocprofv3 --marker-trace (DFL_ROCTX=1); no-ops otherwise */
 void DflRangePush(const char* name);

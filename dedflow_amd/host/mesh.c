@@ -96,6 +96,7 @@ void Mesh3DDestroy(Mesh3D* m) {
         DflFreeRhsPatchSchedule(x->rhspatch);
         DflFreeFlowWork(x->flow);
         DflScalarFree(x->scalar);
+        DflSurfaceFree(x->surface);
         CdamFreeDevice(x->egeo_b, 0);
         CdamFreeDevice(x->nodep, 0);
         CdamFreeDevice(x->nodexu, 0);

@@ -104,8 +104,9 @@ void DflScalarCaptureResidual(Mesh3D* mesh, const f64* F) {
     dirichlet_nodes_vec(mesh, st->cfg.dirichlet_T, st->res + N);
 }
 
-/* the V2E map (every list ascending) of a mesh: built once per transport state, or per call without one */
-static void build_v2e(const Mesh3D* mesh, index_type** vrow_out, index_type** vcol_out) {
+/* the V2E map (every list ascending) of a mesh: built once per transport state, or per call without one; the free-surface
+ * forces (host/surface.c) build theirs with it too */
+void DflMeshBuildSortedV2E(const Mesh3D* mesh, index_type** vrow_out, index_type** vcol_out) {
     const Mesh3DData* dev = Mesh3DDevice(mesh);
     const index_type N = Mesh3DNumNode(mesh), T = Mesh3DNumTet(mesh);
     hipStream_t s = DflStream();
@@ -139,11 +140,11 @@ void DflAssembleScalarJacobian(Mesh3D* mesh, f64* wgalpha, f64* dwgalpha, Matrix
     hipStream_t s = DflStream();
     index_type *vrow = NULL, *vcol = NULL;
     if (st) {
-        if (!st->vrow) build_v2e(mesh, &st->vrow, &st->vcol);
+        if (!st->vrow) DflMeshBuildSortedV2E(mesh, &st->vrow, &st->vcol);
         vrow = st->vrow;
         vcol = st->vcol;
     } else {
-        build_v2e(mesh, &vrow, &vcol);
+        DflMeshBuildSortedV2E(mesh, &vrow, &vcol);
     }
     const CSRAttr* ap = Jphi ? ((MatrixCSR*)Jphi->data)->attr : NULL;
     const CSRAttr* at = JT ? ((MatrixCSR*)JT->data)->attr : NULL;

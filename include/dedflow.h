@@ -1211,6 +1211,63 @@ void ParticleContextCaptureStats(const ParticleContext* ctx, DflParticleCaptureS
 void DflMeshSetVolumeSource(Mesh3D* mesh, const f64* q_vol);     /* device [N], m^3/s; NULL = none; must outlive registration */
 const f64* DflMeshVolumeSource(const Mesh3D* mesh);
 
+/* ---- free-surface forces (build-defined; opt-in) ------------------------------------------------------------------------
+ * The reference's level set carries no surface physics.  A mesh that never calls DflMeshSetSurfaceForces with a
+ * configuration, or clears it with NULL, computes bit for bit what it computes without this section, through the same
+ * launches.  One GPU only.  With a configuration the surface phi = level of the melt pool gets surface tension, the
+ * Marangoni stress of a temperature-dependent sigma, the recoil pressure of the evaporating metal and the surface heat loss,
+ * as a smeared interface with every term explicit, evaluated at the state w the caller passes.
+ *   tet         with nodes n_a = ien[4e + a], coordinates x_a, phi_a = w[4N + n_a], T_a = w[5N + n_a]; grad N_a and det in
+ *               the closed form of the capture section: e_k = x_k - x_0, c23 = e_2 x e_3, c31 = e_3 x e_1, c12 = e_1 x e_2,
+ *               det = e_1 . c23, grad N_1 = c23 / det, grad N_2 = c31 / det, grad N_3 = c12 / det,
+ *               grad N_0 = -((c23 + c31) + c12) / det.  g = sum_a phi_a grad N_a as the capture section forms it,
+ *               |g| = sqrt((g0 g0 + g1 g1) + g2 g2); a tet with !(|g| > 0) contributes nothing.  n = g / |g| and
+ *               d_a = (phi_a - level) / |g|, the tet's own distance: the band keeps its physical half-width eps where phi is
+ *               not a distance function.  A tet with all d_a >= eps or all d_a <= -eps contributes nothing.
+ *   quadrature  the four points of the assembly, N_a(q) = 0.5854101966249685 (a = q) or 0.1381966011250105, weight 1/24:
+ *               d_q = sum_a N_a(q) d_a, T_q = sum_a N_a(q) T_a, t = d_q / eps,
+ *               delta_q = |t| < 1 ? 15 / (16 eps) (1 - t t)^2 : 0   (the biweight kernel: a polynomial, C1, integral 1),
+ *               W_q = |det| / 24 delta_q,
+ *               sigma_q = max(0, sigma0 + dsigma_dT (T_q - T_ref)),
+ *               E_q = exp(recoil_a (1 - T_boil / T_q)) where T_q > 0, else the recoil and evaporation terms are 0,
+ *               p_q = recoil_p0 > 0 ? recoil_p0 E_q : 0,
+ *               loss_q = h_conv (T_q - T_amb) + emissivity kSB (T_q^4 - T_amb^4) + evap_q0 E_q sqrt(T_boil / T_q),
+ *               kSB = 5.670374419e-8, each of the three only while its coefficient is > 0.
+ *   tet node    S = sum_q W_q sigma_q,
+ *               f_a    = -S (grad N_a - n (n . grad N_a)) + side n sum_q W_q p_q N_a(q)   (N),
+ *               heat_a = -sum_q W_q loss_q N_a(q)                                         (W, the unit of DflMeshSetHeatSource),
+ *               area_a =  sum_q W_q N_a(q)                                                (nodal share of the smeared area).
+ *               The first term of f_a is the Laplace-Beltrami weak form -int sigma P : grad v with P = I - n n: it needs
+ *               first derivatives of phi only, and a variable sigma gives the Marangoni stress without further code.  The
+ *               recoil normal side n points into the metal, where side (phi - level) > 0.
+ *   nodes       load[3a + d], q_heat[a], area[a] = the sums over node a's tets in ascending tet id, starting from +0.0:
+ *               a one-byte-per-tet band pass and one launch over the nodes' sorted tet lists (csrc/k_surface.hip), no float
+ *               atomics, bitwise reproducible, the same under every assembly schedule.  DFL_SURFACE_FLAGS=0 (read by
+ *               DflMeshSetSurfaceForces) drops the band pass: the node pass then tests the band itself, with the same bits out.
+ *   time step   with in_time_step, DflTimeStep evaluates load and q_heat at wgold before the predictor into buffers the
+ *               mesh owns, adds the reaction / capture load and the particle / capture heat source that are pending, registers
+ *               both (DflMeshSetExternalLoad, DflMeshSetHeatSource; one the caller registered already is an ASSERT, as for
+ *               the reaction load) and restores the caller's registrations after the solve.  With a communicator it prints
+ *               why and returns -1.
+ * Explicit surface tension is stable only below the capillary time step, dt < sqrt(rho h^3 / (2 pi sigma)) with h the tet
+ * size at the surface: keeping the step (kDT) below it is the caller's condition, nothing here checks it.  The mass the
+ * evaporation carries away and latent heat are not modelled: evap_q0 is a heat loss only. */
+typedef struct DflSurfaceForces {
+    f64 level; index_type side; f64 eps;      /* surface phi = level; metal where side (phi - level) > 0; half-width of the band (length) */
+    f64 sigma0, dsigma_dT, T_ref;
+    f64 recoil_p0, recoil_a, T_boil;          /* recoil_p0 <= 0: no recoil */
+    f64 h_conv, emissivity, T_amb, evap_q0;   /* each <= 0: that loss is off */
+    b32 in_time_step;                         /* DflTimeStep applies load and heat loss itself */
+} DflSurfaceForces;
+/* the configuration is copied; NULL: off, frees everything.  Reported on stderr, mesh unchanged: side not +-1, eps not finite
+ * or not positive, any non-finite parameter, T_boil <= 0 while recoil or evaporation is on.  Builds the sorted tet lists of
+ * the nodes and every buffer here (synchronises): DflMeshSurfaceLoad allocates nothing and does not wait for the device */
+void DflMeshSetSurfaceForces(Mesh3D* mesh, const DflSurfaceForces* cfg);
+b32  DflMeshSurfaceForcesEnabled(const Mesh3D* mesh);
+/* w: device 6N state; load [3N], q_heat [N], area [N] on the device, any of them NULL, every other one overwritten in full.
+ * Without a configuration: a line on stderr, nothing written */
+void DflMeshSurfaceLoad(Mesh3D* mesh, const f64* w, f64* load, f64* q_heat, f64* area);
+
 #ifdef __cplusplus
 }
 #endif

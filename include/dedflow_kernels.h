@@ -748,6 +748,28 @@ void dfl_assemble_scalar_jacobian(dfl_index N, const dfl_index* vrow, const dfl_
                                   const dfl_value* xg, const dfl_value* wgalpha, const dfl_index* row_ptr,
                                   const dfl_index* col_ind, dfl_value* val_phi, dfl_value* val_T, void* stream);
 
+/* ---- free-surface forces (build-defined, opt-in; host/surface.c, csrc/k_surface.hip, model in include/dedflow.h)
+ *    dfl_surface_load    the node sums load [3N], q_heat [N], area [N] (any of them NULL: not written; the others overwritten
+ *                        in full) of the smeared-interface terms at the state w [6N].  vrow / vcol: the V2E map of the tets
+ *                        with every list ascending.  A group of 16 lanes per node walks the node's list, a lane
+ *                        per tet; a lane whose tet lies outside the band leaves, the others evaluate their own node's share,
+ *                        and the group adds the shares in list order through LDS.  No atomics: bitwise reproducible.
+ *                        flag NULL: every lane gathers its tet's ien line, phi and coordinates for the band test;
+ *                        flag [T] (dfl_surface_flag_tets just run on the same w): lanes of tets with flag 0 leave after one
+ *                        byte.  Both give the same bits: the flag is the same test run by the same code.
+ *    dfl_surface_flag_tets  one thread per tet: flag[e] = 1 when the tet passes the |g| > 0 and the band test, else 0 */
+typedef struct dfl_surface_params {
+    dfl_value level, side, eps;
+    dfl_value sigma0, dsigma_dT, T_ref;
+    dfl_value recoil_p0, recoil_a, T_boil;
+    dfl_value h_conv, emissivity, T_amb, evap_q0;
+} dfl_surface_params;
+void dfl_surface_flag_tets(dfl_index T, const dfl_index* ien, const dfl_value* xg, const dfl_value* w, dfl_index N,
+                           const dfl_surface_params* prm, unsigned char* flag, void* stream);
+void dfl_surface_load(dfl_index N, const dfl_index* vrow, const dfl_index* vcol, const dfl_index* ien, const dfl_value* xg,
+                      const dfl_value* w, const dfl_surface_params* prm, const unsigned char* flag, dfl_value* load,
+                      dfl_value* q_heat, dfl_value* area, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
