@@ -646,6 +646,16 @@ class DflSurfaceForces(C.Structure):
                 ("evap_q0", C.c_double), ("in_time_step", C.c_int32)]
 
 
+class DflPhaseChange(C.Structure):
+    _fields_ = [("T_solidus", C.c_double), ("T_liquidus", C.c_double), ("latent", C.c_double), ("darcy_c", C.c_double),
+                ("darcy_b", C.c_double), ("use_phi", C.c_int32), ("level", C.c_double), ("side", C.c_int32), ("eps", C.c_double)]
+
+
+class DflPhaseChangeStats(C.Structure):
+    _fields_ = [("liquid_volume", C.c_double), ("T_max", C.c_double), ("molten", C.c_int64), ("lo", C.c_double * 3),
+                ("hi", C.c_double * 3)]
+
+
 class DflComm(C.Structure):
     _fields_ = [("allreduce_sum", ALLREDUCE_FN), ("halo_exchange", HALO_FN), ("ctx", vp), ("num_owned_node", C.c_int32),
                 ("halo_begin", HALO_FN), ("halo_end", HALO_FN), ("num_interior_node", C.c_int32),
@@ -784,6 +794,11 @@ def _declare(L):
     f("DflMeshSurfaceForcesEnabled", i32, [C.POINTER(Mesh3D)])
     f("DflMeshSurfaceLoad", None, [C.POINTER(Mesh3D), vp, vp, vp, vp])
     f("DflSurfaceForcesCheck", C.c_int, [C.POINTER(DflSurfaceForces), C.c_char_p, C.c_size_t])
+    f("DflMeshSetPhaseChange", None, [C.POINTER(Mesh3D), C.POINTER(DflPhaseChange)])
+    f("DflMeshPhaseChangeEnabled", i32, [C.POINTER(Mesh3D)])
+    f("DflPhaseChangeCheck", C.c_int, [C.POINTER(DflPhaseChange), C.c_char_p, C.c_size_t])
+    f("DflMeshPhaseCoefficients", None, [C.POINTER(Mesh3D), vp, vp, vp, vp])
+    f("DflMeshPhaseChangeStats", None, [C.POINTER(Mesh3D), vp, C.POINTER(DflPhaseChangeStats)])
     f("GenerateRandomColor", None, [vp, i32, i32])
     f("dfl_abi_version", C.c_int, [])
 
@@ -1007,6 +1022,46 @@ class Problem:
         ptr = [out[k].ptr if k in out else None for k in ("load", "heat", "area")]
         lib().DflMeshSurfaceLoad(self.mesh, w.ptr, ptr[0], ptr[1], ptr[2])
         return out
+
+    # ---- phase change (include/dedflow.h, "phase change") ---------------------------------------------------------------------
+    def set_phase_change(self, T_solidus=None, T_liquidus=None, latent=0.0, darcy_c=0.0, darcy_b=1e-3, use_phi=False, level=0.0,
+                         side=1, eps=1.0):
+        """DflMeshSetPhaseChange: latent heat (latent = rho L, J/m^3) and mushy-zone drag (darcy_c, darcy_b) between T_solidus
+        and T_liquidus; use_phi: only in the metal, where side (phi - level) > 0, smeared over eps.  T_solidus None turns the
+        feature off.  A configuration the library refuses (reported on stderr) leaves the mesh as it was: phase_change_on
+        tells."""
+        if T_solidus is None:
+            lib().DflMeshSetPhaseChange(self.mesh, None)
+            return
+        cfg = DflPhaseChange(float(T_solidus), float(T_liquidus), float(latent), float(darcy_c), float(darcy_b),
+                             1 if use_phi else 0, float(level), int(side), float(eps))
+        lib().DflMeshSetPhaseChange(self.mesh, C.byref(cfg))
+
+    @property
+    def phase_change_on(self):
+        return bool(lib().DflMeshPhaseChangeEnabled(self.mesh))
+
+    def phase_coefficients(self, w, want=("D", "H", "G")):
+        """DflMeshPhaseCoefficients at the state w (DeviceArray of 6N): a dict of the wanted outputs as DeviceArrays of N, the
+        drag coefficient D, the latent heat capacity H and the liquid volume G; the others are passed as NULL"""
+        bad = set(want) - {"D", "H", "G"}
+        if bad:
+            raise ValueError(f"phase_coefficients: unknown outputs {sorted(bad)}")
+        if not self.phase_change_on:
+            raise RuntimeError("no phase change is set: call set_phase_change first")
+        out = {k: DeviceArray(self.N) for k in ("D", "H", "G") if k in want}
+        ptr = [out[k].ptr if k in out else None for k in ("D", "H", "G")]
+        lib().DflMeshPhaseCoefficients(self.mesh, w.ptr, ptr[0], ptr[1], ptr[2])
+        return out
+
+    def phase_stats(self, w):
+        """DflMeshPhaseChangeStats at the state w: liquid_volume, T_max, molten (count), lo [3], hi [3] (synchronises)"""
+        if not self.phase_change_on:
+            raise RuntimeError("no phase change is set: call set_phase_change first")
+        s = DflPhaseChangeStats()
+        lib().DflMeshPhaseChangeStats(self.mesh, w.ptr, C.byref(s))
+        return dict(liquid_volume=float(s.liquid_volume), T_max=float(s.T_max), molten=int(s.molten), lo=np.array(s.lo[:]),
+                    hi=np.array(s.hi[:]))
 
     def close(self):
         L = lib()

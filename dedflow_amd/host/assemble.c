@@ -45,7 +45,8 @@ void DflMeshGeometryChanged(Mesh3D* mesh) {
     CdamFreeDevice(x->egeo_b, 0);
     x->egeo_b = NULL;
     /* schedule 4 and the residual kernels recompute the geometry from the node records; the face lists hold no geometry,
-       and the free-surface state (host/surface.c) holds connectivity only: its kernels read xg at every call */
+       and the free-surface and phase-change states (host/surface.c, host/phase.c) hold connectivity only: their kernels read xg
+       at every call */
 }
 b32 DflQuiet(void) { return g_quiet; }
 
@@ -229,6 +230,9 @@ void DflAssembleSystemPrepacked(Mesh3D* mesh, f64* wgalpha, f64* dwgalpha, f64* 
     if (F && x->vol_source) dfl_daxpy(num_node, -1.0, x->vol_source, F + 3 * (size_t)num_node, s);
     /* heat source on the T rows (particle heat, include/dedflow.h): R_T = (...) - q, before the rows are captured */
     if (F && x->heat_source) dfl_daxpy(num_node, -1.0, x->heat_source, F + 5 * (size_t)num_node, s);
+    /* phase change (include/dedflow.h): the drag D u on the momentum rows and fact2 D on J's diagonal blocks, the latent term
+       H dT on the T rows, before those rows are captured and before the Dirichlet rows */
+    if (x->phase) DflPhaseApplySystem(mesh, wgalpha, dwgalpha, F, J, prepacked);
     x->nodep_current = FALSE;
     if (F && x->scalar) DflScalarCaptureResidual(mesh, F); /* the phi / T rows, kept for the scalar transport (host/scalar.c) */
     if (F) HIPGUARD(hipMemsetAsync(F + 4 * (size_t)num_node, 0, (size_t)num_node * sizeof(f64) * 2, s)); /* main.c:63-66 */

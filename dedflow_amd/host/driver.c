@@ -50,6 +50,7 @@ void DflFreeFlowWork(FlowWork* fw) {
 static void alpha_states(Mesh3D* mesh, const f64* wgold, const f64* dwgold, const f64* dwg, f64* wgalpha, f64* dwgalpha) {
     const f64 fact1[] = {1.0 - kALPHAM, kALPHAM};
     const f64 fact2[] = {kDT * kALPHAF * (1.0 - kGAMMA), kDT * kALPHAF * kGAMMA};
+    ((MeshExt*)mesh->ext)->phase_current = FALSE; /* new states: the phase-change coefficients of the old ones are stale */
     f64* const nodep = DflMeshNodeRecords(mesh); /* (allocates the compact (x, u) records of the Jacobian kernel as well) */
     dfl_alpha_states2(Mesh3DNumNode(mesh), wgold, dwgold, dwg, fact1[0], fact1[1], fact2[0], fact2[1], Mesh3DDevice(mesh)->xg, wgalpha,
                       dwgalpha, nodep, ((MeshExt*)mesh->ext)->nodexu, DflStream());
@@ -92,6 +93,10 @@ index_type SolveFlowSystem(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matr
     const b32 scalar = DflMeshScalarTransportEnabled(mesh);
     if (scalar && comm) {
         fprintf(stderr, "SolveFlowSystem: the phi / T transport is single-GPU only; the solver has a communicator: solve refused\n");
+        return -1;
+    }
+    if (DflMeshPhaseChangeEnabled(mesh) && comm) {
+        fprintf(stderr, "SolveFlowSystem: the phase change is single-GPU only; the solver has a communicator: solve refused\n");
         return -1;
     }
     FlowWork* fw = fw_get(mesh);
@@ -160,6 +165,10 @@ index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* 
     }
     if (DflSurfaceInTimeStep(mesh) && KrylovGetComm(ksp)) {
         fprintf(stderr, "DflTimeStep: the free-surface forces are single-GPU only; the solver has a communicator: step refused\n");
+        return -1;
+    }
+    if (DflMeshPhaseChangeEnabled(mesh) && KrylovGetComm(ksp)) {
+        fprintf(stderr, "DflTimeStep: the phase change is single-GPU only; the solver has a communicator: step refused\n");
         return -1;
     }
     DflRangePush("DflTimeStep");

@@ -78,6 +78,8 @@ typedef struct MeshExt {
     const f64* heat_source;        /* device [N] heat source of the T rows (DflMeshSetHeatSource), NULL: none */
     const f64* vol_source;         /* device [N] volume source of the p rows (DflMeshSetVolumeSource), NULL: none */
     struct SurfaceState* surface;  /* free-surface forces (host/surface.c, DflMeshSetSurfaceForces), NULL: off */
+    struct PhaseState* phase;      /* phase change (host/phase.c, DflMeshSetPhaseChange), NULL: off */
+    b32 phase_current;             /* its D and H already hold the alpha states the next driver assembly is given */
 } MeshExt;
 
 void DflMeshPrepareFaces(Mesh3D* mesh, index_type group);
@@ -343,6 +345,16 @@ int DflSurfaceForcesCheck(const DflSurfaceForces* cfg, char* why, size_t why_len
 b32 DflSurfaceInTimeStep(const Mesh3D* mesh); /* a configuration with in_time_step is set */
 /* in_time_step is set: load [3N] and q_heat [N] at the state w into the mesh's own buffers; FALSE and nothing done otherwise */
 b32 DflSurfaceTakeLoad(Mesh3D* mesh, const f64* w, f64** load, f64** q_heat);
+
+/* host/phase.c: the phase change of a mesh (no-ops while it is off) */
+struct PhaseState;
+void DflPhaseFree(struct PhaseState* st);
+/* the drag and latent terms of one assembly: F += D u, H dT and J += fact2 D on the diagonal blocks, D and H evaluated at
+ * wgalpha.  reuse: the caller is the Newton driver, which assembles F, J and JT at the same alpha states and clears
+ * MeshExt.phase_current whenever it forms new ones; any other caller passes FALSE and the coefficients are recomputed */
+void DflPhaseApplySystem(Mesh3D* mesh, const f64* wgalpha, const f64* dwgalpha, f64* F, Matrix* J, b32 reuse);
+/* kALPHAM H on the diagonal of the T Jacobian values val_T over the nodal pattern attr */
+void DflPhaseApplyScalarJacobian(Mesh3D* mesh, const f64* wgalpha, const CSRAttr* attr, f64* val_T, b32 reuse);
 
 /* named ranges for rocprofv3 --marker-trace (DFL_ROCTX=1); no-ops otherwise */
 void DflRangePush(const char* name);

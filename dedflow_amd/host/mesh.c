@@ -97,6 +97,7 @@ void Mesh3DDestroy(Mesh3D* m) {
         DflFreeFlowWork(x->flow);
         DflScalarFree(x->scalar);
         DflSurfaceFree(x->surface);
+        DflPhaseFree(x->phase);
         CdamFreeDevice(x->egeo_b, 0);
         CdamFreeDevice(x->nodep, 0);
         CdamFreeDevice(x->nodexu, 0);

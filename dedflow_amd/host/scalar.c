@@ -131,8 +131,8 @@ static f64* csr_own_values(Matrix* A) {
     return c->val;
 }
 
-void DflAssembleScalarJacobian(Mesh3D* mesh, f64* wgalpha, f64* dwgalpha, Matrix* Jphi, Matrix* JT) {
-    UNUSED(dwgalpha);
+/* phase_reuse: the Newton driver calls, after its F assembly at the same alpha states (host/phase.c) */
+static void assemble_scalar_jacobian(Mesh3D* mesh, f64* wgalpha, Matrix* Jphi, Matrix* JT, b32 phase_reuse) {
     if (!Jphi && !JT) return;
     ScalarState* st = st_of(mesh);
     const Mesh3DData* dev = Mesh3DDevice(mesh);
@@ -160,6 +160,8 @@ void DflAssembleScalarJacobian(Mesh3D* mesh, f64* wgalpha, f64* dwgalpha, Matrix
         const CSRAttr* a = ap ? ap : at;
         dfl_assemble_scalar_jacobian(N, vrow, vcol, dev->ien, dev->xg, wgalpha, a->row_ptr, a->col_ind, vp, vt, s);
     }
+    /* latent heat (include/dedflow.h, "phase change"): kALPHAM H on the T diagonal, before the Dirichlet unit rows */
+    if (JT && ((MeshExt*)mesh->ext)->phase) DflPhaseApplyScalarJacobian(mesh, wgalpha, at, vt, phase_reuse);
     if (st) {
         if (Jphi) dirichlet_nodes_mat(mesh, st->cfg.dirichlet_phi, Jphi);
         if (JT) dirichlet_nodes_mat(mesh, st->cfg.dirichlet_T, JT);
@@ -169,6 +171,11 @@ void DflAssembleScalarJacobian(Mesh3D* mesh, f64* wgalpha, f64* dwgalpha, Matrix
         CdamFreeDevice(vcol, 0);
     }
     DflRangePop();
+}
+
+void DflAssembleScalarJacobian(Mesh3D* mesh, f64* wgalpha, f64* dwgalpha, Matrix* Jphi, Matrix* JT) {
+    UNUSED(dwgalpha);
+    assemble_scalar_jacobian(mesh, wgalpha, Jphi, JT, FALSE);
 }
 
 static Krylov* field_solver(const ScalarState* st, Matrix* A) {
@@ -199,7 +206,8 @@ void DflScalarSolveIncrements(Mesh3D* mesh, f64* wgalpha, f64* dwgalpha, f64* dx
     ASSERT(st);
     const index_type N = st->N;
     ensure_solvers(mesh, st);
-    DflAssembleScalarJacobian(mesh, wgalpha, dwgalpha, st->cfg.phi ? st->Jphi : NULL, st->cfg.T ? st->JT : NULL);
+    UNUSED(dwgalpha);
+    assemble_scalar_jacobian(mesh, wgalpha, st->cfg.phi ? st->Jphi : NULL, st->cfg.T ? st->JT : NULL, TRUE);
     HIPGUARD(hipMemsetAsync(dx2, 0, (size_t)2 * N * sizeof(f64), DflStream()));
     if (st->cfg.phi) {
         KrylovSolve(st->ksp_phi, st->Jphi, dx2, st->res);

@@ -1159,7 +1159,7 @@ index_type ParticleContextLaserColumns(const ParticleContext* ctx, const f64** t
  *   deposits    of a captured particle, with m_i, r_i the particle's mass and radius (ParticleMass / ParticleRadius when
  *               monodisperse): volume V_i = m_i / rho_f (rho_f of the coupling: mass is conserved in the single-density
  *               fluid), excess momentum dP_i = m_i (v_i - u_f), excess heat E_i = (m_i cp_p)(T_i - T_f) with heat on, else
- *               0.  Latent heat is not modelled.
+ *               0.  The latent heat of the particle is not deposited (the phase-change section below models the fluid's).
  *   nodes       one accumulator A[N][5] = (vol, mom0, mom1, mom2, heat), A[n_a] += lambda_a (V_i, dP_i, E_i), summed in
  *               the fixed order of the reaction load (particles sorted by tet, stable by id; nodes walk their sorted V2E
  *               lists) by one sort and one node pass for all five components: no float atomics, bitwise reproducible;
@@ -1251,7 +1251,8 @@ const f64* DflMeshVolumeSource(const Mesh3D* mesh);
  *               why and returns -1.
  * Explicit surface tension is stable only below the capillary time step, dt < sqrt(rho h^3 / (2 pi sigma)) with h the tet
  * size at the surface: keeping the step (kDT) below it is the caller's condition, nothing here checks it.  The mass the
- * evaporation carries away and latent heat are not modelled: evap_q0 is a heat loss only. */
+ * evaporation carries away is not modelled: evap_q0 is a heat loss only; the latent heat of melting is the phase-change
+ * section's. */
 typedef struct DflSurfaceForces {
     f64 level; index_type side; f64 eps;      /* surface phi = level; metal where side (phi - level) > 0; half-width of the band (length) */
     f64 sigma0, dsigma_dT, T_ref;
@@ -1267,6 +1268,80 @@ b32  DflMeshSurfaceForcesEnabled(const Mesh3D* mesh);
 /* w: device 6N state; load [3N], q_heat [N], area [N] on the device, any of them NULL, every other one overwritten in full.
  * Without a configuration: a line on stderr, nothing written */
 void DflMeshSurfaceLoad(Mesh3D* mesh, const f64* w, f64* load, f64* q_heat, f64* area);
+
+/* ---- phase change: latent heat and mushy-zone drag (build-defined; opt-in) ----------------------------------------------
+ * The reference's fluid has one phase.  A mesh that never calls DflMeshSetPhaseChange with a configuration, or clears it
+ * with NULL, computes bit for bit what it computes without this section, through the same launches.  One GPU only.  With
+ * a configuration the metal melts and freezes between T_solidus and T_liquidus: crossing the range costs the latent heat,
+ * and the solid and the mushy zone resist the flow with a Darcy (Carman-Kozeny) drag.
+ *   liquid      s = min(1, max(0, (T - T_solidus) / (T_liquidus - T_solidus))), fl = s s (3 - 2 s),
+ *   fraction    fl' = 6 s (1 - s) / (T_liquidus - T_solidus), which is 0 where s is clamped;
+ *               C(fl) = darcy_c (1 - fl)^2 / (fl^3 + darcy_b).  A NaN T gives fl = fl' = 0 and C = 0: a NaN freezes
+ *               nothing and costs nothing.
+ *   metal       with use_phi, per tet g, |g| and d_a = (phi_a - level) / |g| exactly as the free-surface section forms
+ *   fraction    them (the same closed form, without fused multiply-add); d_q = sum_a N_a(q) d_a, m_q = Hs(side d_q / eps),
+ *               Hs(t) = 0 for t <= -1, 1 for t >= 1, else 0.5 + 15/16 (t - 2/3 t^3 + 1/5 t^5): the integral of the
+ *               biweight kernel of delta_q; a NaN t gives 0.  A tet with !(|g| > 0) has m_q = 1 if
+ *               side (mean phi_a - level) > 0, mean = ((phi_0 + phi_1) + (phi_2 + phi_3)) / 4, else 0.  Without use_phi
+ *               m_q = 1.
+ *   tet to      the four quadrature points and W = |det| / 24 of the assembly, T_q = sum_a N_a(q) T_a:
+ *   node          D_a += W N_a(q) m_q C(fl(T_q))          drag coefficient, kg/s
+ *                 H_a += W N_a(q) m_q latent fl'(T_q)     latent heat capacity, J/K
+ *                 G_a += W N_a(q) m_q fl(T_q)             the node's share of the liquid metal volume, m^3
+ *   skip rules  part of the model, so that the flag pass and the node pass decide alike: a tet adds nothing to D, H and G
+ *               if use_phi and all side d_a <= -eps (a tet with !(|g| > 0): if its m_q = 0); nothing to D and H if all
+ *               T_a >= T_liquidus; nothing to G if all T_a <= T_solidus.
+ *   nodes       D[a], H[a], G[a] = the sums over node a's tets in ascending tet id, starting from +0.0; a switched-off
+ *               part (latent <= 0, darcy_c <= 0) gives exact +0.0.  One launch over the nodes' sorted tet lists (csrc/k_phase.hip)
+ *               that applies the skip rules itself, no float atomics, bitwise reproducible, the same under every assembly
+ *               schedule.  DFL_PHASE_FLAGS=1 (read by DflMeshSetPhaseChange) puts a one-byte-per-tet flag pass in front
+ *               (bit 0: adds to D / H, bit 1: adds to G), DFL_PHASE_FLAGS=0 drops it again, with the same bits out
+ *               either way; it is off by default because most tets stay (the whole substrate is solid) and the pass
+ *               measures slower in front than left out.
+ *   rows        implicit in the rates and lumped per node, with the coefficient evaluated inside the tets so that a mushy
+ *               band thinner than an element is still seen.  Every F assembly adds, after the tet and face terms and the
+ *               sources and before the T rows are saved for the scalar transport and the Dirichlet rows are applied,
+ *                 R[3a + d] += D_a u_a[d]     (u from wgalpha),       R[5N + a] += H_a dT_a     (dT from dwgalpha),
+ *               with D and H evaluated at (wgalpha, dwgalpha).  Every J assembly adds fact2 D_a, fact2 = kDT kALPHAF kGAMMA,
+ *               to the entries (d, d), d < 3, of node a's diagonal 4x4 block: D depends on T only, so this is the exact
+ *               derivative with respect to the velocity rates.  J must have the block layout: drag with a
+ *               reference-layout FS matrix is an ASSERT.  DflAssembleScalarJacobian adds kALPHAM H_a to the diagonal of
+ *               the T Jacobian before its Dirichlet unit rows.  Products are rounded before the add (no fused
+ *               multiply-add).  H is frozen over the Newton iteration: this is the apparent-heat-capacity Picard form.
+ *               The exact term fact2 latent fl'' dT changes sign under cooling and can make the diagonal negative for
+ *               realistic L / (cp dT); the frozen form keeps it positive and converges to the same residual.  The SUPG /
+ *               PSPG parameters do not see C: where C is large, u is approximately 0 and the stabilisation is idle.
+ *   stats       liquid volume = sum_a G_a (a fixed two-stage order), T_max over the metal nodes (a NaN is passed over),
+ *               number and bounding box of the molten nodes: fl(T_a) >= 0.5 and metal (!use_phi or
+ *               side (phi_a - level) > 0).  An empty set gives count 0, lo = +inf, hi = -inf (and T_max = -inf).
+ * Limits: one GPU (SolveFlowSystem and DflTimeStep with a communicator print why and return -1); H frozen per Newton
+ * iteration; C not in the stabilisation; no volume change on freezing (one density). */
+typedef struct DflPhaseChange {
+    f64 T_solidus, T_liquidus;      /* T_liquidus > T_solidus */
+    f64 latent;                     /* rho L, J/m^3; <= 0: no latent heat */
+    f64 darcy_c, darcy_b;           /* C(fl) = darcy_c (1-fl)^2 / (fl^3 + darcy_b), kg/(m^3 s); darcy_c <= 0: no drag; darcy_b > 0 */
+    b32 use_phi; f64 level; index_type side; f64 eps;   /* metal where side (phi - level) > 0, smeared over eps; use_phi 0: metal everywhere */
+} DflPhaseChange;
+typedef struct DflPhaseChangeStats {
+    f64 liquid_volume;  /* sum_a G_a */
+    f64 T_max;          /* over the metal nodes */
+    int64_t molten;     /* nodes with fl >= 0.5 that are metal */
+    f64 lo[3], hi[3];   /* their bounding box */
+} DflPhaseChangeStats;
+/* the configuration is copied; NULL: off, frees everything.  Reported on stderr, mesh unchanged: any non-finite parameter,
+ * T_liquidus <= T_solidus, darcy_b <= 0 while drag is on, use_phi with side not +-1 or eps <= 0.  Builds the sorted tet
+ * lists of the nodes and every buffer here (synchronises): the later calls allocate nothing and, but for the stats, do not
+ * wait for the device */
+void DflMeshSetPhaseChange(Mesh3D* mesh, const DflPhaseChange* cfg);
+b32  DflMeshPhaseChangeEnabled(const Mesh3D* mesh);
+/* host only: 0 when DflMeshSetPhaseChange accepts the configuration, else why not in `why` */
+int  DflPhaseChangeCheck(const DflPhaseChange* cfg, char* why, size_t why_len);
+/* w: device 6N state; D, H, G [N] on the device, any of them NULL, every other one overwritten in full.  Without a
+ * configuration: a line on stderr, nothing written */
+void DflMeshPhaseCoefficients(Mesh3D* mesh, const f64* w, f64* D, f64* H, f64* G);
+/* the statistics at the state w (synchronises, reads 72 bytes back); without a configuration: a line on stderr, the
+ * empty-set values */
+void DflMeshPhaseChangeStats(Mesh3D* mesh, const f64* w, DflPhaseChangeStats* out);
 
 #ifdef __cplusplus
 }

@@ -770,6 +770,42 @@ void dfl_surface_load(dfl_index N, const dfl_index* vrow, const dfl_index* vcol,
                       const dfl_value* w, const dfl_surface_params* prm, const unsigned char* flag, dfl_value* load,
                       dfl_value* q_heat, dfl_value* area, void* stream);
 
+/* ---- phase change (build-defined, opt-in; host/phase.c, csrc/k_phase.hip, model in include/dedflow.h)
+ *    dfl_phase_coefficients  the node sums D [N] (kg/s), H [N] (J/K), G [N] (m^3) at the state w [6N]; any of them NULL: not
+ *                            written, the others overwritten in full.  vrow / vcol: the V2E map of the tets with every list
+ *                            ascending.  A group of 16 lanes per node walks the node's list, a lane per tet; a lane whose
+ *                            tet the skip rules drop leaves, the others evaluate their own node's share, and the group adds
+ *                            the shares in list order through LDS.  No atomics: bitwise reproducible.  flag NULL: every lane
+ *                            gathers its tet and applies the skip rules itself; flag [T] (dfl_phase_flag_tets just run on
+ *                            the same w): a lane whose byte is 0 leaves after that byte.  Both give the same bits.
+ *    dfl_phase_flag_tets     one thread per tet: bit 0 = the tet adds to D / H, bit 1 = it adds to G
+ *    dfl_phase_apply_F       F[3a + d] += D[a] wgalpha[3a + d], F[5N + a] += H[a] dwgalpha[5N + a] (D or H NULL: that part
+ *                            is left out); products rounded before the add
+ *    dfl_phase_apply_J       val[16 k + 5 d] += fact2 D[a], d < 3, k the position of column a in row a of the nodal pattern
+ *    dfl_phase_apply_JT      val[k] += alpham H[a] on the same diagonal of a scalar CSR matrix over the nodal pattern
+ *    dfl_phase_stats         out9 = (sum G in a fixed two-stage order, T_max over metal nodes, number of molten nodes, lo[3],
+ *                            hi[3] of their coordinates); work >= dfl_phase_stats_work_size() doubles
+ * Every launcher returns at once for n <= 0. */
+typedef struct dfl_phase_params {
+    dfl_value T_solidus, T_liquidus, latent, darcy_c, darcy_b;
+    dfl_value level, side, eps;
+    int use_phi;
+} dfl_phase_params;
+void dfl_phase_flag_tets(dfl_index T, const dfl_index* ien, const dfl_value* xg, const dfl_value* w, dfl_index N,
+                         const dfl_phase_params* prm, unsigned char* flag, void* stream);
+void dfl_phase_coefficients(dfl_index N, const dfl_index* vrow, const dfl_index* vcol, const dfl_index* ien, const dfl_value* xg,
+                            const dfl_value* w, const dfl_phase_params* prm, const unsigned char* flag, dfl_value* D,
+                            dfl_value* H, dfl_value* G, void* stream);
+void dfl_phase_apply_F(dfl_index N, const dfl_value* D, const dfl_value* H, const dfl_value* wgalpha, const dfl_value* dwgalpha,
+                       dfl_value* F, void* stream);
+void dfl_phase_apply_J(dfl_index N, const dfl_index* row_ptr, const dfl_index* col_ind, const dfl_value* D, dfl_value fact2,
+                       dfl_value* val, void* stream);
+void dfl_phase_apply_JT(dfl_index N, const dfl_index* row_ptr, const dfl_index* col_ind, const dfl_value* H, dfl_value alpham,
+                        dfl_value* val, void* stream);
+dfl_index dfl_phase_stats_work_size(void);
+void dfl_phase_stats(dfl_index N, const dfl_value* xg, const dfl_value* w, const dfl_value* G, const dfl_phase_params* prm,
+                     dfl_value* work, dfl_value* out9, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
