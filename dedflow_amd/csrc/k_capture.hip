@@ -6,7 +6,7 @@
 // particle counts of a powder stream, so it runs one thread per particle in id order (what measured best for the drag
 // kernel: contiguous per-particle reads and writes), without LDS and without atomics.  The node sums run in
 // couple_node_kernel<5> (k_couple.hip) after the sort by tet; the compaction is flow_compact_kernel (k_flow.hip).
-#include "dfl_common.hpp"
+#include "tet_levelset.hpp"
 
 namespace {
 
@@ -61,22 +61,13 @@ __global__ __launch_bounds__(BLK) void capture_flag_kernel(I P, const I* __restr
             for (int d = 0; d < 3; ++d) x[3 * b + d] = xg[3 * n[b] + d];
         }
         const double phi_p = interp(l, phi), T_f = interp(l, tf);
-        // g = sum_a phi_a grad N_a = ((phi_1 - phi_0) e2 x e3 + (phi_2 - phi_0) e3 x e1 + (phi_3 - phi_0) e1 x e2) / det
-        const double e1[3] = {x[3] - x[0], x[4] - x[1], x[5] - x[2]};
-        const double e2[3] = {x[6] - x[0], x[7] - x[1], x[8] - x[2]};
-        const double e3[3] = {x[9] - x[0], x[10] - x[1], x[11] - x[2]};
-        const double c23[3] = {e2[1] * e3[2] - e2[2] * e3[1], e2[2] * e3[0] - e2[0] * e3[2], e2[0] * e3[1] - e2[1] * e3[0]};
-        const double c31[3] = {e3[1] * e1[2] - e3[2] * e1[1], e3[2] * e1[0] - e3[0] * e1[2], e3[0] * e1[1] - e3[1] * e1[0]};
-        const double c12[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
-        const double det = (e1[0] * c23[0] + e1[1] * c23[1]) + e1[2] * c23[2];
-        const double d1 = phi[1] - phi[0], d2 = phi[2] - phi[0], d3 = phi[3] - phi[0];
-        double g[3];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) g[d] = ((d1 * c23[d] + d2 * c31[d]) + d3 * c12[d]) / det;
-        const double gn = sqrt((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]);
+        TetCross c;
+        tet_cross(x, c);
+        double g[3], gn, dist[4];  // the decision needs |g| only
+        tet_levelset(c, phi, level, g, gn, dist);
         const double mass = POLY ? m[i] : mass_, radius = POLY ? r[i] : radius_;
-        const double c = side * (phi_p - level) + (reach * radius) * gn;
-        captured = c >= 0.0 && T_f >= T_melt;  // (a NaN compares false: it captures nothing)
+        const double reach_c = side * (phi_p - level) + (reach * radius) * gn;
+        captured = reach_c >= 0.0 && T_f >= T_melt;  // (a NaN compares false: it captures nothing)
         if (captured) {
             double uf[3];
             fluid_velocity(w, n, l, uf);

@@ -2,16 +2,10 @@
 // enthalpy-porosity model (build-defined: the reference has one phase; model in include/dedflow.h, "phase change"), their
 // row updates of F, J and JT, and the melt-pool statistics.
 //
-//   phase_node_kernel   row gather, the pattern of surface_node_kernel (k_surface.hip): a group of 16 lanes owns node a (16
-//                       nodes per 256-thread workgroup).  Lane j of the group takes tet j of a's V2E list (ascending tet
-//                       id), gathers the tet's ien line, the four T, the 4 x 24 B of coordinates (and with use_phi four
-//                       phi), applies the skip rules, evaluates the three values of its own node (D_a, H_a, G_a) at the
-//                       four quadrature points and parks them in LDS; lanes 0-2 of the group each own one of the three sums
-//                       and add the parked values in list order.  A wave none of whose lanes stays skips the hand-over (a
-//                       wave-uniform branch).  More than 16 tets per node: more trips.  No atomics, every output written
-//                       once (no zero pass), fixed summation order starting from +0.0 (every term is >= +0.0, so a tet that
-//                       left adds the same bits as its +0.0 would): bitwise reproducible, independent of the assembly
-//                       schedule.
+//   phase_node_kernel   the node gather of node_gather.hpp with three sums per node (D_a, H_a, G_a).  A lane gathers its
+//                       tet's ien line, the four T, the 4 x 24 B of coordinates (and with use_phi four phi), applies the
+//                       skip rules and evaluates the three values of its own node at the four quadrature points.  Every
+//                       term is >= +0.0.
 //   phase_flag_kernel   one thread per tet: the skip rules once per tet instead of four times, one byte out (bit 0: adds to
 //                       D / H, bit 1: adds to G).  The node pass then reads that byte first and a lane whose byte is 0
 //                       leaves without gathering.  Optional (DFL_PHASE_FLAGS=1, host/phase.c): unlike the surface band most
@@ -22,21 +16,20 @@
 //   phase_stats_*       two-stage fixed-order reduction over the nodes (the scheme of k_blas.hip's reduce_stage1 / 2).
 //
 // The skip rules decide what is evaluated, so both kernels must take the same decision from the same numbers: the whole
-// file is compiled without fused multiply-add, and tet_parts is the one function that decides.
+// file is compiled without fused multiply-add (as the geometry of tet_levelset.hpp is wherever it is included), and
+// tet_parts is the one function that decides.
 //
 // HBM view per coefficient call: V2E (4 B x (N + 4T)) + 8 B x N per output written; per (node, tet) pair 16 B of ien, 32 B
 // of T and 96 B of coordinates (with use_phi 32 B of phi more) gathered through L2; the flag pass gathers the same once per
 // tet, writes T bytes and the node pass reads 4T of them back.
-#include "asm_device.hpp"
+#include "node_gather.hpp"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int PH_BLK = 256;
-constexpr int PH_G = 16;                // lanes per node (a Kuhn-cube interior node has 24 tets: two trips)
-constexpr int PH_ROWS = PH_BLK / PH_G;  // nodes per workgroup
-constexpr int PH_NSTAT = 9;             // liquid volume, T_max, molten count, lo[3], hi[3]
+constexpr int PH_BLK = 256;  // the one-thread-per-node and reduction kernels
+constexpr int PH_NSTAT = 9;            // liquid volume, T_max, molten count, lo[3], hi[3]
 constexpr int PH_MAX_PART = 1024;
 
 struct TetPhase {
@@ -46,32 +39,20 @@ struct TetPhase {
     double mflat;
 };
 
-// det and, with use_phi, the signed distances of the four nodes in the closed form of the free-surface section
+// det and, with use_phi, the signed distances of the four nodes
 __device__ __forceinline__ void tet_geometry(const double* x, const double* phi, const dfl_phase_params& p, TetPhase& b) {
-    const double e1[3] = {x[3] - x[0], x[4] - x[1], x[5] - x[2]};
-    const double e2[3] = {x[6] - x[0], x[7] - x[1], x[8] - x[2]};
-    const double e3[3] = {x[9] - x[0], x[10] - x[1], x[11] - x[2]};
-    double c23[3], c31[3], c12[3];
-    c23[0] = e2[1] * e3[2] - e2[2] * e3[1]; c23[1] = e2[2] * e3[0] - e2[0] * e3[2]; c23[2] = e2[0] * e3[1] - e2[1] * e3[0];
-    b.det = (e1[0] * c23[0] + e1[1] * c23[1]) + e1[2] * c23[2];
+    TetCross c;
+    tet_cross(x, c);
+    b.det = c.det;
     b.flat = false;
     b.mflat = 1.0;
     if (!p.use_phi) return;
-    c31[0] = e3[1] * e1[2] - e3[2] * e1[1]; c31[1] = e3[2] * e1[0] - e3[0] * e1[2]; c31[2] = e3[0] * e1[1] - e3[1] * e1[0];
-    c12[0] = e1[1] * e2[2] - e1[2] * e2[1]; c12[1] = e1[2] * e2[0] - e1[0] * e2[2]; c12[2] = e1[0] * e2[1] - e1[1] * e2[0];
-    const double d1 = phi[1] - phi[0], d2 = phi[2] - phi[0], d3 = phi[3] - phi[0];
-    double g[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) g[k] = ((d1 * c23[k] + d2 * c31[k]) + d3 * c12[k]) / b.det;
-    const double gn = sqrt((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]);
-    if (!(gn > 0.0)) {
+    double g[3], gn;
+    if (!tet_levelset(c, phi, p.level, g, gn, b.d)) {
         const double mean = ((phi[0] + phi[1]) + (phi[2] + phi[3])) * 0.25;
         b.flat = true;
         b.mflat = p.side * (mean - p.level) > 0.0 ? 1.0 : 0.0;
-        return;
     }
-#pragma unroll
-    for (int a = 0; a < 4; ++a) b.d[a] = (phi[a] - p.level) / gn;
 }
 
 // the skip rules: bit 0 = the tet adds to D / H, bit 1 = it adds to G
@@ -101,10 +82,6 @@ __device__ __forceinline__ double smooth_step(double t) {  // Hs: the integral o
     if (t >= 1.0) return 1.0;
     const double t2 = t * t, t3 = t2 * t;
     return 0.5 + 0.9375 * ((t - (2.0 / 3.0) * t3) + 0.2 * (t3 * t2));
-}
-
-__device__ __forceinline__ double interp_q(int q, const double* f) {
-    return ((shl(0, q) * f[0] + shl(1, q) * f[1]) + shl(2, q) * f[2]) + shl(3, q) * f[3];
 }
 
 // s, fl, fl' and C of one temperature
@@ -155,66 +132,33 @@ __device__ __forceinline__ void gather_tet(const int4 n4, const T* __restrict__ 
     }
 }
 
-__device__ __forceinline__ int wave_max(int v) {  // the node groups of one wave share trips
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, WAVE));
-    return v;
-}
-
 template <bool FLAGS>
-__global__ __launch_bounds__(PH_BLK) void phase_node_kernel(I N, const I* __restrict__ vrow, const I* __restrict__ vcol,
+__global__ __launch_bounds__(NG_BLK) void phase_node_kernel(I N, const I* __restrict__ vrow, const I* __restrict__ vcol,
                                                              const I* __restrict__ ien, const T* __restrict__ xg,
                                                              const T* __restrict__ w, const dfl_phase_params p,
                                                              const unsigned char* __restrict__ flag, T* __restrict__ D,
                                                              T* __restrict__ H, T* __restrict__ G) {
-    __shared__ double s_val[3][PH_BLK];
-    const int t = threadIdx.x;
-    const int g = t & (PH_G - 1);
-    const int gbase = t & ~(PH_G - 1);
-    const long long row_ll = (long long)blockIdx.x * PH_ROWS + t / PH_G;
-    const bool live = row_ll < N;
-    const I row = live ? (I)row_ll : 0;
-    const I e0 = live ? vrow[row] : 0, ne = live ? vrow[row + 1] - e0 : 0;
-    const int ne_w = wave_max(ne);
-    double acc = 0.0;  // lane g < 3 of the group owns component g of the node
-    for (int jc = 0; jc < ne_w; jc += PH_G) {
-        const int j = jc + g;
-        bool stays = false;
-        double out[3] = {0.0, 0.0, 0.0};
-        if (j < ne) {
-            const I e = vcol[e0 + j];
-            int parts = FLAGS ? flag[e] : 3;
-            if (parts) {
-                const int4 n4 = reinterpret_cast<const int4*>(ien)[e];
-                double x[12], phi[4], Tn[4];
-                gather_tet(n4, xg, w, N, p.use_phi != 0, x, phi, Tn);
-                TetPhase b;
-                tet_geometry(x, phi, p, b);
-                if (!FLAGS) parts = tet_parts(b, Tn, p);
-                if (parts) {
-                    const int la = n4.x == row ? 0 : n4.y == row ? 1 : n4.z == row ? 2 : 3;
-                    tet_node_terms(b, Tn, la, parts, p, out);
-                    stays = true;
-                }
-            }
-        }
-        if (__any(stays)) {  // the same in every lane of the wave: the hand-over below is a wave barrier
-#pragma unroll
-            for (int c = 0; c < 3; ++c) s_val[c][t] = out[c];
-            WAVE_SYNC();
-            const int nj = min(PH_G, (int)ne - jc);
-            if (g < 3)
-                for (int jj = 0; jj < nj; ++jj) acc += s_val[g][gbase + jj];  // V2E order: ascending tet id
-            WAVE_SYNC();  // the parked values are consumed before the next trip overwrites them
-        }
-    }
-    if (live) {
-        if (g == 0) {
-            if (D) D[row] = acc;
-        } else if (g == 1) {
-            if (H) H[row] = acc;
-        } else if (g == 2) {
-            if (G) G[row] = acc;
+    const NodeSum s = node_gather_sum<3>(N, vrow, vcol, [&](I e, I row, double* out) {
+        int parts = FLAGS ? flag[e] : 3;
+        if (!parts) return false;
+        const int4 n4 = reinterpret_cast<const int4*>(ien)[e];
+        double x[12], phi[4], Tn[4];
+        gather_tet(n4, xg, w, N, p.use_phi != 0, x, phi, Tn);
+        TetPhase b;
+        tet_geometry(x, phi, p, b);
+        if (!FLAGS) parts = tet_parts(b, Tn, p);
+        if (!parts) return false;
+        const int la = n4.x == row ? 0 : n4.y == row ? 1 : n4.z == row ? 2 : 3;
+        tet_node_terms(b, Tn, la, parts, p, out);
+        return true;
+    });
+    if (s.live) {
+        if (s.g == 0) {
+            if (D) D[s.row] = s.acc;
+        } else if (s.g == 1) {
+            if (H) H[s.row] = s.acc;
+        } else if (s.g == 2) {
+            if (G) G[s.row] = s.acc;
         }
     }
 }
@@ -387,9 +331,9 @@ void dfl_phase_coefficients(I N, const I* vrow, const I* vcol, const I* ien, con
                             const unsigned char* flag, T* D, T* H, T* G, void* stream) {
     if (N <= 0 || (!D && !H && !G)) return;
     if (flag)
-        phase_node_kernel<true><<<ceil_div(N, PH_ROWS), PH_BLK, 0, S(stream)>>>(N, vrow, vcol, ien, xg, w, *prm, flag, D, H, G);
+        phase_node_kernel<true><<<ceil_div(N, NG_ROWS), NG_BLK, 0, S(stream)>>>(N, vrow, vcol, ien, xg, w, *prm, flag, D, H, G);
     else
-        phase_node_kernel<false><<<ceil_div(N, PH_ROWS), PH_BLK, 0, S(stream)>>>(N, vrow, vcol, ien, xg, w, *prm, flag, D, H, G);
+        phase_node_kernel<false><<<ceil_div(N, NG_ROWS), NG_BLK, 0, S(stream)>>>(N, vrow, vcol, ien, xg, w, *prm, flag, D, H, G);
     DFL_LAUNCH_CHECK();
 }
 

@@ -7,7 +7,8 @@
 // with c_a = u(q) . gradN_a, tau2 / tau3 as rhs_quad forms them at every quadrature point, f1 = alpha_m and
 // f2 = dt alpha_f gamma.  Both depend on the geometry and on u only.
 //
-//   scalar_jac_row_kernel   row gather: a group of 16 lanes owns one nodal CSR row a (16 rows per 256-thread workgroup).
+//   scalar_jac_row_kernel   row gather in the shape of node_gather.hpp (its constants and trip count; a Kuhn-cube interior
+//                           row has 15 nonzeros and 24 tets): a group of 16 lanes owns one nodal CSR row a.
 //                           Phase 1: lane j of the group takes tet j of a's V2E list (ascending tet id), evaluates the
 //                           four entries (a, b) of both element matrices and parks them with the tet's node ids in LDS.
 //                           Phase 2: lane k of the group owns nonzero k of the row and adds the parked entries whose
@@ -17,13 +18,9 @@
 //
 // HBM view per assembly: 2 x 8 B x nnz1 of values written + row_ptr / col_ind (4 B x (N + nnz1)) + V2E (4 B x 4T) + per
 // (row, tet) pair the tet's ien line (16 B) and 4 x 48 B of coordinates and velocities gathered through L2.
-#include "asm_device.hpp"
+#include "node_gather.hpp"
 
 namespace {
-
-constexpr int SC_BLK = 256;
-constexpr int SC_G = 16;                 // lanes per row (a Kuhn-cube interior row has 15 nonzeros and 24 tets)
-constexpr int SC_ROWS = SC_BLK / SC_G;  // rows per workgroup
 
 // the four entries (la, b) of both element matrices of one tet; la = the local index of the row's node
 __device__ __forceinline__ void scalar_tet_row(const double* x, const double* u, int la, double* jp, double* jt) {
@@ -80,35 +77,29 @@ __device__ __forceinline__ void scalar_tet_row(const double* x, const double* u,
     }
 }
 
-__device__ __forceinline__ int group_max(int v) {  // over the 64 lanes of the wave (row groups of one wave share trips)
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, WAVE));
-    return v;
-}
-
-__global__ __launch_bounds__(SC_BLK) void scalar_jac_row_kernel(I N, const I* __restrict__ vrow, const I* __restrict__ vcol,
+__global__ __launch_bounds__(NG_BLK) void scalar_jac_row_kernel(I N, const I* __restrict__ vrow, const I* __restrict__ vcol,
                                                                  const I* __restrict__ ien, const T* __restrict__ xg,
                                                                  const T* __restrict__ wg, const I* __restrict__ row_ptr,
                                                                  const I* __restrict__ col_ind, T* __restrict__ vphi,
                                                                  T* __restrict__ vT) {
-    __shared__ int4 s_node[SC_BLK];
-    __shared__ double s_jp[SC_BLK][4];
-    __shared__ double s_jt[SC_BLK][4];
+    __shared__ int4 s_node[NG_BLK];
+    __shared__ double s_jp[NG_BLK][4];
+    __shared__ double s_jt[NG_BLK][4];
     const int t = threadIdx.x;
-    const int g = t & (SC_G - 1);
-    const int gbase = t & ~(SC_G - 1);
-    const long long row_ll = (long long)blockIdx.x * SC_ROWS + t / SC_G;
+    const int g = t & (NG_LANES - 1);
+    const int gbase = t & ~(NG_LANES - 1);
+    const long long row_ll = (long long)blockIdx.x * NG_ROWS + t / NG_LANES;
     const bool live = row_ll < N;
     const I row = live ? (I)row_ll : 0;
     const I e0 = live ? vrow[row] : 0, ne = live ? vrow[row + 1] - e0 : 0;
     const I c0 = live ? row_ptr[row] : 0, nc = live ? row_ptr[row + 1] - c0 : 0;
     // every lane of a wave takes the same trips (the LDS hand-over below is a wave barrier)
-    const int ne_w = group_max(ne), nc_w = group_max(nc);
-    for (int kc = 0; kc < nc_w; kc += SC_G) {
+    const int ne_w = wave_max(ne), nc_w = wave_max(nc);
+    for (int kc = 0; kc < nc_w; kc += NG_LANES) {
         const int k = kc + g;
         const I col = k < nc ? col_ind[c0 + k] : -1;
         double ap = 0.0, at = 0.0;
-        for (int jc = 0; jc < ne_w; jc += SC_G) {
+        for (int jc = 0; jc < ne_w; jc += NG_LANES) {
             const int j = jc + g;
             if (j < ne) {
                 const I e = vcol[e0 + j];
@@ -133,7 +124,7 @@ __global__ __launch_bounds__(SC_BLK) void scalar_jac_row_kernel(I N, const I* __
                 }
             }
             WAVE_SYNC();
-            const int nj = min(SC_G, (int)ne - jc);
+            const int nj = min(NG_LANES, (int)ne - jc);
             if (col >= 0) {
                 for (int jj = 0; jj < nj; ++jj) {  // V2E order: ascending tet id
                     const int src = gbase + jj;
@@ -159,7 +150,7 @@ __global__ __launch_bounds__(SC_BLK) void scalar_jac_row_kernel(I N, const I* __
 extern "C" void dfl_assemble_scalar_jacobian(I N, const I* vrow, const I* vcol, const I* ien, const T* xg, const T* wgalpha,
                                              const I* row_ptr, const I* col_ind, T* val_phi, T* val_T, void* stream) {
     if (N <= 0 || (!val_phi && !val_T)) return;
-    scalar_jac_row_kernel<<<ceil_div(N, SC_ROWS), SC_BLK, 0, S(stream)>>>(N, vrow, vcol, ien, xg, wgalpha, row_ptr, col_ind,
+    scalar_jac_row_kernel<<<ceil_div(N, NG_ROWS), NG_BLK, 0, S(stream)>>>(N, vrow, vcol, ien, xg, wgalpha, row_ptr, col_ind,
                                                                           val_phi, val_T);
     DFL_LAUNCH_CHECK();
 }

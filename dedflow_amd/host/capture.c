@@ -114,7 +114,9 @@ index_type ParticleContextCapture(ParticleContext* ctx, const f64* w) {
     if (c->imp_time > 0.0) DflCoupleAccumulateRemoved(ctx, f->rtet);
     if (DflHeatPending(ctx) && h->time > 0.0) DflHeatAccumulateRemoved(ctx, f->rtet);
     dfl_couple_sort_by_tet(P, c->T, f->rtet, c->tcount, c->rank, c->tstart, c->slot, c->members, c->scan_tmp, c->scan_bytes, s);
-    dfl_couple_node_deposit(c->N, c->vrow, c->vcol, dev->ien, c->tstart, c->members, c->lambda, k->dep, -1.0, k->A_tmp, s);
+    const index_type *vrow, *vcol;
+    DflMeshSortedV2E(c->mesh, &vrow, &vcol);
+    dfl_couple_node_deposit(c->N, vrow, vcol, dev->ien, c->tstart, c->members, c->lambda, k->dep, -1.0, k->A_tmp, s);
     dfl_daxpy(5 * c->N, 1.0, k->A_tmp, k->A, s);
     k->pending = TRUE;
     if (h) k->heat_pending = TRUE;

@@ -2,8 +2,8 @@
  * dedflow_amd/csrc/k_couple.hip).  The reference keeps the hooks (SolveParticleSystem, ParticleContextUpdate in its time
  * loop) commented out and has no physics behind them.
  *
- * Per coupled mesh, built once at ParticleContextSetFluidCoupling: the V2E map with every list sorted ascending (the
- * reaction scatter walks it in that order), the tet neighbour table (from the V2E map, on the device) and a uniform seed
+ * Per coupled mesh, built once at ParticleContextSetFluidCoupling: the tet neighbour table (on the device, from the mesh's
+ * sorted V2E map, DflMeshSortedV2E, which the reaction scatter walks in that order too) and a uniform seed
  * grid over the bounding box (on the host: per cell the tet whose centroid is nearest the cell centre, empty cells filled
  * breadth-first from their neighbours).  Per particle: tet, lambda[4], impulse[3].  Per call nothing is allocated and
  * nothing waits for the device. */
@@ -22,7 +22,7 @@ void DflCoupleFree(ParticleContext* ctx) {
     if (!c) return;
     HIPGUARD(hipStreamSynchronize(DflStream()));
     DflParticleFieldsFree(ctx, DFL_PF_COUPLE);
-    CdamFreeDevice(c->vrow, 0); CdamFreeDevice(c->vcol, 0); CdamFreeDevice(c->nbr, 0); CdamFreeDevice(c->seed, 0);
+    CdamFreeDevice(c->nbr, 0); CdamFreeDevice(c->seed, 0);
     CdamFreeDevice(c->lost, 0); CdamFreeDevice(c->tcount, 0); CdamFreeDevice(c->tstart, 0); CdamFreeDevice(c->scan_tmp, 0);
     CdamFreeDevice(c->load, 0); CdamFreeDevice(c->rem_load, 0); CdamFreeDevice(c->rem_tmp, 0);
     CdamFreeHost(c, SIZE_OF(CoupleState));
@@ -101,18 +101,10 @@ static void build_mesh_tables(CoupleState* c, Mesh3D* mesh) {
     const Mesh3DData* dev = Mesh3DDevice(mesh);
     const index_type N = c->N, T = c->T;
     hipStream_t s = DflStream();
-    HIPGUARD(hipStreamSynchronize(s));
-    c->vrow = (index_type*)CdamMallocDevice(((ptrdiff_t)N + 1) * SIZE_OF(index_type));
-    HIPGUARD(hipStreamSynchronize(s));
-    GenerateV2EMapRowTetGPU(dev->ien, T, N, c->vrow);
-    index_type vnnz = 0;
-    HIPGUARD(hipMemcpy(&vnnz, c->vrow + N, sizeof vnnz, D2H));
-    c->vcol = (index_type*)CdamMallocDevice((ptrdiff_t)(vnnz > 0 ? vnnz : 1) * SIZE_OF(index_type));
-    HIPGUARD(hipStreamSynchronize(s));
-    GenerateV2EMapColTetGPU(dev->ien, T, N, c->vrow, c->vcol);
-    dfl_couple_sort_v2e(N, c->vrow, c->vcol, s);
+    const index_type *vrow, *vcol;
+    DflMeshSortedV2E(mesh, &vrow, &vcol);
     c->nbr = (index_type*)CdamMallocDevice((ptrdiff_t)(T > 0 ? T : 1) * 4 * SIZE_OF(index_type));
-    dfl_couple_neighbours(T, dev->ien, c->vrow, c->vcol, c->nbr, s);
+    dfl_couple_neighbours(T, dev->ien, vrow, vcol, c->nbr, s);
     /* the seed grid from a host copy of the device mesh (what the kernels will read) */
     f64* xg = (f64*)malloc((size_t)N * 3 * sizeof(f64) + 8);
     index_type* ien = (index_type*)malloc((size_t)T * 4 * sizeof(index_type) + 8);
@@ -229,10 +221,12 @@ void DflCoupleNodeScatter(ParticleContext* ctx, const index_type* tet, const f64
     CoupleState* c = state(ctx);
     hipStream_t s = DflStream();
     const index_type* ien = Mesh3DDevice(c->mesh)->ien;
+    const index_type *vrow, *vcol;
+    DflMeshSortedV2E(c->mesh, &vrow, &vcol);
     dfl_couple_sort_by_tet(ctx->num_particle, c->T, tet, c->tcount, c->rank, c->tstart, c->slot, c->members, c->scan_tmp,
                            c->scan_bytes, s);
-    if (ncomp == 3) dfl_couple_node_load(c->N, c->vrow, c->vcol, ien, c->tstart, c->members, c->lambda, val, scale, out, s);
-    else dfl_couple_node_scalar(c->N, c->vrow, c->vcol, ien, c->tstart, c->members, c->lambda, val, scale, out, s);
+    if (ncomp == 3) dfl_couple_node_load(c->N, vrow, vcol, ien, c->tstart, c->members, c->lambda, val, scale, out, s);
+    else dfl_couple_node_scalar(c->N, vrow, vcol, ien, c->tstart, c->members, c->lambda, val, scale, out, s);
 }
 
 void ParticleContextReactionLoad(ParticleContext* ctx, f64* load) {

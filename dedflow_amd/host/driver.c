@@ -12,11 +12,6 @@
 #include "dedflow_kernels.h"
 #include "host_private.h"
 
-#define kRHOC (0.5)
-#define kDT (5e-2)
-#define kALPHAM ((3.0 - kRHOC) / (1.0 + kRHOC))
-#define kALPHAF (1.0 / (1.0 + kRHOC))
-#define kGAMMA (0.5 + kALPHAM - kALPHAF)
 #define BS (6)
 
 typedef struct FlowWork {

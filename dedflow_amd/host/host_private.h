@@ -80,7 +80,24 @@ typedef struct MeshExt {
     struct SurfaceState* surface;  /* free-surface forces (host/surface.c, DflMeshSetSurfaceForces), NULL: off */
     struct PhaseState* phase;      /* phase change (host/phase.c, DflMeshSetPhaseChange), NULL: off */
     b32 phase_current;             /* its D and H already hold the alpha states the next driver assembly is given */
+    index_type *v2e_row, *v2e_col; /* device [N+1], [4T]: the sorted V2E map (DflMeshSortedV2E), NULL until first asked for */
 } MeshExt;
+
+/* the generalized-alpha constants of the time integration (src/assemble.cu:23-27), textually those of csrc/asm_device.hpp */
+#define kRHOC (0.5)
+#define kDT (5e-2)
+#define kALPHAM ((3.0 - kRHOC) / (1.0 + kRHOC))
+#define kALPHAF (1.0 / (1.0 + kRHOC))
+#define kGAMMA (0.5 + kALPHAM - kALPHAF)
+
+/* the sorted V2E map of a mesh: per node its tets in ascending tet id, device [N + 1] and [4T].  One per mesh, shared by every
+ * pass that sums over a node's tets in that order (scalar Jacobians, free-surface forces, phase change, the particle
+ * coupling's node scatter and neighbour table).  The pointers are borrowed: the mesh builds the map at the first call
+ * (allocates and synchronises, then never again) and Mesh3DDestroy alone frees it, so clearing one feature cannot take it
+ * from another.  It depends on the connectivity only: DflMeshGeometryChanged leaves it alone. */
+void DflMeshSortedV2E(Mesh3D* mesh, const index_type** vrow, const index_type** vcol);
+/* the [T] bytes of a per-tet flag pass, allocated or freed (after a synchronisation) to match `on` */
+void DflTetFlagsMatch(u8** flag, index_type T, b32 on);
 
 void DflMeshPrepareFaces(Mesh3D* mesh, index_type group);
 void DflMeshPrepareFaceNonzeros(Mesh3D* mesh, index_type group, const CSRAttr* spy);
@@ -162,7 +179,6 @@ typedef struct CoupleState {
     index_type N, T, P;
     DflFluidCoupling cfg;
     b32 use_order;                   /* locate in the contact sweep's cell order (DFL_COUPLE_CELL_ORDER=0: id order) */
-    index_type *vrow, *vcol;         /* device V2E map [N+1], [4T], every list ascending */
     index_type* nbr;                 /* device [T][4] */
     index_type* seed;                /* device [gdim^3] */
     index_type gdim;
@@ -334,8 +350,6 @@ void DflScalarCaptureResidual(Mesh3D* mesh, const f64* F);        /* F[4N:6N) ->
 void DflScalarSolveIncrements(Mesh3D* mesh, f64* wgalpha, f64* dwgalpha, f64* dx2); /* Jacobians + both solves -> dx2 [2N] */
 void DflScalarNorms(Mesh3D* mesh, f64* out2);                      /* ||R_phi||, ||R_T|| of that residual (synchronises) */
 void DflScalarWork(Mesh3D* mesh, f64** F, f64** dx2);              /* scratch [6N], [2N] of DflScalarTransportSolve */
-/* the V2E map of a mesh's tets with every list ascending, device [N + 1] and [4T] (allocates and synchronises) */
-void DflMeshBuildSortedV2E(const Mesh3D* mesh, index_type** vrow_out, index_type** vcol_out);
 
 /* host/surface.c: the free-surface forces of a mesh */
 struct SurfaceState;

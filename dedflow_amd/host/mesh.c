@@ -98,6 +98,8 @@ void Mesh3DDestroy(Mesh3D* m) {
         DflScalarFree(x->scalar);
         DflSurfaceFree(x->surface);
         DflPhaseFree(x->phase);
+        CdamFreeDevice(x->v2e_row, 0); /* after the feature states that borrowed it */
+        CdamFreeDevice(x->v2e_col, 0);
         CdamFreeDevice(x->egeo_b, 0);
         CdamFreeDevice(x->nodep, 0);
         CdamFreeDevice(x->nodexu, 0);
@@ -108,6 +110,38 @@ void Mesh3DDestroy(Mesh3D* m) {
         CdamFreeHost(x, SIZE_OF(MeshExt));
     }
     CdamFreeHost(m, SIZE_OF(Mesh3D));
+}
+
+void DflMeshSortedV2E(Mesh3D* mesh, const index_type** vrow_out, const index_type** vcol_out) {
+    MeshExt* x = (MeshExt*)mesh->ext;
+    if (!x->v2e_row) {
+        const Mesh3DData* dev = Mesh3DDevice(mesh);
+        const index_type N = Mesh3DNumNode(mesh), T = Mesh3DNumTet(mesh);
+        hipStream_t s = DflStream();
+        HIPGUARD(hipStreamSynchronize(s));
+        index_type* vrow = (index_type*)CdamMallocDevice(((ptrdiff_t)N + 1) * SIZE_OF(index_type));
+        HIPGUARD(hipStreamSynchronize(s));
+        GenerateV2EMapRowTetGPU(dev->ien, T, N, vrow);
+        index_type vnnz = 0;
+        HIPGUARD(hipMemcpy(&vnnz, vrow + N, sizeof vnnz, D2H));
+        index_type* vcol = (index_type*)CdamMallocDevice((ptrdiff_t)(vnnz > 0 ? vnnz : 1) * SIZE_OF(index_type));
+        HIPGUARD(hipStreamSynchronize(s));
+        GenerateV2EMapColTetGPU(dev->ien, T, N, vrow, vcol);
+        dfl_couple_sort_v2e(N, vrow, vcol, s);
+        x->v2e_row = vrow;
+        x->v2e_col = vcol;
+    }
+    *vrow_out = x->v2e_row;
+    *vcol_out = x->v2e_col;
+}
+
+void DflTetFlagsMatch(u8** flag, index_type T, b32 on) {
+    if (on && !*flag) *flag = (u8*)CdamMallocDevice((ptrdiff_t)(T > 0 ? T : 1));
+    if (!on && *flag) {
+        HIPGUARD(hipStreamSynchronize(DflStream()));
+        CdamFreeDevice(*flag, 0);
+        *flag = NULL;
+    }
 }
 
 void Mesh3DUpdateHost(Mesh3D* m) { Mesh3DDataCopy(m->host, m->device, D2H); }

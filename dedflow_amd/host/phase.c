@@ -1,11 +1,10 @@
 /* Melting and solidification: latent heat and mushy-zone drag (build-defined, opt-in; model in include/dedflow.h, "phase
  * change", kernels in dedflow_amd/csrc/k_phase.hip).  The reference's fluid has one phase.
  *
- * Per mesh, built by DflMeshSetPhaseChange: the configuration, the V2E map of the tets with every list ascending (the
- * summation order of the node pass; the builder of host/scalar.c), the one-byte-per-tet flags (only with DFL_PHASE_FLAGS=1), the
- * nodal D, H and G the assemblies and the statistics use, and the reduction scratch.  The map depends on the connectivity
- * only and the kernels read the node coordinates of the mesh at every call, so nothing here goes stale when the nodes move
- * (DflMeshGeometryChanged).  A coefficient pass is one launch (two with the flags); the assembly hooks add one apply
+ * Per mesh, built by DflMeshSetPhaseChange: the configuration, the one-byte-per-tet flags (only with DFL_PHASE_FLAGS=1), the
+ * nodal D, H and G the assemblies and the statistics use, and the reduction scratch.  The node pass sums in the order of the
+ * mesh's sorted V2E map (DflMeshSortedV2E), which the Set call has the mesh build if nothing did before.  The kernels read
+ * the node coordinates of the mesh at every call, so nothing here goes stale when the nodes move (DflMeshGeometryChanged).  A coefficient pass is one launch (two with the flags); the assembly hooks add one apply
  * launch each.  Nothing is allocated per call and only DflMeshPhaseChangeStats waits for the device.  Without a
  * configuration nothing of this exists and no call path touches it. */
 #include <math.h>
@@ -16,17 +15,10 @@
 #include "dedflow_kernels.h"
 #include "host_private.h"
 
-#define kRHOC (0.5)
-#define kDT (5e-2)
-#define kALPHAM ((3.0 - kRHOC) / (1.0 + kRHOC))
-#define kALPHAF (1.0 / (1.0 + kRHOC))
-#define kGAMMA (0.5 + kALPHAM - kALPHAF)
-
 typedef struct PhaseState {
     DflPhaseChange cfg;
     dfl_phase_params prm;    /* cfg as the kernels take it */
     index_type N, T;
-    index_type *vrow, *vcol; /* device V2E map [N+1], [4T], every list ascending */
     u8* flag;                /* device [T] flags of the last pass (DFL_PHASE_FLAGS=1), NULL: the node pass decides itself */
     f64 *D, *H, *G;          /* device [N] each: D, H of the last assembly hook, G of the last statistics */
     f64 *work, *out;         /* device reduction scratch and the 9 statistics */
@@ -40,8 +32,6 @@ static PhaseState* st_of(const Mesh3D* mesh) {
 void DflPhaseFree(PhaseState* st) {
     if (!st) return;
     HIPGUARD(hipStreamSynchronize(DflStream()));
-    CdamFreeDevice(st->vrow, 0);
-    CdamFreeDevice(st->vcol, 0);
     CdamFreeDevice(st->flag, 0);
     CdamFreeDevice(st->D, 0);
     CdamFreeDevice(st->H, 0);
@@ -93,12 +83,13 @@ void DflMeshSetPhaseChange(Mesh3D* mesh, const DflPhaseChange* cfg) {
     }
     PhaseState* st = x->phase;
     const index_type N = Mesh3DNumNode(mesh), T = Mesh3DNumTet(mesh);
+    const index_type *vrow, *vcol;
+    DflMeshSortedV2E(mesh, &vrow, &vcol); /* built here: no coefficient pass allocates or waits */
     if (!st) {
         st = (PhaseState*)CdamMallocHost(SIZE_OF(PhaseState));
         memset(st, 0, sizeof *st);
         st->N = N;
         st->T = T;
-        DflMeshBuildSortedV2E(mesh, &st->vrow, &st->vcol);
         const ptrdiff_t nb = (ptrdiff_t)(N > 0 ? N : 1) * SIZE_OF(f64);
         st->D = (f64*)CdamMallocDevice(nb);
         st->H = (f64*)CdamMallocDevice(nb);
@@ -114,23 +105,19 @@ void DflMeshSetPhaseChange(Mesh3D* mesh, const DflPhaseChange* cfg) {
     const char* env = getenv("DFL_PHASE_FLAGS");
     /* off unless DFL_PHASE_FLAGS=1: most tets stay (the whole substrate is solid), so the pass in front costs more than it
        saves at bench size ("phase change"); DFL_PHASE_FLAGS=0 is the default spelled out */
-    const b32 flags = env && env[0] == '1';
-    if (flags && !st->flag) st->flag = (u8*)CdamMallocDevice((ptrdiff_t)(T > 0 ? T : 1));
-    if (!flags && st->flag) {
-        HIPGUARD(hipStreamSynchronize(DflStream()));
-        CdamFreeDevice(st->flag, 0);
-        st->flag = NULL;
-    }
+    DflTetFlagsMatch(&st->flag, T, env && env[0] == '1');
     HIPGUARD(hipStreamSynchronize(DflStream()));
 }
 
 b32 DflMeshPhaseChangeEnabled(const Mesh3D* mesh) { return st_of(mesh) != NULL; }
 
-static void coefficients(PhaseState* st, const Mesh3D* mesh, const f64* w, f64* D, f64* H, f64* G) {
+static void coefficients(PhaseState* st, Mesh3D* mesh, const f64* w, f64* D, f64* H, f64* G) {
     const Mesh3DData* dev = Mesh3DDevice(mesh);
     hipStream_t s = DflStream();
+    const index_type *vrow, *vcol;
+    DflMeshSortedV2E(mesh, &vrow, &vcol);
     if (st->flag) dfl_phase_flag_tets(st->T, dev->ien, dev->xg, w, st->N, &st->prm, st->flag, s);
-    dfl_phase_coefficients(st->N, st->vrow, st->vcol, dev->ien, dev->xg, w, &st->prm, st->flag, D, H, G, s);
+    dfl_phase_coefficients(st->N, vrow, vcol, dev->ien, dev->xg, w, &st->prm, st->flag, D, H, G, s);
 }
 
 void DflMeshPhaseCoefficients(Mesh3D* mesh, const f64* w, f64* D, f64* H, f64* G) {

@@ -1,9 +1,9 @@
 /* Scalar transport of the level set phi and the temperature T (include/dedflow.h, "scalar transport").
  *
- * Per mesh, built at the first use after DflMeshSetScalarTransport: the V2E map of the tets with every list ascending (the
- * summation order of the Jacobian kernel, csrc/k_scalar.hip), the nodal pattern, the two CSR matrices over it, one GMRES per
- * field and the [2N] residual the F assemblies leave here (DflScalarCaptureResidual, host/assemble.c).  Without a transport
- * nothing of this exists and no call path touches it. */
+ * Per mesh, built at the first use after DflMeshSetScalarTransport: the nodal pattern, the two CSR matrices over it, one GMRES
+ * per field and the [2N] residual the F assemblies leave here (DflScalarCaptureResidual, host/assemble.c).  Without a
+ * transport nothing of this exists and no call path touches it.  The Jacobian kernel (csrc/k_scalar.hip) sums in the order of
+ * the mesh's sorted V2E map (DflMeshSortedV2E), which belongs to the mesh, not to this state. */
 #include <string.h>
 #include "dedflow.h"
 #include "dedflow_kernels.h"
@@ -13,7 +13,6 @@
 typedef struct ScalarState {
     DflScalarTransport cfg;
     index_type N;
-    index_type *vrow, *vcol; /* device V2E map [N+1], [4T], every list ascending */
     CSRAttr* spy;            /* nodal pattern of the two matrices */
     Matrix *Jphi, *JT;       /* MAT_TYPE_CSR, own values */
     Krylov *ksp_phi, *ksp_T;
@@ -36,8 +35,6 @@ void DflScalarFree(ScalarState* st) {
     if (st->Jphi) MatrixDestroy(st->Jphi);
     if (st->JT) MatrixDestroy(st->JT);
     if (st->spy) CSRAttrDestroy(st->spy);
-    CdamFreeDevice(st->vrow, 0);
-    CdamFreeDevice(st->vcol, 0);
     CdamFreeDevice(st->res, 0);
     CdamFreeDevice(st->F, 0);
     CdamFreeDevice(st->dx, 0);
@@ -104,26 +101,6 @@ void DflScalarCaptureResidual(Mesh3D* mesh, const f64* F) {
     dirichlet_nodes_vec(mesh, st->cfg.dirichlet_T, st->res + N);
 }
 
-/* the V2E map (every list ascending) of a mesh: built once per transport state, or per call without one; the free-surface
- * forces (host/surface.c) build theirs with it too */
-void DflMeshBuildSortedV2E(const Mesh3D* mesh, index_type** vrow_out, index_type** vcol_out) {
-    const Mesh3DData* dev = Mesh3DDevice(mesh);
-    const index_type N = Mesh3DNumNode(mesh), T = Mesh3DNumTet(mesh);
-    hipStream_t s = DflStream();
-    HIPGUARD(hipStreamSynchronize(s));
-    index_type* vrow = (index_type*)CdamMallocDevice(((ptrdiff_t)N + 1) * SIZE_OF(index_type));
-    HIPGUARD(hipStreamSynchronize(s));
-    GenerateV2EMapRowTetGPU(dev->ien, T, N, vrow);
-    index_type vnnz = 0;
-    HIPGUARD(hipMemcpy(&vnnz, vrow + N, sizeof vnnz, D2H));
-    index_type* vcol = (index_type*)CdamMallocDevice((ptrdiff_t)(vnnz > 0 ? vnnz : 1) * SIZE_OF(index_type));
-    HIPGUARD(hipStreamSynchronize(s));
-    GenerateV2EMapColTetGPU(dev->ien, T, N, vrow, vcol);
-    dfl_couple_sort_v2e(N, vrow, vcol, s);
-    *vrow_out = vrow;
-    *vcol_out = vcol;
-}
-
 static f64* csr_own_values(Matrix* A) {
     MatrixCSR* c = (MatrixCSR*)A->data;
     ASSERT(A->type == MAT_TYPE_CSR && !c->owner && "DflAssembleScalarJacobian: a MAT_TYPE_CSR matrix with its own values");
@@ -138,14 +115,8 @@ static void assemble_scalar_jacobian(Mesh3D* mesh, f64* wgalpha, Matrix* Jphi, M
     const Mesh3DData* dev = Mesh3DDevice(mesh);
     const index_type N = Mesh3DNumNode(mesh);
     hipStream_t s = DflStream();
-    index_type *vrow = NULL, *vcol = NULL;
-    if (st) {
-        if (!st->vrow) DflMeshBuildSortedV2E(mesh, &st->vrow, &st->vcol);
-        vrow = st->vrow;
-        vcol = st->vcol;
-    } else {
-        DflMeshBuildSortedV2E(mesh, &vrow, &vcol);
-    }
+    const index_type *vrow, *vcol;
+    DflMeshSortedV2E(mesh, &vrow, &vcol);
     const CSRAttr* ap = Jphi ? ((MatrixCSR*)Jphi->data)->attr : NULL;
     const CSRAttr* at = JT ? ((MatrixCSR*)JT->data)->attr : NULL;
     ASSERT((!ap || (ap->num_row == N && !ap->parent)) && (!at || (at->num_row == N && !at->parent)) &&
@@ -165,10 +136,6 @@ static void assemble_scalar_jacobian(Mesh3D* mesh, f64* wgalpha, Matrix* Jphi, M
     if (st) {
         if (Jphi) dirichlet_nodes_mat(mesh, st->cfg.dirichlet_phi, Jphi);
         if (JT) dirichlet_nodes_mat(mesh, st->cfg.dirichlet_T, JT);
-    } else {
-        HIPGUARD(hipStreamSynchronize(s));
-        CdamFreeDevice(vrow, 0);
-        CdamFreeDevice(vcol, 0);
     }
     DflRangePop();
 }

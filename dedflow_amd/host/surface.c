@@ -1,12 +1,12 @@
 /* Free-surface forces of the melt pool (build-defined, opt-in; model in include/dedflow.h, kernels in
  * dedflow_amd/csrc/k_surface.hip).  The reference's free surface has no physics.
  *
- * Per mesh, built by DflMeshSetSurfaceForces: the configuration, the V2E map of the tets with every list ascending (the
- * summation order of the node pass; the builder of host/scalar.c), the one-byte-per-tet band flags (DFL_SURFACE_FLAGS=0: none),
- * and with in_time_step the two buffers DflTimeStep registers.  The map depends on the connectivity only and the kernels
- * read the node coordinates of the mesh at every call, so nothing here goes stale when the nodes move
- * (DflMeshGeometryChanged).  A DflMeshSurfaceLoad is two launches (one without the flags): it allocates nothing and does not wait
- * for the device.  Without a configuration nothing of this exists and no call path touches it. */
+ * Per mesh, built by DflMeshSetSurfaceForces: the configuration, the one-byte-per-tet band flags (DFL_SURFACE_FLAGS=0: none),
+ * and with in_time_step the two buffers DflTimeStep registers.  The node pass sums in the order of the mesh's sorted V2E map
+ * (DflMeshSortedV2E), which the Set call has the mesh build if nothing did before.  The kernels read the node coordinates of
+ * the mesh at every call, so nothing here goes stale when the nodes move (DflMeshGeometryChanged).  A DflMeshSurfaceLoad is
+ * two launches (one without the flags): it allocates nothing and does not wait for the device.  Without a configuration
+ * nothing of this exists and no call path touches it. */
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -19,7 +19,6 @@ typedef struct SurfaceState {
     DflSurfaceForces cfg;
     dfl_surface_params prm;  /* cfg as the kernels take it */
     index_type N, T;
-    index_type *vrow, *vcol; /* device V2E map [N+1], [4T], every list ascending */
     u8* flag;                /* device [T] band flags of the last call, NULL (DFL_SURFACE_FLAGS=0): the node pass tests the band itself */
     f64 *load, *q_heat;      /* device [3N], [N]: what DflTimeStep registers (in_time_step), else NULL */
 } SurfaceState;
@@ -32,8 +31,6 @@ static SurfaceState* st_of(const Mesh3D* mesh) {
 void DflSurfaceFree(SurfaceState* st) {
     if (!st) return;
     HIPGUARD(hipStreamSynchronize(DflStream()));
-    CdamFreeDevice(st->vrow, 0);
-    CdamFreeDevice(st->vcol, 0);
     CdamFreeDevice(st->flag, 0);
     CdamFreeDevice(st->load, 0);
     CdamFreeDevice(st->q_heat, 0);
@@ -79,12 +76,13 @@ void DflMeshSetSurfaceForces(Mesh3D* mesh, const DflSurfaceForces* cfg) {
     }
     SurfaceState* st = x->surface;
     const index_type N = Mesh3DNumNode(mesh), T = Mesh3DNumTet(mesh);
+    const index_type *vrow, *vcol;
+    DflMeshSortedV2E(mesh, &vrow, &vcol); /* built here: no load call allocates or waits */
     if (!st) {
         st = (SurfaceState*)CdamMallocHost(SIZE_OF(SurfaceState));
         memset(st, 0, sizeof *st);
         st->N = N;
         st->T = T;
-        DflMeshBuildSortedV2E(mesh, &st->vrow, &st->vcol);
         x->surface = st;
     }
     st->cfg = *cfg;
@@ -92,13 +90,7 @@ void DflMeshSetSurfaceForces(Mesh3D* mesh, const DflSurfaceForces* cfg) {
                                     cfg->recoil_a,  cfg->T_boil,    cfg->h_conv, cfg->emissivity, cfg->T_amb, cfg->evap_q0};
     st->prm = prm;
     const char* env = getenv("DFL_SURFACE_FLAGS");
-    const b32 flags = !(env && env[0] == '0'); /* the band pass in front pays at bench size */
-    if (flags && !st->flag) st->flag = (u8*)CdamMallocDevice((ptrdiff_t)(T > 0 ? T : 1));
-    if (!flags && st->flag) {
-        HIPGUARD(hipStreamSynchronize(DflStream()));
-        CdamFreeDevice(st->flag, 0);
-        st->flag = NULL;
-    }
+    DflTetFlagsMatch(&st->flag, T, !(env && env[0] == '0')); /* on: the band pass in front pays at bench size */
     if (cfg->in_time_step && !st->load) {
         st->load = (f64*)CdamMallocDevice((ptrdiff_t)(N > 0 ? N : 1) * 3 * SIZE_OF(f64));
         st->q_heat = (f64*)CdamMallocDevice((ptrdiff_t)(N > 0 ? N : 1) * SIZE_OF(f64));
@@ -116,9 +108,11 @@ void DflMeshSurfaceLoad(Mesh3D* mesh, const f64* w, f64* load, f64* q_heat, f64*
     }
     const Mesh3DData* dev = Mesh3DDevice(mesh);
     hipStream_t s = DflStream();
+    const index_type *vrow, *vcol;
+    DflMeshSortedV2E(mesh, &vrow, &vcol);
     DflRangePush("DflMeshSurfaceLoad");
     if (st->flag) dfl_surface_flag_tets(st->T, dev->ien, dev->xg, w, st->N, &st->prm, st->flag, s);
-    dfl_surface_load(st->N, st->vrow, st->vcol, dev->ien, dev->xg, w, &st->prm, st->flag, load, q_heat, area, s);
+    dfl_surface_load(st->N, vrow, vcol, dev->ien, dev->xg, w, &st->prm, st->flag, load, q_heat, area, s);
     DflRangePop();
 }
 

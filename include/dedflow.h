@@ -767,7 +767,8 @@ typedef struct DflFluidCoupling {
     f64 rho_f, mu_f, gravity[3];
     b32 two_way;
 } DflFluidCoupling;
-/* couple to `mesh` (builds the neighbour table, sorted V2E lists and seed grid once per mesh; resets every particle's tet
+/* couple to `mesh` (builds the neighbour table and seed grid once per mesh, and has the mesh build its sorted V2E lists if
+ * nothing did before: they belong to the mesh and stay with it when the coupling goes; resets every particle's tet
  * to "none", the impulses and the lost count); cfg NULL = defaults; mesh NULL = coupling off (frees its state) */
 void ParticleContextSetFluidCoupling(ParticleContext* ctx, Mesh3D* mesh, const DflFluidCoupling* cfg);
 void ParticleContextLocate(ParticleContext* ctx);
@@ -1260,9 +1261,10 @@ typedef struct DflSurfaceForces {
     f64 h_conv, emissivity, T_amb, evap_q0;   /* each <= 0: that loss is off */
     b32 in_time_step;                         /* DflTimeStep applies load and heat loss itself */
 } DflSurfaceForces;
-/* the configuration is copied; NULL: off, frees everything.  Reported on stderr, mesh unchanged: side not +-1, eps not finite
- * or not positive, any non-finite parameter, T_boil <= 0 while recoil or evaporation is on.  Builds the sorted tet lists of
- * the nodes and every buffer here (synchronises): DflMeshSurfaceLoad allocates nothing and does not wait for the device */
+/* the configuration is copied; NULL: off, frees everything of its own.  Reported on stderr, mesh unchanged: side not +-1, eps not
+ * finite or not positive, any non-finite parameter, T_boil <= 0 while recoil or evaporation is on.  Has the mesh build the
+ * sorted tet lists of the nodes if nothing did before (one copy per mesh, shared with the other features and freed with the
+ * mesh) and builds every buffer here (synchronises): DflMeshSurfaceLoad allocates nothing and does not wait for the device */
 void DflMeshSetSurfaceForces(Mesh3D* mesh, const DflSurfaceForces* cfg);
 b32  DflMeshSurfaceForcesEnabled(const Mesh3D* mesh);
 /* w: device 6N state; load [3N], q_heat [N], area [N] on the device, any of them NULL, every other one overwritten in full.
@@ -1328,9 +1330,10 @@ typedef struct DflPhaseChangeStats {
     int64_t molten;     /* nodes with fl >= 0.5 that are metal */
     f64 lo[3], hi[3];   /* their bounding box */
 } DflPhaseChangeStats;
-/* the configuration is copied; NULL: off, frees everything.  Reported on stderr, mesh unchanged: any non-finite parameter,
- * T_liquidus <= T_solidus, darcy_b <= 0 while drag is on, use_phi with side not +-1 or eps <= 0.  Builds the sorted tet
- * lists of the nodes and every buffer here (synchronises): the later calls allocate nothing and, but for the stats, do not
+/* the configuration is copied; NULL: off, frees everything of its own.  Reported on stderr, mesh unchanged: any non-finite
+ * parameter, T_liquidus <= T_solidus, darcy_b <= 0 while drag is on, use_phi with side not +-1 or eps <= 0.  Has the mesh
+ * build the sorted tet lists of the nodes if nothing did before (shared, freed with the mesh) and builds every buffer here
+ * (synchronises): the later calls allocate nothing and, but for the stats, do not
  * wait for the device */
 void DflMeshSetPhaseChange(Mesh3D* mesh, const DflPhaseChange* cfg);
 b32  DflMeshPhaseChangeEnabled(const Mesh3D* mesh);
