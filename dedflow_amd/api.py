@@ -725,6 +725,13 @@ def _declare(L):
     f("dfl_cgs_update_pc_givens", None, [i32, i32, i32, vp, C.c_int64, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp])
     f("dfl_cgs_update_pc_givens_x4", None, [i32, i32, i32, vp, C.c_int64, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp])
     f("dfl_gmres_trsv", None, [i32, vp, i32, vp, vp])
+    f("dfl_cgs_dots_raw", None, [i32, i32, vp, C.c_int64, vp, vp, vp, vp, vp, vp])
+    f("dfl_cgs_update_jacobi_givens", None, [i32, i32, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp])
+    f("dfl_gmres_scale_inv", None, [i32, vp, vp, vp])
+    f("dfl_bcsr_spmv_x4", None, [i32, i32, i32, vp, vp, vp, f64, vp, vp, vp])
+    f("dfl_bcsr_spmv_x4_scaled", None, [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp])
+    f("dfl_interleave4", None, [i32, i32, i32, vp, vp, vp])
+    f("DflKrylovLastGmresStep", C.c_int, [vp])
     f("dfl_dscal_inv_dev", None, [i32, vp, vp, vp]); f("dfl_dsqrt_dev", None, [vp, vp])
     f("dfl_norms4", None, [i32, vp, vp, C.c_int, vp, vp])
     f("dfl_alpha_states", None, [i32, vp, vp, vp, f64, f64, f64, f64, vp, vp, vp, vp, vp])

@@ -391,6 +391,100 @@ __global__ __launch_bounds__(BLK) void cgs_update_pc_kernel(I nrows, I N, I ncol
     }
 }
 
+// ---- raw (unnormalised) basis, one GPU (GMRES_STEP_RAW_BASIS) ---------------------------------------------------------
+// Column j of the basis holds r_j = nu_j q_j, nu[] the norms.  The coefficients follow from the raw dots g_j = <r_j, w>:
+// h_j = g_j / nu_j goes into H, c_j = h_j / nu_j multiplies r_j in the update.  Same fixed order as cgs_dots_stage2.
+__global__ __launch_bounds__(BLK) void cgs_dots_raw_stage2(int nrb, const T* part, const T* __restrict__ nu, T* d_h, T* d_c) {
+    __shared__ double lds[4];
+    const T* p = part + (long long)blockIdx.x * nrb;
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < nrb; i += BLK) acc += p[i];
+    double r = block_sum_256(acc, lds);
+    if (threadIdx.x == 0) {
+        const double v = nu[blockIdx.x], h = r / v;
+        d_h[blockIdx.x] = h;
+        d_c[blockIdx.x] = h / v;
+    }
+}
+
+// y_j /= nu_j: the triangular-solve result in terms of the raw columns
+__global__ __launch_bounds__(BLK) void scale_inv_vec_kernel(I m, const T* __restrict__ nu, T* __restrict__ y) {
+    const int j = blockIdx.x * BLK + threadIdx.x;
+    if (j < m) y[j] = y[j] / nu[j];
+}
+
+// w -= Q c with ||w||^2 partials, as cgs_update_kernel<true>, and (Z4) the Jacobi application of the NEXT Arnoldi step on the
+// updated w while it is still in registers: z4[node] = M^-1 w'[node], interleaved for dfl_bcsr_spmv_x4.  A workgroup owns the
+// 256 nodes [a, a + 256): 768 u rows at 3a and 256 p rows at 3N + a, 512 double2 slots, two per thread (UPT).  The columns are
+// streamed slot-wise with 16-byte nontemporal loads exactly as cgs_update_kernel streams them; the regrouping to one node per
+// thread goes through LDS ONCE, after the last column (cgs_update_pc_kernel above maps a node to a thread from the start and
+// pays for it with 8-byte column loads).  vec_ok: Q, w 16-byte aligned and ldq even; the p section additionally needs N even.
+template <bool Z4>
+__global__ __launch_bounds__(BLK) void cgs_update_jacobi_kernel(I N, I ncol, const T* __restrict__ Q, long long ldq,
+                                                               const T* __restrict__ d_c, T* __restrict__ w, T* __restrict__ part,
+                                                               const T* __restrict__ dinv33, const T* __restrict__ dinv1,
+                                                               T* __restrict__ z4, int vec_ok) {
+    __shared__ double lds[4];
+    __shared__ double sh[128];
+    __shared__ double2 sm[Z4 ? BLK * UPT : 1];  // the block's updated rows: [0, 768) u, [768, 1024) p
+    for (int j = threadIdx.x; j < ncol && j < 128; j += BLK) sh[j] = d_c[j];
+    __syncthreads();
+    const long long blk = blockIdx.x;
+    const long long a = blk * BLK;
+    const long long nb = (N - a < BLK) ? (N - a) : BLK;  // nodes of this block
+    long long row[UPT], lim[UPT];
+    bool vec[UPT];
+    double2 acc[UPT];
+#pragma unroll
+    for (int i = 0; i < UPT; ++i) {
+        const int slot = threadIdx.x + i * BLK;  // slots [0, 384): u rows, [384, 512): p rows
+        if (slot < 384) { row[i] = 3 * a + 2LL * slot; lim[i] = 3 * (a + nb); }
+        else { row[i] = 3LL * N + a + 2LL * (slot - 384); lim[i] = 3LL * N + a + nb; }
+        vec[i] = vec_ok && row[i] + 1 < lim[i] && !(row[i] & 1);
+        if (vec[i]) acc[i] = *reinterpret_cast<const double2*>(w + row[i]);
+        else { acc[i].x = (row[i] < lim[i]) ? w[row[i]] : 0.0; acc[i].y = (row[i] + 1 < lim[i]) ? w[row[i] + 1] : 0.0; }
+    }
+#pragma unroll 4
+    for (int j = 0; j < ncol; ++j) {
+        const double h = (j < 128) ? sh[j] : d_c[j];
+        const T* q = Q + (long long)j * ldq;
+#pragma unroll
+        for (int i = 0; i < UPT; ++i) {
+            double2 qv;
+            if (vec[i]) qv = ld_stream(q + row[i]);
+            else { qv.x = (row[i] < lim[i]) ? q[row[i]] : 0.0; qv.y = (row[i] + 1 < lim[i]) ? q[row[i] + 1] : 0.0; }
+            acc[i].x -= qv.x * h; acc[i].y -= qv.y * h;
+        }
+    }
+    double ss = 0.0;
+#pragma unroll
+    for (int i = 0; i < UPT; ++i) {
+        if (vec[i]) *reinterpret_cast<double2*>(w + row[i]) = acc[i];
+        else {
+            if (row[i] < lim[i]) w[row[i]] = acc[i].x;
+            if (row[i] + 1 < lim[i]) w[row[i] + 1] = acc[i].y;
+        }
+        ss += acc[i].x * acc[i].x + acc[i].y * acc[i].y;
+        if (Z4) sm[threadIdx.x + i * BLK] = acc[i];
+    }
+    const double r = block_sum_256(ss, lds);  // (its barriers also publish sm)
+    if (threadIdx.x == 0) part[blk] = r;
+    if (Z4) {
+        const double* s = reinterpret_cast<const double*>(sm);
+        const int t = threadIdx.x;
+        if (t < nb) {
+            const long long i = a + t;
+            const T* A = dinv33 + i * 9;  // column-major image, as pc_apply_kernel (Q7)
+            const double x0 = s[3 * t], x1 = s[3 * t + 1], x2 = s[3 * t + 2], xp = s[768 + t];
+            const double y0 = A[0] * x0 + A[3] * x1 + A[6] * x2, y1 = A[1] * x0 + A[4] * x1 + A[7] * x2;
+            const double y2 = A[2] * x0 + A[5] * x1 + A[8] * x2, yp = xp * dinv1[i];
+            double2* o = reinterpret_cast<double2*>(z4 + 4 * i);
+            o[0] = make_double2(y0, y1);
+            o[1] = make_double2(y2, yp);
+        }
+    }
+}
+
 // H[0:m,0:m] y = beta by back substitution (cublasDtrsv, krylov.c:297-301), one workgroup: column-oriented so that every
 // step is one coalesced column update (a single thread walking rows pays a dependent global load per entry: 85 us at m = 40)
 template <bool STAGED>
@@ -670,6 +764,29 @@ void dfl_cgs_update_givens(I n, I ncol, const T* Q, int64_t ldq, const T* d_h, T
     int g = ceil_div(n, UROWS);
     cgs_update_kernel<true><<<g, BLK, 0, S(stream)>>>(n, ncol, Q, ldq, d_h, w, work);
     norm_givens_kernel<<<1, BLK, 0, S(stream)>>>(g, work, d_nrm, iter, d_H, ldh, d_gv, d_beta, d_res_hist);
+    DFL_LAUNCH_CHECK();
+}
+void dfl_cgs_dots_raw(I n, I ncol, const T* Q, int64_t ldq, const T* w, const T* d_nu, T* d_h, T* d_c, T* work, void* stream) {
+    if (ncol <= 0) return;
+    int nrb = ceil_div(n, ROWS_PER_BLOCK);
+    dim3 grid(nrb, ceil_div(ncol, CT));
+    cgs_dots_stage1<<<grid, BLK, 0, S(stream)>>>(n, ncol, Q, ldq, w, work, nrb, CT);
+    cgs_dots_raw_stage2<<<ncol, BLK, 0, S(stream)>>>(nrb, work, d_nu, d_h, d_c);
+    DFL_LAUNCH_CHECK();
+}
+void dfl_cgs_update_jacobi_givens(I N, I ncol, const T* Q, int64_t ldq, const T* d_c, T* w, const T* dinv33, const T* dinv1, T* z4,
+                                  T* d_nrm, T* work, I iter, T* d_H, I ldh, T* d_gv, T* d_beta, T* d_res_hist, void* stream) {
+    if (N <= 0) return;
+    const int g = ceil_div(N, BLK);
+    const int vec_ok = aligned16(Q) && aligned16(w) && !(ldq & 1);
+    if (z4) cgs_update_jacobi_kernel<true><<<g, BLK, 0, S(stream)>>>(N, ncol, Q, ldq, d_c, w, work, dinv33, dinv1, z4, vec_ok);
+    else cgs_update_jacobi_kernel<false><<<g, BLK, 0, S(stream)>>>(N, ncol, Q, ldq, d_c, w, work, nullptr, nullptr, nullptr, vec_ok);
+    norm_givens_kernel<<<1, BLK, 0, S(stream)>>>(g, work, d_nrm, iter, d_H, ldh, d_gv, d_beta, d_res_hist);
+    DFL_LAUNCH_CHECK();
+}
+void dfl_gmres_scale_inv(I m, const T* d_nu, T* d_y, void* stream) {
+    if (m <= 0) return;
+    scale_inv_vec_kernel<<<ceil_div(m, BLK), BLK, 0, S(stream)>>>(m, d_nu, d_y);
     DFL_LAUNCH_CHECK();
 }
 void dfl_spin_us(int us, void* stream) {

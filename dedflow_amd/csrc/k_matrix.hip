@@ -34,10 +34,12 @@ __global__ __launch_bounds__(BLK) void interleave4_kernel(I node0, I node1, I N,
     o[1] = make_double2(x[3 * i + 2], x[3LL * N + i]);
 }
 // The U column indices of a trip come with ONE load per row group (lane l fetches ci[k + l % U]) and are passed round with
-// shuffles, instead of U broadcast loads
+// shuffles, instead of U broadcast loads.  DSCALE: y = tot * (1.0 / *d_nrm) instead of alpha * tot -- the raw-basis GMRES step
+// folds the normalisation of the Krylov column into the matvec that consumes M^-1 of it (host/gmres.c)
+template <bool DSCALE>
 __global__ __launch_bounds__(BLK) void bcsr_spmv_x4_kernel(I row0, I nrows, I N, const I* __restrict__ rp, const I* __restrict__ ci,
                                                           const T* __restrict__ val, T alpha, const T* __restrict__ x4,
-                                                          T* __restrict__ y) {
+                                                          T* __restrict__ y, const T* __restrict__ d_nrm) {
     constexpr int U = 4;  // nodal nonzeros per loop trip
     long long blk = blockIdx.x;
     const long long per = gridDim.x >> 3;  // grid is a multiple of 8
@@ -79,7 +81,11 @@ __global__ __launch_bounds__(BLK) void bcsr_spmv_x4_kernel(I row0, I nrows, I N,
 #pragma unroll
     for (int u = 1; u < U; ++u) tot += acc[u];
     tot += __shfl_xor(tot, 1, WAVE);
-    if (!hi) y[xidx(row, r, N3)] = alpha * tot;
+    if (DSCALE) {
+        if (!hi) y[xidx(row, r, N3)] = tot * (1.0 / d_nrm[0]);
+    } else {
+        if (!hi) y[xidx(row, r, N3)] = alpha * tot;
+    }
 }
 
 // ---- single-precision COPY of the block values (PC_TWOLEVEL only: its smoother and its residual matvec read it; the Krylov
@@ -706,7 +712,15 @@ void dfl_bcsr_spmv_x4(I row0, I row1, I N, const I* rp, const I* ci, const T* va
     const int grid = ceil_div((long long)(row1 - row0) * 8, BLK);
     const int grid8 = (grid + 7) & ~7;
     // (column indices by one cooperative load per row group and trip: 0.4990 against 0.5027 ms back to back)
-    bcsr_spmv_x4_kernel<<<grid8, BLK, 0, S(stream)>>>(row0, row1, N, rp, ci, val, alpha, x4, y);
+    bcsr_spmv_x4_kernel<false><<<grid8, BLK, 0, S(stream)>>>(row0, row1, N, rp, ci, val, alpha, x4, y, nullptr);
+    DFL_LAUNCH_CHECK();
+}
+void dfl_bcsr_spmv_x4_scaled(I row0, I row1, I N, const I* rp, const I* ci, const T* val, const T* d_nrm, const T* x4, T* y,
+                             void* stream) {
+    if (row1 <= row0) return;
+    const int grid = ceil_div((long long)(row1 - row0) * 8, BLK);
+    const int grid8 = (grid + 7) & ~7;
+    bcsr_spmv_x4_kernel<true><<<grid8, BLK, 0, S(stream)>>>(row0, row1, N, rp, ci, val, 1.0, x4, y, d_nrm);
     DFL_LAUNCH_CHECK();
 }
 void dfl_bcsr_values_to_f32(int64_t n, const T* val, float* valf, void* stream) {

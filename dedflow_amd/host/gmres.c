@@ -4,7 +4,9 @@
  * Restates GMRESSolvePrivate (src/krylov.c:56-334): right-preconditioned full GMRES, classical Gram-Schmidt, Givens
  * rotations, residual recurrence, convergence test every 20 iterations.  Differences in mechanism only:
  *   - the two cublasDgemv + Dnrm2 + Dscal of an Arnoldi step are two fused passes (dfl_cgs_dots / dfl_cgs_update) and the
- *     normalisation is folded into the next preconditioner application;
+ *     normalisation is folded into the next preconditioner application -- or, one GPU with the Jacobi tree, never done:
+ *     the basis stays unnormalised, the update applies M^-1 to the column it forms and the matvec divides by the norm
+ *     (GMRES_STEP_RAW_BASIS);
  *   - every scalar recurrence stays on the device; the host reads 8 bytes only when the reference tests convergence (every
  *     20th iteration) -- the reference syncs 2-3 times per iteration;
  *   - work space is cached in the Krylov object instead of malloc+memset per solve;
@@ -172,8 +174,9 @@ void DflPcApplyFused(PC* pc, index_type na, f64* w, const f64* d_nrm, f64* z) { 
 /* ============================== the plan of a solve ======================================= */
 /* Environment switches of the GMRES paths, read here and nowhere else.  Cached for the process: DFL_SPMV_X4=0 (the
    reference-layout gathers, A/B), DFL_SPMV_X4_MIN (smallest matrix, in nodes, that takes the interleaved path; tests set 1).
-   Read at every solve (A/B): eager host reads, boundary rows on the library stream, three launches per fused-norm step */
-typedef struct GmresEnv { b32 x4; index_type x4_min; b32 eager_sync, no_side_rows, no_fused_update_pc; } GmresEnv;
+   Read at every solve (A/B): eager host reads, boundary rows on the library stream, three launches per fused-norm step,
+   DFL_GMRES_RAW_BASIS=0 (one GPU: the normalised basis and the separate Jacobi pass instead of GMRES_STEP_RAW_BASIS) */
+typedef struct GmresEnv { b32 x4; index_type x4_min; b32 eager_sync, no_side_rows, no_fused_update_pc, raw_basis; } GmresEnv;
 static GmresEnv gmres_env(void) {
     static int x4 = -1, x4_min = 4096;
     if (x4 < 0) {
@@ -181,8 +184,9 @@ static GmresEnv gmres_env(void) {
         if (min) x4_min = atoi(min);
         x4 = !(off && atoi(off) == 0);
     }
+    const char* raw = getenv("DFL_GMRES_RAW_BASIS");
     const GmresEnv e = {x4, x4_min, getenv("DFL_KRYLOV_EAGER_SYNC") != NULL, getenv("DFL_NO_SIDE_BOUNDARY_ROWS") != NULL,
-                        getenv("DFL_NO_FUSED_UPDATE_PC") != NULL};
+                        getenv("DFL_NO_FUSED_UPDATE_PC") != NULL, !(raw && atoi(raw) == 0)};
     return e;
 }
 
@@ -230,6 +234,11 @@ void DflGmresPlanFill(GmresPlan* p, const KrylovExt* ex, index_type max_iter, Ma
     /* with the Jacobi tree on 4N-vectors nothing reads z in the reference layout (tmp is rewritten before its next use): the
        kernel then stores the interleaved copy only -- 32 B per node and iteration less to write.  FGMRES keeps every z */
     p->x4_skip_z = p->x4 == GMRES_X4_SINGLE && tree_4n && p->N == p->x4_N && !p->Zb;
+    /* one GPU, Jacobi tree, interleaved matvec input: the basis stays unnormalised (column k = r_k, nrm[k] = ||r_k||), the update
+       kernel applies M^-1 to the column it has just formed and the matvec divides by nrm[k] -- the separate Jacobi pass, which
+       read the new column back only to scale it, is gone (csrc/k_blas.hip, cgs_update_jacobi_kernel).  Restarts, lazy or eager
+       reads and the check interval have no say here: the arithmetic of a solve does not depend on them */
+    if (p->step == GMRES_STEP_REFERENCE && p->x4_skip_z && p->rows == p->N && env.raw_basis) p->step = GMRES_STEP_RAW_BASIS;
 }
 
 /* ============================== operator, residual, Arnoldi step =========================== */
@@ -239,12 +248,20 @@ static void matvec_rows(const GmresPlan* p, Matrix* A, f64* z, f64* y, index_typ
 }
 
 /* z = M^-1 (q / *d_nrm) (d_nrm == NULL: q as it is); halo of z; y = A z  (owned rows).  q is left normalised.  z_ready: `z`
-   already holds M^-1 q, written by the fused step (GMRES_STEP_FUSED_UPDATE_PC) */
+   already holds M^-1 q, written by the fused step (GMRES_STEP_FUSED_UPDATE_PC; GMRES_STEP_RAW_BASIS: the interleaved copy
+   holds M^-1 of the raw column) */
 static void gmres_apply_operator(const GmresPlan* p, KrylovExt* ex, Matrix* A, PC* pc, f64* q, const f64* d_nrm, f64* z, b32 z_ready,
                                  f64* y) {
     const DflComm* c = &ex->comm;
     hipStream_t s = DflStream();
     b32 wrote = FALSE;
+    if (p->step == GMRES_STEP_RAW_BASIS) {
+        /* q = r_k is left as it is; z4 = M^-1 r_k (column 0: made here; later columns: the update kernel has left it),
+           y = (A z4) / nrm[k] */
+        if (!z_ready) DFL_TIMED(DFL_TAG_PC, (void)DflPcApplyFusedX4(pc, p->na, q, NULL, NULL, p->z4));
+        DFL_TIMED(DFL_TAG_SPMV, DflMatrixFSMatVecX4RangeScaled(A, p->z4, d_nrm, y, 0, p->x4_N));
+        return;
+    }
     if (p->x4 == GMRES_X4_SINGLE) {
         /* one GPU: one 16-byte load per lane and nonzero instead of two 8-byte loads (0.50 against 0.57 ms at 10M tets); the
            Jacobi tree writes the interleaved copy from registers, any other preconditioner is followed by one interleave pass */
@@ -307,8 +324,9 @@ static void gmres_initial_residual(const GmresPlan* p, KrylovExt* ex, Matrix* A,
 }
 
 /* Classical Gram-Schmidt of w = Q[:,iter+1] against Q[:,0..iter], then the Givens rotations and the residual recurrence, all on
-   the device: column iter of H, beta[iter+1], res_hist[iter]; nrm[iter+1] = the norm Q[:,iter+1] still has to be divided by */
-static void gmres_orthogonalise(const GmresPlan* p, KrylovExt* ex, index_type iter, f64* res_hist) {
+   the device: column iter of H, beta[iter+1], res_hist[iter]; nrm[iter+1] = the norm Q[:,iter+1] still has to be divided by.
+   last: no Arnoldi step follows in this cycle (the raw-basis step then leaves out M^-1 of the new column) */
+static void gmres_orthogonalise(const GmresPlan* p, KrylovExt* ex, index_type iter, f64* res_hist, b32 last) {
     const index_type na = p->na, ldh = p->ldh;
     const DflComm* c = &ex->comm;
     hipStream_t s = DflStream();
@@ -336,6 +354,13 @@ static void gmres_orthogonalise(const GmresPlan* p, KrylovExt* ex, index_type it
         c->allreduce_sum(c->ctx, nrm, 1);
         dfl_gmres_givens_sq(iter, nrm, H, ldh, ex->gv, ex->beta, res_hist, s);
         break;
+    case GMRES_STEP_RAW_BASIS:
+        /* columns 0..iter are r_j = nrm[j] q_j: h_j = <r_j, w> / nrm[j] into H, hraw[j] = h_j / nrm[j] multiplies r_j */
+        DFL_TIMED(DFL_TAG_CGS_DOTS, dfl_cgs_dots_raw(na, iter + 1, Q, na, w, ex->nrm, h, ex->hraw, ex->work, s));
+        DFL_TIMED(DFL_TAG_CGS_UPDATE, dfl_cgs_update_jacobi_givens(p->N, iter + 1, Q, na, ex->hraw, w, p->d33, p->d1,
+                                                                   last ? NULL : p->z4, nrm, ex->work, iter, H, ldh, ex->gv,
+                                                                   ex->beta, res_hist, s));
+        break;
     case GMRES_STEP_REFERENCE:
         DFL_TIMED(DFL_TAG_CGS_DOTS, dfl_cgs_dots(na, iter + 1, Q, na, w, h, ex->work, s));
         DFL_TIMED(DFL_TAG_CGS_UPDATE, dfl_cgs_update_givens(na, iter + 1, Q, na, h, w, nrm, ex->work, iter, H, ldh, ex->gv, ex->beta,
@@ -345,11 +370,12 @@ static void gmres_orthogonalise(const GmresPlan* p, KrylovExt* ex, index_type it
 }
 
 /* H y = beta, x += M^-1 (Q[:,0:iter] y)   (FGMRES: x += Z[:,0:iter] y).  Column `iter` of the basis may still be
-   un-normalised, but it is not used; columns < iter are normalised */
+   un-normalised, but it is not used; columns < iter are normalised (raw basis: none is, y_j is divided by nrm[j] instead) */
 static void gmres_update_solution(const GmresPlan* p, KrylovExt* ex, PC* pc, index_type iter, f64* x) {
     hipStream_t s = DflStream();
     f64* const tmp = ex->tmp;
     dfl_gmres_trsv(iter, ex->H, p->ldh, ex->beta, s);
+    if (p->step == GMRES_STEP_RAW_BASIS) dfl_gmres_scale_inv(iter, ex->nrm, ex->beta, s);
     dfl_gemv_n(p->na, iter, p->Zb ? p->Zb : ex->Q, p->na, ex->beta, tmp, s);
     if (p->Zb) { dfl_daxpy(p->na, 1.0, tmp, x, s); return; }
     DflPcApplyFused(pc, p->na, tmp, NULL, tmp + p->n);
@@ -515,6 +541,7 @@ static b32 gmres_run(Matrix* A, f64* x, f64* b, Krylov* ksp, b32 force_probe) {
     if (ex->flexible && !ex->Z) ex->Z = ws_vec_malloc((ptrdiff_t)n * m);
     GmresPlan p;
     DflGmresPlanFill(&p, ex, maxit, A, pc, na, FALSE);
+    ex->last_step = (int)p.step;
     f64 *const Q = ex->Q, *const tmp = ex->tmp;
     b32 converged = FALSE;
     index_type total = 0; /* iterations over all cycles */
@@ -535,9 +562,10 @@ static b32 gmres_run(Matrix* A, f64* x, f64* b, Krylov* ksp, b32 force_probe) {
         while (!converged && iter < m && total < maxit) {
             /* 2.0 z = inv(P) Q[:,iter] (FGMRES keeps every z; the fused step has left it in tmp)   2.2 Q[:,iter+1] = A z */
             gmres_apply_operator(&p, ex, A, pc, COL(Q, iter), ex->nrm + iter, p.Zb ? COL(p.Zb, iter) : tmp,
-                                 iter > 0 && p.step == GMRES_STEP_FUSED_UPDATE_PC, COL(Q, iter + 1));
+                                 iter > 0 && (p.step == GMRES_STEP_FUSED_UPDATE_PC || p.step == GMRES_STEP_RAW_BASIS),
+                                 COL(Q, iter + 1));
             /* 3. classical Gram-Schmidt   4. Givens rotations + residual recurrence */
-            gmres_orthogonalise(&p, ex, iter, res_hist);
+            gmres_orthogonalise(&p, ex, iter, res_hist, iter + 1 >= m || total + 1 >= maxit);
             if (hr.pend) {
                 /* the check enqueued behind the PREVIOUS iteration: the device has the iteration just enqueued to work on
                    while the host waits for the 8 (+ 40) bytes */
@@ -674,6 +702,11 @@ void GMRESSolvePrivate(Matrix* A, f64* x, f64* b, void* ctx) {
         ASSERT(!again);
         UNUSED(again);
     }
+}
+
+/* which Arnoldi step (GmresStep, solver_private.h) the most recent unpipelined GMRES solve of this solver ran; -1: none yet */
+int DflKrylovLastGmresStep(Krylov* ksp) {
+    return (ksp && ksp->ksp_solve == GMRESSolvePrivate && kext(ksp)) ? kext(ksp)->last_step : -1;
 }
 
 /* the GMRES work space for this matrix as the next KrylovSolve would size it (host/ws_placement.c calibrates it ahead of

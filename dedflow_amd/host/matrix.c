@@ -453,6 +453,14 @@ void DflMatrixFSMatVecX4Range(Matrix* m, const value_type* x4, value_type* y, in
     dfl_bcsr_spmv_x4(row0, row1, fs->spy1x1->num_row, fs->spy1x1->row_ptr, fs->spy1x1->col_ind, fs->block_val, 1.0, x4, y,
                      DflStream());
 }
+/* y = (A x4) * (1 / *d_nrm), the scale read on the device (the raw-basis GMRES step) */
+void DflMatrixFSMatVecX4RangeScaled(Matrix* m, const value_type* x4, const value_type* d_nrm, value_type* y, index_type row0,
+                                    index_type row1) {
+    MatrixFS* fs = fs_of(m);
+    ASSERT(fs->block_mode && "the interleaved matvec needs the block-mode (u,p) matrix");
+    dfl_bcsr_spmv_x4_scaled(row0, row1, fs->spy1x1->num_row, fs->spy1x1->row_ptr, fs->spy1x1->col_ind, fs->block_val, d_nrm, x4, y,
+                            DflStream());
+}
 void MatrixFSMatVecRange(Matrix* m, value_type* x, value_type* y, index_type row0, index_type row1) {
     MatrixFS* fs = fs_of(m);
     ASSERT(fs->block_mode && "MatrixFSMatVecRange needs the block-mode (u,p) matrix");

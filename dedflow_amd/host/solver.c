@@ -203,6 +203,7 @@ static Krylov* krylov_init(index_type max_iter, f64 atol, f64 rtol, void* handle
     memset(x, 0, sizeof *x);
     x->check_interval = 20; /* krylov.c:281 */
     x->verbose = TRUE;
+    x->last_step = -1;
     ksp->ext = x;
     return ksp;
 }

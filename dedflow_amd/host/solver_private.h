@@ -41,6 +41,7 @@ typedef struct KrylovExt {
     hipEvent_t ev_w, ev_h;
     b32 no_calibration; /* inner / coarse solvers of PC_TWOLEVEL: never time basis placements (DflKrylovMarkInner) */
     char* amgx_cfg;     /* KrylovSetAMGXConfig: options of PCCreateAMGX (NULL: the reference configuration) */
+    int last_step;      /* GmresStep of the most recent gmres_run (DflKrylovLastGmresStep), -1 before the first */
 } KrylovExt;
 
 static inline KrylovExt* kext(const Krylov* k) { return (KrylovExt*)k->ext; }
@@ -51,7 +52,9 @@ typedef enum {
     GMRES_STEP_REFERENCE,      /* one GPU: dots, then update + norm + Givens in one launch (dfl_cgs_update_givens) */
     GMRES_STEP_TWO_REDUCTIONS, /* partitioned: all-reduce of h, update, all-reduce of the norm, dfl_givens_sq */
     GMRES_STEP_FUSED_NORM,     /* KrylovSetFusedNorm: ||w - Qh|| from w.w - sum h^2, one reduction (dfl_gmres_givens_pythagoras) */
-    GMRES_STEP_FUSED_UPDATE_PC /* ... with update, Givens and the next M^-1 in one launch (dfl_cgs_update_pc_givens_x4) */
+    GMRES_STEP_FUSED_UPDATE_PC, /* ... with update, Givens and the next M^-1 in one launch (dfl_cgs_update_pc_givens_x4) */
+    GMRES_STEP_RAW_BASIS       /* one GPU, Jacobi tree, x4: unnormalised basis, raw dots (dfl_cgs_dots_raw), the next M^-1 inside
+                                  the update (dfl_cgs_update_jacobi_givens), the normalisation inside the matvec */
 } GmresStep;
 typedef struct GmresPlan {
     index_type n, na, m, ldh, maxit; /* rows, active length, basis columns per cycle, leading dimension of H, iteration cap */

@@ -54,6 +54,7 @@ typedef struct Loop {
     PC* pc;
     index_type na, m; /* active length = column stride of the basis block; basis columns per cycle */
     index_type x4; /* > 0: the solver's matvec gathers from the interleaved copy (nodes of the unpartitioned block matrix) */
+    b32 raw;       /* ... and divides its output by the column's norm (GMRES_STEP_RAW_BASIS) */
     hipEvent_t a, b;
 } Loop;
 
@@ -64,6 +65,7 @@ static void loop_open(Loop* L, KrylovExt* ex, Matrix* A, PC* pc, index_type max_
     /* (partitioned solvers gather from the interleaved copy too -- owned rows, ghost columns filled behind the unpack; the
        timing loop fills the ghost part from tmp, whatever it holds: placement, not values, is what is measured) */
     L->x4 = plan.x4 != GMRES_X4_NONE ? plan.x4_N : 0;
+    L->raw = plan.step == GMRES_STEP_RAW_BASIS;
     HIPGUARD(hipEventCreate(&L->a));
     HIPGUARD(hipEventCreate(&L->b));
     const f64 one = 1.0;
@@ -92,10 +94,12 @@ static float time_block(const Loop* L, f64* Qk) {
         /* as the solver does it: the interleaved copy in the spare column of THIS block, written by the PC kernel */
         f64* const z4 = L->x4 ? Qk + (size_t)(m + 1) * (size_t)na : NULL;
         const index_type owned = MatrixFSOwnedRows(L->A);
-        if (!DflPcApplyFusedX4(L->pc, na, w, ex->nrm, ex->tmp, z4) && z4) dfl_interleave4(0, owned, L->x4, ex->tmp, z4, s);
+        if (L->raw) (void)DflPcApplyFusedX4(L->pc, na, w, NULL, NULL, z4); /* the raw column's M^-1, interleaved copy only */
+        else if (!DflPcApplyFusedX4(L->pc, na, w, ex->nrm, ex->tmp, z4) && z4) dfl_interleave4(0, owned, L->x4, ex->tmp, z4, s);
         if (z4 && owned < L->x4) dfl_interleave4(owned, L->x4, L->x4, ex->tmp, z4, s);
         HIPGUARD(hipEventRecord(L->a, s));
-        if (z4) DflMatrixFSMatVecX4Range(L->A, z4, y, 0, owned);
+        if (L->raw) DflMatrixFSMatVecX4RangeScaled(L->A, z4, ex->nrm, y, 0, owned); /* nrm[0] = 1 (loop_open) */
+        else if (z4) DflMatrixFSMatVecX4Range(L->A, z4, y, 0, owned);
         else MatrixMatVec(L->A, ex->tmp, y);
         HIPGUARD(hipEventRecord(L->b, s));
         HIPGUARD(hipEventSynchronize(L->b));

@@ -295,6 +295,9 @@ void MatrixMatVec(Matrix* matrix, value_type* x, value_type* y);
  * writes both layouts, e.g. dfl_pc_jacobi_apply_scaled_rows_x4) */
 value_type* DflMatrixFSInterleavedScratch(Matrix* matrix);
 void DflMatrixFSMatVecX4Range(Matrix* matrix, const value_type* x4, value_type* y, index_type row0, index_type row1);
+/* ... with the output divided by the device scalar *d_nrm: y = (A x4) * (1 / *d_nrm) */
+void DflMatrixFSMatVecX4RangeScaled(Matrix* matrix, const value_type* x4, const value_type* d_nrm, value_type* y, index_type row0,
+                                    index_type row1);
 void MatrixMatVecWithMask(Matrix* matrix, value_type* x, value_type* y, value_type* left_mask, value_type* right_mask);
 void MatrixGetDiag(Matrix* matrix, value_type* diag, index_type bs);
 void MatrixSetValuesCOO(Matrix* matrix, value_type alpha, index_type n, const index_type* row, const index_type* col,
@@ -495,6 +498,9 @@ void KrylovSetFusedNorm(Krylov* krylov, b32 on);
  * residual history (~1e-8 r0 instead of 1e-10; heavy cancellation raises KrylovStats.fused_norm_cancelled).  Ignored with
  * FGMRES / PC_TWOLEVEL and with restarts. */
 void KrylovSetPipelined(Krylov* krylov, b32 on);
+/* which Arnoldi step the most recent unpipelined GMRES solve ran (0 reference, 1 two reductions, 2 fused norm, 3 fused update +
+ * preconditioner, 4 raw basis: DESIGN.md section 3); -1 before the first solve or for another solver.  For tests and A/B runs */
+int DflKrylovLastGmresStep(Krylov* krylov);
 /* A non-blocking stream (default priority) that was PROBED to run concurrently with `main_stream`: HIP maps streams onto a few
  * hardware queues round-robin, and a side stream on the main stream's own queue runs behind it instead of beside it; a
  * highest-priority stream avoids that but was seen to delay every kernel of the normal-priority stream (host/comm_rccl.c).

@@ -94,6 +94,20 @@ void dfl_cgs_update(dfl_index n, dfl_index ncol, const dfl_value* Q, int64_t ldq
 void dfl_cgs_update_givens(dfl_index n, dfl_index ncol, const dfl_value* Q, int64_t ldq, const dfl_value* d_h, dfl_value* w,
                            dfl_value* d_nrm, dfl_value* work, dfl_index iter, dfl_value* d_H, dfl_index ldh, dfl_value* d_gv,
                            dfl_value* d_beta, dfl_value* d_res_hist, void* stream);
+/* Raw (unnormalised) basis on one GPU: column j of Q holds r_j = nu_j q_j, d_nu[j] = ||r_j||.
+ * dfl_cgs_dots_raw: g_j = Q[:,j].w, then d_h[j] = g_j / nu_j (the entry of H) and d_c[j] = d_h[j] / nu_j (the coefficient of
+ *   the raw column in the update); same partial sums and summation order as dfl_cgs_dots.
+ * dfl_cgs_update_jacobi_givens: vectors of 4N rows ([u AoS | p]); w -= Q d_c, *d_nrm = ||w||, the Givens step of column
+ *   `iter` (as dfl_cgs_update_givens), and -- z4 != NULL -- z4[node][4] = M^-1 w for the block-Jacobi tree (dinv33, dinv1:
+ *   dfl_pc_jacobi_setup), written from the update's registers for dfl_bcsr_spmv_x4_scaled.  work: dfl_cgs_work_size(4N, ncol).
+ * dfl_gmres_scale_inv: d_y[j] /= d_nu[j], j < m (the triangular-solve result in terms of the raw columns). */
+void dfl_cgs_dots_raw(dfl_index n, dfl_index ncol, const dfl_value* Q, int64_t ldq, const dfl_value* w, const dfl_value* d_nu,
+                      dfl_value* d_h, dfl_value* d_c, dfl_value* work, void* stream);
+void dfl_cgs_update_jacobi_givens(dfl_index N, dfl_index ncol, const dfl_value* Q, int64_t ldq, const dfl_value* d_c, dfl_value* w,
+                                  const dfl_value* dinv33, const dfl_value* dinv1, dfl_value* z4, dfl_value* d_nrm, dfl_value* work,
+                                  dfl_index iter, dfl_value* d_H, dfl_index ldh, dfl_value* d_gv, dfl_value* d_beta,
+                                  dfl_value* d_res_hist, void* stream);
+void dfl_gmres_scale_inv(dfl_index m, const dfl_value* d_nu, dfl_value* d_y, void* stream);
 void dfl_dsqrt_dev(dfl_value* d_val, void* stream); /* *d_val = sqrt(*d_val) */
 /* y = Q[:,0:ncol] c  (cublasDgemv OP_N of krylov.c:304-311) */
 void dfl_gemv_n(dfl_index n, dfl_index ncol, const dfl_value* Q, int64_t ldq, const dfl_value* d_c, dfl_value* y, void* stream);
@@ -394,6 +408,9 @@ void dfl_pc_jacobi_apply_scaled_rows_x4(dfl_index nrows, dfl_index N, dfl_index 
 void dfl_interleave4(dfl_index node0, dfl_index node1, dfl_index N, const dfl_value* x, dfl_value* x4, void* stream);
 void dfl_bcsr_spmv_x4(dfl_index row0, dfl_index row1, dfl_index N, const dfl_index* row_ptr, const dfl_index* col_ind,
                       const dfl_value* val, dfl_value alpha, const dfl_value* x4, dfl_value* y, void* stream);
+/* the same with the output scaled by a device scalar: y = (A x4) * (1.0 / *d_nrm) */
+void dfl_bcsr_spmv_x4_scaled(dfl_index row0, dfl_index row1, dfl_index N, const dfl_index* row_ptr, const dfl_index* col_ind,
+                             const dfl_value* val, const dfl_value* d_nrm, const dfl_value* x4, dfl_value* y, void* stream);
 /* single-precision copy of block values (n = nnz1 * 16 entries) and the matvec / DILU sweeps reading it: PC_TWOLEVEL's
  * smoother and residual matvec (a preconditioner under FGMRES may be inexact; everything outside it stays double) */
 void dfl_bcsr_values_to_f32(int64_t n, const dfl_value* val, float* valf, void* stream);
