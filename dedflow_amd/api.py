@@ -732,6 +732,7 @@ def _declare(L):
     f("dfl_bcsr_spmv_x4_scaled", None, [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp])
     f("dfl_interleave4", None, [i32, i32, i32, vp, vp, vp])
     f("DflKrylovLastGmresStep", C.c_int, [vp])
+    f("DflKrylovLastGmresPairs", None, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)])
     f("dfl_dscal_inv_dev", None, [i32, vp, vp, vp]); f("dfl_dsqrt_dev", None, [vp, vp])
     f("dfl_norms4", None, [i32, vp, vp, C.c_int, vp, vp])
     f("dfl_alpha_states", None, [i32, vp, vp, vp, f64, f64, f64, f64, vp, vp, vp, vp, vp])

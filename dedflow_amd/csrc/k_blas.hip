@@ -309,8 +309,10 @@ __global__ __launch_bounds__(BLK) void gmres_givens_pythagoras_kernel(I iter, T*
 
 // second stage of ||w||^2 (partials of cgs_update_kernel, same fixed order as reduce_stage2) + square root + the Givens
 // step in one launch: one kernel boundary less per Arnoldi step
+// raw_col != NULL: the column as it is before the rotations, h[0..iter] and the norm, is kept there (the paired step's
+// recurrence reads the un-rotated Hessenberg matrix)
 __global__ __launch_bounds__(BLK) void norm_givens_kernel(int npart, const T* part, T* d_nrm, I iter, T* H, I ldh, T* gv, T* beta,
-                                                         T* res_hist) {
+                                                         T* res_hist, T* raw_col) {
     __shared__ double lds[4];
     __shared__ double s_nrm;
     __shared__ double s_col[GIV_MAX], s_gv[2 * GIV_MAX];
@@ -320,6 +322,11 @@ __global__ __launch_bounds__(BLK) void norm_givens_kernel(int npart, const T* pa
     if (threadIdx.x == 0) {
         s_nrm = sqrt(r);
         d_nrm[0] = s_nrm;
+        if (raw_col) raw_col[iter + 1] = s_nrm;
+    }
+    if (raw_col) {
+        const T* col = H + (long long)iter * ldh;
+        for (int i = threadIdx.x; i <= iter; i += BLK) raw_col[i] = col[i];
     }
     __syncthreads();
     givens_step_block(iter, s_nrm, H, ldh, gv, beta, res_hist, s_col, s_gv);
@@ -483,6 +490,222 @@ __global__ __launch_bounds__(BLK) void cgs_update_jacobi_kernel(I N, I ncol, con
             o[1] = make_double2(y2, yp);
         }
     }
+}
+
+// ---- two Arnoldi steps per pass over the raw basis (GmresPlan.pair) -----------------------------------------------------
+// p1 = B v_k and p2 = B p1 (B = A M^-1) are orthogonalised against r_0..r_k together: one dots pass and one update pass
+// over the basis serve both.  v_{k+1} comes from p1 as in the single step; p2 additionally loses its component along
+// v_{k+1} (the one-column fix-up, cgs_update_jacobi_kernel), which leaves a multiple of v_{k+2}; column k+1 of H follows
+// from the raw dots of p2 and the un-rotated earlier columns (pair_second_kernel).
+
+// block-wide sums of two values with the barriers of one; same order as block_sum_256, results valid in thread 0
+__device__ __forceinline__ void block_sum2_256(double& a, double& b, double* lds8) {
+    a = wave_sum(a);
+    b = wave_sum(b);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) { lds8[w] = a; lds8[4 + w] = b; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        a = (lds8[0] + lds8[1]) + (lds8[2] + lds8[3]);
+        b = (lds8[4] + lds8[5]) + (lds8[6] + lds8[7]);
+    }
+    __syncthreads();
+}
+
+// as cgs_dots_stage1 with two vectors in registers: part[col * nrb + blk] of w1, part[(ncol + col) * nrb + blk] of w2
+__global__ __launch_bounds__(BLK) void cgs_dots2_stage1(I n, I ncol, const T* __restrict__ Q, long long ldq,
+                                                       const T* __restrict__ w1, const T* __restrict__ w2, T* __restrict__ part,
+                                                       int nrb, int ct) {
+    __shared__ double lds[8];
+    const long long r0 = (long long)blockIdx.x * ROWS_PER_BLOCK;
+    const int c0 = blockIdx.y * ct;
+    double2 u[RPT], v[RPT];
+    long long row[RPT];
+#pragma unroll
+    for (int i = 0; i < RPT; ++i) {
+        row[i] = r0 + 2LL * threadIdx.x + (long long)i * (2 * BLK);
+        if (row[i] + 1 < n) {
+            u[i] = *reinterpret_cast<const double2*>(w1 + row[i]);
+            v[i] = *reinterpret_cast<const double2*>(w2 + row[i]);
+        } else {
+            u[i].x = (row[i] < n) ? w1[row[i]] : 0.0; u[i].y = 0.0;
+            v[i].x = (row[i] < n) ? w2[row[i]] : 0.0; v[i].y = 0.0;
+        }
+    }
+    for (int c = 0; c < ct; ++c) {
+        const int col = c0 + c;
+        if (col >= ncol) break;  // uniform
+        const T* q = Q + (long long)col * ldq;
+        double a1 = 0.0, a2 = 0.0;
+#pragma unroll
+        for (int i = 0; i < RPT; ++i) {
+            double2 qv;
+            if (row[i] + 1 < n) qv = ld_stream(q + row[i]);
+            else { qv.x = (row[i] < n) ? q[row[i]] : 0.0; qv.y = 0.0; }
+            a1 += qv.x * u[i].x + qv.y * u[i].y;
+            a2 += qv.x * v[i].x + qv.y * v[i].y;
+        }
+        block_sum2_256(a1, a2, lds);
+        if (threadIdx.x == 0) {
+            part[(long long)col * nrb + blockIdx.x] = a1;
+            part[((long long)ncol + col) * nrb + blockIdx.x] = a2;
+        }
+    }
+}
+
+// grid (ncol, 2), the order of cgs_dots_raw_stage2.  y = 0: h1_j = <r_j, w1> / nu_j into column k of H and of its un-rotated
+// copy, c1_j = h1_j / nu_j;  y = 1: e_j = <r_j, w2> / nu_j, c2_j = e_j / nu_j
+__global__ __launch_bounds__(BLK) void cgs_dots2_stage2(int nrb, I ncol, const T* part, const T* __restrict__ nu, T* d_h1, T* d_h1_raw,
+                                                       T* d_c1, T* d_e, T* d_c2) {
+    __shared__ double lds[4];
+    const int j = blockIdx.x;
+    const T* p = part + ((long long)blockIdx.y * ncol + j) * nrb;
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < nrb; i += BLK) acc += p[i];
+    const double r = block_sum_256(acc, lds);
+    if (threadIdx.x == 0) {
+        const double v = nu[j], h = r / v;
+        if (blockIdx.y == 0) {
+            d_h1[j] = h;
+            if (d_h1_raw) d_h1_raw[j] = h;
+            d_c1[j] = h / v;
+        } else {
+            d_e[j] = h;
+            d_c2[j] = h / v;
+        }
+    }
+}
+
+// w1 -= Q c1 and w2 -= Q c2, streamed as cgs_update_kernel<true> streams; partials of ||w1'||^2, <w1', w2'>, ||w2'||^2 at
+// part[blk], part[gridDim.x + blk], part[2 gridDim.x + blk]
+__global__ __launch_bounds__(BLK) void cgs_update2_kernel(I n, I ncol, const T* __restrict__ Q, long long ldq,
+                                                         const T* __restrict__ d_c1, const T* __restrict__ d_c2, T* __restrict__ w1,
+                                                         T* __restrict__ w2, T* __restrict__ part) {
+    __shared__ double lds[8];
+    __shared__ double sh1[128], sh2[128];
+    for (int j = threadIdx.x; j < ncol && j < 128; j += BLK) { sh1[j] = d_c1[j]; sh2[j] = d_c2[j]; }
+    __syncthreads();
+    const long long blk = blockIdx.x;
+    const long long r0 = blk * UROWS;
+    long long row[UPT];
+    double2 a[UPT], b[UPT];
+#pragma unroll
+    for (int i = 0; i < UPT; ++i) {
+        row[i] = r0 + 2LL * threadIdx.x + (long long)i * (2 * BLK);
+        if (row[i] + 1 < n) {
+            a[i] = *reinterpret_cast<const double2*>(w1 + row[i]);
+            b[i] = *reinterpret_cast<const double2*>(w2 + row[i]);
+        } else {
+            a[i].x = (row[i] < n) ? w1[row[i]] : 0.0; a[i].y = 0.0;
+            b[i].x = (row[i] < n) ? w2[row[i]] : 0.0; b[i].y = 0.0;
+        }
+    }
+#pragma unroll 4
+    for (int j = 0; j < ncol; ++j) {
+        const double h1 = (j < 128) ? sh1[j] : d_c1[j], h2 = (j < 128) ? sh2[j] : d_c2[j];
+        const T* q = Q + (long long)j * ldq;
+#pragma unroll
+        for (int i = 0; i < UPT; ++i) {
+            double2 qv;
+            if (row[i] + 1 < n) qv = ld_stream(q + row[i]);
+            else { qv.x = (row[i] < n) ? q[row[i]] : 0.0; qv.y = 0.0; }
+            a[i].x -= qv.x * h1; a[i].y -= qv.y * h1;
+            b[i].x -= qv.x * h2; b[i].y -= qv.y * h2;
+        }
+    }
+    double s11 = 0.0, s12 = 0.0, s22 = 0.0;
+#pragma unroll
+    for (int i = 0; i < UPT; ++i) {
+        if (row[i] + 1 < n) {
+            *reinterpret_cast<double2*>(w1 + row[i]) = a[i];
+            *reinterpret_cast<double2*>(w2 + row[i]) = b[i];
+        } else if (row[i] < n) { w1[row[i]] = a[i].x; w2[row[i]] = b[i].x; }
+        s11 += a[i].x * a[i].x + a[i].y * a[i].y;
+        s12 += a[i].x * b[i].x + a[i].y * b[i].y;
+        s22 += b[i].x * b[i].x + b[i].y * b[i].y;
+    }
+    block_sum2_256(s11, s12, lds);
+    const double r22 = block_sum_256(s22, lds);
+    if (threadIdx.x == 0) {
+        part[blk] = s11;
+        part[(long long)gridDim.x + blk] = s12;
+        part[2LL * gridDim.x + blk] = r22;
+    }
+}
+
+// The scalars of a pair after the two-vector update, one workgroup: second stage of s11, s12, s22 (fixed order), nu1 =
+// sqrt(s11) = nrm[k+1], sc = [c = s12 / s11 (the fix-up coefficient), d = s12 / nu1 = <v_{k+1}, p2>, s22, nu1]; column k of H
+// has h1 in rows 0..k already (cgs_dots2_stage2): nu1 goes below it, in H's un-rotated copy too, then the Givens step
+__global__ __launch_bounds__(BLK) void pair_first_kernel(int npart, const T* part, I k, T* nu, T* H, T* Hraw, I ldh, T* gv, T* beta,
+                                                        T* res_hist, T* sc) {
+    __shared__ double lds[8];
+    __shared__ double s_nrm;
+    __shared__ double s_col[GIV_MAX], s_gv[2 * GIV_MAX];
+    double a11 = 0.0, a12 = 0.0, a22 = 0.0;
+    for (int i = threadIdx.x; i < npart; i += BLK) {
+        a11 += part[i];
+        a12 += part[npart + i];
+        a22 += part[2 * npart + i];
+    }
+    block_sum2_256(a11, a12, lds);
+    const double r22 = block_sum_256(a22, lds);
+    if (threadIdx.x == 0) {
+        const double nu1 = sqrt(a11);
+        nu[k + 1] = nu1;
+        sc[0] = a12 / a11;
+        sc[1] = a12 / nu1;
+        sc[2] = r22;
+        sc[3] = nu1;
+        Hraw[(long long)k * ldh + k + 1] = nu1;
+        s_nrm = nu1;
+    }
+    __syncthreads();
+    givens_step_block(k, s_nrm, H, ldh, gv, beta, res_hist, s_col, s_gv);
+}
+
+// The scalars of a pair after the fix-up, one workgroup: nu_q = ||q|| = nrm[k+2] from the fix-up's partials; *d_flag is raised
+// when nu_q < 1e-4 sqrt(s22) (the relative error of q is about eps ||p2'|| / nu_q: 1e-12 at this threshold).  Column k+1
+// of H from p2 = B p1 = sum_{j<=k} h1_j B v_j + nu1 B v_{k+1} and B v_j = sum_i Hraw[i,j] v_i:
+//   rows i <= k: (e_i - sum_{j<k} h1_j Hraw[i,j] - h1_k h1_i) / nu1   (Hraw[i,j] = 0 for i > j + 1)
+//   row k+1: (d - h1_k nu1) / nu1,   row k+2: nu_q / nu1
+// into H and its un-rotated copy, then the Givens step of that column
+__global__ __launch_bounds__(BLK) void pair_second_kernel(int npart, const T* part, I k, T* nu, T* H, T* Hraw, I ldh,
+                                                         const T* __restrict__ d_e, const T* __restrict__ sc, T* gv, T* beta,
+                                                         T* res_hist, int* d_flag) {
+    __shared__ double lds[4];
+    __shared__ double s_nrm;
+    __shared__ double s_col[GIV_MAX], s_gv[2 * GIV_MAX];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < npart; i += BLK) acc += part[i];
+    const double qq = block_sum_256(acc, lds);
+    const double nu1 = sc[3];
+    if (threadIdx.x == 0) {
+        const double nuq = sqrt(qq);
+        nu[k + 2] = nuq;
+        if (d_flag && nuq < 1e-4 * sqrt(sc[2])) *d_flag = 1;
+        s_nrm = nuq / nu1;
+    }
+    __syncthreads();
+    const T* h1 = Hraw + (long long)k * ldh;
+    T* col = H + (long long)(k + 1) * ldh;
+    T* raw = Hraw + (long long)(k + 1) * ldh;
+    const double h1k = h1[k];
+    for (int i = threadIdx.x; i <= k; i += BLK) {
+        double t = d_e[i];
+        for (int j = (i > 0 ? i - 1 : 0); j < k; ++j) t -= h1[j] * Hraw[(long long)j * ldh + i];
+        t -= h1k * h1[i];
+        const double v = t / nu1;
+        col[i] = v;
+        raw[i] = v;
+    }
+    if (threadIdx.x == 0) {
+        const double v = (sc[1] - h1k * nu1) / nu1;
+        col[k + 1] = v;
+        raw[k + 1] = v;
+        raw[k + 2] = s_nrm;
+    }
+    __syncthreads();
+    givens_step_block(k + 1, s_nrm, H, ldh, gv, beta, res_hist, s_col, s_gv);
 }
 
 // H[0:m,0:m] y = beta by back substitution (cublasDtrsv, krylov.c:297-301), one workgroup: column-oriented so that every
@@ -736,8 +959,8 @@ void dfl_dscal_inv_dev(I n, const T* d_scale, T* x, void* stream) {
 
 int64_t dfl_cgs_work_size(I n, I ncol) {
     int64_t nrb = ceil_div(n, ROWS_PER_BLOCK);
-    int64_t a = nrb * (int64_t)(ncol > 0 ? ncol : 1);
-    int64_t b = ceil_div(n, UROWS);
+    int64_t a = 2 * nrb * (int64_t)(ncol > 0 ? ncol : 1);  // two vectors per dots pass (dfl_cgs_dots2_raw)
+    int64_t b = 3 * (int64_t)ceil_div(n, UROWS);           // s11, s12, s22 of dfl_cgs_update2
     return (a > b ? a : b) + 16;
 }
 void dfl_cgs_dots(I n, I ncol, const T* Q, int64_t ldq, const T* w, T* d_h, T* work, void* stream) {
@@ -763,7 +986,7 @@ void dfl_cgs_update_givens(I n, I ncol, const T* Q, int64_t ldq, const T* d_h, T
                            T* d_gv, T* d_beta, T* d_res_hist, void* stream) {
     int g = ceil_div(n, UROWS);
     cgs_update_kernel<true><<<g, BLK, 0, S(stream)>>>(n, ncol, Q, ldq, d_h, w, work);
-    norm_givens_kernel<<<1, BLK, 0, S(stream)>>>(g, work, d_nrm, iter, d_H, ldh, d_gv, d_beta, d_res_hist);
+    norm_givens_kernel<<<1, BLK, 0, S(stream)>>>(g, work, d_nrm, iter, d_H, ldh, d_gv, d_beta, d_res_hist, nullptr);
     DFL_LAUNCH_CHECK();
 }
 void dfl_cgs_dots_raw(I n, I ncol, const T* Q, int64_t ldq, const T* w, const T* d_nu, T* d_h, T* d_c, T* work, void* stream) {
@@ -774,16 +997,58 @@ void dfl_cgs_dots_raw(I n, I ncol, const T* Q, int64_t ldq, const T* w, const T*
     cgs_dots_raw_stage2<<<ncol, BLK, 0, S(stream)>>>(nrb, work, d_nu, d_h, d_c);
     DFL_LAUNCH_CHECK();
 }
-void dfl_cgs_update_jacobi_givens(I N, I ncol, const T* Q, int64_t ldq, const T* d_c, T* w, const T* dinv33, const T* dinv1, T* z4,
-                                  T* d_nrm, T* work, I iter, T* d_H, I ldh, T* d_gv, T* d_beta, T* d_res_hist, void* stream) {
-    if (N <= 0) return;
+static int launch_update_jacobi(I N, I ncol, const T* Q, int64_t ldq, const T* d_c, T* w, const T* dinv33, const T* dinv1, T* z4,
+                                T* work, void* stream) {
     const int g = ceil_div(N, BLK);
     const int vec_ok = aligned16(Q) && aligned16(w) && !(ldq & 1);
     if (z4) cgs_update_jacobi_kernel<true><<<g, BLK, 0, S(stream)>>>(N, ncol, Q, ldq, d_c, w, work, dinv33, dinv1, z4, vec_ok);
     else cgs_update_jacobi_kernel<false><<<g, BLK, 0, S(stream)>>>(N, ncol, Q, ldq, d_c, w, work, nullptr, nullptr, nullptr, vec_ok);
-    norm_givens_kernel<<<1, BLK, 0, S(stream)>>>(g, work, d_nrm, iter, d_H, ldh, d_gv, d_beta, d_res_hist);
+    return g;
+}
+void dfl_cgs_update_jacobi_givens_keep(I N, I ncol, const T* Q, int64_t ldq, const T* d_c, T* w, const T* dinv33, const T* dinv1,
+                                       T* z4, T* d_nrm, T* work, I iter, T* d_H, I ldh, T* d_gv, T* d_beta, T* d_res_hist,
+                                       T* d_raw_col, void* stream) {
+    if (N <= 0) return;
+    const int g = launch_update_jacobi(N, ncol, Q, ldq, d_c, w, dinv33, dinv1, z4, work, stream);
+    norm_givens_kernel<<<1, BLK, 0, S(stream)>>>(g, work, d_nrm, iter, d_H, ldh, d_gv, d_beta, d_res_hist, d_raw_col);
     DFL_LAUNCH_CHECK();
 }
+void dfl_cgs_update_jacobi_givens(I N, I ncol, const T* Q, int64_t ldq, const T* d_c, T* w, const T* dinv33, const T* dinv1, T* z4,
+                                  T* d_nrm, T* work, I iter, T* d_H, I ldh, T* d_gv, T* d_beta, T* d_res_hist, void* stream) {
+    dfl_cgs_update_jacobi_givens_keep(N, ncol, Q, ldq, d_c, w, dinv33, dinv1, z4, d_nrm, work, iter, d_H, ldh, d_gv, d_beta, d_res_hist,
+                                      nullptr, stream);
+}
+void dfl_cgs_update_jacobi(I N, I ncol, const T* Q, int64_t ldq, const T* d_c, T* w, const T* dinv33, const T* dinv1, T* z4, T* work,
+                           void* stream) {
+    if (N <= 0) return;
+    (void)launch_update_jacobi(N, ncol, Q, ldq, d_c, w, dinv33, dinv1, z4, work, stream);
+    DFL_LAUNCH_CHECK();
+}
+void dfl_cgs_dots2_raw(I n, I ncol, const T* Q, int64_t ldq, const T* w1, const T* w2, const T* d_nu, T* d_h1, T* d_h1_raw, T* d_c1,
+                       T* d_e, T* d_c2, T* work, void* stream) {
+    if (ncol <= 0) return;
+    int nrb = ceil_div(n, ROWS_PER_BLOCK);
+    dim3 grid(nrb, ceil_div(ncol, CT));
+    cgs_dots2_stage1<<<grid, BLK, 0, S(stream)>>>(n, ncol, Q, ldq, w1, w2, work, nrb, CT);
+    cgs_dots2_stage2<<<dim3(ncol, 2), BLK, 0, S(stream)>>>(nrb, ncol, work, d_nu, d_h1, d_h1_raw, d_c1, d_e, d_c2);
+    DFL_LAUNCH_CHECK();
+}
+void dfl_cgs_update2(I n, I ncol, const T* Q, int64_t ldq, const T* d_c1, const T* d_c2, T* w1, T* w2, T* work, void* stream) {
+    if (n <= 0) return;
+    cgs_update2_kernel<<<ceil_div(n, UROWS), BLK, 0, S(stream)>>>(n, ncol, Q, ldq, d_c1, d_c2, w1, w2, work);
+    DFL_LAUNCH_CHECK();
+}
+void dfl_gmres_pair_first(int npart, const T* part, I k, T* d_nu, T* d_H, T* d_Hraw, I ldh, T* d_gv, T* d_beta, T* d_res_hist,
+                          T* d_sc, void* stream) {
+    pair_first_kernel<<<1, BLK, 0, S(stream)>>>(npart, part, k, d_nu, d_H, d_Hraw, ldh, d_gv, d_beta, d_res_hist, d_sc);
+    DFL_LAUNCH_CHECK();
+}
+void dfl_gmres_pair_second(int npart, const T* part, I k, T* d_nu, T* d_H, T* d_Hraw, I ldh, const T* d_e, const T* d_sc, T* d_gv,
+                           T* d_beta, T* d_res_hist, int* d_flag, void* stream) {
+    pair_second_kernel<<<1, BLK, 0, S(stream)>>>(npart, part, k, d_nu, d_H, d_Hraw, ldh, d_e, d_sc, d_gv, d_beta, d_res_hist, d_flag);
+    DFL_LAUNCH_CHECK();
+}
+int dfl_cgs_update2_parts(I n) { return ceil_div(n, UROWS); }
 void dfl_gmres_scale_inv(I m, const T* d_nu, T* d_y, void* stream) {
     if (m <= 0) return;
     scale_inv_vec_kernel<<<ceil_div(m, BLK), BLK, 0, S(stream)>>>(m, d_nu, d_y);

@@ -6,7 +6,8 @@
  *   - the two cublasDgemv + Dnrm2 + Dscal of an Arnoldi step are two fused passes (dfl_cgs_dots / dfl_cgs_update) and the
  *     normalisation is folded into the next preconditioner application -- or, one GPU with the Jacobi tree, never done:
  *     the basis stays unnormalised, the update applies M^-1 to the column it forms and the matvec divides by the norm
- *     (GMRES_STEP_RAW_BASIS);
+ *     (GMRES_STEP_RAW_BASIS); that step takes two products before it orthogonalises, so that one dots pass and one update
+ *     pass over the basis serve two iterations (gmres_pair);
  *   - every scalar recurrence stays on the device; the host reads 8 bytes only when the reference tests convergence (every
  *     20th iteration) -- the reference syncs 2-3 times per iteration;
  *   - work space is cached in the Krylov object instead of malloc+memset per solve;
@@ -52,8 +53,9 @@ void DflWsVecFreeAs(f64* p, int pooled) {
 void DflWsFree(KrylovExt* x) {
     DflWsVecFreeAs(x->Q, x->q_pooled); DflWsVecFreeAs(x->Z, x->ws_pooled); CdamFreeDevice(x->H, 0); DflWsVecFreeAs(x->tmp, x->ws_pooled); CdamFreeDevice(x->gv, 0);
     CdamFreeDevice(x->beta, 0); CdamFreeDevice(x->res_hist, 0); CdamFreeDevice(x->nrm_base, 0); CdamFreeDevice(x->work, 0);
-    CdamFreeDevice(x->d_flag, 0); CdamFreeDevice(x->hraw, 0);
+    CdamFreeDevice(x->d_flag, 0); CdamFreeDevice(x->hraw, 0); CdamFreeDevice(x->h_unrot, 0); CdamFreeDevice(x->pair_buf, 0);
     x->Q = x->Z = x->H = x->tmp = x->gv = x->beta = x->res_hist = x->nrm = x->nrm_base = x->work = x->hraw = NULL;
+    x->h_unrot = x->pair_buf = NULL;
     x->d_flag = NULL;
     x->ws_n = x->ws_maxit = x->ws_hist = 0;
 }
@@ -84,7 +86,10 @@ void DflWsEnsure(KrylovExt* x, index_type n, index_type maxit, index_type ldh, i
     x->work_len = dfl_cgs_work_size(n, maxit + 1) + dfl_reduce_work_size();
     x->work = (f64*)CdamMallocDevice((ptrdiff_t)x->work_len * SIZE_OF(f64));
     x->d_flag = (int*)CdamMallocDevice(16);
+    HIPGUARD(hipMemsetAsync(x->d_flag, 0, 16, DflStream()));
     x->hraw = (f64*)CdamMallocDevice((ptrdiff_t)(ldh + 32) * SIZE_OF(f64));
+    x->h_unrot = (f64*)CdamMallocDevice((ptrdiff_t)ldh * maxit * SIZE_OF(f64));
+    x->pair_buf = (f64*)CdamMallocDevice(4 * (ptrdiff_t)ldh * SIZE_OF(f64));
     x->ws_n = n; x->ws_maxit = maxit; x->ws_fresh = TRUE;
 }
 
@@ -175,8 +180,9 @@ void DflPcApplyFused(PC* pc, index_type na, f64* w, const f64* d_nrm, f64* z) { 
 /* Environment switches of the GMRES paths, read here and nowhere else.  Cached for the process: DFL_SPMV_X4=0 (the
    reference-layout gathers, A/B), DFL_SPMV_X4_MIN (smallest matrix, in nodes, that takes the interleaved path; tests set 1).
    Read at every solve (A/B): eager host reads, boundary rows on the library stream, three launches per fused-norm step,
-   DFL_GMRES_RAW_BASIS=0 (one GPU: the normalised basis and the separate Jacobi pass instead of GMRES_STEP_RAW_BASIS) */
-typedef struct GmresEnv { b32 x4; index_type x4_min; b32 eager_sync, no_side_rows, no_fused_update_pc, raw_basis; } GmresEnv;
+   DFL_GMRES_RAW_BASIS=0 (one GPU: the normalised basis and the separate Jacobi pass instead of GMRES_STEP_RAW_BASIS),
+   DFL_GMRES_TWO_STEP=0 (the raw-basis step one iteration at a time) */
+typedef struct GmresEnv { b32 x4; index_type x4_min; b32 eager_sync, no_side_rows, no_fused_update_pc, raw_basis, two_step; } GmresEnv;
 static GmresEnv gmres_env(void) {
     static int x4 = -1, x4_min = 4096;
     if (x4 < 0) {
@@ -184,9 +190,9 @@ static GmresEnv gmres_env(void) {
         if (min) x4_min = atoi(min);
         x4 = !(off && atoi(off) == 0);
     }
-    const char* raw = getenv("DFL_GMRES_RAW_BASIS");
+    const char *raw = getenv("DFL_GMRES_RAW_BASIS"), *two = getenv("DFL_GMRES_TWO_STEP");
     const GmresEnv e = {x4, x4_min, getenv("DFL_KRYLOV_EAGER_SYNC") != NULL, getenv("DFL_NO_SIDE_BOUNDARY_ROWS") != NULL,
-                        getenv("DFL_NO_FUSED_UPDATE_PC") != NULL, !(raw && atoi(raw) == 0)};
+                        getenv("DFL_NO_FUSED_UPDATE_PC") != NULL, !(raw && atoi(raw) == 0), !(two && atoi(two) == 0)};
     return e;
 }
 
@@ -238,7 +244,10 @@ void DflGmresPlanFill(GmresPlan* p, const KrylovExt* ex, index_type max_iter, Ma
        kernel applies M^-1 to the column it has just formed and the matvec divides by nrm[k] -- the separate Jacobi pass, which
        read the new column back only to scale it, is gone (csrc/k_blas.hip, cgs_update_jacobi_kernel).  Restarts, lazy or eager
        reads and the check interval have no say here: the arithmetic of a solve does not depend on them */
-    if (p->step == GMRES_STEP_REFERENCE && p->x4_skip_z && p->rows == p->N && env.raw_basis) p->step = GMRES_STEP_RAW_BASIS;
+    if (p->step == GMRES_STEP_REFERENCE && p->x4_skip_z && p->rows == p->N && env.raw_basis) {
+        p->step = GMRES_STEP_RAW_BASIS;
+        p->pair = env.two_step;
+    }
 }
 
 /* ============================== operator, residual, Arnoldi step =========================== */
@@ -357,9 +366,11 @@ static void gmres_orthogonalise(const GmresPlan* p, KrylovExt* ex, index_type it
     case GMRES_STEP_RAW_BASIS:
         /* columns 0..iter are r_j = nrm[j] q_j: h_j = <r_j, w> / nrm[j] into H, hraw[j] = h_j / nrm[j] multiplies r_j */
         DFL_TIMED(DFL_TAG_CGS_DOTS, dfl_cgs_dots_raw(na, iter + 1, Q, na, w, ex->nrm, h, ex->hraw, ex->work, s));
-        DFL_TIMED(DFL_TAG_CGS_UPDATE, dfl_cgs_update_jacobi_givens(p->N, iter + 1, Q, na, ex->hraw, w, p->d33, p->d1,
-                                                                   last ? NULL : p->z4, nrm, ex->work, iter, H, ldh, ex->gv,
-                                                                   ex->beta, res_hist, s));
+        /* (paired solves: a later pair reads this column un-rotated) */
+        DFL_TIMED(DFL_TAG_CGS_UPDATE,
+                  dfl_cgs_update_jacobi_givens_keep(p->N, iter + 1, Q, na, ex->hraw, w, p->d33, p->d1, last ? NULL : p->z4, nrm,
+                                                    ex->work, iter, H, ldh, ex->gv, ex->beta, res_hist,
+                                                    p->pair ? ex->h_unrot + (size_t)iter * (size_t)ldh : NULL, s));
         break;
     case GMRES_STEP_REFERENCE:
         DFL_TIMED(DFL_TAG_CGS_DOTS, dfl_cgs_dots(na, iter + 1, Q, na, w, h, ex->work, s));
@@ -367,6 +378,31 @@ static void gmres_orthogonalise(const GmresPlan* p, KrylovExt* ex, index_type it
                                                             res_hist, s));
         break;
     }
+}
+
+/* Iterations k and k+1 of a cycle in one pass over the basis (GmresPlan.pair).  At entry column k holds r_k and, k > 0, z4 holds
+   M^-1 r_k.  p1 = B v_k = (A z4) / nrm[k] into column k+1, z4 = M^-1 p1, p2 = B p1 = A z4 into column k+2 -- in exact arithmetic
+   the component of p2 orthogonal to v_0..v_{k+1} is a multiple of v_{k+2}, because B v_j lies in span(v_0..v_{j+1}).  One dots
+   pass and one update pass over columns 0..k serve both vectors; p1' = r_{k+1}; the fix-up q = p2' - c p1' (one column) leaves
+   r_{k+2} = q in column k+2 with z4 = M^-1 q for the step that follows (last: none does).  Columns k and k+1 of H, their Givens
+   steps, beta and two entries of the history come from two small kernels (csrc/k_blas.hip, pair_first_kernel and
+   pair_second_kernel); nothing waits for the whole grid and no sum is taken atomically */
+static void gmres_pair(const GmresPlan* p, KrylovExt* ex, Matrix* A, PC* pc, index_type k, f64* res_hist, b32 last) {
+    const index_type na = p->na, ldh = p->ldh;
+    hipStream_t s = DflStream();
+    f64 *const Q = ex->Q, *const p1 = Q + (size_t)(k + 1) * (size_t)na, *const p2 = Q + (size_t)(k + 2) * (size_t)na;
+    f64 *const c1 = ex->pair_buf, *const c2 = c1 + ldh, *const e = c2 + ldh, *const sc = e + ldh;
+    f64 *const h1 = ex->H + (size_t)k * (size_t)ldh, *const h1_raw = ex->h_unrot + (size_t)k * (size_t)ldh;
+    const int g2 = dfl_cgs_update2_parts(na), g1 = (int)CEIL_DIV(p->N, 256);
+    if (k == 0) DFL_TIMED(DFL_TAG_PC, (void)DflPcApplyFusedX4(pc, na, Q, NULL, NULL, p->z4));
+    DFL_TIMED(DFL_TAG_SPMV, DflMatrixFSMatVecX4RangeScaled(A, p->z4, ex->nrm + k, p1, 0, p->x4_N));
+    DFL_TIMED(DFL_TAG_PC, (void)DflPcApplyFusedX4(pc, na, p1, NULL, NULL, p->z4));
+    DFL_TIMED(DFL_TAG_SPMV, DflMatrixFSMatVecX4Range(A, p->z4, p2, 0, p->x4_N));
+    DFL_TIMED(DFL_TAG_CGS_DOTS, dfl_cgs_dots2_raw(na, k + 1, Q, na, p1, p2, ex->nrm, h1, h1_raw, c1, e, c2, ex->work, s));
+    DFL_TIMED(DFL_TAG_CGS_UPDATE, dfl_cgs_update2(na, k + 1, Q, na, c1, c2, p1, p2, ex->work, s));
+    dfl_gmres_pair_first(g2, ex->work, k, ex->nrm, ex->H, ex->h_unrot, ldh, ex->gv, ex->beta, res_hist, sc, s);
+    DFL_TIMED(DFL_TAG_CGS_UPDATE, dfl_cgs_update_jacobi(p->N, 1, p1, na, sc, p2, p->d33, p->d1, last ? NULL : p->z4, ex->work, s));
+    dfl_gmres_pair_second(g1, ex->work, k, ex->nrm, ex->H, ex->h_unrot, ldh, e, sc, ex->gv, ex->beta, res_hist, ex->d_flag, s);
 }
 
 /* H y = beta, x += M^-1 (Q[:,0:iter] y)   (FGMRES: x += Z[:,0:iter] y).  Column `iter` of the basis may still be
@@ -542,6 +578,7 @@ static b32 gmres_run(Matrix* A, f64* x, f64* b, Krylov* ksp, b32 force_probe) {
     GmresPlan p;
     DflGmresPlanFill(&p, ex, maxit, A, pc, na, FALSE);
     ex->last_step = (int)p.step;
+    ex->last_pairs = ex->last_singles = ex->last_pair_cancelled = 0;
     f64 *const Q = ex->Q, *const tmp = ex->tmp;
     b32 converged = FALSE;
     index_type total = 0; /* iterations over all cycles */
@@ -560,15 +597,21 @@ static b32 gmres_run(Matrix* A, f64* x, f64* b, Krylov* ksp, b32 force_probe) {
         /* the normalisation of Q[:,k] is folded into the preconditioner application that consumes it;
            nrm[k] holds the norm Q[:,k] still has to be divided by */
         while (!converged && iter < m && total < maxit) {
-            /* 2.0 z = inv(P) Q[:,iter] (FGMRES keeps every z; the fused step has left it in tmp)   2.2 Q[:,iter+1] = A z */
-            gmres_apply_operator(&p, ex, A, pc, COL(Q, iter), ex->nrm + iter, p.Zb ? COL(p.Zb, iter) : tmp,
-                                 iter > 0 && (p.step == GMRES_STEP_FUSED_UPDATE_PC || p.step == GMRES_STEP_RAW_BASIS),
-                                 COL(Q, iter + 1));
-            /* 3. classical Gram-Schmidt   4. Givens rotations + residual recurrence */
-            gmres_orthogonalise(&p, ex, iter, res_hist, iter + 1 >= m || total + 1 >= maxit);
+            /* two iterations at once where both fit and no convergence check falls between them */
+            const b32 pair = p.pair && iter + 2 <= m && total + 2 <= maxit && (total + 1) % ex->check_interval != 0;
+            const index_type adv = pair ? 2 : 1;
+            if (pair) gmres_pair(&p, ex, A, pc, iter, res_hist, iter + 2 >= m || total + 2 >= maxit);
+            else {
+                /* 2.0 z = inv(P) Q[:,iter] (FGMRES keeps every z; the fused step has left it in tmp)   2.2 Q[:,iter+1] = A z */
+                gmres_apply_operator(&p, ex, A, pc, COL(Q, iter), ex->nrm + iter, p.Zb ? COL(p.Zb, iter) : tmp,
+                                     iter > 0 && (p.step == GMRES_STEP_FUSED_UPDATE_PC || p.step == GMRES_STEP_RAW_BASIS),
+                                     COL(Q, iter + 1));
+                /* 3. classical Gram-Schmidt   4. Givens rotations + residual recurrence */
+                gmres_orthogonalise(&p, ex, iter, res_hist, iter + 1 >= m || total + 1 >= maxit);
+            }
             if (hr.pend) {
-                /* the check enqueued behind the PREVIOUS iteration: the device has the iteration just enqueued to work on
-                   while the host waits for the 8 (+ 40) bytes */
+                /* the check enqueued behind the PREVIOUS step: the device has the step just enqueued to work on while the host
+                   waits for the 8 (+ 40) bytes */
                 HIPGUARD(hipEventSynchronize(ex->ev_stat));
                 hr.pend = FALSE;
                 if (hr.pend_first) {
@@ -576,11 +619,13 @@ static b32 gmres_run(Matrix* A, f64* x, f64* b, Krylov* ksp, b32 force_probe) {
                     const FirstRead fr = gmres_first_read(ex, &hr, FALSE);
                     if (fr != FIRST_READ_GO_ON) return fr == FIRST_READ_REDO;
                 }
-                /* converged: the iteration enqueued meanwhile is not counted */
+                /* converged: the step enqueued meanwhile (one iteration or two) is not counted */
                 if (DflKrylovConverged(ksp, fabs(ex->h_stat[8]), hr.rnrm_init)) { converged = TRUE; break; }
             }
-            if ((total + 1) % ex->check_interval == 0) converged = gmres_check(ksp, &p, ex, &hr, iter, total);
-            iter++; total++;
+            if ((total + adv) % ex->check_interval == 0) converged = gmres_check(ksp, &p, ex, &hr, iter + adv - 1, total + adv - 1);
+            iter += adv; total += adv;
+            if (pair) ex->last_pairs++;
+            else ex->last_singles++;
         }
         /* (no check is pending here: one on the last iteration of the loop went to final_check instead) */
         if (!hr.first_read_done) { /* a solve shorter than its check interval: nothing has been read yet */
@@ -593,7 +638,8 @@ static b32 gmres_run(Matrix* A, f64* x, f64* b, Krylov* ksp, b32 force_probe) {
             gmres_update_solution(&p, ex, pc, iter, x);
         }
     }
-    gmres_end_of_solve(ex, total, ex->fused_norm);
+    gmres_end_of_solve(ex, total, ex->fused_norm || p.pair);
+    if (p.pair) { ex->last_pair_cancelled = ex->stats.fused_norm_cancelled; ex->stats.fused_norm_cancelled = FALSE; }
     if (hr.final_check >= 0 && !converged) converged = DflKrylovConverged(ksp, fabs(ex->h_stat[9]), hr.rnrm_init);
     ex->stats.iterations = total; ex->stats.converged = converged;
     return FALSE;
@@ -707,6 +753,15 @@ void GMRESSolvePrivate(Matrix* A, f64* x, f64* b, void* ctx) {
 /* which Arnoldi step (GmresStep, solver_private.h) the most recent unpipelined GMRES solve of this solver ran; -1: none yet */
 int DflKrylovLastGmresStep(Krylov* ksp) {
     return (ksp && ksp->ksp_solve == GMRESSolvePrivate && kext(ksp)) ? kext(ksp)->last_step : -1;
+}
+
+/* how the most recent unpipelined GMRES solve of this solver advanced: counted steps of two iterations (gmres_pair), counted
+   steps of one, and whether a pair raised the cancellation flag (||q|| < 1e-4 ||p2'||); a plan without pairs reports 0 pairs */
+void DflKrylovLastGmresPairs(Krylov* ksp, int* pairs, int* singles, int* cancelled) {
+    const KrylovExt* ex = (ksp && ksp->ksp_solve == GMRESSolvePrivate) ? kext(ksp) : NULL;
+    if (pairs) *pairs = ex ? ex->last_pairs : 0;
+    if (singles) *singles = ex ? ex->last_singles : 0;
+    if (cancelled) *cancelled = ex ? ex->last_pair_cancelled : 0;
 }
 
 /* the GMRES work space for this matrix as the next KrylovSolve would size it (host/ws_placement.c calibrates it ahead of

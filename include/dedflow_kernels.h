@@ -83,7 +83,8 @@ void dfl_norms4(dfl_index N, const dfl_value* F, dfl_value* d_out4, int take_sqr
  *      and the Dnrm2 of :230).
  *   dfl_cgs_dots   : d_h[j] = Q[:,j] . w, j < ncol  (one pass over Q[:,0:ncol] and ~ncol/16 passes over w)
  *   dfl_cgs_update : w -= Q[:,0:ncol] h ; *d_nrm = ||w||_2   (one pass over Q, w read+written once)
- * Q is column-major with leading dimension ldq.  `work` >= dfl_cgs_work_size(n, ncol) doubles. */
+ * Q is column-major with leading dimension ldq.  `work` >= dfl_cgs_work_size(n, ncol) doubles (it covers the two-vector
+ * forms below: two sets of dots partials, three of update partials). */
 int64_t dfl_cgs_work_size(dfl_index n, dfl_index ncol);
 void dfl_cgs_dots(dfl_index n, dfl_index ncol, const dfl_value* Q, int64_t ldq, const dfl_value* w, dfl_value* d_h,
                   dfl_value* work, void* stream);
@@ -108,6 +109,37 @@ void dfl_cgs_update_jacobi_givens(dfl_index N, dfl_index ncol, const dfl_value* 
                                   dfl_index iter, dfl_value* d_H, dfl_index ldh, dfl_value* d_gv, dfl_value* d_beta,
                                   dfl_value* d_res_hist, void* stream);
 void dfl_gmres_scale_inv(dfl_index m, const dfl_value* d_nu, dfl_value* d_y, void* stream);
+/* Two Arnoldi steps per pass over the raw basis: w1 = B v_k, w2 = B w1 (B = A M^-1) against columns 0..ncol-1 = r_0..r_k.
+ * dfl_cgs_dots2_raw: one pass over Q for both vectors; d_h1[j] = <r_j, w1> / nu_j (column k of H; d_h1_raw, may be NULL, gets a
+ *   copy), d_c1 = d_h1 / nu, d_e[j] = <r_j, w2> / nu_j, d_c2 = d_e / nu.  Fixed summation order; work: dfl_cgs_work_size.
+ * dfl_cgs_update2: w1 -= Q d_c1, w2 -= Q d_c2 in one pass; work holds g = dfl_cgs_update2_parts(n) partials each of ||w1'||^2,
+ *   <w1', w2'>, ||w2'||^2 at work[0], work[g], work[2g].
+ * dfl_gmres_pair_first: second stage of those 3 x npart partials; d_nu[k+1] = nu1 = ||w1'||, d_sc = [<w1',w2'> / nu1^2 (the
+ *   coefficient of the fix-up), <w1',w2'> / nu1, ||w2'||^2, nu1], nu1 into row k+1 of column k of d_Hraw (the un-rotated copy of
+ *   H, same leading dimension), the Givens step of column k.
+ * dfl_cgs_update_jacobi: the update of dfl_cgs_update_jacobi_givens without the norm's second stage and the Givens step; one
+ *   partial of ||w'||^2 per block of 256 nodes in work.  With one column and d_c = d_sc it is the fix-up q = w2' - c w1'.
+ * dfl_gmres_pair_second: d_nu[k+2] = nu_q = ||q|| from npart partials; column k+1 of H and of d_Hraw from d_e, d_sc and the
+ *   earlier columns of d_Hraw; its Givens step; *d_flag (may be NULL) raised when nu_q < 1e-4 ||w2'||.
+ * dfl_cgs_update_jacobi_givens_keep: dfl_cgs_update_jacobi_givens that also keeps the un-rotated column (h[0..iter], norm) in
+ *   d_raw_col (NULL: none kept). */
+int dfl_cgs_update2_parts(dfl_index n);
+void dfl_cgs_dots2_raw(dfl_index n, dfl_index ncol, const dfl_value* Q, int64_t ldq, const dfl_value* w1, const dfl_value* w2,
+                       const dfl_value* d_nu, dfl_value* d_h1, dfl_value* d_h1_raw, dfl_value* d_c1, dfl_value* d_e, dfl_value* d_c2,
+                       dfl_value* work, void* stream);
+void dfl_cgs_update2(dfl_index n, dfl_index ncol, const dfl_value* Q, int64_t ldq, const dfl_value* d_c1, const dfl_value* d_c2,
+                     dfl_value* w1, dfl_value* w2, dfl_value* work, void* stream);
+void dfl_gmres_pair_first(int npart, const dfl_value* part, dfl_index k, dfl_value* d_nu, dfl_value* d_H, dfl_value* d_Hraw,
+                          dfl_index ldh, dfl_value* d_gv, dfl_value* d_beta, dfl_value* d_res_hist, dfl_value* d_sc, void* stream);
+void dfl_cgs_update_jacobi(dfl_index N, dfl_index ncol, const dfl_value* Q, int64_t ldq, const dfl_value* d_c, dfl_value* w,
+                           const dfl_value* dinv33, const dfl_value* dinv1, dfl_value* z4, dfl_value* work, void* stream);
+void dfl_gmres_pair_second(int npart, const dfl_value* part, dfl_index k, dfl_value* d_nu, dfl_value* d_H, dfl_value* d_Hraw,
+                           dfl_index ldh, const dfl_value* d_e, const dfl_value* d_sc, dfl_value* d_gv, dfl_value* d_beta,
+                           dfl_value* d_res_hist, int* d_flag, void* stream);
+void dfl_cgs_update_jacobi_givens_keep(dfl_index N, dfl_index ncol, const dfl_value* Q, int64_t ldq, const dfl_value* d_c,
+                                       dfl_value* w, const dfl_value* dinv33, const dfl_value* dinv1, dfl_value* z4, dfl_value* d_nrm,
+                                       dfl_value* work, dfl_index iter, dfl_value* d_H, dfl_index ldh, dfl_value* d_gv,
+                                       dfl_value* d_beta, dfl_value* d_res_hist, dfl_value* d_raw_col, void* stream);
 void dfl_dsqrt_dev(dfl_value* d_val, void* stream); /* *d_val = sqrt(*d_val) */
 /* y = Q[:,0:ncol] c  (cublasDgemv OP_N of krylov.c:304-311) */
 void dfl_gemv_n(dfl_index n, dfl_index ncol, const dfl_value* Q, int64_t ldq, const dfl_value* d_c, dfl_value* y, void* stream);
