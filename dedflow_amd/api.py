@@ -733,6 +733,14 @@ def _declare(L):
     f("dfl_interleave4", None, [i32, i32, i32, vp, vp, vp])
     f("DflKrylovLastGmresStep", C.c_int, [vp])
     f("DflKrylovLastGmresPairs", None, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)])
+    f("DflKrylovLastGmresBlocks", None, [vp, C.POINTER(C.c_int * 5), C.POINTER(C.c_int)])
+    # blocks of 3 or 4 Arnoldi steps per pass over the raw basis (csrc/k_blas.hip)
+    f("dfl_cgs_dots_block_parts", C.c_int, [i32, C.c_int]); f("dfl_cgs_update_block_parts", C.c_int, [i32, C.c_int])
+    f("dfl_cgs_dots_block", None, [i32, i32, C.c_int, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, vp, i32, vp, vp])
+    f("dfl_cgs_update_block", None, [i32, i32, C.c_int, vp, C.c_int64, vp, i32, vp, C.c_int64, vp, vp])
+    f("dfl_gmres_block_first", None, [C.c_int, vp, C.c_int, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp])
+    f("dfl_cgs_fixup_block", None, [i32, C.c_int, vp, C.c_int64, vp, vp, vp, vp, vp, vp])
+    f("dfl_gmres_block_second", None, [C.c_int, vp, C.c_int, i32, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp])
     f("dfl_dscal_inv_dev", None, [i32, vp, vp, vp]); f("dfl_dsqrt_dev", None, [vp, vp])
     f("dfl_norms4", None, [i32, vp, vp, C.c_int, vp, vp])
     f("dfl_alpha_states", None, [i32, vp, vp, vp, f64, f64, f64, f64, vp, vp, vp, vp, vp])

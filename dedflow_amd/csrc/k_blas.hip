@@ -708,6 +708,421 @@ __global__ __launch_bounds__(BLK) void pair_second_kernel(int npart, const T* pa
     givens_step_block(k + 1, s_nrm, H, ldh, gv, beta, res_hist, s_col, s_gv);
 }
 
+// ---- up to four Arnoldi steps per pass over the raw basis (gmres_block, host/gmres.c) ----------------------------------
+// The pair generalised to S = 3 or 4 products p_0 = B v_k, p_i = B p_{i-1}, held in S consecutive columns w + i ldw: one
+// dots pass and one update pass over r_0..r_k serve all of them.  The updated p_i' = (I - V V^T) p_i span v_{k+1}..v_{k+S};
+// they are orthogonalised among themselves through their Gram matrix G (block_first_kernel: q_i = sum_{l<=i} C[i,l] p_l', C
+// unit lower triangular), the q_i are formed in one pass over the S columns (cgs_fixup_block_kernel), and the columns
+// k+1..k+S-1 of H follow from the coordinates of the p_i in the orthonormal basis and the un-rotated earlier columns
+// (block_second_kernel).  Scalars of a block, d_sc: [0,16) G, [16,32) C, [32,48) U[l,i] = C[l].G[:,i] = <q_l, p_i'> (l < i),
+// each 4 x 4 row-major.
+constexpr int SC_G = 0, SC_C = 16, SC_U = 32;
+constexpr int CTB = 64;  // columns per workgroup of the block dots: one tile up to 64 columns, the S vectors are then read once
+// double2 slots per thread of the dots (R) and of the update (U), from the compiler's resource report for gfx950 and bench runs at
+// M = 119.  Dots, S = 4: R = 2 takes 74 VGPRs (6 waves per SIMD), R = 3 100 and R = 4 126 (4 waves); in
+// one job that ran the variants side by side the step time was the same for R = 2, 3, 4 and 0.3 ms longer for R = 1.  Update,
+// S = 4: U = 2 takes 122 VGPRs (4 waves, four columns in flight per wave), U = 1 78 (6 waves) and, likewise side by side, a
+// step 0.9 ms longer; S = 3: 102 VGPRs at U = 2.
+template <int S> struct BlockShape;
+template <> struct BlockShape<3> { static constexpr int R = 2, U = 2; };
+template <> struct BlockShape<4> { static constexpr int R = 2, U = 2; };
+
+// block-wide sums of S values with the barriers of one; same order as block_sum_256, results valid in thread 0
+template <int S>
+__device__ __forceinline__ void block_sumN_256(double (&v)[S], double* lds) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 0; i < S; ++i) {
+        v[i] = wave_sum(v[i]);
+        if (lane == 0) lds[4 * i + w] = v[i];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int i = 0; i < S; ++i) v[i] = (lds[4 * i] + lds[4 * i + 1]) + (lds[4 * i + 2] + lds[4 * i + 3]);
+    }
+    __syncthreads();
+}
+
+// Sums of four values over the wave with 7 shuffles instead of 24: the halves of the wave swap two values each (xor 32), the
+// quarters one (xor 16), then four steps inside 16 lanes.  Returns, in every lane, the wave's sum of v[lane >> 4]; fixed order.
+__device__ __forceinline__ double wave_sum4(const double (&v)[4], int lane) {
+    const bool hi = lane & 32;
+    double k0 = hi ? v[2] : v[0], k1 = hi ? v[3] : v[1];
+    const double s0 = hi ? v[0] : v[2], s1 = hi ? v[1] : v[3];
+    k0 += __shfl_xor(s0, 32, WAVE);
+    k1 += __shfl_xor(s1, 32, WAVE);
+    const bool q = lane & 16;
+    double k = q ? k1 : k0;
+    const double s = q ? k0 : k1;
+    k += __shfl_xor(s, 16, WAVE);
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) k += __shfl_xor(k, off, WAVE);
+    return k;
+}
+
+// as cgs_dots2_stage1 with S vectors in registers: part[(i ncol + col) nrb + rb] of vector i; a row block rb is 512 R rows.
+// The column loop holds no barrier: every wave leaves its S sums of a column in LDS (wave_sum4) and goes on to the next column,
+// so the loads of several columns are in flight; one barrier after the tile, then one thread per (column, vector) adds the four
+// waves in the order of block_sum_256.  (With a block sum per column, as the pair has it, the S x 12 shuffles and the two
+// barriers of every column cost more than its loads at S = 4: 0.337 ms per launch at M = 119 against 0.217 ms now.)
+// A workgroup takes a tile of up to CTB = 64 columns (one thread per (column, vector) in the last step): with 8-column tiles the S
+// vectors were read once per tile, 120 column-lengths per solve at M = 119 instead of 40, and those re-reads reached the HBM
+// (0.262 ms per launch).
+// One-dimensional grid, the column tile running fastest: beyond 64 columns the workgroups that read the same rows of the S
+// vectors are dispatched together.
+template <int S, int R>
+__global__ __launch_bounds__(BLK) void cgs_dots_block_stage1(I n, I ncol, const T* __restrict__ Q, long long ldq,
+                                                            const T* __restrict__ w, long long ldw, T* __restrict__ part, int nrb,
+                                                            int ntile) {
+    __shared__ double lds[CTB * 4 * 4];  // [column of the tile][vector][wave]: 8 KB
+    const int rb = blockIdx.x / ntile;
+    const long long r0 = (long long)rb * (BLK * R * 2);
+    const int c0 = (blockIdx.x - rb * ntile) * CTB;
+    const int nc = (ncol - c0 < CTB) ? (ncol - c0) : CTB;  // columns of this tile
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    double2 u[S][R];
+    long long row[R];
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+        row[i] = r0 + 2LL * threadIdx.x + (long long)i * (2 * BLK);
+#pragma unroll
+        for (int a = 0; a < S; ++a) {
+            const T* wa = w + a * ldw;
+            if (row[i] + 1 < n) u[a][i] = *reinterpret_cast<const double2*>(wa + row[i]);
+            else { u[a][i].x = (row[i] < n) ? wa[row[i]] : 0.0; u[a][i].y = 0.0; }
+        }
+    }
+    auto load = [&](int c, double2(&qv)[R]) {
+        const T* q = Q + (long long)(c0 + c) * ldq;
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            if (row[i] + 1 < n) qv[i] = ld_stream(q + row[i]);
+            else { qv[i].x = (row[i] < n) ? q[row[i]] : 0.0; qv[i].y = 0.0; }
+        }
+    };
+    auto reduce = [&](int c, const double2(&qv)[R]) {
+        double acc[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int i = 0; i < R; ++i)
+#pragma unroll
+            for (int a = 0; a < S; ++a) acc[a] += qv[i].x * u[a][i].x + qv[i].y * u[a][i].y;
+        const double r = wave_sum4(acc, lane);
+        if ((lane & 15) == 0) lds[(c * 4 + (lane >> 4)) * 4 + wv] = r;
+    };
+    int c = 0;
+    for (; c + 1 < nc; c += 2) {  // two columns per trip: the loads of both are issued before the first is reduced
+        double2 qa[R], qb[R];
+        load(c, qa);
+        load(c + 1, qb);
+        reduce(c, qa);
+        reduce(c + 1, qb);
+    }
+    if (c < nc) {
+        double2 qa[R];
+        load(c, qa);
+        reduce(c, qa);
+    }
+    __syncthreads();
+    const int tc = threadIdx.x >> 2, ta = threadIdx.x & 3;
+    if (tc < nc && ta < S) {
+        const double* l = lds + (tc * 4 + ta) * 4;
+        part[((long long)ta * ncol + c0 + tc) * nrb + rb] = (l[0] + l[1]) + (l[2] + l[3]);
+    }
+}
+
+// grid (ncol, S), the order of cgs_dots_raw_stage2: e_i[j] = <r_j, p_i> / nu_j at d_e[i lde + j], c_i = e_i / nu at d_c[i lde + j];
+// e_0 is also column k of H and of its un-rotated copy (d_h, d_h_raw)
+__global__ __launch_bounds__(BLK) void cgs_dots_block_stage2(int nrb, I ncol, const T* part, const T* __restrict__ nu, T* d_h,
+                                                            T* d_h_raw, T* d_e, T* d_c, I lde) {
+    __shared__ double lds[4];
+    const int j = blockIdx.x, i = blockIdx.y;
+    const T* p = part + ((long long)i * ncol + j) * nrb;
+    double acc = 0.0;
+    for (int t = threadIdx.x; t < nrb; t += BLK) acc += p[t];
+    const double r = block_sum_256(acc, lds);
+    if (threadIdx.x == 0) {
+        const double v = nu[j], h = r / v;
+        d_e[(long long)i * lde + j] = h;
+        d_c[(long long)i * lde + j] = h / v;
+        if (i == 0) {
+            d_h[j] = h;
+            if (d_h_raw) d_h_raw[j] = h;
+        }
+    }
+}
+
+// p_i -= Q c_i for the S vectors in one pass, streamed as cgs_update2_kernel streams; partials of G_ab = <p_a', p_b'>, a <= b
+// in row-major order of the upper triangle, at part[g gridDim.x + blk]
+template <int S, int U>
+__global__ __launch_bounds__(BLK) void cgs_update_block_kernel(I n, I ncol, const T* __restrict__ Q, long long ldq,
+                                                              const T* __restrict__ d_c, I lde, T* __restrict__ w, long long ldw,
+                                                              T* __restrict__ part) {
+    constexpr int NG = S * (S + 1) / 2;
+    __shared__ double lds[4 * NG];
+    __shared__ double sh[S][128];
+    for (int j = threadIdx.x; j < ncol && j < 128; j += BLK) {
+#pragma unroll
+        for (int a = 0; a < S; ++a) sh[a][j] = d_c[(long long)a * lde + j];
+    }
+    __syncthreads();
+    const long long blk = blockIdx.x;
+    const long long r0 = blk * (BLK * U * 2);
+    long long row[U];
+    double2 v[S][U];
+#pragma unroll
+    for (int i = 0; i < U; ++i) {
+        row[i] = r0 + 2LL * threadIdx.x + (long long)i * (2 * BLK);
+#pragma unroll
+        for (int a = 0; a < S; ++a) {
+            const T* wa = w + a * ldw;
+            if (row[i] + 1 < n) v[a][i] = *reinterpret_cast<const double2*>(wa + row[i]);
+            else { v[a][i].x = (row[i] < n) ? wa[row[i]] : 0.0; v[a][i].y = 0.0; }
+        }
+    }
+#pragma unroll 4
+    for (int j = 0; j < ncol; ++j) {
+        double h[S];
+#pragma unroll
+        for (int a = 0; a < S; ++a) h[a] = (j < 128) ? sh[a][j] : d_c[(long long)a * lde + j];
+        const T* q = Q + (long long)j * ldq;
+#pragma unroll
+        for (int i = 0; i < U; ++i) {
+            double2 qv;
+            if (row[i] + 1 < n) qv = ld_stream(q + row[i]);
+            else { qv.x = (row[i] < n) ? q[row[i]] : 0.0; qv.y = 0.0; }
+#pragma unroll
+            for (int a = 0; a < S; ++a) { v[a][i].x -= qv.x * h[a]; v[a][i].y -= qv.y * h[a]; }
+        }
+    }
+    double g[NG];
+#pragma unroll
+    for (int t = 0; t < NG; ++t) g[t] = 0.0;
+#pragma unroll
+    for (int i = 0; i < U; ++i) {
+#pragma unroll
+        for (int a = 0; a < S; ++a) {
+            T* wa = w + a * ldw;
+            if (row[i] + 1 < n) *reinterpret_cast<double2*>(wa + row[i]) = v[a][i];
+            else if (row[i] < n) wa[row[i]] = v[a][i].x;
+        }
+        int t = 0;
+#pragma unroll
+        for (int a = 0; a < S; ++a)
+#pragma unroll
+            for (int b = a; b < S; ++b, ++t) g[t] += v[a][i].x * v[b][i].x + v[a][i].y * v[b][i].y;
+    }
+    block_sumN_256<NG>(g, lds);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int t = 0; t < NG; ++t) part[(long long)t * gridDim.x + blk] = g[t];
+    }
+}
+
+// The scalars of a block after the S-vector update, one workgroup: second stage of G (fixed order), nu[k+1] = sqrt(G_00) below
+// e_0 in column k of H and of its un-rotated copy, the Givens step of that column; C by Gram-Schmidt on G: row i starts as the
+// unit vector, then for l < i: C[i] -= (C[l].G[:,i] / C[l].G.C[l]) C[l]  (S = 2: C[1,0] = -s12 / s11, the pair's coefficient)
+template <int S>
+__global__ __launch_bounds__(BLK) void block_first_kernel(int npart, const T* part, I k, T* nu, T* H, T* Hraw, I ldh, T* gv, T* beta,
+                                                         T* res_hist, T* sc) {
+    constexpr int NG = S * (S + 1) / 2;
+    __shared__ double lds[4 * NG];
+    __shared__ double s_nrm;
+    __shared__ double s_col[GIV_MAX], s_gv[2 * GIV_MAX];
+    double g[NG];
+#pragma unroll
+    for (int t = 0; t < NG; ++t) g[t] = 0.0;
+#pragma unroll 2
+    for (int i = threadIdx.x; i < npart; i += BLK) {  // (the NG loads of a trip are independent: one latency per trip, not per load)
+#pragma unroll
+        for (int t = 0; t < NG; ++t) g[t] += part[(long long)t * npart + i];
+    }
+    block_sumN_256<NG>(g, lds);
+    if (threadIdx.x == 0) {
+        double G[4][4], Cm[4][4], Um[4][4], d[4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) { G[a][b] = 0.0; Cm[a][b] = (a == b) ? 1.0 : 0.0; Um[a][b] = 0.0; }
+        int t = 0;
+#pragma unroll
+        for (int a = 0; a < S; ++a)
+#pragma unroll
+            for (int b = a; b < S; ++b, ++t) { G[a][b] = g[t]; G[b][a] = g[t]; }
+#pragma unroll
+        for (int i = 0; i < S; ++i) {
+#pragma unroll
+            for (int l = 0; l < i; ++l) {
+                double u = 0.0;
+#pragma unroll
+                for (int m = 0; m <= l; ++m) u += Cm[l][m] * G[m][i];
+                Um[l][i] = u;
+                const double f = u / d[l];
+#pragma unroll
+                for (int m = 0; m <= l; ++m) Cm[i][m] -= f * Cm[l][m];
+            }
+            double dd = 0.0;  // C[i].G.C[i] = ||q_i||^2 as G has it
+#pragma unroll
+            for (int a = 0; a <= i; ++a) {
+                double r = 0.0;
+#pragma unroll
+                for (int b = 0; b <= i; ++b) r += G[a][b] * Cm[i][b];
+                dd += Cm[i][a] * r;
+            }
+            d[i] = dd;
+        }
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                sc[SC_G + 4 * a + b] = G[a][b];
+                sc[SC_C + 4 * a + b] = Cm[a][b];
+                sc[SC_U + 4 * a + b] = Um[a][b];
+            }
+        const double nu1 = sqrt(G[0][0]);
+        nu[k + 1] = nu1;
+        Hraw[(long long)k * ldh + k + 1] = nu1;
+        s_nrm = nu1;
+    }
+    __syncthreads();
+    givens_step_block(k, s_nrm, H, ldh, gv, beta, res_hist, s_col, s_gv);
+}
+
+// q_i = sum_{l <= i} C[i,l] p_l' for i = 1..S-1, in place (p_0' = q_0 stays), one pass over the S columns: a workgroup owns 256
+// nodes as in cgs_update_jacobi_kernel (same slots, same vec_ok rule); partials of ||q_i||^2 at part[(i-1) gridDim.x + blk];
+// Z4: z4[node] = M^-1 q_{S-1}[node] from the registers through the LDS regroup of cgs_update_jacobi_kernel
+template <int S, bool Z4>
+__global__ __launch_bounds__(BLK) void cgs_fixup_block_kernel(I N, T* __restrict__ w, long long ldw, const T* __restrict__ sc,
+                                                             T* __restrict__ part, const T* __restrict__ dinv33,
+                                                             const T* __restrict__ dinv1, T* __restrict__ z4, int vec_ok) {
+    __shared__ double lds[4 * (S - 1)];
+    __shared__ double2 sm[Z4 ? BLK * UPT : 1];  // q_{S-1} of the block: [0, 768) u, [768, 1024) p
+    double Cm[S][S];
+#pragma unroll
+    for (int a = 1; a < S; ++a)
+#pragma unroll
+        for (int l = 0; l < a; ++l) Cm[a][l] = sc[SC_C + 4 * a + l];
+    const long long blk = blockIdx.x;
+    const long long a0 = blk * BLK;
+    const long long nb = (N - a0 < BLK) ? (N - a0) : BLK;  // nodes of this block
+    double ss[S - 1];
+#pragma unroll
+    for (int a = 0; a < S - 1; ++a) ss[a] = 0.0;
+#pragma unroll
+    for (int i = 0; i < UPT; ++i) {
+        const int slot = threadIdx.x + i * BLK;  // slots [0, 384): u rows, [384, 512): p rows
+        long long row, lim;
+        if (slot < 384) { row = 3 * a0 + 2LL * slot; lim = 3 * (a0 + nb); }
+        else { row = 3LL * N + a0 + 2LL * (slot - 384); lim = 3LL * N + a0 + nb; }
+        const bool vec = vec_ok && row + 1 < lim && !(row & 1);
+        double2 p[S];
+#pragma unroll
+        for (int a = 0; a < S; ++a) {
+            const T* wa = w + a * ldw;
+            if (vec) p[a] = *reinterpret_cast<const double2*>(wa + row);
+            else { p[a].x = (row < lim) ? wa[row] : 0.0; p[a].y = (row + 1 < lim) ? wa[row + 1] : 0.0; }
+        }
+#pragma unroll
+        for (int a = S - 1; a >= 1; --a) {  // descending: q_a needs p_l', l < a, as they were
+#pragma unroll
+            for (int l = 0; l < a; ++l) { p[a].x += Cm[a][l] * p[l].x; p[a].y += Cm[a][l] * p[l].y; }
+            T* wa = w + a * ldw;
+            if (vec) *reinterpret_cast<double2*>(wa + row) = p[a];
+            else {
+                if (row < lim) wa[row] = p[a].x;
+                if (row + 1 < lim) wa[row + 1] = p[a].y;
+            }
+            ss[a - 1] += p[a].x * p[a].x + p[a].y * p[a].y;
+        }
+        if (Z4) sm[slot] = p[S - 1];
+    }
+    block_sumN_256<S - 1>(ss, lds);  // (its barriers also publish sm)
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int a = 0; a < S - 1; ++a) part[(long long)a * gridDim.x + blk] = ss[a];
+    }
+    if (Z4) {
+        const double* s = reinterpret_cast<const double*>(sm);
+        const int t = threadIdx.x;
+        if (t < nb) {
+            const long long i = a0 + t;
+            const T* A = dinv33 + i * 9;  // column-major image, as pc_apply_kernel (Q7)
+            const double x0 = s[3 * t], x1 = s[3 * t + 1], x2 = s[3 * t + 2], xp = s[768 + t];
+            const double y0 = A[0] * x0 + A[3] * x1 + A[6] * x2, y1 = A[1] * x0 + A[4] * x1 + A[7] * x2;
+            const double y2 = A[2] * x0 + A[5] * x1 + A[8] * x2, yp = xp * dinv1[i];
+            double2* o = reinterpret_cast<double2*>(z4 + 4 * i);
+            o[0] = make_double2(y0, y1);
+            o[1] = make_double2(y2, yp);
+        }
+    }
+}
+
+// The scalars of a block after the fix-up, one workgroup: nu[k+1+i] = ||q_i|| (i >= 1) from the fix-up's partials, measured and
+// not derived from G; *d_flag is raised when one of them is below 1e-4 sqrt(G_ii).  rho_i, the coordinates of p_i in v_0..v_{k+1+i}:
+// e_i in rows 0..k, U[l,i] / nu[k+1+l] in row k+1+l (l < i), nu[k+1+i] in row k+1+i.  p_i = B p_{i-1} and B v_j = Hraw[:,j] give
+//   H[:, k+i] = (rho_i - sum_{j < k+i} Hraw[:,j] rho_{i-1}[j]) / nu[k+i],   j ascending, from max(row - 1, 0) (Hessenberg zeros)
+// into H and its un-rotated copy, each column followed by its Givens step; S = 2 is pair_second_kernel term for term
+template <int S>
+__global__ __launch_bounds__(BLK) void block_second_kernel(int npart, const T* part, I k, T* nu, T* H, T* Hraw, I ldh,
+                                                          const T* __restrict__ d_e, I lde, const T* __restrict__ sc, T* gv, T* beta,
+                                                          T* res_hist, int* d_flag) {
+    __shared__ double lds[4 * (S - 1)];
+    __shared__ double s_nu[S + 1];   // nu[k .. k+S]
+    __shared__ double s_t[S][S];     // s_t[l][i] = U[l,i] / nu[k+1+l]
+    __shared__ double s_nrm;
+    __shared__ double s_col[GIV_MAX], s_gv[2 * GIV_MAX];
+    double qq[S - 1];
+#pragma unroll
+    for (int a = 0; a < S - 1; ++a) qq[a] = 0.0;
+#pragma unroll 4
+    for (int i = threadIdx.x; i < npart; i += BLK) {
+#pragma unroll
+        for (int a = 0; a < S - 1; ++a) qq[a] += part[(long long)a * npart + i];
+    }
+    block_sumN_256<S - 1>(qq, lds);
+    if (threadIdx.x == 0) {
+        s_nu[0] = nu[k];
+        s_nu[1] = nu[k + 1];
+        bool low = false;
+#pragma unroll
+        for (int i = 1; i < S; ++i) {
+            const double v = sqrt(qq[i - 1]);
+            nu[k + 1 + i] = v;
+            s_nu[1 + i] = v;
+            low = low || v < 1e-4 * sqrt(sc[SC_G + 5 * i]);
+        }
+        if (d_flag && low) *d_flag = 1;
+        for (int l = 0; l < S; ++l)
+            for (int i = 0; i < S; ++i) s_t[l][i] = (l < i) ? sc[SC_U + 4 * l + i] / s_nu[1 + l] : 0.0;
+    }
+    __syncthreads();
+    for (int i = 1; i < S; ++i) {
+        const I c = k + i;  // the column; rows 0..c+1
+        T* col = H + (long long)c * ldh;
+        T* raw = Hraw + (long long)c * ldh;
+        const T* ei = d_e + (long long)i * lde;
+        const T* ep = d_e + (long long)(i - 1) * lde;
+        const double den = s_nu[i];  // rho_{i-1}[k+i] = nu[k+i]
+        for (int r = threadIdx.x; r <= c + 1; r += BLK) {
+            double t;
+            if (r <= k) t = ei[r];
+            else if (r - k - 1 < i) t = s_t[r - k - 1][i];
+            else t = s_nu[1 + i];
+            for (int j = (r > 0 ? r - 1 : 0); j < c; ++j) {
+                const double rp = (j <= k) ? ep[j] : s_t[j - k - 1][i - 1];  // rho_{i-1}[j], j < k+i
+                t -= rp * Hraw[(long long)j * ldh + r];
+            }
+            const double v = t / den;
+            raw[r] = v;
+            if (r <= c) col[r] = v;
+            else s_nrm = v;
+        }
+        __syncthreads();
+        givens_step_block(c, s_nrm, H, ldh, gv, beta, res_hist, s_col, s_gv);
+        __syncthreads();
+    }
+}
+
 // H[0:m,0:m] y = beta by back substitution (cublasDtrsv, krylov.c:297-301), one workgroup: column-oriented so that every
 // step is one coalesced column update (a single thread walking rows pays a dependent global load per entry: 85 us at m = 40)
 template <bool STAGED>
@@ -857,6 +1272,24 @@ __global__ __launch_bounds__(BLK) void norms4_stage2(int nblk, const T* __restri
     if (threadIdx.x == 0) out[blockIdx.x] = SQRT ? sqrt(r) : r;
 }
 
+// host launchers of the block kernels (templates: outside extern "C")
+template <int NS>
+void launch_dots_block(I n, I ncol, const T* Q, int64_t ldq, const T* w, int64_t ldw, const T* d_nu, T* d_h, T* d_h_raw,
+                              T* d_e, T* d_c, I lde, T* work, void* stream) {
+    const int nrb = ceil_div(n, BLK * BlockShape<NS>::R * 2);
+    const int ntile = ceil_div(ncol, CTB);
+    if ((long long)nrb * ntile > 0x7fffffffLL) abort();
+    cgs_dots_block_stage1<NS, BlockShape<NS>::R><<<nrb * ntile, BLK, 0, S(stream)>>>(n, ncol, Q, ldq, w, ldw, work, nrb, ntile);
+    cgs_dots_block_stage2<<<dim3(ncol, NS), BLK, 0, S(stream)>>>(nrb, ncol, work, d_nu, d_h, d_h_raw, d_e, d_c, lde);
+}
+template <int NS>
+void launch_fixup_block(I N, T* w, int64_t ldw, const T* d_sc, const T* dinv33, const T* dinv1, T* z4, T* work, void* stream) {
+    const int g = ceil_div(N, BLK);
+    const int vec_ok = aligned16(w) && !(ldw & 1);
+    if (z4) cgs_fixup_block_kernel<NS, true><<<g, BLK, 0, S(stream)>>>(N, w, ldw, d_sc, work, dinv33, dinv1, z4, vec_ok);
+    else cgs_fixup_block_kernel<NS, false><<<g, BLK, 0, S(stream)>>>(N, w, ldw, d_sc, work, nullptr, nullptr, nullptr, vec_ok);
+}
+
 }  // namespace
 
 extern "C" {
@@ -961,6 +1394,12 @@ int64_t dfl_cgs_work_size(I n, I ncol) {
     int64_t nrb = ceil_div(n, ROWS_PER_BLOCK);
     int64_t a = 2 * nrb * (int64_t)(ncol > 0 ? ncol : 1);  // two vectors per dots pass (dfl_cgs_dots2_raw)
     int64_t b = 3 * (int64_t)ceil_div(n, UROWS);           // s11, s12, s22 of dfl_cgs_update2
+    for (int s = 3; s <= 4; ++s) {                         // blocks of s products: s sets of dots partials, s (s + 1) / 2 of G
+        const int64_t as = (int64_t)s * dfl_cgs_dots_block_parts(n, s) * (int64_t)(ncol > 0 ? ncol : 1);
+        const int64_t bs = (int64_t)(s * (s + 1) / 2) * dfl_cgs_update_block_parts(n, s);
+        if (as > a) a = as;
+        if (bs > b) b = bs;
+    }
     return (a > b ? a : b) + 16;
 }
 void dfl_cgs_dots(I n, I ncol, const T* Q, int64_t ldq, const T* w, T* d_h, T* work, void* stream) {
@@ -1049,6 +1488,59 @@ void dfl_gmres_pair_second(int npart, const T* part, I k, T* d_nu, T* d_H, T* d_
     DFL_LAUNCH_CHECK();
 }
 int dfl_cgs_update2_parts(I n) { return ceil_div(n, UROWS); }
+// blocks of s = 3 or 4 products: any other s is an error (s = 2 is the pair above, s = 1 the single step)
+int dfl_cgs_dots_block_parts(I n, int s) {
+    if (s == 3) return ceil_div(n, BLK * BlockShape<3>::R * 2);
+    if (s == 4) return ceil_div(n, BLK * BlockShape<4>::R * 2);
+    abort();
+}
+int dfl_cgs_update_block_parts(I n, int s) {
+    if (s == 3) return ceil_div(n, BLK * BlockShape<3>::U * 2);
+    if (s == 4) return ceil_div(n, BLK * BlockShape<4>::U * 2);
+    abort();
+}
+void dfl_cgs_dots_block(I n, I ncol, int s, const T* Q, int64_t ldq, const T* w, int64_t ldw, const T* d_nu, T* d_h, T* d_h_raw,
+                        T* d_e, T* d_c, I lde, T* work, void* stream) {
+    if (ncol <= 0 || n <= 0) return;
+    if (s == 3) launch_dots_block<3>(n, ncol, Q, ldq, w, ldw, d_nu, d_h, d_h_raw, d_e, d_c, lde, work, stream);
+    else if (s == 4) launch_dots_block<4>(n, ncol, Q, ldq, w, ldw, d_nu, d_h, d_h_raw, d_e, d_c, lde, work, stream);
+    else abort();
+    DFL_LAUNCH_CHECK();
+}
+void dfl_cgs_update_block(I n, I ncol, int s, const T* Q, int64_t ldq, const T* d_c, I lde, T* w, int64_t ldw, T* work,
+                          void* stream) {
+    if (n <= 0) return;
+    const int g = dfl_cgs_update_block_parts(n, s);
+    if (s == 3) cgs_update_block_kernel<3, BlockShape<3>::U><<<g, BLK, 0, S(stream)>>>(n, ncol, Q, ldq, d_c, lde, w, ldw, work);
+    else cgs_update_block_kernel<4, BlockShape<4>::U><<<g, BLK, 0, S(stream)>>>(n, ncol, Q, ldq, d_c, lde, w, ldw, work);
+    DFL_LAUNCH_CHECK();
+}
+void dfl_gmres_block_first(int npart, const T* part, int s, I k, T* d_nu, T* d_H, T* d_Hraw, I ldh, T* d_gv, T* d_beta,
+                           T* d_res_hist, T* d_sc, void* stream) {
+    if (s == 3) block_first_kernel<3><<<1, BLK, 0, S(stream)>>>(npart, part, k, d_nu, d_H, d_Hraw, ldh, d_gv, d_beta, d_res_hist, d_sc);
+    else if (s == 4) block_first_kernel<4><<<1, BLK, 0, S(stream)>>>(npart, part, k, d_nu, d_H, d_Hraw, ldh, d_gv, d_beta, d_res_hist, d_sc);
+    else abort();
+    DFL_LAUNCH_CHECK();
+}
+void dfl_cgs_fixup_block(I N, int s, T* w, int64_t ldw, const T* d_sc, const T* dinv33, const T* dinv1, T* z4, T* work,
+                         void* stream) {
+    if (N <= 0) return;
+    if (s == 3) launch_fixup_block<3>(N, w, ldw, d_sc, dinv33, dinv1, z4, work, stream);
+    else if (s == 4) launch_fixup_block<4>(N, w, ldw, d_sc, dinv33, dinv1, z4, work, stream);
+    else abort();
+    DFL_LAUNCH_CHECK();
+}
+void dfl_gmres_block_second(int npart, const T* part, int s, I k, T* d_nu, T* d_H, T* d_Hraw, I ldh, const T* d_e, I lde,
+                            const T* d_sc, T* d_gv, T* d_beta, T* d_res_hist, int* d_flag, void* stream) {
+    if (s == 3)
+        block_second_kernel<3><<<1, BLK, 0, S(stream)>>>(npart, part, k, d_nu, d_H, d_Hraw, ldh, d_e, lde, d_sc, d_gv, d_beta, d_res_hist,
+                                                         d_flag);
+    else if (s == 4)
+        block_second_kernel<4><<<1, BLK, 0, S(stream)>>>(npart, part, k, d_nu, d_H, d_Hraw, ldh, d_e, lde, d_sc, d_gv, d_beta, d_res_hist,
+                                                         d_flag);
+    else abort();
+    DFL_LAUNCH_CHECK();
+}
 void dfl_gmres_scale_inv(I m, const T* d_nu, T* d_y, void* stream) {
     if (m <= 0) return;
     scale_inv_vec_kernel<<<ceil_div(m, BLK), BLK, 0, S(stream)>>>(m, d_nu, d_y);

@@ -6,8 +6,8 @@
  *   - the two cublasDgemv + Dnrm2 + Dscal of an Arnoldi step are two fused passes (dfl_cgs_dots / dfl_cgs_update) and the
  *     normalisation is folded into the next preconditioner application -- or, one GPU with the Jacobi tree, never done:
  *     the basis stays unnormalised, the update applies M^-1 to the column it forms and the matvec divides by the norm
- *     (GMRES_STEP_RAW_BASIS); that step takes two products before it orthogonalises, so that one dots pass and one update
- *     pass over the basis serve two iterations (gmres_pair);
+ *     (GMRES_STEP_RAW_BASIS); that step takes up to four products before it orthogonalises, so that one dots pass and one
+ *     update pass over the basis serve up to four iterations (gmres_pair, gmres_block);
  *   - every scalar recurrence stays on the device; the host reads 8 bytes only when the reference tests convergence (every
  *     20th iteration) -- the reference syncs 2-3 times per iteration;
  *   - work space is cached in the Krylov object instead of malloc+memset per solve;
@@ -89,7 +89,7 @@ void DflWsEnsure(KrylovExt* x, index_type n, index_type maxit, index_type ldh, i
     HIPGUARD(hipMemsetAsync(x->d_flag, 0, 16, DflStream()));
     x->hraw = (f64*)CdamMallocDevice((ptrdiff_t)(ldh + 32) * SIZE_OF(f64));
     x->h_unrot = (f64*)CdamMallocDevice((ptrdiff_t)ldh * maxit * SIZE_OF(f64));
-    x->pair_buf = (f64*)CdamMallocDevice(4 * (ptrdiff_t)ldh * SIZE_OF(f64));
+    x->pair_buf = (f64*)CdamMallocDevice((8 * (ptrdiff_t)ldh + 64) * SIZE_OF(f64));
     x->ws_n = n; x->ws_maxit = maxit; x->ws_fresh = TRUE;
 }
 
@@ -181,8 +181,9 @@ void DflPcApplyFused(PC* pc, index_type na, f64* w, const f64* d_nrm, f64* z) { 
    reference-layout gathers, A/B), DFL_SPMV_X4_MIN (smallest matrix, in nodes, that takes the interleaved path; tests set 1).
    Read at every solve (A/B): eager host reads, boundary rows on the library stream, three launches per fused-norm step,
    DFL_GMRES_RAW_BASIS=0 (one GPU: the normalised basis and the separate Jacobi pass instead of GMRES_STEP_RAW_BASIS),
-   DFL_GMRES_TWO_STEP=0 (the raw-basis step one iteration at a time) */
-typedef struct GmresEnv { b32 x4; index_type x4_min; b32 eager_sync, no_side_rows, no_fused_update_pc, raw_basis, two_step; } GmresEnv;
+   DFL_GMRES_BLOCK=1..4 (the most iterations the raw-basis step takes per pass over the basis, default 4), DFL_GMRES_TWO_STEP=0
+   (the same as block 1: one iteration at a time) */
+typedef struct GmresEnv { b32 x4; index_type x4_min; b32 eager_sync, no_side_rows, no_fused_update_pc, raw_basis; int block; } GmresEnv;
 static GmresEnv gmres_env(void) {
     static int x4 = -1, x4_min = 4096;
     if (x4 < 0) {
@@ -190,9 +191,24 @@ static GmresEnv gmres_env(void) {
         if (min) x4_min = atoi(min);
         x4 = !(off && atoi(off) == 0);
     }
-    const char *raw = getenv("DFL_GMRES_RAW_BASIS"), *two = getenv("DFL_GMRES_TWO_STEP");
+    const char *raw = getenv("DFL_GMRES_RAW_BASIS"), *two = getenv("DFL_GMRES_TWO_STEP"), *blk = getenv("DFL_GMRES_BLOCK");
+    int block = 4;
+    if (blk) {
+        /* a value that is no number from 1 to 4 is clamped into that range (no number at all: the default) and named once, so
+           that an A/B run with a typo does not measure something else unnoticed */
+        static b32 warned = FALSE;
+        char* end = NULL;
+        const long v = strtol(blk, &end, 10);
+        const b32 number = end != blk && *end == '\0';
+        block = !number ? 4 : v < 1 ? 1 : v > 4 ? 4 : (int)v;
+        if ((!number || v != block) && !warned) {
+            fprintf(stderr, "[krylov] DFL_GMRES_BLOCK=%s is not one of 1, 2, 3, 4: using %d\n", blk, block);
+            warned = TRUE;
+        }
+    }
+    if (two && atoi(two) == 0) block = 1;
     const GmresEnv e = {x4, x4_min, getenv("DFL_KRYLOV_EAGER_SYNC") != NULL, getenv("DFL_NO_SIDE_BOUNDARY_ROWS") != NULL,
-                        getenv("DFL_NO_FUSED_UPDATE_PC") != NULL, !(raw && atoi(raw) == 0), !(two && atoi(two) == 0)};
+                        getenv("DFL_NO_FUSED_UPDATE_PC") != NULL, !(raw && atoi(raw) == 0), block};
     return e;
 }
 
@@ -246,7 +262,7 @@ void DflGmresPlanFill(GmresPlan* p, const KrylovExt* ex, index_type max_iter, Ma
        reads and the check interval have no say here: the arithmetic of a solve does not depend on them */
     if (p->step == GMRES_STEP_REFERENCE && p->x4_skip_z && p->rows == p->N && env.raw_basis) {
         p->step = GMRES_STEP_RAW_BASIS;
-        p->pair = env.two_step;
+        p->block = env.block;
     }
 }
 
@@ -264,6 +280,11 @@ static void gmres_apply_operator(const GmresPlan* p, KrylovExt* ex, Matrix* A, P
     const DflComm* c = &ex->comm;
     hipStream_t s = DflStream();
     b32 wrote = FALSE;
+    /* the block-mode matrix stores the (u,p) rows only and its matvec writes nothing beyond them.  With a non-zero phi / T tail of
+       b the vectors cover [0, 6N): rows [4N, na) of A z are the zero of the reference's empty blocks, not what an earlier solve
+       or restart cycle left in this column (a second solve on the same Krylov object gave another history before this) */
+    const index_type up_rows = MatrixFSBlockValues(A) ? 4 * ((MatrixFS*)A->data)->spy1x1->num_row : p->na;
+    if (p->na > up_rows) HIPGUARD(hipMemsetAsync(y + up_rows, 0, (size_t)(p->na - up_rows) * sizeof(f64), s));
     if (p->step == GMRES_STEP_RAW_BASIS) {
         /* q = r_k is left as it is; z4 = M^-1 r_k (column 0: made here; later columns: the update kernel has left it),
            y = (A z4) / nrm[k] */
@@ -366,11 +387,11 @@ static void gmres_orthogonalise(const GmresPlan* p, KrylovExt* ex, index_type it
     case GMRES_STEP_RAW_BASIS:
         /* columns 0..iter are r_j = nrm[j] q_j: h_j = <r_j, w> / nrm[j] into H, hraw[j] = h_j / nrm[j] multiplies r_j */
         DFL_TIMED(DFL_TAG_CGS_DOTS, dfl_cgs_dots_raw(na, iter + 1, Q, na, w, ex->nrm, h, ex->hraw, ex->work, s));
-        /* (paired solves: a later pair reads this column un-rotated) */
+        /* (solves with pairs or blocks: a later one reads this column un-rotated) */
         DFL_TIMED(DFL_TAG_CGS_UPDATE,
                   dfl_cgs_update_jacobi_givens_keep(p->N, iter + 1, Q, na, ex->hraw, w, p->d33, p->d1, last ? NULL : p->z4, nrm,
                                                     ex->work, iter, H, ldh, ex->gv, ex->beta, res_hist,
-                                                    p->pair ? ex->h_unrot + (size_t)iter * (size_t)ldh : NULL, s));
+                                                    p->block > 1 ? ex->h_unrot + (size_t)iter * (size_t)ldh : NULL, s));
         break;
     case GMRES_STEP_REFERENCE:
         DFL_TIMED(DFL_TAG_CGS_DOTS, dfl_cgs_dots(na, iter + 1, Q, na, w, h, ex->work, s));
@@ -380,7 +401,7 @@ static void gmres_orthogonalise(const GmresPlan* p, KrylovExt* ex, index_type it
     }
 }
 
-/* Iterations k and k+1 of a cycle in one pass over the basis (GmresPlan.pair).  At entry column k holds r_k and, k > 0, z4 holds
+/* Iterations k and k+1 of a cycle in one pass over the basis (GmresPlan.block >= 2).  At entry column k holds r_k and, k > 0, z4 holds
    M^-1 r_k.  p1 = B v_k = (A z4) / nrm[k] into column k+1, z4 = M^-1 p1, p2 = B p1 = A z4 into column k+2 -- in exact arithmetic
    the component of p2 orthogonal to v_0..v_{k+1} is a multiple of v_{k+2}, because B v_j lies in span(v_0..v_{j+1}).  One dots
    pass and one update pass over columns 0..k serve both vectors; p1' = r_{k+1}; the fix-up q = p2' - c p1' (one column) leaves
@@ -403,6 +424,33 @@ static void gmres_pair(const GmresPlan* p, KrylovExt* ex, Matrix* A, PC* pc, ind
     dfl_gmres_pair_first(g2, ex->work, k, ex->nrm, ex->H, ex->h_unrot, ldh, ex->gv, ex->beta, res_hist, sc, s);
     DFL_TIMED(DFL_TAG_CGS_UPDATE, dfl_cgs_update_jacobi(p->N, 1, p1, na, sc, p2, p->d33, p->d1, last ? NULL : p->z4, ex->work, s));
     dfl_gmres_pair_second(g1, ex->work, k, ex->nrm, ex->H, ex->h_unrot, ldh, e, sc, ex->gv, ex->beta, res_hist, ex->d_flag, s);
+}
+
+/* Iterations k..k+s-1 of a cycle, s = 3 or 4, in one pass over the basis: gmres_pair generalised.  p_0 = B v_k = (A z4) / nrm[k]
+   into column k+1, then z4 = M^-1 p_{i-1}, p_i = A z4 into column k+1+i.  One dots pass and one update pass over columns 0..k
+   serve all s vectors (dfl_cgs_dots_block, dfl_cgs_update_block); the updated p_i' span v_{k+1}..v_{k+s} and are orthogonalised
+   among themselves through their s x s Gram matrix, whose partials the update leaves: dfl_gmres_block_first forms the unit
+   triangular C, one pass over the s columns writes q_i = sum_{l<=i} C[i,l] p_l' = r_{k+1+i} in place (dfl_cgs_fixup_block) with
+   z4 = M^-1 q_{s-1} for the step that follows (last: none does), dfl_gmres_block_second measures the norms and computes columns
+   k+1..k+s-1 of H.  Nothing waits for the whole grid and no sum is taken atomically */
+static void gmres_block(const GmresPlan* p, KrylovExt* ex, Matrix* A, PC* pc, index_type k, int sb, f64* res_hist, b32 last) {
+    const index_type na = p->na, ldh = p->ldh;
+    hipStream_t s = DflStream();
+    f64 *const Q = ex->Q, *const p0 = Q + (size_t)(k + 1) * (size_t)na;
+    f64 *const c = ex->pair_buf, *const e = c + 4 * (size_t)ldh, *const sc = e + 4 * (size_t)ldh;
+    f64 *const h = ex->H + (size_t)k * (size_t)ldh, *const h_raw = ex->h_unrot + (size_t)k * (size_t)ldh;
+    const int gu = dfl_cgs_update_block_parts(na, sb), gf = (int)CEIL_DIV(p->N, 256);
+    if (k == 0) DFL_TIMED(DFL_TAG_PC, (void)DflPcApplyFusedX4(pc, na, Q, NULL, NULL, p->z4));
+    DFL_TIMED(DFL_TAG_SPMV, DflMatrixFSMatVecX4RangeScaled(A, p->z4, ex->nrm + k, p0, 0, p->x4_N));
+    for (int i = 1; i < sb; ++i) {
+        DFL_TIMED(DFL_TAG_PC, (void)DflPcApplyFusedX4(pc, na, p0 + (size_t)(i - 1) * (size_t)na, NULL, NULL, p->z4));
+        DFL_TIMED(DFL_TAG_SPMV, DflMatrixFSMatVecX4Range(A, p->z4, p0 + (size_t)i * (size_t)na, 0, p->x4_N));
+    }
+    DFL_TIMED(DFL_TAG_CGS_DOTS, dfl_cgs_dots_block(na, k + 1, sb, Q, na, p0, na, ex->nrm, h, h_raw, e, c, ldh, ex->work, s));
+    DFL_TIMED(DFL_TAG_CGS_UPDATE, dfl_cgs_update_block(na, k + 1, sb, Q, na, c, ldh, p0, na, ex->work, s));
+    dfl_gmres_block_first(gu, ex->work, sb, k, ex->nrm, ex->H, ex->h_unrot, ldh, ex->gv, ex->beta, res_hist, sc, s);
+    DFL_TIMED(DFL_TAG_CGS_UPDATE, dfl_cgs_fixup_block(p->N, sb, p0, na, sc, p->d33, p->d1, last ? NULL : p->z4, ex->work, s));
+    dfl_gmres_block_second(gf, ex->work, sb, k, ex->nrm, ex->H, ex->h_unrot, ldh, e, ldh, sc, ex->gv, ex->beta, res_hist, ex->d_flag, s);
 }
 
 /* H y = beta, x += M^-1 (Q[:,0:iter] y)   (FGMRES: x += Z[:,0:iter] y).  Column `iter` of the basis may still be
@@ -578,7 +626,8 @@ static b32 gmres_run(Matrix* A, f64* x, f64* b, Krylov* ksp, b32 force_probe) {
     GmresPlan p;
     DflGmresPlanFill(&p, ex, maxit, A, pc, na, FALSE);
     ex->last_step = (int)p.step;
-    ex->last_pairs = ex->last_singles = ex->last_pair_cancelled = 0;
+    memset(ex->last_blocks, 0, sizeof ex->last_blocks);
+    ex->last_pair_cancelled = 0;
     f64 *const Q = ex->Q, *const tmp = ex->tmp;
     b32 converged = FALSE;
     index_type total = 0; /* iterations over all cycles */
@@ -597,17 +646,21 @@ static b32 gmres_run(Matrix* A, f64* x, f64* b, Krylov* ksp, b32 force_probe) {
         /* the normalisation of Q[:,k] is folded into the preconditioner application that consumes it;
            nrm[k] holds the norm Q[:,k] still has to be divided by */
         while (!converged && iter < m && total < maxit) {
-            /* two iterations at once where both fit and no convergence check falls between them */
-            const b32 pair = p.pair && iter + 2 <= m && total + 2 <= maxit && (total + 1) % ex->check_interval != 0;
-            const index_type adv = pair ? 2 : 1;
-            if (pair) gmres_pair(&p, ex, A, pc, iter, res_hist, iter + 2 >= m || total + 2 >= maxit);
+            /* as many iterations at once as fit into the cycle and the iteration cap with no convergence check between them */
+            index_type adv = p.block > 1 ? p.block : 1;
+            if (adv > m - iter) adv = m - iter;
+            if (adv > maxit - total) adv = maxit - total;
+            if (adv > ex->check_interval - total % ex->check_interval) adv = ex->check_interval - total % ex->check_interval;
+            const b32 last = iter + adv >= m || total + adv >= maxit;
+            if (adv > 2) gmres_block(&p, ex, A, pc, iter, (int)adv, res_hist, last);
+            else if (adv == 2) gmres_pair(&p, ex, A, pc, iter, res_hist, last);
             else {
                 /* 2.0 z = inv(P) Q[:,iter] (FGMRES keeps every z; the fused step has left it in tmp)   2.2 Q[:,iter+1] = A z */
                 gmres_apply_operator(&p, ex, A, pc, COL(Q, iter), ex->nrm + iter, p.Zb ? COL(p.Zb, iter) : tmp,
                                      iter > 0 && (p.step == GMRES_STEP_FUSED_UPDATE_PC || p.step == GMRES_STEP_RAW_BASIS),
                                      COL(Q, iter + 1));
                 /* 3. classical Gram-Schmidt   4. Givens rotations + residual recurrence */
-                gmres_orthogonalise(&p, ex, iter, res_hist, iter + 1 >= m || total + 1 >= maxit);
+                gmres_orthogonalise(&p, ex, iter, res_hist, last);
             }
             if (hr.pend) {
                 /* the check enqueued behind the PREVIOUS step: the device has the step just enqueued to work on while the host
@@ -619,13 +672,12 @@ static b32 gmres_run(Matrix* A, f64* x, f64* b, Krylov* ksp, b32 force_probe) {
                     const FirstRead fr = gmres_first_read(ex, &hr, FALSE);
                     if (fr != FIRST_READ_GO_ON) return fr == FIRST_READ_REDO;
                 }
-                /* converged: the step enqueued meanwhile (one iteration or two) is not counted */
+                /* converged: the step enqueued meanwhile (one iteration or several) is not counted */
                 if (DflKrylovConverged(ksp, fabs(ex->h_stat[8]), hr.rnrm_init)) { converged = TRUE; break; }
             }
             if ((total + adv) % ex->check_interval == 0) converged = gmres_check(ksp, &p, ex, &hr, iter + adv - 1, total + adv - 1);
             iter += adv; total += adv;
-            if (pair) ex->last_pairs++;
-            else ex->last_singles++;
+            ex->last_blocks[adv]++;
         }
         /* (no check is pending here: one on the last iteration of the loop went to final_check instead) */
         if (!hr.first_read_done) { /* a solve shorter than its check interval: nothing has been read yet */
@@ -638,8 +690,8 @@ static b32 gmres_run(Matrix* A, f64* x, f64* b, Krylov* ksp, b32 force_probe) {
             gmres_update_solution(&p, ex, pc, iter, x);
         }
     }
-    gmres_end_of_solve(ex, total, ex->fused_norm || p.pair);
-    if (p.pair) { ex->last_pair_cancelled = ex->stats.fused_norm_cancelled; ex->stats.fused_norm_cancelled = FALSE; }
+    gmres_end_of_solve(ex, total, ex->fused_norm || p.block > 1);
+    if (p.block > 1) { ex->last_pair_cancelled = ex->stats.fused_norm_cancelled; ex->stats.fused_norm_cancelled = FALSE; }
     if (hr.final_check >= 0 && !converged) converged = DflKrylovConverged(ksp, fabs(ex->h_stat[9]), hr.rnrm_init);
     ex->stats.iterations = total; ex->stats.converged = converged;
     return FALSE;
@@ -755,13 +807,19 @@ int DflKrylovLastGmresStep(Krylov* ksp) {
     return (ksp && ksp->ksp_solve == GMRESSolvePrivate && kext(ksp)) ? kext(ksp)->last_step : -1;
 }
 
-/* how the most recent unpipelined GMRES solve of this solver advanced: counted steps of two iterations (gmres_pair), counted
-   steps of one, and whether a pair raised the cancellation flag (||q|| < 1e-4 ||p2'||); a plan without pairs reports 0 pairs */
-void DflKrylovLastGmresPairs(Krylov* ksp, int* pairs, int* singles, int* cancelled) {
+/* how the most recent unpipelined GMRES solve of this solver advanced: counts[s] = counted steps of s iterations, s = 1..4
+   (counts[0] = 0), and whether a pair or a block raised the cancellation flag (some ||q_i|| < 1e-4 ||p_i'||) */
+void DflKrylovLastGmresBlocks(Krylov* ksp, int counts[5], int* cancelled) {
     const KrylovExt* ex = (ksp && ksp->ksp_solve == GMRESSolvePrivate) ? kext(ksp) : NULL;
-    if (pairs) *pairs = ex ? ex->last_pairs : 0;
-    if (singles) *singles = ex ? ex->last_singles : 0;
+    if (counts) for (int s = 0; s < 5; ++s) counts[s] = ex ? ex->last_blocks[s] : 0;
     if (cancelled) *cancelled = ex ? ex->last_pair_cancelled : 0;
+}
+/* the same in pairs and single steps: a counted step of s iterations is floor(s / 2) pairs and s mod 2 single steps */
+void DflKrylovLastGmresPairs(Krylov* ksp, int* pairs, int* singles, int* cancelled) {
+    int c[5];
+    DflKrylovLastGmresBlocks(ksp, c, cancelled);
+    if (pairs) *pairs = c[2] + c[3] + 2 * c[4];
+    if (singles) *singles = c[1] + c[3];
 }
 
 /* the GMRES work space for this matrix as the next KrylovSolve would size it (host/ws_placement.c calibrates it ahead of

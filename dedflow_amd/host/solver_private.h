@@ -42,10 +42,11 @@ typedef struct KrylovExt {
     b32 no_calibration; /* inner / coarse solvers of PC_TWOLEVEL: never time basis placements (DflKrylovMarkInner) */
     char* amgx_cfg;     /* KrylovSetAMGXConfig: options of PCCreateAMGX (NULL: the reference configuration) */
     int last_step;      /* GmresStep of the most recent gmres_run (DflKrylovLastGmresStep), -1 before the first */
-    /* paired raw-basis step (GmresPlan.pair): the un-rotated copy of H (same shape), [c1 | c2 | e | scalars] of a pair (ldh
-       doubles each), and what the most recent gmres_run did (DflKrylovLastGmresPairs) */
+    /* raw-basis steps of more than one iteration (GmresPlan.block): the un-rotated copy of H (same shape); pair_buf, 8 ldh + 64
+       doubles: [c1 | c2 | e | scalars] of a pair (ldh doubles each), or [c_0..c_3 | e_0..e_3 | G, C, U] of a block (gmres_block);
+       and how many counted steps of each size the most recent gmres_run took (DflKrylovLastGmresBlocks) */
     f64 *h_unrot, *pair_buf;
-    int last_pairs, last_singles, last_pair_cancelled;
+    int last_blocks[5], last_pair_cancelled;
 } KrylovExt;
 
 static inline KrylovExt* kext(const Krylov* k) { return (KrylovExt*)k->ext; }
@@ -70,8 +71,9 @@ typedef struct GmresPlan {
     b32 x4_skip_z;             /* one GPU: nothing reads z in the reference layout, the PC kernel does not store it */
     f64* z4;                   /* the interleaved copy: the spare column of the basis block; NULL without x4 */
     GmresStep step;
-    b32 pair;                  /* GMRES_STEP_RAW_BASIS advances two iterations per pass over the basis where both fit and no
-                                  convergence check falls between them (gmres_pair); DFL_GMRES_TWO_STEP=0: never */
+    int block;                 /* GMRES_STEP_RAW_BASIS: the largest number of iterations one pass over the basis serves (1..4); a trip
+                                  takes as many as fit into the cycle with no convergence check between them (gmres_pair: 2,
+                                  gmres_block: 3, 4); DFL_GMRES_BLOCK, default 4; DFL_GMRES_TWO_STEP=0: 1; any other step: 0 */
     const f64 *d33, *d1;       /* Jacobi tree (DflPcJacobiTreeData: d33, d1, N, rows) for the fused step */
     index_type N, rows;
     f64* Zb;                   /* FGMRES: the basis of preconditioned vectors; NULL otherwise */

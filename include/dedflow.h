@@ -501,8 +501,10 @@ void KrylovSetPipelined(Krylov* krylov, b32 on);
 /* which Arnoldi step the most recent unpipelined GMRES solve ran (0 reference, 1 two reductions, 2 fused norm, 3 fused update +
  * preconditioner, 4 raw basis: DESIGN.md section 3); -1 before the first solve or for another solver.  For tests and A/B runs */
 int DflKrylovLastGmresStep(Krylov* krylov);
-/* how that solve advanced: steps of two iterations per pass over the basis, steps of one, and whether a step of two raised its
-   cancellation flag (the second new vector lost more than four digits in the orthogonalisation) */
+/* how that solve advanced: counts[s] = counted steps that took s iterations in one pass over the basis, s = 1..4 (counts[0] is 0),
+   and whether one of them raised its cancellation flag (a new vector lost more than four digits in the orthogonalisation) */
+void DflKrylovLastGmresBlocks(Krylov* krylov, int counts[5], int* cancelled);
+/* the same as pairs and single steps: a counted step of s iterations adds floor(s / 2) to pairs and s mod 2 to singles */
 void DflKrylovLastGmresPairs(Krylov* krylov, int* pairs, int* singles, int* cancelled);
 /* A non-blocking stream (default priority) that was PROBED to run concurrently with `main_stream`: HIP maps streams onto a few
  * hardware queues round-robin, and a side stream on the main stream's own queue runs behind it instead of beside it; a

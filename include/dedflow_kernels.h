@@ -84,7 +84,7 @@ void dfl_norms4(dfl_index N, const dfl_value* F, dfl_value* d_out4, int take_sqr
  *   dfl_cgs_dots   : d_h[j] = Q[:,j] . w, j < ncol  (one pass over Q[:,0:ncol] and ~ncol/16 passes over w)
  *   dfl_cgs_update : w -= Q[:,0:ncol] h ; *d_nrm = ||w||_2   (one pass over Q, w read+written once)
  * Q is column-major with leading dimension ldq.  `work` >= dfl_cgs_work_size(n, ncol) doubles (it covers the two-vector
- * forms below: two sets of dots partials, three of update partials). */
+ * forms below, two sets of dots partials and three of update partials, and the blocks of three and four vectors). */
 int64_t dfl_cgs_work_size(dfl_index n, dfl_index ncol);
 void dfl_cgs_dots(dfl_index n, dfl_index ncol, const dfl_value* Q, int64_t ldq, const dfl_value* w, dfl_value* d_h,
                   dfl_value* work, void* stream);
@@ -140,6 +140,33 @@ void dfl_cgs_update_jacobi_givens_keep(dfl_index N, dfl_index ncol, const dfl_va
                                        dfl_value* w, const dfl_value* dinv33, const dfl_value* dinv1, dfl_value* z4, dfl_value* d_nrm,
                                        dfl_value* work, dfl_index iter, dfl_value* d_H, dfl_index ldh, dfl_value* d_gv,
                                        dfl_value* d_beta, dfl_value* d_res_hist, dfl_value* d_raw_col, void* stream);
+/* Blocks of s = 3 or 4 Arnoldi steps per pass over the raw basis (any other s aborts): the products p_0 = B v_k, p_i = B p_{i-1}
+ * lie in s consecutive columns w + i ldw; d_e, d_c hold s vectors of lde doubles; d_sc holds 48 doubles, three 4 x 4 row-major
+ * tables: G (the Gram matrix of the updated p_i'), C (unit lower triangular, q_i = sum_{l<=i} C[i,l] p_l'), U[l,i] = <q_l, p_i'>.
+ * dfl_cgs_dots_block: one pass over Q; d_e[i lde + j] = <r_j, p_i> / nu_j, d_c = d_e / nu; e_0 also into d_h (column k of H) and
+ *   d_h_raw (may be NULL).  work holds s x ncol x dfl_cgs_dots_block_parts(n, s) partials; fixed summation order.
+ * dfl_cgs_update_block: p_i -= Q d_c[i] for all i in one pass; work holds g = dfl_cgs_update_block_parts(n, s) partials of each
+ *   G_ab, a <= b, the upper triangle in row-major order, at work[t g].
+ * dfl_gmres_block_first: second stage of G, d_nu[k+1] = sqrt(G_00) (also row k+1 of column k of d_Hraw), d_sc, the Givens step
+ *   of column k.
+ * dfl_cgs_fixup_block: q_i in place for i >= 1, vectors of 4N rows; work[(i-1) g + blk] = partials of ||q_i||^2, g = ceil(N / 256);
+ *   z4 != NULL: z4 = M^-1 q_{s-1} as dfl_cgs_update_jacobi writes it.
+ * dfl_gmres_block_second: d_nu[k+1+i] = ||q_i|| from those partials, columns k+1..k+s-1 of H and d_Hraw with their Givens
+ *   steps; *d_flag (may be NULL) raised when some ||q_i|| < 1e-4 sqrt(G_ii). */
+int dfl_cgs_dots_block_parts(dfl_index n, int s);
+int dfl_cgs_update_block_parts(dfl_index n, int s);
+void dfl_cgs_dots_block(dfl_index n, dfl_index ncol, int s, const dfl_value* Q, int64_t ldq, const dfl_value* w, int64_t ldw,
+                        const dfl_value* d_nu, dfl_value* d_h, dfl_value* d_h_raw, dfl_value* d_e, dfl_value* d_c, dfl_index lde,
+                        dfl_value* work, void* stream);
+void dfl_cgs_update_block(dfl_index n, dfl_index ncol, int s, const dfl_value* Q, int64_t ldq, const dfl_value* d_c, dfl_index lde,
+                          dfl_value* w, int64_t ldw, dfl_value* work, void* stream);
+void dfl_gmres_block_first(int npart, const dfl_value* part, int s, dfl_index k, dfl_value* d_nu, dfl_value* d_H, dfl_value* d_Hraw,
+                           dfl_index ldh, dfl_value* d_gv, dfl_value* d_beta, dfl_value* d_res_hist, dfl_value* d_sc, void* stream);
+void dfl_cgs_fixup_block(dfl_index N, int s, dfl_value* w, int64_t ldw, const dfl_value* d_sc, const dfl_value* dinv33,
+                         const dfl_value* dinv1, dfl_value* z4, dfl_value* work, void* stream);
+void dfl_gmres_block_second(int npart, const dfl_value* part, int s, dfl_index k, dfl_value* d_nu, dfl_value* d_H, dfl_value* d_Hraw,
+                            dfl_index ldh, const dfl_value* d_e, dfl_index lde, const dfl_value* d_sc, dfl_value* d_gv,
+                            dfl_value* d_beta, dfl_value* d_res_hist, int* d_flag, void* stream);
 void dfl_dsqrt_dev(dfl_value* d_val, void* stream); /* *d_val = sqrt(*d_val) */
 /* y = Q[:,0:ncol] c  (cublasDgemv OP_N of krylov.c:304-311) */
 void dfl_gemv_n(dfl_index n, dfl_index ncol, const dfl_value* Q, int64_t ldq, const dfl_value* d_c, dfl_value* y, void* stream);
