@@ -656,6 +656,15 @@ class DflPhaseChangeStats(C.Structure):
                 ("hi", C.c_double * 3)]
 
 
+class DflRedistance(C.Structure):
+    _fields_ = [("level", C.c_double), ("band", C.c_double), ("hold_groups", C.c_int32), ("every", C.c_int32)]
+
+
+class DflRedistanceStats(C.Structure):
+    _fields_ = [("facets", C.c_int64), ("band_nodes", C.c_int64), ("max_change", C.c_double), ("grad_dev_before", C.c_double),
+                ("grad_dev_after", C.c_double), ("volume_before", C.c_double), ("volume_after", C.c_double)]
+
+
 class DflComm(C.Structure):
     _fields_ = [("allreduce_sum", ALLREDUCE_FN), ("halo_exchange", HALO_FN), ("ctx", vp), ("num_owned_node", C.c_int32),
                 ("halo_begin", HALO_FN), ("halo_end", HALO_FN), ("num_interior_node", C.c_int32),
@@ -815,6 +824,13 @@ def _declare(L):
     f("DflPhaseChangeCheck", C.c_int, [C.POINTER(DflPhaseChange), C.c_char_p, C.c_size_t])
     f("DflMeshPhaseCoefficients", None, [C.POINTER(Mesh3D), vp, vp, vp, vp])
     f("DflMeshPhaseChangeStats", None, [C.POINTER(Mesh3D), vp, C.POINTER(DflPhaseChangeStats)])
+    f("DflMeshSetRedistance", None, [C.POINTER(Mesh3D), C.POINTER(DflRedistance)])
+    f("DflMeshRedistanceEnabled", i32, [C.POINTER(Mesh3D)])
+    f("DflRedistanceCheck", C.c_int, [C.POINTER(DflRedistance), C.c_char_p, C.c_size_t])
+    f("DflMeshRedistance", i32, [C.POINTER(Mesh3D), vp])
+    f("DflMeshRedistanceFacets", i32, [C.POINTER(Mesh3D), C.POINTER(vp)])
+    f("DflMeshRedistanceStats", None, [C.POINTER(Mesh3D), C.POINTER(DflRedistanceStats)])
+    f("DflMeshLevelSetVolume", f64, [C.POINTER(Mesh3D), vp, f64])
     f("GenerateRandomColor", None, [vp, i32, i32])
     f("dfl_abi_version", C.c_int, [])
 
@@ -1078,6 +1094,51 @@ class Problem:
         lib().DflMeshPhaseChangeStats(self.mesh, w.ptr, C.byref(s))
         return dict(liquid_volume=float(s.liquid_volume), T_max=float(s.T_max), molten=int(s.molten), lo=np.array(s.lo[:]),
                     hi=np.array(s.hi[:]))
+
+    # ---- level-set redistancing (include/dedflow.h, "level-set redistancing") ----------------------------------------------
+    def set_redistance(self, level=None, band=None, hold_groups=0, every=0):
+        """DflMeshSetRedistance: the surface phi = level, the half-width band of the rewritten zone, the boundary groups whose
+        nodes keep their phi (a bit mask) and, with every > 0, redistancing inside every every-th time_step.  level None turns
+        the feature off.  A configuration the library refuses (reported on stderr) leaves the mesh as it was: redistance_on
+        tells."""
+        if level is None:
+            lib().DflMeshSetRedistance(self.mesh, None)
+            return
+        cfg = DflRedistance(float(level), float(band), int(hold_groups), int(every))
+        lib().DflMeshSetRedistance(self.mesh, C.byref(cfg))
+
+    @property
+    def redistance_on(self):
+        return bool(lib().DflMeshRedistanceEnabled(self.mesh))
+
+    def redistance(self, w):
+        """DflMeshRedistance in place on phi of the state w (DeviceArray of 6N, or a raw device pointer); returns the number
+        of facets (reads two totals back: synchronises)"""
+        if not self.redistance_on:
+            raise RuntimeError("no redistancing is set: call set_redistance first")
+        return int(lib().DflMeshRedistance(self.mesh, getattr(w, "ptr", w)))
+
+    def redistance_facets(self):
+        """the facet list of the last redistance call as a numpy array [nf, 9] (A, B, C of every triangle)"""
+        ptr = vp()
+        nf = int(lib().DflMeshRedistanceFacets(self.mesh, C.byref(ptr)))
+        if nf <= 0:
+            return np.zeros((0, 9))
+        sync()
+        return d2h(ptr.value, 9 * nf, np.float64).reshape(nf, 9)
+
+    def redistance_stats(self):
+        """DflMeshRedistanceStats of the last call: facets, band_nodes, max_change, grad_dev_before / _after,
+        volume_before / _after (synchronises)"""
+        if not self.redistance_on:
+            raise RuntimeError("no redistancing is set: call set_redistance first")
+        s = DflRedistanceStats()
+        lib().DflMeshRedistanceStats(self.mesh, C.byref(s))
+        return {k: (int if k in ("facets", "band_nodes") else float)(getattr(s, k)) for k, _ in DflRedistanceStats._fields_}
+
+    def level_set_volume(self, w, level):
+        """DflMeshLevelSetVolume: the volume of {phi > level} at the state w (synchronises); needs no configuration"""
+        return float(lib().DflMeshLevelSetVolume(self.mesh, getattr(w, "ptr", w), float(level)))
 
     def close(self):
         L = lib()

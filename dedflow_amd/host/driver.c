@@ -141,7 +141,8 @@ index_type SolveFlowSystem(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matr
  * ParticleContextAdd runs after the predictor and ParticleContextRemove after the particle sub-steps; with capture set
  * (ParticleContextSetCapture) ParticleContextCapture runs just before that Remove, and with its two_way the deposits of
  * the previous step enter the p, momentum and T rows of this step's Newton solve.  With free-surface forces set on the mesh
- * with in_time_step (DflMeshSetSurfaceForces), their load and heat loss at wgold enter the momentum and T rows as well. */
+ * with in_time_step (DflMeshSetSurfaceForces), their load and heat loss at wgold enter the momentum and T rows as well.  With
+ * redistancing set on the mesh with every > 0 (DflMeshSetRedistance), every every-th call first redistances phi of wgold. */
 index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* J, f64* F, f64* dx, Krylov* ksp, Dirichlet** bcs,
                        index_type nbc, index_type newton_maxit, ParticleContext* pctx, index_type dem_substeps, f64* rnorm_out,
                        f64* rnorm_init_out) {
@@ -166,7 +167,14 @@ index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* 
         fprintf(stderr, "DflTimeStep: the phase change is single-GPU only; the solver has a communicator: step refused\n");
         return -1;
     }
+    if (DflRedistanceInTimeStep(mesh) && KrylovGetComm(ksp)) {
+        fprintf(stderr, "DflTimeStep: the level-set redistancing is single-GPU only; the solver has a communicator: step refused\n");
+        return -1;
+    }
     DflRangePush("DflTimeStep");
+    /* every every-th step (DflMeshSetRedistance): phi of wgold becomes the band distance again before the surface load, the
+       phase change and the solve look at it */
+    DflRedistanceTimeStep(mesh, wgold);
     const f64* user_load = DflMeshExternalLoad(mesh);
     const f64* reaction = coupled && DflParticleTwoWay(pctx) ? DflParticlePendingLoad(pctx) : NULL;
     if (reaction) {

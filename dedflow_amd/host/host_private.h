@@ -80,6 +80,7 @@ typedef struct MeshExt {
     struct SurfaceState* surface;  /* free-surface forces (host/surface.c, DflMeshSetSurfaceForces), NULL: off */
     struct PhaseState* phase;      /* phase change (host/phase.c, DflMeshSetPhaseChange), NULL: off */
     b32 phase_current;             /* its D and H already hold the alpha states the next driver assembly is given */
+    struct RedistanceState* redistance; /* level-set redistancing (host/redistance.c, DflMeshSetRedistance), NULL: off */
     index_type *v2e_row, *v2e_col; /* device [N+1], [4T]: the sorted V2E map (DflMeshSortedV2E), NULL until first asked for */
 } MeshExt;
 
@@ -369,6 +370,14 @@ void DflPhaseFree(struct PhaseState* st);
 void DflPhaseApplySystem(Mesh3D* mesh, const f64* wgalpha, const f64* dwgalpha, f64* F, Matrix* J, b32 reuse);
 /* kALPHAM H on the diagonal of the T Jacobian values val_T over the nodal pattern attr */
 void DflPhaseApplyScalarJacobian(Mesh3D* mesh, const f64* wgalpha, const CSRAttr* attr, f64* val_T, b32 reuse);
+
+/* host/redistance.c: the level-set redistancing of a mesh (no-ops while it is off) */
+struct RedistanceState;
+void DflRedistanceFree(struct RedistanceState* st);
+void DflRedistanceGeometryChanged(struct RedistanceState* st); /* the nodes moved: the next call makes the cell grid again */
+b32 DflRedistanceInTimeStep(const Mesh3D* mesh);                /* a configuration with every > 0 is set */
+/* counts one DflTimeStep; on every every-th since the Set call redistances wgold (DflMeshRedistance) and returns TRUE */
+b32 DflRedistanceTimeStep(Mesh3D* mesh, f64* wgold);
 
 /* named ranges for rocprofv3 --marker-trace (DFL_ROCTX=1); no-ops otherwise */
 void DflRangePush(const char* name);

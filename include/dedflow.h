@@ -1357,6 +1357,90 @@ void DflMeshPhaseCoefficients(Mesh3D* mesh, const f64* w, f64* D, f64* H, f64* G
  * empty-set values */
 void DflMeshPhaseChangeStats(Mesh3D* mesh, const f64* w, DflPhaseChangeStats* out);
 
+/* ---- level-set redistancing: the exact band distance to the surface phi = level (build-defined; opt-in) -----------------
+ * The reference advects phi and never restores |grad phi| = 1.  A mesh that never calls DflMeshSetRedistance with a
+ * configuration, or clears it with NULL, computes bit for bit what it computes without this section, through the same
+ * launches.  One GPU only.  With a configuration DflMeshRedistance replaces phi, inside a band around the surface
+ * phi = level, by the signed distance to the piecewise-linear surface itself: the minimum over its triangles of the
+ * point-triangle distance.  A minimum needs no order, no iteration and no causality, so the result is bitwise reproducible.
+ * No operation below is fused (no multiply-add), and every dot product is associated (x0 y0 + x1 y1) + x2 y2.
+ *   inputs      w (device, 6N), phi_a = w[4N + a], f_a = phi_a - level.  Node a is positive iff f_a > 0: a NaN is not.
+ *   facets      the tets in ascending tet id, nodes n_k = ien[4e + k], k the local index.  A tet with 0 or 4 positive nodes
+ *               has no facet.  The crossing point of edge (i positive, j not) is P_ij = x_i + t (x_j - x_i),
+ *               t = f_i / (f_i - f_j), per component.
+ *                 1 positive node i:   the triangle (P_ij), j over the three others in local order;
+ *                 3 positive nodes:    the triangle (P_ij), i over the positives in local order, j the fourth;
+ *                 2 positive a < b, the others c < d: the quad P_ac, P_ad, P_bd, P_bc (planar: phi is linear in the tet) as
+ *                                      the triangles (0, 1, 2) and (0, 2, 3).
+ *               The facet list is [nf][9] f64 (A, B, C), ascending tet id, a quad's first triangle first.
+ *   distance    of a point p to a facet (A, B, C), squared: the minimum of seven candidates, started from +inf and replaced
+ *               only where candidate < minimum, so a NaN never wins:
+ *                 the vertices   |p - V|^2, V = A, B, C;
+ *                 the segments   (U, V) = (A, B), (B, C), (C, A): e = V - U, only where e . e > 0:
+ *                                t = ((p - U) . e) / (e . e), t < 0 -> 0, t > 1 -> 1, |p - (U + t e)|^2;
+ *                 the plane      n = (B - A) x (C - A), only where n . n > 0 and the projection is inside:
+ *                                b1 = ((p - A) x (C - A)) . n >= 0, b2 = ((B - A) x (p - A)) . n >= 0, b1 + b2 <= n . n:
+ *                                ((p - A) . n)^2 / (n . n).
+ *               a x b = (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0).  Degenerate facets (nodes exactly on the surface)
+ *               need no special case: their vertices and edges still count.
+ *   result      d_a = sqrt(min over all facets), +inf without a facet; phi_a <- level + s_a min(d_a, band), s_a = +1 for a
+ *               positive node, else -1.  A node whose phi is NaN keeps its NaN; a node of a boundary group in hold_groups
+ *               (bit g = group g, g < 31) keeps its value; the rate dphi and every other slot of w are not touched.
+ *   search      a uniform grid over the bounding box of the nodes (made by the Set call and again by the first call after
+ *               DflMeshGeometryChanged), cell edge band x DFL_REDISTANCE_CELL (read by the Set call, default 1, a value below
+ *               1 is refused), enlarged by steps of 1.25 while the grid would have more than 2^24 cells.  Every facet is
+ *               entered into every cell the bounding box of its finite vertices overlaps (a NaN vertex never wins), so the closest point of a node with d_a < band lies in
+ *               one of the 27 cells around the node's own and its facet is listed there; whatever the search finds beyond
+ *               band is clamped to band.  The result therefore does not depend on the cell size.
+ *   statistics  of the last call: facets; band_nodes = the nodes with d_a < band (held and NaN nodes included); max_change =
+ *               max over them of |new phi_a - old phi_a| (0 for a node that kept its value); grad_dev_before / _after =
+ *               max of ||g| - 1| over the cut tets (those with a facet) of the old / new field, g and |g| as the free-surface
+ *               section forms them, a NaN passed over, 0 without a cut tet; volume_before / _after = the volume of
+ *               {phi > level}: the sum over the tets, in a fixed two-stage order, of
+ *                 0 positive nodes: 0;   4: |det| / 6, det = e_1 . (e_2 x e_3) of the free-surface section;
+ *                 1 (i):  |det4(x_i, P_ij1, P_ij2, P_ij3)| / 6, det4(q0, q1, q2, q3) = (q1 - q0) . ((q2 - q0) x (q3 - q0));
+ *                 3 (j not positive):  |det| / 6 - |det4(x_j, P_i1j, P_i2j, P_i3j)| / 6;
+ *                 2:  the wedge u = (x_a, P_ac, P_ad), v = (x_b, P_bc, P_bd) as the tets (u0 u1 u2 v0), (u1 u2 v0 v1),
+ *                     (u2 v0 v1 v2): ((|det4| + |det4|) + |det4|) / 6;
+ *               a tet whose value is NaN (a NaN phi at a node of a cut tet) adds 0.
+ *   time step   with every > 0, DflTimeStep redistances phi of wgold on every every-th call since the Set call, before the
+ *               surface load and anything else is evaluated.  With a communicator it prints why and returns -1.
+ * Limits: the surface ends at the mesh boundary, so the distance is to the part of the surface inside the mesh.  Beyond band
+ * the field is flat at level +- band; there |g| = 0, which the free-surface and phase-change sections treat as "contributes
+ * nothing" / "mean sign", so band >= eps + 2 h (h the tet size) is the caller's condition.  One GPU only.  No volume
+ * correction: the zero set of the new interpolant moves by O(h^2), and volume_before / volume_after say by how much.  Fewer
+ * than 2^31 facets and cell entries. */
+typedef struct DflRedistance {
+    f64 level, band;          /* the surface phi = level; half-width of the band (length), > 0 */
+    index_type hold_groups;   /* bit g: the nodes of boundary group g keep their phi */
+    index_type every;         /* > 0: DflTimeStep redistances wgold on every every-th call; 0: only DflMeshRedistance does */
+} DflRedistance;
+typedef struct DflRedistanceStats {
+    int64_t facets, band_nodes;
+    f64 max_change, grad_dev_before, grad_dev_after, volume_before, volume_after;
+} DflRedistanceStats;
+/* host only: 0 when DflMeshSetRedistance accepts the configuration, else why not in `why`: level or band not finite,
+ * band <= 0, every < 0 */
+int  DflRedistanceCheck(const DflRedistance* cfg, char* why, size_t why_len);
+/* the configuration is copied; NULL: off, frees everything of its own.  A refused configuration (or DFL_REDISTANCE_CELL) is
+ * reported on stderr and leaves the mesh as it was.  Builds the grid, the hold mask and every buffer but the two lists
+ * below (synchronises), and restarts the count of time steps */
+void DflMeshSetRedistance(Mesh3D* mesh, const DflRedistance* cfg);
+b32  DflMeshRedistanceEnabled(const Mesh3D* mesh);
+/* in place on w[4N:5N), w on the device; returns the number of facets, -1 when not set.  Every call waits for the device
+ * once, to read the facet and cell-entry totals back (the first is its return value), and grows the facet and entry lists
+ * when a total exceeds their capacity; it allocates nothing otherwise */
+index_type DflMeshRedistance(Mesh3D* mesh, f64* w);
+/* the facet list of the last call, device [nf][9] (NULL with nf <= 0), valid until the next call or Set; returns nf, -1
+ * when not set or never called */
+index_type DflMeshRedistanceFacets(const Mesh3D* mesh, const f64** facets);
+/* the statistics of the last call (synchronises, reads 48 bytes back); zeros when not set (with a line on stderr) or never
+ * called */
+void DflMeshRedistanceStats(Mesh3D* mesh, DflRedistanceStats* out);
+/* the volume of {phi > level} at the state w (device 6N) as the statistics form it; needs no configuration.  Allocates and
+ * frees its own scratch and synchronises */
+f64  DflMeshLevelSetVolume(Mesh3D* mesh, const f64* w, f64 level);
+
 #ifdef __cplusplus
 }
 #endif

@@ -882,6 +882,49 @@ dfl_index dfl_phase_stats_work_size(void);
 void dfl_phase_stats(dfl_index N, const dfl_value* xg, const dfl_value* w, const dfl_value* G, const dfl_phase_params* prm,
                      dfl_value* work, dfl_value* out9, void* stream);
 
+/* ---- level-set redistancing (build-defined, opt-in; host/redistance.c, csrc/k_redistance.hip, model in include/dedflow.h)
+ * phi = w + 4N.  grid: the uniform cell grid over the mesh's bounding box; a point's cell per axis is
+ * clamp(floor((x - lo) inv_h), 0, n - 1), cell id = cx + n[0] (cy + n[1] cz).
+ *    dfl_redistance_cut      one thread per tet, workgroups of dfl_redistance_tets_per_block() tets.  part[2 b], part[2 b + 1]
+ *                            = workgroup b's volume of {phi > level} (fixed tree) and its maximum of ||g| - 1| over the cut
+ *                            tets.  With blk_count: blk_count[b] = facets of workgroup b, and cell_count[c] += 1 for every
+ *                            cell c the bounding box of a facet's finite vertices overlaps (integer atomics; a vertex
+ *                            with a NaN coordinate cannot win, the others still count).  blk_count NULL: the statistics alone.
+ *    dfl_redistance_scan     start[0 .. n] = exclusive scan of count[0 .. n), count zeroed; chunk_sum holds
+ *                            ceil((n + 1) / 1024) integers
+ *    dfl_redistance_emit     the facets in ascending tet order, a quad's first triangle first: facet blk_base[b] + (facets of
+ *                            the earlier tets of workgroup b), and its index into every cell it overlaps at
+ *                            cell_start[c] + cell_fill[c]++ (cell_fill zero on entry; the order inside a cell is free).
+ *                            Nothing is written at or beyond cap_facets / cap_entries.
+ *    dfl_redistance_nodes    ncand[0] = 0 on entry.  Pass 1, one thread per node: the entries of the 27 cells around the node
+ *                            as nine three-cell runs of cell_start; none: phi = level +- band at once (chg = -1), else
+ *                            the node joins list (wave ballot, one integer atomic per wave).  Pass 2, 16 lanes per listed
+ *                            node: the lanes stride the entries with a running minimum of the squared distance, four
+ *                            xor-shuffles, lane 0 writes phi = level +- min(d, band) and chg = |new - old| where d < band,
+ *                            else -1.  A node with hold[a] != 0 (hold NULL: none) or a NaN phi keeps its value (chg 0 in
+ *                            the band).
+ *    dfl_redistance_node_stats  out2 = (number of nodes with chg >= 0, their maximum chg); work >= 2048 doubles
+ *    dfl_redistance_reduce   out2 = (sum of part[2 i] in a fixed order, max of part[2 i + 1]), i < npart */
+typedef struct dfl_redistance_grid {
+    dfl_value lo[3], inv_h;
+    dfl_index n[3];
+} dfl_redistance_grid;
+dfl_index dfl_redistance_tets_per_block(void);
+void dfl_redistance_cut(dfl_index T, const dfl_index* ien, const dfl_value* xg, const dfl_value* w, dfl_index N, dfl_value level,
+                        const dfl_redistance_grid* grid, dfl_index* blk_count, dfl_index* cell_count, dfl_value* part,
+                        void* stream);
+void dfl_redistance_scan(dfl_index n, dfl_index* count, dfl_index* chunk_sum, dfl_index* start, void* stream);
+void dfl_redistance_emit(dfl_index T, const dfl_index* ien, const dfl_value* xg, const dfl_value* w, dfl_index N, dfl_value level,
+                         const dfl_redistance_grid* grid, const dfl_index* blk_base, const dfl_index* cell_start,
+                         dfl_index* cell_fill, dfl_value* facets, dfl_index cap_facets, dfl_index* entries,
+                         dfl_index cap_entries, void* stream);
+void dfl_redistance_nodes(dfl_index N, const dfl_value* xg, dfl_value* w, dfl_value level, dfl_value band,
+                          const dfl_redistance_grid* grid, const dfl_index* cell_start, const dfl_index* entries,
+                          const dfl_value* facets, dfl_index cap_facets, const unsigned char* hold, dfl_index* ncand,
+                          dfl_index* list, dfl_value* chg, void* stream);
+void dfl_redistance_node_stats(dfl_index N, const dfl_value* chg, dfl_value* work, dfl_value* out2, void* stream);
+void dfl_redistance_reduce(dfl_index npart, const dfl_value* part, dfl_value* out2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
