@@ -525,6 +525,45 @@ class Particles:
         n = int(lib().ParticleContextLaserColumns(self.ctx, C.byref(tp), C.byref(fp)))
         return d2h(tp.value, n, np.float64), d2h(fp.value, n, np.int32)
 
+    # ---- laser on the level-set surface (build-defined; model in include/dedflow.h) ---------------------------------
+    def set_laser_surface(self, level=0.0, side=1):
+        """ParticleContextSetLaserSurface: the transmitted beam is also deposited on the surface phi = level of the coupled
+        mesh (metal where side (phi - level) > 0); level None turns it off.  Needs set_laser and couple.  A configuration the
+        library refuses (reported on stderr) leaves the context as it was: laser_surface_on tells."""
+        if level is None:
+            lib().ParticleContextSetLaserSurface(self.ctx, None)
+            return
+        cfg = DflLaserSurface(float(level), int(side))
+        lib().ParticleContextSetLaserSurface(self.ctx, C.byref(cfg))
+
+    @property
+    def laser_surface_on(self):
+        return int(lib().ParticleContextLaserSurfaceFacets(self.ctx, None, None)) >= 0
+
+    def laser_surface_update(self, w):
+        """ParticleContextLaserSurfaceUpdate at the fluid state w (DeviceArray of 6N): the number of candidate facets, -1 off"""
+        return int(lib().ParticleContextLaserSurfaceUpdate(self.ctx, w.ptr))
+
+    def laser_surface_facets(self):
+        """(facets [nf, 9], tet [nf]) of the last snapshot, copied back from the device"""
+        fp, tp = vp(), vp()
+        n = int(lib().ParticleContextLaserSurfaceFacets(self.ctx, C.byref(fp), C.byref(tp)))
+        if n < 0:
+            raise RuntimeError("no laser surface is set: call set_laser_surface first")
+        if n == 0:
+            return np.zeros((0, 9)), np.zeros(0, np.int32)
+        sync()
+        return d2h(fp.value, 9 * n, np.float64).reshape(n, 9), d2h(tp.value, n, np.int32)
+
+    def laser_surface_power(self, out=None):
+        """ParticleContextLaserSurfacePower into `out` (DeviceArray of N, allocated when None); returns the DeviceArray"""
+        if not self.laser_surface_on:
+            raise RuntimeError("no laser surface is set: call set_laser_surface first")
+        if out is None:
+            out = DeviceArray(self.N)
+        lib().ParticleContextLaserSurfacePower(self.ctx, out.ptr)
+        return out
+
     # ---- melt-pool capture (build-defined; model in include/dedflow.h) ----------------------------------------------
     def set_capture(self, level=0.0, side=1, reach=0.0, T_melt=-np.inf, two_way=False):
         """ParticleContextSetCapture: capture() takes out the particles that reach the metal surface phi = level (side +1:
@@ -613,6 +652,10 @@ class DflLaser(C.Structure):
 class DflLaserTally(C.Structure):
     _fields_ = [("outside", C.c_double), ("absorbed_particles", C.c_double), ("scattered", C.c_double),
                 ("substrate", C.c_double), ("reflected", C.c_double), ("missed", C.c_double)]
+
+
+class DflLaserSurface(C.Structure):
+    _fields_ = [("level", C.c_double), ("side", C.c_int32)]
 
 
 class DflFluidCoupling(C.Structure):
@@ -796,6 +839,10 @@ def _declare(L):
     f("ParticleContextLaserRate", vp, [C.POINTER(ParticleContext)])
     f("ParticleContextLaserTally", None, [C.POINTER(ParticleContext), C.POINTER(DflLaserTally)])
     f("ParticleContextLaserColumns", C.c_int32, [C.POINTER(ParticleContext), C.POINTER(vp), C.POINTER(vp)])
+    f("ParticleContextSetLaserSurface", None, [C.POINTER(ParticleContext), C.POINTER(DflLaserSurface)])
+    f("ParticleContextLaserSurfaceUpdate", C.c_int32, [C.POINTER(ParticleContext), vp])
+    f("ParticleContextLaserSurfaceFacets", C.c_int32, [C.POINTER(ParticleContext), C.POINTER(vp), C.POINTER(vp)])
+    f("ParticleContextLaserSurfacePower", None, [C.POINTER(ParticleContext), vp])
     f("ParticleContextSetCapture", None, [C.POINTER(ParticleContext), C.POINTER(DflParticleCapture)])
     f("ParticleContextCapture", i32, [C.POINTER(ParticleContext), vp])
     f("ParticleContextCaptureSource", None, [C.POINTER(ParticleContext), f64, vp, vp, vp])

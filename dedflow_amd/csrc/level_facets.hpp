@@ -91,6 +91,57 @@ __device__ __forceinline__ int lf_tet_facets(const double* x, const double* f, i
     return 1;
 }
 
+// lf_cross_point that also returns t: the weights of P_ij in the tet are 1 - t at node i, t at node j
+__device__ __forceinline__ double lf_cross_point_t(const double* x, const double* f, int i, int j, double* P) {
+#pragma clang fp contract(off)
+    const double fi = lf_pick1(f, i);
+    const double t = fi / (fi - lf_pick1(f, j));
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        const double xi = lf_pick(x, i, d);
+        P[d] = xi + t * (lf_pick(x, j, d) - xi);
+    }
+    return t;
+}
+
+// lf_tet_facets (the same facets, bit for bit) with the edge of every vertex: vertex v of facet k is P_ij with
+// i | j << 2 in bits [4 v, 4 v + 4) of ij[k], and t in tt[3 k + v] (the laser's surface deposit, k_laser_surface.hip)
+__device__ __forceinline__ int lf_tet_facets_ijt(const double* x, const double* f, int mask, double* out, int* ij, double* tt) {
+    const int np = __popc(mask);
+    if (np == 0 || np == 4) return 0;
+    if (np == 2) {
+        int a, b, c, d;
+        lf_pairs(mask, a, b, c, d);
+        double Q[12], tq[4];
+        tq[0] = lf_cross_point_t(x, f, a, c, Q);
+        tq[1] = lf_cross_point_t(x, f, a, d, Q + 3);
+        tq[2] = lf_cross_point_t(x, f, b, d, Q + 6);
+        tq[3] = lf_cross_point_t(x, f, b, c, Q + 9);
+        const int e0 = a | c << 2, e1 = a | d << 2, e2 = b | d << 2, e3 = b | c << 2;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            out[k] = Q[k]; out[3 + k] = Q[3 + k]; out[6 + k] = Q[6 + k];
+            out[9 + k] = Q[k]; out[12 + k] = Q[6 + k]; out[15 + k] = Q[9 + k];
+        }
+        ij[0] = e0 | e1 << 4 | e2 << 8;
+        ij[1] = e0 | e2 << 4 | e3 << 8;
+        tt[0] = tq[0]; tt[1] = tq[1]; tt[2] = tq[2];
+        tt[3] = tq[0]; tt[4] = tq[2]; tt[5] = tq[3];
+        return 2;
+    }
+    const int lone = np == 1 ? __ffs(mask) - 1 : __ffs(~mask & 15) - 1;
+    int e = 0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int o = k + (k >= lone ? 1 : 0);
+        const int i = np == 1 ? lone : o, j = np == 1 ? o : lone;
+        tt[k] = lf_cross_point_t(x, f, i, j, out + 3 * k);
+        e |= (i | j << 2) << (4 * k);
+    }
+    ij[0] = e;
+    return 1;
+}
+
 // det(q1 - q0, q2 - q0, q3 - q0) in the association of tet_cross
 __device__ __forceinline__ double lf_det4(const double* q0, const double* q1, const double* q2, const double* q3) {
     double e1[3], e2[3], e3[3], c[3];

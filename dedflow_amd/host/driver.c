@@ -142,7 +142,9 @@ index_type SolveFlowSystem(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matr
  * (ParticleContextSetCapture) ParticleContextCapture runs just before that Remove, and with its two_way the deposits of
  * the previous step enter the p, momentum and T rows of this step's Newton solve.  With free-surface forces set on the mesh
  * with in_time_step (DflMeshSetSurfaceForces), their load and heat loss at wgold enter the momentum and T rows as well.  With
- * redistancing set on the mesh with every > 0 (DflMeshSetRedistance), every every-th call first redistances phi of wgold. */
+ * redistancing set on the mesh with every > 0 (DflMeshSetRedistance), every every-th call first redistances phi of wgold.
+ * With a laser surface set on the coupled context (ParticleContextSetLaserSurface), ParticleContextLaserSurfaceUpdate runs
+ * once, before the first particle sub-step, in the state those sub-steps see. */
 index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* J, f64* F, f64* dx, Krylov* ksp, Dirichlet** bcs,
                        index_type nbc, index_type newton_maxit, ParticleContext* pctx, index_type dem_substeps, f64* rnorm_out,
                        f64* rnorm_init_out) {
@@ -224,6 +226,7 @@ index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* 
     if (pctx && !coupled)
         for (index_type k = 0; k < dem_substeps; ++k) ParticleContextUpdate(pctx); /* coupled step: contact sweep (config 4) */
     dfl_alpha_correct(N, fac_corr[0], fac_corr[1], wgold, dwgold, dwg, s);
+    if (coupled) DflLaserSurfaceTimeStep(pctx, wgold); /* the laser's snapshot of phi = level; a no-op unless a surface is set */
     if (coupled)
         for (index_type k = 0; k < dem_substeps; ++k) ParticleContextFluidStep(pctx, wgold); /* u at t_{n+1} */
     if (coupled) ParticleContextCapture(pctx, wgold); /* a no-op unless capture is set; before the outflow */

@@ -247,7 +247,40 @@ typedef struct LaserState {
     f64 *power, *energy;             /* device [ns] */
     f64 vdmin, vdmax;                /* range of v . dir over the candidates' vertices */
     f64 time;                        /* time the energy was accumulated over */
+    struct LaserSurface* surf;       /* the level-set surface as a target (host/laser_surface.c), NULL when off */
 } LaserState;
+/* the laser on the level-set surface (host/laser_surface.c): configuration, the depth range of the coupled mesh's bounding
+ * box, the snapshot of the last Update and the compact nodal power / energy keyed by its node list */
+typedef struct LaserSurface {
+    DflLaserSurface cfg;
+    Mesh3D* mesh;                    /* the coupled mesh the buffers are sized for */
+    index_type N, T, nblk;
+    f64 vdmin, vdmax;                /* range of x . dir over the corners of the node bounding box */
+    index_type *blk_count, *blk_base, *chunk_sum; /* device [nblk], [nblk + 1], [cap_chunk] */
+    index_type cap_chunk;
+    index_type nf;                   /* candidate facets of the snapshot, -1: no Update yet */
+    index_type nfb;                  /* boundary records in front of them in cand */
+    index_type cap, cap_cand;        /* facets the lists hold; records cand holds */
+    dfl_wall_tri* cand;              /* device [cap_cand]: the boundary candidates, then the facets */
+    f64 *facets, *ft;                /* device [cap][9], [cap][3] */
+    index_type *ftet, *fij;          /* device [cap] */
+    uint32_t *nkey, *nkey_out;       /* device [4 cap]: the node sort */
+    index_type *nrec, *nrec_out, *nflag, *nstart, *fslot, *unode; /* device [4 cap] ([4 cap + 1]: nstart) */
+    f64 *power, *energy;             /* device [4 cap], keyed by unode */
+    uint64_t *rkey, *rkey_out;       /* device [4 ncol]: the deposit records */
+    f64* rval;                       /* device [4 ncol] */
+    void* temp;                      /* radix sort scratch */
+    int64_t temp_bytes;
+    f64* carry;                      /* device [N] or NULL: energy pending when a new snapshot replaced the node list */
+    b32 carry_on;                    /* carry holds energy */
+    b32 dirty;                       /* a step deposited into energy since it was last cleared */
+} LaserSurface;
+void DflLaserSurfaceInstall(ParticleContext* ctx, const DflLaserSurface* cfg); /* a checked configuration on a context with a laser */
+void DflLaserSurfaceFree(LaserState* l);             /* frees l->surf */
+void DflLaserSurfaceCouplingChanged(ParticleContext* ctx); /* drops the snapshot and pending energy, the new depth range */
+void DflLaserSurfaceDeposit(LaserState* l, dfl_laser_beam b, f64 dt); /* after the columns of a step with facets */
+void DflLaserSurfaceAddSource(LaserState* l, f64* q); /* q += surface energy / l->time; clears it */
+void DflLaserSurfaceTimeStep(ParticleContext* ctx, const f64* w); /* DflTimeStep: Update when a surface is set */
 void DflLaserFree(ParticleContext* ctx);            /* off: frees the state */
 void DflLaserStep(ParticleContext* ctx, f64 dt);    /* one laser step (the laser must be on) */
 void DflLaserCouplingChanged(ParticleContext* ctx); /* SetFluidCoupling: the substrate list of the new mesh, nothing pending */

@@ -9,7 +9,9 @@
  * list -- the faces of the coupled mesh in the masked groups with n . dir < 0, as the wall records of host/walls.c, and
  * per node of those faces the list of its faces -- is built once per (coupled mesh, mask, direction): at
  * ParticleContextSetLaser and when the coupling changes.  A step launches hit (substrate only), bin + cell sort, columns,
- * deposit (substrate only) and tally; it allocates nothing and does not wait for the device. */
+ * deposit (substrate only) and tally; it allocates nothing and does not wait for the device.  With a laser surface set
+ * (host/laser_surface.c) and a snapshot taken, the facets of phi = level follow the boundary records in one candidate list,
+ * and the step adds the surface deposit; without one, the step's launches and their arguments are what they were. */
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -39,6 +41,7 @@ void DflLaserFree(ParticleContext* ctx) {
     if (!l) return;
     HIPGUARD(hipStreamSynchronize(DflStream()));
     DflParticleFieldsFree(ctx, DFL_PF_LASER);
+    DflLaserSurfaceFree(l);
     CdamFreeDevice(l->count, 0); CdamFreeDevice(l->cell_start, 0); CdamFreeDevice(l->chunk_sum, 0);
     free_substrate(l);
     CdamFreeDevice(l->gw, 0);
@@ -206,6 +209,10 @@ void ParticleContextSetLaser(ParticleContext* ctx, const DflLaser* cfg) {
         fprintf(stderr, "ParticleContextSetLaser: column edge h = %g is below 2 Rmax = %g; unchanged\n", cfg->h, 2.0 * rmax);
         return;
     }
+    /* a laser surface set on the context keeps its configuration and loses its snapshot (host/laser_surface.c) */
+    const b32 had_surface = x->laser && x->laser->surf;
+    DflLaserSurface surface;
+    if (had_surface) surface = x->laser->surf->cfg;
     DflLaserFree(ctx);
     LaserState* l = (LaserState*)CdamMallocHost(SIZE_OF(LaserState));
     memset(l, 0, sizeof *l);
@@ -228,11 +235,13 @@ void ParticleContextSetLaser(ParticleContext* ctx, const DflLaser* cfg) {
     DflParticleFieldsAlloc(ctx, DFL_PF_LASER);
     bin_buffers(l, x->cap);
     build_substrate(ctx, l);
+    if (had_surface) DflLaserSurfaceInstall(ctx, &surface);
 }
 
 void DflLaserCouplingChanged(ParticleContext* ctx) {
     LaserState* l = laser(ctx);
     if (l) build_substrate(ctx, l);
+    DflLaserSurfaceCouplingChanged(ctx);
 }
 
 void DflLaserCapacityChanged(ParticleContext* ctx) {
@@ -247,7 +256,10 @@ void DflLaserCopy(ParticleContext* dst, const ParticleContext* src) {
         return;
     }
     ParticleContextSetLaser(dst, &ls->cfg);
-    if (laser(dst)) laser(dst)->t = ls->t;
+    if (!laser(dst)) return;
+    laser(dst)->t = ls->t;
+    if (ls->surf) DflLaserSurfaceInstall(dst, &ls->surf->cfg); /* the configuration, not the snapshot or pending energy */
+    else ParticleContextSetLaserSurface(dst, NULL);
 }
 
 void DflLaserStep(ParticleContext* ctx, f64 dt) {
@@ -267,12 +279,18 @@ void DflLaserStep(ParticleContext* ctx, f64 dt) {
     b.h = l->cfg.h;
     b.area = l->cfg.h * l->cfg.h;
     b.n = l->n;
-    if (l->nf > 0) { /* depths on a 2^-40 grid of the candidates' range as seen from this step's origin */
+    /* with a snapshot of the level-set surface its facets follow the boundary records in one candidate list; with a surface
+       set the depth range is that of the mesh's bounding box (host/laser_surface.c) */
+    const LaserSurface* sf = l->surf;
+    const index_type nfs = sf && sf->nf > 0 ? sf->nf : 0;
+    const dfl_wall_tri* tri = nfs > 0 ? sf->cand : l->tri;
+    if (l->nf + nfs > 0) { /* depths on a 2^-40 grid of the candidates' range as seen from this step's origin */
+        const f64 vdmin = sf ? sf->vdmin : l->vdmin, vdmax = sf ? sf->vdmax : l->vdmax;
         const f64 od = (b.o[0] * b.dir[0] + b.o[1] * b.dir[1]) + b.o[2] * b.dir[2];
-        const f64 range = l->vdmax - l->vdmin;
-        f64 pad = 1e-6 * (range + fabs(l->vdmin) + fabs(l->vdmax) + fabs(od));
+        const f64 range = vdmax - vdmin;
+        f64 pad = 1e-6 * (range + fabs(vdmin) + fabs(vdmax) + fabs(od));
         if (!(pad > 0.0)) pad = 1.0;
-        dfl_laser_hit(l->nf, l->tri, b, (l->vdmin - od) - pad, 1099511627776.0 / (range + 2.0 * pad), l->colkey, s);
+        dfl_laser_hit(l->nf + nfs, tri, b, (vdmin - od) - pad, 1099511627776.0 / (range + 2.0 * pad), l->colkey, s);
     }
     if (P > 0) {
         dfl_laser_bin(P, ArrayData(ParticleCTXDeviceCoord(ctx)), b, l->cell_of, l->rank, l->count, l->rate, s);
@@ -281,12 +299,11 @@ void DflLaserStep(ParticleContext* ctx, f64 dt) {
                             l->sorted_r, s);
     }
     dfl_laser_columns(P, b, l->cfg.power, l->cfg.eta_p, l->cfg.eta_s, l->gw, l->cell_start, l->order, l->sorted,
-                      x->radius ? l->sorted_r : NULL, ParticleRadius(ctx), l->tri, l->colkey, l->k_tau, l->k_id, l->rate, l->col_T,
+                      x->radius ? l->sorted_r : NULL, ParticleRadius(ctx), tri, l->colkey, l->k_tau, l->k_id, l->rate, l->col_T,
                       l->col_face, l->part, s);
-    if (l->ns > 0) {
-        dfl_laser_deposit(l->ns, l->soff, l->sface, l->tri, b, l->cfg.eta_s, dt, l->colkey, l->col_T, l->power, l->energy, s);
-        l->time += dt;
-    }
+    if (l->ns > 0) dfl_laser_deposit(l->ns, l->soff, l->sface, tri, b, l->cfg.eta_s, dt, l->colkey, l->col_T, l->power, l->energy, s);
+    if (nfs > 0) DflLaserSurfaceDeposit(l, b, dt);
+    if (l->ns > 0 || nfs > 0) l->time += dt;
     dfl_laser_tally(l->ncol, l->cfg.power, l->part, l->tally, s);
     DflRangePop();
 }
@@ -323,12 +340,13 @@ index_type ParticleContextLaserColumns(const ParticleContext* ctx, const f64** t
 
 b32 DflLaserPending(const ParticleContext* ctx) {
     const LaserState* l = laser(ctx);
-    return l && l->ns > 0 && l->time > 0.0;
+    return l && (l->ns > 0 || (l->surf && (l->surf->dirty || l->surf->carry_on))) && l->time > 0.0;
 }
 
 void DflLaserAddSource(ParticleContext* ctx, f64* q) {
     LaserState* l = laser(ctx);
     if (!DflLaserPending(ctx)) return;
     dfl_laser_source_add(l->ns, l->snode, 1.0 / l->time, l->energy, q, DflStream());
+    DflLaserSurfaceAddSource(l, q);
     l->time = 0.0;
 }

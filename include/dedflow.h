@@ -1148,9 +1148,66 @@ void ParticleContextSetLaser(ParticleContext* ctx, const DflLaser* cfg);
 void ParticleContextLaserStep(ParticleContext* ctx, f64 dt);
 const f64* ParticleContextLaserRate(const ParticleContext* ctx); /* device [P] by id: W absorbed in the last step; NULL when off */
 void ParticleContextLaserTally(ParticleContext* ctx, DflLaserTally* out); /* the last step's (synchronises); zeros when off */
-/* device [n n], read-only: every column's transmitted power and the record id of the face it hit (-1: none); returns n n
- * (0 and NULL pointers when off) */
+/* device [n n], read-only: every column's transmitted power and the record id of the face it hit (-1: none; -2 - tet for
+ * a hit on the level-set surface inside that tet, see "laser on the level-set surface"); returns n n (0 and NULL pointers
+ * when off) */
 index_type ParticleContextLaserColumns(const ParticleContext* ctx, const f64** transmitted, const index_type** face);
+
+/* ---- laser on the level-set surface (build-defined; opt-in) -------------------------------------------------------------
+ * The sections around this one place the metal surface phi = level inside the mesh, with gas above; the substrate of "laser
+ * energy deposition" is boundary faces only.  With a laser surface set the transmitted beam is also deposited on the
+ * surface phi = level.  A context that never sets one, or clears it with NULL, computes bit for bit what it computes
+ * without this section, through the same launches.  One GPU only.  No fused multiply-add anywhere; every dot product is
+ * (x0 y0 + x1 y1) + x2 y2.
+ *   snapshot   ParticleContextLaserSurfaceUpdate reads phi = w[4N, 5N) of the coupled mesh.  The candidate facets are the
+ *              facets of "level-set redistancing" (per cut tet one triangle, or a quad as two), in ascending tet id, a
+ *              quad's first triangle first, kept only where (1) the tet's gradient g = sum_a phi_a grad N_a has
+ *              side (g . dir) > 0 -- the beam enters the metal there; a NaN is not greater --, (2) all nine coordinates of
+ *              the facet are finite and (3) |g| > 0.  Every facet vertex is a crossing point P_ij = x_i + t (x_j - x_i),
+ *              t = f_i / (f_i - f_j), f = phi - level; its weights in the tet are 1 - t at local node i, t at j, 0
+ *              elsewhere.  The list is compacted by per-workgroup counts and a scan: its order does not depend on arrival.
+ *              The surface moves on the fluid's time scale: the snapshot is taken by Update (and by DflTimeStep, below),
+ *              never by a laser step; before the first Update there are no facets.
+ *   first hit  the boundary candidates of substrate_groups and the facets compete per column centre ray: the facets are
+ *              appended to the candidate list behind the boundary records, with record id -2 - tet, and the smallest depth
+ *              wins on one depth grid; a tie on the grid goes to the lower list index (boundary faces before facets, facets
+ *              in list order).  With a surface set the depth grid spans x . dir over the eight corners of the coupled
+ *              mesh's node bounding box (computed at Set and when the coupling changes) instead of the boundary candidates'
+ *              range.  At most 2^24 records in total: beyond that the facets are dropped with a line on stderr and the
+ *              step behaves as if there were no snapshot.
+ *   column     unchanged: s_hit is the winner's depth, particles deeper than it are unlit and shadow nothing, T_c splits
+ *              into eta_s T_c absorbed (the `substrate` entry of the tally) and (1 - eta_s) T_c reflected; `missed` gets
+ *              only the columns without any hit.
+ *   deposit    with w_0..2 the barycentric weights of the centre ray in the projected facet (as for a boundary face) and
+ *              c_ka the weight of facet vertex k at local node a of the facet's tet, lambda_a = (w_0 c_0a + w_1 c_1a) +
+ *              w_2 c_2a, and power[n] = the sum, from +0.0 over the columns c that hit a facet in ascending column id, of
+ *              (eta_s T_c) lambda_a(c) for the local node a of that column's tet that is n.  No floating-point atomics;
+ *              bitwise reproducible.  A step costs O(columns + candidates), nothing of the size of the mesh.  Energy
+ *              accumulates as += dt power; ParticleContextHeatSource adds energy / time to q and clears it, exactly as for
+ *              the boundary substrate.
+ *   time step  DflTimeStep calls Update once per call when a surface is set on a context coupled to its mesh: after the
+ *              redistancing of wgold if that is due and before the first particle sub-step, with the fluid state those
+ *              sub-steps see.  ParticleContextFluidStep / HeatStep / LaserStep never update.  The beam axis still moves per
+ *              sub-step with scan_vel; the facets stay fixed between Updates.  Energy pending when an Update replaces the
+ *              node list is kept and reaches the next heat source.
+ *   travel     ParticleContextCopy carries the configuration, not the snapshot or pending energy.
+ *              ParticleContextSetFluidCoupling drops the snapshot and pending energy and recomputes the depth range.
+ *              ParticleContextSetLaser on a context with a surface keeps the surface configuration and drops the snapshot. */
+typedef struct DflLaserSurface {
+    f64 level; index_type side;   /* the surface phi = level; metal where side (phi - level) > 0, side = +-1 */
+} DflLaserSurface;
+/* the configuration is copied; NULL: off, frees the state.  Reported on stderr, context unchanged: the laser is off, the
+ * context is uncoupled, side is not +-1, level is not finite */
+void ParticleContextSetLaserSurface(ParticleContext* ctx, const DflLaserSurface* cfg);
+/* the snapshot at the device 6N state w: returns the number of candidate facets, -1 when off.  Waits for the device once
+ * (the count); grows its lists only when the count exceeds their capacity */
+index_type ParticleContextLaserSurfaceUpdate(ParticleContext* ctx, const f64* w);
+/* the snapshot's device lists [nf][9] and [nf] (the tet of every facet), valid until the next Update or Set; returns nf
+ * (-1 when off, 0 and NULL pointers before the first Update) */
+index_type ParticleContextLaserSurfaceFacets(const ParticleContext* ctx, const f64** facets, const index_type** tet);
+/* the last laser step's nodal surface power in W into the device array q[N], overwritten in full (zero where nothing was
+ * deposited).  For callers and tests; no step calls it */
+void ParticleContextLaserSurfacePower(ParticleContext* ctx, f64* q);
 
 /* ---- melt-pool capture (build-defined; opt-in) ---------------------------------------------------------------------------
  * The reference's particle hooks are empty and its continuity equation has no source.  A context that never calls

@@ -799,6 +799,49 @@ void dfl_laser_tally(dfl_index ncol, dfl_value power, const dfl_value* part, dfl
 void dfl_laser_source_add(dfl_index ns, const dfl_index* snode, dfl_value inv_time, dfl_value* energy, dfl_value* q,
                           void* stream);
 
+/* ---- the laser on the level-set surface (build-defined, opt-in; csrc/k_laser_surface.hip, model in include/dedflow.h)
+ * Snapshot: count -> dfl_redistance_scan of the workgroup counts -> emit -> nodes.  Deposit: once per laser step.  All on
+ * `stream`; nothing allocated or synchronised; no floating-point atomics; no atomic decides an order.
+ *    dfl_laser_surface_count       blk_count[b] = candidate facets of the tets of workgroup b (dfl_redistance_tets_per_block()
+ *                                  tets each): the facets of lf_tet_facets with side (g . dir) > 0, |g| > 0 and nine finite
+ *                                  coordinates.  phi = w + 4N; dir: three host doubles, the normalised beam direction
+ *    dfl_laser_surface_emit        facet f = blk_base[b] + (candidates of the earlier tets of workgroup b), f < cap:
+ *                                  facets[f][9], tet[f], t[f][3], ij[f] = per vertex v the edge i | j << 2 in bits
+ *                                  [4 v, 4 v + 4), and cand[f] = the facet as a wall record with id = -2 - tet (the caller
+ *                                  passes the candidate list offset by the boundary records in front)
+ *    dfl_laser_surface_nodes       the distinct nodes of the facets' tets: unode[0 .. nu) ascending, nu = start[4 nfs], and
+ *                                  fslot[4 f + a] = the index in unode of local node a of facet f's tet.  key, key_out, rec,
+ *                                  rec_out, flag: [4 nfs]; start: [4 nfs + 1]; chunk_sum as dfl_redistance_scan needs for
+ *                                  4 nfs entries; temp: dfl_laser_surface_temp_bytes(4 nfs, .) bytes
+ *    dfl_laser_surface_deposit     power[0 .. 4 nfs) <- 0; then per slot the sum, from +0.0 in ascending column id, of
+ *                                  (eta_s col_T[c]) lambda_a over the columns c whose hit key names a facet (index >= nfb in
+ *                                  cand, the whole candidate list): power[slot], energy[slot] += dt power[slot].  key,
+ *                                  key_out, val: [4 n n]; temp: dfl_laser_surface_temp_bytes(., 4 n n) bytes
+ *    dfl_laser_surface_source_add  q[unode[a]] += energy[a] inv_time, energy[a] = 0, a < min(nmax, *nu)
+ *    dfl_laser_surface_power       q[0 .. N) <- 0, then q[unode[a]] = power[a]
+ *    dfl_laser_surface_carry       carry[unode[a]] += energy[a], energy[a] = 0 (carry dense, [N])
+ *    dfl_laser_surface_carry_add   q[n] += carry[n] inv_time, carry[n] = 0, n < N */
+int64_t dfl_laser_surface_temp_bytes(dfl_index n_node_keys, dfl_index n_records);
+void dfl_laser_surface_count(dfl_index T, const dfl_index* ien, const dfl_value* xg, const dfl_value* w, dfl_index N, dfl_value level,
+                             dfl_index side, const dfl_value* dir, dfl_index* blk_count, void* stream);
+void dfl_laser_surface_emit(dfl_index T, const dfl_index* ien, const dfl_value* xg, const dfl_value* w, dfl_index N, dfl_value level,
+                            dfl_index side, const dfl_value* dir, const dfl_index* blk_base, dfl_wall_tri* cand, dfl_value* facets,
+                            dfl_index* tet, dfl_index* ij, dfl_value* t, dfl_index cap, void* stream);
+void dfl_laser_surface_nodes(dfl_index nfs, const dfl_index* ien, const dfl_index* tet, uint32_t* key, uint32_t* key_out,
+                             dfl_index* rec, dfl_index* rec_out, dfl_index* flag, dfl_index* chunk_sum, dfl_index* start,
+                             dfl_index* fslot, dfl_index* unode, void* temp, int64_t temp_bytes, void* stream);
+void dfl_laser_surface_deposit(dfl_laser_beam b, const uint64_t* colkey, dfl_index nfb, dfl_index nfs, const dfl_wall_tri* cand,
+                               const dfl_index* ij, const dfl_value* t, const dfl_index* fslot, dfl_value eta_s, dfl_value dt,
+                               const dfl_value* col_T, uint64_t* key, uint64_t* key_out, dfl_value* val, dfl_value* power,
+                               dfl_value* energy, void* temp, int64_t temp_bytes, void* stream);
+void dfl_laser_surface_source_add(dfl_index nmax, const dfl_index* nu, const dfl_index* unode, dfl_value inv_time, dfl_value* energy,
+                                  dfl_value* q, void* stream);
+void dfl_laser_surface_power(dfl_index N, dfl_index nmax, const dfl_index* nu, const dfl_index* unode, const dfl_value* power,
+                             dfl_value* q, void* stream);
+void dfl_laser_surface_carry(dfl_index nmax, const dfl_index* nu, const dfl_index* unode, dfl_value* energy, dfl_value* carry,
+                             void* stream);
+void dfl_laser_surface_carry_add(dfl_index N, dfl_value inv_time, dfl_value* carry, dfl_value* q, void* stream);
+
 /* ---- melt-pool capture (build-defined, opt-in; csrc/k_capture.hip, model in include/dedflow.h)
  *    dfl_capture_flag       one thread per particle: the decision of include/dedflow.h from tet / lambda (of a locate just
  *                           run), the node coordinates xg and the fluid state w [6N].  keep[i] = 0 when captured, else 1;
