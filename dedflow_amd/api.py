@@ -699,6 +699,12 @@ class DflPhaseChangeStats(C.Structure):
                 ("hi", C.c_double * 3)]
 
 
+class DflThermalMaterial(C.Structure):
+    _fields_ = [("k_gas", C.c_double), ("k_solid", C.c_double), ("k_liquid", C.c_double), ("c_gas", C.c_double),
+                ("c_metal", C.c_double), ("T_solidus", C.c_double), ("T_liquidus", C.c_double), ("use_phi", C.c_int32),
+                ("level", C.c_double), ("side", C.c_int32), ("eps", C.c_double)]
+
+
 class DflRedistance(C.Structure):
     _fields_ = [("level", C.c_double), ("band", C.c_double), ("hold_groups", C.c_int32), ("every", C.c_int32)]
 
@@ -871,6 +877,10 @@ def _declare(L):
     f("DflPhaseChangeCheck", C.c_int, [C.POINTER(DflPhaseChange), C.c_char_p, C.c_size_t])
     f("DflMeshPhaseCoefficients", None, [C.POINTER(Mesh3D), vp, vp, vp, vp])
     f("DflMeshPhaseChangeStats", None, [C.POINTER(Mesh3D), vp, C.POINTER(DflPhaseChangeStats)])
+    f("DflMeshSetThermalMaterial", None, [C.POINTER(Mesh3D), C.POINTER(DflThermalMaterial)])
+    f("DflMeshThermalMaterialEnabled", i32, [C.POINTER(Mesh3D)])
+    f("DflThermalMaterialCheck", C.c_int, [C.POINTER(DflThermalMaterial), C.c_char_p, C.c_size_t])
+    f("DflMeshThermalRows", None, [C.POINTER(Mesh3D), vp, vp, vp, vp, vp])
     f("DflMeshSetRedistance", None, [C.POINTER(Mesh3D), C.POINTER(DflRedistance)])
     f("DflMeshRedistanceEnabled", i32, [C.POINTER(Mesh3D)])
     f("DflRedistanceCheck", C.c_int, [C.POINTER(DflRedistance), C.c_char_p, C.c_size_t])
@@ -1141,6 +1151,41 @@ class Problem:
         lib().DflMeshPhaseChangeStats(self.mesh, w.ptr, C.byref(s))
         return dict(liquid_volume=float(s.liquid_volume), T_max=float(s.T_max), molten=int(s.molten), lo=np.array(s.lo[:]),
                     hi=np.array(s.hi[:]))
+
+    # ---- thermal material (include/dedflow.h, "thermal material") -------------------------------------------------------------
+    def set_thermal_material(self, k_gas=None, k_solid=None, k_liquid=None, c_gas=None, c_metal=None, T_solidus=0.0,
+                             T_liquidus=0.0, use_phi=False, level=0.0, side=1, eps=1.0):
+        """DflMeshSetThermalMaterial: conductivities (k_gas, k_solid, k_liquid; k_liquid None: k_solid) and capacities rho cp
+        (c_gas, c_metal; c_gas None: c_metal) of the T rows; k between solid and liquid follows the liquid fraction between
+        T_solidus and T_liquidus; use_phi: metal where side (phi - level) > 0, smeared over eps, gas elsewhere.  k_solid None
+        turns the feature off.  A configuration the library refuses (reported on stderr) leaves the mesh as it was:
+        thermal_material_on tells."""
+        if k_solid is None:
+            lib().DflMeshSetThermalMaterial(self.mesh, None)
+            return
+        k_liquid = k_solid if k_liquid is None else k_liquid
+        k_gas = k_solid if k_gas is None else k_gas
+        c_gas = c_metal if c_gas is None else c_gas
+        cfg = DflThermalMaterial(float(k_gas), float(k_solid), float(k_liquid), float(c_gas), float(c_metal), float(T_solidus),
+                                 float(T_liquidus), 1 if use_phi else 0, float(level), int(side), float(eps))
+        lib().DflMeshSetThermalMaterial(self.mesh, C.byref(cfg))
+
+    @property
+    def thermal_material_on(self):
+        return bool(lib().DflMeshThermalMaterialEnabled(self.mesh))
+
+    def thermal_rows(self, w, dw, want=("r", "Kn", "Cn")):
+        """DflMeshThermalRows at (w, dw) taken as the alpha states (DeviceArrays of 6N): a dict of the wanted outputs as
+        DeviceArrays of N, the T-row correction r and the nodal totals Kn, Cn; the others are passed as NULL"""
+        bad = set(want) - {"r", "Kn", "Cn"}
+        if bad:
+            raise ValueError(f"thermal_rows: unknown outputs {sorted(bad)}")
+        if not self.thermal_material_on:
+            raise RuntimeError("no thermal material is set: call set_thermal_material first")
+        out = {k: DeviceArray(self.N) for k in ("r", "Kn", "Cn") if k in want}
+        ptr = [out[k].ptr if k in out else None for k in ("r", "Kn", "Cn")]
+        lib().DflMeshThermalRows(self.mesh, w.ptr, dw.ptr, ptr[0], ptr[1], ptr[2])
+        return out
 
     # ---- level-set redistancing (include/dedflow.h, "level-set redistancing") ----------------------------------------------
     def set_redistance(self, level=None, band=None, hold_groups=0, every=0):

@@ -77,13 +77,6 @@ __device__ __forceinline__ int tet_parts(const TetPhase& b, const double* Tn, co
     return (coeff && !liquid ? 1 : 0) | (!solid ? 2 : 0);
 }
 
-__device__ __forceinline__ double smooth_step(double t) {  // Hs: the integral of the biweight kernel; a NaN gives 0
-    if (!(t > -1.0)) return 0.0;
-    if (t >= 1.0) return 1.0;
-    const double t2 = t * t, t3 = t2 * t;
-    return 0.5 + 0.9375 * ((t - (2.0 / 3.0) * t3) + 0.2 * (t3 * t2));
-}
-
 // s, fl, fl' and C of one temperature
 __device__ __forceinline__ void liquid_fraction(double Tq, const dfl_phase_params& p, double& fl, double& dfl, double& C) {
     const double range = p.T_liquidus - p.T_solidus;

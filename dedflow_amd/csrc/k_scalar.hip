@@ -5,7 +5,8 @@
 //   JT[a][b]   = sum_q w |det J| [ rho cp (N_a + rho cp tau3 c_a) (f1 N_b + f2 c_b) + f2 kappa gradN_a . gradN_b ]
 //
 // with c_a = u(q) . gradN_a, tau2 / tau3 as rhs_quad forms them at every quadrature point, f1 = alpha_m and
-// f2 = dt alpha_f gamma.  Both depend on the geometry and on u only.
+// f2 = dt alpha_f gamma.  Both depend on the geometry and on u only.  With a thermal material (include/dedflow.h) JT also gets
+// the entries jm of that section, from phi and T as well: the MATERIAL instantiation below, in the same single launch.
 //
 //   scalar_jac_row_kernel   row gather in the shape of node_gather.hpp (its constants and trip count; a Kuhn-cube interior
 //                           row has 15 nonzeros and 24 tets): a group of 16 lanes owns one nodal CSR row a.
@@ -17,13 +18,21 @@
 //                           bitwise reproducible, and independent of the assembly schedule of the (u,p) system.
 //
 // HBM view per assembly: 2 x 8 B x nnz1 of values written + row_ptr / col_ind (4 B x (N + nnz1)) + V2E (4 B x 4T) + per
-// (row, tet) pair the tet's ien line (16 B) and 4 x 48 B of coordinates and velocities gathered through L2.
-#include "node_gather.hpp"
+// (row, tet) pair the tet's ien line (16 B) and 4 x 48 B of coordinates and velocities gathered through L2 (MATERIAL: 4 x 8 B
+// of T more, and with use_phi 4 x 8 B of phi).
+#include <type_traits>
+#include "thermal_coeff.hpp"
 
 namespace {
 
-// the four entries (la, b) of both element matrices of one tet; la = the local index of the row's node
-__device__ __forceinline__ void scalar_tet_row(const double* x, const double* u, int la, double* jp, double* jt) {
+// the four entries (la, b) of both element matrices of one tet; la = the local index of the row's node.  MATERIAL: dk / dc =
+// the thermal-material differences at the four quadrature points (thermal_coeff.hpp), any = not all of them are 0; the entries
+//   jm[b] = sum_q w [ dc_q N_la (f1 N_b + f2 c_b) + f2 dk_q gradN_la . gradN_b ]
+// are formed beside the base ones from the same geometry and added to the finished jt[b] (the base is rounded first).  The
+// conduction part depends on q through dk_q alone, so it is w kg[b] (sum_q dk_q) / kKAPPA: jm[b] starts from it
+template <bool MATERIAL>
+__device__ __forceinline__ void scalar_tet_row(const double* x, const double* u, int la, double* jp, double* jt,
+                                               const double* dk = nullptr, const double* dc = nullptr, bool any = false) {
     double invJ[9], shg[12], G[9], detJ;
     tet_geometry(x, invJ, detJ, shg);
     tet_metric(shg, G);
@@ -41,6 +50,12 @@ __device__ __forceinline__ void scalar_tet_row(const double* x, const double* u,
         jp[b] = 0.0;
         jt[b] = 0.0;
         kg[b] = f2 * kKAPPA * (shg[la * 3] * shg[b * 3] + shg[la * 3 + 1] * shg[b * 3 + 1] + shg[la * 3 + 2] * shg[b * 3 + 2]);
+    }
+    double jm[4];
+    if constexpr (MATERIAL) {
+        const double sdk = w * ((((dk[0] + dk[1]) + dk[2]) + dk[3]) * (1.0 / kKAPPA));
+#pragma unroll
+        for (int b = 0; b < 4; ++b) jm[b] = sdk * kg[b];
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -73,15 +88,28 @@ __device__ __forceinline__ void scalar_tet_row(const double* x, const double* u,
             const double cb = f1 * shl(b, q) + f2 * c[b];
             jp[b] += rp * cb;
             jt[b] += rt * cb + w * kg[b];
+            if constexpr (MATERIAL)
+                if (any) jm[b] += ((w * dc[q]) * na) * cb;
         }
     }
+    if constexpr (MATERIAL)
+        if (any)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) jt[b] = jt[b] + jm[b];
 }
 
+struct NoMaterial {};
+template <bool MATERIAL>
+using MaterialArg = std::conditional_t<MATERIAL, dfl_thermal_params, NoMaterial>;
+
+// MATERIAL = false is the kernel of the one-material heat equation, unchanged.  MATERIAL = true (include/dedflow.h, "thermal
+// material") also gathers the tet's four phi and T beside x and u, forms dk_q / dc_q and parks jt[b] + jm[b]: one launch
+template <bool MATERIAL>
 __global__ __launch_bounds__(NG_BLK) void scalar_jac_row_kernel(I N, const I* __restrict__ vrow, const I* __restrict__ vcol,
                                                                  const I* __restrict__ ien, const T* __restrict__ xg,
                                                                  const T* __restrict__ wg, const I* __restrict__ row_ptr,
                                                                  const I* __restrict__ col_ind, T* __restrict__ vphi,
-                                                                 T* __restrict__ vT) {
+                                                                 T* __restrict__ vT, const MaterialArg<MATERIAL> mat) {
     __shared__ int4 s_node[NG_BLK];
     __shared__ double s_jp[NG_BLK][4];
     __shared__ double s_jt[NG_BLK][4];
@@ -115,7 +143,22 @@ __global__ __launch_bounds__(NG_BLK) void scalar_jac_row_kernel(I N, const I* __
                     }
                 const int la = n[0] == row ? 0 : n[1] == row ? 1 : n[2] == row ? 2 : 3;
                 double jp[4], jt[4];
-                scalar_tet_row(x, u, la, jp, jt);
+                if constexpr (MATERIAL) {
+                    double phi[4], Tn[4], m[4], kq[4], cq[4], dk[4], dc[4];
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) {
+                        phi[b] = mat.use_phi ? wg[4LL * N + n[b]] : 0.0;
+                        Tn[b] = wg[5LL * N + n[b]];
+                    }
+                    TetCross c;
+                    if (mat.use_phi) tet_cross(x, c);  // (the metal fraction as the row pass forms it: tet_levelset.hpp)
+                    thermal_metal_fraction(c, phi, mat, m);
+                    thermal_kc(m, Tn, mat, kq, cq);
+                    const bool any = thermal_differences(kq, cq, dk, dc);
+                    scalar_tet_row<true>(x, u, la, jp, jt, dk, dc, any);
+                } else {
+                    scalar_tet_row<false>(x, u, la, jp, jt);
+                }
                 s_node[t] = n4;
 #pragma unroll
                 for (int b = 0; b < 4; ++b) {
@@ -150,7 +193,16 @@ __global__ __launch_bounds__(NG_BLK) void scalar_jac_row_kernel(I N, const I* __
 extern "C" void dfl_assemble_scalar_jacobian(I N, const I* vrow, const I* vcol, const I* ien, const T* xg, const T* wgalpha,
                                              const I* row_ptr, const I* col_ind, T* val_phi, T* val_T, void* stream) {
     if (N <= 0 || (!val_phi && !val_T)) return;
-    scalar_jac_row_kernel<<<ceil_div(N, NG_ROWS), NG_BLK, 0, S(stream)>>>(N, vrow, vcol, ien, xg, wgalpha, row_ptr, col_ind,
-                                                                          val_phi, val_T);
+    scalar_jac_row_kernel<false><<<ceil_div(N, NG_ROWS), NG_BLK, 0, S(stream)>>>(N, vrow, vcol, ien, xg, wgalpha, row_ptr, col_ind,
+                                                                                 val_phi, val_T, NoMaterial{});
+    DFL_LAUNCH_CHECK();
+}
+
+extern "C" void dfl_assemble_scalar_jacobian_material(I N, const I* vrow, const I* vcol, const I* ien, const T* xg, const T* wgalpha,
+                                                      const I* row_ptr, const I* col_ind, const dfl_thermal_params* prm,
+                                                      T* val_phi, T* val_T, void* stream) {
+    if (N <= 0 || (!val_phi && !val_T)) return;
+    scalar_jac_row_kernel<true><<<ceil_div(N, NG_ROWS), NG_BLK, 0, S(stream)>>>(N, vrow, vcol, ien, xg, wgalpha, row_ptr, col_ind,
+                                                                                val_phi, val_T, *prm);
     DFL_LAUNCH_CHECK();
 }

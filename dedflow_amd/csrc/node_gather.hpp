@@ -1,6 +1,6 @@
 // The node gather over the sorted V2E map (one per mesh, host/mesh.c: every node's tets in ascending tet id), shared by the
-// free-surface pass (k_surface.hip), the phase-change pass (k_phase.hip) and, for its shape and trip count, the scalar
-// Jacobian rows (k_scalar.hip).
+// free-surface pass (k_surface.hip), the phase-change pass (k_phase.hip), the thermal-material rows (k_thermal.hip) and, for
+// its shape and trip count, the scalar Jacobian rows (k_scalar.hip).
 //
 // A group of NG_LANES = 16 lanes owns node a (NG_ROWS = 16 nodes per 256-thread workgroup; a Kuhn-cube interior node has 24
 // tets: two trips).  Lane j of the group takes tet j of a's list and evaluates the NC values of its own node, or leaves

@@ -1,6 +1,7 @@
 // The level-set geometry of one linear tet in closed form, shared by the capture decision (k_capture.hip), the free-surface
-// band (k_surface.hip) and the phase-change metal fraction (k_phase.hip).  The operation order is part of the model (two
-// kernels must take the same decision from the same numbers, and the numpy models reproduce it): every function switches
+// band (k_surface.hip), the phase-change metal fraction (k_phase.hip) and the thermal material (thermal_coeff.hpp).  The
+// operation order is part of the model (two kernels must take the same decision from the same numbers, and the numpy models
+// reproduce it): every function switches
 // fused multiply-add off for its own body, so the IEEE operations and their association do not depend on where this header
 // is included or on the contraction mode of the file around it.
 #pragma once
@@ -36,6 +37,15 @@ __device__ __forceinline__ bool tet_levelset(const TetCross& t, const double* ph
 #pragma unroll
     for (int a = 0; a < 4; ++a) d[a] = (phi[a] - level) / gn;
     return true;
+}
+
+// Hs: the integral of the biweight kernel, the metal fraction of the phase-change and thermal-material sections; a NaN gives 0
+__device__ __forceinline__ double smooth_step(double t) {
+#pragma clang fp contract(off)
+    if (!(t > -1.0)) return 0.0;
+    if (t >= 1.0) return 1.0;
+    const double t2 = t * t, t3 = t2 * t;
+    return 0.5 + 0.9375 * ((t - (2.0 / 3.0) * t3) + 0.2 * (t3 * t2));
 }
 
 }  // namespace

@@ -234,6 +234,9 @@ void DflAssembleSystemPrepacked(Mesh3D* mesh, f64* wgalpha, f64* dwgalpha, f64* 
     /* phase change (include/dedflow.h): the drag D u on the momentum rows and fact2 D on J's diagonal blocks, the latent term
        H dT on the T rows, before those rows are captured and before the Dirichlet rows */
     if (x->phase) DflPhaseApplySystem(mesh, wgalpha, dwgalpha, F, J, prepacked);
+    /* thermal material (include/dedflow.h): the T rows' correction to k_q and c_q, after the phase-change rows and before the
+       rows are captured; launched only when the scalar transport advances T */
+    if (F && x->thermal) DflThermalApplyRows(mesh, wgalpha, dwgalpha, F);
     x->nodep_current = FALSE;
     if (F && x->scalar) DflScalarCaptureResidual(mesh, F); /* the phi / T rows, kept for the scalar transport (host/scalar.c) */
     if (F) HIPGUARD(hipMemsetAsync(F + 4 * (size_t)num_node, 0, (size_t)num_node * sizeof(f64) * 2, s)); /* main.c:63-66 */

@@ -80,6 +80,7 @@ typedef struct MeshExt {
     struct SurfaceState* surface;  /* free-surface forces (host/surface.c, DflMeshSetSurfaceForces), NULL: off */
     struct PhaseState* phase;      /* phase change (host/phase.c, DflMeshSetPhaseChange), NULL: off */
     b32 phase_current;             /* its D and H already hold the alpha states the next driver assembly is given */
+    struct ThermalState* thermal;  /* thermal material (host/thermal.c, DflMeshSetThermalMaterial), NULL: off */
     struct RedistanceState* redistance; /* level-set redistancing (host/redistance.c, DflMeshSetRedistance), NULL: off */
     index_type *v2e_row, *v2e_col; /* device [N+1], [4T]: the sorted V2E map (DflMeshSortedV2E), NULL until first asked for */
 } MeshExt;
@@ -384,6 +385,7 @@ void DflScalarCaptureResidual(Mesh3D* mesh, const f64* F);        /* F[4N:6N) ->
 void DflScalarSolveIncrements(Mesh3D* mesh, f64* wgalpha, f64* dwgalpha, f64* dx2); /* Jacobians + both solves -> dx2 [2N] */
 void DflScalarNorms(Mesh3D* mesh, f64* out2);                      /* ||R_phi||, ||R_T|| of that residual (synchronises) */
 void DflScalarWork(Mesh3D* mesh, f64** F, f64** dx2);              /* scratch [6N], [2N] of DflScalarTransportSolve */
+b32 DflScalarAdvancesT(const Mesh3D* mesh);                        /* a transport is set and advances T */
 
 /* host/surface.c: the free-surface forces of a mesh */
 struct SurfaceState;
@@ -403,6 +405,15 @@ void DflPhaseFree(struct PhaseState* st);
 void DflPhaseApplySystem(Mesh3D* mesh, const f64* wgalpha, const f64* dwgalpha, f64* F, Matrix* J, b32 reuse);
 /* kALPHAM H on the diagonal of the T Jacobian values val_T over the nodal pattern attr */
 void DflPhaseApplyScalarJacobian(Mesh3D* mesh, const f64* wgalpha, const CSRAttr* attr, f64* val_T, b32 reuse);
+
+/* host/thermal.c: the thermal material of a mesh (no-ops while it is off) */
+struct ThermalState;
+void DflThermalFree(struct ThermalState* st);
+/* F[5N + a] += r[a] at the alpha states, one launch; nothing unless the mesh's scalar transport advances T (the rows are
+ * zeroed otherwise) */
+void DflThermalApplyRows(Mesh3D* mesh, const f64* wgalpha, const f64* dwgalpha, f64* F);
+/* the configuration as the kernels take it (the T Jacobian's MATERIAL launch, host/scalar.c), NULL: off */
+const dfl_thermal_params* DflThermalParams(const Mesh3D* mesh);
 
 /* host/redistance.c: the level-set redistancing of a mesh (no-ops while it is off) */
 struct RedistanceState;

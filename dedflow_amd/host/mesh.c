@@ -98,6 +98,7 @@ void Mesh3DDestroy(Mesh3D* m) {
         DflScalarFree(x->scalar);
         DflSurfaceFree(x->surface);
         DflPhaseFree(x->phase);
+        DflThermalFree(x->thermal);
         DflRedistanceFree(x->redistance);
         CdamFreeDevice(x->v2e_row, 0); /* after the feature states that borrowed it */
         CdamFreeDevice(x->v2e_col, 0);

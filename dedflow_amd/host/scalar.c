@@ -64,6 +64,11 @@ void DflMeshSetScalarTransport(Mesh3D* mesh, const DflScalarTransport* cfg) {
 
 b32 DflMeshScalarTransportEnabled(const Mesh3D* mesh) { return st_of(mesh) != NULL; }
 
+b32 DflScalarAdvancesT(const Mesh3D* mesh) {
+    const ScalarState* st = st_of(mesh);
+    return st && st->cfg.T;
+}
+
 f64* DflMeshScalarResidual(Mesh3D* mesh) {
     ScalarState* st = st_of(mesh);
     return st ? st->res : NULL;
@@ -123,13 +128,18 @@ static void assemble_scalar_jacobian(Mesh3D* mesh, f64* wgalpha, Matrix* Jphi, M
            "DflAssembleScalarJacobian: the matrices must lie over the nodal pattern");
     f64* vp = Jphi ? csr_own_values(Jphi) : NULL;
     f64* vt = JT ? csr_own_values(JT) : NULL;
+    /* thermal material (include/dedflow.h): the launch that forms JT is the MATERIAL instantiation, which adds the entries jm
+       per tet; Jphi gets the same bits from either */
+    const dfl_thermal_params* mat = JT ? DflThermalParams(mesh) : NULL;
     DflRangePush("AssembleScalarJacobian");
     if (ap && at && ap != at) { /* two pattern objects: one launch each */
         dfl_assemble_scalar_jacobian(N, vrow, vcol, dev->ien, dev->xg, wgalpha, ap->row_ptr, ap->col_ind, vp, NULL, s);
-        dfl_assemble_scalar_jacobian(N, vrow, vcol, dev->ien, dev->xg, wgalpha, at->row_ptr, at->col_ind, NULL, vt, s);
+        if (mat) dfl_assemble_scalar_jacobian_material(N, vrow, vcol, dev->ien, dev->xg, wgalpha, at->row_ptr, at->col_ind, mat, NULL, vt, s);
+        else dfl_assemble_scalar_jacobian(N, vrow, vcol, dev->ien, dev->xg, wgalpha, at->row_ptr, at->col_ind, NULL, vt, s);
     } else {
         const CSRAttr* a = ap ? ap : at;
-        dfl_assemble_scalar_jacobian(N, vrow, vcol, dev->ien, dev->xg, wgalpha, a->row_ptr, a->col_ind, vp, vt, s);
+        if (mat) dfl_assemble_scalar_jacobian_material(N, vrow, vcol, dev->ien, dev->xg, wgalpha, a->row_ptr, a->col_ind, mat, vp, vt, s);
+        else dfl_assemble_scalar_jacobian(N, vrow, vcol, dev->ien, dev->xg, wgalpha, a->row_ptr, a->col_ind, vp, vt, s);
     }
     /* latent heat (include/dedflow.h, "phase change"): kALPHAM H on the T diagonal, before the Dirichlet unit rows */
     if (JT && ((MeshExt*)mesh->ext)->phase) DflPhaseApplyScalarJacobian(mesh, wgalpha, at, vt, phase_reuse);

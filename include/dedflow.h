@@ -1414,6 +1414,64 @@ void DflMeshPhaseCoefficients(Mesh3D* mesh, const f64* w, f64* D, f64* H, f64* G
  * empty-set values */
 void DflMeshPhaseChangeStats(Mesh3D* mesh, const f64* w, DflPhaseChangeStats* out);
 
+/* ---- thermal material: conductivity and heat capacity follow phi (build-defined; opt-in) --------------------------------
+ * The reference's heat equation has one material: the T rows use kKAPPA = 0.66 and kRHO kCP = 1000 everywhere, so the
+ * shielding gas conducts and stores heat as the metal does.  A mesh that never calls DflMeshSetThermalMaterial with a
+ * configuration, or clears it with NULL, computes bit for bit what it computes without this section, through the same
+ * launches.  One GPU only.  With a configuration the Galerkin part of the T rows becomes the one with the conductivity k_q
+ * and the capacity c_q below, by a correction with the differences to the built-in constants.
+ *   per tet     grad N_a, det, g, |g|, d_a, d_q, m_q = Hs(side d_q / eps) and the rule for a tet with !(|g| > 0) exactly as
+ *               the phase-change section forms them (the same closed form, without fused multiply-add); without use_phi
+ *               m_q = 1.  T_q = sum_a N_a(q) T_a, fl_q = fl(T_q), the smoothstep of the phase-change section between
+ *               T_solidus and T_liquidus; a NaN T_q gives 0, and fl_q = 0 when k_liquid == k_solid (the two temperatures are
+ *               then not read).
+ *                 k_q = k_gas + m_q ((k_solid + fl_q (k_liquid - k_solid)) - k_gas)      dk_q = k_q - kKAPPA
+ *                 c_q = c_gas + m_q (c_metal - c_gas)                                    dc_q = c_q - kRHO kCP
+ *               W = |det| / 24 and the four quadrature points of the assembly.
+ *   rows        at the alpha states (T, u from wgalpha, dT from dwgalpha), gT = sum_b T_b grad N_b, u_q and dT_q interpolated
+ *               as the assembly does: the contribution of tet e to node a is
+ *                 r_a(e) = sum_q W [ dc_q N_a(q) (dT_q + u_q . gT) + dk_q (grad N_a . gT) ],
+ *               with the sign of the base terms btc shl + kKAPPA grad . shg of the element residual, so that base + correction
+ *               is the Galerkin T row with c_q and k_q.  r[a] = the sum over a's tets in ascending tet id, from +0.0; a tet
+ *               whose eight dk_q, dc_q are all exactly 0 adds +0.0.  One launch over the nodes' sorted tet lists
+ *               (csrc/k_thermal.hip), no float atomics, bitwise reproducible, the same under every assembly schedule.  Every F
+ *               assembly adds r[a] to R[5N + a] after the phase-change rows and before the T rows are saved for the scalar
+ *               transport; only when that transport advances T (otherwise the rows are zeroed anyway and nothing is launched).
+ *               The capacity correction is the consistent one on purpose: the base term is the consistent mass with
+ *               kRHO kCP, and a lumped correction would leave c0 M_c + (c - c0) M_l, which is indefinite for c < 0.8 c0
+ *               (the smallest eigenvalue of M_l^-1 M_c on linear tets is 1/5) -- the gas.  With the consistent form the total
+ *               is sum_q W c_q N_a N_b, positive definite whenever c_q > 0.
+ *   Jacobian    DflAssembleScalarJacobian adds to every tet's entries of the T Jacobian, coefficients frozen at the alpha states,
+ *                 jm_ab(e) = sum_q W [ dc_q N_a(q) (f1 N_b(q) + f2 u_q . grad N_b) + f2 dk_q grad N_a . grad N_b ],
+ *               f1 = kALPHAM, f2 = kDT kALPHAF kGAMMA: the tet's entry is base + jm (the base rounded first), summed over the
+ *               row's tets in ascending tet id as without the section, in the same single launch, before the phase-change
+ *               diagonal and the Dirichlet unit rows.  This is Picard in fl, as H is in the phase-change section; with
+ *               k_liquid == k_solid it is the exact derivative.  The phi Jacobian is untouched.
+ *   inspection  Kn[a] = sum W N_a(q) k_q and Cn[a] = sum W N_a(q) c_q (totals, not differences): divided by the nodal volume
+ *               they are the node's mean conductivity and capacity.
+ * Limits: one GPU (SolveFlowSystem and DflTimeStep with a communicator print why and return -1); the SUPG part of the T row
+ * keeps kRHO kCP and kKAPPA (tau3 and its test-function factor): it stays a positive streamline-diffusion term, mis-scaled
+ * by c_q / (kRHO kCP); no density change in the momentum rows; k does not depend on T other than through fl.  A 1000 : 1
+ * conductivity jump costs the Jacobi-preconditioned T solve iterations: PC_AMGX (DflScalarTransport.pc) is the remedy. */
+typedef struct DflThermalMaterial {
+    f64 k_gas, k_solid, k_liquid;     /* W/(m K), each > 0 */
+    f64 c_gas, c_metal;               /* rho cp, J/(m^3 K), each > 0 */
+    f64 T_solidus, T_liquidus;        /* read only when k_liquid != k_solid; then T_liquidus > T_solidus */
+    b32 use_phi; f64 level; index_type side; f64 eps;   /* as DflPhaseChange; use_phi 0: metal everywhere */
+} DflThermalMaterial;
+/* host only: 0 when DflMeshSetThermalMaterial accepts the configuration, else why not in `why`.  Refused: any non-finite
+ * value, any of the five coefficients <= 0, k_liquid != k_solid with T_liquidus <= T_solidus, use_phi with side not +-1 or
+ * eps <= 0 */
+int  DflThermalMaterialCheck(const DflThermalMaterial* cfg, char* why, size_t why_len);
+/* the configuration is copied; NULL: off.  A refused configuration is reported on stderr and leaves the mesh unchanged.  Has
+ * the mesh build the sorted tet lists of the nodes if nothing did before (shared, freed with the mesh) and synchronises: the
+ * later calls allocate nothing and do not wait for the device */
+void DflMeshSetThermalMaterial(Mesh3D* mesh, const DflThermalMaterial* cfg);
+b32  DflMeshThermalMaterialEnabled(const Mesh3D* mesh);
+/* w, dw: device 6N, taken as the alpha states; r, Kn, Cn [N] on the device, any of them NULL, every other one overwritten in
+ * full.  Without a configuration: a line on stderr, nothing written */
+void DflMeshThermalRows(Mesh3D* mesh, const f64* w, const f64* dw, f64* r, f64* Kn, f64* Cn);
+
 /* ---- level-set redistancing: the exact band distance to the surface phi = level (build-defined; opt-in) -----------------
  * The reference advects phi and never restores |grad phi| = 1.  A mesh that never calls DflMeshSetRedistance with a
  * configuration, or clears it with NULL, computes bit for bit what it computes without this section, through the same

@@ -925,6 +925,36 @@ dfl_index dfl_phase_stats_work_size(void);
 void dfl_phase_stats(dfl_index N, const dfl_value* xg, const dfl_value* w, const dfl_value* G, const dfl_phase_params* prm,
                      dfl_value* work, dfl_value* out9, void* stream);
 
+/* ---- thermal material (build-defined, opt-in; host/thermal.c, csrc/k_thermal.hip, csrc/k_scalar.hip, model in include/dedflow.h)
+ *    dfl_thermal_rows        the node sums r [N] (W), Kn [N] (W m / K), Cn [N] (J / K) at the states w, dw [6N] (taken as the
+ *                            alpha states); any of them NULL: not written, the others overwritten in full.  vrow / vcol: the
+ *                            V2E map of the tets with every list ascending.  The node gather of the phase-change pass: a lane
+ *                            per (node, tet), the shares added in list order through LDS, no atomics, bitwise reproducible.
+ *                            r alone: a tet whose dk_q and dc_q are all exactly 0 leaves early; its share of r is +0.0 in
+ *                            either case.
+ *    dfl_thermal_add_rows    the same r, added by its owner lane to FT[a] (the T rows F + 5N of an assembly): FT[a] += r[a],
+ *                            r[a] summed and rounded first.  One launch, no buffer.
+ *    dfl_assemble_scalar_jacobian_material   dfl_assemble_scalar_jacobian with the entries jm of the section added to every
+ *                            tet's T entries before they are summed (the base entry is rounded first); val_phi gets the bits of
+ *                            the plain launcher.  wgalpha: u, phi and T are read.
+ * Every launcher returns at once for N <= 0. */
+typedef struct dfl_thermal_params {
+    dfl_value k_gas, k_solid, k_liquid, c_gas, c_metal;
+    dfl_value T_solidus, T_liquidus;
+    dfl_value level, side, eps;
+    int use_phi;
+} dfl_thermal_params;
+void dfl_thermal_rows(dfl_index N, const dfl_index* vrow, const dfl_index* vcol, const dfl_index* ien, const dfl_value* xg,
+                      const dfl_value* w, const dfl_value* dw, const dfl_thermal_params* prm, dfl_value* r, dfl_value* Kn,
+                      dfl_value* Cn, void* stream);
+void dfl_thermal_add_rows(dfl_index N, const dfl_index* vrow, const dfl_index* vcol, const dfl_index* ien, const dfl_value* xg,
+                          const dfl_value* wgalpha, const dfl_value* dwgalpha, const dfl_thermal_params* prm, dfl_value* FT,
+                          void* stream);
+void dfl_assemble_scalar_jacobian_material(dfl_index N, const dfl_index* vrow, const dfl_index* vcol, const dfl_index* ien,
+                                           const dfl_value* xg, const dfl_value* wgalpha, const dfl_index* row_ptr,
+                                           const dfl_index* col_ind, const dfl_thermal_params* prm, dfl_value* val_phi,
+                                           dfl_value* val_T, void* stream);
+
 /* ---- level-set redistancing (build-defined, opt-in; host/redistance.c, csrc/k_redistance.hip, model in include/dedflow.h)
  * phi = w + 4N.  grid: the uniform cell grid over the mesh's bounding box; a point's cell per axis is
  * clamp(floor((x - lo) inv_h), 0, n - 1), cell id = cx + n[0] (cy + n[1] cz).
