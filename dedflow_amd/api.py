@@ -174,7 +174,7 @@ class CSRAttr(C.Structure):
 
 
 CSRAttr._fields_ = [("num_row", C.c_int32), ("num_col", C.c_int32), ("nnz", C.c_int32), ("row_ptr", vp), ("col_ind", vp),
-                    ("parent", C.POINTER(CSRAttr))]
+                    ("parent", C.POINTER(CSRAttr)), ("diag_pos", vp)]
 
 
 class Matrix(C.Structure):
@@ -789,6 +789,11 @@ def _declare(L):
     f("dfl_bcsr_spmv_x4", None, [i32, i32, i32, vp, vp, vp, f64, vp, vp, vp])
     f("dfl_bcsr_spmv_x4_scaled", None, [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp])
     f("dfl_interleave4", None, [i32, i32, i32, vp, vp, vp])
+    # the products that write M^-1 of their own output (N, rp, ci, diag_pos, val, [d_nrm,] x4, y, z4_out, stream)
+    f("dfl_bcsr_spmv_x4_pc", C.c_int, [i32, vp, vp, vp, vp, vp, vp, vp, vp])
+    f("dfl_bcsr_spmv_x4_scaled_pc", C.c_int, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp])
+    f("dfl_bcsr_diag_pos", None, [i32, vp, vp, vp, vp])
+    f("DflKrylovLastFoldedProducts", C.c_int, [vp])
     f("DflKrylovLastGmresStep", C.c_int, [vp])
     f("DflKrylovLastGmresPairs", None, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)])
     f("DflKrylovLastGmresBlocks", None, [vp, C.POINTER(C.c_int * 5), C.POINTER(C.c_int)])

@@ -35,11 +35,20 @@ __global__ __launch_bounds__(BLK) void interleave4_kernel(I node0, I node1, I N,
 }
 // The U column indices of a trip come with ONE load per row group (lane l fetches ci[k + l % U]) and are passed round with
 // shuffles, instead of U broadcast loads.  DSCALE: y = tot * (1.0 / *d_nrm) instead of alpha * tot -- the raw-basis GMRES step
-// folds the normalisation of the Krylov column into the matvec that consumes M^-1 of it (host/gmres.c)
-template <bool DSCALE>
-__global__ __launch_bounds__(BLK) void bcsr_spmv_x4_kernel(I row0, I nrows, I N, const I* __restrict__ rp, const I* __restrict__ ci,
-                                                          const T* __restrict__ val, T alpha, const T* __restrict__ x4,
-                                                          T* __restrict__ y, const T* __restrict__ d_nrm) {
+// folds the normalisation of the Krylov column into the matvec that consumes M^-1 of it (host/gmres.c).
+// FOLD: the row group also writes z4_out[row][4] = M^-1 y_row of the block-Jacobi tree, for the product that follows in a
+// block of Krylov steps: it holds the row's four components of y after the pair reduction and has streamed the row's
+// diagonal block (nonzero diag_pos[row]; each lane keeps its two entries as they pass).  Same inverse (inv3) and same
+// expressions as pc_setup_kernel + pc_apply_kernel; y is stored as without FOLD.  z4_out must not be x4 (rows of one launch
+// gather x4 of arbitrary other rows)
+__device__ __forceinline__ void inv3(const double* m, double* o);
+// (FOLD: seven waves per SIMD asked for, as the plain kernel has -- left alone the compiler takes 76 VGPRs for it, six waves)
+template <bool DSCALE, bool FOLD>
+__global__ __launch_bounds__(BLK, FOLD ? 7 : 1) void bcsr_spmv_x4_kernel(I row0, I nrows, I N, const I* __restrict__ rp,
+                                                          const I* __restrict__ ci, const T* __restrict__ val, T alpha,
+                                                          const T* __restrict__ x4,
+                                                          T* __restrict__ y, const T* __restrict__ d_nrm,
+                                                          const I* __restrict__ diag_pos, T* __restrict__ z4_out) {
     constexpr int U = 4;  // nodal nonzeros per loop trip
     long long blk = blockIdx.x;
     const long long per = gridDim.x >> 3;  // grid is a multiple of 8
@@ -54,6 +63,9 @@ __global__ __launch_bounds__(BLK) void bcsr_spmv_x4_kernel(I row0, I nrows, I N,
     const int s = rp[row], e = rp[row + 1];
     const d2v* __restrict__ v2 = reinterpret_cast<const d2v*>(val) + l;
     const d2v* __restrict__ xv = reinterpret_cast<const d2v*>(x4) + hi;
+    int dp = 0;
+    d2v dd = {0.0, 0.0};  // FOLD: entries (2l, 2l+1) of the row's diagonal block
+    if constexpr (FOLD) dp = diag_pos[row];
     double acc[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) acc[u] = 0.0;
@@ -68,23 +80,54 @@ __global__ __launch_bounds__(BLK) void bcsr_spmv_x4_kernel(I row0, I nrows, I N,
         for (int u = 0; u < U; ++u) a[u] = ld_val(v2 + (long long)(k + u) * 8);
 #pragma unroll
         for (int u = 0; u < U; ++u) xx[u] = xv[2LL * c[u]];
+        // (without this the scheduler, with the diagonal's registers to place, waits for the first gather before it issues the
+        // other three: one more trip to L2 per loop trip)
+        if constexpr (FOLD) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int u = 0; u < U; ++u) acc[u] += a[u].x * xx[u].x + a[u].y * xx[u].y;
+        if constexpr (FOLD) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) dd = (k + u == dp) ? a[u] : dd;
+        }
     }
     for (; k < e; ++k) {
         const int c0 = ci[k];
         const d2v a0 = ld_val(v2 + (long long)k * 8);
         const d2v x0 = xv[2LL * c0];
         acc[0] += a0.x * x0.x + a0.y * x0.y;
+        if constexpr (FOLD) dd = (k == dp) ? a0 : dd;
     }
     double tot = acc[0];
 #pragma unroll
     for (int u = 1; u < U; ++u) tot += acc[u];
     tot += __shfl_xor(tot, 1, WAVE);
-    if (DSCALE) {
-        if (!hi) y[xidx(row, r, N3)] = tot * (1.0 / d_nrm[0]);
+    if constexpr (!FOLD) {
+        if (DSCALE) {
+            if (!hi) y[xidx(row, r, N3)] = tot * (1.0 / d_nrm[0]);
+        } else {
+            if (!hi) y[xidx(row, r, N3)] = alpha * tot;
+        }
     } else {
-        if (!hi) y[xidx(row, r, N3)] = alpha * tot;
+        const double yv = DSCALE ? tot * (1.0 / d_nrm[0]) : alpha * tot;  // both lanes of a pair: the fold reads it from either
+        if (!hi) y[xidx(row, r, N3)] = yv;
+        // lane 2r holds D[r][0], D[r][1], lane 2r+1 holds D[r][2], D[r][3]; both lanes of a pair hold y_r
+        double m[9], o[9];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            m[3 * q + 0] = __shfl(dd.x, 2 * q, 8);
+            m[3 * q + 1] = __shfl(dd.y, 2 * q, 8);
+            m[3 * q + 2] = __shfl(dd.x, 2 * q + 1, 8);
+        }
+        const double x0 = __shfl(yv, 0, 8), x1 = __shfl(yv, 2, 8), x2 = __shfl(yv, 4, 8);
+        inv3(m, o);  // row-major inv(D) == the column-major image A of pc_apply_kernel: A(r,c) = o[r + 3c]
+        d2v* out = reinterpret_cast<d2v*>(z4_out + 4LL * row);
+        if (l == 0) {
+            const d2v z01 = {o[0] * x0 + o[3] * x1 + o[6] * x2, o[1] * x0 + o[4] * x1 + o[7] * x2};
+            out[0] = z01;
+        } else if (l == 7) {  // this lane holds D[3][3] and y_p
+            const d2v z2p = {o[2] * x0 + o[5] * x1 + o[8] * x2, yv * (1.0 / dd.y)};
+            out[1] = z2p;
+        }
     }
 }
 
@@ -243,6 +286,11 @@ __device__ __forceinline__ int find_diag(const I* __restrict__ rp, const I* __re
         if (ci[mid] < node) lo = mid + 1; else hi = mid;
     }
     return lo;
+}
+
+__global__ __launch_bounds__(BLK) void diag_pos_kernel(I N, const I* __restrict__ rp, const I* __restrict__ ci, I* __restrict__ diag_pos) {
+    const int node = blockIdx.x * BLK + threadIdx.x;
+    if (node < N) diag_pos[node] = find_diag(rp, ci, node);
 }
 
 // closed-form inverse of a 3x3 given row-major m; returns inverse row-major
@@ -712,7 +760,7 @@ void dfl_bcsr_spmv_x4(I row0, I row1, I N, const I* rp, const I* ci, const T* va
     const int grid = ceil_div((long long)(row1 - row0) * 8, BLK);
     const int grid8 = (grid + 7) & ~7;
     // (column indices by one cooperative load per row group and trip: 0.4990 against 0.5027 ms back to back)
-    bcsr_spmv_x4_kernel<false><<<grid8, BLK, 0, S(stream)>>>(row0, row1, N, rp, ci, val, alpha, x4, y, nullptr);
+    bcsr_spmv_x4_kernel<false, false><<<grid8, BLK, 0, S(stream)>>>(row0, row1, N, rp, ci, val, alpha, x4, y, nullptr, nullptr, nullptr);
     DFL_LAUNCH_CHECK();
 }
 void dfl_bcsr_spmv_x4_scaled(I row0, I row1, I N, const I* rp, const I* ci, const T* val, const T* d_nrm, const T* x4, T* y,
@@ -720,7 +768,32 @@ void dfl_bcsr_spmv_x4_scaled(I row0, I row1, I N, const I* rp, const I* ci, cons
     if (row1 <= row0) return;
     const int grid = ceil_div((long long)(row1 - row0) * 8, BLK);
     const int grid8 = (grid + 7) & ~7;
-    bcsr_spmv_x4_kernel<true><<<grid8, BLK, 0, S(stream)>>>(row0, row1, N, rp, ci, val, 1.0, x4, y, d_nrm);
+    bcsr_spmv_x4_kernel<true, false><<<grid8, BLK, 0, S(stream)>>>(row0, row1, N, rp, ci, val, 1.0, x4, y, d_nrm, nullptr, nullptr);
+    DFL_LAUNCH_CHECK();
+}
+// the two products above over all N rows, each row group also writing z4_out[row][4] = M^-1 y_row (block-Jacobi tree; diag_pos:
+// dfl_bcsr_diag_pos).  Returns 0, or -1 without a launch when z4_out is the buffer x4 is gathered from
+int dfl_bcsr_spmv_x4_pc(I N, const I* rp, const I* ci, const I* diag_pos, const T* val, const T* x4, T* y, T* z4_out, void* stream) {
+    if (z4_out == x4 || !z4_out || !diag_pos) return -1;
+    if (N <= 0) return 0;
+    const int grid8 = (ceil_div((long long)N * 8, BLK) + 7) & ~7;
+    bcsr_spmv_x4_kernel<false, true><<<grid8, BLK, 0, S(stream)>>>(0, N, N, rp, ci, val, 1.0, x4, y, nullptr, diag_pos, z4_out);
+    DFL_LAUNCH_CHECK();
+    return 0;
+}
+int dfl_bcsr_spmv_x4_scaled_pc(I N, const I* rp, const I* ci, const I* diag_pos, const T* val, const T* d_nrm, const T* x4, T* y,
+                               T* z4_out, void* stream) {
+    if (z4_out == x4 || !z4_out || !diag_pos) return -1;
+    if (N <= 0) return 0;
+    const int grid8 = (ceil_div((long long)N * 8, BLK) + 7) & ~7;
+    bcsr_spmv_x4_kernel<true, true><<<grid8, BLK, 0, S(stream)>>>(0, N, N, rp, ci, val, 1.0, x4, y, d_nrm, diag_pos, z4_out);
+    DFL_LAUNCH_CHECK();
+    return 0;
+}
+// diag_pos[row] = the nonzero that pc_setup_kernel inverts for this row (the stored diagonal; col_ind sorted per row)
+void dfl_bcsr_diag_pos(I N, const I* rp, const I* ci, I* diag_pos, void* stream) {
+    if (N <= 0) return;
+    diag_pos_kernel<<<ceil_div(N, BLK), BLK, 0, S(stream)>>>(N, rp, ci, diag_pos);
     DFL_LAUNCH_CHECK();
 }
 void dfl_bcsr_values_to_f32(int64_t n, const T* val, float* valf, void* stream) {

@@ -65,8 +65,7 @@ void DflWsEnsure(KrylovExt* x, index_type n, index_type maxit, index_type ldh, i
     if (x->ws_n == n && x->ws_maxit == maxit && x->ws_hist >= hist && x->ws_pooled == DflWsInPool()) return;
     DflWsFree(x);
     x->ws_pooled = DflWsInPool();
-    x->Q = ws_vec_malloc((ptrdiff_t)n * (maxit + 2)); /* + one column: the interleaved copy z4 the matvec gathers from shares
-                                                          the basis block, and with it the placement the calibration chose */
+    x->Q = ws_vec_malloc((ptrdiff_t)n * (maxit + 1 + DFL_BASIS_SPARE_COLS)); /* + the interleaved copies z4, z4b */
     x->q_pooled = x->ws_pooled;
     x->H = (f64*)CdamMallocDevice((ptrdiff_t)ldh * maxit * SIZE_OF(f64));
     x->tmp = ws_vec_malloc((ptrdiff_t)n * 2);
@@ -182,8 +181,9 @@ void DflPcApplyFused(PC* pc, index_type na, f64* w, const f64* d_nrm, f64* z) { 
    Read at every solve (A/B): eager host reads, boundary rows on the library stream, three launches per fused-norm step,
    DFL_GMRES_RAW_BASIS=0 (one GPU: the normalised basis and the separate Jacobi pass instead of GMRES_STEP_RAW_BASIS),
    DFL_GMRES_BLOCK=1..4 (the most iterations the raw-basis step takes per pass over the basis, default 4), DFL_GMRES_TWO_STEP=0
-   (the same as block 1: one iteration at a time) */
-typedef struct GmresEnv { b32 x4; index_type x4_min; b32 eager_sync, no_side_rows, no_fused_update_pc, raw_basis; int block; } GmresEnv;
+   (the same as block 1: one iteration at a time), DFL_GMRES_FOLD_PC=0 (pairs and blocks: a Jacobi launch between two products
+   instead of the product that writes M^-1 of its own output) */
+typedef struct GmresEnv { b32 x4; index_type x4_min; b32 eager_sync, no_side_rows, no_fused_update_pc, raw_basis; int block; b32 fold_pc; } GmresEnv;
 static GmresEnv gmres_env(void) {
     static int x4 = -1, x4_min = 4096;
     if (x4 < 0) {
@@ -207,8 +207,9 @@ static GmresEnv gmres_env(void) {
         }
     }
     if (two && atoi(two) == 0) block = 1;
+    const char* fold = getenv("DFL_GMRES_FOLD_PC");
     const GmresEnv e = {x4, x4_min, getenv("DFL_KRYLOV_EAGER_SYNC") != NULL, getenv("DFL_NO_SIDE_BOUNDARY_ROWS") != NULL,
-                        getenv("DFL_NO_FUSED_UPDATE_PC") != NULL, !(raw && atoi(raw) == 0), block};
+                        getenv("DFL_NO_FUSED_UPDATE_PC") != NULL, !(raw && atoi(raw) == 0), block, !(fold && atoi(fold) == 0)};
     return e;
 }
 
@@ -263,6 +264,12 @@ void DflGmresPlanFill(GmresPlan* p, const KrylovExt* ex, index_type max_iter, Ma
     if (p->step == GMRES_STEP_REFERENCE && p->x4_skip_z && p->rows == p->N && env.raw_basis) {
         p->step = GMRES_STEP_RAW_BASIS;
         p->block = env.block;
+        /* between two products of a pair or block the Jacobi launch only read the product just stored and the inverse blocks to
+           write z4: the row group that forms a row of the product holds its four components and has streamed the row's diagonal
+           block, and writes z4 itself -- into the other of two interleaved copies, as rows of the same launch still gather from
+           the one it reads */
+        p->fold_pc = env.fold_pc && p->block > 1 && ((MatrixFS*)A->data)->spy1x1->diag_pos != NULL;
+        if (p->fold_pc) p->z4b = p->z4 + (size_t)na;
     }
 }
 
@@ -401,6 +408,29 @@ static void gmres_orthogonalise(const GmresPlan* p, KrylovExt* ex, index_type it
     }
 }
 
+/* The sb products of a pair or block that starts at column k: p_0 = (A z4) / nrm[k] into p0 (column k+1), p_i = A M^-1 p_{i-1}
+   into column k+1+i.  At entry z4 (buffer 0) holds M^-1 r_k (k == 0: made here).  fold_pc: product i gathers from buffer i % 2 and,
+   unless it is the last, writes M^-1 p_i into buffer (i + 1) % 2 itself; the last one is the plain kernel -- its successor's z4
+   comes from the fix-up, which writes buffer 0 as the k == 0 application does.  Otherwise a Jacobi launch between two products */
+static void gmres_products(const GmresPlan* p, KrylovExt* ex, Matrix* A, PC* pc, index_type k, int sb, f64* p0) {
+    const index_type na = p->na;
+    f64* const zb[2] = {p->z4, p->z4b};
+    if (k == 0) DFL_TIMED(DFL_TAG_PC, (void)DflPcApplyFusedX4(pc, na, ex->Q, NULL, NULL, p->z4));
+    for (int i = 0; i < sb; ++i) {
+        f64* const y = p0 + (size_t)i * (size_t)na;
+        const f64* const d_nrm = i == 0 ? ex->nrm + k : NULL;
+        if (p->fold_pc && i + 1 < sb) {
+            DFL_TIMED(DFL_TAG_SPMV, DflMatrixFSMatVecX4Pc(A, zb[i % 2], d_nrm, y, zb[(i + 1) % 2]));
+            ex->last_folded++;
+            continue;
+        }
+        f64* const src = p->fold_pc ? zb[i % 2] : p->z4;
+        if (i > 0 && !p->fold_pc) DFL_TIMED(DFL_TAG_PC, (void)DflPcApplyFusedX4(pc, na, y - (size_t)na, NULL, NULL, p->z4));
+        if (d_nrm) DFL_TIMED(DFL_TAG_SPMV, DflMatrixFSMatVecX4RangeScaled(A, src, d_nrm, y, 0, p->x4_N));
+        else DFL_TIMED(DFL_TAG_SPMV, DflMatrixFSMatVecX4Range(A, src, y, 0, p->x4_N));
+    }
+}
+
 /* Iterations k and k+1 of a cycle in one pass over the basis (GmresPlan.block >= 2).  At entry column k holds r_k and, k > 0, z4 holds
    M^-1 r_k.  p1 = B v_k = (A z4) / nrm[k] into column k+1, z4 = M^-1 p1, p2 = B p1 = A z4 into column k+2 -- in exact arithmetic
    the component of p2 orthogonal to v_0..v_{k+1} is a multiple of v_{k+2}, because B v_j lies in span(v_0..v_{j+1}).  One dots
@@ -415,10 +445,7 @@ static void gmres_pair(const GmresPlan* p, KrylovExt* ex, Matrix* A, PC* pc, ind
     f64 *const c1 = ex->pair_buf, *const c2 = c1 + ldh, *const e = c2 + ldh, *const sc = e + ldh;
     f64 *const h1 = ex->H + (size_t)k * (size_t)ldh, *const h1_raw = ex->h_unrot + (size_t)k * (size_t)ldh;
     const int g2 = dfl_cgs_update2_parts(na), g1 = (int)CEIL_DIV(p->N, 256);
-    if (k == 0) DFL_TIMED(DFL_TAG_PC, (void)DflPcApplyFusedX4(pc, na, Q, NULL, NULL, p->z4));
-    DFL_TIMED(DFL_TAG_SPMV, DflMatrixFSMatVecX4RangeScaled(A, p->z4, ex->nrm + k, p1, 0, p->x4_N));
-    DFL_TIMED(DFL_TAG_PC, (void)DflPcApplyFusedX4(pc, na, p1, NULL, NULL, p->z4));
-    DFL_TIMED(DFL_TAG_SPMV, DflMatrixFSMatVecX4Range(A, p->z4, p2, 0, p->x4_N));
+    gmres_products(p, ex, A, pc, k, 2, p1);
     DFL_TIMED(DFL_TAG_CGS_DOTS, dfl_cgs_dots2_raw(na, k + 1, Q, na, p1, p2, ex->nrm, h1, h1_raw, c1, e, c2, ex->work, s));
     DFL_TIMED(DFL_TAG_CGS_UPDATE, dfl_cgs_update2(na, k + 1, Q, na, c1, c2, p1, p2, ex->work, s));
     dfl_gmres_pair_first(g2, ex->work, k, ex->nrm, ex->H, ex->h_unrot, ldh, ex->gv, ex->beta, res_hist, sc, s);
@@ -440,12 +467,7 @@ static void gmres_block(const GmresPlan* p, KrylovExt* ex, Matrix* A, PC* pc, in
     f64 *const c = ex->pair_buf, *const e = c + 4 * (size_t)ldh, *const sc = e + 4 * (size_t)ldh;
     f64 *const h = ex->H + (size_t)k * (size_t)ldh, *const h_raw = ex->h_unrot + (size_t)k * (size_t)ldh;
     const int gu = dfl_cgs_update_block_parts(na, sb), gf = (int)CEIL_DIV(p->N, 256);
-    if (k == 0) DFL_TIMED(DFL_TAG_PC, (void)DflPcApplyFusedX4(pc, na, Q, NULL, NULL, p->z4));
-    DFL_TIMED(DFL_TAG_SPMV, DflMatrixFSMatVecX4RangeScaled(A, p->z4, ex->nrm + k, p0, 0, p->x4_N));
-    for (int i = 1; i < sb; ++i) {
-        DFL_TIMED(DFL_TAG_PC, (void)DflPcApplyFusedX4(pc, na, p0 + (size_t)(i - 1) * (size_t)na, NULL, NULL, p->z4));
-        DFL_TIMED(DFL_TAG_SPMV, DflMatrixFSMatVecX4Range(A, p->z4, p0 + (size_t)i * (size_t)na, 0, p->x4_N));
-    }
+    gmres_products(p, ex, A, pc, k, sb, p0);
     DFL_TIMED(DFL_TAG_CGS_DOTS, dfl_cgs_dots_block(na, k + 1, sb, Q, na, p0, na, ex->nrm, h, h_raw, e, c, ldh, ex->work, s));
     DFL_TIMED(DFL_TAG_CGS_UPDATE, dfl_cgs_update_block(na, k + 1, sb, Q, na, c, ldh, p0, na, ex->work, s));
     dfl_gmres_block_first(gu, ex->work, sb, k, ex->nrm, ex->H, ex->h_unrot, ldh, ex->gv, ex->beta, res_hist, sc, s);
@@ -628,6 +650,7 @@ static b32 gmres_run(Matrix* A, f64* x, f64* b, Krylov* ksp, b32 force_probe) {
     ex->last_step = (int)p.step;
     memset(ex->last_blocks, 0, sizeof ex->last_blocks);
     ex->last_pair_cancelled = 0;
+    ex->last_folded = 0;
     f64 *const Q = ex->Q, *const tmp = ex->tmp;
     b32 converged = FALSE;
     index_type total = 0; /* iterations over all cycles */
@@ -652,6 +675,7 @@ static b32 gmres_run(Matrix* A, f64* x, f64* b, Krylov* ksp, b32 force_probe) {
             if (adv > maxit - total) adv = maxit - total;
             if (adv > ex->check_interval - total % ex->check_interval) adv = ex->check_interval - total % ex->check_interval;
             const b32 last = iter + adv >= m || total + adv >= maxit;
+            const int folded_before = ex->last_folded;
             if (adv > 2) gmres_block(&p, ex, A, pc, iter, (int)adv, res_hist, last);
             else if (adv == 2) gmres_pair(&p, ex, A, pc, iter, res_hist, last);
             else {
@@ -673,7 +697,11 @@ static b32 gmres_run(Matrix* A, f64* x, f64* b, Krylov* ksp, b32 force_probe) {
                     if (fr != FIRST_READ_GO_ON) return fr == FIRST_READ_REDO;
                 }
                 /* converged: the step enqueued meanwhile (one iteration or several) is not counted */
-                if (DflKrylovConverged(ksp, fabs(ex->h_stat[8]), hr.rnrm_init)) { converged = TRUE; break; }
+                if (DflKrylovConverged(ksp, fabs(ex->h_stat[8]), hr.rnrm_init)) {
+                    ex->last_folded = folded_before;
+                    converged = TRUE;
+                    break;
+                }
             }
             if ((total + adv) % ex->check_interval == 0) converged = gmres_check(ksp, &p, ex, &hr, iter + adv - 1, total + adv - 1);
             iter += adv; total += adv;
@@ -813,6 +841,11 @@ void DflKrylovLastGmresBlocks(Krylov* ksp, int counts[5], int* cancelled) {
     const KrylovExt* ex = (ksp && ksp->ksp_solve == GMRESSolvePrivate) ? kext(ksp) : NULL;
     if (counts) for (int s = 0; s < 5; ++s) counts[s] = ex ? ex->last_blocks[s] : 0;
     if (cancelled) *cancelled = ex ? ex->last_pair_cancelled : 0;
+}
+/* how many products of that solve wrote M^-1 of their own output for the product that followed (GmresPlan.fold_pc): every product
+   of a counted pair or block but its last; 0 with DFL_GMRES_FOLD_PC=0, single steps, or any other step or preconditioner */
+int DflKrylovLastFoldedProducts(Krylov* ksp) {
+    return (ksp && ksp->ksp_solve == GMRESSolvePrivate && kext(ksp)) ? kext(ksp)->last_folded : 0;
 }
 /* the same in pairs and single steps: a counted step of s iterations is floor(s / 2) pairs and s mod 2 single steps */
 void DflKrylovLastGmresPairs(Krylov* ksp, int* pairs, int* singles, int* cancelled) {

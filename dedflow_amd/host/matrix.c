@@ -461,6 +461,16 @@ void DflMatrixFSMatVecX4RangeScaled(Matrix* m, const value_type* x4, const value
     dfl_bcsr_spmv_x4_scaled(row0, row1, fs->spy1x1->num_row, fs->spy1x1->row_ptr, fs->spy1x1->col_ind, fs->block_val, d_nrm, x4, y,
                             DflStream());
 }
+void DflMatrixFSMatVecX4Pc(Matrix* m, const value_type* x4, const value_type* d_nrm, value_type* y, value_type* z4_out) {
+    MatrixFS* fs = fs_of(m);
+    const CSRAttr* a = fs->spy1x1;
+    int refused;
+    ASSERT(fs->block_mode && "the interleaved matvec needs the block-mode (u,p) matrix");
+    if (d_nrm) refused = dfl_bcsr_spmv_x4_scaled_pc(a->num_row, a->row_ptr, a->col_ind, a->diag_pos, fs->block_val, d_nrm, x4, y, z4_out, DflStream());
+    else refused = dfl_bcsr_spmv_x4_pc(a->num_row, a->row_ptr, a->col_ind, a->diag_pos, fs->block_val, x4, y, z4_out, DflStream());
+    ASSERT(!refused && "dfl_bcsr_spmv_x4_pc: z4_out is the gathered buffer, or the pattern has no diag_pos");
+    UNUSED(refused);
+}
 void MatrixFSMatVecRange(Matrix* m, value_type* x, value_type* y, index_type row0, index_type row1) {
     MatrixFS* fs = fs_of(m);
     ASSERT(fs->block_mode && "MatrixFSMatVecRange needs the block-mode (u,p) matrix");

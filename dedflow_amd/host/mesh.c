@@ -429,6 +429,9 @@ CSRAttr* CSRAttrCreate(const Mesh3D* mesh) {
     attr->nnz = nnz;
     attr->col_ind = (index_type*)CdamMallocDevice((ptrdiff_t)nnz * SIZE_OF(index_type));
     dfl_pattern_fill(N, dev->ien, vrow, vcol, attr->row_ptr, attr->col_ind, s);
+    /* where every row stores its diagonal: fixed with the pattern, read by the matvec that applies the Jacobi tree itself */
+    attr->diag_pos = (index_type*)CdamMallocDevice((ptrdiff_t)N * SIZE_OF(index_type));
+    dfl_bcsr_diag_pos(N, attr->row_ptr, attr->col_ind, attr->diag_pos, s);
     HIPGUARD(hipStreamSynchronize(s));
     CdamFreeDevice(tmp, 0);
     CdamFreeDevice(len, 0);
@@ -450,6 +453,10 @@ CSRAttr* CSRAttrCreateBlock(const CSRAttr* attr, csr_index_type br, csr_index_ty
     if (br == 1 && bc == 1) {
         HIPGUARD(hipMemcpy(na->row_ptr, attr->row_ptr, sizeof(index_type) * (size_t)(attr->num_row + 1), D2D));
         HIPGUARD(hipMemcpy(na->col_ind, attr->col_ind, sizeof(index_type) * (size_t)attr->nnz, D2D));
+        if (attr->diag_pos) {
+            na->diag_pos = (index_type*)CdamMallocDevice((ptrdiff_t)attr->num_row * SIZE_OF(index_type));
+            HIPGUARD(hipMemcpy(na->diag_pos, attr->diag_pos, sizeof(index_type) * (size_t)attr->num_row, D2D));
+        }
     } else {
         dfl_csr_expand(attr->num_row, attr->row_ptr, attr->col_ind, br, bc, na->row_ptr, na->col_ind, DflStream());
         HIPGUARD(hipStreamSynchronize(DflStream()));
@@ -483,5 +490,6 @@ void CSRAttrDestroy(CSRAttr* attr) {
     if (!attr) return;
     CdamFreeDevice(attr->row_ptr, 0);
     CdamFreeDevice(attr->col_ind, 0);
+    if (attr->diag_pos) CdamFreeDevice(attr->diag_pos, 0);
     CdamFreeHost(attr, SIZE_OF(CSRAttr));
 }

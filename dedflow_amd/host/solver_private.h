@@ -47,9 +47,14 @@ typedef struct KrylovExt {
        and how many counted steps of each size the most recent gmres_run took (DflKrylovLastGmresBlocks) */
     f64 *h_unrot, *pair_buf;
     int last_blocks[5], last_pair_cancelled;
+    int last_folded; /* products of the most recent gmres_run that wrote M^-1 of their own output (DflKrylovLastFoldedProducts) */
 } KrylovExt;
 
 static inline KrylovExt* kext(const Krylov* k) { return (KrylovExt*)k->ext; }
+
+/* columns of the basis block behind the m + 1 Krylov vectors of a cycle: the two interleaved copies the matvec gathers from
+   (GmresPlan.z4, z4b) share the block, and with it the placement the calibration chose */
+#define DFL_BASIS_SPARE_COLS 2
 
 /* Everything about one GMRES solve that does not change while it runs; filled once per solve by DflGmresPlanFill. */
 typedef enum { GMRES_X4_NONE, GMRES_X4_SINGLE, GMRES_X4_PARTITIONED } GmresX4; /* matvec gathers from the interleaved copy */
@@ -70,6 +75,10 @@ typedef struct GmresPlan {
     index_type x4_N, x4_owned;
     b32 x4_skip_z;             /* one GPU: nothing reads z in the reference layout, the PC kernel does not store it */
     f64* z4;                   /* the interleaved copy: the spare column of the basis block; NULL without x4 */
+    f64* z4b;                  /* fold_pc: the second interleaved copy, the next spare column (gmres_products) */
+    b32 fold_pc;               /* GMRES_STEP_RAW_BASIS, block > 1: every product of a pair or block but the last writes M^-1 of its
+                                  own output, interleaved, for the product that follows (dfl_bcsr_spmv_x4_pc) instead of a Jacobi
+                                  launch between the two; DFL_GMRES_FOLD_PC=0: the separate launches */
     GmresStep step;
     int block;                 /* GMRES_STEP_RAW_BASIS: the largest number of iterations one pass over the basis serves (1..4); a trip
                                   takes as many as fit into the cycle with no convergence check between them (gmres_pair: 2,

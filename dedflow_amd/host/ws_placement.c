@@ -55,6 +55,7 @@ typedef struct Loop {
     index_type na, m; /* active length = column stride of the basis block; basis columns per cycle */
     index_type x4; /* > 0: the solver's matvec gathers from the interleaved copy (nodes of the unpartitioned block matrix) */
     b32 raw;       /* ... and divides its output by the column's norm (GMRES_STEP_RAW_BASIS) */
+    b32 fold;      /* ... and writes M^-1 of its output into the other interleaved copy (GmresPlan.fold_pc) */
     hipEvent_t a, b;
 } Loop;
 
@@ -66,6 +67,7 @@ static void loop_open(Loop* L, KrylovExt* ex, Matrix* A, PC* pc, index_type max_
        timing loop fills the ghost part from tmp, whatever it holds: placement, not values, is what is measured) */
     L->x4 = plan.x4 != GMRES_X4_NONE ? plan.x4_N : 0;
     L->raw = plan.step == GMRES_STEP_RAW_BASIS;
+    L->fold = plan.fold_pc;
     HIPGUARD(hipEventCreate(&L->a));
     HIPGUARD(hipEventCreate(&L->b));
     const f64 one = 1.0;
@@ -92,13 +94,16 @@ static float time_block(const Loop* L, f64* Qk) {
         dfl_cgs_dots(na, 6, Qk, na, w, ex->H, ex->work, s);
         dfl_cgs_update(na, 6, Qk, na, ex->H, w, ex->nrm + 1, 1, ex->work, s);
         /* as the solver does it: the interleaved copy in the spare column of THIS block, written by the PC kernel */
-        f64* const z4 = L->x4 ? Qk + (size_t)(m + 1) * (size_t)na : NULL;
+        /* (fold: three products of four gather from one of the two copies and write the other, turn about) */
+        f64* const z4 = L->x4 ? Qk + (size_t)(m + 1 + (L->fold ? rep % 2 : 0)) * (size_t)na : NULL;
+        f64* const z4_other = Qk + (size_t)(m + 1 + (rep + 1) % 2) * (size_t)na;
         const index_type owned = MatrixFSOwnedRows(L->A);
         if (L->raw) (void)DflPcApplyFusedX4(L->pc, na, w, NULL, NULL, z4); /* the raw column's M^-1, interleaved copy only */
         else if (!DflPcApplyFusedX4(L->pc, na, w, ex->nrm, ex->tmp, z4) && z4) dfl_interleave4(0, owned, L->x4, ex->tmp, z4, s);
         if (z4 && owned < L->x4) dfl_interleave4(owned, L->x4, L->x4, ex->tmp, z4, s);
         HIPGUARD(hipEventRecord(L->a, s));
-        if (L->raw) DflMatrixFSMatVecX4RangeScaled(L->A, z4, ex->nrm, y, 0, owned); /* nrm[0] = 1 (loop_open) */
+        if (L->fold) DflMatrixFSMatVecX4Pc(L->A, z4, ex->nrm, y, z4_other);
+        else if (L->raw) DflMatrixFSMatVecX4RangeScaled(L->A, z4, ex->nrm, y, 0, owned); /* nrm[0] = 1 (loop_open) */
         else if (z4) DflMatrixFSMatVecX4Range(L->A, z4, y, 0, owned);
         else MatrixMatVec(L->A, ex->tmp, y);
         HIPGUARD(hipEventRecord(L->b, s));
@@ -131,7 +136,7 @@ f64* DflWsPickBasis(KrylovExt* ex, Matrix* A, PC* pc, f64* first, index_type max
     if (ncand < 2 || !eligible(ex, A, na, m)) return first;
     const double t_begin = omp_get_wtime();
     hipStream_t s = DflStream();
-    const size_t bytes = (size_t)MatrixNumRow(A) * (size_t)(m + 2) * sizeof(f64); /* the basis block as DflWsEnsure sizes it */
+    const size_t bytes = (size_t)MatrixNumRow(A) * (size_t)(m + 1 + DFL_BASIS_SPARE_COLS) * sizeof(f64); /* as DflWsEnsure sizes it */
     size_t budget = (size_t)16 << 30;
     if (getenv("DFL_WS_MAX_EXTRA_GB")) budget = (size_t)(atof(getenv("DFL_WS_MAX_EXTRA_GB")) * 1073741824.0);
     {
@@ -244,7 +249,7 @@ void DflKrylovCalibratePlacement(Krylov* ksp, Matrix* A, int64_t max_extra_bytes
     ex->ws_fresh = FALSE;                          /* the first solve does not calibrate again */
     if (ex->flexible || !eligible(ex, A, na, m)) return;
     hipStream_t s = DflStream();
-    const ptrdiff_t count = (ptrdiff_t)n * (m + 2); /* (+ the spare column of the interleaved matvec input, as DflWsEnsure) */
+    const ptrdiff_t count = (ptrdiff_t)n * (m + 1 + DFL_BASIS_SPARE_COLS); /* (+ the interleaved matvec inputs, as DflWsEnsure) */
     const size_t bytes = (size_t)count * sizeof(f64);
     Budget bud = {max_extra_bytes > 0 ? (size_t)max_extra_bytes : ~(size_t)0, 0};
     double settle_cap = 10.0;

@@ -191,6 +191,7 @@ struct CSRAttr {
     index_type* row_ptr; /* device */
     index_type* col_ind; /* device */
     const CSRAttr* parent;
+    index_type* diag_pos; /* device, [num_row]: the stored diagonal of every row of a nodal pattern (CSRAttrCreate); NULL: not built */
 };
 #define CSRAttrNumRow(attr) ((attr)->num_row)
 #define CSRAttrNumCol(attr) ((attr)->num_col)
@@ -298,6 +299,9 @@ void DflMatrixFSMatVecX4Range(Matrix* matrix, const value_type* x4, value_type* 
 /* ... with the output divided by the device scalar *d_nrm: y = (A x4) * (1 / *d_nrm) */
 void DflMatrixFSMatVecX4RangeScaled(Matrix* matrix, const value_type* x4, const value_type* d_nrm, value_type* y, index_type row0,
                                     index_type row1);
+/* y = A x4 over all rows -- d_nrm != NULL: times 1 / *d_nrm -- and z4_out[row][4] = M^-1 y_row of the block-Jacobi tree, written by
+ * the row group that forms y_row (dfl_bcsr_spmv_x4_pc); needs the pattern's diag_pos and z4_out != x4 */
+void DflMatrixFSMatVecX4Pc(Matrix* matrix, const value_type* x4, const value_type* d_nrm, value_type* y, value_type* z4_out);
 void MatrixMatVecWithMask(Matrix* matrix, value_type* x, value_type* y, value_type* left_mask, value_type* right_mask);
 void MatrixGetDiag(Matrix* matrix, value_type* diag, index_type bs);
 void MatrixSetValuesCOO(Matrix* matrix, value_type alpha, index_type n, const index_type* row, const index_type* col,
@@ -504,6 +508,8 @@ int DflKrylovLastGmresStep(Krylov* krylov);
 /* how that solve advanced: counts[s] = counted steps that took s iterations in one pass over the basis, s = 1..4 (counts[0] is 0),
    and whether one of them raised its cancellation flag (a new vector lost more than four digits in the orthogonalisation) */
 void DflKrylovLastGmresBlocks(Krylov* krylov, int counts[5], int* cancelled);
+/* how many matrix products of the most recent unpipelined GMRES solve wrote the Jacobi application of their own output */
+int DflKrylovLastFoldedProducts(Krylov* krylov);
 /* the same as pairs and single steps: a counted step of s iterations adds floor(s / 2) to pairs and s mod 2 to singles */
 void DflKrylovLastGmresPairs(Krylov* krylov, int* pairs, int* singles, int* cancelled);
 /* A non-blocking stream (default priority) that was PROBED to run concurrently with `main_stream`: HIP maps streams onto a few

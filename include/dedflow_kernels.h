@@ -470,6 +470,18 @@ void dfl_bcsr_spmv_x4(dfl_index row0, dfl_index row1, dfl_index N, const dfl_ind
 /* the same with the output scaled by a device scalar: y = (A x4) * (1.0 / *d_nrm) */
 void dfl_bcsr_spmv_x4_scaled(dfl_index row0, dfl_index row1, dfl_index N, const dfl_index* row_ptr, const dfl_index* col_ind,
                              const dfl_value* val, const dfl_value* d_nrm, const dfl_value* x4, dfl_value* y, void* stream);
+/* The two products over all N rows with the block-Jacobi tree folded into the store: the row group that forms y_row also writes
+ * z4_out[row][4] = M^-1 y_row (of the scaled y in the scaled form), interleaved for the product that follows -- same inverse and
+ * same expressions as dfl_pc_jacobi_setup + dfl_pc_jacobi_apply on the row's diagonal block, which the group has just streamed;
+ * y as without the fold, bit for bit.  diag_pos[row]: the nonzero holding that block (dfl_bcsr_diag_pos).  z4_out must not be
+ * x4: rows of one launch gather x4 of arbitrary other rows.  Return 0, or -1 without a launch (z4_out == x4, or a NULL) */
+int dfl_bcsr_spmv_x4_pc(dfl_index N, const dfl_index* row_ptr, const dfl_index* col_ind, const dfl_index* diag_pos,
+                        const dfl_value* val, const dfl_value* x4, dfl_value* y, dfl_value* z4_out, void* stream);
+int dfl_bcsr_spmv_x4_scaled_pc(dfl_index N, const dfl_index* row_ptr, const dfl_index* col_ind, const dfl_index* diag_pos,
+                               const dfl_value* val, const dfl_value* d_nrm, const dfl_value* x4, dfl_value* y, dfl_value* z4_out,
+                               void* stream);
+/* diag_pos[row] = the nonzero dfl_pc_jacobi_setup inverts for the row (col_ind sorted ascending per row) */
+void dfl_bcsr_diag_pos(dfl_index N, const dfl_index* row_ptr, const dfl_index* col_ind, dfl_index* diag_pos, void* stream);
 /* single-precision copy of block values (n = nnz1 * 16 entries) and the matvec / DILU sweeps reading it: PC_TWOLEVEL's
  * smoother and residual matvec (a preconditioner under FGMRES may be inexact; everything outside it stays double) */
 void dfl_bcsr_values_to_f32(int64_t n, const dfl_value* val, float* valf, void* stream);
