@@ -714,6 +714,17 @@ class DflRedistanceStats(C.Structure):
                 ("grad_dev_after", C.c_double), ("volume_before", C.c_double), ("volume_after", C.c_double)]
 
 
+class DflVolumeCorrection(C.Structure):
+    _fields_ = [("level", C.c_double), ("side", C.c_int32), ("max_shift", C.c_double), ("tol", C.c_double),
+                ("target", C.c_double), ("every", C.c_int32), ("track_capture", C.c_int32)]
+
+
+class DflVolumeCorrectionStats(C.Structure):
+    _fields_ = [("status", C.c_int32), ("passes", C.c_int32), ("band_tets", C.c_int64), ("shift", C.c_double),
+                ("target", C.c_double), ("volume_before", C.c_double), ("volume_after", C.c_double),
+                ("volume_mesh", C.c_double)]
+
+
 class DflComm(C.Structure):
     _fields_ = [("allreduce_sum", ALLREDUCE_FN), ("halo_exchange", HALO_FN), ("ctx", vp), ("num_owned_node", C.c_int32),
                 ("halo_begin", HALO_FN), ("halo_end", HALO_FN), ("num_interior_node", C.c_int32),
@@ -892,6 +903,14 @@ def _declare(L):
     f("DflMeshRedistance", i32, [C.POINTER(Mesh3D), vp])
     f("DflMeshRedistanceFacets", i32, [C.POINTER(Mesh3D), C.POINTER(vp)])
     f("DflMeshRedistanceStats", None, [C.POINTER(Mesh3D), C.POINTER(DflRedistanceStats)])
+    f("DflVolumeCorrectionCheck", C.c_int, [C.POINTER(DflVolumeCorrection), C.c_char_p, C.c_size_t])
+    f("DflMeshSetVolumeCorrection", None, [C.POINTER(Mesh3D), C.POINTER(DflVolumeCorrection)])
+    f("DflMeshVolumeCorrectionEnabled", i32, [C.POINTER(Mesh3D)])
+    f("DflMeshVolumeCorrect", i32, [C.POINTER(Mesh3D), vp])
+    f("DflMeshVolumeCorrectionStats", None, [C.POINTER(Mesh3D), C.POINTER(DflVolumeCorrectionStats)])
+    f("DflMeshVolumeCorrectionTarget", f64, [C.POINTER(Mesh3D)])
+    f("DflMeshVolumeCorrectionSetTarget", None, [C.POINTER(Mesh3D), f64])
+    f("DflMeshVolumeCorrectionAddTarget", None, [C.POINTER(Mesh3D), f64])
     f("DflMeshLevelSetVolume", f64, [C.POINTER(Mesh3D), vp, f64])
     f("GenerateRandomColor", None, [vp, i32, i32])
     f("dfl_abi_version", C.c_int, [])
@@ -1236,6 +1255,60 @@ class Problem:
     def level_set_volume(self, w, level):
         """DflMeshLevelSetVolume: the volume of {phi > level} at the state w (synchronises); needs no configuration"""
         return float(lib().DflMeshLevelSetVolume(self.mesh, getattr(w, "ptr", w), float(level)))
+
+    # ---- level-set volume correction (include/dedflow.h, "level-set volume correction") -----------------------------------
+    def set_volume_correction(self, level=None, max_shift=None, tol=1e-10, target=float("nan"), side=1, every=0,
+                              track_capture=False):
+        """DflMeshSetVolumeCorrection: the surface phi = level, the largest shift a call may apply, the tolerance relative to
+        the mesh volume, the volume of {phi > level} to restore (NaN: the first call records it), the metal side and, with
+        every > 0, a correction inside every every-th time_step; track_capture lets time_step add what a two-way capture
+        deposited to the target.  level None turns the feature off.  A configuration the library refuses (reported on
+        stderr) leaves the mesh as it was: volume_correction_on tells."""
+        if level is None:
+            lib().DflMeshSetVolumeCorrection(self.mesh, None)
+            return
+        cfg = DflVolumeCorrection(float(level), int(side), float(max_shift), float(tol), float(target), int(every),
+                                  int(bool(track_capture)))
+        lib().DflMeshSetVolumeCorrection(self.mesh, C.byref(cfg))
+
+    @property
+    def volume_correction_on(self):
+        return bool(lib().DflMeshVolumeCorrectionEnabled(self.mesh))
+
+    def _need_volume_correction(self):
+        if not self.volume_correction_on:
+            raise RuntimeError("no volume correction is set: call set_volume_correction first")
+
+    def volume_correct(self, w):
+        """DflMeshVolumeCorrect in place on phi of the state w (DeviceArray of 6N, or a raw device pointer); returns the
+        status: 0 corrected, 1 already within tolerance, 2 not bracketed, 3 pass limit reached (synchronises)"""
+        self._need_volume_correction()
+        return int(lib().DflMeshVolumeCorrect(self.mesh, getattr(w, "ptr", w)))
+
+    def volume_correction_stats(self):
+        """DflMeshVolumeCorrectionStats of the last call: status (-1: no call yet), passes, band_tets, shift, target,
+        volume_before / _after, volume_mesh"""
+        self._need_volume_correction()
+        s = DflVolumeCorrectionStats()
+        lib().DflMeshVolumeCorrectionStats(self.mesh, C.byref(s))
+        return {k: (int if k in ("status", "passes", "band_tets") else float)(getattr(s, k))
+                for k, _ in DflVolumeCorrectionStats._fields_}
+
+    @property
+    def volume_target(self):
+        """DflMeshVolumeCorrectionTarget: NaN while it is not recorded"""
+        self._need_volume_correction()
+        return float(lib().DflMeshVolumeCorrectionTarget(self.mesh))
+
+    @volume_target.setter
+    def volume_target(self, volume):
+        self._need_volume_correction()
+        lib().DflMeshVolumeCorrectionSetTarget(self.mesh, float(volume))
+
+    def add_volume_target(self, dV):
+        """DflMeshVolumeCorrectionAddTarget: the target grows by dV of {phi > level}"""
+        self._need_volume_correction()
+        lib().DflMeshVolumeCorrectionAddTarget(self.mesh, float(dV))
 
     def close(self):
         L = lib()

@@ -147,6 +147,9 @@ index_type SolveFlowSystem(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matr
  * the previous step enter the p, momentum and T rows of this step's Newton solve.  With free-surface forces set on the mesh
  * with in_time_step (DflMeshSetSurfaceForces), their load and heat loss at wgold enter the momentum and T rows as well.  With
  * redistancing set on the mesh with every > 0 (DflMeshSetRedistance), every every-th call first redistances phi of wgold.
+ * With a volume correction set on the mesh with every > 0 (DflMeshSetVolumeCorrection), every every-th call then shifts phi of
+ * wgold back to the target volume, after that redistancing and before anything else looks at phi; with its track_capture, a
+ * step that took a pending two-way capture source adds the deposited volume to the target after its Newton solve.
  * With a laser surface set on the coupled context (ParticleContextSetLaserSurface), ParticleContextLaserSurfaceUpdate runs
  * once, before the first particle sub-step, in the state those sub-steps see. */
 index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* J, f64* F, f64* dx, Krylov* ksp, Dirichlet** bcs,
@@ -181,10 +184,16 @@ index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* 
         fprintf(stderr, "DflTimeStep: the level-set redistancing is single-GPU only; the solver has a communicator: step refused\n");
         return -1;
     }
+    if (DflVolumeCorrectionInTimeStep(mesh) && KrylovGetComm(ksp)) {
+        fprintf(stderr, "DflTimeStep: the level-set volume correction is single-GPU only; the solver has a communicator: step refused\n");
+        return -1;
+    }
     DflRangePush("DflTimeStep");
     /* every every-th step (DflMeshSetRedistance): phi of wgold becomes the band distance again before the surface load, the
        phase change and the solve look at it */
     DflRedistanceTimeStep(mesh, wgold);
+    /* every every-th step (DflMeshSetVolumeCorrection): then phi of wgold is shifted back to the target volume */
+    DflVolumeCorrectionTimeStep(mesh, wgold);
     const f64* user_load = DflMeshExternalLoad(mesh);
     const f64* reaction = coupled && DflParticleTwoWay(pctx) ? DflParticlePendingLoad(pctx) : NULL;
     if (reaction) {
@@ -230,7 +239,10 @@ index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* 
     index_type it = SolveFlowSystem(mesh, wgold, dwgold, dwg, J, F, dx, ksp, bcs, nbc, newton_maxit, rnorm_out, rnorm_init_out);
     if (reaction) DflMeshSetExternalLoad(mesh, user_load);
     if (heat) DflMeshSetHeatSource(mesh, user_heat);
-    if (cap_vol) DflMeshSetVolumeSource(mesh, user_vol);
+    if (cap_vol) {
+        DflMeshSetVolumeSource(mesh, user_vol);
+        DflVolumeCorrectionCaptured(mesh, cap_vol, kDT); /* track_capture: the target follows what was deposited */
+    }
     if (pctx && !coupled)
         for (index_type k = 0; k < dem_substeps; ++k) ParticleContextUpdate(pctx); /* coupled step: contact sweep (config 4) */
     dfl_alpha_correct(N, fac_corr[0], fac_corr[1], wgold, dwgold, dwg, s);

@@ -82,6 +82,7 @@ typedef struct MeshExt {
     b32 phase_current;             /* its D and H already hold the alpha states the next driver assembly is given */
     struct ThermalState* thermal;  /* thermal material (host/thermal.c, DflMeshSetThermalMaterial), NULL: off */
     struct RedistanceState* redistance; /* level-set redistancing (host/redistance.c, DflMeshSetRedistance), NULL: off */
+    struct VolumeState* volume;    /* level-set volume correction (host/volume.c, DflMeshSetVolumeCorrection), NULL: off */
     index_type *v2e_row, *v2e_col; /* device [N+1], [4T]: the sorted V2E map (DflMeshSortedV2E), NULL until first asked for */
 } MeshExt;
 
@@ -422,6 +423,14 @@ void DflRedistanceGeometryChanged(struct RedistanceState* st); /* the nodes move
 b32 DflRedistanceInTimeStep(const Mesh3D* mesh);                /* a configuration with every > 0 is set */
 /* counts one DflTimeStep; on every every-th since the Set call redistances wgold (DflMeshRedistance) and returns TRUE */
 b32 DflRedistanceTimeStep(Mesh3D* mesh, f64* wgold);
+/* host/volume.c: the level-set volume correction of a mesh (no-ops while it is off) */
+struct VolumeState;
+void DflVolumeCorrectionFree(struct VolumeState* st);
+b32 DflVolumeCorrectionInTimeStep(const Mesh3D* mesh);         /* a configuration with every > 0 is set */
+/* counts one DflTimeStep; on every every-th since the Set call corrects wgold (DflMeshVolumeCorrect) */
+void DflVolumeCorrectionTimeStep(Mesh3D* mesh, f64* wgold);
+/* with track_capture: the target grows by side * time * sum q_vol (device [N]); sums on the device and waits for it */
+void DflVolumeCorrectionCaptured(Mesh3D* mesh, const f64* q_vol, f64 time);
 
 /* named ranges for rocprofv3 --marker-trace (DFL_ROCTX=1); no-ops otherwise */
 void DflRangePush(const char* name);

@@ -100,6 +100,7 @@ void Mesh3DDestroy(Mesh3D* m) {
         DflPhaseFree(x->phase);
         DflThermalFree(x->thermal);
         DflRedistanceFree(x->redistance);
+        DflVolumeCorrectionFree(x->volume);
         CdamFreeDevice(x->v2e_row, 0); /* after the feature states that borrowed it */
         CdamFreeDevice(x->v2e_col, 0);
         CdamFreeDevice(x->egeo_b, 0);

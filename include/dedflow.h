@@ -1528,9 +1528,9 @@ void DflMeshThermalRows(Mesh3D* mesh, const f64* w, const f64* dw, f64* r, f64* 
  *               surface load and anything else is evaluated.  With a communicator it prints why and returns -1.
  * Limits: the surface ends at the mesh boundary, so the distance is to the part of the surface inside the mesh.  Beyond band
  * the field is flat at level +- band; there |g| = 0, which the free-surface and phase-change sections treat as "contributes
- * nothing" / "mean sign", so band >= eps + 2 h (h the tet size) is the caller's condition.  One GPU only.  No volume
- * correction: the zero set of the new interpolant moves by O(h^2), and volume_before / volume_after say by how much.  Fewer
- * than 2^31 facets and cell entries. */
+ * nothing" / "mean sign", so band >= eps + 2 h (h the tet size) is the caller's condition.  One GPU only.  The call
+ * itself does not correct the volume: the zero set of the new interpolant moves by O(h^2), volume_before / volume_after say
+ * by how much, and the "level-set volume correction" section below restores it.  Fewer than 2^31 facets and cell entries. */
 typedef struct DflRedistance {
     f64 level, band;          /* the surface phi = level; half-width of the band (length), > 0 */
     index_type hold_groups;   /* bit g: the nodes of boundary group g keep their phi */
@@ -1561,6 +1561,81 @@ void DflMeshRedistanceStats(Mesh3D* mesh, DflRedistanceStats* out);
 /* the volume of {phi > level} at the state w (device 6N) as the statistics form it; needs no configuration.  Allocates and
  * frees its own scratch and synchronises */
 f64  DflMeshLevelSetVolume(Mesh3D* mesh, const f64* w, f64 level);
+
+/* ---- level-set volume correction: a global shift of phi that restores the metal volume (build-defined; opt-in) -----------
+ * Level-set advection does not conserve volume and every redistancing moves the zero set by O(h^2); the reference does
+ * nothing about either.  A mesh that never calls DflMeshSetVolumeCorrection with a configuration, or clears it with NULL,
+ * computes bit for bit what it computes without this section, through the same launches.  One GPU only.
+ *   volume      V(c) = the volume of {phi > c}, summed over the tets exactly as volume_before / _after of the redistancing
+ *               section form it (a NaN tet adds 0), in a fixed order.  V is continuous, non-increasing in c and piecewise
+ *               cubic.  V_mesh = the sum of |det| / 6 over all tets.
+ *   correction  finds c* in [level - max_shift, level + max_shift] with |V(c*) - target| <= tol V_mesh and writes
+ *               phi_a <- phi_a + delta, delta = level - c*, for every node, as one rounded addition.  A NaN stays a NaN (it is
+ *               not written); no other slot of w is touched.
+ *   status      0 corrected: a c* within the tolerance was found, the shift is applied;
+ *               1 already within tolerance: |V(level) - target| <= tol V_mesh, tested first: delta = 0, no node written, no
+ *                 search pass.  Also the answer of the call that records an unset target (below);
+ *               2 not bracketed: target > V(level - max_shift) or target < V(level + max_shift) (no surface, or a drift
+ *                 larger than the caller allows): nothing written;
+ *               3 pass limit reached before the tolerance: the evaluated c with the smallest |V(c) - target| is applied.
+ *   search      lo = level - max_shift, hi = level + max_shift.  One pass over all tets: a tet whose four phi are > hi is
+ *               inside for every candidate and its |det| / 6 goes into V_in; a tet with no phi > lo adds nothing; every
+ *               other tet is a band tet, and the ids of the band tets are compacted in ascending order into a list.  The
+ *               same pass gives V at level, lo and hi, and V_mesh.  The bracket [a, b], V(a) >= target >= V(b), starts as
+ *               [lo, level] or [level, hi].  A K-section pass (K = 15) evaluates V = V_in + V_band at K candidates in one read
+ *               of the band list: the K - 1 points a + k ((b - a) / K) and the trial c, the linear interpolant of V between
+ *               a and b at the target (the midpoint where V(a) = V(b)), inserted in ascending order.  The host reads the K
+ *               sums back, stops when the best evaluated c meets the tolerance, and else keeps the first sub-interval
+ *               whose right end has V <= target.  The pass limit is 12; DFL_VOLUME_PASSES (an integer >= 1, read by the Set
+ *               call; anything else is refused) replaces it.
+ *   target      the volume of {phi > level} to restore.  NaN in the configuration: the first correction call (direct or
+ *               from DflTimeStep) records V(level) of the state it sees and returns 1 without writing anything.
+ *               SetTarget / AddTarget change it between calls.
+ *   time step   with every > 0, DflTimeStep corrects phi of wgold on every every-th call since the Set call, after the
+ *               redistancing of that call, if any, and before the surface load and anything else is evaluated.  With a
+ *               communicator it prints why and returns -1.  With track_capture, a step that took a pending two-way capture
+ *               source (ParticleContextSetCapture) adds side kDT sum_a q_vol[a], the volume the captured particles brought,
+ *               to the target after its Newton solve (summed on the device in a fixed two-stage order; reads 8 bytes back).
+ *   statistics  of the last call: status, passes, band_tets, shift = delta (0 unless the status is 0 or 3), target,
+ *               volume_before = V(level) as the call found it, volume_after = V(c*) (= volume_before unless shifted: the
+ *               volume of {phi > level} of the new field up to the rounding of the addition), volume_mesh.
+ * Limits: one shift for the whole mesh, so the volume is restored but not where it was lost; the surface moves by delta / |grad
+ * phi| everywhere, and after a redistancing |grad phi| = 1 inside its band.  side only orients what track_capture adds: the
+ * target is the volume of {phi > level} either way, so with side = -1 the metal volume is V_mesh - target.  One GPU only. */
+typedef struct DflVolumeCorrection {
+    f64 level;            /* the surface phi = level */
+    index_type side;      /* +1: metal where phi > level, -1: metal where phi < level (as DflParticleCapture.side) */
+    f64 max_shift;        /* > 0: the largest |delta| the call may apply */
+    f64 tol;              /* >= 0, relative to the mesh volume */
+    f64 target;           /* volume of {phi > level} to restore; NaN: taken from the state the first call sees */
+    index_type every;     /* > 0: DflTimeStep corrects wgold on every every-th call; 0: only DflMeshVolumeCorrect does */
+    b32 track_capture;    /* DflTimeStep adds what a two-way capture deposited to the target */
+} DflVolumeCorrection;
+typedef struct DflVolumeCorrectionStats {
+    index_type status, passes;
+    int64_t band_tets;
+    f64 shift, target, volume_before, volume_after, volume_mesh;
+} DflVolumeCorrectionStats;
+/* host only: 0 when DflMeshSetVolumeCorrection accepts the configuration, else why not in `why`: level, max_shift or tol not
+ * finite, max_shift <= 0, tol < 0, side not +-1, every < 0, target infinite */
+int  DflVolumeCorrectionCheck(const DflVolumeCorrection* cfg, char* why, size_t why_len);
+/* the configuration is copied; NULL: off, frees everything of its own.  A refused configuration (or DFL_VOLUME_PASSES) is
+ * reported on stderr and leaves the mesh as it was.  Allocates every buffer but the band list (synchronises), takes the
+ * target from the configuration and restarts the count of time steps */
+void DflMeshSetVolumeCorrection(Mesh3D* mesh, const DflVolumeCorrection* cfg);
+b32  DflMeshVolumeCorrectionEnabled(const Mesh3D* mesh);
+/* in place on w[4N:5N), w on the device; returns the status, -1 when not set.  Waits for the device once after the pass over
+ * all tets and once per K-section pass.  The band list grows when the band-tet count exceeds its capacity; the call
+ * allocates nothing otherwise.  The geometry is read on every call: DflMeshGeometryChanged needs no rebuild here */
+index_type DflMeshVolumeCorrect(Mesh3D* mesh, f64* w);
+/* the statistics of the last call; zeros, status -1, when not set (with a line on stderr) or never called */
+void DflMeshVolumeCorrectionStats(Mesh3D* mesh, DflVolumeCorrectionStats* out);
+/* the target: NaN when not set, or not recorded yet */
+f64  DflMeshVolumeCorrectionTarget(const Mesh3D* mesh);
+/* NaN: the next call records it again; an infinite volume, a dV that is not finite, or a mesh without a configuration: a line
+ * on stderr, nothing changed.  A dV added to a target not recorded yet is lost: the recording call sees the state with it */
+void DflMeshVolumeCorrectionSetTarget(Mesh3D* mesh, f64 volume);
+void DflMeshVolumeCorrectionAddTarget(Mesh3D* mesh, f64 dV); /* dV of {phi > level} */
 
 #ifdef __cplusplus
 }

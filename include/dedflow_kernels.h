@@ -1010,6 +1010,28 @@ void dfl_redistance_nodes(dfl_index N, const dfl_value* xg, dfl_value* w, dfl_va
 void dfl_redistance_node_stats(dfl_index N, const dfl_value* chg, dfl_value* work, dfl_value* out2, void* stream);
 void dfl_redistance_reduce(dfl_index npart, const dfl_value* part, dfl_value* out2, void* stream);
 
+/* ---- level-set volume correction (build-defined, opt-in; host/volume.c, csrc/k_volume.hip, model in include/dedflow.h)
+ * phi = w + 4N, lo = level - max_shift, hi = level + max_shift.  A tet is inside when its four phi are > hi, a band tet when
+ * it is not inside and has a phi > lo.  Workgroups of dfl_redistance_tets_per_block() tets.  Every sum has a fixed order.
+ *    dfl_volume_classify  one thread per tet.  blk_count[b] = band tets of workgroup b; part: [workgroups][5]; out5 = (V_in: the
+ *                         |det| / 6 of the inside tets, the volume of {phi > level}, {phi > lo} and {phi > hi} inside the
+ *                         band tets, the mesh volume)
+ *    dfl_volume_emit      the ids of the band tets in ascending order: list[blk_base[b] + (band tets among the earlier tets
+ *                         of workgroup b)] = tet id.  Nothing is written at or beyond cap
+ *    dfl_volume_eval      outK[k] = the volume of {phi > cand[k]} inside the nband listed tets, k < DFL_VOLUME_K; cand is on
+ *                         the host and travels as a kernel argument; part: [ceil(nband / 256)][DFL_VOLUME_K]
+ *    dfl_volume_shift     phi_a += delta for every node, one rounded addition; a NaN is not written
+ *    dfl_volume_node_sum  out1[0] = sum of q[0 .. N); work >= 1024 doubles */
+#define DFL_VOLUME_K 15
+void dfl_volume_classify(dfl_index T, const dfl_index* ien, const dfl_value* xg, const dfl_value* w, dfl_index N, dfl_value level,
+                         dfl_value lo, dfl_value hi, dfl_index* blk_count, dfl_value* part, dfl_value* out5, void* stream);
+void dfl_volume_emit(dfl_index T, const dfl_index* ien, const dfl_value* w, dfl_index N, dfl_value lo, dfl_value hi,
+                     const dfl_index* blk_base, dfl_index* list, dfl_index cap, void* stream);
+void dfl_volume_eval(dfl_index nband, const dfl_index* list, const dfl_index* ien, const dfl_value* xg, const dfl_value* w,
+                     dfl_index N, const dfl_value* cand, dfl_value* part, dfl_value* outK, void* stream);
+void dfl_volume_shift(dfl_index N, dfl_value* w, dfl_value delta, void* stream);
+void dfl_volume_node_sum(dfl_index N, const dfl_value* q, dfl_value* work, dfl_value* out1, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
