@@ -805,6 +805,7 @@ def _declare(L):
     f("dfl_bcsr_spmv_x4_scaled_pc", C.c_int, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp])
     f("dfl_bcsr_diag_pos", None, [i32, vp, vp, vp, vp])
     f("DflKrylovLastFoldedProducts", C.c_int, [vp])
+    f("DflKrylovLastFusedBlocks", C.c_int, [vp])
     f("DflKrylovLastGmresStep", C.c_int, [vp])
     f("DflKrylovLastGmresPairs", None, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)])
     f("DflKrylovLastGmresBlocks", None, [vp, C.POINTER(C.c_int * 5), C.POINTER(C.c_int)])
@@ -815,6 +816,11 @@ def _declare(L):
     f("dfl_gmres_block_first", None, [C.c_int, vp, C.c_int, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp])
     f("dfl_cgs_fixup_block", None, [i32, C.c_int, vp, C.c_int64, vp, vp, vp, vp, vp, vp])
     f("dfl_gmres_block_second", None, [C.c_int, vp, C.c_int, i32, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp])
+    # ... with update and fix-up in one pass (C from the Gram matrix derived in the dots pass)
+    f("dfl_cgs_update_fixup_block_parts", C.c_int, [i32])
+    f("dfl_cgs_dots_block_gram", None, [i32, i32, C.c_int, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, vp, i32, vp, vp, vp])
+    f("dfl_cgs_update_fixup_block", None, [i32, i32, C.c_int, vp, C.c_int64, vp, i32, vp, C.c_int64, vp, vp, vp, vp, vp, vp])
+    f("dfl_gmres_block_fused", None, [C.c_int, vp, C.c_int, i32, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, f64, vp])
     f("dfl_dscal_inv_dev", None, [i32, vp, vp, vp]); f("dfl_dsqrt_dev", None, [vp, vp])
     f("dfl_norms4", None, [i32, vp, vp, C.c_int, vp, vp])
     f("dfl_alpha_states", None, [i32, vp, vp, vp, f64, f64, f64, f64, vp, vp, vp, vp, vp])

@@ -771,10 +771,12 @@ __device__ __forceinline__ double wave_sum4(const double (&v)[4], int lane) {
 // (0.262 ms per launch).
 // One-dimensional grid, the column tile running fastest: beyond 64 columns the workgroups that read the same rows of the S
 // vectors are dispatched together.
-template <int S, int R>
+// GRAM: the workgroup of a row block's first column tile also leaves the partials of the Gram matrix of the S vectors themselves,
+// <p_a, p_b> for a <= b in row-major order of the upper triangle, at gram[t nrb + rb] -- they are in its registers
+template <int S, int R, bool GRAM>
 __global__ __launch_bounds__(BLK) void cgs_dots_block_stage1(I n, I ncol, const T* __restrict__ Q, long long ldq,
                                                             const T* __restrict__ w, long long ldw, T* __restrict__ part, int nrb,
-                                                            int ntile) {
+                                                            int ntile, T* __restrict__ gram) {
     __shared__ double lds[CTB * 4 * 4];  // [column of the tile][vector][wave]: 8 KB
     const int rb = blockIdx.x / ntile;
     const long long r0 = (long long)rb * (BLK * R * 2);
@@ -828,6 +830,26 @@ __global__ __launch_bounds__(BLK) void cgs_dots_block_stage1(I n, I ncol, const 
     if (tc < nc && ta < S) {
         const double* l = lds + (tc * 4 + ta) * 4;
         part[((long long)ta * ncol + c0 + tc) * nrb + rb] = (l[0] + l[1]) + (l[2] + l[3]);
+    }
+    if (GRAM && c0 == 0) {  // uniform
+        constexpr int NG = S * (S + 1) / 2;
+        double g[NG];
+#pragma unroll
+        for (int t = 0; t < NG; ++t) g[t] = 0.0;
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            int t = 0;
+#pragma unroll
+            for (int a = 0; a < S; ++a)
+#pragma unroll
+                for (int b = a; b < S; ++b, ++t) g[t] += u[a][i].x * u[b][i].x + u[a][i].y * u[b][i].y;
+        }
+        __syncthreads();  // the column sums have been read out of lds
+        block_sumN_256<NG>(g, lds);
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int t = 0; t < NG; ++t) gram[(long long)t * nrb + rb] = g[t];
+        }
     }
 }
 
@@ -919,6 +941,120 @@ __global__ __launch_bounds__(BLK) void cgs_update_block_kernel(I n, I ncol, cons
     }
 }
 
+// the S x S Gram matrix, symmetric in a zeroed 4 x 4, from its upper triangle in row-major order
+template <int S>
+__device__ __forceinline__ void gram_unpack(const double (&g)[S * (S + 1) / 2], double (&G)[4][4]) {
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) G[a][b] = 0.0;
+    int t = 0;
+#pragma unroll
+    for (int a = 0; a < S; ++a)
+#pragma unroll
+        for (int b = a; b < S; ++b, ++t) { G[a][b] = g[t]; G[b][a] = g[t]; }
+}
+
+// Gram-Schmidt on G, one thread: C unit lower triangular with q_i = sum_{l<=i} C[i,l] p_l' orthogonal as G has them, and
+// U[l,i] = C[l].G[:,i], l < i.  Row i starts as the unit vector, then for l < i: C[i] -= (C[l].G[:,i] / C[l].G.C[l]) C[l]
+template <int S>
+__device__ __forceinline__ void gram_schmidt_on_G(const double (&G)[4][4], double (&Cm)[4][4], double (&Um)[4][4]) {
+    double d[4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) { Cm[a][b] = (a == b) ? 1.0 : 0.0; Um[a][b] = 0.0; }
+#pragma unroll
+    for (int i = 0; i < S; ++i) {
+#pragma unroll
+        for (int l = 0; l < i; ++l) {
+            double u = 0.0;
+#pragma unroll
+            for (int m = 0; m <= l; ++m) u += Cm[l][m] * G[m][i];
+            Um[l][i] = u;
+            const double f = u / d[l];
+#pragma unroll
+            for (int m = 0; m <= l; ++m) Cm[i][m] -= f * Cm[l][m];
+        }
+        double dd = 0.0;  // C[i].G.C[i] = ||q_i||^2 as G has it
+#pragma unroll
+        for (int a = 0; a <= i; ++a) {
+            double r = 0.0;
+#pragma unroll
+            for (int b = 0; b <= i; ++b) r += G[a][b] * Cm[i][b];
+            dd += Cm[i][a] * r;
+        }
+        d[i] = dd;
+    }
+}
+
+// cgs_dots_block_stage2 with S (S + 1) / 2 more workgroups, which finish the raw Gram sums <p_a, p_b> (gram: their partials, t-th
+// entry of the upper triangle at gram[t nrb]) in the same fixed order into graw[t]; one-dimensional grid, the first ncol S
+// workgroups are those of cgs_dots_block_stage2, vector-major, and write what it writes bit for bit
+__global__ __launch_bounds__(BLK) void cgs_dots_block_gram_stage2(int nrb, I ncol, int ns, const T* part, const T* __restrict__ nu,
+                                                                 T* d_h, T* d_h_raw, T* d_e, T* d_c, I lde, const T* gram,
+                                                                 T* graw) {
+    __shared__ double lds[4];
+    const int nd = ncol * ns;
+    const bool dots = (int)blockIdx.x < nd;
+    const int i = blockIdx.x / ncol, j = blockIdx.x - i * ncol;
+    const T* p = dots ? part + ((long long)i * ncol + j) * nrb : gram + (long long)(blockIdx.x - nd) * nrb;
+    double acc = 0.0;
+    for (int t = threadIdx.x; t < nrb; t += BLK) acc += p[t];
+    const double r = block_sum_256(acc, lds);
+    if (threadIdx.x == 0) {
+        if (dots) {
+            const double v = nu[j], h = r / v;
+            d_e[(long long)i * lde + j] = h;
+            d_c[(long long)i * lde + j] = h / v;
+            if (i == 0) {
+                d_h[j] = h;
+                if (d_h_raw) d_h_raw[j] = h;
+            }
+        } else graw[blockIdx.x - nd] = r;
+    }
+}
+
+// After cgs_dots_block_gram_stage2, one workgroup: from the raw Gram sums (sc[SC_GR + t], t-th entry of the upper triangle) the
+// Gram matrix the updated vectors WILL have -- r_j / nu_j are orthonormal, so <p_a', p_b'> = <p_a, p_b> - sum_{j<=k} e_a[j] e_b[j],
+// j ascending -- and C by Gram-Schmidt on it, before the update pass runs.  sc[SC_C] = C, sc[SC_GD] = the derived G, sc[SC_GR] =
+// the raw sums, each 4 x 4.  C only chooses the basis inside the block (block_fused_kernel).
+constexpr int SC_GD = 48, SC_GR = 64;
+template <int S>
+__global__ __launch_bounds__(64) void block_gram_kernel(I ncol, const T* __restrict__ d_e, I lde, T* sc) {
+    constexpr int NG = S * (S + 1) / 2;
+    __shared__ double s_raw[NG], s_der[NG];
+    if (threadIdx.x < NG) s_raw[threadIdx.x] = sc[SC_GR + threadIdx.x];
+    __syncthreads();
+    if (threadIdx.x < NG) {  // one thread per entry of the upper triangle
+        int a = 0, b = threadIdx.x;
+        while (b >= S - a) { b -= S - a; ++a; }
+        b += a;
+        const T* ea = d_e + (long long)a * lde;
+        const T* eb = d_e + (long long)b * lde;
+        double v = s_raw[threadIdx.x];
+        for (int j = 0; j < ncol; ++j) v -= ea[j] * eb[j];
+        s_der[threadIdx.x] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double gr[NG], gd[NG], Gr[4][4], G[4][4], Cm[4][4], Um[4][4];
+#pragma unroll
+        for (int t = 0; t < NG; ++t) { gr[t] = s_raw[t]; gd[t] = s_der[t]; }
+        gram_unpack<S>(gr, Gr);
+        gram_unpack<S>(gd, G);
+        gram_schmidt_on_G<S>(G, Cm, Um);
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                sc[SC_C + 4 * a + b] = Cm[a][b];
+                sc[SC_GD + 4 * a + b] = G[a][b];
+                sc[SC_GR + 4 * a + b] = Gr[a][b];
+            }
+    }
+}
+
 // The scalars of a block after the S-vector update, one workgroup: second stage of G (fixed order), nu[k+1] = sqrt(G_00) below
 // e_0 in column k of H and of its un-rotated copy, the Givens step of that column; C by Gram-Schmidt on G: row i starts as the
 // unit vector, then for l < i: C[i] -= (C[l].G[:,i] / C[l].G.C[l]) C[l]  (S = 2: C[1,0] = -s12 / s11, the pair's coefficient)
@@ -939,38 +1075,9 @@ __global__ __launch_bounds__(BLK) void block_first_kernel(int npart, const T* pa
     }
     block_sumN_256<NG>(g, lds);
     if (threadIdx.x == 0) {
-        double G[4][4], Cm[4][4], Um[4][4], d[4];
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) { G[a][b] = 0.0; Cm[a][b] = (a == b) ? 1.0 : 0.0; Um[a][b] = 0.0; }
-        int t = 0;
-#pragma unroll
-        for (int a = 0; a < S; ++a)
-#pragma unroll
-            for (int b = a; b < S; ++b, ++t) { G[a][b] = g[t]; G[b][a] = g[t]; }
-#pragma unroll
-        for (int i = 0; i < S; ++i) {
-#pragma unroll
-            for (int l = 0; l < i; ++l) {
-                double u = 0.0;
-#pragma unroll
-                for (int m = 0; m <= l; ++m) u += Cm[l][m] * G[m][i];
-                Um[l][i] = u;
-                const double f = u / d[l];
-#pragma unroll
-                for (int m = 0; m <= l; ++m) Cm[i][m] -= f * Cm[l][m];
-            }
-            double dd = 0.0;  // C[i].G.C[i] = ||q_i||^2 as G has it
-#pragma unroll
-            for (int a = 0; a <= i; ++a) {
-                double r = 0.0;
-#pragma unroll
-                for (int b = 0; b <= i; ++b) r += G[a][b] * Cm[i][b];
-                dd += Cm[i][a] * r;
-            }
-            d[i] = dd;
-        }
+        double G[4][4], Cm[4][4], Um[4][4];
+        gram_unpack<S>(g, G);
+        gram_schmidt_on_G<S>(G, Cm, Um);
 #pragma unroll
         for (int a = 0; a < 4; ++a)
 #pragma unroll
@@ -1057,11 +1164,161 @@ __global__ __launch_bounds__(BLK) void cgs_fixup_block_kernel(I N, T* __restrict
     }
 }
 
+// cgs_update_block_kernel and cgs_fixup_block_kernel in one pass, C known beforehand (block_gram_kernel): a workgroup owns 256 nodes
+// as the fix-up does (same slots, same vec_ok rule, which here covers Q as well), streams columns 0..ncol-1 as the update does
+// (p_i -= c_i[j] r_j, j ascending, the same expressions), then from the registers: the partials of the measured G = [<p_a', p_b'>]
+// at part[t gridDim.x + blk], q_a for a = S-1 down to 1 with the fix-up's expressions, the partials of ||q_i||^2 at
+// part[(NG + i - 1) gridDim.x + blk]; every column is stored once (p_0' = q_0 included: nothing has stored it yet).  Given the same
+// tables q_i and z4 are those of the two kernels bit for bit.  The columns leave with nontemporal stores, z4 with plain ones: the
+// product that opens the next block gathers from z4 first, and the 4 c of columns stored after it no longer push it out of the
+// Infinity Cache (M = 119, one trace job: this kernel 276 against 293 us, the product behind it 546 against 561 us).
+template <int S, bool Z4>
+__global__ __launch_bounds__(BLK) void cgs_update_fixup_block_kernel(I N, I ncol, const T* __restrict__ Q, long long ldq,
+                                                                    const T* __restrict__ d_c, I lde, T* __restrict__ w,
+                                                                    long long ldw, const T* __restrict__ sc, T* __restrict__ part,
+                                                                    const T* __restrict__ dinv33, const T* __restrict__ dinv1,
+                                                                    T* __restrict__ z4, int vec_ok) {
+    constexpr int NG = S * (S + 1) / 2, NP = NG + S - 1;
+    __shared__ double lds[4 * NP];
+    __shared__ double sh[S][128];
+    __shared__ double2 sm[Z4 ? BLK * UPT : 1];  // q_{S-1} of the block: [0, 768) u, [768, 1024) p
+    for (int j = threadIdx.x; j < ncol && j < 128; j += BLK) {
+#pragma unroll
+        for (int a = 0; a < S; ++a) sh[a][j] = d_c[(long long)a * lde + j];
+    }
+    __syncthreads();
+    double Cm[S][S];
+#pragma unroll
+    for (int a = 1; a < S; ++a)
+#pragma unroll
+        for (int l = 0; l < a; ++l) Cm[a][l] = sc[SC_C + 4 * a + l];
+    const long long blk = blockIdx.x;
+    const long long a0 = blk * BLK;
+    const long long nb = (N - a0 < BLK) ? (N - a0) : BLK;  // nodes of this block
+    long long row[UPT];
+    int ok[UPT];  // bit 0: row is inside, bit 1: row + 1 is, bit 2: the slot is one aligned double2
+    double2 v[S][UPT];
+#pragma unroll
+    for (int i = 0; i < UPT; ++i) {
+        const int slot = threadIdx.x + i * BLK;  // slots [0, 384): u rows, [384, 512): p rows
+        long long lim;
+        if (slot < 384) { row[i] = 3 * a0 + 2LL * slot; lim = 3 * (a0 + nb); }
+        else { row[i] = 3LL * N + a0 + 2LL * (slot - 384); lim = 3LL * N + a0 + nb; }
+        ok[i] = (row[i] < lim ? 1 : 0) | (row[i] + 1 < lim ? 2 : 0) | ((vec_ok && row[i] + 1 < lim && !(row[i] & 1)) ? 4 : 0);
+#pragma unroll
+        for (int a = 0; a < S; ++a) {
+            const T* wa = w + a * ldw;
+            if (ok[i] & 4) v[a][i] = *reinterpret_cast<const double2*>(wa + row[i]);
+            else { v[a][i].x = (ok[i] & 1) ? wa[row[i]] : 0.0; v[a][i].y = (ok[i] & 2) ? wa[row[i] + 1] : 0.0; }
+        }
+    }
+#pragma unroll 4
+    for (int j = 0; j < ncol; ++j) {
+        double h[S];
+#pragma unroll
+        for (int a = 0; a < S; ++a) h[a] = (j < 128) ? sh[a][j] : d_c[(long long)a * lde + j];
+        const T* q = Q + (long long)j * ldq;
+#pragma unroll
+        for (int i = 0; i < UPT; ++i) {
+            double2 qv;
+            if (ok[i] & 4) qv = ld_stream(q + row[i]);
+            else { qv.x = (ok[i] & 1) ? q[row[i]] : 0.0; qv.y = (ok[i] & 2) ? q[row[i] + 1] : 0.0; }
+#pragma unroll
+            for (int a = 0; a < S; ++a) { v[a][i].x -= qv.x * h[a]; v[a][i].y -= qv.y * h[a]; }
+        }
+    }
+    double g[NP];
+#pragma unroll
+    for (int t = 0; t < NP; ++t) g[t] = 0.0;
+    auto store = [&](int a, int i, const double2& x) {
+        T* wa = w + a * ldw;
+        if (ok[i] & 4) {
+            d2s y;
+            y.x = x.x; y.y = x.y;
+            __builtin_nontemporal_store(y, reinterpret_cast<d2s*>(wa + row[i]));
+        } else {
+            if (ok[i] & 1) wa[row[i]] = x.x;
+            if (ok[i] & 2) wa[row[i] + 1] = x.y;
+        }
+    };
+#pragma unroll
+    for (int i = 0; i < UPT; ++i) {
+        double2 p[S];
+#pragma unroll
+        for (int a = 0; a < S; ++a) p[a] = v[a][i];
+        int t = 0;
+#pragma unroll
+        for (int a = 0; a < S; ++a)
+#pragma unroll
+            for (int b = a; b < S; ++b, ++t) g[t] += p[a].x * p[b].x + p[a].y * p[b].y;
+#pragma unroll
+        for (int a = S - 1; a >= 1; --a) {  // descending: q_a needs p_l', l < a, as they were
+#pragma unroll
+            for (int l = 0; l < a; ++l) { p[a].x += Cm[a][l] * p[l].x; p[a].y += Cm[a][l] * p[l].y; }
+            store(a, i, p[a]);
+            g[NG + a - 1] += p[a].x * p[a].x + p[a].y * p[a].y;
+        }
+        store(0, i, p[0]);
+        if (Z4) sm[threadIdx.x + i * BLK] = p[S - 1];
+    }
+    block_sumN_256<NP>(g, lds);  // (its barriers also publish sm)
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int t = 0; t < NP; ++t) part[(long long)t * gridDim.x + blk] = g[t];
+    }
+    if (Z4) {
+        const double* s = reinterpret_cast<const double*>(sm);
+        const int t = threadIdx.x;
+        if (t < nb) {
+            const long long i = a0 + t;
+            const T* A = dinv33 + i * 9;  // column-major image, as pc_apply_kernel (Q7)
+            const double x0 = s[3 * t], x1 = s[3 * t + 1], x2 = s[3 * t + 2], xp = s[768 + t];
+            const double y0 = A[0] * x0 + A[3] * x1 + A[6] * x2, y1 = A[1] * x0 + A[4] * x1 + A[7] * x2;
+            const double y2 = A[2] * x0 + A[5] * x1 + A[8] * x2, yp = xp * dinv1[i];
+            double2* o = reinterpret_cast<double2*>(z4 + 4 * i);
+            o[0] = make_double2(y0, y1);
+            o[1] = make_double2(y2, yp);
+        }
+    }
+}
+
 // The scalars of a block after the fix-up, one workgroup: nu[k+1+i] = ||q_i|| (i >= 1) from the fix-up's partials, measured and
 // not derived from G; *d_flag is raised when one of them is below 1e-4 sqrt(G_ii).  rho_i, the coordinates of p_i in v_0..v_{k+1+i}:
 // e_i in rows 0..k, U[l,i] / nu[k+1+l] in row k+1+l (l < i), nu[k+1+i] in row k+1+i.  p_i = B p_{i-1} and B v_j = Hraw[:,j] give
 //   H[:, k+i] = (rho_i - sum_{j < k+i} Hraw[:,j] rho_{i-1}[j]) / nu[k+i],   j ascending, from max(row - 1, 0) (Hessenberg zeros)
 // into H and its un-rotated copy, each column followed by its Givens step; S = 2 is pair_second_kernel term for term
+// the columns k+1..k+S-1 of that formula with their Givens steps, by a whole workgroup; s_nu = nu[k..k+S], s_t[l][i] = U[l,i] / nu[k+1+l]
+template <int S>
+__device__ __forceinline__ void block_columns(I k, T* H, T* Hraw, I ldh, const T* __restrict__ d_e, I lde, const double* s_nu,
+                                              const double (*s_t)[S], double* s_nrm, T* gv, T* beta, T* res_hist, double* s_col,
+                                              double* s_gv) {
+    for (int i = 1; i < S; ++i) {
+        const I c = k + i;  // the column; rows 0..c+1
+        T* col = H + (long long)c * ldh;
+        T* raw = Hraw + (long long)c * ldh;
+        const T* ei = d_e + (long long)i * lde;
+        const T* ep = d_e + (long long)(i - 1) * lde;
+        const double den = s_nu[i];  // rho_{i-1}[k+i] = nu[k+i]
+        for (int r = threadIdx.x; r <= c + 1; r += BLK) {
+            double t;
+            if (r <= k) t = ei[r];
+            else if (r - k - 1 < i) t = s_t[r - k - 1][i];
+            else t = s_nu[1 + i];
+            for (int j = (r > 0 ? r - 1 : 0); j < c; ++j) {
+                const double rp = (j <= k) ? ep[j] : s_t[j - k - 1][i - 1];  // rho_{i-1}[j], j < k+i
+                t -= rp * Hraw[(long long)j * ldh + r];
+            }
+            const double v = t / den;
+            raw[r] = v;
+            if (r <= c) col[r] = v;
+            else *s_nrm = v;
+        }
+        __syncthreads();
+        givens_step_block(c, *s_nrm, H, ldh, gv, beta, res_hist, s_col, s_gv);
+        __syncthreads();
+    }
+}
+
 template <int S>
 __global__ __launch_bounds__(BLK) void block_second_kernel(int npart, const T* part, I k, T* nu, T* H, T* Hraw, I ldh,
                                                           const T* __restrict__ d_e, I lde, const T* __restrict__ sc, T* gv, T* beta,
@@ -1096,31 +1353,119 @@ __global__ __launch_bounds__(BLK) void block_second_kernel(int npart, const T* p
             for (int i = 0; i < S; ++i) s_t[l][i] = (l < i) ? sc[SC_U + 4 * l + i] / s_nu[1 + l] : 0.0;
     }
     __syncthreads();
-    for (int i = 1; i < S; ++i) {
-        const I c = k + i;  // the column; rows 0..c+1
-        T* col = H + (long long)c * ldh;
-        T* raw = Hraw + (long long)c * ldh;
-        const T* ei = d_e + (long long)i * lde;
-        const T* ep = d_e + (long long)(i - 1) * lde;
-        const double den = s_nu[i];  // rho_{i-1}[k+i] = nu[k+i]
-        for (int r = threadIdx.x; r <= c + 1; r += BLK) {
-            double t;
-            if (r <= k) t = ei[r];
-            else if (r - k - 1 < i) t = s_t[r - k - 1][i];
-            else t = s_nu[1 + i];
-            for (int j = (r > 0 ? r - 1 : 0); j < c; ++j) {
-                const double rp = (j <= k) ? ep[j] : s_t[j - k - 1][i - 1];  // rho_{i-1}[j], j < k+i
-                t -= rp * Hraw[(long long)j * ldh + r];
-            }
-            const double v = t / den;
-            raw[r] = v;
-            if (r <= c) col[r] = v;
-            else s_nrm = v;
-        }
-        __syncthreads();
-        givens_step_block(c, s_nrm, H, ldh, gv, beta, res_hist, s_col, s_gv);
-        __syncthreads();
+    block_columns<S>(k, H, Hraw, ldh, d_e, lde, s_nu, s_t, &s_nrm, gv, beta, res_hist, s_col, s_gv);
+}
+
+// The scalars of a fused block (cgs_update_fixup_block_kernel), one workgroup, in the place of block_first_kernel and
+// block_second_kernel: C came from the derived Gram matrix before the pass (block_gram_kernel, sc[SC_C]); here everything that
+// enters H is measured on the vectors the pass formed.  part: S (S + 1) / 2 sets of npart partials of G = [<p_a', p_b'>], then
+// S - 1 sets of ||q_i||^2.  nu[k+1] = sqrt(G_00) and the Givens step of column k as block_first_kernel; U[l,i] = C[l].G[:,i], the
+// measured nu[k+1+i], the cancellation flag d_flag[0] and the columns k+1..k+S-1 by the code of block_second_kernel.  d_flag[1] is
+// raised when the q_a the pass formed are not orthogonal: |C[a].G.C[b]| > tau ||q_a|| ||q_b|| for some a < b.
+// One thing differs from block_second_kernel: the coordinate of p_i' along v_{k+1+l} is D[i,l] nu[k+1+l], D = C^-1, not
+// U[l,i] / nu[k+1+l].  The two agree when the q_i are orthogonal; with C from the derived G they are orthogonal only as far as
+// r_0..r_k are, the projection U / nu is then no coordinate, while p' = C^-1 q holds for the vectors formed whatever C is: the
+// relation B V = V H stays exact and a less accurate C costs orthogonality only.  (Dense "spread" operator of the numpy model,
+// s = 4: history 1.1e-12 r0 from plain Arnoldi with U / nu, 7.8e-14 with C^-1.)  U is still formed and left in sc.
+template <int S>
+__global__ __launch_bounds__(BLK) void block_fused_kernel(int npart, const T* __restrict__ part, I k, T* nu, T* H, T* Hraw, I ldh,
+                                                         const T* __restrict__ d_e, I lde, T* sc, T* gv, T* beta, T* res_hist,
+                                                         int* d_flag, double tau) {
+    constexpr int NG = S * (S + 1) / 2, NP = NG + S - 1;
+    __shared__ double lds[4 * NP];
+    __shared__ double s_nu[S + 1];
+    __shared__ double s_t[S][S];
+    __shared__ double s_nrm;
+    __shared__ double s_col[GIV_MAX], s_gv[2 * GIV_MAX];
+    double g[NP];
+#pragma unroll
+    for (int t = 0; t < NP; ++t) g[t] = 0.0;
+#pragma unroll 2
+    for (int i = threadIdx.x; i < npart; i += BLK) {  // (independent loads: one latency per trip)
+#pragma unroll
+        for (int t = 0; t < NP; ++t) g[t] += part[(long long)t * npart + i];
     }
+    block_sumN_256<NP>(g, lds);
+    if (threadIdx.x == 0) {
+        double gm[NG], G[4][4], Cm[4][4], Um[4][4];
+#pragma unroll
+        for (int t = 0; t < NG; ++t) gm[t] = g[t];
+        gram_unpack<S>(gm, G);
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) { Cm[a][b] = sc[SC_C + 4 * a + b]; Um[a][b] = 0.0; }
+#pragma unroll
+        for (int i = 0; i < S; ++i)
+#pragma unroll
+            for (int l = 0; l < i; ++l) {
+                double u = 0.0;
+#pragma unroll
+                for (int m = 0; m <= l; ++m) u += Cm[l][m] * G[m][i];
+                Um[l][i] = u;
+            }
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                sc[SC_G + 4 * a + b] = G[a][b];
+                sc[SC_U + 4 * a + b] = Um[a][b];
+            }
+        const double nu1 = sqrt(G[0][0]);
+        nu[k + 1] = nu1;
+        Hraw[(long long)k * ldh + k + 1] = nu1;
+        s_nrm = nu1;
+        s_nu[0] = nu[k];
+        s_nu[1] = nu1;
+        bool low = false;
+#pragma unroll
+        for (int i = 1; i < S; ++i) {
+            const double v = sqrt(g[NG + i - 1]);
+            nu[k + 1 + i] = v;
+            s_nu[1 + i] = v;
+            low = low || v < 1e-4 * sqrt(G[i][i]);
+        }
+        bool skew = false;  // <q_a, q_b> = C[a].G.C[b] as achieved, a < b
+#pragma unroll
+        for (int b = 1; b < S; ++b) {
+            double Gc[4];
+#pragma unroll
+            for (int m = 0; m < S; ++m) {
+                double r = 0.0;
+#pragma unroll
+                for (int l = 0; l <= b; ++l) r += G[m][l] * Cm[b][l];
+                Gc[m] = r;
+            }
+#pragma unroll
+            for (int a = 0; a < b; ++a) {
+                double qq = 0.0;
+#pragma unroll
+                for (int m = 0; m <= a; ++m) qq += Cm[a][m] * Gc[m];
+                skew = skew || !(fabs(qq) <= tau * s_nu[1 + a] * s_nu[1 + b]);
+            }
+        }
+        if (d_flag && low) d_flag[0] = 1;
+        if (d_flag && skew) d_flag[1] = 1;
+        // coordinates of p_i' in q_0..q_i from the identity p' = D q, D = C^-1 (forward substitution, m ascending): D[i][l] nu[k+1+l]
+        double D[4][4];
+#pragma unroll
+        for (int i = 0; i < S; ++i)
+#pragma unroll
+            for (int l = 0; l < i; ++l) {
+                double v = 0.0;
+#pragma unroll
+                for (int m = l; m < i; ++m) v -= Cm[i][m] * (m == l ? 1.0 : D[m][l]);
+                D[i][l] = v;
+            }
+#pragma unroll
+        for (int l = 0; l < S; ++l)
+#pragma unroll
+            for (int i = 0; i < S; ++i) s_t[l][i] = (l < i) ? D[i][l] * s_nu[1 + l] : 0.0;
+    }
+    __syncthreads();
+    givens_step_block(k, s_nrm, H, ldh, gv, beta, res_hist, s_col, s_gv);
+    __syncthreads();
+    block_columns<S>(k, H, Hraw, ldh, d_e, lde, s_nu, s_t, &s_nrm, gv, beta, res_hist, s_col, s_gv);
 }
 
 // H[0:m,0:m] y = beta by back substitution (cublasDtrsv, krylov.c:297-301), one workgroup: column-oriented so that every
@@ -1279,8 +1624,33 @@ void launch_dots_block(I n, I ncol, const T* Q, int64_t ldq, const T* w, int64_t
     const int nrb = ceil_div(n, BLK * BlockShape<NS>::R * 2);
     const int ntile = ceil_div(ncol, CTB);
     if ((long long)nrb * ntile > 0x7fffffffLL) abort();
-    cgs_dots_block_stage1<NS, BlockShape<NS>::R><<<nrb * ntile, BLK, 0, S(stream)>>>(n, ncol, Q, ldq, w, ldw, work, nrb, ntile);
+    cgs_dots_block_stage1<NS, BlockShape<NS>::R, false><<<nrb * ntile, BLK, 0, S(stream)>>>(n, ncol, Q, ldq, w, ldw, work, nrb, ntile,
+                                                                                            nullptr);
     cgs_dots_block_stage2<<<dim3(ncol, NS), BLK, 0, S(stream)>>>(nrb, ncol, work, d_nu, d_h, d_h_raw, d_e, d_c, lde);
+}
+// ... with the Gram partials of the S vectors behind the dots partials in work, and C from the derived Gram matrix into d_sc
+template <int NS>
+void launch_dots_block_gram(I n, I ncol, const T* Q, int64_t ldq, const T* w, int64_t ldw, const T* d_nu, T* d_h, T* d_h_raw,
+                            T* d_e, T* d_c, I lde, T* d_sc, T* work, void* stream) {
+    const int nrb = ceil_div(n, BLK * BlockShape<NS>::R * 2);
+    const int ntile = ceil_div(ncol, CTB);
+    if ((long long)nrb * ntile > 0x7fffffffLL) abort();
+    T* const gram = work + (size_t)NS * (size_t)ncol * (size_t)nrb;
+    cgs_dots_block_stage1<NS, BlockShape<NS>::R, true><<<nrb * ntile, BLK, 0, S(stream)>>>(n, ncol, Q, ldq, w, ldw, work, nrb, ntile,
+                                                                                           gram);
+    cgs_dots_block_gram_stage2<<<ncol * NS + NS * (NS + 1) / 2, BLK, 0, S(stream)>>>(nrb, ncol, NS, work, d_nu, d_h, d_h_raw, d_e, d_c, lde,
+                                                                                   gram, d_sc + SC_GR);
+    block_gram_kernel<NS><<<1, 64, 0, S(stream)>>>(ncol, d_e, lde, d_sc);
+}
+template <int NS>
+void launch_update_fixup_block(I N, I ncol, const T* Q, int64_t ldq, const T* d_c, I lde, T* w, int64_t ldw, const T* d_sc,
+                               const T* dinv33, const T* dinv1, T* z4, T* work, void* stream) {
+    const int g = ceil_div(N, BLK);
+    const int vec_ok = aligned16(Q) && aligned16(w) && !(ldq & 1) && !(ldw & 1);
+    if (z4) cgs_update_fixup_block_kernel<NS, true><<<g, BLK, 0, S(stream)>>>(N, ncol, Q, ldq, d_c, lde, w, ldw, d_sc, work, dinv33, dinv1,
+                                                                              z4, vec_ok);
+    else cgs_update_fixup_block_kernel<NS, false><<<g, BLK, 0, S(stream)>>>(N, ncol, Q, ldq, d_c, lde, w, ldw, d_sc, work, nullptr, nullptr,
+                                                                            nullptr, vec_ok);
 }
 template <int NS>
 void launch_fixup_block(I N, T* w, int64_t ldw, const T* d_sc, const T* dinv33, const T* dinv1, T* z4, T* work, void* stream) {
@@ -1395,8 +1765,12 @@ int64_t dfl_cgs_work_size(I n, I ncol) {
     int64_t a = 2 * nrb * (int64_t)(ncol > 0 ? ncol : 1);  // two vectors per dots pass (dfl_cgs_dots2_raw)
     int64_t b = 3 * (int64_t)ceil_div(n, UROWS);           // s11, s12, s22 of dfl_cgs_update2
     for (int s = 3; s <= 4; ++s) {                         // blocks of s products: s sets of dots partials, s (s + 1) / 2 of G
-        const int64_t as = (int64_t)s * dfl_cgs_dots_block_parts(n, s) * (int64_t)(ncol > 0 ? ncol : 1);
-        const int64_t bs = (int64_t)(s * (s + 1) / 2) * dfl_cgs_update_block_parts(n, s);
+        const int64_t ng = s * (s + 1) / 2;
+        // (fused blocks: the Gram partials of the raw vectors behind the dots partials; G and the s - 1 norms of the one pass)
+        const int64_t as = ((int64_t)s * (int64_t)(ncol > 0 ? ncol : 1) + ng) * dfl_cgs_dots_block_parts(n, s);
+        int64_t bs = ng * dfl_cgs_update_block_parts(n, s);
+        const int64_t fs = (ng + s - 1) * (int64_t)dfl_cgs_update_fixup_block_parts((I)ceil_div(n, 4));
+        if (fs > bs) bs = fs;
         if (as > a) a = as;
         if (bs > b) b = bs;
     }
@@ -1538,6 +1912,34 @@ void dfl_gmres_block_second(int npart, const T* part, int s, I k, T* d_nu, T* d_
     else if (s == 4)
         block_second_kernel<4><<<1, BLK, 0, S(stream)>>>(npart, part, k, d_nu, d_H, d_Hraw, ldh, d_e, lde, d_sc, d_gv, d_beta, d_res_hist,
                                                          d_flag);
+    else abort();
+    DFL_LAUNCH_CHECK();
+}
+int dfl_cgs_update_fixup_block_parts(I N) { return ceil_div(N, BLK); }
+void dfl_cgs_dots_block_gram(I n, I ncol, int s, const T* Q, int64_t ldq, const T* w, int64_t ldw, const T* d_nu, T* d_h, T* d_h_raw,
+                             T* d_e, T* d_c, I lde, T* d_sc, T* work, void* stream) {
+    if (ncol <= 0 || n <= 0) return;
+    if (s == 3) launch_dots_block_gram<3>(n, ncol, Q, ldq, w, ldw, d_nu, d_h, d_h_raw, d_e, d_c, lde, d_sc, work, stream);
+    else if (s == 4) launch_dots_block_gram<4>(n, ncol, Q, ldq, w, ldw, d_nu, d_h, d_h_raw, d_e, d_c, lde, d_sc, work, stream);
+    else abort();
+    DFL_LAUNCH_CHECK();
+}
+void dfl_cgs_update_fixup_block(I N, I ncol, int s, const T* Q, int64_t ldq, const T* d_c, I lde, T* w, int64_t ldw, const T* d_sc,
+                                const T* dinv33, const T* dinv1, T* z4, T* work, void* stream) {
+    if (N <= 0) return;
+    if (s == 3) launch_update_fixup_block<3>(N, ncol, Q, ldq, d_c, lde, w, ldw, d_sc, dinv33, dinv1, z4, work, stream);
+    else if (s == 4) launch_update_fixup_block<4>(N, ncol, Q, ldq, d_c, lde, w, ldw, d_sc, dinv33, dinv1, z4, work, stream);
+    else abort();
+    DFL_LAUNCH_CHECK();
+}
+void dfl_gmres_block_fused(int npart, const T* part, int s, I k, T* d_nu, T* d_H, T* d_Hraw, I ldh, const T* d_e, I lde, T* d_sc,
+                           T* d_gv, T* d_beta, T* d_res_hist, int* d_flag, T tau, void* stream) {
+    if (s == 3)
+        block_fused_kernel<3><<<1, BLK, 0, S(stream)>>>(npart, part, k, d_nu, d_H, d_Hraw, ldh, d_e, lde, d_sc, d_gv, d_beta, d_res_hist,
+                                                        d_flag, tau);
+    else if (s == 4)
+        block_fused_kernel<4><<<1, BLK, 0, S(stream)>>>(npart, part, k, d_nu, d_H, d_Hraw, ldh, d_e, lde, d_sc, d_gv, d_beta, d_res_hist,
+                                                        d_flag, tau);
     else abort();
     DFL_LAUNCH_CHECK();
 }

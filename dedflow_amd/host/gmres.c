@@ -88,7 +88,7 @@ void DflWsEnsure(KrylovExt* x, index_type n, index_type maxit, index_type ldh, i
     HIPGUARD(hipMemsetAsync(x->d_flag, 0, 16, DflStream()));
     x->hraw = (f64*)CdamMallocDevice((ptrdiff_t)(ldh + 32) * SIZE_OF(f64));
     x->h_unrot = (f64*)CdamMallocDevice((ptrdiff_t)ldh * maxit * SIZE_OF(f64));
-    x->pair_buf = (f64*)CdamMallocDevice((8 * (ptrdiff_t)ldh + 64) * SIZE_OF(f64));
+    x->pair_buf = (f64*)CdamMallocDevice((8 * (ptrdiff_t)ldh + 96) * SIZE_OF(f64));
     x->ws_n = n; x->ws_maxit = maxit; x->ws_fresh = TRUE;
 }
 
@@ -182,8 +182,9 @@ void DflPcApplyFused(PC* pc, index_type na, f64* w, const f64* d_nrm, f64* z) { 
    DFL_GMRES_RAW_BASIS=0 (one GPU: the normalised basis and the separate Jacobi pass instead of GMRES_STEP_RAW_BASIS),
    DFL_GMRES_BLOCK=1..4 (the most iterations the raw-basis step takes per pass over the basis, default 4), DFL_GMRES_TWO_STEP=0
    (the same as block 1: one iteration at a time), DFL_GMRES_FOLD_PC=0 (pairs and blocks: a Jacobi launch between two products
-   instead of the product that writes M^-1 of its own output) */
-typedef struct GmresEnv { b32 x4; index_type x4_min; b32 eager_sync, no_side_rows, no_fused_update_pc, raw_basis; int block; b32 fold_pc; } GmresEnv;
+   instead of the product that writes M^-1 of its own output), DFL_GMRES_FUSE_FIXUP=0 (blocks of three and four: the update and
+   the fix-up as two passes with the Gram matrix measured between them, instead of the one pass of dfl_cgs_update_fixup_block) */
+typedef struct GmresEnv { b32 x4; index_type x4_min; b32 eager_sync, no_side_rows, no_fused_update_pc, raw_basis; int block; b32 fold_pc, fuse_fixup; } GmresEnv;
 static GmresEnv gmres_env(void) {
     static int x4 = -1, x4_min = 4096;
     if (x4 < 0) {
@@ -207,9 +208,10 @@ static GmresEnv gmres_env(void) {
         }
     }
     if (two && atoi(two) == 0) block = 1;
-    const char* fold = getenv("DFL_GMRES_FOLD_PC");
+    const char *fold = getenv("DFL_GMRES_FOLD_PC"), *fuse = getenv("DFL_GMRES_FUSE_FIXUP");
     const GmresEnv e = {x4, x4_min, getenv("DFL_KRYLOV_EAGER_SYNC") != NULL, getenv("DFL_NO_SIDE_BOUNDARY_ROWS") != NULL,
-                        getenv("DFL_NO_FUSED_UPDATE_PC") != NULL, !(raw && atoi(raw) == 0), block, !(fold && atoi(fold) == 0)};
+                        getenv("DFL_NO_FUSED_UPDATE_PC") != NULL, !(raw && atoi(raw) == 0), block, !(fold && atoi(fold) == 0),
+                        !(fuse && atoi(fuse) == 0)};
     return e;
 }
 
@@ -270,6 +272,7 @@ void DflGmresPlanFill(GmresPlan* p, const KrylovExt* ex, index_type max_iter, Ma
            the one it reads */
         p->fold_pc = env.fold_pc && p->block > 1 && ((MatrixFS*)A->data)->spy1x1->diag_pos != NULL;
         if (p->fold_pc) p->z4b = p->z4 + (size_t)na;
+        p->fuse_fixup = env.fuse_fixup && p->block >= 3;
     }
 }
 
@@ -468,6 +471,19 @@ static void gmres_block(const GmresPlan* p, KrylovExt* ex, Matrix* A, PC* pc, in
     f64 *const h = ex->H + (size_t)k * (size_t)ldh, *const h_raw = ex->h_unrot + (size_t)k * (size_t)ldh;
     const int gu = dfl_cgs_update_block_parts(na, sb), gf = (int)CEIL_DIV(p->N, 256);
     gmres_products(p, ex, A, pc, k, sb, p0);
+    if (p->fuse_fixup) {
+        /* r_j / nu_j are orthonormal, so the Gram matrix of the updated vectors follows from that of the products and the dots
+           before the update runs: C is known beforehand, and one pass subtracts the old columns, applies C in its registers and
+           stores q_0..q_{s-1} and z4 once -- the p_i' never travel through memory.  C only chooses the basis inside the block; the
+           norms and the U[l,i] that go into H are measured on the vectors formed, as is their orthogonality (DFL_GMRES_ORTH_TAU) */
+        DFL_TIMED(DFL_TAG_CGS_DOTS, dfl_cgs_dots_block_gram(na, k + 1, sb, Q, na, p0, na, ex->nrm, h, h_raw, e, c, ldh, sc, ex->work, s));
+        DFL_TIMED(DFL_TAG_CGS_UPDATE, dfl_cgs_update_fixup_block(p->N, k + 1, sb, Q, na, c, ldh, p0, na, sc, p->d33, p->d1,
+                                                                 last ? NULL : p->z4, ex->work, s));
+        dfl_gmres_block_fused(gf, ex->work, sb, k, ex->nrm, ex->H, ex->h_unrot, ldh, e, ldh, sc, ex->gv, ex->beta, res_hist, ex->d_flag,
+                              DFL_GMRES_ORTH_TAU, s);
+        ex->last_fused++;
+        return;
+    }
     DFL_TIMED(DFL_TAG_CGS_DOTS, dfl_cgs_dots_block(na, k + 1, sb, Q, na, p0, na, ex->nrm, h, h_raw, e, c, ldh, ex->work, s));
     DFL_TIMED(DFL_TAG_CGS_UPDATE, dfl_cgs_update_block(na, k + 1, sb, Q, na, c, ldh, p0, na, ex->work, s));
     dfl_gmres_block_first(gu, ex->work, sb, k, ex->nrm, ex->H, ex->h_unrot, ldh, ex->gv, ex->beta, res_hist, sc, s);
@@ -615,14 +631,14 @@ static b32 gmres_check(const Krylov* ksp, const GmresPlan* p, KrylovExt* ex, Hos
 static void gmres_end_of_solve(KrylovExt* ex, index_type total, b32 read_flag) {
     hipStream_t s = DflStream();
     const index_type nh = total < 512 ? total : 512;
-    int flag = 0;
+    int flag[2] = {0, 0}; /* [0] cancellation; [1] a fused block whose q_i came out skew (dfl_gmres_block_fused) */
     if (nh) HIPGUARD(hipMemcpyAsync(ex->stats.res_hist, ex->res_hist, sizeof(f64) * (size_t)nh, D2H, s));
     if (read_flag) {
-        HIPGUARD(hipMemcpyAsync(&flag, ex->d_flag, sizeof flag, D2H, s));
-        HIPGUARD(hipMemsetAsync(ex->d_flag, 0, sizeof(int), s));
+        HIPGUARD(hipMemcpyAsync(flag, ex->d_flag, sizeof flag, D2H, s));
+        HIPGUARD(hipMemsetAsync(ex->d_flag, 0, sizeof flag, s));
     }
     HIPGUARD(hipStreamSynchronize(s));
-    ex->stats.fused_norm_cancelled = flag != 0;
+    ex->stats.fused_norm_cancelled = (flag[0] != 0 ? 1 : 0) | (flag[1] != 0 ? 2 : 0);
 }
 
 /* ============================== drivers ==================================================== */
@@ -651,6 +667,7 @@ static b32 gmres_run(Matrix* A, f64* x, f64* b, Krylov* ksp, b32 force_probe) {
     memset(ex->last_blocks, 0, sizeof ex->last_blocks);
     ex->last_pair_cancelled = 0;
     ex->last_folded = 0;
+    ex->last_fused = 0;
     f64 *const Q = ex->Q, *const tmp = ex->tmp;
     b32 converged = FALSE;
     index_type total = 0; /* iterations over all cycles */
@@ -675,7 +692,7 @@ static b32 gmres_run(Matrix* A, f64* x, f64* b, Krylov* ksp, b32 force_probe) {
             if (adv > maxit - total) adv = maxit - total;
             if (adv > ex->check_interval - total % ex->check_interval) adv = ex->check_interval - total % ex->check_interval;
             const b32 last = iter + adv >= m || total + adv >= maxit;
-            const int folded_before = ex->last_folded;
+            const int folded_before = ex->last_folded, fused_before = ex->last_fused;
             if (adv > 2) gmres_block(&p, ex, A, pc, iter, (int)adv, res_hist, last);
             else if (adv == 2) gmres_pair(&p, ex, A, pc, iter, res_hist, last);
             else {
@@ -699,6 +716,7 @@ static b32 gmres_run(Matrix* A, f64* x, f64* b, Krylov* ksp, b32 force_probe) {
                 /* converged: the step enqueued meanwhile (one iteration or several) is not counted */
                 if (DflKrylovConverged(ksp, fabs(ex->h_stat[8]), hr.rnrm_init)) {
                     ex->last_folded = folded_before;
+                    ex->last_fused = fused_before;
                     converged = TRUE;
                     break;
                 }
@@ -836,7 +854,8 @@ int DflKrylovLastGmresStep(Krylov* ksp) {
 }
 
 /* how the most recent unpipelined GMRES solve of this solver advanced: counts[s] = counted steps of s iterations, s = 1..4
-   (counts[0] = 0), and whether a pair or a block raised the cancellation flag (some ||q_i|| < 1e-4 ||p_i'||) */
+   (counts[0] = 0), and whether a pair or a block raised a flag: bit 0 cancellation (some ||q_i|| < 1e-4 ||p_i'||), bit 1 a fused
+   block whose q_i came out less orthogonal than DFL_GMRES_ORTH_TAU */
 void DflKrylovLastGmresBlocks(Krylov* ksp, int counts[5], int* cancelled) {
     const KrylovExt* ex = (ksp && ksp->ksp_solve == GMRESSolvePrivate) ? kext(ksp) : NULL;
     if (counts) for (int s = 0; s < 5; ++s) counts[s] = ex ? ex->last_blocks[s] : 0;
@@ -846,6 +865,11 @@ void DflKrylovLastGmresBlocks(Krylov* ksp, int counts[5], int* cancelled) {
    of a counted pair or block but its last; 0 with DFL_GMRES_FOLD_PC=0, single steps, or any other step or preconditioner */
 int DflKrylovLastFoldedProducts(Krylov* ksp) {
     return (ksp && ksp->ksp_solve == GMRESSolvePrivate && kext(ksp)) ? kext(ksp)->last_folded : 0;
+}
+/* how many counted blocks of three or four iterations of that solve ran the update and the fix-up as one pass
+   (GmresPlan.fuse_fixup): all of them by default, 0 with DFL_GMRES_FUSE_FIXUP=0 or where no such block runs */
+int DflKrylovLastFusedBlocks(Krylov* ksp) {
+    return (ksp && ksp->ksp_solve == GMRESSolvePrivate && kext(ksp)) ? kext(ksp)->last_fused : 0;
 }
 /* the same in pairs and single steps: a counted step of s iterations is floor(s / 2) pairs and s mod 2 single steps */
 void DflKrylovLastGmresPairs(Krylov* ksp, int* pairs, int* singles, int* cancelled) {

@@ -42,12 +42,14 @@ typedef struct KrylovExt {
     b32 no_calibration; /* inner / coarse solvers of PC_TWOLEVEL: never time basis placements (DflKrylovMarkInner) */
     char* amgx_cfg;     /* KrylovSetAMGXConfig: options of PCCreateAMGX (NULL: the reference configuration) */
     int last_step;      /* GmresStep of the most recent gmres_run (DflKrylovLastGmresStep), -1 before the first */
-    /* raw-basis steps of more than one iteration (GmresPlan.block): the un-rotated copy of H (same shape); pair_buf, 8 ldh + 64
-       doubles: [c1 | c2 | e | scalars] of a pair (ldh doubles each), or [c_0..c_3 | e_0..e_3 | G, C, U] of a block (gmres_block);
+    /* raw-basis steps of more than one iteration (GmresPlan.block): the un-rotated copy of H (same shape); pair_buf, 8 ldh + 96
+       doubles: [c1 | c2 | e | scalars] of a pair (ldh doubles each), or [c_0..c_3 | e_0..e_3 | G, C, U, derived G, raw sums] of a
+       block (gmres_block);
        and how many counted steps of each size the most recent gmres_run took (DflKrylovLastGmresBlocks) */
     f64 *h_unrot, *pair_buf;
     int last_blocks[5], last_pair_cancelled;
     int last_folded; /* products of the most recent gmres_run that wrote M^-1 of their own output (DflKrylovLastFoldedProducts) */
+    int last_fused;  /* counted blocks of that run whose update and fix-up were one pass (DflKrylovLastFusedBlocks) */
 } KrylovExt;
 
 static inline KrylovExt* kext(const Krylov* k) { return (KrylovExt*)k->ext; }
@@ -79,6 +81,9 @@ typedef struct GmresPlan {
     b32 fold_pc;               /* GMRES_STEP_RAW_BASIS, block > 1: every product of a pair or block but the last writes M^-1 of its
                                   own output, interleaved, for the product that follows (dfl_bcsr_spmv_x4_pc) instead of a Jacobi
                                   launch between the two; DFL_GMRES_FOLD_PC=0: the separate launches */
+    b32 fuse_fixup;            /* GMRES_STEP_RAW_BASIS, block >= 3: a block of three or four takes C from the Gram matrix derived in
+                                  the dots pass and runs update and fix-up as one pass (dfl_cgs_update_fixup_block), 9 launches
+                                  instead of 10; DFL_GMRES_FUSE_FIXUP=0: the two passes with G measured between them */
     GmresStep step;
     int block;                 /* GMRES_STEP_RAW_BASIS: the largest number of iterations one pass over the basis serves (1..4); a trip
                                   takes as many as fit into the cycle with no convergence check between them (gmres_pair: 2,
@@ -88,6 +93,11 @@ typedef struct GmresPlan {
     f64* Zb;                   /* FGMRES: the basis of preconditioned vectors; NULL otherwise */
     b32 lazy;                  /* host reads ride behind the next iteration instead of idling the device */
 } GmresPlan;
+
+/* A fused block raises bit 1 of the flag DflKrylovLastGmresBlocks reports when some |<q_a, q_b>| > tau ||q_a|| ||q_b||, measured on
+   the vectors it formed: 100 times the largest value the numpy model shows on the six Kuhn-cube systems M = 6..40
+   (9.3e-8 at M = 6; tests/fused_block_model.py: table()) */
+#define DFL_GMRES_ORTH_TAU 9.3e-6
 
 #define DFL_INTERNAL __attribute__((visibility("hidden"))) /* shared between the host sources, not exported */
 

@@ -506,10 +506,13 @@ void KrylovSetPipelined(Krylov* krylov, b32 on);
  * preconditioner, 4 raw basis: DESIGN.md section 3); -1 before the first solve or for another solver.  For tests and A/B runs */
 int DflKrylovLastGmresStep(Krylov* krylov);
 /* how that solve advanced: counts[s] = counted steps that took s iterations in one pass over the basis, s = 1..4 (counts[0] is 0),
-   and whether one of them raised its cancellation flag (a new vector lost more than four digits in the orthogonalisation) */
+   and whether one of them raised a flag: bit 0, a new vector lost more than four digits in the orthogonalisation; bit 1, a block
+   whose update and fix-up ran as one pass formed vectors less orthogonal to each other than 9.3e-6 */
 void DflKrylovLastGmresBlocks(Krylov* krylov, int counts[5], int* cancelled);
 /* how many matrix products of the most recent unpipelined GMRES solve wrote the Jacobi application of their own output */
 int DflKrylovLastFoldedProducts(Krylov* krylov);
+/* ... and how many of its counted blocks of three or four iterations ran update and fix-up as one pass (DFL_GMRES_FUSE_FIXUP=0: none) */
+int DflKrylovLastFusedBlocks(Krylov* krylov);
 /* the same as pairs and single steps: a counted step of s iterations adds floor(s / 2) to pairs and s mod 2 to singles */
 void DflKrylovLastGmresPairs(Krylov* krylov, int* pairs, int* singles, int* cancelled);
 /* A non-blocking stream (default priority) that was PROBED to run concurrently with `main_stream`: HIP maps streams onto a few

@@ -167,6 +167,32 @@ void dfl_cgs_fixup_block(dfl_index N, int s, dfl_value* w, int64_t ldw, const df
 void dfl_gmres_block_second(int npart, const dfl_value* part, int s, dfl_index k, dfl_value* d_nu, dfl_value* d_H, dfl_value* d_Hraw,
                             dfl_index ldh, const dfl_value* d_e, dfl_index lde, const dfl_value* d_sc, dfl_value* d_gv,
                             dfl_value* d_beta, dfl_value* d_res_hist, int* d_flag, void* stream);
+/* The same blocks with the update and the fix-up in one pass (host/gmres.c, GmresPlan.fuse_fixup).  r_j / nu_j are orthonormal, so
+ * the Gram matrix of the updated vectors is known before the update: G_ab = <p_a, p_b> - sum_{j<ncol} e_a[j] e_b[j]; C comes from it.
+ * d_sc holds 80 doubles here: G, C, U as above, then the derived G at 48 and the raw sums <p_a, p_b> at 64.
+ * dfl_cgs_dots_block_gram: dfl_cgs_dots_block (d_h, d_h_raw, d_e, d_c bit for bit) whose pass also sums <p_a, p_b>; work holds the
+ *   dots partials, then s (s + 1) / 2 x dfl_cgs_dots_block_parts(n, s) Gram partials; the second stage finishes both kinds of sums
+ *   in one launch, and a one-workgroup kernel then writes C, the derived G and the raw sums into d_sc (C by the Gram-Schmidt of
+ *   dfl_gmres_block_first).
+ * dfl_cgs_update_fixup_block: vectors of 4N rows; p_i -= Q d_c[i], then q_i = sum_{l<=i} C[i,l] p_l' from the registers, every
+ *   column stored once, z4 as dfl_cgs_fixup_block; q_i and z4 are those of dfl_cgs_update_block + dfl_cgs_fixup_block bit for bit.
+ *   work, g = dfl_cgs_update_fixup_block_parts(N): the partials of the measured G_ab = <p_a', p_b'>, a <= b, at work[t g], then
+ *   those of ||q_i||^2 at work[(s (s + 1) / 2 + i - 1) g].
+ * dfl_gmres_block_fused: in the place of dfl_gmres_block_first and dfl_gmres_block_second; reads C from d_sc, writes the measured
+ *   G and U = C G there, d_nu[k+1..k+s], columns k..k+s-1 of H and d_Hraw with their Givens steps.  The columns are those of
+ *   dfl_gmres_block_second with the coordinate of p_i' along v_{k+1+l} taken as (C^-1)[i,l] nu[k+1+l] -- exact for the vectors
+ *   formed whatever C is -- where U[l,i] / nu[k+1+l] presumes the q_i orthogonal.  d_flag (may be NULL) points to
+ *   two ints: [0] raised when some ||q_i|| < 1e-4 sqrt(G_ii), [1] when some |<q_a, q_b>| = |C[a].G.C[b]| > tau ||q_a|| ||q_b||. */
+int dfl_cgs_update_fixup_block_parts(dfl_index N);
+void dfl_cgs_dots_block_gram(dfl_index n, dfl_index ncol, int s, const dfl_value* Q, int64_t ldq, const dfl_value* w, int64_t ldw,
+                             const dfl_value* d_nu, dfl_value* d_h, dfl_value* d_h_raw, dfl_value* d_e, dfl_value* d_c, dfl_index lde,
+                             dfl_value* d_sc, dfl_value* work, void* stream);
+void dfl_cgs_update_fixup_block(dfl_index N, dfl_index ncol, int s, const dfl_value* Q, int64_t ldq, const dfl_value* d_c,
+                                dfl_index lde, dfl_value* w, int64_t ldw, const dfl_value* d_sc, const dfl_value* dinv33,
+                                const dfl_value* dinv1, dfl_value* z4, dfl_value* work, void* stream);
+void dfl_gmres_block_fused(int npart, const dfl_value* part, int s, dfl_index k, dfl_value* d_nu, dfl_value* d_H, dfl_value* d_Hraw,
+                           dfl_index ldh, const dfl_value* d_e, dfl_index lde, dfl_value* d_sc, dfl_value* d_gv, dfl_value* d_beta,
+                           dfl_value* d_res_hist, int* d_flag, dfl_value tau, void* stream);
 void dfl_dsqrt_dev(dfl_value* d_val, void* stream); /* *d_val = sqrt(*d_val) */
 /* y = Q[:,0:ncol] c  (cublasDgemv OP_N of krylov.c:304-311) */
 void dfl_gemv_n(dfl_index n, dfl_index ncol, const dfl_value* Q, int64_t ldq, const dfl_value* d_c, dfl_value* y, void* stream);

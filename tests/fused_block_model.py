@@ -1,0 +1,200 @@
+"""numpy model of the blocked raw-basis Arnoldi step whose update and fix-up are one pass (csrc/k_blas.hip: block_gram_kernel,
+cgs_update_fixup_block_kernel, block_fused_kernel; host/gmres.c: gmres_block with GmresPlan.fuse_fixup).  Test infrastructure
+only; block_step_model.py is the scheme with the two passes, and everything the two share is imported from it.
+
+The columns r_j / nu_j are orthonormal, so the Gram matrix of the updated vectors p_i' = p_i - sum_j (e_i[j] / nu_j) r_j is
+known before the update:  G_ab = <p_a, p_b> - sum_{j<=k} e_a[j] e_b[j]  (j ascending).  C, the unit lower triangular matrix
+with q_i = sum_{l<=i} C[i,l] p_l', comes from this derived G by the Gram-Schmidt of block_first_kernel.  C only chooses the
+basis inside the block: nu[k+1+i] = ||q_i||, U[l,i] = C[l].G[:,i] = <q_l, p_i'> and the cancellation flag (bit 0) are taken from
+the Gram matrix MEASURED on the p_i' and from the measured ||q_i||^2, as is the achieved <q_a, q_b> = C[a].G.C[b]; bit 1 of the
+flag is raised when one of them exceeds tau ||q_a|| ||q_b||.  The q_i from a derived G are orthogonal only as far as r_0..r_k
+are, so H takes the coordinates of p_i' from the identity p' = C^-1 q and the measured norms, not from the projections U / nu.  Blocks of one and two iterations are those of block_step_model.
+"""
+import numpy as np
+
+from block_step_model import SC_C, SC_U, block_second, block_sizes, fixup, gram_coefficients
+from two_step_model import givens_step
+
+TAU = 9.3e-6  # DFL_GMRES_ORTH_TAU (host/solver_private.h): 100 times the largest skew of table(), 9.3e-8 at M = 6
+TABLE_SIZES = (6, 8, 12, 16, 24, 40)
+
+
+def derived_gram(Graw, e, lde, ncol):
+    """G_ab = <p_a, p_b> - sum_{j<ncol} e_a[j] e_b[j], j ascending, upper triangle mirrored (block_gram_kernel)"""
+    s = Graw.shape[0]
+    G = np.zeros((s, s))
+    for a in range(s):
+        for b in range(a, s):
+            v = Graw[a, b]
+            for j in range(ncol):
+                v -= e[a * lde + j] * e[b * lde + j]
+            G[a, b] = G[b, a] = v
+    return G
+
+
+def measured_u(Cm, G):
+    """U[l,i] = sum_{m<=l} C[l,m] G[m,i], l < i, with C given (block_fused_kernel)"""
+    s = G.shape[0]
+    Um = np.zeros((4, 4))
+    for i in range(s):
+        for l in range(i):
+            u = 0.0
+            for m in range(l + 1):
+                u += Cm[l, m] * G[m, i]
+            Um[l, i] = u
+    return Um
+
+
+def achieved_skew(Cm, G, nus):
+    """largest |C[a].G.C[b]| / (||q_a|| ||q_b||), a < b; nus[a] = the measured ||q_a||"""
+    s = G.shape[0]
+    worst = 0.0
+    for b in range(1, s):
+        Gc = [sum(G[m, l] * Cm[b, l] for l in range(b + 1)) for m in range(s)]
+        for a in range(b):
+            qq = sum(Cm[a, m] * Gc[m] for m in range(a + 1))
+            worst = max(worst, abs(qq) / (nus[a] * nus[b]))
+    return worst
+
+
+def unit_lower_inverse(Cm, s):
+    """D = C^-1 of the unit lower triangular C by forward substitution: D[i,l] = -sum_{l<=m<i} C[i,m] D[m,l], m ascending"""
+    D = np.eye(4)
+    for i in range(s):
+        for l in range(i):
+            v = 0.0
+            for m in range(l, i):
+                v -= Cm[i, m] * D[m, l]
+            D[i, l] = v
+    return D
+
+
+def block_fused(G, Cm, qq, k, nu, H, Hraw, ldh, e, lde, gv, beta, hist, tau=TAU):
+    """the scalars of a fused block: G measured, C given, qq[i-1] = ||q_i||^2 measured; returns (sc, flag bits, skew).
+    The coordinates of p_i' that enter H are those of the identity p_i' = sum_l D[i,l] q_l, D = C^-1: D[i,l] nu[k+1+l] in row
+    k+1+l -- with q_i orthogonal that is U[l,i] / nu[k+1+l], and with C from the derived G, whose q_i are orthogonal only as far
+    as the basis is, it keeps B V = V H exact for the vectors formed.  U = C G is still formed and stored (sc)."""
+    s = G.shape[0]
+    G4 = np.zeros((4, 4))
+    G4[:s, :s] = G
+    Um = measured_u(Cm, G)
+    sc = np.concatenate([G4.reshape(-1), Cm.reshape(-1), Um.reshape(-1)])
+    nu1 = np.sqrt(G[0, 0])
+    nu[k + 1] = nu1
+    Hraw[k * ldh + k + 1] = nu1
+    givens_step(k, nu1, H, ldh, gv, beta, hist)
+    # block_second divides the U table it is given by nu[k+1+l]: hand it D[i,l] nu^2 in the place of U
+    D = unit_lower_inverse(Cm, s)
+    nus = [nu1] + [np.sqrt(q) for q in qq]
+    sc_d = sc.copy()
+    for l in range(s):
+        for i in range(l + 1, s):
+            sc_d[SC_U + 4 * l + i] = D[i, l] * nus[l] * nus[l]
+    flag = block_second(qq, k, nu, H, Hraw, ldh, e, lde, sc_d, gv, beta, hist)
+    skew = achieved_skew(Cm, G, nu[k + 1: k + 1 + s])
+    if not skew <= tau:
+        flag |= 2
+    return sc, flag, skew
+
+
+def gmres_blocked_fused(B, r0, m, block, tau=TAU):
+    """gmres_blocked of block_step_model with blocks of three and four fused: (H un-rotated (m+1, m), residual history, flag
+    bits, smallest ||q_i|| / ||p_i'||, largest |<q_a, q_b>| / (||q_a|| ||q_b||) as measured).  B: anything with B @ x"""
+    n = r0.size
+    R = np.zeros((m + 1, n))
+    ldh = m + 2
+    H, Hraw, gv, beta, hist = np.zeros(ldh * m), np.zeros(ldh * m), np.zeros(2 * m), np.zeros(m + 1), np.zeros(m)
+    nu = np.zeros(m + 2)
+    nu[0] = beta[0] = np.linalg.norm(r0)
+    R[0] = r0
+    k, flags, ratio, skew = 0, 0, 1.0, 0.0
+    for s in block_sizes(m, block):
+        P = np.zeros((s, n))
+        P[0] = (B @ R[k]) / nu[k]
+        for i in range(1, s):
+            P[i] = B @ P[i - 1]
+        e = np.zeros(s * ldh)
+        for i in range(s):
+            e[i * ldh: i * ldh + k + 1] = (R[:k + 1] @ P[i]) / nu[:k + 1]
+        H[k * ldh: k * ldh + k + 1] = e[:k + 1]
+        Hraw[k * ldh: k * ldh + k + 1] = e[:k + 1]
+        Graw = P @ P.T
+        for i in range(s):
+            P[i] = P[i] - (e[i * ldh: i * ldh + k + 1] / nu[:k + 1]) @ R[:k + 1]
+        if s == 1:  # the single raw-basis step
+            nu[k + 1] = np.linalg.norm(P[0])
+            Hraw[k * ldh + k + 1] = nu[k + 1]
+            R[k + 1] = P[0]
+            givens_step(k, nu[k + 1], H, ldh, gv, beta, hist)
+            k += 1
+            continue
+        G = P @ P.T
+        # blocks of two are the pair as it is: C from the measured G
+        Cm = gram_coefficients(derived_gram(Graw, e, ldh, k + 1) if s >= 3 else G)[0]
+        sc = np.zeros(48)
+        sc[SC_C:SC_C + 16] = Cm.reshape(-1)
+        Qn = fixup(P, sc)
+        R[k + 1: k + 1 + s] = Qn
+        qq = [Qn[i] @ Qn[i] for i in range(1, s)]
+        _, f, sk = block_fused(G, Cm, qq, k, nu, H, Hraw, ldh, e, ldh, gv, beta, hist, tau)
+        flags |= f if s >= 3 else f & 1
+        if s >= 3:
+            skew = max(skew, sk)
+        ratio = min([ratio] + [np.sqrt(qq[i - 1] / G[i, i]) for i in range(1, s)])
+        k += s
+    return Hraw.reshape(m, ldh).T[:m + 1], hist, flags, ratio, skew
+
+
+class OracleOperator:
+    """B = A M^-1 of the CPU oracle on the (u,p) rows: 4N-vectors, the phi / T tail held at zero"""
+
+    def __init__(self, S, vals):
+        self.S, self.vals, self.N = S, vals, S.N
+        self.d33, self.d1 = S.pc_setup(vals)
+
+    def __matmul__(self, x):
+        N = self.N
+        full = np.zeros(6 * N)
+        full[:4 * N] = x
+        return self.S.matvec(self.vals, self.S.pc_apply(self.d33, self.d1, full))[:4 * N].copy()
+
+
+def oracle_system(orc, M):
+    """(B, b, reference history, ||r0||) of the jittered Kuhn cube M, 40 iterations of the oracle's GMRES from x = 0"""
+    from dedflow_amd.meshgen import kuhn_cube, synthetic_fields
+    mesh = kuhn_cube(M, jitter=0.2)
+    wg, dwg = synthetic_fields(mesh)
+    S = orc.System(mesh)
+    F, vals = S.assemble_system(wg, dwg, True, True)
+    b = F.copy()
+    b[4 * S.N:] = 0.0
+    _, hist, r0, it = S.gmres(vals, b, maxit=40, atol=0.0, rtol=0.0)
+    assert it == 40
+    return OracleOperator(S, vals), b[:4 * S.N].copy(), hist, r0
+
+
+def table_row(orc, M):
+    """one system of table(): (M, err/bar of the two-pass scheme, err/bar of the fused scheme, flag bits of the fused scheme,
+    smallest ||q_i|| / ||p_i'||, largest measured |<q_a, q_b>| / (||q_a|| ||q_b||)); bar = 1e-10 r0 max(1, k / 10)"""
+    from block_step_model import gmres_blocked
+    B, b, href, r0 = oracle_system(orc, M)
+    bar = 1e-10 * r0 * np.maximum(1.0, np.arange(1, 41) / 10.0)
+    _, h_two, _, _ = gmres_blocked(B, b, 40, 4)
+    _, h_one, flags, ratio, skew = gmres_blocked_fused(B, b, 40, 4)
+    return M, np.max(np.abs(h_two - href) / bar), np.max(np.abs(h_one - href) / bar), flags, ratio, skew
+
+
+def table(orc, sizes=TABLE_SIZES):
+    """the six-system table of DESIGN.md section 3: 40 iterations in blocks of four on jittered Kuhn cubes"""
+    return [table_row(orc, M) for M in sizes]
+
+
+if __name__ == "__main__":
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from oracle import orc
+    orc.build()
+    print("   M   two passes   one pass  flags  min ||q||/||p'||  max skew")
+    for row in table(orc, tuple(int(a) for a in sys.argv[1:]) or TABLE_SIZES):
+        print("%4d   %10.3g %10.3g  %5d  %16.3g  %8.3g" % row, flush=True)
