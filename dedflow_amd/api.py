@@ -705,6 +705,12 @@ class DflThermalMaterial(C.Structure):
                 ("level", C.c_double), ("side", C.c_int32), ("eps", C.c_double)]
 
 
+class DflFluidMaterial(C.Structure):
+    _fields_ = [("rho_gas", C.c_double), ("rho_metal", C.c_double), ("mu_gas", C.c_double), ("mu_metal", C.c_double),
+                ("gravity", C.c_double * 3), ("beta", C.c_double), ("T_ref", C.c_double), ("use_phi", C.c_int32),
+                ("level", C.c_double), ("side", C.c_int32), ("eps", C.c_double)]
+
+
 class DflRedistance(C.Structure):
     _fields_ = [("level", C.c_double), ("band", C.c_double), ("hold_groups", C.c_int32), ("every", C.c_int32)]
 
@@ -903,6 +909,10 @@ def _declare(L):
     f("DflMeshThermalMaterialEnabled", i32, [C.POINTER(Mesh3D)])
     f("DflThermalMaterialCheck", C.c_int, [C.POINTER(DflThermalMaterial), C.c_char_p, C.c_size_t])
     f("DflMeshThermalRows", None, [C.POINTER(Mesh3D), vp, vp, vp, vp, vp])
+    f("DflMeshSetFluidMaterial", None, [C.POINTER(Mesh3D), C.POINTER(DflFluidMaterial)])
+    f("DflMeshFluidMaterialEnabled", i32, [C.POINTER(Mesh3D)])
+    f("DflFluidMaterialCheck", C.c_int, [C.POINTER(DflFluidMaterial), C.c_char_p, C.c_size_t])
+    f("DflMeshFluidRows", None, [C.POINTER(Mesh3D), vp, vp, vp, vp, vp])
     f("DflMeshSetRedistance", None, [C.POINTER(Mesh3D), C.POINTER(DflRedistance)])
     f("DflMeshRedistanceEnabled", i32, [C.POINTER(Mesh3D)])
     f("DflRedistanceCheck", C.c_int, [C.POINTER(DflRedistance), C.c_char_p, C.c_size_t])
@@ -1215,6 +1225,40 @@ class Problem:
         out = {k: DeviceArray(self.N) for k in ("r", "Kn", "Cn") if k in want}
         ptr = [out[k].ptr if k in out else None for k in ("r", "Kn", "Cn")]
         lib().DflMeshThermalRows(self.mesh, w.ptr, dw.ptr, ptr[0], ptr[1], ptr[2])
+        return out
+
+    # ---- fluid material (include/dedflow.h, "fluid material") -----------------------------------------------------------------
+    def set_fluid_material(self, rho_gas=None, rho_metal=None, mu_gas=None, mu_metal=None, gravity=(0.0, 0.0, 0.0), beta=0.0,
+                           T_ref=0.0, use_phi=False, level=0.0, side=1, eps=1.0):
+        """DflMeshSetFluidMaterial: densities (rho_gas None: rho_metal) and viscosities (mu_gas None: mu_metal) of the (u,p)
+        rows, the gravity vector and the thermal expansion beta of the metal about T_ref (Boussinesq: only the weight sees
+        it); use_phi: metal where side (phi - level) > 0, smeared over eps, gas elsewhere.  rho_metal None turns the feature
+        off.  A configuration the library refuses (reported on stderr) leaves the mesh as it was: fluid_material_on tells."""
+        if rho_metal is None:
+            lib().DflMeshSetFluidMaterial(self.mesh, None)
+            return
+        rho_gas = rho_metal if rho_gas is None else rho_gas
+        mu_gas = mu_metal if mu_gas is None else mu_gas
+        cfg = DflFluidMaterial(float(rho_gas), float(rho_metal), float(mu_gas), float(mu_metal),
+                               (C.c_double * 3)(*[float(v) for v in gravity]), float(beta), float(T_ref), 1 if use_phi else 0,
+                               float(level), int(side), float(eps))
+        lib().DflMeshSetFluidMaterial(self.mesh, C.byref(cfg))
+
+    @property
+    def fluid_material_on(self):
+        return bool(lib().DflMeshFluidMaterialEnabled(self.mesh))
+
+    def fluid_rows(self, w, dw, want=("r", "Rn", "Mn")):
+        """DflMeshFluidRows at (w, dw) taken as the alpha states (DeviceArrays of 6N): a dict of the wanted outputs as
+        DeviceArrays, the (u,p)-row correction r [4N] and the nodal totals Rn, Mn [N]; the others are passed as NULL"""
+        bad = set(want) - {"r", "Rn", "Mn"}
+        if bad:
+            raise ValueError(f"fluid_rows: unknown outputs {sorted(bad)}")
+        if not self.fluid_material_on:
+            raise RuntimeError("no fluid material is set: call set_fluid_material first")
+        out = {k: DeviceArray(4 * self.N if k == "r" else self.N) for k in ("r", "Rn", "Mn") if k in want}
+        ptr = [out[k].ptr if k in out else None for k in ("r", "Rn", "Mn")]
+        lib().DflMeshFluidRows(self.mesh, w.ptr, dw.ptr, ptr[0], ptr[1], ptr[2])
         return out
 
     # ---- level-set redistancing (include/dedflow.h, "level-set redistancing") ----------------------------------------------

@@ -237,6 +237,9 @@ void DflAssembleSystemPrepacked(Mesh3D* mesh, f64* wgalpha, f64* dwgalpha, f64* 
     /* thermal material (include/dedflow.h): the T rows' correction to k_q and c_q, after the phase-change rows and before the
        rows are captured; launched only when the scalar transport advances T */
     if (F && x->thermal) DflThermalApplyRows(mesh, wgalpha, dwgalpha, F);
+    /* fluid material (include/dedflow.h): the (u,p) rows' correction to rho_q, mu_q and the body force on F, the matching
+       difference blocks on J after the phase-change diagonal; both before the Dirichlet rows */
+    if (x->fluid) DflFluidApplySystem(mesh, wgalpha, dwgalpha, F, J);
     x->nodep_current = FALSE;
     if (F && x->scalar) DflScalarCaptureResidual(mesh, F); /* the phi / T rows, kept for the scalar transport (host/scalar.c) */
     if (F) HIPGUARD(hipMemsetAsync(F + 4 * (size_t)num_node, 0, (size_t)num_node * sizeof(f64) * 2, s)); /* main.c:63-66 */

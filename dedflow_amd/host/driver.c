@@ -98,6 +98,10 @@ index_type SolveFlowSystem(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matr
         fprintf(stderr, "SolveFlowSystem: the thermal material is single-GPU only; the solver has a communicator: solve refused\n");
         return -1;
     }
+    if (DflMeshFluidMaterialEnabled(mesh) && comm) {
+        fprintf(stderr, "SolveFlowSystem: the fluid material is single-GPU only; the solver has a communicator: solve refused\n");
+        return -1;
+    }
     FlowWork* fw = fw_get(mesh);
     KrylovSetMesh(ksp, mesh); /* node coordinates for aggregation-based preconditioners */
     f64 *wgalpha = fw->wgalpha, *dwgalpha = fw->dwgalpha;
@@ -178,6 +182,10 @@ index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* 
     }
     if (DflMeshThermalMaterialEnabled(mesh) && KrylovGetComm(ksp)) {
         fprintf(stderr, "DflTimeStep: the thermal material is single-GPU only; the solver has a communicator: step refused\n");
+        return -1;
+    }
+    if (DflMeshFluidMaterialEnabled(mesh) && KrylovGetComm(ksp)) {
+        fprintf(stderr, "DflTimeStep: the fluid material is single-GPU only; the solver has a communicator: step refused\n");
         return -1;
     }
     if (DflRedistanceInTimeStep(mesh) && KrylovGetComm(ksp)) {

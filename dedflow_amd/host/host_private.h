@@ -81,6 +81,7 @@ typedef struct MeshExt {
     struct PhaseState* phase;      /* phase change (host/phase.c, DflMeshSetPhaseChange), NULL: off */
     b32 phase_current;             /* its D and H already hold the alpha states the next driver assembly is given */
     struct ThermalState* thermal;  /* thermal material (host/thermal.c, DflMeshSetThermalMaterial), NULL: off */
+    struct FluidState* fluid;      /* fluid material (host/fluid.c, DflMeshSetFluidMaterial), NULL: off */
     struct RedistanceState* redistance; /* level-set redistancing (host/redistance.c, DflMeshSetRedistance), NULL: off */
     struct VolumeState* volume;    /* level-set volume correction (host/volume.c, DflMeshSetVolumeCorrection), NULL: off */
     index_type *v2e_row, *v2e_col; /* device [N+1], [4T]: the sorted V2E map (DflMeshSortedV2E), NULL until first asked for */
@@ -415,6 +416,13 @@ void DflThermalFree(struct ThermalState* st);
 void DflThermalApplyRows(Mesh3D* mesh, const f64* wgalpha, const f64* dwgalpha, f64* F);
 /* the configuration as the kernels take it (the T Jacobian's MATERIAL launch, host/scalar.c), NULL: off */
 const dfl_thermal_params* DflThermalParams(const Mesh3D* mesh);
+
+/* host/fluid.c: the fluid material of a mesh (no-ops while it is off) */
+struct FluidState;
+void DflFluidFree(struct FluidState* st);
+/* F[0 .. 4N) += r at the alpha states (one launch) and, with J, the block values += S (one launch; J must keep the block
+ * layout) */
+void DflFluidApplySystem(Mesh3D* mesh, const f64* wgalpha, const f64* dwgalpha, f64* F, Matrix* J);
 
 /* host/redistance.c: the level-set redistancing of a mesh (no-ops while it is off) */
 struct RedistanceState;

@@ -99,6 +99,7 @@ void Mesh3DDestroy(Mesh3D* m) {
         DflSurfaceFree(x->surface);
         DflPhaseFree(x->phase);
         DflThermalFree(x->thermal);
+        DflFluidFree(x->fluid);
         DflRedistanceFree(x->redistance);
         DflVolumeCorrectionFree(x->volume);
         CdamFreeDevice(x->v2e_row, 0); /* after the feature states that borrowed it */

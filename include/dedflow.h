@@ -1460,7 +1460,8 @@ void DflMeshPhaseChangeStats(Mesh3D* mesh, const f64* w, DflPhaseChangeStats* ou
  *               they are the node's mean conductivity and capacity.
  * Limits: one GPU (SolveFlowSystem and DflTimeStep with a communicator print why and return -1); the SUPG part of the T row
  * keeps kRHO kCP and kKAPPA (tau3 and its test-function factor): it stays a positive streamline-diffusion term, mis-scaled
- * by c_q / (kRHO kCP); no density change in the momentum rows; k does not depend on T other than through fl.  A 1000 : 1
+ * by c_q / (kRHO kCP); no density change in the momentum rows from this section (density, viscosity and weight there are the
+ * section "fluid material" below); k does not depend on T other than through fl.  A 1000 : 1
  * conductivity jump costs the Jacobi-preconditioned T solve iterations: PC_AMGX (DflScalarTransport.pc) is the remedy. */
 typedef struct DflThermalMaterial {
     f64 k_gas, k_solid, k_liquid;     /* W/(m K), each > 0 */
@@ -1480,6 +1481,76 @@ b32  DflMeshThermalMaterialEnabled(const Mesh3D* mesh);
 /* w, dw: device 6N, taken as the alpha states; r, Kn, Cn [N] on the device, any of them NULL, every other one overwritten in
  * full.  Without a configuration: a line on stderr, nothing written */
 void DflMeshThermalRows(Mesh3D* mesh, const f64* w, const f64* dw, f64* r, f64* Kn, f64* Cn);
+
+/* ---- fluid material: density, viscosity and buoyancy of the (u,p) rows follow phi (build-defined; opt-in) ----------------
+ * The reference's momentum and continuity rows belong to one fluid without weight: kRHO = 1000, kMU = 10/3 and a zero body
+ * force everywhere, so the shielding gas is as heavy and as viscous as the metal and a hot pool has no natural convection.
+ * A mesh that never calls DflMeshSetFluidMaterial with a configuration, or clears it with NULL, computes bit for bit what it
+ * computes without this section, through the same launches.  One GPU only.  With a configuration the (u,p) rows and the
+ * (u,p) Jacobian become those with rho_q, mu_q and the body force f_q below at every quadrature point, by a correction that
+ * is added to what the untouched assembly kernels give.
+ *   per tet     grad N_a, det, g, |g|, d_a, d_q, m_q = Hs(side d_q / eps) and the rule for a tet with !(|g| > 0) exactly as
+ *               the phase-change and thermal-material sections form them (the same closed form, without fused
+ *               multiply-add); without use_phi m_q = 1.  T_q = sum_a N_a(q) T_a.
+ *                 rho_q  = rho_gas + m_q (rho_metal - rho_gas)
+ *                 mu_q   = mu_gas  + m_q (mu_metal  - mu_gas)
+ *                 f_q[i] = gravity[i] (1 - m_q beta (T_q - T_ref))          a NaN T_q gives the factor 1
+ *               Only the weight sees beta; the inertia keeps rho_q (Boussinesq).  T is read only when beta != 0.
+ *               W = |det| / 24 and the four quadrature points of the assembly.
+ *   rows        E_a[0..3](rho[4], mu[4], f[4][3]) is the contribution of a tet to the three momentum rows and the continuity
+ *               row of its node a: the terms of the element residual of the assembly (rLi, tmp0, tmp1, tau[0], tau[1] and the
+ *               two weak forms) at the alpha states (u from wgalpha; du and the pressure from dwgalpha, as the assembly takes
+ *               them), with rho_q for kRHO, mu_q for kMU and f_q for the body force at quadrature point q wherever they occur.
+ *               Stabilisation: nu_q = mu_q / rho_q, y_q = t1_q + 3 nu_q^2 sum G_ij^2, tau0_q = (1 / sqrt(4 / dt^2 + y_q)) / rho_q,
+ *               tau1_q = sqrt(y_q) / tr G, where t1_q is the velocity term of the kernel that the correction belongs to: u.G.u
+ *               as the residual forms it in the rows, |J^-1 u_q|^2 = sum_{b=1..3} (u_q . grad N_b)^2 as the element Jacobian
+ *               forms it in the blocks.  The correction of a tet is
+ *                 r_a(e) = E_a(rho_q, mu_q, f_q) - E_a(kRHO, kMU, 0),
+ *               both evaluations through the same function without fused multiply-add, so a tet whose coefficients are the
+ *               built-in ones and whose f_q are zero gives exactly +0.0.  r[3a + d] and r[3N + a] are the sums over a's tets in
+ *               ascending tet id, from +0.0.  One launch over the nodes' sorted tet lists (csrc/k_fluid.hip), no float atomics,
+ *               bitwise reproducible, the same under every assembly schedule.  Every F assembly adds r to R[0 .. 4N) after the
+ *               thermal-material rows and before the Dirichlet rows.
+ *   Jacobian    B_ab(rho[4], mu[4]) is the 4 x 4 block of the element Jacobian with the coefficients inside the quadrature
+ *               sums (s_a = N_a(q), c_a = u_q . grad N_a, eK = grad N_a . grad N_b, f1 = kALPHAM, f2 = kDT kALPHAF kGAMMA,
+ *               w = W):
+ *                 diag = w sum_q [ f1 rho_q s_a s_b + f1 rho_q^2 tau0_q c_a s_b + f2 rho_q s_a c_b + f2 rho_q^2 tau0_q c_a c_b
+ *                                  + f2 mu_q eK ]
+ *                 B[i][j] = cK gradN_a[j] gradN_b[i] + cT gradN_a[i] gradN_b[j] (+ diag for i == j),
+ *                           cK = f2 w sum_q mu_q, cT = f2 w sum_q rho_q tau1_q
+ *                 B[i][3] = cP1 gradN_b[i] - cP0 gradN_a[i],  cP0 = w sum_q s_b, cP1 = w sum_q rho_q tau0_q c_a
+ *                 B[3][i] = cU0 gradN_a[i] + cU1 gradN_b[i],  cU0 = w sum_q rho_q tau0_q (f1 s_b + f2 c_b), cU1 = w f2 sum_q s_a
+ *                 B[3][3] = w eK sum_q tau0_q
+ *               The body force does not enter (the base Jacobian does not differentiate rLi either), and the coefficients are
+ *               frozen at the alpha states: Picard in phi and T, as in the two sections before.
+ *                 jm_ab(e) = B_ab(rho_q, mu_q) - B_ab(kRHO, kMU).
+ *               For every nonzero (a, b) of the nodal pattern S = the sum of jm_ab(e) over a's tets that hold b, in ascending
+ *               tet id from +0.0, and val[16 nz + e] = fl(val[16 nz + e] + S[e]): every J assembly, after the tet and face
+ *               terms AND after the phase-change diagonal, before the Dirichlet unit rows.  J needs the block layout of the
+ *               (u,p) matrix (with MatrixFSUseReferenceLayout: an ASSERT with a message, as for the phase-change drag).
+ *   inspection  Rn[a] = sum W N_a(q) rho_q and Mn[a] = sum W N_a(q) mu_q (totals, not differences): divided by the nodal volume
+ *               they are the node's mean density and viscosity.
+ * Limits: one GPU (SolveFlowSystem and DflTimeStep with a communicator print why and return -1); the weak-boundary-condition
+ * face terms keep kRHO and kMU; the SUPG part of the T row and the DEM drag keep their own constants; the mixing is arithmetic
+ * in m_q; no volume change on melting (the continuity row stays div u). */
+typedef struct DflFluidMaterial {
+    f64 rho_gas, rho_metal;   /* kg/m^3, each > 0 */
+    f64 mu_gas,  mu_metal;    /* Pa s,   each > 0 */
+    f64 gravity[3];           /* m/s^2; all zero: no weight */
+    f64 beta, T_ref;          /* thermal expansion of the metal, 1/K (Boussinesq); beta = 0: none */
+    b32 use_phi; f64 level; index_type side; f64 eps;   /* as DflPhaseChange; use_phi 0: metal everywhere */
+} DflFluidMaterial;
+/* host only: 0 when DflMeshSetFluidMaterial accepts the configuration, else why not in `why`.  Refused: any non-finite
+ * value, a density or viscosity <= 0, use_phi with side not +-1 or eps <= 0 */
+int  DflFluidMaterialCheck(const DflFluidMaterial* cfg, char* why, size_t why_len);
+/* the configuration is copied; NULL: off.  A refused configuration is reported on stderr and leaves the mesh unchanged.  Has
+ * the mesh build the sorted tet lists of the nodes if nothing did before (shared, freed with the mesh) and synchronises: the
+ * later calls allocate nothing and do not wait for the device */
+void DflMeshSetFluidMaterial(Mesh3D* mesh, const DflFluidMaterial* cfg);
+b32  DflMeshFluidMaterialEnabled(const Mesh3D* mesh);
+/* w, dw: device 6N, taken as the alpha states; r [4N], Rn, Mn [N] on the device, any of them NULL, every other one
+ * overwritten in full.  Without a configuration: a line on stderr, nothing written */
+void DflMeshFluidRows(Mesh3D* mesh, const f64* w, const f64* dw, f64* r, f64* Rn, f64* Mn);
 
 /* ---- level-set redistancing: the exact band distance to the surface phi = level (build-defined; opt-in) -----------------
  * The reference advects phi and never restores |grad phi| = 1.  A mesh that never calls DflMeshSetRedistance with a

@@ -993,6 +993,38 @@ void dfl_assemble_scalar_jacobian_material(dfl_index N, const dfl_index* vrow, c
                                            const dfl_index* col_ind, const dfl_thermal_params* prm, dfl_value* val_phi,
                                            dfl_value* val_T, void* stream);
 
+/* ---- fluid material (build-defined, opt-in; host/fluid.c, csrc/k_fluid.hip, csrc/fluid_coeff.hpp, model in include/dedflow.h)
+ *    dfl_fluid_rows          the node sums r [4N] (momentum rows r[3a + d], continuity rows r[3N + a]), Rn [N] (kg), Mn [N]
+ *                            (Pa s m^3) at the states w, dw [6N] (taken as the alpha states; the pressure is dw[3N + a], as
+ *                            in the assembly); any of them NULL: not written, the others overwritten in full.  vrow / vcol:
+ *                            the V2E map of the tets with every list ascending.  The node gather of the thermal rows: a lane
+ *                            per (node, tet), the shares added in list order through LDS, no atomics, bitwise reproducible.
+ *                            r alone: a tet whose rho_q, mu_q are the built-in constants and whose f_q are zero leaves
+ *                            early; its share of r is +0.0 in either case.
+ *    dfl_fluid_add_rows      the same r, added by its owner lanes to F[0 .. 4N): F[i] += r[i], r[i] summed and rounded
+ *                            first.  One launch, no buffer.
+ *    dfl_fluid_add_jacobian  val[16 nz + e] += S[e] for every nonzero nz of the nodal pattern row_ptr / col_ind (block values
+ *                            of the (u,p) matrix, e = 4 i + j): S = the sum of the difference blocks jm_ab over the row's
+ *                            tets that hold the column, ascending tet id, from +0.0, rounded before the one
+ *                            read-modify-write by the lane that owns the nonzero.  wgalpha: u, phi (with use_phi) are read.
+ * Every launcher returns at once for N <= 0. */
+typedef struct dfl_fluid_params {
+    dfl_value rho_gas, rho_metal, mu_gas, mu_metal;
+    dfl_value gravity[3];
+    dfl_value beta, T_ref;
+    dfl_value level, side, eps;
+    int use_phi;
+} dfl_fluid_params;
+void dfl_fluid_rows(dfl_index N, const dfl_index* vrow, const dfl_index* vcol, const dfl_index* ien, const dfl_value* xg,
+                    const dfl_value* w, const dfl_value* dw, const dfl_fluid_params* prm, dfl_value* r, dfl_value* Rn,
+                    dfl_value* Mn, void* stream);
+void dfl_fluid_add_rows(dfl_index N, const dfl_index* vrow, const dfl_index* vcol, const dfl_index* ien, const dfl_value* xg,
+                        const dfl_value* wgalpha, const dfl_value* dwgalpha, const dfl_fluid_params* prm, dfl_value* F,
+                        void* stream);
+void dfl_fluid_add_jacobian(dfl_index N, const dfl_index* vrow, const dfl_index* vcol, const dfl_index* ien, const dfl_value* xg,
+                            const dfl_value* wgalpha, const dfl_index* row_ptr, const dfl_index* col_ind,
+                            const dfl_fluid_params* prm, dfl_value* val, void* stream);
+
 /* ---- level-set redistancing (build-defined, opt-in; host/redistance.c, csrc/k_redistance.hip, model in include/dedflow.h)
  * phi = w + 4N.  grid: the uniform cell grid over the mesh's bounding box; a point's cell per axis is
  * clamp(floor((x - lo) inv_h), 0, n - 1), cell id = cx + n[0] (cy + n[1] cz).
