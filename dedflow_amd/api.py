@@ -815,7 +815,7 @@ def _declare(L):
     f("DflKrylovLastGmresStep", C.c_int, [vp])
     f("DflKrylovLastGmresPairs", None, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)])
     f("DflKrylovLastGmresBlocks", None, [vp, C.POINTER(C.c_int * 5), C.POINTER(C.c_int)])
-    # blocks of 3 or 4 Arnoldi steps per pass over the raw basis (csrc/k_blas.hip)
+    # blocks of 3 or 4 Arnoldi steps per pass over the raw basis (csrc/k_cgs_block.hip)
     f("dfl_cgs_dots_block_parts", C.c_int, [i32, C.c_int]); f("dfl_cgs_update_block_parts", C.c_int, [i32, C.c_int])
     f("dfl_cgs_dots_block", None, [i32, i32, C.c_int, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, vp, i32, vp, vp])
     f("dfl_cgs_update_block", None, [i32, i32, C.c_int, vp, C.c_int64, vp, i32, vp, C.c_int64, vp, vp])

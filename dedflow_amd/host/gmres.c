@@ -240,7 +240,7 @@ void DflGmresPlanFill(GmresPlan* p, const KrylovExt* ex, index_type max_iter, Ma
     const b32 tree_4n = DflPcJacobiTreeData(pc, &p->d33, &p->d1, &p->N, &p->rows) && na == 4 * p->N;
     /* fused norm + Jacobi tree on the (u,p) rows (partitioned runs of <= 500k owned nodes; the small last-level solver of
        PC_TWOLEVEL, which is bound by launch latency): update, Givens step and the next step's preconditioner application in
-       one launch (csrc/k_blas.hip, cgs_update_pc_kernel) */
+       one launch (csrc/k_cgs.hip, cgs_update_pc_kernel) */
     const b32 fuse_pc = ex->fused_norm && !ex->flexible && p->m + 2 <= 1024 && !env.no_fused_update_pc && tree_4n && p->rows > 0 &&
                         p->rows <= 500000; /* measured: 38 us against 31 + 7 + 6 us for the three kernels at 227k owned nodes, but
                                               274 us against 192 + 46 + 10 us at 1.73M (the node-per-thread mapping streams the
@@ -261,7 +261,7 @@ void DflGmresPlanFill(GmresPlan* p, const KrylovExt* ex, index_type max_iter, Ma
     p->x4_skip_z = p->x4 == GMRES_X4_SINGLE && tree_4n && p->N == p->x4_N && !p->Zb;
     /* one GPU, Jacobi tree, interleaved matvec input: the basis stays unnormalised (column k = r_k, nrm[k] = ||r_k||), the update
        kernel applies M^-1 to the column it has just formed and the matvec divides by nrm[k] -- the separate Jacobi pass, which
-       read the new column back only to scale it, is gone (csrc/k_blas.hip, cgs_update_jacobi_kernel).  Restarts, lazy or eager
+       read the new column back only to scale it, is gone (csrc/k_cgs.hip, cgs_update_jacobi_kernel).  Restarts, lazy or eager
        reads and the check interval have no say here: the arithmetic of a solve does not depend on them */
     if (p->step == GMRES_STEP_REFERENCE && p->x4_skip_z && p->rows == p->N && env.raw_basis) {
         p->step = GMRES_STEP_RAW_BASIS;
@@ -439,7 +439,7 @@ static void gmres_products(const GmresPlan* p, KrylovExt* ex, Matrix* A, PC* pc,
    the component of p2 orthogonal to v_0..v_{k+1} is a multiple of v_{k+2}, because B v_j lies in span(v_0..v_{j+1}).  One dots
    pass and one update pass over columns 0..k serve both vectors; p1' = r_{k+1}; the fix-up q = p2' - c p1' (one column) leaves
    r_{k+2} = q in column k+2 with z4 = M^-1 q for the step that follows (last: none does).  Columns k and k+1 of H, their Givens
-   steps, beta and two entries of the history come from two small kernels (csrc/k_blas.hip, pair_first_kernel and
+   steps, beta and two entries of the history come from two small kernels (csrc/k_cgs_block.hip, pair_first_kernel and
    pair_second_kernel); nothing waits for the whole grid and no sum is taken atomically */
 static void gmres_pair(const GmresPlan* p, KrylovExt* ex, Matrix* A, PC* pc, index_type k, f64* res_hist, b32 last) {
     const index_type na = p->na, ldh = p->ldh;

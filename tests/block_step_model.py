@@ -1,4 +1,4 @@
-"""numpy model of the raw-basis Arnoldi step that takes s = 1..4 iterations per pass over the basis (csrc/k_blas.hip:
+"""numpy model of the raw-basis Arnoldi step that takes s = 1..4 iterations per pass over the basis (csrc/k_cgs_block.hip:
 block_first_kernel, cgs_fixup_block_kernel, block_second_kernel; host/gmres.c: gmres_block) and of a whole blocked GMRES on a
 dense operator.  Test infrastructure only; two_step_model.py is the s = 2 case written out.
 

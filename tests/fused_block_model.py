@@ -1,4 +1,4 @@
-"""numpy model of the blocked raw-basis Arnoldi step whose update and fix-up are one pass (csrc/k_blas.hip: block_gram_kernel,
+"""numpy model of the blocked raw-basis Arnoldi step whose update and fix-up are one pass (csrc/k_cgs_block.hip: block_gram_kernel,
 cgs_update_fixup_block_kernel, block_fused_kernel; host/gmres.c: gmres_block with GmresPlan.fuse_fixup).  Test infrastructure
 only; block_step_model.py is the scheme with the two passes, and everything the two share is imported from it.
 

@@ -1,5 +1,5 @@
-"""numpy model of the Krylov kernels of dedflow_amd/csrc/k_blas.hip: one function per launcher, with the launcher's
-argument meaning, on host arrays.  Test infrastructure only: no GPU, no import of the library.
+"""numpy model of the Krylov kernels of dedflow_amd/csrc (k_blas.hip, k_cgs.hip, k_cgs_block.hip): one function per
+launcher, with the launcher's argument meaning, on host arrays.  Test infrastructure only: no GPU, no import of the library.
 
 Matrices are flat column-major arrays with a leading dimension, as the launchers take them: column j of the basis is
 Q[j * ldq : j * ldq + n], column j of the Hessenberg matrix is H[j * ldh : ...].  In-place arguments are modified in

@@ -1,4 +1,5 @@
-"""Every Krylov kernel of dedflow_amd/csrc/k_blas.hip alone, through its C launcher, against tests/krylov_model.py.
+"""Every Krylov kernel of dedflow_amd/csrc (k_blas.hip, k_cgs.hip, k_cgs_block.hip) alone, through its C launcher, against
+tests/krylov_model.py.
 
 Tier A (exact): inputs are small integers stored as float64 (generators of krylov_model.py; test_krylov_model_cpu.py
 shows that every product and partial sum stays an integer below 2**53 in any order), so the expectation is BITWISE

@@ -1,5 +1,6 @@
-"""numpy model of the scalar recurrences of the paired raw-basis Arnoldi step (csrc/k_blas.hip: givens_step_block,
-pair_first_kernel, pair_second_kernel) and of a whole paired GMRES on a dense operator.  Test infrastructure only.
+"""numpy model of the scalar recurrences of the paired raw-basis Arnoldi step (csrc/cgs_device.hpp:
+givens_step_block; csrc/k_cgs_block.hip: pair_first_kernel, pair_second_kernel) and of a whole paired GMRES on a dense operator.
+Test infrastructure only.
 
 A pair advances iterations k and k+1 with one pass over the basis: p1 = B v_k, p2 = B p1; the raw dots of both against
 r_0..r_k, the two-vector update, the one-column fix-up q = p2' - c p1'.  H is column-major with leading dimension ldh;
