@@ -21,7 +21,6 @@
 namespace {
 
 constexpr int BLK = 256;
-constexpr int SCAN_CHUNK = 1024;  // cells per scan block
 
 using dfl_dem::cell_coord;
 
@@ -29,7 +28,7 @@ using dfl_dem::cell_coord;
 //   bin    cell of every particle; count[cell]++ (integer atomics: the COUNTS are deterministic, the returned ranks are
 //          not -- the segment sort below removes that freedom).  The grid is sized for a few particles per cell, so the
 //          atomics are nearly uncontended (a per-chunk counter bumped by every particle cost 18 us of serialised atomics)
-//   chunk  total of every 1024-cell chunk
+//   chunk  total of every 1024-cell chunk (this launch and the next are dfl_scan_counts, k_scan.hip)
 //   scan   cell_start = exclusive scan of count (every block adds up the chunk totals before it), count zeroed
 //   place  slot[cell_start[cell] + rank] = particle (arrival order)
 //   sort   every particle finds its place among the few members of its cell (number of members with a smaller id => the
@@ -46,66 +45,6 @@ __global__ __launch_bounds__(BLK) void dem_bin_kernel(I P, const T* __restrict__
     const int c = cx + ncell * (cy + ncell * cz);
     cell_of[i] = c;
     rank[i] = atomicAdd(&count[c], 1);
-}
-
-// cell_start[0 .. n] = exclusive scan of count[0 .. n) (cell_start[n] = total); block b owns cells [b*1024, (b+1)*1024)
-__global__ __launch_bounds__(BLK) void dem_scan_kernel(I n, I* __restrict__ count, const I* __restrict__ chunk_sum,
-                                                      I* __restrict__ cell_start) {
-    __shared__ int s_part[BLK];
-    __shared__ int s_base;
-    const int t = threadIdx.x, b = blockIdx.x;
-    int acc = 0;
-    for (int k = t; k < b; k += BLK) acc += chunk_sum[k];
-    s_part[t] = acc;
-    __syncthreads();
-    for (int off = BLK / 2; off > 0; off >>= 1) {
-        if (t < off) s_part[t] += s_part[t + off];
-        __syncthreads();
-    }
-    if (t == 0) s_base = s_part[0];
-    __syncthreads();
-    const int base = s_base;
-    __syncthreads();
-    // 4 consecutive cells per thread
-    const long long c0 = (long long)b * SCAN_CHUNK + 4 * t;
-    int v[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        v[k] = (c0 + k < n) ? count[c0 + k] : 0;
-        if (c0 + k < n) count[c0 + k] = 0;  // ready for the next sweep
-    }
-    const int mine = v[0] + v[1] + v[2] + v[3];
-    s_part[t] = mine;
-    __syncthreads();
-    for (int off = 1; off < BLK; off <<= 1) {  // Hillis-Steele inclusive scan of the 256 thread sums
-        const int add = t >= off ? s_part[t - off] : 0;
-        __syncthreads();
-        s_part[t] += add;
-        __syncthreads();
-    }
-    int run = base + s_part[t] - mine;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (c0 + k <= n) cell_start[c0 + k] = run;
-        run += v[k];
-    }
-}
-
-// total of every 1024-cell chunk (large grids only: feeds dem_scan_kernel)
-__global__ __launch_bounds__(BLK) void dem_chunk_sum_kernel(I n, const I* __restrict__ count, I* __restrict__ chunk_sum) {
-    __shared__ int s_part[BLK];
-    const int t = threadIdx.x;
-    const long long c0 = (long long)blockIdx.x * SCAN_CHUNK + 4 * t;
-    int v = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v += (c0 + k < n) ? count[c0 + k] : 0;
-    s_part[t] = v;
-    __syncthreads();
-    for (int off = BLK / 2; off > 0; off >>= 1) {
-        if (t < off) s_part[t] += s_part[t + off];
-        __syncthreads();
-    }
-    if (t == 0) chunk_sum[blockIdx.x] = s_part[0];
 }
 
 __global__ __launch_bounds__(BLK) void dem_place_kernel(I P, const I* __restrict__ cell_of, const I* __restrict__ rank,
@@ -224,16 +163,12 @@ __global__ void dem_spin_kernel(I n3, T dt, T* __restrict__ omega, const T* __re
 
 extern "C" {
 
-I dfl_dem_num_chunks(I ncell3) { return (I)(((long long)ncell3 + 1 + SCAN_CHUNK - 1) / SCAN_CHUNK); }
-
-// count[ncell3 + 1] must be zero on entry (it is again on return); chunk_sum[dfl_dem_num_chunks] and slot[P] are scratch
+// count[ncell3 + 1] must be zero on entry (it is again on return); chunk_sum[dfl_scan_num_chunks] and slot[P] are scratch
 // chunk / scan / place / sort after a bin pass that left cell_of, rank and count[nbin] (the wall sweep, k_walls.hip, bins
 // with its own kernel)
 void dfl_dem_sort_binned(I P, I nbin, const T* coord, const T* vel, const T* omega, const T* radius, I* cell_of, I* rank, I* count,
                          I* chunk_sum, I* cell_start, I* slot, I* order, T* sorted, T* sorted_w, T* sorted_r, void* stream) {
-    const I nchunk = dfl_dem_num_chunks(nbin);
-    dem_chunk_sum_kernel<<<nchunk, BLK, 0, S(stream)>>>(nbin, count, chunk_sum);
-    dem_scan_kernel<<<nchunk, BLK, 0, S(stream)>>>(nbin, count, chunk_sum, cell_start);
+    dfl_scan_counts(nbin, count, chunk_sum, cell_start, stream);
     dem_place_kernel<<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, cell_of, rank, cell_start, slot);
     dem_sort_cells_kernel<<<ceil_div(P, BLK), BLK, 0, S(stream)>>>(P, cell_of, cell_start, slot, order, coord, vel, omega, radius,
                                                                  sorted, sorted_w, sorted_r);

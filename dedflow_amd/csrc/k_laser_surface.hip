@@ -4,11 +4,11 @@
 //
 // Snapshot (ParticleContextLaserSurfaceUpdate), O(tets):
 //   ls_count_kernel   one thread per tet: the facets of the tet that are candidates (the beam enters the metal there:
-//                     side (g . dir) > 0, |g| > 0, nine finite coordinates), summed per workgroup.  The workgroup counts
-//                     go through dfl_redistance_scan: the list is in ascending tet order, a quad's first triangle first.
-//                     Stable by construction: no atomic decides a position
-//   ls_emit_kernel    one thread per tet again, the same decision from the same numbers: facet index = blk_base[b] + the
-//                     exclusive scan inside the workgroup.  Writes the 9 doubles, the tet, the edge (i, j) and t of every
+//                     side (g . dir) > 0, |g| > 0, nine finite coordinates), summed per workgroup (block_count_256 of
+//                     block_ops.hpp).  The workgroup counts go through dfl_scan_counts (k_scan.hip): the list is in
+//                     ascending tet order, a quad's first triangle first.  Stable by construction: no atomic decides a position
+//   ls_emit_kernel    one thread per tet again, the same decision from the same numbers: facet index = blk_base[b] +
+//                     block_scan_incl_256 inside the workgroup.  Writes the 9 doubles, the tet, the edge (i, j) and t of every
 //                     vertex, and the facet as a dfl_wall_tri record (id = -2 - tet) behind the boundary records of the
 //                     laser's candidate list, so that laser_hit_kernel / laser_column_kernel see one list
 //   ls_node_*         the distinct nodes of the candidate facets' tets: the (node, 4 facet + local node) pairs sorted by
@@ -24,6 +24,7 @@
 //                     owns the slot.  No floating-point atomics; the order is fixed => bitwise reproducible
 //   ls_source_add / ls_power / ls_carry   q[node] += energy / time; the dense scatter of power; and pending energy moved to
 //                     a dense array when a new snapshot replaces the node list it was keyed by
+#include "block_ops.hpp"
 #include "laser_geom.hpp"
 #include "level_facets.hpp"
 #include <cstring>
@@ -48,17 +49,10 @@ struct Dir3 {
 __device__ __forceinline__ int ls_tet_candidates(const int4 n4, const T* __restrict__ xg, const T* __restrict__ phi_g, double level,
                                                   double side, const Dir3& dir, double* F, int* ij, double* tt) {
     double phi[4], f[4];
-    phi[0] = phi_g[n4.x]; phi[1] = phi_g[n4.y]; phi[2] = phi_g[n4.z]; phi[3] = phi_g[n4.w];
-#pragma unroll
-    for (int a = 0; a < 4; ++a) f[a] = phi[a] - level;
-    const int mask = lf_positive_mask(f);
+    const int mask = lf_levels(n4, phi_g, level, phi, f);
     if (!lf_facet_count(mask)) return 0;
-    const long long n[4] = {n4.x, n4.y, n4.z, n4.w};
     double x[12];
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-#pragma unroll
-        for (int d = 0; d < 3; ++d) x[b * 3 + d] = xg[n[b] * 3 + d];
+    lf_gather_tet(n4, xg, x);
     TetCross c;
     tet_cross(x, c);
     double g[3], gn, dd[4];
@@ -89,11 +83,9 @@ __global__ __launch_bounds__(BLK) void ls_count_kernel(I NT, const I* __restrict
         int ij[2];
         cnt = __popc(ls_tet_candidates(reinterpret_cast<const int4*>(ien)[e], xg, w + 4LL * N, level, side, dir, F, ij, tt));
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, WAVE);
-    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = cnt;
+    block_count_256(cnt, s_cnt);
     __syncthreads();
-    if (threadIdx.x == 0) blk_count[blockIdx.x] = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+    if (threadIdx.x == 0) blk_count[blockIdx.x] = block_count_read(s_cnt);
 }
 
 __global__ __launch_bounds__(BLK) void ls_emit_kernel(I NT, const I* __restrict__ ien, const T* __restrict__ xg,
@@ -108,16 +100,9 @@ __global__ __launch_bounds__(BLK) void ls_emit_kernel(I NT, const I* __restrict_
     int ij[2] = {0, 0}, keep = 0;
     if (e < NT) keep = ls_tet_candidates(reinterpret_cast<const int4*>(ien)[e], xg, w + 4LL * N, level, side, dir, F, ij, tt);
     const int cnt = __popc(keep);
-    s_scan[t] = cnt;
-    __syncthreads();
-    for (int off = 1; off < BLK; off <<= 1) {
-        const int add = t >= off ? s_scan[t - off] : 0;
-        __syncthreads();
-        s_scan[t] += add;
-        __syncthreads();
-    }
+    const int incl = block_scan_incl_256(cnt, s_scan);
     if (!cnt) return;  // (after the last barrier)
-    long long id = (long long)blk_base[blockIdx.x] + (s_scan[t] - cnt);
+    long long id = (long long)blk_base[blockIdx.x] + (incl - cnt);
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
         if (!((keep >> k) & 1)) continue;
@@ -300,7 +285,7 @@ void dfl_laser_surface_nodes(I nfs, const I* ien, const I* tet, uint32_t* key, u
     DFL_GUARD(rocprim::radix_sort_pairs(temp, bytes, key, key_out, rec, rec_out, (size_t)n, 0, 32, S(stream)));
     ls_node_head_kernel<<<ceil_div(n, BLK), BLK, 0, S(stream)>>>(n, key_out, flag);
     DFL_LAUNCH_CHECK();
-    dfl_redistance_scan(n, flag, chunk_sum, start, stream);
+    dfl_scan_counts(n, flag, chunk_sum, start, stream);
     ls_node_slot_kernel<<<ceil_div(n, BLK), BLK, 0, S(stream)>>>(n, key_out, rec_out, start, fslot, unode);
     DFL_LAUNCH_CHECK();
 }

@@ -13,7 +13,7 @@
 //   phase_apply_F / _J / _JT   one thread per node: F += D u and H dT; fact2 D on the (d, d) entries of the node's diagonal
 //                       4x4 block, kALPHAM H on the diagonal of the scalar T Jacobian (the diagonal by binary search in the
 //                       ascending col_ind row).  Products are rounded before the add.
-//   phase_stats_*       two-stage fixed-order reduction over the nodes (the scheme of k_blas.hip's reduce_stage1 / 2).
+//   phase_stats_*       two-stage fixed-order reduction over the nodes: block_tree_256, then block_reduce_kernel (block_ops.hpp).
 //
 // The skip rules decide what is evaluated, so both kernels must take the same decision from the same numbers: the whole
 // file is compiled without fused multiply-add (as the geometry of tet_levelset.hpp is wherever it is included), and
@@ -22,15 +22,15 @@
 // HBM view per coefficient call: V2E (4 B x (N + 4T)) + 8 B x N per output written; per (node, tet) pair 16 B of ien, 32 B
 // of T and 96 B of coordinates (with use_phi 32 B of phi more) gathered through L2; the flag pass gathers the same once per
 // tet, writes T bytes and the node pass reads 4T of them back.
+#include "block_ops.hpp"
 #include "node_gather.hpp"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int PH_BLK = 256;  // the one-thread-per-node and reduction kernels
+constexpr int PH_BLK = BLOCK_OPS_BLK;  // the one-thread-per-node and reduction kernels
 constexpr int PH_NSTAT = 9;            // liquid volume, T_max, molten count, lo[3], hi[3]
-constexpr int PH_MAX_PART = 1024;
 
 struct TetPhase {
     double det;
@@ -218,52 +218,24 @@ __global__ __launch_bounds__(PH_BLK) void phase_apply_diag_kernel(I N, const I* 
     }
 }
 
-struct Stat {
+// the nine statistics: sums (liquid volume, molten count), maxima (T_max, hi) and minima (lo); a + b in this order, fmax /
+// fmin drop a NaN
+struct MergeStat {
+    __device__ __forceinline__ static bool is_sum(int j) { return j == 0 || j == 2; }
+    __device__ __forceinline__ static bool is_max(int j) { return j == 1 || j >= 6; }
+    __device__ __forceinline__ double operator()(int j, double a, double b) const {
+        return is_sum(j) ? a + b : is_max(j) ? fmax(a, b) : fmin(a, b);
+    }
+    __device__ __forceinline__ double identity(int j) const { return is_sum(j) ? 0.0 : is_max(j) ? -HUGE_VAL : HUGE_VAL; }
+};
+
+struct Stat {  // (a struct: with bare arrays phase_stats_stage1 takes 80 VGPRs, not 46, and loses two waves of occupancy)
     double v[PH_NSTAT];
 };
 __device__ __forceinline__ Stat stat_identity() {
     Stat s;
-    s.v[0] = 0.0;
-    s.v[1] = -HUGE_VAL;
-    s.v[2] = 0.0;
 #pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        s.v[3 + d] = HUGE_VAL;
-        s.v[6 + d] = -HUGE_VAL;
-    }
-    return s;
-}
-__device__ __forceinline__ void stat_merge(Stat& a, const Stat& b) {  // sums a + b in this order, fmax / fmin drop a NaN
-    a.v[0] = a.v[0] + b.v[0];
-    a.v[1] = fmax(a.v[1], b.v[1]);
-    a.v[2] = a.v[2] + b.v[2];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        a.v[3 + d] = fmin(a.v[3 + d], b.v[3 + d]);
-        a.v[6 + d] = fmax(a.v[6 + d], b.v[6 + d]);
-    }
-}
-// fixed tree over the 256 threads of a block: xor shuffles in the wave, then the four waves in order; valid in thread 0
-__device__ __forceinline__ Stat stat_block(Stat s, double (*lds)[PH_NSTAT]) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        Stat o;
-#pragma unroll
-        for (int k = 0; k < PH_NSTAT; ++k) o.v[k] = __shfl_xor(s.v[k], off, WAVE);
-        stat_merge(s, o);
-    }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < PH_NSTAT; ++k) lds[wv][k] = s.v[k];
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int i = 1; i < 4; ++i) {
-            Stat o;
-#pragma unroll
-            for (int k = 0; k < PH_NSTAT; ++k) o.v[k] = lds[i][k];
-            stat_merge(s, o);
-        }
+    for (int k = 0; k < PH_NSTAT; ++k) s.v[k] = MergeStat().identity(k);
     return s;
 }
 
@@ -271,6 +243,7 @@ __global__ __launch_bounds__(PH_BLK) void phase_stats_stage1(I N, const T* __res
                                                               const T* __restrict__ G, const dfl_phase_params p,
                                                               T* __restrict__ part) {
     __shared__ double lds[4][PH_NSTAT];
+    const MergeStat merge;
     Stat s = stat_identity();
     const long long stride = (long long)gridDim.x * PH_BLK;
     for (long long a = (long long)blockIdx.x * PH_BLK + threadIdx.x; a < N; a += stride) {
@@ -286,27 +259,13 @@ __global__ __launch_bounds__(PH_BLK) void phase_stats_stage1(I N, const T* __res
 #pragma unroll
             for (int d = 0; d < 3; ++d) o.v[3 + d] = o.v[6 + d] = xg[3 * a + d];
         }
-        stat_merge(s, o);
+#pragma unroll
+        for (int k = 0; k < PH_NSTAT; ++k) s.v[k] = merge(k, s.v[k], o.v[k]);
     }
-    s = stat_block(s, lds);
+    block_tree_256<PH_NSTAT>(s.v, merge, lds);
     if (threadIdx.x == 0)
 #pragma unroll
         for (int k = 0; k < PH_NSTAT; ++k) part[(long long)blockIdx.x * PH_NSTAT + k] = s.v[k];
-}
-
-__global__ __launch_bounds__(PH_BLK) void phase_stats_stage2(int npart, const T* __restrict__ part, T* __restrict__ out) {
-    __shared__ double lds[4][PH_NSTAT];
-    Stat s = stat_identity();
-    for (int i = threadIdx.x; i < npart; i += PH_BLK) {
-        Stat o;
-#pragma unroll
-        for (int k = 0; k < PH_NSTAT; ++k) o.v[k] = part[(long long)i * PH_NSTAT + k];
-        stat_merge(s, o);
-    }
-    s = stat_block(s, lds);
-    if (threadIdx.x == 0)
-#pragma unroll
-        for (int k = 0; k < PH_NSTAT; ++k) out[k] = s.v[k];
 }
 
 }  // namespace
@@ -348,14 +307,13 @@ void dfl_phase_apply_JT(I N, const I* row_ptr, const I* col_ind, const T* H, T a
     DFL_LAUNCH_CHECK();
 }
 
-I dfl_phase_stats_work_size(void) { return PH_MAX_PART * PH_NSTAT; }
+I dfl_phase_stats_work_size(void) { return NODE_REDUCE_MAX_PART * PH_NSTAT; }
 
 void dfl_phase_stats(I N, const T* xg, const T* w, const T* G, const dfl_phase_params* prm, T* work, T* out9, void* stream) {
     if (N <= 0) return;
-    int g = ceil_div(N, PH_BLK * 8);
-    if (g > PH_MAX_PART) g = PH_MAX_PART;
+    const int g = node_reduce_grid(N);
     phase_stats_stage1<<<g, PH_BLK, 0, S(stream)>>>(N, xg, w, G, *prm, work);
-    phase_stats_stage2<<<1, PH_BLK, 0, S(stream)>>>(g, work, out9);
+    block_reduce<PH_NSTAT>(g, work, out9, MergeStat(), stream);
     DFL_LAUNCH_CHECK();
 }
 

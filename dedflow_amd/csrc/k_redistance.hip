@@ -2,12 +2,12 @@
 // band (build-defined; model in include/dedflow.h, "level-set redistancing"; geometry in level_facets.hpp).
 //
 //   rd_cut_kernel        one thread per tet.  The volume of {phi > level} in the tet and, for a cut tet, ||g| - 1| go through a
-//                        fixed tree to one (sum, max) pair per workgroup.  COUNT: also the number of facets of the workgroup
-//                        (level 1 of the scan that makes the facet index the ascending-tet order) and, per facet, count[c]++
-//                        for every cell its bounding box overlaps.  Only a tet with a positive node gathers coordinates.
-//   rd_chunk_sum / rd_scan   the exclusive scan of the DEM cell sort (k_dem.hip): 1024 entries per workgroup, every workgroup
-//                        adds up the chunk totals before it.  Used for the workgroup facet counts and for the cells.
-//   rd_emit_kernel       one thread per tet again: facet index = blk_base[b] + the exclusive scan inside the workgroup;
+//                        fixed tree (block_tree_256 of block_ops.hpp) to one (sum, max) pair per workgroup.  COUNT: also the
+//                        number of facets of the workgroup (block_count_256; level 1 of the scan that makes the facet index
+//                        the ascending-tet order) and, per facet, count[c]++ for every cell its bounding box overlaps.  Only a
+//                        tet with a positive node gathers coordinates.  The host scans the workgroup counts and the cells
+//                        with dfl_scan_counts (k_scan.hip).
+//   rd_emit_kernel       one thread per tet again: facet index = blk_base[b] + block_scan_incl_256 inside the workgroup;
 //                        writes the 9 doubles and enters the index into its cells (integer atomic on the cell's fill count:
 //                        the order inside a cell is free because the result is a minimum).
 //   rd_node_count_kernel one thread per node: the entries of the 27 cells around it as nine three-cell runs of cell_start.
@@ -16,20 +16,19 @@
 //   rd_node_dist_kernel  16 lanes per compacted node (the NG_LANES idiom of node_gather.hpp), the groups stride the list.  The
 //                        lanes stride the entries of a run, each keeps a running minimum of d^2; four xor-shuffles; lane 0
 //                        writes.  The trip counts are uniform inside a group, so the shuffles only ever meet active lanes.
-//   rd_node_stats / rd_reduce   two-stage fixed-order (sum, max) reductions (the scheme of k_phase.hip's statistics).
+//   rd_node_stats, then block_reduce_kernel   two-stage fixed-order (sum, max) reductions.
 //
 // No float atomics anywhere.  The same facet may sit in several of a node's 27 cells: it is evaluated again, which a
 // minimum does not see.  The file is compiled without fused multiply-add, as level_facets.hpp is wherever it is included.
+#include "block_ops.hpp"
 #include "level_facets.hpp"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int RD_BLK = 256;
-constexpr int RD_CHUNK = 1024;     // entries per scan workgroup
+constexpr int RD_BLK = BLOCK_OPS_BLK;
 constexpr int RD_LANES = 16;       // lanes per compacted node
-constexpr int RD_MAX_PART = 1024;  // partial pairs of a node reduction
 constexpr int RD_MAX_GROUP_BLOCKS = 2048;
 
 typedef dfl_redistance_grid Grid;
@@ -68,51 +67,11 @@ __device__ __forceinline__ bool rd_facet_cells(const double* F, const Grid& g, i
     return true;
 }
 
-__device__ __forceinline__ void rd_gather(const int4 n4, const T* __restrict__ xg, double* x) {
-    const long long n[4] = {n4.x, n4.y, n4.z, n4.w};
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-#pragma unroll
-        for (int d = 0; d < 3; ++d) x[b * 3 + d] = xg[n[b] * 3 + d];
-}
-
-// phi of the tet's nodes and f = phi - level; returns the mask of the positive nodes
-__device__ __forceinline__ int rd_levels(const int4 n4, const T* __restrict__ phi_g, double level, double* phi, double* f) {
-    phi[0] = phi_g[n4.x]; phi[1] = phi_g[n4.y]; phi[2] = phi_g[n4.z]; phi[3] = phi_g[n4.w];
-#pragma unroll
-    for (int a = 0; a < 4; ++a) f[a] = phi[a] - level;
-    return lf_positive_mask(f);
-}
-
-struct Pair {
-    double s, m;  // a sum and a maximum (of values >= 0; fmax passes over a NaN)
+// a sum and a maximum (of values >= 0; fmax passes over a NaN)
+struct MergePair {
+    __device__ __forceinline__ double operator()(int j, double a, double b) const { return j == 0 ? a + b : fmax(a, b); }
+    __device__ __forceinline__ double identity(int) const { return 0.0; }
 };
-__device__ __forceinline__ void pair_merge(Pair& a, const Pair& b) {
-    a.s = a.s + b.s;
-    a.m = fmax(a.m, b.m);
-}
-// fixed tree over the 256 threads of a workgroup: xor shuffles in the wave, then the four waves in order; valid in thread 0
-__device__ __forceinline__ Pair pair_block(Pair p, double (*lds)[2]) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        Pair o;
-        o.s = __shfl_xor(p.s, off, WAVE);
-        o.m = __shfl_xor(p.m, off, WAVE);
-        pair_merge(p, o);
-    }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) {
-        lds[wv][0] = p.s;
-        lds[wv][1] = p.m;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int i = 1; i < 4; ++i) {
-            Pair o = {lds[i][0], lds[i][1]};
-            pair_merge(p, o);
-        }
-    return p;
-}
 
 template <bool COUNT>
 __global__ __launch_bounds__(RD_BLK) void rd_cut_kernel(I NT, const I* __restrict__ ien, const T* __restrict__ xg,
@@ -122,23 +81,23 @@ __global__ __launch_bounds__(RD_BLK) void rd_cut_kernel(I NT, const I* __restric
     __shared__ double lds[4][2];
     __shared__ int s_cnt[4];
     const long long e = (long long)blockIdx.x * RD_BLK + threadIdx.x;
-    Pair p = {0.0, 0.0};
+    double p[2] = {0.0, 0.0};  // volume, | |g| - 1 |
     int nf = 0;
     if (e < NT) {
         const int4 n4 = reinterpret_cast<const int4*>(ien)[e];
         double phi[4], f[4];
-        const int mask = rd_levels(n4, w + 4LL * N, level, phi, f);
+        const int mask = lf_levels(n4, w + 4LL * N, level, phi, f);
         if (mask) {
             double x[12];
-            rd_gather(n4, xg, x);
+            lf_gather_tet(n4, xg, x);
             TetCross c;
             tet_cross(x, c);
             const double vol = lf_positive_volume(x, f, mask, c.det);
-            p.s = vol == vol ? vol : 0.0;  // a NaN phi at a node of a cut tet: the tet adds nothing
+            p[0] = vol == vol ? vol : 0.0;  // a NaN phi at a node of a cut tet: the tet adds nothing
             if (mask != 15) {
                 double gr[3], gn, dd[4];
                 tet_levelset(c, phi, level, gr, gn, dd);
-                p.m = fabs(gn - 1.0);
+                p[1] = fabs(gn - 1.0);
                 if (COUNT) {
                     double F[18];
                     nf = lf_tet_facets(x, f, mask, F);
@@ -154,76 +113,12 @@ __global__ __launch_bounds__(RD_BLK) void rd_cut_kernel(I NT, const I* __restric
             }
         }
     }
-    if (COUNT) {
-        int cnt = nf;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, WAVE);
-        if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = cnt;
-    }
-    p = pair_block(p, lds);  // (its barrier also publishes s_cnt)
+    if (COUNT) block_count_256(nf, s_cnt);
+    block_tree_256<2>(p, MergePair(), lds);  // (its barrier also publishes s_cnt)
     if (threadIdx.x == 0) {
-        part[2LL * blockIdx.x] = p.s;
-        part[2LL * blockIdx.x + 1] = p.m;
-        if (COUNT) blk_count[blockIdx.x] = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
-    }
-}
-
-// total of every 1024-entry chunk
-__global__ __launch_bounds__(RD_BLK) void rd_chunk_sum_kernel(I n, const I* __restrict__ count, I* __restrict__ chunk_sum) {
-    __shared__ int s_part[RD_BLK];
-    const int t = threadIdx.x;
-    const long long c0 = (long long)blockIdx.x * RD_CHUNK + 4 * t;
-    int v = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v += (c0 + k < n) ? count[c0 + k] : 0;
-    s_part[t] = v;
-    __syncthreads();
-    for (int off = RD_BLK / 2; off > 0; off >>= 1) {
-        if (t < off) s_part[t] += s_part[t + off];
-        __syncthreads();
-    }
-    if (t == 0) chunk_sum[blockIdx.x] = s_part[0];
-}
-
-// start[0 .. n] = exclusive scan of count[0 .. n) (start[n] = total), count zeroed; workgroup b owns [b * 1024, (b + 1) * 1024)
-__global__ __launch_bounds__(RD_BLK) void rd_scan_kernel(I n, I* __restrict__ count, const I* __restrict__ chunk_sum,
-                                                          I* __restrict__ start) {
-    __shared__ int s_part[RD_BLK];
-    __shared__ int s_base;
-    const int t = threadIdx.x, b = blockIdx.x;
-    int acc = 0;
-    for (int k = t; k < b; k += RD_BLK) acc += chunk_sum[k];
-    s_part[t] = acc;
-    __syncthreads();
-    for (int off = RD_BLK / 2; off > 0; off >>= 1) {
-        if (t < off) s_part[t] += s_part[t + off];
-        __syncthreads();
-    }
-    if (t == 0) s_base = s_part[0];
-    __syncthreads();
-    const int base = s_base;
-    __syncthreads();
-    const long long c0 = (long long)b * RD_CHUNK + 4 * t;
-    int v[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        v[k] = (c0 + k < n) ? count[c0 + k] : 0;
-        if (c0 + k < n) count[c0 + k] = 0;
-    }
-    const int mine = (v[0] + v[1]) + (v[2] + v[3]);
-    s_part[t] = mine;
-    __syncthreads();
-    for (int off = 1; off < RD_BLK; off <<= 1) {  // Hillis-Steele inclusive scan of the 256 thread sums
-        const int add = t >= off ? s_part[t - off] : 0;
-        __syncthreads();
-        s_part[t] += add;
-        __syncthreads();
-    }
-    int run = base + s_part[t] - mine;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (c0 + k <= n) start[c0 + k] = run;
-        run += v[k];
+        part[2LL * blockIdx.x] = p[0];
+        part[2LL * blockIdx.x + 1] = p[1];
+        if (COUNT) blk_count[blockIdx.x] = block_count_read(s_cnt);
     }
 }
 
@@ -240,21 +135,14 @@ __global__ __launch_bounds__(RD_BLK) void rd_emit_kernel(I NT, const I* __restri
     int mask = 0;
     if (e < NT) {
         n4 = reinterpret_cast<const int4*>(ien)[e];
-        mask = rd_levels(n4, w + 4LL * N, level, phi, f);
+        mask = lf_levels(n4, w + 4LL * N, level, phi, f);
     }
     const int nf = lf_facet_count(mask);
-    s_scan[t] = nf;
-    __syncthreads();
-    for (int off = 1; off < RD_BLK; off <<= 1) {
-        const int add = t >= off ? s_scan[t - off] : 0;
-        __syncthreads();
-        s_scan[t] += add;
-        __syncthreads();
-    }
+    const int incl = block_scan_incl_256(nf, s_scan);
     if (!nf) return;  // (after the last barrier)
-    const long long first = (long long)blk_base[blockIdx.x] + (s_scan[t] - nf);
+    const long long first = (long long)blk_base[blockIdx.x] + (incl - nf);
     double x[12], F[18];
-    rd_gather(n4, xg, x);
+    lf_gather_tet(n4, xg, x);
     lf_tet_facets(x, f, mask, F);
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
@@ -380,41 +268,26 @@ __global__ __launch_bounds__(RD_BLK) void rd_node_dist_kernel(I N, const T* __re
 
 __global__ __launch_bounds__(RD_BLK) void rd_node_stats_kernel(I N, const T* __restrict__ chg, T* __restrict__ part) {
     __shared__ double lds[4][2];
-    Pair p = {0.0, 0.0};
+    const MergePair merge;
+    double p[2] = {0.0, 0.0};  // band nodes, largest change
     const long long stride = (long long)gridDim.x * RD_BLK;
     for (long long a = (long long)blockIdx.x * RD_BLK + threadIdx.x; a < N; a += stride) {
         const double c = chg[a];
         if (c >= 0.0) {
-            const Pair o = {1.0, c};
-            pair_merge(p, o);
+            p[0] = merge(0, p[0], 1.0);
+            p[1] = merge(1, p[1], c);
         }
     }
-    p = pair_block(p, lds);
+    block_tree_256<2>(p, merge, lds);
     if (threadIdx.x == 0) {
-        part[2LL * blockIdx.x] = p.s;
-        part[2LL * blockIdx.x + 1] = p.m;
-    }
-}
-
-__global__ __launch_bounds__(RD_BLK) void rd_reduce_kernel(I npart, const T* __restrict__ part, T* __restrict__ out2) {
-    __shared__ double lds[4][2];
-    Pair p = {0.0, 0.0};
-    for (long long i = threadIdx.x; i < npart; i += RD_BLK) {
-        const Pair o = {part[2 * i], part[2 * i + 1]};
-        pair_merge(p, o);
-    }
-    p = pair_block(p, lds);
-    if (threadIdx.x == 0) {
-        out2[0] = p.s;
-        out2[1] = p.m;
+        part[2LL * blockIdx.x] = p[0];
+        part[2LL * blockIdx.x + 1] = p[1];
     }
 }
 
 }  // namespace
 
 extern "C" {
-
-I dfl_redistance_tets_per_block(void) { return RD_BLK; }
 
 void dfl_redistance_cut(I NT, const I* ien, const T* xg, const T* w, I N, T level, const dfl_redistance_grid* grid, I* blk_count,
                         I* cell_count, T* part, void* stream) {
@@ -426,14 +299,6 @@ void dfl_redistance_cut(I NT, const I* ien, const T* xg, const T* w, I N, T leve
         rd_cut_kernel<false><<<ceil_div(NT, RD_BLK), RD_BLK, 0, S(stream)>>>(NT, ien, xg, w, N, level, grid ? *grid : none, nullptr,
                                                                             nullptr, part);
     }
-    DFL_LAUNCH_CHECK();
-}
-
-void dfl_redistance_scan(I n, I* count, I* chunk_sum, I* start, void* stream) {
-    if (n < 0) return;
-    const int nchunk = ceil_div((long long)n + 1, RD_CHUNK);
-    rd_chunk_sum_kernel<<<nchunk, RD_BLK, 0, S(stream)>>>(n, count, chunk_sum);
-    rd_scan_kernel<<<nchunk, RD_BLK, 0, S(stream)>>>(n, count, chunk_sum, start);
     DFL_LAUNCH_CHECK();
 }
 
@@ -460,16 +325,15 @@ void dfl_redistance_nodes(I N, const T* xg, T* w, T level, T band, const dfl_red
 
 void dfl_redistance_node_stats(I N, const T* chg, T* work, T* out2, void* stream) {
     if (N <= 0) return;
-    int g = ceil_div(N, RD_BLK * 8);
-    if (g > RD_MAX_PART) g = RD_MAX_PART;
+    const int g = node_reduce_grid(N);
     rd_node_stats_kernel<<<g, RD_BLK, 0, S(stream)>>>(N, chg, work);
-    rd_reduce_kernel<<<1, RD_BLK, 0, S(stream)>>>(g, work, out2);
+    block_reduce<2>(g, work, out2, MergePair(), stream);
     DFL_LAUNCH_CHECK();
 }
 
 void dfl_redistance_reduce(I npart, const T* part, T* out2, void* stream) {
     if (npart <= 0) return;
-    rd_reduce_kernel<<<1, RD_BLK, 0, S(stream)>>>(npart, part, out2);
+    block_reduce<2>(npart, part, out2, MergePair(), stream);
     DFL_LAUNCH_CHECK();
 }
 

@@ -39,6 +39,22 @@ __device__ __forceinline__ int lf_facet_count(int mask) {
     return np == 0 || np == 4 ? 0 : np == 2 ? 2 : 1;
 }
 
+// the coordinates of the tet's nodes: x[b * 3 + d] of local node b
+__device__ __forceinline__ void lf_gather_tet(const int4 n4, const double* __restrict__ xg, double* x) {
+    const long long n[4] = {n4.x, n4.y, n4.z, n4.w};
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+        for (int d = 0; d < 3; ++d) x[b * 3 + d] = xg[n[b] * 3 + d];
+}
+// phi of the tet's nodes and f = phi - level; returns the mask of the positive nodes
+__device__ __forceinline__ int lf_levels(const int4 n4, const double* __restrict__ phi_g, double level, double* phi, double* f) {
+    phi[0] = phi_g[n4.x]; phi[1] = phi_g[n4.y]; phi[2] = phi_g[n4.z]; phi[3] = phi_g[n4.w];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) f[a] = phi[a] - level;
+    return lf_positive_mask(f);
+}
+
 // P_ij = x_i + t (x_j - x_i), t = f_i / (f_i - f_j): the crossing point of edge (i positive, j not)
 __device__ __forceinline__ void lf_cross_point(const double* x, const double* f, int i, int j, double* P) {
 #pragma clang fp contract(off)

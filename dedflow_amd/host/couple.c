@@ -34,12 +34,8 @@ void DflCoupleFree(ParticleContext* ctx) {
  * cell order (deterministic) */
 static void build_seed_grid(CoupleState* c, const f64* xg, const index_type* ien) {
     const index_type N = c->N, T = c->T;
-    f64 lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
-    for (index_type a = 0; a < N; ++a)
-        for (int d = 0; d < 3; ++d) {
-            if (xg[3 * (size_t)a + d] < lo[d]) lo[d] = xg[3 * (size_t)a + d];
-            if (xg[3 * (size_t)a + d] > hi[d]) hi[d] = xg[3 * (size_t)a + d];
-        }
+    f64 lo[3], hi[3];
+    DflNodeBounds(xg, N, lo, hi);
     index_type g = (index_type)floor(cbrt((f64)T / 8.0));
     if (g < 1) g = 1;
     if (g > 128) g = 128;

@@ -103,6 +103,28 @@ void DflMeshSortedV2E(Mesh3D* mesh, const index_type** vrow, const index_type** 
 /* the [T] bytes of a per-tet flag pass, allocated or freed (after a synchronisation) to match `on` */
 void DflTetFlagsMatch(u8** flag, index_type T, b32 on);
 
+/* the host side of a "count per workgroup -> scan -> emit in ascending tet order" pass (redistancing, volume correction, the
+ * laser surface): the counts of the one-thread-per-tet kernels, their exclusive scan and the scan's scratch.  chunk_sum may
+ * serve other scans of the same owner (the redistancing cells, the laser surface's node heads) */
+typedef struct DflBlockScan {
+    index_type nblk;                  /* workgroups of the tet passes: ceil(T / dfl_tets_per_block()) */
+    index_type *count, *base;         /* device [nblk], [nblk + 1] */
+    index_type *chunk_sum, cap_chunk; /* device [cap_chunk] */
+} DflBlockScan;
+/* other_n: the largest other count that will be scanned through chunk_sum (0: none) */
+void DflBlockScanAlloc(DflBlockScan* bs, index_type T, index_type other_n);
+/* chunk_sum grows to serve a scan of n entries; the caller has synchronised */
+void DflBlockScanReserve(DflBlockScan* bs, index_type n);
+void DflBlockScanFree(DflBlockScan* bs);
+/* enqueues the scan of count into base and the copy of the total base[nblk] to *total; does not synchronise */
+void DflBlockScanEnqueue(const DflBlockScan* bs, index_type* total, hipStream_t s);
+/* the capacity a list grows to when it must hold n entries: n + n / 2, n itself where that overflows */
+index_type DflGrowCap(index_type n);
+/* the bounding box of N > 0 nodes from host coordinates xg [N][3] (a NaN coordinate is passed over), and that of the nodes
+ * the device holds (copies them to the host: the caller has synchronised) */
+void DflNodeBounds(const f64* xg, index_type N, f64 lo[3], f64 hi[3]);
+void DflMeshNodeBounds(Mesh3D* mesh, f64 lo[3], f64 hi[3]);
+
 void DflMeshPrepareFaces(Mesh3D* mesh, index_type group);
 void DflMeshPrepareFaceNonzeros(Mesh3D* mesh, index_type group, const CSRAttr* spy);
 void DflMeshFreeFaceLists(struct MeshExt* x);
@@ -257,10 +279,9 @@ typedef struct LaserState {
 typedef struct LaserSurface {
     DflLaserSurface cfg;
     Mesh3D* mesh;                    /* the coupled mesh the buffers are sized for */
-    index_type N, T, nblk;
+    index_type N, T;
     f64 vdmin, vdmax;                /* range of x . dir over the corners of the node bounding box */
-    index_type *blk_count, *blk_base, *chunk_sum; /* device [nblk], [nblk + 1], [cap_chunk] */
-    index_type cap_chunk;
+    DflBlockScan scan;               /* the facet counts of the tet passes; its chunk_sum also serves the 4 cap node heads */
     index_type nf;                   /* candidate facets of the snapshot, -1: no Update yet */
     index_type nfb;                  /* boundary records in front of them in cand */
     index_type cap, cap_cand;        /* facets the lists hold; records cand holds */

@@ -59,7 +59,7 @@ static void bin_buffers(LaserState* l, index_type cap) {
     HIPGUARD(hipMemsetAsync(l->rate, 0, (size_t)n * sizeof(f64), s));
     /* the bins: every column, then one per 2^DFL_LASER_OUTSIDE_SHIFT particle ids for the particles outside the grid */
     const index_type nbin = l->ncol + (index_type)((n - 1) >> DFL_LASER_OUTSIDE_SHIFT) + 1;
-    const index_type nchunk = dfl_dem_num_chunks(nbin);
+    const index_type nchunk = dfl_scan_num_chunks(nbin);
     l->count = (index_type*)CdamMallocDevice(((ptrdiff_t)nbin + 1) * SIZE_OF(index_type));
     l->cell_start = (index_type*)CdamMallocDevice(((ptrdiff_t)nbin + 1) * SIZE_OF(index_type));
     l->chunk_sum = (index_type*)CdamMallocDevice((ptrdiff_t)nchunk * SIZE_OF(index_type));

@@ -26,9 +26,9 @@ static void free_lists(LaserSurface* s) {
     CdamFreeDevice(s->facets, 0); CdamFreeDevice(s->ft, 0); CdamFreeDevice(s->ftet, 0); CdamFreeDevice(s->fij, 0);
     CdamFreeDevice(s->nkey, 0); CdamFreeDevice(s->nkey_out, 0); CdamFreeDevice(s->nrec, 0); CdamFreeDevice(s->nrec_out, 0);
     CdamFreeDevice(s->nflag, 0); CdamFreeDevice(s->nstart, 0); CdamFreeDevice(s->fslot, 0); CdamFreeDevice(s->unode, 0);
-    CdamFreeDevice(s->power, 0); CdamFreeDevice(s->energy, 0); CdamFreeDevice(s->chunk_sum, 0); CdamFreeDevice(s->temp, 0);
+    CdamFreeDevice(s->power, 0); CdamFreeDevice(s->energy, 0); CdamFreeDevice(s->temp, 0);
     s->facets = s->ft = s->power = s->energy = NULL;
-    s->ftet = s->fij = s->nrec = s->nrec_out = s->nflag = s->nstart = s->fslot = s->unode = s->chunk_sum = NULL;
+    s->ftet = s->fij = s->nrec = s->nrec_out = s->nflag = s->nstart = s->fslot = s->unode = NULL;
     s->nkey = s->nkey_out = NULL;
     s->temp = NULL;
     s->cap = 0;
@@ -36,8 +36,8 @@ static void free_lists(LaserSurface* s) {
 
 static void free_mesh_buffers(LaserSurface* s) {
     free_lists(s);
-    CdamFreeDevice(s->blk_count, 0); CdamFreeDevice(s->blk_base, 0); CdamFreeDevice(s->cand, 0); CdamFreeDevice(s->carry, 0);
-    s->blk_count = s->blk_base = NULL;
+    DflBlockScanFree(&s->scan);
+    CdamFreeDevice(s->cand, 0); CdamFreeDevice(s->carry, 0);
     s->cand = NULL;
     s->carry = NULL;
     s->cap_cand = 0;
@@ -45,10 +45,11 @@ static void free_mesh_buffers(LaserSurface* s) {
     s->nf = -1;
     s->nfb = 0;
     s->mesh = NULL;
-    s->N = s->T = s->nblk = 0;
+    s->N = s->T = 0;
 }
 
-/* the lists sized by the facet capacity (and the sort scratch, which also serves the 4 ncol deposit records) */
+/* the lists sized by the facet capacity (with the scan scratch of the 4 cap node heads and the sort scratch, which also
+ * serves the 4 ncol deposit records) */
 static void alloc_lists(LaserSurface* s, index_type cap, index_type ncol) {
     free_lists(s);
     const ptrdiff_t c = cap, c4 = 4 * (ptrdiff_t)cap;
@@ -67,9 +68,7 @@ static void alloc_lists(LaserSurface* s, index_type cap, index_type ncol) {
     s->unode = (index_type*)CdamMallocDevice(c4 * SIZE_OF(index_type));
     s->power = (f64*)CdamMallocDevice(c4 * SIZE_OF(f64));
     s->energy = (f64*)CdamMallocDevice(c4 * SIZE_OF(f64));
-    const ptrdiff_t most = c4 > s->nblk ? c4 : s->nblk;
-    s->cap_chunk = (index_type)(most / 1024 + 2);
-    s->chunk_sum = (index_type*)CdamMallocDevice((ptrdiff_t)s->cap_chunk * SIZE_OF(index_type));
+    DflBlockScanReserve(&s->scan, (index_type)c4);
     s->temp_bytes = dfl_laser_surface_temp_bytes((index_type)c4, 4 * ncol);
     s->temp = CdamMallocDevice((ptrdiff_t)s->temp_bytes);
 }
@@ -89,24 +88,11 @@ static void bind_mesh(ParticleContext* ctx, LaserState* l, LaserSurface* s) {
     s->mesh = mesh;
     s->N = N;
     s->T = T;
-    const index_type per = dfl_redistance_tets_per_block();
-    s->nblk = (T + per - 1) / per;
-    const ptrdiff_t nb = s->nblk > 0 ? s->nblk : 1;
-    s->blk_count = (index_type*)CdamMallocDevice(nb * SIZE_OF(index_type));
-    s->blk_base = (index_type*)CdamMallocDevice((nb + 1) * SIZE_OF(index_type));
+    DflBlockScanAlloc(&s->scan, T, 0);
     alloc_lists(s, LASER_SURFACE_FIRST_CAP, l->ncol);
     if (N > 0) {
-        f64* x = (f64*)CdamMallocHost((ptrdiff_t)N * 3 * SIZE_OF(f64));
         f64 lo[3], hi[3];
-        HIPGUARD(hipMemcpy(x, Mesh3DDevice(mesh)->xg, (size_t)N * 3 * sizeof(f64), D2H));
-        for (int d = 0; d < 3; ++d) lo[d] = hi[d] = x[d];
-        for (index_type a = 1; a < N; ++a)
-            for (int d = 0; d < 3; ++d) {
-                const f64 v = x[3 * (size_t)a + d];
-                if (v < lo[d]) lo[d] = v;
-                if (v > hi[d]) hi[d] = v;
-            }
-        CdamFreeHost(x, (ptrdiff_t)N * 3 * SIZE_OF(f64));
+        DflMeshNodeBounds(mesh, lo, hi);
         s->vdmin = HUGE_VAL;
         s->vdmax = -HUGE_VAL;
         for (int k = 0; k < 8; ++k) {
@@ -200,10 +186,9 @@ index_type ParticleContextLaserSurfaceUpdate(ParticleContext* ctx, const f64* w)
         return 0;
     }
     const Mesh3DData* dev = Mesh3DDevice(s->mesh);
-    dfl_laser_surface_count(s->T, dev->ien, dev->xg, w, s->N, s->cfg.level, s->cfg.side, l->dir, s->blk_count, st);
-    dfl_redistance_scan(s->nblk, s->blk_count, s->chunk_sum, s->blk_base, st);
+    dfl_laser_surface_count(s->T, dev->ien, dev->xg, w, s->N, s->cfg.level, s->cfg.side, l->dir, s->scan.count, st);
     index_type nf = 0;
-    HIPGUARD(hipMemcpyAsync(&nf, s->blk_base + s->nblk, sizeof nf, D2H, st));
+    DflBlockScanEnqueue(&s->scan, &nf, st);
     HIPGUARD(hipStreamSynchronize(st)); /* the one synchronisation: the count */
     if (nf <= 0) {
         DflRangePop();
@@ -215,16 +200,16 @@ index_type ParticleContextLaserSurfaceUpdate(ParticleContext* ctx, const f64* w)
         DflRangePop();
         return nf;
     }
-    if (nf > s->cap) alloc_lists(s, nf + nf / 2, l->ncol);
+    if (nf > s->cap) alloc_lists(s, DflGrowCap(nf), l->ncol);
     if (l->nf + nf > s->cap_cand) {
         CdamFreeDevice(s->cand, 0);
         s->cap_cand = l->nf + (nf > s->cap ? nf : s->cap);
         s->cand = (dfl_wall_tri*)CdamMallocDevice((ptrdiff_t)s->cap_cand * SIZE_OF(dfl_wall_tri));
     }
     if (l->nf > 0) HIPGUARD(hipMemcpyAsync(s->cand, l->tri, (size_t)l->nf * sizeof(dfl_wall_tri), hipMemcpyDeviceToDevice, st));
-    dfl_laser_surface_emit(s->T, dev->ien, dev->xg, w, s->N, s->cfg.level, s->cfg.side, l->dir, s->blk_base, s->cand + l->nf, s->facets,
+    dfl_laser_surface_emit(s->T, dev->ien, dev->xg, w, s->N, s->cfg.level, s->cfg.side, l->dir, s->scan.base, s->cand + l->nf, s->facets,
                            s->ftet, s->fij, s->ft, nf, st);
-    dfl_laser_surface_nodes(nf, dev->ien, s->ftet, s->nkey, s->nkey_out, s->nrec, s->nrec_out, s->nflag, s->chunk_sum, s->nstart,
+    dfl_laser_surface_nodes(nf, dev->ien, s->ftet, s->nkey, s->nkey_out, s->nrec, s->nrec_out, s->nflag, s->scan.chunk_sum, s->nstart,
                             s->fslot, s->unode, s->temp, s->temp_bytes, st);
     HIPGUARD(hipMemsetAsync(s->power, 0, (size_t)4 * nf * sizeof(f64), st));
     HIPGUARD(hipMemsetAsync(s->energy, 0, (size_t)4 * nf * sizeof(f64), st));

@@ -2,6 +2,7 @@
  * API of src/MeshData.c, src/Mesh.c, src/color.c, src/csr.c; the algorithms run on
  * the device through include/dedflow_kernels.h (the reference builds the pattern on
  * one host thread, src/csr.c:81-190). */
+#include <math.h>
 #include <string.h>
 #include "dedflow.h"
 #include "dedflow_kernels.h"
@@ -146,6 +147,62 @@ void DflTetFlagsMatch(u8** flag, index_type T, b32 on) {
         CdamFreeDevice(*flag, 0);
         *flag = NULL;
     }
+}
+
+void DflBlockScanReserve(DflBlockScan* bs, index_type n) {
+    const index_type need = dfl_scan_num_chunks(n);
+    if (need <= bs->cap_chunk) return;
+    CdamFreeDevice(bs->chunk_sum, 0);
+    bs->chunk_sum = (index_type*)CdamMallocDevice((ptrdiff_t)need * SIZE_OF(index_type));
+    bs->cap_chunk = need;
+}
+
+void DflBlockScanAlloc(DflBlockScan* bs, index_type T, index_type other_n) {
+    const index_type per = dfl_tets_per_block();
+    memset(bs, 0, sizeof *bs);
+    bs->nblk = (T + per - 1) / per;
+    const ptrdiff_t nb = bs->nblk > 0 ? bs->nblk : 1;
+    bs->count = (index_type*)CdamMallocDevice(nb * SIZE_OF(index_type));
+    bs->base = (index_type*)CdamMallocDevice((nb + 1) * SIZE_OF(index_type));
+    DflBlockScanReserve(bs, bs->nblk > other_n ? bs->nblk : other_n);
+}
+
+void DflBlockScanFree(DflBlockScan* bs) {
+    CdamFreeDevice(bs->count, 0);
+    CdamFreeDevice(bs->base, 0);
+    CdamFreeDevice(bs->chunk_sum, 0);
+    memset(bs, 0, sizeof *bs);
+}
+
+void DflBlockScanEnqueue(const DflBlockScan* bs, index_type* total, hipStream_t s) {
+    dfl_scan_counts(bs->nblk, bs->count, bs->chunk_sum, bs->base, s);
+    HIPGUARD(hipMemcpyAsync(total, bs->base + bs->nblk, sizeof *total, D2H, s));
+}
+
+index_type DflGrowCap(index_type n) {
+    const int64_t cap = (int64_t)n + n / 2;
+    return cap > INT32_MAX ? n : (index_type)cap;
+}
+
+void DflNodeBounds(const f64* xg, index_type N, f64 lo[3], f64 hi[3]) {
+    for (int d = 0; d < 3; ++d) {
+        lo[d] = HUGE_VAL;
+        hi[d] = -HUGE_VAL;
+    }
+    for (index_type a = 0; a < N; ++a)
+        for (int d = 0; d < 3; ++d) {
+            const f64 v = xg[3 * (size_t)a + d];
+            if (v < lo[d]) lo[d] = v;
+            if (v > hi[d]) hi[d] = v;
+        }
+}
+
+void DflMeshNodeBounds(Mesh3D* mesh, f64 lo[3], f64 hi[3]) {
+    const index_type N = Mesh3DNumNode(mesh);
+    f64* x = (f64*)CdamMallocHost((ptrdiff_t)N * 3 * SIZE_OF(f64));
+    HIPGUARD(hipMemcpy(x, Mesh3DDevice(mesh)->xg, (size_t)N * 3 * sizeof(f64), D2H));
+    DflNodeBounds(x, N, lo, hi);
+    CdamFreeHost(x, (ptrdiff_t)N * 3 * SIZE_OF(f64));
 }
 
 void Mesh3DUpdateHost(Mesh3D* m) { Mesh3DDataCopy(m->host, m->device, D2H); }

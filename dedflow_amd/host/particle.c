@@ -115,7 +115,7 @@ void DflDemReserve(ParticleExt* x, index_type P, index_type nbin) {
         CdamFreeDevice(x->count, 0); CdamFreeDevice(x->cell_start, 0); CdamFreeDevice(x->chunk_sum, 0);
         x->count = (index_type*)CdamMallocDevice(((ptrdiff_t)nbin + 1) * SIZE_OF(index_type));
         x->cell_start = (index_type*)CdamMallocDevice(((ptrdiff_t)nbin + 1) * SIZE_OF(index_type));
-        x->chunk_sum = (index_type*)CdamMallocDevice((ptrdiff_t)dfl_dem_num_chunks(nbin) * SIZE_OF(index_type));
+        x->chunk_sum = (index_type*)CdamMallocDevice((ptrdiff_t)dfl_scan_num_chunks(nbin) * SIZE_OF(index_type));
         x->cap_cell = nbin + 1;
     }
 }

@@ -16,24 +16,23 @@
 #include "host_private.h"
 
 #define RD_MAX_CELLS (1 << 24)
-#define RD_NODE_WORK 2048 /* doubles dfl_redistance_node_stats needs */
 
 typedef struct RedistanceState {
     DflRedistance cfg;
-    index_type N, T, nblk;           /* nblk: workgroups of the tet passes */
+    index_type N, T;
     f64 cell_factor;                 /* DFL_REDISTANCE_CELL as the Set call read it */
     dfl_redistance_grid grid;
     index_type ncell;
     b32 grid_stale;                  /* the nodes moved since the grid was made */
     u8* hold;                        /* device [N], NULL: no group is held */
-    index_type *blk_count, *blk_base; /* device [nblk], [nblk + 1] */
-    index_type *cell_count, *cell_start, *chunk_sum; /* device [cap_cell], [cap_cell + 1], [cap_chunk] */
-    index_type cap_cell, cap_chunk;
+    DflBlockScan scan;               /* the facet counts of the tet passes; its chunk_sum also serves the cells */
+    index_type *cell_count, *cell_start; /* device [cap_cell], [cap_cell + 1] */
+    index_type cap_cell;
     f64* facets;                     /* device [cap_facets][9] */
     index_type* entries;             /* device [cap_entries] */
     index_type cap_facets, cap_entries;
     index_type *ncand, *list;        /* device [1], [N] */
-    f64 *chg, *part, *out;           /* device [N], [2 max(nblk, RD_NODE_WORK / 2)], [6] */
+    f64 *chg, *part, *out;           /* device [N], [2 max(nblk, dfl_node_reduce_max_part())], [6] */
     index_type nf_last;              /* facets of the last call, -1: none yet */
     index_type steps;                /* DflTimeStep calls since the Set call */
 } RedistanceState;
@@ -46,8 +45,7 @@ static RedistanceState* st_of(const Mesh3D* mesh) {
 static void free_cells(RedistanceState* st) {
     CdamFreeDevice(st->cell_count, 0);
     CdamFreeDevice(st->cell_start, 0);
-    CdamFreeDevice(st->chunk_sum, 0);
-    st->cell_count = st->cell_start = st->chunk_sum = NULL;
+    st->cell_count = st->cell_start = NULL;
 }
 
 void DflRedistanceFree(RedistanceState* st) {
@@ -55,8 +53,7 @@ void DflRedistanceFree(RedistanceState* st) {
     HIPGUARD(hipStreamSynchronize(DflStream()));
     free_cells(st);
     CdamFreeDevice(st->hold, 0);
-    CdamFreeDevice(st->blk_count, 0);
-    CdamFreeDevice(st->blk_base, 0);
+    DflBlockScanFree(&st->scan);
     CdamFreeDevice(st->facets, 0);
     CdamFreeDevice(st->entries, 0);
     CdamFreeDevice(st->ncand, 0);
@@ -95,21 +92,9 @@ int DflRedistanceCheck(const DflRedistance* c, char* why, size_t why_len) {
  * cells; the cell arrays grow to match.  Synchronises */
 static void build_grid(RedistanceState* st, Mesh3D* mesh) {
     hipStream_t s = DflStream();
-    const index_type N = st->N;
     f64 lo[3] = {0.0, 0.0, 0.0}, hi[3] = {0.0, 0.0, 0.0};
     HIPGUARD(hipStreamSynchronize(s));
-    if (N > 0) {
-        f64* x = (f64*)CdamMallocHost((ptrdiff_t)N * 3 * SIZE_OF(f64));
-        HIPGUARD(hipMemcpy(x, Mesh3DDevice(mesh)->xg, (size_t)N * 3 * sizeof(f64), D2H));
-        for (int d = 0; d < 3; ++d) lo[d] = hi[d] = x[d];
-        for (index_type a = 1; a < N; ++a)
-            for (int d = 0; d < 3; ++d) {
-                const f64 v = x[3 * (size_t)a + d];
-                if (v < lo[d]) lo[d] = v;
-                if (v > hi[d]) hi[d] = v;
-            }
-        CdamFreeHost(x, (ptrdiff_t)N * 3 * SIZE_OF(f64));
-    }
+    if (st->N > 0) DflMeshNodeBounds(mesh, lo, hi);
     f64 h = st->cfg.band * st->cell_factor;
     int64_t n[3];
     for (;;) {
@@ -128,15 +113,13 @@ static void build_grid(RedistanceState* st, Mesh3D* mesh) {
     }
     st->grid.inv_h = 1.0 / h;
     st->ncell = (index_type)(n[0] * n[1] * n[2]);
-    const index_type most = st->ncell > st->nblk ? st->ncell : st->nblk;
-    if (st->ncell > st->cap_cell || most / 1024 + 1 > st->cap_chunk) {
+    if (st->ncell > st->cap_cell) {
         free_cells(st);
         st->cap_cell = st->ncell;
-        st->cap_chunk = most / 1024 + 1;
         st->cell_count = (index_type*)CdamMallocDevice((ptrdiff_t)st->cap_cell * SIZE_OF(index_type));
         st->cell_start = (index_type*)CdamMallocDevice(((ptrdiff_t)st->cap_cell + 1) * SIZE_OF(index_type));
-        st->chunk_sum = (index_type*)CdamMallocDevice((ptrdiff_t)st->cap_chunk * SIZE_OF(index_type));
     }
+    DflBlockScanReserve(&st->scan, st->ncell);
     st->grid_stale = FALSE;
 }
 
@@ -193,15 +176,12 @@ void DflMeshSetRedistance(Mesh3D* mesh, const DflRedistance* cfg) {
         memset(st, 0, sizeof *st);
         st->N = N;
         st->T = T;
-        const index_type per = dfl_redistance_tets_per_block();
-        st->nblk = (T + per - 1) / per;
-        const ptrdiff_t nb = st->nblk > 0 ? st->nblk : 1, nn = N > 0 ? N : 1;
-        st->blk_count = (index_type*)CdamMallocDevice(nb * SIZE_OF(index_type));
-        st->blk_base = (index_type*)CdamMallocDevice((nb + 1) * SIZE_OF(index_type));
+        DflBlockScanAlloc(&st->scan, T, 0);
+        const ptrdiff_t nb = st->scan.nblk > 0 ? st->scan.nblk : 1, nn = N > 0 ? N : 1, most = dfl_node_reduce_max_part();
         st->ncand = (index_type*)CdamMallocDevice(SIZE_OF(index_type));
         st->list = (index_type*)CdamMallocDevice(nn * SIZE_OF(index_type));
         st->chg = (f64*)CdamMallocDevice(nn * SIZE_OF(f64));
-        st->part = (f64*)CdamMallocDevice((2 * nb > RD_NODE_WORK ? 2 * nb : RD_NODE_WORK) * SIZE_OF(f64));
+        st->part = (f64*)CdamMallocDevice(2 * (nb > most ? nb : most) * SIZE_OF(f64));
         st->out = (f64*)CdamMallocDevice(6 * SIZE_OF(f64));
         st->cap_facets = st->cap_entries = 1024;
         st->facets = (f64*)CdamMallocDevice((ptrdiff_t)st->cap_facets * 9 * SIZE_OF(f64));
@@ -242,13 +222,12 @@ index_type DflMeshRedistance(Mesh3D* mesh, f64* w) {
     HIPGUARD(hipMemsetAsync(st->cell_count, 0, (size_t)st->ncell * sizeof(index_type), s));
     HIPGUARD(hipMemsetAsync(st->ncand, 0, sizeof(index_type), s));
     /* count: facets per workgroup, entries per cell, and the statistics of the field as it came */
-    dfl_redistance_cut(st->T, dev->ien, dev->xg, w, st->N, level, &st->grid, st->blk_count, st->cell_count, st->part, s);
-    dfl_redistance_reduce(st->nblk, st->part, st->out, s);
-    dfl_redistance_scan(st->nblk, st->blk_count, st->chunk_sum, st->blk_base, s);
-    dfl_redistance_scan(st->ncell, st->cell_count, st->chunk_sum, st->cell_start, s);
-    /* the one synchronisation: both totals */
+    dfl_redistance_cut(st->T, dev->ien, dev->xg, w, st->N, level, &st->grid, st->scan.count, st->cell_count, st->part, s);
+    dfl_redistance_reduce(st->scan.nblk, st->part, st->out, s);
+    /* both scans (they take turns with chunk_sum), then the one synchronisation: both totals */
     index_type nf = 0, ne = 0;
-    HIPGUARD(hipMemcpyAsync(&nf, st->blk_base + st->nblk, sizeof nf, D2H, s));
+    dfl_scan_counts(st->ncell, st->cell_count, st->scan.chunk_sum, st->cell_start, s);
+    DflBlockScanEnqueue(&st->scan, &nf, s);
     HIPGUARD(hipMemcpyAsync(&ne, st->cell_start + st->ncell, sizeof ne, D2H, s));
     HIPGUARD(hipStreamSynchronize(s));
     if (nf < 0 || ne < 0) {
@@ -259,22 +238,22 @@ index_type DflMeshRedistance(Mesh3D* mesh, f64* w) {
     }
     if (nf > st->cap_facets) {
         CdamFreeDevice(st->facets, 0);
-        st->cap_facets = nf + nf / 2 < nf ? nf : nf + nf / 2;
+        st->cap_facets = DflGrowCap(nf);
         st->facets = (f64*)CdamMallocDevice((ptrdiff_t)st->cap_facets * 9 * SIZE_OF(f64));
     }
     if (ne > st->cap_entries) {
         CdamFreeDevice(st->entries, 0);
-        st->cap_entries = ne + ne / 2 < ne ? ne : ne + ne / 2;
+        st->cap_entries = DflGrowCap(ne);
         st->entries = (index_type*)CdamMallocDevice((ptrdiff_t)st->cap_entries * SIZE_OF(index_type));
     }
     if (nf > 0)
-        dfl_redistance_emit(st->T, dev->ien, dev->xg, w, st->N, level, &st->grid, st->blk_base, st->cell_start, st->cell_count,
+        dfl_redistance_emit(st->T, dev->ien, dev->xg, w, st->N, level, &st->grid, st->scan.base, st->cell_start, st->cell_count,
                             st->facets, st->cap_facets, st->entries, st->cap_entries, s);
     dfl_redistance_nodes(st->N, dev->xg, w, level, band, &st->grid, st->cell_start, st->entries, st->facets, st->cap_facets, st->hold,
                          st->ncand, st->list, st->chg, s);
     /* the statistics of the new field */
     dfl_redistance_cut(st->T, dev->ien, dev->xg, w, st->N, level, NULL, NULL, NULL, st->part, s);
-    dfl_redistance_reduce(st->nblk, st->part, st->out + 2, s);
+    dfl_redistance_reduce(st->scan.nblk, st->part, st->out + 2, s);
     dfl_redistance_node_stats(st->N, st->chg, st->part, st->out + 4, s);
     st->nf_last = nf;
     DflRangePop();
@@ -313,7 +292,7 @@ f64 DflMeshLevelSetVolume(Mesh3D* mesh, const f64* w, f64 level) {
     if (N <= 0 || T <= 0) return 0.0;
     const Mesh3DData* dev = Mesh3DDevice(mesh);
     hipStream_t s = DflStream();
-    const index_type per = dfl_redistance_tets_per_block(), nblk = (T + per - 1) / per;
+    const index_type per = dfl_tets_per_block(), nblk = (T + per - 1) / per;
     /* scratch of its own: the call works on a mesh without a configuration and leaves the last call's statistics alone */
     f64* part = (f64*)CdamMallocDevice(((ptrdiff_t)2 * nblk + 2) * SIZE_OF(f64));
     f64 h[2] = {0.0, 0.0};

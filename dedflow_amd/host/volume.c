@@ -16,15 +16,14 @@
 
 #define VC_K DFL_VOLUME_K
 #define VC_PASSES 12
-#define VC_NODE_WORK 1024 /* doubles dfl_volume_node_sum needs */
 
 typedef struct VolumeState {
     DflVolumeCorrection cfg;
-    index_type N, T, nblk;            /* nblk: workgroups of the tet passes */
+    index_type N, T;
     index_type pass_limit;            /* DFL_VOLUME_PASSES as the Set call read it */
     f64 target;                       /* NaN: the next call records it */
-    index_type *blk_count, *blk_base, *chunk_sum; /* device [nblk], [nblk + 1], [nblk / 1024 + 1] */
-    f64 *part, *out;                  /* device [max(VC_K nblk, VC_NODE_WORK)], [VC_K] */
+    DflBlockScan scan;                /* the band-tet counts of the tet passes */
+    f64 *part, *out;                  /* device [max(VC_K nblk, dfl_node_reduce_max_part())], [VC_K] */
     index_type* list;                 /* device [cap]: the band list, tet ids */
     index_type cap;
     DflVolumeCorrectionStats last;    /* status -1: no call yet */
@@ -39,9 +38,7 @@ static VolumeState* st_of(const Mesh3D* mesh) {
 void DflVolumeCorrectionFree(VolumeState* st) {
     if (!st) return;
     HIPGUARD(hipStreamSynchronize(DflStream()));
-    CdamFreeDevice(st->blk_count, 0);
-    CdamFreeDevice(st->blk_base, 0);
-    CdamFreeDevice(st->chunk_sum, 0);
+    DflBlockScanFree(&st->scan);
     CdamFreeDevice(st->part, 0);
     CdamFreeDevice(st->out, 0);
     CdamFreeDevice(st->list, 0);
@@ -117,13 +114,9 @@ void DflMeshSetVolumeCorrection(Mesh3D* mesh, const DflVolumeCorrection* cfg) {
         memset(st, 0, sizeof *st);
         st->N = Mesh3DNumNode(mesh);
         st->T = Mesh3DNumTet(mesh);
-        const index_type per = dfl_redistance_tets_per_block();
-        st->nblk = (st->T + per - 1) / per;
-        const ptrdiff_t nb = st->nblk > 0 ? st->nblk : 1;
-        st->blk_count = (index_type*)CdamMallocDevice(nb * SIZE_OF(index_type));
-        st->blk_base = (index_type*)CdamMallocDevice((nb + 1) * SIZE_OF(index_type));
-        st->chunk_sum = (index_type*)CdamMallocDevice((nb / 1024 + 1) * SIZE_OF(index_type));
-        st->part = (f64*)CdamMallocDevice((VC_K * nb > VC_NODE_WORK ? VC_K * nb : VC_NODE_WORK) * SIZE_OF(f64));
+        DflBlockScanAlloc(&st->scan, st->T, 0);
+        const ptrdiff_t nb = st->scan.nblk > 0 ? st->scan.nblk : 1, most = dfl_node_reduce_max_part();
+        st->part = (f64*)CdamMallocDevice((VC_K * nb > most ? VC_K * nb : most) * SIZE_OF(f64));
         st->out = (f64*)CdamMallocDevice(VC_K * SIZE_OF(f64));
         st->cap = 1024;
         st->list = (index_type*)CdamMallocDevice((ptrdiff_t)st->cap * SIZE_OF(index_type));
@@ -181,10 +174,9 @@ index_type DflMeshVolumeCorrect(Mesh3D* mesh, f64* w) {
     DflRangePush("DflMeshVolumeCorrect");
     if (st->N > 0 && st->T > 0) {
         const Mesh3DData* dev = Mesh3DDevice(mesh);
-        dfl_volume_classify(st->T, dev->ien, dev->xg, w, st->N, level, lo, hi, st->blk_count, st->part, st->out, s);
-        dfl_redistance_scan(st->nblk, st->blk_count, st->chunk_sum, st->blk_base, s);
+        dfl_volume_classify(st->T, dev->ien, dev->xg, w, st->N, level, lo, hi, st->scan.count, st->part, st->out, s);
+        DflBlockScanEnqueue(&st->scan, &nb, s);
         HIPGUARD(hipMemcpyAsync(h, st->out, sizeof h, D2H, s));
-        HIPGUARD(hipMemcpyAsync(&nb, st->blk_base + st->nblk, sizeof nb, D2H, s));
         HIPGUARD(hipStreamSynchronize(s));
     }
     const f64 V_in = h[0], V_mesh = h[4];
@@ -205,11 +197,11 @@ index_type DflMeshVolumeCorrect(Mesh3D* mesh, f64* w) {
         Point best = fabs(a.V - target) <= fabs(b.V - target) ? a : b;
         if (nb > st->cap) {
             CdamFreeDevice(st->list, 0);
-            st->cap = nb + nb / 2 < nb ? nb : nb + nb / 2;
+            st->cap = DflGrowCap(nb);
             st->list = (index_type*)CdamMallocDevice((ptrdiff_t)st->cap * SIZE_OF(index_type));
         }
         const Mesh3DData* dev = Mesh3DDevice(mesh);
-        dfl_volume_emit(st->T, dev->ien, w, st->N, lo, hi, st->blk_base, st->list, st->cap, s);
+        dfl_volume_emit(st->T, dev->ien, w, st->N, lo, hi, st->scan.base, st->list, st->cap, s);
         r->status = 3;
         while (fabs(best.V - target) > tolV && r->passes < st->pass_limit) {
             Point p[VC_K + 2];

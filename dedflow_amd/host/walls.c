@@ -227,16 +227,7 @@ dfl_wall_tri* DflMeshBoundaryTris(Mesh3D* mesh, index_type group_mask, index_typ
         HIPGUARD(hipMemcpy(f2e, mesh->bound_f2e, (size_t)nfall * sizeof(index_type), D2H));
         HIPGUARD(hipMemcpy(forn, mesh->bound_forn, (size_t)nfall * sizeof(index_type), D2H));
     }
-    for (int d = 0; d < 3; ++d) {
-        lo[d] = HUGE_VAL;
-        hi[d] = -HUGE_VAL;
-    }
-    for (index_type a = 0; a < N; ++a)
-        for (int d = 0; d < 3; ++d) {
-            const f64 c = xg[3 * (size_t)a + d];
-            if (c < lo[d]) lo[d] = c;
-            if (c > hi[d]) hi[d] = c;
-        }
+    DflNodeBounds(xg, N, lo, hi);
     index_type nf = 0;
     for (index_type g = 0; g < nb && g < 31; ++g)
         if (group_mask >> g & 1) nf += mesh->bound_elem_offset[g + 1] - mesh->bound_elem_offset[g];

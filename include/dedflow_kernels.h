@@ -562,14 +562,25 @@ void dfl_amgx_tail_setup(const dfl_amgx_level* levels, dfl_index l0, dfl_index n
 void dfl_amgx_tail_cycle(const dfl_amgx_level* levels, dfl_index l0, dfl_index nlev, int jacobi, int presweeps, int postsweeps,
                          dfl_value omega, const dfl_value* b0, dfl_value* x0, dfl_value* w0, void* stream);
 
+/* ---- shared pieces of the count -> scan -> emit passes and of the two-stage reductions (csrc/k_scan.hip, csrc/block_ops.hpp)
+ *    dfl_scan_num_chunks       integers of chunk_sum that dfl_scan_counts needs for n entries: ceil((n + 1) / 1024)
+ *    dfl_scan_counts           start[0 .. n] = exclusive scan of count[0 .. n), start[n] = the total, count zeroed; two
+ *                              launches on `stream`, nothing allocated or synchronised; returns at once for n < 0
+ *    dfl_tets_per_block        tets per workgroup of the one-thread-per-tet passes (redistancing, volume correction, laser
+ *                              surface): their blk_count / blk_base hold ceil(T / that) and one more entries
+ *    dfl_node_reduce_max_part  the most partials a two-stage node reduction writes per value: `work` of dfl_phase_stats,
+ *                              dfl_redistance_node_stats and dfl_volume_node_sum holds that many times their values */
+dfl_index dfl_scan_num_chunks(dfl_index n);
+void dfl_scan_counts(dfl_index n, dfl_index* count, dfl_index* chunk_sum, dfl_index* start, void* stream);
+dfl_index dfl_tets_per_block(void);
+dfl_index dfl_node_reduce_max_part(void);
+
 /* ---- DEM contact sweep (build-defined; the reference's Particle.c holds storage only)
  *  model: spheres, linear spring-dashpot normal contact F = (kn*overlap - gamma_n*vn) n between particles and against
  *  the six walls of the unit box or the boundary faces of a tet mesh; uniform cell list with cell edge >= 4R.  Opt-in:
  *  contact friction with rotation, per-particle radius and mass (the blocks below).  The launchers of the sweep
  *  (dfl_dem_build_cells ... dfl_walls_forces) follow the types they take: "DEM contact sweep: launchers" below.
- *    dfl_dem_num_chunks   length of the chunk_sum scratch for a cell list of ncell3 bins
  *    dfl_dem_integrate    v += dt*a ; x += dt*v */
-dfl_index dfl_dem_num_chunks(dfl_index ncell3);
 void dfl_dem_integrate(dfl_index P, dfl_value dt, dfl_value* coord, dfl_value* vel, const dfl_value* acc, void* stream);
 
 /* ---- DEM contacts with the boundary faces of a tet mesh (build-defined, csrc/k_walls.hip; model in include/dedflow.h)
@@ -734,13 +745,13 @@ typedef struct dfl_sizes {
  *    dfl_dem_build_cells    counting sort of the particles by cell (5 launches): cell_start[ncell^3 + 1], order[P] =
  *                           particle ids by (cell, id), and the copies in that order: sorted[P][6] = position and
  *                           velocity, sorted_w[P][3] = omega (friction), sorted_r[P] = radius (sizes).  count[ncell^3 + 1]
- *                           and chunk_sum[dfl_dem_num_chunks(ncell^3)] are zero-initialised scratch that the call leaves
+ *                           and chunk_sum[dfl_scan_num_chunks(ncell^3)] are zero-initialised scratch that the call leaves
  *                           zeroed again; cell_of, rank and slot [P] are scratch
  *    dfl_dem_sort_binned    the last four launches of dfl_dem_build_cells, for a bin pass of the caller's over nbin bins
  *    dfl_dem_forces         acc[i] = (sum_j F_ij + F_walls) / m_i, neighbours from the cells within the interaction range;
  *                           with friction also alpha[i] = torque / I_i and the new history rows
  *    dfl_walls_build_cells  dfl_dem_build_cells on `grid`; a particle outside it goes to the extra bin nx*ny*nz (count and
- *                           cell_start then hold nx*ny*nz + 2 entries, chunk_sum dfl_dem_num_chunks(nx*ny*nz + 1))
+ *                           cell_start then hold nx*ny*nz + 2 entries, chunk_sum dfl_scan_num_chunks(nx*ny*nz + 1))
  *    dfl_walls_forces       dfl_dem_forces for the particles inside `grid` with the mesh's walls, 0 for the others; the
  *                           wall candidates of a particle are wall_list[wall_start[c] .. wall_start[c+1]) of the wall_grid
  *                           cell c holding its centre; *dropped += contacts over DFL_WALL_MAX_CONTACTS; plane[F] = the
@@ -838,9 +849,9 @@ void dfl_laser_source_add(dfl_index ns, const dfl_index* snode, dfl_value inv_ti
                           void* stream);
 
 /* ---- the laser on the level-set surface (build-defined, opt-in; csrc/k_laser_surface.hip, model in include/dedflow.h)
- * Snapshot: count -> dfl_redistance_scan of the workgroup counts -> emit -> nodes.  Deposit: once per laser step.  All on
+ * Snapshot: count -> dfl_scan_counts of the workgroup counts -> emit -> nodes.  Deposit: once per laser step.  All on
  * `stream`; nothing allocated or synchronised; no floating-point atomics; no atomic decides an order.
- *    dfl_laser_surface_count       blk_count[b] = candidate facets of the tets of workgroup b (dfl_redistance_tets_per_block()
+ *    dfl_laser_surface_count       blk_count[b] = candidate facets of the tets of workgroup b (dfl_tets_per_block()
  *                                  tets each): the facets of lf_tet_facets with side (g . dir) > 0, |g| > 0 and nine finite
  *                                  coordinates.  phi = w + 4N; dir: three host doubles, the normalised beam direction
  *    dfl_laser_surface_emit        facet f = blk_base[b] + (candidates of the earlier tets of workgroup b), f < cap:
@@ -849,7 +860,7 @@ void dfl_laser_source_add(dfl_index ns, const dfl_index* snode, dfl_value inv_ti
  *                                  passes the candidate list offset by the boundary records in front)
  *    dfl_laser_surface_nodes       the distinct nodes of the facets' tets: unode[0 .. nu) ascending, nu = start[4 nfs], and
  *                                  fslot[4 f + a] = the index in unode of local node a of facet f's tet.  key, key_out, rec,
- *                                  rec_out, flag: [4 nfs]; start: [4 nfs + 1]; chunk_sum as dfl_redistance_scan needs for
+ *                                  rec_out, flag: [4 nfs]; start: [4 nfs + 1]; chunk_sum as dfl_scan_counts needs for
  *                                  4 nfs entries; temp: dfl_laser_surface_temp_bytes(4 nfs, .) bytes
  *    dfl_laser_surface_deposit     power[0 .. 4 nfs) <- 0; then per slot the sum, from +0.0 in ascending column id, of
  *                                  (eta_s col_T[c]) lambda_a over the columns c whose hit key names a facet (index >= nfb in
@@ -1028,13 +1039,11 @@ void dfl_fluid_add_jacobian(dfl_index N, const dfl_index* vrow, const dfl_index*
 /* ---- level-set redistancing (build-defined, opt-in; host/redistance.c, csrc/k_redistance.hip, model in include/dedflow.h)
  * phi = w + 4N.  grid: the uniform cell grid over the mesh's bounding box; a point's cell per axis is
  * clamp(floor((x - lo) inv_h), 0, n - 1), cell id = cx + n[0] (cy + n[1] cz).
- *    dfl_redistance_cut      one thread per tet, workgroups of dfl_redistance_tets_per_block() tets.  part[2 b], part[2 b + 1]
+ *    dfl_redistance_cut      one thread per tet, workgroups of dfl_tets_per_block() tets.  part[2 b], part[2 b + 1]
  *                            = workgroup b's volume of {phi > level} (fixed tree) and its maximum of ||g| - 1| over the cut
  *                            tets.  With blk_count: blk_count[b] = facets of workgroup b, and cell_count[c] += 1 for every
  *                            cell c the bounding box of a facet's finite vertices overlaps (integer atomics; a vertex
  *                            with a NaN coordinate cannot win, the others still count).  blk_count NULL: the statistics alone.
- *    dfl_redistance_scan     start[0 .. n] = exclusive scan of count[0 .. n), count zeroed; chunk_sum holds
- *                            ceil((n + 1) / 1024) integers
  *    dfl_redistance_emit     the facets in ascending tet order, a quad's first triangle first: facet blk_base[b] + (facets of
  *                            the earlier tets of workgroup b), and its index into every cell it overlaps at
  *                            cell_start[c] + cell_fill[c]++ (cell_fill zero on entry; the order inside a cell is free).
@@ -1046,17 +1055,16 @@ void dfl_fluid_add_jacobian(dfl_index N, const dfl_index* vrow, const dfl_index*
  *                            xor-shuffles, lane 0 writes phi = level +- min(d, band) and chg = |new - old| where d < band,
  *                            else -1.  A node with hold[a] != 0 (hold NULL: none) or a NaN phi keeps its value (chg 0 in
  *                            the band).
- *    dfl_redistance_node_stats  out2 = (number of nodes with chg >= 0, their maximum chg); work >= 2048 doubles
+ *    dfl_redistance_node_stats  out2 = (number of nodes with chg >= 0, their maximum chg); work >= 2 dfl_node_reduce_max_part()
+ *                            doubles
  *    dfl_redistance_reduce   out2 = (sum of part[2 i] in a fixed order, max of part[2 i + 1]), i < npart */
 typedef struct dfl_redistance_grid {
     dfl_value lo[3], inv_h;
     dfl_index n[3];
 } dfl_redistance_grid;
-dfl_index dfl_redistance_tets_per_block(void);
 void dfl_redistance_cut(dfl_index T, const dfl_index* ien, const dfl_value* xg, const dfl_value* w, dfl_index N, dfl_value level,
                         const dfl_redistance_grid* grid, dfl_index* blk_count, dfl_index* cell_count, dfl_value* part,
                         void* stream);
-void dfl_redistance_scan(dfl_index n, dfl_index* count, dfl_index* chunk_sum, dfl_index* start, void* stream);
 void dfl_redistance_emit(dfl_index T, const dfl_index* ien, const dfl_value* xg, const dfl_value* w, dfl_index N, dfl_value level,
                          const dfl_redistance_grid* grid, const dfl_index* blk_base, const dfl_index* cell_start,
                          dfl_index* cell_fill, dfl_value* facets, dfl_index cap_facets, dfl_index* entries,
@@ -1070,7 +1078,7 @@ void dfl_redistance_reduce(dfl_index npart, const dfl_value* part, dfl_value* ou
 
 /* ---- level-set volume correction (build-defined, opt-in; host/volume.c, csrc/k_volume.hip, model in include/dedflow.h)
  * phi = w + 4N, lo = level - max_shift, hi = level + max_shift.  A tet is inside when its four phi are > hi, a band tet when
- * it is not inside and has a phi > lo.  Workgroups of dfl_redistance_tets_per_block() tets.  Every sum has a fixed order.
+ * it is not inside and has a phi > lo.  Workgroups of dfl_tets_per_block() tets.  Every sum has a fixed order.
  *    dfl_volume_classify  one thread per tet.  blk_count[b] = band tets of workgroup b; part: [workgroups][5]; out5 = (V_in: the
  *                         |det| / 6 of the inside tets, the volume of {phi > level}, {phi > lo} and {phi > hi} inside the
  *                         band tets, the mesh volume)
@@ -1079,7 +1087,7 @@ void dfl_redistance_reduce(dfl_index npart, const dfl_value* part, dfl_value* ou
  *    dfl_volume_eval      outK[k] = the volume of {phi > cand[k]} inside the nband listed tets, k < DFL_VOLUME_K; cand is on
  *                         the host and travels as a kernel argument; part: [ceil(nband / 256)][DFL_VOLUME_K]
  *    dfl_volume_shift     phi_a += delta for every node, one rounded addition; a NaN is not written
- *    dfl_volume_node_sum  out1[0] = sum of q[0 .. N); work >= 1024 doubles */
+ *    dfl_volume_node_sum  out1[0] = sum of q[0 .. N); work >= dfl_node_reduce_max_part() doubles */
 #define DFL_VOLUME_K 15
 void dfl_volume_classify(dfl_index T, const dfl_index* ien, const dfl_value* xg, const dfl_value* w, dfl_index N, dfl_value level,
                          dfl_value lo, dfl_value hi, dfl_index* blk_count, dfl_value* part, dfl_value* out5, void* stream);

@@ -42,7 +42,7 @@ def kernel_path(L, P, m, phi0, level, band, reps, warmup):
     n = [int(np.floor((hi[d] - lo[d]) / band)) + 1 for d in range(3)]
     grid = Grid((C.c_double * 3)(*lo), 1.0 / band, (C.c_int32 * 3)(*n))
     ncell = n[0] * n[1] * n[2]
-    per = int(L.dfl_redistance_tets_per_block())
+    per = int(L.dfl_tets_per_block())
     nblk = (T + per - 1) // per
     I, F = np.int32, np.float64
     dev = P.mesh.contents.device.contents
@@ -51,13 +51,13 @@ def kernel_path(L, P, m, phi0, level, band, reps, warmup):
     w_src, w = api.DeviceArray.from_numpy(w0), api.DeviceArray(6 * N)
     blk_count, blk_base = api.DeviceArray(nblk, I), api.DeviceArray(nblk + 1, I)
     cell_count, cell_start = api.DeviceArray(ncell, I), api.DeviceArray(ncell + 1, I)
-    chunk = api.DeviceArray(max(ncell, nblk) // 1024 + 1, I)
-    part, out = api.DeviceArray(max(2 * nblk, 2048)), api.DeviceArray(6)
+    chunk = api.DeviceArray(int(L.dfl_scan_num_chunks(max(ncell, nblk))), I)
+    part, out = api.DeviceArray(2 * max(nblk, int(L.dfl_node_reduce_max_part()))), api.DeviceArray(6)
     ncand, lst, chg = api.DeviceArray(1, I), api.DeviceArray(N, I), api.DeviceArray(N)
     s = L.DflStream()
     vp, i32, f64 = C.c_void_p, C.c_int32, C.c_double
     for name, args in (("dfl_redistance_cut", [i32, vp, vp, vp, i32, f64, C.POINTER(Grid), vp, vp, vp, vp]),
-                       ("dfl_redistance_scan", [i32, vp, vp, vp, vp]),
+                       ("dfl_scan_counts", [i32, vp, vp, vp, vp]),
                        ("dfl_redistance_emit", [i32, vp, vp, vp, i32, f64, C.POINTER(Grid), vp, vp, vp, vp, i32, vp, i32, vp]),
                        ("dfl_redistance_nodes", [i32, vp, vp, f64, f64, C.POINTER(Grid), vp, vp, vp, i32, vp, vp, vp, vp, vp]),
                        ("dfl_redistance_node_stats", [i32, vp, vp, vp, vp]), ("dfl_redistance_reduce", [i32, vp, vp, vp])):
@@ -68,8 +68,8 @@ def kernel_path(L, P, m, phi0, level, band, reps, warmup):
         L.dfl_redistance_reduce(nblk, part.ptr, out.ptr, s)
 
     def scans():
-        L.dfl_redistance_scan(nblk, blk_count.ptr, chunk.ptr, blk_base.ptr, s)
-        L.dfl_redistance_scan(ncell, cell_count.ptr, chunk.ptr, cell_start.ptr, s)
+        L.dfl_scan_counts(nblk, blk_count.ptr, chunk.ptr, blk_base.ptr, s)
+        L.dfl_scan_counts(ncell, cell_count.ptr, chunk.ptr, cell_start.ptr, s)
 
     def reset():
         api._chk(api.hip().hipMemcpy(w.ptr, w_src.ptr, w.nbytes, 3))
