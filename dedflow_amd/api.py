@@ -731,6 +731,18 @@ class DflVolumeCorrectionStats(C.Structure):
                 ("volume_mesh", C.c_double)]
 
 
+class DflSolidification(C.Structure):
+    _fields_ = [("T_front", C.c_double), ("use_phi", C.c_int32), ("level", C.c_double), ("side", C.c_int32),
+                ("in_time_step", C.c_int32)]
+
+
+class DflSolidificationStats(C.Structure):
+    _fields_ = [("time", C.c_double), ("updates", C.c_int64), ("frozen", C.c_int64), ("liquid", C.c_int64),
+                ("freeze_events_last", C.c_int64), ("melt_events_last", C.c_int64), ("G_min", C.c_double), ("G_max", C.c_double),
+                ("cool_min", C.c_double), ("cool_max", C.c_double), ("R_min", C.c_double), ("R_max", C.c_double),
+                ("T_peak_max", C.c_double)]
+
+
 class DflComm(C.Structure):
     _fields_ = [("allreduce_sum", ALLREDUCE_FN), ("halo_exchange", HALO_FN), ("ctx", vp), ("num_owned_node", C.c_int32),
                 ("halo_begin", HALO_FN), ("halo_end", HALO_FN), ("num_interior_node", C.c_int32),
@@ -928,6 +940,14 @@ def _declare(L):
     f("DflMeshVolumeCorrectionSetTarget", None, [C.POINTER(Mesh3D), f64])
     f("DflMeshVolumeCorrectionAddTarget", None, [C.POINTER(Mesh3D), f64])
     f("DflMeshLevelSetVolume", f64, [C.POINTER(Mesh3D), vp, f64])
+    f("DflSolidificationCheck", C.c_int, [C.POINTER(DflSolidification), C.c_char_p, C.c_size_t])
+    f("DflMeshSetSolidification", None, [C.POINTER(Mesh3D), C.POINTER(DflSolidification)])
+    f("DflMeshSolidificationEnabled", i32, [C.POINTER(Mesh3D)])
+    f("DflMeshSolidificationUpdate", None, [C.POINTER(Mesh3D), vp, f64])
+    f("DflMeshSolidificationReset", None, [C.POINTER(Mesh3D)])
+    f("DflMeshSolidificationFields", None, [C.POINTER(Mesh3D)] + 6 * [C.POINTER(vp)])
+    f("DflMeshSolidificationEvents", i32, [C.POINTER(Mesh3D), C.POINTER(vp)])
+    f("DflMeshSolidificationStats", None, [C.POINTER(Mesh3D), C.POINTER(DflSolidificationStats)])
     f("GenerateRandomColor", None, [vp, i32, i32])
     f("dfl_abi_version", C.c_int, [])
 
@@ -1359,6 +1379,68 @@ class Problem:
         """DflMeshVolumeCorrectionAddTarget: the target grows by dV of {phi > level}"""
         self._need_volume_correction()
         lib().DflMeshVolumeCorrectionAddTarget(self.mesh, float(dV))
+
+    # ---- solidification record (include/dedflow.h, "solidification record") --------------------------------------------------
+    def set_solidification(self, T_front=None, use_phi=False, level=0.0, side=1, in_time_step=False):
+        """DflMeshSetSolidification: the per-node record of the last freezing through the isotherm T_front (time, cooling rate,
+        recovered thermal gradient), peak temperature, time spent liquid and remelts; use_phi: only in the metal, where
+        side (phi - level) > 0; in_time_step: DflTimeStep updates the record itself.  T_front None turns the feature off.  A
+        configuration the library refuses (reported on stderr) leaves the mesh as it was: solidification_on tells."""
+        if T_front is None:
+            lib().DflMeshSetSolidification(self.mesh, None)
+            return
+        cfg = DflSolidification(float(T_front), 1 if use_phi else 0, float(level), int(side), 1 if in_time_step else 0)
+        lib().DflMeshSetSolidification(self.mesh, C.byref(cfg))
+
+    @property
+    def solidification_on(self):
+        return bool(lib().DflMeshSolidificationEnabled(self.mesh))
+
+    def _need_solidification(self):
+        if not self.solidification_on:
+            raise RuntimeError("no solidification record is set: call set_solidification first")
+
+    def solidification_update(self, w, dt):
+        """DflMeshSolidificationUpdate: w (DeviceArray of 6N, or a device pointer) is the state at the END of a step of
+        length dt; the first call after set_solidification or solidification_reset only primes the record"""
+        self._need_solidification()
+        lib().DflMeshSolidificationUpdate(self.mesh, getattr(w, "ptr", w), float(dt))
+
+    def solidification_reset(self):
+        self._need_solidification()
+        lib().DflMeshSolidificationReset(self.mesh)
+
+    def solidification_fields(self):
+        """numpy copies of the record (synchronises): t_solid, cool, T_peak, t_liquid [N], grad3 [N, 3], melts [N] and the
+        derived front speed R = |G| > 0 ? cool / |G| : 0 [N], |G| = sqrt((g0 g0 + g1 g1) + g2 g2)"""
+        self._need_solidification()
+        p = [vp() for _ in range(6)]
+        lib().DflMeshSolidificationFields(self.mesh, *[C.byref(q) for q in p])
+        sync()
+        N = self.N
+        out = {k: d2h(q.value, n * N, t) for k, q, n, t in zip(("t_solid", "grad3", "cool", "T_peak", "t_liquid", "melts"), p,
+                                                               (1, 3, 1, 1, 1, 1), 5 * [np.float64] + [np.int32])}
+        g = out["grad3"] = out["grad3"].reshape(N, 3)
+        G = np.sqrt((g[:, 0] * g[:, 0] + g[:, 1] * g[:, 1]) + g[:, 2] * g[:, 2])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["R"] = np.where(G > 0.0, out["cool"] / G, 0.0)
+        return out
+
+    def solidification_events(self):
+        """DflMeshSolidificationEvents: the nodes frozen by the last update, ascending (synchronises)"""
+        self._need_solidification()
+        p = vp()
+        n = int(lib().DflMeshSolidificationEvents(self.mesh, C.byref(p)))
+        return d2h(p.value, n, np.int32) if n > 0 else np.zeros(0, np.int32)
+
+    def solidification_stats(self):
+        """DflMeshSolidificationStats: time, updates, frozen, liquid, freeze_events_last, melt_events_last, G / cool / R min and
+        max over the records, T_peak_max over the metal nodes (synchronises)"""
+        self._need_solidification()
+        s = DflSolidificationStats()
+        lib().DflMeshSolidificationStats(self.mesh, C.byref(s))
+        ints = ("updates", "frozen", "liquid", "freeze_events_last", "melt_events_last")
+        return {k: (int if k in ints else float)(getattr(s, k)) for k, _ in DflSolidificationStats._fields_}
 
     def close(self):
         L = lib()

@@ -1,6 +1,6 @@
 // Workgroup-wide integer counts and scans and fixed-order reductions for 256-thread workgroups: the one copy of every idiom
 // the "count per workgroup -> scan (k_scan.hip) -> emit in ascending order" passes and the two-stage statistics share
-// (k_redistance.hip, k_volume.hip, k_laser_surface.hip, k_phase.hip, k_scan.hip).  Results that must stay bitwise
+// (k_redistance.hip, k_volume.hip, k_laser_surface.hip, k_phase.hip, k_solidify.hip, k_scan.hip).  Results that must stay bitwise
 // reproducible depend on the association written here:
 //   block_tree_256    ((w0 o w1) o w2) o w3 after the xor shuffles inside every wave
 //   block_sum_256     of dfl_common.hpp is another tree, (w0 + w1) + (w2 + w3): the Krylov kernels keep it

@@ -1,6 +1,6 @@
 // The chunked exclusive scan of integer counts for gfx950: the one scan behind the DEM cell sort (k_dem.hip, k_walls.hip,
 // the laser's column bins), the workgroup counts of the count -> scan -> emit passes (k_redistance.hip, k_volume.hip,
-// k_laser_surface.hip), the redistancing cells and the laser surface's node heads.
+// k_laser_surface.hip, k_solidify.hip), the redistancing cells and the laser surface's node heads.
 //
 //   scan_chunk_sum_kernel   total of every 1024-entry chunk
 //   scan_chunk_kernel       workgroup b owns [b * 1024, (b + 1) * 1024): adds up the chunk totals before it, scans its own

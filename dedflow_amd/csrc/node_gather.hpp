@@ -1,6 +1,7 @@
 // The node gather over the sorted V2E map (one per mesh, host/mesh.c: every node's tets in ascending tet id), shared by the
-// free-surface pass (k_surface.hip), the phase-change pass (k_phase.hip), the thermal-material rows (k_thermal.hip) and, for
-// its shape and trip count, the scalar Jacobian rows (k_scalar.hip).
+// free-surface pass (k_surface.hip), the phase-change pass (k_phase.hip), the thermal-material rows (k_thermal.hip), the
+// solidification record's gradient over a node list (k_solidify.hip) and, for its shape and trip count, the scalar Jacobian rows
+// (k_scalar.hip).
 //
 // A group of NG_LANES = 16 lanes owns node a (NG_ROWS = 16 nodes per 256-thread workgroup; a Kuhn-cube interior node has 24
 // tets: two trips).  Lane j of the group takes tet j of a's list and evaluates the NC values of its own node, or leaves
@@ -46,17 +47,19 @@ struct NodeSum {
 };
 
 // eval(e, row, out[NC]) -> stays: the NC values of node `row` from tet e into out (which arrives as +0.0), false: the tet
-// adds nothing.  Launch with NG_BLK threads and ceil(N / NG_ROWS) workgroups; uses NC * NG_BLK * 8 bytes of LDS.
+// adds nothing.  The row-mapping form: the caller says which node this lane's group owns (the same for the 16 lanes of a
+// group; !live: none) -- the k-th entry of a node list, say (k_solidify.hip).  It may be called again and again by the same
+// workgroup: a group's parked values are consumed before the call returns.  NG_BLK threads; NC * NG_BLK * 8 bytes of LDS.
 template <int NC, class Eval>
-__device__ __forceinline__ NodeSum node_gather_sum(I N, const I* __restrict__ vrow, const I* __restrict__ vcol, Eval eval) {
+__device__ __forceinline__ NodeSum node_gather_row(I row, bool live, const I* __restrict__ vrow, const I* __restrict__ vcol,
+                                                   Eval eval) {
     __shared__ double s_val[NC][NG_BLK];
     const int t = threadIdx.x;
     const int gbase = t & ~(NG_LANES - 1);
-    const long long row_ll = (long long)blockIdx.x * NG_ROWS + t / NG_LANES;
     NodeSum r;
     r.g = t & (NG_LANES - 1);
-    r.live = row_ll < N;
-    r.row = r.live ? (I)row_ll : 0;
+    r.live = live;
+    r.row = r.live ? row : 0;
     r.acc = 0.0;
     const I e0 = r.live ? vrow[r.row] : 0, ne = r.live ? vrow[r.row + 1] - e0 : 0;
     const int ne_w = wave_max(ne);
@@ -78,6 +81,14 @@ __device__ __forceinline__ NodeSum node_gather_sum(I N, const I* __restrict__ vr
         }
     }
     return r;
+}
+
+// the form of the passes over all nodes: group t / NG_LANES of workgroup b owns node b * NG_ROWS + t / NG_LANES.  Launch with
+// NG_BLK threads and ceil(N / NG_ROWS) workgroups
+template <int NC, class Eval>
+__device__ __forceinline__ NodeSum node_gather_sum(I N, const I* __restrict__ vrow, const I* __restrict__ vcol, Eval eval) {
+    const long long row_ll = (long long)blockIdx.x * NG_ROWS + threadIdx.x / NG_LANES;
+    return node_gather_row<NC>((I)row_ll, row_ll < N, vrow, vcol, eval);
 }
 
 }  // namespace

@@ -155,7 +155,9 @@ index_type SolveFlowSystem(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matr
  * wgold back to the target volume, after that redistancing and before anything else looks at phi; with its track_capture, a
  * step that took a pending two-way capture source adds the deposited volume to the target after its Newton solve.
  * With a laser surface set on the coupled context (ParticleContextSetLaserSurface), ParticleContextLaserSurfaceUpdate runs
- * once, before the first particle sub-step, in the state those sub-steps see. */
+ * once, before the first particle sub-step, in the state those sub-steps see.
+ * With a solidification record set on the mesh with in_time_step (DflMeshSetSolidification), the record is updated with the
+ * new wgold and kDT right after the step has written it; the first such call primes the record at its incoming wgold. */
 index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* J, f64* F, f64* dx, Krylov* ksp, Dirichlet** bcs,
                        index_type nbc, index_type newton_maxit, ParticleContext* pctx, index_type dem_substeps, f64* rnorm_out,
                        f64* rnorm_init_out) {
@@ -196,7 +198,13 @@ index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* 
         fprintf(stderr, "DflTimeStep: the level-set volume correction is single-GPU only; the solver has a communicator: step refused\n");
         return -1;
     }
+    if (DflSolidificationInTimeStep(mesh) && KrylovGetComm(ksp)) {
+        fprintf(stderr, "DflTimeStep: the solidification record is single-GPU only; the solver has a communicator: step refused\n");
+        return -1;
+    }
     DflRangePush("DflTimeStep");
+    /* the solidification record (in_time_step), not primed yet: T_prev is the incoming T, so that this step is booked */
+    DflSolidificationTimeStepPrime(mesh, wgold);
     /* every every-th step (DflMeshSetRedistance): phi of wgold becomes the band distance again before the surface load, the
        phase change and the solve look at it */
     DflRedistanceTimeStep(mesh, wgold);
@@ -254,6 +262,7 @@ index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* 
     if (pctx && !coupled)
         for (index_type k = 0; k < dem_substeps; ++k) ParticleContextUpdate(pctx); /* coupled step: contact sweep (config 4) */
     dfl_alpha_correct(N, fac_corr[0], fac_corr[1], wgold, dwgold, dwg, s);
+    DflSolidificationTimeStep(mesh, wgold); /* the record of this step (in_time_step); reads wgold only */
     if (coupled) DflLaserSurfaceTimeStep(pctx, wgold); /* the laser's snapshot of phi = level; a no-op unless a surface is set */
     if (coupled)
         for (index_type k = 0; k < dem_substeps; ++k) ParticleContextFluidStep(pctx, wgold); /* u at t_{n+1} */

@@ -84,6 +84,7 @@ typedef struct MeshExt {
     struct FluidState* fluid;      /* fluid material (host/fluid.c, DflMeshSetFluidMaterial), NULL: off */
     struct RedistanceState* redistance; /* level-set redistancing (host/redistance.c, DflMeshSetRedistance), NULL: off */
     struct VolumeState* volume;    /* level-set volume correction (host/volume.c, DflMeshSetVolumeCorrection), NULL: off */
+    struct SolidifyState* solidify; /* solidification record (host/solidify.c, DflMeshSetSolidification), NULL: off */
     index_type *v2e_row, *v2e_col; /* device [N+1], [4T]: the sorted V2E map (DflMeshSortedV2E), NULL until first asked for */
 } MeshExt;
 
@@ -460,6 +461,16 @@ b32 DflVolumeCorrectionInTimeStep(const Mesh3D* mesh);         /* a configuratio
 void DflVolumeCorrectionTimeStep(Mesh3D* mesh, f64* wgold);
 /* with track_capture: the target grows by side * time * sum q_vol (device [N]); sums on the device and waits for it */
 void DflVolumeCorrectionCaptured(Mesh3D* mesh, const f64* q_vol, f64 time);
+/* host/solidify.c: the solidification record of a mesh (no-ops while it is off) */
+struct SolidifyState;
+void DflSolidificationFree(struct SolidifyState* st);
+b32 DflSolidificationInTimeStep(const Mesh3D* mesh);            /* a configuration with in_time_step is set */
+/* DflTimeStep, on entry: with in_time_step and a record not primed yet, the priming update at the incoming wgold */
+void DflSolidificationTimeStepPrime(Mesh3D* mesh, const f64* wgold);
+/* DflTimeStep, once the step has written wgold: with in_time_step, DflMeshSolidificationUpdate(mesh, wgold, kDT) */
+void DflSolidificationTimeStep(Mesh3D* mesh, const f64* wgold);
+/* T_prev [N] and the metal flags [N] of the record on the device (tests, probes); NULL when not set */
+void DflSolidificationTestFields(const Mesh3D* mesh, const f64** T_prev, const u8** metal);
 
 /* named ranges for rocprofv3 --marker-trace (DFL_ROCTX=1); no-ops otherwise */
 void DflRangePush(const char* name);

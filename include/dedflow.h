@@ -1711,6 +1711,87 @@ f64  DflMeshVolumeCorrectionTarget(const Mesh3D* mesh);
 void DflMeshVolumeCorrectionSetTarget(Mesh3D* mesh, f64 volume);
 void DflMeshVolumeCorrectionAddTarget(Mesh3D* mesh, f64 dV); /* dV of {phi > level} */
 
+/* ---- solidification record: gradient, cooling rate and front speed per node (build-defined; opt-in) ----------------------
+ * The phase-change statistics are a snapshot of the pool; nothing there survives the step in which a node crosses the
+ * freezing isotherm.  This section keeps, per node, how the node froze the last time: when, how fast it cooled and the thermal
+ * gradient G at that moment (the front speed R = cooling rate / |G|; G / R and G R say what grains to expect), and besides
+ * the peak temperature, the time spent liquid and the number of remelts.  It is passive: it reads the state and never writes
+ * it, so a mesh computes bit for bit the same flow with it on, and a mesh that never calls DflMeshSetSolidification with a
+ * configuration, or clears it with NULL, runs the launches it runs without this section.  One GPU only.
+ *   record      per node a: T_prev (NaN until primed), T_peak (-inf), t_liquid (0), melts (0, index_type), t_solid (NaN: no
+ *               record), cool (0), grad3[3a + d] (0); the metal flag of the node as its last update saw it; on the host the
+ *               elapsed time t (0) and the number of updates.  DflMeshSetSolidification and DflMeshSolidificationReset set
+ *               these initial values.
+ *   priming     the first Update after Set or Reset sets T_prev = T and T_peak = fmax(T_peak, T) for every node, leaves t as
+ *               it is, books no event (the event list is empty) and ignores dt, which must still be finite and positive.
+ *   update      every later one, with Tp = T_prev[a], Tn = w[5N + a], metal = !use_phi || side (w[4N + a] - level) > 0,
+ *               above_p = Tp >= T_front, above_n = Tn >= T_front:
+ *                 a NaN Tn leaves every entry of the node as it was, T_prev included;
+ *                 T_peak[a] = fmax(T_peak[a], Tn), metal or not;
+ *                 where metal: above at both ends adds dt to t_liquid; a freezing crossing (above_p && !above_n) adds
+ *                 theta dt, theta = (Tp - T_front) / (Tp - Tn); a melting crossing (!above_p && above_n) adds
+ *                 (1 - (T_front - Tp) / (Tn - Tp)) dt.  Every product is rounded before the add (no fused multiply-add);
+ *                 freeze event (metal && above_p && !above_n): t_solid = t + theta dt, cool = (Tp - Tn) / dt, grad3 = the
+ *                 recovered gradient below at w; the node enters the event list;
+ *                 melt event (metal && !above_p && above_n): melts += 1, t_solid = NaN, cool = 0, grad3 = 0: a remelted
+ *                 node has no record until it freezes again;
+ *                 T_prev[a] = Tn.
+ *               After the launches t += dt on the host.  A node primed with a NaN has a NaN T_prev: it compares as below
+ *               the isotherm, and a melt event from it makes t_liquid NaN.
+ *   gradient    of node a, over the tets e of its sorted list (ascending tet id): det and the cross products of the edge
+ *               vectors in the closed form the free-surface and phase-change sections use (without fused multiply-add),
+ *               gN_1 = c23 / det, gN_2 = c31 / det, gN_3 = c12 / det, gN_0 = -((gN_1 + gN_2) + gN_3), each component
+ *               divided on its own; g_e[d] = ((T_0 gN_0[d] + T_1 gN_1[d]) + T_2 gN_2[d]) + T_3 gN_3[d].  A tet adds nothing
+ *               if !(|det| > 0), or with use_phi if side (mean phi - level) > 0 is false, mean = ((phi_0 + phi_1) +
+ *               (phi_2 + phi_3)) * 0.25.  S_d = sum |det_e| g_e[d] and V = sum |det_e|, each in ascending tet id from +0.0;
+ *               grad3[3a + d] = V > 0 ? S_d / V : 0: the volume-weighted mean of the tet gradients, exact for a linear T.
+ *   front speed not stored: R = |G| > 0 ? cool / |G| : 0, |G| = sqrt((g0 g0 + g1 g1) + g2 g2).
+ *   statistics  time = t, updates = accepted Update calls since Set or Reset (the priming one included), frozen = nodes with
+ *               a record (t_solid not NaN), liquid = nodes with the metal flag and T_prev >= T_front, the event counts of the
+ *               last update, minimum and maximum of |G|, cool and R over the records (a NaN is passed over), T_peak_max over
+ *               the nodes with the metal flag (a NaN is passed over); in a fixed two-stage order.  An empty set gives count 0,
+ *               minimum +inf, maximum -inf.
+ *   time step   with in_time_step, DflTimeStep calls DflMeshSolidificationUpdate(mesh, wgold, kDT) once the step has
+ *               written wgold.  The first DflTimeStep after Set or Reset first primes the record at its incoming wgold, so
+ *               that its own step is already booked.  With a communicator DflTimeStep prints why and returns -1.
+ * Every sum has a fixed order and no float atomic is used: two runs agree bit for bit, under every assembly schedule.  An
+ * Update is five launches and one 4-byte copy to pinned host memory; it allocates nothing and does not wait for the device.
+ * The geometry is read on every call: DflMeshGeometryChanged needs nothing here. */
+typedef struct DflSolidification {
+    f64 T_front;                                /* the freezing isotherm (typically T_solidus or T_liquidus) */
+    b32 use_phi; f64 level; index_type side;    /* metal where side (phi - level) > 0; use_phi 0: metal everywhere */
+    b32 in_time_step;                           /* DflTimeStep updates the record itself */
+} DflSolidification;
+typedef struct DflSolidificationStats {
+    f64 time;                                   /* elapsed time t */
+    int64_t updates;                            /* accepted Update calls since Set or Reset */
+    int64_t frozen, liquid;                     /* nodes with a record; metal nodes with T_prev >= T_front */
+    int64_t freeze_events_last, melt_events_last;
+    f64 G_min, G_max, cool_min, cool_max, R_min, R_max; /* over the records */
+    f64 T_peak_max;                             /* over the metal nodes */
+} DflSolidificationStats;
+/* host only: 0 when DflMeshSetSolidification accepts the configuration, else why not in `why`: T_front or level not finite,
+ * use_phi with side not +-1 */
+int  DflSolidificationCheck(const DflSolidification* cfg, char* why, size_t why_len);
+/* the configuration is copied; NULL: off, frees everything of its own (the sorted tet lists of the nodes are the mesh's and
+ * stay).  A refused configuration is reported on stderr and leaves the mesh and the record as they were.  Has the mesh build
+ * the sorted tet lists if nothing did before, builds every buffer and sets the record to its initial values (synchronises) */
+void DflMeshSetSolidification(Mesh3D* mesh, const DflSolidification* cfg);
+b32  DflMeshSolidificationEnabled(const Mesh3D* mesh);
+/* w: device 6N state at the END of a step of length dt.  Without a configuration, or with a dt that is not finite or not
+ * positive: a line on stderr, nothing changed */
+void DflMeshSolidificationUpdate(Mesh3D* mesh, const f64* w, f64 dt);
+/* records to their initial values, time 0, unprimed */
+void DflMeshSolidificationReset(Mesh3D* mesh);
+/* borrowed device arrays, valid until the feature is cleared or the mesh destroyed: t_solid, cool, T_peak, t_liquid [N],
+ * grad3 [3N], melts [N]; any out pointer NULL.  Without a configuration every pointer asked for comes back NULL */
+void DflMeshSolidificationFields(const Mesh3D* mesh, const f64** t_solid, const f64** grad3, const f64** cool,
+                                 const f64** T_peak, const f64** t_liquid, const index_type** melts);
+/* device list of the nodes frozen by the last update, ascending; returns its length (synchronises); 0 and NULL when not set */
+index_type DflMeshSolidificationEvents(const Mesh3D* mesh, const index_type** nodes);
+/* synchronises, reads 88 bytes back; without a configuration: a line on stderr, the empty-set values */
+void DflMeshSolidificationStats(Mesh3D* mesh, DflSolidificationStats* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1098,6 +1098,43 @@ void dfl_volume_eval(dfl_index nband, const dfl_index* list, const dfl_index* ie
 void dfl_volume_shift(dfl_index N, dfl_value* w, dfl_value delta, void* stream);
 void dfl_volume_node_sum(dfl_index N, const dfl_value* q, dfl_value* work, dfl_value* out1, void* stream);
 
+/* ---- solidification record (build-defined, opt-in; host/solidify.c, csrc/k_solidify.hip, model in include/dedflow.h)
+ * The record arrays: T_prev, T_peak, t_liquid, t_solid, cool [N], grad3 [3N], melts [N] integers, metal [N] bytes (the metal
+ * flag of every node as its last update saw it).  nblk = ceil(N / dfl_tets_per_block()) workgroups of the per-node kernels.
+ *    dfl_solid_reset     the initial values: T_prev NaN, T_peak -inf, t_solid NaN, everything else 0
+ *    dfl_solid_prime     T_prev = T, T_peak = fmax(T_peak, T), metal, of the state w [6N]
+ *    dfl_solid_count     the freeze and melt events of an update of w as two counts per workgroup, blk_count and melt_count
+ *                        [nblk]; writes nothing else.  The caller scans blk_count into blk_base [nblk + 1] (dfl_scan_counts)
+ *    dfl_solid_events    the same decision again and every elementwise rule of the update of length dt at the elapsed time t;
+ *                        the freeze-event nodes into list [N] in ascending order, blk_base[nblk] of them
+ *    dfl_solid_gradient  grad3[3a + d] of the first *count nodes of list: a group of 16 lanes per listed node walks the node's
+ *                        sorted V2E list, a lane per tet, four sums per node in list order through LDS.  The grid strides
+ *                        over the list and reads count on the device.  No atomics: bitwise reproducible
+ *    dfl_solid_stats     out11 = (frozen, liquid, freeze events, melt events, G_min, G_max, cool_min, cool_max, R_min, R_max,
+ *                        T_peak_max) in a fixed two-stage order; freeze_total: the device word that holds the list length;
+ *                        work >= dfl_solid_stats_work_size() doubles
+ * Every launcher returns at once for N <= 0. */
+typedef struct dfl_solid_params {
+    dfl_value T_front, level, side;
+    int use_phi;
+} dfl_solid_params;
+void dfl_solid_reset(dfl_index N, dfl_value* T_prev, dfl_value* T_peak, dfl_value* t_liquid, dfl_index* melts, dfl_value* t_solid,
+                     dfl_value* cool, dfl_value* grad3, unsigned char* metal, void* stream);
+void dfl_solid_prime(dfl_index N, const dfl_value* w, const dfl_solid_params* prm, dfl_value* T_prev, dfl_value* T_peak,
+                     unsigned char* metal, void* stream);
+void dfl_solid_count(dfl_index N, const dfl_value* w, const dfl_solid_params* prm, dfl_value dt, const dfl_value* T_prev,
+                     dfl_index* blk_count, dfl_index* melt_count, void* stream);
+void dfl_solid_events(dfl_index N, const dfl_value* w, const dfl_solid_params* prm, dfl_value t, dfl_value dt,
+                      const dfl_index* blk_base, dfl_value* T_prev, dfl_value* T_peak, dfl_value* t_liquid, dfl_index* melts,
+                      dfl_value* t_solid, dfl_value* cool, dfl_value* grad3, unsigned char* metal, dfl_index* list, void* stream);
+void dfl_solid_gradient(dfl_index N, const dfl_index* count, const dfl_index* list, const dfl_index* vrow, const dfl_index* vcol,
+                        const dfl_index* ien, const dfl_value* xg, const dfl_value* w, const dfl_solid_params* prm,
+                        dfl_value* grad3, void* stream);
+dfl_index dfl_solid_stats_work_size(void);
+void dfl_solid_stats(dfl_index N, dfl_value T_front, const dfl_value* T_prev, const dfl_value* T_peak, const dfl_value* t_solid,
+                     const dfl_value* cool, const dfl_value* grad3, const unsigned char* metal, dfl_index nblk,
+                     const dfl_index* freeze_total, const dfl_index* melt_count, dfl_value* work, dfl_value* out11, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
