@@ -743,6 +743,18 @@ class DflSolidificationStats(C.Structure):
                 ("T_peak_max", C.c_double)]
 
 
+class DflTrackSections(C.Structure):
+    _fields_ = [("origin", C.c_double * 3), ("normal", C.c_double * 3), ("up", C.c_double * 3), ("num_station", C.c_int32),
+                ("station", C.c_double * 64), ("level", C.c_double), ("side", C.c_int32), ("T_fuse", C.c_double),
+                ("every", C.c_int32)]
+
+
+class DflTrackSection(C.Structure):
+    _fields_ = [("area_clad", C.c_double), ("area_fused", C.c_double), ("area_scale", C.c_double), ("height", C.c_double),
+                ("depth", C.c_double), ("y_lo_clad", C.c_double), ("y_hi_clad", C.c_double), ("y_lo_fused", C.c_double),
+                ("y_hi_fused", C.c_double), ("pairs", C.c_int64), ("dilution", C.c_double)]
+
+
 class DflComm(C.Structure):
     _fields_ = [("allreduce_sum", ALLREDUCE_FN), ("halo_exchange", HALO_FN), ("ctx", vp), ("num_owned_node", C.c_int32),
                 ("halo_begin", HALO_FN), ("halo_end", HALO_FN), ("num_interior_node", C.c_int32),
@@ -948,8 +960,30 @@ def _declare(L):
     f("DflMeshSolidificationFields", None, [C.POINTER(Mesh3D)] + 6 * [C.POINTER(vp)])
     f("DflMeshSolidificationEvents", i32, [C.POINTER(Mesh3D), C.POINTER(vp)])
     f("DflMeshSolidificationStats", None, [C.POINTER(Mesh3D), C.POINTER(DflSolidificationStats)])
+    f("DflTrackSectionsCheck", C.c_int, [C.POINTER(DflTrackSections), C.c_char_p, C.c_size_t])
+    f("DflMeshSetTrackSections", None, [C.POINTER(Mesh3D), C.POINTER(DflTrackSections)])
+    f("DflMeshTrackSectionsEnabled", i32, [C.POINTER(Mesh3D)])
+    f("DflMeshTrackSectionsStations", i32, [C.POINTER(Mesh3D)])
+    f("DflMeshTrackSections", None, [C.POINTER(Mesh3D), vp, vp])
+    f("DflMeshTrackSectionsResult", None, [C.POINTER(Mesh3D), C.POINTER(DflTrackSection)])
+    f("DflTrackSectionsTestPairs", i32, [C.POINTER(Mesh3D), C.POINTER(vp), C.POINTER(i32)])
+    f("DflTrackSectionsTestCapacity", None, [C.POINTER(Mesh3D), C.POINTER(i32), C.POINTER(i32)])
     f("GenerateRandomColor", None, [vp, i32, i32])
     f("dfl_abi_version", C.c_int, [])
+
+
+def track_sections_config(stations, origin=(0.0, 0.0, 0.0), normal=(1.0, 0.0, 0.0), up=(0.0, 0.0, 1.0), level=0.0, side=1,
+                          T_fuse=0.0, every=0, num_station=None):
+    """a DflTrackSections; num_station: what the structure claims where that is not len(stations) (the refusals)"""
+    st = [float(c) for c in stations]
+    cfg = DflTrackSections()
+    for k in range(3):
+        cfg.origin[k], cfg.normal[k], cfg.up[k] = float(origin[k]), float(normal[k]), float(up[k])
+    cfg.num_station = len(st) if num_station is None else int(num_station)
+    for k, c in enumerate(st[:64]):
+        cfg.station[k] = c
+    cfg.level, cfg.side, cfg.T_fuse, cfg.every = float(level), int(side), float(T_fuse), int(every)
+    return cfg
 
 
 BC_STRONG = 1
@@ -1441,6 +1475,44 @@ class Problem:
         lib().DflMeshSolidificationStats(self.mesh, C.byref(s))
         ints = ("updates", "frozen", "liquid", "freeze_events_last", "melt_events_last")
         return {k: (int if k in ints else float)(getattr(s, k)) for k, _ in DflSolidificationStats._fields_}
+
+    # ---- track cross-sections (include/dedflow.h, "track cross-sections") ------------------------------------------------------
+    def set_track_sections(self, stations=None, origin=(0.0, 0.0, 0.0), normal=(1.0, 0.0, 0.0), up=(0.0, 0.0, 1.0), level=0.0,
+                           side=1, T_fuse=0.0, every=0):
+        """DflMeshSetTrackSections: the planes (x - origin) . n = stations[k] (at most 64, strictly ascending) across the scan
+        direction `normal`, with `up` the build direction and origin on the original substrate surface; metal where
+        side (phi - level) > 0, fused where T_peak >= T_fuse; every > 0: time_step evaluates on every every-th call.  stations
+        None turns the feature off.  A configuration the library refuses (reported on stderr) leaves the mesh as it was:
+        track_sections_on tells."""
+        if stations is None:
+            lib().DflMeshSetTrackSections(self.mesh, None)
+            return
+        lib().DflMeshSetTrackSections(self.mesh, C.byref(track_sections_config(stations, origin, normal, up, level, side, T_fuse,
+                                                                             every)))
+
+    @property
+    def track_sections_on(self):
+        return bool(lib().DflMeshTrackSectionsEnabled(self.mesh))
+
+    def _need_track_sections(self):
+        if not self.track_sections_on:
+            raise RuntimeError("no track sections are set: call set_track_sections first")
+
+    def track_sections(self, w, T_peak=None):
+        """DflMeshTrackSections at the state w (DeviceArray of 6N, or a device pointer); T_peak: a DeviceArray of N or a device
+        pointer, None: the solidification record's when one is set, else nothing is fused.  Returns track_sections_result()"""
+        self._need_track_sections()
+        lib().DflMeshTrackSections(self.mesh, getattr(w, "ptr", w), getattr(T_peak, "ptr", T_peak))
+        return self.track_sections_result()
+
+    def track_sections_result(self):
+        """DflMeshTrackSectionsResult: one dict per station of the last evaluation (synchronises): area_clad, area_fused,
+        area_scale, height, depth, y_lo_clad, y_hi_clad, y_lo_fused, y_hi_fused, pairs, dilution"""
+        self._need_track_sections()
+        out = (DflTrackSection * 64)()
+        lib().DflMeshTrackSectionsResult(self.mesh, out)
+        return [{k: (int if k == "pairs" else float)(getattr(r, k)) for k, _ in DflTrackSection._fields_}
+                for r in out[:int(lib().DflMeshTrackSectionsStations(self.mesh))]]
 
     def close(self):
         L = lib()

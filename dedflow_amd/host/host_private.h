@@ -85,6 +85,7 @@ typedef struct MeshExt {
     struct RedistanceState* redistance; /* level-set redistancing (host/redistance.c, DflMeshSetRedistance), NULL: off */
     struct VolumeState* volume;    /* level-set volume correction (host/volume.c, DflMeshSetVolumeCorrection), NULL: off */
     struct SolidifyState* solidify; /* solidification record (host/solidify.c, DflMeshSetSolidification), NULL: off */
+    struct TrackState* track;      /* track cross-sections (host/track.c, DflMeshSetTrackSections), NULL: off */
     index_type *v2e_row, *v2e_col; /* device [N+1], [4T]: the sorted V2E map (DflMeshSortedV2E), NULL until first asked for */
 } MeshExt;
 
@@ -471,6 +472,18 @@ void DflSolidificationTimeStepPrime(Mesh3D* mesh, const f64* wgold);
 void DflSolidificationTimeStep(Mesh3D* mesh, const f64* wgold);
 /* T_prev [N] and the metal flags [N] of the record on the device (tests, probes); NULL when not set */
 void DflSolidificationTestFields(const Mesh3D* mesh, const f64** T_prev, const u8** metal);
+/* host/track.c: the track cross-sections of a mesh (no-ops while they are off) */
+struct TrackState;
+void DflTrackSectionsFree(struct TrackState* st);
+b32 DflTrackSectionsInTimeStep(const Mesh3D* mesh);             /* a configuration with every > 0 is set */
+/* DflTimeStep, once the step has written wgold: counts the call; on every every-th since the Set call
+ * DflMeshTrackSections(mesh, wgold, NULL) */
+void DflTrackSectionsTimeStep(Mesh3D* mesh, const f64* wgold);
+/* the pair list of the last evaluation on the device (tet ids, by station, then ascending) and its 65 segment offsets:
+ * station k owns [off65[k], off65[k + 1]), every entry from num_station on is the total, which is returned (synchronises;
+ * tests, probes) */
+index_type DflTrackSectionsTestPairs(const Mesh3D* mesh, const index_type** list, index_type* off65);
+void DflTrackSectionsTestCapacity(const Mesh3D* mesh, index_type* cap_list, index_type* cap_part);
 
 /* named ranges for rocprofv3 --marker-trace (DFL_ROCTX=1); no-ops otherwise */
 void DflRangePush(const char* name);

@@ -104,6 +104,7 @@ void Mesh3DDestroy(Mesh3D* m) {
         DflRedistanceFree(x->redistance);
         DflVolumeCorrectionFree(x->volume);
         DflSolidificationFree(x->solidify);
+        DflTrackSectionsFree(x->track);
         CdamFreeDevice(x->v2e_row, 0); /* after the feature states that borrowed it */
         CdamFreeDevice(x->v2e_col, 0);
         CdamFreeDevice(x->egeo_b, 0);

@@ -1792,6 +1792,88 @@ index_type DflMeshSolidificationEvents(const Mesh3D* mesh, const index_type** no
 /* synchronises, reads 88 bytes back; without a configuration: a line on stderr, the empty-set values */
 void DflMeshSolidificationStats(Mesh3D* mesh, DflSolidificationStats* out);
 
+/* ---- track cross-sections: bead height, width, depth and dilution per station (build-defined; opt-in) -------------------------
+ * What a DED experiment measures on a cut and polished sample: the bead above the original substrate surface, the fused zone
+ * below it, their areas and the ratio of the two, the dilution.  The phase-change statistics are a box around what is molten
+ * now and the solidification statistics are extrema over nodes; neither is geometry.  This section cuts the mesh on the device
+ * by up to 64 parallel planes.  It is passive: it reads the state and never writes it, so a mesh computes bit for bit the same
+ * flow with it on, and a mesh that never calls DflMeshSetTrackSections with a configuration, or clears it with NULL, runs the
+ * launches it runs without this section.  One GPU only.
+ *   frame       n = normal / sqrt((n0 n0 + n1 n1) + n2 n2), the scan direction; u = up - (up . n) n, divided by its own length
+ *               formed the same way, the build direction; t = u x n (t0 = u1 n2 - u2 n1, cyclic).  Every dot product is
+ *               (a0 b0 + a1 b1) + a2 b2 and every product is rounded before it is added (no fused multiply-add), as in the
+ *               laser section.  Station k is the plane (x - origin) . n = c_k, c = station, strictly ascending.
+ *   nodes       with d = x_a - origin formed first: s_a = d . n, y_a = d . t, h_a = d . u; f_a = phi_a - level, negated for
+ *               side = -1: metal where f > 0; g_a = Tpk_a - T_fuse: fused where g >= 0.  h = 0 is the original substrate
+ *               surface: origin lies on it.
+ *   pairs       tet e and station k form a pair when the mask of sigma_a = s_a - c_k > 0 over the tet's four nodes is neither
+ *               0 nor 15 (a NaN is not positive) and at least one f_a > 0.  So a station that lies exactly on a plane of nodes
+ *               sees the tets on its positive side, once, and a station on the far boundary of the mesh sees nothing.  The
+ *               pair list is ordered by station, then by tet id.
+ *   cut         of one pair: the facets of the surface sigma = 0 in the tet as the redistancing section makes them (one
+ *               positive node i: P_ij, j over the three others in local order; three: P_ij, i over the positives in local
+ *               order; two, a < b, the others c < d: the quad P_ac, P_ad, P_bd, P_bc as (0, 1, 2) and (0, 2, 3)).  Vertex P_ij
+ *               has tt = sigma_i / (sigma_i - sigma_j) and carries q_i + tt (q_j - q_i) for each q of (y, h, f, g); (y, h) are
+ *               its coordinates in the station's plane.
+ *   clip        Sutherland-Hodgman on a polygon of carried vertices against inside(q): walking the edges U -> V in order (the
+ *               last V is vertex 0), U goes out when it is inside, then, when exactly one of U, V is inside, the crossing
+ *               A + tau (B - A) from the inside vertex A towards the outside B, tau = q_A / (q_A - q_B), for all four
+ *               quantities.  metal = the triangle clipped by f > 0 (at most 4 vertices); clad = metal clipped by h > 0 (at
+ *               most 5); fused = metal clipped by !(h > 0) (5) and then by g >= 0 (6).  More vertices than that cannot come
+ *               out in exact arithmetic; where rounding makes one, it is dropped.
+ *   polygon     with at least 3 vertices: its area = the sum from +0.0, in fan order, of 0.5 |(y_k - y_0)(h_k+1 - h_0) -
+ *               (y_k+1 - y_0)(h_k - h_0)|, k = 1 .. n - 2, counted as 0 when it is a NaN; and the minima and maxima of its
+ *               vertices' y and h, where a NaN never wins a comparison.
+ *   result      per station: area_clad, area_fused = the sums of the polygon areas, area_scale = the sum of the uncut facets'
+ *               areas (the same fan); a pair adds its facets in their order from the pair's partial sum, and the pairs are
+ *               summed in a fixed tree over chunks of 256 consecutive pairs of the list (the xor tree inside every wave of
+ *               64, then waves 1, 2, 3 into wave 0), the chunks then by one workgroup (thread t takes chunks t, t + 256, ...;
+ *               then the same tree).  height = max h over the clad vertices, depth = max of -h over the fused vertices,
+ *               y_lo / y_hi of both.  An empty set gives +inf for a minimum and -inf for a maximum; a zero extent is +0.0.
+ *               pairs = the station's pairs; dilution = area_fused / (area_clad + area_fused) where that sum is > 0, else 0,
+ *               formed on the host.
+ *   T_peak      a device [N] array; NULL: the T_peak of the solidification record when one is set on the mesh; without one
+ *               every g is -inf and nothing is fused.
+ *   time step   with every > 0, DflTimeStep evaluates on every every-th call since the Set call, at the wgold it has just
+ *               written and after the solidification record's update of that step.  With a communicator it prints why and
+ *               returns -1.
+ * No atomics, on floats or on integers; the list order does not depend on arrival: two evaluations agree bit for bit.  Limits:
+ * one normal for all stations; a NaN in a tet's numbers costs the station that tet's share of the areas, nothing else; the
+ * pairs of all stations together must stay below 2^31. */
+typedef struct DflTrackSections {
+    f64 origin[3], normal[3], up[3];            /* a point of the substrate surface, the scan direction, the build direction */
+    index_type num_station;                     /* 1 .. 64 */
+    f64 station[64];                            /* the offsets c_k along n, strictly ascending */
+    f64 level; index_type side;                 /* metal where side (phi - level) > 0 */
+    f64 T_fuse;                                 /* fused where T_peak >= T_fuse */
+    index_type every;                           /* > 0: DflTimeStep evaluates on every every-th call; 0: never */
+} DflTrackSections;
+typedef struct DflTrackSection {
+    f64 area_clad, area_fused;                  /* metal above / fused metal at or below h = 0 */
+    f64 area_scale;                             /* the station's whole cut through its pairs' tets: the parity scale */
+    f64 height, depth;                          /* max h of the clad, max -h of the fused */
+    f64 y_lo_clad, y_hi_clad, y_lo_fused, y_hi_fused;
+    int64_t pairs;
+    f64 dilution;
+} DflTrackSection;
+/* host only: 0 when DflMeshSetTrackSections accepts the configuration, else why not in `why`: an entry of origin, normal or up
+ * that is not finite, a normal without length, an up parallel to the normal, num_station outside 1 .. 64, a station that is not
+ * finite or does not ascend strictly, a level or T_fuse that is not finite, side not +-1, every < 0 */
+int  DflTrackSectionsCheck(const DflTrackSections* cfg, char* why, size_t why_len);
+/* the configuration is copied; NULL: off, frees everything of its own.  A refused configuration is reported on stderr and
+ * leaves the mesh as it was.  Builds every buffer but the lists, forgets the last evaluation and restarts the count of time
+ * steps (synchronises) */
+void DflMeshSetTrackSections(Mesh3D* mesh, const DflTrackSections* cfg);
+b32  DflMeshTrackSectionsEnabled(const Mesh3D* mesh);
+index_type DflMeshTrackSectionsStations(const Mesh3D* mesh); /* num_station of the configuration; 0 when not set */
+/* w: the device 6N state; T_peak: device [N] or NULL (above).  Waits for the device once, for the pair counts; the pair list
+ * and the reduction records grow when a count exceeds their capacity and the call allocates nothing otherwise.  The geometry
+ * is read on every call: DflMeshGeometryChanged needs nothing here.  Without a configuration: a line on stderr */
+void DflMeshTrackSections(Mesh3D* mesh, const f64* w, const f64* T_peak);
+/* synchronises and writes the num_station results of the last evaluation; before the first one every station has no pairs
+ * and the empty-set values.  Without a configuration: a line on stderr, out untouched */
+void DflMeshTrackSectionsResult(Mesh3D* mesh, DflTrackSection* out);
+
 #ifdef __cplusplus
 }
 #endif

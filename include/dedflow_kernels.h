@@ -1135,6 +1135,38 @@ void dfl_solid_stats(dfl_index N, dfl_value T_front, const dfl_value* T_prev, co
                      const dfl_value* cool, const dfl_value* grad3, const unsigned char* metal, dfl_index nblk,
                      const dfl_index* freeze_total, const dfl_index* melt_count, dfl_value* work, dfl_value* out11, void* stream);
 
+/* ---- track cross-sections (build-defined, opt-in; host/track.c, csrc/k_track.hip, model in include/dedflow.h)
+ * prm: the frame (o, n, t, u) as the host formed it, level, side (+-1.0), T_fuse and the num_station ascending offsets c.
+ * Workgroups of dfl_tets_per_block() tets, nblk of them; count [num_station nblk] and base [num_station nblk + 1] are
+ * station-major: entry k nblk + b belongs to station k and workgroup b.  No atomics; every sum has a fixed order.
+ *    dfl_track_count    count[k nblk + b] = pairs of station k among the tets of workgroup b.  A workgroup without a pair
+ *                       writes nothing: count is zero on entry (dfl_scan_counts leaves it so)
+ *    dfl_track_offsets  off65[k] = base[k nblk] for k < num_station, the total base[num_station nblk] from there on
+ *    dfl_track_emit     the same decisions again: the tet ids of station k into list[off65[k] ..) in ascending order.  Nothing is
+ *                       written at or beyond cap
+ *    dfl_track_eval     one thread per pair, grid (max_chunk, num_station) with max_chunk >= ceil(longest segment / 256): the
+ *                       DFL_TRACK_NSTAT components of every station (area_clad, area_fused, area_scale, height, depth,
+ *                       y_lo_clad, y_hi_clad, y_lo_fused, y_hi_fused) through part [num_station][max_chunk][DFL_TRACK_NSTAT]
+ *                       into out [num_station][DFL_TRACK_NSTAT]; T_peak NULL: every g is -inf.  A station without a pair gets
+ *                       0 for the sums, +inf for the minima, -inf for the maxima */
+#define DFL_TRACK_MAX_STATION 64
+#define DFL_TRACK_NSTAT 9
+typedef struct dfl_track_params {
+    dfl_value o[3], n[3], t[3], u[3];
+    dfl_value level, side, T_fuse;
+    dfl_index num_station;
+    dfl_value c[DFL_TRACK_MAX_STATION];
+} dfl_track_params;
+void dfl_track_count(dfl_index T, const dfl_index* ien, const dfl_value* xg, const dfl_value* w, dfl_index N,
+                     const dfl_track_params* prm, dfl_index nblk, dfl_index* count, void* stream);
+void dfl_track_offsets(dfl_index num_station, dfl_index nblk, const dfl_index* base, dfl_index* off65, void* stream);
+void dfl_track_emit(dfl_index T, const dfl_index* ien, const dfl_value* xg, const dfl_value* w, dfl_index N,
+                    const dfl_track_params* prm, dfl_index nblk, const dfl_index* base, dfl_index* list, dfl_index cap,
+                    void* stream);
+void dfl_track_eval(dfl_index max_chunk, const dfl_index* off65, const dfl_index* list, const dfl_index* ien, const dfl_value* xg,
+                    const dfl_value* w, dfl_index N, const dfl_value* T_peak, const dfl_track_params* prm, dfl_value* part,
+                    dfl_value* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
