@@ -601,6 +601,37 @@ class Particles:
         lib().ParticleContextCaptureStats(self.ctx, C.byref(st))
         return {"captured": int(st.captured), "last": int(st.last)}
 
+    # ---- solid-surface contact (build-defined; model in include/dedflow.h) -----------------------------------------
+    def set_surface_contact(self, level=0.0, side=1, T_solid=np.inf):
+        """ParticleContextSetSurfaceContact: every fluid_step also collides the particles with the surface phi = level (side
+        +1: metal where phi > level, -1: where phi < level) wherever the fluid has T_f < T_solid (inf: everywhere); level None
+        turns it off.  Needs couple.  A configuration the library refuses (reported on stderr) leaves the context as it was:
+        surface_contact_on tells."""
+        if level is None:
+            lib().ParticleContextSetSurfaceContact(self.ctx, None)
+            return
+        cfg = DflSurfaceContact(float(level), int(side), float(T_solid))
+        lib().ParticleContextSetSurfaceContact(self.ctx, C.byref(cfg))
+
+    @property
+    def surface_contact_on(self):
+        return bool(lib().DflParticleSurfaceContactOn(self.ctx))
+
+    def surface_contact_stats(self):
+        """dict last / buried (particles in contact / buried in the last sub-step) / total (particle-sub-steps in contact
+        since the configuration was set); waits for the device"""
+        st = DflSurfaceContactStats()
+        lib().ParticleContextSurfaceContactStats(self.ctx, C.byref(st))
+        return {"last": int(st.last), "buried": int(st.buried), "total": int(st.total)}
+
+    def _surface_contact_apply(self, w):
+        """the contact alone, as fluid_step runs it after compute_forces() and locate() (library-private, for tests)"""
+        lib().DflSurfaceContactApply(self.ctx, w.ptr)
+
+    def _surface_contact_no_early_exit(self):
+        """zero the bound behind the contact kernel's early exit (library-private, for the cost probe; same results)"""
+        lib().DflSurfaceContactTestNoEarlyExit(self.ctx)
+
     def arrays(self):
         """(coord, vel, acc) copied back from the device"""
         c = self.ctx.contents
@@ -641,6 +672,21 @@ class DflParticleCapture(C.Structure):
 
 class DflParticleCaptureStats(C.Structure):
     _fields_ = [("captured", C.c_int64), ("last", C.c_int32)]
+
+
+class DflSurfaceContact(C.Structure):
+    _fields_ = [("level", C.c_double), ("side", C.c_int32), ("T_solid", C.c_double)]
+
+
+class DflSurfaceContactStats(C.Structure):
+    _fields_ = [("last", C.c_int32), ("buried", C.c_int32), ("total", C.c_int64)]
+
+
+def surface_contact_check(level, side, T_solid):
+    """DflSurfaceContactCheck (host only): None when the library accepts the configuration, else the reason"""
+    why = C.create_string_buffer(160)
+    cfg = DflSurfaceContact(float(level), int(side), float(T_solid))
+    return None if lib().DflSurfaceContactCheck(C.byref(cfg), why, 160) == 0 else why.value.decode()
 
 
 class DflLaser(C.Structure):
@@ -906,6 +952,12 @@ def _declare(L):
     f("ParticleContextCaptureSource", None, [C.POINTER(ParticleContext), f64, vp, vp, vp])
     f("ParticleContextCaptureStats", None, [C.POINTER(ParticleContext), C.POINTER(DflParticleCaptureStats)])
     f("DflParticleCaptureOn", i32, [C.POINTER(ParticleContext)])
+    f("ParticleContextSetSurfaceContact", None, [C.POINTER(ParticleContext), C.POINTER(DflSurfaceContact)])
+    f("ParticleContextSurfaceContactStats", None, [C.POINTER(ParticleContext), C.POINTER(DflSurfaceContactStats)])
+    f("DflSurfaceContactCheck", C.c_int, [C.POINTER(DflSurfaceContact), C.c_char_p, C.c_size_t])
+    f("DflParticleSurfaceContactOn", i32, [C.POINTER(ParticleContext)])
+    f("DflSurfaceContactApply", None, [C.POINTER(ParticleContext), vp])
+    f("DflSurfaceContactTestNoEarlyExit", None, [C.POINTER(ParticleContext)])
     f("DflMeshSetVolumeSource", None, [C.POINTER(Mesh3D), vp]); f("DflMeshVolumeSource", vp, [C.POINTER(Mesh3D)])
     f("DflParticlePendingEnergy", vp, [C.POINTER(ParticleContext)]); f("DflParticleConductionRate", vp, [C.POINTER(ParticleContext)])
     f("SolveFlowSystem", i32, [C.POINTER(Mesh3D), vp, vp, vp, C.POINTER(Matrix), vp, vp, vp, vp, i32, i32, vp, vp])

@@ -17,6 +17,7 @@ constexpr uint64_t KEY_PARTNER = 0ull << 62;  // | partner particle id
 constexpr uint64_t KEY_WALL = 1ull << 62;     // | 2 axis + side (unit box) or plane id (mesh)
 constexpr uint64_t KEY_EDGE = 2ull << 62;     // | n0 << 31 | n1, n0 < n1
 constexpr uint64_t KEY_VERTEX = 3ull << 62;   // | node id
+constexpr uint64_t KEY_SURFACE = KEY_WALL | (1ull << 61);  // the surface phi = level (k_surface_contact.hip)
 
 __device__ __forceinline__ uint64_t edge_key(int n0, int n1) { return KEY_EDGE | ((uint64_t)n0 << 31) | (uint64_t)n1; }
 

@@ -30,10 +30,6 @@ __device__ __forceinline__ void fluid_velocity(const T* __restrict__ w, const lo
 
 namespace {
 
-__device__ __forceinline__ double interp(const double l[4], const double f[4]) {
-    return ((l[0] * f[0] + l[1] * f[1]) + l[2] * f[2]) + l[3] * f[3];
-}
-
 // POLY: mass and radius of particle i are m[i] and r[i]
 template <bool POLY>
 __global__ __launch_bounds__(BLK) void capture_flag_kernel(I P, const I* __restrict__ tet, const T* __restrict__ lambda,
@@ -60,7 +56,7 @@ __global__ __launch_bounds__(BLK) void capture_flag_kernel(I P, const I* __restr
 #pragma unroll
             for (int d = 0; d < 3; ++d) x[3 * b + d] = xg[3 * n[b] + d];
         }
-        const double phi_p = interp(l, phi), T_f = interp(l, tf);
+        const double phi_p = tet_interp(l, phi), T_f = tet_interp(l, tf);
         TetCross c;
         tet_cross(x, c);
         double g[3], gn, dist[4];  // the decision needs |g| only

@@ -1,4 +1,4 @@
-// The level-set geometry of one linear tet in closed form, shared by the capture decision (k_capture.hip), the free-surface
+// The level-set geometry of one linear tet in closed form, shared by the capture decision (k_capture.hip), the solid-surface contact (k_surface_contact.hip), the free-surface
 // band (k_surface.hip), the phase-change metal fraction (k_phase.hip) and the thermal material (thermal_coeff.hpp).  The
 // operation order is part of the model (two kernels must take the same decision from the same numbers, and the numpy models
 // reproduce it): every function switches
@@ -8,6 +8,12 @@
 #include "dfl_common.hpp"
 
 namespace {
+
+// I(f) = ((l_0 f_0 + l_1 f_1) + l_2 f_2) + l_3 f_3: a nodal field at a point with barycentric weights l
+__device__ __forceinline__ double tet_interp(const double* l, const double* f) {
+#pragma clang fp contract(off)
+    return ((l[0] * f[0] + l[1] * f[1]) + l[2] * f[2]) + l[3] * f[3];
+}
 
 struct TetCross {
     double c23[3], c31[3], c12[3], det;  // grad N_1 = c23 / det, grad N_2 = c31 / det, grad N_3 = c12 / det

@@ -44,6 +44,7 @@ void DflMeshGeometryChanged(Mesh3D* mesh) {
     if (!x) return;
     CdamFreeDevice(x->egeo_b, 0);
     x->egeo_b = NULL;
+    x->geom_epoch++; /* a coupled particle context's bound on |grad N| (host/surface_contact.c) is recomputed at its next use */
     DflRedistanceGeometryChanged(x->redistance); /* its cell grid covers the old bounding box */
     /* schedule 4 and the residual kernels recompute the geometry from the node records; the face lists hold no geometry,
        and the free-surface and phase-change states (host/surface.c, host/phase.c) hold connectivity only: their kernels read xg

@@ -130,10 +130,12 @@ void ParticleContextSetFluidCoupling(ParticleContext* ctx, Mesh3D* mesh, const D
     if (!mesh) {
         DflHeatCouplingChanged(ctx);
         DflCaptureCouplingChanged(ctx);
+        DflSurfaceContactCouplingChanged(ctx);
         return;
     }
     if (Mesh3DNumTet(mesh) <= 0) {
         fprintf(stderr, "ParticleContextSetFluidCoupling: the mesh has no tets; coupling stays off\n");
+        DflSurfaceContactCouplingChanged(ctx);
         return;
     }
     if (!c) {
@@ -162,6 +164,7 @@ void ParticleContextSetFluidCoupling(ParticleContext* ctx, Mesh3D* mesh, const D
     c->imp_time = 0.0;
     DflHeatCouplingChanged(ctx);
     DflCaptureCouplingChanged(ctx);
+    DflSurfaceContactCouplingChanged(ctx);
 }
 
 /* the thread -> particle map of the walk: the contact sweep's (cell, id) order when it has run since the particle count
@@ -199,6 +202,7 @@ void ParticleContextFluidStep(ParticleContext* ctx, const f64* w) {
     DflRangePush("ParticleContextFluidStep");
     ParticleContextComputeForces(ctx);
     ParticleContextLocate(ctx);
+    if (x->surface_contact) DflSurfaceContactApply(ctx, w); /* acc, alpha and the rows of the sweep above, before the drag */
     int slot = DflProfileBegin(DFL_TAG_SMALL + 3);
     /* particle-id order: the kernel's contiguous per-particle reads and writes outweigh the gather locality of the cell
        order (1M tets, 100k particles: 14.2 us in id order, 23.4 us in cell order; tools/probe_coupling.py) */

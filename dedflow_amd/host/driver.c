@@ -154,6 +154,8 @@ index_type SolveFlowSystem(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matr
  * With a volume correction set on the mesh with every > 0 (DflMeshSetVolumeCorrection), every every-th call then shifts phi of
  * wgold back to the target volume, after that redistancing and before anything else looks at phi; with its track_capture, a
  * step that took a pending two-way capture source adds the deposited volume to the target after its Newton solve.
+ * With a surface contact set on the coupled context (ParticleContextSetSurfaceContact) every one of those fluid sub-steps also
+ * collides the particles with the solid part of the surface phi = level, inside ParticleContextFluidStep: nothing here calls it.
  * With a laser surface set on the coupled context (ParticleContextSetLaserSurface), ParticleContextLaserSurfaceUpdate runs
  * once, before the first particle sub-step, in the state those sub-steps see.
  * With a solidification record set on the mesh with in_time_step (DflMeshSetSolidification), the record is updated with the

@@ -87,6 +87,7 @@ typedef struct MeshExt {
     struct SolidifyState* solidify; /* solidification record (host/solidify.c, DflMeshSetSolidification), NULL: off */
     struct TrackState* track;      /* track cross-sections (host/track.c, DflMeshSetTrackSections), NULL: off */
     index_type *v2e_row, *v2e_col; /* device [N+1], [4T]: the sorted V2E map (DflMeshSortedV2E), NULL until first asked for */
+    uint64_t geom_epoch;           /* counts DflMeshGeometryChanged: what a particle context derived from the coordinates is stale */
 } MeshExt;
 
 /* the generalized-alpha constants of the time integration (src/assemble.cu:23-27), textually those of csrc/asm_device.hpp */
@@ -169,6 +170,7 @@ typedef struct ParticleExt {
     struct HeatState* heat;                     /* particle heat transfer (host/heat.c), NULL when off */
     struct LaserState* laser;                   /* laser energy deposition (host/laser.c), NULL when off; needs heat */
     struct CaptureState* capture;               /* melt-pool capture (host/capture.c), NULL when off; needs the coupling */
+    struct SurfaceContactState* surface_contact; /* solid-surface contact (host/surface_contact.c), NULL when off; needs the coupling */
 } ParticleExt;
 /* the per-particle sizes of the kernels (all NULL, rmax 0 while x->radius == NULL: one size) */
 dfl_sizes DflSizes(const ParticleExt* x);
@@ -176,6 +178,9 @@ dfl_sizes DflSizes(const ParticleExt* x);
 void DflInflowRadii(const ParticleContext* ctx, f64* r_lo, f64* r_hi);
 /* the history of the next sweep (flips the ping-pong: call once per sweep); friction off: all NULL */
 dfl_contact_history DflFrictionHistory(ParticleExt* x);
+/* after a sweep, without flipping: the rows that sweep read as the previous ones, and the rows it wrote (with their counts) as
+ * the current ones, for a contact that appends to them (host/surface_contact.c); friction off: all NULL */
+dfl_contact_history DflFrictionHistoryCurrent(const ParticleExt* x);
 dfl_friction_law DflFrictionLaw(const ParticleContext* ctx);
 void DflFrictionClearHistory(ParticleContext* ctx); /* no-op when friction is off */
 /* the sweep's device workspace for P particles over nbin cell-list bins (count / cell_start [nbin + 1]); grows only */
@@ -367,6 +372,25 @@ b32 DflParticleCaptureOn(const ParticleContext* ctx);
 /* two_way and something pending: the source over `time` into the context's own buffers (heat NULL when nothing was captured
  * with heat on); FALSE and nothing done otherwise */
 b32 DflCaptureTakePending(ParticleContext* ctx, f64 time, f64** q_vol, f64** load, f64** q_heat);
+/* solid-surface contact (host/surface_contact.c) */
+typedef struct SurfaceContactState {
+    DflSurfaceContact cfg;
+    dfl_surface_counters* cnt;       /* device [1] */
+    dfl_surface_counters* host;      /* host [1]: where the Stats call copies them */
+    int cur;                         /* the parity the last launch counted into */
+    f64* grad_max;                   /* device [1]: >= |grad N_k| over the coupled mesh (dfl_surface_grad_max) */
+    uint64_t geom_epoch;             /* the mesh's geometry epoch grad_max was computed at */
+} SurfaceContactState;
+void DflSurfaceContactFree(ParticleContext* ctx);
+void DflSurfaceContactCopy(ParticleContext* dst, const ParticleContext* src);
+void DflSurfaceContactCouplingChanged(ParticleContext* ctx); /* SetFluidCoupling: uncoupled frees the state; a mesh keeps it */
+b32 DflParticleSurfaceContactOn(const ParticleContext* ctx);
+/* the contact alone, as ParticleContextFluidStep runs it between the locate and the drag (tests, probes call it by hand
+ * after ParticleContextComputeForces and ParticleContextLocate); a no-op when off */
+void DflSurfaceContactApply(ParticleContext* ctx, const f64* w);
+/* probes only: zeroes the bound, so that every located particle gathers T and the coordinates until the bound is next
+ * recomputed (a coupling or geometry change); results are the same */
+void DflSurfaceContactTestNoEarlyExit(ParticleContext* ctx);
 struct WallState;
 void DflWallsFree(struct WallState* w);
 /* the contact sweep against the mesh walls (ParticleContextComputeForces when walls are set) */

@@ -49,6 +49,7 @@ void ParticleContextDestroy(ParticleContext* ctx) {
         DflWallsFree(x->walls);
         ParticleContextSetFriction(ctx, NULL);
         DflCaptureFree(ctx);
+        DflSurfaceContactFree(ctx);
         DflFlowFree(ctx);
         ParticleContextSetSizes(ctx, NULL, NULL);
         DflLaserFree(ctx);
@@ -66,6 +67,7 @@ void ParticleContextCopy(ParticleContext* dst, const ParticleContext* src) {
     }
     DflHeatCopy(dst, src); /* the thermal state travels too */
     DflCaptureCopy(dst, src); /* the capture configuration (nothing pending) */
+    DflSurfaceContactCopy(dst, src); /* the surface-contact configuration (not the counters) */
     /* the sizes travel with the particles (the inflow radius range is configuration and stays) */
     const ParticleExt* xs = (const ParticleExt*)src->ext;
     ParticleExt* xd = (ParticleExt*)dst->ext;
@@ -241,6 +243,18 @@ dfl_contact_history DflFrictionHistory(ParticleExt* x) {
     h.new_count = x->hist_count[b];
     h.overflow = x->overflow;
     x->hist_cur = b;
+    return h;
+}
+
+dfl_contact_history DflFrictionHistoryCurrent(const ParticleExt* x) {
+    dfl_contact_history h = {NULL, NULL, NULL, NULL, NULL};
+    if (!x->omega) return h;
+    const int b = x->hist_cur, a = 1 - b;
+    h.old_row = x->hist[a];
+    h.old_count = x->hist_count[a];
+    h.new_row = x->hist[b];
+    h.new_count = x->hist_count[b];
+    h.overflow = x->overflow;
     return h;
 }
 

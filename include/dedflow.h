@@ -878,6 +878,7 @@ index_type ParticleContextWallDroppedCount(const ParticleContext* ctx);
  *                                             one history)
  *                2 << 62 | n0 << 31 | n1      mesh edge contact, node ids n0 < n1
  *                3 << 62 | node               mesh vertex contact
+ *                1 << 62 | 1 << 61            the surface phi = level ("solid-surface contact"; beyond every plane id)
  *              (a context has unit-box walls or mesh walls, never both, so the two wall keys do not meet.)
  *   capacity   at most DFL_DEM_MAX_HISTORY entries per particle, pairs and walls together, taken in the sweep's visit
  *              order (pairs, then walls).  A contact that finds no free entry gets its normal force and the tangential
@@ -1288,6 +1289,77 @@ void ParticleContextCaptureSource(ParticleContext* ctx, f64 time, f64* q_vol, f6
 void ParticleContextCaptureStats(const ParticleContext* ctx, DflParticleCaptureStats* out); /* zeros when off */
 void DflMeshSetVolumeSource(Mesh3D* mesh, const f64* q_vol);     /* device [N], m^3/s; NULL = none; must outlive registration */
 const f64* DflMeshVolumeSource(const Mesh3D* mesh);
+
+/* ---- solid-surface contact (build-defined; opt-in) ----------------------------------------------------------------------
+ * Particle walls are boundary faces of a mesh; the metal surface phi = level lies inside the mesh, and capture takes a
+ * particle that reaches it only where the fluid is molten.  With a surface contact set, every coupled sub-step
+ * (ParticleContextFluidStep, hence the coupled DEM sub-steps of DflTimeStep) also collides every particle with the implicit
+ * surface phi = level wherever the fluid there counts as solid.  A context that never calls ParticleContextSetSurfaceContact
+ * with a configuration, or clears it with NULL, computes bit for bit what it computes without this section, through the same
+ * launches.  The context must be coupled to a mesh (ParticleContextSetFluidCoupling).  One GPU only.  ParticleContextUpdate
+ * (the uncoupled step) never runs it.  No fused multiply-add anywhere; every dot product is (a0 b0 + a1 b1) + a2 b2.
+ *   where       inside ParticleContextFluidStep, after the contact sweep and ParticleContextLocate and before the drag and
+ *               the integration: one launch, one thread per particle.  It sees the positions, velocities and angular
+ *               velocities the sweep saw, the tets and weights of this sub-step's locate and the fluid state w of the call.
+ *   quantities  for particle i in tet t = tet_i >= 0: lambda_a, phi_p = I(w[4N + n_a]), T_f = I(w[5N + n_a]), the tet's
+ *               gradient g and |g| exactly as "melt-pool capture" defines them (the same device functions).  Then, with
+ *               r_i, m_i the particle's radius and mass (ParticleRadius / ParticleMass when monodisperse),
+ *                 f = phi_p - level,  q = -(side f),  s = q / |g|,  n_d = (-(side g_d)) / |g|:
+ *               s is the centre's distance from the surface, positive on the gas side, and n the unit normal towards the
+ *               gas, that is, towards the particle.  side is +-1, so q and side g_d carry no rounding.
+ *   decision    contact iff t >= 0, |g| > 0, -r_i < s < r_i and T_f < T_solid.  A NaN anywhere compares false: no contact.
+ *               Tets -1 and -2: no contact.  s <= -r_i with the other conditions true is "buried": no force, as the walls
+ *               treat a centre further than R behind a face; it is counted.  With T_solid equal to capture's T_melt exactly
+ *               one of contact and capture applies to a particle that touches the surface.
+ *   normal law  that of the pairs and walls, the wall at rest, not clamped:
+ *                 delta = r_i - s,  v_n = (v_0 n_0 + v_1 n_1) + v_2 n_2,  f_n = kn delta - gamma_n v_n
+ *               with kn, gamma_n of ParticleContextSetContactModel.
+ *   friction    off: F_d = f_n n_d.  On (ParticleContextSetFriction): the law of "contact friction and particle rotation"
+ *               for a wall at rest, by the sweeps' own device function, with lever ell = max(r_i - delta, 0), v = v_i,
+ *               w = omega_i; F_d = f_n n_d + F_t,d and torque tau = (-ell n) x F_t.  The history key is
+ *                 1 << 62 | 1 << 61             the surface phi = level
+ *               which no plane id (31 bits) and no unit-box wall can equal.  The spring is looked up in the row the previous
+ *               sweep left (which holds the surface entry of the previous sub-step) and the new entry is appended to the
+ *               row this sub-step's sweep wrote, behind the sweep's entries; the capacity and the overflow rule are those
+ *               of that section (a full row: the force of a new contact, nothing stored, counted).  The entry is dropped by
+ *               the first sweep after the particle has left the surface.  ParticleContextRemove leaves the key alone, as it
+ *               does the wall keys.
+ *   result      acc_d <- acc_d + F_d (1 / m_i), and with friction alpha_d <- alpha_d + tau_d (1 / I_i), I_i = 2/5 m_i r_i^2
+ *               as that section evaluates it, added to what the sweep wrote.  A particle without contact is not written:
+ *               its acc, alpha and history row keep the sweep's bits.
+ *   energy      the contact is adiabatic, as the walls are, and exerts no reaction on the fluid: the solid metal is held by
+ *               the mushy-zone drag of "phase change", not by the particles.
+ *   geometry    the contact is exact for a distance-like phi that is linear in the centre's tet: phi is extrapolated
+ *               linearly from the centre's tet over the distance r_i, the approximation capture's `reach` already makes;
+ *               "level-set redistancing" keeps it good.
+ *   stats       integer counters on the device, at most one atomic per wave, read only by
+ *               ParticleContextSurfaceContactStats (which waits for the device): `last` and `buried` of the last sub-step,
+ *               `total` = particle-sub-steps in contact since the configuration was last set.
+ *   travel      ParticleContextSetFluidCoupling with NULL frees the state; coupling to another mesh keeps the configuration
+ *               and the counters; ParticleContextCopy carries the configuration to a coupled dst (not the counters).  A
+ *               sub-step allocates nothing and does not wait for the device; the state is sized at Set.  The kernel lets a
+ *               particle far on the gas side go before it gathers T and the coordinates, by a bound on |grad N| over the mesh
+ *               that never changes a decision; one pass over the tets computes it at Set, when the coupling changes and, as
+ *               a second launch, in the first sub-step after DflMeshGeometryChanged.
+ *   limits      not modelled: conduction between a resting particle and the substrate; a moving solid (the wall is at rest);
+ *               a reaction force on the fluid; more than one GPU; a facet-based contact for meshes much finer than the
+ *               particles (a sphere larger than its tet still sees that tet's plane only). */
+typedef struct DflSurfaceContact {
+    f64 level;        /* phi value of the metal surface */
+    index_type side;  /* +1: metal where phi > level, -1: metal where phi < level (as DflParticleCapture.side) */
+    f64 T_solid;      /* contact only where the fluid has T_f < T_solid; HUGE_VAL: everywhere */
+} DflSurfaceContact;
+typedef struct DflSurfaceContactStats {
+    index_type last, buried; /* particles in contact / buried in the last sub-step */
+    int64_t total;           /* particle-sub-steps in contact since the configuration was last set */
+} DflSurfaceContactStats;
+/* host only; 0 when ParticleContextSetSurfaceContact accepts the configuration, else why not in `why`: side must be +1 or
+ * -1, level finite, T_solid not a NaN */
+int DflSurfaceContactCheck(const DflSurfaceContact* cfg, char* why, size_t why_len);
+/* the configuration is copied; NULL: off, frees the state.  Reported on stderr, context unchanged: what the check refuses,
+ * an uncoupled context */
+void ParticleContextSetSurfaceContact(ParticleContext* ctx, const DflSurfaceContact* cfg);
+void ParticleContextSurfaceContactStats(const ParticleContext* ctx, DflSurfaceContactStats* out); /* zeros when off */
 
 /* ---- free-surface forces (build-defined; opt-in) ------------------------------------------------------------------------
  * The reference's level set carries no surface physics.  A mesh that never calls DflMeshSetSurfaceForces with a

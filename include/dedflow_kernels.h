@@ -907,6 +907,36 @@ void dfl_capture_flag(dfl_index P, const dfl_index* tet, const dfl_value* lambda
 void dfl_capture_source(dfl_index N, const dfl_value* A, dfl_value time, dfl_value* q_vol, dfl_value* load, dfl_value* q_heat,
                         void* stream);
 
+/* ---- solid-surface contact (build-defined, opt-in; csrc/k_surface_contact.hip, model in include/dedflow.h)
+ *  dfl_surface_counters  step[k]: the counts of the last sub-step of parity k, in contact in the low and buried in the high 32
+ *                        bits, spread over DFL_SURFACE_SLOTS slots of one cache line each (a workgroup adds to slot
+ *                        blockIdx mod DFL_SURFACE_SLOTS; their sum is the count); total: the contacts of every earlier sub-step
+ *    dfl_surface_grad_max   one thread per tet: *grad_max = max over the tets and k = 1, 2, 3 of |c_k| / |det| (the |grad N_k|
+ *                           of the closed form of g, from the same device function the contact divides by); +inf or a NaN
+ *                           when a tet is degenerate or a coordinate is not finite, which turns the early exit off.  A
+ *                           memset and one launch
+ *    dfl_surface_contact    one launch, one thread per particle (one workgroup when P = 0): the contact of include/dedflow.h
+ *                           from tet / lambda of the locate just run, xg, the fluid state w [6N], vel and omega; acc, alpha
+ *                           and the history row of a particle in contact are added to / appended to, no other particle is
+ *                           written.  Variants: friction when omega is not NULL (hist = previous rows and the rows this
+ *                           sub-step's sweep wrote with their counts; off: omega, law, hist and alpha are not read), sizes per
+ *                           particle when sz.radius is not NULL (then the scalars are not read).  grad_max: device [1], what
+ *                           dfl_surface_grad_max wrote for this mesh; it lets a particle far on the gas side leave before T and
+ *                           the coordinates are gathered, and the result does not depend on it (a value that is not > 0 lets nothing leave early).  cur (0 or 1) alternates between launches: the launch adds to cnt->step[cur], and
+ *                           folds step[1 - cur] into total and clears it.  No allocation, no synchronisation */
+#define DFL_SURFACE_SLOTS 64
+#define DFL_SURFACE_SLOT_STRIDE 16
+typedef struct dfl_surface_counters {
+    unsigned long long step[2][DFL_SURFACE_SLOTS * DFL_SURFACE_SLOT_STRIDE];
+    long long total;
+} dfl_surface_counters;
+void dfl_surface_grad_max(dfl_index T, const dfl_index* ien, const dfl_value* xg, dfl_value* grad_max, void* stream);
+void dfl_surface_contact(dfl_index P, const dfl_index* tet, const dfl_value* lambda, const dfl_index* ien, const dfl_value* xg,
+                         const dfl_value* w, dfl_index N, const dfl_value* vel, const dfl_value* omega, dfl_value mass,
+                         dfl_value radius, dfl_sizes sz, dfl_value kn, dfl_value gamma_n, dfl_friction_law law, dfl_value level,
+                         dfl_value side, dfl_value T_solid, const dfl_value* grad_max, dfl_contact_history hist,
+                         dfl_surface_counters* cnt, int cur, dfl_value* acc, dfl_value* alpha, void* stream);
+
 /* ---- scalar transport (host/scalar.c, csrc/k_scalar.hip) ------------------------------------------------------------
  * dfl_assemble_scalar_jacobian: the level-set and temperature Jacobians (d R_phi / d dphi, d R_T / d dT) over the nodal
  * pattern (row_ptr / col_ind, columns ascending), one value per nonzero, overwritten (beta = 0).  vrow / vcol: the V2E map
