@@ -113,7 +113,7 @@ void DflDemReserve(ParticleExt* x, index_type P, index_type nbin) {
         x->sorted = (f64*)CdamMallocDevice((ptrdiff_t)P * 6 * SIZE_OF(f64));
         x->cap_particle = P;
     }
-    if (x->cap_cell < nbin + 1) { /* zero-filled by the allocator; every sweep leaves count / chunk_sum zeroed again */
+    if (x->cap_cell < nbin + 1) { /* zero-filled by the allocator; every sweep leaves count zeroed again (chunk_sum is plain scratch) */
         CdamFreeDevice(x->count, 0); CdamFreeDevice(x->cell_start, 0); CdamFreeDevice(x->chunk_sum, 0);
         x->count = (index_type*)CdamMallocDevice(((ptrdiff_t)nbin + 1) * SIZE_OF(index_type));
         x->cell_start = (index_type*)CdamMallocDevice(((ptrdiff_t)nbin + 1) * SIZE_OF(index_type));

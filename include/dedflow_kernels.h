@@ -745,8 +745,9 @@ typedef struct dfl_sizes {
  *    dfl_dem_build_cells    counting sort of the particles by cell (5 launches): cell_start[ncell^3 + 1], order[P] =
  *                           particle ids by (cell, id), and the copies in that order: sorted[P][6] = position and
  *                           velocity, sorted_w[P][3] = omega (friction), sorted_r[P] = radius (sizes).  count[ncell^3 + 1]
- *                           and chunk_sum[dfl_scan_num_chunks(ncell^3)] are zero-initialised scratch that the call leaves
- *                           zeroed again; cell_of, rank and slot [P] are scratch
+ *                           is zero on entry and the call leaves it zeroed again (its last entry is never touched);
+ *                           chunk_sum[dfl_scan_num_chunks(ncell^3)], cell_of, rank and slot [P] are plain scratch:
+ *                           written before they are read, left with whatever the call put there
  *    dfl_dem_sort_binned    the last four launches of dfl_dem_build_cells, for a bin pass of the caller's over nbin bins
  *    dfl_dem_forces         acc[i] = (sum_j F_ij + F_walls) / m_i, neighbours from the cells within the interaction range;
  *                           with friction also alpha[i] = torque / I_i and the new history rows
