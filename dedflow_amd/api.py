@@ -801,6 +801,21 @@ class DflTrackSection(C.Structure):
                 ("y_hi_fused", C.c_double), ("pairs", C.c_int64), ("dilution", C.c_double)]
 
 
+class DflTimeStepLimits(C.Structure):
+    _fields_ = [("rate_adv", C.c_double), ("rate_adv_surface", C.c_double), ("cap_q", C.c_double), ("tet_adv", C.c_int32),
+                ("tet_surface", C.c_int32), ("tet_cap", C.c_int32), ("num_cut", C.c_int32), ("num_nonfinite", C.c_int32),
+                ("dt_adv", C.c_double), ("dt_surface", C.c_double), ("dt_capillary", C.c_double), ("dt", C.c_double)]
+
+
+class dfl_step_consts(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("dt", "t0", "fact2", "fact2_rho", "fact2_rho2", "fact2_mu4", "fact2_kappa",
+                                          "states_old", "corr_old", "corr_new")]
+
+
+class dfl_step_limit_params(C.Structure):
+    _fields_ = [("level", C.c_double), ("sigma0", C.c_double), ("dsigma_dT", C.c_double), ("T_ref", C.c_double)]
+
+
 class DflComm(C.Structure):
     _fields_ = [("allreduce_sum", ALLREDUCE_FN), ("halo_exchange", HALO_FN), ("ctx", vp), ("num_owned_node", C.c_int32),
                 ("halo_begin", HALO_FN), ("halo_end", HALO_FN), ("num_interior_node", C.c_int32),
@@ -1020,6 +1035,12 @@ def _declare(L):
     f("DflMeshTrackSectionsResult", None, [C.POINTER(Mesh3D), C.POINTER(DflTrackSection)])
     f("DflTrackSectionsTestPairs", i32, [C.POINTER(Mesh3D), C.POINTER(vp), C.POINTER(i32)])
     f("DflTrackSectionsTestCapacity", None, [C.POINTER(Mesh3D), C.POINTER(i32), C.POINTER(i32)])
+    f("DflTimeStepCheck", C.c_int, [f64, C.c_char_p, C.c_size_t])
+    f("DflMeshSetTimeStep", None, [C.POINTER(Mesh3D), f64]); f("DflMeshTimeStep", f64, [C.POINTER(Mesh3D)])
+    f("DflMeshTimeStepLimits", None, [C.POINTER(Mesh3D), vp, f64, C.POINTER(DflTimeStepLimits)])
+    f("dfl_step_consts_from_dt", None, [f64, C.POINTER(dfl_step_consts)])
+    f("dfl_step_limit_grid", i32, [i32, i32])
+    f("dfl_step_limits", None, [i32, vp, vp, vp, i32, C.POINTER(dfl_step_limit_params), i32, vp, vp, vp, vp, vp])
     f("GenerateRandomColor", None, [vp, i32, i32])
     f("dfl_abi_version", C.c_int, [])
 
@@ -1180,6 +1201,23 @@ class Problem:
                                len(self.bcs), newton_maxit, particles.ctx if particles is not None else None, dem_substeps,
                                C.cast(rn, vp), C.cast(r0, vp))
         return int(it), np.array(rn[:]), np.array(r0[:])
+
+    # ---- time step (include/dedflow.h, "time step") ----------------------------------------------------------------------
+    def set_time_step(self, dt):
+        """DflMeshSetTimeStep: the step every later call on this problem uses.  A dt the library refuses (not finite, not
+        positive; reported on stderr) leaves the step as it was: time_step_size tells."""
+        lib().DflMeshSetTimeStep(self.mesh, float(dt))
+
+    def time_step_size(self):
+        """DflMeshTimeStep: the step of this problem, DFL_DEFAULT_TIME_STEP until set"""
+        return float(lib().DflMeshTimeStep(self.mesh))
+
+    def time_step_limits(self, w, level=0.0):
+        """DflMeshTimeStepLimits at the state w (DeviceArray of 6N) and the surface phi = level: a dict of the fields of
+        DflTimeStepLimits (synchronises)"""
+        s = DflTimeStepLimits()
+        lib().DflMeshTimeStepLimits(self.mesh, w.ptr, float(level), C.byref(s))
+        return {n: (int if t is C.c_int32 else float)(getattr(s, n)) for n, t in DflTimeStepLimits._fields_}
 
     # ---- phi / T transport (include/dedflow.h, "scalar transport") -----------------------------------------------------
     def set_scalar_transport(self, phi=True, T=True, dirichlet_phi=(), dirichlet_T=(), pc="jacobi", rtol=1e-10, maxit=200):

@@ -9,7 +9,6 @@ namespace {
 
 // ---- constants: src/assemble.cu:23-52,65-118 -------------------------------------
 #define kRHOC (0.5)
-#define kDT (5e-2)
 #define kALPHAM ((3.0 - kRHOC) / (1.0 + kRHOC))
 #define kALPHAF (1.0 / (1.0 + kRHOC))
 #define kGAMMA (0.5 + kALPHAM - kALPHAF)
@@ -24,6 +23,12 @@ namespace {
 #define FB0 (0.0)
 #define FB1 (0.0)
 #define FB2 (-9.81 * 0.0)
+
+// What the kernels take from the time step: dfl_step_consts (include/dedflow_kernels.h), formed once on the host by
+// dfl_step_consts_from_dt and passed by value as a kernel argument.  It is wave-uniform, so it lives in SGPRs where the literals
+// of the compile-time step lived; every product that used to fold into one literal arrives as one number, so the fused
+// multiply-adds the compiler forms around it are the ones it formed around the literal.
+typedef dfl_step_consts StepK;
 
 __device__ __forceinline__ double shl(int a, int q) { return a == q ? SHA : SHB; }
 
@@ -146,11 +151,11 @@ __device__ __forceinline__ void tet_metric(const double* shg, double* G) {
 // eleven scalar sums followed by ONE pass over the 16 block entries: ~5x fewer fp64 operations than the
 // literal loop.  Same terms, different association: results differ from the oracle by rounding only
 // (tests bound it at 1e-10).
-__device__ __forceinline__ void lhs_block_eval(int aa, int bb, const double* ga, const double* gb, double detJ,
+__device__ __forceinline__ void lhs_block_eval(const StepK& sk, int aa, int bb, const double* ga, const double* gb, double detJ,
                                                const double* t0, const double* t1, const double* cav,
                                                const double* cbv, double* Bk) {
     const double fact1 = kALPHAM;
-    const double fact2 = kDT * kALPHAF * kGAMMA;
+    const double fact2 = sk.fact2;
     const double eK = ga[0] * gb[0] + ga[1] * gb[1] + ga[2] * gb[2];
     double S_t0 = 0.0, S_t1 = 0.0, S_sa = 0.0, S_sb = 0.0, S_sasb = 0.0, S_t0ca = 0.0, S_t0casb = 0.0, S_sacb = 0.0,
            S_t0cacb = 0.0, S_t0sb = 0.0, S_t0cb = 0.0;
@@ -173,18 +178,20 @@ __device__ __forceinline__ void lhs_block_eval(int aa, int bb, const double* ga,
         S_t0cb += tau0 * cb;
     }
     const double w = detJ * GW;
-    const double diag = w * (fact1 * kRHO * S_sasb + fact1 * kRHO * kRHO * S_t0casb + fact2 * kRHO * S_sacb +
-                             fact2 * kRHO * kRHO * S_t0cacb + 4.0 * fact2 * kMU * eK);
-    const double cK = 4.0 * fact2 * kMU * w, cT = fact2 * kRHO * S_t1 * w;
+    const double diag = w * (fact1 * kRHO * S_sasb + fact1 * kRHO * kRHO * S_t0casb + sk.fact2_rho * S_sacb +
+                             sk.fact2_rho2 * S_t0cacb + sk.fact2_mu4 * eK);
+    const double cK = sk.fact2_mu4 * w, cT = sk.fact2_rho * S_t1 * w;
 #pragma unroll
     for (int ii = 0; ii < 3; ++ii)
 #pragma unroll
-        for (int jj = 0; jj < 3; ++jj) Bk[ii * 4 + jj] = cK * ga[jj] * gb[ii] + cT * ga[ii] * gb[jj];
+        // (which of the two products the compiler fuses into the addition depended on cK being built from a literal: the
+        //  fusion it chose then is written out, so that the bits do not depend on where the step comes from)
+        for (int jj = 0; jj < 3; ++jj) Bk[ii * 4 + jj] = fma(cK * ga[jj], gb[ii], cT * ga[ii] * gb[jj]);
     Bk[0] += diag;
     Bk[5] += diag;
     Bk[10] += diag;
     const double cP0 = w * S_sb, cP1 = w * kRHO * S_t0ca;
-    const double cU0 = w * (fact1 * kRHO * S_t0sb + fact2 * kRHO * S_t0cb), cU1 = w * fact2 * S_sa;
+    const double cU0 = w * (fact1 * kRHO * S_t0sb + sk.fact2_rho * S_t0cb), cU1 = w * fact2 * S_sa;
 #pragma unroll
     for (int ii = 0; ii < 3; ++ii) {
         Bk[ii * 4 + 3] = cP1 * gb[ii] - cP0 * ga[ii];  // dRM/dP
@@ -199,11 +206,11 @@ __device__ __forceinline__ void lhs_block_eval(int aa, int bb, const double* ga,
 // S_t0 = sum of tauM) plus three single entries the caller reads by index (cb[aa], ca[bb], t0[bb]).  Same terms as
 // lhs_block_eval; the sums that carry a shape-function factor collapse through shl(c, q) = SHB + (SHA - SHB)[c == q], and
 // every entry is accumulated by fused multiply-adds straight into `acc` (about 85 fp64 operations instead of ~140).
-__device__ __forceinline__ void lhs_block_accumulate(bool same, const double* ga, const double* gb, double w, double cK, double cT,
+__device__ __forceinline__ void lhs_block_accumulate(const StepK& sk, bool same, const double* ga, const double* gb, double w, double cK, double cT,
                                                      double S_t0, const double* t0, const double* ca, const double* cb, double cb_a,
                                                      double ca_b, double t0_b, double* acc) {
     const double fact1 = kALPHAM;
-    const double fact2 = kDT * kALPHAF * kGAMMA;
+    const double fact2 = sk.fact2;
     const double tc0 = t0[0] * ca[0], tc1 = t0[1] * ca[1], tc2 = t0[2] * ca[2], tc3 = t0[3] * ca[3];
     const double S_t0ca = (tc0 + tc1) + (tc2 + tc3);
     const double S_t0cacb = fma(tc3, cb[3], fma(tc2, cb[2], fma(tc1, cb[1], tc0 * cb[0])));
@@ -215,9 +222,9 @@ __device__ __forceinline__ void lhs_block_accumulate(bool same, const double* ga
     const double S_sasb = same ? (SHA * SHA + 3.0 * SHB * SHB) : (2.0 * SHA * SHB + 2.0 * SHB * SHB);
     const double S_one = SHA + 3.0 * SHB;  // sum of the shape functions over the quadrature points
     const double eK = fma(ga[2], gb[2], fma(ga[1], gb[1], ga[0] * gb[0]));
-    double d = (4.0 * fact2 * kMU) * eK;
-    d = fma(fact2 * kRHO * kRHO, S_t0cacb, d);
-    d = fma(fact2 * kRHO, S_sacb, d);
+    double d = (sk.fact2_mu4) * eK;
+    d = fma(sk.fact2_rho2, S_t0cacb, d);
+    d = fma(sk.fact2_rho, S_sacb, d);
     d = fma(fact1 * kRHO * kRHO, S_t0casb, d);
     d = fma(fact1 * kRHO, S_sasb, d);
     const double diag = w * d;
@@ -245,11 +252,11 @@ __device__ __forceinline__ void lhs_block_accumulate(bool same, const double* ga
 }
 
 // the same block with the sum of tauC over the quadrature points formed by the caller (tauC enters only through it)
-__device__ __forceinline__ void lhs_block_eval_s(int aa, int bb, const double* ga, const double* gb, double detJ,
+__device__ __forceinline__ void lhs_block_eval_s(const StepK& sk, int aa, int bb, const double* ga, const double* gb, double detJ,
                                                  const double* t0, double S_t1, const double* cav,
                                                const double* cbv, double* Bk) {
     const double fact1 = kALPHAM;
-    const double fact2 = kDT * kALPHAF * kGAMMA;
+    const double fact2 = sk.fact2;
     const double eK = ga[0] * gb[0] + ga[1] * gb[1] + ga[2] * gb[2];
     double S_t0 = 0.0, S_sa = 0.0, S_sb = 0.0, S_sasb = 0.0, S_t0ca = 0.0, S_t0casb = 0.0, S_sacb = 0.0,
            S_t0cacb = 0.0, S_t0sb = 0.0, S_t0cb = 0.0;
@@ -271,9 +278,9 @@ __device__ __forceinline__ void lhs_block_eval_s(int aa, int bb, const double* g
         S_t0cb += tau0 * cb;
     }
     const double w = detJ * GW;
-    const double diag = w * (fact1 * kRHO * S_sasb + fact1 * kRHO * kRHO * S_t0casb + fact2 * kRHO * S_sacb +
-                             fact2 * kRHO * kRHO * S_t0cacb + 4.0 * fact2 * kMU * eK);
-    const double cK = 4.0 * fact2 * kMU * w, cT = fact2 * kRHO * S_t1 * w;
+    const double diag = w * (fact1 * kRHO * S_sasb + fact1 * kRHO * kRHO * S_t0casb + sk.fact2_rho * S_sacb +
+                             sk.fact2_rho2 * S_t0cacb + sk.fact2_mu4 * eK);
+    const double cK = sk.fact2_mu4 * w, cT = sk.fact2_rho * S_t1 * w;
 #pragma unroll
     for (int ii = 0; ii < 3; ++ii)
 #pragma unroll
@@ -282,7 +289,7 @@ __device__ __forceinline__ void lhs_block_eval_s(int aa, int bb, const double* g
     Bk[5] += diag;
     Bk[10] += diag;
     const double cP0 = w * S_sb, cP1 = w * kRHO * S_t0ca;
-    const double cU0 = w * (fact1 * kRHO * S_t0sb + fact2 * kRHO * S_t0cb), cU1 = w * fact2 * S_sa;
+    const double cU0 = w * (fact1 * kRHO * S_t0sb + sk.fact2_rho * S_t0cb), cU1 = w * fact2 * S_sa;
 #pragma unroll
     for (int ii = 0; ii < 3; ++ii) {
         Bk[ii * 4 + 3] = cP1 * gb[ii] - cP0 * ga[ii];  // dRM/dP
@@ -312,7 +319,7 @@ constexpr int FREC = 8;  // packed residual record: F_u0 F_u1 F_u2 F_p F_phi F_T
 // Residual of one tet on 4 lanes (lane a: node a for the result, quadrature point a for the weak form).
 // r[b] = node record of vertex b (x[3] u[3] phi T du[3] p dphi dT, in LDS); result: mine[0..5] = the 6 residual
 // components of node a summed over the 4 quadrature points (DPP quad reduce-scatter).
-__device__ __forceinline__ void rhs_quad(const double* const* r, int a, double* mine) {
+__device__ __forceinline__ void rhs_quad(const StepK& sk, const double* const* r, int a, double* mine) {
     const int iq = a;
     double shg[12], detJ, gg, itr;
     {  // geometry from the vertex coordinates in the node records (already staged in LDS: no extra HBM stream; the
@@ -374,7 +381,7 @@ __device__ __forceinline__ void rhs_quad(const double* const* r, int a, double* 
     // 1/tr G come from the geometry record; 1/sqrt and sqrt through v_rsq_f64 (no fp64 divisions left)
     double tau[4];
     {
-        const double t0 = 4.0 / (kDT * kDT);
+        const double t0 = sk.t0;
         double t1 = 0.0;
 #pragma unroll
         for (int r = 0; r < 3; ++r) {

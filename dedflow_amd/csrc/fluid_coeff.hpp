@@ -129,7 +129,7 @@ __device__ __forceinline__ void fluid_row_point(const FluidGeom& g, const FluidF
 // E[0..2] += the momentum rows, E[3] += the continuity row of the own node at one quadrature point (the element residual of
 // rhs_quad) with the density r, the viscosity m and the body force f there.  The caller adds the four points in ascending q
 // from +0.0, once with (rho_q, mu_q, f_q) and once with (kRHO, kMU, 0), through this one function
-__device__ __forceinline__ void fluid_E_add(const FluidGeom& g, const FluidRowTet& t, const FluidRowPoint& s, double r, double m,
+__device__ __forceinline__ void fluid_E_add(const StepK& sk, const FluidGeom& g, const FluidRowTet& t, const FluidRowPoint& s, double r, double m,
                                             const double* f, double* E) {
 #pragma clang fp contract(off)
     double acc[3], rLi[3];
@@ -140,7 +140,7 @@ __device__ __forceinline__ void fluid_E_add(const FluidGeom& g, const FluidRowTe
         rLi[i] = (((r * acc[i] + (r * s.uq[0]) * t.grad[i][0]) + (r * s.uq[1]) * t.grad[i][1]) + (r * s.uq[2]) * t.grad[i][2]) + t.gp[i];
     const double nu = m / r;
     const double y = s.t1 + ((3.0 * nu) * nu) * g.gg;
-    const double tau0 = (1.0 / sqrt(4.0 / (kDT * kDT) + y)) / r;
+    const double tau0 = (1.0 / sqrt(sk.t0 + y)) / r;
     const double tau1 = sqrt(y) / g.tr;
     const double diag = r * tau1 * t.divu - s.pq;
 #pragma unroll
@@ -176,15 +176,15 @@ struct FluidJacTet {
     double t0b[4], t1b[4];       // with kRHO, kMU
 };
 
-__device__ __forceinline__ void fluid_tau(double y1, double gg, double tr, double rho, double mu, double& tau0, double& tau1) {
+__device__ __forceinline__ void fluid_tau(const StepK& sk, double y1, double gg, double tr, double rho, double mu, double& tau0, double& tau1) {
 #pragma clang fp contract(off)
     const double nu = mu / rho;
     const double y = y1 + ((3.0 * nu) * nu) * gg;
-    tau0 = (1.0 / sqrt(4.0 / (kDT * kDT) + y)) / rho;
+    tau0 = (1.0 / sqrt(sk.t0 + y)) / rho;
     tau1 = sqrt(y) / tr;
 }
 
-__device__ __forceinline__ void fluid_jac_tet(const FluidGeom& g, const double (*u)[3], const double* rho, const double* mu,
+__device__ __forceinline__ void fluid_jac_tet(const StepK& sk, const FluidGeom& g, const double (*u)[3], const double* rho, const double* mu,
                                               FluidJacTet& j) {
 #pragma clang fp contract(off)
 #pragma unroll
@@ -199,16 +199,16 @@ __device__ __forceinline__ void fluid_jac_tet(const FluidGeom& g, const double (
 #pragma unroll
         for (int b = 0; b < 4; ++b) j.c[q][b] = (uq[0] * g.gN[b][0] + uq[1] * g.gN[b][1]) + uq[2] * g.gN[b][2];
         const double y1 = (j.c[q][1] * j.c[q][1] + j.c[q][2] * j.c[q][2]) + j.c[q][3] * j.c[q][3];  // |J^-1 u_q|^2
-        fluid_tau(y1, g.gg, g.tr, rho[q], mu[q], j.t0[q], j.t1[q]);
-        fluid_tau(y1, g.gg, g.tr, kRHO, kMU, j.t0b[q], j.t1b[q]);
+        fluid_tau(sk, y1, g.gg, g.tr, rho[q], mu[q], j.t0[q], j.t1[q]);
+        fluid_tau(sk, y1, g.gg, g.tr, kRHO, kMU, j.t0b[q], j.t1b[q]);
     }
 }
 
 // B[ii * 4 + jj] of node pair (la, lb) (lb a compile-time index after unrolling), coefficients inside the quadrature sums (ascending q, from +0.0)
-__device__ __forceinline__ void fluid_tet_B(const FluidGeom& g, const double (*cq)[4], int la, int lb, const double* rho,
+__device__ __forceinline__ void fluid_tet_B(const StepK& sk, const FluidGeom& g, const double (*cq)[4], int la, int lb, const double* rho,
                                             const double* mu, const double* t0, const double* t1, double* B) {
 #pragma clang fp contract(off)
-    const double f1 = kALPHAM, f2 = kDT * kALPHAF * kGAMMA;
+    const double f1 = kALPHAM, f2 = sk.fact2;
     double ga[3];  // (la is the lane's own: selects, no indexed register array)
 #pragma unroll
     for (int d = 0; d < 3; ++d) ga[d] = la == 0 ? g.gN[0][d] : la == 1 ? g.gN[1][d] : la == 2 ? g.gN[2][d] : g.gN[3][d];

@@ -40,7 +40,7 @@ struct LhsStage {
 // `egeo` = the element's cached geometry record (elem_geometry_kernel: shg[12], detJ, gg, 1/tr, pad), read as
 // one coalesced 128-byte line by the element's 16 lanes -- the mesh does not move inside the time loop, so the
 // Jacobian inverse / shape gradients / metric are computed once per mesh instead of once per assembly.
-__device__ __forceinline__ void lhs_element_block(LhsStage& S, int te, int p, bool valid, const I* __restrict__ nodes,
+__device__ __forceinline__ void lhs_element_block(const StepK& sk, LhsStage& S, int te, int p, bool valid, const I* __restrict__ nodes,
                                                   const T* __restrict__ egeo, const T* __restrict__ nodep, double* Bk) {
     double (*s_u)[12] = S.u;
     double (*s_shg)[12] = S.shg;
@@ -85,7 +85,7 @@ __device__ __forceinline__ void lhs_element_block(LhsStage& S, int te, int p, bo
         tmp += s_conv[te][2][p] * s_conv[te][2][p];
         tmp += s_conv[te][3][p] * s_conv[te][3][p];
         const double gg = s_scal[te][1];
-        s_tau[te][p][0] = (1.0 / sqrt(4.0 / (kDT * kDT) + tmp + 3.0 * knu * knu * gg)) / kRHO;
+        s_tau[te][p][0] = (1.0 / sqrt(sk.t0 + tmp + 3.0 * knu * knu * gg)) / kRHO;
         s_tau[te][p][1] = sqrt(tmp + 3.0 * knu * knu * gg) * s_scal[te][2];
     }
     WAVE_SYNC();
@@ -107,13 +107,13 @@ __device__ __forceinline__ void lhs_element_block(LhsStage& S, int te, int p, bo
             ca[iq] = s_conv[te][aa][iq];
             cb[iq] = s_conv[te][bb][iq];
         }
-        lhs_block_eval(aa, bb, ga, gb, s_scal[te][0], t0, t1, ca, cb, Bk);
+        lhs_block_eval(sk, aa, bb, ga, gb, s_scal[te][0], t0, t1, ca, cb, Bk);
     }
 }
 
 __global__ __launch_bounds__(LBLK) void tet_lhs_kernel(I B, const I* __restrict__ ien_b, const I* __restrict__ nzmap_b,
                                                       const T* __restrict__ egeo, const T* __restrict__ nodep,
-                                                      T* __restrict__ val) {
+                                                      T* __restrict__ val, const StepK sk) {
     __shared__ LhsStage S;
     __shared__ double s_blk[16 * TRS];
     __shared__ int s_nz[LBLK];
@@ -125,7 +125,7 @@ __global__ __launch_bounds__(LBLK) void tet_lhs_kernel(I B, const I* __restrict_
 
     s_nz[t] = valid ? nzmap_b[(long long)blockIdx.x * LBLK + t] : -1;
     double Bk[16];
-    lhs_element_block(S, te, p, valid, ien_b + (valid ? e : 0) * 4, egeo + (valid ? e : 0) * 16, nodep, Bk);
+    lhs_element_block(sk, S, te, p, valid, ien_b + (valid ? e : 0) * 4, egeo + (valid ? e : 0) * 16, nodep, Bk);
     // transpose through LDS: s_blk[i][t] = entry i of the block owned by thread t
 #pragma unroll
     for (int i = 0; i < 16; ++i) s_blk[i * TRS + t] = Bk[i];
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(LBLK) void tet_lhs_kernel(I B, const I* __restrict_
 
 
 __global__ __launch_bounds__(RBLK) void tet_rhs_kernel(I B, const I* __restrict__ ien_b, const T* __restrict__ nodep,
-                                                      T* __restrict__ Fp) {
+                                                      T* __restrict__ Fp, const StepK sk) {
     __shared__ double s_n[REPB][4][NV + 1];
     const int t = threadIdx.x;
     const int te = t >> 2, a = t & 3;
@@ -185,7 +185,7 @@ __global__ __launch_bounds__(RBLK) void tet_rhs_kernel(I B, const I* __restrict_
     if (!valid) return;  // whole 4-lane groups leave together; shuffles below stay inside a group
     const double* r[4] = {s_n[te][0], s_n[te][1], s_n[te][2], s_n[te][3]};
     double mine[6];
-    rhs_quad(r, a, mine);
+    rhs_quad(sk, r, a, mine);
     // ElemRHSLocal2Global: non-atomic, race-free inside a class; one 64-byte record per node
     double2* dst = reinterpret_cast<double2*>(Fp + node * FREC);
     double2 f0 = dst[0], f1 = dst[1], f2 = dst[2];
@@ -322,7 +322,7 @@ __global__ __launch_bounds__(64) void face_kernel(I nf, const I* __restrict__ fa
                                                  const I* __restrict__ forn, const I* __restrict__ ien, I N,
                                                  const T* __restrict__ xg, const T* __restrict__ wg, const T* __restrict__ dwg,
                                                  T* __restrict__ F, const I* __restrict__ rp, const I* __restrict__ ci,
-                                                 T* __restrict__ val, T* __restrict__ pF, T* __restrict__ pJ) {
+                                                 T* __restrict__ val, T* __restrict__ pF, T* __restrict__ pJ, const StepK sk) {
     // pF / pJ != NULL: two-pass form -- the face's contributions are parked ([i][a][4] and [i][a*4+b][16]) and summed per
     // node / per nonzero in a fixed order by face_sum_*_kernel: one launch for all faces, no conflict classes
     const int i = blockIdx.x * 64 + threadIdx.x;
@@ -438,7 +438,7 @@ __global__ __launch_bounds__(64) void face_kernel(I nf, const I* __restrict__ fa
         }
     }
     if (val || pJ) {
-        const double fact2 = kDT * kALPHAF * kGAMMA;
+        const double fact2 = sk.fact2;
         double shnorm[4];
 #pragma unroll
         for (int aa = 0; aa < 4; ++aa) {
@@ -575,10 +575,40 @@ void dfl_elem_geometry(I T_, const I* ien_x, const T* xg, T* egeo, void* stream)
     DFL_LAUNCH_CHECK();
 }
 
-void dfl_assemble_tet_lhs(I B, const I* ien_b, const I* nzmap_b, const T* egeo_b, const T* nodep, T* val, void* stream) {
+// The one place that derives what the kernels and the driver take from the time step (include/dedflow_kernels.h,
+// dfl_step_consts): every entry in exactly the operation order of the expression it replaces, products only
+void dfl_step_consts_from_dt(double dt, dfl_step_consts* k) {
+    const double fact2 = dt * kALPHAF * kGAMMA;
+    k->dt = dt;
+    k->t0 = 4.0 / (dt * dt);
+    k->fact2 = fact2;
+    k->fact2_rho = fact2 * kRHO;
+    k->fact2_rho2 = fact2 * kRHO * kRHO;
+    k->fact2_mu4 = 4.0 * fact2 * kMU;
+    k->fact2_kappa = fact2 * kKAPPA;
+    k->states_old = dt * kALPHAF * (1.0 - kGAMMA);
+    k->corr_old = dt * (1.0 - kGAMMA);
+    k->corr_new = dt * kGAMMA;
+}
+
+const dfl_step_consts* dfl_step_consts_default(void) {
+    static dfl_step_consts k;
+    static bool made = false;
+    if (!made) {  // (every caller writes the same values: a race here is harmless)
+        dfl_step_consts_from_dt(DFL_DEFAULT_TIME_STEP, &k);  // the reference's kDT
+        made = true;
+    }
+    return &k;
+}
+
+void dfl_assemble_tet_lhs_dt(I B, const I* ien_b, const I* nzmap_b, const T* egeo_b, const T* nodep, T* val,
+                             const dfl_step_consts* k, void* stream) {
     if (B <= 0) return;
-    tet_lhs_kernel<<<ceil_div(B, EPB), LBLK, 0, S(stream)>>>(B, ien_b, nzmap_b, egeo_b, nodep, val);
+    tet_lhs_kernel<<<ceil_div(B, EPB), LBLK, 0, S(stream)>>>(B, ien_b, nzmap_b, egeo_b, nodep, val, *k);
     DFL_LAUNCH_CHECK();
+}
+void dfl_assemble_tet_lhs(I B, const I* ien_b, const I* nzmap_b, const T* egeo_b, const T* nodep, T* val, void* stream) {
+    dfl_assemble_tet_lhs_dt(B, ien_b, nzmap_b, egeo_b, nodep, val, dfl_step_consts_default(), stream);
 }
 
 void dfl_rhs_node_sum(I N, const I* goff, const I* gidx, const T* partial, T* F, void* stream) {
@@ -588,10 +618,13 @@ void dfl_rhs_node_sum(I N, const I* goff, const I* gidx, const T* partial, T* F,
     DFL_LAUNCH_CHECK();
 }
 
-void dfl_assemble_tet_rhs(I B, const I* ien_b, const T* nodep, T* Fp, void* stream) {
+void dfl_assemble_tet_rhs_dt(I B, const I* ien_b, const T* nodep, T* Fp, const dfl_step_consts* k, void* stream) {
     if (B <= 0) return;
-    tet_rhs_kernel<<<ceil_div(B, REPB), RBLK, 0, S(stream)>>>(B, ien_b, nodep, Fp);
+    tet_rhs_kernel<<<ceil_div(B, REPB), RBLK, 0, S(stream)>>>(B, ien_b, nodep, Fp, *k);
     DFL_LAUNCH_CHECK();
+}
+void dfl_assemble_tet_rhs(I B, const I* ien_b, const T* nodep, T* Fp, void* stream) {
+    dfl_assemble_tet_rhs_dt(B, ien_b, nodep, Fp, dfl_step_consts_default(), stream);
 }
 
 void dfl_pack_nodes2(I N, const T* xg, const T* wg, const T* dwg, T* nodep, T* nodexu, void* stream) {
@@ -609,21 +642,29 @@ void dfl_unpack_rhs(I N, T* Fp, T* F, void* stream) {
     DFL_LAUNCH_CHECK();
 }
 
-void dfl_assemble_face(I nf, const I* face_list, const I* f2e, const I* forn, const I* ien, I N, const T* xg, const T* wg,
-                       const T* dwg, T* F, const I* rp, const I* ci, T* val, void* stream) {
+void dfl_assemble_face_dt(I nf, const I* face_list, const I* f2e, const I* forn, const I* ien, I N, const T* xg, const T* wg,
+                          const T* dwg, T* F, const I* rp, const I* ci, T* val, const dfl_step_consts* k, void* stream) {
     if (nf <= 0) return;
     face_kernel<<<ceil_div(nf, 64), 64, 0, S(stream)>>>(nf, face_list, f2e, forn, ien, N, xg, wg, dwg, F, rp, ci, val, nullptr,
-                                                         nullptr);
+                                                         nullptr, *k);
     DFL_LAUNCH_CHECK();
 }
+void dfl_assemble_face(I nf, const I* face_list, const I* f2e, const I* forn, const I* ien, I N, const T* xg, const T* wg,
+                       const T* dwg, T* F, const I* rp, const I* ci, T* val, void* stream) {
+    dfl_assemble_face_dt(nf, face_list, f2e, forn, ien, N, xg, wg, dwg, F, rp, ci, val, dfl_step_consts_default(), stream);
+}
 
-void dfl_assemble_face_park(I nf, const I* f2e, const I* forn, const I* ien, I N, const T* xg, const T* wg, const T* dwg,
-                            T* pF, T* pJ, void* stream) {
+void dfl_assemble_face_park_dt(I nf, const I* f2e, const I* forn, const I* ien, I N, const T* xg, const T* wg, const T* dwg,
+                               T* pF, T* pJ, const dfl_step_consts* k, void* stream) {
     if (nf <= 0) return;
     // F / val are only used as "is this part wanted" switches inside the kernel
     face_kernel<<<ceil_div(nf, 64), 64, 0, S(stream)>>>(nf, nullptr, f2e, forn, ien, N, xg, wg, dwg, pF, nullptr, nullptr, nullptr, pF,
-                                                         pJ);
+                                                         pJ, *k);
     DFL_LAUNCH_CHECK();
+}
+void dfl_assemble_face_park(I nf, const I* f2e, const I* forn, const I* ien, I N, const T* xg, const T* wg, const T* dwg,
+                            T* pF, T* pJ, void* stream) {
+    dfl_assemble_face_park_dt(nf, f2e, forn, ien, N, xg, wg, dwg, pF, pJ, dfl_step_consts_default(), stream);
 }
 void dfl_face_sum_F(I nn, const I* fnode, const I* off, const I* ent, const T* pF, I N, T* F, void* stream) {
     if (nn <= 0) return;

@@ -54,7 +54,7 @@ __device__ __forceinline__ unsigned slot_desc_word(const unsigned* __restrict__ 
 }
 
 // phase 1 of one tet: everything its sixteen (a,b) blocks share -> one LDS record
-__device__ __forceinline__ void slot_tet_record(const double2* r, double* rec) {
+__device__ __forceinline__ void slot_tet_record(const StepK& sk, const double2* r, double* rec) {
     double x[12], u[12];
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
@@ -88,17 +88,16 @@ __device__ __forceinline__ void slot_tet_record(const double2* r, double* rec) {
         }
         // |J^-1 u|^2 (rows of J^-1 = shape gradients of nodes 1..3) and the stabilisation parameters (:587-603)
         const double y = cv[1] * cv[1] + cv[2] * cv[2] + cv[3] * cv[3] + (3.0 * knu * knu) * gg;
-        t0v[q] = rsqrt_nr1(4.0 / (kDT * kDT) + y) * (1.0 / kRHO);
+        t0v[q] = rsqrt_nr1(sk.t0 + y) * (1.0 / kRHO);
         rec[28 + q] = t0v[q];
         s_t1 += y * rsqrt_nr1(y) * itr;  // tauC enters the block only through its sum over the quadrature points
     }
     // the four numbers every block of the tet starts from (lhs_block_accumulate), formed once here instead of 16 times there
-    const double fact2 = kDT * kALPHAF * kGAMMA;
     const double w = detJ * GW;
-    rec[32] = (fact2 * kRHO) * s_t1 * w;
+    rec[32] = sk.fact2_rho * s_t1 * w;
     rec[33] = w;
     rec[34] = (t0v[0] + t0v[1]) + (t0v[2] + t0v[3]);
-    rec[35] = (4.0 * fact2 * kMU) * w;
+    rec[35] = sk.fact2_mu4 * w;
 }
 
 // Node records of a patch in LDS.  The tets touching a 7-node patch (~90) have ~55 distinct nodes; round 2 gathered four
@@ -137,7 +136,7 @@ template <bool BETA0>
 __global__ __launch_bounds__(SBLK, 4) void tet_lhs_slot_kernel(I P, const int4* __restrict__ hdr, const unsigned* __restrict__ ptet_lid,
                                                                const I* __restrict__ pnode, const I* __restrict__ slot_nz,
                                                                const unsigned* __restrict__ ldesc, const T* __restrict__ nodep,
-                                                               T* __restrict__ val, T beta, int max_tets, int* __restrict__ claim) {
+                                                               T* __restrict__ val, T beta, int max_tets, int* __restrict__ claim, const StepK stepk) {
     static_assert(SBLK == 256, "trip bytes: four waves x two passes");
     extern __shared__ __attribute__((aligned(16))) double s_tet[];
     const double2* const s_nrec = reinterpret_cast<const double2*>(s_tet + (size_t)max_tets * SP_RS);  // [3][SP_NC]
@@ -234,7 +233,7 @@ __global__ __launch_bounds__(SBLK, 4) void tet_lhs_slot_kernel(I P, const int4* 
                 r[3 * b4 + 1] = s_nrec[SP_NC + n];
                 r[3 * b4 + 2] = s_nrec[2 * SP_NC + n];
             }
-            slot_tet_record(r, s_tet + t * SP_RS);
+            slot_tet_record(stepk, r, s_tet + t * SP_RS);
         }
         __syncthreads();  // tet records complete; nobody reads s_nrec any more
         // (c) everything requested for the next patch has arrived
@@ -280,7 +279,7 @@ __global__ __launch_bounds__(SBLK, 4) void tet_lhs_slot_kernel(I P, const int4* 
                     ca[0] = ca01.x; ca[1] = ca01.y; ca[2] = ca23.x; ca[3] = ca23.y;
                     cb[0] = cb01.x; cb[1] = cb01.y; cb[2] = cb23.x; cb[3] = cb23.y;
                     t0q[0] = ta01.x; t0q[1] = ta01.y; t0q[2] = ta23.x; t0q[3] = ta23.y;
-                    lhs_block_accumulate(aa == bb, ga, gb3, sc.y, sk.y, sc.x, sk.x, t0q, ca, cb, cb_a, ca_b, t0_b, acc);
+                    lhs_block_accumulate(stepk, aa == bb, ga, gb3, sc.y, sk.y, sc.x, sk.x, t0q, ca, cb, cb_a, ca_b, t0_b, acc);
                 };
                 // Up to four trips come out of the two prefetched descriptor words: NO memory instruction in that loop, so the
                 // compiler places no s_waitcnt vmcnt in it -- with a load inside (the refill below) it waits vmcnt(0) at the top
@@ -410,7 +409,7 @@ __global__ __launch_bounds__(512, 2) void tet_rhs_lane_kernel(I P, const I* __re
                                                               const unsigned char* __restrict__ lien,
                                                               const unsigned short* __restrict__ sub4,
                                                               const unsigned short* __restrict__ sub_start,
-                                                              const T* __restrict__ nodep, T* __restrict__ partial) {
+                                                              const T* __restrict__ nodep, T* __restrict__ partial, const StepK sk) {
     constexpr int NODES = 64;                  // node slots of a padded patch
     constexpr int WPB = 8;                     // waves per workgroup: one workgroup per CU, two waves per SIMD
     constexpr int RS = NV + 1;                 // padded node record in LDS
@@ -506,7 +505,7 @@ __global__ __launch_bounds__(512, 2) void tet_rhs_lane_kernel(I P, const I* __re
             const double DS = SHA - SHB;
             const double fb[3] = {FB0, FB1, FB2};
             const double mu = kMU / kRHO, kappa = kKAPPA / (kRHO * kCP);
-            const double t0 = 4.0 / (kDT * kDT);
+            const double t0 = sk.t0;
             const double wq = GW * detJ;
             double Su[3] = {0.0, 0.0, 0.0};  // vertex sums of u: both passes
             // ---- pass 1: momentum + continuity rows.  out[a*6+j] first collects (SHA-SHB) X_j(a) (the point q = a), then
@@ -712,6 +711,12 @@ static int g_rhs_lane_grid_cap = 0;  // test knob: few workgroups make a small m
 void dfl_set_rhs_lane_grid_cap(int workgroups) { g_rhs_lane_grid_cap = workgroups > 0 ? workgroups : 0; }
 void dfl_assemble_tet_lhs_slot(I npatch, const int32_t* hdr, const uint32_t* ptet_lid, const I* pnode, const I* slot_nz,
                                const uint32_t* ldesc, const T* nodep, T* val, T beta, I max_tets, void* stream) {
+    dfl_assemble_tet_lhs_slot_dt(npatch, hdr, ptet_lid, pnode, slot_nz, ldesc, nodep, val, beta, max_tets, dfl_step_consts_default(),
+                                 stream);
+}
+void dfl_assemble_tet_lhs_slot_dt(I npatch, const int32_t* hdr, const uint32_t* ptet_lid, const I* pnode, const I* slot_nz,
+                                  const uint32_t* ldesc, const T* nodep, T* val, T beta, I max_tets, const dfl_step_consts* k,
+                                  void* stream) {
     if (npatch <= 0) return;
     if (max_tets > SBLK) {
         fprintf(stderr, "dfl_assemble_tet_lhs_slot: patch limit exceeded (tets %d <= %d)\n", (int)max_tets, SBLK);
@@ -741,9 +746,9 @@ void dfl_assemble_tet_lhs_slot(I npatch, const int32_t* hdr, const uint32_t* pte
     if (!d_claim) DFL_GUARD(hipMalloc((void**)&d_claim, 8 * sizeof(int)));
     DFL_GUARD(hipMemsetAsync(d_claim, 0, 8 * sizeof(int), S(stream)));
     if (beta == 0.0)
-        tet_lhs_slot_kernel<true><<<grid, SBLK, lds, S(stream)>>>(npatch, h4, ptet_lid, pnode, slot_nz, ldesc, nodep, val, beta, max_tets, d_claim);
+        tet_lhs_slot_kernel<true><<<grid, SBLK, lds, S(stream)>>>(npatch, h4, ptet_lid, pnode, slot_nz, ldesc, nodep, val, beta, max_tets, d_claim, *k);
     else
-        tet_lhs_slot_kernel<false><<<grid, SBLK, lds, S(stream)>>>(npatch, h4, ptet_lid, pnode, slot_nz, ldesc, nodep, val, beta, max_tets, d_claim);
+        tet_lhs_slot_kernel<false><<<grid, SBLK, lds, S(stream)>>>(npatch, h4, ptet_lid, pnode, slot_nz, ldesc, nodep, val, beta, max_tets, d_claim, *k);
     DFL_LAUNCH_CHECK();
 }
 
@@ -751,6 +756,11 @@ void dfl_assemble_tet_lhs_slot(I npatch, const int32_t* hdr, const uint32_t* pte
 // LDS counter (see the kernel)
 void dfl_assemble_tet_rhs_lane(I npatch, const I* cnt, const I* pnode, const unsigned char* lien, const unsigned short* sub4,
                                const unsigned short* sub_start, const T* nodep, T* partial, void* stream) {
+    dfl_assemble_tet_rhs_lane_dt(npatch, cnt, pnode, lien, sub4, sub_start, nodep, partial, dfl_step_consts_default(), stream);
+}
+void dfl_assemble_tet_rhs_lane_dt(I npatch, const I* cnt, const I* pnode, const unsigned char* lien, const unsigned short* sub4,
+                                  const unsigned short* sub_start, const T* nodep, T* partial, const dfl_step_consts* k,
+                                  void* stream) {
     if (!nodep) { fprintf(stderr, "dfl_assemble_tet_rhs_lane: NULL node records\n"); abort(); }
     if (npatch <= 0) return;
     static int cus = 0;
@@ -764,7 +774,7 @@ void dfl_assemble_tet_rhs_lane(I npatch, const I* cnt, const I* pnode, const uns
     const int need = 8 * ((((npatch + 7) / 8) + 7) / 8);  // one wave per patch of an XCD's share
     if (g > need) g = need;
     if (g_rhs_lane_grid_cap > 0 && g > g_rhs_lane_grid_cap) g = (g_rhs_lane_grid_cap + 7) / 8 * 8;
-    tet_rhs_lane_kernel<<<g, 512, 0, S(stream)>>>(npatch, cnt, pnode, lien, sub4, sub_start, nodep, partial);
+    tet_rhs_lane_kernel<<<g, 512, 0, S(stream)>>>(npatch, cnt, pnode, lien, sub4, sub_start, nodep, partial, *k);
     DFL_LAUNCH_CHECK();
 }
 

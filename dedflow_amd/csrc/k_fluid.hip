@@ -50,7 +50,7 @@ __device__ __forceinline__ void fluid_gather_coefficients(const long long* n, I 
 
 // out[0..2] the momentum rows, out[3] the continuity row, and with NC = 6 out[4] = Rn_a, out[5] = Mn_a, of local node la
 template <int NC>
-__device__ __forceinline__ bool fluid_tet_node(const int4 n4, I row, I N, const T* __restrict__ xg, const T* __restrict__ w,
+__device__ __forceinline__ bool fluid_tet_node(const StepK& sk, const int4 n4, I row, I N, const T* __restrict__ xg, const T* __restrict__ w,
                                                const T* __restrict__ dw, const dfl_fluid_params& p, double* out) {
     const long long n[4] = {n4.x, n4.y, n4.z, n4.w};
     FluidTet t;
@@ -81,8 +81,8 @@ __device__ __forceinline__ bool fluid_tet_node(const int4 n4, I row, I N, const 
             fluid_row_point(g, v, la, q, pt);
             const double fq = sel4(q, t.fac);
             const double f[3] = {p.gravity[0] * fq, p.gravity[1] * fq, p.gravity[2] * fq};
-            fluid_E_add(g, rt, pt, sel4(q, t.rho), sel4(q, t.mu), f, E);
-            fluid_E_add(g, rt, pt, kRHO, kMU, f0, E0);
+            fluid_E_add(sk, g, rt, pt, sel4(q, t.rho), sel4(q, t.mu), f, E);
+            fluid_E_add(sk, g, rt, pt, kRHO, kMU, f0, E0);
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) out[k] = E[k] - E0[k];
@@ -105,9 +105,9 @@ __global__ __launch_bounds__(NG_BLK) void fluid_rows_kernel(I N, const I* __rest
                                                              const I* __restrict__ ien, const T* __restrict__ xg,
                                                              const T* __restrict__ w, const T* __restrict__ dw,
                                                              const dfl_fluid_params p, T* __restrict__ r, T* __restrict__ Rn,
-                                                             T* __restrict__ Mn, T* __restrict__ add) {
+                                                             T* __restrict__ Mn, T* __restrict__ add, const StepK sk) {
     const NodeSum s = node_gather_sum<NC>(N, vrow, vcol, [&](I e, I row, double* out) {
-        return fluid_tet_node<NC>(reinterpret_cast<const int4*>(ien)[e], row, N, xg, w, dw, p, out);
+        return fluid_tet_node<NC>(sk, reinterpret_cast<const int4*>(ien)[e], row, N, xg, w, dw, p, out);
     });
     if (!s.live) return;
     if (s.g < 4) {
@@ -129,7 +129,7 @@ __global__ __launch_bounds__(NG_BLK) void fluid_jac_row_kernel(I N, const I* __r
                                                                 const I* __restrict__ ien, const T* __restrict__ xg,
                                                                 const T* __restrict__ wg, const I* __restrict__ row_ptr,
                                                                 const I* __restrict__ col_ind, const dfl_fluid_params p,
-                                                                T* __restrict__ val) {
+                                                                T* __restrict__ val, const StepK sk) {
     __shared__ int4 s_node[FJ_SLOTS];
     __shared__ double2 s_blk[FJ_SLOTS][4][8];  // [slot][b][pair of entries]
     const int t = threadIdx.x;
@@ -171,13 +171,13 @@ __global__ __launch_bounds__(NG_BLK) void fluid_jac_row_kernel(I N, const I* __r
 #pragma unroll
                         for (int d = 0; d < 3; ++d) u[b][d] = wg[n[b] * 3 + d];
                     FluidJacTet jt;
-                    fluid_jac_tet(geo, u, tt.rho, tt.mu, jt);
+                    fluid_jac_tet(sk, geo, u, tt.rho, tt.mu, jt);
                     const double rho0[4] = {kRHO, kRHO, kRHO, kRHO}, mu0[4] = {kMU, kMU, kMU, kMU};
 #pragma unroll
                     for (int b = 0; b < 4; ++b) {
                         double B[16], B0[16];
-                        fluid_tet_B(geo, jt.c, la, b, tt.rho, tt.mu, jt.t0, jt.t1, B);
-                        fluid_tet_B(geo, jt.c, la, b, rho0, mu0, jt.t0b, jt.t1b, B0);
+                        fluid_tet_B(sk, geo, jt.c, la, b, tt.rho, tt.mu, jt.t0, jt.t1, B);
+                        fluid_tet_B(sk, geo, jt.c, la, b, rho0, mu0, jt.t0b, jt.t1b, B0);
 #pragma unroll
                         for (int e = 0; e < 16; ++e) jm[b][e] = B[e] - B0[e];
                     }
@@ -239,27 +239,39 @@ extern "C" {
 
 void dfl_fluid_rows(I N, const I* vrow, const I* vcol, const I* ien, const T* xg, const T* w, const T* dw,
                     const dfl_fluid_params* prm, T* r, T* Rn, T* Mn, void* stream) {
+    dfl_fluid_rows_dt(N, vrow, vcol, ien, xg, w, dw, prm, r, Rn, Mn, dfl_step_consts_default(), stream);
+}
+void dfl_fluid_rows_dt(I N, const I* vrow, const I* vcol, const I* ien, const T* xg, const T* w, const T* dw,
+                       const dfl_fluid_params* prm, T* r, T* Rn, T* Mn, const dfl_step_consts* k, void* stream) {
     if (N <= 0 || (!r && !Rn && !Mn)) return;
     if (Rn || Mn)
-        fluid_rows_kernel<6><<<ceil_div(N, NG_ROWS), NG_BLK, 0, S(stream)>>>(N, vrow, vcol, ien, xg, w, dw, *prm, r, Rn, Mn, nullptr);
+        fluid_rows_kernel<6><<<ceil_div(N, NG_ROWS), NG_BLK, 0, S(stream)>>>(N, vrow, vcol, ien, xg, w, dw, *prm, r, Rn, Mn, nullptr, *k);
     else
         fluid_rows_kernel<4><<<ceil_div(N, NG_ROWS), NG_BLK, 0, S(stream)>>>(N, vrow, vcol, ien, xg, w, dw, *prm, r, nullptr, nullptr,
-                                                                            nullptr);
+                                                                            nullptr, *k);
     DFL_LAUNCH_CHECK();
 }
 
 void dfl_fluid_add_rows(I N, const I* vrow, const I* vcol, const I* ien, const T* xg, const T* wgalpha, const T* dwgalpha,
                         const dfl_fluid_params* prm, T* F, void* stream) {
+    dfl_fluid_add_rows_dt(N, vrow, vcol, ien, xg, wgalpha, dwgalpha, prm, F, dfl_step_consts_default(), stream);
+}
+void dfl_fluid_add_rows_dt(I N, const I* vrow, const I* vcol, const I* ien, const T* xg, const T* wgalpha, const T* dwgalpha,
+                           const dfl_fluid_params* prm, T* F, const dfl_step_consts* k, void* stream) {
     if (N <= 0 || !F) return;
     fluid_rows_kernel<4><<<ceil_div(N, NG_ROWS), NG_BLK, 0, S(stream)>>>(N, vrow, vcol, ien, xg, wgalpha, dwgalpha, *prm, nullptr,
-                                                                        nullptr, nullptr, F);
+                                                                        nullptr, nullptr, F, *k);
     DFL_LAUNCH_CHECK();
 }
 
 void dfl_fluid_add_jacobian(I N, const I* vrow, const I* vcol, const I* ien, const T* xg, const T* wgalpha, const I* row_ptr,
                             const I* col_ind, const dfl_fluid_params* prm, T* val, void* stream) {
+    dfl_fluid_add_jacobian_dt(N, vrow, vcol, ien, xg, wgalpha, row_ptr, col_ind, prm, val, dfl_step_consts_default(), stream);
+}
+void dfl_fluid_add_jacobian_dt(I N, const I* vrow, const I* vcol, const I* ien, const T* xg, const T* wgalpha, const I* row_ptr,
+                               const I* col_ind, const dfl_fluid_params* prm, T* val, const dfl_step_consts* k, void* stream) {
     if (N <= 0 || !val) return;
-    fluid_jac_row_kernel<<<ceil_div(N, NG_ROWS), NG_BLK, 0, S(stream)>>>(N, vrow, vcol, ien, xg, wgalpha, row_ptr, col_ind, *prm, val);
+    fluid_jac_row_kernel<<<ceil_div(N, NG_ROWS), NG_BLK, 0, S(stream)>>>(N, vrow, vcol, ien, xg, wgalpha, row_ptr, col_ind, *prm, val, *k);
     DFL_LAUNCH_CHECK();
 }
 

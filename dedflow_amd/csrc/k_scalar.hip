@@ -31,7 +31,7 @@ namespace {
 // are formed beside the base ones from the same geometry and added to the finished jt[b] (the base is rounded first).  The
 // conduction part depends on q through dk_q alone, so it is w kg[b] (sum_q dk_q) / kKAPPA: jm[b] starts from it
 template <bool MATERIAL>
-__device__ __forceinline__ void scalar_tet_row(const double* x, const double* u, int la, double* jp, double* jt,
+__device__ __forceinline__ void scalar_tet_row(const StepK& sk, const double* x, const double* u, int la, double* jp, double* jt,
                                                const double* dk = nullptr, const double* dc = nullptr, bool any = false) {
     double invJ[9], shg[12], G[9], detJ;
     tet_geometry(x, invJ, detJ, shg);
@@ -39,8 +39,8 @@ __device__ __forceinline__ void scalar_tet_row(const double* x, const double* u,
     double gg = 0.0;
 #pragma unroll
     for (int k = 0; k < 9; ++k) gg += G[k] * G[k];
-    const double f1 = kALPHAM, f2 = kDT * kALPHAF * kGAMMA;
-    const double t0 = 4.0 / (kDT * kDT);
+    const double f1 = kALPHAM, f2 = sk.fact2;
+    const double t0 = sk.t0;
     const double kappa = kKAPPA / (kRHO * kCP);
     const double rc = kRHO * kCP;
     const double w = GW * detJ;
@@ -49,7 +49,7 @@ __device__ __forceinline__ void scalar_tet_row(const double* x, const double* u,
     for (int b = 0; b < 4; ++b) {
         jp[b] = 0.0;
         jt[b] = 0.0;
-        kg[b] = f2 * kKAPPA * (shg[la * 3] * shg[b * 3] + shg[la * 3 + 1] * shg[b * 3 + 1] + shg[la * 3 + 2] * shg[b * 3 + 2]);
+        kg[b] = sk.fact2_kappa * (shg[la * 3] * shg[b * 3] + shg[la * 3 + 1] * shg[b * 3 + 1] + shg[la * 3 + 2] * shg[b * 3 + 2]);
     }
     double jm[4];
     if constexpr (MATERIAL) {
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(NG_BLK) void scalar_jac_row_kernel(I N, const I* __
                                                                  const I* __restrict__ ien, const T* __restrict__ xg,
                                                                  const T* __restrict__ wg, const I* __restrict__ row_ptr,
                                                                  const I* __restrict__ col_ind, T* __restrict__ vphi,
-                                                                 T* __restrict__ vT, const MaterialArg<MATERIAL> mat) {
+                                                                 T* __restrict__ vT, const MaterialArg<MATERIAL> mat, const StepK sk) {
     __shared__ int4 s_node[NG_BLK];
     __shared__ double s_jp[NG_BLK][4];
     __shared__ double s_jt[NG_BLK][4];
@@ -155,9 +155,9 @@ __global__ __launch_bounds__(NG_BLK) void scalar_jac_row_kernel(I N, const I* __
                     thermal_metal_fraction(c, phi, mat, m);
                     thermal_kc(m, Tn, mat, kq, cq);
                     const bool any = thermal_differences(kq, cq, dk, dc);
-                    scalar_tet_row<true>(x, u, la, jp, jt, dk, dc, any);
+                    scalar_tet_row<true>(sk, x, u, la, jp, jt, dk, dc, any);
                 } else {
-                    scalar_tet_row<false>(x, u, la, jp, jt);
+                    scalar_tet_row<false>(sk, x, u, la, jp, jt);
                 }
                 s_node[t] = n4;
 #pragma unroll
@@ -192,17 +192,29 @@ __global__ __launch_bounds__(NG_BLK) void scalar_jac_row_kernel(I N, const I* __
 
 extern "C" void dfl_assemble_scalar_jacobian(I N, const I* vrow, const I* vcol, const I* ien, const T* xg, const T* wgalpha,
                                              const I* row_ptr, const I* col_ind, T* val_phi, T* val_T, void* stream) {
+    dfl_assemble_scalar_jacobian_dt(N, vrow, vcol, ien, xg, wgalpha, row_ptr, col_ind, val_phi, val_T, dfl_step_consts_default(), stream);
+}
+extern "C" void dfl_assemble_scalar_jacobian_dt(I N, const I* vrow, const I* vcol, const I* ien, const T* xg, const T* wgalpha,
+                                                const I* row_ptr, const I* col_ind, T* val_phi, T* val_T,
+                                                const dfl_step_consts* k, void* stream) {
     if (N <= 0 || (!val_phi && !val_T)) return;
     scalar_jac_row_kernel<false><<<ceil_div(N, NG_ROWS), NG_BLK, 0, S(stream)>>>(N, vrow, vcol, ien, xg, wgalpha, row_ptr, col_ind,
-                                                                                 val_phi, val_T, NoMaterial{});
+                                                                                 val_phi, val_T, NoMaterial{}, *k);
     DFL_LAUNCH_CHECK();
 }
 
 extern "C" void dfl_assemble_scalar_jacobian_material(I N, const I* vrow, const I* vcol, const I* ien, const T* xg, const T* wgalpha,
                                                       const I* row_ptr, const I* col_ind, const dfl_thermal_params* prm,
                                                       T* val_phi, T* val_T, void* stream) {
+    dfl_assemble_scalar_jacobian_material_dt(N, vrow, vcol, ien, xg, wgalpha, row_ptr, col_ind, prm, val_phi, val_T,
+                                             dfl_step_consts_default(), stream);
+}
+extern "C" void dfl_assemble_scalar_jacobian_material_dt(I N, const I* vrow, const I* vcol, const I* ien, const T* xg,
+                                                         const T* wgalpha, const I* row_ptr, const I* col_ind,
+                                                         const dfl_thermal_params* prm, T* val_phi, T* val_T,
+                                                         const dfl_step_consts* k, void* stream) {
     if (N <= 0 || (!val_phi && !val_T)) return;
     scalar_jac_row_kernel<true><<<ceil_div(N, NG_ROWS), NG_BLK, 0, S(stream)>>>(N, vrow, vcol, ien, xg, wgalpha, row_ptr, col_ind,
-                                                                                val_phi, val_T, *prm);
+                                                                                val_phi, val_T, *prm, *k);
     DFL_LAUNCH_CHECK();
 }

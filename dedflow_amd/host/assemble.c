@@ -155,22 +155,22 @@ void DflAssembleSystemTetBeta(Mesh3D* mesh, f64* wgalpha_dptr, f64* dwgalpha_dpt
         const index_type bsz = x->sched_offset[b + 1] - off;
         if (bsz == 0) continue;
         const index_type* ien_b = x->ien_b + (size_t)off * 4;
-        if (F && !patch_rhs) DFL_TIMED(DFL_TAG_ASM_RHS, dfl_assemble_tet_rhs(bsz, ien_b, x->nodep, x->Fp, s));
+        if (F && !patch_rhs) DFL_TIMED(DFL_TAG_ASM_RHS, dfl_assemble_tet_rhs_dt(bsz, ien_b, x->nodep, x->Fp, &x->step, s));
         if (J && !slot_lhs)
-            DFL_TIMED(DFL_TAG_ASM_LHS, dfl_assemble_tet_lhs(bsz, ien_b, x->nzmap_b + (size_t)off * 16, x->egeo_b + (size_t)off * 16,
-                                                            x->nodep, val, s));
+            DFL_TIMED(DFL_TAG_ASM_LHS, dfl_assemble_tet_lhs_dt(bsz, ien_b, x->nzmap_b + (size_t)off * 16, x->egeo_b + (size_t)off * 16,
+                                                               x->nodep, val, &x->step, s));
     }
     if (slot_lhs) { /* schedule 4: ONE launch, every nodal nonzero is summed in registers by its owner lanes (host/slotpatch.c) */
         const SlotPatchSched* ss = x->slotpatch;
-        DFL_TIMED(DFL_TAG_ASM_LHS, dfl_assemble_tet_lhs_slot(ss->num_patch, ss->d_hdr, ss->d_ptet_lid, ss->d_pnode, ss->d_slot_nz, ss->d_ldesc,
-                                                             x->nodexu, val, beta_J, ss->max_tets, s));
+        DFL_TIMED(DFL_TAG_ASM_LHS, dfl_assemble_tet_lhs_slot_dt(ss->num_patch, ss->d_hdr, ss->d_ptet_lid, ss->d_pnode, ss->d_slot_nz, ss->d_ldesc,
+                                                                x->nodexu, val, beta_J, ss->max_tets, &x->step, s));
     }
     if (patch_rhs) { /* schedule 4: patch-staged residual, two launches, fixed summation order (host/patch.c) */
         if (!x->rhspatch) x->rhspatch = DflBuildRhsPatchSchedule(mesh);
         const RhsPatchSched* rp = x->rhspatch;
         int slot = DflProfileBegin(DFL_TAG_ASM_RHS);
-        dfl_assemble_tet_rhs_lane(rp->num_patch, rp->d_cnt, rp->d_pnode, rp->d_lien, rp->d_sub4, rp->d_sub_start, x->nodep,
-                                  rp->d_partial, s);
+        dfl_assemble_tet_rhs_lane_dt(rp->num_patch, rp->d_cnt, rp->d_pnode, rp->d_lien, rp->d_sub4, rp->d_sub_start, x->nodep,
+                                     rp->d_partial, &x->step, s);
         dfl_rhs_node_sum(N, rp->d_goff, rp->d_gidx, rp->d_partial, F, s);
         DflProfileEnd(slot);
     } else if (F) {
@@ -196,8 +196,8 @@ void AssembleSystemTetFace(Mesh3D* mesh, f64* wgalpha_dptr, f64* dwgalpha_dptr, 
     int slot = DflProfileBegin(DFL_TAG_FACE);
     if (spy) DflMeshPrepareFaceNonzeros(mesh, group, spy);
     /* pass 1: every face parks its terms; pass 2: ordered sums into F and the block values */
-    dfl_assemble_face_park(x->face_nf, f2e, forn, dev->ien, N, dev->xg, wgalpha_dptr, dwgalpha_dptr, F ? x->face_pF : NULL,
-                           spy ? x->face_pJ : NULL, s);
+    dfl_assemble_face_park_dt(x->face_nf, f2e, forn, dev->ien, N, dev->xg, wgalpha_dptr, dwgalpha_dptr, F ? x->face_pF : NULL,
+                              spy ? x->face_pJ : NULL, &x->step, s);
     if (F) dfl_face_sum_F(x->face_nn, x->face_node, x->face_node_off, x->face_node_ent, x->face_pF, N, F, s);
     if (spy) dfl_face_sum_J(x->face_nnz, x->face_nz, x->face_nz_off, x->face_nz_ent, x->face_pJ, val, s);
     DflProfileEnd(slot);

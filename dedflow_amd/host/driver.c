@@ -44,7 +44,8 @@ void DflFreeFlowWork(FlowWork* fw) {
  * the packed node records the assembly kernels gather from -- the two AssembleSystem calls that follow skip their pack */
 static void alpha_states(Mesh3D* mesh, const f64* wgold, const f64* dwgold, const f64* dwg, f64* wgalpha, f64* dwgalpha) {
     const f64 fact1[] = {1.0 - kALPHAM, kALPHAM};
-    const f64 fact2[] = {kDT * kALPHAF * (1.0 - kGAMMA), kDT * kALPHAF * kGAMMA};
+    const dfl_step_consts* k = DflMeshStepConsts(mesh);
+    const f64 fact2[] = {k->states_old, k->fact2};
     ((MeshExt*)mesh->ext)->phase_current = FALSE; /* new states: the phase-change coefficients of the old ones are stale */
     f64* const nodep = DflMeshNodeRecords(mesh); /* (allocates the compact (x, u) records of the Jacobian kernel as well) */
     dfl_alpha_states2(Mesh3DNumNode(mesh), wgold, dwgold, dwg, fact1[0], fact1[1], fact2[0], fact2[1], Mesh3DDevice(mesh)->xg, wgalpha,
@@ -159,7 +160,7 @@ index_type SolveFlowSystem(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matr
  * With a laser surface set on the coupled context (ParticleContextSetLaserSurface), ParticleContextLaserSurfaceUpdate runs
  * once, before the first particle sub-step, in the state those sub-steps see.
  * With a solidification record set on the mesh with in_time_step (DflMeshSetSolidification), the record is updated with the
- * new wgold and kDT right after the step has written it; the first such call primes the record at its incoming wgold.
+ * new wgold and the mesh's time step right after the step has written it; the first such call primes the record at its incoming wgold.
  * With track cross-sections set on the mesh with every > 0 (DflMeshSetTrackSections), every every-th call evaluates them at
  * the new wgold, after that record, whose T_peak they read. */
 index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* J, f64* F, f64* dx, Krylov* ksp, Dirichlet** bcs,
@@ -168,7 +169,8 @@ index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* 
     const index_type N = Mesh3DNumNode(mesh);
     hipStream_t s = DflStream();
     const f64 fac_pred = (kGAMMA - 1.0) / kGAMMA;
-    const f64 fac_corr[] = {kDT * (1.0 - kGAMMA), kDT * kGAMMA};
+    const dfl_step_consts* k = DflMeshStepConsts(mesh); /* read once: the step of this call */
+    const f64 fac_corr[] = {k->corr_old, k->corr_new};
     const b32 coupled = pctx && DflParticleCoupledMesh(pctx) == mesh;
     if (coupled && KrylovGetComm(ksp)) {
         fprintf(stderr, "DflTimeStep: particle-fluid coupling is single-GPU only; the solver has a communicator: step refused\n");
@@ -235,7 +237,7 @@ index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* 
        heat rates on top of the load and the heat source, in the capture's own buffers */
     const f64* user_vol = DflMeshVolumeSource(mesh);
     f64 *cap_vol = NULL, *cap_load = NULL, *cap_heat = NULL;
-    if (coupled && DflCaptureTakePending(pctx, kDT, &cap_vol, &cap_load, &cap_heat)) {
+    if (coupled && DflCaptureTakePending(pctx, k->dt, &cap_vol, &cap_load, &cap_heat)) {
         ASSERT(!user_vol && "DflTimeStep: a two-way capture step cannot add to a volume source already registered");
         DflMeshSetVolumeSource(mesh, cap_vol);
         if (reaction) dfl_daxpy(3 * N, 1.0, reaction, cap_load, s);
@@ -265,7 +267,7 @@ index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* 
     if (heat) DflMeshSetHeatSource(mesh, user_heat);
     if (cap_vol) {
         DflMeshSetVolumeSource(mesh, user_vol);
-        DflVolumeCorrectionCaptured(mesh, cap_vol, kDT); /* track_capture: the target follows what was deposited */
+        DflVolumeCorrectionCaptured(mesh, cap_vol, k->dt); /* track_capture: the target follows what was deposited */
     }
     if (pctx && !coupled)
         for (index_type k = 0; k < dem_substeps; ++k) ParticleContextUpdate(pctx); /* coupled step: contact sweep (config 4) */

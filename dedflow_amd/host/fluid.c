@@ -88,6 +88,7 @@ void DflMeshSetFluidMaterial(Mesh3D* mesh, const DflFluidMaterial* cfg) {
 }
 
 b32 DflMeshFluidMaterialEnabled(const Mesh3D* mesh) { return st_of(mesh) != NULL; }
+const DflFluidMaterial* DflFluidConfig(const Mesh3D* mesh) { return st_of(mesh) ? &st_of(mesh)->cfg : NULL; }
 
 void DflMeshFluidRows(Mesh3D* mesh, const f64* w, const f64* dw, f64* r, f64* Rn, f64* Mn) {
     FluidState* st = st_of(mesh);
@@ -100,7 +101,7 @@ void DflMeshFluidRows(Mesh3D* mesh, const f64* w, const f64* dw, f64* r, f64* Rn
     const index_type *vrow, *vcol;
     DflMeshSortedV2E(mesh, &vrow, &vcol);
     DflRangePush("DflMeshFluidRows");
-    dfl_fluid_rows(st->N, vrow, vcol, dev->ien, dev->xg, w, dw, &st->prm, r, Rn, Mn, DflStream());
+    dfl_fluid_rows_dt(st->N, vrow, vcol, dev->ien, dev->xg, w, dw, &st->prm, r, Rn, Mn, DflMeshStepConsts(mesh), DflStream());
     DflRangePop();
 }
 
@@ -111,7 +112,7 @@ void DflFluidApplySystem(Mesh3D* mesh, const f64* wgalpha, const f64* dwgalpha, 
     const index_type *vrow, *vcol;
     DflMeshSortedV2E(mesh, &vrow, &vcol);
     DflRangePush("FluidMaterial(F,J)");
-    if (F) dfl_fluid_add_rows(st->N, vrow, vcol, dev->ien, dev->xg, wgalpha, dwgalpha, &st->prm, F, DflStream());
+    if (F) dfl_fluid_add_rows_dt(st->N, vrow, vcol, dev->ien, dev->xg, wgalpha, dwgalpha, &st->prm, F, DflMeshStepConsts(mesh), DflStream());
     if (J) {
         value_type* val = MatrixFSBlockValues(J);
         if (!val) {
@@ -120,7 +121,8 @@ void DflFluidApplySystem(Mesh3D* mesh, const f64* wgalpha, const f64* dwgalpha, 
             ASSERT(FALSE && "fluid material with a reference-layout FS matrix");
         }
         const CSRAttr* spy = ((MatrixFS*)J->data)->spy1x1;
-        dfl_fluid_add_jacobian(st->N, vrow, vcol, dev->ien, dev->xg, wgalpha, spy->row_ptr, spy->col_ind, &st->prm, val, DflStream());
+        dfl_fluid_add_jacobian_dt(st->N, vrow, vcol, dev->ien, dev->xg, wgalpha, spy->row_ptr, spy->col_ind, &st->prm, val,
+                                  DflMeshStepConsts(mesh), DflStream());
     }
     DflRangePop();
 }

@@ -87,15 +87,25 @@ typedef struct MeshExt {
     struct SolidifyState* solidify; /* solidification record (host/solidify.c, DflMeshSetSolidification), NULL: off */
     struct TrackState* track;      /* track cross-sections (host/track.c, DflMeshSetTrackSections), NULL: off */
     index_type *v2e_row, *v2e_col; /* device [N+1], [4T]: the sorted V2E map (DflMeshSortedV2E), NULL until first asked for */
+    dfl_step_consts step;          /* the time step of this mesh and everything derived from it (host/timestep.c): DflMeshStepConsts */
+    struct StepLimitState* steplimit; /* DflMeshTimeStepLimits: partials and results, sized at the first call (host/timestep.c) */
     uint64_t geom_epoch;           /* counts DflMeshGeometryChanged: what a particle context derived from the coordinates is stale */
 } MeshExt;
 
 /* the generalized-alpha constants of the time integration (src/assemble.cu:23-27), textually those of csrc/asm_device.hpp */
 #define kRHOC (0.5)
-#define kDT (5e-2)
 #define kALPHAM ((3.0 - kRHOC) / (1.0 + kRHOC))
 #define kALPHAF (1.0 / (1.0 + kRHOC))
 #define kGAMMA (0.5 + kALPHAM - kALPHAF)
+
+/* the time step of a mesh (include/dedflow.h, "time step"; host/timestep.c): what the kernels and the driver take from it, derived
+ * by dfl_step_consts_from_dt alone when the mesh is made and whenever DflMeshSetTimeStep accepts a step.  Read it at the call */
+static inline const dfl_step_consts* DflMeshStepConsts(const Mesh3D* mesh) { return &((const MeshExt*)mesh->ext)->step; }
+struct StepLimitState;
+void DflStepLimitFree(struct StepLimitState* st);
+/* the configurations the step limits read (host/surface.c, host/fluid.c): NULL while the feature is off */
+const DflSurfaceForces* DflSurfaceConfig(const Mesh3D* mesh);
+const DflFluidMaterial* DflFluidConfig(const Mesh3D* mesh);
 
 /* the sorted V2E map of a mesh: per node its tets in ascending tet id, device [N + 1] and [4T].  One per mesh, shared by every
  * pass that sums over a node's tets in that order (scalar Jacobians, free-surface forces, phase change, the particle
@@ -492,7 +502,7 @@ void DflSolidificationFree(struct SolidifyState* st);
 b32 DflSolidificationInTimeStep(const Mesh3D* mesh);            /* a configuration with in_time_step is set */
 /* DflTimeStep, on entry: with in_time_step and a record not primed yet, the priming update at the incoming wgold */
 void DflSolidificationTimeStepPrime(Mesh3D* mesh, const f64* wgold);
-/* DflTimeStep, once the step has written wgold: with in_time_step, DflMeshSolidificationUpdate(mesh, wgold, kDT) */
+/* DflTimeStep, once the step has written wgold: with in_time_step, DflMeshSolidificationUpdate(mesh, wgold, DflMeshTimeStep(mesh)) */
 void DflSolidificationTimeStep(Mesh3D* mesh, const f64* wgold);
 /* T_prev [N] and the metal flags [N] of the record on the device (tests, probes); NULL when not set */
 void DflSolidificationTestFields(const Mesh3D* mesh, const f64** T_prev, const u8** metal);

@@ -57,6 +57,7 @@ Mesh3D* Mesh3DCreate(index_type nn, index_type nt, index_type np, index_type nh)
     memset(x, 0, sizeof *x);
     x->face_group = -1;
     x->cfg = *DflAsmDefaults();
+    dfl_step_consts_from_dt(DFL_DEFAULT_TIME_STEP, &x->step);
     m->ext = x;
     return m;
 }
@@ -105,6 +106,7 @@ void Mesh3DDestroy(Mesh3D* m) {
         DflVolumeCorrectionFree(x->volume);
         DflSolidificationFree(x->solidify);
         DflTrackSectionsFree(x->track);
+        DflStepLimitFree(x->steplimit);
         CdamFreeDevice(x->v2e_row, 0); /* after the feature states that borrowed it */
         CdamFreeDevice(x->v2e_col, 0);
         CdamFreeDevice(x->egeo_b, 0);

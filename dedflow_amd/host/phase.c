@@ -179,7 +179,7 @@ void DflPhaseApplySystem(Mesh3D* mesh, const f64* wgalpha, const f64* dwgalpha, 
             ASSERT(FALSE && "phase-change drag with a reference-layout FS matrix");
         }
         const CSRAttr* spy = ((MatrixFS*)J->data)->spy1x1;
-        dfl_phase_apply_J(st->N, spy->row_ptr, spy->col_ind, st->D, kDT * kALPHAF * kGAMMA, val, s);
+        dfl_phase_apply_J(st->N, spy->row_ptr, spy->col_ind, st->D, DflMeshStepConsts(mesh)->fact2, val, s);
     }
     DflRangePop();
 }

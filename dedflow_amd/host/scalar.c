@@ -131,15 +131,16 @@ static void assemble_scalar_jacobian(Mesh3D* mesh, f64* wgalpha, Matrix* Jphi, M
     /* thermal material (include/dedflow.h): the launch that forms JT is the MATERIAL instantiation, which adds the entries jm
        per tet; Jphi gets the same bits from either */
     const dfl_thermal_params* mat = JT ? DflThermalParams(mesh) : NULL;
+    const dfl_step_consts* k = DflMeshStepConsts(mesh);
     DflRangePush("AssembleScalarJacobian");
     if (ap && at && ap != at) { /* two pattern objects: one launch each */
-        dfl_assemble_scalar_jacobian(N, vrow, vcol, dev->ien, dev->xg, wgalpha, ap->row_ptr, ap->col_ind, vp, NULL, s);
-        if (mat) dfl_assemble_scalar_jacobian_material(N, vrow, vcol, dev->ien, dev->xg, wgalpha, at->row_ptr, at->col_ind, mat, NULL, vt, s);
-        else dfl_assemble_scalar_jacobian(N, vrow, vcol, dev->ien, dev->xg, wgalpha, at->row_ptr, at->col_ind, NULL, vt, s);
+        dfl_assemble_scalar_jacobian_dt(N, vrow, vcol, dev->ien, dev->xg, wgalpha, ap->row_ptr, ap->col_ind, vp, NULL, k, s);
+        if (mat) dfl_assemble_scalar_jacobian_material_dt(N, vrow, vcol, dev->ien, dev->xg, wgalpha, at->row_ptr, at->col_ind, mat, NULL, vt, k, s);
+        else dfl_assemble_scalar_jacobian_dt(N, vrow, vcol, dev->ien, dev->xg, wgalpha, at->row_ptr, at->col_ind, NULL, vt, k, s);
     } else {
         const CSRAttr* a = ap ? ap : at;
-        if (mat) dfl_assemble_scalar_jacobian_material(N, vrow, vcol, dev->ien, dev->xg, wgalpha, a->row_ptr, a->col_ind, mat, vp, vt, s);
-        else dfl_assemble_scalar_jacobian(N, vrow, vcol, dev->ien, dev->xg, wgalpha, a->row_ptr, a->col_ind, vp, vt, s);
+        if (mat) dfl_assemble_scalar_jacobian_material_dt(N, vrow, vcol, dev->ien, dev->xg, wgalpha, a->row_ptr, a->col_ind, mat, vp, vt, k, s);
+        else dfl_assemble_scalar_jacobian_dt(N, vrow, vcol, dev->ien, dev->xg, wgalpha, a->row_ptr, a->col_ind, vp, vt, k, s);
     }
     /* latent heat (include/dedflow.h, "phase change"): kALPHAM H on the T diagonal, before the Dirichlet unit rows */
     if (JT && ((MeshExt*)mesh->ext)->phase) DflPhaseApplyScalarJacobian(mesh, wgalpha, at, vt, phase_reuse);

@@ -241,9 +241,9 @@ b32 DflSolidificationInTimeStep(const Mesh3D* mesh) {
 void DflSolidificationTimeStepPrime(Mesh3D* mesh, const f64* wgold) {
     SolidifyState* st = st_of(mesh);
     if (!st || !st->cfg.in_time_step || st->primed) return;
-    DflMeshSolidificationUpdate(mesh, wgold, kDT);
+    DflMeshSolidificationUpdate(mesh, wgold, DflMeshTimeStep(mesh));
 }
 
 void DflSolidificationTimeStep(Mesh3D* mesh, const f64* wgold) {
-    if (DflSolidificationInTimeStep(mesh)) DflMeshSolidificationUpdate(mesh, wgold, kDT);
+    if (DflSolidificationInTimeStep(mesh)) DflMeshSolidificationUpdate(mesh, wgold, DflMeshTimeStep(mesh));
 }

@@ -99,6 +99,7 @@ void DflMeshSetSurfaceForces(Mesh3D* mesh, const DflSurfaceForces* cfg) {
 }
 
 b32 DflMeshSurfaceForcesEnabled(const Mesh3D* mesh) { return st_of(mesh) != NULL; }
+const DflSurfaceForces* DflSurfaceConfig(const Mesh3D* mesh) { return st_of(mesh) ? &st_of(mesh)->cfg : NULL; }
 
 void DflMeshSurfaceLoad(Mesh3D* mesh, const f64* w, f64* load, f64* q_heat, f64* area) {
     SurfaceState* st = st_of(mesh);

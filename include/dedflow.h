@@ -590,6 +590,52 @@ struct ParticleContext;
 index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* J, f64* F, f64* dx, Krylov* ksp, Dirichlet** bcs,
                        index_type nbc, index_type newton_maxit, struct ParticleContext* pctx, index_type dem_substeps,
                        f64* rnorm_out, f64* rnorm_init_out);
+/* ---- time step: a per-mesh dt, and the step limits of a state (build-defined) ----------------------------------------------
+ * The reference steps with a compile-time literal (src/main.c:24, src/assemble.cu:24).  Here every mesh carries its own step,
+ * DFL_DEFAULT_TIME_STEP until DflMeshSetTimeStep accepts another, and everything that uses dt reads the mesh's value at the
+ * call: the volume and weak-BC face kernels of F and J under every schedule, the scalar residual rows and Jacobians, the
+ * thermal-material Jacobian entries, the fluid-material rows and blocks, the phase-change J diagonal, the alpha states, the
+ * predictor / corrector of DflTimeStep, the time window of a two-way capture source and of the volume target that follows it,
+ * the solidification record's in_time_step updates, and DflScalarTransportSolve.  dt enters the kernels as kernel arguments
+ * formed by one host function (dfl_step_consts_from_dt, include/dedflow_kernels.h); at the default step every result has the
+ * bits of the compile-time build.  The step may change between any two calls and two meshes in one process may differ;
+ * nothing cached depends on it.  In a partitioned run every rank sets the step of its own mesh.  The particle context's own
+ * dt (ParticleContextSetContactModel) and dem_substeps stay the caller's business.
+ *
+ * Step limits of a state w (level: the surface phi = level).  No fused multiply-add anywhere; dot products are
+ * (a0 b0 + a1 b1) + a2 b2.  Per tet e with nodes n_a, g_a = grad N_a in the closed form of the melt-pool capture section
+ * (g_1 = c23 / det, g_2 = c31 / det, g_3 = c12 / det, g_0d = -((g_1d + g_2d) + g_3d)):
+ *   ubar_d = 0.25 (((u_0d + u_1d) + u_2d) + u_3d),  c_a = ubar . g_a,  r_e = max_a |c_a|   (the rate at which a material
+ *               point's barycentric coordinate changes: 1 / r_e is the time the fluid takes to cross the tet's altitude)
+ *   m_e = max_a (g_a . g_a)                        1 / (shortest altitude)^2
+ *   f_a = phi_a - level; the tet is CUT iff not all f_a > 0 and not all f_a < 0 (phi equal to level at a vertex: cut)
+ *   Tbar        the vertex mean of T, formed as ubar
+ *   sigma_e = max(0, sigma0 + dsigma_dT (Tbar - T_ref)) from the mesh's DflSurfaceForces, 0 when none is set
+ *   q_e = sigma_e (m_e sqrt(m_e))                  sigma / h^3
+ *   a tet is NON-FINITE when any of its twelve gradient entries, ubar, Tbar or any f_a is not finite: it is counted and takes
+ *               part in no maximum.  A NaN never wins a comparison.
+ * rate_adv = max r_e over the finite tets, rate_adv_surface = max r_e and cap_q = max q_e over the cut ones; each with the
+ * lowest tet id that attains it.  The host finishes dt_adv = 1 / rate_adv, dt_surface = 1 / rate_adv_surface and
+ * dt_capillary = sqrt(rho_bar / (2 pi cap_q)), the explicit surface-tension bound of the free-surface section, with
+ * rho_bar = 0.5 (rho_gas + rho_metal) of the fluid material when one is set, else the built-in density.  The implicit parts
+ * (viscosity, conduction, Darcy drag) impose no bound and get none.  One pass over the tets and a one-workgroup second stage,
+ * no atomics: maxima and "the lowest id" are exact in any order, two runs agree bit for bit.  The state is sized at the first
+ * call on a mesh and freed with it; later calls allocate nothing.  DflTimeStep does not adapt the step itself: with the setter
+ * and the limits a controller is a few lines in the caller's loop. */
+#ifndef DFL_DEFAULT_TIME_STEP
+#define DFL_DEFAULT_TIME_STEP (5e-2)               /* the reference's kDT */
+#endif
+int  DflTimeStepCheck(f64 dt, char* why, size_t why_len);   /* host only; 0 = accepted: finite and > 0 */
+void DflMeshSetTimeStep(Mesh3D* mesh, f64 dt);     /* refused on stderr, mesh unchanged, when the check refuses */
+f64  DflMeshTimeStep(const Mesh3D* mesh);          /* DFL_DEFAULT_TIME_STEP until set */
+typedef struct DflTimeStepLimits {
+    f64 rate_adv, rate_adv_surface, cap_q;     /* maxima over the tets, above; 0 when no tet qualifies */
+    index_type tet_adv, tet_surface, tet_cap;  /* the lowest tet id that attains each maximum; -1 when none */
+    index_type num_cut, num_nonfinite;         /* cut tets; tets left out of every maximum */
+    f64 dt_adv, dt_surface, dt_capillary;      /* 1 / rate_adv, 1 / rate_adv_surface, sqrt(rho_bar / (2 pi cap_q)); HUGE_VAL when the maximum is 0 */
+    f64 dt;                                    /* DflMeshTimeStep(mesh) at the call */
+} DflTimeStepLimits;
+void DflMeshTimeStepLimits(Mesh3D* mesh, const f64* w, f64 level, DflTimeStepLimits* out);  /* w: device 6N state; waits for the device once */
 /* ---- scalar transport: level set phi and temperature T (build-defined; opt-in) -------------------------------------------
  * The residual has SUPG rows for phi (advection) and T (advection-diffusion) (src/assemble.cu:885-906), but the reference
  * zeroes them before the solve (main.c:63-66) and its matrix has no phi / T blocks, so neither field ever moves.  With a
@@ -1256,7 +1302,7 @@ void ParticleContextLaserSurfacePower(ParticleContext* ctx, f64* q);
  *               residual is R_p = (...) - q_V, after the tet and face terms and before the Dirichlet rows, so the converged
  *               field has int N_a div u = q_V[a]: the velocity diverges where metal arrives, the level set moves out with
  *               u, and the liquid volume grows by the deposited volume.  Explicit: not in J.
- *   time step   with two_way and something pending, DflTimeStep takes the source with time = kDT, registers q_vol as the
+ *   time step   with two_way and something pending, DflTimeStep takes the source with time = dt (the mesh's time step), registers q_vol as the
  *               volume source (one already registered is an ASSERT, as for the load), adds the momentum rate to the load
  *               and the heat rate to the heat source it registers (in the capture's own buffers, together with the reaction
  *               load / particle heat source when those are pending too) and restores the caller's registrations after the
@@ -1400,7 +1446,7 @@ void ParticleContextSurfaceContactStats(const ParticleContext* ctx, DflSurfaceCo
  *               the reaction load) and restores the caller's registrations after the solve.  With a communicator it prints
  *               why and returns -1.
  * Explicit surface tension is stable only below the capillary time step, dt < sqrt(rho h^3 / (2 pi sigma)) with h the tet
- * size at the surface: keeping the step (kDT) below it is the caller's condition, nothing here checks it.  The mass the
+ * size at the surface: keeping the step (DflMeshSetTimeStep) below it is the caller's condition: DflMeshTimeStepLimits reports it as dt_capillary.  The mass the
  * evaporation carries away is not modelled: evap_q0 is a heat loss only; the latent heat of melting is the phase-change
  * section's. */
 typedef struct DflSurfaceForces {
@@ -1453,7 +1499,7 @@ void DflMeshSurfaceLoad(Mesh3D* mesh, const f64* w, f64* load, f64* q_heat, f64*
  *               band thinner than an element is still seen.  Every F assembly adds, after the tet and face terms and the
  *               sources and before the T rows are saved for the scalar transport and the Dirichlet rows are applied,
  *                 R[3a + d] += D_a u_a[d]     (u from wgalpha),       R[5N + a] += H_a dT_a     (dT from dwgalpha),
- *               with D and H evaluated at (wgalpha, dwgalpha).  Every J assembly adds fact2 D_a, fact2 = kDT kALPHAF kGAMMA,
+ *               with D and H evaluated at (wgalpha, dwgalpha).  Every J assembly adds fact2 D_a, fact2 = dt kALPHAF kGAMMA,
  *               to the entries (d, d), d < 3, of node a's diagonal 4x4 block: D depends on T only, so this is the exact
  *               derivative with respect to the velocity rates.  J must have the block layout: drag with a
  *               reference-layout FS matrix is an ASSERT.  DflAssembleScalarJacobian adds kALPHAM H_a to the diagonal of
@@ -1524,7 +1570,7 @@ void DflMeshPhaseChangeStats(Mesh3D* mesh, const f64* w, DflPhaseChangeStats* ou
  *               is sum_q W c_q N_a N_b, positive definite whenever c_q > 0.
  *   Jacobian    DflAssembleScalarJacobian adds to every tet's entries of the T Jacobian, coefficients frozen at the alpha states,
  *                 jm_ab(e) = sum_q W [ dc_q N_a(q) (f1 N_b(q) + f2 u_q . grad N_b) + f2 dk_q grad N_a . grad N_b ],
- *               f1 = kALPHAM, f2 = kDT kALPHAF kGAMMA: the tet's entry is base + jm (the base rounded first), summed over the
+ *               f1 = kALPHAM, f2 = dt kALPHAF kGAMMA: the tet's entry is base + jm (the base rounded first), summed over the
  *               row's tets in ascending tet id as without the section, in the same single launch, before the phase-change
  *               diagonal and the Dirichlet unit rows.  This is Picard in fl, as H is in the phase-change section; with
  *               k_liquid == k_solid it is the exact derivative.  The phi Jacobian is untouched.
@@ -1584,7 +1630,7 @@ void DflMeshThermalRows(Mesh3D* mesh, const f64* w, const f64* dw, f64* r, f64* 
  *               bitwise reproducible, the same under every assembly schedule.  Every F assembly adds r to R[0 .. 4N) after the
  *               thermal-material rows and before the Dirichlet rows.
  *   Jacobian    B_ab(rho[4], mu[4]) is the 4 x 4 block of the element Jacobian with the coefficients inside the quadrature
- *               sums (s_a = N_a(q), c_a = u_q . grad N_a, eK = grad N_a . grad N_b, f1 = kALPHAM, f2 = kDT kALPHAF kGAMMA,
+ *               sums (s_a = N_a(q), c_a = u_q . grad N_a, eK = grad N_a . grad N_b, f1 = kALPHAM, f2 = dt kALPHAF kGAMMA,
  *               w = W):
  *                 diag = w sum_q [ f1 rho_q s_a s_b + f1 rho_q^2 tau0_q c_a s_b + f2 rho_q s_a c_b + f2 rho_q^2 tau0_q c_a c_b
  *                                  + f2 mu_q eK ]
@@ -1740,7 +1786,7 @@ f64  DflMeshLevelSetVolume(Mesh3D* mesh, const f64* w, f64 level);
  *   time step   with every > 0, DflTimeStep corrects phi of wgold on every every-th call since the Set call, after the
  *               redistancing of that call, if any, and before the surface load and anything else is evaluated.  With a
  *               communicator it prints why and returns -1.  With track_capture, a step that took a pending two-way capture
- *               source (ParticleContextSetCapture) adds side kDT sum_a q_vol[a], the volume the captured particles brought,
+ *               source (ParticleContextSetCapture) adds side dt sum_a q_vol[a], the volume the captured particles brought,
  *               to the target after its Newton solve (summed on the device in a fixed two-stage order; reads 8 bytes back).
  *   statistics  of the last call: status, passes, band_tets, shift = delta (0 unless the status is 0 or 3), target,
  *               volume_before = V(level) as the call found it, volume_after = V(c*) (= volume_before unless shifted: the
@@ -1823,7 +1869,7 @@ void DflMeshVolumeCorrectionAddTarget(Mesh3D* mesh, f64 dV); /* dV of {phi > lev
  *               last update, minimum and maximum of |G|, cool and R over the records (a NaN is passed over), T_peak_max over
  *               the nodes with the metal flag (a NaN is passed over); in a fixed two-stage order.  An empty set gives count 0,
  *               minimum +inf, maximum -inf.
- *   time step   with in_time_step, DflTimeStep calls DflMeshSolidificationUpdate(mesh, wgold, kDT) once the step has
+ *   time step   with in_time_step, DflTimeStep calls DflMeshSolidificationUpdate(mesh, wgold, DflMeshTimeStep(mesh)) once the step has
  *               written wgold.  The first DflTimeStep after Set or Reset first primes the record at its incoming wgold, so
  *               that its own step is already booked.  With a communicator DflTimeStep prints why and returns -1.
  * Every sum has a fixed order and no float atomic is used: two runs agree bit for bit, under every assembly schedule.  An

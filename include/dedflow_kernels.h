@@ -1198,6 +1198,88 @@ void dfl_track_eval(dfl_index max_chunk, const dfl_index* off65, const dfl_index
                     const dfl_value* w, dfl_index N, const dfl_value* T_peak, const dfl_track_params* prm, dfl_value* part,
                     dfl_value* out, void* stream);
 
+/* ---- the time step as a run-time value (include/dedflow.h, "time step") ------------------------------------------------------
+ * dfl_step_consts is everything the kernels and the driver take from the step dt, formed by dfl_step_consts_from_dt alone, every
+ * entry in the operation order of the compile-time expression it replaces (products only: nothing a compiler could fuse).  The
+ * kernels get it by value as a kernel argument: it is wave-uniform and lives in SGPRs.  A product that the compiler used to
+ * fold into ONE literal is ONE entry here, so that the fused multiply-adds formed around it stay the ones formed around the
+ * literal, and the default step gives the bits of the compile-time build.
+ *
+ * Every launcher above that depends on the step keeps its name, arguments and behaviour (the default step) and forwards to the
+ * *_dt entry point of the same argument list with `const dfl_step_consts* k` before the stream.
+ *
+ * Step limits (csrc/k_steplimit.hip; the formulas are in include/dedflow.h, "time step"):
+ *    dfl_step_limit_partials  grid-stride over 256-tet workgroups, `grid` of them: the three maxima and their lowest tet ids
+ *                             and the two counts of every workgroup into part_v [grid][3], part_i [grid][5]
+ *    dfl_step_limit_finish    one workgroup: the same over the partials into out_v [3], out_i [5]
+ *    dfl_step_limits          both; max_workgroups 0: the default grid.  part_v / part_i hold dfl_step_limit_grid(T, max_workgroups)
+ *                             records.  out_i = tet_adv, tet_surface, tet_cap, num_cut, num_nonfinite.  No atomics: maxima are
+ *                             exact in any order and "the lowest id that attains it" is order-free */
+#ifndef DFL_DEFAULT_TIME_STEP
+#define DFL_DEFAULT_TIME_STEP (5e-2)
+#endif
+typedef struct dfl_step_consts {
+    dfl_value dt;
+    dfl_value t0;          /* 4.0 / (dt * dt) */
+    dfl_value fact2;       /* dt * kALPHAF * kGAMMA */
+    dfl_value fact2_rho;   /* fact2 * kRHO */
+    dfl_value fact2_rho2;  /* fact2 * kRHO * kRHO */
+    dfl_value fact2_mu4;   /* 4.0 * fact2 * kMU */
+    dfl_value fact2_kappa; /* fact2 * kKAPPA */
+    dfl_value states_old;  /* dt * kALPHAF * (1.0 - kGAMMA): with fact2 the alpha-level state */
+    dfl_value corr_old;    /* dt * (1.0 - kGAMMA): with corr_new the corrector */
+    dfl_value corr_new;    /* dt * kGAMMA */
+} dfl_step_consts;
+void dfl_step_consts_from_dt(double dt, dfl_step_consts* k);
+const dfl_step_consts* dfl_step_consts_default(void); /* those of DFL_DEFAULT_TIME_STEP */
+void dfl_assemble_tet_lhs_dt(dfl_index batch_size, const dfl_index* ien_b, const dfl_index* nzmap_b, const dfl_value* egeo_b,
+                             const dfl_value* nodep, dfl_value* val, const dfl_step_consts* k, void* stream);
+void dfl_assemble_tet_rhs_dt(dfl_index batch_size, const dfl_index* ien_b, const dfl_value* nodep, dfl_value* Fp,
+                             const dfl_step_consts* k, void* stream);
+void dfl_assemble_tet_lhs_slot_dt(dfl_index npatch, const int32_t* hdr, const uint32_t* ptet_lid, const dfl_index* pnode,
+                                  const dfl_index* slot_nz, const uint32_t* ldesc, const dfl_value* nodep, dfl_value* val,
+                                  dfl_value beta, dfl_index max_tets, const dfl_step_consts* k, void* stream);
+void dfl_assemble_tet_rhs_lane_dt(dfl_index npatch, const dfl_index* cnt, const dfl_index* pnode, const unsigned char* lien,
+                                  const unsigned short* sub4, const unsigned short* sub_start, const dfl_value* nodep,
+                                  dfl_value* partial, const dfl_step_consts* k, void* stream);
+void dfl_assemble_face_dt(dfl_index n_face, const dfl_index* face_list, const dfl_index* f2e, const dfl_index* forn,
+                          const dfl_index* ien, dfl_index N, const dfl_value* xg, const dfl_value* wg, const dfl_value* dwg,
+                          dfl_value* F, const dfl_index* rp, const dfl_index* ci, dfl_value* val, const dfl_step_consts* k,
+                          void* stream);
+void dfl_assemble_face_park_dt(dfl_index nf, const dfl_index* f2e, const dfl_index* forn, const dfl_index* ien, dfl_index N,
+                               const dfl_value* xg, const dfl_value* wg, const dfl_value* dwg, dfl_value* pF, dfl_value* pJ,
+                               const dfl_step_consts* k, void* stream);
+void dfl_assemble_scalar_jacobian_dt(dfl_index N, const dfl_index* vrow, const dfl_index* vcol, const dfl_index* ien,
+                                     const dfl_value* xg, const dfl_value* wgalpha, const dfl_index* row_ptr,
+                                     const dfl_index* col_ind, dfl_value* val_phi, dfl_value* val_T, const dfl_step_consts* k,
+                                     void* stream);
+void dfl_assemble_scalar_jacobian_material_dt(dfl_index N, const dfl_index* vrow, const dfl_index* vcol, const dfl_index* ien,
+                                              const dfl_value* xg, const dfl_value* wgalpha, const dfl_index* row_ptr,
+                                              const dfl_index* col_ind, const dfl_thermal_params* prm, dfl_value* val_phi,
+                                              dfl_value* val_T, const dfl_step_consts* k, void* stream);
+void dfl_fluid_rows_dt(dfl_index N, const dfl_index* vrow, const dfl_index* vcol, const dfl_index* ien, const dfl_value* xg,
+                       const dfl_value* w, const dfl_value* dw, const dfl_fluid_params* prm, dfl_value* r, dfl_value* Rn,
+                       dfl_value* Mn, const dfl_step_consts* k, void* stream);
+void dfl_fluid_add_rows_dt(dfl_index N, const dfl_index* vrow, const dfl_index* vcol, const dfl_index* ien, const dfl_value* xg,
+                           const dfl_value* wgalpha, const dfl_value* dwgalpha, const dfl_fluid_params* prm, dfl_value* F,
+                           const dfl_step_consts* k, void* stream);
+void dfl_fluid_add_jacobian_dt(dfl_index N, const dfl_index* vrow, const dfl_index* vcol, const dfl_index* ien,
+                               const dfl_value* xg, const dfl_value* wgalpha, const dfl_index* row_ptr, const dfl_index* col_ind,
+                               const dfl_fluid_params* prm, dfl_value* val, const dfl_step_consts* k, void* stream);
+
+typedef struct dfl_step_limit_params {
+    dfl_value level;
+    dfl_value sigma0, dsigma_dT, T_ref; /* all 0 without surface forces: sigma_e = 0 */
+} dfl_step_limit_params;
+dfl_index dfl_step_limit_grid(dfl_index T, dfl_index max_workgroups);
+void dfl_step_limit_partials(dfl_index T, const dfl_index* ien, const dfl_value* xg, const dfl_value* w, dfl_index N,
+                             const dfl_step_limit_params* prm, dfl_index grid, dfl_value* part_v, dfl_index* part_i, void* stream);
+void dfl_step_limit_finish(dfl_index grid, const dfl_value* part_v, const dfl_index* part_i, dfl_value* out_v, dfl_index* out_i,
+                           void* stream);
+void dfl_step_limits(dfl_index T, const dfl_index* ien, const dfl_value* xg, const dfl_value* w, dfl_index N,
+                     const dfl_step_limit_params* prm, dfl_index max_workgroups, dfl_value* part_v, dfl_index* part_i,
+                     dfl_value* out_v, dfl_index* out_i, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
