@@ -87,7 +87,7 @@ __device__ __forceinline__ unsigned mix32(unsigned h) {
 
 __device__ __forceinline__ int grid_coord(double x, double lo, double inv_h, int g) {
     const double c = floor((x - lo) * inv_h);
-    return c < 0.0 ? 0 : (c >= (double)g ? g - 1 : (int)c);
+    return c >= (double)g ? g - 1 : (c >= 1.0 ? (int)c : 0);  // a NaN compares false twice: cell 0, and is never converted
 }
 
 // one thread per particle (in the contact sweep's cell order when `order` is given): walk from the previous tet, or from
@@ -109,6 +109,7 @@ __global__ __launch_bounds__(BLK) void couple_locate_kernel(I P, const I* __rest
                   cz = grid_coord(p[2], lo2, inv_h2, gdim);
         t = seed[cx + gdim * (cy + gdim * cz)];
     }
+    const bool finite = isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]);
     double lam[4] = {0.0, 0.0, 0.0, 0.0};
     int result = t < 0 ? -1 : -2;  // (a seed grid without a tet: a mesh without tets)
     for (int step = 0; t >= 0 && step < DFL_COUPLE_MAX_WALK; ++step) {
@@ -120,9 +121,13 @@ __global__ __launch_bounds__(BLK) void couple_locate_kernel(I P, const I* __rest
             for (int d = 0; d < 3; ++d) x[3 * b + d] = xg[3 * v + d];
         }
         barycentric(x, p, lam);
-        const double lmin = fmin(fmin(lam[0], lam[1]), fmin(lam[2], lam[3]));
-        if (lmin >= -LAMBDA_EPS) {
+        // every lambda by comparison: fmin drops a NaN, and a tet must never accept a lambda that is one
+        if (lam[0] >= -LAMBDA_EPS && lam[1] >= -LAMBDA_EPS && lam[2] >= -LAMBDA_EPS && lam[3] >= -LAMBDA_EPS) {
             result = t;
+            break;
+        }
+        if (!finite) {  // no tet accepts an inf or a NaN (lambda_1..3 are none of them finite); outside, and no walk on them
+            result = -1;
             break;
         }
         int nb[4], cand[4], ncand = 0, best = -1;

@@ -809,7 +809,10 @@ void ParticleContextComputeForces(ParticleContext* ctx); /* acc <- contact force
  *   location   every particle is located on the tet mesh by a walk over the tet neighbour table, starting from its tet
  *              of the previous call (or from a uniform seed grid over the mesh's bounding box when it has none).  The
  *              result is the tet (-1: outside the mesh, -2: the walk hit its cap of DFL_COUPLE_MAX_WALK steps; such a
- *              particle is counted by ParticleContextLostCount) and the barycentric coordinates lambda[4] (min >= -1e-12).
+ *              particle is counted by ParticleContextLostCount) and the barycentric coordinates lambda[4] (min >= -1e-12:
+ *              a tet is accepted when each of its four lambdas compares >= -1e-12, so never with a NaN among them).
+ *              A particle with a coordinate that is not finite (+-inf, NaN) is outside: tet -1, lambda 0, not counted as
+ *              lost, whatever tet it came from.
  *              "Outside" means the walk stood in a tet whose only faces with lambda < -1e-12 are boundary faces: exact
  *              for CONVEX domains; in a non-convex domain a particle may be reported outside wrongly.
  *   drag       u_f = sum_a lambda_a u(node_a) (u = the first 3N entries of the 6N state), d = 2R,

@@ -635,7 +635,8 @@ void dfl_dem_spin(dfl_index P, dfl_value dt, dfl_value* omega, const dfl_value* 
  *    dfl_couple_neighbours    nbr[4t + k] = tet across the face opposite local vertex k, -1 on the boundary
  *    dfl_couple_locate        walk of every particle from tet[i] (or the seed-grid tet when tet[i] < 0); writes tet[i]
  *                             (-1 outside, -2 walk cap hit: *lost += 1) and lambda[i][4]; `order` (may be NULL) = the
- *                             thread -> particle map
+ *                             thread -> particle map.  A tet >= 0 has every lambda >= -1e-12 by comparison (no NaN); tet
+ *                             < 0 has lambda 0.  A coordinate that is not finite gives -1, lambda 0 and no lost count
  *    dfl_couple_fluid_step    drag + gravity + integration of every particle; imp[i][3] += drag impulse.  With
  *                             radius_i != NULL (per-particle sizes) d = 2 r_i, rho_p = m_i / (4/3 pi r_i^3) from mass_i /
  *                             radius_i, and the scalars mass and radius are not read

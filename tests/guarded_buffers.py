@@ -1,5 +1,6 @@
 """Guarded device buffers and the parity-record writer shared by the kernel-level GPU tests
-(test_gpu_krylov_kernels.py, test_gpu_matrix_kernels.py, test_gpu_assembly_kernels.py).  Test infrastructure only.
+(test_gpu_krylov_kernels.py, test_gpu_matrix_kernels.py, test_gpu_assembly_kernels.py, test_gpu_dem_kernels.py,
+test_gpu_levelset_kernels.py, test_gpu_scan.py, test_gpu_exchange_kernels.py).  Test infrastructure only.
 
 Every host array sits inside a larger device buffer between guard bands of GUARD sentinels of its own type: a NaN with a
 recognisable payload for float64 and float32, a fixed bit pattern for the integer types.  Slot.check compares the bands
