@@ -801,6 +801,27 @@ class DflTrackSection(C.Structure):
                 ("y_hi_fused", C.c_double), ("pairs", C.c_int64), ("dilution", C.c_double)]
 
 
+class DflPorosity(C.Structure):
+    _fields_ = [("level", C.c_double), ("side", C.c_int32), ("open_groups", C.c_int32), ("max_pores", C.c_int32),
+                ("every", C.c_int32)]
+
+
+class DflPore(C.Structure):
+    _fields_ = [("label", C.c_int32), ("nodes", C.c_int32), ("tets", C.c_int32), ("volume", C.c_double),
+                ("volume_scale", C.c_double), ("lo", C.c_double * 3), ("hi", C.c_double * 3), ("T_wall_min", C.c_double),
+                ("T_wall_max", C.c_double)]
+
+
+class DflPorosityStats(C.Structure):
+    _fields_ = [("components", C.c_int64), ("pores", C.c_int64), ("listed", C.c_int64), ("bad_nodes", C.c_int64),
+                ("bad_tets", C.c_int64), ("volume_metal", C.c_double), ("volume_open", C.c_double), ("volume_pores", C.c_double),
+                ("porosity", C.c_double)]
+
+
+class dfl_porosity_params(C.Structure):
+    _fields_ = [("level", C.c_double), ("side", C.c_double), ("max_pores", C.c_int32)]
+
+
 class DflTimeStepLimits(C.Structure):
     _fields_ = [("rate_adv", C.c_double), ("rate_adv_surface", C.c_double), ("cap_q", C.c_double), ("tet_adv", C.c_int32),
                 ("tet_surface", C.c_int32), ("tet_cap", C.c_int32), ("num_cut", C.c_int32), ("num_nonfinite", C.c_int32),
@@ -1035,6 +1056,21 @@ def _declare(L):
     f("DflMeshTrackSectionsResult", None, [C.POINTER(Mesh3D), C.POINTER(DflTrackSection)])
     f("DflTrackSectionsTestPairs", i32, [C.POINTER(Mesh3D), C.POINTER(vp), C.POINTER(i32)])
     f("DflTrackSectionsTestCapacity", None, [C.POINTER(Mesh3D), C.POINTER(i32), C.POINTER(i32)])
+    f("DflPorosityCheck", C.c_int, [C.POINTER(DflPorosity), C.c_char_p, C.c_size_t])
+    f("DflMeshSetPorosity", None, [C.POINTER(Mesh3D), C.POINTER(DflPorosity)])
+    f("DflMeshPorosityEnabled", i32, [C.POINTER(Mesh3D)])
+    f("DflMeshPorosity", i32, [C.POINTER(Mesh3D), vp])
+    f("DflMeshPorosityStats", None, [C.POINTER(Mesh3D), C.POINTER(DflPorosityStats)])
+    f("DflMeshPorosityResult", i32, [C.POINTER(Mesh3D), C.POINTER(DflPore), i32])
+    f("DflMeshPorosityLabels", i32, [C.POINTER(Mesh3D), C.POINTER(vp), C.POINTER(vp)])
+    f("DflPorosityTestLaunches", i32, [C.POINTER(Mesh3D)])
+    f("DflPorosityTestCapacity", i32, [C.POINTER(Mesh3D), i32])
+    pp = C.POINTER(dfl_porosity_params)
+    f("dfl_porosity_temp_bytes", C.c_int64, [i32])
+    f("dfl_porosity_label", C.c_int, [i32, i32, vp, vp, pp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp])
+    f("dfl_porosity_rank", C.c_int, [i32, vp, pp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])
+    f("dfl_porosity_tets", C.c_int, [i32, vp, vp, vp, i32, pp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp])
+    f("dfl_porosity_pores", C.c_int, [i32, vp, vp, vp, i32, pp, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, C.c_int64, vp, vp])
     f("DflTimeStepCheck", C.c_int, [f64, C.c_char_p, C.c_size_t])
     f("DflMeshSetTimeStep", None, [C.POINTER(Mesh3D), f64]); f("DflMeshTimeStep", f64, [C.POINTER(Mesh3D)])
     f("DflMeshTimeStepLimits", None, [C.POINTER(Mesh3D), vp, f64, C.POINTER(DflTimeStepLimits)])
@@ -1056,6 +1092,13 @@ def track_sections_config(stations, origin=(0.0, 0.0, 0.0), normal=(1.0, 0.0, 0.
     for k, c in enumerate(st[:64]):
         cfg.station[k] = c
     cfg.level, cfg.side, cfg.T_fuse, cfg.every = float(level), int(side), float(T_fuse), int(every)
+    return cfg
+
+
+def porosity_config(level=0.0, side=1, open_groups=0, max_pores=1024, every=0):
+    """a DflPorosity"""
+    cfg = DflPorosity()
+    cfg.level, cfg.side, cfg.open_groups, cfg.max_pores, cfg.every = float(level), int(side), int(open_groups), int(max_pores), int(every)
     return cfg
 
 
@@ -1603,6 +1646,46 @@ class Problem:
         lib().DflMeshTrackSectionsResult(self.mesh, out)
         return [{k: (int if k == "pairs" else float)(getattr(r, k)) for k, _ in DflTrackSection._fields_}
                 for r in out[:int(lib().DflMeshTrackSectionsStations(self.mesh))]]
+
+    # ---- porosity record (include/dedflow.h, "porosity record") ----------------------------------------------------------------
+    def set_porosity(self, level=None, side=1, open_groups=0, max_pores=1024, every=0):
+        """DflMeshSetPorosity: metal where side (phi - level) > 0; the gas components that hold a node of a boundary face of a
+        group in open_groups (bit g: group g) are open, every other one is a pore; at most max_pores rows are kept, lowest
+        labels first; every > 0: time_step evaluates on every every-th call.  level None turns the record off.  A configuration
+        the library refuses (reported on stderr) leaves the mesh as it was: porosity_on tells."""
+        if level is None:
+            lib().DflMeshSetPorosity(self.mesh, None)
+            return
+        lib().DflMeshSetPorosity(self.mesh, C.byref(porosity_config(level, side, open_groups, max_pores, every)))
+
+    @property
+    def porosity_on(self):
+        return bool(lib().DflMeshPorosityEnabled(self.mesh))
+
+    def _need_porosity(self):
+        if not self.porosity_on:
+            raise RuntimeError("no porosity record is set: call set_porosity first")
+
+    def porosity(self, w=None):
+        """DflMeshPorosity at the state w (DeviceArray of 6N, or a device pointer; None: the last evaluation).  Returns a dict
+        (synchronises): the totals of DflPorosityStats, `list` = one dict per listed pore (label, nodes, tets, volume,
+        volume_scale, lo, hi, T_wall_min, T_wall_max), `label` and `pore` = the two [N] int32 arrays of DflMeshPorosityLabels"""
+        self._need_porosity()
+        L = lib()
+        if w is not None:
+            L.DflMeshPorosity(self.mesh, getattr(w, "ptr", w))
+        s = DflPorosityStats()
+        L.DflMeshPorosityStats(self.mesh, C.byref(s))
+        out = {k: (float if k.startswith("volume") or k == "porosity" else int)(getattr(s, k)) for k, _ in DflPorosityStats._fields_}
+        rows = (DflPore * max(out["listed"], 1))()
+        n = int(L.DflMeshPorosityResult(self.mesh, rows, out["listed"]))
+        out["list"] = [dict(label=int(r.label), nodes=int(r.nodes), tets=int(r.tets), volume=float(r.volume),
+                            volume_scale=float(r.volume_scale), lo=tuple(r.lo), hi=tuple(r.hi), T_wall_min=float(r.T_wall_min),
+                            T_wall_max=float(r.T_wall_max)) for r in rows[:n]]
+        lab, por = vp(), vp()
+        N = int(L.DflMeshPorosityLabels(self.mesh, C.byref(lab), C.byref(por)))
+        out["label"], out["pore"] = d2h(lab.value, N, np.int32), d2h(por.value, N, np.int32)
+        return out
 
     def close(self):
         L = lib()

@@ -86,6 +86,7 @@ typedef struct MeshExt {
     struct VolumeState* volume;    /* level-set volume correction (host/volume.c, DflMeshSetVolumeCorrection), NULL: off */
     struct SolidifyState* solidify; /* solidification record (host/solidify.c, DflMeshSetSolidification), NULL: off */
     struct TrackState* track;      /* track cross-sections (host/track.c, DflMeshSetTrackSections), NULL: off */
+    struct PorosityState* porosity; /* porosity record (host/porosity.c, DflMeshSetPorosity), NULL: off */
     index_type *v2e_row, *v2e_col; /* device [N+1], [4T]: the sorted V2E map (DflMeshSortedV2E), NULL until first asked for */
     dfl_step_consts step;          /* the time step of this mesh and everything derived from it (host/timestep.c): DflMeshStepConsts */
     struct StepLimitState* steplimit; /* DflMeshTimeStepLimits: partials and results, sized at the first call (host/timestep.c) */
@@ -518,6 +519,17 @@ void DflTrackSectionsTimeStep(Mesh3D* mesh, const f64* wgold);
  * tests, probes) */
 index_type DflTrackSectionsTestPairs(const Mesh3D* mesh, const index_type** list, index_type* off65);
 void DflTrackSectionsTestCapacity(const Mesh3D* mesh, index_type* cap_list, index_type* cap_part);
+/* host/porosity.c: the porosity record of a mesh (no-ops while it is off) */
+struct PorosityState;
+void DflPorosityFree(struct PorosityState* st);
+b32 DflPorosityInTimeStep(const Mesh3D* mesh);                  /* a configuration with every > 0 is set */
+/* DflTimeStep, once the step has written wgold: counts the call; on every every-th since the Set call DflMeshPorosity(mesh, wgold) */
+void DflPorosityTimeStep(Mesh3D* mesh, const f64* wgold);
+/* launches of the last evaluation (a sort counts as one; 0 before the first): it depends on the mesh and the configuration,
+ * never on the state (tests, probes) */
+index_type DflPorosityTestLaunches(const Mesh3D* mesh);
+/* the capacity of the key lists (tests: they grow only when the closed tets exceed it); cap > 0 sets a smaller one first */
+index_type DflPorosityTestCapacity(Mesh3D* mesh, index_type cap);
 
 /* named ranges for rocprofv3 --marker-trace (DFL_ROCTX=1); no-ops otherwise */
 void DflRangePush(const char* name);

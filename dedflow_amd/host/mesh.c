@@ -106,6 +106,7 @@ void Mesh3DDestroy(Mesh3D* m) {
         DflVolumeCorrectionFree(x->volume);
         DflSolidificationFree(x->solidify);
         DflTrackSectionsFree(x->track);
+        DflPorosityFree(x->porosity);
         DflStepLimitFree(x->steplimit);
         CdamFreeDevice(x->v2e_row, 0); /* after the feature states that borrowed it */
         CdamFreeDevice(x->v2e_col, 0);

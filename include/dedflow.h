@@ -1995,6 +1995,81 @@ void DflMeshTrackSections(Mesh3D* mesh, const f64* w, const f64* T_peak);
  * and the empty-set values.  Without a configuration: a line on stderr, out untouched */
 void DflMeshTrackSectionsResult(Mesh3D* mesh, DflTrackSection* out);
 
+/* ---- porosity record: closed gas pores by connected components of phi (build-defined; opt-in) -----------------------------
+ * Gas trapped in the metal: a bubble in the pool, a void frozen under the bead, a gap between a particle-fed bead and the
+ * substrate.  Whether a gas pocket is closed is a question of connectivity, which no box, no single volume and no cutting plane
+ * answers.  This section labels the connected components of the gas region on the device and lists the closed ones.  It is
+ * passive: it reads the state and never writes it, so a mesh computes bit for bit the same flow with it on, and a mesh that
+ * never calls DflMeshSetPorosity with a configuration, or clears it with NULL, runs the launches it runs without this section.
+ * One GPU only.
+ *   sign        f_a = phi_a - level, negated for side = -1.  A node whose phi is not finite is bad: neither metal nor gas, and
+ *               counted.  Every other node is metal where f_a > 0 and gas otherwise (also where the difference of two finite
+ *               numbers overflowed to -inf).  A tet with a bad node joins nothing and adds no volume; such tets are counted.
+ *   graph       two gas nodes are joined when they share a tet that has no bad node.  For a piecewise-linear phi this is the
+ *               connectivity of the gas region itself: inside a tet the gas part is convex and contains the tet's gas nodes,
+ *               and across a face it contains that face's gas nodes.  A component is a connected set of gas nodes; its label is
+ *               the smallest node id in it, which no order of evaluation changes.  Every tet with at least one gas node and no
+ *               bad node belongs to exactly one component, that of its gas nodes.
+ *   open        a component is open when it holds a node of a boundary face of a group in open_groups (bit g: group g, as in
+ *               ParticleContextSetWallMesh and the laser's substrate_groups; the faces are those of bound_elem_offset /
+ *               bound_f2e / bound_forn).  Every other component is a pore.  With open_groups = 0 every component is closed
+ *               and the atmosphere itself is listed as a pore.
+ *   pore        pores are listed by ascending label; row k is the pore of rank k.  label; nodes = its gas nodes; tets = its
+ *               tets; volume = the sum over its tets in ascending tet id, from +0.0, of the tet's gas volume |det| / 6 - V+,
+ *               V+ the volume of {f > 0} in the tet exactly as the redistancing section decomposes it (a NaN adds 0);
+ *               volume_scale = the same sum of |det| / 6, the parity scale; lo, hi = the box of the pore's gas nodes and of
+ *               the crossing points P_ij = x_i + t (x_j - x_i), t = f_i / (f_i - f_j), on every edge from a gas node i to a
+ *               metal node j of its tets, formed as in the redistancing section without fused multiply-add; T_wall_min,
+ *               T_wall_max = the extremes of T over the metal nodes of its tets.  A NaN never wins a comparison; an empty
+ *               set gives +inf for a minimum and -inf for a maximum; a zero is +0.0.  "Frozen in" is T_wall_max < T_solidus:
+ *               the caller's decision, not the library's.
+ *   totals      components, pores, listed = min(pores, max_pores); bad_nodes, bad_tets; volume_metal = the sum of V+ over the
+ *               tets without a bad node, volume_open and volume_pores = the gas volumes of the tets of open and of closed
+ *               components (all pores, listed or not), each summed in a fixed tree over workgroups of 256 consecutive tets
+ *               (the xor tree inside every wave of 64, then waves 1, 2, 3 into wave 0), the workgroups then by one workgroup
+ *               (thread t takes workgroups t, t + 256, ...; then the same tree); porosity = volume_pores / (volume_metal +
+ *               volume_pores) where that sum is > 0, else 0, formed on the host.
+ *   time step   with every > 0, DflTimeStep evaluates on every every-th call since the Set call, at the wgold it has just
+ *               written, after the solidification record's update and the track cross-sections of that step.  With a
+ *               communicator it prints why and returns -1.
+ * No atomics on floats: every sum has a fixed order.  Counts and extremes use integer atomics, whose result no order changes:
+ * two evaluations of one state agree bit for bit, lists included.  The number of launches and the one wait of an evaluation do
+ * not depend on the state.  Limits: node and tet counts below 2^31. */
+typedef struct DflPorosity {
+    f64 level; index_type side;                 /* metal where side (phi - level) > 0 */
+    index_type open_groups;                     /* boundary groups that are the atmosphere, bit g: group g */
+    index_type max_pores;                       /* 1 .. 65536 rows kept, lowest labels first */
+    index_type every;                           /* > 0: DflTimeStep evaluates on every every-th call; 0: never */
+} DflPorosity;
+typedef struct DflPore {
+    index_type label, nodes, tets;
+    f64 volume, volume_scale, lo[3], hi[3], T_wall_min, T_wall_max;
+} DflPore;
+typedef struct DflPorosityStats {
+    int64_t components, pores, listed, bad_nodes, bad_tets;
+    f64 volume_metal, volume_open, volume_pores, porosity;
+} DflPorosityStats;
+/* host only: 0 when DflMeshSetPorosity accepts the configuration, else why not in `why`: a level that is not finite, side not
+ * +-1, a negative open_groups, max_pores outside 1 .. 65536, every < 0 */
+int  DflPorosityCheck(const DflPorosity* cfg, char* why, size_t why_len);
+/* the configuration is copied; NULL: off, frees everything of its own.  A refused configuration is reported on stderr and
+ * leaves the mesh as it was.  Builds every buffer whose size follows from the mesh, forgets the last evaluation and restarts
+ * the count of time steps (synchronises) */
+void DflMeshSetPorosity(Mesh3D* mesh, const DflPorosity* cfg);
+b32  DflMeshPorosityEnabled(const Mesh3D* mesh);
+/* w: the device 6N state.  Returns the number of pores; waits for the device once, for the pore and closed-tet counts; the key
+ * lists grow when the closed tets exceed their capacity and the call allocates nothing otherwise.  The geometry is read on
+ * every call: DflMeshGeometryChanged needs nothing here.  Without a configuration: a line on stderr, returns -1 */
+index_type DflMeshPorosity(Mesh3D* mesh, const f64* w);
+/* synchronises; the totals of the last evaluation (all zero before the first).  Without a configuration: a line on stderr */
+void DflMeshPorosityStats(Mesh3D* mesh, DflPorosityStats* out);
+/* copies min(listed, cap) rows of the last evaluation, returns listed (synchronises); -1 without a configuration */
+index_type DflMeshPorosityResult(Mesh3D* mesh, DflPore* out, index_type cap);
+/* two device [N] arrays that stay valid until the next evaluation or Set call: label[a] = the label of a's component, -1 for
+ * metal, -2 for bad; pore[a] = the rank of a's pore in the list, -1 for metal, bad or open (a rank at or above listed is a pore
+ * that the list did not keep).  Returns N, 0 without a configuration (both NULL then) */
+index_type DflMeshPorosityLabels(const Mesh3D* mesh, const index_type** label, const index_type** pore);
+
 #ifdef __cplusplus
 }
 #endif

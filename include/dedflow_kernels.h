@@ -1281,6 +1281,59 @@ void dfl_step_limits(dfl_index T, const dfl_index* ien, const dfl_value* xg, con
                      const dfl_step_limit_params* prm, dfl_index max_workgroups, dfl_value* part_v, dfl_index* part_i,
                      dfl_value* out_v, dfl_index* out_i, void* stream);
 
+/* ---- porosity record (build-defined, opt-in; host/porosity.c, csrc/k_porosity.hip, model in include/dedflow.h)
+ * prm: level, side (+-1.0) and the rows kept.  parent / label / open / rank / pore are [N]; rows [max_pores]; tot is one device
+ * record that a single copy brings back.  Every launcher returns the number of launches it made, which depends on its
+ * arguments' sizes and never on the state (a sort counts as one).  No float atomics; integer atomics carry counts and extremes.
+ *    dfl_porosity_label   rows and counters to their empty values; parent[a] = a (gas), -1 (metal), -2 (phi not finite, counted);
+ *                         the lock-free union-find over the tets without a bad node (agent-scope atomics on parent[] only);
+ *                         label[a] = the smallest node id of a's component; open[label] = 1 at the gas nodes of the nof faces
+ *                         oface (indices into f2e / forn)
+ *    dfl_porosity_rank    the pore roots (label[a] == a, not open) in ascending id get rank[a]; row rank gets its label;
+ *                         pore[a] = the rank of a's pore or -1; nodes and the node part of the box of every row; the
+ *                         components counted.  count [nblk], base [nblk + 1] with nblk = ceil(N / dfl_tets_per_block())
+ *    dfl_porosity_tets    per tet without a bad node the metal volume, and the gas volume to the open or the pore total, through
+ *                         part [nblk][3] into tot->volume; the bad tets counted; count / base as above over the tets: the tets of
+ *                         closed components.  Then pores = node_base[nblk_node] and the closed tets into tot->count
+ *    dfl_porosity_pores   the keys rank << 32 | tet of the nclosed closed tets in ascending tet id, sorted (the keys are distinct) into
+ *                         key_out (temp of dfl_porosity_temp_bytes(cap) bytes); per key the gas volume and |det| / 6 into vals
+ *                         [cap][2], the crossing points and the metal nodes' T into the row's extremes; the head of every run
+ *                         sums its run in order and owns volume, volume_scale and tets of its row.  Rows at or beyond max_pores
+ *                         are not kept */
+#define DFL_POROSITY_NCOUNT 8
+#define DFL_POROSITY_MAX_PORES 65536
+typedef struct dfl_porosity_params {
+    dfl_value level, side;
+    dfl_index max_pores;
+} dfl_porosity_params;
+/* ext: lo[3], hi[3], T_wall_min, T_wall_max as integers of the doubles' order: bits | 2^63 for a value whose sign bit is clear,
+ * ~bits otherwise */
+typedef struct dfl_pore_row {
+    dfl_index label, nodes, tets, pad;
+    dfl_value volume, volume_scale;
+    uint64_t ext[8];
+} dfl_pore_row;
+/* count: 0 components, 1 pores, 2 tets of closed components, 3 bad nodes, 4 bad tets; volume: metal, open, pores */
+typedef struct dfl_porosity_totals {
+    dfl_index count[DFL_POROSITY_NCOUNT];
+    dfl_value volume[3];
+} dfl_porosity_totals;
+int64_t dfl_porosity_temp_bytes(dfl_index n);
+int dfl_porosity_label(dfl_index N, dfl_index T, const dfl_index* ien, const dfl_value* w, const dfl_porosity_params* prm,
+                       dfl_index nof, const dfl_index* oface, const dfl_index* f2e, const dfl_index* forn, dfl_index* parent,
+                       dfl_index* label, dfl_index* open, dfl_pore_row* rows, dfl_porosity_totals* tot, void* stream);
+int dfl_porosity_rank(dfl_index N, const dfl_value* xg, const dfl_porosity_params* prm, const dfl_index* label,
+                      const dfl_index* open, dfl_index* count, dfl_index* base, dfl_index* chunk_sum, dfl_index* rank,
+                      dfl_index* pore, dfl_pore_row* rows, dfl_porosity_totals* tot, void* stream);
+int dfl_porosity_tets(dfl_index T, const dfl_index* ien, const dfl_value* xg, const dfl_value* w, dfl_index N,
+                      const dfl_porosity_params* prm, const dfl_index* label, const dfl_index* open, dfl_index nblk_node,
+                      const dfl_index* node_base, dfl_index* count, dfl_index* base, dfl_index* chunk_sum, dfl_value* part,
+                      dfl_porosity_totals* tot, void* stream);
+int dfl_porosity_pores(dfl_index T, const dfl_index* ien, const dfl_value* xg, const dfl_value* w, dfl_index N,
+                       const dfl_porosity_params* prm, const dfl_index* label, const dfl_index* open, const dfl_index* pore,
+                       const dfl_index* base, dfl_index nclosed, uint64_t* key, uint64_t* key_out, dfl_index cap, dfl_value* vals,
+                       void* temp, int64_t temp_bytes, dfl_pore_row* rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
