@@ -205,7 +205,7 @@ __global__ __launch_bounds__(BLK) void laser_column_kernel(I P, dfl_laser_beam b
         // the ranks of its column are meaningless.  The guard only keeps every write inside the arrays
         if (k < len && (unsigned)id < (unsigned)P) {
             const double p_in = pc * exp(-prefix);
-            const double got = p_in * (-expm1(-tau));
+            const double got = p_in * (0.0 - expm1(-tau));  // (0 - x, not -x: an unlit particle, tau = 0, gets +0.0 and not -0.0)
             const double mine = eta_p * got;
             rate[id] = mine;
             absorbed += mine;

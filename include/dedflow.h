@@ -1162,7 +1162,8 @@ void DflMeshSetHeatSource(Mesh3D* mesh, const f64* q);           /* device [N], 
  *              id.  With A_i = pi r_i^2, a = h^2: p_in = P_c exp(-sum_{j before i} A_j / a); particle i intercepts
  *              p_in (1 - exp(-A_i / a)), evaluated as -expm1(-A_i / a), and absorbs the fraction eta_p of it
  *              (laser_rate_i, W); the rest of what it intercepts is scattered and leaves the beam.  A particle deeper
- *              than its column's substrate hit (s > s_hit) is unlit and shadows nothing.
+ *              than its column's substrate hit (s > s_hit) is unlit and shadows nothing; a particle AT the hit depth is
+ *              lit.  The laser_rate of an unlit particle, outside the grid or behind the hit, is +0.0.
  *   substrate  on a coupled context with substrate_groups != 0: the candidate faces are the boundary faces of the coupled
  *              mesh in those groups (bit g = group g, the records of ParticleContextSetWallMesh) whose inward normal
  *              opposes the beam, n . dir < 0.  Each column's centre ray ((i - n/2 + 1/2) h, (j - n/2 + 1/2) h) is

@@ -816,10 +816,13 @@ void dfl_heat_fill(dfl_index first, dfl_index count, dfl_value t_init, dfl_value
  *                           then rate[i] = 0): n n + ((P - 1) >> DFL_LASER_OUTSIDE_SHIFT) + 1 bins; rank, count as the bin
  *                           pass of dfl_walls_build_cells
  *    dfl_laser_hit          colkey[n n] <- all ones, then per column the minimum over the candidate faces tri[0, nf) whose
- *                           projection holds the column centre of floor((depth - s_lo) scale) << 24 | face (nf <= 2^24,
- *                           (depth - s_lo) scale in [0, 2^40))
+ *                           projection holds the column centre (edges and vertices included) of
+ *                           floor((depth - s_lo) scale) << 24 | face, the depth field clamped to [0, 2^40 - 1] (nf <= 2^24).
+ *                           Two faces whose depths fall into one grid step tie: the lower face index wins, also where it is
+ *                           the deeper of the two; so do all depths below s_lo, and all at or beyond s_lo + 2^40 / scale
  *    dfl_laser_columns      per column the run cell_start[c] .. cell_start[c+1] of order / sorted / sorted_r (NULL: every
- *                           particle has `radius`) by (depth, id): rate[id], col_T[c] = transmitted power, col_face[c] = id
+ *                           particle has `radius`) by (depth, id): rate[id] (+0.0, never -0.0, for a particle deeper than
+ *                           the column's hit; one at the hit depth is lit), col_T[c] = transmitted power, col_face[c] = id
  *                           of the hit face's record (-1: none), part[6][n n] = column power, absorbed, scattered,
  *                           substrate, reflected, missed.  gw[2n] = the column weights gx, gy.  k_tau / k_id [P]: scratch
  *                           of runs longer than the cap.  P <= 0: no particles, cell_start is not read

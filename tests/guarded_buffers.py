@@ -1,6 +1,6 @@
 """Guarded device buffers and the parity-record writer shared by the kernel-level GPU tests
 (test_gpu_krylov_kernels.py, test_gpu_matrix_kernels.py, test_gpu_assembly_kernels.py, test_gpu_dem_kernels.py,
-test_gpu_levelset_kernels.py, test_gpu_scan.py, test_gpu_exchange_kernels.py).  Test infrastructure only.
+test_gpu_levelset_kernels.py, test_gpu_scan.py, test_gpu_exchange_kernels.py, test_gpu_laser_kernels.py).  Test infrastructure only.
 
 Every host array sits inside a larger device buffer between guard bands of GUARD sentinels of its own type: a NaN with a
 recognisable payload for float64 and float32, a fixed bit pattern for the integer types.  Slot.check compares the bands
@@ -11,11 +11,12 @@ import os
 
 import numpy as np
 
-F64, F32, I32, U8 = np.float64, np.float32, np.int32, np.uint8
+F64, F32, I32, U8, U32, U64 = np.float64, np.float32, np.int32, np.uint8, np.uint32, np.uint64
 GUARD = 64
 SENT = np.array([0x7FF8DEADBEEF0BAD], np.uint64).view(F64)[0]
 SENT32 = np.array([0x7FC0BEEF], np.uint32).view(F32)[0]
-_FILL = {np.dtype(F64): SENT, np.dtype(F32): SENT32, np.dtype(I32): 0x5A5A5A5A, np.dtype(U8): 0xA5}
+_FILL = {np.dtype(F64): SENT, np.dtype(F32): SENT32, np.dtype(I32): 0x5A5A5A5A, np.dtype(U8): 0xA5, np.dtype(U32): 0xA5A55A5A,
+         np.dtype(U64): 0xA5A55A5AC3C33C3C}
 _RAW = {8: np.uint64, 4: np.uint32, 1: np.uint8}
 
 

@@ -7,7 +7,7 @@ hash is the `commit` entry of each file) and hold the inputs as well as the raw 
 and the particles from the file, run the same calls through the tool's own `run` and compare every output byte for byte --
 DflMeshRedistance (phi, facets, statistics), DflMeshLevelSetVolume, DflMeshVolumeCorrect towards a drifted target (statistics,
 phi), DflMeshPhaseChangeStats, the laser-surface snapshot (facets, tets) and one laser step on it (surface power, heat source,
-particle rates, tally) and, on cube6, the accelerations of a DEM sweep whose cell scan has two chunks.  cube6 is
+particle rates -- with +0.0 where the parent wrote -0.0 for a particle behind the hit --, tally) and, on cube6, the accelerations of a DEM sweep whose cell scan has two chunks.  cube6 is
 kuhn_cube(6, jitter=0.2) (1296 tets: five full workgroups and one of 16 tets); fan is fan_mesh (76 tets, one workgroup)."""
 import importlib.util
 import os
@@ -65,6 +65,12 @@ def test_every_output_has_the_parents_bits(api, tool, golden):
     name, g = golden
     got = tool.run(api, g)
     want = {k: v for k, v in g.items() if k.startswith("out_")}
+    # the parent wrote -0.0 as the laser_rate of a particle behind its column's hit; the header now fixes +0.0 there
+    # (test_gpu_laser_kernels.py).  Every other bit, and every other zero, is the parent's
+    r = want["out_laser_surface_rate"]
+    behind = (r == 0.0) & np.signbit(r)
+    assert behind.any() and ((r == 0.0) & ~np.signbit(r)).any()
+    want["out_laser_surface_rate"] = np.where(behind, 0.0, r)
     assert sorted(got) == sorted(want)
     differ = [k for k in want if not tool.same_bits(got[k], want[k])]
     assert not differ, (name, differ)
