@@ -564,6 +564,53 @@ class Particles:
         lib().ParticleContextLaserSurfacePower(self.ctx, out.ptr)
         return out
 
+    # ---- laser reflections (build-defined; model in include/dedflow.h) ----------------------------------------------
+    def set_laser_reflection(self, max_bounce=4, model=1, eps=0.25):
+        """ParticleContextSetLaserReflection: column rays that hit a facet of phi = level are reflected up to max_bounce times
+        over all its facets, absorbing eta_s (model 0) or a Fresnel share with the material constant eps (model 1) at every
+        hit; max_bounce None turns it off.  Needs set_laser and set_laser_surface; the next laser_surface_update takes the
+        snapshot the rays run on.  A configuration the library refuses (reported on stderr) leaves the context as it was:
+        laser_reflection_on tells."""
+        if max_bounce is None:
+            lib().ParticleContextSetLaserReflection(self.ctx, None)
+            return
+        cfg = DflLaserReflection(int(max_bounce), int(model), float(eps))
+        lib().ParticleContextSetLaserReflection(self.ctx, C.byref(cfg))
+
+    @property
+    def laser_reflection_on(self):
+        return int(lib().ParticleContextLaserReflectionFacets(self.ctx, None, None, None)) >= 0
+
+    def laser_reflection_tally(self):
+        """dict absorbed [9] / escaped / remaining (W) / rays [9] of the last laser step; zeros when off"""
+        t = DflLaserReflectionTally()
+        lib().ParticleContextLaserReflectionTally(self.ctx, C.byref(t))
+        return dict(absorbed=np.array(t.absorbed[:], np.float64), escaped=float(t.escaped), remaining=float(t.remaining),
+                    rays=np.array(t.rays[:], np.int64))
+
+    def laser_reflection_rays(self):
+        """(facet [max_bounce + 1, n n] as indices into the reflection list, -1: none; absorbed [max_bounce + 1, n n] in W) of
+        the last laser step, copied back from the device; (None, None) before the first step with a reflection list"""
+        fp, ap = vp(), vp()
+        n = int(lib().ParticleContextLaserReflectionRays(self.ctx, C.byref(fp), C.byref(ap)))
+        if n <= 0:
+            return None, None
+        sync()
+        ncol = int(lib().ParticleContextLaserColumns(self.ctx, C.byref(vp()), C.byref(vp())))
+        return d2h(fp.value, n, np.int32).reshape(-1, ncol), d2h(ap.value, n, np.float64).reshape(-1, ncol)
+
+    def laser_reflection_facets(self):
+        """(facets [nr, 9], tet [nr], gradient [nr, 3]) of the reflection list of the last snapshot, copied back"""
+        fp, tp, gp = vp(), vp(), vp()
+        n = int(lib().ParticleContextLaserReflectionFacets(self.ctx, C.byref(fp), C.byref(tp), C.byref(gp)))
+        if n < 0:
+            raise RuntimeError("no laser reflection is set: call set_laser_reflection first")
+        if n == 0:
+            return np.zeros((0, 9)), np.zeros(0, np.int32), np.zeros((0, 3))
+        sync()
+        return (d2h(fp.value, 9 * n, np.float64).reshape(n, 9), d2h(tp.value, n, np.int32),
+                d2h(gp.value, 3 * n, np.float64).reshape(n, 3))
+
     # ---- melt-pool capture (build-defined; model in include/dedflow.h) ----------------------------------------------
     def set_capture(self, level=0.0, side=1, reach=0.0, T_melt=-np.inf, two_way=False):
         """ParticleContextSetCapture: capture() takes out the particles that reach the metal surface phi = level (side +1:
@@ -702,6 +749,14 @@ class DflLaserTally(C.Structure):
 
 class DflLaserSurface(C.Structure):
     _fields_ = [("level", C.c_double), ("side", C.c_int32)]
+
+
+class DflLaserReflection(C.Structure):
+    _fields_ = [("max_bounce", C.c_int32), ("model", C.c_int32), ("eps", C.c_double)]
+
+
+class DflLaserReflectionTally(C.Structure):
+    _fields_ = [("absorbed", C.c_double * 9), ("escaped", C.c_double), ("remaining", C.c_double), ("rays", C.c_int32 * 9)]
 
 
 class DflFluidCoupling(C.Structure):
@@ -983,6 +1038,13 @@ def _declare(L):
     f("ParticleContextLaserSurfaceUpdate", C.c_int32, [C.POINTER(ParticleContext), vp])
     f("ParticleContextLaserSurfaceFacets", C.c_int32, [C.POINTER(ParticleContext), C.POINTER(vp), C.POINTER(vp)])
     f("ParticleContextLaserSurfacePower", None, [C.POINTER(ParticleContext), vp])
+    f("DflLaserReflectionCheck", C.c_int, [C.POINTER(DflLaserReflection), C.c_char_p, C.c_size_t])
+    f("DflLaserReflectionGridStats", None, [C.POINTER(ParticleContext), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                            C.POINTER(C.c_double), C.POINTER(C.c_double)])
+    f("ParticleContextSetLaserReflection", None, [C.POINTER(ParticleContext), C.POINTER(DflLaserReflection)])
+    f("ParticleContextLaserReflectionTally", None, [C.POINTER(ParticleContext), C.POINTER(DflLaserReflectionTally)])
+    f("ParticleContextLaserReflectionRays", C.c_int32, [C.POINTER(ParticleContext), C.POINTER(vp), C.POINTER(vp)])
+    f("ParticleContextLaserReflectionFacets", C.c_int32, [C.POINTER(ParticleContext), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)])
     f("ParticleContextSetCapture", None, [C.POINTER(ParticleContext), C.POINTER(DflParticleCapture)])
     f("ParticleContextCapture", i32, [C.POINTER(ParticleContext), vp])
     f("ParticleContextCaptureSource", None, [C.POINTER(ParticleContext), f64, vp, vp, vp])

@@ -301,6 +301,7 @@ typedef struct LaserSurface {
     f64 vdmin, vdmax;                /* range of x . dir over the corners of the node bounding box */
     DflBlockScan scan;               /* the facet counts of the tet passes; its chunk_sum also serves the 4 cap node heads */
     index_type nf;                   /* candidate facets of the snapshot, -1: no Update yet */
+    index_type nn;                   /* facets whose tets the node list covers: nf, or the reflection list's nr */
     index_type nfb;                  /* boundary records in front of them in cand */
     index_type cap, cap_cand;        /* facets the lists hold; records cand holds */
     dfl_wall_tri* cand;              /* device [cap_cand]: the boundary candidates, then the facets */
@@ -316,9 +317,51 @@ typedef struct LaserSurface {
     f64* carry;                      /* device [N] or NULL: energy pending when a new snapshot replaced the node list */
     b32 carry_on;                    /* carry holds energy */
     b32 dirty;                       /* a step deposited into energy since it was last cleared */
+    struct LaserReflect* refl;       /* reflections on the surface (host/laser_reflect.c), NULL when off */
 } LaserSurface;
+/* the laser's reflections (host/laser_reflect.c): configuration, the reflection list R of the last Update and the per
+ * (bounce, column) output of the last step.  With it set the surface's node list covers the tets of R and fslot is indexed
+ * by R, and the step deposits through DflLaserReflectDeposit instead of DflLaserSurfaceDeposit */
+typedef struct LaserReflect {
+    DflLaserReflection cfg;
+    DflBlockScan scan;               /* R's counts of the tet passes */
+    index_type nr, cap;              /* facets of R (0: none), facets its lists hold */
+    f64 *facets, *grad, *ft;         /* device [cap][9], [cap][3], [cap][3] */
+    index_type *tet, *fij;           /* device [cap] */
+    index_type nhit;                 /* (max_bounce + 1) ncol */
+    index_type* hit_facet;           /* device [nhit] */
+    f64 *hit_abs, *hit_w, *ray_end;  /* device [nhit], [nhit][3], [2][ncol] */
+    uint64_t *rkey, *rkey_out;       /* device [4 nhit]: the deposit records */
+    f64* rval;                       /* device [4 nhit] */
+    void* temp;                      /* radix sort scratch of the records */
+    int64_t temp_bytes;
+    f64* tally;                      /* device [20] */
+    b32 stepped;                     /* hit_* hold a step's output */
+    /* the cell grid over the coupled mesh's node bounding box: R's facets entered into every cell their boxes overlap */
+    f64 lo[3], hi[3];                /* the node bounding box */
+    index_type cells_env, group;     /* DFL_LASER_REFLECT_CELLS (0: sized from nr), DFL_LASER_REFLECT_GROUP (lanes per ray) */
+    dfl_grid3 grid;
+    index_type ncell, cap_cell;      /* cells of the grid of the last Update (0: no grid), cells the arrays hold */
+    index_type *cell_count, *cell_start, *cell_chunk; /* device [cap_cell], [cap_cell + 1], [chunks] */
+    index_type nentry, cap_entry;
+    index_type* cell_entry;          /* device [cap_entry] */
+    f64* visited;                    /* device [ncol]: entries tested per column in the last step */
+} LaserReflect;
+/* for probes: facets in cells and cells of the last Update, mean and max entries tested per ray of the last step (synchronises) */
+void DflLaserReflectionGridStats(ParticleContext* ctx, index_type* entries, index_type* cells, f64* mean_visited, f64* max_visited);
+void DflLaserReflectFree(LaserSurface* s);           /* frees s->refl */
+void DflLaserReflectInstall(LaserState* l, const DflLaserReflection* cfg); /* a checked configuration on a state with a surface */
+void DflLaserReflectDropLists(LaserSurface* s);      /* no R, no step output; the capacity stays */
+void DflLaserReflectMeshChanged(LaserSurface* s);    /* after bind_mesh: no R, the scan sized for the new mesh */
+/* Update: enqueue R's count at the state w with the copy of its total to *nr (rides on Update's one synchronisation); then,
+ * with that total, grow R's lists when they must and emit R */
+void DflLaserReflectCount(LaserState* l, const f64* w, index_type* nr);
+void DflLaserReflectEmit(LaserState* l, const f64* w, index_type nr);
+void DflLaserReflectDeposit(LaserState* l, dfl_laser_beam b, f64 dt); /* the step's trace, records, sum and tally */
+void DflLaserReflectIdle(LaserState* l);             /* a step without facets: no ray, a zero tally */
 void DflLaserSurfaceInstall(ParticleContext* ctx, const DflLaserSurface* cfg); /* a checked configuration on a context with a laser */
 void DflLaserSurfaceFree(LaserState* l);             /* frees l->surf */
+void DflLaserSurfaceDropSnapshot(LaserState* l, index_type nf); /* pending energy to the dense array, no facets, no keys */
 void DflLaserSurfaceCouplingChanged(ParticleContext* ctx); /* drops the snapshot and pending energy, the new depth range */
 void DflLaserSurfaceDeposit(LaserState* l, dfl_laser_beam b, f64 dt); /* after the columns of a step with facets */
 void DflLaserSurfaceAddSource(LaserState* l, f64* q); /* q += surface energy / l->time; clears it */

@@ -211,8 +211,11 @@ void ParticleContextSetLaser(ParticleContext* ctx, const DflLaser* cfg) {
     }
     /* a laser surface set on the context keeps its configuration and loses its snapshot (host/laser_surface.c) */
     const b32 had_surface = x->laser && x->laser->surf;
+    const b32 had_reflection = had_surface && x->laser->surf->refl;
     DflLaserSurface surface;
+    DflLaserReflection reflection;
     if (had_surface) surface = x->laser->surf->cfg;
+    if (had_reflection) reflection = x->laser->surf->refl->cfg;
     DflLaserFree(ctx);
     LaserState* l = (LaserState*)CdamMallocHost(SIZE_OF(LaserState));
     memset(l, 0, sizeof *l);
@@ -236,6 +239,7 @@ void ParticleContextSetLaser(ParticleContext* ctx, const DflLaser* cfg) {
     bin_buffers(l, x->cap);
     build_substrate(ctx, l);
     if (had_surface) DflLaserSurfaceInstall(ctx, &surface);
+    if (had_reflection) DflLaserReflectInstall(l, &reflection);
 }
 
 void DflLaserCouplingChanged(ParticleContext* ctx) {
@@ -258,8 +262,11 @@ void DflLaserCopy(ParticleContext* dst, const ParticleContext* src) {
     ParticleContextSetLaser(dst, &ls->cfg);
     if (!laser(dst)) return;
     laser(dst)->t = ls->t;
-    if (ls->surf) DflLaserSurfaceInstall(dst, &ls->surf->cfg); /* the configuration, not the snapshot or pending energy */
-    else ParticleContextSetLaserSurface(dst, NULL);
+    if (ls->surf) {
+        DflLaserSurfaceInstall(dst, &ls->surf->cfg); /* the configuration, not the snapshot or pending energy */
+        if (ls->surf->refl) DflLaserReflectInstall(laser(dst), &ls->surf->refl->cfg);
+        else DflLaserReflectFree(laser(dst)->surf);
+    } else ParticleContextSetLaserSurface(dst, NULL);
 }
 
 void DflLaserStep(ParticleContext* ctx, f64 dt) {
@@ -303,6 +310,7 @@ void DflLaserStep(ParticleContext* ctx, f64 dt) {
                       l->col_face, l->part, s);
     if (l->ns > 0) dfl_laser_deposit(l->ns, l->soff, l->sface, tri, b, l->cfg.eta_s, dt, l->colkey, l->col_T, l->power, l->energy, s);
     if (nfs > 0) DflLaserSurfaceDeposit(l, b, dt);
+    else if (sf && sf->refl) DflLaserReflectIdle(l); /* no facets, no ray: the reflection tally of this step is zero */
     if (l->ns > 0 || nfs > 0) l->time += dt;
     dfl_laser_tally(l->ncol, l->cfg.power, l->part, l->tally, s);
     DflRangePop();

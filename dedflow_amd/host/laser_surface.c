@@ -43,6 +43,7 @@ static void free_mesh_buffers(LaserSurface* s) {
     s->cap_cand = 0;
     s->carry_on = s->dirty = FALSE;
     s->nf = -1;
+    s->nn = 0;
     s->nfb = 0;
     s->mesh = NULL;
     s->N = s->T = 0;
@@ -83,11 +84,15 @@ static void bind_mesh(ParticleContext* ctx, LaserState* l, LaserSurface* s) {
     HIPGUARD(hipMemsetAsync(l->colkey, 0xff, (size_t)l->ncol * sizeof(uint64_t), st));
     s->vdmin = s->vdmax = 0.0;
     Mesh3D* mesh = DflParticleCoupledMesh(ctx);
-    if (!mesh) return;
+    if (!mesh) {
+        DflLaserReflectMeshChanged(s);
+        return;
+    }
     const index_type N = Mesh3DNumNode(mesh), T = Mesh3DNumTet(mesh);
     s->mesh = mesh;
     s->N = N;
     s->T = T;
+    DflLaserReflectMeshChanged(s);
     DflBlockScanAlloc(&s->scan, T, 0);
     alloc_lists(s, LASER_SURFACE_FIRST_CAP, l->ncol);
     if (N > 0) {
@@ -108,6 +113,7 @@ void DflLaserSurfaceFree(LaserState* l) {
     LaserSurface* s = l->surf;
     if (!s) return;
     HIPGUARD(hipStreamSynchronize(DflStream()));
+    DflLaserReflectFree(s);
     free_mesh_buffers(s);
     CdamFreeDevice(s->rkey, 0); CdamFreeDevice(s->rkey_out, 0); CdamFreeDevice(s->rval, 0);
     CdamFreeHost(s, SIZE_OF(LaserSurface));
@@ -117,6 +123,9 @@ void DflLaserSurfaceFree(LaserState* l) {
 void DflLaserSurfaceInstall(ParticleContext* ctx, const DflLaserSurface* cfg) {
     LaserState* l = laser(ctx);
     const DflLaserSurface keep = *cfg; /* (cfg may live in the state that goes) */
+    const b32 had_reflection = l->surf && l->surf->refl; /* a reflection keeps its configuration, not its lists */
+    DflLaserReflection reflection;
+    if (had_reflection) reflection = l->surf->refl->cfg;
     DflLaserSurfaceFree(l);
     LaserSurface* s = (LaserSurface*)CdamMallocHost(SIZE_OF(LaserSurface));
     memset(s, 0, sizeof *s);
@@ -128,6 +137,7 @@ void DflLaserSurfaceInstall(ParticleContext* ctx, const DflLaserSurface* cfg) {
     s->rval = (f64*)CdamMallocDevice(r4 * SIZE_OF(f64));
     l->surf = s;
     bind_mesh(ctx, l, s);
+    if (had_reflection) DflLaserReflectInstall(l, &reflection);
 }
 
 void ParticleContextSetLaserSurface(ParticleContext* ctx, const DflLaserSurface* cfg) {
@@ -163,33 +173,44 @@ void DflLaserSurfaceCouplingChanged(ParticleContext* ctx) {
     if (l && l->surf) bind_mesh(ctx, l, l->surf);
 }
 
+/* the snapshot goes (nf as given: 0, or -1 for "no Update yet"): energy keyed by its node list moves to the dense array
+ * first, the reflection lists go with it, and no key names a facet that goes */
+void DflLaserSurfaceDropSnapshot(LaserState* l, index_type nf) {
+    LaserSurface* s = l->surf;
+    hipStream_t st = DflStream();
+    if (s->nf > 0 && s->dirty) {
+        if (!s->carry) {
+            s->carry = (f64*)CdamMallocDevice((ptrdiff_t)s->N * SIZE_OF(f64));
+            HIPGUARD(hipMemsetAsync(s->carry, 0, (size_t)s->N * sizeof(f64), st));
+        }
+        dfl_laser_surface_carry(4 * s->nn, s->nstart + 4 * (size_t)s->nn, s->unode, s->energy, s->carry, st);
+        s->carry_on = TRUE;
+    }
+    s->dirty = FALSE;
+    s->nf = nf;
+    s->nn = 0;
+    DflLaserReflectDropLists(s);
+    HIPGUARD(hipMemsetAsync(l->colkey, 0xff, (size_t)l->ncol * sizeof(uint64_t), st));
+}
+
 index_type ParticleContextLaserSurfaceUpdate(ParticleContext* ctx, const f64* w) {
     LaserState* l = laser(ctx);
     LaserSurface* s = l ? l->surf : NULL;
     if (!s) return -1;
     hipStream_t st = DflStream();
     DflRangePush("ParticleContextLaserSurfaceUpdate");
-    if (s->nf > 0 && s->dirty) { /* energy keyed by the node list that goes: to the dense array */
-        if (!s->carry) {
-            s->carry = (f64*)CdamMallocDevice((ptrdiff_t)s->N * SIZE_OF(f64));
-            HIPGUARD(hipMemsetAsync(s->carry, 0, (size_t)s->N * sizeof(f64), st));
-        }
-        dfl_laser_surface_carry(4 * s->nf, s->nstart + 4 * (size_t)s->nf, s->unode, s->energy, s->carry, st);
-        s->carry_on = TRUE;
-    }
-    s->dirty = FALSE;
-    s->nf = 0;
+    DflLaserSurfaceDropSnapshot(l, 0);
     s->nfb = l->nf;
-    HIPGUARD(hipMemsetAsync(l->colkey, 0xff, (size_t)l->ncol * sizeof(uint64_t), st)); /* no key names a facet that goes */
     if (!s->mesh || s->N <= 0 || s->T <= 0) {
         DflRangePop();
         return 0;
     }
     const Mesh3DData* dev = Mesh3DDevice(s->mesh);
     dfl_laser_surface_count(s->T, dev->ien, dev->xg, w, s->N, s->cfg.level, s->cfg.side, l->dir, s->scan.count, st);
-    index_type nf = 0;
+    index_type nf = 0, nr = 0;
     DflBlockScanEnqueue(&s->scan, &nf, st);
-    HIPGUARD(hipStreamSynchronize(st)); /* the one synchronisation: the count */
+    if (s->refl) DflLaserReflectCount(l, w, &nr);
+    HIPGUARD(hipStreamSynchronize(st)); /* the one synchronisation: the count (and that of the reflection list) */
     if (nf <= 0) {
         DflRangePop();
         return nf < 0 ? -1 : 0;
@@ -200,7 +221,15 @@ index_type ParticleContextLaserSurfaceUpdate(ParticleContext* ctx, const f64* w)
         DflRangePop();
         return nf;
     }
-    if (nf > s->cap) alloc_lists(s, DflGrowCap(nf), l->ncol);
+    if (s->refl && nr > LASER_MAX_RECORDS) {
+        fprintf(stderr, "ParticleContextLaserSurfaceUpdate: %d facets in the reflection list, at most %d; no ray is reflected\n", (int)nr,
+                LASER_MAX_RECORDS);
+        nr = 0;
+    }
+    /* with a reflection list the node list covers the tets of all its facets (the candidates are among them) */
+    const b32 with_r = s->refl && nr >= nf;
+    const index_type nn = with_r ? nr : nf;
+    if (nn > s->cap) alloc_lists(s, DflGrowCap(nn), l->ncol);
     if (l->nf + nf > s->cap_cand) {
         CdamFreeDevice(s->cand, 0);
         s->cap_cand = l->nf + (nf > s->cap ? nf : s->cap);
@@ -209,11 +238,13 @@ index_type ParticleContextLaserSurfaceUpdate(ParticleContext* ctx, const f64* w)
     if (l->nf > 0) HIPGUARD(hipMemcpyAsync(s->cand, l->tri, (size_t)l->nf * sizeof(dfl_wall_tri), hipMemcpyDeviceToDevice, st));
     dfl_laser_surface_emit(s->T, dev->ien, dev->xg, w, s->N, s->cfg.level, s->cfg.side, l->dir, s->scan.base, s->cand + l->nf, s->facets,
                            s->ftet, s->fij, s->ft, nf, st);
-    dfl_laser_surface_nodes(nf, dev->ien, s->ftet, s->nkey, s->nkey_out, s->nrec, s->nrec_out, s->nflag, s->scan.chunk_sum, s->nstart,
+    if (with_r) DflLaserReflectEmit(l, w, nr);
+    dfl_laser_surface_nodes(nn, dev->ien, with_r ? s->refl->tet : s->ftet, s->nkey, s->nkey_out, s->nrec, s->nrec_out, s->nflag, s->scan.chunk_sum, s->nstart,
                             s->fslot, s->unode, s->temp, s->temp_bytes, st);
-    HIPGUARD(hipMemsetAsync(s->power, 0, (size_t)4 * nf * sizeof(f64), st));
-    HIPGUARD(hipMemsetAsync(s->energy, 0, (size_t)4 * nf * sizeof(f64), st));
+    HIPGUARD(hipMemsetAsync(s->power, 0, (size_t)4 * nn * sizeof(f64), st));
+    HIPGUARD(hipMemsetAsync(s->energy, 0, (size_t)4 * nn * sizeof(f64), st));
     s->nf = nf;
+    s->nn = nn;
     DflRangePop();
     return nf;
 }
@@ -234,12 +265,18 @@ void ParticleContextLaserSurfacePower(ParticleContext* ctx, f64* q) {
         fprintf(stderr, "ParticleContextLaserSurfacePower: no laser surface is set on this context (ParticleContextSetLaserSurface)\n");
         return;
     }
-    const index_type nmax = s->nf > 0 ? 4 * s->nf : 0;
+    const index_type nmax = s->nf > 0 ? 4 * s->nn : 0;
     dfl_laser_surface_power(s->N, nmax, nmax ? s->nstart + nmax : NULL, s->unode, s->power, q, DflStream());
 }
 
 void DflLaserSurfaceDeposit(LaserState* l, dfl_laser_beam b, f64 dt) {
     LaserSurface* s = l->surf;
+    if (s->refl && s->refl->nr > 0) {
+        DflLaserReflectDeposit(l, b, dt);
+        s->dirty = TRUE;
+        return;
+    }
+    if (s->refl) DflLaserReflectIdle(l);
     dfl_laser_surface_deposit(b, l->colkey, s->nfb, s->nf, s->cand, s->fij, s->ft, s->fslot, l->cfg.eta_s, dt, l->col_T, s->rkey,
                               s->rkey_out, s->rval, s->power, s->energy, s->temp, s->temp_bytes, DflStream());
     s->dirty = TRUE;
@@ -250,7 +287,7 @@ void DflLaserSurfaceAddSource(LaserState* l, f64* q) {
     if (!s || !(l->time > 0.0)) return;
     hipStream_t st = DflStream();
     if (s->dirty && s->nf > 0)
-        dfl_laser_surface_source_add(4 * s->nf, s->nstart + 4 * (size_t)s->nf, s->unode, 1.0 / l->time, s->energy, q, st);
+        dfl_laser_surface_source_add(4 * s->nn, s->nstart + 4 * (size_t)s->nn, s->unode, 1.0 / l->time, s->energy, q, st);
     if (s->carry_on) dfl_laser_surface_carry_add(s->N, 1.0 / l->time, s->carry, q, st);
     s->dirty = s->carry_on = FALSE;
 }

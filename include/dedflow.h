@@ -1269,6 +1269,90 @@ index_type ParticleContextLaserSurfaceFacets(const ParticleContext* ctx, const f
  * deposited).  For callers and tests; no step calls it */
 void ParticleContextLaserSurfacePower(ParticleContext* ctx, f64* q);
 
+/* ---- laser reflections (build-defined; opt-in) ---------------------------------------------------------------------------
+ * "laser on the level-set surface" ends at the first hit: (1 - eta_s) T_c leaves the simulation, and eta_s does not depend on
+ * the angle of incidence.  With a reflection set on a context that has a laser and a laser surface, a column ray that hits a
+ * facet of the snapshot is reflected specularly and followed for up to max_bounce reflections over all facets of
+ * phi = level, and deposits at every hit a share given by the constant eta_s (model 0) or by a Fresnel approximation of the
+ * angle of incidence (model 1).  A context that never sets one, or clears it with NULL, computes bit for bit what it computes
+ * without this section, through the same launches.  One GPU only.  No fused multiply-add anywhere; every dot product is
+ * (a0 b0 + a1 b1) + a2 b2, every cross product (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0).
+ *   list R     with a reflection set, ParticleContextLaserSurfaceUpdate also builds the reflection list R: every facet of
+ *              phi = level that satisfies conditions (2) and (3) of the snapshot -- nine finite coordinates, |g| > 0 --
+ *              without the side (g . dir) > 0 filter: a reflected ray travels in any direction.  R is in ascending tet id, a
+ *              quad's first triangle first, and keeps per facet the tet, its gradient g and (i, j, t) of every vertex.  The
+ *              candidate list stays what it is, bit for bit; it is a subset of R; the primary hit is found by the unchanged
+ *              hit and column kernels.  The node list of the surface covers the nodes of every tet in R.  R's total rides on
+ *              Update's one synchronisation.  At most 2^24 facets: beyond that no ray is reflected (a line on stderr).
+ *              Setting or clearing a reflection drops the snapshot (pending energy is kept): the next Update takes a new one.
+ *   rays       only a column whose primary hit is a facet (record id -2 - tet) starts a ray; a column that hits a boundary
+ *              face, or nothing, behaves as without a reflection.  X_0 = (w_0 V_0 + w_1 V_1) + w_2 V_2 with w the weights
+ *              of the centre ray in the projected facet and V its vertices; d_0 = dir (normalised); g_0 the gradient of the
+ *              facet's tet; p_0 = T_c.  At bounce b (b = 0: the primary hit):
+ *                c = |d . g| / sqrt((g . g) (d . d));
+ *                model 0: A = eta_s;  model 1: A(c) = 1 - ((1 + (1 - eps c)^2) / (1 + (1 + eps c)^2)
+ *                                                          + (eps^2 - 2 eps c + 2 c^2) / (eps^2 + 2 eps c + 2 c^2)) / 2;
+ *                absorbed_b = A p_b;  p_{b+1} = p_b - absorbed_b.
+ *              Under model 1 A(c_0) replaces eta_s for primary hits on facets; boundary faces keep eta_s.
+ *              After bounce b = max_bounce the power left goes to `remaining`.  Otherwise the ray is reflected,
+ *              d' = d - (2 (d . g) / (g . g)) g (no square root on the ray's path), and its next hit leaving tet t0 is looked
+ *              for over all facets k of R with tet_k != t0 (this drops both triangles of a quad) and side (g_k . d') > 0
+ *              (the ray enters the metal there; a NaN is not greater), by Moeller-Trumbore in this order:
+ *                e1 = B - A, e2 = C - A, p = d x e2, det = e1 . p; skip the facet when det == 0;
+ *                s = X - A, u = (s . p) / det, q = s x e1, v = (d . q) / det, tau = (e2 . q) / det;
+ *                a hit iff u >= 0, v >= 0, u + v <= 1 and tau > 0.
+ *              The smallest tau wins, compared as doubles; on a tie the lowest index in R.  Then
+ *              X' = ((1 - u - v) A + u B) + v C, with 1 - u - v = (1 - u) - v, and g' = g_k.  No hit: the ray's power goes
+ *              to `escaped`.  This test is the definition; it is not watertight along shared edges.
+ *   deposit    at a hit with facet weights (w_0, w_1, w_2) -- primary: those of the centre ray; later: (1 - u - v, u, v) --
+ *              lambda_a is formed as in "laser on the level-set surface" from the facet's (i, j, t).  The record (bounce b,
+ *              column c, local node a) carries absorbed_b lambda_a; nodal power is the sum, from +0.0, of a node's records
+ *              in ascending (b n^2 + c) 4 + a: bounce-major, then column id.  With only bounce-0 records this is the order of
+ *              the surface alone.  No floating-point atomics; bitwise reproducible.  Energy accumulates and reaches
+ *              ParticleContextHeatSource exactly as for the surface.
+ *   tallies    DflLaserTally: `substrate` = boundary hits + the sum over b of absorbed[b] (per column in ascending b, then
+ *              the columns' tree), `reflected` = boundary reflections + escaped + remaining; the six entries still sum to P
+ *              up to rounding.  One exception in the last bit: under model 0 a ray that finds no second facet leaves its
+ *              column's entries as the column kernel booked them, eta_s T_c and (1 - eta_s) T_c, so that the six entries of a
+ *              surface without second hits have the bits of a step without reflections.  DflLaserReflectionTally is that of the last laser step.
+ *   limits     reflected rays see neither particles nor boundary faces; a ray that leaves the node bounding box has escaped;
+ *              specular reflection only, one ray per column.
+ *   search     the next hit is the minimum over all of R by definition.  Update enters the facets of R into a uniform grid
+ *              over the coupled mesh's node bounding box (every cell that the box of a facet's vertices overlaps; n cells per
+ *              axis, n = ceil(sqrt(|R| / 4)) <= 128, or DFL_LASER_REFLECT_CELLS = 1 .. 256 as read by Set), which costs one
+ *              more read of four bytes in Update.  A lane group per ray (a wave; DFL_LASER_REFLECT_GROUP = 16 or 64) walks
+ *              the layers of cells along the ray's dominant axis -- in each the rectangle that the ray's entry and exit
+ *              points span, padded by one cell, starting one layer behind the ray's origin -- and stops one layer behind
+ *              the best hit so far.  The grid changes no bit of the result for rays that decide with a margin (a facet hit
+ *              only through rounding, more than a cell away from the exact ray, could be missed).
+ *   travel     ParticleContextSetLaserSurface(ctx, NULL) also clears the reflection; a new surface configuration keeps it.
+ *              ParticleContextSetLaser keeps the reflection configuration and drops the snapshot; ParticleContextCopy
+ *              carries the configuration, not the lists; ParticleContextSetFluidCoupling drops the lists. */
+typedef struct DflLaserReflection {
+    index_type max_bounce;   /* 1 .. 8: reflections followed per column ray */
+    index_type model;        /* 0: eta_s at every facet hit; 1: Fresnel approximation with eps */
+    f64 eps;                 /* model 1: material constant, finite and > 0 (ignored by model 0) */
+} DflLaserReflection;
+typedef struct DflLaserReflectionTally {
+    f64 absorbed[9];         /* W absorbed at bounce b (b = 0: the primary hit on a facet), last laser step */
+    f64 escaped;             /* W on rays that found no facet */
+    f64 remaining;           /* W still on rays after bounce max_bounce */
+    index_type rays[9];      /* rays that hit a facet at bounce b */
+} DflLaserReflectionTally;
+/* host only; 0 = accepted, otherwise the reason in why (when not NULL): max_bounce outside 1..8, model not 0 or 1, eps not
+ * finite or not > 0 under model 1 */
+int DflLaserReflectionCheck(const DflLaserReflection* cfg, char* why, size_t why_len);
+/* the configuration is copied; NULL: off, frees the state.  Reported on stderr, context unchanged: the laser or the laser
+ * surface is off, or DflLaserReflectionCheck refuses */
+void ParticleContextSetLaserReflection(ParticleContext* ctx, const DflLaserReflection* cfg);
+void ParticleContextLaserReflectionTally(ParticleContext* ctx, DflLaserReflectionTally* out); /* synchronises; zeros when off */
+/* device, read-only, valid until the next laser step: for (b, c), index b n n + c, the facet hit at bounce b as an index
+ * into the reflection list (-1: none) and the power absorbed there; returns (max_bounce + 1) n n, 0 when off or before the
+ * first step with a reflection list */
+index_type ParticleContextLaserReflectionRays(const ParticleContext* ctx, const index_type** facet, const f64** absorbed);
+/* the reflection list of the last Update: facets [nr][9], their tets [nr], the tets' gradients [nr][3]; -1 when off */
+index_type ParticleContextLaserReflectionFacets(const ParticleContext* ctx, const f64** facets, const index_type** tet, const f64** grad);
+
 /* ---- melt-pool capture (build-defined; opt-in) ---------------------------------------------------------------------------
  * The reference's particle hooks are empty and its continuity equation has no source.  A context that never calls
  * ParticleContextSetCapture with a configuration, and a mesh that never gets a volume source, compute bit for bit what they

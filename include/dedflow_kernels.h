@@ -896,6 +896,59 @@ void dfl_laser_surface_carry(dfl_index nmax, const dfl_index* nu, const dfl_inde
                              void* stream);
 void dfl_laser_surface_carry_add(dfl_index N, dfl_value inv_time, dfl_value* carry, dfl_value* q, void* stream);
 
+/* ---- laser reflections (build-defined, opt-in; csrc/k_laser_reflect.hip, model in include/dedflow.h "laser reflections")
+ * Reflection list R: count -> dfl_scan_counts of the workgroup counts -> emit; its node slots are dfl_laser_surface_nodes on
+ * R's tets.  One laser step: trace -> deposit -> tally.  All on `stream`, no synchronisation.
+ *    dfl_laser_reflect_count    blk_count[b] = facets of R in the tets of workgroup b (dfl_tets_per_block() tets each)
+ *    dfl_laser_reflect_emit     facet f = blk_base[b] + (facets of the earlier tets of workgroup b), f < cap: facets [.][9],
+ *                               tet [.], grad [.][3] (the tet's gradient), ij [.], t [.][3] as dfl_laser_surface_emit
+ *    dfl_laser_reflect_trace    one wave per column c < n n.  colkey, nfb, nfs, cand as the surface deposit sees them, ftet
+ *                               [nfs] the candidates' tets; R = (nr, facets, rtet, rgrad).  Writes, for every b <=
+ *                               max_bounce (1 .. 8), hit_facet[b n n + c] (index into R, -1), hit_abs[.], hit_w[.][3];
+ *                               ray_end[c] = escaped, ray_end[n n + c] = remaining; and, for a column that starts a ray,
+ *                               part[3 n n + c] = its absorbed sum, part[4 n n + c] = escaped + remaining (part: the
+ *                               [6][n n] tally partials of dfl_laser_columns)
+ *    dfl_laser_reflect_deposit  power[0 .. 4 nr) <- 0; then per slot the sum, from +0.0 in ascending (b n n + c) 4 + a, of
+ *                               hit_abs lambda_a; energy[slot] += dt power[slot] for the slots with a record.  nrec =
+ *                               (max_bounce + 1) n n; key, key_out, val: [4 nrec]; temp: dfl_laser_reflect_temp_bytes(4 nrec)
+ *    dfl_laser_reflect_tally    out[0 .. 9) absorbed per bounce, out[9] escaped, out[10] remaining, out[11 .. 20) rays per
+ *                               bounce as doubles; one workgroup, a fixed tree */
+int64_t dfl_laser_reflect_temp_bytes(dfl_index n_records);
+void dfl_laser_reflect_count(dfl_index T, const dfl_index* ien, const dfl_value* xg, const dfl_value* w, dfl_index N, dfl_value level,
+                             dfl_index* blk_count, void* stream);
+void dfl_laser_reflect_emit(dfl_index T, const dfl_index* ien, const dfl_value* xg, const dfl_value* w, dfl_index N, dfl_value level,
+                            const dfl_index* blk_base, dfl_value* facets, dfl_index* tet, dfl_value* grad, dfl_index* ij, dfl_value* t,
+                            dfl_index cap, void* stream);
+void dfl_laser_reflect_trace(dfl_laser_beam b, const uint64_t* colkey, dfl_index nfb, dfl_index nfs, const dfl_wall_tri* cand,
+                             const dfl_index* ftet, dfl_index nr, const dfl_value* facets, const dfl_index* rtet, const dfl_value* rgrad,
+                             dfl_index side, dfl_index model, dfl_index max_bounce, dfl_value eta_s, dfl_value eps,
+                             const dfl_value* col_T, dfl_index* hit_facet, dfl_value* hit_abs, dfl_value* hit_w, dfl_value* ray_end,
+                             dfl_value* part, void* stream);
+/*    dfl_laser_reflect_cells_count / _emit   the uniform grid `grid` (dfl_grid3: lo, cells per unit length inv, n per axis) over R:
+ *                               count[cell] += 1, then entry[start[cell] + arrival] = facet, for every cell that the box of
+ *                               a facet's vertices overlaps (coordinates clamped into the grid).  count / cursor: [cells],
+ *                               zero on entry; start: the exclusive scan of count, [cells + 1]; entry: [cap], clipped
+ *    dfl_laser_reflect_trace_grid   dfl_laser_reflect_trace through the cells (cell_start NULL: over all of R); group = 16 or
+ *                               64 lanes per ray; visited (or NULL): [n n] entries tested per column, all bounces.  The
+ *                               result has the bits of dfl_laser_reflect_trace where the grid's box holds the hit points
+ *                               (Update's is the node bounding box, which holds every facet); a facet beyond the box sits in
+ *                               the boundary cells and is found only where the ray's rectangle in the last layer holds it */
+void dfl_laser_reflect_cells_count(dfl_index nr, const dfl_value* facets, dfl_grid3 grid, dfl_index* count, void* stream);
+void dfl_laser_reflect_cells_emit(dfl_index nr, const dfl_value* facets, dfl_grid3 grid, const dfl_index* start, dfl_index* cursor,
+                                  dfl_index* entry, dfl_index cap, void* stream);
+void dfl_laser_reflect_trace_grid(dfl_laser_beam b, const uint64_t* colkey, dfl_index nfb, dfl_index nfs, const dfl_wall_tri* cand,
+                                  const dfl_index* ftet, dfl_index nr, const dfl_value* facets, const dfl_index* rtet,
+                                  const dfl_value* rgrad, dfl_index side, dfl_index model, dfl_index max_bounce, dfl_value eta_s,
+                                  dfl_value eps, const dfl_value* col_T, dfl_index* hit_facet, dfl_value* hit_abs, dfl_value* hit_w,
+                                  dfl_value* ray_end, dfl_value* part, dfl_grid3 grid, const dfl_index* cell_start,
+                                  const dfl_index* cell_entry, dfl_index group, dfl_value* visited, void* stream);
+void dfl_laser_reflect_deposit(dfl_index nrec, const dfl_index* hit_facet, const dfl_value* hit_abs, const dfl_value* hit_w, dfl_index nr,
+                               const dfl_index* ij, const dfl_value* t, const dfl_index* fslot, dfl_value dt, uint64_t* key,
+                               uint64_t* key_out, dfl_value* val, dfl_value* power, dfl_value* energy, void* temp, int64_t temp_bytes,
+                               void* stream);
+void dfl_laser_reflect_tally(dfl_index ncol, dfl_index max_bounce, const dfl_index* hit_facet, const dfl_value* hit_abs,
+                             const dfl_value* ray_end, dfl_value* out, void* stream);
+
 /* ---- melt-pool capture (build-defined, opt-in; csrc/k_capture.hip, model in include/dedflow.h)
  *    dfl_capture_flag       one thread per particle: the decision of include/dedflow.h from tet / lambda (of a locate just
  *                           run), the node coordinates xg and the fluid state w [6N].  keep[i] = 0 when captured, else 1;
