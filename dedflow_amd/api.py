@@ -877,6 +877,19 @@ class dfl_porosity_params(C.Structure):
     _fields_ = [("level", C.c_double), ("side", C.c_double), ("max_pores", C.c_int32)]
 
 
+class DflSurfaceMesh(C.Structure):
+    _fields_ = [("level", C.c_double), ("side", C.c_int32), ("every", C.c_int32)]
+
+
+class DflSurfaceMeshStats(C.Structure):
+    _fields_ = [("vertices", C.c_int64), ("triangles", C.c_int64), ("bad_nodes", C.c_int64), ("bad_tets", C.c_int64),
+                ("degenerate_tets", C.c_int64), ("fields", C.c_int64), ("area", C.c_double)]
+
+
+class dfl_surface_mesh_params(C.Structure):
+    _fields_ = [("level", C.c_double), ("side", C.c_double)]
+
+
 class DflTimeStepLimits(C.Structure):
     _fields_ = [("rate_adv", C.c_double), ("rate_adv_surface", C.c_double), ("cap_q", C.c_double), ("tet_adv", C.c_int32),
                 ("tet_surface", C.c_int32), ("tet_cap", C.c_int32), ("num_cut", C.c_int32), ("num_nonfinite", C.c_int32),
@@ -1133,6 +1146,21 @@ def _declare(L):
     f("dfl_porosity_rank", C.c_int, [i32, vp, pp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])
     f("dfl_porosity_tets", C.c_int, [i32, vp, vp, vp, i32, pp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp])
     f("dfl_porosity_pores", C.c_int, [i32, vp, vp, vp, i32, pp, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, C.c_int64, vp, vp])
+    f("DflSurfaceMeshCheck", C.c_int, [C.POINTER(DflSurfaceMesh), C.c_char_p, C.c_size_t])
+    f("DflMeshSetSurfaceMesh", None, [C.POINTER(Mesh3D), C.POINTER(DflSurfaceMesh)])
+    f("DflMeshSurfaceMeshEnabled", i32, [C.POINTER(Mesh3D)])
+    f("DflMeshSurfaceMesh", i32, [C.POINTER(Mesh3D), vp, C.POINTER(vp), i32])
+    f("DflMeshSurfaceMeshStats", None, [C.POINTER(Mesh3D), C.POINTER(DflSurfaceMeshStats)])
+    f("DflMeshSurfaceMeshArrays", i32, [C.POINTER(Mesh3D)] + 6 * [C.POINTER(vp)] + [C.POINTER(i32)])
+    f("DflMeshSurfaceMeshCopy", None, [C.POINTER(Mesh3D), vp, vp, vp])
+    f("DflSurfaceMeshTestLaunches", i32, [C.POINTER(Mesh3D)])
+    f("DflSurfaceMeshTestGrows", i32, [C.POINTER(Mesh3D), C.POINTER(i32), C.POINTER(i32)])
+    f("dfl_surface_mesh_sort_block", i32, [])
+    sp = C.POINTER(dfl_surface_mesh_params)
+    f("dfl_surface_mesh_temp_bytes", C.c_int64, [i32, i32])
+    f("dfl_surface_mesh_count", C.c_int, [i32, i32, vp, vp, vp, sp, vp, vp, vp, vp, vp, vp])
+    f("dfl_surface_mesh_build", C.c_int, [i32, i32, vp, vp, vp, sp, vp, vp, i32, i32, vp, vp, i32, vp, C.c_int64, vp, vp, vp,
+                                         C.POINTER(vp), i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp])
     f("DflTimeStepCheck", C.c_int, [f64, C.c_char_p, C.c_size_t])
     f("DflMeshSetTimeStep", None, [C.POINTER(Mesh3D), f64]); f("DflMeshTimeStep", f64, [C.POINTER(Mesh3D)])
     f("DflMeshTimeStepLimits", None, [C.POINTER(Mesh3D), vp, f64, C.POINTER(DflTimeStepLimits)])
@@ -1161,6 +1189,13 @@ def porosity_config(level=0.0, side=1, open_groups=0, max_pores=1024, every=0):
     """a DflPorosity"""
     cfg = DflPorosity()
     cfg.level, cfg.side, cfg.open_groups, cfg.max_pores, cfg.every = float(level), int(side), int(open_groups), int(max_pores), int(every)
+    return cfg
+
+
+def surface_mesh_config(level=0.0, side=1, every=0):
+    """a DflSurfaceMesh"""
+    cfg = DflSurfaceMesh()
+    cfg.level, cfg.side, cfg.every = float(level), int(side), int(every)
     return cfg
 
 
@@ -1747,6 +1782,48 @@ class Problem:
         lab, por = vp(), vp()
         N = int(L.DflMeshPorosityLabels(self.mesh, C.byref(lab), C.byref(por)))
         out["label"], out["pore"] = d2h(lab.value, N, np.int32), d2h(por.value, N, np.int32)
+        return out
+
+    # ---- surface mesh (include/dedflow.h, "surface mesh") ------------------------------------------------------------------------
+    def set_surface_mesh(self, level=None, side=1, every=0):
+        """DflMeshSetSurfaceMesh: metal where side (phi - level) > 0; every > 0: time_step evaluates on every every-th call with
+        the field T.  level None turns the section off.  A configuration the library refuses (reported on stderr) leaves the
+        mesh as it was: surface_mesh_on tells."""
+        if level is None:
+            lib().DflMeshSetSurfaceMesh(self.mesh, None)
+            return
+        lib().DflMeshSetSurfaceMesh(self.mesh, C.byref(surface_mesh_config(level, side, every)))
+
+    @property
+    def surface_mesh_on(self):
+        return bool(lib().DflMeshSurfaceMeshEnabled(self.mesh))
+
+    def surface_mesh(self, w=None, fields=()):
+        """DflMeshSurfaceMesh at the state w (DeviceArray of 6N, or a device pointer; None: the last evaluation) with the nodal
+        fields (DeviceArrays of N, or device pointers; at most 8).  Returns a dict (synchronises): the totals of
+        DflSurfaceMeshStats, verts [nv, 3], edge [nv, 2], t [nv], vals [nv, K], tris [nt, 3], tri_tet [nt].  An evaluation
+        the library refuses (reported on stderr) returns None."""
+        if not self.surface_mesh_on:
+            raise RuntimeError("no surface mesh is set: call set_surface_mesh first")
+        L = lib()
+        if w is not None:
+            ptrs = (vp * max(len(fields), 1))(*[getattr(q, "ptr", q) for q in fields])
+            if L.DflMeshSurfaceMesh(self.mesh, getattr(w, "ptr", w), ptrs, len(fields)) < 0:
+                return None
+        s = DflSurfaceMeshStats()
+        L.DflMeshSurfaceMeshStats(self.mesh, C.byref(s))
+        out = {k: (float if k == "area" else int)(getattr(s, k)) for k, _ in DflSurfaceMeshStats._fields_}
+        p = [vp() for _ in range(6)]
+        nv = C.c_int32()
+        nt = int(L.DflMeshSurfaceMeshArrays(self.mesh, *[C.byref(q) for q in p], C.byref(nv)))
+        nv = int(nv.value)
+        assert (nv, nt) == (out["vertices"], out["triangles"])
+        verts, tris = np.empty((nv, 3)), np.empty((nt, 3), np.int32)
+        K = out["fields"]
+        vals = np.empty((nv, K))
+        L.DflMeshSurfaceMeshCopy(self.mesh, verts.ctypes.data, vals.ctypes.data if K else None, tris.ctypes.data)
+        out.update(verts=verts, vals=vals, tris=tris, edge=d2h(p[1].value, 2 * nv, np.int32).reshape(-1, 2),
+                   t=d2h(p[2].value, nv, np.float64), tri_tet=d2h(p[5].value, nt, np.int32))
         return out
 
     def close(self):

@@ -164,7 +164,9 @@ index_type SolveFlowSystem(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matr
  * With track cross-sections set on the mesh with every > 0 (DflMeshSetTrackSections), every every-th call evaluates them at
  * the new wgold, after that record, whose T_peak they read.
  * With a porosity record set on the mesh with every > 0 (DflMeshSetPorosity), every every-th call evaluates it at the new wgold,
- * after the track cross-sections. */
+ * after the track cross-sections.
+ * With a surface mesh set on the mesh with every > 0 (DflMeshSetSurfaceMesh), every every-th call evaluates it at the new wgold
+ * with the field T, after the porosity record. */
 index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* J, f64* F, f64* dx, Krylov* ksp, Dirichlet** bcs,
                        index_type nbc, index_type newton_maxit, ParticleContext* pctx, index_type dem_substeps, f64* rnorm_out,
                        f64* rnorm_init_out) {
@@ -216,6 +218,10 @@ index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* 
     }
     if (DflPorosityInTimeStep(mesh) && KrylovGetComm(ksp)) {
         fprintf(stderr, "DflTimeStep: the porosity record is single-GPU only; the solver has a communicator: step refused\n");
+        return -1;
+    }
+    if (DflMeshSurfaceMeshEnabled(mesh) && DflSurfaceMeshInTimeStep(mesh) && KrylovGetComm(ksp)) {
+        fprintf(stderr, "DflTimeStep: the surface mesh is single-GPU only; the solver has a communicator: step refused\n");
         return -1;
     }
     DflRangePush("DflTimeStep");
@@ -281,6 +287,7 @@ index_type DflTimeStep(Mesh3D* mesh, f64* wgold, f64* dwgold, f64* dwg, Matrix* 
     DflSolidificationTimeStep(mesh, wgold); /* the record of this step (in_time_step); reads wgold only */
     DflTrackSectionsTimeStep(mesh, wgold);  /* every every-th step: the cross-sections of the new wgold; reads it only */
     DflPorosityTimeStep(mesh, wgold);       /* every every-th step: the pores of the new wgold; reads it only; nothing when off */
+    if (DflMeshSurfaceMeshEnabled(mesh)) DflSurfaceMeshTimeStep(mesh, wgold); /* every every-th step: phi = level with T; reads only */
     if (coupled) DflLaserSurfaceTimeStep(pctx, wgold); /* the laser's snapshot of phi = level; a no-op unless a surface is set */
     if (coupled)
         for (index_type k = 0; k < dem_substeps; ++k) ParticleContextFluidStep(pctx, wgold); /* u at t_{n+1} */

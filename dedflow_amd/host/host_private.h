@@ -87,6 +87,7 @@ typedef struct MeshExt {
     struct SolidifyState* solidify; /* solidification record (host/solidify.c, DflMeshSetSolidification), NULL: off */
     struct TrackState* track;      /* track cross-sections (host/track.c, DflMeshSetTrackSections), NULL: off */
     struct PorosityState* porosity; /* porosity record (host/porosity.c, DflMeshSetPorosity), NULL: off */
+    struct SurfaceMeshState* surface_mesh; /* surface mesh (host/surface_mesh.c, DflMeshSetSurfaceMesh), NULL: off */
     index_type *v2e_row, *v2e_col; /* device [N+1], [4T]: the sorted V2E map (DflMeshSortedV2E), NULL until first asked for */
     dfl_step_consts step;          /* the time step of this mesh and everything derived from it (host/timestep.c): DflMeshStepConsts */
     struct StepLimitState* steplimit; /* DflMeshTimeStepLimits: partials and results, sized at the first call (host/timestep.c) */
@@ -573,6 +574,18 @@ void DflPorosityTimeStep(Mesh3D* mesh, const f64* wgold);
 index_type DflPorosityTestLaunches(const Mesh3D* mesh);
 /* the capacity of the key lists (tests: they grow only when the closed tets exceed it); cap > 0 sets a smaller one first */
 index_type DflPorosityTestCapacity(Mesh3D* mesh, index_type cap);
+
+/* host/surface_mesh.c: the surface mesh of a mesh (no-ops while it is off) */
+struct SurfaceMeshState;
+void DflSurfaceMeshFree(struct SurfaceMeshState* st);
+b32 DflSurfaceMeshInTimeStep(const Mesh3D* mesh);               /* a configuration with every > 0 is set */
+/* DflTimeStep, once the step has written wgold: counts the call; on every every-th since the Set call
+ * DflMeshSurfaceMesh(mesh, wgold, {T}, 1) */
+void DflSurfaceMeshTimeStep(Mesh3D* mesh, const f64* wgold);
+/* test hooks (exported, not in dedflow.h): the launches of the last evaluation; the evaluations that allocated so far, with the
+ * capacities of the key and triangle lists */
+index_type DflSurfaceMeshTestLaunches(const Mesh3D* mesh);
+index_type DflSurfaceMeshTestGrows(const Mesh3D* mesh, index_type* cap_key, index_type* cap_tri);
 
 /* named ranges for rocprofv3 --marker-trace (DFL_ROCTX=1); no-ops otherwise */
 void DflRangePush(const char* name);

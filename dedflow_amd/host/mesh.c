@@ -107,6 +107,7 @@ void Mesh3DDestroy(Mesh3D* m) {
         DflSolidificationFree(x->solidify);
         DflTrackSectionsFree(x->track);
         DflPorosityFree(x->porosity);
+        DflSurfaceMeshFree(x->surface_mesh);
         DflStepLimitFree(x->steplimit);
         CdamFreeDevice(x->v2e_row, 0); /* after the feature states that borrowed it */
         CdamFreeDevice(x->v2e_col, 0);

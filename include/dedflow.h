@@ -2155,6 +2155,85 @@ index_type DflMeshPorosityResult(Mesh3D* mesh, DflPore* out, index_type cap);
  * that the list did not keep).  Returns N, 0 without a configuration (both NULL then) */
 index_type DflMeshPorosityLabels(const Mesh3D* mesh, const index_type** label, const index_type** pore);
 
+/* ---- surface mesh: welded, oriented triangles of phi = level with vertex fields (build-defined; opt-in) --------------------
+ * The bead as a geometric object: the surface phi = level as one indexed triangle mesh with connectivity, a consistent
+ * orientation and nodal fields interpolated to its vertices, to view, to compare with a scan, to measure roughness on, to colour
+ * by temperature or cooling rate, or to hand on as the next layer's substrate (dedflow_amd/surface_io.py writes PLY and STL).
+ * It is passive: it reads the state and never writes it, and a mesh that never calls DflMeshSetSurfaceMesh with a
+ * configuration, or clears it with NULL, runs the launches it runs without this section.  One GPU only.
+ *   sign        f_a = phi_a - level, negated for side = -1.  A node whose phi is not finite is bad and counted in bad_nodes; a
+ *               tet with a bad node emits nothing and is counted in bad_tets.  Every other node is metal where f_a > 0 and gas
+ *               otherwise: the porosity record's convention.  A tet is cut when it has no bad node and one, two or three
+ *               metal nodes.  A cut tet whose determinant (tet_cross) is zero or not finite emits nothing and is counted in
+ *               degenerate_tets; every other cut tet emits.
+ *   vertices    one per cut mesh edge: an unordered node pair {i, j} of at least one emitting tet, i metal and j not.  The
+ *               vertex is P = x_i + t (x_j - x_i), t = f_i / (f_i - f_j), formed exactly as the redistancing section forms its
+ *               crossing points, metal node first and without fused multiply-add, so every tet around the edge would compute
+ *               the same bits and every coordinate is bit for bit a coordinate of that section's unwelded facets.  Vertex ids
+ *               are the ranks of the keys min(i, j) << 32 | max(i, j) in ascending order.  Welding is by edge, never by
+ *               coordinates: where phi == level exactly at a gas node, several vertices coincide with that node and stay
+ *               distinct.
+ *   triangles   emitting tets in ascending tet id; inside a tet the facets of the redistancing section in its order (one
+ *               metal node i: P_ij over the three others in local order; three: P_ij, i over the metal nodes in local order;
+ *               two, a < b, the others c < d: the quad P_ac, P_ad, P_bd, P_bc as (0, 1, 2) and (0, 2, 3)).  Each triangle is
+ *               an index triple into the vertex list; tri_tet[k] is the tet it came from.
+ *   orientation the normal (B - A) x (C - A) points out of the metal: in exact arithmetic ((B - A) x (C - A)) . g < 0 with
+ *               g = sum_a f_a grad N_a.  Where the facet as listed fails that, its second and third index are swapped.  The
+ *               decision is combinatorial, a table over the 14 masks of metal nodes times the sign of the tet's determinant,
+ *               and never looks at the rounded crossing points; a zero-area triangle gets the table's answer like any other.
+ *               Inside one mask and one sign the answer cannot change, because the triangle does not degenerate while the
+ *               signs of f are strict.
+ *   per vertex  edge[v] = (i, j), metal node first; t[v]; and for each of the K <= 8 nodal fields q the caller passes,
+ *               val[v][k] = q_i + t (q_j - q_i), without fused multiply-add.
+ *   totals      vertices, triangles, bad_nodes, bad_tets, degenerate_tets, and area = the sum over the triangles in list
+ *               order of 0.5 |(B - A) x (C - A)| of the oriented triple (differences, cross product, (n0 n0 + n1 n1) + n2 n2,
+ *               square root), summed in the fixed tree of the porosity totals over workgroups of 256 consecutive triangles;
+ *               +0.0 for no triangle.
+ *   properties  every triangle edge lies on a tet face or is a quad's diagonal.  An interior tet face that the surface cuts
+ *               holds exactly one segment, and both its tets emit it (unless one of them is bad or degenerate), so the mesh is
+ *               edge-manifold: every edge that is not on a boundary face of the tet mesh is used by exactly two triangles, in
+ *               opposite directions.  A metal region that does not touch the boundary gives a closed, consistently oriented
+ *               surface, and the volume (1 / 6) sum A . (B x C) it encloses is the volume of {f > 0} that
+ *               DflMeshLevelSetVolume sums tet by tet.
+ *   time step   with every > 0, DflTimeStep evaluates on every every-th call since the Set call, at the wgold it has just
+ *               written, after the porosity record, with the one field T.  With a communicator it prints why and returns -1.
+ * No atomics on floats; counts use integer atomics, whose result no order changes: two evaluations of one state agree bit for
+ * bit, lists included.  An evaluation is 5 launches, one wait for the counts and, where there is a triangle, 9 more launches.
+ * Limits: node, tet, triangle and key counts below 2^31. */
+typedef struct DflSurfaceMesh {
+    f64 level; index_type side;                 /* metal where side (phi - level) > 0 */
+    index_type every;                           /* > 0: DflTimeStep evaluates on every every-th call; 0: never */
+} DflSurfaceMesh;
+typedef struct DflSurfaceMeshStats {
+    int64_t vertices, triangles, bad_nodes, bad_tets, degenerate_tets;
+    int64_t fields;                             /* K of the last evaluation: the row length of vals */
+    f64 area;
+} DflSurfaceMeshStats;
+#define DFL_SURFACE_MESH_FIELDS 8
+/* host only: 0 when DflMeshSetSurfaceMesh accepts the configuration, else why not in `why`: a level that is not finite, side not
+ * +-1, every < 0 */
+int  DflSurfaceMeshCheck(const DflSurfaceMesh* cfg, char* why, size_t why_len);
+/* the configuration is copied; NULL: off, frees everything of its own.  A refused configuration is reported on stderr and
+ * leaves the mesh as it was.  Builds every buffer whose size follows from the mesh, forgets the last evaluation and restarts
+ * the count of time steps (synchronises) */
+void DflMeshSetSurfaceMesh(Mesh3D* mesh, const DflSurfaceMesh* cfg);
+b32  DflMeshSurfaceMeshEnabled(const Mesh3D* mesh);
+/* w: the device 6N state; fields: num_fields device [N] arrays (a host array of pointers; NULL with 0).  Returns the number of
+ * triangles.  Waits for the device once, for the triangle and key counts; the lists grow by x 1.5 when a count exceeds their
+ * capacity (the vertex lists are sized by the key count, which bounds the vertices; the field values by keys x num_fields)
+ * and the call allocates nothing otherwise.  The geometry is read on every call: DflMeshGeometryChanged needs nothing here.
+ * Without a configuration, or with num_fields outside 0 .. 8: a line on stderr, returns -1, the last evaluation stays */
+index_type DflMeshSurfaceMesh(Mesh3D* mesh, const f64* w, const f64* const* fields, index_type num_fields);
+/* synchronises; the totals of the last evaluation (all zero before the first).  Without a configuration: a line on stderr */
+void DflMeshSurfaceMeshStats(Mesh3D* mesh, DflSurfaceMeshStats* out);
+/* synchronises; device pointers that stay valid until the next evaluation or Set call: verts [nv][3], edge [nv][2], t [nv],
+ * vals [nv][K] (K of the last evaluation; NULL for 0), tris [nt][3], tri_tet [nt]; any of them may be NULL.  Returns nt and
+ * writes nv; 0 and NULL pointers without a configuration */
+index_type DflMeshSurfaceMeshArrays(Mesh3D* mesh, const f64** verts, const index_type** edge, const f64** t, const f64** vals,
+                                    const index_type** tris, const index_type** tri_tet, index_type* nv);
+/* copies the last evaluation to host buffers verts [nv][3], vals [nv][K], tris [nt][3]; any of them may be NULL; synchronises */
+void DflMeshSurfaceMeshCopy(Mesh3D* mesh, f64* verts, f64* vals, index_type* tris);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1390,6 +1390,45 @@ int dfl_porosity_pores(dfl_index T, const dfl_index* ien, const dfl_value* xg, c
                        const dfl_index* base, dfl_index nclosed, uint64_t* key, uint64_t* key_out, dfl_index cap, dfl_value* vals,
                        void* temp, int64_t temp_bytes, dfl_pore_row* rows, void* stream);
 
+/* ---- surface mesh (build-defined, opt-in; host/surface_mesh.c, csrc/k_surface_mesh.hip, model in include/dedflow.h)
+ * prm: level and side (+-1.0).  code is [T] bytes; count [2 nblk] and start [2 nblk + 1] with nblk = ceil(T /
+ * dfl_tets_per_block()), chunk_sum for a scan of 2 nblk entries; tot is one device record that a single copy brings back.  Every
+ * launcher returns the number of launches it made, which depends on its arguments' sizes and never on the state (a sort counts
+ * as one).  No float atomics; integer atomics carry counts only.
+ *    dfl_surface_mesh_count   zeroes tot; the bad nodes counted; code[e] = 0 for a tet that emits nothing (bad and degenerate
+ *                             tets counted), else the mask of its metal nodes | 16 for a negative determinant; the triangles
+ *                             and edge keys per workgroup scanned into start; tot->count[0] = triangles, [1] = edge keys
+ *    dfl_surface_mesh_build   nt and nkeys are those two counts (nothing is launched when either is 0).  tri_tet [capt] at every
+ *                             tet's triangle offset; the keys min << bits | max of the cut edges, bits = ceil(log2 N), sorted
+ *                             into key_out (temp of dfl_surface_mesh_temp_bytes(N, nkeys) bytes at least); the heads of the
+ *                             runs counted per workgroup (kcount [nkb], kbase [nkb + 1], nkb = ceil(nkeys / 256), kchunk for
+ *                             that scan); per head its rank's key (into key: the unique list), edge [.][2], t, verts [.][3] and
+ *                             vals [.][num_fields] (each list holds capk rows); per triangle the three ranks by binary search,
+ *                             oriented by the table, into tris [capt][3], and its area through part [ceil(nt / 256)] into
+ *                             tot->area; tot->count[2] = vertices.  fields: num_fields <= 8 device [N] arrays (a host array) */
+#define DFL_SURFACE_MESH_NCOUNT 8
+#define DFL_SURFACE_MESH_MAX_FIELDS 8
+typedef struct dfl_surface_mesh_params {
+    dfl_value level, side;
+} dfl_surface_mesh_params;
+/* count: 0 triangles, 1 edge keys (one per cut edge of every emitting tet), 2 vertices, 3 bad nodes, 4 bad tets, 5 degenerate tets */
+typedef struct dfl_surface_mesh_totals {
+    dfl_index count[DFL_SURFACE_MESH_NCOUNT];
+    dfl_value area;
+} dfl_surface_mesh_totals;
+/* the largest number of keys rocprim sorts inside one workgroup (the tests size a case beyond it) */
+dfl_index dfl_surface_mesh_sort_block(void);
+int64_t dfl_surface_mesh_temp_bytes(dfl_index N, dfl_index n);
+int dfl_surface_mesh_count(dfl_index N, dfl_index T, const dfl_index* ien, const dfl_value* xg, const dfl_value* w,
+                           const dfl_surface_mesh_params* prm, unsigned char* code, dfl_index* count, dfl_index* start,
+                           dfl_index* chunk_sum, dfl_surface_mesh_totals* tot, void* stream);
+int dfl_surface_mesh_build(dfl_index N, dfl_index T, const dfl_index* ien, const dfl_value* xg, const dfl_value* w,
+                           const dfl_surface_mesh_params* prm, const unsigned char* code, const dfl_index* start, dfl_index nt,
+                           dfl_index nkeys, uint64_t* key, uint64_t* key_out, dfl_index capk, void* temp, int64_t temp_bytes,
+                           dfl_index* kcount, dfl_index* kbase, dfl_index* kchunk, const dfl_value* const* fields,
+                           dfl_index num_fields, dfl_value* verts, dfl_index* edge, dfl_value* t, dfl_value* vals, dfl_index* tris,
+                           dfl_index* tri_tet, dfl_index capt, dfl_value* part, dfl_surface_mesh_totals* tot, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
